@@ -33,9 +33,12 @@ Other workloads of BASELINE.json (same metric, named in config.workload):
 
 Sites are independent: with N GPUs every rank owns S sites (weak scaling), no collective inside the loop.
 
-usage: python bench.py --gpus N --steps K --warmup W
+usage: python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   N > 1 without WORLD_SIZE in the environment: this process only launches `python -m torch.distributed.run --nproc-per-node N`
   on itself (it never touches the GPU) and relays the ranks' output; under torch.distributed.run WORLD_SIZE must equal N.
+  A plain run sets up, warms up, times the K steps and prints the line.  --full adds what takes runs of its own: the LDOS stage
+  behind the recursion ("ldos") and the CPU baseline ("cpu_baseline"); --no-green / --no-cpu leave either out again.
+  --dump-outputs DIR: the arrays the last timed step returned (a_b / b2_b, mu_n, or the Kubo moments), see dump_outputs().
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -54,6 +57,31 @@ FLOP_PER_BLOCK_MULT = 46656.0   # 18x18x18 complex MACs x 8 flop
 CPU_SAMPLE_SITES = 10
 BYTES_PER_ATOM_STEP = {"block": 51840.0, "chebyshev": 15552.0}   # 10 resp. 3 blocks of 5184 B per active atom per level, H_B = 0
 POST_FLOP_BLOCKS = {"block": 5.0, "chebyshev": 2.0}              # (nb + 5) resp. (nb + 2) x 46 656 flop per atom-step
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SEED = 20260
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write every array of ``arrays`` as <path>/<name>.npy in float64, complex ones with a trailing (re, im) axis.
+    Past DUMP_BUDGET_BYTES in all, each array keeps a share of the budget proportional to its size: a fixed, seeded sample of its
+    flattened entries (sorted indices; the same shapes give the same sample in every run), written as a 1-D array next to
+    <name>_sample_index.npy (those indices into the C-order array) and <name>_shape.npy (its shape)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    out = {}
+    for name, v in arrays.items():
+        v = np.asarray(v)
+        out[name] = np.stack([v.real, v.imag], axis=-1).astype(np.float64) if np.iscomplexobj(v) else v.astype(np.float64)
+    total = sum(v.nbytes for v in out.values())
+    for name, v in out.items():
+        if total > DUMP_BUDGET_BYTES:
+            keep = max(1, int(DUMP_BUDGET_BYTES * (v.nbytes / total)) // v.itemsize)
+            rng = np.random.default_rng(DUMP_SEED)
+            idx = np.sort(rng.choice(v.size, size=keep, replace=False)) if v.size <= 1 << 24 else np.unique(rng.integers(0, v.size, keep))
+            np.save(os.path.join(path, name + "_sample_index.npy"), idx.astype(np.float64))
+            np.save(os.path.join(path, name + "_shape.npy"), np.array(v.shape, np.float64))
+            v = np.ascontiguousarray(v).reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), v)
 
 
 def parse_args():
@@ -74,8 +102,11 @@ def parse_args():
     ap.add_argument("--batch", type=int, default=0)
     ap.add_argument("--no-positions", action="store_true", help="do not pass atom positions (locality hint)")
     ap.add_argument("--opt", action="append", default=[], help="library option key=value (development sweeps), may be repeated")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-green", action="store_true", help="skip the (untimed, separately reported) LDOS stage")
+    ap.add_argument("--full", action="store_true", help="also run the untimed extras: the LDOS stage and the CPU baseline (off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the last step returned as DIR/<name>.npy (float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-green", action="store_true", help="with --full: skip the (untimed, separately reported) LDOS stage")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--master-port", type=int, default=0)
     args = ap.parse_args()
@@ -281,7 +312,9 @@ def main_kubo(args):
                               "achieved": gemm_flop / gemm_s * 1e-12 if gemm_s > 0 else None, "frac": gemm_flop / gemm_s * 1e-12 / FP64_PEAK_TFLOPS if gemm_s > 0 else None,
                               "share_of_device_time": acc["rest_ms"] / max(acc["total_ms"], 1e-9)}},
     }
-    if not args.no_cpu:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"mu_nm_stochastic": mu})
+    if args.full and not args.no_cpu:
         from rslmtoasa_amd._proc import under_profiler
         if under_profiler():
             print("cpu_baseline skipped: running under a profiler", file=sys.stderr)
@@ -604,7 +637,14 @@ def main():
                          "hbm_view": {"achieved": bytes_total / world / elapsed * 1e-9, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": bytes_total / world / elapsed * 1e-9 / HBM_PEAK_GBS,
                                       "note": "whole recursion level per GPU, algorithmic %d B per atom-step" % BYTES_PER_ATOM_STEP[args.recur]}},
         }
-        if world == 1 and not args.no_green and args.recur == "block":
+        if args.dump_outputs:
+            # what recur_b / chebyshev_recur hand their caller for this rank's sites (+ the gathered image of all ranks at N > 1)
+            n = end - start + 1
+            arrays = {"a_b": rec.a_b[:, :, :, :n], "b2_b": rec.b2_b[:, :, :, :n]} if args.recur == "block" else {"mu_n": rec.mu_n[:, :, :, :n]}
+            if img is not None:
+                arrays["gathered_image"] = img.cpu().numpy()
+            dump_outputs(args.dump_outputs, arrays)
+        if args.full and world == 1 and not args.no_green and args.recur == "block":
             # Not part of `value`: the LDOS stage behind the recursion for the same sites, entirely on the device from the resident
             # coefficients (zsqr + get_terminf + bgreen + the -Im g0_jj/pi reduction of bands.f90:227-268), so that a true
             # "sites/s from Hamiltonian to LDOS" can be quoted.  2510 energies = the reference's default mesh.
@@ -614,7 +654,7 @@ def main():
                 out["ldos"] = ldos_stage(rec, gz, ene, args.sites, elapsed / args.steps)
             except Exception as e:  # noqa
                 print("LDOS stage skipped: %r" % (e,), file=sys.stderr)
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             threads = args.cpu_threads or min(os.cpu_count() or 1, 16)
             cb = cpu_baseline(W, args.lld, threads, args.recur, args.hoh)
             if cb:

@@ -62,6 +62,9 @@ CASES["Pt2MnGa_nsp4_local_axis"] = ("tests/scf/cases/bulk/Pt2MnGa", {"control": 
 CASES["Pt2MnGa_nsp4_local_axis_hoh"] = ("tests/scf/cases/bulk/Pt2MnGa", {"control": {"nsp": 4, "recur": "'block'", "lld": 10}, "hamiltonian": {"hoh": ".true.", "local_axis": ".true."}})
 MOM_PATCH = {"Pt2MnGa_nsp4_local_axis": {"Mn.nml": (0.6, 0.0, 0.8), "Ga.nml": (0.0, 0.0, 1.0), "Pt1.nml": (0.0, 0.8, 0.6), "Pt2.nml": (-0.36, 0.48, 0.8)}}
 MOM_PATCH["Pt2MnGa_nsp4_local_axis_hoh"] = MOM_PATCH["Pt2MnGa_nsp4_local_axis"]
+# the recursion of the manifest case Generated_bulk_bccFe_nsp4_local_axis (oracle/make_scf_fixtures.py): the moment tilted to (0.6, 0, 0.8)
+CASES["bccFe_nsp4_local_axis"] = ("tests/scf/cases/bulk/bccFe", {"control": {"nsp": 4, "recur": "'block'", "lld": 20}, "hamiltonian": {"hoh": ".false.", "local_axis": ".true."}})
+MOM_PATCH["bccFe_nsp4_local_axis"] = {"Fe.nml": (0.6, 0.0, 0.8)}
 OUTPUTS_ONLY = {"fccCu001_cheb50": "fccCu001_cheb"}      # name -> fixture that holds the (identical) inputs
 # Green-function-only variants: same recursion inputs as the base case (tests pair them with <base>.npz), other terminator options
 GREEN_ONLY = {

@@ -87,3 +87,26 @@ def test_hopping_blocks_are_real_in_a_common_basis(name):
     assert np.abs(back - p["ee"])[:, :, :nb].max() < 1e-12 * np.abs(p["ee"]).max()
     if np.abs(p["lsham"]).max() > 0:
         assert np.abs(q["lsham"].imag).max() > 1e-6 * np.abs(q["lsham"]).max()      # l.s is not real there
+
+
+def test_dump_outputs_budget_and_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float64 files, complex arrays with a trailing (re, im) axis; past the byte budget every array keeps its share as
+    the same seeded sample in every run."""
+    b = load_module(os.path.join(ROOT, "bench.py"), "bench_mod4")
+    x = (np.arange(600.0) + 1j * np.arange(600.0)[::-1]).reshape(10, 60)
+    y = np.arange(200, dtype=np.float32)
+    b.dump_outputs(str(tmp_path / "full"), {"x": x, "y": y})
+    fx, fy = np.load(tmp_path / "full" / "x.npy"), np.load(tmp_path / "full" / "y.npy")
+    assert fx.dtype == fy.dtype == np.float64 and fx.shape == (10, 60, 2) and np.array_equal(fx[..., 0], x.real) and np.array_equal(fx[..., 1], x.imag)
+    assert np.array_equal(fy, y)
+    monkeypatch.setattr(b, "DUMP_BUDGET_BYTES", 4000)
+    runs = []
+    for i in range(2):
+        b.dump_outputs(str(tmp_path / str(i)), {"x": x, "y": y})
+        runs.append([np.load(tmp_path / str(i) / n) for n in ("x.npy", "y.npy")])
+    sx, sy = runs[0]
+    assert sx.nbytes + sy.nbytes <= 4000 and sx.size > sy.size > 0
+    ix, shx = np.load(tmp_path / "0" / "x_sample_index.npy"), np.load(tmp_path / "0" / "x_shape.npy")
+    assert tuple(shx.astype(int)) == fx.shape and np.array_equal(sx, fx.ravel()[ix.astype(np.int64)])
+    assert np.array_equal(sy, fy[np.load(tmp_path / "0" / "y_sample_index.npy").astype(np.int64)])
+    assert all(np.array_equal(p, q) for p, q in zip(runs[0], runs[1]))

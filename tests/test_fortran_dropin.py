@@ -2,7 +2,8 @@
 (fortran/recursion_gpu.f90) swapped in, against the reference's committed expected values
 (tests/scf/references/*/ref.json and tests/regression/bccFe_lanczos/Fe.nml.ref, copied as data to tests/golden/scf/).
 
-Two builds of the boundary, both linked in the build container and travelling to the GPU box with oracle/_ref/:
+Two builds of the boundary, both linked by build() where the reference sources are readable (they contain its object code, so they
+live under the git-ignored oracle/_ref/ and travel with a built tree):
   * "dropin": oracle/_ref/rslmto_dropin.x (fortran/build_dropin.sh) -- the reference's OWN main program, linked from its unmodified
     main.f90 / calculation.f90 / self.f90 ... with the GPU types behind the reference's module names (fortran/shadow/): the zero-edit
     drop-in BASELINE.json's north_star asks for.  It runs every case of the manifest, the conductivity post-processing included
@@ -11,18 +12,25 @@ Two builds of the boundary, both linked in the build container and travelling to
     declares the GPU types explicitly (the edited-declarations integration; also the host of the flows the reference's program has no
     switch for: LDOS only, the library's own communicator).
 Comparison rule = the reference's own (tests/run_test.py:201-219): a value fails only if BOTH abs and rel differences exceed the
-tolerance."""
+tolerance.
+
+Every case first replays, without any reference code, the stage its workflow hands the library: the recursion problem the
+reference's run of the same case directory built (tests/golden/<fixture>.npz, oracle/make_fixtures.py) through the library, against
+that run's outputs at 1e-10.  A tree without the programs (a checkout that never saw the reference sources) runs that part only
+and says so in a warning; a tree with them runs both."""
 import json
 import os
 import re
 import shutil
-import subprocess
 
+import numpy as np
 import pytest
 
-from helpers import require_built
+from helpers import (RTOL, load_golden, objects_from, problem_dict, program_built, random_vec_coefficients, rel_err,
+                     rel_err_rows)
 from oracle.make_fixtures import patch_namelist
 from rslmtoasa_amd._proc import run_with_unlimited_stack
+from rslmtoasa_amd.recursion import Recursion
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCF = os.path.join(ROOT, "tests", "golden", "scf")
@@ -31,6 +39,134 @@ DROPIN = os.path.join(ROOT, "oracle", "_ref", "rslmto_dropin.x")
 MANIFEST = json.load(open(os.path.join(SCF, "manifest.json")))
 
 pytestmark = pytest.mark.gpu
+
+# manifest case -> the fixture of the reference's run of the same case directory (tests/golden/<name>.npz)
+FIXTURE = {
+    "Example_bulk_bccFe_nsp2_block": "bccFe_nsp2_block",
+    "Example_bulk_bccFe_nsp2_block_hoh": "bccFe_nsp2_block_hoh",
+    "Example_bulk_bccFe_nsp2_chebyshev": "bccFe_nsp2_cheb",
+    "Example_bulk_bccFe_nsp4_block": "bccFe_nsp4_block",
+    "Example_impurity_B2FeCo_block_hoh": "B2FeCo_block_hoh",
+    "Example_surface_fccCu001_block_hoh": "fccCu001_block_hoh",
+    "Generated_bulk_Pt2MnGa_nsp4_local_axis": "Pt2MnGa_nsp4_local_axis",
+    "Generated_bulk_bccFe_nsp4_local_axis": "bccFe_nsp4_local_axis",
+    "Generated_conductivity_fccPt_spin": "fccPt_kubo",
+    "Generated_conductivity_fccPt_spin_hoh": "fccPt_kubo_hoh",
+    "Generated_conductivity_fccPt_spin_random_vec": "fccPt_kubo_random",
+    "Regression_bccFe_lanczos": "bccFe_nsp1_lanczos",
+}
+GREEN = {"bccFe_nsp2_block", "bccFe_nsp4_block", "B2FeCo_block_hoh", "fccCu001_block_hoh"}     # tests/golden/<name>_green.npz
+
+
+def recursion(g, irec):
+    """The engine on the fixture's problem for the sites irec, set up as tests/test_gpu_parity.py sets up each kind of case."""
+    kw = {"nsp": g["nsp"]}
+    if "mu_n" in g:
+        kw.update(emin=g["emin"], emax=g["emax"])
+    elif "a_b" not in g:
+        kw.update(llsp=g["a"].shape[0])
+    return Recursion(*objects_from(problem_dict(g), irec, g["lld"], **kw), device=0)
+
+
+def run_sites(g, fixture, idx):
+    """The recursion stage of the case for the fixture's sites idx, in one call: the outputs as the caller receives them."""
+    rec = recursion(g, np.asarray(g["irec"])[idx])
+    n = len(idx)
+    try:
+        if "local_axis" in g:
+            rec.recur_b_local_axis(np.asarray(g["rot"])[:, :, idx])
+            return {"a_b": rec.a_b[:, :, :, :n].copy(), "b2_b": rec.b2_b[:, :, :, :n].copy()}
+        if "mu_n" in g:
+            rec.chebyshev_recur()
+            return {"mu_n": rec.mu_n[:, :, :, :n].copy()}
+        if "a_b" in g:
+            rec.recur_b()
+            out = {"a_b": rec.a_b[:, :, :, :n].copy(), "b2_b": rec.b2_b[:, :, :, :n].copy()}
+            if fixture in GREEN:
+                # the device LDOS stage on the coefficients left resident: get_terminf's a_inf / b_inf against the reference's
+                from rslmtoasa_amd.green import Green
+                from test_gpu_green import load_green
+                z = load_green(fixture)
+                r = Green(rec, z["ene"], sym_term=bool(z["sym_term"])).block_ldos()
+                out.update(a_inf=r["a_inf"], b_inf=r["b_inf"], dosial=r["dosial"])
+            return out
+        rec.recur()
+        return {"a": rec.a[:, :, :n, 0].copy(), "b2": rec.b2[:, :, :n, 0].copy()}
+    finally:
+        rec.close()
+
+
+def kubo(z, vectors):
+    """compute_moments_stochastic for the fixture's vectors ``vectors`` in one call (the fixture's Chebyshev window)."""
+    import rslmtoasa_amd.recursion as R
+    from test_gpu_kubo import make_rec
+    rec, _ = make_rec(z)
+    orig, R.chebyshev_scaling = R.chebyshev_scaling, lambda emin, emax: (float(z["acheb"]), float(z["bcheb"]))
+    try:
+        if "rng" in z:
+            seeds, coefs = random_vec_coefficients(z["rng"])
+            return rec.compute_moments_stochastic(z["v_a"], z["v_b"], int(z["cond_ll"]), seeds=seeds[vectors], coefs=coefs[vectors])
+        return rec.compute_moments_stochastic(z["v_a"], z["v_b"], int(z["cond_ll"]), vo_a=z.get("vo_a"), vo_b=z.get("vo_b"),
+                                              atlist=np.asarray(z["atlist"])[vectors])
+    finally:
+        R.chebyshev_scaling = orig
+        rec.close()
+
+
+def replay_case(name, build):
+    """The stage the case's workflow hands the library, on the stored fixture of the reference's run of the case, against that run's
+    outputs: "dropin" issues it as one call over every site (vector), "driver" as one call per site (vector)."""
+    fixture = FIXTURE[name]
+    g = load_golden(fixture)
+    if "mu_nm" in g:
+        nvec = g["mu_nm"].shape[-1]
+        groups = [np.arange(nvec)] if build == "dropin" else [np.array([v]) for v in range(nvec)]
+        mu = np.concatenate([kubo(g, v) for v in groups], axis=-1)
+        assert mu.shape == g["mu_nm"].shape
+        for v in range(nvec):          # per vector: max over all (n, m) blocks against that vector's largest moment (test_gpu_kubo.py)
+            assert np.abs(mu[..., v] - g["mu_nm"][..., v]).max() < RTOL * np.abs(g["mu_nm"][..., v]).max(), (v, name)
+        return
+    n = int(g["nrec"])
+    parts = [run_sites(g, fixture, np.arange(n))] if build == "dropin" else [run_sites(g, fixture, np.array([i])) for i in range(n)]
+    out = {k: np.concatenate([p[k] for p in parts], axis=0 if k == "dosial" else -1) for k in parts[0]}       # the site axis
+    for key in ("a_b", "b2_b", "mu_n"):
+        if key in out:
+            assert rel_err(out[key], g[key]) < RTOL, (name, key)
+    for key in ("a", "b2"):
+        if key in out:
+            assert rel_err_rows(out[key], g[key]) < RTOL, (name, key)
+    if "a_b" in out:
+        assert np.all(out["a_b"][:, :, -1] == 0) and all(np.array_equal(out["b2_b"][:, :, 0, i], np.eye(18)) for i in range(n))
+    if "a_inf" in out:
+        from test_gpu_green import load_green
+        z = load_green(fixture)
+        assert np.abs(out["a_inf"] - z["a_inf"]).max() <= 1e-9 * np.abs(z["a_inf"]).max()      # continuous in the coefficients
+        assert np.abs(out["b_inf"] - z["b_inf"]).max() <= 1e-9 * np.abs(z["b_inf"]).max()
+        assert np.isfinite(out["dosial"]).all() and out["dosial"].shape[0] == n
+
+
+def replay_ldos(name):
+    """dtot / dosia / dosial from rsrec_block_ldos on the resident coefficients of the stored fixture's problem, against the host
+    reduction (bands.f90:258-268) over a g0 downloaded from the same coefficients and over the reference run's g0."""
+    from rslmtoasa_amd.green import Green
+    from test_gpu_green import load_green
+    from test_gpu_ldos import ldos_from_g0
+    fixture = FIXTURE[name]
+    g, z = load_golden(fixture), load_green(fixture)
+    n = int(z["nrec"])
+    rec = recursion(g, g["irec"])
+    rec.recur_b()
+    gr = Green(rec, z["ene"], sym_term=bool(z["sym_term"]))
+    dev = gr.block_ldos()
+    rec.zsqr()
+    host = ldos_from_g0(gr.block_green(dev["a_inf"], dev["b_inf"], nsites=n))
+    ref = ldos_from_g0(z["g0"])
+    rec.close()
+    scale = np.abs(ref[2]).max()
+    for got, h, r, what, bar in zip((dev["dtot"], dev["dosia"], dev["dosial"]), host, ref, ("dtot", "dosia", "dosial"), (n, 1, 1)):
+        assert got.shape == h.shape == r.shape, what
+        assert np.abs(got - h).max() <= 1e-12 * np.abs(h).max(), what
+        assert np.abs(got - r).max() <= 1e-10 * bar * scale, what
 
 
 def read_nml_value(path, key, index=None):
@@ -56,8 +192,10 @@ def fortran_float(tok):
 @pytest.mark.parametrize("name", sorted(MANIFEST))
 def test_scf_workflow_with_gpu_recursion(name, build, tmp_path):
     case = MANIFEST[name]
+    replay_case(name, build)
     exe = DROPIN if build == "dropin" else os.path.join(os.path.dirname(EXE), case.get("exe", "rslmto_gpu.x"))    # kubo_gpu.x: the conductivity post-processing workflow
-    require_built(exe)
+    if not program_built(exe):
+        return
     work = tmp_path / "run"
     shutil.copytree(os.path.join(SCF, case["inputs"]), work)
     inp = work / "input.nml"
@@ -124,7 +262,9 @@ def test_density_of_states_without_g0(name, tmp_path):
     self.f90:821-833) with `bands_gpu` + `green_gpu%defer_g0`: dtot / dosia / dosial come from rsrec_block_ldos on the coefficients
     the recursion left on the device, and g0 (13 MB per site) is never produced.  Checked against the same flow with the reference's
     own host reduction over a downloaded g0: the three files the reference writes must agree to the printed digits."""
-    require_built(EXE)
+    replay_ldos(name)
+    if not program_built(EXE):
+        return
     case = MANIFEST[name]
     outs = {}
     # (the device run also brings up the library's own communicator through a file -- one rank: the box has one GPU)

@@ -22,7 +22,7 @@ def last_json(out):
 
 def test_bench_single_gpu_small():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--sites", "8", "--cells", "10", "--lld", "12",
-                        "--no-green"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--no-green", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = last_json(r.stdout)
     assert REQUIRED <= set(d) and "cpu_baseline" in d
@@ -66,3 +66,37 @@ def test_bench_step_fractions():
     assert abs(rf["frac_step_algorithmic"] - d["value"] * 1e-3 / d["n_gpus"] / rf["peak"]) < 1e-9 and rf["frac"] == rf["frac_kernel"]
     assert 0 < rf["frac_step"] <= rf["frac_step_algorithmic"] and rf["frac_step"] <= 1
     assert "Chebyshev" in d["config"]["workload"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run prints the headline line only (the LDOS stage and the CPU baseline sit behind --full), times exactly --steps steps,
+    and --dump-outputs writes the coefficients the last timed step returned: the CPU oracle's on the same sites."""
+    import importlib.util
+    import numpy as np
+    from helpers import RTOL, rel_err
+    from oracle import oracle
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--sites", "8", "--cells", "10", "--lld", "12",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = last_json(r.stdout)
+    assert REQUIRED <= set(d) and "cpu_baseline" not in d and "ldos" not in d
+    assert d["steps"] == 2 and d["ms_per_step"] > 0
+    # the launches counted inside the timed loop follow --steps: twice those of a one-step run
+    r1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--sites", "8", "--cells", "10", "--lld", "12"],
+                        capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r1.returncode == 0, r1.stderr[-2000:]
+    launches1 = last_json(r1.stdout)["roofline"]["launches"]
+    assert launches1 > 0 and d["roofline"]["launches"] == 2 * launches1, (d["roofline"]["launches"], launches1)
+    assert sorted(os.listdir(out)) == ["a_b.npy", "b2_b.npy"]
+    a, b2 = np.load(out / "a_b.npy"), np.load(out / "b2_b.npy")
+    assert a.dtype == b2.dtype == np.float64 and a.shape == b2.shape == (18, 18, 12, 8, 2)
+    spec = importlib.util.spec_from_file_location("bench_dump", os.path.join(ROOT, "bench.py"))
+    bm = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bm)
+
+    class Args:
+        sites, cells, lld, hoh, spin_mixing, no_positions, recur, workload, cells_given = 8, 10, 12, False, False, False, "block", "bcc", True
+    W = bm.build_workload(Args(), 1)
+    a_o, b_o = oracle.Oracle(dict(nn=W["nn"], iz=W["iz"], nmax=0, ee=W["ee"], lsham=W["lsham"], hoh=0, nsp=2)).block_lanczos(np.asarray(W["irec"], np.int32), 12)
+    assert rel_err(a[..., 0] + 1j * a[..., 1], a_o) < RTOL and rel_err(b2[..., 0] + 1j * b2[..., 1], b_o) < RTOL
