@@ -1,0 +1,189 @@
+!------------------------------------------------------------------------------
+! conductivity_gpu_mod -- GPU drop-in for type(conductivity) (conductivity.f90:47-72).
+!
+! The energy-resolved Kubo-Bastin integrand that calculate_gamma_nm (:158-225) + the loops of calculate_conductivity_tensor
+! (:259-281) form on the host through the complex (channels_ldos + 10, cond_ll, cond_ll) array gamma_nm (10 GB at cond_ll = 500) is
+! one call of librsrec, rsrec_kubo_integrand, on the per-process device context (rsrec_context_mod); the sum factorises and no
+! array of that size exists anywhere (rslmtoasa_amd/csrc/kernels_cond.hpp).  So:
+!   calculate_gamma_nm            : allocates nothing (the tables it would fill are built on the device per call)
+!   calculate_conductivity_tensor : the device integrand, then the reference's tail (:283-372) restated line for line: the sums over
+!                                   the orbitals, simpson_f of math_mod (kept as it is, read past the array end included), and the
+!                                   same files and formats (fort.123, cond_total*.out, <symbol>_cond*.out with 'per_type').
+! Errors of the library become g_logger%fatal, the reference's error behaviour on this path.
+!------------------------------------------------------------------------------
+module conductivity_gpu_mod
+   use, intrinsic :: iso_c_binding
+   use conductivity_mod
+   use self_mod, only: self
+   use precision_mod, only: rp
+   use string_mod, only: sl
+   use math_mod, only: pi, cross_product, simpson_f
+   use logger_mod, only: g_logger
+   use timer_mod, only: g_timer
+   use rsrec_binding
+   use rsrec_context_mod, only: rsrec_gpu_context
+   implicit none
+
+   private
+
+   type, public, extends(conductivity) :: conductivity_gpu
+   contains
+      procedure :: calculate_gamma_nm => gpu_calculate_gamma_nm
+      procedure :: calculate_conductivity_tensor => gpu_calculate_conductivity_tensor
+   end type conductivity_gpu
+
+   interface conductivity_gpu
+      procedure :: gpu_constructor
+   end interface conductivity_gpu
+
+contains
+
+   !> constructor (:87-100)
+   function gpu_constructor(self_obj) result(obj)
+      type(conductivity_gpu) :: obj
+      class(self), target, intent(in) :: self_obj
+
+      obj%self => self_obj
+      obj%control => self_obj%control
+      obj%lattice => self_obj%lattice
+      obj%en => self_obj%en
+      obj%recursion => self_obj%recursion
+
+      call obj%restore_to_default()
+      call obj%build_from_file()
+   end function gpu_constructor
+
+   !> calculate_gamma_nm (:158-225): nothing to do -- gamma_nm is never formed (calculate_conductivity_tensor below)
+   subroutine gpu_calculate_gamma_nm(this)
+      class(conductivity_gpu), intent(inout) :: this
+      if (allocated(this%gamma_nm)) deallocate (this%gamma_nm)
+   end subroutine gpu_calculate_gamma_nm
+
+   subroutine gpu_calculate_conductivity_tensor(this)
+      class(conductivity_gpu), intent(inout) :: this
+      integer :: i, l2, ntype, loop_over, nen
+      integer(c_int) :: rc
+      type(c_ptr) :: ctx
+      complex(rp), dimension(:, :, :), allocatable, target :: integ           ! (18, nen, loop_over): integrand_at(l2, l2, :, v), factor applied
+      real(rp), dimension(:, :), allocatable :: integrand_l_im, integrand_l_real
+      real(rp), dimension(:), allocatable :: integrand_tot_real, integrand_tot_im, wscale, real_part_l, im_part_l
+      real(rp), dimension(:), allocatable, target :: ene
+      real(rp) :: a, b, real_part, im_part, factor, volume, de
+      character(len=*), parameter :: fname_cond_total = "cond_total.out"
+      character(len=*), parameter :: fname_cond_orb_real = "cond_total_orb_real.out"
+      character(len=*), parameter :: fname_cond_orb_im = "cond_total_orb_im.out"
+      character(len=sl) :: fname_r, fname_orb_r, fname_orb_i
+
+      nen = this%en%channels_ldos + 10
+      ! :238-241, :249-252
+      a = (this%en%energy_max - this%en%energy_min)/(2 - 0.3)
+      b = (this%en%energy_max + this%en%energy_min)/2
+      de = this%en%energy_max - this%en%energy_min
+      allocate (wscale(nen), ene(nen), real_part_l(18), im_part_l(18), integrand_tot_real(nen), integrand_tot_im(nen))
+      allocate (integrand_l_real(18, nen), integrand_l_im(18, nen))
+      ene(:) = this%en%ene(1:nen)
+      wscale(:) = (this%en%ene(:) - b)/a
+
+      ! :254-259
+      select case (this%control%cond_calctype)
+      case ('per_type')
+         loop_over = this%lattice%ntype
+      case ('random_vec')
+         loop_over = this%control%random_vec_num
+      case default
+         call g_logger%fatal('conductivity_gpu: unknown cond_calctype '//trim(this%control%cond_calctype), __FILE__, __LINE__)
+      end select
+      if (.not. allocated(this%recursion%mu_nm_stochastic)) &
+         call g_logger%fatal('conductivity_gpu: recursion%mu_nm_stochastic is not allocated', __FILE__, __LINE__)
+      if (size(this%recursion%mu_nm_stochastic, 3) /= this%control%cond_ll .or. size(this%recursion%mu_nm_stochastic, 5) < loop_over) &
+         call g_logger%fatal('conductivity_gpu: mu_nm_stochastic does not match cond_ll / the vectors', __FILE__, __LINE__)
+
+      ! :261-267
+      volume = dot_product(this%lattice%a(:, 1), (cross_product(this%lattice%a(:, 2), this%lattice%a(:, 3))))
+      factor = 16/(pi*(de**2))
+      write (*, *) factor, volume, de
+
+      ! :268-281 (and calculate_gamma_nm :158-225): integrand_at(l2, l2, i, ntype) for every vector, on the device
+      call g_timer%start('conductivity-integrand-gpu')
+      allocate (integ(18, nen, loop_over))
+      ctx = rsrec_gpu_context()
+      rc = rsrec_kubo_integrand(ctx, int(loop_over, c_int), int(this%control%cond_ll, c_int), c_loc(this%recursion%mu_nm_stochastic), &
+                                int(nen, c_int), c_loc(ene), real(this%en%energy_min, c_double), real(this%en%energy_max, c_double), &
+                                c_loc(integ))
+      if (rc /= 0) call g_logger%fatal('conductivity_gpu%calculate_conductivity_tensor: '//rsrec_error_string(ctx), __FILE__, __LINE__)
+      call g_timer%stop('conductivity-integrand-gpu')
+
+      ! :283-291: integrand(l2, l2, :) is the sum of integrand_at over the vectors
+      integrand_tot_real(:) = 0.0d0
+      integrand_tot_im(:) = 0.0d0
+      do l2 = 1, 18
+         integrand_l_real(l2, :) = 0.0d0
+         integrand_l_im(l2, :) = 0.0d0
+         do ntype = 1, loop_over
+            integrand_l_real(l2, :) = integrand_l_real(l2, :) + real(integ(l2, :, ntype))
+            integrand_l_im(l2, :) = integrand_l_im(l2, :) + aimag(integ(l2, :, ntype))
+         end do
+         integrand_tot_real(:) = integrand_tot_real(:) + integrand_l_real(l2, :)
+         integrand_tot_im(:) = integrand_tot_im(:) + integrand_l_im(l2, :)
+      end do
+
+      ! :293-313
+      open (unit=3, file=fname_cond_total, status='replace', action='write')
+      open (unit=32, file=fname_cond_orb_real, status='replace', action='write')
+      open (unit=33, file=fname_cond_orb_im, status='replace', action='write')
+      do i = 1, nen
+         real_part = 0.0d0; im_part = 0.0d0; real_part_l(:) = 0.0d0; im_part_l(:) = 0.0d0
+         write (123, '(3es16.6)') (a*wscale(i) + b) - this%en%fermi, integrand_tot_real(i), integrand_tot_im(i)
+         call simpson_f(real_part, wscale, wscale(i), this%en%nv1, integrand_tot_real(:), .true., .false., 0.0d0)
+         call simpson_f(im_part, wscale, wscale(i), this%en%nv1, integrand_tot_im(:), .true., .false., 0.0d0)
+         write (3, '(3es16.6)') (a*wscale(i) + b) - this%en%fermi, real_part/real(loop_over), im_part/real(loop_over)
+         do l2 = 1, 18
+            call simpson_f(real_part_l(l2), wscale, wscale(i), this%en%nv1, integrand_l_real(l2, :), .true., .false., 0.0d0)
+            call simpson_f(im_part_l(l2), wscale, wscale(i), this%en%nv1, integrand_l_im(l2, :), .true., .false., 0.0d0)
+         end do
+         write (32, '(19es16.6)') (a*wscale(i) + b) - this%en%fermi, real_part_l(1:18)/real(loop_over)
+         write (33, '(19es16.6)') (a*wscale(i) + b) - this%en%fermi, im_part_l(1:18)/real(loop_over)
+      end do
+
+      ! :316-367
+      if (this%control%cond_calctype == 'per_type') then
+         do ntype = 1, loop_over
+            integrand_tot_real(:) = 0.0d0
+            integrand_tot_im(:) = 0.0d0
+            do l2 = 1, 18
+               integrand_l_real(l2, :) = real(integ(l2, :, ntype))
+               integrand_l_im(l2, :) = aimag(integ(l2, :, ntype))
+               integrand_tot_real(:) = integrand_tot_real(:) + integrand_l_real(l2, :)
+               integrand_tot_im(:) = integrand_tot_im(:) + integrand_l_im(l2, :)
+            end do
+
+            fname_r = trim(this%lattice%symbolic_atoms(ntype)%element%symbol)//"_cond.out"
+            fname_orb_r = trim(this%lattice%symbolic_atoms(ntype)%element%symbol)//"_cond_orb_real.out"
+            fname_orb_i = trim(this%lattice%symbolic_atoms(ntype)%element%symbol)//"_cond_orb_im.out"
+
+            open (unit=100 + ntype, file=fname_r, status='replace', action='write')
+            open (unit=300 + ntype, file=fname_orb_r, status='replace', action='write')
+            open (unit=400 + ntype, file=fname_orb_i, status='replace', action='write')
+
+            do i = 1, nen
+               real_part = 0.0d0; im_part = 0.0d0; real_part_l(:) = 0.0d0; im_part_l(:) = 0.0d0
+               call simpson_f(real_part, wscale, wscale(i), this%en%nv1, integrand_tot_real(:), .true., .false., 0.0d0)
+               call simpson_f(im_part, wscale, wscale(i), this%en%nv1, integrand_tot_im(:), .true., .false., 0.0d0)
+               write (100 + ntype, '(3es16.6)') (a*wscale(i) + b) - this%en%fermi, real_part, im_part
+               do l2 = 1, 18
+                  call simpson_f(real_part_l(l2), wscale, wscale(i), this%en%nv1, integrand_l_real(l2, :), .true., .false., 0.0d0)
+                  call simpson_f(im_part_l(l2), wscale, wscale(i), this%en%nv1, integrand_l_im(l2, :), .true., .false., 0.0d0)
+               end do
+               write (300 + ntype, '(19es16.6)') (a*wscale(i) + b) - this%en%fermi, real_part_l(1:18)
+               write (400 + ntype, '(19es16.6)') (a*wscale(i) + b) - this%en%fermi, im_part_l(1:18)
+            end do
+            close (100 + ntype)
+            close (300 + ntype)
+            close (400 + ntype)
+         end do
+      end if
+
+      deallocate (integ, integrand_tot_real, integrand_tot_im, wscale, ene, real_part_l, im_part_l, integrand_l_real, integrand_l_im)
+   end subroutine gpu_calculate_conductivity_tensor
+
+end module conductivity_gpu_mod

@@ -150,6 +150,17 @@ module rsrec_binding
          integer(c_int) :: rc
       end function
 
+      ! the Kubo-Bastin conductivity integrand integrand_at(l,l,:,v), factor applied, without gamma_nm (conductivity.f90:158-281)
+      function rsrec_kubo_integrand(handle, nvec, cond_ll, mu_nm, nen, ene, energy_min, energy_max, integrand) &
+         bind(C, name='rsrec_kubo_integrand') result(rc)
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: handle
+         integer(c_int), value :: nvec, cond_ll, nen
+         type(c_ptr), value :: mu_nm, ene, integrand
+         real(c_double), value :: energy_min, energy_max
+         integer(c_int) :: rc
+      end function
+
       function rsrec_kubo_moments(handle, nvec, nseed, seed_atoms, seed_coef, cond_ll, a, b, v_a, vo_a, v_b, vo_b, mu_nm) &
          bind(C, name='rsrec_kubo_moments') result(rc)
          import :: c_int, c_ptr, c_double

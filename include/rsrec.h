@@ -207,6 +207,20 @@ int rsrec_chebyshev_seeded(rsrec_t *h, int nchains, int nseed, const int32_t *se
 int rsrec_kubo_moments(rsrec_t *h, int nvec, int nseed, const int32_t *seed_atoms, const double *seed_coef, int cond_ll, double a, double b,
                        const double *v_a, const double *vo_a, const double *v_b, const double *vo_b, double *mu_nm);
 
+/* The Kubo-Bastin conductivity integrand of calculate_gamma_nm + calculate_conductivity_tensor (conductivity.f90:158-268), without the
+ * (nen, cond_ll, cond_ll) array gamma_nm (the sum factorises into two tables of nen x cond_ll, kernels_cond.hpp):
+ *   integrand(l, i, v) = factor sum_{n,m} gamma_nm(i, n, m) mu_nm(l, l, n, m, v),   factor = 16 / (pi (energy_max - energy_min)^2)
+ *   mu_nm     : complex (18,18,cond_ll,cond_ll,nvec) in = recursion%mu_nm_stochastic; host or device memory (a device array must be
+ *               complete when the call is made: it is read on the library's own stream)
+ *   ene       : real (nen) host = energy%ene (the reference passes channels_ldos + 10 points)
+ *   integrand : complex (18,nen,nvec) out, host or device = the reference's integrand_at(l,l,:,v); the caller sums over v to get its
+ *               integrand(l,l,:).  1 <= cond_ll <= RSREC_COND_LL_MAX.
+ * Two calls with the same inputs give the same bits (fixed summation order, no atomics).  rsrec_get_timing: out[0] device ms of the
+ * call, out[5] ms in the contraction kernels. */
+#define RSREC_COND_LL_MAX 4096
+int rsrec_kubo_integrand(rsrec_t *h, int nvec, int cond_ll, const double *mu_nm, int nen, const double *ene, double energy_min,
+                         double energy_max, double *integrand);
+
 /* One whole-vector product on caller arrays psi(18,18,kk) (complex, the reference's layout):
  *   vel = 0 : psi_out = (H psi_in - b psi_in)/a      ham_vec_matmul (:913) / ham_hoh_vec_matmul (:785); v_op, vo_op ignored
  *   vel = 1 : psi_out = V psi_in                      velo_vec_matmul (:587, 'n') / velo_hoh_vec_matmul (:656) with v_op (and vo_op with hoh)

@@ -36,6 +36,7 @@
 #include "kernels_green.hpp"
 #include "kernels_ldos.hpp"
 #include "kernels_kubo.hpp"
+#include "kernels_cond.hpp"
 #include "kernels_assemble.hpp"
 #include <dlfcn.h>
 
@@ -111,6 +112,8 @@ struct rsrec_handle {
     DevBuf d_green_in, d_green_out;   // rsrec_block_green
     DevBuf d_kubo[5];                 // rsrec_kubo_moments: work vectors, left / right matrices, slice partials, moments -- kept between calls (tens of GB:
                                       // their hipMalloc / hipFree cost 0.1-1.3 s per call on some boxes of the pool); given back when the recursion plans a batch
+    DevBuf d_cond[4];                 // rsrec_kubo_integrand: basis tables, S / D planes, column-tile partials, staging (mu diagonals, integrand);
+                                      // given back with d_kubo when the recursion plans a batch
     DevBuf d_bsqrt, d_term, d_gim, d_ldos;   // LDOS stage on resident coefficients: sqrt(B^2), terminators, Im g0_jj, output images
     void* pin = nullptr;              // pinned host staging buffer: every per-call transfer goes through it (see xfer_*)
     size_t pin_bytes = 0;
@@ -392,7 +395,7 @@ extern "C" int rsrec_destroy(rsrec_t* h) {
     (void)rsrec_comm_destroy(h);
     h->d_comm.release();
     for (auto e : h->ev_pool) (void)hipEventDestroy(e);
-    DevBuf* all[] = {&h->d_bsqrt, &h->d_term, &h->d_gim, &h->d_ldos, &h->d_green_in, &h->d_green_out, &h->d_kubo[0], &h->d_kubo[1], &h->d_kubo[2], &h->d_kubo[3], &h->d_kubo[4], &h->d_nbr, &h->d_nbr5, &h->d_s5queue, &h->d_iz, &h->d_hst, &h->d_hloc, &h->d_host, &h->d_holoc, &h->d_enim, &h->d_lsham, &h->d_vec[0], &h->d_vec[1],
+    DevBuf* all[] = {&h->d_bsqrt, &h->d_term, &h->d_gim, &h->d_ldos, &h->d_green_in, &h->d_green_out, &h->d_kubo[0], &h->d_kubo[1], &h->d_kubo[2], &h->d_kubo[3], &h->d_kubo[4], &h->d_cond[0], &h->d_cond[1], &h->d_cond[2], &h->d_cond[3], &h->d_nbr, &h->d_nbr5, &h->d_s5queue, &h->d_iz, &h->d_hst, &h->d_hloc, &h->d_host, &h->d_holoc, &h->d_enim, &h->d_lsham, &h->d_vec[0], &h->d_vec[1],
                      &h->d_vec[2], &h->d_vec[3], &h->d_vec[4], &h->d_vec[5], &h->d_order, &h->d_cum, &h->d_partial, &h->d_partial2, &h->d_coefA, &h->d_coefB, &h->d_bmats,
                      &h->d_status, &h->d_frags, &h->d_seed, &h->d_seedcoef, &h->d_mu, &h->d_scal, &h->d_zsqr};
     for (auto b : all) b->release();
@@ -705,13 +708,21 @@ DevProblem make_problem(const rsrec_t* h) {
     return P;
 }
 
+// Buffers a Kubo call keeps for the next one: d_kubo (rsrec_kubo_moments: work vectors and moment matrices, tens of GB) and d_cond
+// (rsrec_kubo_integrand: tables, S / D planes, partials; up to ~10 GB at RSREC_COND_LL_MAX).  Every entry point that reserves large
+// buffers of its own gives them back before it does, so that it plans on memory that is really free.
+void release_kubo_buffers(rsrec_t* h, bool moments, bool integrand) {
+    if (moments) for (auto& kb : h->d_kubo) kb.release();
+    if (integrand) for (auto& cb : h->d_cond) cb.release();
+}
+
 struct BatchPlan {
     int batch = 1, nblk = 1;
 };
 
 // how many chains are advanced together, and how many workgroups each gets
 int plan_batch(rsrec_t* h, int nchains, int nvec, size_t vec_elems_per_chain, BatchPlan& bp) {
-    for (auto& kb : h->d_kubo) kb.release();                     // (a Kubo call keeps its buffers for the next one; the recursion takes the memory back)
+    release_kubo_buffers(h, true, true);                         // (a Kubo call keeps its buffers for the next one; the recursion takes the memory back)
     size_t free_b = 0, total_b = 0;
     HIPCK(h, hipMemGetInfo(&free_b, &total_b));
     size_t reusable = 0;
@@ -1931,6 +1942,7 @@ extern "C" int rsrec_block_green(rsrec_t* h, int nsites, int lld, int nen, const
     const size_t gbytes = (size_t)nen * BLK * sizeof(double2);       // g0 of one site
     const size_t in_site = 2 * cbytes + 2 * tbytes;
     const int super = (int)std::max<size_t>(1, std::min<size_t>((size_t)nsites, ((size_t)4 << 30) / in_site));   // <= 4 GiB of coefficients resident
+    release_kubo_buffers(h, true, true);
     HIPCK(h, h->d_green_in.reserve((size_t)super * in_site + (size_t)nen * sizeof(double)));
     char* base = static_cast<char*>(h->d_green_in.p);
     double* d_ene = reinterpret_cast<double*>(base);
@@ -1988,6 +2000,7 @@ extern "C" int rsrec_terminator(rsrec_t* h, int nsites, int lld, const double* a
     if (nsites == 0) return RSREC_OK;
     HIPCK(h, hipSetDevice(h->device));
     const size_t cbytes = (size_t)nsites * lld * BLK * sizeof(double2), tbytes = (size_t)nsites * BLK * sizeof(double);
+    release_kubo_buffers(h, true, true);
     HIPCK(h, h->d_green_in.reserve(2 * cbytes));
     HIPCK(h, h->d_term.reserve(2 * tbytes + 2 * (size_t)nsites * sizeof(double)));
     double2* d_ab = h->d_green_in.as<double2>();
@@ -2025,6 +2038,7 @@ extern "C" int rsrec_scalar_density(rsrec_t* h, int nsites, int nmdir, int llmax
     const int nchain = NB * nsites * nmdir;
     const size_t cb = (size_t)nchain * llmax * sizeof(double), pb = (size_t)NB * nsites * sizeof(double), eb = (size_t)npts * sizeof(double),
                  gb = 2 * (size_t)nchain * sizeof(double), tb = (size_t)nchain * npts * sizeof(double);
+    release_kubo_buffers(h, true, true);
     HIPCK(h, h->d_green_in.reserve(2 * cb + 2 * pb + eb + gb));
     HIPCK(h, h->d_green_out.reserve(tb));
     double* d_a = h->d_green_in.as<double>();
@@ -2068,6 +2082,7 @@ extern "C" int rsrec_block_ldos(rsrec_t* h, int nen, const double* ene, double e
     HIPCK(h, hipSetDevice(h->device));
     h->n_ldos_calls++;
     const size_t cel = (size_t)n * lld * BLK;
+    release_kubo_buffers(h, true, true);
     HIPCK(h, h->d_bsqrt.reserve(cel * sizeof(double2)));
     HIPCK(h, h->d_term.reserve(2 * (size_t)n * BLK * sizeof(double) + 2 * (size_t)n * sizeof(double)));
     HIPCK(h, h->d_gim.reserve((size_t)n * nen * NB * sizeof(double) + (size_t)nen * sizeof(double)));
@@ -2141,6 +2156,7 @@ extern "C" int rsrec_chebyshev_green(rsrec_t* h, int nsites, int lld, int nen, c
     }
     const size_t mbytes = (size_t)nm * BLK * sizeof(double2), gbytes = (size_t)nen * BLK * sizeof(double2);
     const int super = (int)std::max<size_t>(1, std::min<size_t>((size_t)nsites, ((size_t)4 << 30) / mbytes));
+    release_kubo_buffers(h, true, true);
     HIPCK(h, h->d_green_in.reserve((size_t)super * mbytes + (size_t)(nen + nm) * sizeof(double)));
     double* d_ene = static_cast<double*>(h->d_green_in.p);
     double* d_kern = d_ene + nen;
@@ -2477,6 +2493,7 @@ extern "C" int rsrec_kubo_moments(rsrec_t* h, int nvec, int nseed, const int32_t
     HIPCK(h, hipSetDevice(h->device));
     reset_timing(h);
     if (nvec == 0) return RSREC_OK;
+    release_kubo_buffers(h, false, true);                          // (the integrand's buffers; this call's own stay for the next one)
     rc = build_kubo_operator(h, 0, v_a, vo_a); if (rc) return rc;
     rc = build_kubo_operator(h, 1, v_b, vo_b); if (rc) return rc;
     if (h->hoh && h->nmax > 0) { rc = build_kubo_hbulk(h); if (rc) return rc; }
@@ -2662,6 +2679,89 @@ extern "C" int rsrec_kubo_moments(rsrec_t* h, int nvec, int nseed, const int32_t
         h->n_atom_steps = (double)kk * h->n_kubo_chain_launches;
     }
     cleanup();
+    return RSREC_OK;
+}
+
+// The conductivity integrand of calculate_gamma_nm + calculate_conductivity_tensor (conductivity.f90:158-268) in factorised form
+// (kernels_cond.hpp): integrand(l, i, v) = factor sum_{n,m} Gamma(i,n,m) mu(l,l,n,m,v), no Gamma array.  Vectors one after another:
+// the S / D planes of one vector (18 x L x L x 32 B: 144 MB at L = 500) are the largest buffer.
+extern "C" int rsrec_kubo_integrand(rsrec_t* h, int nvec, int cond_ll, const double* mu_nm, int nen, const double* ene, double energy_min,
+                                    double energy_max, double* integrand) {
+    if (!h) return RSREC_ERR_ARG;
+    if (nvec < 1 || cond_ll < 1 || cond_ll > RSREC_COND_LL_MAX || nen < 1 || !mu_nm || !ene || !integrand)
+        return fail(h, RSREC_ERR_ARG, "rsrec_kubo_integrand: bad argument (nvec=%d cond_ll=%d nen=%d)", nvec, cond_ll, nen);
+    if (!std::isfinite(energy_min) || !std::isfinite(energy_max) || !(energy_max > energy_min))
+        return fail(h, RSREC_ERR_ARG, "rsrec_kubo_integrand: energy window [%g, %g] is empty", energy_min, energy_max);
+    HIPCK(h, hipSetDevice(h->device));
+    reset_timing(h);
+    const int L = cond_ll, lk = (L + 3) / 4 * 4, ln = (L + 15) / 16 * 16, ep = (nen + KC_ROWS - 1) / KC_ROWS * KC_ROWS, ntiles = ln / 16;
+    // a, b and factor as the reference forms them (:179-180, :254-256): 2 - 0.3 is default REAL(4)
+    const double a = (energy_max - energy_min) / (double)(2.0f - 0.3f), b = (energy_max + energy_min) / 2, de = energy_max - energy_min;
+    const double factor = 16 / (3.14159265358979323846 * (de * de));
+    // Lorentz kernel x weights (:186-194): lorentz_kernel forms (real(ll) - 1)/real(bign) and 1 - that in single precision (math.f90:1674)
+    std::vector<double> w(L);
+    for (int ll = 1; ll <= L; ++ll) {
+        const float r = ((float)ll - 1.0f) / (float)L, t = 1.0f - r;
+        w[ll - 1] = std::sinh(6.0 * (double)t) / std::sinh(6.0) * (ll == 1 ? 0.5 : 1.0);
+    }
+    const bool mu_dev = is_device_ptr(mu_nm), out_dev = is_device_ptr(integrand);
+    const size_t per_vec_out = (size_t)NB * nen;
+    // buffer 0: tb (lk x ep), ta (ln x ep complex), pre (ep), w (L), ene (nen);  1: S / D planes;  2: partials;  3: staging
+    const size_t o_ta = (size_t)lk * ep, o_pre = o_ta + 2 * (size_t)ln * ep, o_w = o_pre + ep, o_ene = o_w + L, n0 = o_ene + nen;
+    const size_t mu_compact = mu_dev ? 0 : (size_t)NB * L * L * 2, n3 = mu_compact + (out_dev ? 0 : 2 * per_vec_out * nvec);
+    // the moments' buffers (d_kubo) stay for the next rsrec_kubo_moments call unless this call needs their memory
+    const size_t want[4] = {n0 * sizeof(double), (size_t)NB * lk * ln * sizeof(double4_t), (size_t)NB * ntiles * ep * sizeof(double2), n3 * sizeof(double)};
+    for (int k = 0; k < 4; ++k) {
+        if (!want[k]) continue;
+        if (h->d_cond[k].reserve(want[k]) != hipSuccess) {
+            (void)hipGetLastError();
+            release_kubo_buffers(h, true, false);
+            HIPCK(h, h->d_cond[k].reserve(want[k]));
+        }
+    }
+    double* T = h->d_cond[0].as<double>();
+    XFER(xfer_h2d(h, T + o_w, w.data(), (size_t)L * sizeof(double)));
+    XFER(xfer_h2d(h, T + o_ene, ene, (size_t)nen * sizeof(double)));
+    hipEvent_t e_begin = next_event(h);
+    k_cond_basis<<<(ep + 255) / 256, 256, 0, h->stream>>>(nen, ep, L, lk, ln, T + o_ene, T + o_w, a, b, factor, T, reinterpret_cast<double2*>(T + o_ta), T + o_pre);
+    HIPCK(h, hipGetLastError());
+    double* stage = h->d_cond[3].as<double>();
+    double2* out = out_dev ? reinterpret_cast<double2*>(integrand) : reinterpret_cast<double2*>(stage + mu_compact);
+    std::vector<double> diag(mu_dev ? 0 : mu_compact);
+    const size_t gelems = (size_t)NB * lk * ln;
+    const dim3 cgrid((unsigned)((ep + 4 * KC_ROWS - 1) / (4 * KC_ROWS)), (unsigned)ntiles, NB);
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> cev;
+    for (int v = 0; v < nvec; ++v) {
+        const double2* src;
+        int sl, sn;
+        if (mu_dev) {
+            src = reinterpret_cast<const double2*>(mu_nm) + (size_t)BLK * L * L * v;
+            sl = NB + 1; sn = BLK;                                   // the diagonals where they lie: nothing of size 18 x 18 x L x L is copied
+        } else {                                                     // host moments: only the 18 diagonals cross the bus
+            const double* mv = mu_nm + 2 * (size_t)BLK * L * L * v;
+            for (size_t nm = 0; nm < (size_t)L * L; ++nm)
+                for (int l = 0; l < NB; ++l) {
+                    diag[2 * (nm * NB + l)] = mv[2 * (nm * BLK + (size_t)l * (NB + 1))];
+                    diag[2 * (nm * NB + l) + 1] = mv[2 * (nm * BLK + (size_t)l * (NB + 1)) + 1];
+                }
+            XFER(xfer_h2d(h, stage, diag.data(), mu_compact * sizeof(double)));
+            src = reinterpret_cast<const double2*>(stage);
+            sl = 1; sn = NB;
+        }
+        k_cond_gather<<<(int)std::min<size_t>(4096, (gelems + 255) / 256), 256, 0, h->stream>>>(src, sl, sn, L, lk, ln, h->d_cond[1].as<double4_t>());
+        hipEvent_t c0 = next_event(h);
+        k_cond_contract<<<cgrid, 256, 0, h->stream>>>(ep, lk, ln, T, reinterpret_cast<const double2*>(T + o_ta), h->d_cond[1].as<double4_t>(), h->d_cond[2].as<double2>());
+        k_cond_reduce<<<(int)((per_vec_out + 255) / 256), 256, 0, h->stream>>>(nen, ep, ntiles, h->d_cond[2].as<double2>(), T + o_pre, out + per_vec_out * v);
+        hipEvent_t c1 = next_event(h);
+        HIPCK(h, hipGetLastError());
+        if (!mu_dev) HIPCK(h, hipStreamSynchronize(h->stream));    // (the staging of the next vector's diagonals is overwritten)
+        cev.emplace_back(c0, c1);
+    }
+    hipEvent_t e_end = next_event(h);
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    if (!out_dev) XFER(xfer_d2h(h, integrand, out, per_vec_out * nvec * sizeof(double2)));
+    h->t_total_ms = ev_ms(e_begin, e_end);
+    for (auto& pr : cev) h->t_rest_ms += ev_ms(pr.first, pr.second);      // the contractions (k_cond_contract + k_cond_reduce)
     return RSREC_OK;
 }
 
@@ -2872,6 +2972,7 @@ extern "C" int rsrec_scalar_lanczos(rsrec_t* h, int nsites, const int32_t* seed_
     const int B = (int)std::min<long>(nsites, h->opt_batch > 0 ? h->opt_batch : 16);
     const int nblk = (int)std::min<long>(std::max<long>(1, (kk + TILE_ATOMS - 1) / TILE_ATOMS), 64);
     const int nch = B * NB;
+    release_kubo_buffers(h, true, true);
     for (int v = 0; v < 2; ++v) HIPCK(h, h->d_vec[v].reserve((size_t)nch * velems * sizeof(double2)));
     HIPCK(h, h->d_scal.reserve((size_t)nch * (nblk + 2 * (size_t)lld) * sizeof(double) + 64));
     HIPCK(h, h->d_seed.reserve((size_t)nch * 2 * 4));
