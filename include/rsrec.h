@@ -221,6 +221,33 @@ int rsrec_kubo_moments(rsrec_t *h, int nvec, int nseed, const int32_t *seed_atom
 int rsrec_kubo_integrand(rsrec_t *h, int nvec, int cond_ll, const double *mu_nm, int nen, const double *ene, double energy_min,
                          double energy_max, double *integrand);
 
+/* Exchange couplings of the pairs of one rank: green%calculate_intersite_gf / _twoindex (green.f90:386-469) and the integrands and
+ * Fermi-weighted Simpson integrals of exchange%calculate_exchange / _twoindex (exchange.f90:1032-1615), without the intersite arrays
+ * (kernels_exchange.hpp: g0 of a pair's chains stays in LDS; every quantity is a trace Tr(D_i A D_j B) of the diagonal d_matrix).
+ *   kind        : 0 block (green%block_green_ij, eta = 0), 1 Chebyshev (chebyshev_green_ij)
+ *   same        : int32 (npairs), 1 where ijpair(p,1) == ijpair(p,2): chain 1 alone is used (slots 2..4 are not read)
+ *   lld, nen, ene, nv1, fermi : control%lld, channels_ldos + 10, energy%ene (host), energy%nv1, energy%fermi; nen >= nv1 + 9
+ *   sym_term    : control%sym_term (block);  energy_min / energy_max: the Chebyshev scaling (kind 1)
+ *   a_inf, b_inf: real (18,18,4*npairs) terminators of the chains (block), or both NULL: computed on the device (get_terminf).  With
+ *               resident chains of a seeded call that skipped the repeats of i == j pairs they must be NULL (RSREC_ERR_ARG otherwise)
+ *   coef_a, coef_b: block: a_b and b2_b AFTER zsqr, complex (18,18,lld,4*npairs); Chebyshev: coef_a = mu_n (18,18,2*lld+2,4*npairs),
+ *               coef_b NULL.  Both NULL: the chains the last rsrec_*_seeded / rsrec_block_lanczos / rsrec_chebyshev call left on the device
+ *               (block: b2_b, square-rooted here); it must have run 4*npairs chains of depth lld.  Slot order ij_loc*4 - 4 + reci.
+ *   dpar        : real (4,3,2,npairs): per l = 0..2 and side i / j, (c_up + vmad, c_dn + vmad, dele_up, dele_dn) of the atom's type
+ *   pair_offset, npairs_total : this rank's pairs are columns pair_offset+1 .. pair_offset+npairs of the zero-padded images
+ *   xc, so, fo  : real (13,npairs_total) out = T_comm_xc / T_comm_xcso / T_comm_xcfo;  parts: real (28,npairs_total) = T_comm_xcparts
+ *   jcum        : real (nen,npairs) out or NULL: the second-order J of fort.150 with Ef = ene(nv) (second column, scaled)
+ *   integrand   : real (41,nen,npairs) out or NULL: the energy-resolved integrands (row order in kernels_exchange.hpp)
+ * d_matrix's parameters are rounded to single precision as its cmplx() calls do.  Scalings as the reference: *1.0d3/4/pi, 2.0d3/4/pi
+ * for the DMI parts.  simpson_f's read one element past its arrays is taken as 0.
+ * Every array may be host or device memory.  Pairs run in chunks: the device memory that scales with energies (integrands, staged
+ * coefficients) is bounded independent of npairs; only dpar, same and the output images (~0.8 KB per pair) grow with it.  Two calls with
+ * the same inputs give the same bits.  rsrec_get_timing: out[0] device ms of the call, out[5] ms in the Green + trace kernels. */
+int rsrec_exchange(rsrec_t *h, int kind, int npairs, const int32_t *same, int lld, int nen, const double *ene, int nv1, double fermi,
+                   int sym_term, double energy_min, double energy_max, const double *a_inf, const double *b_inf, const double *coef_a,
+                   const double *coef_b, const double *dpar, int pair_offset, int npairs_total, double *xc, double *so, double *fo,
+                   double *parts, double *jcum, double *integrand);
+
 /* One whole-vector product on caller arrays psi(18,18,kk) (complex, the reference's layout):
  *   vel = 0 : psi_out = (H psi_in - b psi_in)/a      ham_vec_matmul (:913) / ham_hoh_vec_matmul (:785); v_op, vo_op ignored
  *   vel = 1 : psi_out = V psi_in                      velo_vec_matmul (:587, 'n') / velo_hoh_vec_matmul (:656) with v_op (and vo_op with hoh)

@@ -210,25 +210,11 @@ __device__ __forceinline__ void green_stage_b(GreenLds& L, const double2* __rest
     }
 }
 
-// grid = (ceil(nen / GREEN_WAVES), nsites).  a_b, b_sqrt: [site][lld][324] complex; a_inf, b_inf: [site][324] real; g0: [site][nen][324]
-#ifndef GREEN_WAVES_PER_SIMD
-#define GREEN_WAVES_PER_SIMD 3
-#endif
-// LDOS = true: only Im g0(j,j) leaves the kernel, gim[site][nen][18] (the LDOS stage needs nothing else: bands.f90:258-268), 144 B
-// per (site, energy) instead of 5184 B.
-template <bool LDOS>
-__global__ __launch_bounds__(GREEN_WAVES * 64, GREEN_WAVES_PER_SIMD) void k_block_green(int lld, int nen, const double* __restrict__ ene, double eta_re, double eta_im, int sym_term,
-                                                                 const double* __restrict__ a_inf, const double* __restrict__ b_inf,
-                                                                 const double2* __restrict__ a_b, const double2* __restrict__ b_sqrt, double2* __restrict__ g0,
-                                                                 double* __restrict__ gim = nullptr) {
-    __shared__ GreenLds lds[GREEN_WAVES];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int ei = blockIdx.x * GREEN_WAVES + wave, site = blockIdx.y;
-    if (ei >= nen) return;                                       // wave-uniform; no workgroup barriers below
-    GreenLds& L = lds[wave];
-    const bool act = lane < 54;                                  // lanes 54..63 shadow lane 53 and never store
-    const int ig = act ? lane / 6 : 8, jg = act ? lane % 6 : 5;
-    const double e = ene[ei];
+// One (site, energy) chain of green%bgreen on one wave: on return L.M holds g0(:,:,E) of the site, column-major (wave-synchronous;
+// shared by k_block_green and the exchange kernel, which keeps the result in LDS).
+__device__ __forceinline__ void block_green_wave(GreenLds& L, int lane, int ig, int jg, bool act, double e, int site, int lld, double eta_re, double eta_im,
+                                                 int sym_term, const double* __restrict__ a_inf, const double* __restrict__ b_inf,
+                                                 const double2* __restrict__ a_b, const double2* __restrict__ b_sqrt) {
     const double* ai = a_inf + (size_t)site * BLK;
     const double* bi = b_inf + (size_t)site * BLK;
     const double a_diag = 0.5 * (ai[0] + ai[9 + NB * 9]), b_diag = 0.5 * (bi[0] + bi[9 + NB * 9]);
@@ -327,6 +313,28 @@ __global__ __launch_bounds__(GREEN_WAVES * 64, GREEN_WAVES_PER_SIMD) void k_bloc
             for (int c = 0; c < 3; ++c) L.M[(2 * ig + rr) + NB * (3 * jg + c)] = q[rr][c];
     }
     wave_sync();
+}
+
+// grid = (ceil(nen / GREEN_WAVES), nsites).  a_b, b_sqrt: [site][lld][324] complex; a_inf, b_inf: [site][324] real; g0: [site][nen][324]
+#ifndef GREEN_WAVES_PER_SIMD
+#define GREEN_WAVES_PER_SIMD 3
+#endif
+// LDOS = true: only Im g0(j,j) leaves the kernel, gim[site][nen][18] (the LDOS stage needs nothing else: bands.f90:258-268), 144 B
+// per (site, energy) instead of 5184 B.
+template <bool LDOS>
+__global__ __launch_bounds__(GREEN_WAVES * 64, GREEN_WAVES_PER_SIMD) void k_block_green(int lld, int nen, const double* __restrict__ ene, double eta_re, double eta_im, int sym_term,
+                                                                 const double* __restrict__ a_inf, const double* __restrict__ b_inf,
+                                                                 const double2* __restrict__ a_b, const double2* __restrict__ b_sqrt, double2* __restrict__ g0,
+                                                                 double* __restrict__ gim = nullptr) {
+    __shared__ GreenLds lds[GREEN_WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int ei = blockIdx.x * GREEN_WAVES + wave, site = blockIdx.y;
+    if (ei >= nen) return;                                       // wave-uniform; no workgroup barriers below
+    GreenLds& L = lds[wave];
+    const bool act = lane < 54;                                  // lanes 54..63 shadow lane 53 and never store
+    const int ig = act ? lane / 6 : 8, jg = act ? lane % 6 : 5;
+    const double e = ene[ei];
+    block_green_wave(L, lane, ig, jg, act, e, site, lld, eta_re, eta_im, sym_term, a_inf, b_inf, a_b, b_sqrt);
     if (LDOS) {
         if (lane < NB) gim[((size_t)site * nen + ei) * NB + lane] = L.M[lane * (NB + 1)].y;
         return;
@@ -334,6 +342,17 @@ __global__ __launch_bounds__(GREEN_WAVES * 64, GREEN_WAVES_PER_SIMD) void k_bloc
     double2* out = g0 + ((size_t)site * nen + ei) * BLK;
 #pragma unroll
     for (int m = 0; m < 6; ++m) { const int el = lane + 64 * m; if (el < BLK) out[el] = L.M[el]; }
+}
+
+// One element of chebyshev_green's g0 at one energy: the moments of the site `m` against the phase factors `ef` (also the exchange kernel's).
+__device__ __forceinline__ double2 chebyshev_green_elem(const double2* __restrict__ m, const double2* ef, int nm, int el, double den) {
+    double sr = 0.0, si = 0.0;
+    for (int i = 0; i < nm; ++i) {
+        const double2 v = m[(size_t)i * BLK + el], f = ef[i];
+        sr += v.x * f.x - v.y * f.y;
+        si += v.x * f.y + v.y * f.x;
+    }
+    return make_double2(sr / den, si / den);
 }
 
 // green%chebyshev_green (green.f90:1030-1108): g0(:,:,ie) = sum_i mu_ng(:,:,i) (-i exp(-i (i-1) acos w_ie)) / sqrt(a^2 - (e_ie - b)^2),
@@ -353,15 +372,7 @@ __global__ __launch_bounds__(256) void k_chebyshev_green(int nm, int nen, const 
     __syncthreads();
     const double den = sqrt(a * a - (e - b) * (e - b));
     const double2* m = mu + (size_t)site * nm * BLK;
-    for (int el = threadIdx.x; el < BLK; el += blockDim.x) {
-        double sr = 0.0, si = 0.0;
-        for (int i = 0; i < nm; ++i) {
-            const double2 v = m[(size_t)i * BLK + el], f = ef[i];
-            sr += v.x * f.x - v.y * f.y;
-            si += v.x * f.y + v.y * f.x;
-        }
-        g0[((size_t)site * nen + ie) * BLK + el] = make_double2(sr / den, si / den);
-    }
+    for (int el = threadIdx.x; el < BLK; el += blockDim.x) g0[((size_t)site * nen + ie) * BLK + el] = chebyshev_green_elem(m, ef, nm, el, den);
 }
 
 }  // namespace rsrec

@@ -37,6 +37,7 @@
 #include "kernels_ldos.hpp"
 #include "kernels_kubo.hpp"
 #include "kernels_cond.hpp"
+#include "kernels_exchange.hpp"
 #include "kernels_assemble.hpp"
 #include <dlfcn.h>
 
@@ -2134,6 +2135,23 @@ extern "C" int rsrec_block_ldos(rsrec_t* h, int nen, const double* ene, double e
     return RSREC_OK;
 }
 
+namespace {
+
+// The Jackson kernel of green%chebyshev_green (math.f90:1641-1655; real(ll) is a default-REAL conversion, exact for these small
+// integers) with mu_ng(:,:,2:) *= 2 (green.f90:1074) folded in.
+std::vector<double> chebyshev_green_kernel(int nm) {
+    std::vector<double> kern(nm);
+    const double pi = 3.14159265358979323846;
+    for (int ll = 1; ll <= nm; ++ll) {
+        const double theta = pi * ((double)ll - 1.0) / ((double)nm + 1.0);
+        kern[ll - 1] = (((double)nm - ((double)ll - 1.0) + 1.0) * cos(theta) + sin(theta) / tan(pi / ((double)nm + 1.0))) / ((double)nm + 1.0);
+        if (ll > 1) kern[ll - 1] *= 2.0;
+    }
+    return kern;
+}
+
+}  // namespace
+
 // green%chebyshev_green (green.f90:1030-1108): g0 from the Chebyshev moments of every site.
 extern "C" int rsrec_chebyshev_green(rsrec_t* h, int nsites, int lld, int nen, const double* ene, double energy_min, double energy_max,
                                      const double* mu_n, double* g0) {
@@ -2143,17 +2161,8 @@ extern "C" int rsrec_chebyshev_green(rsrec_t* h, int nsites, int lld, int nen, c
     HIPCK(h, hipSetDevice(h->device));
     const int nm = 2 * lld + 2;
     // scale/shift as the reference writes them (default-REAL literals 2 and 0.3, green.f90:1046-1047) and the Jackson kernel
-    // (math.f90:1641-1655; real(ll) is a default-REAL conversion, exact for these small integers)
     const double a = (energy_max - energy_min) / (double)(2.0f - 0.3f), b = (energy_max + energy_min) / 2;
-    std::vector<double> kern(nm);
-    {
-        const double pi = 3.14159265358979323846;
-        for (int ll = 1; ll <= nm; ++ll) {
-            const double theta = pi * ((double)ll - 1.0) / ((double)nm + 1.0);
-            kern[ll - 1] = (((double)nm - ((double)ll - 1.0) + 1.0) * cos(theta) + sin(theta) / tan(pi / ((double)nm + 1.0))) / ((double)nm + 1.0);
-            if (ll > 1) kern[ll - 1] *= 2.0;                 // mu_ng(:,:,2:) *= 2 (:1074)
-        }
-    }
+    const std::vector<double> kern = chebyshev_green_kernel(nm);
     const size_t mbytes = (size_t)nm * BLK * sizeof(double2), gbytes = (size_t)nen * BLK * sizeof(double2);
     const int super = (int)std::max<size_t>(1, std::min<size_t>((size_t)nsites, ((size_t)4 << 30) / mbytes));
     release_kubo_buffers(h, true, true);
@@ -2175,6 +2184,163 @@ extern "C" int rsrec_chebyshev_green(rsrec_t* h, int nsites, int lld, int nen, c
     hipEvent_t ev1 = next_event(h);
     HIPCK(h, hipStreamSynchronize(h->stream));
     h->t_total_ms = ev_ms(ev0, ev1);
+    return RSREC_OK;
+}
+
+namespace {
+
+__global__ void k_copy_d(const double* __restrict__ src, double* __restrict__ dst, size_t n) {
+    for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (size_t)gridDim.x * blockDim.x) dst[k] = src[k];
+}
+
+// device -> caller array (host or device memory; a device array may belong to another HIP runtime of the process: copied by a kernel)
+int xc_deliver(rsrec_t* h, double* dst, const double* src, size_t n) {
+    if (n == 0) return RSREC_OK;
+    if (is_device_ptr(dst)) {
+        k_copy_d<<<(unsigned)std::min<size_t>((n + 255) / 256, 4096), 256, 0, h->stream>>>(src, dst, n);
+        HIPCK(h, hipGetLastError());
+        return RSREC_OK;
+    }
+    return xfer_d2h(h, dst, src, n * sizeof(double));
+}
+
+// caller array -> device: a device array is read where it lies, a host array is staged in `stage`
+int xc_fetch(rsrec_t* h, const double* src, double* stage, size_t n, const double** out) {
+    if (is_device_ptr(src)) { *out = src; return RSREC_OK; }
+    *out = stage;
+    return xfer_h2d(h, stage, src, n * sizeof(double));
+}
+
+}  // namespace
+
+// green%calculate_intersite_gf / _twoindex + exchange%calculate_exchange / _twoindex (integrands and integrals) for the pairs of one rank.
+extern "C" int rsrec_exchange(rsrec_t* h, int kind, int npairs, const int32_t* same, int lld, int nen, const double* ene, int nv1, double fermi,
+                              int sym_term, double energy_min, double energy_max, const double* a_inf, const double* b_inf, const double* coef_a,
+                              const double* coef_b, const double* dpar, int pair_offset, int npairs_total, double* xc, double* so, double* fo,
+                              double* parts, double* jcum, double* integrand) {
+    if (!h) return RSREC_ERR_ARG;
+    if (kind < 0 || kind > 1) return fail(h, RSREC_ERR_ARG, "rsrec_exchange: kind %d is neither 0 (block) nor 1 (Chebyshev)", kind);
+    if (npairs < 1 || lld < 1 || nv1 < 1 || !same || !ene || !dpar || !xc || !so || !fo || !parts || pair_offset < 0 || npairs_total < pair_offset + npairs)
+        return fail(h, RSREC_ERR_ARG, "rsrec_exchange: bad argument");
+    if (nen < nv1 + 9) return fail(h, RSREC_ERR_ARG, "rsrec_exchange: nen = %d < nv1 + 9 = %d (simpson_f integrates to nv1 + 10)", nen, nv1 + 9);
+    if ((a_inf == nullptr) != (b_inf == nullptr)) return fail(h, RSREC_ERR_ARG, "rsrec_exchange: give both terminators or neither");
+    if (kind == 0 && (coef_a == nullptr) != (coef_b == nullptr)) return fail(h, RSREC_ERR_ARG, "rsrec_exchange: give both a_b and b_sqrt or neither");
+    if (kind == 0 && !a_inf && lld < 2) return fail(h, RSREC_ERR_ARG, "rsrec_exchange: the device terminator needs lld >= 2");
+    const int nchains = 4 * npairs;
+    const bool resident = coef_a == nullptr;
+    int nsame = 0;
+    for (int p = 0; p < npairs; ++p) nsame += same[p] != 0;
+    // first chain of every pair: slot order (4 per pair), or -- resident chains of a seeded call that skipped the repeats of i == j
+    // pairs (recur_b_ij, recursion.f90:1705) -- 1 chain for such a pair
+    const bool compact = resident && nsame > 0 && h->res_n == nchains - 3 * nsame;
+    if (resident && (h->res_kind != (kind == 0 ? 1 : 2) || (h->res_n != nchains && !compact) || h->res_lld != lld))
+        return fail(h, RSREC_ERR_ARG, "rsrec_exchange: no %s chains of %d pairs at lld = %d resident (call the seeded recursion first)",
+                    kind == 0 ? "block-Lanczos" : "Chebyshev", npairs, lld);
+    if (compact && a_inf)        // terminators come in slot order (4 per pair); the compacted chains have no slot for the skipped repeats
+        return fail(h, RSREC_ERR_ARG, "rsrec_exchange: resident chains with skipped i == j repeats take no caller terminators (pass NULL)");
+    std::vector<int> cbase(npairs + 1, 0);
+    for (int p = 0; p < npairs; ++p) cbase[p + 1] = cbase[p] + ((compact && same[p]) ? 1 : 4);
+    HIPCK(h, hipSetDevice(h->device));
+    const int nm = 2 * lld + 2;
+    const size_t cel = kind == 0 ? (size_t)lld * BLK : (size_t)nm * BLK;                // complex elements per chain (each of a_b, b_sqrt / mu_n)
+    const size_t ibytes = (size_t)nen * XC_NINT * sizeof(double);                          // integrand rows of one pair
+    const size_t cbytes = (size_t)4 * cel * sizeof(double2) * (kind == 0 ? 2 : 1);        // coefficients of one pair
+    // pairs per chunk: the integrand scratch <= 256 MiB and the staged coefficients <= 512 MiB, whatever npairs
+    const int P = (int)std::max<size_t>(1, std::min<size_t>((size_t)npairs, std::min(((size_t)256 << 20) / ibytes, ((size_t)512 << 20) / cbytes)));
+    const size_t nimg = (size_t)XC_NOUT * npairs_total;
+    release_kubo_buffers(h, true, true);
+    // d_green_in: ene | fermi weights | dpar | same | a_b (or mu_n) | b_sqrt | a_inf | b_inf  (chunk-sized from a_b on)
+    const size_t off_fw = nen, off_dpar = off_fw + nen, off_same = off_dpar + (size_t)24 * npairs, off_cb = off_same + (npairs + 1) / 2 + 1, off_ab = off_cb + (npairs + 2) / 2 + 1;
+    const size_t off_bs = off_ab + (size_t)4 * P * cel * 2, off_ai = off_bs + (kind == 0 ? (size_t)4 * P * cel * 2 : 0), off_bi = off_ai + std::max<size_t>((size_t)4 * P * BLK, nm);
+    const size_t in_doubles = off_bi + (size_t)4 * P * BLK;
+    HIPCK(h, h->d_green_in.reserve(in_doubles * sizeof(double)));
+    // d_green_out: integrand scratch | images (xc, so, fo, parts) | jcum of the chunk
+    const size_t off_img = (size_t)P * nen * XC_NINT, off_jc = off_img + nimg;
+    HIPCK(h, h->d_green_out.reserve((off_jc + (size_t)P * nen) * sizeof(double)));
+    if (resident && kind == 0) HIPCK(h, h->d_bsqrt.reserve((size_t)4 * P * cel * sizeof(double2)));
+    HIPCK(h, h->d_status.reserve(64));
+    HIPCK(h, hipMemsetAsync(h->d_status.p, 0, 64, h->stream));
+    double* din = h->d_green_in.as<double>();
+    double* dout = h->d_green_out.as<double>();
+    double* d_ene = din;
+    double* d_fw = din + off_fw;
+    double* d_dpar = din + off_dpar;
+    int* d_same = reinterpret_cast<int*>(din + off_same);
+    int* d_cb = reinterpret_cast<int*>(din + off_cb);
+    double* d_int = dout;
+    double* d_img = dout + off_img;
+    double* d_jc = dout + off_jc;
+    XFER(xfer_h2d(h, d_ene, ene, (size_t)nen * sizeof(double)));
+    XFER(xfer_h2d(h, d_dpar, dpar, (size_t)24 * npairs * sizeof(double)));
+    XFER(xfer_h2d(h, d_same, same, (size_t)npairs * sizeof(int32_t)));
+    XFER(xfer_h2d(h, d_cb, cbase.data(), (size_t)(npairs + 1) * sizeof(int)));
+    std::vector<double> kern;
+    const double ca = (energy_max - energy_min) / (double)(2.0f - 0.3f), cb = (energy_max + energy_min) / 2;    // chebyshev_green_ij's scaling
+    if (kind == 1) {
+        if (nm > (int)((64 * 1024) / sizeof(double2))) return fail(h, RSREC_ERR_ARG, "rsrec_exchange: lld = %d too deep for the Chebyshev phase table", lld);
+        kern = chebyshev_green_kernel(nm);
+        XFER(xfer_h2d(h, din + off_ai, kern.data(), (size_t)nm * sizeof(double)));      // (the terminator slot is unused by kind 1)
+    }
+    reset_timing(h);
+    hipEvent_t e0 = next_event(h);
+    HIPCK(h, hipMemsetAsync(d_img, 0, nimg * sizeof(double), h->stream));
+    k_exchange_fermi<<<(nen + 255) / 256, 256, 0, h->stream>>>(nen, d_ene, fermi, d_fw);
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> kev;
+    for (int p0 = 0; p0 < npairs; p0 += P) {
+        const int np = std::min(P, npairs - p0);
+        const size_t c0 = (size_t)cbase[p0], nc = (size_t)(cbase[p0 + np] - cbase[p0]);     // chains of the chunk
+        const double* sa = nullptr;
+        if (resident) sa = reinterpret_cast<const double*>((kind == 0 ? h->d_coefA.as<double2>() : h->d_mu.as<double2>()) + c0 * cel);
+        else XFER(xc_fetch(h, coef_a + c0 * cel * 2, din + off_ab, nc * cel * 2, &sa));
+        std::pair<hipEvent_t, hipEvent_t> ev;
+        if (kind == 0) {
+            const double* sb = nullptr;
+            if (resident) {                                 // b2_b of the recursion stays B^2: the square root goes to its own buffer
+                double2* dBs = h->d_bsqrt.as<double2>();
+                HIPCK(h, hipMemcpyAsync(dBs, h->d_coefB.as<double2>() + c0 * cel, nc * cel * sizeof(double2), hipMemcpyDeviceToDevice, h->stream));
+                k_zsqr<<<(unsigned)(nc * lld), 256, 0, h->stream>>>(dBs, h->d_status.as<int>());
+                sb = reinterpret_cast<const double*>(dBs);
+            } else XFER(xc_fetch(h, coef_b + c0 * cel * 2, din + off_bs, nc * cel * 2, &sb));
+            const double *ta = nullptr, *tb = nullptr;
+            if (a_inf) {
+                XFER(xc_fetch(h, a_inf + c0 * BLK, din + off_ai, nc * BLK, &ta));
+                XFER(xc_fetch(h, b_inf + c0 * BLK, din + off_bi, nc * BLK, &tb));
+            } else {
+                int rc = launch_terminator(h, (int)nc, lld, reinterpret_cast<const double2*>(sa), reinterpret_cast<const double2*>(sb), din + off_ai, din + off_bi);
+                if (rc) return rc;
+                ta = din + off_ai; tb = din + off_bi;
+            }
+            ev.first = next_event(h);
+            k_exchange_block<<<dim3(nen, np), 256, 0, h->stream>>>(lld, nen, d_ene, sym_term, ta, tb, reinterpret_cast<const double2*>(sa),
+                                                                reinterpret_cast<const double2*>(sb), d_same + p0, d_cb + p0, (int)c0, d_dpar + (size_t)24 * p0, d_int);
+        } else {
+            ev.first = next_event(h);
+            k_exchange_cheb<<<dim3(nen, np), 256, (size_t)nm * sizeof(double2), h->stream>>>(nm, nen, d_ene, ca, cb, din + off_ai, reinterpret_cast<const double2*>(sa),
+                                                                                           d_same + p0, d_cb + p0, (int)c0, d_dpar + (size_t)24 * p0, d_int);
+        }
+        HIPCK(h, hipGetLastError());
+        k_exchange_integrate<<<np, 128, 0, h->stream>>>(nen, nv1, d_ene, d_fw, d_int, pair_offset + p0, d_img, d_img + (size_t)13 * npairs_total,
+                                                        d_img + (size_t)26 * npairs_total, d_img + (size_t)39 * npairs_total, jcum ? d_jc : nullptr, 0);
+        HIPCK(h, hipGetLastError());
+        ev.second = next_event(h);
+        kev.push_back(ev);
+        if (jcum) XFER(xc_deliver(h, jcum + (size_t)p0 * nen, d_jc, (size_t)np * nen));
+        if (integrand) XFER(xc_deliver(h, integrand + (size_t)p0 * nen * XC_NINT, d_int, (size_t)np * nen * XC_NINT));
+        if (p0 + P < npairs) HIPCK(h, hipStreamSynchronize(h->stream));         // the chunk's staging buffers are reused
+    }
+    XFER(xc_deliver(h, xc, d_img, (size_t)13 * npairs_total));
+    XFER(xc_deliver(h, so, d_img + (size_t)13 * npairs_total, (size_t)13 * npairs_total));
+    XFER(xc_deliver(h, fo, d_img + (size_t)26 * npairs_total, (size_t)13 * npairs_total));
+    XFER(xc_deliver(h, parts, d_img + (size_t)39 * npairs_total, (size_t)28 * npairs_total));
+    hipEvent_t e1 = next_event(h);
+    int status = 0;
+    XFER(xfer_d2h(h, &status, h->d_status.p, 4));
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    h->t_total_ms = ev_ms(e0, e1);
+    h->t_rest_ms = 0.0;
+    for (auto& pr : kev) h->t_rest_ms += ev_ms(pr.first, pr.second);
+    h->t_hop_ms = h->t_rest_ms;
+    if (status & 1) return fail(h, RSREC_ERR_EIG, "Diagonalization error (18x18 Jacobi did not converge)");
     return RSREC_OK;
 }
 

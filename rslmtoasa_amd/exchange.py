@@ -1,0 +1,109 @@
+"""Drop-in counterpart of ``type(exchange)``'s two main routines (exchange.f90:1032-1615) on the GPU.
+
+green%calculate_intersite_gf + _twoindex (green.f90:386-469) and the integrands and Fermi-weighted Simpson integrals of
+exchange%calculate_exchange + _twoindex become one call, ``rsrec_exchange``.  Neither g0 nor the 24 intersite arrays are formed: per
+(pair, energy) the kernel reduces g0 of the pair's chains to 41 real integrands, and per pair to 67 numbers (kernels_exchange.hpp).
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+
+NINT = 41   # integrand rows per (pair, energy), order in kernels_exchange.hpp
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def exchange_dpar(c, dele, vmad, iz, pairs):
+    """dpar (4,3,2,npairs) for rsrec_exchange from the potential parameters of the atom types (potential%c, %dele, %vmad).
+
+    ``c, dele``: (ntype, 3, 2) -- per type, l = 0..2, spin up / down; ``vmad``: (ntype,); ``iz``: lattice%iz (1-based types per atom);
+    ``pairs``: (npairs, 2) 1-based atoms (lattice%ijpair).  Per side (i, j) and l: (c_up + vmad, c_dn + vmad, dele_up, dele_dn), the
+    sums formed in double as d_matrix forms them (symbolic_atom.f90:251-252); d_matrix's cmplx() then rounds them to single precision,
+    which rsrec_exchange does too."""
+    c, dele, vmad = np.asarray(c, np.float64), np.asarray(dele, np.float64), np.asarray(vmad, np.float64)
+    iz, pairs = np.asarray(iz), np.asarray(pairs)
+    out = np.zeros((4, 3, 2, len(pairs)), np.float64, order="F")
+    for p, ij in enumerate(pairs):
+        for side in range(2):
+            t = int(iz[int(ij[side]) - 1]) - 1
+            out[0, :, side, p] = c[t, :, 0] + vmad[t]
+            out[1, :, side, p] = c[t, :, 1] + vmad[t]
+            out[2, :, side, p] = dele[t, :, 0]
+            out[3, :, side, p] = dele[t, :, 1]
+    return out
+
+
+class Exchange:
+    """``Exchange(recursion, green).compute(...)`` on the rank's pairs after recur_b_ij / chebyshev_recur_ij (block: and zsqr)."""
+
+    def __init__(self, recursion, green):
+        self.recursion = recursion
+        self.green = green
+
+    def compute(self, fermi, nv1, dpar, kind="block", integrand=False, cumulative=False, resident=False, a_inf=None, b_inf=None,
+                pair_offset=0, npairs_total=None, coef=None):
+        """Returns (xc, so, fo, parts) = T_comm_xc, T_comm_xcso, T_comm_xcfo (13, npairs_total), T_comm_xcparts (28, npairs_total),
+        then jcum (nen, npairs) if ``cumulative`` and the integrand (41, nen, npairs) if ``integrand``.
+
+        The pairs are lattice%ijpair of this rank.  Coefficients: ``resident=True`` reads the chains the last seeded recursion left on the
+        device; else ``coef`` (a_b, b_sqrt) / (mu_n,) if given, else the recursion's arrays (a_b, b2_b after zsqr / mu_n).  Terminators:
+        ``a_inf, b_inf`` (18,18,4*npairs) or None (computed on the device)."""
+        rec, ene = self.recursion, np.ascontiguousarray(self.green.ene, dtype=np.float64)
+        pairs = np.asarray(rec.lattice.ijpair, dtype=np.int32)
+        from .recursion import site_partition
+        start, end = site_partition(rec.rank, rec.nprocs, len(pairs))
+        mine = pairs[start - 1:end]
+        npairs = len(mine)
+        npairs_total = len(pairs) if npairs_total is None else npairs_total
+        same = np.ascontiguousarray(mine[:, 0] == mine[:, 1], dtype=np.int32)
+        lld = int(rec.control.lld)
+        k = {"block": 0, "chebyshev": 1}[kind] if isinstance(kind, str) else int(kind)
+        ca = cb = None
+        if not resident:
+            if coef is not None:
+                arrs = list(coef)
+            elif k == 0:
+                arrs = [rec.a_b[:, :, :, :4 * npairs], rec.b2_b[:, :, :, :4 * npairs]]
+            else:
+                arrs = [rec.mu_n[:, :, :, :4 * npairs]]
+            arrs = [a if hasattr(a, "data_ptr") else np.asfortranarray(a, dtype=np.complex128) for a in arrs]
+            ca = arrs[0]
+            cb = arrs[1] if len(arrs) > 1 else None
+        keep = [ca, cb]
+        if a_inf is not None:
+            a_inf, b_inf = np.asfortranarray(a_inf, dtype=np.float64), np.asfortranarray(b_inf, dtype=np.float64)
+        dpar = np.asfortranarray(dpar, dtype=np.float64)
+        xc = np.zeros((13, npairs_total), order="F")
+        so, fo = np.zeros_like(xc), np.zeros_like(xc)
+        parts = np.zeros((28, npairs_total), order="F")
+        jcum = np.zeros((len(ene), npairs), order="F") if cumulative else None
+        integ = np.zeros((NINT, len(ene), npairs), order="F") if integrand else None
+
+        def p(a):
+            if a is None:
+                return None
+            if hasattr(a, "data_ptr"):
+                import torch
+                torch.cuda.synchronize(a.device)
+                return C.c_void_p(a.data_ptr())
+            return _ptr(a)
+
+        rec._check(rec._L.rsrec_exchange(rec._h, k, npairs, _ptr(same), lld, len(ene), _ptr(ene), int(nv1), float(fermi), int(self.green.sym_term),
+                                          float(rec.en.energy_min), float(rec.en.energy_max), _ptr(a_inf), _ptr(b_inf), p(ca), p(cb), _ptr(dpar),
+                                          int(pair_offset), int(npairs_total), _ptr(xc), _ptr(so), _ptr(fo), _ptr(parts), _ptr(jcum), _ptr(integ)))
+        del keep
+        out = [xc, so, fo, parts]
+        if cumulative:
+            out.append(jcum)
+        if integrand:
+            out.append(integ)
+        return tuple(out)
+
+    def timing(self):
+        """(device ms of the last call, ms in its Green + trace + integration kernels)."""
+        t = self.recursion.timing()
+        return t["total_ms"], t["rest_ms"]
