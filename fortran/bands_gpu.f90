@@ -56,6 +56,7 @@ module bands_gpu_mod
       procedure :: calculate_projected_green => gpu_calculate_projected_green
       procedure :: calculate_projected_dos => gpu_calculate_projected_dos
       procedure :: calculate_orbital_dos => gpu_calculate_orbital_dos
+      procedure :: restore_to_default => gpu_restore_to_default
    end type bands_gpu
 
    interface bands_gpu
@@ -80,6 +81,23 @@ contains
       call obj%restore_to_default()
       if (rsrec_env_flag('RSREC_HOST_LDOS')) obj%device_ldos = .false.   ! (hosts that cannot reach the member: fortran/shadow/)
    end function gpu_constructor
+
+   !> bands.f90:178-217.  In a pair run (lattice%njij /= 0: the exchange post-processing, calculation.f90:816-950) atoms_per_process
+   !> counts pairs, and the per-site energy arrays dx ... d_orb (20 MB per pair at 2500 energies) are read by no routine of the flow:
+   !> there they are allocated with no site columns.  Otherwise the reference's routine.
+   subroutine gpu_restore_to_default(this)
+      class(bands_gpu) :: this
+      integer :: nv
+      if (this%lattice%njij == 0) then
+         call this%bands%restore_to_default()
+         return
+      end if
+      nv = this%en%channels_ldos + 10
+      allocate (this%dtot(nv), this%dtotcheb(nv), this%dx(nv, 0), this%dy(nv, 0), this%dz(nv, 0), this%g0_x(9, 9, nv, 0), &
+                this%g0_y(9, 9, nv, 0), this%g0_z(9, 9, nv, 0), this%dspd(6, nv, 0), this%d_orb(9, 9, 3, nv, 0), this%mag_for(3, 0))
+      this%dtot(:) = 0.0d0
+      this%dtotcheb(:) = 0.0d0
+   end subroutine gpu_restore_to_default
 
    !> `g0` must exist before an inherited routine reads it
    subroutine ensure_g0(this)

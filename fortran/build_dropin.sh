@@ -2,7 +2,7 @@
 # ZERO-EDIT DROP-IN BUILD: the reference program linked from its own UNMODIFIED sources (main.f90, calculation.f90, self.f90 and every
 # other file, compiled where they lie under /root/reference/source) with the GPU types behind the reference's module names.
 #
-# How: the seven reference files whose types have a GPU counterpart are compiled under another module name
+# How: the eight reference files whose types have a GPU counterpart are compiled under another module name
 # (-D<name>_mod=<name>_ref_mod; the reference's sources are compiled with -cpp anyway, CMakeLists.txt), the GPU type of fortran/
 # extends the reference type from there (same -D, so its `use <name>_mod` finds the renamed reference module), and
 # fortran/shadow/<name>_mod.f90 re-exports the extended type under the reference's names.  Everything downstream -- `type(recursion) ::
@@ -11,7 +11,7 @@
 # A maintainer's version of this recipe is a CMake diff of a dozen lines.
 #
 # Outputs (oracle/_ref/dropin/, git-ignored like the rest of oracle/_ref: they contain reference object code):
-#   oracle/_ref/rslmto_dropin.x     = the reference's main program + librsrec behind its recursion / green / bands / hamiltonian / lattice / density_of_states / conductivity modules
+#   oracle/_ref/rslmto_dropin.x     = the reference's main program + librsrec behind its recursion / green / bands / hamiltonian / lattice / density_of_states / exchange / conductivity modules
 set -euo pipefail
 HERE="$(cd "$(dirname "$0")" && pwd)"
 ROOT="$(dirname "$HERE")"
@@ -51,7 +51,8 @@ shadowed recursion recursion_gpu
 shadowed density_of_states dos_gpu
 shadowed green green_gpu
 shadowed bands bands_gpu
-ref xc.f90 mix.f90 self.f90 exchange.f90
+ref xc.f90 mix.f90 self.f90
+shadowed exchange exchange_gpu
 shadowed conductivity conductivity_gpu
 ref include_codes/abspinlib/stdtypes.f90 include_codes/abspinlib/mtprng.f90 include_codes/abspinlib/parameters.f90 include_codes/abspinlib/constants.f90 include_codes/abspinlib/randomnumbers.f90 include_codes/abspinlib/depondt.f90 spin_dynamics.f90 calculation.f90 include_codes/abspinlib/abSpinlib.f90 include_codes/abspinlib/constrain.f90
 LIBOBJS="$OBJS"

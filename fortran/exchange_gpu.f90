@@ -1,0 +1,308 @@
+!------------------------------------------------------------------------------
+! exchange_gpu_mod -- GPU drop-in for type(exchange) (exchange.f90:46-96).
+!
+! green%calculate_intersite_gf / _twoindex (green.f90:386-469) and the integrands and Fermi-weighted Simpson integrals of
+! calculate_exchange / _twoindex (exchange.f90:1032-1615) are one call of librsrec, rsrec_exchange, on the chains the pair recursion
+! (recursion_gpu%recur_b_ij / chebyshev_recur_ij) left on the device; the 24 intersite arrays (0.1 GB per pair at 2500 energies) are
+! never formed (rslmtoasa_amd/csrc/kernels_exchange.hpp).  So:
+!   constructor                 : the reference's, then green_gpu is told that the intersite stage is done here (its
+!                                 calculate_intersite_gf / _twoindex then allocate and fill nothing)
+!   calculate_exchange          : the call for the rank's pairs, then the reference's tail (:1543-1612) restated line for line: the
+!                                 MPI_ALLREDUCE, the rank-0 stdout lines, jij.out / dij.out / aij.out / jtens.out and unit 99
+!   calculate_exchange_twoindex : the values of that call (or the call, if calculate_exchange did not run), then the eleven files of
+!                                 :1061-1131 and fort.150 in the reference's formats and order
+! What stays on the host is O(pairs): the T_comm images and the formatting, plus fort.150's cumulative J of the rank's pairs (one real
+! per pair and energy, 20 KB per pair at 2500 energies) between the two routines.
+! Errors of the library become g_logger%fatal, the reference's error behaviour on this path.
+!------------------------------------------------------------------------------
+module exchange_gpu_mod
+   use, intrinsic :: iso_c_binding
+   use exchange_mod
+   use bands_mod, only: bands
+   use green_gpu_mod, only: green_gpu
+   use mpi_mod
+   use precision_mod, only: rp
+   use math_mod, only: pi
+   use logger_mod, only: g_logger
+   use timer_mod, only: g_timer
+   use rsrec_binding
+   use rsrec_context_mod, only: rsrec_gpu_context
+#ifdef USE_MPI
+   use mpi
+#endif
+   implicit none
+
+   private
+
+   type, public, extends(exchange) :: exchange_gpu
+      !> T_comm_xc, T_comm_xcso, T_comm_xcfo (13, njij) and T_comm_xcparts (28, njij) of the last call, reduced over the ranks
+      real(rp), dimension(:, :), allocatable :: xc, so, fo, parts
+      !> fort.150's second column for the rank's pairs (channels_ldos + 10, end_atom - start_atom + 1)
+      real(rp), dimension(:, :), allocatable :: jcum
+   contains
+      procedure :: calculate_exchange => gpu_calculate_exchange
+      procedure :: calculate_exchange_twoindex => gpu_calculate_exchange_twoindex
+   end type exchange_gpu
+
+   interface exchange_gpu
+      procedure :: gpu_constructor
+   end interface exchange_gpu
+
+contains
+
+   !> constructor (:101-115)
+   function gpu_constructor(bands_obj) result(obj)
+      type(exchange_gpu) :: obj
+      type(bands), target, intent(in) :: bands_obj
+
+      obj%bands => bands_obj
+      obj%green => bands_obj%green
+      obj%lattice => bands_obj%lattice
+      obj%symbolic_atom => bands_obj%symbolic_atom
+      obj%en => bands_obj%en
+      obj%control => bands_obj%lattice%control
+      obj%recursion => bands_obj%recursion
+      obj%hamiltonian => bands_obj%recursion%hamiltonian
+
+      call obj%restore_to_default()
+      ! the intersite stage is ours: green's arrays go, its calculate_intersite_gf / _twoindex only keep their side effect (green_gpu.f90)
+      select type (g => obj%green)
+      class is (green_gpu)
+         call g%release_intersite()
+      end select
+   end function gpu_constructor
+
+   !> rsrec_exchange for the pairs start_atom .. end_atom of this rank (get_mpi_variables over njij), on the resident chains of the
+   !> pair recursion; the images are reduced over the ranks as :1543-1546 / :1375-1382 reduce theirs.
+   subroutine exchange_on_device(this)
+      class(exchange_gpu), intent(inout) :: this
+      integer :: nloc, nen, njij, p, ij, side, l, at, ikind
+      integer(c_int) :: rc, sym_i
+      type(c_ptr) :: ctx
+      integer(c_int), dimension(:), allocatable, target :: same
+      real(rp), dimension(:), allocatable, target :: ene
+      real(rp), dimension(:, :, :, :), allocatable, target :: dpar
+      real(rp), dimension(:, :), allocatable, target :: xc, so, fo, parts, jcum
+
+      nen = this%en%channels_ldos + 10
+      njij = this%lattice%njij
+      nloc = end_atom - start_atom + 1
+      select case (this%control%recur)
+      case ('block')
+         ikind = 0
+      case ('chebyshev')
+         ikind = 1
+      case default
+         call g_logger%fatal('exchange_gpu: control%recur '//trim(this%control%recur)//' has no pair recursion', __FILE__, __LINE__)
+      end select
+      allocate (xc(13, njij), so(13, njij), fo(13, njij), parts(28, njij), jcum(nen, max(nloc, 0)))
+      xc = 0.0_rp; so = 0.0_rp; fo = 0.0_rp; parts = 0.0_rp; jcum = 0.0_rp
+      if (nloc > 0) then
+         allocate (same(nloc), ene(nen), dpar(4, 3, 2, nloc))
+         ene(:) = this%en%ene(1:nen)
+         ! d_matrix's parameters of atoms i and j (symbolic_atom.f90:250-255): (c_up + vmad, c_dn + vmad, dele_up, dele_dn) per l
+         do ij = start_atom, end_atom
+            p = ij - start_atom + 1
+            same(p) = 0
+            if (this%lattice%ijpair(ij, 1) == this%lattice%ijpair(ij, 2)) same(p) = 1
+            do side = 1, 2
+               at = this%lattice%iz(this%lattice%ijpair(ij, side))
+               associate (pot => this%symbolic_atom(at)%potential)
+                  do l = 0, 2
+                     dpar(1, l + 1, side, p) = pot%c(l, 1) + pot%vmad
+                     dpar(2, l + 1, side, p) = pot%c(l, 2) + pot%vmad
+                     dpar(3, l + 1, side, p) = pot%dele(l, 1)
+                     dpar(4, l + 1, side, p) = pot%dele(l, 2)
+                  end do
+               end associate
+            end do
+         end do
+         sym_i = 0
+         if (this%control%sym_term) sym_i = 1
+         ctx = rsrec_gpu_context()
+         call g_timer%start('exchange-gpu')
+         ! coefficients and terminators NULL: the chains recur_b_ij / chebyshev_recur_ij left on the device (i == j pairs: one chain)
+         rc = rsrec_exchange(ctx, int(ikind, c_int), int(nloc, c_int), c_loc(same), int(this%control%lld, c_int), int(nen, c_int), &
+                             c_loc(ene), int(this%en%nv1, c_int), real(this%en%fermi, c_double), sym_i, &
+                             real(this%en%energy_min, c_double), real(this%en%energy_max, c_double), c_null_ptr, c_null_ptr, &
+                             c_null_ptr, c_null_ptr, c_loc(dpar), int(start_atom - 1, c_int), int(njij, c_int), c_loc(xc), c_loc(so), &
+                             c_loc(fo), c_loc(parts), c_loc(jcum), c_null_ptr)
+         call g_timer%stop('exchange-gpu')
+         if (rc /= 0) call g_logger%fatal('exchange_gpu: rsrec_exchange: '//rsrec_error_string(ctx), __FILE__, __LINE__)
+      end if
+#ifdef USE_MPI
+      call MPI_ALLREDUCE(MPI_IN_PLACE, xc, product(shape(xc)), MPI_DOUBLE_PRECISION, MPI_SUM, MPI_COMM_WORLD, ierr)
+      call MPI_ALLREDUCE(MPI_IN_PLACE, so, product(shape(so)), MPI_DOUBLE_PRECISION, MPI_SUM, MPI_COMM_WORLD, ierr)
+      call MPI_ALLREDUCE(MPI_IN_PLACE, fo, product(shape(fo)), MPI_DOUBLE_PRECISION, MPI_SUM, MPI_COMM_WORLD, ierr)
+      call MPI_ALLREDUCE(MPI_IN_PLACE, parts, product(shape(parts)), MPI_DOUBLE_PRECISION, MPI_SUM, MPI_COMM_WORLD, ierr)
+#endif
+      call move_alloc(xc, this%xc)
+      call move_alloc(so, this%so)
+      call move_alloc(fo, this%fo)
+      call move_alloc(parts, this%parts)
+      call move_alloc(jcum, this%jcum)
+   end subroutine exchange_on_device
+
+   !> open `fname` on `funit` as :1467-1490 / :1061-1131 do (a unit already open is fatal)
+   subroutine open_unit(funit, fname, what)
+      integer, intent(in) :: funit
+      character(len=*), intent(in) :: fname, what
+      logical :: isopen
+      inquire (unit=funit, opened=isopen)
+      if (isopen) then
+         call g_logger%fatal('exchange%calculate_exchange, file '//what, __FILE__, __LINE__)
+      else
+         open (unit=funit, file=fname)
+      end if
+   end subroutine open_unit
+
+   !> calculate_exchange (:1437-1615)
+   subroutine gpu_calculate_exchange(this)
+      class(exchange_gpu) :: this
+      real(rp), dimension(3, 3) :: jtens
+      integer :: i, j, njij_glob
+
+      call exchange_on_device(this)
+
+      call open_unit(20, 'jij.out', 'jij.out: Unit 20 is already open')
+      call open_unit(30, 'dij.out', 'dij.out: Unit 30 is already open')
+      call open_unit(40, 'aij.out', 'aij.out: Unit 40 is already open')
+      call open_unit(60, 'jtens.out', 'jtens.out: Unit 40 is already open')
+
+      ! :1549-1603
+      if (rank == 0) then
+         do njij_glob = 1, this%lattice%njij
+            i = this%lattice%ijpair(njij_glob, 1)
+            j = this%lattice%ijpair(njij_glob, 2)
+
+            write (*, *) 'Atom', i, 'coordinates:', this%lattice%cr(:, i)
+            write (*, *) 'Atom', j, 'coordinates:', this%lattice%cr(:, j)
+
+            this%jij = this%xc(1, njij_glob)
+            write (*, *) 'Jij between pair', i, 'and ', j, 'is ', this%jij
+            this%dmi = this%xc(2:4, njij_glob)
+            write (*, *) 'Dij between pair', i, 'and ', j, 'is ', this%dmi
+            this%aij = reshape(this%xc(5:13, njij_glob), [3, 3])
+            write (*, *) 'Iij between pair', i, 'and ', j, 'is'
+            print '(3f12.6)', this%aij(1, :)
+            print '(3f12.6)', this%aij(2, :)
+            print '(3f12.6)', this%aij(3, :)
+
+            write (20, '(2i8,2x,3f12.6,2x,1f12.6,1x,f12.6)') &
+               this%lattice%iz(i), this%lattice%iz(j), this%lattice%cr(:, j) - this%lattice%cr(:, i), this%jij, norm2(this%lattice%cr(:, i) - this%lattice%cr(:, j))
+            write (30, '(2i8,2x,3f12.6,2x,3f12.6,1x,f12.6)') &
+               this%lattice%iz(i), this%lattice%iz(j), this%lattice%cr(:, j) - this%lattice%cr(:, i), this%dmi, norm2(this%lattice%cr(:, i) - this%lattice%cr(:, j))
+            write (40, '(2i8,2x,3f12.6,2x,9f12.6,1x,f12.6)') &
+               this%lattice%iz(i), this%lattice%iz(j), this%lattice%cr(:, j) - this%lattice%cr(:, i), this%aij, norm2(this%lattice%cr(:, i) - this%lattice%cr(:, j))
+            write (99, *) 'null', (this%lattice%cr(:, j) + this%lattice%cr(:, i))/2, this%dmi/norm2(this%dmi)
+            jtens = 0.0d0
+            jtens(1, 1) = this%jij
+            jtens(2, 2) = jtens(1, 1)
+            jtens(3, 3) = jtens(1, 1)
+            jtens(1, 2) = this%dmi(3)
+            jtens(2, 1) = -jtens(1, 2)
+            jtens(1, 3) = -this%dmi(2)
+            jtens(3, 1) = -jtens(1, 3)
+            jtens(2, 3) = this%dmi(1)
+            jtens(3, 2) = -jtens(2, 3)
+            jtens(:, :) = jtens(:, :) + this%aij(:, :)
+            write (*, *) 'J tensor between pair', i, 'and ', j, 'is'
+            print '(3f12.6)', jtens(1, :)
+            print '(3f12.6)', jtens(2, :)
+            print '(3f12.6)', jtens(3, :)
+         end do
+      end if
+
+      close (20)
+      close (30)
+      close (40)
+      close (60)
+
+#ifdef USE_MPI
+      call MPI_BARRIER(MPI_COMM_WORLD, ierr)
+#endif
+   end subroutine gpu_calculate_exchange
+
+   !> calculate_exchange_twoindex (:1032-1435)
+   subroutine gpu_calculate_exchange_twoindex(this)
+      class(exchange_gpu) :: this
+      integer :: i, j, nv, njij_glob
+
+      if (.not. allocated(this%jcum)) call exchange_on_device(this)
+
+      call open_unit(20, 'jijso.out', 'jijso.out: Unit 20 is already open')
+      call open_unit(25, 'jijfo.out', 'jijfo.out: Unit 25 is already open')
+      call open_unit(30, 'dijso.out', 'dijso.out: Unit 30 is already open')
+      call open_unit(35, 'dijfo.out', 'dijfo.out: Unit 30 is already open')
+      call open_unit(40, 'aijso.out', 'aijso.out: Unit 40 is already open')
+      call open_unit(45, 'aijfo.out', 'aijfo.out: Unit 45 is already open')
+      call open_unit(60, 'jtensfo.out', 'jtensso.out: Unit 60 is already open')
+      call open_unit(65, 'jtensso.out', 'jtensfo.out: Unit 65 is already open')
+      call open_unit(70, 'jijparts.out', 'jijparts.out: Unit 70 is already open')
+      call open_unit(75, 'dijparts.out', 'dijparts.out: Unit 75 is already open')
+      call open_unit(80, 'aijparts.out', 'aijparts.out: Unit 80 is already open')
+
+      ! :1281-1285: fort.150, per pair of this rank in order, written before the reduction
+      do njij_glob = start_atom, end_atom
+         do nv = 1, this%en%channels_ldos + 10
+            write (150, *) this%en%ene(nv) - this%en%fermi, this%jcum(nv, njij_glob - start_atom + 1)
+         end do
+      end do
+
+      ! :1385-1414
+      if (rank == 0) then
+         do njij_glob = 1, this%lattice%njij
+            i = this%lattice%ijpair(njij_glob, 1)
+            j = this%lattice%ijpair(njij_glob, 2)
+
+            this%jij = this%so(1, njij_glob)
+            write (20, '(2i8,2x,3e20.11,2x,1es16.6,1x,f12.6)') &
+               this%lattice%iz(i), this%lattice%iz(j), this%lattice%cr(:, j) - this%lattice%cr(:, i), this%jij, norm2(this%lattice%cr(:, i) - this%lattice%cr(:, j))
+            this%jij = this%fo(1, njij_glob)
+            write (25, '(2i8,2x,3e20.11,2x,1es16.6,1x,f12.6)') &
+               this%lattice%iz(i), this%lattice%iz(j), this%lattice%cr(:, j) - this%lattice%cr(:, i), this%jij, norm2(this%lattice%cr(:, i) - this%lattice%cr(:, j))
+            this%jijcd = this%parts(1, njij_glob); this%jijsd = this%parts(2, njij_glob)
+            this%jijcc = this%parts(3, njij_glob); this%jijsc = this%parts(4, njij_glob)
+            write (70, '(2i8,2x,3e20.11,2x,4es16.6,1x,f12.6)') &
+               this%lattice%iz(i), this%lattice%iz(j), this%lattice%cr(:, j) - this%lattice%cr(:, i), this%jijcd, this%jijsd, this%jijcc, this%jijsc, &
+               norm2(this%lattice%cr(:, i) - this%lattice%cr(:, j))
+            this%dmi = this%so(2:4, njij_glob)
+            write (30, '(2i8,2x,3e20.11,2x,3es16.6,1x,f12.6)') &
+               this%lattice%iz(i), this%lattice%iz(j), this%lattice%cr(:, j) - this%lattice%cr(:, i), this%dmi, norm2(this%lattice%cr(:, i) - this%lattice%cr(:, j))
+            this%dmi = this%fo(2:4, njij_glob)
+            write (35, '(2i8,2x,3e20.11,2x,3es16.6,1x,f12.6)') &
+               this%lattice%iz(i), this%lattice%iz(j), this%lattice%cr(:, j) - this%lattice%cr(:, i), this%dmi, norm2(this%lattice%cr(:, i) - this%lattice%cr(:, j))
+            this%dmicc = this%parts(5:7, njij_glob); this%dmisc = this%parts(8:10, njij_glob)
+            write (75, '(2i8,2x,3e20.11,2x,6es16.6,1x,f12.6)') &
+               this%lattice%iz(i), this%lattice%iz(j), this%lattice%cr(:, j) - this%lattice%cr(:, i), this%dmicc, this%dmisc, norm2(this%lattice%cr(:, i) - this%lattice%cr(:, j))
+            this%aij = reshape(this%so(5:13, njij_glob), [3, 3])
+            write (40, '(2i8,2x,3e20.11,2x,9es16.6,1x,f12.6)') &
+               this%lattice%iz(i), this%lattice%iz(j), this%lattice%cr(:, j) - this%lattice%cr(:, i), this%aij, norm2(this%lattice%cr(:, i) - this%lattice%cr(:, j))
+            this%aij = reshape(this%fo(5:13, njij_glob), [3, 3])
+            write (45, '(2i8,2x,3e20.11,2x,9es16.6,1x,f12.6)') &
+               this%lattice%iz(i), this%lattice%iz(j), this%lattice%cr(:, j) - this%lattice%cr(:, i), this%aij, norm2(this%lattice%cr(:, i) - this%lattice%cr(:, j))
+            this%aijsd = reshape(this%parts(11:19, njij_glob), [3, 3]); this%aijsc = reshape(this%parts(20:28, njij_glob), [3, 3])
+            write (80, '(2i8,2x,3e20.11,2x,18es16.6,1x,f12.6)') &
+               this%lattice%iz(i), this%lattice%iz(j), this%lattice%cr(:, j) - this%lattice%cr(:, i), this%aijsd, this%aijsc, norm2(this%lattice%cr(:, i) - this%lattice%cr(:, j))
+         end do
+      end if
+
+      close (20)
+      close (25)
+      close (30)
+      close (35)
+      close (40)
+      close (45)
+      close (60)
+      close (65)
+      close (70)
+      close (75)
+      close (80)
+
+      deallocate (this%jcum)
+#ifdef USE_MPI
+      call MPI_BARRIER(MPI_COMM_WORLD, ierr)
+#endif
+   end subroutine gpu_calculate_exchange_twoindex
+
+end module exchange_gpu_mod

@@ -14,6 +14,12 @@
 !> `bands`, `self` and `exchange` hold `class(green), pointer` (bands.f90:49, self.f90:76, exchange.f90:48); the only
 !> non-polymorphic spot is the dummy of the `bands` constructor (bands.f90:121, `type(green), target`), which a maintainer
 !> changes to `class(green), target` (INTEGRATION.md).
+!>
+!> Intersite stage (green.f90:386-469): the 24 arrays `gij, gji, ginmag ... gz1ji` are (9|18, 9|18, channels_ldos + 10, pairs), about
+!> 0.1 GB per pair at 2500 energies.  The reference's `restore_to_default` allocates and zeroes them at construction; here they are
+!> allocated (and zeroed) only when a host routine that fills them runs (`intersite_arrays`).  When `exchange_gpu` (exchange_gpu.f90)
+!> has taken the stage over -- `rsrec_exchange` forms Jij / Dij / Iij straight from the recursion's chains -- `calculate_intersite_gf`
+!> and `_twoindex` allocate and fill nothing; the first keeps only the reference's side effect on the recursion (zsqr, :434).
 !------------------------------------------------------------------------------
 module green_gpu_mod
    use, intrinsic :: iso_c_binding
@@ -36,7 +42,14 @@ module green_gpu_mod
       logical :: defer_g0 = .false.
       logical :: g0_stale = .false.
       logical :: fetching = .false.   ! set by fetch_g0 around its own block_green call: the one caller that makes a deferred g0
+      !> .true. once exchange_gpu owns the intersite stage (its constructor, `release_intersite`)
+      logical :: intersite_on_device = .false.
    contains
+      procedure :: restore_to_default => gpu_restore_to_default
+      procedure :: calculate_intersite_gf => gpu_calculate_intersite_gf
+      procedure :: calculate_intersite_gf_twoindex => gpu_calculate_intersite_gf_twoindex
+      procedure :: calculate_intersite_gf_eta => gpu_calculate_intersite_gf_eta
+      procedure :: release_intersite => gpu_release_intersite
       procedure :: bgreen => gpu_bgreen
       procedure :: block_green => gpu_block_green
       procedure :: chebyshev_green => gpu_chebyshev_green
@@ -214,5 +227,96 @@ contains
       call g_timer%stop('chebyshev-green-gpu')
       if (rc /= 0) call g_logger%fatal('rsrec_chebyshev_green: '//rsrec_error_string(handle), __FILE__, __LINE__)
    end subroutine gpu_chebyshev_green
+
+   !> green.f90:186-313 without the pair x energy arrays `gij ... gz1ji`: `g0` and the `_eta` set as the reference allocates and zeroes
+   !> them; the others come with the first host routine that fills them (`intersite_arrays`).
+   subroutine gpu_restore_to_default(this)
+      use mpi_mod, only: atoms_per_process
+      class(green_gpu) :: this
+      integer :: nv, n
+      nv = this%en%channels_ldos + 10
+      n = atoms_per_process
+      if (this%lattice%njij == 0) then
+         allocate (this%g0(18, 18, nv, this%lattice%nrec))
+      else
+         allocate (this%g0(18, 18, nv, 4))
+      end if
+      allocate (this%gij_eta(64, 18, 18, n), this%gji_eta(64, 18, 18, n))
+      allocate (this%ginmag_eta(64, 9, 9, n), this%gjnmag_eta(64, 9, 9, n), this%gix_eta(64, 9, 9, n), this%giy_eta(64, 9, 9, n), &
+                this%giz_eta(64, 9, 9, n), this%gjx_eta(64, 9, 9, n), this%gjy_eta(64, 9, 9, n), this%gjz_eta(64, 9, 9, n))
+      this%g0(:, :, :, :) = (0.0d0, 0.0d0)
+      this%gij_eta(:, :, :, :) = (0.0d0, 0.0d0)
+      this%gji_eta(:, :, :, :) = (0.0d0, 0.0d0)
+      this%ginmag_eta(:, :, :, :) = (0.0d0, 0.0d0)
+      this%gjnmag_eta(:, :, :, :) = (0.0d0, 0.0d0)
+      this%gix_eta(:, :, :, :) = (0.0d0, 0.0d0)
+      this%giy_eta(:, :, :, :) = (0.0d0, 0.0d0)
+      this%giz_eta(:, :, :, :) = (0.0d0, 0.0d0)
+      this%gjx_eta(:, :, :, :) = (0.0d0, 0.0d0)
+      this%gjy_eta(:, :, :, :) = (0.0d0, 0.0d0)
+      this%gjz_eta(:, :, :, :) = (0.0d0, 0.0d0)
+   end subroutine gpu_restore_to_default
+
+   !> The pair x energy arrays of green.f90:208-263, allocated and zeroed as restore_to_default (:276-300) leaves them; a no-op once
+   !> they exist.
+   subroutine intersite_arrays(this)
+      use mpi_mod, only: atoms_per_process
+      class(green_gpu), intent(inout) :: this
+      integer :: nv, n
+      if (allocated(this%gij)) return
+      nv = this%en%channels_ldos + 10
+      n = atoms_per_process
+      allocate (this%gij(18, 18, nv, n), this%gji(18, 18, nv, n))
+      allocate (this%ginmag(9, 9, nv, n), this%gjnmag(9, 9, nv, n), this%gix(9, 9, nv, n), this%giy(9, 9, nv, n), this%giz(9, 9, nv, n), &
+                this%gjx(9, 9, nv, n), this%gjy(9, 9, nv, n), this%gjz(9, 9, nv, n))
+      allocate (this%g00ij(9, 9, nv, n), this%g00ji(9, 9, nv, n), this%g01ij(9, 9, nv, n), this%g01ji(9, 9, nv, n), &
+                this%gx0ij(9, 9, nv, n), this%gy0ij(9, 9, nv, n), this%gz0ij(9, 9, nv, n), this%gx1ij(9, 9, nv, n), &
+                this%gy1ij(9, 9, nv, n), this%gz1ij(9, 9, nv, n), this%gx0ji(9, 9, nv, n), this%gy0ji(9, 9, nv, n), &
+                this%gz0ji(9, 9, nv, n), this%gx1ji(9, 9, nv, n), this%gy1ji(9, 9, nv, n), this%gz1ji(9, 9, nv, n))
+      this%gij = 0.0d0; this%gji = 0.0d0
+      this%ginmag = 0.0d0; this%gjnmag = 0.0d0; this%gix = 0.0d0; this%giy = 0.0d0; this%giz = 0.0d0
+      this%gjx = 0.0d0; this%gjy = 0.0d0; this%gjz = 0.0d0
+      this%g00ij = 0.0d0; this%g00ji = 0.0d0; this%g01ij = 0.0d0; this%g01ji = 0.0d0
+      this%gx0ij = 0.0d0; this%gy0ij = 0.0d0; this%gz0ij = 0.0d0; this%gx1ij = 0.0d0; this%gy1ij = 0.0d0; this%gz1ij = 0.0d0
+      this%gx0ji = 0.0d0; this%gy0ji = 0.0d0; this%gz0ji = 0.0d0; this%gx1ji = 0.0d0; this%gy1ji = 0.0d0; this%gz1ji = 0.0d0
+   end subroutine intersite_arrays
+
+   !> Called by exchange_gpu's constructor: the intersite stage is done on the device from now on, and the host arrays go (if any).
+   subroutine gpu_release_intersite(this)
+      class(green_gpu), intent(inout) :: this
+      this%intersite_on_device = .true.
+      if (allocated(this%gij)) deallocate (this%gij, this%gji, this%ginmag, this%gjnmag, this%gix, this%giy, this%giz, this%gjx, &
+                                           this%gjy, this%gjz, this%g00ij, this%g00ji, this%g01ij, this%g01ji, this%gx0ij, this%gy0ij, &
+                                           this%gz0ij, this%gx1ij, this%gy1ij, this%gz1ij, this%gx0ji, this%gy0ji, this%gz0ji, &
+                                           this%gx1ji, this%gy1ji, this%gz1ji)
+   end subroutine gpu_release_intersite
+
+   !> green.f90:425-469.  With exchange_gpu behind the stage only its side effect on the recursion stays: b2_b <- sqrt(b2_b) for
+   !> block (:434), on the host arrays.  (rsrec_exchange reads the B^2 chains resident on the device and roots a copy of its own;
+   !> rsrec_zsqr works in a buffer of its own, so the resident chains are rooted once.)
+   subroutine gpu_calculate_intersite_gf(this)
+      class(green_gpu), intent(inout) :: this
+      if (this%intersite_on_device) then
+         if (this%control%recur == 'block') call this%recursion%zsqr()
+         return
+      end if
+      call intersite_arrays(this)
+      call this%green%calculate_intersite_gf()
+   end subroutine gpu_calculate_intersite_gf
+
+   !> green.f90:386-423: nothing to do when exchange_gpu owns the stage.
+   subroutine gpu_calculate_intersite_gf_twoindex(this)
+      class(green_gpu), intent(inout) :: this
+      if (this%intersite_on_device) return
+      call intersite_arrays(this)
+      call this%green%calculate_intersite_gf_twoindex()
+   end subroutine gpu_calculate_intersite_gf_twoindex
+
+   !> green.f90:471-536, inherited; its readers (exchange%calculate_exchange_gauss_legendre) may also read the arrays above.
+   subroutine gpu_calculate_intersite_gf_eta(this)
+      class(green_gpu), intent(inout) :: this
+      call intersite_arrays(this)
+      call this%green%calculate_intersite_gf_eta()
+   end subroutine gpu_calculate_intersite_gf_eta
 
 end module green_gpu_mod

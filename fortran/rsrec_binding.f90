@@ -161,6 +161,18 @@ module rsrec_binding
          integer(c_int) :: rc
       end function
 
+      ! exchange couplings of the rank's pairs: intersite g + Jij / Dij / Iij integrands + Simpson integrals (exchange.f90:1032-1615)
+      function rsrec_exchange(handle, kind, npairs, same, lld, nen, ene, nv1, fermi, sym_term, energy_min, energy_max, a_inf, b_inf, &
+                              coef_a, coef_b, dpar, pair_offset, npairs_total, xc, so, fo, parts, jcum, integrand) &
+         bind(C, name='rsrec_exchange') result(rc)
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: handle
+         integer(c_int), value :: kind, npairs, lld, nen, nv1, sym_term, pair_offset, npairs_total
+         real(c_double), value :: fermi, energy_min, energy_max
+         type(c_ptr), value :: same, ene, a_inf, b_inf, coef_a, coef_b, dpar, xc, so, fo, parts, jcum, integrand
+         integer(c_int) :: rc
+      end function
+
       function rsrec_kubo_moments(handle, nvec, nseed, seed_atoms, seed_coef, cond_ll, a, b, v_a, vo_a, v_b, vo_b, mu_nm) &
          bind(C, name='rsrec_kubo_moments') result(rc)
          import :: c_int, c_ptr, c_double
