@@ -46,6 +46,10 @@ struct Spmm4Operator {
     int ntau = 0, nslots = 0, have_o = 0;
     static constexpr int META = 5 * 2 * (1 + S4_MAXSLOTS);   // [share][pattern][count, slots...]; share 0 = all slots (one wave per group), 1..4 = the four cooperating waves
 
+    Spmm4Operator() = default;
+    Spmm4Operator(const Spmm4Operator&) = delete;            // owns its device tables
+    Spmm4Operator& operator=(const Spmm4Operator&) = delete;
+    ~Spmm4Operator() { release(); }
     void release() {
         if (d_frag) (void)hipFree(d_frag);
         if (d_meta) (void)hipFree(d_meta);

@@ -136,6 +136,10 @@ struct Spmm5Operator {
     std::vector<int> ksteps;       // [set][tau]: MFMA k-steps a wave runs per group (X, Y steps: 2, Z steps: 1)
     std::vector<signed char> mixing;   // [set][tau][nslots + 1]: -1 absent, 0 spin-diagonal block (one quadrant pair: 23 328 flop), 1 spin-mixing (46 656 flop)
 
+    Spmm5Operator() = default;
+    Spmm5Operator(const Spmm5Operator&) = delete;            // owns its device tables
+    Spmm5Operator& operator=(const Spmm5Operator&) = delete;
+    ~Spmm5Operator() { release(); }
     void release() {
         if (d_frag) (void)hipFree(d_frag);
         if (d_meta) (void)hipFree(d_meta);

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <hsa/hsa.h>
 #include <hsa/hsa_ext_amd.h>
+#include <dlfcn.h>
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -22,6 +23,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <thread>
 #include <tuple>
@@ -39,18 +41,22 @@
 #include "kernels_cond.hpp"
 #include "kernels_exchange.hpp"
 #include "kernels_assemble.hpp"
-#include <dlfcn.h>
 
 using namespace rsrec;
 
 namespace {
 
+// Owned device memory: freed when the owner goes (the handle, a region entry); moves, never copies.
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(bytes, o.bytes); return *this; }
+    ~DevBuf() { release(); }
     hipError_t reserve(size_t n) {
         if (n <= bytes) return hipSuccess;
-        if (p) { (void)hipFree(p); p = nullptr; bytes = 0; }
+        release();
         hipError_t e = hipMalloc(&p, n);
         if (e == hipSuccess) bytes = n;
         return e;
@@ -118,7 +124,7 @@ struct rsrec_handle {
     DevBuf d_bsqrt, d_term, d_gim, d_ldos;   // LDOS stage on resident coefficients: sqrt(B^2), terminators, Im g0_jj, output images
     void* pin = nullptr;              // pinned host staging buffer: every per-call transfer goes through it (see xfer_*)
     size_t pin_bytes = 0;
-    DevBuf d_frags, d_vec[6], d_order, d_cum, d_partial, d_partial2, d_coefA, d_coefB, d_bmats, d_status, d_seed, d_seedcoef, d_mu, d_scal, d_zsqr;
+    DevBuf d_frags, d_vec[6], d_partial, d_partial2, d_coefA, d_coefB, d_bmats, d_status, d_seed, d_seedcoef, d_mu, d_scal, d_zsqr;
     // options
     long opt_batch = 0, opt_kernels = 0, opt_nblk = 0, opt_spmm5 = 2, opt_chain_fold = 1, opt_s5_cap = 0, opt_side = 1, opt_s5_lds = 1, opt_s5_queue = 1, opt_cheb_fused = 1;
     long opt_s5_waves = 8;
@@ -162,7 +168,7 @@ struct rsrec_handle {
         std::vector<int> level_sat;         // per level: chains of this entry that use that list
         int sat_base = 0;                   // its offset inside an order row
     };
-    std::vector<RegionEntry*> region_cache;
+    std::vector<std::unique_ptr<RegionEntry>> region_cache;
     int lattice_epoch = 0;
     const int* cur_order = nullptr;
     const int* cur_cum = nullptr;     // [nrows][nlev] counts, [nrows][nlev] list offsets (the lists of H|psi>), then the same two tables for the streaming passes
@@ -179,10 +185,37 @@ struct rsrec_handle {
     void* comm = nullptr;
     int comm_rank = 0, comm_nranks = 1;
     DevBuf d_comm;               // staging buffer of rsrec_allreduce_sum on host arrays
+    ~rsrec_handle();
 };
 
 namespace {
 
+// Every option of rsrec_set_option, once: the key is looked up here, and the captured level loop is keyed by all of them (see run_block_lanczos).
+struct OptionEntry { const char* name; long rsrec_handle::*member; };
+const OptionEntry OPTIONS[] = {
+    {"batch", &rsrec_handle::opt_batch},
+    {"kernels", &rsrec_handle::opt_kernels},
+    {"nblk", &rsrec_handle::opt_nblk},
+    {"spmm5", &rsrec_handle::opt_spmm5},
+    {"chain_fold", &rsrec_handle::opt_chain_fold},
+    {"s5_cap", &rsrec_handle::opt_s5_cap},
+    {"s5_lds", &rsrec_handle::opt_s5_lds},
+    {"s5_queue", &rsrec_handle::opt_s5_queue},
+    {"cheb_fused", &rsrec_handle::opt_cheb_fused},
+    {"side_stream", &rsrec_handle::opt_side},
+    {"graph", &rsrec_handle::opt_graph},
+    {"orth3", &rsrec_handle::opt_orth3},
+    {"s5_waves", &rsrec_handle::opt_s5_waves},
+    {"s5_split", &rsrec_handle::opt_s5_split},
+    {"orth_oop", &rsrec_handle::opt_orth_oop},
+    {"sat_pct", &rsrec_handle::opt_sat_pct},
+    {"kubo_lchunk", &rsrec_handle::opt_kubo_lchunk},
+    {"kubo_vbatch", &rsrec_handle::opt_kubo_vbatch},
+    {"s5_host_emit", &rsrec_handle::opt_s5_host_emit},
+    {"s5_octet", &rsrec_handle::opt_s5_octet},
+    {"s5_spin_xcd", &rsrec_handle::opt_s5_spin_xcd},
+    {"s5_run_min", &rsrec_handle::opt_s5_run_min},
+};
 
 int fail(rsrec_t* h, int code, const char* fmt, ...) {
     char buf[512];
@@ -296,10 +329,6 @@ void grow_region(const rsrec_t* h, const int* seeds, int nseed, int nlev, Region
     R.order.resize(kk, 0);   // tail is never read (cum bounds every loop)
 }
 
-}  // namespace
-
-namespace {
-
 inline unsigned spread3(unsigned v) {           // 10 bits -> every third bit
     v &= 1023u;
     v = (v | (v << 16)) & 0x030000FFu;
@@ -388,33 +417,22 @@ extern "C" int rsrec_create(rsrec_t** out, int device) {
     return RSREC_OK;
 }
 
+// Every hipFree of the handle happens in here or in the members' destructors right behind it, with the handle's device current.  Also
+// safe on a handle that never got its stream (rsrec_create's early delete): nothing below touches the device then.
+rsrec_handle::~rsrec_handle() {
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+    if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
+    (void)rsrec_comm_destroy(this);
+    for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
+    for (hipStream_t s : {stream, copy_stream, side_stream, oct_stream}) if (s) (void)hipStreamDestroy(s);
+    for (hipEvent_t e : {ev_green[0], ev_green[1], ev_orth, ev_bred, ev_oct_in, ev_oct_out}) if (e) (void)hipEventDestroy(e);
+    if (pin) (void)hipHostFree(pin);
+}
+
 extern "C" int rsrec_destroy(rsrec_t* h) {
     if (!h) return RSREC_ERR_ARG;
     if (g_report_handle == h) { report_at_exit(); g_report_handle = nullptr; }
-    (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    (void)rsrec_comm_destroy(h);
-    h->d_comm.release();
-    for (auto e : h->ev_pool) (void)hipEventDestroy(e);
-    DevBuf* all[] = {&h->d_bsqrt, &h->d_term, &h->d_gim, &h->d_ldos, &h->d_green_in, &h->d_green_out, &h->d_kubo[0], &h->d_kubo[1], &h->d_kubo[2], &h->d_kubo[3], &h->d_kubo[4], &h->d_cond[0], &h->d_cond[1], &h->d_cond[2], &h->d_cond[3], &h->d_nbr, &h->d_nbr5, &h->d_s5queue, &h->d_iz, &h->d_hst, &h->d_hloc, &h->d_host, &h->d_holoc, &h->d_enim, &h->d_lsham, &h->d_vec[0], &h->d_vec[1],
-                     &h->d_vec[2], &h->d_vec[3], &h->d_vec[4], &h->d_vec[5], &h->d_order, &h->d_cum, &h->d_partial, &h->d_partial2, &h->d_coefA, &h->d_coefB, &h->d_bmats,
-                     &h->d_status, &h->d_frags, &h->d_seed, &h->d_seedcoef, &h->d_mu, &h->d_scal, &h->d_zsqr};
-    for (auto b : all) b->release();
-    for (auto* e : h->region_cache) { e->order.release(); e->cum.release(); delete e; }
-    h->s4_op.release();
-    h->s5_op.release();
-    h->kubo_op[0].release(); h->kubo_op[1].release(); h->kubo_hbulk.release(); h->orb_plain.release(); h->s5_la.release(); h->d_la_extra.release();
-    if (h->pin) (void)hipHostFree(h->pin);
-    (void)hipStreamDestroy(h->stream);
-    if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
-    for (hipEvent_t e : h->ev_green) if (e) (void)hipEventDestroy(e);
-    if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
-    if (h->side_stream) (void)hipStreamDestroy(h->side_stream);
-    if (h->oct_stream) (void)hipStreamDestroy(h->oct_stream);
-    if (h->ev_oct_in) (void)hipEventDestroy(h->ev_oct_in);
-    if (h->ev_oct_out) (void)hipEventDestroy(h->ev_oct_out);
-    if (h->ev_orth) (void)hipEventDestroy(h->ev_orth);
-    if (h->ev_bred) (void)hipEventDestroy(h->ev_bred);
     delete h;
     return RSREC_OK;
 }
@@ -427,30 +445,9 @@ extern "C" int rsrec_last_error(rsrec_t* h, char* buf, size_t n) {
 
 extern "C" int rsrec_set_option(rsrec_t* h, const char* key, long value) {
     if (!h || !key) return RSREC_ERR_ARG;
-    if (!strcmp(key, "batch")) h->opt_batch = value;
-    else if (!strcmp(key, "kernels")) h->opt_kernels = value;
-    else if (!strcmp(key, "nblk")) h->opt_nblk = value;
-    else if (!strcmp(key, "spmm5")) h->opt_spmm5 = value;
-    else if (!strcmp(key, "chain_fold")) h->opt_chain_fold = value;
-    else if (!strcmp(key, "s5_cap")) h->opt_s5_cap = value;
-    else if (!strcmp(key, "s5_lds")) h->opt_s5_lds = value;
-    else if (!strcmp(key, "s5_queue")) h->opt_s5_queue = value;
-    else if (!strcmp(key, "cheb_fused")) h->opt_cheb_fused = value;
-    else if (!strcmp(key, "side_stream")) h->opt_side = value;
-    else if (!strcmp(key, "graph")) h->opt_graph = value;
-    else if (!strcmp(key, "orth3")) h->opt_orth3 = value;
-    else if (!strcmp(key, "s5_waves")) h->opt_s5_waves = value;
-    else if (!strcmp(key, "s5_split")) h->opt_s5_split = value;
-    else if (!strcmp(key, "orth_oop")) h->opt_orth_oop = value;
-    else if (!strcmp(key, "sat_pct")) h->opt_sat_pct = value;
-    else if (!strcmp(key, "kubo_lchunk")) h->opt_kubo_lchunk = value;
-    else if (!strcmp(key, "kubo_vbatch")) h->opt_kubo_vbatch = value;
-    else if (!strcmp(key, "s5_host_emit")) h->opt_s5_host_emit = value;
-    else if (!strcmp(key, "s5_octet")) h->opt_s5_octet = value;
-    else if (!strcmp(key, "s5_spin_xcd")) h->opt_s5_spin_xcd = value;
-    else if (!strcmp(key, "s5_run_min")) h->opt_s5_run_min = value;
-    else return fail(h, RSREC_ERR_ARG, "unknown option '%s'", key);
-    return RSREC_OK;
+    for (const OptionEntry& o : OPTIONS)
+        if (!strcmp(key, o.name)) { h->*o.member = value; return RSREC_OK; }
+    return fail(h, RSREC_ERR_ARG, "unknown option '%s'", key);
 }
 
 extern "C" int rsrec_get_timing(rsrec_t* h, double* out, int n) {
@@ -472,7 +469,6 @@ extern "C" void rsrec_site_partition(int rank, int nprocs, int nsites, int* star
     *end_atom = start + per - 1;
 }
 
-// cached regions (device order lists) of lattice epochs that ended; the stream is idle between calls
 static void release_graph(rsrec_t* h) {
     if (h->graph_exec) { (void)hipDeviceSynchronize(); (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
     h->graph_key.clear();
@@ -484,7 +480,6 @@ static void release_graph(rsrec_t* h) {
 static void release_regions(rsrec_t* h) {
     release_graph(h);
     if (!h->region_cache.empty()) (void)hipDeviceSynchronize();
-    for (auto* e : h->region_cache) { e->order.release(); e->cum.release(); delete e; }
     h->region_cache.clear();
     h->cur_order = nullptr; h->cur_cum = nullptr; h->cur_entry = nullptr; h->cur_level_max = nullptr; h->cur_level_groups = nullptr; h->cur_mult_hist = nullptr;
 }
@@ -761,12 +756,12 @@ int upload_regions(rsrec_t* h, const int* seeds0, int nb, int nseed, int nlev, i
     const int cap = grouped ? kk + 7 * h->nmax + 7 * h->ntype + 8 : kk;          // capacity of one list of all atoms
     const int cap_pre = ((grouped ? kk + 7 * h->nmax + 7 * h->ntype * nlev + 8 : kk) + GROUP - 1) / GROUP * GROUP;   // capacity of the level-major list (a multiple of 8: every list starts on a group border)
     const int flags = (two_pass ? 1 : 0) | (grouped ? 2 : 0) | ((int)std::min<long>(100, std::max<long>(1, h->opt_sat_pct)) << 2) | (nseed << 9);
-    for (auto* e : h->region_cache)
+    for (const auto& e : h->region_cache)
         if (e->epoch == h->lattice_epoch && e->nlev == nlev && e->napply == napply && e->flags == flags && (int)e->seeds.size() == nb * nseed &&
             std::equal(e->seeds.begin(), e->seeds.end(), seeds0)) {
             h->cur_order = e->order.as<int>(); h->cur_cum = e->cum.as<int>(); h->cur_nrows = nb; h->cur_level_max = &e->level_max; h->cur_level_groups = &e->level_groups;
             h->cur_mult_hist = &e->mult_hist;
-            h->cur_entry = e;
+            h->cur_entry = e.get();
             ostride = e->ostride;
             atom_steps += e->atom_steps; block_mults += e->block_mults;
             return RSREC_OK;
@@ -911,18 +906,17 @@ int upload_regions(rsrec_t* h, const int* seeds0, int nb, int nseed, int nlev, i
     atom_steps += as_sum; block_mults += bm_sum;
     if (h->region_cache.size() >= 256) {          // bounded: drop everything (the engine is idle between calls)
         HIPCK(h, hipStreamSynchronize(h->stream));
-        for (auto* e : h->region_cache) { e->order.release(); e->cum.release(); delete e; }
         h->region_cache.clear();
         h->cur_entry = nullptr;
     }
-    auto* e = new rsrec_handle::RegionEntry();
+    h->region_cache.push_back(std::make_unique<rsrec_handle::RegionEntry>());
+    rsrec_handle::RegionEntry* e = h->region_cache.back().get();
     e->seeds.assign(seeds0, seeds0 + (size_t)nb * nseed);
     e->nlev = nlev; e->napply = napply; e->flags = flags; e->epoch = h->lattice_epoch; e->ostride = ostride;
     e->atom_steps = as_sum; e->block_mults = bm_sum;
     e->mult_hist.assign(hist_n, 0.0);
     for (int c = 0; c < nb; ++c)
         for (size_t q = 0; q < hist_n; ++q) e->mult_hist[q] += hist[(size_t)c * hist_n + q];
-    h->region_cache.push_back(e);
     HIPCK(h, e->order.reserve(order.size() * 4));
     HIPCK(h, e->cum.reserve(cum.size() * 4));
     XFER(xfer_h2d(h, e->order.p, order.data(), order.size() * 4));
@@ -1003,11 +997,61 @@ int check_ready(rsrec_t* h, const char* who) {
     return RSREC_OK;
 }
 
-}  // namespace
+// seed atoms of a call as the caller numbers them: lo..kk (1-based; rsrec_kubo_moments also takes 0 = unused entry)
+int check_seeds(rsrec_t* h, const char* who, const int32_t* atoms, size_t n, int lo) {
+    for (size_t q = 0; q < n; ++q)
+        if (atoms[q] < lo || atoms[q] > h->kk) return fail(h, RSREC_ERR_ARG, "%s: seed atom %d outside %d..%d", who, atoms[q], lo, h->kk);
+    return RSREC_OK;
+}
+
+// the seeds of chains c0 .. c0 + nb - 1 as the kernels take them: 0-based atoms, complex coefficients (1 where the caller gives none)
+void stage_seeds(const int32_t* seed_atoms, const double* seed_coef, int c0, int nb, int nseed, std::vector<int>& seeds0, std::vector<double>& coef) {
+    const size_t n = (size_t)nb * nseed, g0 = (size_t)c0 * nseed;
+    seeds0.resize(n);
+    coef.resize(2 * n);
+    for (size_t q = 0; q < n; ++q) {
+        seeds0[q] = seed_atoms[g0 + q] - 1;
+        coef[2 * q] = seed_coef ? seed_coef[2 * (g0 + q)] : 1.0;
+        coef[2 * q + 1] = seed_coef ? seed_coef[2 * (g0 + q) + 1] : 0.0;
+    }
+}
+
+// the side stream and the two events that tie it to the main stream, created when a recursion first runs
+int ensure_side_stream(rsrec_t* h) {
+    if (h->side_stream) return RSREC_OK;
+    HIPCK(h, hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking));
+    HIPCK(h, hipEventCreateWithFlags(&h->ev_orth, hipEventDisableTiming));
+    HIPCK(h, hipEventCreateWithFlags(&h->ev_bred, hipEventDisableTiming));
+    return RSREC_OK;
+}
+
+// Partial sums of a batch of B chains: the first stage as the caller sizes it, the second stage (presum) in two slots -- slot 1 is the side
+// stream's -- sized once, never grown mid-stream.  p2_slot decides which reductions take the two-stage path, and with it their rounding.
+int reserve_partials(rsrec_t* h, int B, size_t first_stage_bytes) {
+    HIPCK(h, h->d_partial.reserve(first_stage_bytes));
+    h->p2_slot = (size_t)B * 16 * 2 * 1296;
+    HIPCK(h, h->d_partial2.reserve(2 * h->p2_slot * sizeof(double)));
+    return RSREC_OK;
+}
+
+// the lists of the region entry upload_regions made current, as the kernels walk them: CV the per-level lists of H|psi>, CVp (where asked
+// for) the level-major lists of the streaming passes behind it
+void chain_views(const rsrec_t* h, int nlev, size_t velems, int cpo, int ostride, ChainView& CV, ChainView* CVp = nullptr) {
+    const size_t tab = (size_t)h->cur_nrows * nlev;
+    CV.order = h->cur_order; CV.cum = h->cur_cum; CV.obase = h->cur_cum + tab; CV.nlev = nlev; CV.vstride = velems; CV.cpo = cpo; CV.ostride = ostride;
+    if (!CVp) return;
+    *CVp = CV;
+    CVp->cum = h->cur_cum + 2 * tab; CVp->obase = h->cur_cum + 3 * tab;
+}
+
+// timing of a call from its events: the whole call, the H|psi> kernels (or whatever hop_ev brackets), and the rest
+void finish_timing(rsrec_t* h, hipEvent_t ev_begin, hipEvent_t ev_end, const std::vector<std::pair<hipEvent_t, hipEvent_t>>& hop_ev) {
+    h->t_total_ms = ev_ms(ev_begin, ev_end);
+    for (auto& pr : hop_ev) h->t_hop_ms += ev_ms(pr.first, pr.second);
+    h->t_rest_ms = h->t_total_ms - h->t_hop_ms;
+}
 
 // ------------------------------------------------------------------------------------------------------------------
-namespace {
-
 // Workgroups per chain of the matrix-core post-hop kernels (Gram, orthogonalisation, Chebyshev step): they hold their 36x36
 // coefficient tables in registers and run one wave per SIMD, so long-lived waves win -- about two workgroups per CU over
 // the whole batch (measured at 64 chains: 8 per chain 4.3 ms per level, 64 per chain 5.0 ms).  Three fixed bands, so that the
@@ -1288,14 +1332,8 @@ int run_block_lanczos(rsrec_t* h, int nchains, int nseed, const int32_t* seed_at
     const int B = bp.batch, nblk = bp.nblk;
     for (int v = 0; v < nvec; ++v) if (v != 1 || use_v1) HIPCK(h, h->d_vec[v].reserve((size_t)B * velems * sizeof(double)));
     const size_t gram_elems = (size_t)B * 256 * 1296;                                  // doubles: Gram partials of one kernel (<= 256 workgroups per chain)
-    HIPCK(h, h->d_partial.reserve(std::max((size_t)B * std::max(nblk * 2, 256) * 2 * BLK * sizeof(double2), 2 * gram_elems * sizeof(double))));
-    h->p2_slot = (size_t)B * 16 * 2 * 1296;
-    HIPCK(h, h->d_partial2.reserve(2 * h->p2_slot * sizeof(double)));                  // second stage of the partial sums (presum), two slots: sized once, never grown mid-stream
-    if (!h->side_stream) {
-        HIPCK(h, hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking));
-        HIPCK(h, hipEventCreateWithFlags(&h->ev_orth, hipEventDisableTiming));
-        HIPCK(h, hipEventCreateWithFlags(&h->ev_bred, hipEventDisableTiming));
-    }
+    XFER(reserve_partials(h, B, std::max((size_t)B * std::max(nblk * 2, 256) * 2 * BLK * sizeof(double2), 2 * gram_elems * sizeof(double))));
+    XFER(ensure_side_stream(h));
     HIPCK(h, h->d_frags.reserve((size_t)B * 3 * 27 * 64 * sizeof(double)));
     HIPCK(h, h->d_bmats.reserve((size_t)B * 2 * BLK * sizeof(double2)));
     HIPCK(h, h->d_status.reserve(64));
@@ -1323,13 +1361,9 @@ int run_block_lanczos(rsrec_t* h, int nchains, int nseed, const int32_t* seed_at
         double2* dA = h->d_coefA.as<double2>() + (size_t)c0 * cstride;       // this batch's slice of the resident coefficients
         double2* dB = h->d_coefB.as<double2>() + (size_t)c0 * cstride;
         const auto th0 = std::chrono::steady_clock::now();
-        std::vector<int> seeds0((size_t)nb * nseed);
-        std::vector<double> coef((size_t)nb * nseed * 2);
-        for (int q = 0; q < nb * nseed; ++q) {
-            seeds0[q] = seed_atoms[(size_t)c0 * nseed + q] - 1;
-            coef[2 * q] = seed_coef ? seed_coef[2 * ((size_t)c0 * nseed + q)] : 1.0;
-            coef[2 * q + 1] = seed_coef ? seed_coef[2 * ((size_t)c0 * nseed + q) + 1] : 0.0;
-        }
+        std::vector<int> seeds0;
+        std::vector<double> coef;
+        stage_seeds(seed_atoms, seed_coef, c0, nb, nseed, seeds0, coef);
         int ostride = kk;
         rc = upload_regions(h, seeds0.data(), nb, nseed, nlev, nsteps, hoh, MFMA, ostride, h->n_atom_steps, h->n_block_mult);
         if (rc) return rc;
@@ -1373,10 +1407,8 @@ int run_block_lanczos(rsrec_t* h, int nchains, int nseed, const int32_t* seed_at
         HIPCK(h, hipStreamSynchronize(h->stream));
         h->t_host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - th0).count();
 
-        ChainView CV;
-        CV.order = h->cur_order; CV.cum = h->cur_cum; CV.obase = h->cur_cum + (size_t)h->cur_nrows * nlev; CV.nlev = nlev; CV.vstride = velems; CV.cpo = 1; CV.ostride = ostride;
-        ChainView CVp = CV;                                   // the streaming passes walk the level-major lists (upload_regions)
-        CVp.cum = h->cur_cum + (size_t)2 * h->cur_nrows * nlev; CVp.obase = h->cur_cum + (size_t)3 * h->cur_nrows * nlev;
+        ChainView CV, CVp;                                    // CVp: the streaming passes walk the level-major lists (upload_regions)
+        chain_views(h, nlev, velems, 1, ostride, CV, &CVp);
         // Everything from here to the coefficients' download is stream work only (kernels, memsets, cross-stream events): for small
         // batches it is captured ONCE as a HIP graph and replayed by every later call with the same lattice, seeds, depth and buffers
         // (each SCF iteration of the reference: recur_b on the same <= 4 sites) -- 49 levels x 6-8 dependent launches otherwise cost
@@ -1494,11 +1526,13 @@ int run_block_lanczos(rsrec_t* h, int nchains, int nseed, const int32_t* seed_at
                                           (uintptr_t)h->s4_op.frag_set(0), (uintptr_t)h->s4_op.meta_set(0), (uintptr_t)h->d_nbr.p, (uintptr_t)h->d_nbr5.p, (uintptr_t)h->d_iz.p,
                                           (uintptr_t)h->d_partial.p, (uintptr_t)h->d_partial2.p, (uintptr_t)h->d_frags.p, (uintptr_t)dA, (uintptr_t)dB, (uintptr_t)h->d_bmats.p,
                                           (uintptr_t)h->d_status.p, (uintptr_t)h->d_seed.p, (uintptr_t)h->d_seedcoef.p, (uintptr_t)h->d_la_extra.p, (uintptr_t)h->d_s5queue.p,
-                                          (uintptr_t)h->opt_side, (uintptr_t)h->opt_orth3, (uintptr_t)h->opt_orth_oop, (uintptr_t)h->opt_nblk, (uintptr_t)h->opt_spmm5, (uintptr_t)h->opt_s5_lds, (uintptr_t)h->opt_s5_queue, (uintptr_t)h->opt_s5_run_min, (uintptr_t)h->cur_entry,
-                                          (uintptr_t)h->opt_chain_fold, (uintptr_t)h->opt_s5_cap, (uintptr_t)h->p2_slot, (uintptr_t)OP.single_class(0), (uintptr_t)OP.spin_mixing, (uintptr_t)h->opt_s5_octet, (uintptr_t)h->opt_s5_spin_xcd,
+                                          (uintptr_t)h->cur_entry, (uintptr_t)h->p2_slot, (uintptr_t)OP.single_class(0), (uintptr_t)OP.spin_mixing,
                                           (uintptr_t)h->lattice_epoch, (uintptr_t)OP.sched_epoch, (uintptr_t)h->nslots, (uintptr_t)h->nmax, (uintptr_t)h->ntype, (uintptr_t)h->hslots,
-                                          (uintptr_t)h->opt_s5_waves, (uintptr_t)h->opt_s5_split, (uintptr_t)h->opt_batch, (uintptr_t)B, (uintptr_t)h->opt_kernels, (uintptr_t)h->n_cu};
+                                          (uintptr_t)B, (uintptr_t)h->n_cu};
             for (int v = 0; v < nvec; ++v) key.push_back((uintptr_t)h->d_vec[v].p);
+            // ... and every option: launch shapes and kernel choices follow them (all but `graph`, which only decides whether this path is taken)
+            for (const OptionEntry& o : OPTIONS)
+                if (o.member != &rsrec_handle::opt_graph) key.push_back((uintptr_t)(h->*o.member));
             if (!h->graph_exec || key != h->graph_key) {
                 if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
                 h->graph_key.clear();
@@ -1527,9 +1561,7 @@ int run_block_lanczos(rsrec_t* h, int nchains, int nseed, const int32_t* seed_at
     }
     hipEvent_t ev_end = next_event(h);
     HIPCK(h, hipStreamSynchronize(h->stream));
-    h->t_total_ms = ev_ms(ev_begin, ev_end);
-    for (auto& pr : hop_ev) h->t_hop_ms += ev_ms(pr.first, pr.second);
-    h->t_rest_ms = h->t_total_ms - h->t_hop_ms;
+    finish_timing(h, ev_begin, ev_end, hop_ev);
     int status = 0;
     XFER(xfer_d2h(h, &status, h->d_status.p, 4));
     if (status & 1) return fail(h, RSREC_ERR_EIG, "Diagonalization error (18x18 Jacobi did not converge)");
@@ -1544,8 +1576,7 @@ extern "C" int rsrec_block_lanczos_seeded(rsrec_t* h, int nchains, int nseed, co
     int rc = check_ready(h, "rsrec_block_lanczos");
     if (rc) return rc;
     if (nchains < 0 || nseed < 1 || lld < 1 || !a_b || !b2_b || (nchains > 0 && !seed_atoms)) return fail(h, RSREC_ERR_ARG, "rsrec_block_lanczos: bad argument");
-    for (int q = 0; q < nchains * nseed; ++q)
-        if (seed_atoms[q] < 1 || seed_atoms[q] > h->kk) return fail(h, RSREC_ERR_ARG, "rsrec_block_lanczos: seed atom %d outside 1..%d", seed_atoms[q], h->kk);
+    XFER(check_seeds(h, "rsrec_block_lanczos", seed_atoms, (size_t)nchains * nseed, 1));
     HIPCK(h, hipSetDevice(h->device));
     reset_timing(h);
     if (nchains == 0) return RSREC_OK;
@@ -1604,8 +1635,7 @@ extern "C" int rsrec_block_lanczos_local_axis(rsrec_t* h, int nsites, const int3
     int rc = check_ready(h, "rsrec_block_lanczos_local_axis");
     if (rc) return rc;
     if (nsites < 0 || lld < 1 || !a_b || !b2_b || (nsites > 0 && (!seed_atoms || !rot))) return fail(h, RSREC_ERR_ARG, "rsrec_block_lanczos_local_axis: bad argument");
-    for (int q = 0; q < nsites; ++q)
-        if (seed_atoms[q] < 1 || seed_atoms[q] > h->kk) return fail(h, RSREC_ERR_ARG, "rsrec_block_lanczos_local_axis: seed atom %d outside 1..%d", seed_atoms[q], h->kk);
+    XFER(check_seeds(h, "rsrec_block_lanczos_local_axis", seed_atoms, (size_t)nsites, 1));
     if (!h->s5_built) return fail(h, RSREC_ERR_ARG, "rsrec_block_lanczos_local_axis: lattice has too many neighbour slots for the SpMM kernel");
     HIPCK(h, hipSetDevice(h->device));
     reset_timing(h);
@@ -2128,9 +2158,7 @@ extern "C" int rsrec_block_ldos(rsrec_t* h, int nen, const double* ene, double e
     int status = 0;
     XFER(xfer_d2h(h, &status, h->d_status.p, 4));
     HIPCK(h, hipStreamSynchronize(h->stream));
-    h->t_total_ms = ev_ms(e0, e1);
-    h->t_hop_ms = ev_ms(k0, k1);                      // the Green kernel alone
-    h->t_rest_ms = h->t_total_ms - h->t_hop_ms;       // zsqr + terminator + reduction
+    finish_timing(h, e0, e1, {{k0, k1}});             // hop: the Green kernel alone; rest: zsqr + terminator + reduction
     if (status & 1) return fail(h, RSREC_ERR_EIG, "Diagonalization error (18x18 Jacobi did not converge)");
     return RSREC_OK;
 }
@@ -2357,7 +2385,6 @@ int run_chebyshev(rsrec_t* h, int nsites, int nseed, const int32_t* seed_atoms, 
     const size_t velems = (size_t)(kk + 1) * BLD;
     // matrix-core set: k_mfma_cheb epilogue; large launches and hoh use k_spmm5 on CI vectors, small launches of the plain
     // operator the cooperative k_spmm4<4> on LayoutRM
-    const bool mf_cheb = MFMA;
     const bool use_kp = MFMA && (hoh || h->opt_spmm5 == 2 || (h->opt_spmm5 == 1 && (long)std::min(nsites, 64) * (kk / GROUP + 1) >= 4096) || !spmm4_usable(h));
     const int nvec = MFMA ? (hoh ? 5 : 4) : (hoh ? 4 : 3);
     const int ci = use_kp ? 1 : 0;                              // vectors of this call are CI (else LayoutRM / LayoutCM)
@@ -2368,20 +2395,14 @@ int run_chebyshev(rsrec_t* h, int nsites, int nseed, const int32_t* seed_atoms, 
     HIPCK(h, h->d_mu.reserve((size_t)nsites * nmom * BLK * sizeof(double2)));
     // with the Chebyshev step fused into the SpMM's epilogue (the default of the matrix-core set) H psi is never held: vector 3 is neither
     // allocated nor cleared
-    const bool use_v3 = !(mf_cheb && (hoh || use_kp) && h->opt_cheb_fused);
+    const bool use_v3 = !(MFMA && (hoh || use_kp) && h->opt_cheb_fused);
     BatchPlan bp;
     rc = plan_batch(h, nsites, nvec - (use_v3 ? 0 : 1), velems / 2, bp);
     if (rc) return rc;
     const int B = bp.batch, nblk = bp.nblk;
     for (int v = 0; v < nvec; ++v) if (v != 3 || use_v3) HIPCK(h, h->d_vec[v].reserve((size_t)B * velems * sizeof(double)));
-    HIPCK(h, h->d_partial.reserve(std::max((size_t)B * nblk * 2 * BLK * sizeof(double2), (size_t)B * 256 * 2 * 1296 * sizeof(double))));
-    h->p2_slot = (size_t)B * 16 * 2 * 1296;
-    HIPCK(h, h->d_partial2.reserve(2 * h->p2_slot * sizeof(double)));
-    if (!h->side_stream) {
-        HIPCK(h, hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking));
-        HIPCK(h, hipEventCreateWithFlags(&h->ev_orth, hipEventDisableTiming));
-        HIPCK(h, hipEventCreateWithFlags(&h->ev_bred, hipEventDisableTiming));
-    }
+    XFER(reserve_partials(h, B, std::max((size_t)B * nblk * 2 * BLK * sizeof(double2), (size_t)B * 256 * 2 * 1296 * sizeof(double))));
+    XFER(ensure_side_stream(h));
     const bool side = h->opt_side && h->side_stream;     // moment reduction of level t under the SpMM of level t + 1 (it feeds nothing on the device)
     bool red_pending = false;
     HIPCK(h, h->d_status.reserve(64));
@@ -2396,16 +2417,12 @@ int run_chebyshev(rsrec_t* h, int nsites, int nseed, const int32_t* seed_atoms, 
         const int nb = std::min(B, nsites - c0);
         double2* mu = h->d_mu.as<double2>() + (size_t)c0 * mstride;       // this batch's slice of the resident moments
         const auto th0 = std::chrono::steady_clock::now();
-        std::vector<int> seeds0((size_t)nb * nseed);
-        std::vector<double> coef((size_t)nb * nseed * 2 + nb);     // coefficients, then one mu_1 scale per chain
+        std::vector<int> seeds0;
+        std::vector<double> coef;
+        stage_seeds(seed_atoms, seed_coef, c0, nb, nseed, seeds0, coef);
+        coef.resize((size_t)nb * nseed * 2 + nb);                  // coefficients, then one mu_1 scale per chain
         for (int c = 0; c < nb; ++c) {
             double m0 = 0.0;
-            for (int k = 0; k < nseed; ++k) {
-                const size_t q = (size_t)c * nseed + k, g = (size_t)(c0 + c) * nseed + k;
-                seeds0[q] = seed_atoms[g] - 1;
-                coef[2 * q] = seed_coef ? seed_coef[2 * g] : 1.0;
-                coef[2 * q + 1] = seed_coef ? seed_coef[2 * g + 1] : 0.0;
-            }
             // mu_1 = sum over seed atoms of |final coefficient|^2 (later seeds overwrite earlier ones on the same atom)
             for (int k = 0; k < nseed; ++k) {
                 bool overwritten = false;
@@ -2423,10 +2440,8 @@ int run_chebyshev(rsrec_t* h, int nsites, int nseed, const int32_t* seed_atoms, 
         XFER(xfer_h2d(h, h->d_seedcoef.p, coef.data(), coef.size() * 8));
         HIPCK(h, hipStreamSynchronize(h->stream));
         h->t_host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - th0).count();
-        ChainView CV;
-        CV.order = h->cur_order; CV.cum = h->cur_cum; CV.obase = h->cur_cum + (size_t)h->cur_nrows * nlev; CV.nlev = nlev; CV.vstride = velems; CV.cpo = 1; CV.ostride = ostride;
-        ChainView CVp = CV;                                   // the streaming moment pass walks the level-major lists (upload_regions)
-        CVp.cum = h->cur_cum + (size_t)2 * h->cur_nrows * nlev; CVp.obase = h->cur_cum + (size_t)3 * h->cur_nrows * nlev;
+        ChainView CV, CVp;                                    // CVp: the streaming moment pass walks the level-major lists (upload_regions)
+        chain_views(h, nlev, velems, 1, ostride, CV, &CVp);
         for (int v = 0; v < nvec; ++v) if (v != 3 || use_v3) HIPCK(h, hipMemsetAsync(h->d_vec[v].p, 0, (size_t)nb * velems * sizeof(double), h->stream));
         HIPCK(h, hipMemsetAsync(mu, 0, (size_t)nb * mstride * sizeof(double2), h->stream));
         double* p0 = h->d_vec[0].as<double>();
@@ -2449,7 +2464,7 @@ int run_chebyshev(rsrec_t* h, int nsites, int nseed, const int32_t* seed_atoms, 
             G.a = a; G.b = b;
             double* src = first ? p0 : p1;
             double* dst = first ? p1 : p2;
-            if (mf_cheb) {
+            if (MFMA) {
                 SpmmDims SD{kk, P.nslots, P.nmax, nlev, 1, ostride, lv_final, velems, CV.obase, nb};
                 const dim3 gl = level_grid(h, grid_mf, lv_final);
                 // k_spmm5 forms the new vector in its epilogue (dst = (H src - b src)/a [* 2 - p0]); k_mfma_cheb then only sums the Grams
@@ -2509,9 +2524,7 @@ int run_chebyshev(rsrec_t* h, int nsites, int nseed, const int32_t* seed_atoms, 
     }
     hipEvent_t ev_end = next_event(h);
     HIPCK(h, hipStreamSynchronize(h->stream));
-    h->t_total_ms = ev_ms(ev_begin, ev_end);
-    for (auto& pr : hop_ev) h->t_hop_ms += ev_ms(pr.first, pr.second);
-    h->t_rest_ms = h->t_total_ms - h->t_hop_ms;
+    finish_timing(h, ev_begin, ev_end, hop_ev);
     int status = 0;
     XFER(xfer_d2h(h, &status, h->d_status.p, 4));
     if (status & 2) return fail(h, RSREC_ERR_DIVERGED, "Chebyshev moments did not converge. Check energy limits energy_min and energy_max");
@@ -2526,8 +2539,7 @@ extern "C" int rsrec_chebyshev_seeded(rsrec_t* h, int nchains, int nseed, const 
     int rc = check_ready(h, "rsrec_chebyshev");
     if (rc) return rc;
     if (nchains < 0 || nseed < 1 || nseed > 8 || lld < 1 || !mu_n || (nchains > 0 && !seed_atoms) || a == 0.0) return fail(h, RSREC_ERR_ARG, "rsrec_chebyshev: bad argument");
-    for (int q = 0; q < nchains * nseed; ++q)
-        if (seed_atoms[q] < 1 || seed_atoms[q] > h->kk) return fail(h, RSREC_ERR_ARG, "rsrec_chebyshev: seed atom %d outside 1..%d", seed_atoms[q], h->kk);
+    XFER(check_seeds(h, "rsrec_chebyshev", seed_atoms, (size_t)nchains * nseed, 1));
     HIPCK(h, hipSetDevice(h->device));
     reset_timing(h);
     if (nchains == 0) return RSREC_OK;
@@ -2595,6 +2607,25 @@ struct KuboCtx {
     std::vector<std::tuple<const Spmm5Operator*, int, double>>* req = nullptr;
 };
 
+// The context of launches over the whole lattice: the list of all atoms as the one order row that the `cpo` chains of a launch share
+// (cached like every region), and the launch shape for `nchains` of them.  The temporaries and the timing tables stay with the caller.
+int whole_lattice_ctx(rsrec_t* h, int cpo, int nchains, KuboCtx& K) {
+    const int kk = h->kk;
+    const size_t velems = (size_t)(kk + 1) * BLD;
+    std::vector<int> all(kk);
+    for (int i = 0; i < kk; ++i) all[i] = i;
+    int ostride = kk;
+    double dummy1 = 0, dummy2 = 0;
+    const int rc = upload_regions(h, all.data(), 1, kk, 1, 1, false, true, ostride, dummy1, dummy2);
+    if (rc) return rc;
+    K.h = h;
+    chain_views(h, 1, velems, cpo, ostride, K.CV);
+    K.SD = SpmmDims{kk, h->nslots, h->nmax, 1, cpo, ostride, 0, velems, K.CV.obase, nchains};
+    K.grid = s5_grid(h, dim3(256, (unsigned)nchains), 0);
+    K.iz = h->d_iz.as<int>();
+    return RSREC_OK;
+}
+
 // flops one whole-lattice product with operator (op, set) requires by its block structure (see required_hop_flops)
 double kubo_required_flops(const rsrec_t* h, const Spmm5Operator& op, int set) {
     double f = 0.0;
@@ -2654,8 +2685,7 @@ extern "C" int rsrec_kubo_moments(rsrec_t* h, int nvec, int nseed, const int32_t
         return fail(h, RSREC_ERR_ARG, "rsrec_kubo_moments: bad argument");
     if (h->hoh && (!vo_a || !vo_b)) return fail(h, RSREC_ERR_ARG, "rsrec_kubo_moments: hoh requires vo_a and vo_b");
     if (!h->s5_built) return fail(h, RSREC_ERR_ARG, "rsrec_kubo_moments: lattice has too many neighbour slots for the SpMM kernel");
-    for (size_t q = 0; q < (size_t)nvec * nseed; ++q)
-        if (seed_atoms[q] < 0 || seed_atoms[q] > h->kk) return fail(h, RSREC_ERR_ARG, "rsrec_kubo_moments: seed atom %d outside 0..%d", seed_atoms[q], h->kk);
+    XFER(check_seeds(h, "rsrec_kubo_moments", seed_atoms, (size_t)nvec * nseed, 0));
     HIPCK(h, hipSetDevice(h->device));
     reset_timing(h);
     if (nvec == 0) return RSREC_OK;
@@ -2703,7 +2733,6 @@ extern "C" int rsrec_kubo_moments(rsrec_t* h, int nvec, int nseed, const int32_t
     for (int v = 0; v < 6; ++v) h->d_vec[v].release();
     const size_t sstride = (size_t)nbv * velems;                                // doubles between two slots of a buffer (nbv chains each)
     DevBuf &work = h->d_kubo[0], &Lm = h->d_kubo[1], &Rm = h->d_kubo[2], &Part = h->d_kubo[3], &Mu = h->d_kubo[4];
-    auto cleanup = [&]() {};                                      // the buffers stay with the handle for the next call
     {   // buffers that have to grow are given back first, so that the new sizes are asked of the memory the budget counted on
         const size_t want[5] = {11 * sstride * 8, (size_t)lchunk * sstride * 8, (size_t)nchunk * sstride * 8, (size_t)part_bytes(lchunk), (size_t)nbv * cond_ll * cond_ll * BLK * 16};
         for (int q = 0; q < 5; ++q) if (h->d_kubo[q].bytes < want[q]) h->d_kubo[q].release();
@@ -2722,17 +2751,9 @@ extern "C" int rsrec_kubo_moments(rsrec_t* h, int nvec, int nseed, const int32_t
     double *l0 = V[4], *l1 = V[9];                                              // T_{m0-2} r, T_{m0-1} r: the left recurrence across a chunk border
     HIPCK(h, h->d_seed.reserve((size_t)nseed * 4));
     HIPCK(h, h->d_seedcoef.reserve((size_t)nseed * sizeof(double2)));
-    // region list: all atoms (every launch of this path runs over the whole lattice), one row shared by the chains of a launch
-    std::vector<int> all(kk);
-    for (int i = 0; i < kk; ++i) all[i] = i;
-    int ostride = kk;
-    double dummy1 = 0, dummy2 = 0;
-    rc = upload_regions(h, all.data(), 1, kk, 1, 1, false, true, ostride, dummy1, dummy2);
-    if (rc) { cleanup(); return rc; }
     KuboCtx K;
-    K.h = h;
-    K.CV.order = h->cur_order; K.CV.cum = h->cur_cum; K.CV.obase = h->cur_cum + (size_t)h->cur_nrows * 1; K.CV.nlev = 1; K.CV.vstride = velems; K.CV.cpo = nbv; K.CV.ostride = ostride;
-    K.iz = h->d_iz.as<int>();
+    rc = whole_lattice_ctx(h, nbv, nbv, K);
+    if (rc) return rc;
     K.hps = V[6]; K.p1 = V[7]; K.p2 = V[8];
     std::vector<std::pair<hipEvent_t, hipEvent_t>> spmm_ev, gemm_ev;
     K.spmm_ev = &spmm_ev;
@@ -2745,7 +2766,7 @@ extern "C" int rsrec_kubo_moments(rsrec_t* h, int nvec, int nseed, const int32_t
     auto Rslot = [&](int q) { return Rm.as<double>() + (size_t)q * sstride; };
     for (int iv0 = 0; iv0 < nvec; iv0 += nbv) {
         const int nb = std::min(nbv, nvec - iv0);                                 // vectors of this batch = chains of its launches
-        K.SD = SpmmDims{kk, h->nslots, h->nmax, 1, nbv, ostride, 0, velems, K.CV.obase, nb};
+        K.SD.nchains = nb;                                                        // (the last batch may be shorter; its slots keep nbv chains)
         K.grid = s5_grid(h, dim3(256, (unsigned)nb), 0);
         // r_i: psiref(l,l,seed(k)) = coef(k); seed atom 0 = unused entry
         HIPCK(h, hipMemsetAsync(psiref, 0, sstride * 8, h->stream));
@@ -2757,7 +2778,7 @@ extern "C" int rsrec_kubo_moments(rsrec_t* h, int nvec, int nseed, const int32_t
                 if (at == 0) continue;
                 s0.push_back(at - 1); c0.push_back(seed_coef[2 * ((size_t)iv * nseed + k)]); c0.push_back(seed_coef[2 * ((size_t)iv * nseed + k) + 1]);
             }
-            if (s0.empty()) { cleanup(); return fail(h, RSREC_ERR_ARG, "rsrec_kubo_moments: vector %d has no seed", iv + 1); }
+            if (s0.empty()) return fail(h, RSREC_ERR_ARG, "rsrec_kubo_moments: vector %d has no seed", iv + 1);
             XFER(xfer_h2d(h, h->d_seed.p, s0.data(), s0.size() * 4));
             XFER(xfer_h2d(h, h->d_seedcoef.p, c0.data(), c0.size() * 8));
             k_seed<LayoutCI><<<1, 64, 0, h->stream>>>(psiref + (size_t)c * velems, velems, h->d_seed.as<int>(), h->d_seedcoef.as<double2>(), (int)s0.size());
@@ -2844,7 +2865,6 @@ extern "C" int rsrec_kubo_moments(rsrec_t* h, int nvec, int nseed, const int32_t
         h->n_block_mult = fan * h->n_kubo_chain_launches;
         h->n_atom_steps = (double)kk * h->n_kubo_chain_launches;
     }
-    cleanup();
     return RSREC_OK;
 }
 
@@ -2965,8 +2985,7 @@ extern "C" int rsrec_orbital_moments(rsrec_t* h, int nseeds, const int32_t* seed
     int rc = check_ready(h, "rsrec_orbital_moments");
     if (rc) return rc;
     if (nseeds < 0 || lld < 1 || a == 0.0 || !cr || !mu_orb || (nseeds > 0 && !seed_atoms)) return fail(h, RSREC_ERR_ARG, "rsrec_orbital_moments: bad argument");
-    for (int q = 0; q < nseeds; ++q)
-        if (seed_atoms[q] < 1 || seed_atoms[q] > h->kk) return fail(h, RSREC_ERR_ARG, "rsrec_orbital_moments: seed atom %d outside 1..%d", seed_atoms[q], h->kk);
+    XFER(check_seeds(h, "rsrec_orbital_moments", seed_atoms, (size_t)nseeds, 1));
     if (!h->s5_built) return fail(h, RSREC_ERR_ARG, "rsrec_orbital_moments: lattice has too many neighbour slots for the SpMM kernel");
     HIPCK(h, hipSetDevice(h->device));
     reset_timing(h);
@@ -2976,27 +2995,21 @@ extern "C" int rsrec_orbital_moments(rsrec_t* h, int nseeds, const int32_t* seed
     const bool hoh = h->hoh != 0;
     if (hoh) { rc = build_plain_operator(h); if (rc) return rc; }
     const Spmm5Operator& plain = hoh ? h->orb_plain : h->s5_op;
-    const size_t velems = (size_t)(kk + 1) * BLD, nd = (size_t)kk * BLD;
+    const size_t velems = (size_t)(kk + 1) * BLD;
     const int nvec = hoh ? 5 : 4;                                  // left, v0, v1, v2 (+ h v of the two-pass product)
     BatchPlan bp;
     rc = plan_batch(h, nseeds, nvec, velems / 2, bp);
     if (rc) return rc;
     const int B = bp.batch;
     for (int v = 0; v < nvec; ++v) HIPCK(h, h->d_vec[v].reserve((size_t)B * velems * sizeof(double)));
-    const size_t gram_elems = (size_t)B * 256 * 1296;
-    HIPCK(h, h->d_partial.reserve(2 * gram_elems * sizeof(double)));
-    h->p2_slot = (size_t)B * 16 * 2 * 1296;
-    HIPCK(h, h->d_partial2.reserve(2 * h->p2_slot * sizeof(double)));
+    XFER(reserve_partials(h, B, 2 * (size_t)B * 256 * 1296 * sizeof(double)));
     HIPCK(h, h->d_seed.reserve((size_t)B * 4));
     HIPCK(h, h->d_seedcoef.reserve((size_t)B * sizeof(double2)));
     HIPCK(h, h->d_scal.reserve((size_t)3 * kk * sizeof(double)));
     HIPCK(h, h->d_zsqr.reserve((size_t)B * lld * BLK * sizeof(double2)));           // the chains' moments
     XFER(xfer_h2d(h, h->d_scal.p, cr, (size_t)3 * kk * sizeof(double)));
-    std::vector<int> all(kk);
-    for (int i = 0; i < kk; ++i) all[i] = i;
-    int ostride = kk;
-    double dummy1 = 0, dummy2 = 0;
-    rc = upload_regions(h, all.data(), 1, kk, 1, 1, false, true, ostride, dummy1, dummy2);
+    KuboCtx K;
+    rc = whole_lattice_ctx(h, B, B, K);
     if (rc) return rc;
     double2* d_out = h->d_zsqr.as<double2>();
     const size_t ostr = (size_t)lld * BLK;
@@ -3004,20 +3017,16 @@ extern "C" int rsrec_orbital_moments(rsrec_t* h, int nseeds, const int32_t* seed
     hipEvent_t e_begin = next_event(h);
     std::vector<std::pair<hipEvent_t, hipEvent_t>> spmm_ev;
     std::vector<std::tuple<const Spmm5Operator*, int, double>> req_tab;
+    K.spmm_ev = &spmm_ev; K.req = &req_tab;
     for (int c0 = 0; c0 < nseeds; c0 += B) {
         const int nb = std::min(B, nseeds - c0);
-        std::vector<int> s0(nb);
-        std::vector<double> one(2 * (size_t)nb, 0.0);
-        for (int q = 0; q < nb; ++q) { s0[q] = seed_atoms[c0 + q] - 1; one[2 * (size_t)q] = 1.0; }
+        std::vector<int> s0;
+        std::vector<double> one;
+        stage_seeds(seed_atoms, nullptr, c0, nb, 1, s0, one);
         XFER(xfer_h2d(h, h->d_seed.p, s0.data(), s0.size() * 4));
         XFER(xfer_h2d(h, h->d_seedcoef.p, one.data(), one.size() * 8));
-        KuboCtx K;
-        K.h = h;
-        K.CV.order = h->cur_order; K.CV.cum = h->cur_cum; K.CV.obase = h->cur_cum + (size_t)h->cur_nrows * 1; K.CV.nlev = 1; K.CV.vstride = velems; K.CV.cpo = nb; K.CV.ostride = ostride;
-        K.SD = SpmmDims{kk, h->nslots, h->nmax, 1, nb, ostride, 0, velems, K.CV.obase, nb};
+        K.CV.cpo = K.SD.cpo = K.SD.nchains = nb;                      // (the last batch may be shorter: its chains share the order row)
         K.grid = s5_grid(h, dim3(256, nb), 0);
-        K.iz = h->d_iz.as<int>();
-        K.spmm_ev = &spmm_ev; K.req = &req_tab;
         double* left = h->d_vec[0].as<double>();
         double *v0 = h->d_vec[1].as<double>(), *v1 = h->d_vec[2].as<double>(), *v2 = h->d_vec[3].as<double>();
         K.hps = hoh ? h->d_vec[4].as<double>() : nullptr; K.p1 = nullptr; K.p2 = nullptr;
@@ -3026,7 +3035,7 @@ extern "C" int rsrec_orbital_moments(rsrec_t* h, int nseeds, const int32_t* seed
         // t = H~ psiref with the plain operator, then the position factors
         kubo_spmm(K, plain, 0, v1, left, nullptr, cheb_epilogue(true, v1, nullptr, a, b));
         k_orb_left<<<dim3(std::min(kk, 1024), nb), 256, 0, h->stream>>>(kk, velems, h->d_seed.as<int>(), h->d_scal.as<double>(), alat, reinterpret_cast<double2*>(left));
-        const dim3 grid_mf(std::max(1, std::min(mfma_workgroups_per_chain(h, nb), (ostride / GROUP + MF_WAVES - 1) / MF_WAVES)), nb);
+        const dim3 grid_mf(std::max(1, std::min(mfma_workgroups_per_chain(h, nb), (K.CV.ostride / GROUP + MF_WAVES - 1) / MF_WAVES)), nb);
         const dim3 gl = level_grid(h, grid_mf, 0);
         for (int n = 0; n < lld; ++n) {
             if (n == 1) {
@@ -3052,12 +3061,9 @@ extern "C" int rsrec_orbital_moments(rsrec_t* h, int nseeds, const int32_t* seed
     }
     hipEvent_t e_end = next_event(h);
     HIPCK(h, hipStreamSynchronize(h->stream));
-    h->t_total_ms = ev_ms(e_begin, e_end);
-    for (auto& pr : spmm_ev) h->t_hop_ms += ev_ms(pr.first, pr.second);
-    h->t_rest_ms = h->t_total_ms - h->t_hop_ms;
+    finish_timing(h, e_begin, e_end, spmm_ev);
     h->n_hop_launch = (double)spmm_ev.size();
     h->res_kind = 0;
-    (void)nd;
     return RSREC_OK;
 }
 
@@ -3077,18 +3083,9 @@ extern "C" int rsrec_apply_operator(rsrec_t* h, int vel, const double* v_op, con
     if (vel == 2 && h->hoh) { rc = build_plain_operator(h); if (rc) return rc; }        // ham_vec_matmul under hoh: the plain operator (recursion.f90:913)
     for (int v = 0; v < 6; ++v) HIPCK(h, h->d_vec[v].reserve(velems * 8));
     for (int v = 0; v < 6; ++v) HIPCK(h, hipMemsetAsync(h->d_vec[v].p, 0, velems * 8, h->stream));
-    std::vector<int> all(kk);
-    for (int i = 0; i < kk; ++i) all[i] = i;
-    int ostride = kk;
-    double dummy1 = 0, dummy2 = 0;
-    rc = upload_regions(h, all.data(), 1, kk, 1, 1, false, true, ostride, dummy1, dummy2);
-    if (rc) return rc;
     KuboCtx K;
-    K.h = h;
-    K.CV.order = h->cur_order; K.CV.cum = h->cur_cum; K.CV.obase = h->cur_cum + (size_t)h->cur_nrows * 1; K.CV.nlev = 1; K.CV.vstride = velems; K.CV.cpo = 1; K.CV.ostride = ostride;
-    K.SD = SpmmDims{kk, h->nslots, h->nmax, 1, 1, ostride, 0, velems, K.CV.obase, 1};
-    K.grid = s5_grid(h, dim3(256, 1), 0);
-    K.iz = h->d_iz.as<int>();
+    rc = whole_lattice_ctx(h, 1, 1, K);
+    if (rc) return rc;
     double* in = h->d_vec[0].as<double>(); double* out = h->d_vec[1].as<double>(); double* tmp = h->d_vec[2].as<double>();
     K.hps = h->d_vec[3].as<double>(); K.p1 = h->d_vec[4].as<double>(); K.p2 = h->d_vec[5].as<double>();
     XFER(xfer_h2d(h, tmp, psi_in, nd * 8));
@@ -3115,8 +3112,7 @@ extern "C" int rsrec_scalar_lanczos(rsrec_t* h, int nsites, const int32_t* seed_
     int rc = check_ready(h, "rsrec_scalar_lanczos");
     if (rc) return rc;
     if (nsites < 0 || lld < 1 || llmax < lld || !a || !b2 || (nsites > 0 && !seed_atoms)) return fail(h, RSREC_ERR_ARG, "rsrec_scalar_lanczos: bad argument");
-    for (int q = 0; q < nsites; ++q)
-        if (seed_atoms[q] < 1 || seed_atoms[q] > h->kk) return fail(h, RSREC_ERR_ARG, "rsrec_scalar_lanczos: seed atom %d outside 1..%d", seed_atoms[q], h->kk);
+    XFER(check_seeds(h, "rsrec_scalar_lanczos", seed_atoms, (size_t)nsites, 1));
     HIPCK(h, hipSetDevice(h->device));
     reset_timing(h);
     std::fill(a, a + (size_t)llmax * NB * nsites, 0.0);
@@ -3166,7 +3162,7 @@ extern "C" int rsrec_scalar_lanczos(rsrec_t* h, int nsites, const int32_t* seed_
         XFER(xfer_h2d(h, h->d_seed.p, so.data(), so.size() * 4));
         HIPCK(h, hipStreamSynchronize(h->stream));
         ChainView CV;
-        CV.order = h->cur_order; CV.cum = h->cur_cum; CV.obase = h->cur_cum + (size_t)h->cur_nrows * nlev; CV.nlev = nlev; CV.vstride = velems; CV.cpo = NB; CV.ostride = ostride;
+        chain_views(h, nlev, velems, NB, ostride, CV);
         for (int v = 0; v < 2; ++v) HIPCK(h, hipMemsetAsync(h->d_vec[v].p, 0, (size_t)nc * velems * sizeof(double2), h->stream));
         HIPCK(h, hipMemsetAsync(ca, 0, (size_t)nch * 2 * lld * sizeof(double), h->stream));
         k_scalar_seed<<<nc, 64, 0, h->stream>>>(psi, velems, h->d_seed.as<int>(), cb, lld);

@@ -61,6 +61,33 @@ def test_device_assembled_blocks_match_reference_and_are_reused(name):
     rec.close()
 
 
+def test_destroyed_handle_gives_back_the_assembled_blocks():
+    """The handle keeps the input and the blocks of rsrec_assemble_blocks on the device (that is what update_hamiltonian reuses); destroying
+    it frees them with everything else.  32 rounds of create / assemble / destroy leave the device's free memory within 2 MiB -- one granule
+    of the driver's allocator, the finest step hipMemGetInfo is sure to resolve -- of the reading after a first round (which pays what the
+    process allocates once).  A handle that kept them would lose hmag + ee + eeo + hall + hallo = 4.5 MB per round, 68 granules in all."""
+    import torch
+    name, rounds, granule = "B2FeCo_block_hoh", 32, 2 << 20
+    z, hm = load_golden(name), load_golden(name + "_hmag")
+    ham = Hamiltonian(ee=z["ee"], lsham=z["lsham"], eeo=z["eeo"], enim=z["enim"], hall=z["hall"], hallo=z["hallo"], hoh=True)
+    kept = sum(hm[k].nbytes for k in ("hmag_type", "hmag_atom")) + sum(z[k].nbytes for k in ("ee", "eeo", "hall", "hallo"))
+    assert rounds * kept > 8 * granule                 # the case can tell a leak from a granule
+
+    def one_round():
+        rec = make_rec(z, ham)
+        rec.build_bulkham(hm["hmag_type"], hm["nbr_type_type"], hm["obarm"])
+        rec.build_locham(hm["hmag_atom"], hm["nbr_type_atom"], hm["obarm"])
+        rec.close()
+
+    one_round()
+    free0 = torch.cuda.mem_get_info(0)[0]
+    for _ in range(rounds):
+        one_round()
+    free1 = torch.cuda.mem_get_info(0)[0]
+    print("free device memory: %d -> %d bytes after %d rounds (%d bytes assembled per round)" % (free0, free1, rounds, kept))
+    assert free0 - free1 <= granule
+
+
 def test_assemble_blocks_refuses_bad_arguments():
     z, hm = load_golden("fccCu001_block_hoh"), load_golden("fccCu001_block_hoh_hmag")
     ham = Hamiltonian(ee=z["ee"], lsham=z["lsham"], eeo=z["eeo"], enim=z["enim"], hoh=True)
