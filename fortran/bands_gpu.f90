@@ -10,7 +10,10 @@
 !> from the full `g0(18,18,nE,site)` -- 13 MB per site that a GPU Green function first has to send over PCIe.  With a
 !> `recursion_gpu` behind the class pointer the block coefficients of the rank's sites are still on the device after `recur_b`
 !> (`rsrec_gpu_block_resident`), and `rsrec_block_ldos` (include/rsrec.h) runs zsqr -> get_terminf -> bgreen -> this reduction
-!> there: 18 doubles per site and energy come back instead of 648, summed in the reference's loop order.  Everything after the
+!> there: 18 doubles per site and energy come back instead of 648, summed in the reference's loop order.
+!> The Chebyshev recursion has the same stage: after `chebyshev_recur` the moments of the rank's sites are on the device
+!> (`rsrec_gpu_cheb_resident`), and `rsrec_chebyshev_ldos` forms the diagonal of `green%chebyshev_green` and the same reduction there.
+!> The two recursions differ in that one library call; everything after it is one code path.  Everything after the
 !> reduction -- the MPI_ALLREDUCE of the zero-padded arrays (:271-274), the three output files (:279-324), the Fermi level
 !> (:326-343) -- is the reference's, restated here because `calculate_fermi` is one routine.
 !>
@@ -19,7 +22,7 @@
 !> An SCF iteration reads `g0` in `calculate_magnetic_moments`, so it is produced once per iteration either way; a flow that stops
 !> at the densities of states (calculation.f90:700-712 `block_green` + `calculate_fermi`) never produces it.
 !>
-!> Falls back to the inherited routine whenever the device does not hold this call's coefficients (Chebyshev / scalar recursion,
+!> Falls back to the inherited routine whenever the device does not hold this call's coefficients or moments (scalar recursion,
 !> local-axis runs, a `green` that is not `green_gpu`).
 !------------------------------------------------------------------------------
 module bands_gpu_mod
@@ -34,7 +37,7 @@ module bands_gpu_mod
    use string_mod, only: fmt
    use rsrec_binding
    use rsrec_context_mod, only: rsrec_gpu_context, rsrec_env_flag
-   use recursion_gpu_mod, only: rsrec_gpu_block_resident
+   use recursion_gpu_mod, only: rsrec_gpu_block_resident, rsrec_gpu_cheb_resident
 #ifdef USE_MPI
    use mpi
 #endif
@@ -108,12 +111,22 @@ contains
       end select
    end subroutine ensure_g0
 
-   !> .true. if the device holds the block coefficients this call's densities of states are made of
+   !> .true. if the device holds what this call's densities of states are made of: the block coefficients (recur = 'block') or the
+   !> Chebyshev moments (recur = 'chebyshev') of the rank's sites
    function device_stage_usable(this) result(ok)
       class(bands_gpu), intent(in) :: this
       logical :: ok
-      ok = this%device_ldos .and. trim(this%control%recur) == 'block' .and. end_atom >= start_atom
-      if (ok) ok = rsrec_gpu_block_resident() == end_atom - start_atom + 1
+      ok = this%device_ldos .and. end_atom >= start_atom
+      if (ok) then
+         select case (trim(this%control%recur))
+         case ('block')
+            ok = rsrec_gpu_block_resident() == end_atom - start_atom + 1
+         case ('chebyshev')
+            ok = rsrec_gpu_cheb_resident() == end_atom - start_atom + 1
+         case default
+            ok = .false.
+         end select
+      end if
       if (ok) then
          select type (g => this%green)
          class is (green_gpu)
@@ -151,10 +164,15 @@ contains
       ! zero-padded images over all nrec sites, this rank's sites start_atom .. end_atom filled (what bands.f90:258-268 leaves
       ! in dtot / dosia / dosial before the all-reduce); sums in the reference's loop order
       call g_timer%start('ldos-gpu')
-      rc = rsrec_block_ldos(handle, int(nv, c_int), c_loc(ene), 0.0_c_double, 0.0_c_double, sym_i, int(start_atom - 1, c_int), int(nrec, c_int), &
-                            c_loc(dtot), c_loc(dosia), c_loc(dosial), c_null_ptr, c_null_ptr)
+      if (trim(this%control%recur) == 'chebyshev') then
+         rc = rsrec_chebyshev_ldos(handle, int(nv, c_int), c_loc(ene), real(this%en%energy_min, c_double), real(this%en%energy_max, c_double), &
+                                   int(start_atom - 1, c_int), int(nrec, c_int), c_loc(dtot), c_loc(dosia), c_loc(dosial))
+      else
+         rc = rsrec_block_ldos(handle, int(nv, c_int), c_loc(ene), 0.0_c_double, 0.0_c_double, sym_i, int(start_atom - 1, c_int), int(nrec, c_int), &
+                               c_loc(dtot), c_loc(dosia), c_loc(dosial), c_null_ptr, c_null_ptr)
+      end if
       call g_timer%stop('ldos-gpu')
-      if (rc /= 0) call g_logger%fatal('rsrec_block_ldos: '//rsrec_error_string(handle), __FILE__, __LINE__)
+      if (rc /= 0) call g_logger%fatal('rsrec_'//trim(this%control%recur)//'_ldos: '//rsrec_error_string(handle), __FILE__, __LINE__)
       this%n_device_ldos = this%n_device_ldos + 1
       this%dtot(1:nv) = dtot
 

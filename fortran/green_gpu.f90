@@ -41,7 +41,8 @@ module green_gpu_mod
       !> device LDOS stage from the coefficients the recursion left on the GPU) then never produces `g0` at all.
       logical :: defer_g0 = .false.
       logical :: g0_stale = .false.
-      logical :: fetching = .false.   ! set by fetch_g0 around its own block_green call: the one caller that makes a deferred g0
+      logical :: fetching = .false.   ! set by fetch_g0 around its own Green call: the one caller that makes a deferred g0
+      logical :: stale_is_chebyshev = .false.   ! which routine postponed it: chebyshev_green (else block_green)
       !> .true. once exchange_gpu owns the intersite stage (its constructor, `release_intersite`)
       logical :: intersite_on_device = .false.
    contains
@@ -130,7 +131,8 @@ contains
 
       if (this%defer_g0 .and. .not. this%fetching) then
          this%g0_stale = .true.                               ! produced by fetch_g0 when somebody reads g0; repeated calls without a
-         return                                               ! reader in between (block_green + calculate_fermi, DOS-only flows) stay free
+         this%stale_is_chebyshev = .false.                    ! reader in between (block_green + calculate_fermi, DOS-only flows) stay free
+         return
       end if
       this%g0_stale = .false.
       ll = this%control%lld
@@ -172,17 +174,22 @@ contains
       if (rc /= 0) call g_logger%fatal('rsrec_block_green: '//rsrec_error_string(handle), __FILE__, __LINE__)
    end subroutine gpu_block_green
 
-   !> `g0` of the last (deferred) `block_green` call, now.  A no-op when `g0` is up to date.
+   !> `g0` of the last (deferred) `block_green` / `chebyshev_green` call, now.  A no-op when `g0` is up to date.
    subroutine gpu_fetch_g0(this)
       class(green_gpu), intent(inout) :: this
       if (.not. this%g0_stale) return
       this%fetching = .true.
-      call this%block_green()                                ! the one call that does the work
+      if (this%stale_is_chebyshev) then                      ! the one call that does the work
+         call this%chebyshev_green()
+      else
+         call this%block_green()
+      end if
       this%fetching = .false.
    end subroutine gpu_fetch_g0
 
    !> Replaces green.f90:1030-1108: g0 of the sites of this rank from the Chebyshev moments.  The side effect of the reference
-   !> routine -- recursion%mu_ng = mu_n * Jackson kernel (* 2 beyond the first moment), read later by bands.f90:762 -- is kept.
+   !> routine -- recursion%mu_ng = mu_n * Jackson kernel (* 2 beyond the first moment), read later by bands.f90:762 -- is kept, and is
+   !> made at once even when `defer_g0` postpones the library call and the download of `g0` to `fetch_g0` (it is cheap host work).
    subroutine gpu_chebyshev_green(this)
       use mpi_mod, only: start_atom, end_atom, g2l_map
       use math_mod, only: jackson_kernel
@@ -194,21 +201,31 @@ contains
       real(rp), allocatable, target :: ene(:)
       complex(rp), allocatable, target :: mu(:, :, :, :), gt(:, :, :, :)
 
-      this%g0 = 0.0d0
       nv = this%en%channels_ldos + 10
       nm = this%control%lld*2 + 2
       nloc = end_atom - start_atom + 1
-      if (nloc <= 0) return
-      call jackson_kernel(nm, kernel)
-      do n_glob = start_atom, end_atom
-         n = g2l_map(n_glob)
-         do l = 1, 18
-            do m = 1, 18
-               this%recursion%mu_ng(l, m, :, n) = this%recursion%mu_n(l, m, :, n)*kernel(:)
+      if (.not. this%fetching) then                          ! (fetch_g0 repeats a call whose side effect is already made)
+         if (.not. this%defer_g0) this%g0 = 0.0d0
+         if (nloc <= 0) return
+         call jackson_kernel(nm, kernel)
+         do n_glob = start_atom, end_atom
+            n = g2l_map(n_glob)
+            do l = 1, 18
+               do m = 1, 18
+                  this%recursion%mu_ng(l, m, :, n) = this%recursion%mu_n(l, m, :, n)*kernel(:)
+               end do
             end do
+            this%recursion%mu_ng(:, :, 2:nm, n) = this%recursion%mu_ng(:, :, 2:nm, n)*2.0_rp
          end do
-         this%recursion%mu_ng(:, :, 2:nm, n) = this%recursion%mu_ng(:, :, 2:nm, n)*2.0_rp
-      end do
+         if (this%defer_g0) then
+            this%g0_stale = .true.
+            this%stale_is_chebyshev = .true.
+            return
+         end if
+      else
+         this%g0 = 0.0d0
+      end if
+      this%g0_stale = .false.
       n1 = g2l_map(start_atom)
       allocate (ene(nv), mu(18, 18, nm, nloc))
       ene = this%en%ene(1:nv)

@@ -58,12 +58,14 @@ module recursion_gpu_mod
       procedure :: gpu_constructor
    end interface recursion_gpu
 
-   public :: rsrec_gpu_shutdown, rsrec_gpu_context, rsrec_gpu_block_resident
+   public :: rsrec_gpu_shutdown, rsrec_gpu_context, rsrec_gpu_block_resident, rsrec_gpu_cheb_resident
 
    !> (the per-process device context g_handle lives in rsrec_context_mod; re-exported above for the hosts that used it from here)
    !> number of sites whose block coefficients the last driver call left on the device (0: none -- another driver ran since, or the
    !> coefficients there are not the ones in a_b / b2_b, as after a local-axis run): the input of the device LDOS stage
    integer, save :: g_block_resident = 0
+   !> the same for the Chebyshev moments mu_n of chebyshev_recur (every other driver resets it)
+   integer, save :: g_cheb_resident = 0
 
 contains
 
@@ -85,6 +87,12 @@ contains
       integer :: n
       n = g_block_resident
    end function rsrec_gpu_block_resident
+
+   !> Sites of this rank whose mu_n (as chebyshev_recur produced them) are also resident on the device; 0 if they are not.
+   function rsrec_gpu_cheb_resident() result(n)
+      integer :: n
+      n = g_cheb_resident
+   end function rsrec_gpu_cheb_resident
 
    subroutine check(rc, where)
       integer(c_int), intent(in) :: rc
@@ -166,6 +174,7 @@ contains
       llmax = this%lattice%control%lld
       nloc = end_atom - start_atom + 1
       g_block_resident = 0
+      g_cheb_resident = 0
       if (nloc <= 0) return
       allocate (seeds(nloc), ab(18, 18, llmax, nloc), bb(18, 18, llmax, nloc))
 
@@ -268,6 +277,7 @@ contains
       allocate (ab(18, 18, llmax, nch), bb(18, 18, llmax, nch))
       call sync_device(this, .true.)
       g_block_resident = 0
+      g_cheb_resident = 0
       rc = rsrec_block_lanczos_seeded(g_handle, int(nch, c_int), 2_c_int, c_loc(seeds), c_loc(coef), int(llmax, c_int), c_loc(ab), c_loc(bb))
       call check(rc, 'rsrec_block_lanczos_seeded')
       do c = 1, nch
@@ -325,9 +335,11 @@ contains
       call sync_device(this, .true.)
       call g_timer%start('<PSI_0|PSI_n>')
       g_block_resident = 0
+      g_cheb_resident = 0
       rc = rsrec_chebyshev(g_handle, int(nloc, c_int), c_loc(seeds), int(this%control%lld, c_int), real(a, c_double), real(b, c_double), c_loc(mu))
       call g_timer%stop('<PSI_0|PSI_n>')
       call check(rc, 'rsrec_chebyshev')
+      g_cheb_resident = nloc
       this%mu_n(:, :, 1:nmom, 1:nloc) = mu
    end subroutine gpu_chebyshev_recur
 
@@ -371,6 +383,7 @@ contains
       call sync_device(this, .true.)
       call g_timer%start('<PSI_0|PSI_n>')
       g_block_resident = 0
+      g_cheb_resident = 0
       rc = rsrec_chebyshev_seeded(g_handle, int(nch, c_int), 2_c_int, c_loc(seeds), c_loc(coef), int(this%control%lld, c_int), &
                                   real(a, c_double), real(b, c_double), c_loc(mu))
       call g_timer%stop('<PSI_0|PSI_n>')
@@ -399,6 +412,7 @@ contains
       end do
       call sync_device(this, .true.)
       g_block_resident = 0
+      g_cheb_resident = 0
       rc = rsrec_scalar_lanczos(g_handle, int(nloc, c_int), c_loc(seeds), int(this%lattice%control%lld, c_int), int(llmax_a, c_int), c_loc(a), c_loc(b2))
       call check(rc, 'rsrec_scalar_lanczos')
       ! the reference fills rows 1..lld of a(:,:,i_loc,1) / b2 and leaves the rest untouched (:3516-3519)
@@ -528,6 +542,7 @@ contains
       call jackson_kernel(ll, kernel)
       call sync_device(this, .true.)
       g_block_resident = 0
+      g_cheb_resident = 0
       allocate (seeds(this%lattice%kk), cr(3, this%lattice%kk), mu_n_orb(18, 18, ll))
       do k = 1, this%lattice%kk
          seeds(k) = int(k, c_int)

@@ -150,6 +150,17 @@ module rsrec_binding
          integer(c_int) :: rc
       end function
 
+      ! the LDOS stage on the Chebyshev moments resident on the device: the images of rsrec_block_ldos
+      function rsrec_chebyshev_ldos(handle, nen, ene, energy_min, energy_max, site_offset, nsites_total, dtot, dosia, dosial) &
+         bind(C, name='rsrec_chebyshev_ldos') result(rc)
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: handle
+         integer(c_int), value :: nen, site_offset, nsites_total
+         real(c_double), value :: energy_min, energy_max
+         type(c_ptr), value :: ene, dtot, dosia, dosial
+         integer(c_int) :: rc
+      end function
+
       ! the Kubo-Bastin conductivity integrand integrand_at(l,l,:,v), factor applied, without gamma_nm (conductivity.f90:158-281)
       function rsrec_kubo_integrand(handle, nvec, cond_ll, mu_nm, nen, ene, energy_min, energy_max, integrand) &
          bind(C, name='rsrec_kubo_integrand') result(rc)

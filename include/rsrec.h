@@ -175,6 +175,20 @@ int rsrec_block_ldos(rsrec_t *h, int nen, const double *ene, double eta_re, doub
 int rsrec_chebyshev_green(rsrec_t *h, int nsites, int lld, int nen, const double *ene, double energy_min, double energy_max,
                           const double *mu_n, double *g0);
 
+/* The LDOS stage for the sites of the LAST rsrec_chebyshev call, from the moments that call left on the device (nothing is uploaded
+ * but the energy mesh and the 2*lld+2 kernel weights): the diagonal of green%chebyshev_green (green.f90:1030-1108; a, b and the
+ * Jackson kernel as in rsrec_chebyshev_green, the sum over the moments in the reference's order) -> the reduction of
+ * bands%calculate_fermi (bands.f90:258-268), the one rsrec_block_ldos ends with.  Only the 18 diagonal elements of every moment are
+ * read and no g0 is formed.  The moments stay resident and unchanged (rsrec_pack_moments, rsrec_exchange kind = 1 and a second call
+ * still find them); two calls with the same input give the same bits.
+ *   dtot : real (nen);  dosia : real (nsites_total, nen);  dosial : real (nsites_total, 18, nen)  -- the zero-padded images of
+ *   rsrec_block_ldos (this rank's sites at site_offset+1 ..), HOST or DEVICE memory (all three alike, detected).
+ * Energies on or outside b -+ a give NaN, as in the reference (acos and the square root of a negative number).
+ * RSREC_ERR_ARG unless the moments of rsrec_chebyshev are what the device holds.
+ * rsrec_get_timing: out[0] device ms of the call, out[1] ms of the diagonal kernel alone. */
+int rsrec_chebyshev_ldos(rsrec_t *h, int nen, const double *ene, double energy_min, double energy_max, int site_offset, int nsites_total,
+                         double *dtot, double *dosia, double *dosial);
+
 /* Chebyshev (KPM, moment doubling) recursion.  Replaces chebyshev_recur (recursion.f90:3057-3130) with
  * cheb_0th_mom (:2145), cheb_1st_mom[_hoh] (:2169/:2245), chebyshev_recur_ll[_hoh] (:2495/:2605).
  *   a, b : scale and shift, a = (energy_max-energy_min)/(2-0.3), b = (energy_max+energy_min)/2 (:3078-3079)

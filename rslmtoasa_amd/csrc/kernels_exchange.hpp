@@ -180,10 +180,7 @@ __global__ __launch_bounds__(256) void k_exchange_cheb(int nm, int nen, const do
     const bool sm = same[pair] != 0;
     const double e = ene[ie];
     const double th = acos((e - b) / a);
-    for (int i = threadIdx.x; i < nm; i += blockDim.x) {
-        const double x = (double)i * th;
-        ef[i] = make_double2(-sin(x) * kern[i], -cos(x) * kern[i]);
-    }
+    for (int i = threadIdx.x; i < nm; i += blockDim.x) ef[i] = chebyshev_phase(i, th, kern[i]);
     __syncthreads();
     const double den = sqrt(a * a - (e - b) * (e - b));
     const int nch = sm ? 1 : 4;

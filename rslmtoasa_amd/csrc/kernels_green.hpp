@@ -344,6 +344,13 @@ __global__ __launch_bounds__(GREEN_WAVES * 64, GREEN_WAVES_PER_SIMD) void k_bloc
     for (int m = 0; m < 6; ++m) { const int el = lane + 64 * m; if (el < BLK) out[el] = L.M[el]; }
 }
 
+// Phase factor of moment i (0-based: the reference's i - 1) at the energy with th = acos w, kernel weight folded in (green.f90:1085-1095):
+// -i exp(-i i th) k = (-sin(i th) k, -cos(i th) k).  The one place the Chebyshev Green kernels form it.
+__device__ __forceinline__ double2 chebyshev_phase(int i, double th, double k) {
+    const double x = (double)i * th;
+    return make_double2(-sin(x) * k, -cos(x) * k);
+}
+
 // One element of chebyshev_green's g0 at one energy: the moments of the site `m` against the phase factors `ef` (also the exchange kernel's).
 __device__ __forceinline__ double2 chebyshev_green_elem(const double2* __restrict__ m, const double2* ef, int nm, int el, double den) {
     double sr = 0.0, si = 0.0;
@@ -365,14 +372,51 @@ __global__ __launch_bounds__(256) void k_chebyshev_green(int nm, int nen, const 
     const int ie = blockIdx.x, site = blockIdx.y;
     const double e = ene[ie];
     const double th = acos((e - b) / a);
-    for (int i = threadIdx.x; i < nm; i += blockDim.x) {
-        const double x = (double)i * th;                    // (i - 1) with the reference's 1-based i
-        ef[i] = make_double2(-sin(x) * kern[i], -cos(x) * kern[i]);
-    }
+    for (int i = threadIdx.x; i < nm; i += blockDim.x) ef[i] = chebyshev_phase(i, th, kern[i]);
     __syncthreads();
     const double den = sqrt(a * a - (e - b) * (e - b));
     const double2* m = mu + (size_t)site * nm * BLK;
     for (int el = threadIdx.x; el < BLK; el += blockDim.x) g0[((size_t)site * nen + ie) * BLK + el] = chebyshev_green_elem(m, ef, nm, el, den);
+}
+
+// The diagonal of chebyshev_green's g0, imaginary part only: gim[site][ie][j] = Im g0(j,j,ie,site), the input of k_ldos_finish
+// (bands.f90:258-268 reads nothing else of g0).  grid = (ceil(nen / CHEB_LDOS_TILE), nsites), block = CHEB_LDOS_TILE threads, dynamic
+// LDS = 18 nm complex.  The workgroup stages the 18 diagonal moments of every order of its site (stride 19 in the 324; the blocks
+// themselves are never read) in LDS, dm[i][j]; then ONE THREAD OWNS ONE ENERGY: it forms the phase factor of order i once
+// (chebyshev_phase, as k_chebyshev_green does), and adds its product with the 18 moments to 18 accumulators in registers, i = 1 .. nm in
+// the reference's order with the expression of chebyshev_green_elem.  All lanes of a wave read the same dm[i][j]: a broadcast, one LDS
+// address per instruction, no bank conflicts whatever the layout.  No g0 is formed and no sum crosses threads (no atomics: repeatable
+// bit for bit, and a site's numbers do not depend on the other sites of the call).
+constexpr int CHEB_LDOS_TILE = 64;
+__global__ __launch_bounds__(CHEB_LDOS_TILE) void k_chebyshev_ldos(int nm, int nen, const double* __restrict__ ene, double a, double b,
+                                                                  const double* __restrict__ kern /*[nm] jackson * {1,2,2,...}*/,
+                                                                  const double2* __restrict__ mu /*[site][nm][324]*/, double* __restrict__ gim /*[site][nen][18]*/) {
+    extern __shared__ double2 dm[];
+    const int site = blockIdx.y, ie = blockIdx.x * CHEB_LDOS_TILE + threadIdx.x;
+    const double2* m = mu + (size_t)site * nm * BLK;
+    for (int k = threadIdx.x; k < nm * NB; k += CHEB_LDOS_TILE) {
+        const int i = k / NB, j = k - NB * i;
+        dm[k] = m[(size_t)i * BLK + j * (NB + 1)];
+    }
+    __syncthreads();
+    if (ie >= nen) return;                                   // (no barrier below)
+    const double e = ene[ie];
+    const double th = acos((e - b) / a);
+    double si[NB];
+#pragma unroll
+    for (int j = 0; j < NB; ++j) si[j] = 0.0;
+    for (int i = 0; i < nm; ++i) {
+        const double2 f = chebyshev_phase(i, th, kern[i]);
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            const double2 v = dm[i * NB + j];
+            si[j] += v.x * f.y + v.y * f.x;
+        }
+    }
+    const double den = sqrt(a * a - (e - b) * (e - b));
+    double* out = gim + ((size_t)site * nen + ie) * NB;
+#pragma unroll
+    for (int j = 0; j < NB; ++j) out[j] = si[j] / den;
 }
 
 }  // namespace rsrec

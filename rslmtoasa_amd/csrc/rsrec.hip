@@ -99,7 +99,7 @@ struct rsrec_handle {
     size_t s5_lds_limit = (size_t)-1;   // LDS a k_spmm5 workgroup may ask for on THIS handle's device ((size_t)-1: not asked yet; hipFuncSetAttribute is per device)
     int n_cu = 0;                       // compute units of the device (size of the persistent launches)
     bool s4_attr = false;               // k_spmm4's and k_terminator's LDS opt-ins, per handle for the same reason
-    size_t term_attr_lds = 0;
+    size_t term_attr_lds = 0, cheb_ldos_attr_lds = 0;   // (k_chebyshev_ldos asks only beyond the 64 KB every kernel may have)
     std::vector<double> host_ee, host_lsham, host_eeo, host_enim, host_hall, host_hallo;   // operator arrays as last set (Kubo operator tables; local-axis runs)
     std::vector<double> host_st, host_loc;   // ee / hall with l.s folded into the on-site block when !hoh (what d_hst / d_hloc hold)
     // raw blocks assembled on the device (rsrec_assemble_blocks): [part: 0 per-type, 1 per-atom][0: blocks, 1: blocks x obar]; asm_host = what the
@@ -2178,6 +2178,12 @@ std::vector<double> chebyshev_green_kernel(int nm) {
     return kern;
 }
 
+// Scale and shift of green%chebyshev_green as the reference writes them (default-REAL literals 2 and 0.3, green.f90:1046-1047)
+void chebyshev_green_scaling(double energy_min, double energy_max, double& a, double& b) {
+    a = (energy_max - energy_min) / (double)(2.0f - 0.3f);
+    b = (energy_max + energy_min) / 2;
+}
+
 }  // namespace
 
 // green%chebyshev_green (green.f90:1030-1108): g0 from the Chebyshev moments of every site.
@@ -2188,8 +2194,8 @@ extern "C" int rsrec_chebyshev_green(rsrec_t* h, int nsites, int lld, int nen, c
     if (nsites == 0 || nen == 0) return RSREC_OK;
     HIPCK(h, hipSetDevice(h->device));
     const int nm = 2 * lld + 2;
-    // scale/shift as the reference writes them (default-REAL literals 2 and 0.3, green.f90:1046-1047) and the Jackson kernel
-    const double a = (energy_max - energy_min) / (double)(2.0f - 0.3f), b = (energy_max + energy_min) / 2;
+    double a, b;
+    chebyshev_green_scaling(energy_min, energy_max, a, b);
     const std::vector<double> kern = chebyshev_green_kernel(nm);
     const size_t mbytes = (size_t)nm * BLK * sizeof(double2), gbytes = (size_t)nen * BLK * sizeof(double2);
     const int super = (int)std::max<size_t>(1, std::min<size_t>((size_t)nsites, ((size_t)4 << 30) / mbytes));
@@ -2212,6 +2218,60 @@ extern "C" int rsrec_chebyshev_green(rsrec_t* h, int nsites, int lld, int nen, c
     hipEvent_t ev1 = next_event(h);
     HIPCK(h, hipStreamSynchronize(h->stream));
     h->t_total_ms = ev_ms(ev0, ev1);
+    return RSREC_OK;
+}
+
+// The LDOS stage for the sites of the last rsrec_chebyshev call, from the moments it left on the device: the diagonal of
+// green%chebyshev_green (green.f90:1030-1108) -> the reduction of calculate_fermi (bands.f90:258-268).  Neither the moments nor a g0
+// cross PCIe: the energy mesh and the nm kernel weights go up, 18 doubles per site and energy come back.
+extern "C" int rsrec_chebyshev_ldos(rsrec_t* h, int nen, const double* ene, double energy_min, double energy_max, int site_offset, int nsites_total,
+                                    double* dtot, double* dosia, double* dosial) {
+    if (!h) return RSREC_ERR_ARG;
+    if (nen < 1 || !ene || !dtot || !dosia || !dosial || site_offset < 0) return fail(h, RSREC_ERR_ARG, "rsrec_chebyshev_ldos: bad argument");
+    if (h->res_kind != 2) return fail(h, RSREC_ERR_ARG, "rsrec_chebyshev_ldos: no Chebyshev moments resident (call rsrec_chebyshev first)");
+    const int n = h->res_n, nm = 2 * h->res_lld + 2;
+    if (site_offset + n > nsites_total) return fail(h, RSREC_ERR_ARG, "rsrec_chebyshev_ldos: sites %d..%d outside 1..%d", site_offset + 1, site_offset + n, nsites_total);
+    HIPCK(h, hipSetDevice(h->device));
+    const size_t lds = (size_t)nm * NB * sizeof(double2);            // the diagonal moments of one site (29 KB at lld = 50)
+    if (lds > (size_t)150 * 1024) return fail(h, RSREC_ERR_ARG, "rsrec_chebyshev_ldos: lld = %d too deep for the LDS staging", h->res_lld);
+    if (lds > (size_t)64 * 1024 && lds > h->cheb_ldos_attr_lds) {
+        HIPCK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_chebyshev_ldos), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        h->cheb_ldos_attr_lds = lds;
+    }
+    h->n_ldos_calls++;
+    double a, b;
+    chebyshev_green_scaling(energy_min, energy_max, a, b);
+    const std::vector<double> kern = chebyshev_green_kernel(nm);
+    release_kubo_buffers(h, true, true);
+    HIPCK(h, h->d_gim.reserve(((size_t)n * nen * NB + (size_t)nen + nm) * sizeof(double)));
+    const size_t img = (size_t)nen * ((size_t)nsites_total * (NB + 1) + 1);          // dosial + dosia + dtot
+    const bool dev = is_device_ptr(dtot) && is_device_ptr(dosia) && is_device_ptr(dosial);
+    if (!dev) HIPCK(h, h->d_ldos.reserve(img * sizeof(double)));
+    double* d_gim = h->d_gim.as<double>();
+    double* d_ene = d_gim + (size_t)n * nen * NB;
+    double* d_kern = d_ene + nen;
+    XFER(xfer_h2d(h, d_ene, ene, (size_t)nen * sizeof(double)));
+    XFER(xfer_h2d(h, d_kern, kern.data(), (size_t)nm * sizeof(double)));
+    reset_timing(h);
+    hipEvent_t e0 = next_event(h);
+    {
+        const dim3 grid((nen + CHEB_LDOS_TILE - 1) / CHEB_LDOS_TILE, n);
+        k_chebyshev_ldos<<<grid, CHEB_LDOS_TILE, lds, h->stream>>>(nm, nen, d_ene, a, b, d_kern, h->d_mu.as<double2>(), d_gim);
+    }
+    hipEvent_t k1 = next_event(h);
+    double* o_dosial = dev ? dosial : h->d_ldos.as<double>();
+    double* o_dosia = dev ? dosia : o_dosial + (size_t)nsites_total * NB * nen;
+    double* o_dtot = dev ? dtot : o_dosia + (size_t)nsites_total * nen;
+    k_ldos_finish<<<(nen + 63) / 64, 64, 0, h->stream>>>(d_gim, n, nen, site_offset, nsites_total, o_dosial, o_dosia, o_dtot);
+    HIPCK(h, hipGetLastError());
+    hipEvent_t e1 = next_event(h);
+    if (!dev) {
+        XFER(xfer_d2h(h, dosial, o_dosial, (size_t)nsites_total * NB * nen * sizeof(double)));
+        XFER(xfer_d2h(h, dosia, o_dosia, (size_t)nsites_total * nen * sizeof(double)));
+        XFER(xfer_d2h(h, dtot, o_dtot, (size_t)nen * sizeof(double)));
+    }
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    finish_timing(h, e0, e1, {{e0, k1}});             // hop: k_chebyshev_ldos alone; rest: the reduction
     return RSREC_OK;
 }
 
@@ -2303,7 +2363,8 @@ extern "C" int rsrec_exchange(rsrec_t* h, int kind, int npairs, const int32_t* s
     XFER(xfer_h2d(h, d_same, same, (size_t)npairs * sizeof(int32_t)));
     XFER(xfer_h2d(h, d_cb, cbase.data(), (size_t)(npairs + 1) * sizeof(int)));
     std::vector<double> kern;
-    const double ca = (energy_max - energy_min) / (double)(2.0f - 0.3f), cb = (energy_max + energy_min) / 2;    // chebyshev_green_ij's scaling
+    double ca, cb;
+    chebyshev_green_scaling(energy_min, energy_max, ca, cb);       // chebyshev_green_ij's scaling
     if (kind == 1) {
         if (nm > (int)((64 * 1024) / sizeof(double2))) return fail(h, RSREC_ERR_ARG, "rsrec_exchange: lld = %d too deep for the Chebyshev phase table", lld);
         kern = chebyshev_green_kernel(nm);

@@ -120,6 +120,29 @@ class Green:
                                                 _ptr(mu), _ptr(g0)))
         return g0
 
+    def chebyshev_ldos(self, site_offset=0, nsites_total=None, out=None):
+        """The LDOS stage for the sites of the last ``chebyshev_recur`` call, on the device from the moments that call left there:
+        the diagonal of green%chebyshev_green -> the reduction of bands%calculate_fermi (bands.f90:258-268).  Returns a dict with the
+        zero-padded images ``dtot(nen)``, ``dosia(nsites_total, nen)``, ``dosial(nsites_total, 18, nen)``, as ``block_ldos`` does.
+        ``out`` = (dtot, dosia, dosial) raw DEVICE addresses: the images are written there in place."""
+        import ctypes as C
+        rec = self.recursion
+        start, end = rec._my_sites()[:2]
+        n = end - start + 1
+        ntot = n + site_offset if nsites_total is None else nsites_total
+        nen = len(self.ene)
+        if out is None:
+            dtot = np.zeros(nen)
+            dosia = np.zeros((ntot, nen), order="F")
+            dosial = np.zeros((ntot, 18, nen), order="F")
+            ptrs = (_ptr(dtot), _ptr(dosia), _ptr(dosial))
+        else:
+            dtot = dosia = dosial = None
+            ptrs = tuple(C.c_void_p(int(p)) for p in out)
+        rec._check(rec._L.rsrec_chebyshev_ldos(rec._h, nen, _ptr(self.ene), float(rec.en.energy_min), float(rec.en.energy_max),
+                                               int(site_offset), int(ntot), ptrs[0], ptrs[1], ptrs[2]))
+        return dict(dtot=dtot, dosia=dosia, dosial=dosial)
+
     def ldos(self):
         """Orbital-resolved local density of states, -Im g0_jj / pi (density_of_states.f90:248-260)."""
         d = np.arange(18)
