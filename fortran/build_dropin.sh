@@ -11,6 +11,7 @@
 # A maintainer's version of this recipe is a CMake diff of a dozen lines.
 #
 # Outputs (oracle/_ref/dropin/, git-ignored like the rest of oracle/_ref: they contain reference object code):
+#   oracle/_ref/damping_gpu.x       = tests/fortran/damping_gpu_driver.f90 on the same objects (tests/test_damping_dropin.py)
 #   oracle/_ref/rslmto_dropin.x     = the reference's main program + librsrec behind its recursion / green / bands / hamiltonian / lattice / density_of_states / exchange / conductivity modules
 set -euo pipefail
 HERE="$(cd "$(dirname "$0")" && pwd)"
@@ -60,4 +61,10 @@ ref main.f90
 "$FC" "$OUT/obj/main.o" $LIBOBJS -fopenmp -L"$MKLDIR" -lmkl_rt -Wl,-rpath,"$MKLDIR" \
   -L"$ROOT/rslmtoasa_amd" -lrsrec -Wl,-rpath,'$ORIGIN/../../rslmtoasa_amd' -Wl,-rpath,/opt/rocm/lib \
   -o "$ROOT/oracle/_ref/rslmto_dropin.x"
+# tests/fortran/damping_gpu_driver.f90: the exchange flow up to the pair recursion, then calculate_gilbert_damping / calculate_jij_auxgreen
+# (which the reference's main program leaves commented out), on the same object set
+fc "$ROOT/tests/fortran/damping_gpu_driver.f90" damping_gpu_driver
+"$FC" "$OUT/obj/damping_gpu_driver.o" $LIBOBJS -fopenmp -L"$MKLDIR" -lmkl_rt -Wl,-rpath,"$MKLDIR" \
+  -L"$ROOT/rslmtoasa_amd" -lrsrec -Wl,-rpath,'$ORIGIN/../../rslmtoasa_amd' -Wl,-rpath,/opt/rocm/lib \
+  -o "$ROOT/oracle/_ref/damping_gpu.x"
 echo "built $ROOT/oracle/_ref/rslmto_dropin.x (zero-edit drop-in: the reference's own main program)"

@@ -13,6 +13,19 @@
 !                                 :1061-1131 and fort.150 in the reference's formats and order
 ! What stays on the host is O(pairs): the T_comm images and the formatting, plus fort.150's cumulative J of the rank's pairs (one real
 ! per pair and energy, 20 KB per pair at 2500 energies) between the two routines.
+!   calculate_gilbert_damping   : (:613-743) the nsp == 2 guard and hamiltonian%torque_operator_collinear on the host, then one
+!                                 rsrec_damping call on the same resident chains for the rank's pairs (the traces of :674-694 without
+!                                 gij / gji or the seven temporaries), the reduction of its images over the ranks, and the reference's
+!                                 tail (:695-733): the nearest-energy search, the stdout lines, alldampings.out and damping-energy.out
+!                                 in its formats, written by rank 0.
+!                                 One deliberate deviation: the reference never initialises spin_i in this routine, so it starts
+!                                 undefined and accumulates across the pairs; here it starts at zero for every pair.
+!                                 damping-energy.out uses the last pair's factor, as the reference's code does.
+!   calculate_moment_of_inertia, calculate_jij_auxgreen, calculate_jijk : these read green%gij / gji ..., which the constructor
+!                                 released.  Each is a wrapper: green_gpu%fetch_intersite first (the host arrays, allocated and filled by
+!                                 the inherited calculate_intersite_gf / _twoindex from the recursion's host coefficients), then the
+!                                 inherited routine.  None is ported to the device; the moment of inertia in particular defines no
+!                                 result to match (its final loop indexes with nv after the energy loop has ended, :869-882).
 ! Errors of the library become g_logger%fatal, the reference's error behaviour on this path.
 !------------------------------------------------------------------------------
 module exchange_gpu_mod
@@ -42,6 +55,10 @@ module exchange_gpu_mod
    contains
       procedure :: calculate_exchange => gpu_calculate_exchange
       procedure :: calculate_exchange_twoindex => gpu_calculate_exchange_twoindex
+      procedure :: calculate_gilbert_damping => gpu_calculate_gilbert_damping
+      procedure :: calculate_moment_of_inertia => gpu_calculate_moment_of_inertia
+      procedure :: calculate_jij_auxgreen => gpu_calculate_jij_auxgreen
+      procedure :: calculate_jijk => gpu_calculate_jijk
    end type exchange_gpu
 
    interface exchange_gpu
@@ -304,5 +321,137 @@ contains
       call MPI_BARRIER(MPI_COMM_WORLD, ierr)
 #endif
    end subroutine gpu_calculate_exchange_twoindex
+
+   !> calculate_gilbert_damping (:613-743)
+   subroutine gpu_calculate_gilbert_damping(this)
+      class(exchange_gpu) :: this
+      integer :: nloc, nen, njij, p, ij, side, i, j, k, nv, ief, ikind, lmaxi
+      integer(c_int) :: rc, sym_i
+      type(c_ptr) :: ctx
+      real(rp) :: spin_i, diff, factor, distance_alat
+      integer(c_int), dimension(:), allocatable, target :: same
+      real(rp), dimension(:), allocatable, target :: ene
+      complex(rp), dimension(:, :, :, :, :), allocatable, target :: tmat
+      real(rp), dimension(:, :), allocatable, target :: at_ef, total
+
+      if (this%control%nsp .ne. 2) return ! check if spin-orbit (l.s) is enabled
+
+      call this%hamiltonian%torque_operator_collinear() ! the torque operators for all NTYPE
+      nen = size(this%en%ene)
+      njij = this%lattice%njij
+      nloc = end_atom - start_atom + 1
+      select case (this%control%recur)
+      case ('block')
+         ikind = 0
+      case ('chebyshev')
+         ikind = 1
+      case default
+         call g_logger%fatal('exchange_gpu: control%recur '//trim(this%control%recur)//' has no pair recursion', __FILE__, __LINE__)
+      end select
+      ! :695-702, the closest energy point of the Fermi level (the same for every pair)
+      ief = 0; diff = 1000.0_rp
+      do nv = 1, nen
+         if (abs(this%en%ene(nv) - this%en%fermi) .lt. diff) then
+            diff = abs(this%en%ene(nv) - this%en%fermi)
+            ief = nv
+         end if
+      end do
+      allocate (at_ef(18, njij), total(9, nen))
+      at_ef = 0.0_rp; total = 0.0_rp
+      if (nloc > 0) then
+         allocate (same(nloc), ene(nen), tmat(18, 18, 3, 2, nloc))
+         ene(:) = this%en%ene(1:nen)
+         do ij = start_atom, end_atom
+            p = ij - start_atom + 1
+            same(p) = 0
+            if (this%lattice%ijpair(ij, 1) == this%lattice%ijpair(ij, 2)) same(p) = 1
+            do side = 1, 2
+               tmat(:, :, :, side, p) = this%hamiltonian%tmat(:, :, :, this%lattice%iz(this%lattice%ijpair(ij, side)))
+            end do
+         end do
+         sym_i = 0
+         if (this%control%sym_term) sym_i = 1
+         ctx = rsrec_gpu_context()
+         call g_timer%start('damping-gpu')
+         ! coefficients and terminators NULL: the chains recur_b_ij / chebyshev_recur_ij left on the device (i == j pairs: one chain)
+         rc = rsrec_damping(ctx, int(ikind, c_int), int(nloc, c_int), c_loc(same), int(this%control%lld, c_int), int(nen, c_int), &
+                            c_loc(ene), int(ief, c_int), sym_i, real(this%en%energy_min, c_double), real(this%en%energy_max, c_double), &
+                            c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_loc(tmat), int(start_atom - 1, c_int), int(njij, c_int), &
+                            c_loc(at_ef), c_loc(total), c_null_ptr)
+         call g_timer%stop('damping-gpu')
+         if (rc /= 0) call g_logger%fatal('exchange_gpu: rsrec_damping: '//rsrec_error_string(ctx), __FILE__, __LINE__)
+      end if
+#ifdef USE_MPI
+      call MPI_ALLREDUCE(MPI_IN_PLACE, at_ef, product(shape(at_ef)), MPI_DOUBLE_PRECISION, MPI_SUM, MPI_COMM_WORLD, ierr)
+      call MPI_ALLREDUCE(MPI_IN_PLACE, total, product(shape(total)), MPI_DOUBLE_PRECISION, MPI_SUM, MPI_COMM_WORLD, ierr)
+#endif
+
+      if (rank == 0) then
+         open (UNIT=103, FILE='damping-energy.out', STATUS='replace', ACTION='write')
+         open (UNIT=104, FILE='alldampings.out', STATUS='replace', ACTION='write')
+         write (104, *) '    #i     #j   #xx          #xy           #xz           '// &
+            '#yx           #yy           #yz           #zx           #zy           '// &
+            '#zz          #0.5*(xx + yy)     #Dist           #rij = (ri - rj)'
+         factor = 0.0_rp
+         do ij = 1, njij
+            i = this%lattice%ijpair(ij, 1)
+            j = this%lattice%ijpair(ij, 2)
+            distance_alat = norm2(this%lattice%cr(:, i) - this%lattice%cr(:, j))
+            lmaxi = this%symbolic_atom(this%lattice%iz(i))%potential%lmax
+            ! the spin magnetic moment of the i-th atom, from zero for every pair (see the file header)
+            spin_i = 0.0_rp
+            do k = 0, lmaxi
+               spin_i = spin_i + this%symbolic_atom(this%lattice%iz(i))%potential%ql(1, k, 1) - &
+                        this%symbolic_atom(this%lattice%iz(i))%potential%ql(1, k, 2)
+            end do
+            factor = (-0.25_rp)*(2.0_rp/(pi*spin_i))
+            write (*, '(A,I6,A,I6,A)') 'Damping tensor between pair', i, ' and ', j, ' is'
+            write (*, '(3F14.9)') factor*at_ef(1:9, ij)
+            write (*, '(A,I6,A,I6,A)') 'Imaginary part of the tensor between pair', i, ' and ', j, ' is'
+            write (*, '(3F14.9)') factor*at_ef(10:18, ij)
+            write (*, *) '----------------------'
+            write (104, '(2I7,11F14.9,3F10.6)') i, j, factor*at_ef(1:9, ij), 0.5*factor*(at_ef(1, ij) + at_ef(5, ij)), &
+               distance_alat, this%lattice%cr(:, i) - this%lattice%cr(:, j)
+            write (*, *) 'ief = ', this%en%ene(ief), 'fermi = ', this%en%fermi
+         end do
+         write (103, *) '#Energy (E-Ef)         #xx         #xy           #xz           '// &
+            '#yx           #yy           #yz           #zx           #zy           #zz'
+         do nv = 1, nen
+            write (103, '(10F14.9)') this%en%ene(nv) - this%en%fermi, factor*total(:, nv)
+         end do
+         close (103)
+         close (104)
+      end if
+#ifdef USE_MPI
+      call MPI_BARRIER(MPI_COMM_WORLD, ierr)
+#endif
+   end subroutine gpu_calculate_gilbert_damping
+
+   !> the host intersite arrays for an inherited routine that reads them (green_gpu%fetch_intersite)
+   subroutine host_intersite(this)
+      class(exchange_gpu), intent(inout) :: this
+      select type (g => this%green)
+      class is (green_gpu)
+         call g%fetch_intersite()
+      end select
+   end subroutine host_intersite
+
+   subroutine gpu_calculate_moment_of_inertia(this)
+      class(exchange_gpu) :: this
+      call host_intersite(this)
+      call this%exchange%calculate_moment_of_inertia()
+   end subroutine gpu_calculate_moment_of_inertia
+
+   subroutine gpu_calculate_jij_auxgreen(this)
+      class(exchange_gpu) :: this
+      call host_intersite(this)
+      call this%exchange%calculate_jij_auxgreen()
+   end subroutine gpu_calculate_jij_auxgreen
+
+   subroutine gpu_calculate_jijk(this)
+      class(exchange_gpu) :: this
+      call host_intersite(this)
+      call this%exchange%calculate_jijk()
+   end subroutine gpu_calculate_jijk
 
 end module exchange_gpu_mod

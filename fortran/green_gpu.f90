@@ -20,6 +20,9 @@
 !> allocated (and zeroed) only when a host routine that fills them runs (`intersite_arrays`).  When `exchange_gpu` (exchange_gpu.f90)
 !> has taken the stage over -- `rsrec_exchange` forms Jij / Dij / Iij straight from the recursion's chains -- `calculate_intersite_gf`
 !> and `_twoindex` allocate and fill nothing; the first keeps only the reference's side effect on the recursion (zsqr, :434).
+!> The inherited routines of `exchange` that still read the host arrays (calculate_moment_of_inertia, calculate_jij_auxgreen,
+!> calculate_jijk) get them through `fetch_intersite`, which `exchange_gpu` calls before each of them: it allocates the arrays and runs
+!> the inherited `calculate_intersite_gf` / `_twoindex` on the recursion's host coefficients (the idea of bands_gpu's `fetch_g0`).
 !------------------------------------------------------------------------------
 module green_gpu_mod
    use, intrinsic :: iso_c_binding
@@ -45,12 +48,18 @@ module green_gpu_mod
       logical :: stale_is_chebyshev = .false.   ! which routine postponed it: chebyshev_green (else block_green)
       !> .true. once exchange_gpu owns the intersite stage (its constructor, `release_intersite`)
       logical :: intersite_on_device = .false.
+      !> .true. once fetch_intersite has filled the host arrays from the present coefficients
+      logical :: intersite_fetched = .false.
+      !> recursion%b2_b as it was before the first zsqr of the on-device branch (B^2; 0.4 MB per pair at lld 20): fetch_intersite puts it
+      !> back before the inherited calculate_intersite_gf, which takes the root itself (:434)
+      complex(rp), dimension(:, :, :, :), allocatable :: b2_unrooted
    contains
       procedure :: restore_to_default => gpu_restore_to_default
       procedure :: calculate_intersite_gf => gpu_calculate_intersite_gf
       procedure :: calculate_intersite_gf_twoindex => gpu_calculate_intersite_gf_twoindex
       procedure :: calculate_intersite_gf_eta => gpu_calculate_intersite_gf_eta
       procedure :: release_intersite => gpu_release_intersite
+      procedure :: fetch_intersite => gpu_fetch_intersite
       procedure :: bgreen => gpu_bgreen
       procedure :: block_green => gpu_block_green
       procedure :: chebyshev_green => gpu_chebyshev_green
@@ -302,6 +311,8 @@ contains
    subroutine gpu_release_intersite(this)
       class(green_gpu), intent(inout) :: this
       this%intersite_on_device = .true.
+      this%intersite_fetched = .false.
+      if (allocated(this%b2_unrooted)) deallocate (this%b2_unrooted)
       if (allocated(this%gij)) deallocate (this%gij, this%gji, this%ginmag, this%gjnmag, this%gix, this%giy, this%giz, this%gjx, &
                                            this%gjy, this%gjz, this%g00ij, this%g00ji, this%g01ij, this%g01ji, this%gx0ij, this%gy0ij, &
                                            this%gz0ij, this%gx1ij, this%gy1ij, this%gz1ij, this%gx0ji, this%gy0ji, this%gz0ji, &
@@ -314,12 +325,40 @@ contains
    subroutine gpu_calculate_intersite_gf(this)
       class(green_gpu), intent(inout) :: this
       if (this%intersite_on_device) then
-         if (this%control%recur == 'block') call this%recursion%zsqr()
+         if (this%control%recur == 'block') then
+            if (.not. allocated(this%b2_unrooted)) this%b2_unrooted = this%recursion%b2_b
+            call this%recursion%zsqr()
+         end if
+         this%intersite_fetched = .false.
          return
       end if
       call intersite_arrays(this)
       call this%green%calculate_intersite_gf()
    end subroutine gpu_calculate_intersite_gf
+
+   !> The host intersite arrays, now: for the inherited routines of `exchange` that read `gij / gji / ginmag ...` after exchange_gpu
+   !> released them.  Allocates the 24 arrays and runs the inherited calculate_intersite_gf and _twoindex on the recursion's host
+   !> coefficients.  The inherited routine roots b2_b itself (block, :434): where the on-device branch above has rooted it already, B^2
+   !> is put back first, so the arrays carry the bits of a run with the plain types and b2_b is left rooted once, as before.
+   !> A no-op while the arrays are up to date; a new pair recursion is followed by a new calculate_intersite_gf, which marks them stale.
+   subroutine gpu_fetch_intersite(this)
+      class(green_gpu), intent(inout) :: this
+      if (.not. this%intersite_on_device) return              ! the host stage is the reference's own: its arrays are the caller's business
+      if (this%intersite_fetched .and. allocated(this%gij)) return
+      call intersite_arrays(this)
+      if (this%control%recur == 'block') then
+         if (allocated(this%b2_unrooted)) then
+            this%recursion%b2_b = this%b2_unrooted
+         else
+            this%b2_unrooted = this%recursion%b2_b
+         end if
+      end if
+      call g_timer%start('fetch-intersite')
+      call this%green%calculate_intersite_gf()
+      call this%green%calculate_intersite_gf_twoindex()
+      call g_timer%stop('fetch-intersite')
+      this%intersite_fetched = .true.
+   end subroutine gpu_fetch_intersite
 
    !> green.f90:386-423: nothing to do when exchange_gpu owns the stage.
    subroutine gpu_calculate_intersite_gf_twoindex(this)

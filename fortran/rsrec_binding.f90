@@ -184,6 +184,18 @@ module rsrec_binding
          integer(c_int) :: rc
       end function
 
+      ! torque-correlation damping traces of the rank's pairs on the same chains (exchange.f90:674-694); the prefactor stays the caller's
+      function rsrec_damping(handle, kind, npairs, same, lld, nen, ene, ief, sym_term, energy_min, energy_max, a_inf, b_inf, &
+                             coef_a, coef_b, tmat, pair_offset, npairs_total, at_ef, total, rows) &
+         bind(C, name='rsrec_damping') result(rc)
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: handle
+         integer(c_int), value :: kind, npairs, lld, nen, ief, sym_term, pair_offset, npairs_total
+         real(c_double), value :: energy_min, energy_max
+         type(c_ptr), value :: same, ene, a_inf, b_inf, coef_a, coef_b, tmat, at_ef, total, rows
+         integer(c_int) :: rc
+      end function
+
       function rsrec_kubo_moments(handle, nvec, nseed, seed_atoms, seed_coef, cond_ll, a, b, v_a, vo_a, v_b, vo_b, mu_nm) &
          bind(C, name='rsrec_kubo_moments') result(rc)
          import :: c_int, c_ptr, c_double

@@ -262,6 +262,26 @@ int rsrec_exchange(rsrec_t *h, int kind, int npairs, const int32_t *same, int ll
                    const double *coef_b, const double *dpar, int pair_offset, int npairs_total, double *xc, double *so, double *fo,
                    double *parts, double *jcum, double *integrand);
 
+/* Gilbert damping (torque correlation) of the pairs of one rank: the traces of exchange%calculate_gilbert_damping (exchange.f90:674-694)
+ * on the chains rsrec_exchange reads, without gij / gji (kernels_exchange.hpp: a second epilogue on g0 of a pair's chains in LDS).  Per
+ * pair and energy, with Aij = gij - gji^H and Aji = gji - gij^H:
+ *   row m = 3 (k-1) + l, k, l = 1..3:  Tr( tmati(:,:,k) Aij  tmatj(:,:,l)^H Aji ),  rows 1..9 its real parts (dtott), 10..18 its imaginary
+ *   parts (dtottim).  The prefactor -0.25 * 2 / (pi spin_i) is NOT applied: it is the caller's.
+ *   kind, same, lld, nen, ene, sym_term, energy_min, energy_max, a_inf, b_inf, coef_a, coef_b, pair_offset, npairs_total: as rsrec_exchange
+ *               (coef_a and coef_b NULL: the resident chains of the last seeded call; the same compaction and terminator rules)
+ *   ief         : 1-based index into ene of the energy whose rows go to at_ef (the reference's point nearest the Fermi level)
+ *   tmat        : complex (18,18,3,2,npairs): hamiltonian%tmat(:,:,:,iz) of atom i (side 1) and atom j (side 2) of every pair
+ *   at_ef       : real (18,npairs_total) out: the 18 rows at ene(ief), this rank's pairs in their columns of the zero-padded image
+ *   total       : real (9,nen) out: total_damping = the sum of dtott over THIS call's pairs, added in ascending pair order (:690-694)
+ *   rows        : real (18,nen,npairs) out or NULL: every row at every energy
+ * Every array may be host or device memory.  Pairs run in chunks: the device memory that scales with energies is bounded independent of
+ * npairs; tmat is staged per chunk.  Every sum runs in a fixed order without atomics: two calls give the same bits, a pair's rows do not
+ * depend on the other pairs of the call, and total does not depend on the chunking.  Errors as rsrec_exchange.  rsrec_get_timing: out[0]
+ * device ms of the call, out[5] ms in the Green + trace + reduction kernels. */
+int rsrec_damping(rsrec_t *h, int kind, int npairs, const int32_t *same, int lld, int nen, const double *ene, int ief, int sym_term,
+                  double energy_min, double energy_max, const double *a_inf, const double *b_inf, const double *coef_a, const double *coef_b,
+                  const double *tmat, int pair_offset, int npairs_total, double *at_ef, double *total, double *rows);
+
 /* One whole-vector product on caller arrays psi(18,18,kk) (complex, the reference's layout):
  *   vel = 0 : psi_out = (H psi_in - b psi_in)/a      ham_vec_matmul (:913) / ham_hoh_vec_matmul (:785); v_op, vo_op ignored
  *   vel = 1 : psi_out = V psi_in                      velo_vec_matmul (:587, 'n') / velo_hoh_vec_matmul (:656) with v_op (and vo_op with hoh)

@@ -41,6 +41,8 @@ _SIGNATURES = {
     "rsrec_kubo_moments": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double] + [C.c_void_p] * 5),
     "rsrec_exchange": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double]
                        + [C.c_void_p] * 5 + [C.c_int, C.c_int] + [C.c_void_p] * 6),
+    "rsrec_damping": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double]
+                      + [C.c_void_p] * 5 + [C.c_int, C.c_int] + [C.c_void_p] * 3),
     "rsrec_kubo_integrand": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_void_p]),
     "rsrec_apply_operator": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double]),
     "rsrec_zsqr": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),

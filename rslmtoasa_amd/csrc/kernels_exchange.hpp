@@ -43,6 +43,18 @@ __device__ __forceinline__ void xc_trace_pair(int t, int& ma, int& mb) {
 // the reflection 2*j0 - j of calculate_intersite_gf_twoindex (0-based): l = 0 (s), 1 (p: 1..3), 2 (d: 4..8); m -> -m within the shell
 __device__ __forceinline__ int xc_refl(int j) { const int j0 = j == 0 ? 0 : (j < 4 ? 2 : 6); return 2 * j0 - j; }
 
+// Element idx of gij (side 0) or gji (side 1) from g0 of the pair's chains, M(w) = Mb + w * stride (green.f90:446-453); an i == j pair
+// reads chain 1 alone.  Shared by the exchange and the damping epilogue.
+__device__ __forceinline__ double2 xc_gpair(const double2* Mb, int stride, bool same, int side, int idx) {
+#pragma clang fp contract(off)
+    const double2 g1 = Mb[idx];
+    if (same) return g1;
+    const double2 g2 = Mb[stride + idx], g3 = Mb[2 * stride + idx], g4 = Mb[3 * stride + idx];
+    const double2 dd = make_double2(g1.x - g2.x, g1.y - g2.y);
+    const double2 s = make_double2(g3.y - g4.y, (-g3.x) - (-g4.x));          // 1/i g3 - 1/i g4
+    return side == 0 ? make_double2((dd.x + s.x) * 0.5, (dd.y + s.y) * 0.5) : make_double2((dd.x - s.x) * 0.5, (dd.y - s.y) * 0.5);
+}
+
 // Workgroup epilogue (256 threads); no FMA contraction, so the elementwise arithmetic is the reference's operation by operation (the
 // traces sum in their own fixed order).  M(w) = Mb + w * stride holds g0 of chain w (column-major 18 x 18); S(w) = Sb + w * stride is free
 // scratch of 324 complex.  Both are overwritten.  dpar: (4, 3, 2) of the pair; out: the 41 integrand rows of this (pair, energy).
@@ -66,14 +78,7 @@ __device__ __forceinline__ void xc_epilogue(double2* Mb, double2* Sb, int stride
         double2 v[4];                                  // gij or gji at (j,i), (j+9,i+9), (j,i+9), (j+9,i)
         const int idx[4] = {j + NB * i, (j + 9) + NB * (i + 9), j + NB * (i + 9), (j + 9) + NB * i};
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const double2 g1 = Mb[idx[r]];
-            if (same) { v[r] = g1; continue; }
-            const double2 g2 = Mb[stride + idx[r]], g3 = Mb[2 * stride + idx[r]], g4 = Mb[3 * stride + idx[r]];
-            const double2 dd = make_double2(g1.x - g2.x, g1.y - g2.y);
-            const double2 s = make_double2(g3.y - g4.y, (-g3.x) - (-g4.x));          // 1/i g3 - 1/i g4
-            v[r] = side == 0 ? make_double2((dd.x + s.x) * 0.5, (dd.y + s.y) * 0.5) : make_double2((dd.x - s.x) * 0.5, (dd.y - s.y) * 0.5);
-        }
+        for (int r = 0; r < 4; ++r) v[r] = xc_gpair(Mb, stride, same, side, idx[r]);
         double2 p;
         if (comp == 0) p = make_double2((v[0].x + v[1].x) * 0.5, (v[0].y + v[1].y) * 0.5);
         else if (comp == 3) p = make_double2(0.5 * (v[0].x - v[1].x), 0.5 * (v[0].y - v[1].y));
@@ -139,6 +144,21 @@ __device__ __forceinline__ void xc_epilogue(double2* Mb, double2* Sb, int stride
     }
 }
 
+// Green stage of kind 0 for one (pair, energy): wave w of the 256 threads runs chain chain0 + w through block_green_wave with eta = 0 and
+// leaves g0 in lds[w].M; an i == j pair runs wave 0 only.  Ends with a workgroup barrier.
+constexpr int PAIR_BLOCK_STRIDE = (int)(sizeof(GreenLds) / sizeof(double2));
+static_assert(sizeof(GreenLds) % sizeof(double2) == 0, "GreenLds stride");
+__device__ __forceinline__ void pair_green_block(GreenLds* lds, bool same, double e, int chain0, int lld, int sym_term, const double* __restrict__ a_inf,
+                                                 const double* __restrict__ b_inf, const double2* __restrict__ a_b, const double2* __restrict__ b_sqrt) {
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (wave == 0 || !same) {
+        const bool act = lane < 54;
+        const int ig = act ? lane / 6 : 8, jg = act ? lane % 6 : 5;
+        block_green_wave(lds[wave], lane, ig, jg, act, e, chain0 + wave, lld, 0.0, 0.0, sym_term, a_inf, b_inf, a_b, b_sqrt);
+    }
+    __syncthreads();
+}
+
 // kind 0.  grid = (nen, npairs), 256 threads: wave w runs chain w of the pair through green%bgreen (eta = 0: block_green_ij, green.f90:354-384)
 // on k_block_green's path; an i == j pair runs chain 1 only (calculate_intersite_gf reads g0(:,:,:,1) alone, and recur_b_ij leaves slots
 // 2..4 zero).  a_b, b_sqrt, a_inf, b_inf: the chains of the launch; the pair's first chain is cbase[pair] - cb0 (4 per pair, or 1 for
@@ -150,16 +170,9 @@ __global__ __launch_bounds__(256, GREEN_WAVES_PER_SIMD) void k_exchange_block(in
                                                                            const double* __restrict__ dpar, double* __restrict__ integ) {
     __shared__ GreenLds lds[4];
     __shared__ XcShared xs;
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int ie = blockIdx.x, pair = blockIdx.y;
-    if (wave == 0 || same[pair] == 0) {
-        const bool act = lane < 54;
-        const int ig = act ? lane / 6 : 8, jg = act ? lane % 6 : 5;
-        block_green_wave(lds[wave], lane, ig, jg, act, ene[ie], cbase[pair] - cb0 + wave, lld, 0.0, 0.0, sym_term, a_inf, b_inf, a_b, b_sqrt);
-    }
-    __syncthreads();
-    constexpr int stride = (int)(sizeof(GreenLds) / sizeof(double2));
-    static_assert(sizeof(GreenLds) % sizeof(double2) == 0, "GreenLds stride");
+    pair_green_block(lds, same[pair] != 0, ene[ie], cbase[pair] - cb0, lld, sym_term, a_inf, b_inf, a_b, b_sqrt);
+    constexpr int stride = PAIR_BLOCK_STRIDE;
     // (same and e are read again here rather than held across the continued fraction: the kernel then stays within k_block_green's registers)
     xc_epilogue(lds[0].M, lds[0].B, stride, xs, same[pair] != 0, ene[ie], dpar + (size_t)24 * pair, integ + ((size_t)pair * nen + ie) * XC_NINT);
 }
@@ -170,6 +183,21 @@ struct XcChebLds {
     double2 g[4][BLK];
     double2 s[4][BLK];
 };
+// Green stage of kind 1 for one (pair, energy): the phase table into ef (nm entries), then g0 of the pair's chains (1 for an i == j pair)
+// into cl.g.  mu: the pair's first chain.  Ends with a workgroup barrier.
+__device__ __forceinline__ void pair_green_cheb(XcChebLds& cl, double2* ef, int nm, double e, double a, double b, const double* __restrict__ kern,
+                                                const double2* __restrict__ mu, bool same) {
+    const double th = acos((e - b) / a);
+    for (int i = threadIdx.x; i < nm; i += blockDim.x) ef[i] = chebyshev_phase(i, th, kern[i]);
+    __syncthreads();
+    const double den = sqrt(a * a - (e - b) * (e - b));
+    const int nch = same ? 1 : 4;
+    for (int it = threadIdx.x; it < nch * BLK; it += blockDim.x) {
+        const int c = it / BLK, el = it % BLK;
+        cl.g[c][el] = chebyshev_green_elem(mu + (size_t)c * nm * BLK, ef, nm, el, den);
+    }
+    __syncthreads();
+}
 __global__ __launch_bounds__(256) void k_exchange_cheb(int nm, int nen, const double* __restrict__ ene, double a, double b, const double* __restrict__ kern,
                                                       const double2* __restrict__ mu, const int* __restrict__ same, const int* __restrict__ cbase, int cb0,
                                                       const double* __restrict__ dpar, double* __restrict__ integ) {
@@ -179,16 +207,7 @@ __global__ __launch_bounds__(256) void k_exchange_cheb(int nm, int nen, const do
     const int ie = blockIdx.x, pair = blockIdx.y;
     const bool sm = same[pair] != 0;
     const double e = ene[ie];
-    const double th = acos((e - b) / a);
-    for (int i = threadIdx.x; i < nm; i += blockDim.x) ef[i] = chebyshev_phase(i, th, kern[i]);
-    __syncthreads();
-    const double den = sqrt(a * a - (e - b) * (e - b));
-    const int nch = sm ? 1 : 4;
-    for (int it = threadIdx.x; it < nch * BLK; it += blockDim.x) {
-        const int c = it / BLK, el = it % BLK;
-        cl.g[c][el] = chebyshev_green_elem(mu + (size_t)(cbase[pair] - cb0 + c) * nm * BLK, ef, nm, el, den);
-    }
-    __syncthreads();
+    pair_green_cheb(cl, ef, nm, e, a, b, kern, mu + (size_t)(cbase[pair] - cb0) * nm * BLK, sm);
     xc_epilogue(&cl.g[0][0], &cl.s[0][0], BLK, xs, sm, e, dpar + (size_t)24 * pair, integ + ((size_t)pair * nen + ie) * XC_NINT);
 }
 
@@ -270,6 +289,118 @@ __global__ __launch_bounds__(128) void k_exchange_integrate(int nen, int nv1, co
             A = H * A / 3.0;
             jcum[(size_t)(jcol0 + pair) * nen + n] = A * 1.0e3 / 4.0 / pi;
         }
+    }
+}
+
+// ---- Gilbert damping (torque correlation): exchange%calculate_gilbert_damping (exchange.f90:674-694) on the same g0 ----
+//   Aij = gij - gji^H,  Aji = gji - gij^H,  X_k = T_i^k Aij,  Y_l = (T_j^l)^H Aji,  row m = 3 k + l:  Tr(X_k Y_l) = sum_ab X_k(a,b) Y_l(b,a)
+// with the dense 18 x 18 torque matrices of the two atoms' types.  The product X_k Y_l (the reference's temp3) is never formed.
+// Rows per (pair, energy): 0..8 the real parts (dtott, l fastest), 9..17 the imaginary parts (dtottim).
+constexpr int DP_NROW = 18;
+constexpr int DP_TMAT = 6 * BLK;      // complex elements of tmat per pair: (18, 18, 3, side)
+
+struct DampShared {
+    double2 rows[9 * NB];             // row sums of the nine traces, [m][a]
+};
+
+// Workgroup epilogue (256 threads), every sum in a fixed order; no FMA contraction.  M(w), S(w) as in xc_epilogue: both are overwritten
+// (gij, gji -> S(0), S(1);  Aij, Aji -> M(0), M(1);  X_1..3 -> S(0..2);  Y_1..3 -> S(3), M(2), M(3)).  tm: (18, 18, 3, 2) of the pair.
+__device__ __forceinline__ void damping_epilogue(double2* Mb, double2* Sb, int stride, DampShared& ds, bool same, const double2* __restrict__ tm,
+                                                 double* __restrict__ out) {
+#pragma clang fp contract(off)
+    const int t = threadIdx.x;
+#pragma unroll 1
+    for (int it = t; it < 2 * BLK; it += 256) {
+        const int side = it / BLK, el = it % BLK;
+        Sb[side * stride + el] = xc_gpair(Mb, stride, same, side, el);
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int it = t; it < 2 * BLK; it += 256) {                        // A(r,c) = G(r,c) - conjg(G'(c,r))
+        const int side = it / BLK, el = it % BLK, r = el % NB, c = el / NB;
+        const double2 g = Sb[side * stride + el], o = Sb[(1 - side) * stride + c + NB * r];
+        Mb[side * stride + el] = make_double2(g.x - o.x, g.y - (-o.y));
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int it = t; it < 6 * BLK; it += 256) {
+        const int q = it / BLK, el = it % BLK, r = el % NB, c = el / NB, side = q / 3;
+        const double2* T = tm + (size_t)q * BLK;
+        const double2* A = Mb + side * stride + NB * c;
+        double sr = 0.0, si = 0.0;
+        for (int b = 0; b < NB; ++b) {
+            double2 x = side == 0 ? T[r + NB * b] : T[b + NB * r];
+            if (side) x.y = -x.y;                                      // transpose(conjg(tmatj))
+            const double2 y = A[b];
+            sr += x.x * y.x - x.y * y.y;
+            si += x.x * y.y + x.y * y.x;
+        }
+        (q < 4 ? Sb + q * stride : Mb + (q - 2) * stride)[el] = make_double2(sr, si);
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int it = t; it < 9 * NB; it += 256) {
+        const int m = it / NB, a = it % NB, k = m / 3, l = m % 3;
+        const double2* X = Sb + k * stride;
+        const double2* Y = (l == 0 ? Sb + 3 * stride : Mb + (l + 1) * stride) + NB * a;
+        double sr = 0.0, si = 0.0;
+        for (int b = 0; b < NB; ++b) {
+            const double2 x = X[a + NB * b], y = Y[b];
+            sr += x.x * y.x - x.y * y.y;
+            si += x.x * y.y + x.y * y.x;
+        }
+        ds.rows[it] = make_double2(sr, si);
+    }
+    __syncthreads();
+    if (t < 9) {
+        double sr = 0.0, si = 0.0;
+        for (int a = 0; a < NB; ++a) { sr += ds.rows[t * NB + a].x; si += ds.rows[t * NB + a].y; }
+        out[t] = sr;
+        out[9 + t] = si;
+    }
+}
+
+// The exchange kernels' grid and Green stage, the damping epilogue.  tmat: [pair][side][k][18 x 18]; rows: [pair][nen][18].
+__global__ __launch_bounds__(256, GREEN_WAVES_PER_SIMD) void k_damping_block(int lld, int nen, const double* __restrict__ ene, int sym_term,
+                                                                          const double* __restrict__ a_inf, const double* __restrict__ b_inf,
+                                                                          const double2* __restrict__ a_b, const double2* __restrict__ b_sqrt,
+                                                                          const int* __restrict__ same, const int* __restrict__ cbase, int cb0,
+                                                                          const double2* __restrict__ tmat, double* __restrict__ rows) {
+    __shared__ GreenLds lds[4];
+    __shared__ DampShared ds;
+    const int ie = blockIdx.x, pair = blockIdx.y;
+    pair_green_block(lds, same[pair] != 0, ene[ie], cbase[pair] - cb0, lld, sym_term, a_inf, b_inf, a_b, b_sqrt);
+    damping_epilogue(lds[0].M, lds[0].B, PAIR_BLOCK_STRIDE, ds, same[pair] != 0, tmat + (size_t)DP_TMAT * pair, rows + ((size_t)pair * nen + ie) * DP_NROW);
+}
+
+__global__ __launch_bounds__(256) void k_damping_cheb(int nm, int nen, const double* __restrict__ ene, double a, double b, const double* __restrict__ kern,
+                                                     const double2* __restrict__ mu, const int* __restrict__ same, const int* __restrict__ cbase, int cb0,
+                                                     const double2* __restrict__ tmat, double* __restrict__ rows) {
+    extern __shared__ double2 ef[];
+    __shared__ XcChebLds cl;
+    __shared__ DampShared ds;
+    const int ie = blockIdx.x, pair = blockIdx.y;
+    const bool sm = same[pair] != 0;
+    pair_green_cheb(cl, ef, nm, ene[ie], a, b, kern, mu + (size_t)(cbase[pair] - cb0) * nm * BLK, sm);
+    damping_epilogue(&cl.g[0][0], &cl.s[0][0], BLK, ds, sm, tmat + (size_t)DP_TMAT * pair, rows + ((size_t)pair * nen + ie) * DP_NROW);
+}
+
+// The two reductions the reference prints, for the np pairs of a chunk: total(m, ie) += dtott(m, ie) of the pairs in ascending order
+// (exchange.f90:690-694; the running value carries over from the chunk before, so the sum does not depend on the chunking), and the 18
+// rows of every pair at energy index ief0 (0-based) into column col0 + pair of the image.  One thread per output, no atomics.
+__global__ __launch_bounds__(256) void k_damping_reduce(int nen, int np, int ief0, const double* __restrict__ rows, int col0, double* __restrict__ at_ef,
+                                                        double* __restrict__ total) {
+#pragma clang fp contract(off)
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x, n1 = (size_t)9 * nen, n2 = (size_t)DP_NROW * np;
+    if (i < n1) {
+        const int m = (int)(i % 9);
+        const size_t ie = i / 9;
+        double s = total[i];
+        for (int p = 0; p < np; ++p) s += rows[((size_t)p * nen + ie) * DP_NROW + m];
+        total[i] = s;
+    } else if (i < n1 + n2) {
+        const size_t j = i - n1, p = j / DP_NROW, m = j % DP_NROW;
+        at_ef[(size_t)(col0 + p) * DP_NROW + m] = rows[(p * nen + ief0) * DP_NROW + m];
     }
 }
 }  // namespace rsrec

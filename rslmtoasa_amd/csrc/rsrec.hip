@@ -2301,126 +2301,137 @@ int xc_fetch(rsrec_t* h, const double* src, double* stage, size_t n, const doubl
 
 }  // namespace
 
-// green%calculate_intersite_gf / _twoindex + exchange%calculate_exchange / _twoindex (integrands and integrals) for the pairs of one rank.
-extern "C" int rsrec_exchange(rsrec_t* h, int kind, int npairs, const int32_t* same, int lld, int nen, const double* ene, int nv1, double fermi,
-                              int sym_term, double energy_min, double energy_max, const double* a_inf, const double* b_inf, const double* coef_a,
-                              const double* coef_b, const double* dpar, int pair_offset, int npairs_total, double* xc, double* so, double* fo,
-                              double* parts, double* jcum, double* integrand) {
-    if (!h) return RSREC_ERR_ARG;
-    if (kind < 0 || kind > 1) return fail(h, RSREC_ERR_ARG, "rsrec_exchange: kind %d is neither 0 (block) nor 1 (Chebyshev)", kind);
-    if (npairs < 1 || lld < 1 || nv1 < 1 || !same || !ene || !dpar || !xc || !so || !fo || !parts || pair_offset < 0 || npairs_total < pair_offset + npairs)
-        return fail(h, RSREC_ERR_ARG, "rsrec_exchange: bad argument");
-    if (nen < nv1 + 9) return fail(h, RSREC_ERR_ARG, "rsrec_exchange: nen = %d < nv1 + 9 = %d (simpson_f integrates to nv1 + 10)", nen, nv1 + 9);
-    if ((a_inf == nullptr) != (b_inf == nullptr)) return fail(h, RSREC_ERR_ARG, "rsrec_exchange: give both terminators or neither");
-    if (kind == 0 && (coef_a == nullptr) != (coef_b == nullptr)) return fail(h, RSREC_ERR_ARG, "rsrec_exchange: give both a_b and b_sqrt or neither");
-    if (kind == 0 && !a_inf && lld < 2) return fail(h, RSREC_ERR_ARG, "rsrec_exchange: the device terminator needs lld >= 2");
+namespace {
+
+// Call setup shared by the entry points that run a kernel per (pair, energy) on the four chains of every pair (rsrec_exchange,
+// rsrec_damping): the coefficient-source rules, the compaction of resident i == j pairs, the chunking over pairs and the device buffers.
+//   d_green_in : ene | the call's own inputs (fixed_in) | same | cbase | a_b (or mu_n) | b_sqrt | a_inf (or the Chebyshev kernel) | b_inf |
+//                the chunk's own inputs (chunk_in per pair)                                       (chunk-sized from a_b on)
+//   d_green_out: the rows of the chunk (row_doubles per pair) | the call's own outputs (fixed_out) | chunk_out per pair
+struct PairCall {
+    const char* who;
+    int kind, npairs, lld, nen, nm, P;             // P: pairs per chunk
+    bool resident, compact;
+    std::vector<int> cbase;                        // first chain of every pair
+    size_t cel;                                    // complex elements per chain (each of a_b, b_sqrt / mu_n)
+    double ca, cb;                                 // chebyshev_green_ij's scaling
+    const double *a_inf, *b_inf, *coef_a, *coef_b;
+    double *din, *d_ene, *d_fixed_in, *d_chunk_in, *d_rows, *d_fixed_out, *d_chunk_out;
+    int *d_same, *d_cb;
+    size_t off_ab, off_bs, off_ai, off_bi;
+};
+
+// the chains of one chunk, as the kernels read them
+struct PairChunk {
+    int np, c0;                                    // pairs, first chain
+    const double2 *sa, *sb;                        // a_b and b_sqrt, or mu_n and nullptr
+    const double *ta, *tb;                         // terminators (kind 0), or the Chebyshev kernel weights and nullptr
+};
+
+size_t even(size_t n) { return (n + 1) & ~(size_t)1; }
+
+int pair_call_begin(rsrec_t* h, PairCall& c, const char* who, int kind, int npairs, const int32_t* same, int lld, int nen, const double* ene,
+                    double energy_min, double energy_max, const double* a_inf, const double* b_inf, const double* coef_a, const double* coef_b,
+                    size_t row_doubles, size_t fixed_in, size_t chunk_in, size_t fixed_out, size_t chunk_out) {
+    if (kind < 0 || kind > 1) return fail(h, RSREC_ERR_ARG, "%s: kind %d is neither 0 (block) nor 1 (Chebyshev)", who, kind);
+    if ((a_inf == nullptr) != (b_inf == nullptr)) return fail(h, RSREC_ERR_ARG, "%s: give both terminators or neither", who);
+    if (kind == 0 && (coef_a == nullptr) != (coef_b == nullptr)) return fail(h, RSREC_ERR_ARG, "%s: give both a_b and b_sqrt or neither", who);
+    if (kind == 0 && !a_inf && lld < 2) return fail(h, RSREC_ERR_ARG, "%s: the device terminator needs lld >= 2", who);
+    c.who = who; c.kind = kind; c.npairs = npairs; c.lld = lld; c.nen = nen;
+    c.a_inf = a_inf; c.b_inf = b_inf; c.coef_a = coef_a; c.coef_b = coef_b;
     const int nchains = 4 * npairs;
-    const bool resident = coef_a == nullptr;
+    c.resident = coef_a == nullptr;
     int nsame = 0;
     for (int p = 0; p < npairs; ++p) nsame += same[p] != 0;
     // first chain of every pair: slot order (4 per pair), or -- resident chains of a seeded call that skipped the repeats of i == j
     // pairs (recur_b_ij, recursion.f90:1705) -- 1 chain for such a pair
-    const bool compact = resident && nsame > 0 && h->res_n == nchains - 3 * nsame;
-    if (resident && (h->res_kind != (kind == 0 ? 1 : 2) || (h->res_n != nchains && !compact) || h->res_lld != lld))
-        return fail(h, RSREC_ERR_ARG, "rsrec_exchange: no %s chains of %d pairs at lld = %d resident (call the seeded recursion first)",
+    c.compact = c.resident && nsame > 0 && h->res_n == nchains - 3 * nsame;
+    if (c.resident && (h->res_kind != (kind == 0 ? 1 : 2) || (h->res_n != nchains && !c.compact) || h->res_lld != lld))
+        return fail(h, RSREC_ERR_ARG, "%s: no %s chains of %d pairs at lld = %d resident (call the seeded recursion first)", who,
                     kind == 0 ? "block-Lanczos" : "Chebyshev", npairs, lld);
-    if (compact && a_inf)        // terminators come in slot order (4 per pair); the compacted chains have no slot for the skipped repeats
-        return fail(h, RSREC_ERR_ARG, "rsrec_exchange: resident chains with skipped i == j repeats take no caller terminators (pass NULL)");
-    std::vector<int> cbase(npairs + 1, 0);
-    for (int p = 0; p < npairs; ++p) cbase[p + 1] = cbase[p] + ((compact && same[p]) ? 1 : 4);
+    if (c.compact && a_inf)        // terminators come in slot order (4 per pair); the compacted chains have no slot for the skipped repeats
+        return fail(h, RSREC_ERR_ARG, "%s: resident chains with skipped i == j repeats take no caller terminators (pass NULL)", who);
+    c.nm = 2 * lld + 2;
+    if (kind == 1 && c.nm > (int)((64 * 1024) / sizeof(double2))) return fail(h, RSREC_ERR_ARG, "%s: lld = %d too deep for the Chebyshev phase table", who, lld);
+    c.cbase.assign(npairs + 1, 0);
+    for (int p = 0; p < npairs; ++p) c.cbase[p + 1] = c.cbase[p] + ((c.compact && same[p]) ? 1 : 4);
     HIPCK(h, hipSetDevice(h->device));
-    const int nm = 2 * lld + 2;
-    const size_t cel = kind == 0 ? (size_t)lld * BLK : (size_t)nm * BLK;                // complex elements per chain (each of a_b, b_sqrt / mu_n)
-    const size_t ibytes = (size_t)nen * XC_NINT * sizeof(double);                          // integrand rows of one pair
+    const int nm = c.nm;
+    c.cel = kind == 0 ? (size_t)lld * BLK : (size_t)nm * BLK;
+    const size_t cel = c.cel;
+    const size_t rbytes = row_doubles * sizeof(double);                                    // rows of one pair
     const size_t cbytes = (size_t)4 * cel * sizeof(double2) * (kind == 0 ? 2 : 1);        // coefficients of one pair
-    // pairs per chunk: the integrand scratch <= 256 MiB and the staged coefficients <= 512 MiB, whatever npairs
-    const int P = (int)std::max<size_t>(1, std::min<size_t>((size_t)npairs, std::min(((size_t)256 << 20) / ibytes, ((size_t)512 << 20) / cbytes)));
-    const size_t nimg = (size_t)XC_NOUT * npairs_total;
+    // pairs per chunk: the row scratch <= 256 MiB and the staged coefficients <= 512 MiB, whatever npairs
+    c.P = (int)std::max<size_t>(1, std::min<size_t>((size_t)npairs, std::min(((size_t)256 << 20) / rbytes, ((size_t)512 << 20) / cbytes)));
+    const size_t P = (size_t)c.P;
     release_kubo_buffers(h, true, true);
-    // d_green_in: ene | fermi weights | dpar | same | a_b (or mu_n) | b_sqrt | a_inf | b_inf  (chunk-sized from a_b on)
-    const size_t off_fw = nen, off_dpar = off_fw + nen, off_same = off_dpar + (size_t)24 * npairs, off_cb = off_same + (npairs + 1) / 2 + 1, off_ab = off_cb + (npairs + 2) / 2 + 1;
-    const size_t off_bs = off_ab + (size_t)4 * P * cel * 2, off_ai = off_bs + (kind == 0 ? (size_t)4 * P * cel * 2 : 0), off_bi = off_ai + std::max<size_t>((size_t)4 * P * BLK, nm);
-    const size_t in_doubles = off_bi + (size_t)4 * P * BLK;
-    HIPCK(h, h->d_green_in.reserve(in_doubles * sizeof(double)));
-    // d_green_out: integrand scratch | images (xc, so, fo, parts) | jcum of the chunk
-    const size_t off_img = (size_t)P * nen * XC_NINT, off_jc = off_img + nimg;
-    HIPCK(h, h->d_green_out.reserve((off_jc + (size_t)P * nen) * sizeof(double)));
-    if (resident && kind == 0) HIPCK(h, h->d_bsqrt.reserve((size_t)4 * P * cel * sizeof(double2)));
+    // every region starts at an even double: the kernels read complex numbers as double2
+    const size_t off_fixed = even(nen), off_same = off_fixed + even(fixed_in), off_cb = off_same + even((npairs + 1) / 2 + 1);
+    c.off_ab = off_cb + even((npairs + 2) / 2 + 1);
+    c.off_bs = c.off_ab + 4 * P * cel * 2;
+    c.off_ai = c.off_bs + (kind == 0 ? 4 * P * cel * 2 : 0);
+    c.off_bi = c.off_ai + even(std::max<size_t>(4 * P * BLK, nm));
+    const size_t off_chunk = c.off_bi + 4 * P * BLK;
+    HIPCK(h, h->d_green_in.reserve((off_chunk + P * chunk_in) * sizeof(double)));
+    const size_t off_fo = P * row_doubles, off_co = off_fo + fixed_out;
+    HIPCK(h, h->d_green_out.reserve((off_co + P * chunk_out) * sizeof(double)));
+    if (c.resident && kind == 0) HIPCK(h, h->d_bsqrt.reserve(4 * P * cel * sizeof(double2)));
     HIPCK(h, h->d_status.reserve(64));
     HIPCK(h, hipMemsetAsync(h->d_status.p, 0, 64, h->stream));
-    double* din = h->d_green_in.as<double>();
-    double* dout = h->d_green_out.as<double>();
-    double* d_ene = din;
-    double* d_fw = din + off_fw;
-    double* d_dpar = din + off_dpar;
-    int* d_same = reinterpret_cast<int*>(din + off_same);
-    int* d_cb = reinterpret_cast<int*>(din + off_cb);
-    double* d_int = dout;
-    double* d_img = dout + off_img;
-    double* d_jc = dout + off_jc;
-    XFER(xfer_h2d(h, d_ene, ene, (size_t)nen * sizeof(double)));
-    XFER(xfer_h2d(h, d_dpar, dpar, (size_t)24 * npairs * sizeof(double)));
-    XFER(xfer_h2d(h, d_same, same, (size_t)npairs * sizeof(int32_t)));
-    XFER(xfer_h2d(h, d_cb, cbase.data(), (size_t)(npairs + 1) * sizeof(int)));
-    std::vector<double> kern;
-    double ca, cb;
-    chebyshev_green_scaling(energy_min, energy_max, ca, cb);       // chebyshev_green_ij's scaling
+    c.din = h->d_green_in.as<double>();
+    c.d_ene = c.din;
+    c.d_fixed_in = c.din + off_fixed;
+    c.d_same = reinterpret_cast<int*>(c.din + off_same);
+    c.d_cb = reinterpret_cast<int*>(c.din + off_cb);
+    c.d_chunk_in = c.din + off_chunk;
+    c.d_rows = h->d_green_out.as<double>();
+    c.d_fixed_out = c.d_rows + off_fo;
+    c.d_chunk_out = c.d_rows + off_co;
+    XFER(xfer_h2d(h, c.d_ene, ene, (size_t)nen * sizeof(double)));
+    XFER(xfer_h2d(h, c.d_same, same, (size_t)npairs * sizeof(int32_t)));
+    XFER(xfer_h2d(h, c.d_cb, c.cbase.data(), (size_t)(npairs + 1) * sizeof(int)));
+    chebyshev_green_scaling(energy_min, energy_max, c.ca, c.cb);
     if (kind == 1) {
-        if (nm > (int)((64 * 1024) / sizeof(double2))) return fail(h, RSREC_ERR_ARG, "rsrec_exchange: lld = %d too deep for the Chebyshev phase table", lld);
-        kern = chebyshev_green_kernel(nm);
-        XFER(xfer_h2d(h, din + off_ai, kern.data(), (size_t)nm * sizeof(double)));      // (the terminator slot is unused by kind 1)
+        const std::vector<double> kern = chebyshev_green_kernel(nm);
+        XFER(xfer_h2d(h, c.din + c.off_ai, kern.data(), (size_t)nm * sizeof(double)));      // (the terminator slot is unused by kind 1)
     }
-    reset_timing(h);
-    hipEvent_t e0 = next_event(h);
-    HIPCK(h, hipMemsetAsync(d_img, 0, nimg * sizeof(double), h->stream));
-    k_exchange_fermi<<<(nen + 255) / 256, 256, 0, h->stream>>>(nen, d_ene, fermi, d_fw);
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> kev;
-    for (int p0 = 0; p0 < npairs; p0 += P) {
-        const int np = std::min(P, npairs - p0);
-        const size_t c0 = (size_t)cbase[p0], nc = (size_t)(cbase[p0 + np] - cbase[p0]);     // chains of the chunk
-        const double* sa = nullptr;
-        if (resident) sa = reinterpret_cast<const double*>((kind == 0 ? h->d_coefA.as<double2>() : h->d_mu.as<double2>()) + c0 * cel);
-        else XFER(xc_fetch(h, coef_a + c0 * cel * 2, din + off_ab, nc * cel * 2, &sa));
-        std::pair<hipEvent_t, hipEvent_t> ev;
-        if (kind == 0) {
-            const double* sb = nullptr;
-            if (resident) {                                 // b2_b of the recursion stays B^2: the square root goes to its own buffer
-                double2* dBs = h->d_bsqrt.as<double2>();
-                HIPCK(h, hipMemcpyAsync(dBs, h->d_coefB.as<double2>() + c0 * cel, nc * cel * sizeof(double2), hipMemcpyDeviceToDevice, h->stream));
-                k_zsqr<<<(unsigned)(nc * lld), 256, 0, h->stream>>>(dBs, h->d_status.as<int>());
-                sb = reinterpret_cast<const double*>(dBs);
-            } else XFER(xc_fetch(h, coef_b + c0 * cel * 2, din + off_bs, nc * cel * 2, &sb));
-            const double *ta = nullptr, *tb = nullptr;
-            if (a_inf) {
-                XFER(xc_fetch(h, a_inf + c0 * BLK, din + off_ai, nc * BLK, &ta));
-                XFER(xc_fetch(h, b_inf + c0 * BLK, din + off_bi, nc * BLK, &tb));
-            } else {
-                int rc = launch_terminator(h, (int)nc, lld, reinterpret_cast<const double2*>(sa), reinterpret_cast<const double2*>(sb), din + off_ai, din + off_bi);
-                if (rc) return rc;
-                ta = din + off_ai; tb = din + off_bi;
-            }
-            ev.first = next_event(h);
-            k_exchange_block<<<dim3(nen, np), 256, 0, h->stream>>>(lld, nen, d_ene, sym_term, ta, tb, reinterpret_cast<const double2*>(sa),
-                                                                reinterpret_cast<const double2*>(sb), d_same + p0, d_cb + p0, (int)c0, d_dpar + (size_t)24 * p0, d_int);
-        } else {
-            ev.first = next_event(h);
-            k_exchange_cheb<<<dim3(nen, np), 256, (size_t)nm * sizeof(double2), h->stream>>>(nm, nen, d_ene, ca, cb, din + off_ai, reinterpret_cast<const double2*>(sa),
-                                                                                           d_same + p0, d_cb + p0, (int)c0, d_dpar + (size_t)24 * p0, d_int);
-        }
-        HIPCK(h, hipGetLastError());
-        k_exchange_integrate<<<np, 128, 0, h->stream>>>(nen, nv1, d_ene, d_fw, d_int, pair_offset + p0, d_img, d_img + (size_t)13 * npairs_total,
-                                                        d_img + (size_t)26 * npairs_total, d_img + (size_t)39 * npairs_total, jcum ? d_jc : nullptr, 0);
-        HIPCK(h, hipGetLastError());
-        ev.second = next_event(h);
-        kev.push_back(ev);
-        if (jcum) XFER(xc_deliver(h, jcum + (size_t)p0 * nen, d_jc, (size_t)np * nen));
-        if (integrand) XFER(xc_deliver(h, integrand + (size_t)p0 * nen * XC_NINT, d_int, (size_t)np * nen * XC_NINT));
-        if (p0 + P < npairs) HIPCK(h, hipStreamSynchronize(h->stream));         // the chunk's staging buffers are reused
+    return RSREC_OK;
+}
+
+// Coefficients and terminators of the pairs p0 .. p0 + P - 1 (resident: read in place, b2_b square-rooted into a buffer of its own; caller
+// arrays: staged, or read in place when they are device memory; terminators from the device unless given)
+int pair_call_chunk(rsrec_t* h, const PairCall& c, int p0, PairChunk& k) {
+    const size_t cel = c.cel;
+    k.np = std::min(c.P, c.npairs - p0);
+    const size_t c0 = (size_t)c.cbase[p0], nc = (size_t)(c.cbase[p0 + k.np] - c.cbase[p0]);     // chains of the chunk
+    k.c0 = (int)c0;
+    k.sb = nullptr; k.tb = nullptr;
+    const double* sa = nullptr;
+    if (c.resident) sa = reinterpret_cast<const double*>((c.kind == 0 ? h->d_coefA.as<double2>() : h->d_mu.as<double2>()) + c0 * cel);
+    else XFER(xc_fetch(h, c.coef_a + c0 * cel * 2, c.din + c.off_ab, nc * cel * 2, &sa));
+    k.sa = reinterpret_cast<const double2*>(sa);
+    if (c.kind == 1) { k.ta = c.din + c.off_ai; return RSREC_OK; }
+    const double* sb = nullptr;
+    if (c.resident) {                                 // b2_b of the recursion stays B^2: the square root goes to its own buffer
+        double2* dBs = h->d_bsqrt.as<double2>();
+        HIPCK(h, hipMemcpyAsync(dBs, h->d_coefB.as<double2>() + c0 * cel, nc * cel * sizeof(double2), hipMemcpyDeviceToDevice, h->stream));
+        k_zsqr<<<(unsigned)(nc * c.lld), 256, 0, h->stream>>>(dBs, h->d_status.as<int>());
+        sb = reinterpret_cast<const double*>(dBs);
+    } else XFER(xc_fetch(h, c.coef_b + c0 * cel * 2, c.din + c.off_bs, nc * cel * 2, &sb));
+    k.sb = reinterpret_cast<const double2*>(sb);
+    if (c.a_inf) {
+        XFER(xc_fetch(h, c.a_inf + c0 * BLK, c.din + c.off_ai, nc * BLK, &k.ta));
+        XFER(xc_fetch(h, c.b_inf + c0 * BLK, c.din + c.off_bi, nc * BLK, &k.tb));
+    } else {
+        int rc = launch_terminator(h, (int)nc, c.lld, k.sa, k.sb, c.din + c.off_ai, c.din + c.off_bi);
+        if (rc) return rc;
+        k.ta = c.din + c.off_ai; k.tb = c.din + c.off_bi;
     }
-    XFER(xc_deliver(h, xc, d_img, (size_t)13 * npairs_total));
-    XFER(xc_deliver(h, so, d_img + (size_t)13 * npairs_total, (size_t)13 * npairs_total));
-    XFER(xc_deliver(h, fo, d_img + (size_t)26 * npairs_total, (size_t)13 * npairs_total));
-    XFER(xc_deliver(h, parts, d_img + (size_t)39 * npairs_total, (size_t)28 * npairs_total));
+    return RSREC_OK;
+}
+
+// end of such a call: the status word, the stream, the timing (total; hop = rest = the kernel stages of the chunks)
+int pair_call_end(rsrec_t* h, hipEvent_t e0, const std::vector<std::pair<hipEvent_t, hipEvent_t>>& kev) {
     hipEvent_t e1 = next_event(h);
     int status = 0;
     XFER(xfer_d2h(h, &status, h->d_status.p, 4));
@@ -2431,6 +2442,116 @@ extern "C" int rsrec_exchange(rsrec_t* h, int kind, int npairs, const int32_t* s
     h->t_hop_ms = h->t_rest_ms;
     if (status & 1) return fail(h, RSREC_ERR_EIG, "Diagonalization error (18x18 Jacobi did not converge)");
     return RSREC_OK;
+}
+
+}  // namespace
+
+// green%calculate_intersite_gf / _twoindex + exchange%calculate_exchange / _twoindex (integrands and integrals) for the pairs of one rank.
+extern "C" int rsrec_exchange(rsrec_t* h, int kind, int npairs, const int32_t* same, int lld, int nen, const double* ene, int nv1, double fermi,
+                              int sym_term, double energy_min, double energy_max, const double* a_inf, const double* b_inf, const double* coef_a,
+                              const double* coef_b, const double* dpar, int pair_offset, int npairs_total, double* xc, double* so, double* fo,
+                              double* parts, double* jcum, double* integrand) {
+    if (!h) return RSREC_ERR_ARG;
+    if (npairs < 1 || lld < 1 || nv1 < 1 || !same || !ene || !dpar || !xc || !so || !fo || !parts || pair_offset < 0 || npairs_total < pair_offset + npairs)
+        return fail(h, RSREC_ERR_ARG, "rsrec_exchange: bad argument");
+    if (nen < nv1 + 9) return fail(h, RSREC_ERR_ARG, "rsrec_exchange: nen = %d < nv1 + 9 = %d (simpson_f integrates to nv1 + 10)", nen, nv1 + 9);
+    const size_t nimg = (size_t)XC_NOUT * npairs_total;
+    PairCall c;
+    // own inputs: fermi weights | dpar;  own outputs: the images (xc, so, fo, parts) and jcum of the chunk
+    int rc = pair_call_begin(h, c, "rsrec_exchange", kind, npairs, same, lld, nen, ene, energy_min, energy_max, a_inf, b_inf, coef_a, coef_b,
+                             (size_t)nen * XC_NINT, (size_t)nen + (size_t)24 * npairs, 0, nimg, (size_t)nen);
+    if (rc) return rc;
+    double* d_ene = c.d_ene;
+    double* d_fw = c.d_fixed_in;
+    double* d_dpar = d_fw + nen;
+    double* d_int = c.d_rows;
+    double* d_img = c.d_fixed_out;
+    double* d_jc = c.d_chunk_out;
+    XFER(xfer_h2d(h, d_dpar, dpar, (size_t)24 * npairs * sizeof(double)));
+    reset_timing(h);
+    hipEvent_t e0 = next_event(h);
+    HIPCK(h, hipMemsetAsync(d_img, 0, nimg * sizeof(double), h->stream));
+    k_exchange_fermi<<<(nen + 255) / 256, 256, 0, h->stream>>>(nen, d_ene, fermi, d_fw);
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> kev;
+    for (int p0 = 0; p0 < npairs; p0 += c.P) {
+        PairChunk k;
+        rc = pair_call_chunk(h, c, p0, k);
+        if (rc) return rc;
+        const int np = k.np;
+        std::pair<hipEvent_t, hipEvent_t> ev;
+        ev.first = next_event(h);
+        if (kind == 0)
+            k_exchange_block<<<dim3(nen, np), 256, 0, h->stream>>>(lld, nen, d_ene, sym_term, k.ta, k.tb, k.sa, k.sb, c.d_same + p0, c.d_cb + p0, k.c0,
+                                                                d_dpar + (size_t)24 * p0, d_int);
+        else
+            k_exchange_cheb<<<dim3(nen, np), 256, (size_t)c.nm * sizeof(double2), h->stream>>>(c.nm, nen, d_ene, c.ca, c.cb, k.ta, k.sa, c.d_same + p0, c.d_cb + p0,
+                                                                                             k.c0, d_dpar + (size_t)24 * p0, d_int);
+        HIPCK(h, hipGetLastError());
+        k_exchange_integrate<<<np, 128, 0, h->stream>>>(nen, nv1, d_ene, d_fw, d_int, pair_offset + p0, d_img, d_img + (size_t)13 * npairs_total,
+                                                        d_img + (size_t)26 * npairs_total, d_img + (size_t)39 * npairs_total, jcum ? d_jc : nullptr, 0);
+        HIPCK(h, hipGetLastError());
+        ev.second = next_event(h);
+        kev.push_back(ev);
+        if (jcum) XFER(xc_deliver(h, jcum + (size_t)p0 * nen, d_jc, (size_t)np * nen));
+        if (integrand) XFER(xc_deliver(h, integrand + (size_t)p0 * nen * XC_NINT, d_int, (size_t)np * nen * XC_NINT));
+        if (p0 + c.P < npairs) HIPCK(h, hipStreamSynchronize(h->stream));         // the chunk's staging buffers are reused
+    }
+    XFER(xc_deliver(h, xc, d_img, (size_t)13 * npairs_total));
+    XFER(xc_deliver(h, so, d_img + (size_t)13 * npairs_total, (size_t)13 * npairs_total));
+    XFER(xc_deliver(h, fo, d_img + (size_t)26 * npairs_total, (size_t)13 * npairs_total));
+    XFER(xc_deliver(h, parts, d_img + (size_t)39 * npairs_total, (size_t)28 * npairs_total));
+    return pair_call_end(h, e0, kev);
+}
+
+// exchange%calculate_gilbert_damping (exchange.f90:674-694) for the pairs of one rank: the nine traces Tr(T_i^k Aij (T_j^l)^H Aji) per
+// energy, without gij / gji or the reference's temporaries.
+extern "C" int rsrec_damping(rsrec_t* h, int kind, int npairs, const int32_t* same, int lld, int nen, const double* ene, int ief, int sym_term,
+                             double energy_min, double energy_max, const double* a_inf, const double* b_inf, const double* coef_a, const double* coef_b,
+                             const double* tmat, int pair_offset, int npairs_total, double* at_ef, double* total, double* rows) {
+    if (!h) return RSREC_ERR_ARG;
+    if (npairs < 1 || lld < 1 || nen < 1 || !same || !ene || !at_ef || !total || pair_offset < 0 || npairs_total < pair_offset + npairs)
+        return fail(h, RSREC_ERR_ARG, "rsrec_damping: bad argument");
+    if (!tmat) return fail(h, RSREC_ERR_ARG, "rsrec_damping: no torque matrices (tmat is NULL)");
+    if (ief < 1 || ief > nen) return fail(h, RSREC_ERR_ARG, "rsrec_damping: ief = %d outside 1..%d", ief, nen);
+    const size_t nimg = (size_t)DP_NROW * npairs_total, ntot = (size_t)9 * nen, rdoubles = (size_t)nen * DP_NROW;
+    PairCall c;
+    // own chunk inputs: tmat of the chunk's pairs;  own outputs: the at_ef image | total
+    int rc = pair_call_begin(h, c, "rsrec_damping", kind, npairs, same, lld, nen, ene, energy_min, energy_max, a_inf, b_inf, coef_a, coef_b, rdoubles, 0,
+                             (size_t)2 * DP_TMAT, nimg + ntot, 0);
+    if (rc) return rc;
+    double* d_img = c.d_fixed_out;
+    double* d_tot = d_img + nimg;
+    reset_timing(h);
+    hipEvent_t e0 = next_event(h);
+    // (total's running value lives in d_tot across the chunks, k_damping_reduce adding to it: this one memset is what starts it at zero)
+    HIPCK(h, hipMemsetAsync(d_img, 0, (nimg + ntot) * sizeof(double), h->stream));
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> kev;
+    for (int p0 = 0; p0 < npairs; p0 += c.P) {
+        PairChunk k;
+        rc = pair_call_chunk(h, c, p0, k);
+        if (rc) return rc;
+        const int np = k.np;
+        const double* tm = nullptr;
+        XFER(xc_fetch(h, tmat + (size_t)p0 * 2 * DP_TMAT, c.d_chunk_in, (size_t)np * 2 * DP_TMAT, &tm));
+        std::pair<hipEvent_t, hipEvent_t> ev;
+        ev.first = next_event(h);
+        if (kind == 0)
+            k_damping_block<<<dim3(nen, np), 256, 0, h->stream>>>(lld, nen, c.d_ene, sym_term, k.ta, k.tb, k.sa, k.sb, c.d_same + p0, c.d_cb + p0, k.c0,
+                                                               reinterpret_cast<const double2*>(tm), c.d_rows);
+        else
+            k_damping_cheb<<<dim3(nen, np), 256, (size_t)c.nm * sizeof(double2), h->stream>>>(c.nm, nen, c.d_ene, c.ca, c.cb, k.ta, k.sa, c.d_same + p0, c.d_cb + p0,
+                                                                                            k.c0, reinterpret_cast<const double2*>(tm), c.d_rows);
+        HIPCK(h, hipGetLastError());
+        k_damping_reduce<<<(unsigned)((ntot + (size_t)DP_NROW * np + 255) / 256), 256, 0, h->stream>>>(nen, np, ief - 1, c.d_rows, pair_offset + p0, d_img, d_tot);
+        HIPCK(h, hipGetLastError());
+        ev.second = next_event(h);
+        kev.push_back(ev);
+        if (rows) XFER(xc_deliver(h, rows + (size_t)p0 * rdoubles, c.d_rows, (size_t)np * rdoubles));
+        if (p0 + c.P < npairs) HIPCK(h, hipStreamSynchronize(h->stream));         // the chunk's staging buffers are reused
+    }
+    XFER(xc_deliver(h, at_ef, d_img, nimg));
+    XFER(xc_deliver(h, total, d_tot, ntot));
+    return pair_call_end(h, e0, kev);
 }
 
 namespace {

@@ -3,6 +3,7 @@
 green%calculate_intersite_gf + _twoindex (green.f90:386-469) and the integrands and Fermi-weighted Simpson integrals of
 exchange%calculate_exchange + _twoindex become one call, ``rsrec_exchange``.  Neither g0 nor the 24 intersite arrays are formed: per
 (pair, energy) the kernel reduces g0 of the pair's chains to 41 real integrands, and per pair to 67 numbers (kernels_exchange.hpp).
+The traces of exchange%calculate_gilbert_damping (exchange.f90:674-694) come from the same chains through ``rsrec_damping``.
 """
 import ctypes as C
 
@@ -11,10 +12,22 @@ import numpy as np
 from . import _lib
 
 NINT = 41   # integrand rows per (pair, energy), order in kernels_exchange.hpp
+NDAMP = 18  # damping rows per (pair, energy): dtott (9, l fastest), then dtottim (9)
 
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _any_ptr(a):
+    """Pointer of a numpy array or of a device tensor (complete before the call: the library reads it on its own stream)."""
+    if a is None:
+        return None
+    if hasattr(a, "data_ptr"):
+        import torch
+        torch.cuda.synchronize(a.device)
+        return C.c_void_p(a.data_ptr())
+    return _ptr(a)
 
 
 def exchange_dpar(c, dele, vmad, iz, pairs):
@@ -37,6 +50,16 @@ def exchange_dpar(c, dele, vmad, iz, pairs):
     return out
 
 
+def damping_tmat(tmat, iz, pairs):
+    """tmat (18,18,3,2,npairs) for rsrec_damping from hamiltonian%tmat (18,18,3,ntype): the type of atom i, then of atom j, per pair."""
+    tmat, iz, pairs = np.asarray(tmat, np.complex128), np.asarray(iz), np.asarray(pairs)
+    out = np.zeros((18, 18, 3, 2, len(pairs)), np.complex128, order="F")
+    for p, ij in enumerate(pairs):
+        for side in range(2):
+            out[:, :, :, side, p] = tmat[:, :, :, int(iz[int(ij[side]) - 1]) - 1]
+    return out
+
+
 class Exchange:
     """``Exchange(recursion, green).compute(...)`` on the rank's pairs after recur_b_ij / chebyshev_recur_ij (block: and zsqr)."""
 
@@ -52,6 +75,29 @@ class Exchange:
         The pairs are lattice%ijpair of this rank.  Coefficients: ``resident=True`` reads the chains the last seeded recursion left on the
         device; else ``coef`` (a_b, b_sqrt) / (mu_n,) if given, else the recursion's arrays (a_b, b2_b after zsqr / mu_n).  Terminators:
         ``a_inf, b_inf`` (18,18,4*npairs) or None (computed on the device)."""
+        rec = self.recursion
+        ene, npairs, npairs_total, same, lld, k, ca, cb, a_inf, b_inf = self._call_setup(kind, resident, coef, a_inf, b_inf, npairs_total)
+        dpar = np.asfortranarray(dpar, dtype=np.float64)
+        xc = np.zeros((13, npairs_total), order="F")
+        so, fo = np.zeros_like(xc), np.zeros_like(xc)
+        parts = np.zeros((28, npairs_total), order="F")
+        jcum = np.zeros((len(ene), npairs), order="F") if cumulative else None
+        integ = np.zeros((NINT, len(ene), npairs), order="F") if integrand else None
+
+        rec._check(rec._L.rsrec_exchange(rec._h, k, npairs, _ptr(same), lld, len(ene), _ptr(ene), int(nv1), float(fermi), int(self.green.sym_term),
+                                          float(rec.en.energy_min), float(rec.en.energy_max), _ptr(a_inf), _ptr(b_inf), _any_ptr(ca), _any_ptr(cb), _ptr(dpar),
+                                          int(pair_offset), int(npairs_total), _ptr(xc), _ptr(so), _ptr(fo), _ptr(parts), _ptr(jcum), _ptr(integ)))
+        del ca, cb
+        out = [xc, so, fo, parts]
+        if cumulative:
+            out.append(jcum)
+        if integrand:
+            out.append(integ)
+        return tuple(out)
+
+    def _call_setup(self, kind, resident, coef, a_inf, b_inf, npairs_total):
+        """What rsrec_exchange and rsrec_damping take alike, for this rank's pairs: (ene, npairs, npairs_total, same, lld, kind, coef_a,
+        coef_b, a_inf, b_inf).  Coefficients: None with ``resident``, else ``coef`` or the recursion's arrays; device tensors as they are."""
         rec, ene = self.recursion, np.ascontiguousarray(self.green.ene, dtype=np.float64)
         pairs = np.asarray(rec.lattice.ijpair, dtype=np.int32)
         from .recursion import site_partition
@@ -73,35 +119,31 @@ class Exchange:
             arrs = [a if hasattr(a, "data_ptr") else np.asfortranarray(a, dtype=np.complex128) for a in arrs]
             ca = arrs[0]
             cb = arrs[1] if len(arrs) > 1 else None
-        keep = [ca, cb]
         if a_inf is not None:
             a_inf, b_inf = np.asfortranarray(a_inf, dtype=np.float64), np.asfortranarray(b_inf, dtype=np.float64)
-        dpar = np.asfortranarray(dpar, dtype=np.float64)
-        xc = np.zeros((13, npairs_total), order="F")
-        so, fo = np.zeros_like(xc), np.zeros_like(xc)
-        parts = np.zeros((28, npairs_total), order="F")
-        jcum = np.zeros((len(ene), npairs), order="F") if cumulative else None
-        integ = np.zeros((NINT, len(ene), npairs), order="F") if integrand else None
+        return ene, npairs, npairs_total, same, lld, k, ca, cb, a_inf, b_inf
 
-        def p(a):
-            if a is None:
-                return None
-            if hasattr(a, "data_ptr"):
-                import torch
-                torch.cuda.synchronize(a.device)
-                return C.c_void_p(a.data_ptr())
-            return _ptr(a)
+    def damping(self, tmat, ief, kind="block", rows=False, resident=False, coef=None, a_inf=None, b_inf=None, pair_offset=0, npairs_total=None):
+        """Returns (at_ef, total) = the 9 real then 9 imaginary traces of every pair at ene(ief) (18, npairs_total) and total_damping
+        (9, nen) of this rank's pairs, then the rows (18, nen, npairs) if ``rows``.  The prefactor -0.25 * 2 / (pi spin_i) is the caller's.
 
-        rec._check(rec._L.rsrec_exchange(rec._h, k, npairs, _ptr(same), lld, len(ene), _ptr(ene), int(nv1), float(fermi), int(self.green.sym_term),
-                                          float(rec.en.energy_min), float(rec.en.energy_max), _ptr(a_inf), _ptr(b_inf), p(ca), p(cb), _ptr(dpar),
-                                          int(pair_offset), int(npairs_total), _ptr(xc), _ptr(so), _ptr(fo), _ptr(parts), _ptr(jcum), _ptr(integ)))
-        del keep
-        out = [xc, so, fo, parts]
-        if cumulative:
-            out.append(jcum)
-        if integrand:
-            out.append(integ)
-        return tuple(out)
+        ``tmat``: (18,18,3,2,npairs) complex, the torque matrices of atom i and atom j of this rank's pairs (``damping_tmat``), a numpy
+        array or a device tensor in that memory order; ``ief``: 1-based energy index.  Pairs, coefficients and terminators as ``compute``."""
+        rec = self.recursion
+        ene, npairs, npairs_total, same, lld, k, ca, cb, a_inf, b_inf = self._call_setup(kind, resident, coef, a_inf, b_inf, npairs_total)
+        if tmat is not None and not hasattr(tmat, "data_ptr"):
+            tmat = np.asfortranarray(tmat, dtype=np.complex128)
+            if tmat.shape != (18, 18, 3, 2, npairs):
+                raise ValueError("tmat must be (18, 18, 3, 2, %d), got %r" % (npairs, tmat.shape))
+        at_ef = np.zeros((NDAMP, npairs_total), order="F")
+        total = np.zeros((9, len(ene)), order="F")
+        out_rows = np.zeros((NDAMP, len(ene), npairs), order="F") if rows else None
+
+        rec._check(rec._L.rsrec_damping(rec._h, k, npairs, _ptr(same), lld, len(ene), _ptr(ene), int(ief), int(self.green.sym_term),
+                                         float(rec.en.energy_min), float(rec.en.energy_max), _ptr(a_inf), _ptr(b_inf), _any_ptr(ca), _any_ptr(cb), _any_ptr(tmat),
+                                         int(pair_offset), int(npairs_total), _ptr(at_ef), _ptr(total), _ptr(out_rows)))
+        del ca, cb
+        return (at_ef, total, out_rows) if rows else (at_ef, total)
 
     def timing(self):
         """(device ms of the last call, ms in its Green + trace + integration kernels)."""
