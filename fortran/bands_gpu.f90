@@ -32,6 +32,7 @@ module bands_gpu_mod
    use green_mod
    use green_gpu_mod
    use precision_mod, only: rp
+   use math_mod, only: pi, gauss_legendre
    use logger_mod, only: g_logger
    use timer_mod, only: g_timer
    use string_mod, only: fmt
@@ -56,6 +57,8 @@ module bands_gpu_mod
       procedure :: calculate_orbital_moments => gpu_calculate_orbital_moments
       procedure :: calculate_orbital_quadrupoles => gpu_calculate_orbital_quadrupoles
       procedure :: calculate_moments => gpu_calculate_moments
+      procedure :: calculate_moments_gauss_legendre => gpu_calculate_moments_gauss_legendre
+      procedure :: calculate_occupation_gauss_legendre => gpu_calculate_occupation_gauss_legendre
       procedure :: calculate_projected_green => gpu_calculate_projected_green
       procedure :: calculate_projected_dos => gpu_calculate_projected_dos
       procedure :: calculate_orbital_dos => gpu_calculate_orbital_dos
@@ -271,6 +274,105 @@ contains
       call ensure_g0(this)
       call this%bands%calculate_moments()
    end subroutine gpu_calculate_moments
+
+   !> occ(site, orbital) of the rank's sites on the 64-point Gauss-Legendre contour at ene(fermi_point), from the on-site chains the
+   !> recursion left on the device: one rsrec_contour_occupation call (the loop of bands.f90:559-586 / :631-650: block_green_eta or
+   !> chebyshev_green_eta at 64 points, the terminator once per chain instead of once per point)
+   subroutine occupation_on_device(this, fermi_point, occ)
+      class(bands_gpu), intent(inout) :: this
+      integer, intent(in) :: fermi_point
+      real(rp), dimension(this%lattice%nrec, 18), intent(out) :: occ
+      real(rp), dimension(64), target :: x, w
+      real(rp), dimension(:, :), allocatable, target :: img
+      integer(c_int) :: rc, sym_i, ikind
+      type(c_ptr) :: ctx
+
+      call gauss_legendre(64, 0.0_rp, 1.0_rp, x, w)
+      allocate (img(18, this%lattice%nrec))
+      img = 0.0_rp
+      ikind = 0
+      if (trim(this%control%recur) == 'chebyshev') ikind = 1
+      sym_i = 0
+      if (this%control%sym_term) sym_i = 1
+      ctx = rsrec_gpu_context()
+      call g_timer%start('contour-occupation-gpu')
+      rc = rsrec_contour_occupation(ctx, ikind, int(end_atom - start_atom + 1, c_int), int(this%control%lld, c_int), 64_c_int, c_loc(x), &
+                                    c_loc(w), real(this%en%ene(fermi_point), c_double), sym_i, real(this%en%energy_min, c_double), &
+                                    real(this%en%energy_max, c_double), c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, &
+                                    int(start_atom - 1, c_int), int(this%lattice%nrec, c_int), c_loc(img), c_null_ptr)
+      call g_timer%stop('contour-occupation-gpu')
+      if (rc /= 0) call g_logger%fatal('bands_gpu: rsrec_contour_occupation: '//rsrec_error_string(ctx), __FILE__, __LINE__)
+      occ = transpose(img)
+   end subroutine occupation_on_device
+
+   !> calculate_moments_gauss_legendre (bands.f90:526-604): occ from the device, the rest the reference's lines
+   subroutine gpu_calculate_moments_gauss_legendre(this)
+      class(bands_gpu) :: this
+      integer :: i, m, fermi_point
+      real(rp) :: sumocc
+      real(rp), dimension(this%lattice%nrec, 18) :: occ
+
+      if (.not. device_stage_usable(this)) then
+         call this%bands%calculate_moments_gauss_legendre()
+         return
+      end if
+
+      call this%en%e_mesh()
+
+      fermi_point = 0
+      do i = 1, this%en%channels_ldos + 10
+         if ((this%en%ene(i) - this%en%fermi) .le. 0.0001d0) fermi_point = i
+      end do
+      if (rank == 0) write (*, *) this%en%fermi, fermi_point
+
+      call occupation_on_device(this, fermi_point, occ)
+
+      ! Transfer calculated occupations across MPI
+#ifdef USE_MPI
+      call MPI_ALLREDUCE(MPI_IN_PLACE, occ, product(shape(occ)), MPI_DOUBLE_PRECISION, MPI_SUM, MPI_COMM_WORLD, ierr)
+#endif
+
+      sumocc = 0.0d0
+      do m = 1, this%lattice%nrec
+         if (rank == 0) call g_logger%info('Spin moment of atom'//fmt('i4', m)//' is '//fmt('f10.6', sum(occ(m, 1:9)) - sum(occ(m, 10:18))), __FILE__, __LINE__)
+         if (rank == 0) call g_logger%info('Total charge for atom'//fmt('i4', m)//' is '// &
+                                           'total= '//fmt('f10.6', sum(occ(m, 1:18)))// &
+                                           ' s= '//fmt('f10.6', occ(m, 1) + occ(m, 10))// &
+                                           ' p= '//fmt('f10.6', sum(occ(m, 2:4)) + sum(occ(m, 11:13)))// &
+                                           ' d= '//fmt('f10.6', sum(occ(m, 5:9)) + sum(occ(m, 14:18))), __FILE__, __LINE__)
+         sumocc = sumocc + sum(occ(m, :))
+      end do
+      if (rank == 0) call g_logger%info('Total number of electrons is '//fmt('f16.6', sumocc), __FILE__, __LINE__)
+   end subroutine gpu_calculate_moments_gauss_legendre
+
+   !> calculate_occupation_gauss_legendre (bands.f90:606-656), which calculate_fermi_gauss bisects on.  The reference uses block_green_eta
+   !> whatever control%recur is and sizes its arrays for one rank: the device path is taken for block chains on a single rank only.
+   subroutine gpu_calculate_occupation_gauss_legendre(this, fermi_energy, sumocc_out)
+      class(bands_gpu) :: this
+      real(rp), intent(in)  :: fermi_energy
+      real(rp), intent(out) :: sumocc_out
+      integer :: i, m, fermi_point
+      real(rp), dimension(this%lattice%nrec, 18) :: occ
+
+      if (.not. (device_stage_usable(this) .and. trim(this%control%recur) == 'block' .and. numprocs == 1)) then
+         call this%bands%calculate_occupation_gauss_legendre(fermi_energy, sumocc_out)
+         return
+      end if
+
+      fermi_point = 0
+      do i = 1, this%en%channels_ldos + 10
+         if ((this%en%ene(i) - fermi_energy) .le. 0.001d0) fermi_point = i
+      end do
+      write (*, *) fermi_energy, fermi_point
+
+      call occupation_on_device(this, fermi_point, occ)
+
+      sumocc_out = 0.0d0
+      do m = 1, this%lattice%nrec
+         sumocc_out = sumocc_out + sum(occ(m, :))
+      end do
+      write (*, *) 'Total electrons:', sumocc_out
+   end subroutine gpu_calculate_occupation_gauss_legendre
 
    subroutine gpu_calculate_projected_green(this)
       class(bands_gpu) :: this

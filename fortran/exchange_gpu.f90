@@ -26,6 +26,15 @@
 !                                 the inherited calculate_intersite_gf / _twoindex from the recursion's host coefficients), then the
 !                                 inherited routine.  None is ported to the device; the moment of inertia in particular defines no
 !                                 result to match (its final loop indexes with nv after the energy loop has ended, :869-882).
+!   calculate_exchange_gauss_legendre : (:1756-1919) one rsrec_exchange_contour call for the rank's pairs on the resident chains
+!                                 (green%calculate_intersite_gf_eta + the 64-point loop of :1811-1867: the terminator once per chain
+!                                 instead of once per point, no _eta array, no gij_eta_to_gij), x and w from the reference's own
+!                                 gauss_legendre, e0 = ene(fermi_point) with the `.le. 1.0d-6` rule of green.f90:489-491; then the
+!                                 reference's tail (:1869-1918) restated line for line.
+!                                 One deliberate deviation, i == j pairs: recur_b_ij runs one chain for such a pair and never writes
+!                                 slots 2..4 (recursion.f90:1702-1707), and the reference's contour routine combines chain 1 with
+!                                 those unwritten slots; here gij = gji = g(chain 1), as calculate_intersite_gf takes it
+!                                 (green.f90:446-448).
 ! Errors of the library become g_logger%fatal, the reference's error behaviour on this path.
 !------------------------------------------------------------------------------
 module exchange_gpu_mod
@@ -35,7 +44,7 @@ module exchange_gpu_mod
    use green_gpu_mod, only: green_gpu
    use mpi_mod
    use precision_mod, only: rp
-   use math_mod, only: pi
+   use math_mod, only: pi, gauss_legendre
    use logger_mod, only: g_logger
    use timer_mod, only: g_timer
    use rsrec_binding
@@ -56,6 +65,7 @@ module exchange_gpu_mod
       procedure :: calculate_exchange => gpu_calculate_exchange
       procedure :: calculate_exchange_twoindex => gpu_calculate_exchange_twoindex
       procedure :: calculate_gilbert_damping => gpu_calculate_gilbert_damping
+      procedure :: calculate_exchange_gauss_legendre => gpu_calculate_exchange_gauss_legendre
       procedure :: calculate_moment_of_inertia => gpu_calculate_moment_of_inertia
       procedure :: calculate_jij_auxgreen => gpu_calculate_jij_auxgreen
       procedure :: calculate_jijk => gpu_calculate_jijk
@@ -426,6 +436,115 @@ contains
       call MPI_BARRIER(MPI_COMM_WORLD, ierr)
 #endif
    end subroutine gpu_calculate_gilbert_damping
+
+   !> calculate_exchange_gauss_legendre (:1756-1919)
+   subroutine gpu_calculate_exchange_gauss_legendre(this)
+      class(exchange_gpu) :: this
+      integer :: nloc, njij, p, ij, side, i, j, ikind, fermi_point, njij_glob, at
+      integer(c_int) :: rc, sym_i
+      type(c_ptr) :: ctx
+      integer(c_int), dimension(:), allocatable, target :: same
+      real(rp), dimension(64), target :: x, w
+      real(rp), dimension(:, :, :, :), allocatable, target :: dmat
+      real(rp), dimension(:, :), allocatable, target :: T_comm_xc
+
+      njij = this%lattice%njij
+      nloc = end_atom - start_atom + 1
+      select case (this%control%recur)
+      case ('block')
+         ikind = 0
+      case ('chebyshev')
+         ikind = 1
+      case default
+         call g_logger%fatal('exchange_gpu: control%recur '//trim(this%control%recur)//' has no pair recursion', __FILE__, __LINE__)
+      end select
+      allocate (T_comm_xc(13, njij))
+      T_comm_xc = 0.0_rp
+
+      call open_unit(20, 'jij.out', 'jij.outt: Unit 20 is already open')
+      call open_unit(30, 'dij.out', 'dij.outt: Unit 30 is already open')
+      call open_unit(40, 'aij.out', 'aij.out: Unit 40 is already open')
+      call open_unit(60, 'jtens.out', 'jtens.out: Unit 40 is already open')
+
+      ! Find the Gauss Legendre roots and weights
+      call gauss_legendre(64, 0.00_rp, 1.0_rp, x, w)
+      ! the point of the mesh the Green functions were taken at (green.f90:489-491)
+      fermi_point = 0
+      do i = 1, this%en%channels_ldos + 10
+         if ((this%en%ene(i) - this%en%fermi) .le. 0.000001d0) fermi_point = i
+      end do
+
+      if (nloc > 0) then
+         allocate (same(nloc), dmat(9, 9, 2, nloc))
+         do ij = start_atom, end_atom
+            p = ij - start_atom + 1
+            same(p) = 0
+            if (this%lattice%ijpair(ij, 1) == this%lattice%ijpair(ij, 2)) same(p) = 1
+            do side = 1, 2
+               at = this%lattice%iz(this%lattice%ijpair(ij, side))
+               dmat(:, :, side, p) = real(this%hamiltonian%ee(1:9, 1:9, 1, at) - this%hamiltonian%ee(10:18, 10:18, 1, at))
+            end do
+         end do
+         sym_i = 0
+         if (this%control%sym_term) sym_i = 1
+         ctx = rsrec_gpu_context()
+         call g_timer%start('exchange-contour-gpu')
+         ! coefficients and terminators NULL: the chains recur_b_ij / chebyshev_recur_ij left on the device (i == j pairs: one chain)
+         rc = rsrec_exchange_contour(ctx, int(ikind, c_int), int(nloc, c_int), c_loc(same), int(this%control%lld, c_int), 64_c_int, &
+                                     c_loc(x), c_loc(w), real(this%en%ene(fermi_point), c_double), sym_i, &
+                                     real(this%en%energy_min, c_double), real(this%en%energy_max, c_double), c_null_ptr, c_null_ptr, &
+                                     c_null_ptr, c_null_ptr, c_loc(dmat), int(start_atom - 1, c_int), int(njij, c_int), &
+                                     c_loc(T_comm_xc), c_null_ptr)
+         call g_timer%stop('exchange-contour-gpu')
+         if (rc /= 0) call g_logger%fatal('exchange_gpu: rsrec_exchange_contour: '//rsrec_error_string(ctx), __FILE__, __LINE__)
+      end if
+
+#ifdef USE_MPI
+      call MPI_ALLREDUCE(MPI_IN_PLACE, T_comm_xc, product(shape(T_comm_xc)), &
+                         MPI_DOUBLE_PRECISION, MPI_SUM, MPI_COMM_WORLD, ierr)
+#endif
+
+      if (rank == 0) then
+         do njij_glob = 1, this%lattice%njij
+            i = this%lattice%ijpair(njij_glob, 1) ! Atom number in the clust file, atom i
+            j = this%lattice%ijpair(njij_glob, 2) ! Atom number in the clust file, atom j
+
+            write (*, *) 'Atom', i, 'coordinates:', this%lattice%cr(:, i), 'Atom Type', this%lattice%iz(i)
+            write (*, *) 'Atom', j, 'coordinates:', this%lattice%cr(:, j), 'Atom Type', this%lattice%iz(j)
+            write (*, *) 'Distance = ', norm2(this%lattice%cr(:, i) - this%lattice%cr(:, j))
+
+            ! Jij
+            this%jij = T_comm_xc(1, njij_glob)
+            write (*, *) 'Jij between pair', i, 'and ', j, 'is ', this%jij
+
+            ! Dij
+            this%dmi = T_comm_xc(2:4, njij_glob)
+            write (*, *) 'Dij between pair', i, 'and ', j, 'is ', this%dmi
+
+            ! Aij
+            this%aij = reshape(T_comm_xc(5:13, njij_glob), [3, 3])
+            write (*, *) 'Iij between pair', i, 'and ', j, 'is'
+            print '(3f12.6)', this%aij(1, :)
+            print '(3f12.6)', this%aij(2, :)
+            print '(3f12.6)', this%aij(3, :)
+            !
+            write (20, '(2i8,2x,3f12.6,2x,1f12.6,1x,f12.6)') &
+               this%lattice%iz(i), this%lattice%iz(j), this%lattice%cr(:, j) - this%lattice%cr(:, i), (this%jij), norm2(this%lattice%cr(:, i) - this%lattice%cr(:, j))
+            write (30, '(2i8,2x,3f12.6,2x,3f12.6,1x,f12.6)') &
+               this%lattice%iz(i), this%lattice%iz(j), this%lattice%cr(:, j) - this%lattice%cr(:, i), (this%dmi), norm2(this%lattice%cr(:, i) - this%lattice%cr(:, j))
+            write (40, '(2i8,2x,3f12.6,2x,9f12.6,1x,f12.6)') &
+               this%lattice%iz(i), this%lattice%iz(j), this%lattice%cr(:, j) - this%lattice%cr(:, i), this%aij, norm2(this%lattice%cr(:, i) - this%lattice%cr(:, j))
+            write (99, *) 'null', (this%lattice%cr(:, j) + this%lattice%cr(:, i))/2, this%dmi/norm2(this%dmi)
+         end do
+      end if
+      close (20)
+      close (30)
+      close (40)
+      deallocate (T_comm_xc)
+#ifdef USE_MPI
+      call MPI_BARRIER(MPI_COMM_WORLD, ierr)
+#endif
+   end subroutine gpu_calculate_exchange_gauss_legendre
 
    !> the host intersite arrays for an inherited routine that reads them (green_gpu%fetch_intersite)
    subroutine host_intersite(this)

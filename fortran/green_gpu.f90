@@ -317,6 +317,9 @@ contains
                                            this%gjy, this%gjz, this%g00ij, this%g00ji, this%g01ij, this%g01ji, this%gx0ij, this%gy0ij, &
                                            this%gz0ij, this%gx1ij, this%gy1ij, this%gz1ij, this%gx0ji, this%gy0ji, this%gz0ji, &
                                            this%gx1ji, this%gy1ji, this%gz1ji)
+      ! the Gauss-Legendre images of the same stage (64 x 18 x 18 per pair and array): exchange_gpu's contour routine forms none of them
+      if (allocated(this%gij_eta)) deallocate (this%gij_eta, this%gji_eta, this%ginmag_eta, this%gjnmag_eta, this%gix_eta, this%giy_eta, &
+                                               this%giz_eta, this%gjx_eta, this%gjy_eta, this%gjz_eta)
    end subroutine gpu_release_intersite
 
    !> green.f90:425-469.  With exchange_gpu behind the stage only its side effect on the recursion stays: b2_b <- sqrt(b2_b) for
@@ -368,9 +371,27 @@ contains
       call this%green%calculate_intersite_gf_twoindex()
    end subroutine gpu_calculate_intersite_gf_twoindex
 
-   !> green.f90:471-536, inherited; its readers (exchange%calculate_exchange_gauss_legendre) may also read the arrays above.
+   !> green.f90:471-536.  With exchange_gpu behind the stage (rsrec_exchange_contour forms T_comm_xc from the resident chains, the
+   !> terminator once per chain) only the side effects stay: e_mesh, the `fermi, fermi_point` line (:487-493), and zsqr on the host
+   !> arrays exactly as gpu_calculate_intersite_gf does it.  The ten _eta arrays are neither allocated (release_intersite let them go)
+   !> nor filled.  Otherwise the inherited routine, as before.
    subroutine gpu_calculate_intersite_gf_eta(this)
       class(green_gpu), intent(inout) :: this
+      integer :: i, fermi_point
+      if (this%intersite_on_device) then
+         call this%en%e_mesh()
+         fermi_point = 0
+         do i = 1, this%en%channels_ldos + 10
+            if ((this%en%ene(i) - this%en%fermi) .le. 0.000001d0) fermi_point = i
+         end do
+         write (*, *) this%en%fermi, fermi_point
+         if (this%control%recur == 'block') then
+            if (.not. allocated(this%b2_unrooted)) this%b2_unrooted = this%recursion%b2_b
+            call this%recursion%zsqr()
+         end if
+         this%intersite_fetched = .false.
+         return
+      end if
       call intersite_arrays(this)
       call this%green%calculate_intersite_gf_eta()
    end subroutine gpu_calculate_intersite_gf_eta

@@ -196,6 +196,30 @@ module rsrec_binding
          integer(c_int) :: rc
       end function
 
+      ! T_comm_xc of the rank's pairs on the Gauss-Legendre contour at e0 (green.f90:471-536 + exchange.f90:1804-1865); x, w host arrays
+      function rsrec_exchange_contour(handle, kind, npairs, same, lld, npts, x, w, e0, sym_term, energy_min, energy_max, a_inf, b_inf, &
+                                      coef_a, coef_b, dmat, pair_offset, npairs_total, xc, rows) &
+         bind(C, name='rsrec_exchange_contour') result(rc)
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: handle
+         integer(c_int), value :: kind, npairs, lld, npts, sym_term, pair_offset, npairs_total
+         real(c_double), value :: e0, energy_min, energy_max
+         type(c_ptr), value :: same, x, w, a_inf, b_inf, coef_a, coef_b, dmat, xc, rows
+         integer(c_int) :: rc
+      end function
+
+      ! orbital occupations of the rank's on-site chains on the same contour (bands.f90:559-586, :631-650); occ is (18, nsites_total)
+      function rsrec_contour_occupation(handle, kind, nsites, lld, npts, x, w, e0, sym_term, energy_min, energy_max, a_inf, b_inf, &
+                                        coef_a, coef_b, site_offset, nsites_total, occ, gdiag) &
+         bind(C, name='rsrec_contour_occupation') result(rc)
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: handle
+         integer(c_int), value :: kind, nsites, lld, npts, sym_term, site_offset, nsites_total
+         real(c_double), value :: e0, energy_min, energy_max
+         type(c_ptr), value :: x, w, a_inf, b_inf, coef_a, coef_b, occ, gdiag
+         integer(c_int) :: rc
+      end function
+
       function rsrec_kubo_moments(handle, nvec, nseed, seed_atoms, seed_coef, cond_ll, a, b, v_a, vo_a, v_b, vo_b, mu_nm) &
          bind(C, name='rsrec_kubo_moments') result(rc)
          import :: c_int, c_ptr, c_double

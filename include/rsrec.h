@@ -282,6 +282,47 @@ int rsrec_damping(rsrec_t *h, int kind, int npairs, const int32_t *same, int lld
                   double energy_min, double energy_max, const double *a_inf, const double *b_inf, const double *coef_a, const double *coef_b,
                   const double *tmat, int pair_offset, int npairs_total, double *at_ef, double *total, double *rows);
 
+/* Exchange couplings on the Gauss-Legendre contour at the Fermi level for the pairs of one rank: green%calculate_intersite_gf_eta
+ * (green.f90:471-536) and exchange%calculate_exchange_gauss_legendre (exchange.f90:1804-1865) in one call, without the *_eta arrays
+ * (kernels_contour.hpp: g of a pair's chains at a point stays in LDS).  Point k is the complex energy e0 + i (1 - x_k) / x_k and carries
+ * the factor w_k / (x_k x_k), applied as the reference applies it: (value * w) / (x * x).  (1 - x_k) / x_k is rounded to single precision, as
+ * the reference's eta = cmplx(0.0_rp, res) without a KIND does (green.f90:508, bands.f90:563).
+ *   kind, same, lld, sym_term, energy_min, energy_max, a_inf, b_inf, coef_a, coef_b, pair_offset, npairs_total: as rsrec_exchange (kind 0:
+ *               block_green_ij_eta, 1: chebyshev_green_ij_eta, all 324 elements; coef_a and coef_b NULL: the resident chains of the last
+ *               seeded call, the same compaction and terminator rules).  Device terminators are computed once per chain, not once per point
+ *   npts, x, w  : the contour: Gauss-Legendre nodes and weights on (0, 1), real (npts) HOST arrays; any npts >= 1 (the reference: 64)
+ *   e0          : ene(fermi_point), the real part of every point
+ *   dmat        : real (9,9,2,npairs): real(ee(1:9,1:9,1,iz) - ee(10:18,10:18,1,iz)) of atom i (side 1) and atom j (side 2), DENSE
+ *   xc          : real (13,npairs_total) out = T_comm_xc: jij = -sum, dmi(1:3) = +sum, aij(3,3) = -sum over the points in ascending
+ *               order, each * 1.0d3 / 4 / pi
+ *   rows        : real (13,npts,npairs) out or NULL: the weighted per-point values jtot, jjtot(1:3), itot(3,3) before sign and scaling
+ * Deviation from the reference, i == j pairs (same = 1): recur_b_ij runs one chain for such a pair and never writes slots 2..4
+ * (recursion.f90:1702-1707), and the reference's contour routine combines chain 1 with those unwritten slots.  Here gij = gji = g(chain 1),
+ * as calculate_intersite_gf takes it (green.f90:446-448).
+ * coef_a, coef_b, a_inf, b_inf, dmat, xc, rows may be host or device memory.  Pairs run in chunks: the device memory that scales with
+ * points is bounded independent of npairs.  Fixed summation order, no atomics: two calls give the same bits and a pair's numbers do not
+ * depend on the other pairs of the call.  Errors: RSREC_ERR_ARG with a message; the handle stays usable.  rsrec_get_timing: out[0] device
+ * ms of the call, out[5] ms in the Green + trace + point-sum kernels. */
+int rsrec_exchange_contour(rsrec_t *h, int kind, int npairs, const int32_t *same, int lld, int npts, const double *x, const double *w, double e0,
+                           int sym_term, double energy_min, double energy_max, const double *a_inf, const double *b_inf, const double *coef_a,
+                           const double *coef_b, const double *dmat, int pair_offset, int npairs_total, double *xc, double *rows);
+
+/* Orbital occupations on the same contour for the on-site chains of one rank: bands%calculate_moments_gauss_legendre (bands.f90:559-586)
+ * and calculate_occupation_gauss_legendre (:631-650):  occ(i) = sum_k Re g_ii(z_k) w_k / x_k^2 / pi + 0.5, k ascending.
+ *   kind        : 0 block_green_eta (green.f90:544-581: bgreen with the point's eta, honouring sym_term), 1 chebyshev_green_eta
+ *               (:1116-1184).  For kind 1 only the diagonal of g is defined: the reference refreshes only mu_ng(i,i,..) there
+ *   nsites, lld : chains (one per site) and their depth
+ *   npts, x, w, e0, sym_term, energy_min, energy_max: as rsrec_exchange_contour
+ *   a_inf, b_inf: real (18,18,nsites) or both NULL: the device terminator, once per chain
+ *   coef_a, coef_b: block: a_b and b2_b AFTER zsqr (18,18,lld,nsites); Chebyshev: mu_n (18,18,2*lld+2,nsites) and NULL.  Both NULL: the
+ *               chains rsrec_block_lanczos / rsrec_chebyshev left on the device (b2_b square-rooted in a private copy)
+ *   site_offset, nsites_total: this rank's sites are columns site_offset+1 .. of the zero-padded image
+ *   occ         : real (18,nsites_total) out;  gdiag: complex (18,npts,nsites) out or NULL: g_ii at every point
+ * Memory, repeatability, errors and timing as rsrec_exchange_contour. */
+int rsrec_contour_occupation(rsrec_t *h, int kind, int nsites, int lld, int npts, const double *x, const double *w, double e0, int sym_term,
+                             double energy_min, double energy_max, const double *a_inf, const double *b_inf, const double *coef_a,
+                             const double *coef_b, int site_offset, int nsites_total, double *occ, double *gdiag);
+
 /* One whole-vector product on caller arrays psi(18,18,kk) (complex, the reference's layout):
  *   vel = 0 : psi_out = (H psi_in - b psi_in)/a      ham_vec_matmul (:913) / ham_hoh_vec_matmul (:785); v_op, vo_op ignored
  *   vel = 1 : psi_out = V psi_in                      velo_vec_matmul (:587, 'n') / velo_hoh_vec_matmul (:656) with v_op (and vo_op with hoh)

@@ -40,6 +40,7 @@
 #include "kernels_kubo.hpp"
 #include "kernels_cond.hpp"
 #include "kernels_exchange.hpp"
+#include "kernels_contour.hpp"
 #include "kernels_assemble.hpp"
 
 using namespace rsrec;
@@ -181,6 +182,7 @@ struct rsrec_handle {
     // coefficients left on the device by the last recursion call: 0 = none, 1 = block Lanczos (d_coefA = a_b, d_coefB = b2_b or its root),
     // 2 = Chebyshev (d_mu = mu_n of all chains)
     int res_kind = 0, res_n = 0, res_lld = 0, res_sqrt = 0;
+    bool res_seeded = false;            // the resident chains come from a seeded (pair) call, not from one chain per site
     // library-level communicator (RCCL, bound with dlopen at rsrec_comm_init): the one exchange of the path without MPI or torch
     void* comm = nullptr;
     int comm_rank = 0, comm_nranks = 1;
@@ -1565,7 +1567,7 @@ int run_block_lanczos(rsrec_t* h, int nchains, int nseed, const int32_t* seed_at
     int status = 0;
     XFER(xfer_d2h(h, &status, h->d_status.p, 4));
     if (status & 1) return fail(h, RSREC_ERR_EIG, "Diagonalization error (18x18 Jacobi did not converge)");
-    h->res_kind = 1; h->res_n = nchains; h->res_lld = lld; h->res_sqrt = 0;
+    h->res_kind = 1; h->res_n = nchains; h->res_lld = lld; h->res_sqrt = 0; h->res_seeded = seed_coef != nullptr;
     return RSREC_OK;
 }
 
@@ -2304,13 +2306,14 @@ int xc_fetch(rsrec_t* h, const double* src, double* stage, size_t n, const doubl
 namespace {
 
 // Call setup shared by the entry points that run a kernel per (pair, energy) on the four chains of every pair (rsrec_exchange,
-// rsrec_damping): the coefficient-source rules, the compaction of resident i == j pairs, the chunking over pairs and the device buffers.
+// rsrec_damping, rsrec_exchange_contour) or, with per = 1, per (site, point) on the one chain of every site (rsrec_contour_occupation): the coefficient-source rules, the compaction of resident i == j pairs, the chunking over pairs and the device buffers.
 //   d_green_in : ene | the call's own inputs (fixed_in) | same | cbase | a_b (or mu_n) | b_sqrt | a_inf (or the Chebyshev kernel) | b_inf |
 //                the chunk's own inputs (chunk_in per pair)                                       (chunk-sized from a_b on)
 //   d_green_out: the rows of the chunk (row_doubles per pair) | the call's own outputs (fixed_out) | chunk_out per pair
 struct PairCall {
     const char* who;
     int kind, npairs, lld, nen, nm, P;             // P: pairs per chunk
+    int per;                                       // chain slots per pair: 4, or 1 when the "pairs" are on-site chains (rsrec_contour_occupation)
     bool resident, compact;
     std::vector<int> cbase;                        // first chain of every pair
     size_t cel;                                    // complex elements per chain (each of a_b, b_sqrt / mu_n)
@@ -2332,35 +2335,37 @@ size_t even(size_t n) { return (n + 1) & ~(size_t)1; }
 
 int pair_call_begin(rsrec_t* h, PairCall& c, const char* who, int kind, int npairs, const int32_t* same, int lld, int nen, const double* ene,
                     double energy_min, double energy_max, const double* a_inf, const double* b_inf, const double* coef_a, const double* coef_b,
-                    size_t row_doubles, size_t fixed_in, size_t chunk_in, size_t fixed_out, size_t chunk_out) {
+                    size_t row_doubles, size_t fixed_in, size_t chunk_in, size_t fixed_out, size_t chunk_out, int per = 4) {
     if (kind < 0 || kind > 1) return fail(h, RSREC_ERR_ARG, "%s: kind %d is neither 0 (block) nor 1 (Chebyshev)", who, kind);
     if ((a_inf == nullptr) != (b_inf == nullptr)) return fail(h, RSREC_ERR_ARG, "%s: give both terminators or neither", who);
     if (kind == 0 && (coef_a == nullptr) != (coef_b == nullptr)) return fail(h, RSREC_ERR_ARG, "%s: give both a_b and b_sqrt or neither", who);
     if (kind == 0 && !a_inf && lld < 2) return fail(h, RSREC_ERR_ARG, "%s: the device terminator needs lld >= 2", who);
-    c.who = who; c.kind = kind; c.npairs = npairs; c.lld = lld; c.nen = nen;
+    c.who = who; c.kind = kind; c.npairs = npairs; c.lld = lld; c.nen = nen; c.per = per;
     c.a_inf = a_inf; c.b_inf = b_inf; c.coef_a = coef_a; c.coef_b = coef_b;
-    const int nchains = 4 * npairs;
+    const int nchains = per * npairs;
     c.resident = coef_a == nullptr;
     int nsame = 0;
-    for (int p = 0; p < npairs; ++p) nsame += same[p] != 0;
+    for (int p = 0; p < npairs; ++p) nsame += (per == 4 && same[p] != 0);
     // first chain of every pair: slot order (4 per pair), or -- resident chains of a seeded call that skipped the repeats of i == j
     // pairs (recur_b_ij, recursion.f90:1705) -- 1 chain for such a pair
     c.compact = c.resident && nsame > 0 && h->res_n == nchains - 3 * nsame;
     if (c.resident && (h->res_kind != (kind == 0 ? 1 : 2) || (h->res_n != nchains && !c.compact) || h->res_lld != lld))
-        return fail(h, RSREC_ERR_ARG, "%s: no %s chains of %d pairs at lld = %d resident (call the seeded recursion first)", who,
-                    kind == 0 ? "block-Lanczos" : "Chebyshev", npairs, lld);
+        return fail(h, RSREC_ERR_ARG, "%s: no %s chains of %d %s at lld = %d resident (call the %s first)", who,
+                    kind == 0 ? "block-Lanczos" : "Chebyshev", npairs, per == 4 ? "pairs" : "sites", lld, per == 4 ? "seeded recursion" : "on-site recursion");
+    if (c.resident && per == 1 && h->res_seeded)     // 4 * npairs seeded chains are not nsites on-site chains, whatever their count
+        return fail(h, RSREC_ERR_ARG, "%s: the resident chains are those of a seeded pair recursion, not on-site chains (call the on-site recursion first)", who);
     if (c.compact && a_inf)        // terminators come in slot order (4 per pair); the compacted chains have no slot for the skipped repeats
         return fail(h, RSREC_ERR_ARG, "%s: resident chains with skipped i == j repeats take no caller terminators (pass NULL)", who);
     c.nm = 2 * lld + 2;
     if (kind == 1 && c.nm > (int)((64 * 1024) / sizeof(double2))) return fail(h, RSREC_ERR_ARG, "%s: lld = %d too deep for the Chebyshev phase table", who, lld);
     c.cbase.assign(npairs + 1, 0);
-    for (int p = 0; p < npairs; ++p) c.cbase[p + 1] = c.cbase[p] + ((c.compact && same[p]) ? 1 : 4);
+    for (int p = 0; p < npairs; ++p) c.cbase[p + 1] = c.cbase[p] + ((c.compact && same[p]) ? 1 : per);
     HIPCK(h, hipSetDevice(h->device));
     const int nm = c.nm;
     c.cel = kind == 0 ? (size_t)lld * BLK : (size_t)nm * BLK;
     const size_t cel = c.cel;
     const size_t rbytes = row_doubles * sizeof(double);                                    // rows of one pair
-    const size_t cbytes = (size_t)4 * cel * sizeof(double2) * (kind == 0 ? 2 : 1);        // coefficients of one pair
+    const size_t cbytes = (size_t)per * cel * sizeof(double2) * (kind == 0 ? 2 : 1);      // coefficients of one pair
     // pairs per chunk: the row scratch <= 256 MiB and the staged coefficients <= 512 MiB, whatever npairs
     c.P = (int)std::max<size_t>(1, std::min<size_t>((size_t)npairs, std::min(((size_t)256 << 20) / rbytes, ((size_t)512 << 20) / cbytes)));
     const size_t P = (size_t)c.P;
@@ -2368,14 +2373,15 @@ int pair_call_begin(rsrec_t* h, PairCall& c, const char* who, int kind, int npai
     // every region starts at an even double: the kernels read complex numbers as double2
     const size_t off_fixed = even(nen), off_same = off_fixed + even(fixed_in), off_cb = off_same + even((npairs + 1) / 2 + 1);
     c.off_ab = off_cb + even((npairs + 2) / 2 + 1);
-    c.off_bs = c.off_ab + 4 * P * cel * 2;
-    c.off_ai = c.off_bs + (kind == 0 ? 4 * P * cel * 2 : 0);
-    c.off_bi = c.off_ai + even(std::max<size_t>(4 * P * BLK, nm));
-    const size_t off_chunk = c.off_bi + 4 * P * BLK;
+    const size_t Q = (size_t)per * P;                                                    // chain slots per chunk
+    c.off_bs = c.off_ab + Q * cel * 2;
+    c.off_ai = c.off_bs + (kind == 0 ? Q * cel * 2 : 0);
+    c.off_bi = c.off_ai + even(std::max<size_t>(Q * BLK, nm));
+    const size_t off_chunk = c.off_bi + Q * BLK;
     HIPCK(h, h->d_green_in.reserve((off_chunk + P * chunk_in) * sizeof(double)));
     const size_t off_fo = P * row_doubles, off_co = off_fo + fixed_out;
     HIPCK(h, h->d_green_out.reserve((off_co + P * chunk_out) * sizeof(double)));
-    if (c.resident && kind == 0) HIPCK(h, h->d_bsqrt.reserve(4 * P * cel * sizeof(double2)));
+    if (c.resident && kind == 0) HIPCK(h, h->d_bsqrt.reserve(Q * cel * sizeof(double2)));
     HIPCK(h, h->d_status.reserve(64));
     HIPCK(h, hipMemsetAsync(h->d_status.p, 0, 64, h->stream));
     c.din = h->d_green_in.as<double>();
@@ -2556,6 +2562,127 @@ extern "C" int rsrec_damping(rsrec_t* h, int kind, int npairs, const int32_t* sa
 
 namespace {
 
+// eta_k = (1 - x_k) / x_k of the contour points, as the reference forms it (green.f90:507-508, bands.f90:562-563): eta = cmplx(0.0_rp, res)
+// has no KIND, so it is default (single-precision) complex and res passes through float before it is added to the energy
+int contour_eta(rsrec_t* h, const char* who, int npts, const double* x, std::vector<double>& eta) {
+    eta.resize(npts);
+    for (int k = 0; k < npts; ++k) {
+        if (!(x[k] > 0.0)) return fail(h, RSREC_ERR_ARG, "%s: x(%d) = %g is not a node on (0, 1]", who, k + 1, x[k]);
+        eta[k] = (double)(float)((1 - x[k]) / x[k]);
+    }
+    return RSREC_OK;
+}
+
+}  // namespace
+
+// green%calculate_intersite_gf_eta + exchange%calculate_exchange_gauss_legendre for the pairs of one rank (kernels_contour.hpp).
+extern "C" int rsrec_exchange_contour(rsrec_t* h, int kind, int npairs, const int32_t* same, int lld, int npts, const double* x, const double* w, double e0,
+                                      int sym_term, double energy_min, double energy_max, const double* a_inf, const double* b_inf, const double* coef_a,
+                                      const double* coef_b, const double* dmat, int pair_offset, int npairs_total, double* xc, double* rows) {
+    if (!h) return RSREC_ERR_ARG;
+    if (npts < 1 || npairs < 1 || lld < 1 || !same || !x || !w || !xc || pair_offset < 0 || npairs_total < pair_offset + npairs)
+        return fail(h, RSREC_ERR_ARG, "rsrec_exchange_contour: bad argument");
+    if (!dmat) return fail(h, RSREC_ERR_ARG, "rsrec_exchange_contour: no dmat (NULL)");
+    if (is_device_ptr(x) || is_device_ptr(w)) return fail(h, RSREC_ERR_ARG, "rsrec_exchange_contour: x and w are host arrays");
+    std::vector<double> eta;
+    int rc = contour_eta(h, "rsrec_exchange_contour", npts, x, eta);
+    if (rc) return rc;
+    const size_t nimg = (size_t)CT_NROW * npairs_total, rdoubles = (size_t)npts * CT_NROW;
+    PairCall c;
+    // the "energies" of the call are the points' eta;  own inputs: x | w;  own chunk inputs: dmat of the chunk's pairs;  own output: the xc image
+    rc = pair_call_begin(h, c, "rsrec_exchange_contour", kind, npairs, same, lld, npts, eta.data(), energy_min, energy_max, a_inf, b_inf, coef_a, coef_b,
+                         rdoubles, (size_t)2 * npts, (size_t)CT_DMAT, nimg, 0);
+    if (rc) return rc;
+    double* d_x = c.d_fixed_in;
+    double* d_w = d_x + npts;
+    double* d_img = c.d_fixed_out;
+    XFER(xfer_h2d(h, d_x, x, (size_t)npts * sizeof(double)));
+    XFER(xfer_h2d(h, d_w, w, (size_t)npts * sizeof(double)));
+    reset_timing(h);
+    hipEvent_t ev0 = next_event(h);
+    HIPCK(h, hipMemsetAsync(d_img, 0, nimg * sizeof(double), h->stream));
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> kev;
+    for (int p0 = 0; p0 < npairs; p0 += c.P) {
+        PairChunk k;
+        rc = pair_call_chunk(h, c, p0, k);                                      // (the terminators: once per chain, not once per point)
+        if (rc) return rc;
+        const int np = k.np;
+        const double* dm = nullptr;
+        XFER(xc_fetch(h, dmat + (size_t)p0 * CT_DMAT, c.d_chunk_in, (size_t)np * CT_DMAT, &dm));
+        std::pair<hipEvent_t, hipEvent_t> ev;
+        ev.first = next_event(h);
+        if (kind == 0)
+            k_contour_xc_block<<<dim3(npts, np), 256, 0, h->stream>>>(lld, npts, e0, c.d_ene, d_x, d_w, sym_term, k.ta, k.tb, k.sa, k.sb, c.d_same + p0, c.d_cb + p0,
+                                                                   k.c0, dm, c.d_rows);
+        else
+            k_contour_xc_cheb<<<dim3(npts, np), 256, (size_t)c.nm * sizeof(double2), h->stream>>>(c.nm, npts, e0, c.d_ene, d_x, d_w, c.ca, c.cb, k.ta, k.sa,
+                                                                                                c.d_same + p0, c.d_cb + p0, k.c0, dm, c.d_rows);
+        HIPCK(h, hipGetLastError());
+        k_contour_xc_sum<<<(np * CT_NROW + 255) / 256, 256, 0, h->stream>>>(npts, np, c.d_rows, pair_offset + p0, d_img);
+        HIPCK(h, hipGetLastError());
+        ev.second = next_event(h);
+        kev.push_back(ev);
+        if (rows) XFER(xc_deliver(h, rows + (size_t)p0 * rdoubles, c.d_rows, (size_t)np * rdoubles));
+        if (p0 + c.P < npairs) HIPCK(h, hipStreamSynchronize(h->stream));         // the chunk's staging buffers are reused
+    }
+    XFER(xc_deliver(h, xc, d_img, nimg));
+    return pair_call_end(h, ev0, kev);
+}
+
+// The occupations of bands%calculate_moments_gauss_legendre / calculate_occupation_gauss_legendre for the on-site chains of one rank.
+extern "C" int rsrec_contour_occupation(rsrec_t* h, int kind, int nsites, int lld, int npts, const double* x, const double* w, double e0, int sym_term,
+                                        double energy_min, double energy_max, const double* a_inf, const double* b_inf, const double* coef_a,
+                                        const double* coef_b, int site_offset, int nsites_total, double* occ, double* gdiag) {
+    if (!h) return RSREC_ERR_ARG;
+    if (npts < 1 || nsites < 1 || lld < 1 || !x || !w || !occ || site_offset < 0 || nsites_total < site_offset + nsites)
+        return fail(h, RSREC_ERR_ARG, "rsrec_contour_occupation: bad argument");
+    if (is_device_ptr(x) || is_device_ptr(w)) return fail(h, RSREC_ERR_ARG, "rsrec_contour_occupation: x and w are host arrays");
+    std::vector<double> eta;
+    int rc = contour_eta(h, "rsrec_contour_occupation", npts, x, eta);
+    if (rc) return rc;
+    const size_t nimg = (size_t)NB * nsites_total, rdoubles = (size_t)npts * NB * 2;
+    const std::vector<int32_t> same(nsites, 0);
+    PairCall c;
+    // one chain per site;  own inputs: x | w;  own output: the occ image;  the rows of a chunk: the diagonal of g at every point
+    rc = pair_call_begin(h, c, "rsrec_contour_occupation", kind, nsites, same.data(), lld, npts, eta.data(), energy_min, energy_max, a_inf, b_inf, coef_a,
+                         coef_b, rdoubles, (size_t)2 * npts, 0, nimg, 0, 1);
+    if (rc) return rc;
+    double* d_x = c.d_fixed_in;
+    double* d_w = d_x + npts;
+    double* d_img = c.d_fixed_out;
+    double2* d_gd = reinterpret_cast<double2*>(c.d_rows);
+    XFER(xfer_h2d(h, d_x, x, (size_t)npts * sizeof(double)));
+    XFER(xfer_h2d(h, d_w, w, (size_t)npts * sizeof(double)));
+    reset_timing(h);
+    hipEvent_t ev0 = next_event(h);
+    HIPCK(h, hipMemsetAsync(d_img, 0, nimg * sizeof(double), h->stream));
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> kev;
+    for (int s0 = 0; s0 < nsites; s0 += c.P) {
+        PairChunk k;
+        rc = pair_call_chunk(h, c, s0, k);
+        if (rc) return rc;
+        const int ns = k.np;
+        std::pair<hipEvent_t, hipEvent_t> ev;
+        ev.first = next_event(h);
+        if (kind == 0)
+            k_contour_occ_block<<<dim3((npts + GREEN_WAVES - 1) / GREEN_WAVES, ns), GREEN_WAVES * 64, 0, h->stream>>>(lld, npts, e0, c.d_ene, sym_term, k.ta, k.tb,
+                                                                                                                   k.sa, k.sb, d_gd);
+        else
+            k_contour_occ_cheb<<<dim3(npts, ns), 64, (size_t)c.nm * sizeof(double2), h->stream>>>(c.nm, npts, e0, c.d_ene, c.ca, c.cb, k.ta, k.sa, d_gd);
+        HIPCK(h, hipGetLastError());
+        k_contour_occ_sum<<<(ns * NB + 255) / 256, 256, 0, h->stream>>>(npts, ns, d_x, d_w, d_gd, site_offset + s0, d_img);
+        HIPCK(h, hipGetLastError());
+        ev.second = next_event(h);
+        kev.push_back(ev);
+        if (gdiag) XFER(xc_deliver(h, gdiag + (size_t)s0 * rdoubles, c.d_rows, (size_t)ns * rdoubles));
+        if (s0 + c.P < nsites) HIPCK(h, hipStreamSynchronize(h->stream));         // the chunk's staging buffers are reused
+    }
+    XFER(xc_deliver(h, occ, d_img, nimg));
+    return pair_call_end(h, ev0, kev);
+}
+
+namespace {
+
 template <class L, bool MFMA>
 int run_chebyshev(rsrec_t* h, int nsites, int nseed, const int32_t* seed_atoms, const double* seed_coef, int lld, double a, double b, double* mu_n) {
     int rc = 0;
@@ -2710,7 +2837,7 @@ int run_chebyshev(rsrec_t* h, int nsites, int nseed, const int32_t* seed_atoms, 
     int status = 0;
     XFER(xfer_d2h(h, &status, h->d_status.p, 4));
     if (status & 2) return fail(h, RSREC_ERR_DIVERGED, "Chebyshev moments did not converge. Check energy limits energy_min and energy_max");
-    h->res_kind = 2; h->res_n = nsites; h->res_lld = lld; h->res_sqrt = 0;
+    h->res_kind = 2; h->res_n = nsites; h->res_lld = lld; h->res_sqrt = 0; h->res_seeded = seed_coef != nullptr;
     return RSREC_OK;
 }
 

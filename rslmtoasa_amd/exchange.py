@@ -13,6 +13,7 @@ from . import _lib
 
 NINT = 41   # integrand rows per (pair, energy), order in kernels_exchange.hpp
 NDAMP = 18  # damping rows per (pair, energy): dtott (9, l fastest), then dtottim (9)
+NCONT = 13  # contour rows per (pair, point): jtot, jjtot(1:3), itot(3,3) (k fastest) = T_comm_xc's order
 
 
 def _ptr(a):
@@ -58,6 +59,38 @@ def damping_tmat(tmat, iz, pairs):
         for side in range(2):
             out[:, :, :, side, p] = tmat[:, :, :, int(iz[int(ij[side]) - 1]) - 1]
     return out
+
+
+def contour_dmat(ee, iz, pairs):
+    """dmat (9,9,2,npairs) for rsrec_exchange_contour from hamiltonian%ee (18,18,nnmax,ntype): per pair, of atom i then atom j,
+    real(ee(1:9,1:9,1,iz) - ee(10:18,10:18,1,iz)) (exchange.f90:1819-1820) -- a dense matrix, unlike the diagonal d_matrix of ``exchange_dpar``."""
+    ee, iz, pairs = np.asarray(ee), np.asarray(iz), np.asarray(pairs)
+    out = np.zeros((9, 9, 2, len(pairs)), np.float64, order="F")
+    for p, ij in enumerate(pairs):
+        for side in range(2):
+            t = int(iz[int(ij[side]) - 1]) - 1
+            out[:, :, side, p] = np.real(ee[0:9, 0:9, 0, t] - ee[9:18, 9:18, 0, t])
+    return out
+
+
+def gauss_legendre(n, a=0.0, b=1.0):
+    """n-point Gauss-Legendre nodes and weights on (a, b), the nodes in DESCENDING order as the reference's gauss_legendre returns them
+    (math.f90:1763-1794): Newton's iteration on P_n from the Chebyshev guess, to 1e-14, the node pairs filled symmetrically."""
+    x, w = np.zeros(n), np.zeros(n)
+    for i in range(1, (n + 1) // 2 + 1):
+        z = np.cos(np.pi * (i - 0.25) / (n + 0.5))
+        while True:
+            p1, p2 = 1.0, 0.0
+            for j in range(1, n + 1):
+                p1, p2 = ((2.0 * j - 1.0) * z * p1 - (j - 1.0) * p2) / j, p1
+            pp = n * (z * p1 - p2) / (z * z - 1.0)
+            z1, z = z, z - p1 / pp
+            if abs(z - z1) <= 1e-14:
+                break
+        x[i - 1] = a + (b - a) * (z + 1) / 2
+        x[n - i] = a + (b - a) * (1 - z) / 2
+        w[i - 1] = w[n - i] = (b - a) * 2.0 / ((1.0 - z * z) * pp * pp) / 2
+    return x, w
 
 
 class Exchange:
@@ -144,6 +177,30 @@ class Exchange:
                                          int(pair_offset), int(npairs_total), _ptr(at_ef), _ptr(total), _ptr(out_rows)))
         del ca, cb
         return (at_ef, total, out_rows) if rows else (at_ef, total)
+
+    def contour(self, x, w, e0, dmat, kind="block", resident=False, coef=None, a_inf=None, b_inf=None, pair_offset=0, npairs_total=None, rows=False):
+        """green%calculate_intersite_gf_eta + exchange%calculate_exchange_gauss_legendre in one call (``rsrec_exchange_contour``): returns
+        xc = T_comm_xc (13, npairs_total), then the weighted per-point values (13, npts, npairs) if ``rows``.
+
+        ``x, w``: Gauss-Legendre nodes and weights on (0, 1) (``gauss_legendre``); ``e0`` = ene(fermi_point); ``dmat``: (9,9,2,npairs)
+        (``contour_dmat``), a numpy array or a device tensor in that memory order.  Pairs, coefficients and terminators as ``compute``.
+        An i == j pair takes gij = gji = g(chain 1), as calculate_intersite_gf does (the reference's contour routine defines no result there)."""
+        rec = self.recursion
+        _, npairs, npairs_total, same, lld, k, ca, cb, a_inf, b_inf = self._call_setup(kind, resident, coef, a_inf, b_inf, npairs_total)
+        x, w = np.ascontiguousarray(x, dtype=np.float64), np.ascontiguousarray(w, dtype=np.float64)
+        if x.ndim != 1 or x.shape != w.shape:
+            raise ValueError("x and w must be one-dimensional and alike, got %r and %r" % (x.shape, w.shape))
+        if dmat is not None and not hasattr(dmat, "data_ptr"):
+            dmat = np.asfortranarray(dmat, dtype=np.float64)
+            if dmat.shape != (9, 9, 2, npairs):
+                raise ValueError("dmat must be (9, 9, 2, %d), got %r" % (npairs, dmat.shape))
+        xc = np.zeros((NCONT, npairs_total), order="F")
+        out_rows = np.zeros((NCONT, len(x), npairs), order="F") if rows else None
+        rec._check(rec._L.rsrec_exchange_contour(rec._h, k, npairs, _ptr(same), lld, len(x), _ptr(x), _ptr(w), float(e0), int(self.green.sym_term),
+                                                  float(rec.en.energy_min), float(rec.en.energy_max), _ptr(a_inf), _ptr(b_inf), _any_ptr(ca), _any_ptr(cb),
+                                                  _any_ptr(dmat), int(pair_offset), int(npairs_total), _ptr(xc), _ptr(out_rows)))
+        del ca, cb
+        return (xc, out_rows) if rows else xc
 
     def timing(self):
         """(device ms of the last call, ms in its Green + trace + integration kernels)."""

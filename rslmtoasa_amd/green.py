@@ -109,6 +109,47 @@ class Green:
                                            int(site_offset), int(ntot), ptrs[0], ptrs[1], ptrs[2], _ptr(a_inf), _ptr(b_inf)))
         return dict(dtot=dtot, dosia=dosia, dosial=dosial, a_inf=a_inf, b_inf=b_inf)
 
+    def contour_occupation(self, x, w, e0, kind="block", site_offset=0, nsites_total=None, diag=False, resident=False, coef=None, a_inf=None, b_inf=None):
+        """The orbital occupations of bands%calculate_moments_gauss_legendre / calculate_occupation_gauss_legendre (bands.f90:559-586,
+        :631-650) on the Gauss-Legendre contour at ``e0`` = ene(fermi_point), in one call (``rsrec_contour_occupation``): returns
+        occ (18, nsites_total), then g_ii at every point (18, npts, nsites) if ``diag``.
+
+        ``x, w``: nodes and weights on (0, 1).  ``kind``: "block" (block_green_eta) or "chebyshev" (chebyshev_green_eta, the diagonal
+        only).  Chains: ``resident=True`` reads what the last ``recur_b`` / ``chebyshev_recur`` left on the device; else ``coef`` (a_b, b_sqrt) / (mu_n,) if
+        given (numpy arrays or device tensors in that memory order, one chain per site of this rank), else the recursion's arrays (a_b,
+        b2_b after zsqr / mu_n).  Terminators: ``a_inf, b_inf`` (18,18,nsites) or None (computed on the device, once per chain)."""
+        rec = self.recursion
+        k = {"block": 0, "chebyshev": 1}[kind] if isinstance(kind, str) else int(kind)
+        start, end = rec._my_sites()[:2]
+        n = end - start + 1
+        ntot = n + site_offset if nsites_total is None else nsites_total
+        lld = int(rec.control.lld)
+        x, w = np.ascontiguousarray(x, dtype=np.float64), np.ascontiguousarray(w, dtype=np.float64)
+        if x.ndim != 1 or x.shape != w.shape:
+            raise ValueError("x and w must be one-dimensional and alike, got %r and %r" % (x.shape, w.shape))
+        ca = cb = None
+        if not resident and coef is not None:
+            arrs = [a if hasattr(a, "data_ptr") else np.asfortranarray(a, dtype=np.complex128) for a in coef]
+            ca, cb = arrs[0], (arrs[1] if len(arrs) > 1 else None)
+            n = int(ca.shape[0] if hasattr(ca, "data_ptr") else ca.shape[3])
+            lld = int(ca.shape[1] if hasattr(ca, "data_ptr") else ca.shape[2])
+            lld = lld if k == 0 else (lld - 2) // 2
+            ntot = n + site_offset if nsites_total is None else nsites_total
+        elif not resident:
+            if k == 0:
+                ca = np.asfortranarray(rec.a_b[:, :, :, :n], dtype=np.complex128)
+                cb = np.asfortranarray(rec.b2_b[:, :, :, :n], dtype=np.complex128)
+            else:
+                ca = np.asfortranarray(rec.mu_n[:, :, :, :n], dtype=np.complex128)
+        if a_inf is not None:
+            a_inf, b_inf = np.asfortranarray(a_inf, dtype=np.float64), np.asfortranarray(b_inf, dtype=np.float64)
+        from .exchange import _any_ptr as P             # numpy arrays, device tensors, None
+        occ = np.zeros((18, ntot), order="F")
+        gd = np.zeros((18, len(x), n), np.complex128, order="F") if diag else None
+        rec._check(rec._L.rsrec_contour_occupation(rec._h, k, n, lld, len(x), _ptr(x), _ptr(w), float(e0), int(self.sym_term), float(rec.en.energy_min),
+                                                   float(rec.en.energy_max), P(a_inf), P(b_inf), P(ca), P(cb), int(site_offset), int(ntot), _ptr(occ), P(gd)))
+        return (occ, gd) if diag else occ
+
     def chebyshev_green(self, nsites=None):
         """green%chebyshev_green (green.f90:1030-1108): g0 from the Chebyshev moments ``recursion.mu_n``."""
         rec = self.recursion
