@@ -17,10 +17,19 @@
 !> reduction -- the MPI_ALLREDUCE of the zero-padded arrays (:271-274), the three output files (:279-324), the Fermi level
 !> (:326-343) -- is the reference's, restated here because `calculate_fermi` is one routine.
 !>
-!> `g0` on demand: the other consumers of `g0` in `bands` (magnetic / orbital moments, band moments, projected DOS) are inherited;
-!> the overrides below only make sure `g0` exists first (`green_gpu%fetch_g0`, a no-op unless `green_gpu%defer_g0` postponed it).
-!> An SCF iteration reads `g0` in `calculate_magnetic_moments`, so it is produced once per iteration either way; a flow that stops
-!> at the densities of states (calculation.f90:700-712 `block_green` + `calculate_fermi`) never produces it.
+!> The moment stage of an SCF iteration (self.f90:837-852: `calculate_magnetic_moments`, `calculate_moments` with
+!> `calculate_orbital_moments`) reads `g0` only through linear functionals Im Tr(O g0): the spin-resolved s / p / d brackets of
+!> bands.f90:449-452 (whose sums are dx, dy, dz of :1175-1177) and Im Tr(L_a g0) of :1124-1126.  While `g0` is still pending in
+!> `green_gpu` (`defer_g0`) and `device_moments` is set, ONE `rsrec_block_spectra` / `rsrec_chebyshev_spectra` call per recursion result
+!> evaluates those 15 functionals on the resident chains (timer region `spectra-gpu`), the image is kept in the type, and the three
+!> routines take their energy-resolved arrays from it; their tails (Simpson integrals, `<sym>_orbene.out`, log lines, `gravity_center`,
+!> `ql`, `calculate_pl`, the exchange of the potentials between ranks) are the reference's lines restated.  No `g0` is produced in such
+!> an iteration.  Deviation: `g0_x, g0_y, g0_z, d_orb` stay zero on this route (no routine of the reference reads them);
+!> RSREC_HOST_MOMENTS restores them with the host route.
+!>
+!> `g0` on demand: the remaining consumers of `g0` (orbital quadrupoles, projected Green function, orbital DOS) and every case the
+!> device route does not take are inherited; the overrides below only make sure `g0` exists first (`green_gpu%fetch_g0`, a no-op unless
+!> `green_gpu%defer_g0` postponed it).
 !>
 !> Falls back to the inherited routine whenever the device does not hold this call's coefficients or moments (scalar recursion,
 !> local-axis runs, a `green` that is not `green_gpu`).
@@ -32,7 +41,7 @@ module bands_gpu_mod
    use green_mod
    use green_gpu_mod
    use precision_mod, only: rp
-   use math_mod, only: pi, gauss_legendre
+   use math_mod, only: pi, gauss_legendre, simpson_m, simpson_f, L_x, L_y, L_z, hcpx, i_unit
    use logger_mod, only: g_logger
    use timer_mod, only: g_timer
    use string_mod, only: fmt
@@ -51,6 +60,16 @@ module bands_gpu_mod
       logical :: device_ldos = .true.
       !> number of calculate_fermi calls served by the device stage (diagnostics / tests)
       integer :: n_device_ldos = 0
+      !> .false.: the moment stage always reads a g0 on the host (the inherited routines)
+      logical :: device_moments = .true.
+      !> number of spectra calls made (diagnostics / tests)
+      integer :: n_device_spectra = 0
+      !> Im Tr(O_k g0) of the 15 SCF operators, (15, nE, nrec), this rank's sites filled; valid until calculate_fermi runs again
+      real(rp), dimension(:, :, :), allocatable :: spec
+      logical :: spec_valid = .false.
+      integer :: spec_resident = -1       ! residency count the image was made for
+      !> the operators, built once: 1-12 = P(c, l), c = 0, x, y, z outer, l = s, p, d inner; 13-15 = Lx, Ly, Lz
+      complex(rp), dimension(:, :, :), allocatable :: spec_ops
    contains
       procedure :: calculate_fermi => gpu_calculate_fermi
       procedure :: calculate_magnetic_moments => gpu_calculate_magnetic_moments
@@ -86,6 +105,7 @@ contains
       obj%recursion => green_obj%dos%recursion
       call obj%restore_to_default()
       if (rsrec_env_flag('RSREC_HOST_LDOS')) obj%device_ldos = .false.   ! (hosts that cannot reach the member: fortran/shadow/)
+      if (rsrec_env_flag('RSREC_HOST_MOMENTS')) obj%device_moments = .false.
    end function gpu_constructor
 
    !> bands.f90:178-217.  In a pair run (lattice%njij /= 0: the exchange post-processing, calculation.f90:816-950) atoms_per_process
@@ -151,6 +171,7 @@ contains
       real(rp) :: e1, e1_mag, ef_mag
       real(rp), allocatable, target :: ene(:), dtot(:), dosia(:, :), dosial(:, :, :)
 
+      this%spec_valid = .false.           ! a new Green function: the moment stage after it forms its own image
       if (.not. device_stage_usable(this)) then
          call ensure_g0(this)
          call this%bands%calculate_fermi()
@@ -250,17 +271,208 @@ contains
       close (unitnum)
    end subroutine write_columns
 
-   ! ---- inherited consumers of g0: make sure it exists, then the reference's routine ------------------------------------
+   ! ---- the moment stage: from the spectra image where g0 is still pending on the device, else g0 and the reference's routine ------
+   !> .true. if this call is served from the resident chains: the device holds them, device_moments, and g0 is pending in green_gpu
+   function spectra_route(this) result(ok)
+      class(bands_gpu), intent(in) :: this
+      logical :: ok
+      ok = this%device_moments
+      if (ok) ok = device_stage_usable(this)
+      if (ok) then
+         select type (g => this%green)
+         class is (green_gpu)
+            ok = g%defer_g0 .and. g%g0_stale
+         class default
+            ok = .false.
+         end select
+      end if
+   end function spectra_route
+
+   !> The 15 operators: P(c, l) such that Im Tr(P g) is the bracket of bands.f90:449-452 with spin component c over the orbitals of l,
+   !> and the cartesian L matrices through cart2sph, the same block in both spins (bands.f90:1094-1111).  Tr(P g) = sum P(j, i) g(i, j).
+   subroutine build_spectra_ops(this)
+      class(bands_gpu), intent(inout) :: this
+      integer :: l, m, o, k
+      complex(rp), dimension(9, 9) :: mL
+
+      allocate (this%spec_ops(18, 18, 15))
+      this%spec_ops = (0.0_rp, 0.0_rp)
+      do l = 1, 3
+         do m = 1, 2*l - 1
+            o = (l - 1)**2 + m
+            this%spec_ops(o, o, l) = 1.0_rp;          this%spec_ops(o + 9, o + 9, l) = 1.0_rp          ! g(o,o) + g(o+9,o+9)
+            this%spec_ops(o + 9, o, 3 + l) = 1.0_rp;  this%spec_ops(o, o + 9, 3 + l) = 1.0_rp          ! g(o,o+9) + g(o+9,o)
+            this%spec_ops(o + 9, o, 6 + l) = i_unit;  this%spec_ops(o, o + 9, 6 + l) = -i_unit         ! i g(o,o+9) - i g(o+9,o)
+            this%spec_ops(o, o, 9 + l) = 1.0_rp;      this%spec_ops(o + 9, o + 9, 9 + l) = -1.0_rp     ! g(o,o) - g(o+9,o+9)
+         end do
+      end do
+      do k = 1, 3
+         select case (k)
+         case (1); mL = L_x
+         case (2); mL = L_y
+         case (3); mL = L_z
+         end select
+         call hcpx(mL, 'cart2sph')
+         this%spec_ops(1:9, 1:9, 12 + k) = mL
+         this%spec_ops(10:18, 10:18, 12 + k) = mL
+      end do
+   end subroutine build_spectra_ops
+
+   !> One library call per recursion result: the image of the 15 functionals for the rank's sites
+   subroutine ensure_spectra(this)
+      class(bands_gpu), intent(inout), target :: this
+      integer :: nv, nrec, nres
+      integer(c_int) :: rc, sym_i
+      type(c_ptr) :: handle
+      real(rp), allocatable, target :: ene(:)
+      real(rp), dimension(:, :, :), pointer :: sp
+      complex(rp), dimension(:, :, :), pointer :: op
+
+      nv = this%en%channels_ldos + 10
+      nrec = this%lattice%nrec
+      nres = rsrec_gpu_block_resident() + rsrec_gpu_cheb_resident()
+      if (this%spec_valid .and. allocated(this%spec) .and. nres == this%spec_resident) then
+         if (size(this%spec, 2) == nv .and. size(this%spec, 3) == nrec) return
+      end if
+      if (.not. allocated(this%spec_ops)) call build_spectra_ops(this)
+      if (allocated(this%spec)) then
+         if (size(this%spec, 2) /= nv .or. size(this%spec, 3) /= nrec) deallocate (this%spec)
+      end if
+      if (.not. allocated(this%spec)) allocate (this%spec(15, nv, nrec))
+      allocate (ene(nv))
+      ene = this%en%ene(1:nv)
+      sym_i = 0
+      if (this%control%sym_term) sym_i = 1
+      handle = rsrec_gpu_context()
+      sp => this%spec
+      op => this%spec_ops
+      call g_timer%start('spectra-gpu')
+      if (trim(this%control%recur) == 'chebyshev') then
+         rc = rsrec_chebyshev_spectra(handle, 15_c_int, c_loc(op), int(nv, c_int), c_loc(ene), real(this%en%energy_min, c_double), &
+                                      real(this%en%energy_max, c_double), int(start_atom - 1, c_int), int(nrec, c_int), c_loc(sp))
+      else
+         rc = rsrec_block_spectra(handle, 15_c_int, c_loc(op), int(nv, c_int), c_loc(ene), 0.0_c_double, 0.0_c_double, sym_i, &
+                                  int(start_atom - 1, c_int), int(nrec, c_int), c_loc(sp))
+      end if
+      call g_timer%stop('spectra-gpu')
+      if (rc /= 0) call g_logger%fatal('rsrec_'//trim(this%control%recur)//'_spectra: '//rsrec_error_string(handle), __FILE__, __LINE__)
+      this%n_device_spectra = this%n_device_spectra + 1
+      this%spec_valid = .true.
+      this%spec_resident = nres
+   end subroutine ensure_spectra
+
+   !> calculate_magnetic_moments (bands.f90:791-855) reads nothing of g0 itself: it integrates the dx, dy, dz of calculate_projected_dos.
+   !> A call through the parent component would bind that inner call to the reference's routine (the parent component's dynamic type is
+   !> `bands`), so on the device route the routine is restated here around this type's calculate_projected_dos.
    subroutine gpu_calculate_magnetic_moments(this)
       class(bands_gpu) :: this
-      call ensure_g0(this)
-      call this%bands%calculate_magnetic_moments()
+      real(rp) :: mx, my, mz, mxe, mye, mze
+      integer :: na, ie, na_loc, unitmag, pb
+      character(len=256) :: fnamemag
+
+      if (.not. spectra_route(this)) then
+         call ensure_g0(this)
+         call this%bands%calculate_magnetic_moments()
+         return
+      end if
+
+      call this%calculate_projected_dos()
+
+      do na = start_atom, end_atom
+         na_loc = g2l_map(na)
+         pb = this%lattice%nbulk + na
+         call simpson_m(this%symbolic_atom(pb)%potential%mx, this%en%edel, this%en%fermi, this%nv1, this%dx(:, na_loc), this%e1, 0, this%en%ene)
+         call simpson_m(this%symbolic_atom(pb)%potential%my, this%en%edel, this%en%fermi, this%nv1, this%dy(:, na_loc), this%e1, 0, this%en%ene)
+         call simpson_m(this%symbolic_atom(pb)%potential%mz, this%en%edel, this%en%fermi, this%nv1, this%dz(:, na_loc), this%e1, 0, this%en%ene)
+
+         fnamemag = trim(this%symbolic_atom(pb)%element%symbol)//"_spinene.out"
+         unitmag = 1000
+         open (unit=unitmag, file=fnamemag, status='replace', action='write')
+         do ie = 1, this%en%channels_ldos + 10
+            mxe = 0.0d0; mye = 0.d00; mze = 0.0d0
+            call simpson_f(mxe, this%en%ene, this%en%ene(ie), this%en%nv1, this%dx(:, na_loc), .true., .false., 0.0d0)
+            call simpson_f(mye, this%en%ene, this%en%ene(ie), this%en%nv1, this%dy(:, na_loc), .true., .false., 0.0d0)
+            call simpson_f(mze, this%en%ene, this%en%ene(ie), this%en%nv1, this%dz(:, na_loc), .true., .false., 0.0d0)
+            write (unitmag, '(4es16.6)') this%en%ene(ie) - this%en%fermi, mxe, mye, mze
+         end do
+         rewind (unitmag)
+         close (unitmag)
+
+         this%symbolic_atom(pb)%potential%mom0(1) = this%symbolic_atom(pb)%potential%mx
+         this%symbolic_atom(pb)%potential%mom0(2) = this%symbolic_atom(pb)%potential%my
+         this%symbolic_atom(pb)%potential%mom0(3) = this%symbolic_atom(pb)%potential%mz
+
+         call simpson_m(this%symbolic_atom(pb)%potential%mom1(1), this%en%edel, this%en%fermi, this%nv1, this%dx(:, na_loc), this%e1, 1, this%en%ene)
+         call simpson_m(this%symbolic_atom(pb)%potential%mom1(2), this%en%edel, this%en%fermi, this%nv1, this%dy(:, na_loc), this%e1, 1, this%en%ene)
+         call simpson_m(this%symbolic_atom(pb)%potential%mom1(3), this%en%edel, this%en%fermi, this%nv1, this%dz(:, na_loc), this%e1, 1, this%en%ene)
+
+         this%symbolic_atom(pb)%potential%mtot = sqrt((this%symbolic_atom(pb)%potential%mx**2) + (this%symbolic_atom(pb)%potential%my**2) + &
+                                                      (this%symbolic_atom(pb)%potential%mz**2)) + 1.0d-15
+
+         this%symbolic_atom(pb)%potential%mom(1) = this%symbolic_atom(pb)%potential%mx/this%symbolic_atom(pb)%potential%mtot
+         this%symbolic_atom(pb)%potential%mom(2) = this%symbolic_atom(pb)%potential%my/this%symbolic_atom(pb)%potential%mtot
+         this%symbolic_atom(pb)%potential%mom(3) = this%symbolic_atom(pb)%potential%mz/this%symbolic_atom(pb)%potential%mtot
+
+         call g_logger%info('Spin moment of atom'//fmt('i4', na)//' is '//fmt('f10.6', this%symbolic_atom(pb)%potential%mtot), __FILE__, __LINE__)
+         mx = this%symbolic_atom(pb)%potential%mx
+         my = this%symbolic_atom(pb)%potential%my
+         mz = this%symbolic_atom(pb)%potential%mz
+
+         if (this%control%nsp < 3) this%symbolic_atom(pb)%potential%mom(:) = [0.0d0, 0.0d0, 1.00d0]
+
+         ! (local-axis runs never take this route: device_stage_usable)
+         call g_logger%info('Spin moment projections of atom'//fmt('i4', na)//' is '//fmt('f10.6', mx)//' '//fmt('f10.6', my)//' '//fmt('f10.6', mz), __FILE__, __LINE__)
+      end do
    end subroutine gpu_calculate_magnetic_moments
 
+   !> calculate_orbital_moments (bands.f90:1075-1156): lxi, lyi, lzi from the image, the tail restated
    subroutine gpu_calculate_orbital_moments(this)
       class(bands_gpu) :: this
-      call ensure_g0(this)
-      call this%bands%calculate_orbital_moments()
+      real(rp) :: lx, ly, lz, lxe, lye, lze
+      ! one element longer than the reference's, and zero there: with nv1 = channels_ldos + 1 simpson_f reads Y(nv1 + 10)
+      real(rp), dimension(this%en%channels_ldos + 11) :: lxi, lyi, lzi
+      integer :: na, ie, unitorb, nv
+      character(len=256) :: fnameorb
+
+      if (.not. spectra_route(this)) then
+         call ensure_g0(this)
+         call this%bands%calculate_orbital_moments()
+         return
+      end if
+      call ensure_spectra(this)
+      nv = this%en%channels_ldos + 10
+      do na = start_atom, end_atom
+         lx = 0.0d0; ly = 0.0d0; lz = 0.d0
+         lxi = 0.0d0; lyi = 0.0d0; lzi = 0.0d0
+         lxi(1:nv) = this%spec(13, :, na)
+         lyi(1:nv) = this%spec(14, :, na)
+         lzi(1:nv) = this%spec(15, :, na)
+
+         call simpson_m(lx, this%en%edel, this%en%fermi, this%nv1, lxi, this%e1, 0, this%en%ene)
+         call simpson_m(ly, this%en%edel, this%en%fermi, this%nv1, lyi, this%e1, 0, this%en%ene)
+         call simpson_m(lz, this%en%edel, this%en%fermi, this%nv1, lzi, this%e1, 0, this%en%ene)
+
+         fnameorb = trim(this%symbolic_atom(this%lattice%nbulk + na)%element%symbol)//"_orbene.out"
+         unitorb = (rank + 1)*132 + na
+         open (unit=unitorb, file=fnameorb, status='replace', action='write')
+         do ie = 1, this%en%channels_ldos + 10
+            call simpson_f(lxe, this%en%ene, this%en%ene(ie), this%en%nv1, lxi, .true., .false., 0.0d0)
+            call simpson_f(lye, this%en%ene, this%en%ene(ie), this%en%nv1, lyi, .true., .false., 0.0d0)
+            call simpson_f(lze, this%en%ene, this%en%ene(ie), this%en%nv1, lzi, .true., .false., 0.0d0)
+            write (unitorb, '(4es16.6)') this%en%ene(ie) - this%en%fermi, -(lxe/pi), -(lye/pi), -(lze/pi)
+         end do
+         rewind (unitorb)
+         close (unitorb)
+
+         lz = -(lz/pi)
+         lx = -(lx/pi)
+         ly = -(ly/pi)
+
+         call g_logger%info('Orbital moment of atom'//fmt('i4', na)//' is '//fmt('f10.6', lx)//' '//fmt('f10.6', ly)//' '//fmt('f10.6', lz), __FILE__, __LINE__)
+         this%symbolic_atom(this%lattice%nbulk + na)%potential%lmom(1) = lx
+         this%symbolic_atom(this%lattice%nbulk + na)%potential%lmom(2) = ly
+         this%symbolic_atom(this%lattice%nbulk + na)%potential%lmom(3) = lz
+      end do
    end subroutine gpu_calculate_orbital_moments
 
    subroutine gpu_calculate_orbital_quadrupoles(this)
@@ -269,10 +481,83 @@ contains
       call this%bands%calculate_orbital_quadrupoles()
    end subroutine gpu_calculate_orbital_quadrupoles
 
+   !> calculate_moments (bands.f90:409-524): dspd from the image and the (mixed) moment directions, the tail restated.  Local-axis runs
+   !> never come here (their chains are not resident: device_stage_usable), so the rotation branch of :458-467 has no counterpart.
    subroutine gpu_calculate_moments(this)
       class(bands_gpu) :: this
-      call ensure_g0(this)
-      call this%bands%calculate_moments()
+      integer :: i, l, ie, na, na_glob, isp, soff, nsp, plusbulk
+      real(rp) :: sgef, pmef, smef, isgn
+      real(rp), dimension(3) :: mom
+      real(rp), dimension(this%en%channels_ldos + 10) :: y
+#ifdef USE_MPI
+      integer :: pot_size
+      real(rp), dimension(:, :), allocatable :: T_comm
+#endif
+
+      if (.not. spectra_route(this)) then
+         call ensure_g0(this)
+         call this%bands%calculate_moments()
+         return
+      end if
+
+      call this%calculate_orbital_moments()
+      call ensure_spectra(this)
+
+      this%dspd(:, :, :) = 0.0d0
+      do na_glob = start_atom, end_atom
+         na = g2l_map(na_glob)
+         plusbulk = this%lattice%nbulk + na_glob
+         mom = this%symbolic_atom(plusbulk)%potential%mom
+         do isp = 1, 2
+            isgn = (-1.0d0)**(isp - 1)
+            soff = 3*(isp - 1)
+            do l = 1, 3
+               do ie = 1, this%en%channels_ldos
+                  this%dspd(l + soff, ie, na) = -this%spec(l, ie, na_glob) - isgn*mom(3)*this%spec(9 + l, ie, na_glob) &
+                                                - isgn*mom(2)*this%spec(6 + l, ie, na_glob) - isgn*mom(1)*this%spec(3 + l, ie, na_glob)
+               end do
+            end do
+         end do
+      end do
+      this%dspd(:, :, :) = this%dspd(:, :, :)*0.5d0/pi
+
+      do na_glob = start_atom, end_atom
+         na = g2l_map(na_glob)
+         plusbulk = this%lattice%nbulk + na_glob
+         do i = 1, 6
+            if (i > 3) then
+               nsp = 2
+            else
+               nsp = 1
+            end if
+            soff = 3*(nsp - 1)
+            y(:) = this%dspd(i, :, na)
+            sgef = 0.0d0; pmef = 0.0d0; smef = 0.0d0
+            call simpson_m(sgef, this%en%edel, this%en%fermi, this%nv1, y, this%e1, 0, this%en%ene)
+            call simpson_m(pmef, this%en%edel, this%en%fermi, this%nv1, y, this%e1, 1, this%en%ene)
+            call simpson_m(smef, this%en%edel, this%en%fermi, this%nv1, y, this%e1, 2, this%en%ene)
+            this%symbolic_atom(plusbulk)%potential%gravity_center(i - soff, nsp) = (pmef/sgef) - this%symbolic_atom(plusbulk)%potential%vmad
+            this%symbolic_atom(plusbulk)%potential%ql(1, i - soff - 1, nsp) = sgef
+            this%symbolic_atom(plusbulk)%potential%ql(2, i - soff - 1, nsp) = 0.0d0
+            this%symbolic_atom(plusbulk)%potential%ql(3, i - soff - 1, nsp) = smef - 2.0d0*(pmef/sgef)*pmef + ((pmef/sgef)**2)*sgef
+         end do
+      end do
+
+      call this%calculate_pl()
+
+#ifdef USE_MPI
+      pot_size = this%symbolic_atom(start_atom)%potential%sizeof_potential_lite()
+      allocate (T_comm(pot_size, this%lattice%nrec))
+      T_comm = 0.0_rp
+      do na_glob = start_atom, end_atom
+         call this%symbolic_atom(this%lattice%nbulk + na_glob)%potential%flatten_potential_lite(T_comm(:, na_glob))
+      end do
+      call MPI_ALLREDUCE(MPI_IN_PLACE, T_comm, product(shape(T_comm)), MPI_DOUBLE_PRECISION, MPI_SUM, MPI_COMM_WORLD, ierr)
+      do na_glob = 1, this%lattice%nrec
+         call this%symbolic_atom(this%lattice%nbulk + na_glob)%potential%expand_potential_lite(T_comm(:, na_glob))
+      end do
+      deallocate (T_comm)
+#endif
    end subroutine gpu_calculate_moments
 
    !> occ(site, orbital) of the rank's sites on the 64-point Gauss-Legendre contour at ene(fermi_point), from the on-site chains the
@@ -380,10 +665,25 @@ contains
       call this%bands%calculate_projected_green()
    end subroutine gpu_calculate_projected_green
 
+   !> calculate_projected_dos (bands.f90:1158-1181): dx, dy, dz are the s + p + d sums of the x, y, z brackets of the image
    subroutine gpu_calculate_projected_dos(this)
       class(bands_gpu) :: this
-      call ensure_g0(this)
-      call this%bands%calculate_projected_dos()
+      integer :: na, na_glob, ie
+      if (.not. spectra_route(this)) then
+         call ensure_g0(this)
+         call this%bands%calculate_projected_dos()
+         return
+      end if
+      call ensure_spectra(this)
+      this%dz = 0.0d0; this%dy = 0.0d0; this%dx = 0.0d0
+      do na_glob = start_atom, end_atom
+         na = g2l_map(na_glob)
+         do ie = 1, this%en%channels_ldos + 10
+            this%dz(ie, na) = -(this%spec(10, ie, na_glob) + this%spec(11, ie, na_glob) + this%spec(12, ie, na_glob))/pi
+            this%dy(ie, na) = -(this%spec(7, ie, na_glob) + this%spec(8, ie, na_glob) + this%spec(9, ie, na_glob))/pi
+            this%dx(ie, na) = -(this%spec(4, ie, na_glob) + this%spec(5, ie, na_glob) + this%spec(6, ie, na_glob))/pi
+         end do
+      end do
    end subroutine gpu_calculate_projected_dos
 
    subroutine gpu_calculate_orbital_dos(this)

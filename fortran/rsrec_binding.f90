@@ -161,6 +161,28 @@ module rsrec_binding
          integer(c_int) :: rc
       end function
 
+      ! spec(k, ie, site) = Im Tr(O_k g0) on the chains resident on the device (no g0 is formed): ops complex (18,18,nop), spec real
+      ! (nop, nen, nsites_total), this rank's sites at site_offset+1 ..
+      function rsrec_block_spectra(handle, nop, ops, nen, ene, eta_re, eta_im, sym_term, site_offset, nsites_total, spec) &
+         bind(C, name='rsrec_block_spectra') result(rc)
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: handle
+         integer(c_int), value :: nop, nen, sym_term, site_offset, nsites_total
+         real(c_double), value :: eta_re, eta_im
+         type(c_ptr), value :: ops, ene, spec
+         integer(c_int) :: rc
+      end function
+
+      function rsrec_chebyshev_spectra(handle, nop, ops, nen, ene, energy_min, energy_max, site_offset, nsites_total, spec) &
+         bind(C, name='rsrec_chebyshev_spectra') result(rc)
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: handle
+         integer(c_int), value :: nop, nen, site_offset, nsites_total
+         real(c_double), value :: energy_min, energy_max
+         type(c_ptr), value :: ops, ene, spec
+         integer(c_int) :: rc
+      end function
+
       ! the Kubo-Bastin conductivity integrand integrand_at(l,l,:,v), factor applied, without gamma_nm (conductivity.f90:158-281)
       function rsrec_kubo_integrand(handle, nvec, cond_ll, mu_nm, nen, ene, energy_min, energy_max, integrand) &
          bind(C, name='rsrec_kubo_integrand') result(rc)

@@ -45,7 +45,7 @@ contains
    end subroutine rsrec_gpu_shutdown
 
    !> .true. if the environment variable `name` is set to a non-empty value: run-time switches of the drop-in types for hosts that
-   !> cannot set their members (the reference's unmodified calculation.f90 behind the shadow modules): RSREC_HOST_LDOS, RSREC_HOST_HAM,
+   !> cannot set their members (the reference's unmodified calculation.f90 behind the shadow modules): RSREC_HOST_LDOS, RSREC_HOST_MOMENTS, RSREC_HOST_HAM,
    !> RSREC_DEFER_G0
    function rsrec_env_flag(name) result(set)
       character(len=*), intent(in) :: name

@@ -189,6 +189,27 @@ int rsrec_chebyshev_green(rsrec_t *h, int nsites, int lld, int nen, const double
 int rsrec_chebyshev_ldos(rsrec_t *h, int nen, const double *ene, double energy_min, double energy_max, int site_offset, int nsites_total,
                          double *dtot, double *dosia, double *dosial);
 
+/* Operator spectra of the on-site Green function for the sites of the LAST rsrec_block_lanczos / rsrec_chebyshev call, from the chains
+ * that call left on the device:
+ *   spec(k, ie, s) = Im Tr(O_k g0(:,:,ie,s))          (no -1/pi applied)
+ * with g0 exactly what green%bgreen (block: zsqr -> get_terminf -> the continued fraction, eta / sym_term as in rsrec_block_green) or
+ * green%chebyshev_green (a, b and the Jackson kernel as in rsrec_chebyshev_green) gives for that site and energy.  No g0 is formed in
+ * memory: the block kernel contracts it where it lies after the last level, the Chebyshev route forms Tr(O_k mu_i) once per site and
+ * sums those over the moments.  Everything bands%calculate_magnetic_moments, calculate_orbital_moments, calculate_moments and
+ * calculate_orbital_quadrupoles read of g0 is such a functional (bands.f90:437-456, :985-993, :1123-1127, :1168-1180).
+ *   ops  : complex (18,18,nop), column-major, interleaved re/im, 1 <= nop <= 32 -- HOST or DEVICE memory (detected)
+ *   spec : real (nop, nen, nsites_total) out, HOST or DEVICE memory (detected): the zero-padded image, this rank's sites at
+ *          site_offset+1 .. site_offset+nsites, every other site zero.
+ * The sums over the 324 elements run in a fixed order: repeated calls, host and device `spec`, and calls that differ in site_offset give
+ * the same bits.  The resident chains stay as they are (b2_b stays B^2).
+ * RSREC_ERR_ARG unless the chains of the matching recursion are what the device holds; rsrec_chebyshev_spectra also refuses an lld whose
+ * nop (2 lld + 2) traces do not fit the LDS staging.  RSREC_ERR_EIG as rsrec_block_ldos.
+ * rsrec_get_timing: out[0] device ms of the call, out[1] ms of the Green kernel (block) / the energy sum (Chebyshev) alone. */
+int rsrec_block_spectra(rsrec_t *h, int nop, const double *ops, int nen, const double *ene, double eta_re, double eta_im,
+                        int sym_term, int site_offset, int nsites_total, double *spec);
+int rsrec_chebyshev_spectra(rsrec_t *h, int nop, const double *ops, int nen, const double *ene, double energy_min, double energy_max,
+                        int site_offset, int nsites_total, double *spec);
+
 /* Chebyshev (KPM, moment doubling) recursion.  Replaces chebyshev_recur (recursion.f90:3057-3130) with
  * cheb_0th_mom (:2145), cheb_1st_mom[_hoh] (:2169/:2245), chebyshev_recur_ll[_hoh] (:2495/:2605).
  *   a, b : scale and shift, a = (energy_max-energy_min)/(2-0.3), b = (energy_max+energy_min)/2 (:3078-3079)

@@ -37,6 +37,7 @@
 #include "kernels_uscheme.hpp"
 #include "kernels_green.hpp"
 #include "kernels_ldos.hpp"
+#include "kernels_spectra.hpp"
 #include "kernels_kubo.hpp"
 #include "kernels_cond.hpp"
 #include "kernels_exchange.hpp"
@@ -100,7 +101,7 @@ struct rsrec_handle {
     size_t s5_lds_limit = (size_t)-1;   // LDS a k_spmm5 workgroup may ask for on THIS handle's device ((size_t)-1: not asked yet; hipFuncSetAttribute is per device)
     int n_cu = 0;                       // compute units of the device (size of the persistent launches)
     bool s4_attr = false;               // k_spmm4's and k_terminator's LDS opt-ins, per handle for the same reason
-    size_t term_attr_lds = 0, cheb_ldos_attr_lds = 0;   // (k_chebyshev_ldos asks only beyond the 64 KB every kernel may have)
+    size_t term_attr_lds = 0, cheb_ldos_attr_lds = 0, cheb_spec_attr_lds = 0;   // (k_chebyshev_ldos / k_chebyshev_spectra ask only beyond the 64 KB every kernel may have)
     std::vector<double> host_ee, host_lsham, host_eeo, host_enim, host_hall, host_hallo;   // operator arrays as last set (Kubo operator tables; local-axis runs)
     std::vector<double> host_st, host_loc;   // ee / hall with l.s folded into the on-site block when !hoh (what d_hst / d_hloc hold)
     // raw blocks assembled on the device (rsrec_assemble_blocks): [part: 0 per-type, 1 per-atom][0: blocks, 1: blocks x obar]; asm_host = what the
@@ -123,6 +124,7 @@ struct rsrec_handle {
     DevBuf d_cond[4];                 // rsrec_kubo_integrand: basis tables, S / D planes, column-tile partials, staging (mu diagonals, integrand);
                                       // given back with d_kubo when the recursion plans a batch
     DevBuf d_bsqrt, d_term, d_gim, d_ldos;   // LDOS stage on resident coefficients: sqrt(B^2), terminators, Im g0_jj, output images
+    DevBuf d_ops, d_spec;                    // spectra stage: operators (+ their traces with the Chebyshev moments), Im Tr(O g0) of the rank's sites
     void* pin = nullptr;              // pinned host staging buffer: every per-call transfer goes through it (see xfer_*)
     size_t pin_bytes = 0;
     DevBuf d_frags, d_vec[6], d_partial, d_partial2, d_coefA, d_coefB, d_bmats, d_status, d_seed, d_seedcoef, d_mu, d_scal, d_zsqr;
@@ -2274,6 +2276,136 @@ extern "C" int rsrec_chebyshev_ldos(rsrec_t* h, int nen, const double* ene, doub
     }
     HIPCK(h, hipStreamSynchronize(h->stream));
     finish_timing(h, e0, e1, {{e0, k1}});             // hop: k_chebyshev_ldos alone; rest: the reduction
+    return RSREC_OK;
+}
+
+namespace {
+
+// what rsrec_block_spectra and rsrec_chebyshev_spectra share: argument rules, the operators on the device, the way out of the compact
+// block spec[site][nen][nop] of the rank's sites into the caller's zero-padded image
+int spectra_check(rsrec_t* h, const char* who, int kind, int nop, const double* ops, int nen, const double* ene, int site_offset, int nsites_total, const double* spec) {
+    if (nen < 1 || !ene || !ops || !spec || site_offset < 0) return fail(h, RSREC_ERR_ARG, "%s: bad argument", who);
+    if (nop < 1 || nop > SPECTRA_MAX_OPS) return fail(h, RSREC_ERR_ARG, "%s: nop = %d outside 1..%d", who, nop, SPECTRA_MAX_OPS);
+    if (h->res_kind != kind)
+        return fail(h, RSREC_ERR_ARG, kind == 1 ? "%s: no block-Lanczos coefficients resident (call rsrec_block_lanczos first)" : "%s: no Chebyshev moments resident (call rsrec_chebyshev first)", who);
+    if (site_offset + h->res_n > nsites_total) return fail(h, RSREC_ERR_ARG, "%s: sites %d..%d outside 1..%d", who, site_offset + 1, site_offset + h->res_n, nsites_total);
+    return RSREC_OK;
+}
+
+int spectra_deliver(rsrec_t* h, const double* d_spec, size_t per_site, int n, int site_offset, int nsites_total, double* spec) {
+    const size_t lo = per_site * site_offset, nfill = per_site * n, total = per_site * nsites_total;
+    if (is_device_ptr(spec)) {
+        k_spectra_image<<<(unsigned)std::min<size_t>((total + 255) / 256, 4096), 256, 0, h->stream>>>(d_spec, lo, nfill, total, spec);
+        HIPCK(h, hipGetLastError());
+        return RSREC_OK;
+    }
+    memset(spec, 0, lo * sizeof(double));
+    memset(spec + lo + nfill, 0, (total - lo - nfill) * sizeof(double));
+    return xfer_d2h(h, spec + lo, d_spec, nfill * sizeof(double));
+}
+
+}  // namespace
+
+// Im Tr(O_k g0) of green%bgreen for the sites of the last rsrec_block_lanczos call, from the coefficients it left on the device:
+// zsqr -> get_terminf -> the continued fraction of bgreen with the contraction as its epilogue.  No g0 leaves the kernel.
+extern "C" int rsrec_block_spectra(rsrec_t* h, int nop, const double* ops, int nen, const double* ene, double eta_re, double eta_im, int sym_term,
+                                   int site_offset, int nsites_total, double* spec) {
+    if (!h) return RSREC_ERR_ARG;
+    int rc = spectra_check(h, "rsrec_block_spectra", 1, nop, ops, nen, ene, site_offset, nsites_total, spec);
+    if (rc) return rc;
+    const int n = h->res_n, lld = h->res_lld;
+    HIPCK(h, hipSetDevice(h->device));
+    const size_t cel = (size_t)n * lld * BLK, obytes = (size_t)nop * BLK * sizeof(double2), per_site = (size_t)nop * nen;
+    release_kubo_buffers(h, true, true);
+    HIPCK(h, h->d_bsqrt.reserve(cel * sizeof(double2)));
+    HIPCK(h, h->d_term.reserve(2 * (size_t)n * BLK * sizeof(double) + 2 * (size_t)n * sizeof(double)));
+    HIPCK(h, h->d_spec.reserve((per_site * n + (size_t)nen) * sizeof(double)));
+    HIPCK(h, h->d_status.reserve(64));
+    HIPCK(h, hipMemsetAsync(h->d_status.p, 0, 64, h->stream));
+    double* d_spec = h->d_spec.as<double>();
+    double* d_ene = d_spec + per_site * n;
+    XFER(xfer_h2d(h, d_ene, ene, (size_t)nen * sizeof(double)));
+    const double2* d_ops = reinterpret_cast<const double2*>(ops);
+    if (!is_device_ptr(ops)) {
+        HIPCK(h, h->d_ops.reserve(obytes));
+        XFER(xfer_h2d(h, h->d_ops.p, ops, obytes));
+        d_ops = h->d_ops.as<double2>();
+    }
+    reset_timing(h);
+    hipEvent_t e0 = next_event(h);
+    const double2* dA = h->d_coefA.as<double2>();
+    double2* dBs = h->d_bsqrt.as<double2>();
+    // b2_b of the recursion stays B^2; the stage works on its own square root (as rsrec_block_ldos)
+    HIPCK(h, hipMemcpyAsync(dBs, h->d_coefB.p, cel * sizeof(double2), hipMemcpyDeviceToDevice, h->stream));
+    k_zsqr<<<n * lld, 256, 0, h->stream>>>(dBs, h->d_status.as<int>());
+    double* d_ai = h->d_term.as<double>();
+    double* d_bi = d_ai + (size_t)n * BLK;
+    rc = launch_terminator(h, n, lld, dA, dBs, d_ai, d_bi);
+    if (rc) return rc;
+    hipEvent_t k0 = next_event(h);
+    {
+        const dim3 grid((nen + GREEN_WAVES - 1) / GREEN_WAVES, n);
+        k_block_spectra<<<grid, GREEN_WAVES * 64, 0, h->stream>>>(lld, nen, d_ene, eta_re, eta_im, sym_term, d_ai, d_bi, dA, dBs, nop, d_ops, d_spec);
+    }
+    HIPCK(h, hipGetLastError());
+    hipEvent_t k1 = next_event(h);
+    XFER(spectra_deliver(h, d_spec, per_site, n, site_offset, nsites_total, spec));
+    hipEvent_t e1 = next_event(h);
+    int status = 0;
+    XFER(xfer_d2h(h, &status, h->d_status.p, 4));
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    finish_timing(h, e0, e1, {{k0, k1}});             // hop: the Green kernel with its epilogue; rest: zsqr + terminator + delivery
+    if (status & 1) return fail(h, RSREC_ERR_EIG, "Diagonalization error (18x18 Jacobi did not converge)");
+    return RSREC_OK;
+}
+
+// Im Tr(O_k g0) of green%chebyshev_green for the sites of the last rsrec_chebyshev call, from the moments it left on the device:
+// t(k, i) = Tr(O_k mu_i) once per site, then the energy sum of rsrec_chebyshev_ldos on t.
+extern "C" int rsrec_chebyshev_spectra(rsrec_t* h, int nop, const double* ops, int nen, const double* ene, double energy_min, double energy_max,
+                                       int site_offset, int nsites_total, double* spec) {
+    if (!h) return RSREC_ERR_ARG;
+    int rc = spectra_check(h, "rsrec_chebyshev_spectra", 2, nop, ops, nen, ene, site_offset, nsites_total, spec);
+    if (rc) return rc;
+    const int n = h->res_n, nm = 2 * h->res_lld + 2;
+    const size_t lds = (size_t)nm * nop * sizeof(double2);            // the operator traces of one site (24 KB at lld = 50, 15 operators)
+    if (lds > (size_t)150 * 1024) return fail(h, RSREC_ERR_ARG, "rsrec_chebyshev_spectra: lld = %d with %d operators too deep for the LDS staging", h->res_lld, nop);
+    HIPCK(h, hipSetDevice(h->device));
+    if (lds > (size_t)64 * 1024 && lds > h->cheb_spec_attr_lds) {
+        HIPCK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_chebyshev_spectra), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        h->cheb_spec_attr_lds = lds;
+    }
+    double a, b;
+    chebyshev_green_scaling(energy_min, energy_max, a, b);
+    const std::vector<double> kern = chebyshev_green_kernel(nm);
+    const size_t obytes = (size_t)nop * BLK * sizeof(double2), tbytes = (size_t)n * nm * nop * sizeof(double2), per_site = (size_t)nop * nen;
+    release_kubo_buffers(h, true, true);
+    HIPCK(h, h->d_spec.reserve((per_site * n + (size_t)nen + nm) * sizeof(double)));
+    HIPCK(h, h->d_ops.reserve(obytes + tbytes));
+    double* d_spec = h->d_spec.as<double>();
+    double* d_ene = d_spec + per_site * n;
+    double* d_kern = d_ene + nen;
+    XFER(xfer_h2d(h, d_ene, ene, (size_t)nen * sizeof(double)));
+    XFER(xfer_h2d(h, d_kern, kern.data(), (size_t)nm * sizeof(double)));
+    const double2* d_ops = reinterpret_cast<const double2*>(ops);
+    if (!is_device_ptr(ops)) {
+        XFER(xfer_h2d(h, h->d_ops.p, ops, obytes));
+        d_ops = h->d_ops.as<double2>();
+    }
+    double2* d_t = reinterpret_cast<double2*>(static_cast<char*>(h->d_ops.p) + obytes);
+    reset_timing(h);
+    hipEvent_t e0 = next_event(h);
+    k_chebyshev_optrace<<<dim3(nm, n), 64, 0, h->stream>>>(nm, nop, d_ops, h->d_mu.as<double2>(), d_t);
+    hipEvent_t k0 = next_event(h);
+    {
+        const dim3 grid((nen + CHEB_LDOS_TILE - 1) / CHEB_LDOS_TILE, n);
+        k_chebyshev_spectra<<<grid, CHEB_LDOS_TILE, lds, h->stream>>>(nm, nop, nen, d_ene, a, b, d_kern, d_t, d_spec);
+    }
+    HIPCK(h, hipGetLastError());
+    hipEvent_t k1 = next_event(h);
+    XFER(spectra_deliver(h, d_spec, per_site, n, site_offset, nsites_total, spec));
+    hipEvent_t e1 = next_event(h);
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    finish_timing(h, e0, e1, {{k0, k1}});             // hop: the energy sum alone; rest: the operator traces + delivery
     return RSREC_OK;
 }
 

@@ -184,6 +184,50 @@ class Green:
                                                int(site_offset), int(ntot), ptrs[0], ptrs[1], ptrs[2]))
         return dict(dtot=dtot, dosia=dosia, dosial=dosial)
 
+    def _spectra_args(self, ops, site_offset, nsites_total, out):
+        """Operators as complex (nop, 18, 18) C-ordered stacks of column-major matrices are what the library reads: ``ops[k]`` is O_k as
+        numpy indexes it (row, column), so each matrix is transposed into column-major storage here.  A device tensor is passed as it is
+        and must hold that layout already (``[k][column][row]``, complex128)."""
+        import ctypes as C
+        rec = self.recursion
+        start, end = rec._my_sites()[:2]
+        n = end - start + 1
+        ntot = n + site_offset if nsites_total is None else nsites_total
+        if hasattr(ops, "data_ptr"):
+            nop, keep, optr = int(ops.shape[0]), ops, C.c_void_p(int(ops.data_ptr()))
+        else:
+            o = np.asarray(ops, dtype=np.complex128)
+            if o.ndim == 2:
+                o = o[None]
+            if o.ndim != 3 or o.shape[1:] != (18, 18):
+                raise ValueError("ops must be (nop, 18, 18), got %r" % (o.shape,))
+            keep = np.ascontiguousarray(o.transpose(0, 2, 1))           # [k][column][row]
+            nop, optr = keep.shape[0], _ptr(keep)
+        if out is None:
+            spec = np.zeros((nop, len(self.ene), ntot), order="F")
+            sptr = _ptr(spec)
+        else:
+            spec, sptr = None, C.c_void_p(int(out))
+        return rec, nop, keep, optr, ntot, spec, sptr
+
+    def block_spectra(self, ops, eta=0.0 + 0.0j, site_offset=0, nsites_total=None, out=None):
+        """``spec(k, ie, s) = Im Tr(ops[k] g0(:,:,ie,s))`` for the sites of the last ``recur_b`` call, on the device from the coefficients
+        that call left there (zsqr -> get_terminf -> bgreen with the contraction as its epilogue: ``rsrec_block_spectra``).  No g0 is
+        formed in memory and no -1/pi is applied.  Returns the zero-padded image (nop, nen, nsites_total); ``out`` = raw DEVICE address of
+        such an image (Fortran order), written in place (None is returned)."""
+        rec, nop, keep, optr, ntot, spec, sptr = self._spectra_args(ops, site_offset, nsites_total, out)
+        rec._check(rec._L.rsrec_block_spectra(rec._h, nop, optr, len(self.ene), _ptr(self.ene), float(np.real(eta)), float(np.imag(eta)),
+                                              int(self.sym_term), int(site_offset), int(ntot), sptr))
+        return spec
+
+    def chebyshev_spectra(self, ops, site_offset=0, nsites_total=None, out=None):
+        """``block_spectra`` for the sites of the last ``chebyshev_recur`` call: g0 is green%chebyshev_green's, formed from the moments on
+        the device through the traces ``Tr(ops[k] mu_i)`` (``rsrec_chebyshev_spectra``)."""
+        rec, nop, keep, optr, ntot, spec, sptr = self._spectra_args(ops, site_offset, nsites_total, out)
+        rec._check(rec._L.rsrec_chebyshev_spectra(rec._h, nop, optr, len(self.ene), _ptr(self.ene), float(rec.en.energy_min), float(rec.en.energy_max),
+                                                  int(site_offset), int(ntot), sptr))
+        return spec
+
     def ldos(self):
         """Orbital-resolved local density of states, -Im g0_jj / pi (density_of_states.f90:248-260)."""
         d = np.arange(18)
