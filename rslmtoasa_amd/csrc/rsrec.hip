@@ -100,8 +100,10 @@ struct rsrec_handle {
     int s5_built = 0;
     size_t s5_lds_limit = (size_t)-1;   // LDS a k_spmm5 workgroup may ask for on THIS handle's device ((size_t)-1: not asked yet; hipFuncSetAttribute is per device)
     int n_cu = 0;                       // compute units of the device (size of the persistent launches)
-    bool s4_attr = false;               // k_spmm4's and k_terminator's LDS opt-ins, per handle for the same reason
-    size_t term_attr_lds = 0, cheb_ldos_attr_lds = 0, cheb_spec_attr_lds = 0;   // (k_chebyshev_ldos / k_chebyshev_spectra ask only beyond the 64 KB every kernel may have)
+    bool s4_attr = false;               // k_spmm4's LDS opt-in, per handle for the same reason
+    // dynamic LDS granted on this handle to k_terminator, k_chebyshev_ldos and k_chebyshev_spectra (lds_opt_in; the 64 KB every kernel may
+    // have need no asking, and k_terminator has always asked)
+    size_t term_lds = 0, cheb_ldos_lds = (size_t)64 * 1024, cheb_spec_lds = (size_t)64 * 1024;
     std::vector<double> host_ee, host_lsham, host_eeo, host_enim, host_hall, host_hallo;   // operator arrays as last set (Kubo operator tables; local-axis runs)
     std::vector<double> host_st, host_loc;   // ee / hall with l.s folded into the on-site block when !hoh (what d_hst / d_hloc hold)
     // raw blocks assembled on the device (rsrec_assemble_blocks): [part: 0 per-type, 1 per-atom][0: blocks, 1: blocks x obar]; asm_host = what the
@@ -118,12 +120,13 @@ struct rsrec_handle {
     Spmm5Operator kubo_op[2], kubo_hbulk;   // v_a / v_b tables of the last rsrec_kubo_moments call
     Spmm5Operator orb_plain;                // h as ham_vec_matmul applies it when hoh is set (rsrec_orbital_moments, rsrec_apply_operator vel = 2)
     // work
-    DevBuf d_green_in, d_green_out;   // rsrec_block_green
+    DevBuf d_green_in, d_green_out;   // inputs and outputs of the calls on caller arrays: the Green stages (green_pipeline), rsrec_terminator,
+                                      // rsrec_scalar_density, and the pair calls (PairCall)
     DevBuf d_kubo[5];                 // rsrec_kubo_moments: work vectors, left / right matrices, slice partials, moments -- kept between calls (tens of GB:
                                       // their hipMalloc / hipFree cost 0.1-1.3 s per call on some boxes of the pool); given back when the recursion plans a batch
     DevBuf d_cond[4];                 // rsrec_kubo_integrand: basis tables, S / D planes, column-tile partials, staging (mu diagonals, integrand);
                                       // given back with d_kubo when the recursion plans a batch
-    DevBuf d_bsqrt, d_term, d_gim, d_ldos;   // LDOS stage on resident coefficients: sqrt(B^2), terminators, Im g0_jj, output images
+    DevBuf d_bsqrt, d_term, d_gim, d_ldos;   // stages on resident coefficients: sqrt(B^2), terminators; LDOS stage: Im g0_jj, output images
     DevBuf d_ops, d_spec;                    // spectra stage: operators (+ their traces with the Chebyshev moments), Im Tr(O g0) of the rank's sites
     void* pin = nullptr;              // pinned host staging buffer: every per-call transfer goes through it (see xfer_*)
     size_t pin_bytes = 0;
@@ -181,9 +184,9 @@ struct rsrec_handle {
     const RegionEntry* cur_entry = nullptr;
     int cur_nrows = 0;
     std::vector<unsigned> spatial_key;   // per atom: position along a space-filling curve (locality hint for the saturated order)
-    // coefficients left on the device by the last recursion call: 0 = none, 1 = block Lanczos (d_coefA = a_b, d_coefB = b2_b or its root),
-    // 2 = Chebyshev (d_mu = mu_n of all chains)
-    int res_kind = 0, res_n = 0, res_lld = 0, res_sqrt = 0;
+    // coefficients left on the device by the last recursion call: 0 = none, 1 = block Lanczos (d_coefA = a_b, d_coefB = b2_b, never its
+    // root), 2 = Chebyshev (d_mu = mu_n of all chains)
+    int res_kind = 0, res_n = 0, res_lld = 0;
     bool res_seeded = false;            // the resident chains come from a seeded (pair) call, not from one chain per site
     // library-level communicator (RCCL, bound with dlopen at rsrec_comm_init): the one exchange of the path without MPI or torch
     void* comm = nullptr;
@@ -1055,6 +1058,15 @@ void finish_timing(rsrec_t* h, hipEvent_t ev_begin, hipEvent_t ev_end, const std
     h->t_rest_ms = h->t_total_ms - h->t_hop_ms;
 }
 
+// end of a call whose kernels report through the status word (cleared when the call began): the word, the stream, the eigen-solver's failure
+int finish_status(rsrec_t* h) {
+    int status = 0;
+    XFER(xfer_d2h(h, &status, h->d_status.p, 4));
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    if (status & 1) return fail(h, RSREC_ERR_EIG, "Diagonalization error (18x18 Jacobi did not converge)");
+    return RSREC_OK;
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // Workgroups per chain of the matrix-core post-hop kernels (Gram, orthogonalisation, Chebyshev step): they hold their 36x36
 // coefficient tables in registers and run one wave per SIMD, so long-lived waves win -- about two workgroups per CU over
@@ -1564,12 +1576,10 @@ int run_block_lanczos(rsrec_t* h, int nchains, int nseed, const int32_t* seed_at
         HIPCK(h, hipStreamSynchronize(h->stream));
     }
     hipEvent_t ev_end = next_event(h);
-    HIPCK(h, hipStreamSynchronize(h->stream));
+    rc = finish_status(h);
     finish_timing(h, ev_begin, ev_end, hop_ev);
-    int status = 0;
-    XFER(xfer_d2h(h, &status, h->d_status.p, 4));
-    if (status & 1) return fail(h, RSREC_ERR_EIG, "Diagonalization error (18x18 Jacobi did not converge)");
-    h->res_kind = 1; h->res_n = nchains; h->res_lld = lld; h->res_sqrt = 0; h->res_seeded = seed_coef != nullptr;
+    if (rc) return rc;
+    h->res_kind = 1; h->res_n = nchains; h->res_lld = lld; h->res_seeded = seed_coef != nullptr;
     return RSREC_OK;
 }
 
@@ -1915,11 +1925,7 @@ extern "C" int rsrec_zsqr(rsrec_t* h, int nmat, double* b2_b) {
     k_zsqr<<<nmat, 256, 0, h->stream>>>(h->d_zsqr.as<double2>(), h->d_status.as<int>());
     HIPCK(h, hipGetLastError());
     XFER(xfer_d2h(h, b2_b, h->d_zsqr.p, bytes));
-    int status = 0;
-    XFER(xfer_d2h(h, &status, h->d_status.p, 4));
-    HIPCK(h, hipStreamSynchronize(h->stream));
-    if (status & 1) return fail(h, RSREC_ERR_EIG, "Diagonalization error (18x18 Jacobi did not converge)");
-    return RSREC_OK;
+    return finish_status(h);
 }
 
 namespace {
@@ -2008,6 +2014,14 @@ extern "C" int rsrec_block_green(rsrec_t* h, int nsites, int lld, int nen, const
 
 namespace {
 
+// Dynamic LDS for `kernel` beyond what `granted` records for it on this handle (the opt-in is per device: see s5_lds_limit)
+int lds_opt_in(rsrec_t* h, const void* kernel, size_t bytes, size_t& granted) {
+    if (bytes <= granted) return RSREC_OK;
+    HIPCK(h, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    granted = bytes;
+    return RSREC_OK;
+}
+
 // get_terminf for n sites on the device: a_inf, b_inf [site][324], optional means
 int launch_terminator(rsrec_t* h, int n, int lld, const double2* d_ab, const double2* d_bs, double* d_ainf, double* d_binf) {
     if (lld < 2) return fail(h, RSREC_ERR_ARG, "terminator needs lld >= 2");
@@ -2016,13 +2030,23 @@ int launch_terminator(rsrec_t* h, int n, int lld, const double2* d_ab, const dou
     while (T > 8 && (size_t)2 * lld * T * sizeof(double) > (size_t)128 * 1024) T >>= 1;
     const size_t lds = (size_t)2 * lld * T * sizeof(double);
     if (lds > (size_t)150 * 1024) return fail(h, RSREC_ERR_ARG, "terminator: lld = %d too deep for the LDS staging", lld);
-    if (lds > h->term_attr_lds) {
-        HIPCK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_terminator), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        h->term_attr_lds = lds;
-    }
+    XFER(lds_opt_in(h, reinterpret_cast<const void*>(k_terminator), lds, h->term_lds));
     k_terminator<<<dim3((BLK + T - 1) / T, n), T, lds, h->stream>>>(lld, d_ab, d_bs, d_ainf, d_binf);
     HIPCK(h, hipGetLastError());
     return RSREC_OK;
+}
+
+// The block prologue on the resident chains c0 .. c0 + nc - 1, for every stage that reads them (SiteStage, PairCall).  b2_b of the recursion
+// stays B^2 -- the caller may still fetch it, and the next stage starts from it again -- so a stage works on a square root of its own: in
+// d_bsqrt, which the call's setup has reserved for nc chains, as it has cleared the status word.  Then get_terminf of those chains into
+// d_ainf / d_binf, unless the caller gave terminators (d_ainf == nullptr).
+int resident_block_prologue(rsrec_t* h, size_t c0, size_t nc, int lld, double* d_ainf, double* d_binf) {
+    const size_t cel = (size_t)lld * BLK;
+    double2* dBs = h->d_bsqrt.as<double2>();
+    HIPCK(h, hipMemcpyAsync(dBs, h->d_coefB.as<double2>() + c0 * cel, nc * cel * sizeof(double2), hipMemcpyDeviceToDevice, h->stream));
+    k_zsqr<<<(unsigned)(nc * lld), 256, 0, h->stream>>>(dBs, h->d_status.as<int>());
+    if (!d_ainf) return RSREC_OK;
+    return launch_terminator(h, (int)nc, lld, h->d_coefA.as<double2>() + c0 * cel, dBs, d_ainf, d_binf);
 }
 
 }  // namespace
@@ -2104,69 +2128,6 @@ extern "C" int rsrec_scalar_density(rsrec_t* h, int nsites, int nmdir, int llmax
     return RSREC_OK;
 }
 
-// The whole LDOS stage for the sites of the last rsrec_block_lanczos call, from the coefficients it left on the device:
-// zsqr (recursion.f90:1980) -> get_terminf (:2092) -> bgreen (green.f90:1191) -> the reduction of calculate_fermi (bands.f90:258-268).
-// Only the densities of states leave the GPU (18 doubles per site and energy instead of 648).
-extern "C" int rsrec_block_ldos(rsrec_t* h, int nen, const double* ene, double eta_re, double eta_im, int sym_term, int site_offset, int nsites_total,
-                                double* dtot, double* dosia, double* dosial, double* a_inf_out, double* b_inf_out) {
-    if (!h) return RSREC_ERR_ARG;
-    if (nen < 1 || !ene || !dtot || !dosia || !dosial || site_offset < 0) return fail(h, RSREC_ERR_ARG, "rsrec_block_ldos: bad argument");
-    if (h->res_kind != 1) return fail(h, RSREC_ERR_ARG, "rsrec_block_ldos: no block-Lanczos coefficients resident (call rsrec_block_lanczos first)");
-    const int n = h->res_n, lld = h->res_lld;
-    if (site_offset + n > nsites_total) return fail(h, RSREC_ERR_ARG, "rsrec_block_ldos: sites %d..%d outside 1..%d", site_offset + 1, site_offset + n, nsites_total);
-    HIPCK(h, hipSetDevice(h->device));
-    h->n_ldos_calls++;
-    const size_t cel = (size_t)n * lld * BLK;
-    release_kubo_buffers(h, true, true);
-    HIPCK(h, h->d_bsqrt.reserve(cel * sizeof(double2)));
-    HIPCK(h, h->d_term.reserve(2 * (size_t)n * BLK * sizeof(double) + 2 * (size_t)n * sizeof(double)));
-    HIPCK(h, h->d_gim.reserve((size_t)n * nen * NB * sizeof(double) + (size_t)nen * sizeof(double)));
-    const size_t img = (size_t)nen * ((size_t)nsites_total * (NB + 1) + 1);          // dosial + dosia + dtot
-    const bool dev = is_device_ptr(dtot) && is_device_ptr(dosia) && is_device_ptr(dosial);
-    if (!dev) HIPCK(h, h->d_ldos.reserve(img * sizeof(double)));
-    HIPCK(h, h->d_status.reserve(64));
-    HIPCK(h, hipMemsetAsync(h->d_status.p, 0, 64, h->stream));
-    double* d_gim = h->d_gim.as<double>();
-    double* d_ene = d_gim + (size_t)n * nen * NB;
-    XFER(xfer_h2d(h, d_ene, ene, (size_t)nen * sizeof(double)));
-    reset_timing(h);
-    hipEvent_t e0 = next_event(h);
-    const double2* dA = h->d_coefA.as<double2>();
-    double2* dBs = h->d_bsqrt.as<double2>();
-    // b2_b of the recursion stays B^2 (the caller may still fetch it); the stage works on its own square root
-    HIPCK(h, hipMemcpyAsync(dBs, h->d_coefB.p, cel * sizeof(double2), hipMemcpyDeviceToDevice, h->stream));
-    k_zsqr<<<n * lld, 256, 0, h->stream>>>(dBs, h->d_status.as<int>());
-    double* d_ai = h->d_term.as<double>();
-    double* d_bi = d_ai + (size_t)n * BLK;
-    int rc = launch_terminator(h, n, lld, dA, dBs, d_ai, d_bi);
-    if (rc) return rc;
-    hipEvent_t k0 = next_event(h);
-    {
-        const dim3 grid((nen + GREEN_WAVES - 1) / GREEN_WAVES, n);
-        k_block_green<true><<<grid, GREEN_WAVES * 64, 0, h->stream>>>(lld, nen, d_ene, eta_re, eta_im, sym_term, d_ai, d_bi, dA, dBs, nullptr, d_gim);
-    }
-    hipEvent_t k1 = next_event(h);
-    double* o_dosial = dev ? dosial : h->d_ldos.as<double>();
-    double* o_dosia = dev ? dosia : o_dosial + (size_t)nsites_total * NB * nen;
-    double* o_dtot = dev ? dtot : o_dosia + (size_t)nsites_total * nen;
-    k_ldos_finish<<<(nen + 63) / 64, 64, 0, h->stream>>>(d_gim, n, nen, site_offset, nsites_total, o_dosial, o_dosia, o_dtot);
-    HIPCK(h, hipGetLastError());
-    hipEvent_t e1 = next_event(h);
-    if (!dev) {
-        XFER(xfer_d2h(h, dosial, o_dosial, (size_t)nsites_total * NB * nen * sizeof(double)));
-        XFER(xfer_d2h(h, dosia, o_dosia, (size_t)nsites_total * nen * sizeof(double)));
-        XFER(xfer_d2h(h, dtot, o_dtot, (size_t)nen * sizeof(double)));
-    }
-    if (a_inf_out) XFER(xfer_d2h(h, a_inf_out, d_ai, (size_t)n * BLK * sizeof(double)));
-    if (b_inf_out) XFER(xfer_d2h(h, b_inf_out, d_bi, (size_t)n * BLK * sizeof(double)));
-    int status = 0;
-    XFER(xfer_d2h(h, &status, h->d_status.p, 4));
-    HIPCK(h, hipStreamSynchronize(h->stream));
-    finish_timing(h, e0, e1, {{k0, k1}});             // hop: the Green kernel alone; rest: zsqr + terminator + reduction
-    if (status & 1) return fail(h, RSREC_ERR_EIG, "Diagonalization error (18x18 Jacobi did not converge)");
-    return RSREC_OK;
-}
-
 namespace {
 
 // The Jackson kernel of green%chebyshev_green (math.f90:1641-1655; real(ll) is a default-REAL conversion, exact for these small
@@ -2225,70 +2186,99 @@ extern "C" int rsrec_chebyshev_green(rsrec_t* h, int nsites, int lld, int nen, c
     return RSREC_OK;
 }
 
-// The LDOS stage for the sites of the last rsrec_chebyshev call, from the moments it left on the device: the diagonal of
-// green%chebyshev_green (green.f90:1030-1108) -> the reduction of calculate_fermi (bands.f90:258-268).  Neither the moments nor a g0
-// cross PCIe: the energy mesh and the nm kernel weights go up, 18 doubles per site and energy come back.
-extern "C" int rsrec_chebyshev_ldos(rsrec_t* h, int nen, const double* ene, double energy_min, double energy_max, int site_offset, int nsites_total,
-                                    double* dtot, double* dosia, double* dosial) {
-    if (!h) return RSREC_ERR_ARG;
-    if (nen < 1 || !ene || !dtot || !dosia || !dosial || site_offset < 0) return fail(h, RSREC_ERR_ARG, "rsrec_chebyshev_ldos: bad argument");
-    if (h->res_kind != 2) return fail(h, RSREC_ERR_ARG, "rsrec_chebyshev_ldos: no Chebyshev moments resident (call rsrec_chebyshev first)");
-    const int n = h->res_n, nm = 2 * h->res_lld + 2;
-    if (site_offset + n > nsites_total) return fail(h, RSREC_ERR_ARG, "rsrec_chebyshev_ldos: sites %d..%d outside 1..%d", site_offset + 1, site_offset + n, nsites_total);
-    HIPCK(h, hipSetDevice(h->device));
-    const size_t lds = (size_t)nm * NB * sizeof(double2);            // the diagonal moments of one site (29 KB at lld = 50)
-    if (lds > (size_t)150 * 1024) return fail(h, RSREC_ERR_ARG, "rsrec_chebyshev_ldos: lld = %d too deep for the LDS staging", h->res_lld);
-    if (lds > (size_t)64 * 1024 && lds > h->cheb_ldos_attr_lds) {
-        HIPCK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_chebyshev_ldos), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        h->cheb_ldos_attr_lds = lds;
-    }
-    h->n_ldos_calls++;
-    double a, b;
-    chebyshev_green_scaling(energy_min, energy_max, a, b);
-    const std::vector<double> kern = chebyshev_green_kernel(nm);
-    release_kubo_buffers(h, true, true);
-    HIPCK(h, h->d_gim.reserve(((size_t)n * nen * NB + (size_t)nen + nm) * sizeof(double)));
-    const size_t img = (size_t)nen * ((size_t)nsites_total * (NB + 1) + 1);          // dosial + dosia + dtot
-    const bool dev = is_device_ptr(dtot) && is_device_ptr(dosia) && is_device_ptr(dosial);
-    if (!dev) HIPCK(h, h->d_ldos.reserve(img * sizeof(double)));
-    double* d_gim = h->d_gim.as<double>();
-    double* d_ene = d_gim + (size_t)n * nen * NB;
-    double* d_kern = d_ene + nen;
-    XFER(xfer_h2d(h, d_ene, ene, (size_t)nen * sizeof(double)));
-    XFER(xfer_h2d(h, d_kern, kern.data(), (size_t)nm * sizeof(double)));
-    reset_timing(h);
-    hipEvent_t e0 = next_event(h);
-    {
-        const dim3 grid((nen + CHEB_LDOS_TILE - 1) / CHEB_LDOS_TILE, n);
-        k_chebyshev_ldos<<<grid, CHEB_LDOS_TILE, lds, h->stream>>>(nm, nen, d_ene, a, b, d_kern, h->d_mu.as<double2>(), d_gim);
-    }
-    hipEvent_t k1 = next_event(h);
-    double* o_dosial = dev ? dosial : h->d_ldos.as<double>();
-    double* o_dosia = dev ? dosia : o_dosial + (size_t)nsites_total * NB * nen;
-    double* o_dtot = dev ? dtot : o_dosia + (size_t)nsites_total * nen;
-    k_ldos_finish<<<(nen + 63) / 64, 64, 0, h->stream>>>(d_gim, n, nen, site_offset, nsites_total, o_dosial, o_dosia, o_dtot);
-    HIPCK(h, hipGetLastError());
-    hipEvent_t e1 = next_event(h);
-    if (!dev) {
-        XFER(xfer_d2h(h, dosial, o_dosial, (size_t)nsites_total * NB * nen * sizeof(double)));
-        XFER(xfer_d2h(h, dosia, o_dosia, (size_t)nsites_total * nen * sizeof(double)));
-        XFER(xfer_d2h(h, dtot, o_dtot, (size_t)nen * sizeof(double)));
-    }
-    HIPCK(h, hipStreamSynchronize(h->stream));
-    finish_timing(h, e0, e1, {{e0, k1}});             // hop: k_chebyshev_ldos alone; rest: the reduction
-    return RSREC_OK;
-}
-
 namespace {
 
-// what rsrec_block_spectra and rsrec_chebyshev_spectra share: argument rules, the operators on the device, the way out of the compact
-// block spec[site][nen][nop] of the rank's sites into the caller's zero-padded image
-int spectra_check(rsrec_t* h, const char* who, int kind, int nop, const double* ops, int nen, const double* ene, int site_offset, int nsites_total, const double* spec) {
-    if (nen < 1 || !ene || !ops || !spec || site_offset < 0) return fail(h, RSREC_ERR_ARG, "%s: bad argument", who);
-    if (nop < 1 || nop > SPECTRA_MAX_OPS) return fail(h, RSREC_ERR_ARG, "%s: nop = %d outside 1..%d", who, nop, SPECTRA_MAX_OPS);
+// Call setup shared by the stages that run on the on-site chains the last recursion left on the device (rsrec_block_ldos,
+// rsrec_chebyshev_ldos, rsrec_block_spectra, rsrec_chebyshev_spectra), as PairCall is for the calls on pairs:
+//   site_stage_begin  the residency and site-range rules, the device, the stage's scratch with ene (| the Chebyshev kernel weights)
+//                     behind it, the buffers and the cleared status word of the block prologue or the Chebyshev scaling;
+//   (the stage's own uploads and LDS opt-in, outside the timed span)
+//   site_stage_open   the timed span opens; the block prologue;
+//   (the stage's kernels and delivery)
+//   site_stage_end    the status word, the stream, the timing.
+struct SiteStage {
+    int kind, n, lld, nm;                          // 1 = block Lanczos, 2 = Chebyshev; sites; depth; moments per site
+    const double2 *sa, *sb;                        // a_b and the stage's sqrt(b2_b), or mu_n and nullptr
+    double *ta, *tb;                               // terminators (kind 1)
+    double ca, cb;                                 // chebyshev_green's scaling (kind 2)
+    double *d_out, *d_ene, *d_kern;                // the scratch (per_site doubles per site), the energies, the Chebyshev kernel weights (kind 2)
+    hipEvent_t e0, k0;                             // the opening event, the event behind the prologue (e0 itself where there is none)
+};
+
+int site_stage_begin(rsrec_t* h, SiteStage& S, const char* who, int kind, int nen, const double* ene, double energy_min, double energy_max,
+                     int site_offset, int nsites_total, DevBuf& scratch, size_t per_site) {
+    if (nen < 1 || !ene || site_offset < 0) return fail(h, RSREC_ERR_ARG, "%s: bad argument", who);
     if (h->res_kind != kind)
         return fail(h, RSREC_ERR_ARG, kind == 1 ? "%s: no block-Lanczos coefficients resident (call rsrec_block_lanczos first)" : "%s: no Chebyshev moments resident (call rsrec_chebyshev first)", who);
     if (site_offset + h->res_n > nsites_total) return fail(h, RSREC_ERR_ARG, "%s: sites %d..%d outside 1..%d", who, site_offset + 1, site_offset + h->res_n, nsites_total);
+    HIPCK(h, hipSetDevice(h->device));
+    S.kind = kind; S.n = h->res_n; S.lld = h->res_lld; S.nm = 2 * h->res_lld + 2;
+    const size_t n = (size_t)S.n;
+    release_kubo_buffers(h, true, true);
+    HIPCK(h, scratch.reserve((per_site * n + (size_t)nen + (kind == 2 ? S.nm : 0)) * sizeof(double)));
+    S.d_out = scratch.as<double>();
+    S.d_ene = S.d_out + per_site * n;
+    S.d_kern = S.d_ene + nen;
+    if (kind == 1) {
+        HIPCK(h, h->d_bsqrt.reserve(n * S.lld * BLK * sizeof(double2)));
+        HIPCK(h, h->d_term.reserve(2 * n * BLK * sizeof(double) + 2 * n * sizeof(double)));
+        HIPCK(h, h->d_status.reserve(64));
+        HIPCK(h, hipMemsetAsync(h->d_status.p, 0, 64, h->stream));
+        S.sa = h->d_coefA.as<double2>(); S.sb = h->d_bsqrt.as<double2>();
+        S.ta = h->d_term.as<double>(); S.tb = S.ta + n * BLK;
+    } else {
+        chebyshev_green_scaling(energy_min, energy_max, S.ca, S.cb);
+        const std::vector<double> kern = chebyshev_green_kernel(S.nm);
+        XFER(xfer_h2d(h, S.d_kern, kern.data(), (size_t)S.nm * sizeof(double)));
+        S.sa = h->d_mu.as<double2>(); S.sb = nullptr;
+        S.ta = S.tb = nullptr;
+    }
+    return xfer_h2d(h, S.d_ene, ene, (size_t)nen * sizeof(double));
+}
+
+int site_stage_open(rsrec_t* h, SiteStage& S) {
+    reset_timing(h);
+    S.e0 = S.k0 = next_event(h);
+    if (S.kind == 2) return RSREC_OK;
+    XFER(resident_block_prologue(h, 0, (size_t)S.n, S.lld, S.ta, S.tb));
+    S.k0 = next_event(h);
+    return RSREC_OK;
+}
+
+// e1: where the stage's timed span ends; k0, k1: what it reports as hop
+int site_stage_end(rsrec_t* h, const SiteStage& S, hipEvent_t k0, hipEvent_t k1, hipEvent_t e1) {
+    int rc = RSREC_OK;
+    if (S.kind == 1) rc = finish_status(h);
+    else HIPCK(h, hipStreamSynchronize(h->stream));
+    finish_timing(h, S.e0, e1, {{k0, k1}});
+    return rc;
+}
+
+// The way out of Im g0_jj [site][nen][18] of the rank's sites: the zero-padded images dosial | dosia | dtot of calculate_fermi's reduction,
+// formed in the caller's arrays if those are device memory, else in d_ldos and downloaded.  reduced: the event behind the reduction (the
+// timed span of an LDOS stage ends there, before the downloads).
+int ldos_deliver(rsrec_t* h, const double* d_gim, int n, int nen, int site_offset, int nsites_total, double* dtot, double* dosia, double* dosial,
+                 hipEvent_t& reduced) {
+    const size_t nial = (size_t)nsites_total * NB * nen, nia = (size_t)nsites_total * nen;
+    const bool dev = is_device_ptr(dtot) && is_device_ptr(dosia) && is_device_ptr(dosial);
+    if (!dev) HIPCK(h, h->d_ldos.reserve((nial + nia + (size_t)nen) * sizeof(double)));
+    double* o_dosial = dev ? dosial : h->d_ldos.as<double>();
+    double* o_dosia = dev ? dosia : o_dosial + nial;
+    double* o_dtot = dev ? dtot : o_dosia + nia;
+    k_ldos_finish<<<(nen + 63) / 64, 64, 0, h->stream>>>(d_gim, n, nen, site_offset, nsites_total, o_dosial, o_dosia, o_dtot);
+    HIPCK(h, hipGetLastError());
+    reduced = next_event(h);
+    if (dev) return RSREC_OK;
+    XFER(xfer_d2h(h, dosial, o_dosial, nial * sizeof(double)));
+    XFER(xfer_d2h(h, dosia, o_dosia, nia * sizeof(double)));
+    return xfer_d2h(h, dtot, o_dtot, (size_t)nen * sizeof(double));
+}
+
+// what rsrec_block_spectra and rsrec_chebyshev_spectra share beside the stage setup: the rules for the operators, the way out of the compact
+// block spec[site][nen][nop] of the rank's sites into the caller's zero-padded image
+int spectra_check(rsrec_t* h, const char* who, int nop, const double* ops, const double* spec) {
+    if (!ops || !spec) return fail(h, RSREC_ERR_ARG, "%s: bad argument", who);
+    if (nop < 1 || nop > SPECTRA_MAX_OPS) return fail(h, RSREC_ERR_ARG, "%s: nop = %d outside 1..%d", who, nop, SPECTRA_MAX_OPS);
     return RSREC_OK;
 }
 
@@ -2306,57 +2296,75 @@ int spectra_deliver(rsrec_t* h, const double* d_spec, size_t per_site, int n, in
 
 }  // namespace
 
+// The whole LDOS stage for the sites of the last rsrec_block_lanczos call, from the coefficients it left on the device:
+// zsqr (recursion.f90:1980) -> get_terminf (:2092) -> bgreen (green.f90:1191) -> the reduction of calculate_fermi (bands.f90:258-268).
+// Only the densities of states leave the GPU (18 doubles per site and energy instead of 648).
+extern "C" int rsrec_block_ldos(rsrec_t* h, int nen, const double* ene, double eta_re, double eta_im, int sym_term, int site_offset, int nsites_total,
+                                double* dtot, double* dosia, double* dosial, double* a_inf_out, double* b_inf_out) {
+    if (!h) return RSREC_ERR_ARG;
+    if (!dtot || !dosia || !dosial) return fail(h, RSREC_ERR_ARG, "rsrec_block_ldos: bad argument");
+    SiteStage S;
+    XFER(site_stage_begin(h, S, "rsrec_block_ldos", 1, nen, ene, 0.0, 0.0, site_offset, nsites_total, h->d_gim, (size_t)nen * NB));
+    h->n_ldos_calls++;
+    XFER(site_stage_open(h, S));
+    {
+        const dim3 grid((nen + GREEN_WAVES - 1) / GREEN_WAVES, S.n);
+        k_block_green<true><<<grid, GREEN_WAVES * 64, 0, h->stream>>>(S.lld, nen, S.d_ene, eta_re, eta_im, sym_term, S.ta, S.tb, S.sa, S.sb, nullptr, S.d_out);
+    }
+    hipEvent_t k1 = next_event(h), e1 = nullptr;
+    XFER(ldos_deliver(h, S.d_out, S.n, nen, site_offset, nsites_total, dtot, dosia, dosial, e1));
+    if (a_inf_out) XFER(xfer_d2h(h, a_inf_out, S.ta, (size_t)S.n * BLK * sizeof(double)));
+    if (b_inf_out) XFER(xfer_d2h(h, b_inf_out, S.tb, (size_t)S.n * BLK * sizeof(double)));
+    return site_stage_end(h, S, S.k0, k1, e1);        // hop: the Green kernel alone; rest: zsqr + terminator + reduction
+}
+
+// The LDOS stage for the sites of the last rsrec_chebyshev call, from the moments it left on the device: the diagonal of
+// green%chebyshev_green (green.f90:1030-1108) -> the reduction of calculate_fermi (bands.f90:258-268).  Neither the moments nor a g0
+// cross PCIe: the energy mesh and the nm kernel weights go up, 18 doubles per site and energy come back.
+extern "C" int rsrec_chebyshev_ldos(rsrec_t* h, int nen, const double* ene, double energy_min, double energy_max, int site_offset, int nsites_total,
+                                    double* dtot, double* dosia, double* dosial) {
+    if (!h) return RSREC_ERR_ARG;
+    if (!dtot || !dosia || !dosial) return fail(h, RSREC_ERR_ARG, "rsrec_chebyshev_ldos: bad argument");
+    SiteStage S;
+    XFER(site_stage_begin(h, S, "rsrec_chebyshev_ldos", 2, nen, ene, energy_min, energy_max, site_offset, nsites_total, h->d_gim, (size_t)nen * NB));
+    const size_t lds = (size_t)S.nm * NB * sizeof(double2);          // the diagonal moments of one site (29 KB at lld = 50)
+    if (lds > (size_t)150 * 1024) return fail(h, RSREC_ERR_ARG, "rsrec_chebyshev_ldos: lld = %d too deep for the LDS staging", S.lld);
+    XFER(lds_opt_in(h, reinterpret_cast<const void*>(k_chebyshev_ldos), lds, h->cheb_ldos_lds));
+    h->n_ldos_calls++;
+    XFER(site_stage_open(h, S));
+    {
+        const dim3 grid((nen + CHEB_LDOS_TILE - 1) / CHEB_LDOS_TILE, S.n);
+        k_chebyshev_ldos<<<grid, CHEB_LDOS_TILE, lds, h->stream>>>(S.nm, nen, S.d_ene, S.ca, S.cb, S.d_kern, S.sa, S.d_out);
+    }
+    hipEvent_t k1 = next_event(h), e1 = nullptr;
+    XFER(ldos_deliver(h, S.d_out, S.n, nen, site_offset, nsites_total, dtot, dosia, dosial, e1));
+    return site_stage_end(h, S, S.e0, k1, e1);        // hop: from the opening event through k_chebyshev_ldos; rest: the reduction
+}
+
 // Im Tr(O_k g0) of green%bgreen for the sites of the last rsrec_block_lanczos call, from the coefficients it left on the device:
 // zsqr -> get_terminf -> the continued fraction of bgreen with the contraction as its epilogue.  No g0 leaves the kernel.
 extern "C" int rsrec_block_spectra(rsrec_t* h, int nop, const double* ops, int nen, const double* ene, double eta_re, double eta_im, int sym_term,
                                    int site_offset, int nsites_total, double* spec) {
     if (!h) return RSREC_ERR_ARG;
-    int rc = spectra_check(h, "rsrec_block_spectra", 1, nop, ops, nen, ene, site_offset, nsites_total, spec);
-    if (rc) return rc;
-    const int n = h->res_n, lld = h->res_lld;
-    HIPCK(h, hipSetDevice(h->device));
-    const size_t cel = (size_t)n * lld * BLK, obytes = (size_t)nop * BLK * sizeof(double2), per_site = (size_t)nop * nen;
-    release_kubo_buffers(h, true, true);
-    HIPCK(h, h->d_bsqrt.reserve(cel * sizeof(double2)));
-    HIPCK(h, h->d_term.reserve(2 * (size_t)n * BLK * sizeof(double) + 2 * (size_t)n * sizeof(double)));
-    HIPCK(h, h->d_spec.reserve((per_site * n + (size_t)nen) * sizeof(double)));
-    HIPCK(h, h->d_status.reserve(64));
-    HIPCK(h, hipMemsetAsync(h->d_status.p, 0, 64, h->stream));
-    double* d_spec = h->d_spec.as<double>();
-    double* d_ene = d_spec + per_site * n;
-    XFER(xfer_h2d(h, d_ene, ene, (size_t)nen * sizeof(double)));
+    XFER(spectra_check(h, "rsrec_block_spectra", nop, ops, spec));
+    const size_t obytes = (size_t)nop * BLK * sizeof(double2), per_site = (size_t)nop * nen;
+    SiteStage S;
+    XFER(site_stage_begin(h, S, "rsrec_block_spectra", 1, nen, ene, 0.0, 0.0, site_offset, nsites_total, h->d_spec, per_site));
     const double2* d_ops = reinterpret_cast<const double2*>(ops);
     if (!is_device_ptr(ops)) {
         HIPCK(h, h->d_ops.reserve(obytes));
         XFER(xfer_h2d(h, h->d_ops.p, ops, obytes));
         d_ops = h->d_ops.as<double2>();
     }
-    reset_timing(h);
-    hipEvent_t e0 = next_event(h);
-    const double2* dA = h->d_coefA.as<double2>();
-    double2* dBs = h->d_bsqrt.as<double2>();
-    // b2_b of the recursion stays B^2; the stage works on its own square root (as rsrec_block_ldos)
-    HIPCK(h, hipMemcpyAsync(dBs, h->d_coefB.p, cel * sizeof(double2), hipMemcpyDeviceToDevice, h->stream));
-    k_zsqr<<<n * lld, 256, 0, h->stream>>>(dBs, h->d_status.as<int>());
-    double* d_ai = h->d_term.as<double>();
-    double* d_bi = d_ai + (size_t)n * BLK;
-    rc = launch_terminator(h, n, lld, dA, dBs, d_ai, d_bi);
-    if (rc) return rc;
-    hipEvent_t k0 = next_event(h);
+    XFER(site_stage_open(h, S));
     {
-        const dim3 grid((nen + GREEN_WAVES - 1) / GREEN_WAVES, n);
-        k_block_spectra<<<grid, GREEN_WAVES * 64, 0, h->stream>>>(lld, nen, d_ene, eta_re, eta_im, sym_term, d_ai, d_bi, dA, dBs, nop, d_ops, d_spec);
+        const dim3 grid((nen + GREEN_WAVES - 1) / GREEN_WAVES, S.n);
+        k_block_spectra<<<grid, GREEN_WAVES * 64, 0, h->stream>>>(S.lld, nen, S.d_ene, eta_re, eta_im, sym_term, S.ta, S.tb, S.sa, S.sb, nop, d_ops, S.d_out);
     }
     HIPCK(h, hipGetLastError());
     hipEvent_t k1 = next_event(h);
-    XFER(spectra_deliver(h, d_spec, per_site, n, site_offset, nsites_total, spec));
-    hipEvent_t e1 = next_event(h);
-    int status = 0;
-    XFER(xfer_d2h(h, &status, h->d_status.p, 4));
-    HIPCK(h, hipStreamSynchronize(h->stream));
-    finish_timing(h, e0, e1, {{k0, k1}});             // hop: the Green kernel with its epilogue; rest: zsqr + terminator + delivery
-    if (status & 1) return fail(h, RSREC_ERR_EIG, "Diagonalization error (18x18 Jacobi did not converge)");
-    return RSREC_OK;
+    XFER(spectra_deliver(h, S.d_out, per_site, S.n, site_offset, nsites_total, spec));
+    return site_stage_end(h, S, S.k0, k1, next_event(h));   // hop: the Green kernel with its epilogue; rest: zsqr + terminator + delivery
 }
 
 // Im Tr(O_k g0) of green%chebyshev_green for the sites of the last rsrec_chebyshev call, from the moments it left on the device:
@@ -2364,49 +2372,31 @@ extern "C" int rsrec_block_spectra(rsrec_t* h, int nop, const double* ops, int n
 extern "C" int rsrec_chebyshev_spectra(rsrec_t* h, int nop, const double* ops, int nen, const double* ene, double energy_min, double energy_max,
                                        int site_offset, int nsites_total, double* spec) {
     if (!h) return RSREC_ERR_ARG;
-    int rc = spectra_check(h, "rsrec_chebyshev_spectra", 2, nop, ops, nen, ene, site_offset, nsites_total, spec);
-    if (rc) return rc;
-    const int n = h->res_n, nm = 2 * h->res_lld + 2;
-    const size_t lds = (size_t)nm * nop * sizeof(double2);            // the operator traces of one site (24 KB at lld = 50, 15 operators)
-    if (lds > (size_t)150 * 1024) return fail(h, RSREC_ERR_ARG, "rsrec_chebyshev_spectra: lld = %d with %d operators too deep for the LDS staging", h->res_lld, nop);
-    HIPCK(h, hipSetDevice(h->device));
-    if (lds > (size_t)64 * 1024 && lds > h->cheb_spec_attr_lds) {
-        HIPCK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_chebyshev_spectra), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        h->cheb_spec_attr_lds = lds;
-    }
-    double a, b;
-    chebyshev_green_scaling(energy_min, energy_max, a, b);
-    const std::vector<double> kern = chebyshev_green_kernel(nm);
-    const size_t obytes = (size_t)nop * BLK * sizeof(double2), tbytes = (size_t)n * nm * nop * sizeof(double2), per_site = (size_t)nop * nen;
-    release_kubo_buffers(h, true, true);
-    HIPCK(h, h->d_spec.reserve((per_site * n + (size_t)nen + nm) * sizeof(double)));
-    HIPCK(h, h->d_ops.reserve(obytes + tbytes));
-    double* d_spec = h->d_spec.as<double>();
-    double* d_ene = d_spec + per_site * n;
-    double* d_kern = d_ene + nen;
-    XFER(xfer_h2d(h, d_ene, ene, (size_t)nen * sizeof(double)));
-    XFER(xfer_h2d(h, d_kern, kern.data(), (size_t)nm * sizeof(double)));
+    XFER(spectra_check(h, "rsrec_chebyshev_spectra", nop, ops, spec));
+    const size_t obytes = (size_t)nop * BLK * sizeof(double2), per_site = (size_t)nop * nen;
+    SiteStage S;
+    XFER(site_stage_begin(h, S, "rsrec_chebyshev_spectra", 2, nen, ene, energy_min, energy_max, site_offset, nsites_total, h->d_spec, per_site));
+    const size_t lds = (size_t)S.nm * nop * sizeof(double2);          // the operator traces of one site (24 KB at lld = 50, 15 operators)
+    if (lds > (size_t)150 * 1024) return fail(h, RSREC_ERR_ARG, "rsrec_chebyshev_spectra: lld = %d with %d operators too deep for the LDS staging", S.lld, nop);
+    XFER(lds_opt_in(h, reinterpret_cast<const void*>(k_chebyshev_spectra), lds, h->cheb_spec_lds));
+    HIPCK(h, h->d_ops.reserve(obytes + (size_t)S.n * lds));           // the operators (if they are host memory) | their traces with every moment of every site
     const double2* d_ops = reinterpret_cast<const double2*>(ops);
     if (!is_device_ptr(ops)) {
         XFER(xfer_h2d(h, h->d_ops.p, ops, obytes));
         d_ops = h->d_ops.as<double2>();
     }
     double2* d_t = reinterpret_cast<double2*>(static_cast<char*>(h->d_ops.p) + obytes);
-    reset_timing(h);
-    hipEvent_t e0 = next_event(h);
-    k_chebyshev_optrace<<<dim3(nm, n), 64, 0, h->stream>>>(nm, nop, d_ops, h->d_mu.as<double2>(), d_t);
+    XFER(site_stage_open(h, S));
+    k_chebyshev_optrace<<<dim3(S.nm, S.n), 64, 0, h->stream>>>(S.nm, nop, d_ops, S.sa, d_t);
     hipEvent_t k0 = next_event(h);
     {
-        const dim3 grid((nen + CHEB_LDOS_TILE - 1) / CHEB_LDOS_TILE, n);
-        k_chebyshev_spectra<<<grid, CHEB_LDOS_TILE, lds, h->stream>>>(nm, nop, nen, d_ene, a, b, d_kern, d_t, d_spec);
+        const dim3 grid((nen + CHEB_LDOS_TILE - 1) / CHEB_LDOS_TILE, S.n);
+        k_chebyshev_spectra<<<grid, CHEB_LDOS_TILE, lds, h->stream>>>(S.nm, nop, nen, S.d_ene, S.ca, S.cb, S.d_kern, d_t, S.d_out);
     }
     HIPCK(h, hipGetLastError());
     hipEvent_t k1 = next_event(h);
-    XFER(spectra_deliver(h, d_spec, per_site, n, site_offset, nsites_total, spec));
-    hipEvent_t e1 = next_event(h);
-    HIPCK(h, hipStreamSynchronize(h->stream));
-    finish_timing(h, e0, e1, {{k0, k1}});             // hop: the energy sum alone; rest: the operator traces + delivery
-    return RSREC_OK;
+    XFER(spectra_deliver(h, S.d_out, per_site, S.n, site_offset, nsites_total, spec));
+    return site_stage_end(h, S, k0, k1, next_event(h));     // hop: the energy sum alone; rest: the operator traces + delivery
 }
 
 namespace {
@@ -2513,7 +2503,7 @@ int pair_call_begin(rsrec_t* h, PairCall& c, const char* who, int kind, int npai
     HIPCK(h, h->d_green_in.reserve((off_chunk + P * chunk_in) * sizeof(double)));
     const size_t off_fo = P * row_doubles, off_co = off_fo + fixed_out;
     HIPCK(h, h->d_green_out.reserve((off_co + P * chunk_out) * sizeof(double)));
-    if (c.resident && kind == 0) HIPCK(h, h->d_bsqrt.reserve(Q * cel * sizeof(double2)));
+    if (c.resident && kind == 0) HIPCK(h, h->d_bsqrt.reserve(Q * cel * sizeof(double2)));      // resident_block_prologue's, for the largest chunk
     HIPCK(h, h->d_status.reserve(64));
     HIPCK(h, hipMemsetAsync(h->d_status.p, 0, 64, h->stream));
     c.din = h->d_green_in.as<double>();
@@ -2536,7 +2526,7 @@ int pair_call_begin(rsrec_t* h, PairCall& c, const char* who, int kind, int npai
     return RSREC_OK;
 }
 
-// Coefficients and terminators of the pairs p0 .. p0 + P - 1 (resident: read in place, b2_b square-rooted into a buffer of its own; caller
+// Coefficients and terminators of the pairs p0 .. p0 + P - 1 (resident: read in place, behind resident_block_prologue; caller
 // arrays: staged, or read in place when they are device memory; terminators from the device unless given)
 int pair_call_chunk(rsrec_t* h, const PairCall& c, int p0, PairChunk& k) {
     const size_t cel = c.cel;
@@ -2544,26 +2534,27 @@ int pair_call_chunk(rsrec_t* h, const PairCall& c, int p0, PairChunk& k) {
     const size_t c0 = (size_t)c.cbase[p0], nc = (size_t)(c.cbase[p0 + k.np] - c.cbase[p0]);     // chains of the chunk
     k.c0 = (int)c0;
     k.sb = nullptr; k.tb = nullptr;
+    double* const d_ai = c.din + c.off_ai;
+    double* const d_bi = c.din + c.off_bi;
     const double* sa = nullptr;
     if (c.resident) sa = reinterpret_cast<const double*>((c.kind == 0 ? h->d_coefA.as<double2>() : h->d_mu.as<double2>()) + c0 * cel);
     else XFER(xc_fetch(h, c.coef_a + c0 * cel * 2, c.din + c.off_ab, nc * cel * 2, &sa));
     k.sa = reinterpret_cast<const double2*>(sa);
-    if (c.kind == 1) { k.ta = c.din + c.off_ai; return RSREC_OK; }
-    const double* sb = nullptr;
-    if (c.resident) {                                 // b2_b of the recursion stays B^2: the square root goes to its own buffer
-        double2* dBs = h->d_bsqrt.as<double2>();
-        HIPCK(h, hipMemcpyAsync(dBs, h->d_coefB.as<double2>() + c0 * cel, nc * cel * sizeof(double2), hipMemcpyDeviceToDevice, h->stream));
-        k_zsqr<<<(unsigned)(nc * c.lld), 256, 0, h->stream>>>(dBs, h->d_status.as<int>());
-        sb = reinterpret_cast<const double*>(dBs);
-    } else XFER(xc_fetch(h, c.coef_b + c0 * cel * 2, c.din + c.off_bs, nc * cel * 2, &sb));
-    k.sb = reinterpret_cast<const double2*>(sb);
-    if (c.a_inf) {
-        XFER(xc_fetch(h, c.a_inf + c0 * BLK, c.din + c.off_ai, nc * BLK, &k.ta));
-        XFER(xc_fetch(h, c.b_inf + c0 * BLK, c.din + c.off_bi, nc * BLK, &k.tb));
+    k.ta = d_ai;
+    if (c.kind == 1) return RSREC_OK;
+    k.tb = d_bi;
+    if (c.resident) {
+        XFER(resident_block_prologue(h, c0, nc, c.lld, c.a_inf ? nullptr : d_ai, d_bi));
+        k.sb = h->d_bsqrt.as<double2>();
     } else {
-        int rc = launch_terminator(h, (int)nc, c.lld, k.sa, k.sb, c.din + c.off_ai, c.din + c.off_bi);
-        if (rc) return rc;
-        k.ta = c.din + c.off_ai; k.tb = c.din + c.off_bi;
+        const double* sb = nullptr;
+        XFER(xc_fetch(h, c.coef_b + c0 * cel * 2, c.din + c.off_bs, nc * cel * 2, &sb));
+        k.sb = reinterpret_cast<const double2*>(sb);
+        if (!c.a_inf) XFER(launch_terminator(h, (int)nc, c.lld, k.sa, k.sb, d_ai, d_bi));
+    }
+    if (c.a_inf) {
+        XFER(xc_fetch(h, c.a_inf + c0 * BLK, d_ai, nc * BLK, &k.ta));
+        XFER(xc_fetch(h, c.b_inf + c0 * BLK, d_bi, nc * BLK, &k.tb));
     }
     return RSREC_OK;
 }
@@ -2571,15 +2562,12 @@ int pair_call_chunk(rsrec_t* h, const PairCall& c, int p0, PairChunk& k) {
 // end of such a call: the status word, the stream, the timing (total; hop = rest = the kernel stages of the chunks)
 int pair_call_end(rsrec_t* h, hipEvent_t e0, const std::vector<std::pair<hipEvent_t, hipEvent_t>>& kev) {
     hipEvent_t e1 = next_event(h);
-    int status = 0;
-    XFER(xfer_d2h(h, &status, h->d_status.p, 4));
-    HIPCK(h, hipStreamSynchronize(h->stream));
+    const int rc = finish_status(h);
     h->t_total_ms = ev_ms(e0, e1);
     h->t_rest_ms = 0.0;
     for (auto& pr : kev) h->t_rest_ms += ev_ms(pr.first, pr.second);
     h->t_hop_ms = h->t_rest_ms;
-    if (status & 1) return fail(h, RSREC_ERR_EIG, "Diagonalization error (18x18 Jacobi did not converge)");
-    return RSREC_OK;
+    return rc;
 }
 
 }  // namespace
@@ -2969,7 +2957,7 @@ int run_chebyshev(rsrec_t* h, int nsites, int nseed, const int32_t* seed_atoms, 
     int status = 0;
     XFER(xfer_d2h(h, &status, h->d_status.p, 4));
     if (status & 2) return fail(h, RSREC_ERR_DIVERGED, "Chebyshev moments did not converge. Check energy limits energy_min and energy_max");
-    h->res_kind = 2; h->res_n = nsites; h->res_lld = lld; h->res_sqrt = 0; h->res_seeded = seed_coef != nullptr;
+    h->res_kind = 2; h->res_n = nsites; h->res_lld = lld; h->res_seeded = seed_coef != nullptr;
     return RSREC_OK;
 }
 

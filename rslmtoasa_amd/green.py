@@ -26,6 +26,25 @@ class Green:
             self.g0 = np.zeros(shape, dtype=np.complex128, order="F")
         return self.g0
 
+    def _sites(self, site_offset, nsites_total):
+        """The sites of this rank: their number and the number of sites in the zero-padded images (all ranks')."""
+        start, end = self.recursion._my_sites()[:2]
+        n = end - start + 1
+        return n, (n + site_offset if nsites_total is None else nsites_total)
+
+    def _ldos_args(self, site_offset, nsites_total, out):
+        """The images of an LDOS stage and their addresses: host arrays, or ``out`` = (dtot, dosia, dosial) raw DEVICE addresses."""
+        import ctypes as C
+        n, ntot = self._sites(site_offset, nsites_total)
+        nen = len(self.ene)
+        if out is None:
+            img = dict(dtot=np.zeros(nen), dosia=np.zeros((ntot, nen), order="F"), dosial=np.zeros((ntot, 18, nen), order="F"))
+            ptrs = tuple(_ptr(img[k]) for k in ("dtot", "dosia", "dosial"))
+        else:
+            img = dict(dtot=None, dosia=None, dosial=None)
+            ptrs = tuple(C.c_void_p(int(p)) for p in out)
+        return self.recursion, n, nen, ntot, img, ptrs
+
     def block_green(self, a_inf, b_inf, eta=0.0 + 0.0j, nsites=None):
         """green%block_green: requires ``recursion.zsqr()`` to have been called (self.f90:829), like the reference."""
         rec = self.recursion
@@ -89,25 +108,12 @@ class Green:
         there: zsqr -> get_terminf -> bgreen -> the reduction of bands%calculate_fermi (bands.f90:258-268).  Returns a dict with the
         zero-padded images ``dtot(nen)``, ``dosia(nsites_total, nen)``, ``dosial(nsites_total, 18, nen)`` and the terminators used.
         ``out`` = (dtot, dosia, dosial) raw DEVICE addresses (e.g. ``tensor.data_ptr()``): the images are written there in place."""
-        import ctypes as C
-        rec = self.recursion
-        start, end = rec._my_sites()[:2]
-        n = end - start + 1
-        ntot = n + site_offset if nsites_total is None else nsites_total
-        nen = len(self.ene)
+        rec, n, nen, ntot, img, ptrs = self._ldos_args(site_offset, nsites_total, out)
         a_inf = np.zeros((18, 18, n), np.float64, order="F")
         b_inf = np.zeros_like(a_inf)
-        if out is None:
-            dtot = np.zeros(nen)
-            dosia = np.zeros((ntot, nen), order="F")
-            dosial = np.zeros((ntot, 18, nen), order="F")
-            ptrs = (_ptr(dtot), _ptr(dosia), _ptr(dosial))
-        else:
-            dtot = dosia = dosial = None
-            ptrs = tuple(C.c_void_p(int(p)) for p in out)
         rec._check(rec._L.rsrec_block_ldos(rec._h, nen, _ptr(self.ene), float(np.real(eta)), float(np.imag(eta)), int(self.sym_term),
                                            int(site_offset), int(ntot), ptrs[0], ptrs[1], ptrs[2], _ptr(a_inf), _ptr(b_inf)))
-        return dict(dtot=dtot, dosia=dosia, dosial=dosial, a_inf=a_inf, b_inf=b_inf)
+        return dict(img, a_inf=a_inf, b_inf=b_inf)
 
     def contour_occupation(self, x, w, e0, kind="block", site_offset=0, nsites_total=None, diag=False, resident=False, coef=None, a_inf=None, b_inf=None):
         """The orbital occupations of bands%calculate_moments_gauss_legendre / calculate_occupation_gauss_legendre (bands.f90:559-586,
@@ -120,9 +126,7 @@ class Green:
         b2_b after zsqr / mu_n).  Terminators: ``a_inf, b_inf`` (18,18,nsites) or None (computed on the device, once per chain)."""
         rec = self.recursion
         k = {"block": 0, "chebyshev": 1}[kind] if isinstance(kind, str) else int(kind)
-        start, end = rec._my_sites()[:2]
-        n = end - start + 1
-        ntot = n + site_offset if nsites_total is None else nsites_total
+        n, ntot = self._sites(site_offset, nsites_total)
         lld = int(rec.control.lld)
         x, w = np.ascontiguousarray(x, dtype=np.float64), np.ascontiguousarray(w, dtype=np.float64)
         if x.ndim != 1 or x.shape != w.shape:
@@ -166,23 +170,10 @@ class Green:
         the diagonal of green%chebyshev_green -> the reduction of bands%calculate_fermi (bands.f90:258-268).  Returns a dict with the
         zero-padded images ``dtot(nen)``, ``dosia(nsites_total, nen)``, ``dosial(nsites_total, 18, nen)``, as ``block_ldos`` does.
         ``out`` = (dtot, dosia, dosial) raw DEVICE addresses: the images are written there in place."""
-        import ctypes as C
-        rec = self.recursion
-        start, end = rec._my_sites()[:2]
-        n = end - start + 1
-        ntot = n + site_offset if nsites_total is None else nsites_total
-        nen = len(self.ene)
-        if out is None:
-            dtot = np.zeros(nen)
-            dosia = np.zeros((ntot, nen), order="F")
-            dosial = np.zeros((ntot, 18, nen), order="F")
-            ptrs = (_ptr(dtot), _ptr(dosia), _ptr(dosial))
-        else:
-            dtot = dosia = dosial = None
-            ptrs = tuple(C.c_void_p(int(p)) for p in out)
+        rec, n, nen, ntot, img, ptrs = self._ldos_args(site_offset, nsites_total, out)
         rec._check(rec._L.rsrec_chebyshev_ldos(rec._h, nen, _ptr(self.ene), float(rec.en.energy_min), float(rec.en.energy_max),
                                                int(site_offset), int(ntot), ptrs[0], ptrs[1], ptrs[2]))
-        return dict(dtot=dtot, dosia=dosia, dosial=dosial)
+        return img
 
     def _spectra_args(self, ops, site_offset, nsites_total, out):
         """Operators as complex (nop, 18, 18) C-ordered stacks of column-major matrices are what the library reads: ``ops[k]`` is O_k as
@@ -190,9 +181,7 @@ class Green:
         and must hold that layout already (``[k][column][row]``, complex128)."""
         import ctypes as C
         rec = self.recursion
-        start, end = rec._my_sites()[:2]
-        n = end - start + 1
-        ntot = n + site_offset if nsites_total is None else nsites_total
+        ntot = self._sites(site_offset, nsites_total)[1]
         if hasattr(ops, "data_ptr"):
             nop, keep, optr = int(ops.shape[0]), ops, C.c_void_p(int(ops.data_ptr()))
         else:

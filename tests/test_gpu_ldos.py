@@ -178,6 +178,45 @@ def test_ldos_positive_on_full_mesh():
     rec.close()
 
 
+@pytest.mark.parametrize("name, recur, ldos, spectra", [("bccFe_nsp2_block", "recur_b", "block_ldos", "block_spectra"),
+                                                        ("bccFe_nsp2_cheb", "chebyshev_recur", "chebyshev_ldos", "chebyshev_spectra")])
+def test_interleaved_stages_leak_no_state(name, recur, ldos, spectra):
+    """The stages on resident chains share one setup, one prologue and its buffers (the square root of B^2, the terminators, the status
+    word): LDOS, spectra, contour occupation, spectra, LDOS on one handle after one recursion.  The first and the last call of a stage
+    give the same bits in every field, and those are the bits of a fresh handle that runs that stage alone.  No tolerance."""
+    from rslmtoasa_amd import bands
+    from rslmtoasa_amd.exchange import gauss_legendre
+    ops = bands.stack(bands.ALL_OPERATORS)
+    z, g = load_green(name), load_golden(name)
+    window = dict(emin=g["emin"], emax=g["emax"]) if recur == "chebyshev_recur" else {}
+    x, w = gauss_legendre(16)
+
+    def fresh():
+        rec = Recursion(*objects_from(problem_dict(g), g["irec"], g["lld"], nsp=g["nsp"], **window), device=0)
+        getattr(rec, recur)()
+        return rec, Green(rec, z["ene"])
+
+    rec, gr = fresh()
+    l1 = getattr(gr, ldos)()
+    s1 = getattr(gr, spectra)(ops)
+    occ = gr.contour_occupation(x, w, float(z["ene"][31]), kind="chebyshev" if window else "block", resident=True)
+    s2 = getattr(gr, spectra)(ops)
+    l2 = getattr(gr, ldos)()
+    rec.close()
+    rec, gr = fresh()
+    l0 = getattr(gr, ldos)()
+    rec.close()
+    rec, gr = fresh()
+    s0 = getattr(gr, spectra)(ops)
+    rec.close()
+    assert len(z["ene"]) == 63 and g["lld"] == 20 and np.isfinite(occ).all() and np.abs(occ).max() > 0
+    assert np.abs(s0).max() > 0 and np.abs(l0["dosial"]).max() > 0
+    assert set(l1) == set(l2) == set(l0) and {"dtot", "dosia", "dosial"} <= set(l0)
+    for k in l0:
+        assert np.array_equal(l1[k], l2[k]) and np.array_equal(l1[k], l0[k]), k
+    assert np.array_equal(s1, s2) and np.array_equal(s1, s0)
+
+
 def test_ldos_needs_resident_coefficients():
     from rslmtoasa_amd import _lib
     g = load_golden("bccFe_nsp2_block")
