@@ -32,7 +32,8 @@
 !> `green_gpu%defer_g0` postponed it).
 !>
 !> Falls back to the inherited routine whenever the device does not hold this call's coefficients or moments (scalar recursion,
-!> local-axis runs, a `green` that is not `green_gpu`).
+!> local-axis runs without RSREC_LOCAL_AXIS_DEVICE, a `green` that is not `green_gpu`).  With that switch `recursion_gpu` announces the
+!> chains of a local-axis run, resident in each site's local frame, and every stage here takes them as it takes a collinear run's.
 !------------------------------------------------------------------------------
 module bands_gpu_mod
    use, intrinsic :: iso_c_binding
@@ -41,7 +42,7 @@ module bands_gpu_mod
    use green_mod
    use green_gpu_mod
    use precision_mod, only: rp
-   use math_mod, only: pi, gauss_legendre, simpson_m, simpson_f, L_x, L_y, L_z, hcpx, i_unit
+   use math_mod, only: pi, gauss_legendre, simpson_m, simpson_f, L_x, L_y, L_z, hcpx, i_unit, updatrotmom_single
    use logger_mod, only: g_logger
    use timer_mod, only: g_timer
    use string_mod, only: fmt
@@ -420,8 +421,11 @@ contains
 
          if (this%control%nsp < 3) this%symbolic_atom(pb)%potential%mom(:) = [0.0d0, 0.0d0, 1.00d0]
 
-         ! (local-axis runs never take this route: device_stage_usable)
-         call g_logger%info('Spin moment projections of atom'//fmt('i4', na)//' is '//fmt('f10.6', mx)//' '//fmt('f10.6', my)//' '//fmt('f10.6', mz), __FILE__, __LINE__)
+         if (this%recursion%hamiltonian%local_axis) then            ! bands.f90:849-853
+            call g_logger%info('Local spin moment projections of atom'//fmt('i4', na)//' is '//fmt('f10.6', mx)//' '//fmt('f10.6', my)//' '//fmt('f10.6', mz), __FILE__, __LINE__)
+         else
+            call g_logger%info('Spin moment projections of atom'//fmt('i4', na)//' is '//fmt('f10.6', mx)//' '//fmt('f10.6', my)//' '//fmt('f10.6', mz), __FILE__, __LINE__)
+         end if
       end do
    end subroutine gpu_calculate_magnetic_moments
 
@@ -482,13 +486,15 @@ contains
    end subroutine gpu_calculate_orbital_quadrupoles
 
    !> calculate_moments (bands.f90:409-524): dspd from the image and the (mixed) moment directions, the tail restated.  Local-axis runs
-   !> never come here (their chains are not resident: device_stage_usable), so the rotation branch of :458-467 has no counterpart.
+   !> (chains resident in each site's frame, RSREC_LOCAL_AXIS_DEVICE) rotate every site's direction back to the global frame inside the
+   !> atom loop, as :427-432 and :458-467 do.
    subroutine gpu_calculate_moments(this)
       class(bands_gpu) :: this
       integer :: i, l, ie, na, na_glob, isp, soff, nsp, plusbulk
-      real(rp) :: sgef, pmef, smef, isgn
+      real(rp) :: sgef, pmef, smef, isgn, mnorm
       real(rp), dimension(3) :: mom
       real(rp), dimension(this%en%channels_ldos + 10) :: y
+      real(rp), dimension(3, atoms_per_process) :: mom_prev
 #ifdef USE_MPI
       integer :: pot_size
       real(rp), dimension(:, :), allocatable :: T_comm
@@ -499,6 +505,12 @@ contains
          call this%bands%calculate_moments()
          return
       end if
+
+      do na_glob = start_atom, end_atom                             ! bands.f90:427-432
+         na = g2l_map(na_glob)
+         plusbulk = this%lattice%nbulk + na_glob
+         mom_prev(:, na) = this%symbolic_atom(plusbulk)%potential%mom
+      end do
 
       call this%calculate_orbital_moments()
       call ensure_spectra(this)
@@ -518,6 +530,16 @@ contains
                end do
             end do
          end do
+         if (this%recursion%hamiltonian%local_axis) then            ! bands.f90:458-467
+            call updatrotmom_single(this%symbolic_atom(plusbulk)%potential%mom, mom_prev(:, na))
+            call this%symbolic_atom(plusbulk)%potential%copy_mom_to_scal()
+
+            mnorm = this%symbolic_atom(plusbulk)%potential%mtot
+            call g_logger%info('Global spin moment projections of atom'//fmt('i4', na)//' is '// &
+                               fmt('f10.6', this%symbolic_atom(plusbulk)%potential%mom(1)*mnorm)//' '// &
+                               fmt('f10.6', this%symbolic_atom(plusbulk)%potential%mom(2)*mnorm)//' '// &
+                               fmt('f10.6', this%symbolic_atom(plusbulk)%potential%mom(3)*mnorm), __FILE__, __LINE__)
+         end if
       end do
       this%dspd(:, :, :) = this%dspd(:, :, :)*0.5d0/pi
 

@@ -38,6 +38,9 @@ module recursion_gpu_mod
    private
 
    type, public, extends(recursion) :: recursion_gpu
+      !> local-axis runs: announce the chains recur_b leaves on the device (in each site's local frame) to the device LDOS / moment
+      !> stages of bands_gpu.  Off unless RSREC_LOCAL_AXIS_DEVICE is set: such a run then keeps the inherited host stages.
+      logical :: local_axis_device = .false.
    contains
       procedure :: recur => gpu_recur
       procedure :: recur_b => gpu_recur_b
@@ -62,7 +65,7 @@ module recursion_gpu_mod
 
    !> (the per-process device context g_handle lives in rsrec_context_mod; re-exported above for the hosts that used it from here)
    !> number of sites whose block coefficients the last driver call left on the device (0: none -- another driver ran since, or the
-   !> coefficients there are not the ones in a_b / b2_b, as after a local-axis run): the input of the device LDOS stage
+   !> coefficients there are not announced, as after a local-axis run without RSREC_LOCAL_AXIS_DEVICE): the input of the device LDOS stage
    integer, save :: g_block_resident = 0
    !> the same for the Chebyshev moments mu_n of chebyshev_recur (every other driver resets it)
    integer, save :: g_cheb_resident = 0
@@ -80,6 +83,7 @@ contains
       obj%en => energy_obj
       obj%control => hamiltonian_obj%charge%lattice%control
       call obj%restore_to_default()
+      if (rsrec_env_flag('RSREC_LOCAL_AXIS_DEVICE')) obj%local_axis_device = .true.   ! (hosts that cannot reach the member: fortran/shadow/)
    end function gpu_constructor
 
    !> Sites of this rank whose a_b / b2_b (as recur_b produced them) are also resident on the device; 0 if they are not.
@@ -182,7 +186,8 @@ contains
          ! The reference re-rotates every block into the spin frame of each site before its chain (recursion.f90:1830-1832), i.e.
          ! H is per site.  All sites still go in ONE call: the library gets the GLOBAL-frame blocks (the *_glob arrays
          ! rotate_to_local_axis starts from, hamiltonian.f90:2451-2461) plus one rotation matrix per site, runs every chain on the
-         ! global blocks with that site's on-site term R l.s R^H and conjugates the 18x18 outputs (see include/rsrec.h).
+         ! global blocks with that site's on-site term R l.s R^H and conjugates the 18x18 coefficients on the device (see include/rsrec.h):
+         ! ab / bb and the chains left resident are the same numbers, in each site's local frame.
          allocate (rot(18, 18, nloc))
          do i = start_atom, end_atom
             i_loc = i - start_atom + 1
@@ -201,6 +206,7 @@ contains
          call check(rc, 'rsrec_block_lanczos_local_axis')
          ! leave the Hamiltonian object as the reference's loop does: rotated into the frame of the last site
          call this%hamiltonian%rotate_to_local_axis(this%lattice%symbolic_atoms(end_atom)%potential%mom)
+         if (this%local_axis_device) g_block_resident = nloc
       else
          call sync_device(this, .true.)
          do i = start_atom, end_atom

@@ -105,12 +105,16 @@ int rsrec_block_lanczos_seeded(rsrec_t *h, int nchains, int nseed, const int32_t
  * lsham) and every chain carries its rotation:
  *   rot : complex (18,18,nsites), R_i = ROTMAT(alpha_i, beta_i, 0) of site i's moment direction (math.f90:2026, car2sph :2155)
  * The chain of the rotated operator equals the chain of the global operator with the on-site term R_i l.s R_i^H, conjugated:
- * a_b(:,:,:,i) = R_i^H A R_i, b2_b likewise -- the library does both; outputs are in the local frame of each site like the
- * reference's.  a_b, b2_b : complex (18,18,lld,nsites) out. */
+ * a_b(:,:,:,i) = R_i^H A R_i, b2_b likewise -- the library does both, the conjugation on the device (sums in a fixed order, no FMA
+ * contraction); a_b(:,:,lld,:) = 0 and b2_b(:,:,1,:) = I stay exact.  Outputs are in the local frame of each site like the reference's.
+ *   a_b, b2_b : complex (18,18,lld,nsites) out.
+ * The chains are LEFT RESIDENT in each site's local frame, the same bits as the returned arrays: rsrec_pack_diag, rsrec_block_ldos,
+ * rsrec_block_spectra and rsrec_contour_occupation (resident) follow this call as they follow rsrec_block_lanczos (the continued fraction,
+ * zsqr, get_terminf and their epilogues are covariant under the unitary transform).  rsrec_get_timing: out[12] ms of the conjugation. */
 int rsrec_block_lanczos_local_axis(rsrec_t *h, int nsites, const int32_t *seed_atoms, const double *rot, int lld, double *a_b, double *b2_b);
 
 /* The per-site result the ranks exchange after the recursion, packed ON THE DEVICE from the coefficients the last
- * rsrec_block_lanczos call left there: a(ll,l,site) = Re a_b(l,l,ll,site), b2 likewise (recursion.f90:1850-1851).
+ * rsrec_block_lanczos / rsrec_block_lanczos_local_axis call left there: a(ll,l,site) = Re a_b(l,l,ll,site), b2 likewise (recursion.f90:1850-1851).
  * The reference gathers per-site arrays with MPI_ALLREDUCE(MPI_IN_PLACE, ..., MPI_SUM) on zero-padded images
  * (bands.f90:271-274); this writes such an image for this rank: sites site_offset+1 .. site_offset+nsites (the rank's
  * start_atom-1 from rsrec_site_partition) are filled, every other site is zero, so one RCCL all-reduce(sum) over the
@@ -437,6 +441,7 @@ int rsrec_set_option(rsrec_t *h, const char *key, long value);
  *          hamiltonian.f90:1553-1617) needs 23 328, a spin-mixing block 46 656 -- the unit roofline fractions are quoted in.
  *   out[10] block arrays (0..4: ee, eeo, hall, hallo) the last rsrec_set_hamiltonian took from rsrec_assemble_blocks' device copies.
  *   out[11] H|psi> launches of the last call in which the atoms with their own operator blocks were grouped over 8 chains (option "s5_octet").
+ *   out[12] rsrec_block_lanczos_local_axis: ms in the conjugation of the resident coefficients with the sites' rotations (part of out[5]).
  * After rsrec_block_green: out[0] = kernel + transfers, out[1] = the Green kernel alone. */
 int rsrec_get_timing(rsrec_t *h, double *out, int n);
 

@@ -116,7 +116,7 @@ struct rsrec_handle {
     int n_asm_reused = 0;        // block arrays the last rsrec_set_hamiltonian took from those device copies (0..4)
     long n_asm_calls = 0, n_ldos_calls = 0, n_recursion_calls = 0;   // life-time counters of the handle (RSREC_REPORT)
     Spmm5Operator s5_la; int s5_la_ok = 0;   // operator tables of local-axis runs: H without the on-site l.s term, which comes per chain
-    DevBuf d_la_extra;
+    DevBuf d_la_extra, d_rot;               // per-chain on-site fragments; the rotations of all chains of the call (k_rotate_coef)
     Spmm5Operator kubo_op[2], kubo_hbulk;   // v_a / v_b tables of the last rsrec_kubo_moments call
     Spmm5Operator orb_plain;                // h as ham_vec_matmul applies it when hoh is set (rsrec_orbital_moments, rsrec_apply_operator vel = 2)
     // work
@@ -153,6 +153,7 @@ struct rsrec_handle {
     bool capturing = false;      // between hipStreamBeginCapture and hipStreamEndCapture: no timing events, no allocation
     // timing of last call
     double t_total_ms = 0, t_hop_ms = 0, t_rest_ms = 0, t_host_ms = 0;
+    double t_rot_ms = 0;      // local-axis recursion: ms in k_rotate_coef (part of t_rest_ms)
     double n_hop_launch = 0, n_atom_steps = 0, n_block_mult = 0, n_hop_mfma_flop = 0;   // mfma_flop: matrix flops EXECUTED by the timed k_spmm5 launches
     double n_req_flop = 0;    // flops of H|psi> the operator's block structure requires (spin-diagonal blocks: half a zgemm), see required_hop_flops
     int hop_fuses_a = 1;      // 1: the timed H|psi> kernel also forms pmn and the A_n partial (VALU path); 0: pure SpMM (MFMA path)
@@ -459,9 +460,9 @@ extern "C" int rsrec_set_option(rsrec_t* h, const char* key, long value) {
 
 extern "C" int rsrec_get_timing(rsrec_t* h, double* out, int n) {
     if (!h || !out) return RSREC_ERR_ARG;
-    const double v[12] = {h->t_total_ms, h->t_hop_ms, h->n_hop_launch, h->n_atom_steps, h->n_block_mult, h->t_rest_ms, h->t_host_ms, (double)h->hop_fuses_a, h->n_hop_mfma_flop,
-                          h->n_req_flop, (double)h->n_asm_reused, (double)h->n_octet_launch};
-    for (int i = 0; i < n && i < 12; ++i) out[i] = v[i];
+    const double v[13] = {h->t_total_ms, h->t_hop_ms, h->n_hop_launch, h->n_atom_steps, h->n_block_mult, h->t_rest_ms, h->t_host_ms, (double)h->hop_fuses_a, h->n_hop_mfma_flop,
+                          h->n_req_flop, (double)h->n_asm_reused, (double)h->n_octet_launch, h->t_rot_ms};
+    for (int i = 0; i < n && i < 13; ++i) out[i] = v[i];
     return RSREC_OK;
 }
 
@@ -985,7 +986,7 @@ double required_hop_flops(const rsrec_t* h, const Spmm5Operator& op) {
 }
 
 void reset_timing(rsrec_t* h) {
-    h->t_total_ms = h->t_hop_ms = h->t_rest_ms = h->t_host_ms = 0;
+    h->t_total_ms = h->t_hop_ms = h->t_rest_ms = h->t_host_ms = h->t_rot_ms = 0;
     h->n_hop_launch = h->n_atom_steps = h->n_block_mult = h->n_hop_mfma_flop = h->n_req_flop = 0;
     h->n_octet_launch = 0;
     h->ev_used = 0;
@@ -1303,6 +1304,43 @@ int launch_spmm(rsrec_t* h, const SpmmDims& SD, const ChainView& CV, const DevPr
     return RSREC_OK;
 }
 
+// Local-axis runs: the resident coefficients of chain s into the spin frame of its site, M <- R_s^H (M R_s) in place, for every matrix
+// the reference's chain leaves general: a_b of levels 1 .. lld - 1 and b2_b of levels 2 .. lld (a_b(:,:,lld) = 0 and b2_b(:,:,1) = I stay
+// exact, recursion.f90:1836-1837).  One workgroup per matrix: blockIdx.x < lld - 1 is a_b at level blockIdx.x, the others b2_b one level up.
+// Both 18-term sums run k ascending, every term ar*br - ai*bi / ar*bi + ai*br rounded before it is added, no FMA contraction: the bits of
+// the same loops on a host without FMA.  M, R: column-major 18 x 18.
+__global__ __launch_bounds__(256) void k_rotate_coef(double2* __restrict__ A, double2* __restrict__ B, const double2* __restrict__ rot, int lld) {
+#pragma clang fp contract(off)
+    __shared__ double2 sM[BLK], sR[BLK], sT[BLK];
+    const int chain = blockIdx.y, m = blockIdx.x;
+    const bool is_a = m < lld - 1;
+    double2* M = (is_a ? A : B) + ((size_t)chain * lld + (is_a ? m : m - (lld - 1) + 1)) * BLK;
+    const double2* R = rot + (size_t)chain * BLK;
+    for (int e = threadIdx.x; e < BLK; e += blockDim.x) { sM[e] = M[e]; sR[e] = R[e]; }
+    __syncthreads();
+    for (int e = threadIdx.x; e < BLK; e += blockDim.x) {            // T = M R
+        const int i = e % NB, j = e / NB;
+        double sr = 0.0, si = 0.0;
+#pragma unroll
+        for (int k = 0; k < NB; ++k) {
+            const double ar = sM[i + NB * k].x, ai = sM[i + NB * k].y, br = sR[k + NB * j].x, bi = sR[k + NB * j].y;
+            sr += ar * br - ai * bi; si += ar * bi + ai * br;
+        }
+        sT[e] = make_double2(sr, si);
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < BLK; e += blockDim.x) {            // M = R^H T
+        const int i = e % NB, j = e / NB;
+        double sr = 0.0, si = 0.0;
+#pragma unroll
+        for (int k = 0; k < NB; ++k) {
+            const double ar = sR[k + NB * i].x, ai = -sR[k + NB * i].y, br = sT[k + NB * j].x, bi = sT[k + NB * j].y;
+            sr += ar * br - ai * bi; si += ar * bi + ai * br;
+        }
+        M[e] = make_double2(sr, si);
+    }
+}
+
 // One implementation for both kernel sets: L = LayoutCM with the VALU kernels, LayoutRM with the MFMA SpMM.
 template <class L, bool MFMA>
 int run_block_lanczos(rsrec_t* h, int nchains, int nseed, const int32_t* seed_atoms, const double* seed_coef, int lld, double* a_b, double* b2_b,
@@ -1330,6 +1368,10 @@ int run_block_lanczos(rsrec_t* h, int nchains, int nseed, const int32_t* seed_at
     h->res_kind = 0;
     HIPCK(h, h->d_coefA.reserve((size_t)nchains * lld * BLK * sizeof(double2)));
     HIPCK(h, h->d_coefB.reserve((size_t)nchains * lld * BLK * sizeof(double2)));
+    if (rot) {                                          // the rotations of all chains, once per call (k_rotate_coef)
+        HIPCK(h, h->d_rot.reserve((size_t)nchains * BLK * sizeof(double2)));
+        XFER(xfer_h2d(h, h->d_rot.p, rot, (size_t)nchains * BLK * sizeof(double2)));
+    }
     // matrix-core set without hoh: vector 1 (pmn of the VALU set, h psi of the hoh passes) is not used by the u-scheme -- it is neither allocated
     // nor cleared (32 GB and a 5 ms memset per call for 64 sites of the 10^5-atom cell).  Of vector 2, H psi, only the zero block kk is
     // cleared: the SpMM writes every atom the passes behind it read, but those passes run padding entries of the lists as the zero block,
@@ -1369,7 +1411,7 @@ int run_block_lanczos(rsrec_t* h, int nchains, int nseed, const int32_t* seed_at
     const size_t cstride = (size_t)lld * BLK;
     const size_t orth_lds = TILE_ATOMS * BLK * sizeof(double2);
     hipEvent_t ev_begin = next_event(h);
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> hop_ev;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> hop_ev, rot_ev;
     h->hop_fuses_a = MFMA ? 0 : 1;
 
     for (int c0 = 0; c0 < nchains; c0 += B) {
@@ -1571,6 +1613,14 @@ int run_block_lanczos(rsrec_t* h, int nchains, int nseed, const int32_t* seed_at
             HIPCK(h, hipGraphLaunch(h->graph_exec, h->stream));
             h->n_hop_launch += (double)nsteps * (hoh ? 2 : 1);
         }
+        if (rot && lld > 1) {
+            // local-axis runs: A' = R^H A R, B'^2 = R^H B^2 R on the resident copy, which is then what the caller gets back and what the
+            // stages on resident chains read -- one set of bits (get_terminf is a chain of bisections)
+            hipEvent_t r0 = next_event(h);
+            k_rotate_coef<<<dim3(2 * (lld - 1), nb), 256, 0, h->stream>>>(dA, dB, h->d_rot.as<double2>() + (size_t)c0 * BLK, lld);
+            HIPCK(h, hipGetLastError());
+            rot_ev.emplace_back(r0, next_event(h));
+        }
         XFER(xfer_d2h(h, a_b + (size_t)c0 * cstride * 2, dA, (size_t)nb * cstride * sizeof(double2)));
         XFER(xfer_d2h(h, b2_b + (size_t)c0 * cstride * 2, dB, (size_t)nb * cstride * sizeof(double2)));
         HIPCK(h, hipStreamSynchronize(h->stream));
@@ -1578,6 +1628,7 @@ int run_block_lanczos(rsrec_t* h, int nchains, int nseed, const int32_t* seed_at
     hipEvent_t ev_end = next_event(h);
     rc = finish_status(h);
     finish_timing(h, ev_begin, ev_end, hop_ev);
+    for (auto& pr : rot_ev) h->t_rot_ms += ev_ms(pr.first, pr.second);
     if (rc) return rc;
     h->res_kind = 1; h->res_n = nchains; h->res_lld = lld; h->res_seeded = seed_coef != nullptr;
     return RSREC_OK;
@@ -1644,7 +1695,10 @@ int build_local_axis_operator(rsrec_t* h) {
 // chain of H'_i from the seed 1 is the chain of  H''_i = H + onsite(R_i l.s R_i^H - l.s)  from the seed R_i, i.e. from the seed 1
 // followed by a right-multiplication with the unitary R_i:   A'_n = R_i^H A''_n R_i,  B'^2_n = R_i^H B''^2_n R_i.
 // So every chain runs on the SAME global-frame blocks and differs only in its on-site term (per-chain extra slot of k_spmm5); the
-// 18x18 outputs are conjugated on the host.  Checked against the compiled reference on four sites with four moment directions.
+// 18x18 coefficients are conjugated where they lie on the device (k_rotate_coef) before they are downloaded: the returned arrays and the
+// resident chains are one set of bits, in each site's local frame.  The continued fraction, zsqr, get_terminf and the epilogues are covariant
+// under the transform, so rsrec_block_ldos / _spectra / rsrec_contour_occupation / rsrec_pack_diag follow as after rsrec_block_lanczos.
+// Checked against the compiled reference on four sites with four moment directions.
 extern "C" int rsrec_block_lanczos_local_axis(rsrec_t* h, int nsites, const int32_t* seed_atoms, const double* rot, int lld, double* a_b, double* b2_b) {
     int rc = check_ready(h, "rsrec_block_lanczos_local_axis");
     if (rc) return rc;
@@ -1655,39 +1709,8 @@ extern "C" int rsrec_block_lanczos_local_axis(rsrec_t* h, int nsites, const int3
     reset_timing(h);
     if (nsites == 0) return RSREC_OK;
     rc = build_local_axis_operator(h); if (rc) return rc;
-    rc = run_block_lanczos<LayoutRM, true>(h, nsites, 1, seed_atoms, nullptr, lld, a_b, b2_b, rot);
-    if (rc) return rc;
-    // A' = R^H A R, B'^2 = R^H B^2 R; b2_b(:,:,1) = I and a_b(:,:,lld) = 0 stay exact (recursion.f90:1836-1837)
-    std::vector<double> T(2 * BLK);
-    auto conj_sim = [&](double* M, const double* R) {
-        for (int j = 0; j < NB; ++j)
-            for (int i = 0; i < NB; ++i) {
-                double sr = 0.0, si = 0.0;
-                for (int k = 0; k < NB; ++k) {
-                    const double ar = M[2 * (i + NB * k)], ai = M[2 * (i + NB * k) + 1], br = R[2 * (k + NB * j)], bi = R[2 * (k + NB * j) + 1];
-                    sr += ar * br - ai * bi; si += ar * bi + ai * br;
-                }
-                T[2 * (i + NB * j)] = sr; T[2 * (i + NB * j) + 1] = si;
-            }
-        for (int j = 0; j < NB; ++j)
-            for (int i = 0; i < NB; ++i) {
-                double sr = 0.0, si = 0.0;
-                for (int k = 0; k < NB; ++k) {
-                    const double ar = R[2 * (k + NB * i)], ai = -R[2 * (k + NB * i) + 1], br = T[2 * (k + NB * j)], bi = T[2 * (k + NB * j) + 1];
-                    sr += ar * br - ai * bi; si += ar * bi + ai * br;
-                }
-                M[2 * (i + NB * j)] = sr; M[2 * (i + NB * j) + 1] = si;
-            }
-    };
-    for (int s = 0; s < nsites; ++s) {
-        const double* R = rot + 2 * (size_t)BLK * s;
-        for (int ll = 0; ll < lld; ++ll) {
-            if (ll < lld - 1) conj_sim(a_b + 2 * (size_t)BLK * ((size_t)s * lld + ll), R);
-            if (ll > 0) conj_sim(b2_b + 2 * (size_t)BLK * ((size_t)s * lld + ll), R);
-        }
-    }
-    h->res_kind = 0;          // the resident coefficients are the un-rotated ones: not valid input for the LDOS stage
-    return RSREC_OK;
+    // the chains stay resident in each site's frame (res_kind = 1): the stages on resident chains take them as they take rsrec_block_lanczos'
+    return run_block_lanczos<LayoutRM, true>(h, nsites, 1, seed_atoms, nullptr, lld, a_b, b2_b, rot);
 }
 
 namespace {

@@ -129,10 +129,10 @@ class Recursion:
 
 
     def timing(self):
-        out = (C.c_double * 12)()
-        self._L.rsrec_get_timing(self._h, out, 12)
+        out = (C.c_double * 13)()
+        self._L.rsrec_get_timing(self._h, out, 13)
         keys = ("total_ms", "hop_ms", "hop_launches", "atom_steps", "block_multiplies", "rest_ms", "host_ms", "hop_fuses_a", "hop_mfma_flop", "hop_required_flop",
-                "operator_arrays_from_device", "octet_launches")
+                "operator_arrays_from_device", "octet_launches", "rotate_ms")
         return dict(zip(keys, list(out)))
 
     # -- state (restore_to_default, recursion.f90:3713-3825) --------------------------------------------
@@ -222,7 +222,10 @@ class Recursion:
 
     def recur_b_local_axis(self, rot):
         """recur_b with hamiltonian%local_axis = T (recursion.f90:1830-1832): the Hamiltonian object holds the GLOBAL-frame blocks
-        (ee_glob, ...), ``rot`` (18,18,nrec) the spin-frame rotation of every site; all sites go in one batched call."""
+        (ee_glob, ...), ``rot`` (18,18,nrec) the spin-frame rotation of every site; all sites go in one batched call.  The coefficients
+        are conjugated with the rotations on the device and the chains stay resident there in each site's local frame, the same bits as
+        ``a_b`` / ``b2_b``: ``Green.block_ldos()``, ``Green.block_spectra()``, ``Green.contour_occupation(resident=True)`` and
+        ``pack_diag()`` follow as after ``recur_b``."""
         lld = self.control.lld
         start, end, seeds = self._my_sites()
         n = len(seeds)
