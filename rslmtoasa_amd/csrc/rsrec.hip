@@ -136,7 +136,7 @@ struct rsrec_handle {
     long opt_s5_waves = 8;
     long opt_sat_pct = 100;      // a chain whose region holds at least this share (per cent) of the lattice runs on the list of ALL atoms (blocks outside the region are zero); rounds 1-3: 80 -- with a position-sorted list per level the superset no longer buys locality and costs its extra atoms (46^3: -1 %)
     long opt_orth_oop = 1;       // 1 = k_mfma_orth3 writes u_{n+1} into a third u vector instead of over u_{n-1} (faster on the HBM; one more work vector)
-    long opt_s5_split = 0;       // persistent k_spmm5: 3 = a wave takes a third of a group's tiles (k_spmm5<., true, false, 3>; s5_waves = 8 / 12 / 16 waves per CU then)
+    long opt_s5_split = 0;       // persistent k_spmm5: 3 = a wave takes a third of a group's tiles (k_spmm5<., true, false, 3>; s5_waves = 8 .. 12 waves per CU then, clamped to the 768 threads of its launch bounds)
     long opt_s5_run_min = 0;     // operators with several classes: smallest class run (in groups) that gets an LDS launch of its own (0: by launch size)
     long opt_s5_spin_xcd = 0;    // persistent k_spmm5 on collinear operators: 1 = even XCDs serve output spin 0, odd XCDs spin 1; 0 = both spins on every XCD
     long opt_s5_octet = 8;       // atoms with their own operator blocks (nmax) from which their groups are formed over 8 CHAINS instead of one atom + 7 padding tiles (0: never; round 3: 64; B2FeCo, nmax = 15: 2.38 -> 2.34 ms per launch)
@@ -1059,12 +1059,14 @@ void finish_timing(rsrec_t* h, hipEvent_t ev_begin, hipEvent_t ev_end, const std
     h->t_rest_ms = h->t_total_ms - h->t_hop_ms;
 }
 
-// end of a call whose kernels report through the status word (cleared when the call began): the word, the stream, the eigen-solver's failure
+// end of a call whose kernels report through the status word (cleared when the call began): the word, the stream, the eigen-solver's
+// failure (bit 1) or the Chebyshev moments' divergence (bit 2)
 int finish_status(rsrec_t* h) {
     int status = 0;
     XFER(xfer_d2h(h, &status, h->d_status.p, 4));
     HIPCK(h, hipStreamSynchronize(h->stream));
     if (status & 1) return fail(h, RSREC_ERR_EIG, "Diagonalization error (18x18 Jacobi did not converge)");
+    if (status & 2) return fail(h, RSREC_ERR_DIVERGED, "Chebyshev moments did not converge. Check energy limits energy_min and energy_max");
     return RSREC_OK;
 }
 
@@ -1341,28 +1343,244 @@ __global__ __launch_bounds__(256) void k_rotate_coef(double2* __restrict__ A, do
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// What run_block_lanczos and run_chebyshev share, as the pair calls share PairCall and the on-site stages SiteStage: the call's decisions and
+// reservations (RecursionCall), a batch's uploads (RecursionBatch), the matrix-core H|psi> step (apply_h), SideReduce and replay_level_loop.
+struct RecursionCall {
+    bool mfma = false, side = false;     // kernel set; the side stream takes the levels' reductions
+    int nchains = 0, nseed = 1, napply = 0, nlev = 0;   // napply: applications of H per chain; nlev: levels of its region lists
+    const double* rot = nullptr;         // local-axis runs: complex (18,18,nchains), the spin-frame rotation of every chain
+    const Spmm5Operator* op = nullptr;   // what k_spmm5 applies (local-axis runs: H without the on-site l.s term)
+    int ci = 0;                          // 1: CI vectors and k_spmm5; 0: LayoutRM with k_spmm4, or LayoutCM with the VALU set
+    size_t velems = 0;                   // doubles per chain per vector (+1: the all-zero block)
+    int nvec = 0, skip_vec = -1, B = 1, nblk = 1;   // (recursion_begin) work vectors -- skip_vec is neither allocated nor cleared --, batch, workgroups
+    DevProblem P;
+    hipEvent_t ev_begin = nullptr;       // start of the timed span
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> hop_ev, rot_ev;   // H|psi> of every step; k_rotate_coef of every batch
+};
+
+// Matrix-core set: k_spmm5 with every vector in the CI layout (option spmm5 = 2, the default since round 3: with the operator
+// streams assembled on the device a call no longer pays k_spmm4's host swizzle -- 3 ms per SCF iteration on the 18 operator classes
+// of B2FeCo, tools/time_set_hamiltonian.py -- and k_spmm5 is as fast on one chain).  spmm5 = 1: small launches of the plain operator
+// take the cooperative k_spmm4<4> on LayoutRM (kept as the cross-check of the parity tests); 0: k_spmm4 whenever it can.  hoh and
+// local-axis (rot) calls always take k_spmm5.
+RecursionCall recursion_call(const rsrec_t* h, bool mfma, int nchains, int nseed, int napply, const double* rot = nullptr) {
+    RecursionCall RC;
+    RC.mfma = mfma; RC.nchains = nchains; RC.nseed = nseed; RC.napply = napply; RC.rot = rot;
+    RC.nlev = (h->hoh ? 2 * napply : napply) + 1; RC.op = rot ? &h->s5_la : &h->s5_op; RC.velems = (size_t)(h->kk + 1) * BLD;
+    const bool large = (long)std::min(nchains, 64) * (h->kk / GROUP + 1) >= 4096;
+    RC.ci = (mfma && (h->hoh || rot || h->opt_spmm5 == 2 || (h->opt_spmm5 == 1 && large) || !spmm4_usable(h))) ? 1 : 0;
+    return RC;
+}
+
+// Plans the batches and reserves what every recursion needs: `nvec` work vectors (all but `skip_vec`), the partials, the seeds with `coef_slots`
+// coefficients per chain, the status word (cleared here), the side stream; opens the timed span.  The caller reserves its resident outputs BEFORE it.
+int recursion_begin(rsrec_t* h, RecursionCall& RC, int nvec, int skip_vec, int coef_slots) {
+    if (RC.mfma && !RC.ci) XFER(ensure_s4(h));
+    RC.nvec = nvec; RC.skip_vec = skip_vec;
+    BatchPlan bp;
+    XFER(plan_batch(h, RC.nchains, nvec - (skip_vec >= 0 ? 1 : 0), RC.velems / 2, bp));
+    const int B = RC.B = bp.batch; RC.nblk = bp.nblk;
+    for (int v = 0; v < nvec; ++v) if (v != skip_vec) HIPCK(h, h->d_vec[v].reserve((size_t)B * RC.velems * sizeof(double)));
+    // first stage: two Gram partials (1296 doubles) of up to 256 workgroups per chain; the VALU set's 2 nblk <= 512 partials are as large
+    XFER(reserve_partials(h, B, (size_t)B * 256 * 2 * 1296 * sizeof(double)));
+    XFER(ensure_side_stream(h));
+    RC.side = h->opt_side && h->side_stream;
+    if (RC.rot) HIPCK(h, h->d_la_extra.reserve((size_t)B * (h->nmax + h->ntype) * S5_HEAD_DOUBLES * sizeof(double)));
+    HIPCK(h, h->d_status.reserve(64));
+    HIPCK(h, h->d_seed.reserve((size_t)B * RC.nseed * 4));
+    HIPCK(h, h->d_seedcoef.reserve((size_t)B * coef_slots * sizeof(double2)));
+    HIPCK(h, hipMemsetAsync(h->d_status.p, 0, 64, h->stream));
+    RC.P = make_problem(h); RC.ev_begin = next_event(h);
+    return RSREC_OK;
+}
+
+// local-axis runs: the on-site term of chains c0 .. c0 + nb - 1 in the GLOBAL frame, (e_nu +) R l.s R^H, as k_spmm5's stream heads (see rsrec_block_lanczos_local_axis)
+void local_axis_fragments(const rsrec_t* h, const Spmm5Operator& OP, const double* rot, int c0, int nb, std::vector<double>& fr) {
+    const bool hoh = h->hoh != 0;
+    const int ntau = h->nmax + h->ntype, la_fps = S5_HEAD_DOUBLES;
+    std::vector<double> E(2 * BLK), T(2 * BLK); fr.assign((size_t)nb * ntau * la_fps, 0.0);
+    for (int c = 0; c < nb; ++c) {
+        const double* R = rot + 2 * (size_t)BLK * (c0 + c);
+        for (int tau = 0; tau < ntau; ++tau) {
+            const int ty = tau < h->nmax ? h->iz0[tau] : tau - h->nmax;
+            const double* ls = h->host_lsham.data() + 2 * (size_t)BLK * ty;
+            for (int j = 0; j < NB; ++j)                    // T = l.s R^H
+                for (int i = 0; i < NB; ++i) {
+                    double sr = 0.0, si = 0.0;
+                    for (int k = 0; k < NB; ++k) {
+                        const double ar = ls[2 * (i + NB * k)], ai = ls[2 * (i + NB * k) + 1], br = R[2 * (j + NB * k)], bi = -R[2 * (j + NB * k) + 1];
+                        sr += ar * br - ai * bi; si += ar * bi + ai * br;
+                    }
+                    T[2 * (i + NB * j)] = sr; T[2 * (i + NB * j) + 1] = si;
+                }
+            for (int j = 0; j < NB; ++j)                    // E = R T
+                for (int i = 0; i < NB; ++i) {
+                    double sr = 0.0, si = 0.0;
+                    for (int k = 0; k < NB; ++k) {
+                        const double ar = R[2 * (i + NB * k)], ai = R[2 * (i + NB * k) + 1], br = T[2 * (k + NB * j)], bi = T[2 * (k + NB * j) + 1];
+                        sr += ar * br - ai * bi; si += ar * bi + ai * br;
+                    }
+                    E[2 * (i + NB * j)] = sr; E[2 * (i + NB * j) + 1] = si;
+                }
+            if (hoh) for (int e = 0; e < 2 * BLK; ++e) E[e] += h->host_enim[2 * (size_t)BLK * ty + e];
+            OP.emit_head(hoh ? 1 : 0, tau, E.data(), fr.data() + ((size_t)c * ntau + tau) * la_fps);
+        }
+    }
+}
+
+struct RecursionBatch {                  // what the level loop of one batch works on
+    int nb = 0, ostride = 0;
+    ChainView CV, CVp;                   // CVp: the streaming passes walk the level-major lists (upload_regions)
+    dim3 grid_mf;                        // launch of the matrix-core passes: workgroups per chain x chains
+    const double* la_extra = nullptr;    // local-axis runs: the chains' on-site fragments (d_la_extra)
+};
+// Per-batch prologue of chains c0 .. c0 + nb - 1: seeds, regions (cached) and, in a local-axis run, the on-site fragments go to the device;
+// returns when they are there.  `extra_coef` may append to the staged coefficients before they are uploaded.  All of it is host time.
+using SeedCoefHook = void (*)(int nb, int nseed, const std::vector<int>& seeds0, std::vector<double>& coef);
+int recursion_batch(rsrec_t* h, const RecursionCall& RC, const int32_t* seed_atoms, const double* seed_coef, int c0, int nb, RecursionBatch& b,
+                    SeedCoefHook extra_coef = nullptr) {
+    const auto th0 = std::chrono::steady_clock::now();
+    std::vector<int> seeds0;
+    std::vector<double> coef, fr;
+    stage_seeds(seed_atoms, seed_coef, c0, nb, RC.nseed, seeds0, coef);
+    if (extra_coef) extra_coef(nb, RC.nseed, seeds0, coef);
+    b.nb = nb; b.ostride = h->kk;
+    XFER(upload_regions(h, seeds0.data(), nb, RC.nseed, RC.nlev, RC.napply, h->hoh != 0, RC.mfma, b.ostride, h->n_atom_steps, h->n_block_mult));
+    h->n_req_flop += required_hop_flops(h, *RC.op);
+    XFER(xfer_h2d(h, h->d_seed.p, seeds0.data(), seeds0.size() * 4));
+    XFER(xfer_h2d(h, h->d_seedcoef.p, coef.data(), coef.size() * 8));
+    if (RC.rot) {
+        local_axis_fragments(h, *RC.op, RC.rot, c0, nb, fr);
+        XFER(xfer_h2d(h, h->d_la_extra.p, fr.data(), fr.size() * sizeof(double)));
+        b.la_extra = h->d_la_extra.as<double>();
+    }
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    h->t_host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - th0).count();
+    chain_views(h, RC.nlev, RC.velems, 1, b.ostride, b.CV, &b.CVp);
+    b.grid_mf = dim3(std::max(1, std::min(mfma_workgroups_per_chain(h, RC.B), (b.ostride / GROUP + MF_WAVES - 1) / MF_WAVES)), nb);
+    return RSREC_OK;
+}
+
+// clears the work vectors of a batch; of vector `zero_block_only` (-1: none) only the zero block kk (one 2-D memset over the chains)
+int clear_vectors(rsrec_t* h, const RecursionCall& RC, int nb, int zero_block_only = -1) {
+    for (int v = 0; v < RC.nvec; ++v) {
+        if (v == RC.skip_vec) continue;
+        if (v == zero_block_only)
+            HIPCK(h, hipMemset2DAsync(static_cast<char*>(h->d_vec[v].p) + (size_t)h->kk * BLD * sizeof(double), RC.velems * sizeof(double), 0, BLD * sizeof(double), (size_t)nb, h->stream));
+        else HIPCK(h, hipMemsetAsync(h->d_vec[v].p, 0, (size_t)nb * RC.velems * sizeof(double), h->stream));
+    }
+    return RSREC_OK;
+}
+// One H|psi> of the matrix-core set, dst = H src, as application `step` (1, 2, ...) of the batch's chains, between the events the call's hop
+// time is read from.  k_spmm5 on CI vectors: one launch, or with hoh two -- h src into `hps` on the lists of level 2 step - 1, then
+// H = h - (h o) h + e_nu + l.s with src as second input (extra on-site slot) on those of level 2 step.  `extra` / `ntau`: the per-chain on-site
+// fragments of a local-axis run (the single launch is then a two-input one as well).  Else the cooperative k_spmm4 on LayoutRM (plain operator).
+int apply_h(rsrec_t* h, RecursionCall& RC, const RecursionBatch& b, int step, const double* src, double* dst, double* hps, const double* extra, int ntau,
+            S5Epilogue epi = S5Epilogue()) {
+    const bool hoh = h->hoh != 0;
+    const int lv_final = hoh ? 2 * step : step;
+    const Spmm5Operator& OP = *RC.op; const DevProblem& P = RC.P; const ChainView& CV = b.CV;
+    hipEvent_t e0 = next_event(h);                   // [e0, e1] brackets exactly the H|psi> kernel(s) of this step
+    SpmmDims SD{h->kk, P.nslots, P.nmax, RC.nlev, 1, b.ostride, hoh ? 2 * step - 1 : lv_final, RC.velems, CV.obase, b.nb};
+    if (!RC.ci) XFER(launch_spmm(h, SD, CV, P, 0, src, dst, b.grid_mf));
+    else if (hoh) {
+        launch_s5<false>(h, s5_grid(h, b.grid_mf, 2 * step - 1), SD, CV.order, CV.cum, P.iz, OP, 0, src, hps);
+        SD.level = lv_final;
+        launch_s5<true>(h, s5_grid(h, b.grid_mf, lv_final), SD, CV.order, CV.cum, P.iz, OP, 1, hps, dst, src, extra, ntau, epi);
+    } else if (extra) launch_s5<true>(h, s5_grid(h, b.grid_mf, lv_final), SD, CV.order, CV.cum, P.iz, OP, 0, src, dst, src, extra, ntau, epi);
+    else launch_s5<false>(h, s5_grid(h, b.grid_mf, lv_final), SD, CV.order, CV.cum, P.iz, OP, 0, src, dst, nullptr, nullptr, 0, epi);
+    RC.hop_ev.emplace_back(e0, next_event(h)); h->n_hop_launch += hoh ? 2 : 1;
+    return RSREC_OK;
+}
+
+// the Chebyshev step as the epilogue of the launch that forms H cur:  out = (H cur - b cur)/a  [* 2 - old]
+S5Epilogue cheb_epilogue(bool first, const double* cur, const double* old, double a, double b) {
+    S5Epilogue E; E.kind = first ? 1 : 2; E.cur = cur; E.old = first ? nullptr : old; E.a = a; E.b = b;
+    return E;
+}
+// The side-stream hand-off of a level's reduction (partial sums -> coefficients), which the main stream's next H|psi> does not need: begin
+// gives the stream to reduce on -- with `side` the side stream, behind everything queued on the main stream so far --, end marks the
+// reduction's end there, and wait holds the main stream until then: before the first launch that reads its result or reuses its input.
+struct SideReduce { bool side = false, pending = false; };
+int side_reduce_begin(rsrec_t* h, const SideReduce& S, hipStream_t& st) {
+    st = S.side ? h->side_stream : h->stream;
+    if (S.side) { HIPCK(h, hipEventRecord(h->ev_orth, h->stream)); HIPCK(h, hipStreamWaitEvent(h->side_stream, h->ev_orth, 0)); }
+    return RSREC_OK;
+}
+int side_reduce_end(rsrec_t* h, SideReduce& S) { if (S.side) { HIPCK(h, hipEventRecord(h->ev_bred, h->side_stream)); S.pending = true; } return RSREC_OK; }
+int side_reduce_wait(rsrec_t* h, SideReduce& S) { if (S.pending) { HIPCK(h, hipStreamWaitEvent(h->stream, h->ev_bred, 0)); S.pending = false; } return RSREC_OK; }
+
+// Runs `enqueue` -- stream work only: kernels, memsets, cross-stream events -- as the handle's HIP graph: captured and instantiated when
+// `key` (everything the nodes hold by value) differs from that of the graph the handle keeps, replayed otherwise.  The level loop of a
+// small block-Lanczos batch is captured ONCE and replayed by every later call with the same lattice, seeds, depth and buffers (each SCF
+// iteration of the reference: recur_b on the same <= 4 sites) -- 49 levels x 6-8 dependent launches otherwise cost more host time than
+// device time (13 ms for one site of the 22^3 cell, two thirds of it launch latency).
+template <class Enqueue>
+int replay_level_loop(rsrec_t* h, const std::vector<uintptr_t>& key, Enqueue&& enqueue) {
+    if (!h->graph_exec || key != h->graph_key) {
+        if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
+        h->graph_key.clear();
+        s5_prepare(h);
+        XFER(s4_prepare(h));
+        HIPCK(h, hipStreamSynchronize(h->stream));
+        HIPCK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeRelaxed));
+        h->capturing = true;
+        const int rc = enqueue();
+        h->capturing = false;
+        hipGraph_t graph = nullptr;
+        const hipError_t ec = hipStreamEndCapture(h->stream, &graph);
+        if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+        if (ec != hipSuccess || !graph) return fail(h, RSREC_ERR_DEVICE, "hipStreamEndCapture failed: %s", hipGetErrorString(ec));
+        const hipError_t ei = hipGraphInstantiate(&h->graph_exec, graph, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(graph);
+        if (ei != hipSuccess) { h->graph_exec = nullptr; return fail(h, RSREC_ERR_DEVICE, "hipGraphInstantiate failed: %s", hipGetErrorString(ei)); }
+        h->graph_key = key;
+    }
+    HIPCK(h, hipGraphLaunch(h->graph_exec, h->stream));
+    return RSREC_OK;
+}
+
+// Local-axis runs: A' = R^H A R, B'^2 = R^H B^2 R on the resident copy of chains c0 .. c0 + nb - 1, which is then what the caller gets back
+// and what the stages on resident chains read -- one set of bits (get_terminf is a chain of bisections)
+int rotate_resident_coef(rsrec_t* h, RecursionCall& RC, double2* dA, double2* dB, int c0, int nb, int lld) {
+    hipEvent_t r0 = next_event(h);
+    k_rotate_coef<<<dim3(2 * (lld - 1), nb), 256, 0, h->stream>>>(dA, dB, h->d_rot.as<double2>() + (size_t)c0 * BLK, lld);
+    HIPCK(h, hipGetLastError());
+    RC.rot_ev.emplace_back(r0, next_event(h));
+    return RSREC_OK;
+}
+// End of a recursion: the status word and the timing; on success the chains' coefficients are the handle's resident ones (res_kind, see there)
+int recursion_end(rsrec_t* h, const RecursionCall& RC, int res_kind, int lld, bool seeded) {
+    hipEvent_t ev_end = next_event(h);
+    const int rc = finish_status(h);
+    finish_timing(h, RC.ev_begin, ev_end, RC.hop_ev);
+    for (auto& pr : RC.rot_ev) h->t_rot_ms += ev_ms(pr.first, pr.second);
+    if (rc) return rc;
+    h->res_kind = res_kind; h->res_n = RC.nchains; h->res_lld = lld; h->res_seeded = seeded;
+    return RSREC_OK;
+}
+
 // One implementation for both kernel sets: L = LayoutCM with the VALU kernels, LayoutRM with the MFMA SpMM.
+// Work vectors.  Matrix-core set without hoh: vector 1 (pmn of the VALU set, h psi of the hoh passes) is not used by the u-scheme -- it is neither allocated
+// nor cleared (32 GB and a 5 ms memset per call for 64 sites of the 10^5-atom cell).  Of vector 2, H psi, only the zero block kk is
+// cleared: the SpMM writes every atom the passes behind it read, but those passes run padding entries of the lists as the zero block,
+// which has to BE zero in every vector (left uncleared on recycled device memory, dying chains of the fuzz seeds survived:
+// tests/test_gpu_breakdown.py).  46^3 x 64 sites: 2 387 -> 2 361-2 381 ms per step.
+// u_{n+1} goes into a THIRD u vector instead of over u_{n-1} (option orth_oop, round 4): k_mfma_orth3 then reads three vectors and writes a
+// fourth one -- 64 x 46^3: 25.7 -> 24.5 ms per saturated level (the in-place pass alternated 26.3 / 25.0 with the level's parity, the out-of-place
+// one cycles 25.0 / 25.6 / 22.9 with the three arrangements of its buffers), the step 2 387 -> 2 361 ms, 22^3 387 -> 379 ms; bitwise the same results.
+// The vector is number 1 without hoh (unused by the u-scheme otherwise) and number 4 with hoh (vector 1 holds h psi of the first pass).
 template <class L, bool MFMA>
 int run_block_lanczos(rsrec_t* h, int nchains, int nseed, const int32_t* seed_atoms, const double* seed_coef, int lld, double* a_b, double* b2_b,
                       const double* rot = nullptr /*local-axis runs: complex (18,18,nchains), the spin-frame rotation of every chain*/) {
     const int kk = h->kk;
     const bool hoh = h->hoh != 0;
     const int nsteps = lld - 1;
-    const int nlev = (hoh ? 2 * nsteps : nsteps) + 1;
-    const size_t velems = (size_t)(kk + 1) * BLD;           // doubles per chain per vector (+1: the all-zero block)
-    int nvec = MFMA ? 4 : (hoh ? 3 : 2);
-    // Matrix-core set: k_spmm5 with every vector in the CI layout (option spmm5 = 2, the default since round 3: with the operator
-    // streams assembled on the device a call no longer pays k_spmm4's host swizzle -- 3 ms per SCF iteration on the 18 operator classes
-    // of B2FeCo, tools/time_set_hamiltonian.py -- and k_spmm5 is as fast on one chain).  spmm5 = 1: small launches of the plain operator
-    // take the cooperative k_spmm4<4> on LayoutRM (kept as the cross-check of the parity tests); 0: k_spmm4 whenever it can
-    const bool large = (long)std::min(nchains, 64) * (kk / GROUP + 1) >= 4096;
-    const int ci = (MFMA && (hoh || rot || h->opt_spmm5 == 2 || (h->opt_spmm5 == 1 && large) || !spmm4_usable(h))) ? 1 : 0;   // vectors of this call are CI (else LayoutRM / LayoutCM)
     if (rot && !MFMA) return fail(h, RSREC_ERR_ARG, "local-axis recursion needs the matrix-core kernel set (option kernels = 0 or 2)");
-    if (MFMA && !ci) { const int rc4 = ensure_s4(h); if (rc4) return rc4; }
-    const int ntau = h->nmax + h->ntype;
-    const Spmm5Operator& OP = rot ? h->s5_la : h->s5_op;
-    const int la_fps = S5_HEAD_DOUBLES;
-    if (rot) HIPCK(h, h->d_la_extra.reserve((size_t)std::min(nchains, 64) * ntau * la_fps * sizeof(double)));
+    RecursionCall RC = recursion_call(h, MFMA, nchains, nseed, nsteps, rot);
+    const int ci = RC.ci, ntau = h->nmax + h->ntype;
+    const size_t velems = RC.velems, cstride = (size_t)lld * BLK, orth_lds = TILE_ATOMS * BLK * sizeof(double2);
     // the coefficients of ALL chains of the call stay on the device (resident input of rsrec_pack_diag / rsrec_block_ldos): reserved before
     // the batch is planned from the free memory
     h->res_kind = 0;
@@ -1372,215 +1590,95 @@ int run_block_lanczos(rsrec_t* h, int nchains, int nseed, const int32_t* seed_at
         HIPCK(h, h->d_rot.reserve((size_t)nchains * BLK * sizeof(double2)));
         XFER(xfer_h2d(h, h->d_rot.p, rot, (size_t)nchains * BLK * sizeof(double2)));
     }
-    // matrix-core set without hoh: vector 1 (pmn of the VALU set, h psi of the hoh passes) is not used by the u-scheme -- it is neither allocated
-    // nor cleared (32 GB and a 5 ms memset per call for 64 sites of the 10^5-atom cell).  Of vector 2, H psi, only the zero block kk is
-    // cleared: the SpMM writes every atom the passes behind it read, but those passes run padding entries of the lists as the zero block,
-    // which has to BE zero in every vector (left uncleared on recycled device memory, dying chains of the fuzz seeds survived:
-    // tests/test_gpu_breakdown.py).  46^3 x 64 sites: 2 387 -> 2 361-2 381 ms per step.
-    // u_{n+1} goes into a THIRD u vector instead of over u_{n-1} (option orth_oop, round 4): k_mfma_orth3 then reads three vectors and writes a
-    // fourth one -- 64 x 46^3: 25.7 -> 24.5 ms per saturated level (the in-place pass alternated 26.3 / 25.0 with the level's parity, the out-of-place
-    // one cycles 25.0 / 25.6 / 22.9 with the three arrangements of its buffers), the step 2 387 -> 2 361 ms, 22^3 387 -> 379 ms; bitwise the same results.
-    // The vector is number 1 without hoh (unused by the u-scheme otherwise) and number 4 with hoh (vector 1 holds h psi of the first pass).
     const bool oop = MFMA && h->opt_orth_oop != 0 && h->opt_orth3 != 2;
-    if (oop && hoh) nvec = 5;
+    const int nvec = MFMA ? (oop && hoh ? 5 : 4) : (hoh ? 3 : 2);
     const bool use_v1 = !MFMA || hoh || oop;
-    BatchPlan bp;
-    int rc = plan_batch(h, nchains, nvec - (use_v1 ? 0 : 1), velems / 2, bp);
-    if (rc) return rc;
-    const int B = bp.batch, nblk = bp.nblk;
-    for (int v = 0; v < nvec; ++v) if (v != 1 || use_v1) HIPCK(h, h->d_vec[v].reserve((size_t)B * velems * sizeof(double)));
-    const size_t gram_elems = (size_t)B * 256 * 1296;                                  // doubles: Gram partials of one kernel (<= 256 workgroups per chain)
-    XFER(reserve_partials(h, B, std::max((size_t)B * std::max(nblk * 2, 256) * 2 * BLK * sizeof(double2), 2 * gram_elems * sizeof(double))));
-    XFER(ensure_side_stream(h));
+    XFER(recursion_begin(h, RC, nvec, use_v1 ? -1 : 1, nseed));
+    const int B = RC.B, nblk = RC.nblk;
     HIPCK(h, h->d_frags.reserve((size_t)B * 3 * 27 * 64 * sizeof(double)));
     HIPCK(h, h->d_bmats.reserve((size_t)B * 2 * BLK * sizeof(double2)));
-    HIPCK(h, h->d_status.reserve(64));
-    HIPCK(h, h->d_seed.reserve((size_t)B * nseed * 4));
-    HIPCK(h, h->d_seedcoef.reserve((size_t)B * nseed * sizeof(double2)));
-    HIPCK(h, hipMemsetAsync(h->d_status.p, 0, 64, h->stream));
-    double* psi = h->d_vec[0].as<double>();
-    double* pmn = h->d_vec[1].as<double>();
-    double* hpsi = h->d_vec[2].as<double>();
-    double* t2 = h->d_vec[3].as<double>();
+    const size_t gram_elems = (size_t)B * 256 * 1296;    // doubles: Gram partials of one kernel (<= 256 workgroups per chain)
+    double *pmn = h->d_vec[1].as<double>(), *hpsi = h->d_vec[2].as<double>();
     double2* partial = h->d_partial.as<double2>();
-    double* gpartial = h->d_partial.as<double>();
-    double* gpartial_b = gpartial + gram_elems;          // Gram partials of k_mfma_orth3 when their reduction runs on the side stream
-    double* bfrags = h->d_frags.as<double>();            // [chain][3][27 * 64]: the three right-multiply tables of k_mfma_orth3
-    const DevProblem P = make_problem(h);
+    double *gpartial = h->d_partial.as<double>(), *bfrags = h->d_frags.as<double>();   // bfrags [chain][3][27 * 64]: the three right-multiply tables of k_mfma_orth3
     HIPCK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_orth<L>), hipFuncAttributeMaxDynamicSharedMemorySize, TILE_ATOMS * BLK * (int)sizeof(double2)));
-    const size_t cstride = (size_t)lld * BLK;
-    const size_t orth_lds = TILE_ATOMS * BLK * sizeof(double2);
-    hipEvent_t ev_begin = next_event(h);
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> hop_ev, rot_ev;
     h->hop_fuses_a = MFMA ? 0 : 1;
 
     for (int c0 = 0; c0 < nchains; c0 += B) {
         const int nb = std::min(B, nchains - c0);
         double2* dA = h->d_coefA.as<double2>() + (size_t)c0 * cstride;       // this batch's slice of the resident coefficients
         double2* dB = h->d_coefB.as<double2>() + (size_t)c0 * cstride;
-        const auto th0 = std::chrono::steady_clock::now();
-        std::vector<int> seeds0;
-        std::vector<double> coef;
-        stage_seeds(seed_atoms, seed_coef, c0, nb, nseed, seeds0, coef);
-        int ostride = kk;
-        rc = upload_regions(h, seeds0.data(), nb, nseed, nlev, nsteps, hoh, MFMA, ostride, h->n_atom_steps, h->n_block_mult);
-        if (rc) return rc;
-        h->n_req_flop += required_hop_flops(h, OP);
-        XFER(xfer_h2d(h, h->d_seed.p, seeds0.data(), seeds0.size() * 4));
-        XFER(xfer_h2d(h, h->d_seedcoef.p, coef.data(), coef.size() * 8));
-        const double* la_extra = nullptr;
-        if (rot) {
-            // per-chain on-site term of the local-axis operator in the GLOBAL frame: (e_nu +) R l.s R^H  (see rsrec_block_lanczos_local_axis)
-            std::vector<double> fr((size_t)nb * ntau * la_fps), E(2 * BLK), T(2 * BLK);
-            for (int c = 0; c < nb; ++c) {
-                const double* R = rot + 2 * (size_t)BLK * (c0 + c);
-                for (int tau = 0; tau < ntau; ++tau) {
-                    const int ty = tau < h->nmax ? h->iz0[tau] : tau - h->nmax;
-                    const double* ls = h->host_lsham.data() + 2 * (size_t)BLK * ty;
-                    for (int j = 0; j < NB; ++j)                    // T = l.s R^H
-                        for (int i = 0; i < NB; ++i) {
-                            double sr = 0.0, si = 0.0;
-                            for (int k = 0; k < NB; ++k) {
-                                const double ar = ls[2 * (i + NB * k)], ai = ls[2 * (i + NB * k) + 1], br = R[2 * (j + NB * k)], bi = -R[2 * (j + NB * k) + 1];
-                                sr += ar * br - ai * bi; si += ar * bi + ai * br;
-                            }
-                            T[2 * (i + NB * j)] = sr; T[2 * (i + NB * j) + 1] = si;
-                        }
-                    for (int j = 0; j < NB; ++j)                    // E = R T
-                        for (int i = 0; i < NB; ++i) {
-                            double sr = 0.0, si = 0.0;
-                            for (int k = 0; k < NB; ++k) {
-                                const double ar = R[2 * (i + NB * k)], ai = R[2 * (i + NB * k) + 1], br = T[2 * (k + NB * j)], bi = T[2 * (k + NB * j) + 1];
-                                sr += ar * br - ai * bi; si += ar * bi + ai * br;
-                            }
-                            E[2 * (i + NB * j)] = sr; E[2 * (i + NB * j) + 1] = si;
-                        }
-                    if (hoh) for (int e = 0; e < 2 * BLK; ++e) E[e] += h->host_enim[2 * (size_t)BLK * ty + e];
-                    OP.emit_head(hoh ? 1 : 0, tau, E.data(), fr.data() + ((size_t)c * ntau + tau) * la_fps);
-                }
-            }
-            XFER(xfer_h2d(h, h->d_la_extra.p, fr.data(), fr.size() * sizeof(double)));
-            la_extra = h->d_la_extra.as<double>();
-        }
-        HIPCK(h, hipStreamSynchronize(h->stream));
-        h->t_host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - th0).count();
-
-        ChainView CV, CVp;                                    // CVp: the streaming passes walk the level-major lists (upload_regions)
-        chain_views(h, nlev, velems, 1, ostride, CV, &CVp);
-        // Everything from here to the coefficients' download is stream work only (kernels, memsets, cross-stream events): for small
-        // batches it is captured ONCE as a HIP graph and replayed by every later call with the same lattice, seeds, depth and buffers
-        // (each SCF iteration of the reference: recur_b on the same <= 4 sites) -- 49 levels x 6-8 dependent launches otherwise cost
-        // more host time than device time (13 ms for one site of the 22^3 cell, two thirds of it launch latency).
+        RecursionBatch bt;
+        XFER(recursion_batch(h, RC, seed_atoms, seed_coef, c0, nb, bt));
+        const ChainView &CV = bt.CV, &CVp = bt.CVp;
+        // everything from here to the coefficients' download is stream work only: small batches replay it as a HIP graph
         auto enqueue_levels = [&]() -> int {
-            for (int v = 0; v < nvec; ++v) {
-                if (v == 1 && !use_v1) continue;
-                if (v == 2 && MFMA && !hoh) {
-                    // H psi: only its zero block (one 2-D memset over the chains); every other block is written by the SpMM before it is read
-                    HIPCK(h, hipMemset2DAsync(static_cast<char*>(h->d_vec[v].p) + (size_t)kk * BLD * sizeof(double), velems * sizeof(double), 0, BLD * sizeof(double), (size_t)nb, h->stream));
-                    continue;
-                }
-                HIPCK(h, hipMemsetAsync(h->d_vec[v].p, 0, (size_t)nb * velems * sizeof(double), h->stream));
-            }
+            XFER(clear_vectors(h, RC, nb, MFMA && !hoh ? 2 : -1));
             HIPCK(h, hipMemsetAsync(dA, 0, (size_t)nb * cstride * sizeof(double2), h->stream));
             HIPCK(h, hipMemsetAsync(dB, 0, (size_t)nb * cstride * sizeof(double2), h->stream));
             if (MFMA) HIPCK(h, hipMemsetAsync(bfrags, 0, (size_t)nb * 3 * 27 * 64 * sizeof(double), h->stream));
-            psi = h->d_vec[0].as<double>(); t2 = h->d_vec[3].as<double>();   // (swapped every level)
+            double *psi = h->d_vec[0].as<double>(), *t2 = h->d_vec[3].as<double>();   // (swapped every level)
             double* t3 = oop ? h->d_vec[hoh ? 4 : 1].as<double>() : nullptr;
             if (ci) k_seed<LayoutCI><<<nb, 64, 0, h->stream>>>(psi, velems, h->d_seed.as<int>(), h->d_seedcoef.as<double2>(), nseed);
             else k_seed<L><<<nb, 64, 0, h->stream>>>(psi, velems, h->d_seed.as<int>(), h->d_seedcoef.as<double2>(), nseed);
             k_set_identity<<<nb, 256, 0, h->stream>>>(dB, cstride);                                  // b2temp_b(:,:,1) = I  (:1837)
             if (MFMA) k_uscheme_init<<<nb, 256, 0, h->stream>>>(h->d_bmats.as<double2>(), bfrags, ci);
             const dim3 grid(nblk, nb);
-            const dim3 grid_mf(std::max(1, std::min(mfma_workgroups_per_chain(h, B), (ostride / GROUP + MF_WAVES - 1) / MF_WAVES)), nb);
             // u-scheme: H u_{n+1} does not need B_{n+1}, so the reduction of sum u_{n+1}^H u_{n+1} and its 18x18 eigen-solve (one
             // workgroup per chain, 80 us) leave the critical path: they run on the side stream while the main stream already applies H.
             // The main stream waits for them before k_reduce_a_u of the next level (first consumer of Binv_{n+1}).
-            const bool side = h->opt_side && h->side_stream;
-            double* gp_b = side ? gpartial_b : gpartial;
-            bool b_pending = false;
-            auto wait_b_level = [&]() -> int {
-                if (b_pending) { HIPCK(h, hipStreamWaitEvent(h->stream, h->ev_bred, 0)); b_pending = false; }
-                return RSREC_OK;
-            };
-            auto reduce_b_level = [&](int nwg, int ll) -> int {
-                hipStream_t st = h->stream;
-                if (side) {
-                    HIPCK(h, hipEventRecord(h->ev_orth, h->stream));
-                    HIPCK(h, hipStreamWaitEvent(h->side_stream, h->ev_orth, 0));
-                    st = h->side_stream;
-                }
-                int n2 = nwg;
-                const double* p2 = presum(h, gp_b, nb, n2, 1296, st, side ? 1 : 0);
-                k_reduce_b_u<<<nb, 1024, 0, st>>>(p2, n2, dB + (size_t)(ll + 1) * BLK, cstride, h->d_bmats.as<double2>(), bfrags, h->d_status.as<int>(), ci);
-                if (side) { HIPCK(h, hipEventRecord(h->ev_bred, h->side_stream)); b_pending = true; }
-                return RSREC_OK;
-            };
+            SideReduce SR{RC.side};
+            double* gp_b = SR.side ? gpartial + gram_elems : gpartial;   // Gram partials of k_mfma_orth3: their own when the side stream reduces them
             for (int ll = 0; ll < nsteps; ++ll) {
                 const int lv_final = hoh ? 2 * ll + 2 : ll + 1;
-                const double* tvec = nullptr;                      // H psi when it is held in a vector of its own
-                hipEvent_t e0 = next_event(h);
-                hipEvent_t e1 = nullptr;
-                ApplyArgs G{};
-                G.partial = partial;
                 if (MFMA) {
                     // matrix-core kernel set, un-normalised vectors (kernels_uscheme.hpp): psi = u_n, t2 = u_{n-1}; u_{n+1} overwrites u_{n-1}
-                    SpmmDims SD{kk, P.nslots, P.nmax, nlev, 1, ostride, hoh ? 2 * ll + 1 : lv_final, velems, CV.obase, nb};
-                    if (!hoh) {
-                        if (ci && rot) launch_s5<true>(h, s5_grid(h, grid_mf, lv_final), SD, CV.order, CV.cum, P.iz, OP, 0, psi, hpsi, psi, la_extra, ntau);
-                        else if (ci) launch_s5<false>(h, s5_grid(h, grid_mf, lv_final), SD, CV.order, CV.cum, P.iz, OP, 0, psi, hpsi);
-                        else { rc = launch_spmm(h, SD, CV, P, 0, psi, hpsi, grid_mf); if (rc) return rc; }
-                    } else {
-                        // H = h - (h o) h + e_nu + l.s in two passes of k_spmm5: h psi, then the rest with psi as second input (extra on-site slot)
-                        double* hps = pmn;                   // (the pmn buffer is free in the u-scheme)
-                        launch_s5<false>(h, s5_grid(h, grid_mf, 2 * ll + 1), SD, CV.order, CV.cum, P.iz, OP, 0, psi, hps);
-                        SD.level = lv_final;
-                        launch_s5<true>(h, s5_grid(h, grid_mf, lv_final), SD, CV.order, CV.cum, P.iz, OP, 1, hps, hpsi, psi, la_extra, ntau);
-                    }
-                    e1 = next_event(h);
-                    const dim3 gl = level_grid(h, grid_mf, lv_final);
+                    // (with hoh, h psi of the first pass goes into the pmn buffer, free in the u-scheme)
+                    XFER(apply_h(h, RC, bt, ll + 1, psi, hpsi, pmn, bt.la_extra, ntau));
+                    const dim3 gl = level_grid(h, bt.grid_mf, lv_final);
                     k_mfma_adot<<<gl, MF_WAVES * 64, 0, h->stream>>>(CVp, lv_final, kk, psi, hpsi, gpartial);
-                    { int n2 = gl.x; const double* p2 = presum(h, gpartial, nb, n2, 1296);
-                      rc = wait_b_level(); if (rc) return rc;
-                      k_reduce_a_u<<<nb, 1024, 0, h->stream>>>(p2, n2, dA + (size_t)ll * BLK, cstride, h->d_bmats.as<double2>(), bfrags, ci); }
+                    int n2 = gl.x; const double* p2 = presum(h, gpartial, nb, n2, 1296);
+                    XFER(side_reduce_wait(h, SR));
+                    k_reduce_a_u<<<nb, 1024, 0, h->stream>>>(p2, n2, dA + (size_t)ll * BLK, cstride, h->d_bmats.as<double2>(), bfrags, ci);
                     if (h->opt_orth3 == 2) k_mfma_orth3w<<<gl, MF_WAVES * 64, 0, h->stream>>>(CVp, lv_final, kk, hpsi, psi, t2, bfrags, gp_b);
-                else k_mfma_orth3<<<gl, MF_WAVES * 64, 0, h->stream>>>(CVp, lv_final, kk, hpsi, psi, t2, bfrags, gp_b, t3);
-                    rc = reduce_b_level(gl.x, ll); if (rc) return rc;
+                    else k_mfma_orth3<<<gl, MF_WAVES * 64, 0, h->stream>>>(CVp, lv_final, kk, hpsi, psi, t2, bfrags, gp_b, t3);
+                    hipStream_t st; XFER(side_reduce_begin(h, SR, st));
+                    n2 = gl.x; p2 = presum(h, gp_b, nb, n2, 1296, st, SR.side ? 1 : 0);
+                    k_reduce_b_u<<<nb, 1024, 0, st>>>(p2, n2, dB + (size_t)(ll + 1) * BLK, cstride, h->d_bmats.as<double2>(), bfrags, h->d_status.as<int>(), ci);
+                    XFER(side_reduce_end(h, SR));
                     if (oop) { double* f = t2; t2 = psi; psi = t3; t3 = f; }      // u_{n+1} is in t3; the vector of u_{n-1} is free
                     else std::swap(psi, t2);
-                    hop_ev.emplace_back(e0, e1);
-                    h->n_hop_launch += hoh ? 2 : 1;
                     continue;
                 }
                 // FP64 VALU kernel set: the reference's literal order on the reference's layout
+                hipEvent_t e0 = next_event(h);
+                ApplyArgs G{}; G.partial = partial;
                 if (!hoh) {
                     G.in = psi; G.v0 = psi; G.out = pmn; G.level = lv_final;
-                    k_apply<AM_LANCZOS, L><<<grid, NTHREADS, 0, h->stream>>>(P, CV, G);
-                    e1 = next_event(h);
+                    k_apply<AM_LANCZOS, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
                 } else {
                     G.in = psi; G.out = hpsi; G.level = 2 * ll + 1;
-                    k_apply<AM_STORE, L><<<grid, NTHREADS, 0, h->stream>>>(P, CV, G);
+                    k_apply<AM_STORE, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
                     G.in = hpsi; G.v1 = hpsi; G.cur = psi; G.v0 = psi; G.out = pmn; G.level = lv_final;
-                    k_apply<AM_HOH_LANCZOS, L><<<grid, NTHREADS, 0, h->stream>>>(P, CV, G);
-                    e1 = next_event(h);
+                    k_apply<AM_HOH_LANCZOS, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
                 }
-                hop_ev.emplace_back(e0, e1);                       // [e0,e1] brackets exactly the H|psi> kernel(s) of this step
-                h->n_hop_launch += hoh ? 2 : 1;
+                RC.hop_ev.emplace_back(e0, next_event(h)); h->n_hop_launch += hoh ? 2 : 1;   // [e0, e1] brackets exactly the H|psi> kernel(s) of this step
                 k_reduce_a<<<nb, 1024, 0, h->stream>>>(partial, nblk, dA + (size_t)ll * BLK, cstride);
-                k_orth<L><<<grid, NTHREADS, orth_lds, h->stream>>>(CV, lv_final, psi, pmn, tvec, dA + (size_t)ll * BLK, cstride, partial);
+                k_orth<L><<<grid, NTHREADS, orth_lds, h->stream>>>(CV, lv_final, psi, pmn, (const double*)nullptr, dA + (size_t)ll * BLK, cstride, partial);
                 k_reduce_b_eig<<<nb, 1024, 0, h->stream>>>(partial, nblk, dB + (size_t)(ll + 1) * BLK, cstride, h->d_bmats.as<double2>(), h->d_status.as<int>());
                 k_update<L><<<grid, NTHREADS, 0, h->stream>>>(CV, lv_final, psi, pmn, h->d_bmats.as<double2>());
             }
             HIPCK(h, hipGetLastError());
-            rc = wait_b_level(); if (rc) return rc;
-            return RSREC_OK;
+            return side_reduce_wait(h, SR);
         };
         const bool use_graph = MFMA && nchains <= B && ((h->opt_graph == 1 && nchains <= 8) || h->opt_graph >= 2) && getenv("RSREC_NO_GRAPH") == nullptr;
-        if (!use_graph) { rc = enqueue_levels(); if (rc) return rc; }
+        if (!use_graph) XFER(enqueue_levels());
         else {
             if (ci) HIPCK(h, h->d_s5queue.reserve((size_t)nb * 16 * sizeof(int)));
+            const Spmm5Operator& OP = *RC.op;
             // what the nodes hold BY VALUE: every pointer and dimension a kernel argument is made of
             std::vector<uintptr_t> key = {(uintptr_t)1 /*block Lanczos*/, (uintptr_t)nb, (uintptr_t)lld, (uintptr_t)nseed, (uintptr_t)hoh, (uintptr_t)ci, (uintptr_t)(rot != nullptr), (uintptr_t)kk,
-                                          (uintptr_t)h->cur_order, (uintptr_t)h->cur_cum, (uintptr_t)ostride, (uintptr_t)OP.d_frag, (uintptr_t)OP.d_meta, (uintptr_t)OP.ntr,
+                                          (uintptr_t)h->cur_order, (uintptr_t)h->cur_cum, (uintptr_t)bt.ostride, (uintptr_t)OP.d_frag, (uintptr_t)OP.d_meta, (uintptr_t)OP.ntr,
                                           (uintptr_t)h->s4_op.frag_set(0), (uintptr_t)h->s4_op.meta_set(0), (uintptr_t)h->d_nbr.p, (uintptr_t)h->d_nbr5.p, (uintptr_t)h->d_iz.p,
                                           (uintptr_t)h->d_partial.p, (uintptr_t)h->d_partial2.p, (uintptr_t)h->d_frags.p, (uintptr_t)dA, (uintptr_t)dB, (uintptr_t)h->d_bmats.p,
                                           (uintptr_t)h->d_status.p, (uintptr_t)h->d_seed.p, (uintptr_t)h->d_seedcoef.p, (uintptr_t)h->d_la_extra.p, (uintptr_t)h->d_s5queue.p,
@@ -1591,47 +1689,15 @@ int run_block_lanczos(rsrec_t* h, int nchains, int nseed, const int32_t* seed_at
             // ... and every option: launch shapes and kernel choices follow them (all but `graph`, which only decides whether this path is taken)
             for (const OptionEntry& o : OPTIONS)
                 if (o.member != &rsrec_handle::opt_graph) key.push_back((uintptr_t)(h->*o.member));
-            if (!h->graph_exec || key != h->graph_key) {
-                if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
-                h->graph_key.clear();
-                s5_prepare(h);
-                rc = s4_prepare(h); if (rc) return rc;
-                HIPCK(h, hipStreamSynchronize(h->stream));
-                HIPCK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeRelaxed));
-                h->capturing = true;
-                rc = enqueue_levels();
-                h->capturing = false;
-                hipGraph_t graph = nullptr;
-                const hipError_t ec = hipStreamEndCapture(h->stream, &graph);
-                if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-                if (ec != hipSuccess || !graph) return fail(h, RSREC_ERR_DEVICE, "hipStreamEndCapture failed: %s", hipGetErrorString(ec));
-                const hipError_t ei = hipGraphInstantiate(&h->graph_exec, graph, nullptr, nullptr, 0);
-                (void)hipGraphDestroy(graph);
-                if (ei != hipSuccess) { h->graph_exec = nullptr; return fail(h, RSREC_ERR_DEVICE, "hipGraphInstantiate failed: %s", hipGetErrorString(ei)); }
-                h->graph_key = key;
-            }
-            HIPCK(h, hipGraphLaunch(h->graph_exec, h->stream));
+            XFER(replay_level_loop(h, key, enqueue_levels));
             h->n_hop_launch += (double)nsteps * (hoh ? 2 : 1);
         }
-        if (rot && lld > 1) {
-            // local-axis runs: A' = R^H A R, B'^2 = R^H B^2 R on the resident copy, which is then what the caller gets back and what the
-            // stages on resident chains read -- one set of bits (get_terminf is a chain of bisections)
-            hipEvent_t r0 = next_event(h);
-            k_rotate_coef<<<dim3(2 * (lld - 1), nb), 256, 0, h->stream>>>(dA, dB, h->d_rot.as<double2>() + (size_t)c0 * BLK, lld);
-            HIPCK(h, hipGetLastError());
-            rot_ev.emplace_back(r0, next_event(h));
-        }
+        if (rot && lld > 1) XFER(rotate_resident_coef(h, RC, dA, dB, c0, nb, lld));
         XFER(xfer_d2h(h, a_b + (size_t)c0 * cstride * 2, dA, (size_t)nb * cstride * sizeof(double2)));
         XFER(xfer_d2h(h, b2_b + (size_t)c0 * cstride * 2, dB, (size_t)nb * cstride * sizeof(double2)));
         HIPCK(h, hipStreamSynchronize(h->stream));
     }
-    hipEvent_t ev_end = next_event(h);
-    rc = finish_status(h);
-    finish_timing(h, ev_begin, ev_end, hop_ev);
-    for (auto& pr : rot_ev) h->t_rot_ms += ev_ms(pr.first, pr.second);
-    if (rc) return rc;
-    h->res_kind = 1; h->res_n = nchains; h->res_lld = lld; h->res_seeded = seed_coef != nullptr;
-    return RSREC_OK;
+    return recursion_end(h, RC, 1, lld, seed_coef != nullptr);
 }
 
 }  // namespace
@@ -2826,162 +2892,99 @@ extern "C" int rsrec_contour_occupation(rsrec_t* h, int kind, int nsites, int ll
 
 namespace {
 
+// behind a batch's staged seed coefficients, one mu_1 scale per chain: sum over its seed atoms of |final coefficient|^2 (later seeds overwrite earlier ones on the same atom)
+void cheb_mu1_scales(int nb, int nseed, const std::vector<int>& seeds0, std::vector<double>& coef) {
+    coef.resize((size_t)nb * nseed * 2 + nb);
+    for (int c = 0; c < nb; ++c) {
+        double m0 = 0.0;
+        for (int k = 0; k < nseed; ++k) {
+            bool overwritten = false;
+            for (int k2 = k + 1; k2 < nseed; ++k2) overwritten |= seeds0[(size_t)c * nseed + k2] == seeds0[(size_t)c * nseed + k];
+            const size_t q = (size_t)c * nseed + k;
+            if (!overwritten) m0 += coef[2 * q] * coef[2 * q] + coef[2 * q + 1] * coef[2 * q + 1];
+        }
+        coef[(size_t)nb * nseed * 2 + c] = m0;
+    }
+}
+
 template <class L, bool MFMA>
 int run_chebyshev(rsrec_t* h, int nsites, int nseed, const int32_t* seed_atoms, const double* seed_coef, int lld, double a, double b, double* mu_n) {
-    int rc = 0;
     const int kk = h->kk;
     const bool hoh = h->hoh != 0;
     const int napply = lld + 1;                                  // first moment + lld steps
-    const int nlev = (hoh ? 2 * napply : napply) + 1;
     const int nmom = 2 * lld + 2;
-    const size_t velems = (size_t)(kk + 1) * BLD;
-    // matrix-core set: k_mfma_cheb epilogue; large launches and hoh use k_spmm5 on CI vectors, small launches of the plain
-    // operator the cooperative k_spmm4<4> on LayoutRM
-    const bool use_kp = MFMA && (hoh || h->opt_spmm5 == 2 || (h->opt_spmm5 == 1 && (long)std::min(nsites, 64) * (kk / GROUP + 1) >= 4096) || !spmm4_usable(h));
-    const int nvec = MFMA ? (hoh ? 5 : 4) : (hoh ? 4 : 3);
-    const int ci = use_kp ? 1 : 0;                              // vectors of this call are CI (else LayoutRM / LayoutCM)
-    if (MFMA && !use_kp) { rc = ensure_s4(h); if (rc) return rc; }
+    RecursionCall RC = recursion_call(h, MFMA, nsites, nseed, napply);
+    const int ci = RC.ci;
+    const size_t velems = RC.velems, mstride = (size_t)nmom * BLK;
     // the moments of ALL chains of the call stay on the device (rsrec_pack_moments): reserved BEFORE the batch is planned from the free
     // memory, so a call over many sites (nrec ~ kk) sizes its vectors around them instead of failing behind them
     h->res_kind = 0;
     HIPCK(h, h->d_mu.reserve((size_t)nsites * nmom * BLK * sizeof(double2)));
-    // with the Chebyshev step fused into the SpMM's epilogue (the default of the matrix-core set) H psi is never held: vector 3 is neither
-    // allocated nor cleared
-    const bool use_v3 = !(MFMA && (hoh || use_kp) && h->opt_cheb_fused);
-    BatchPlan bp;
-    rc = plan_batch(h, nsites, nvec - (use_v3 ? 0 : 1), velems / 2, bp);
-    if (rc) return rc;
-    const int B = bp.batch, nblk = bp.nblk;
-    for (int v = 0; v < nvec; ++v) if (v != 3 || use_v3) HIPCK(h, h->d_vec[v].reserve((size_t)B * velems * sizeof(double)));
-    XFER(reserve_partials(h, B, std::max((size_t)B * nblk * 2 * BLK * sizeof(double2), (size_t)B * 256 * 2 * 1296 * sizeof(double))));
-    XFER(ensure_side_stream(h));
-    const bool side = h->opt_side && h->side_stream;     // moment reduction of level t under the SpMM of level t + 1 (it feeds nothing on the device)
-    bool red_pending = false;
-    HIPCK(h, h->d_status.reserve(64));
-    HIPCK(h, h->d_seed.reserve((size_t)B * nseed * 4));
-    HIPCK(h, h->d_seedcoef.reserve((size_t)B * (nseed + 1) * sizeof(double2)));
-    HIPCK(h, hipMemsetAsync(h->d_status.p, 0, 64, h->stream));
-    const DevProblem P = make_problem(h);
-    const size_t mstride = (size_t)nmom * BLK;
-    hipEvent_t ev_begin = next_event(h);
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> hop_ev;
-    for (int c0 = 0; c0 < nsites; c0 += B) {
-        const int nb = std::min(B, nsites - c0);
+    // k_spmm5 forms the new vector in its epilogue (dst = (H src - b src)/a [* 2 - p0]; the default of the matrix-core set); k_mfma_cheb then
+    // only sums the Grams and H psi is never held: vector 3 is neither allocated nor cleared
+    const bool fused = ci && h->opt_cheb_fused;
+    XFER(recursion_begin(h, RC, MFMA ? (hoh ? 5 : 4) : (hoh ? 4 : 3), fused ? 3 : -1, nseed + 1));
+    const int nblk = RC.nblk;
+    SideReduce SR{RC.side};               // moment reduction of level t under the SpMM of level t + 1 (it feeds nothing on the device)
+    for (int c0 = 0; c0 < nsites; c0 += RC.B) {
+        const int nb = std::min(RC.B, nsites - c0);
         double2* mu = h->d_mu.as<double2>() + (size_t)c0 * mstride;       // this batch's slice of the resident moments
-        const auto th0 = std::chrono::steady_clock::now();
-        std::vector<int> seeds0;
-        std::vector<double> coef;
-        stage_seeds(seed_atoms, seed_coef, c0, nb, nseed, seeds0, coef);
-        coef.resize((size_t)nb * nseed * 2 + nb);                  // coefficients, then one mu_1 scale per chain
-        for (int c = 0; c < nb; ++c) {
-            double m0 = 0.0;
-            // mu_1 = sum over seed atoms of |final coefficient|^2 (later seeds overwrite earlier ones on the same atom)
-            for (int k = 0; k < nseed; ++k) {
-                bool overwritten = false;
-                for (int k2 = k + 1; k2 < nseed; ++k2) overwritten |= seeds0[(size_t)c * nseed + k2] == seeds0[(size_t)c * nseed + k];
-                const size_t q = (size_t)c * nseed + k;
-                if (!overwritten) m0 += coef[2 * q] * coef[2 * q] + coef[2 * q + 1] * coef[2 * q + 1];
-            }
-            coef[(size_t)nb * nseed * 2 + c] = m0;
-        }
-        int ostride = kk;
-        rc = upload_regions(h, seeds0.data(), nb, nseed, nlev, napply, hoh, MFMA, ostride, h->n_atom_steps, h->n_block_mult);
-        if (rc) return rc;
-        h->n_req_flop += required_hop_flops(h, h->s5_op);
-        XFER(xfer_h2d(h, h->d_seed.p, seeds0.data(), seeds0.size() * 4));
-        XFER(xfer_h2d(h, h->d_seedcoef.p, coef.data(), coef.size() * 8));
-        HIPCK(h, hipStreamSynchronize(h->stream));
-        h->t_host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - th0).count();
-        ChainView CV, CVp;                                    // CVp: the streaming moment pass walks the level-major lists (upload_regions)
-        chain_views(h, nlev, velems, 1, ostride, CV, &CVp);
-        for (int v = 0; v < nvec; ++v) if (v != 3 || use_v3) HIPCK(h, hipMemsetAsync(h->d_vec[v].p, 0, (size_t)nb * velems * sizeof(double), h->stream));
+        RecursionBatch bt;
+        XFER(recursion_batch(h, RC, seed_atoms, seed_coef, c0, nb, bt, cheb_mu1_scales));
+        const ChainView &CV = bt.CV, &CVp = bt.CVp;
+        XFER(clear_vectors(h, RC, nb));
         HIPCK(h, hipMemsetAsync(mu, 0, (size_t)nb * mstride * sizeof(double2), h->stream));
-        double* p0 = h->d_vec[0].as<double>();
-        double* p1 = h->d_vec[1].as<double>();
-        double* p2 = h->d_vec[2].as<double>();
-        double* tmp = h->d_vec[3].as<double>();
-        double* tmp2 = h->d_vec[4].as<double>();
-        const dim3 grid_mf(std::max(1, std::min(mfma_workgroups_per_chain(h, B), (ostride / GROUP + MF_WAVES - 1) / MF_WAVES)), nb);
+        double *p0 = h->d_vec[0].as<double>(), *p1 = h->d_vec[1].as<double>(), *p2 = h->d_vec[2].as<double>(), *tmp = h->d_vec[3].as<double>();
+        double* hps = (ci && hoh) ? h->d_vec[4].as<double>() : nullptr;     // hoh: h psi of the first pass
         if (ci) k_seed<LayoutCI><<<nb, 64, 0, h->stream>>>(p0, velems, h->d_seed.as<int>(), h->d_seedcoef.as<double2>(), nseed);
         else k_seed<L><<<nb, 64, 0, h->stream>>>(p0, velems, h->d_seed.as<int>(), h->d_seedcoef.as<double2>(), nseed);
         k_set_identity<<<nb, 256, 0, h->stream>>>(mu, mstride, h->d_seedcoef.as<double>() + (size_t)nb * nseed * 2);   // mu_1 (cheb_0th_mom :2157)
-        double* hps = (use_kp && hoh) ? tmp2 : nullptr;         // hoh: h psi of the first pass
         const dim3 grid(nblk, nb);
         for (int t = 1; t <= napply; ++t) {      // t = 1: first moment; t >= 2: recursion step ll = t-1
             const bool first = (t == 1);
             const int lv_final = hoh ? 2 * t : t;
-            hipEvent_t e0 = next_event(h);
-            ApplyArgs G{};
-            G.partial = h->d_partial.as<double2>();
-            G.a = a; G.b = b;
-            double* src = first ? p0 : p1;
-            double* dst = first ? p1 : p2;
+            double *src = first ? p0 : p1, *dst = first ? p1 : p2;
             if (MFMA) {
-                SpmmDims SD{kk, P.nslots, P.nmax, nlev, 1, ostride, lv_final, velems, CV.obase, nb};
-                const dim3 gl = level_grid(h, grid_mf, lv_final);
-                // k_spmm5 forms the new vector in its epilogue (dst = (H src - b src)/a [* 2 - p0]); k_mfma_cheb then only sums the Grams
-                const bool fused = (hoh || use_kp) && h->opt_cheb_fused;
-                S5Epilogue E;
-                if (fused) { E.kind = first ? 1 : 2; E.cur = src; E.old = first ? nullptr : p0; E.a = a; E.b = b; }
-                if (hoh) {
-                    SD.level = 2 * t - 1;
-                    launch_s5<false>(h, s5_grid(h, grid_mf, 2 * t - 1), SD, CV.order, CV.cum, P.iz, h->s5_op, 0, src, hps);
-                    SD.level = lv_final;
-                    launch_s5<true>(h, s5_grid(h, grid_mf, lv_final), SD, CV.order, CV.cum, P.iz, h->s5_op, 1, hps, fused ? dst : tmp, src, nullptr, 0, E);
-                } else if (use_kp) launch_s5<false>(h, s5_grid(h, grid_mf, lv_final), SD, CV.order, CV.cum, P.iz, h->s5_op, 0, src, fused ? dst : tmp, nullptr, nullptr, 0, E);
-                else { rc = launch_spmm(h, SD, CV, P, 0, src, tmp, grid_mf); if (rc) return rc; }
-                hipEvent_t e1 = next_event(h);
-                hop_ev.emplace_back(e0, e1);
-                h->n_hop_launch += hoh ? 2 : 1;
+                const dim3 gl = level_grid(h, bt.grid_mf, lv_final);
+                XFER(apply_h(h, RC, bt, t, src, fused ? dst : tmp, hps, nullptr, 0, fused ? cheb_epilogue(first, src, p0, a, b) : S5Epilogue()));
                 double* gp = h->d_partial.as<double>();
-                if (red_pending) { HIPCK(h, hipStreamWaitEvent(h->stream, h->ev_bred, 0)); red_pending = false; }   // gp is free again
+                XFER(side_reduce_wait(h, SR));                    // gp is free again
                 if (fused) {
                     if (first) k_mfma_cheb<true, true><<<gl, MF_WAVES * 64, 0, h->stream>>>(CVp, lv_final, kk, nullptr, src, nullptr, dst, a, b, gp);
                     else k_mfma_cheb<false, true><<<gl, MF_WAVES * 64, 0, h->stream>>>(CVp, lv_final, kk, nullptr, src, nullptr, dst, a, b, gp);
                 } else if (first) k_mfma_cheb<true><<<gl, MF_WAVES * 64, 0, h->stream>>>(CVp, lv_final, kk, tmp, src, nullptr, dst, a, b, gp);
                 else k_mfma_cheb<false><<<gl, MF_WAVES * 64, 0, h->stream>>>(CVp, lv_final, kk, tmp, src, p0, dst, a, b, gp);
-                hipStream_t rs = h->stream;
-                if (side) {
-                    HIPCK(h, hipEventRecord(h->ev_orth, h->stream));
-                    HIPCK(h, hipStreamWaitEvent(h->side_stream, h->ev_orth, 0));
-                    rs = h->side_stream;
-                }
-                int n2 = gl.x; const double* gp2 = presum(h, gp, nb, n2, 2 * 1296, rs, side ? 1 : 0);
+                hipStream_t rs; XFER(side_reduce_begin(h, SR, rs));
+                int n2 = gl.x; const double* gp2 = presum(h, gp, nb, n2, 2 * 1296, rs, SR.side ? 1 : 0);
                 k_reduce_cheb_mf<<<nb, 1024, 0, rs>>>(gp2, n2, first ? 1 : 0, t - 1, mu, mstride, h->d_status.as<int>(), nseed > 1 ? 1 : 0, ci);
-                if (side) { HIPCK(h, hipEventRecord(h->ev_bred, h->side_stream)); red_pending = true; }
+                XFER(side_reduce_end(h, SR));
                 if (!first) { double* o = p0; p0 = p1; p1 = p2; p2 = o; }
                 continue;
             }
+            hipEvent_t e0 = next_event(h);
+            ApplyArgs G{};
+            G.partial = h->d_partial.as<double2>(); G.a = a; G.b = b;
             if (!hoh) {
                 G.in = src; G.cur = src; G.v0 = p0; G.out = dst; G.level = lv_final;
-                if (first) k_apply<AM_CHEB1, L><<<grid, NTHREADS, 0, h->stream>>>(P, CV, G);
-                else k_apply<AM_CHEBN, L><<<grid, NTHREADS, 0, h->stream>>>(P, CV, G);
+                if (first) k_apply<AM_CHEB1, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
+                else k_apply<AM_CHEBN, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
             } else {
                 G.in = src; G.out = tmp; G.level = 2 * t - 1;
-                k_apply<AM_STORE, L><<<grid, NTHREADS, 0, h->stream>>>(P, CV, G);
+                k_apply<AM_STORE, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
                 G.in = tmp; G.v1 = tmp; G.cur = src; G.v0 = p0; G.out = dst; G.level = lv_final;
-                if (first) k_apply<AM_HOH_CHEB1, L><<<grid, NTHREADS, 0, h->stream>>>(P, CV, G);
-                else k_apply<AM_HOH_CHEBN, L><<<grid, NTHREADS, 0, h->stream>>>(P, CV, G);
+                if (first) k_apply<AM_HOH_CHEB1, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
+                else k_apply<AM_HOH_CHEBN, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
             }
-            hipEvent_t e1 = next_event(h);
-            hop_ev.emplace_back(e0, e1);
-            h->n_hop_launch += hoh ? 2 : 1;
+            RC.hop_ev.emplace_back(e0, next_event(h)); h->n_hop_launch += hoh ? 2 : 1;
             k_reduce_cheb<<<nb, 1024, 0, h->stream>>>(h->d_partial.as<double2>(), nblk, first ? 1 : 0, t - 1, mu, mstride, h->d_status.as<int>(), nseed > 1 ? 1 : 0);
             if (!first) { double* o = p0; p0 = p1; p1 = p2; p2 = o; }   // psi0 <- psi1 <- psi2 (:2585-2587) by rotating buffers
         }
         HIPCK(h, hipGetLastError());
-        if (red_pending) { HIPCK(h, hipStreamWaitEvent(h->stream, h->ev_bred, 0)); red_pending = false; }
+        XFER(side_reduce_wait(h, SR));
         XFER(xfer_d2h(h, mu_n + (size_t)c0 * mstride * 2, mu, (size_t)nb * mstride * sizeof(double2)));
         HIPCK(h, hipStreamSynchronize(h->stream));
     }
-    hipEvent_t ev_end = next_event(h);
-    HIPCK(h, hipStreamSynchronize(h->stream));
-    finish_timing(h, ev_begin, ev_end, hop_ev);
-    int status = 0;
-    XFER(xfer_d2h(h, &status, h->d_status.p, 4));
-    if (status & 2) return fail(h, RSREC_ERR_DIVERGED, "Chebyshev moments did not converge. Check energy limits energy_min and energy_max");
-    h->res_kind = 2; h->res_n = nsites; h->res_lld = lld; h->res_seeded = seed_coef != nullptr;
-    return RSREC_OK;
+    return recursion_end(h, RC, 2, lld, seed_coef != nullptr);
 }
 
 }  // namespace
@@ -3111,10 +3114,6 @@ void kubo_apply_h(const KuboCtx& K, const double* in, double* out, S5Epilogue ep
     if (!K.h->hoh) { kubo_spmm(K, K.h->s5_op, 0, in, out, nullptr, epi); return; }
     kubo_spmm(K, K.h->s5_op, 0, in, K.hps, nullptr);
     kubo_spmm(K, K.h->s5_op, 1, K.hps, out, in, epi);
-}
-S5Epilogue cheb_epilogue(bool first, const double* cur, const double* old, double a, double b) {
-    S5Epilogue E; E.kind = first ? 1 : 2; E.cur = cur; E.old = first ? nullptr : old; E.a = a; E.b = b;
-    return E;
 }
 // out = V in   (velo_vec_matmul :587 / velo_hoh_vec_matmul :656)
 void kubo_apply_v(const KuboCtx& K, const Spmm5Operator& vop, const double* in, double* out) {
