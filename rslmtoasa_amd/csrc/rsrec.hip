@@ -111,7 +111,6 @@ struct rsrec_handle {
     DevBuf d_asm[2][2], d_asm_in;
     std::vector<double> asm_host[2][2];
     int asm_nslots[2] = {0, 0}, asm_ncls[2] = {0, 0}, asm_hoh[2] = {0, 0};
-    double n_kubo_chain_launches = 0;   // rsrec_kubo_moments: whole-lattice products of the last call (launches x vectors in flight)
     int n_octet_launch = 0;      // launches of the last call that formed the groups of per-atom-block atoms over 8 chains (k_spmm5<., false, true>)
     int n_asm_reused = 0;        // block arrays the last rsrec_set_hamiltonian took from those device copies (0..4)
     long n_asm_calls = 0, n_ldos_calls = 0, n_recursion_calls = 0;   // life-time counters of the handle (RSREC_REPORT)
@@ -3007,8 +3006,21 @@ extern "C" int rsrec_chebyshev(rsrec_t* h, int nsites, const int32_t* seed_atoms
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// Stochastic Kubo double moments
+// Products over the whole lattice: the stochastic Kubo double moments, the orbital moments, single products on caller arrays
 namespace {
+
+// An operator table of k_spmm5 from blocks on the host (2 BLK doubles each): `fill` gets blk(set, tau, slot), the pointer of class tau <
+// nmax + ntype (per-atom classes first, then types) and slot <= nslots (the last: the extra on-site slot of two-input passes), and sets
+// those that exist.  What the pointers refer to has to live until this returns.  A failure is reported as "`who`: ...".
+template <class Fill>
+int build_operator_table(rsrec_t* h, Spmm5Operator& op, int nset, const char* who, Fill&& fill) {
+    const int ntau = h->nmax + h->ntype, nfs = h->nslots + 1;
+    std::vector<const double*> blk((size_t)nset * ntau * nfs, nullptr);
+    fill([&](int set, int tau, int slot) -> const double*& { return blk[((size_t)set * ntau + tau) * nfs + slot]; });
+    const char* msg = op.build_custom(h->nslots, ntau, nset, blk);
+    if (msg) return fail(h, RSREC_ERR_DEVICE, "%s: %s", who, msg);
+    return RSREC_OK;
+}
 
 // Operator tables of a velocity-type operator (recursion.f90:587-784): which = 0 -> kubo_op[0] (v_a), 1 -> kubo_op[1] (v_b).
 //   set 0: V itself -- per-type blocks v_op(:,:,slot,type) for the bulk atoms; the reference has no velocity operator for the
@@ -3017,72 +3029,98 @@ namespace {
 //          second input gives  V psi - sum_{slot >= 2} vo_slot (h psi)_nbr  (velo_hoh_vec_matmul :750-776; its on-site vo term is
 //          commented out in the reference, its e_nu / l.s terms are zero).
 int build_kubo_operator(rsrec_t* h, int which, const double* v, const double* vo) {
-    const int ntau = h->nmax + h->ntype, nfs = h->nslots + 1, nset = h->hoh ? 2 : 1;
+    const int nset = h->hoh ? 2 : 1;
     const size_t B = 2 * (size_t)BLK;
-    std::vector<const double*> blk((size_t)nset * ntau * nfs, nullptr);
     std::vector<double> neg((size_t)h->ntype * h->nslots * B, 0.0), ident(B, 0.0);
     for (int d = 0; d < NB; ++d) ident[2 * (d + NB * d)] = 1.0;
-    for (int t = 0; t < h->ntype; ++t)
-        for (int s = 0; s < h->nslots; ++s) {
-            blk[((size_t)0 * ntau + h->nmax + t) * nfs + s] = v + B * (s + (size_t)h->hslots * t);
-            if (nset > 1 && s >= 1) {
-                double* d = neg.data() + B * (s + (size_t)h->nslots * t);
-                const double* src = vo + B * (s + (size_t)h->hslots * t);
-                for (size_t e = 0; e < B; ++e) d[e] = -src[e];
-                blk[((size_t)1 * ntau + h->nmax + t) * nfs + s] = d;
+    return build_operator_table(h, h->kubo_op[which], nset, "rsrec_kubo_moments", [&](auto&& blk) {
+        for (int t = 0; t < h->ntype; ++t)
+            for (int s = 0; s < h->nslots; ++s) {
+                blk(0, h->nmax + t, s) = v + B * (s + (size_t)h->hslots * t);
+                if (nset > 1 && s >= 1) {
+                    double* d = neg.data() + B * (s + (size_t)h->nslots * t);
+                    const double* src = vo + B * (s + (size_t)h->hslots * t);
+                    for (size_t e = 0; e < B; ++e) d[e] = -src[e];
+                    blk(1, h->nmax + t, s) = d;
+                }
             }
-        }
-    if (nset > 1)
-        for (int t = 0; t < h->ntype; ++t) blk[((size_t)1 * ntau + h->nmax + t) * nfs + h->nslots] = ident.data();
-    const char* msg = h->kubo_op[which].build_custom(h->nslots, ntau, nset, blk);
-    if (msg) return fail(h, RSREC_ERR_DEVICE, "rsrec_kubo_moments: %s", msg);
-    return RSREC_OK;
+        if (nset > 1)
+            for (int t = 0; t < h->ntype; ++t) blk(1, h->nmax + t, h->nslots) = ident.data();
+    });
 }
 
 // h restricted to the bulk atoms (psi1 of velo_hoh_vec_matmul :727-741 is only formed for k > nmax)
 int build_kubo_hbulk(rsrec_t* h) {
-    const int ntau = h->nmax + h->ntype, nfs = h->nslots + 1;
     const size_t B = 2 * (size_t)BLK;
-    std::vector<const double*> blk((size_t)ntau * nfs, nullptr);
-    for (int t = 0; t < h->ntype; ++t)
-        for (int s = 0; s < h->nslots; ++s) blk[((size_t)h->nmax + t) * nfs + s] = h->host_ee.data() + B * (s + (size_t)h->hslots * t);
-    const char* msg = h->kubo_hbulk.build_custom(h->nslots, ntau, 1, blk);
-    if (msg) return fail(h, RSREC_ERR_DEVICE, "rsrec_kubo_moments: %s", msg);
-    return RSREC_OK;
+    return build_operator_table(h, h->kubo_hbulk, 1, "rsrec_kubo_moments", [&](auto&& blk) {
+        for (int t = 0; t < h->ntype; ++t)
+            for (int s = 0; s < h->nslots; ++s) blk(0, h->nmax + t, s) = h->host_ee.data() + B * (s + (size_t)h->hslots * t);
+    });
 }
 
-struct KuboCtx {
-    rsrec_t* h;
-    SpmmDims SD;
-    ChainView CV;
-    dim3 grid;
-    const int* iz;
-    double *hps, *p1, *p2;      // temporaries of the two-pass products
-    std::vector<std::pair<hipEvent_t, hipEvent_t>>* spmm_ev = nullptr;   // timing of every SpMM launch (rsrec_kubo_moments)
-    std::vector<std::tuple<const Spmm5Operator*, int, double>>* req = nullptr;
+// h as ham_vec_matmul applies it (recursion.f90:913-977): per-type blocks ee (per-atom hall for the impurity region) with l.s added to
+// the on-site block -- whatever hamiltonian%hoh says.  Without hoh that is set 0 of s5_op; with hoh a table of its own.
+int build_plain_operator(rsrec_t* h) {
+    const int ntau = h->nmax + h->ntype;
+    const size_t B = 2 * (size_t)BLK;
+    std::vector<double> onsite((size_t)ntau * B);
+    return build_operator_table(h, h->orb_plain, 1, "plain operator table", [&](auto&& blk) {
+        for (int tau = 0; tau < ntau; ++tau) {
+            const int ty = tau < h->nmax ? h->iz0[tau] : tau - h->nmax;
+            const double* base = tau < h->nmax ? h->host_hall.data() + B * (size_t)h->hslots * tau : h->host_ee.data() + B * (size_t)h->hslots * (tau - h->nmax);
+            for (size_t e = 0; e < B; ++e) onsite[(size_t)tau * B + e] = base[e] + h->host_lsham[B * ty + e];
+            blk(0, tau, 0) = onsite.data() + (size_t)tau * B;
+            for (int s = 1; s < h->nslots; ++s) blk(0, tau, s) = base + B * s;
+        }
+    });
+}
+
+// What rsrec_kubo_moments, rsrec_orbital_moments and rsrec_apply_operator share, as the recursion drivers share RecursionCall: every product
+// is one k_spmm5 launch (two with hoh) over the list of ALL atoms -- one order row, level 0, shared by the chains of the launch -- on whole
+// vectors side by side in buffer slots of `chains_per_slot` chains.  The call reads:  reserve -> whole_lattice_begin -> set the temporaries ->
+// ev_begin -> per batch { whole_lattice_batch; products } -> whole_lattice_end.
+struct WholeLatticeCall {
+    rsrec_t* h = nullptr;
+    bool timed = false;                  // events around every launch and the flop accounting (false: rsrec_apply_operator, the call's span only)
+    SpmmDims SD; ChainView CV; dim3 grid; const int* iz = nullptr;   // what launch_s5 takes (CV also k_mfma_adot)
+    double *hps = nullptr, *p1 = nullptr, *p2 = nullptr;   // the caller's temporaries of the two-pass products (hoh): h psi; h_bulk psi and V psi
+    hipEvent_t ev_begin = nullptr;       // start of the timed span: the caller records it once its uploads are done
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> hop_ev, rest_ev;   // every SpMM launch; what else a call times by itself (Kubo: the contractions)
+    std::vector<std::tuple<const Spmm5Operator*, int, double>> req;   // required flops of a product with (operator, set): computed once per call
+    double chain_launches = 0;           // whole-lattice products of the call: launches x chains in them
 };
 
-// The context of launches over the whole lattice: the list of all atoms as the one order row that the `cpo` chains of a launch share
-// (cached like every region), and the launch shape for `nchains` of them.  The temporaries and the timing tables stay with the caller.
-int whole_lattice_ctx(rsrec_t* h, int cpo, int nchains, KuboCtx& K) {
+// The list of all atoms as the one region (cached like every region) and the launch shape for a full batch of `chains_per_slot` chains.
+int whole_lattice_begin(rsrec_t* h, WholeLatticeCall& W, int chains_per_slot, bool timed) {
     const int kk = h->kk;
     const size_t velems = (size_t)(kk + 1) * BLD;
     std::vector<int> all(kk);
     for (int i = 0; i < kk; ++i) all[i] = i;
     int ostride = kk;
     double dummy1 = 0, dummy2 = 0;
-    const int rc = upload_regions(h, all.data(), 1, kk, 1, 1, false, true, ostride, dummy1, dummy2);
-    if (rc) return rc;
-    K.h = h;
-    chain_views(h, 1, velems, cpo, ostride, K.CV);
-    K.SD = SpmmDims{kk, h->nslots, h->nmax, 1, cpo, ostride, 0, velems, K.CV.obase, nchains};
-    K.grid = s5_grid(h, dim3(256, (unsigned)nchains), 0);
-    K.iz = h->d_iz.as<int>();
+    XFER(upload_regions(h, all.data(), 1, kk, 1, 1, false, true, ostride, dummy1, dummy2));
+    W.h = h; W.timed = timed;
+    chain_views(h, 1, velems, chains_per_slot, ostride, W.CV);
+    W.SD = SpmmDims{kk, h->nslots, h->nmax, 1, chains_per_slot, ostride, 0, velems, W.CV.obase, chains_per_slot};
+    W.grid = s5_grid(h, dim3(256, (unsigned)chains_per_slot), 0);
+    W.iz = h->d_iz.as<int>();
     return RSREC_OK;
 }
 
+// The launches of a batch of nb <= chains_per_slot chains (the last batch of a call may be short; the slots keep their width).
+// The kernels find a chain's order row as chain / cpo (k_spmm5, k_mfma_adot): with one row and nb <= cpo that is row 0 whether cpo stays the
+// slot's width (rsrec_kubo_moments) or follows the batch (rsrec_orbital_moments) -- the same memory either way.  The HOST side of launch_s5
+// reads it too: only launches with cpo == 1 add to the executed-flop counter (and may take the class-run and octet forms), so a short batch of
+// ONE chain counts under the second form and not under the first.  Hence the parameter: each caller keeps what it did, and the counters of
+// rsrec_get_timing with them.
+void whole_lattice_batch(WholeLatticeCall& W, int nb, bool cpo_follows_batch) {
+    W.SD.nchains = nb;
+    if (cpo_follows_batch) W.CV.cpo = W.SD.cpo = nb;
+    W.grid = s5_grid(W.h, dim3(256, (unsigned)nb), 0);
+}
+
 // flops one whole-lattice product with operator (op, set) requires by its block structure (see required_hop_flops)
-double kubo_required_flops(const rsrec_t* h, const Spmm5Operator& op, int set) {
+double whole_lattice_required_flops(const rsrec_t* h, const Spmm5Operator& op, int set) {
     double f = 0.0;
     const int ns = h->nslots;
     for (int i = 0; i < h->kk; ++i) {
@@ -3094,44 +3132,228 @@ double kubo_required_flops(const rsrec_t* h, const Spmm5Operator& op, int set) {
     return f;
 }
 
-void kubo_spmm(const KuboCtx& K, const Spmm5Operator& op, int set, const double* in, double* out, const double* in2, S5Epilogue epi = S5Epilogue()) {
-    rsrec_t* h = K.h;
-    hipEvent_t e0 = K.spmm_ev ? next_event(h) : nullptr;
-    if (in2) launch_s5<true>(h, K.grid, K.SD, K.CV.order, K.CV.cum, K.iz, op, set, in, out, in2, nullptr, 0, epi);
-    else launch_s5<false>(h, K.grid, K.SD, K.CV.order, K.CV.cum, K.iz, op, set, in, out, nullptr, nullptr, 0, epi);
-    if (K.spmm_ev) {
-        K.spmm_ev->emplace_back(e0, next_event(h));
-        double f = -1.0;                                  // required flops of (op, set): computed once per call
-        for (auto& e : *K.req) if (std::get<0>(e) == &op && std::get<1>(e) == set) f = std::get<2>(e);
-        if (f < 0.0) { f = kubo_required_flops(h, op, set); K.req->emplace_back(&op, set, f); }
-        h->n_req_flop += f * K.SD.nchains;
-        h->n_kubo_chain_launches += K.SD.nchains;
-    }
+// one launch: out = op(set) in  [+ the extra slot's block on in2], through the epilogue
+void whole_lattice_spmm(WholeLatticeCall& W, const Spmm5Operator& op, int set, const double* in, double* out, const double* in2, S5Epilogue epi = S5Epilogue()) {
+    rsrec_t* h = W.h;
+    hipEvent_t e0 = W.timed ? next_event(h) : nullptr;
+    if (in2) launch_s5<true>(h, W.grid, W.SD, W.CV.order, W.CV.cum, W.iz, op, set, in, out, in2, nullptr, 0, epi);
+    else launch_s5<false>(h, W.grid, W.SD, W.CV.order, W.CV.cum, W.iz, op, set, in, out, nullptr, nullptr, 0, epi);
+    if (!W.timed) return;
+    W.hop_ev.emplace_back(e0, next_event(h));
+    double f = -1.0;
+    for (auto& e : W.req) if (std::get<0>(e) == &op && std::get<1>(e) == set) f = std::get<2>(e);
+    if (f < 0.0) { f = whole_lattice_required_flops(h, op, set); W.req.emplace_back(&op, set, f); }
+    h->n_req_flop += f * W.SD.nchains;
+    W.chain_launches += W.SD.nchains;
 }
 // out = H in   (ham_vec_matmul :913 / ham_hoh_vec_matmul :785 before their scale-and-shift), or with an epilogue the whole Chebyshev
 // step  out = (H in - b in)/a  [* 2 - old]  (their scale-and-shift :968-970 and the caller's recurrence :1132-1136) in the same kernel
-void kubo_apply_h(const KuboCtx& K, const double* in, double* out, S5Epilogue epi = S5Epilogue()) {
-    if (!K.h->hoh) { kubo_spmm(K, K.h->s5_op, 0, in, out, nullptr, epi); return; }
-    kubo_spmm(K, K.h->s5_op, 0, in, K.hps, nullptr);
-    kubo_spmm(K, K.h->s5_op, 1, K.hps, out, in, epi);
+void whole_lattice_apply_h(WholeLatticeCall& W, const double* in, double* out, S5Epilogue epi = S5Epilogue()) {
+    if (!W.h->hoh) { whole_lattice_spmm(W, W.h->s5_op, 0, in, out, nullptr, epi); return; }
+    whole_lattice_spmm(W, W.h->s5_op, 0, in, W.hps, nullptr);
+    whole_lattice_spmm(W, W.h->s5_op, 1, W.hps, out, in, epi);
 }
 // out = V in   (velo_vec_matmul :587 / velo_hoh_vec_matmul :656)
-void kubo_apply_v(const KuboCtx& K, const Spmm5Operator& vop, const double* in, double* out) {
-    if (!K.h->hoh) { kubo_spmm(K, vop, 0, in, out, nullptr); return; }
-    kubo_spmm(K, vop, 0, in, K.p2, nullptr);
-    kubo_spmm(K, K.h->nmax > 0 ? K.h->kubo_hbulk : K.h->s5_op, 0, in, K.p1, nullptr);
-    kubo_spmm(K, vop, 1, K.p1, out, K.p2);
+void whole_lattice_apply_v(WholeLatticeCall& W, const Spmm5Operator& vop, const double* in, double* out) {
+    if (!W.h->hoh) { whole_lattice_spmm(W, vop, 0, in, out, nullptr); return; }
+    whole_lattice_spmm(W, vop, 0, in, W.p2, nullptr);
+    whole_lattice_spmm(W, W.h->nmax > 0 ? W.h->kubo_hbulk : W.h->s5_op, 0, in, W.p1, nullptr);
+    whole_lattice_spmm(W, vop, 1, W.p1, out, W.p2);
+}
+
+// The three-term recurrence on whole vectors, H~ = (H - b)/a: with T_0(H~) x in `cur`, step(n) for n = 0, 1, 2, ... leaves T_n(H~) x in `cur`
+// (n = 0: nothing to do) and T_{n-1}(H~) x in `old`; from n = 2 on the three buffers rotate, and `spare` is T_{n-2}(H~) x during the launch.
+struct ChebyshevStepper {
+    double *old, *cur, *spare;
+    void step(WholeLatticeCall& W, int n, double a, double b) {
+        if (n == 0) return;
+        if (n == 1) std::swap(old, cur);
+        else { double* o = spare; spare = old; old = cur; cur = o; }
+        whole_lattice_apply_h(W, old, cur, cheb_epilogue(n == 1, old, spare, a, b));
+    }
+};
+
+// End of a call: the closing event, the stream, the timing.  Untimed calls report total_ms only.  Timed ones report every SpMM launch as hop_ms
+// and hop_launches; rest_ms is total - hop (finish_timing) unless `rest_is_own_spans`: then it is the sum of rest_ev -- rsrec_kubo_moments'
+// contractions, so that hop_ms + rest_ms < total_ms there -- and the work counters are in the reference's terms: every product is over the
+// whole lattice, one block multiply per (atom, present slot).
+int whole_lattice_end(rsrec_t* h, WholeLatticeCall& W, bool rest_is_own_spans = false) {
+    hipEvent_t ev_end = next_event(h);
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    HIPCK(h, hipGetLastError());
+    if (!W.timed) { h->t_total_ms = ev_ms(W.ev_begin, ev_end); return RSREC_OK; }
+    finish_timing(h, W.ev_begin, ev_end, W.hop_ev);
+    h->n_hop_launch = (double)W.hop_ev.size();
+    if (!rest_is_own_spans) return RSREC_OK;
+    h->t_rest_ms = 0;
+    for (auto& pr : W.rest_ev) h->t_rest_ms += ev_ms(pr.first, pr.second);
+    const double fan = (double)std::count_if(h->nbr.begin(), h->nbr.end(), [](int nbr) { return nbr >= 0; });
+    h->n_block_mult = fan * W.chain_launches;
+    h->n_atom_steps = (double)h->kk * W.chain_launches;
+    return RSREC_OK;
+}
+
+// The device memory of a rsrec_kubo_moments call, decided before anything is reserved: 11 work vectors, `lchunk` left vectors, one block of
+// right vectors, the slices' partial blocks, the moments of the vectors in flight -- the five buffers of d_kubo, in that order.
+// The left matrix is held in chunks of `lchunk` vectors (all of them if they fit: cond_ll x kk x 5184 B is 21 GB for cond_ll = 500
+// on 8 000 atoms, 252 GB on 10^5): each chunk continues the left recurrence where the previous one stopped and is contracted
+// with ALL right vectors, so the right recurrence (2 of the 3 SpMMs per moment order) is repeated once per chunk.
+// Vectors in flight: the vectors of a call are independent (recursion.f90:1104: one pass of the loop each) and one whole-lattice product is
+// kk / 8 groups -- 1 000 on 8 000 atoms, half a round of the device's wave slots per spin.  Up to 8 of them advance together as the CHAINS of
+// every launch (chain c of a buffer slot lies c vectors behind chain 0, exactly like the sites of a recursion batch); each keeps its own
+// left / right matrices and is contracted by itself.  A whole left matrix per vector goes first: vectors are added only while it fits.
+struct KuboPlan {
+    int cond_ll = 0, n_cu = 0;
+    int nchunk = 0, lchunk = 0, nbv = 0;     // right vectors per contraction; left vectors held at a time; vectors in flight
+    int ksteps_total = 0, nbn_max = 0;       // k-steps of 4 rows (the last one may end inside the zero block); column blocks of a full contraction
+    size_t velems = 0, sstride = 0;          // doubles of one vector; between two slots of a buffer (nbv chains each)
+    size_t bytes[5] = {0, 0, 0, 0, 0};       // of the five buffers
+    // slices of the row index per contraction: enough wave tasks for a few rounds of the device, at least 64 k-steps per task
+    int ksplit_for(int lc) const {
+        const long blocks = (long)((lc * NB + KG_BLK - 1) / KG_BLK) * nbn_max;
+        long ksp = (12L * 8 * n_cu + blocks - 1) / std::max(1L, blocks);          // up to a dozen rounds of the device's wave slots
+        ksp = std::min<long>({ksp, 64, std::max(1, ksteps_total / 64)});
+        return (int)std::max<long>(8, (ksp + 7) / 8 * 8);
+    }
+    // where the buffers lie (kubo_reserve).  The slots of Lm / Rm ARE the left / right vectors (CI layout = dense row-major (18 kk) x 18
+    // matrices side by side), written there by the SpMMs themselves and contracted in place.
+    double *work = nullptr, *Lm = nullptr, *Rm = nullptr;
+    double2 *part = nullptr, *mu = nullptr;
+    enum { PSIREF = 0, Y = 1 /* .. 3: the right recurrence */, L0 = 4, HPS = 6, P1 = 7, P2 = 8, L1 = 9 };   // work vectors (L0, L1: T_{m0-2} r, T_{m0-1} r, the left recurrence across a chunk border)
+    double* vec(int v) const { return work + (size_t)v * sstride; }
+    double* Lslot(int q) const { return Lm + (size_t)q * sstride; }
+    double* Rslot(int q) const { return Rm + (size_t)q * sstride; }
+};
+
+int kubo_plan(rsrec_t* h, int nvec, int cond_ll, KuboPlan& P) {
+    const int kk = h->kk;
+    P.cond_ll = cond_ll; P.n_cu = h->n_cu; P.velems = (size_t)(kk + 1) * BLD;
+    P.nchunk = std::min(cond_ll, 64);
+    size_t free_b = 0, total_b = 0;
+    HIPCK(h, hipMemGetInfo(&free_b, &total_b));
+    size_t reusable = 0;
+    for (int v = 0; v < 6; ++v) reusable += h->d_vec[v].bytes;
+    for (auto& kb : h->d_kubo) reusable += kb.bytes;             // the buffers of the previous call (reused where they are large enough)
+    const double budget = 0.9 * (double)(free_b + reusable);
+    P.ksteps_total = (int)((NB * (size_t)kk + 3) / 4);
+    P.nbn_max = (P.nchunk * NB + KG_BLK - 1) / KG_BLK;
+    auto part_bytes = [&](int lc) { return (double)P.ksplit_for(lc) * ((lc * NB + KG_BLK - 1) / KG_BLK) * KG_BLK * (double)P.nbn_max * KG_BLK * 16.0; };
+    auto need_for = [&](int lc, int nv) { return (11.0 + lc + P.nchunk) * nv * P.velems * 8 + part_bytes(lc) + (double)nv * cond_ll * cond_ll * BLK * 16.0; };
+    int lchunk = cond_ll;
+    if (h->opt_kubo_lchunk > 0) lchunk = (int)std::min<long>(cond_ll, h->opt_kubo_lchunk);
+    int nbv = (int)std::min<long>(nvec, h->opt_kubo_vbatch > 0 ? h->opt_kubo_vbatch : 8);
+    while (nbv > 1 && need_for(lchunk, nbv) > budget) --nbv;
+    while (lchunk > 1 && need_for(lchunk, nbv) > budget) lchunk = (lchunk + 1) / 2;
+    if (need_for(lchunk, nbv) > budget)
+        return fail(h, RSREC_ERR_DEVICE, "rsrec_kubo_moments: %.1f GB needed for one left vector at a time on %d atoms, %.1f GB free", need_for(1, 1) * 1e-9, kk, free_b * 1e-9);
+    P.lchunk = lchunk; P.nbv = nbv; P.sstride = (size_t)nbv * P.velems;
+    P.bytes[0] = 11 * P.sstride * 8; P.bytes[1] = (size_t)lchunk * P.sstride * 8; P.bytes[2] = (size_t)P.nchunk * P.sstride * 8;
+    P.bytes[3] = (size_t)part_bytes(lchunk); P.bytes[4] = (size_t)nbv * cond_ll * cond_ll * BLK * 16;
+    return RSREC_OK;
+}
+
+// The plan's buffers: the recursion's work vectors go, and buffers that have to grow are given back first, so that the new sizes are asked of
+// the memory the budget counted on.  Block kk of every vector and slot stays the zero block.
+int kubo_reserve(rsrec_t* h, KuboPlan& P) {
+    for (int v = 0; v < 6; ++v) h->d_vec[v].release();
+    for (int q = 0; q < 5; ++q) if (h->d_kubo[q].bytes < P.bytes[q]) h->d_kubo[q].release();
+    for (int q = 0; q < 5; ++q)
+        if (h->d_kubo[q].reserve(P.bytes[q]) != hipSuccess) {
+            for (auto& kb : h->d_kubo) kb.release();
+            return fail(h, RSREC_ERR_DEVICE, "rsrec_kubo_moments: out of device memory");
+        }
+    P.work = h->d_kubo[0].as<double>(); P.Lm = h->d_kubo[1].as<double>(); P.Rm = h->d_kubo[2].as<double>();
+    P.part = h->d_kubo[3].as<double2>(); P.mu = h->d_kubo[4].as<double2>();
+    HIPCK(h, hipMemsetAsync(P.Lm, 0, P.bytes[1], h->stream));
+    HIPCK(h, hipMemsetAsync(P.Rm, 0, P.bytes[2], h->stream));
+    HIPCK(h, hipMemsetAsync(P.work, 0, P.bytes[0], h->stream));
+    return RSREC_OK;
+}
+
+struct KuboSeeds { int nseed; const int32_t* atoms; const double* coef; };   // the caller's (nvec, nseed) tables; atom 0 = unused entry
+
+// r_i of vectors iv0 .. iv0 + nb - 1 as the chains of PSIREF: psiref(l,l,seed(k)) = coef(k)
+int kubo_seed_batch(rsrec_t* h, const KuboPlan& P, const KuboSeeds& S, int iv0, int nb) {
+    double* psiref = P.vec(KuboPlan::PSIREF);
+    HIPCK(h, hipMemsetAsync(psiref, 0, P.sstride * 8, h->stream));
+    for (int c = 0; c < nb; ++c) {
+        const int iv = iv0 + c;
+        std::vector<int> s0; std::vector<double> c0;
+        for (int k = 0; k < S.nseed; ++k) {
+            const size_t e = (size_t)iv * S.nseed + k;
+            if (S.atoms[e] == 0) continue;
+            s0.push_back(S.atoms[e] - 1); c0.push_back(S.coef[2 * e]); c0.push_back(S.coef[2 * e + 1]);
+        }
+        if (s0.empty()) return fail(h, RSREC_ERR_ARG, "rsrec_kubo_moments: vector %d has no seed", iv + 1);
+        XFER(xfer_h2d(h, h->d_seed.p, s0.data(), s0.size() * 4));
+        XFER(xfer_h2d(h, h->d_seedcoef.p, c0.data(), c0.size() * 8));
+        k_seed<LayoutCI><<<1, 64, 0, h->stream>>>(psiref + (size_t)c * P.velems, P.velems, h->d_seed.as<int>(), h->d_seedcoef.as<double2>(), (int)s0.size());
+        HIPCK(h, hipStreamSynchronize(h->stream));                            // the seed tables are reused by the next vector
+    }
+    return RSREC_OK;
+}
+
+// Left vectors  T_{m-1}(H~) r,  m = m0 .. m0 + lchunk - 1 (recursion.f90:1120-1142), each written by its SpMM into its slot of Lm; the
+// recurrence reads the two slots before it -- across a chunk border the copies L0 = T_{m0-2} r, L1 = T_{m0-1} r, saved here for the next chunk
+int kubo_left_chunk(WholeLatticeCall& W, const KuboPlan& P, int m0, double a, double b) {
+    rsrec_t* h = W.h;
+    const int ml = std::min(P.lchunk, P.cond_ll - m0);
+    const size_t cpy = ((size_t)W.SD.nchains * P.velems - BLD) * 8;      // the chains of a slot, up to the last one's zero block
+    double *l0 = P.vec(KuboPlan::L0), *l1 = P.vec(KuboPlan::L1);
+    for (int m = m0; m < m0 + ml; ++m) {
+        double* out = P.Lslot(m - m0);
+        const double* prev1 = m - 1 >= m0 ? P.Lslot(m - 1 - m0) : l1;
+        const double* prev2 = m - 2 >= m0 ? P.Lslot(m - 2 - m0) : (m - 2 == m0 - 1 ? l1 : l0);
+        if (m == 0) HIPCK(h, hipMemcpyAsync(out, P.vec(KuboPlan::PSIREF), cpy, hipMemcpyDeviceToDevice, h->stream));
+        else if (m == 1) whole_lattice_apply_h(W, prev1, out, cheb_epilogue(true, prev1, nullptr, a, b));
+        else whole_lattice_apply_h(W, prev1, out, cheb_epilogue(false, prev1, prev2, a, b));
+    }
+    if (m0 + ml < P.cond_ll) {                                          // (the slots are about to be reused)
+        if (ml >= 2) HIPCK(h, hipMemcpyAsync(l0, P.Lslot(ml - 2), cpy, hipMemcpyDeviceToDevice, h->stream));
+        else HIPCK(h, hipMemcpyAsync(l0, l1, cpy, hipMemcpyDeviceToDevice, h->stream));
+        HIPCK(h, hipMemcpyAsync(l1, P.Lslot(ml - 1), cpy, hipMemcpyDeviceToDevice, h->stream));
+    }
+    return RSREC_OK;
+}
+
+// The block of right vectors that ends with order n (slots 0 .. n % nchunk of Rm) against the left chunk from m0 on, between its events:
+// C[(m,c)][(n,c')] = sum_{k,r} conj(L_m[(k,r)][c]) R_n[(k,r)][c'], blocks of C x `ksplit` slices of (k,r), one wave each (k_kubo_gram), then
+// the slices summed in fixed order into mu (k_kubo_gram_reduce).  One contraction per vector of the batch: its matrices are the chain-c
+// columns of the slots (leading dimension = a whole slot).
+int kubo_contract(WholeLatticeCall& W, const KuboPlan& P, int m0, int n) {
+    rsrec_t* h = W.h;
+    const int nl = n % P.nchunk, n0 = n - nl, ncols = (nl + 1) * NB, m_rows = std::min(P.lchunk, P.cond_ll - m0) * NB;
+    const int nbm = (m_rows + KG_BLK - 1) / KG_BLK, nbn = (ncols + KG_BLK - 1) / KG_BLK;
+    // slices: the multiple of 8 (<= what the partial buffer was sized for, >= 64 k-steps per task) that fills whole rounds of
+    // the device's wave slots best -- 361 blocks x 24 slices are 4.2 rounds of 2 048 slots (85 % of the last round idle), x 32 are 5.6
+    int ksplit = 8;
+    const long slots = 8L * h->n_cu, cap = std::min<long>(P.ksplit_for(P.lchunk), std::max(8, P.ksteps_total / 64 / 8 * 8));
+    double best = 0.0;
+    for (long c = 8; c <= cap; c += 8) {
+        const long tasks = (long)nbm * nbn * c, rounds = (tasks + slots - 1) / slots;
+        const double eff = (double)tasks / (double)(rounds * slots) * (rounds >= 3 ? 1.0 : 0.9);   // (few rounds: the tail of the slowest wave shows)
+        if (eff > best + 1e-9) { best = eff; ksplit = (int)c; }
+    }
+    HIPCK(h, hipGetLastError());
+    hipEvent_t g0 = next_event(h);
+    const unsigned wgs = 8u * (unsigned)(((long)nbm * nbn * (ksplit / 8) + 3) / 4);
+    const size_t mu_vec = (size_t)P.cond_ll * P.cond_ll * BLK;
+    for (int c = 0; c < W.SD.nchains; ++c) {
+        k_kubo_gram<<<wgs, 256, 0, h->stream>>>(P.Lm + (size_t)c * P.velems, P.sstride, m_rows, P.Rm + (size_t)c * P.velems, P.sstride, ncols, P.ksteps_total, ksplit, P.part, nbm, nbn);
+        k_kubo_gram_reduce<<<std::min(4096, (m_rows * ncols + 255) / 256), 256, 0, h->stream>>>(P.part, ksplit, nbm * KG_BLK, nbn * KG_BLK, m_rows, ncols, P.mu + (size_t)c * mu_vec, P.cond_ll, m0, n0);
+    }
+    W.rest_ev.emplace_back(g0, next_event(h));
+    return RSREC_OK;
 }
 
 }  // namespace
 
 // compute_moments_stochastic (recursion.f90:979-1234):  mu(:,:,n,m,i) = sum_k [T_{m-1}(H~) r_i]_k^H [v_a T_{n-1}(H~) v_b r_i]_k,
 // H~ = (H - b)/a.  The SpMMs are k_spmm5 over all atoms (blocks outside the reference's growing region are exact zeros); the
-// cond_ll x cond_ll moment contraction of a vector is one complex GEMM  L^H R  over the (atom, row) index (rocBLAS zgemm).
+// cond_ll x cond_ll moment contraction of a vector is one complex GEMM  L^H R  over the (atom, row) index (k_kubo_gram on the vectors in place).
 extern "C" int rsrec_kubo_moments(rsrec_t* h, int nvec, int nseed, const int32_t* seed_atoms, const double* seed_coef, int cond_ll, double a, double b,
                                   const double* v_a, const double* vo_a, const double* v_b, const double* vo_b, double* mu_nm) {
-    int rc = check_ready(h, "rsrec_kubo_moments");
-    if (rc) return rc;
+    XFER(check_ready(h, "rsrec_kubo_moments"));
     if (nvec < 0 || nseed < 1 || cond_ll < 1 || a == 0.0 || !v_a || !v_b || !mu_nm || (nvec > 0 && (!seed_atoms || !seed_coef)))
         return fail(h, RSREC_ERR_ARG, "rsrec_kubo_moments: bad argument");
     if (h->hoh && (!vo_a || !vo_b)) return fail(h, RSREC_ERR_ARG, "rsrec_kubo_moments: hoh requires vo_a and vo_b");
@@ -3141,181 +3363,42 @@ extern "C" int rsrec_kubo_moments(rsrec_t* h, int nvec, int nseed, const int32_t
     reset_timing(h);
     if (nvec == 0) return RSREC_OK;
     release_kubo_buffers(h, false, true);                          // (the integrand's buffers; this call's own stay for the next one)
-    rc = build_kubo_operator(h, 0, v_a, vo_a); if (rc) return rc;
-    rc = build_kubo_operator(h, 1, v_b, vo_b); if (rc) return rc;
-    if (h->hoh && h->nmax > 0) { rc = build_kubo_hbulk(h); if (rc) return rc; }
-    const int kk = h->kk;
-    const size_t velems = (size_t)(kk + 1) * BLD, nd = (size_t)kk * BLD;
-    const int nchunk = std::min(cond_ll, 64);                // right vectors per contraction
-    // The moment contraction L^H R is k_kubo_gram on the vectors where they lie (CI layout = dense row-major (18 kk) x 18 matrices side by
-    // side): the slots of Lm / Rm ARE the left / right vectors, written there by the SpMMs themselves.
-    // device memory: 11 work vectors, `lchunk` left vectors, one chunk of right vectors, the slices' partial blocks, one vector's moments.
-    // The left matrix is held in chunks of `lchunk` vectors (all of them if they fit: cond_ll x kk x 5184 B is 21 GB for cond_ll = 500
-    // on 8 000 atoms, 252 GB on 10^5): each chunk continues the left recurrence where the previous one stopped and is contracted
-    // with ALL right vectors, so the right recurrence (2 of the 3 SpMMs per moment order) is repeated once per chunk.
-    size_t free_b = 0, total_b = 0;
-    HIPCK(h, hipMemGetInfo(&free_b, &total_b));
-    size_t reusable = 0;
-    for (int v = 0; v < 6; ++v) reusable += h->d_vec[v].bytes;
-    for (auto& kb : h->d_kubo) reusable += kb.bytes;             // the buffers of the previous call (reused where they are large enough)
-    const double budget = 0.9 * (double)(free_b + reusable);
-    const int ksteps_total = (int)((NB * (size_t)kk + 3) / 4);            // k-steps of 4 rows (the last one may end inside the zero block)
-    const int nbn_max = (nchunk * NB + KG_BLK - 1) / KG_BLK;
-    // slices of the row index per contraction: enough wave tasks for a few rounds of the device, at least 64 k-steps per task
-    auto ksplit_for = [&](int lc) {
-        const long blocks = (long)((lc * NB + KG_BLK - 1) / KG_BLK) * nbn_max;
-        long ksp = (12L * 8 * h->n_cu + blocks - 1) / std::max(1L, blocks);          // up to a dozen rounds of the device's wave slots
-        ksp = std::min<long>({ksp, 64, std::max(1, ksteps_total / 64)});
-        return (int)std::max<long>(8, (ksp + 7) / 8 * 8);
-    };
-    auto part_bytes = [&](int lc) { return (double)ksplit_for(lc) * ((lc * NB + KG_BLK - 1) / KG_BLK) * KG_BLK * (double)nbn_max * KG_BLK * 16.0; };
-    // Vectors in flight: the vectors of a call are independent (recursion.f90:1104: one pass of the loop each) and one whole-lattice product is
-    // kk / 8 groups -- 1 000 on 8 000 atoms, half a round of the device's wave slots per spin.  Up to 8 of them advance together as the CHAINS of
-    // every launch (chain c of a buffer slot lies c vectors behind chain 0, exactly like the sites of a recursion batch); each keeps its own
-    // left / right matrices and is contracted by itself.  A whole left matrix per vector goes first: vectors are added only while it fits.
-    auto need_for = [&](int lc, int nv) { return (11.0 + lc + nchunk) * nv * velems * 8 + part_bytes(lc) + (double)nv * cond_ll * cond_ll * BLK * 16.0; };
-    int lchunk = cond_ll;
-    if (h->opt_kubo_lchunk > 0) lchunk = (int)std::min<long>(cond_ll, h->opt_kubo_lchunk);
-    int nbv = (int)std::min<long>(nvec, h->opt_kubo_vbatch > 0 ? h->opt_kubo_vbatch : 8);
-    while (nbv > 1 && need_for(lchunk, nbv) > budget) --nbv;
-    while (lchunk > 1 && need_for(lchunk, nbv) > budget) lchunk = (lchunk + 1) / 2;
-    if (need_for(lchunk, nbv) > budget)
-        return fail(h, RSREC_ERR_DEVICE, "rsrec_kubo_moments: %.1f GB needed for one left vector at a time on %d atoms, %.1f GB free", need_for(1, 1) * 1e-9, kk, free_b * 1e-9);
-    for (int v = 0; v < 6; ++v) h->d_vec[v].release();
-    const size_t sstride = (size_t)nbv * velems;                                // doubles between two slots of a buffer (nbv chains each)
-    DevBuf &work = h->d_kubo[0], &Lm = h->d_kubo[1], &Rm = h->d_kubo[2], &Part = h->d_kubo[3], &Mu = h->d_kubo[4];
-    {   // buffers that have to grow are given back first, so that the new sizes are asked of the memory the budget counted on
-        const size_t want[5] = {11 * sstride * 8, (size_t)lchunk * sstride * 8, (size_t)nchunk * sstride * 8, (size_t)part_bytes(lchunk), (size_t)nbv * cond_ll * cond_ll * BLK * 16};
-        for (int q = 0; q < 5; ++q) if (h->d_kubo[q].bytes < want[q]) h->d_kubo[q].release();
-    }
-    if (work.reserve(11 * sstride * 8) != hipSuccess || Lm.reserve((size_t)lchunk * sstride * 8) != hipSuccess || Rm.reserve((size_t)nchunk * sstride * 8) != hipSuccess ||
-        Part.reserve((size_t)part_bytes(lchunk)) != hipSuccess || Mu.reserve((size_t)nbv * cond_ll * cond_ll * BLK * 16) != hipSuccess) {
-        for (auto& kb : h->d_kubo) kb.release();
-        return fail(h, RSREC_ERR_DEVICE, "rsrec_kubo_moments: out of device memory");
-    }
-    HIPCK(h, hipMemsetAsync(Lm.p, 0, (size_t)lchunk * sstride * 8, h->stream));    // (block kk of every slot stays the zero block)
-    HIPCK(h, hipMemsetAsync(Rm.p, 0, (size_t)nchunk * sstride * 8, h->stream));
-    HIPCK(h, hipMemsetAsync(work.p, 0, 11 * sstride * 8, h->stream));            // block kk of every vector stays the zero block
-    double* V[11];
-    for (int v = 0; v < 11; ++v) V[v] = work.as<double>() + (size_t)v * sstride;
-    double *psiref = V[0], *w0 = V[1], *w1 = V[2], *w2 = V[3];
-    double *l0 = V[4], *l1 = V[9];                                              // T_{m0-2} r, T_{m0-1} r: the left recurrence across a chunk border
+    XFER(build_kubo_operator(h, 0, v_a, vo_a));
+    XFER(build_kubo_operator(h, 1, v_b, vo_b));
+    if (h->hoh && h->nmax > 0) XFER(build_kubo_hbulk(h));
+    KuboPlan P;
+    XFER(kubo_plan(h, nvec, cond_ll, P));
+    XFER(kubo_reserve(h, P));
     HIPCK(h, h->d_seed.reserve((size_t)nseed * 4));
     HIPCK(h, h->d_seedcoef.reserve((size_t)nseed * sizeof(double2)));
-    KuboCtx K;
-    rc = whole_lattice_ctx(h, nbv, nbv, K);
-    if (rc) return rc;
-    K.hps = V[6]; K.p1 = V[7]; K.p2 = V[8];
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> spmm_ev, gemm_ev;
-    K.spmm_ev = &spmm_ev;
-    std::vector<std::tuple<const Spmm5Operator*, int, double>> req_tab;
-    K.req = &req_tab;
-    h->n_kubo_chain_launches = 0;
-    hipEvent_t e_begin = next_event(h);
+    WholeLatticeCall W;
+    XFER(whole_lattice_begin(h, W, P.nbv, true));
+    W.hps = P.vec(KuboPlan::HPS); W.p1 = P.vec(KuboPlan::P1); W.p2 = P.vec(KuboPlan::P2);
+    W.ev_begin = next_event(h);
+    const KuboSeeds S{nseed, seed_atoms, seed_coef};
+    const size_t mu_vec = 2 * (size_t)BLK * cond_ll * cond_ll;                    // doubles of one vector's moments
     int n_left_chunks = 0;
-    auto Lslot = [&](int q) { return Lm.as<double>() + (size_t)q * sstride; };
-    auto Rslot = [&](int q) { return Rm.as<double>() + (size_t)q * sstride; };
-    for (int iv0 = 0; iv0 < nvec; iv0 += nbv) {
-        const int nb = std::min(nbv, nvec - iv0);                                 // vectors of this batch = chains of its launches
-        K.SD.nchains = nb;                                                        // (the last batch may be shorter; its slots keep nbv chains)
-        K.grid = s5_grid(h, dim3(256, (unsigned)nb), 0);
-        // r_i: psiref(l,l,seed(k)) = coef(k); seed atom 0 = unused entry
-        HIPCK(h, hipMemsetAsync(psiref, 0, sstride * 8, h->stream));
-        for (int c = 0; c < nb; ++c) {
-            const int iv = iv0 + c;
-            std::vector<int> s0; std::vector<double> c0;
-            for (int k = 0; k < nseed; ++k) {
-                const int at = seed_atoms[(size_t)iv * nseed + k];
-                if (at == 0) continue;
-                s0.push_back(at - 1); c0.push_back(seed_coef[2 * ((size_t)iv * nseed + k)]); c0.push_back(seed_coef[2 * ((size_t)iv * nseed + k) + 1]);
-            }
-            if (s0.empty()) return fail(h, RSREC_ERR_ARG, "rsrec_kubo_moments: vector %d has no seed", iv + 1);
-            XFER(xfer_h2d(h, h->d_seed.p, s0.data(), s0.size() * 4));
-            XFER(xfer_h2d(h, h->d_seedcoef.p, c0.data(), c0.size() * 8));
-            k_seed<LayoutCI><<<1, 64, 0, h->stream>>>(psiref + (size_t)c * velems, velems, h->d_seed.as<int>(), h->d_seedcoef.as<double2>(), (int)s0.size());
-            HIPCK(h, hipStreamSynchronize(h->stream));                            // the seed tables are reused by the next vector
-        }
-        const size_t cpy = ((size_t)(nb - 1) * velems + nd) * 8;                  // the chains of a slot, up to the last one's zero block
-        for (int m0 = 0; m0 < cond_ll; m0 += lchunk) {
-            const int ml = std::min(lchunk, cond_ll - m0), m_rows = ml * NB;
-            ++n_left_chunks;
-            // left vectors  T_{m-1}(H~) r,  m = m0 .. m0 + ml - 1 (recursion.f90:1120-1142), each written by its SpMM into its slot of Lm;
-            // the recurrence reads the two slots before it -- across a chunk border the copies l0 = T_{m0-2} r, l1 = T_{m0-1} r
-            for (int m = m0; m < m0 + ml; ++m) {
-                double* out = Lslot(m - m0);
-                const double* prev1 = m - 1 >= m0 ? Lslot(m - 1 - m0) : l1;
-                const double* prev2 = m - 2 >= m0 ? Lslot(m - 2 - m0) : (m - 2 == m0 - 1 ? l1 : l0);
-                if (m == 0) HIPCK(h, hipMemcpyAsync(out, psiref, cpy, hipMemcpyDeviceToDevice, h->stream));
-                else if (m == 1) kubo_apply_h(K, prev1, out, cheb_epilogue(true, prev1, nullptr, a, b));
-                else kubo_apply_h(K, prev1, out, cheb_epilogue(false, prev1, prev2, a, b));
-            }
-            if (m0 + ml < cond_ll) {                                          // state for the next chunk (its slots are about to be reused)
-                if (ml >= 2) HIPCK(h, hipMemcpyAsync(l0, Lslot(ml - 2), cpy, hipMemcpyDeviceToDevice, h->stream));
-                else HIPCK(h, hipMemcpyAsync(l0, l1, cpy, hipMemcpyDeviceToDevice, h->stream));
-                HIPCK(h, hipMemcpyAsync(l1, Lslot(ml - 1), cpy, hipMemcpyDeviceToDevice, h->stream));
-            }
+    for (int iv0 = 0; iv0 < nvec; iv0 += P.nbv) {
+        const int nb = std::min(P.nbv, nvec - iv0);                               // vectors of this batch = chains of its launches
+        whole_lattice_batch(W, nb, false);
+        XFER(kubo_seed_batch(h, P, S, iv0, nb));
+        for (int m0 = 0; m0 < cond_ll; m0 += P.lchunk, ++n_left_chunks) {
+            XFER(kubo_left_chunk(W, P, m0, a, b));
             // right vectors  v_a T_{n-1}(H~) v_b r  (:1154-1187), written into the slots of Rm and contracted with the left vectors of
             // this chunk, 64 at a time
-            double *y0 = w0, *y1 = w1, *y2 = w2;
-            kubo_apply_v(K, h->kubo_op[1], psiref, y1);                       // v1 = v0 = v_b r
+            ChebyshevStepper Y{P.vec(KuboPlan::Y), P.vec(KuboPlan::Y + 1), P.vec(KuboPlan::Y + 2)};
+            whole_lattice_apply_v(W, h->kubo_op[1], P.vec(KuboPlan::PSIREF), Y.cur);      // v1 = v0 = v_b r
             for (int n = 0; n < cond_ll; ++n) {
-                if (n == 1) {
-                    std::swap(y0, y1);
-                    kubo_apply_h(K, y0, y1, cheb_epilogue(true, y0, nullptr, a, b));
-                } else if (n > 1) {
-                    kubo_apply_h(K, y1, y2, cheb_epilogue(false, y1, y0, a, b));
-                    double* o = y0; y0 = y1; y1 = y2; y2 = o;
-                }
-                const int nl = n % nchunk;
-                kubo_apply_v(K, h->kubo_op[0], y1, Rslot(nl));
-                if (nl == nchunk - 1 || n == cond_ll - 1) {
-                    const int ncols = (nl + 1) * NB, n0 = n - nl;
-                    // C[(m,c)][(n,c')] = sum_{k,r} conj(L_m[(k,r)][c]) R_n[(k,r)][c']: blocks of C x `ksplit` slices of (k,r), one wave each.
-                    const int bmr = KG_BLK, bnc = KG_BLK;
-                    const int nbm = (m_rows + bmr - 1) / bmr, nbn = (ncols + bnc - 1) / bnc;
-                    // slices: the multiple of 8 (<= what the partial buffer was sized for, >= 64 k-steps per task) that fills whole rounds of
-                    // the device's wave slots best -- 361 blocks x 24 slices are 4.2 rounds of 2 048 slots (85 % of the last round idle), x 32 are 5.6
-                    int ksplit = 8;
-                    {
-                        const long slots = 8L * h->n_cu, cap = std::min<long>(ksplit_for(lchunk), std::max(8, ksteps_total / 64 / 8 * 8));
-                        double best = 0.0;
-                        for (long c = 8; c <= cap; c += 8) {
-                            const long tasks = (long)nbm * nbn * c, rounds = (tasks + slots - 1) / slots;
-                            const double eff = (double)tasks / (double)(rounds * slots) * (rounds >= 3 ? 1.0 : 0.9);   // (few rounds: the tail of the slowest wave shows)
-                            if (eff > best + 1e-9) { best = eff; ksplit = (int)c; }
-                        }
-                    }
-                    HIPCK(h, hipGetLastError());
-                    hipEvent_t g0 = next_event(h);
-                    const unsigned wgs = 8u * (unsigned)(((long)nbm * nbn * (ksplit / 8) + 3) / 4);
-                    // one contraction per vector of the batch: its matrices are the chain-c columns of the slots (leading dimension = a whole slot)
-                    for (int c = 0; c < nb; ++c) {
-                        k_kubo_gram<<<wgs, 256, 0, h->stream>>>(Lm.as<double>() + (size_t)c * velems, sstride, m_rows, Rm.as<double>() + (size_t)c * velems, sstride, ncols, ksteps_total, ksplit, Part.as<double2>(), nbm, nbn);
-                        k_kubo_gram_reduce<<<std::min(4096, (m_rows * ncols + 255) / 256), 256, 0, h->stream>>>(Part.as<double2>(), ksplit, nbm * bmr, nbn * bnc, m_rows, ncols, Mu.as<double2>() + (size_t)c * cond_ll * cond_ll * BLK, cond_ll, m0, n0);
-                    }
-                    gemm_ev.emplace_back(g0, next_event(h));
-                }
+                Y.step(W, n, a, b);
+                whole_lattice_apply_v(W, h->kubo_op[0], Y.cur, P.Rslot(n % P.nchunk));
+                if (n % P.nchunk == P.nchunk - 1 || n == cond_ll - 1) XFER(kubo_contract(W, P, m0, n));
             }
         }
         HIPCK(h, hipGetLastError());
-        XFER(xfer_d2h(h, mu_nm + 2 * (size_t)BLK * cond_ll * cond_ll * iv0, Mu.p, (size_t)nb * cond_ll * cond_ll * BLK * 16));
+        XFER(xfer_d2h(h, mu_nm + mu_vec * iv0, P.mu, (size_t)nb * mu_vec * 8));
     }
-    hipEvent_t e_end = next_event(h);
-    HIPCK(h, hipStreamSynchronize(h->stream));
-    HIPCK(h, hipGetLastError());
-    h->t_total_ms = ev_ms(e_begin, e_end);
-    for (auto& pr : spmm_ev) h->t_hop_ms += ev_ms(pr.first, pr.second);          // the SpMM kernels (H and velocity products)
-    for (auto& pr : gemm_ev) h->t_rest_ms += ev_ms(pr.first, pr.second);         // "rest_ms" here: the moment contractions (k_kubo_gram + its reduction)
-    h->n_hop_launch = (double)spmm_ev.size();
+    XFER(whole_lattice_end(h, W, true));
     h->n_kubo_left_chunks = n_left_chunks;
-    // work in the reference's terms: every product is over the whole lattice -- one block multiply per (atom, present slot)
-    {
-        double fan = 0.0;
-        for (int i = 0; i < kk; ++i)
-            for (int s2 = 0; s2 < h->nslots; ++s2) if (h->nbr[(size_t)i * h->nslots + s2] >= 0) fan += 1.0;
-        h->n_block_mult = fan * h->n_kubo_chain_launches;
-        h->n_atom_steps = (double)kk * h->n_kubo_chain_launches;
-    }
     return RSREC_OK;
 }
 
@@ -3402,29 +3485,6 @@ extern "C" int rsrec_kubo_integrand(rsrec_t* h, int nvec, int cond_ll, const dou
     return RSREC_OK;
 }
 
-namespace {
-
-// h as ham_vec_matmul applies it (recursion.f90:913-977): per-type blocks ee (per-atom hall for the impurity region) with l.s added to
-// the on-site block -- whatever hamiltonian%hoh says.  Without hoh that is set 0 of s5_op; with hoh a table of its own.
-int build_plain_operator(rsrec_t* h) {
-    const int ntau = h->nmax + h->ntype, nfs = h->nslots + 1;
-    const size_t B = 2 * (size_t)BLK;
-    std::vector<const double*> blk((size_t)ntau * nfs, nullptr);
-    std::vector<double> onsite((size_t)ntau * B);
-    for (int tau = 0; tau < ntau; ++tau) {
-        const int ty = tau < h->nmax ? h->iz0[tau] : tau - h->nmax;
-        const double* base = tau < h->nmax ? h->host_hall.data() + B * (size_t)h->hslots * tau : h->host_ee.data() + B * (size_t)h->hslots * (tau - h->nmax);
-        for (size_t e = 0; e < B; ++e) onsite[(size_t)tau * B + e] = base[e] + h->host_lsham[B * ty + e];
-        blk[(size_t)tau * nfs] = onsite.data() + (size_t)tau * B;
-        for (int s = 1; s < h->nslots; ++s) blk[(size_t)tau * nfs + s] = base + B * s;
-    }
-    const char* msg = h->orb_plain.build_custom(h->nslots, ntau, 1, blk);
-    if (msg) return fail(h, RSREC_ERR_DEVICE, "plain operator table: %s", msg);
-    return RSREC_OK;
-}
-
-}  // namespace
-
 // chebyshev_orbital_mod (recursion.f90:2834-3049), the moment part (:2893-3013), device-resident: the seeds are chains advanced together.
 // For seed atom s:  psiref = 1 on s;  left = i (Y H~ X - X H~ Y) psiref  (X, Y = alat cr(1,:), alat cr(2,:); H~ = ham_vec_matmul, the
 // plain operator also when hoh is set);  v_1 = psiref, v_2 = H~' v_1, v_n = 2 H~' v_{n-1} - v_{n-2}  (H~' = ham_hoh_vec_matmul with hoh);
@@ -3433,8 +3493,7 @@ int build_plain_operator(rsrec_t* h) {
 //           divides by kk afterwards, :3006);  mu_seed (optional) complex (18,18,lld,nseeds): every seed's contribution.
 extern "C" int rsrec_orbital_moments(rsrec_t* h, int nseeds, const int32_t* seed_atoms, int lld, double a, double b, const double* cr, double alat,
                                      double* mu_orb, double* mu_seed) {
-    int rc = check_ready(h, "rsrec_orbital_moments");
-    if (rc) return rc;
+    XFER(check_ready(h, "rsrec_orbital_moments"));
     if (nseeds < 0 || lld < 1 || a == 0.0 || !cr || !mu_orb || (nseeds > 0 && !seed_atoms)) return fail(h, RSREC_ERR_ARG, "rsrec_orbital_moments: bad argument");
     XFER(check_seeds(h, "rsrec_orbital_moments", seed_atoms, (size_t)nseeds, 1));
     if (!h->s5_built) return fail(h, RSREC_ERR_ARG, "rsrec_orbital_moments: lattice has too many neighbour slots for the SpMM kernel");
@@ -3444,13 +3503,12 @@ extern "C" int rsrec_orbital_moments(rsrec_t* h, int nseeds, const int32_t* seed
     if (nseeds == 0) return RSREC_OK;
     const int kk = h->kk;
     const bool hoh = h->hoh != 0;
-    if (hoh) { rc = build_plain_operator(h); if (rc) return rc; }
+    if (hoh) XFER(build_plain_operator(h));
     const Spmm5Operator& plain = hoh ? h->orb_plain : h->s5_op;
     const size_t velems = (size_t)(kk + 1) * BLD;
     const int nvec = hoh ? 5 : 4;                                  // left, v0, v1, v2 (+ h v of the two-pass product)
     BatchPlan bp;
-    rc = plan_batch(h, nseeds, nvec, velems / 2, bp);
-    if (rc) return rc;
+    XFER(plan_batch(h, nseeds, nvec, velems / 2, bp));
     const int B = bp.batch;
     for (int v = 0; v < nvec; ++v) HIPCK(h, h->d_vec[v].reserve((size_t)B * velems * sizeof(double)));
     XFER(reserve_partials(h, B, 2 * (size_t)B * 256 * 1296 * sizeof(double)));
@@ -3459,16 +3517,13 @@ extern "C" int rsrec_orbital_moments(rsrec_t* h, int nseeds, const int32_t* seed
     HIPCK(h, h->d_scal.reserve((size_t)3 * kk * sizeof(double)));
     HIPCK(h, h->d_zsqr.reserve((size_t)B * lld * BLK * sizeof(double2)));           // the chains' moments
     XFER(xfer_h2d(h, h->d_scal.p, cr, (size_t)3 * kk * sizeof(double)));
-    KuboCtx K;
-    rc = whole_lattice_ctx(h, B, B, K);
-    if (rc) return rc;
+    WholeLatticeCall W;
+    XFER(whole_lattice_begin(h, W, B, true));
+    W.hps = hoh ? h->d_vec[4].as<double>() : nullptr;
+    W.ev_begin = next_event(h);
     double2* d_out = h->d_zsqr.as<double2>();
     const size_t ostr = (size_t)lld * BLK;
     std::vector<double> host_out;
-    hipEvent_t e_begin = next_event(h);
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> spmm_ev;
-    std::vector<std::tuple<const Spmm5Operator*, int, double>> req_tab;
-    K.spmm_ev = &spmm_ev; K.req = &req_tab;
     for (int c0 = 0; c0 < nseeds; c0 += B) {
         const int nb = std::min(B, nseeds - c0);
         std::vector<int> s0;
@@ -3476,27 +3531,19 @@ extern "C" int rsrec_orbital_moments(rsrec_t* h, int nseeds, const int32_t* seed
         stage_seeds(seed_atoms, nullptr, c0, nb, 1, s0, one);
         XFER(xfer_h2d(h, h->d_seed.p, s0.data(), s0.size() * 4));
         XFER(xfer_h2d(h, h->d_seedcoef.p, one.data(), one.size() * 8));
-        K.CV.cpo = K.SD.cpo = K.SD.nchains = nb;                      // (the last batch may be shorter: its chains share the order row)
-        K.grid = s5_grid(h, dim3(256, nb), 0);
+        whole_lattice_batch(W, nb, true);
         double* left = h->d_vec[0].as<double>();
-        double *v0 = h->d_vec[1].as<double>(), *v1 = h->d_vec[2].as<double>(), *v2 = h->d_vec[3].as<double>();
-        K.hps = hoh ? h->d_vec[4].as<double>() : nullptr; K.p1 = nullptr; K.p2 = nullptr;
+        ChebyshevStepper V{h->d_vec[1].as<double>(), h->d_vec[2].as<double>(), h->d_vec[3].as<double>()};
         for (int v = 0; v < nvec; ++v) HIPCK(h, hipMemsetAsync(h->d_vec[v].p, 0, (size_t)nb * velems * sizeof(double), h->stream));
-        k_seed<LayoutCI><<<nb, 64, 0, h->stream>>>(v1, velems, h->d_seed.as<int>(), h->d_seedcoef.as<double2>(), 1);     // v_1 = psiref
+        k_seed<LayoutCI><<<nb, 64, 0, h->stream>>>(V.cur, velems, h->d_seed.as<int>(), h->d_seedcoef.as<double2>(), 1);     // v_1 = psiref
         // t = H~ psiref with the plain operator, then the position factors
-        kubo_spmm(K, plain, 0, v1, left, nullptr, cheb_epilogue(true, v1, nullptr, a, b));
+        whole_lattice_spmm(W, plain, 0, V.cur, left, nullptr, cheb_epilogue(true, V.cur, nullptr, a, b));
         k_orb_left<<<dim3(std::min(kk, 1024), nb), 256, 0, h->stream>>>(kk, velems, h->d_seed.as<int>(), h->d_scal.as<double>(), alat, reinterpret_cast<double2*>(left));
-        const dim3 grid_mf(std::max(1, std::min(mfma_workgroups_per_chain(h, nb), (K.CV.ostride / GROUP + MF_WAVES - 1) / MF_WAVES)), nb);
+        const dim3 grid_mf(std::max(1, std::min(mfma_workgroups_per_chain(h, nb), (W.CV.ostride / GROUP + MF_WAVES - 1) / MF_WAVES)), nb);
         const dim3 gl = level_grid(h, grid_mf, 0);
         for (int n = 0; n < lld; ++n) {
-            if (n == 1) {
-                std::swap(v0, v1);
-                kubo_apply_h(K, v0, v1, cheb_epilogue(true, v0, nullptr, a, b));
-            } else if (n > 1) {
-                kubo_apply_h(K, v1, v2, cheb_epilogue(false, v1, v0, a, b));
-                double* o = v0; v0 = v1; v1 = v2; v2 = o;
-            }
-            k_mfma_adot<<<gl, MF_WAVES * 64, 0, h->stream>>>(K.CV, 0, kk, left, v1, h->d_partial.as<double>());
+            V.step(W, n, a, b);
+            k_mfma_adot<<<gl, MF_WAVES * 64, 0, h->stream>>>(W.CV, 0, kk, left, V.cur, h->d_partial.as<double>());
             int n2 = gl.x;
             const double* p2 = presum(h, h->d_partial.as<double>(), nb, n2, 1296);
             k_reduce_gram_out<<<nb, 1024, 0, h->stream>>>(p2, n2, d_out + (size_t)n * BLK, ostr, 1);
@@ -3510,10 +3557,7 @@ extern "C" int rsrec_orbital_moments(rsrec_t* h, int nseeds, const int32_t* seed
             if (mu_seed) memcpy(mu_seed + (size_t)(c0 + q) * ostr * 2, src, ostr * 2 * sizeof(double));
         }
     }
-    hipEvent_t e_end = next_event(h);
-    HIPCK(h, hipStreamSynchronize(h->stream));
-    finish_timing(h, e_begin, e_end, spmm_ev);
-    h->n_hop_launch = (double)spmm_ev.size();
+    XFER(whole_lattice_end(h, W));
     h->res_kind = 0;
     return RSREC_OK;
 }
@@ -3522,40 +3566,33 @@ extern "C" int rsrec_orbital_moments(rsrec_t* h, int nseeds, const int32_t* seed
 // psi(18,18,kk) in the reference's layout (host arrays); with vel = 1: velo_vec_matmul / velo_hoh_vec_matmul (:587 / :656) with
 // the operator blocks v_op (and vo_op with hoh), no scaling.
 extern "C" int rsrec_apply_operator(rsrec_t* h, int vel, const double* v_op, const double* vo_op, const double* psi_in, double* psi_out, double a, double b) {
-    int rc = check_ready(h, "rsrec_apply_operator");
-    if (rc) return rc;
+    XFER(check_ready(h, "rsrec_apply_operator"));
     if (!psi_in || !psi_out || (vel != 1 && a == 0.0) || (vel == 1 && (!v_op || (h->hoh && !vo_op))) || vel < 0 || vel > 2) return fail(h, RSREC_ERR_ARG, "rsrec_apply_operator: bad argument");
     if (!h->s5_built) return fail(h, RSREC_ERR_ARG, "rsrec_apply_operator: lattice has too many neighbour slots for the SpMM kernel");
     HIPCK(h, hipSetDevice(h->device));
     reset_timing(h);
     const int kk = h->kk;
     const size_t velems = (size_t)(kk + 1) * BLD, nd = (size_t)kk * BLD;
-    if (vel == 1) { rc = build_kubo_operator(h, 0, v_op, vo_op); if (rc) return rc; if (h->hoh && h->nmax > 0) { rc = build_kubo_hbulk(h); if (rc) return rc; } }
-    if (vel == 2 && h->hoh) { rc = build_plain_operator(h); if (rc) return rc; }        // ham_vec_matmul under hoh: the plain operator (recursion.f90:913)
+    if (vel == 1) { XFER(build_kubo_operator(h, 0, v_op, vo_op)); if (h->hoh && h->nmax > 0) XFER(build_kubo_hbulk(h)); }
+    if (vel == 2 && h->hoh) XFER(build_plain_operator(h));                              // ham_vec_matmul under hoh: the plain operator (recursion.f90:913)
     for (int v = 0; v < 6; ++v) HIPCK(h, h->d_vec[v].reserve(velems * 8));
     for (int v = 0; v < 6; ++v) HIPCK(h, hipMemsetAsync(h->d_vec[v].p, 0, velems * 8, h->stream));
-    KuboCtx K;
-    rc = whole_lattice_ctx(h, 1, 1, K);
-    if (rc) return rc;
+    WholeLatticeCall W;
+    XFER(whole_lattice_begin(h, W, 1, false));
     double* in = h->d_vec[0].as<double>(); double* out = h->d_vec[1].as<double>(); double* tmp = h->d_vec[2].as<double>();
-    K.hps = h->d_vec[3].as<double>(); K.p1 = h->d_vec[4].as<double>(); K.p2 = h->d_vec[5].as<double>();
+    W.hps = h->d_vec[3].as<double>(); W.p1 = h->d_vec[4].as<double>(); W.p2 = h->d_vec[5].as<double>();
     XFER(xfer_h2d(h, tmp, psi_in, nd * 8));
-    hipEvent_t e0 = next_event(h);
+    W.ev_begin = next_event(h);
     k_block_transpose<true><<<std::min(kk, 2048), 384, 0, h->stream>>>(kk, reinterpret_cast<const double2*>(tmp), reinterpret_cast<double2*>(in));
-    if (vel == 1) kubo_apply_v(K, h->kubo_op[0], in, out);
-    else if (vel == 2 && h->hoh) {
-        kubo_spmm(K, h->orb_plain, 0, in, tmp, nullptr);
-        k_cheb_combine<true><<<(int)std::min<size_t>(4096, (nd + 255) / 256), 256, 0, h->stream>>>(nd, tmp, in, nullptr, out, a, b);
-    } else {
-        kubo_apply_h(K, in, tmp);
+    if (vel == 1) whole_lattice_apply_v(W, h->kubo_op[0], in, out);
+    else {
+        if (vel == 2 && h->hoh) whole_lattice_spmm(W, h->orb_plain, 0, in, tmp, nullptr);
+        else whole_lattice_apply_h(W, in, tmp);
         k_cheb_combine<true><<<(int)std::min<size_t>(4096, (nd + 255) / 256), 256, 0, h->stream>>>(nd, tmp, in, nullptr, out, a, b);
     }
     k_block_transpose<false><<<std::min(kk, 2048), 384, 0, h->stream>>>(kk, reinterpret_cast<const double2*>(out), reinterpret_cast<double2*>(tmp));
-    hipEvent_t e1 = next_event(h);
-    HIPCK(h, hipGetLastError());
+    XFER(whole_lattice_end(h, W));                        // (the span ends before the download)
     XFER(xfer_d2h(h, psi_out, tmp, nd * 8));
-    HIPCK(h, hipStreamSynchronize(h->stream));
-    h->t_total_ms = ev_ms(e0, e1);
     return RSREC_OK;
 }
 
