@@ -12,6 +12,7 @@
 #
 # Outputs (oracle/_ref/dropin/, git-ignored like the rest of oracle/_ref: they contain reference object code):
 #   oracle/_ref/damping_gpu.x       = tests/fortran/damping_gpu_driver.f90 on the same objects (tests/test_damping_dropin.py)
+#   oracle/_ref/jijk_gpu.x          = tests/fortran/jijk_gpu_driver.f90 on the same objects (tests/test_jijk_dropin.py)
 #   oracle/_ref/contour_gpu.x       = tests/fortran/contour_gpu_driver.f90 on the same objects (tests/test_contour_dropin.py)
 #   oracle/_ref/rslmto_dropin.x     = the reference's main program + librsrec behind its recursion / green / bands / hamiltonian / lattice / density_of_states / exchange / conductivity modules
 set -euo pipefail
@@ -74,4 +75,9 @@ fc "$ROOT/tests/fortran/contour_gpu_driver.f90" contour_gpu_driver
 "$FC" "$OUT/obj/contour_gpu_driver.o" $LIBOBJS -fopenmp -L"$MKLDIR" -lmkl_rt -Wl,-rpath,"$MKLDIR" \
   -L"$ROOT/rslmtoasa_amd" -lrsrec -Wl,-rpath,'$ORIGIN/../../rslmtoasa_amd' -Wl,-rpath,/opt/rocm/lib \
   -o "$ROOT/oracle/_ref/contour_gpu.x"
+# tests/fortran/jijk_gpu_driver.f90: the same flow on an input with trios, then calculate_jijk (GPU type, or the reference's own in plain mode)
+fc "$ROOT/tests/fortran/jijk_gpu_driver.f90" jijk_gpu_driver
+"$FC" "$OUT/obj/jijk_gpu_driver.o" $LIBOBJS -fopenmp -L"$MKLDIR" -lmkl_rt -Wl,-rpath,"$MKLDIR" \
+  -L"$ROOT/rslmtoasa_amd" -lrsrec -Wl,-rpath,'$ORIGIN/../../rslmtoasa_amd' -Wl,-rpath,/opt/rocm/lib \
+  -o "$ROOT/oracle/_ref/jijk_gpu.x"
 echo "built $ROOT/oracle/_ref/rslmto_dropin.x (zero-edit drop-in: the reference's own main program)"

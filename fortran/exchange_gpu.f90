@@ -21,11 +21,18 @@
 !                                 One deliberate deviation: the reference never initialises spin_i in this routine, so it starts
 !                                 undefined and accumulates across the pairs; here it starts at zero for every pair.
 !                                 damping-energy.out uses the last pair's factor, as the reference's code does.
-!   calculate_moment_of_inertia, calculate_jij_auxgreen, calculate_jijk : these read green%gij / gji ..., which the constructor
-!                                 released.  Each is a wrapper: green_gpu%fetch_intersite first (the host arrays, allocated and filled by
-!                                 the inherited calculate_intersite_gf / _twoindex from the recursion's host coefficients), then the
-!                                 inherited routine.  None is ported to the device; the moment of inertia in particular defines no
-!                                 result to match (its final loop indexes with nv after the energy loop has ended, :869-882).
+!   calculate_jijk              : (:338-601) one rsrec_spin_lattice call for all trios on the resident chains (timer region jijk-gpu):
+!                                 apar = (c + vmad, dele, qpar) of atoms i, j, k from potential, dmat = one spin block of the
+!                                 reference's own disp_matrix of atom k for uni_disp, then the reference's three stdout lines per trio
+!                                 (:558-560), format for format.  Neither green%gij / gji nor the 18 work arrays per trio are formed.
+!                                 Falls back to the host route below when an atom has lmax /= 2, when the pairs are not exactly the
+!                                 trios' pairs, or when the rank does not hold every pair (more than one rank).
+!   calculate_moment_of_inertia, calculate_jij_auxgreen : these read green%gij / gji ..., which the constructor released.  Each is a
+!                                 wrapper: green_gpu%fetch_intersite first (the host arrays, allocated and filled by the inherited
+!                                 calculate_intersite_gf / _twoindex from the recursion's host coefficients), then the inherited
+!                                 routine.  The moment of inertia defines no result to match (its final loop indexes with nv after
+!                                 the energy loop has ended, :869-882).  Jij_aux is on the device through the library
+!                                 (rsrec_exchange_aux) and Exchange.aux only: this type keeps the host route for it.
 !   calculate_exchange_gauss_legendre : (:1756-1919) one rsrec_exchange_contour call for the rank's pairs on the resident chains
 !                                 (green%calculate_intersite_gf_eta + the 64-point loop of :1811-1867: the terminator once per chain
 !                                 instead of once per point, no _eta array, no gij_eta_to_gij), x and w from the reference's own
@@ -567,10 +574,95 @@ contains
       call this%exchange%calculate_jij_auxgreen()
    end subroutine gpu_calculate_jij_auxgreen
 
+   !> calculate_jijk (:338-601) as one rsrec_spin_lattice call for all trios on the resident chains of the pair recursion: the pairs are
+   !> the trios' (i,j), (i,k), (j,k) (lattice.f90:644-651).  apar: (c + vmad, dele, qpar) per l, spin and atom, as p_matrix, auxiliary_gij
+   !> and transform_pmatrix read them; dmat: one spin block of the reference's own disp_matrix of atom k for uni_disp (:489-495, :507).
+   !> Then the reference's three stdout lines per trio (:558-560).  Host route (fetch_intersite + the inherited routine) when an atom has
+   !> lmax /= 2, when the pairs are not exactly the trios' pairs, or when this rank does not hold every pair (more than one rank).
    subroutine gpu_calculate_jijk(this)
       class(exchange_gpu) :: this
-      call host_intersite(this)
-      call this%exchange%calculate_jijk()
+      integer :: ntrio, njij, nen, t, a, l, s, at, ikind, q
+      integer :: atoms(3)
+      logical :: device
+      integer(c_int) :: rc, sym_i
+      type(c_ptr) :: ctx
+      integer(c_int), dimension(:), allocatable, target :: same
+      real(rp), dimension(:), allocatable, target :: ene
+      real(rp), dimension(:, :, :, :, :), allocatable, target :: apar
+      real(rp), dimension(:, :), allocatable, target :: jijk
+      real(rp), dimension(:, :), allocatable :: uni
+      complex(rp), dimension(:, :, :), allocatable, target :: dmat
+      complex(rp), dimension(:, :), allocatable :: d18
+      real(rp) :: disp(3)
+
+      ntrio = this%lattice%njijk
+      njij = this%lattice%njij
+      ikind = -1
+      if (this%control%recur == 'block') ikind = 0
+      if (this%control%recur == 'chebyshev') ikind = 1
+      device = ntrio > 0 .and. njij == 3*ntrio .and. start_atom == 1 .and. end_atom == njij .and. ikind >= 0
+      if (device) then
+         do t = 1, ntrio
+            do a = 1, 3
+               at = this%lattice%iz(int(this%lattice%ijktrio(t, a)))
+               if (this%symbolic_atom(at)%potential%lmax /= 2) device = .false.
+            end do
+         end do
+      end if
+      if (.not. device) then
+         call host_intersite(this)
+         call this%exchange%calculate_jijk()
+         return
+      end if
+
+      nen = this%en%channels_ldos + 10
+      allocate (same(njij), ene(nen), apar(3, 3, 2, 3, ntrio), dmat(9, 9, ntrio), jijk(9, ntrio), uni(3, ntrio), d18(18, 18))
+      ene(:) = this%en%ene(1:nen)
+      jijk = 0.0_rp
+      do q = 1, njij
+         same(q) = 0
+         if (this%lattice%ijpair(q, 1) == this%lattice%ijpair(q, 2)) same(q) = 1
+      end do
+      do t = 1, ntrio
+         atoms(:) = int(this%lattice%ijktrio(t, 1:3))
+         do a = 1, 3
+            at = this%lattice%iz(atoms(a))
+            associate (pot => this%symbolic_atom(at)%potential)
+               do s = 1, 2
+                  do l = 0, 2
+                     apar(1, l + 1, s, a, t) = pot%c(l, s) + pot%vmad
+                     apar(2, l + 1, s, a, t) = pot%dele(l, s)
+                     apar(3, l + 1, s, a, t) = pot%qpar(l, s)
+                  end do
+               end do
+            end associate
+         end do
+         disp(:) = 1.0_rp*this%lattice%ijktrio(t, 4:6)
+         uni(1, t) = disp(1)/norm2(disp)
+         uni(2, t) = disp(2)/norm2(disp)
+         uni(3, t) = disp(3)/norm2(disp)
+         d18 = (0.0_rp, 0.0_rp)
+         call this%symbolic_atom(this%lattice%iz(atoms(3)))%disp_matrix(d18, uni(:, t), 2, this%lattice%wav)
+         dmat(:, :, t) = d18(1:9, 1:9)
+      end do
+      sym_i = 0
+      if (this%control%sym_term) sym_i = 1
+      ctx = rsrec_gpu_context()
+      call g_timer%start('jijk-gpu')
+      ! coefficients and terminators NULL: the chains recur_b_ij / chebyshev_recur_ij left on the device (i == j pairs: one chain)
+      rc = rsrec_spin_lattice(ctx, int(ikind, c_int), int(njij, c_int), c_loc(same), int(this%control%lld, c_int), int(nen, c_int), &
+                              c_loc(ene), int(this%en%nv1, c_int), real(this%en%fermi, c_double), sym_i, &
+                              real(this%en%energy_min, c_double), real(this%en%energy_max, c_double), c_null_ptr, c_null_ptr, &
+                              c_null_ptr, c_null_ptr, c_loc(apar), c_loc(dmat), 0_c_int, int(ntrio, c_int), c_loc(jijk), c_null_ptr)
+      call g_timer%stop('jijk-gpu')
+      if (rc /= 0) call g_logger%fatal('exchange_gpu: rsrec_spin_lattice: '//rsrec_error_string(ctx), __FILE__, __LINE__)
+      do t = 1, ntrio
+         atoms(:) = int(this%lattice%ijktrio(t, 1:3))
+         this%jijk(:) = jijk(:, t)
+         write (*, *) 'Jijk tensor between trio ', atoms(1), ',', atoms(2), ' and ', atoms(3), 'is (in meV/a.u.)'
+         write (*, '(A, "(", F7.4, ", ", F7.4, ", ", F7.4, ")")') ' Displacement vector: ', uni(1, t), uni(2, t), uni(3, t)
+         write (*, '(3F14.9)') this%jijk*(1.0d3/8.0d0/pi)*(13.605693122994d0/1.8897261246d0)
+      end do
    end subroutine gpu_calculate_jijk
 
 end module exchange_gpu_mod

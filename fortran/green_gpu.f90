@@ -20,8 +20,9 @@
 !> allocated (and zeroed) only when a host routine that fills them runs (`intersite_arrays`).  When `exchange_gpu` (exchange_gpu.f90)
 !> has taken the stage over -- `rsrec_exchange` forms Jij / Dij / Iij straight from the recursion's chains -- `calculate_intersite_gf`
 !> and `_twoindex` allocate and fill nothing; the first keeps only the reference's side effect on the recursion (zsqr, :434).
-!> The inherited routines of `exchange` that still read the host arrays (calculate_moment_of_inertia, calculate_jij_auxgreen,
-!> calculate_jijk) get them through `fetch_intersite`, which `exchange_gpu` calls before each of them: it allocates the arrays and runs
+!> The inherited routines of `exchange` that still read the host arrays (calculate_moment_of_inertia, calculate_jij_auxgreen, and
+!> calculate_jijk only where its device route does not apply: lmax /= 2, or more than one rank) get them through `fetch_intersite`,
+!> which `exchange_gpu` calls before each of them: it allocates the arrays and runs
 !> the inherited `calculate_intersite_gf` / `_twoindex` on the recursion's host coefficients (the idea of bands_gpu's `fetch_g0`).
 !------------------------------------------------------------------------------
 module green_gpu_mod

@@ -218,6 +218,30 @@ module rsrec_binding
          integer(c_int) :: rc
       end function
 
+      ! auxiliary-GF exchange tensor of the rank's pairs on the same chains (exchange.f90:171-335); jaux unscaled (caller: * 1.0d3/4/pi)
+      function rsrec_exchange_aux(handle, kind, npairs, same, lld, nen, ene, nv1, fermi, sym_term, energy_min, energy_max, a_inf, b_inf, &
+                                  coef_a, coef_b, apar, pair_offset, npairs_total, jaux, rows) &
+         bind(C, name='rsrec_exchange_aux') result(rc)
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: handle
+         integer(c_int), value :: kind, npairs, lld, nen, nv1, sym_term, pair_offset, npairs_total
+         real(c_double), value :: fermi, energy_min, energy_max
+         type(c_ptr), value :: same, ene, a_inf, b_inf, coef_a, coef_b, apar, jaux, rows
+         integer(c_int) :: rc
+      end function
+
+      ! spin-lattice coupling of the rank's trios, three pairs (i,j), (i,k), (j,k) each (exchange.f90:338-601); jijk unscaled
+      function rsrec_spin_lattice(handle, kind, npairs, same, lld, nen, ene, nv1, fermi, sym_term, energy_min, energy_max, a_inf, b_inf, &
+                                  coef_a, coef_b, apar, dmat, trio_offset, ntrios_total, jijk, rows) &
+         bind(C, name='rsrec_spin_lattice') result(rc)
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: handle
+         integer(c_int), value :: kind, npairs, lld, nen, nv1, sym_term, trio_offset, ntrios_total
+         real(c_double), value :: fermi, energy_min, energy_max
+         type(c_ptr), value :: same, ene, a_inf, b_inf, coef_a, coef_b, apar, dmat, jijk, rows
+         integer(c_int) :: rc
+      end function
+
       ! T_comm_xc of the rank's pairs on the Gauss-Legendre contour at e0 (green.f90:471-536 + exchange.f90:1804-1865); x, w host arrays
       function rsrec_exchange_contour(handle, kind, npairs, same, lld, npts, x, w, e0, sym_term, energy_min, energy_max, a_inf, b_inf, &
                                       coef_a, coef_b, dmat, pair_offset, npairs_total, xc, rows) &

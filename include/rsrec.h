@@ -307,6 +307,40 @@ int rsrec_damping(rsrec_t *h, int kind, int npairs, const int32_t *same, int lld
                   double energy_min, double energy_max, const double *a_inf, const double *b_inf, const double *coef_a, const double *coef_b,
                   const double *tmat, int pair_offset, int npairs_total, double *at_ef, double *total, double *rows);
 
+/* Exchange tensor in the auxiliary Green-function formalism for the pairs of one rank: exchange%calculate_jij_auxgreen
+ * (exchange.f90:171-335) on the chains rsrec_exchange reads (kernels_auxgreen.hpp: a third epilogue on g0 of a pair's chains in LDS; gij and
+ * gji are dressed with sqrt(Delta) and P_up - P_dn while their up-up and down-down blocks leave g0).  lmax = 2 only.
+ *   kind, same, lld, nen, ene, nv1, fermi, sym_term, energy_min, energy_max, a_inf, b_inf, coef_a, coef_b, pair_offset, npairs_total: as
+ *               rsrec_exchange (coef_a and coef_b NULL: the resident chains of the last seeded call; the same compaction and terminator rules)
+ *   apar        : real (2,3,2,2,npairs): (c + vmad, dele) per l = 0..2, spin (up, down) and side (atom i, atom j).  The library rounds them
+ *               and the energy to single precision where the reference's cmplx() without a KIND does (p_matrix, auxiliary_gij)
+ *   jaux        : real (9,npairs_total) out: simpson_f of the rows, UNSCALED (the reference prints them * 1.0d3 / 4 / pi); an i == j pair
+ *               carries J00 in row 1 and zeros in rows 2..9; this rank's pairs in their columns of the zero-padded image
+ *   rows        : real (9,nen,npairs) out or NULL: jtot_aux(nv, 1:9) = xx, xy, xz, yx, .. zz (imtrace * 0.5), or jtot_00 (imtrace * -1) in row 1
+ * Memory, repeatability, errors and timing as rsrec_damping; apar is staged per chunk. */
+int rsrec_exchange_aux(rsrec_t *h, int kind, int npairs, const int32_t *same, int lld, int nen, const double *ene, int nv1, double fermi,
+                       int sym_term, double energy_min, double energy_max, const double *a_inf, const double *b_inf, const double *coef_a,
+                       const double *coef_b, const double *apar, int pair_offset, int npairs_total, double *jaux, double *rows);
+
+/* Spin-lattice coupling Jijk of the atom trios of one rank: exchange%calculate_jijk (exchange.f90:338-601).  Trio t is the pairs 3t+1..3t+3
+ * = (i,j), (i,k), (j,k) of the call (lattice.f90:644-651), 4 chains each; one workgroup per (trio, energy) runs their Green stages one after
+ * another, keeps the canonical auxiliary blocks it needs (gij, gji, gki, gjk, gkj; gik is never read) in LDS and forms the 8 triple
+ * products there.  lmax = 2 only.
+ *   npairs      : 3 * ntrios.  kind .. coef_b as rsrec_exchange_aux; `same` per pair (a trio may repeat an atom)
+ *   apar        : real (3,3,2,3,ntrios): (c + vmad, dele, qpar) per l, spin and atom (i, j, k), rounded as in rsrec_exchange_aux
+ *   dmat        : complex (9,9,ntrios): one spin block of disp_matrix of atom k for the trio's unit displacement (symbolic_atom.f90:274-355)
+ *   trio_offset, ntrios_total: this rank's columns of the zero-padded image
+ *   jijk        : real (9,ntrios_total) out: simpson_f of the rows, UNSCALED (the reference prints them * (1.0d3 / 8 / pi) *
+ *               (13.605693122994 / 1.8897261246))
+ *   rows        : real (9,nen,ntrios) out or NULL: jijk_tot(nv, 1:9)
+ * Every array may be host or device memory.  The call runs in chunks of whole trios: device memory is bounded independent of ntrios.
+ * Fixed summation order, no atomics: two calls give the same bits and a trio's numbers do not depend on the other trios or on the
+ * chunking.  Errors and timing as rsrec_damping; npairs that is no multiple of 3 is RSREC_ERR_ARG. */
+int rsrec_spin_lattice(rsrec_t *h, int kind, int npairs, const int32_t *same, int lld, int nen, const double *ene, int nv1, double fermi,
+                       int sym_term, double energy_min, double energy_max, const double *a_inf, const double *b_inf, const double *coef_a,
+                       const double *coef_b, const double *apar, const double *dmat, int trio_offset, int ntrios_total, double *jijk,
+                       double *rows);
+
 /* Exchange couplings on the Gauss-Legendre contour at the Fermi level for the pairs of one rank: green%calculate_intersite_gf_eta
  * (green.f90:471-536) and exchange%calculate_exchange_gauss_legendre (exchange.f90:1804-1865) in one call, without the *_eta arrays
  * (kernels_contour.hpp: g of a pair's chains at a point stays in LDS).  Point k is the complex energy e0 + i (1 - x_k) / x_k and carries

@@ -43,6 +43,10 @@ _SIGNATURES = {
                        + [C.c_void_p] * 5 + [C.c_int, C.c_int] + [C.c_void_p] * 6),
     "rsrec_damping": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double]
                       + [C.c_void_p] * 5 + [C.c_int, C.c_int] + [C.c_void_p] * 3),
+    "rsrec_exchange_aux": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double]
+                           + [C.c_void_p] * 5 + [C.c_int, C.c_int] + [C.c_void_p] * 2),
+    "rsrec_spin_lattice": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double]
+                           + [C.c_void_p] * 6 + [C.c_int, C.c_int] + [C.c_void_p] * 2),
     "rsrec_exchange_contour": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_double,
                                          C.c_double] + [C.c_void_p] * 5 + [C.c_int, C.c_int] + [C.c_void_p] * 2),
     "rsrec_contour_occupation": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_double,

@@ -239,8 +239,23 @@ __device__ __forceinline__ double xc_quantity(const double* __restrict__ r, int 
     return r[13 + q - 39];
 }
 
-// simpson_f(fermi = .true., T = 0) (math.f90:1600-1632) of every output of every pair, and the cumulative second-order J of fort.150.
-// The reference's loop runs I = 2, nv1 + 9, 2 and reads Y(I + 1) one element past its arrays at the last I; that term is zero here.
+// simpson_f(fermi = .true., T = 0) (math.f90:1600-1632) of one integrand y(k) (0-based k; zero from nen on) with the Fermi weights fw,
+// in the reference's summation order.  Its loop runs I = 2, nv1 + 9, 2 and reads Y(I + 1) one element past its arrays at the last I;
+// that term is zero here.  The one Simpson rule of the exchange module's integrals (k_exchange_integrate, k_rows_integrate).
+template <class Y>
+__device__ __forceinline__ double xc_simpson_fermi(int nen, int nv1, double H, const double* __restrict__ fw, Y y) {
+#pragma clang fp contract(off)
+    const int itop = nv1 + 9;                                       // last I (1-based) of the loop
+    double A = 0.0;
+    for (int I = 2; I <= itop; I += 2) {
+        const int k = I - 1;                                        // 0-based index of Y(I)
+        const double f0 = fw[k - 1], f1 = k < nen ? fw[k] : 0.0, f2 = k + 1 < nen ? fw[k + 1] : 0.0;
+        A = ((A + y(k - 1) * f0) + 4.0 * y(k) * f1) + y(k + 1) * f2;
+    }
+    return H * A / 3.0;
+}
+
+// xc_simpson_fermi of every output of every pair, and the cumulative second-order J of fort.150.
 // grid = npairs, 128 threads: thread q < 67 integrates output q in the reference's summation order; thread 67 writes jcum.
 __global__ __launch_bounds__(128) void k_exchange_integrate(int nen, int nv1, const double* __restrict__ ene, const double* __restrict__ fw,
                                                             const double* __restrict__ integ, int col0, double* __restrict__ xc, double* __restrict__ so,
@@ -253,13 +268,7 @@ __global__ __launch_bounds__(128) void k_exchange_integrate(int nen, int nv1, co
     const int itop = nv1 + 9;                                       // last I (1-based) of the loop
     auto y = [&](int k) -> double { return k < nen ? xc_quantity(R + (size_t)k * XC_NINT, q < XC_NOUT ? q : 13) : 0.0; };
     if (q < XC_NOUT) {
-        double A = 0.0;
-        for (int I = 2; I <= itop; I += 2) {
-            const int k = I - 1;                                    // 0-based index of Y(I)
-            const double f0 = fw[k - 1], f1 = k < nen ? fw[k] : 0.0, f2 = k + 1 < nen ? fw[k + 1] : 0.0;
-            A = ((A + y(k - 1) * f0) + 4.0 * y(k) * f1) + y(k + 1) * f2;
-        }
-        A = H * A / 3.0;
+        const double A = xc_simpson_fermi(nen, nv1, H, fw, y);
         const int col = col0 + pair;
         if (q < 13) xc[13 * col + q] = A * 1.0e3 / 4.0 / pi;
         else if (q < 26) so[13 * col + q - 13] = A * 1.0e3 / 4.0 / pi;

@@ -41,6 +41,7 @@
 #include "kernels_kubo.hpp"
 #include "kernels_cond.hpp"
 #include "kernels_exchange.hpp"
+#include "kernels_auxgreen.hpp"
 #include "kernels_contour.hpp"
 #include "kernels_assemble.hpp"
 
@@ -2516,7 +2517,7 @@ int xc_fetch(rsrec_t* h, const double* src, double* stage, size_t n, const doubl
 namespace {
 
 // Call setup shared by the entry points that run a kernel per (pair, energy) on the four chains of every pair (rsrec_exchange,
-// rsrec_damping, rsrec_exchange_contour) or, with per = 1, per (site, point) on the one chain of every site (rsrec_contour_occupation): the coefficient-source rules, the compaction of resident i == j pairs, the chunking over pairs and the device buffers.
+// rsrec_damping, rsrec_exchange_contour, rsrec_exchange_aux, rsrec_spin_lattice) or, with per = 1, per (site, point) on the one chain of every site (rsrec_contour_occupation): the coefficient-source rules, the compaction of resident i == j pairs, the chunking over pairs and the device buffers.
 //   d_green_in : ene | the call's own inputs (fixed_in) | same | cbase | a_b (or mu_n) | b_sqrt | a_inf (or the Chebyshev kernel) | b_inf |
 //                the chunk's own inputs (chunk_in per pair)                                       (chunk-sized from a_b on)
 //   d_green_out: the rows of the chunk (row_doubles per pair) | the call's own outputs (fixed_out) | chunk_out per pair
@@ -2545,7 +2546,7 @@ size_t even(size_t n) { return (n + 1) & ~(size_t)1; }
 
 int pair_call_begin(rsrec_t* h, PairCall& c, const char* who, int kind, int npairs, const int32_t* same, int lld, int nen, const double* ene,
                     double energy_min, double energy_max, const double* a_inf, const double* b_inf, const double* coef_a, const double* coef_b,
-                    size_t row_doubles, size_t fixed_in, size_t chunk_in, size_t fixed_out, size_t chunk_out, int per = 4) {
+                    size_t row_doubles, size_t fixed_in, size_t chunk_in, size_t fixed_out, size_t chunk_out, int per = 4, int group = 1) {
     if (kind < 0 || kind > 1) return fail(h, RSREC_ERR_ARG, "%s: kind %d is neither 0 (block) nor 1 (Chebyshev)", who, kind);
     if ((a_inf == nullptr) != (b_inf == nullptr)) return fail(h, RSREC_ERR_ARG, "%s: give both terminators or neither", who);
     if (kind == 0 && (coef_a == nullptr) != (coef_b == nullptr)) return fail(h, RSREC_ERR_ARG, "%s: give both a_b and b_sqrt or neither", who);
@@ -2578,6 +2579,9 @@ int pair_call_begin(rsrec_t* h, PairCall& c, const char* who, int kind, int npai
     const size_t cbytes = (size_t)per * cel * sizeof(double2) * (kind == 0 ? 2 : 1);      // coefficients of one pair
     // pairs per chunk: the row scratch <= 256 MiB and the staged coefficients <= 512 MiB, whatever npairs
     c.P = (int)std::max<size_t>(1, std::min<size_t>((size_t)npairs, std::min(((size_t)256 << 20) / rbytes, ((size_t)512 << 20) / cbytes)));
+    // RSREC_PAIR_CHUNK (environment, for tests): an upper limit on the pairs per chunk, so that small calls run the multi-chunk loop
+    if (const char* cap = getenv("RSREC_PAIR_CHUNK")) c.P = std::max(1, std::min(c.P, atoi(cap)));
+    c.P = std::max(group, c.P - c.P % group);                                              // whole groups of pairs (the trios of rsrec_spin_lattice)
     const size_t P = (size_t)c.P;
     release_kubo_buffers(h, true, true);
     // every region starts at an even double: the kernels read complex numbers as double2
@@ -2765,6 +2769,120 @@ extern "C" int rsrec_damping(rsrec_t* h, int kind, int npairs, const int32_t* sa
     }
     XFER(xc_deliver(h, at_ef, d_img, nimg));
     XFER(xc_deliver(h, total, d_tot, ntot));
+    return pair_call_end(h, e0, kev);
+}
+
+// exchange%calculate_jij_auxgreen (exchange.f90:171-335) for the pairs of one rank: the 9 tensor components (or J00) per energy from the
+// dressed up-up and down-down blocks of gij / gji (kernels_auxgreen.hpp), and their Fermi-weighted Simpson integrals, unscaled.
+extern "C" int rsrec_exchange_aux(rsrec_t* h, int kind, int npairs, const int32_t* same, int lld, int nen, const double* ene, int nv1, double fermi,
+                                  int sym_term, double energy_min, double energy_max, const double* a_inf, const double* b_inf, const double* coef_a,
+                                  const double* coef_b, const double* apar, int pair_offset, int npairs_total, double* jaux, double* rows) {
+    if (!h) return RSREC_ERR_ARG;
+    if (npairs < 1 || lld < 1 || nv1 < 1 || !same || !ene || pair_offset < 0 || npairs_total < pair_offset + npairs)
+        return fail(h, RSREC_ERR_ARG, "rsrec_exchange_aux: bad argument");
+    if (!apar) return fail(h, RSREC_ERR_ARG, "rsrec_exchange_aux: no potential parameters (apar is NULL)");
+    if (!jaux) return fail(h, RSREC_ERR_ARG, "rsrec_exchange_aux: no output (jaux is NULL)");
+    if (kind == 1 && (size_t)(2 * lld + 2) * sizeof(double2) + sizeof(XcChebLds) + sizeof(AuxShared) > (size_t)64 * 1024)
+        return fail(h, RSREC_ERR_ARG, "rsrec_exchange_aux: lld = %d too deep for the Chebyshev phase table beside the pair's blocks", lld);
+    if (nen < nv1 + 9) return fail(h, RSREC_ERR_ARG, "rsrec_exchange_aux: nen = %d < nv1 + 9 = %d (simpson_f integrates to nv1 + 10)", nen, nv1 + 9);
+    const size_t nimg = (size_t)AX_NROW * npairs_total, rdoubles = (size_t)nen * AX_NROW;
+    PairCall c;
+    // own inputs: fermi weights;  own chunk inputs: apar of the chunk's pairs;  own output: the jaux image
+    int rc = pair_call_begin(h, c, "rsrec_exchange_aux", kind, npairs, same, lld, nen, ene, energy_min, energy_max, a_inf, b_inf, coef_a, coef_b, rdoubles,
+                             (size_t)nen, (size_t)2 * AX_APAR, nimg, 0);
+    if (rc) return rc;
+    double* d_fw = c.d_fixed_in;
+    double* d_img = c.d_fixed_out;
+    reset_timing(h);
+    hipEvent_t e0 = next_event(h);
+    HIPCK(h, hipMemsetAsync(d_img, 0, nimg * sizeof(double), h->stream));
+    k_exchange_fermi<<<(nen + 255) / 256, 256, 0, h->stream>>>(nen, c.d_ene, fermi, d_fw);
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> kev;
+    for (int p0 = 0; p0 < npairs; p0 += c.P) {
+        PairChunk k;
+        rc = pair_call_chunk(h, c, p0, k);
+        if (rc) return rc;
+        const int np = k.np;
+        const double* ap = nullptr;
+        XFER(xc_fetch(h, apar + (size_t)p0 * 2 * AX_APAR, c.d_chunk_in, (size_t)np * 2 * AX_APAR, &ap));
+        std::pair<hipEvent_t, hipEvent_t> ev;
+        ev.first = next_event(h);
+        if (kind == 0)
+            k_aux_block<<<dim3(nen, np), 256, 0, h->stream>>>(lld, nen, c.d_ene, sym_term, k.ta, k.tb, k.sa, k.sb, c.d_same + p0, c.d_cb + p0, k.c0, ap, c.d_rows);
+        else
+            k_aux_cheb<<<dim3(nen, np), 256, (size_t)c.nm * sizeof(double2), h->stream>>>(c.nm, nen, c.d_ene, c.ca, c.cb, k.ta, k.sa, c.d_same + p0, c.d_cb + p0,
+                                                                                        k.c0, ap, c.d_rows);
+        HIPCK(h, hipGetLastError());
+        k_rows_integrate<<<np, 64, 0, h->stream>>>(nen, nv1, AX_NROW, c.d_ene, d_fw, c.d_rows, pair_offset + p0, d_img);
+        HIPCK(h, hipGetLastError());
+        ev.second = next_event(h);
+        kev.push_back(ev);
+        if (rows) XFER(xc_deliver(h, rows + (size_t)p0 * rdoubles, c.d_rows, (size_t)np * rdoubles));
+        if (p0 + c.P < npairs) HIPCK(h, hipStreamSynchronize(h->stream));         // the chunk's staging buffers are reused
+    }
+    XFER(xc_deliver(h, jaux, d_img, nimg));
+    return pair_call_end(h, e0, kev);
+}
+
+// exchange%calculate_jijk (exchange.f90:338-601) for the trios of one rank.  The pairs of trio t are 3 t .. 3 t + 2 = (i,j), (i,k), (j,k)
+// (lattice.f90:644-651); one workgroup per (trio, energy) runs their Green stages one after another and keeps the dressed blocks in LDS.
+extern "C" int rsrec_spin_lattice(rsrec_t* h, int kind, int npairs, const int32_t* same, int lld, int nen, const double* ene, int nv1, double fermi,
+                                  int sym_term, double energy_min, double energy_max, const double* a_inf, const double* b_inf, const double* coef_a,
+                                  const double* coef_b, const double* apar, const double* dmat, int trio_offset, int ntrios_total, double* jijk,
+                                  double* rows) {
+    if (!h) return RSREC_ERR_ARG;
+    if (npairs < 1 || lld < 1 || nv1 < 1 || !same || !ene || trio_offset < 0) return fail(h, RSREC_ERR_ARG, "rsrec_spin_lattice: bad argument");
+    if (npairs % 3) return fail(h, RSREC_ERR_ARG, "rsrec_spin_lattice: npairs = %d is not a multiple of 3 (a trio is the pairs (i,j), (i,k), (j,k))", npairs);
+    const int ntrios = npairs / 3;
+    if (ntrios_total < trio_offset + ntrios) return fail(h, RSREC_ERR_ARG, "rsrec_spin_lattice: bad argument");
+    if (!apar) return fail(h, RSREC_ERR_ARG, "rsrec_spin_lattice: no potential parameters (apar is NULL)");
+    if (!dmat) return fail(h, RSREC_ERR_ARG, "rsrec_spin_lattice: no displacement matrices (dmat is NULL)");
+    if (!jijk) return fail(h, RSREC_ERR_ARG, "rsrec_spin_lattice: no output (jijk is NULL)");
+    if (nen < nv1 + 9) return fail(h, RSREC_ERR_ARG, "rsrec_spin_lattice: nen = %d < nv1 + 9 = %d (simpson_f integrates to nv1 + 10)", nen, nv1 + 9);
+    if (kind == 1 && (size_t)(2 * lld + 2) * sizeof(double2) + sizeof(XcChebLds) + sizeof(JkShared) > (size_t)64 * 1024)
+        return fail(h, RSREC_ERR_ARG, "rsrec_spin_lattice: lld = %d too deep for the Chebyshev phase table beside the trio's blocks", lld);
+    const size_t nimg = (size_t)AX_NROW * ntrios_total, rdoubles = (size_t)nen * AX_NROW;      // rows of one trio
+    constexpr size_t TRIO_IN = (size_t)3 * JK_APAR + 2 * 81;                                   // apar | dmat of one trio
+    static_assert(TRIO_IN % 3 == 0 && (3 * JK_APAR) % 2 == 0, "trio inputs split over its pairs; dmat is read as double2");
+    PairCall c;
+    // chunks of whole trios.  Per pair: a third of a trio's rows and inputs.  Own inputs: fermi weights;  own output: the jijk image
+    int rc = pair_call_begin(h, c, "rsrec_spin_lattice", kind, npairs, same, lld, nen, ene, energy_min, energy_max, a_inf, b_inf, coef_a, coef_b,
+                             rdoubles / 3, (size_t)nen, TRIO_IN / 3, nimg, 0, 4, 3);
+    if (rc) return rc;
+    double* d_fw = c.d_fixed_in;
+    double* d_img = c.d_fixed_out;
+    double* d_ap = c.d_chunk_in;
+    double* d_dm = d_ap + (size_t)(c.P / 3) * 3 * JK_APAR;
+    reset_timing(h);
+    hipEvent_t e0 = next_event(h);
+    HIPCK(h, hipMemsetAsync(d_img, 0, nimg * sizeof(double), h->stream));
+    k_exchange_fermi<<<(nen + 255) / 256, 256, 0, h->stream>>>(nen, c.d_ene, fermi, d_fw);
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> kev;
+    for (int p0 = 0; p0 < npairs; p0 += c.P) {
+        PairChunk k;
+        rc = pair_call_chunk(h, c, p0, k);
+        if (rc) return rc;
+        const int nt = k.np / 3, t0 = p0 / 3;
+        const double *ap = nullptr, *dm = nullptr;
+        XFER(xc_fetch(h, apar + (size_t)t0 * 3 * JK_APAR, d_ap, (size_t)nt * 3 * JK_APAR, &ap));
+        XFER(xc_fetch(h, dmat + (size_t)t0 * 2 * 81, d_dm, (size_t)nt * 2 * 81, &dm));
+        std::pair<hipEvent_t, hipEvent_t> ev;
+        ev.first = next_event(h);
+        if (kind == 0)
+            k_jijk_block<<<dim3(nen, nt), 256, 0, h->stream>>>(lld, nen, c.d_ene, sym_term, k.ta, k.tb, k.sa, k.sb, c.d_same + p0, c.d_cb + p0, k.c0, ap,
+                                                            reinterpret_cast<const double2*>(dm), c.d_rows);
+        else
+            k_jijk_cheb<<<dim3(nen, nt), 256, (size_t)c.nm * sizeof(double2), h->stream>>>(c.nm, nen, c.d_ene, c.ca, c.cb, k.ta, k.sa, c.d_same + p0, c.d_cb + p0,
+                                                                                         k.c0, ap, reinterpret_cast<const double2*>(dm), c.d_rows);
+        HIPCK(h, hipGetLastError());
+        k_rows_integrate<<<nt, 64, 0, h->stream>>>(nen, nv1, AX_NROW, c.d_ene, d_fw, c.d_rows, trio_offset + t0, d_img);
+        HIPCK(h, hipGetLastError());
+        ev.second = next_event(h);
+        kev.push_back(ev);
+        if (rows) XFER(xc_deliver(h, rows + (size_t)t0 * rdoubles, c.d_rows, (size_t)nt * rdoubles));
+        if (p0 + c.P < npairs) HIPCK(h, hipStreamSynchronize(h->stream));         // the chunk's staging buffers are reused
+    }
+    XFER(xc_deliver(h, jijk, d_img, nimg));
     return pair_call_end(h, e0, kev);
 }
 

@@ -3,7 +3,9 @@
 green%calculate_intersite_gf + _twoindex (green.f90:386-469) and the integrands and Fermi-weighted Simpson integrals of
 exchange%calculate_exchange + _twoindex become one call, ``rsrec_exchange``.  Neither g0 nor the 24 intersite arrays are formed: per
 (pair, energy) the kernel reduces g0 of the pair's chains to 41 real integrands, and per pair to 67 numbers (kernels_exchange.hpp).
-The traces of exchange%calculate_gilbert_damping (exchange.f90:674-694) come from the same chains through ``rsrec_damping``.
+The traces of exchange%calculate_gilbert_damping (exchange.f90:674-694) come from the same chains through ``rsrec_damping``, the
+auxiliary-GF exchange tensor of calculate_jij_auxgreen (:171-335) through ``rsrec_exchange_aux`` and the spin-lattice coupling of
+calculate_jijk (:338-601) through ``rsrec_spin_lattice`` (kernels_auxgreen.hpp).
 """
 import ctypes as C
 
@@ -13,6 +15,7 @@ from . import _lib
 
 NINT = 41   # integrand rows per (pair, energy), order in kernels_exchange.hpp
 NDAMP = 18  # damping rows per (pair, energy): dtott (9, l fastest), then dtottim (9)
+NAUX = 9    # Jij_aux rows per (pair, energy) and Jijk rows per (trio, energy): xx, xy, xz, yx, .. zz
 NCONT = 13  # contour rows per (pair, point): jtot, jjtot(1:3), itot(3,3) (k fastest) = T_comm_xc's order
 
 
@@ -49,6 +52,93 @@ def exchange_dpar(c, dele, vmad, iz, pairs):
             out[2, :, side, p] = dele[t, :, 0]
             out[3, :, side, p] = dele[t, :, 1]
     return out
+
+
+def aux_apar(c, dele, vmad, iz, pairs):
+    """apar (2,3,2,2,npairs) for rsrec_exchange_aux: (c + vmad, dele) per l, spin and side (atom i, atom j) of every pair, the sums formed
+    in double as p_matrix forms them (symbolic_atom.f90:420); the library rounds them to single precision as the reference's cmplx() does.
+    Arguments as ``exchange_dpar``."""
+    c, dele, vmad = np.asarray(c, np.float64), np.asarray(dele, np.float64), np.asarray(vmad, np.float64)
+    iz, pairs = np.asarray(iz), np.asarray(pairs)
+    out = np.zeros((2, 3, 2, 2, len(pairs)), np.float64, order="F")
+    for p, ij in enumerate(pairs):
+        for side in range(2):
+            t = int(iz[int(ij[side]) - 1]) - 1
+            out[0, :, :, side, p] = c[t] + vmad[t]
+            out[1, :, :, side, p] = dele[t]
+    return out
+
+
+def trio_apar(c, dele, vmad, qpar, iz, trios):
+    """apar (3,3,2,3,ntrios) for rsrec_spin_lattice: (c + vmad, dele, qpar) per l, spin and atom (i, j, k) of every trio.
+    ``qpar``: (ntype, 3, 2) like ``c``; ``trios``: (ntrios, 3) 1-based atoms (lattice%ijktrio(:, 1:3))."""
+    c, dele, vmad, qpar = (np.asarray(a, np.float64) for a in (c, dele, vmad, qpar))
+    iz, trios = np.asarray(iz), np.asarray(trios)
+    out = np.zeros((3, 3, 2, 3, len(trios)), np.float64, order="F")
+    for n, ijk in enumerate(trios):
+        for atom in range(3):
+            t = int(iz[int(ijk[atom]) - 1]) - 1
+            out[0, :, :, atom, n] = c[t] + vmad[t]
+            out[1, :, :, atom, n] = dele[t]
+            out[2, :, :, atom, n] = qpar[t]
+    return out
+
+
+def trio_pairs(trios):
+    """The pairs of the trios in the order lattice%ijpair holds them (lattice.f90:644-651): (i,j), (i,k), (j,k) per trio -> (3 ntrios, 2)."""
+    t = np.asarray(trios, np.int32).reshape(-1, 3)
+    return np.stack([t[:, [0, 1]], t[:, [0, 2]], t[:, [1, 2]]], axis=1).reshape(-1, 2)
+
+
+def _factorial2(n):
+    return 1.0 if n <= 0 else float(np.prod(np.arange(n, 0, -2)))
+
+
+def _real_harmonic_p(u):
+    """Real spherical harmonics of l = 1 at the unit vector u, m = -1, 0, 1 (y, z, x)."""
+    k = np.sqrt(3.0 / (4.0 * np.pi))
+    return {-1: k * u[1], 0: k * u[2], 1: k * u[0]}
+
+
+def _ylm_grid(n=32):
+    """Real spherical harmonics l = 0..2 in (l, m) order on a Gauss-Legendre x uniform-phi grid, with the quadrature weights."""
+    x, w = np.polynomial.legendre.leggauss(n)
+    phi = 2.0 * np.pi * np.arange(2 * n) / (2 * n)
+    ct, ph = np.meshgrid(x, phi, indexing="ij")
+    wt = np.repeat(w[:, None], 2 * n, axis=1) * (2.0 * np.pi / (2 * n))
+    st = np.sqrt(1.0 - ct * ct)
+    X, Y, Z = st * np.cos(ph), st * np.sin(ph), ct
+    k0, k1 = 0.5 / np.sqrt(np.pi), np.sqrt(3.0 / (4.0 * np.pi))
+    k2 = 0.5 * np.sqrt(15.0 / np.pi)
+    ylm = {(0, 0): k0 + 0 * X, (1, -1): k1 * Y, (1, 0): k1 * Z, (1, 1): k1 * X,
+           (2, -2): k2 * X * Y, (2, -1): k2 * Y * Z, (2, 0): 0.25 * np.sqrt(5.0 / np.pi) * (3 * Z * Z - 1), (2, 1): k2 * X * Z,
+           (2, 2): 0.5 * k2 * (X * X - Y * Y)}
+    return ylm, wt
+
+
+def disp_matrix(disp_vec, ws_radius):
+    """One 9 x 9 spin block of symbolic_atom%disp_matrix (symbolic_atom.f90:274-355) for lmax = 2, complex: the approximate displacement
+    of the regular solution of the Laplace equation, in the program's orbital order s, px, py, pz, dxy, dyz, dzx, x2-y2, 3z2-r2.
+    mat(l'm', lm) = -(4 pi / (3 ws_radius)) (2l-1)!! / (2l'-1)!! sum_m'' G(lm, l'm', 1m'') Y_1m''(u) for l' <= l, zero otherwise,
+    with G the Gaunt coefficients of real harmonics (here by quadrature, exact for these degrees) and u the unit displacement."""
+    d = np.asarray(disp_vec, np.float64)
+    nrm = np.sqrt(np.sum(d * d))
+    u = d / nrm if nrm != 0 else np.zeros(3)
+    order = {(0, 0): 1, (1, -1): 3, (1, 0): 4, (1, 1): 2, (2, -2): 5, (2, -1): 6, (2, 0): 9, (2, 1): 7, (2, 2): 8}
+    ylm, wt = _ylm_grid()
+    y1 = _real_harmonic_p(u)
+    mat = np.zeros((9, 9), np.complex128)
+    for i in range(3):
+        for j in range(3):
+            if i > j:
+                continue
+            f = _factorial2(2 * j - 1) / _factorial2(2 * i - 1)
+            for k in range(-i, i + 1):
+                for n in range(-j, j + 1):
+                    for m in (-1, 0, 1):
+                        gaunt = float(np.sum(wt * ylm[(j, n)] * ylm[(i, k)] * ylm[(1, m)]))
+                        mat[order[(i, k)] - 1, order[(j, n)] - 1] += f * gaunt * y1[m]
+    return mat * ((-4.0 * np.pi) / (3.0 * ws_radius))
 
 
 def damping_tmat(tmat, iz, pairs):
@@ -201,6 +291,53 @@ class Exchange:
                                                   _any_ptr(dmat), int(pair_offset), int(npairs_total), _ptr(xc), _ptr(out_rows)))
         del ca, cb
         return (xc, out_rows) if rows else xc
+
+    def aux(self, fermi, nv1, apar, kind="block", rows=False, resident=False, coef=None, a_inf=None, b_inf=None, pair_offset=0, npairs_total=None):
+        """exchange%calculate_jij_auxgreen in one call (``rsrec_exchange_aux``): returns jaux (9, npairs_total), the unscaled Simpson
+        integrals of the tensor components xx, xy, .. zz (the reference prints them * 1.0d3 / 4 / pi; an i == j pair: J00 in row 0, zeros
+        below), then the rows (9, nen, npairs) if ``rows``.  ``apar``: (2,3,2,2,npairs) (``aux_apar``), a numpy array or a device tensor
+        in that memory order.  Pairs, coefficients and terminators as ``compute``."""
+        rec = self.recursion
+        ene, npairs, npairs_total, same, lld, k, ca, cb, a_inf, b_inf = self._call_setup(kind, resident, coef, a_inf, b_inf, npairs_total)
+        if apar is not None and not hasattr(apar, "data_ptr"):
+            apar = np.asfortranarray(apar, dtype=np.float64)
+            if apar.shape != (2, 3, 2, 2, npairs):
+                raise ValueError("apar must be (2, 3, 2, 2, %d), got %r" % (npairs, apar.shape))
+        jaux = np.zeros((NAUX, npairs_total), order="F")
+        out_rows = np.zeros((NAUX, len(ene), npairs), order="F") if rows else None
+        rec._check(rec._L.rsrec_exchange_aux(rec._h, k, npairs, _ptr(same), lld, len(ene), _ptr(ene), int(nv1), float(fermi), int(self.green.sym_term),
+                                              float(rec.en.energy_min), float(rec.en.energy_max), _ptr(a_inf), _ptr(b_inf), _any_ptr(ca), _any_ptr(cb),
+                                              _any_ptr(apar), int(pair_offset), int(npairs_total), _ptr(jaux), _ptr(out_rows)))
+        del ca, cb
+        return (jaux, out_rows) if rows else jaux
+
+    def spin_lattice(self, fermi, nv1, apar, dmat, kind="block", rows=False, resident=False, coef=None, a_inf=None, b_inf=None, trio_offset=0,
+                     ntrios_total=None):
+        """exchange%calculate_jijk in one call (``rsrec_spin_lattice``): returns jijk (9, ntrios_total), the unscaled Simpson integrals
+        (the reference prints them * (1.0d3 / 8 / pi) * (13.605693122994 / 1.8897261246)), then the rows (9, nen, ntrios) if ``rows``.
+
+        The rank's pairs are the trios' pairs, three per trio in the order (i,j), (i,k), (j,k) (``trio_pairs``).  ``apar``:
+        (3,3,2,3,ntrios) (``trio_apar``); ``dmat``: (9,9,ntrios) complex, one spin block of disp_matrix of atom k for every trio's
+        displacement (``disp_matrix``); numpy arrays or device tensors in that memory order.  Coefficients and terminators as ``compute``."""
+        rec = self.recursion
+        ene, npairs, _, same, lld, k, ca, cb, a_inf, b_inf = self._call_setup(kind, resident, coef, a_inf, b_inf, None)
+        ntrios = npairs // 3
+        ntrios_total = ntrios if ntrios_total is None else ntrios_total
+        if apar is not None and not hasattr(apar, "data_ptr"):
+            apar = np.asfortranarray(apar, dtype=np.float64)
+            if apar.shape != (3, 3, 2, 3, ntrios):
+                raise ValueError("apar must be (3, 3, 2, 3, %d), got %r" % (ntrios, apar.shape))
+        if dmat is not None and not hasattr(dmat, "data_ptr"):
+            dmat = np.asfortranarray(dmat, dtype=np.complex128)
+            if dmat.shape != (9, 9, ntrios):
+                raise ValueError("dmat must be (9, 9, %d), got %r" % (ntrios, dmat.shape))
+        jijk = np.zeros((NAUX, ntrios_total), order="F")
+        out_rows = np.zeros((NAUX, len(ene), ntrios), order="F") if rows else None
+        rec._check(rec._L.rsrec_spin_lattice(rec._h, k, npairs, _ptr(same), lld, len(ene), _ptr(ene), int(nv1), float(fermi), int(self.green.sym_term),
+                                              float(rec.en.energy_min), float(rec.en.energy_max), _ptr(a_inf), _ptr(b_inf), _any_ptr(ca), _any_ptr(cb),
+                                              _any_ptr(apar), _any_ptr(dmat), int(trio_offset), int(ntrios_total), _ptr(jijk), _ptr(out_rows)))
+        del ca, cb
+        return (jijk, out_rows) if rows else jijk
 
     def timing(self):
         """(device ms of the last call, ms in its Green + trace + integration kernels)."""
