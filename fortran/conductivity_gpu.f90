@@ -22,6 +22,7 @@ module conductivity_gpu_mod
    use timer_mod, only: g_timer
    use rsrec_binding
    use rsrec_context_mod, only: rsrec_gpu_context
+   use recursion_gpu_mod, only: rsrec_gpu_kubo_diag_resident
    implicit none
 
    private
@@ -104,12 +105,23 @@ contains
       write (*, *) factor, volume, de
 
       ! :268-281 (and calculate_gamma_nm :158-225): integrand_at(l2, l2, i, ntype) for every vector, on the device
-      call g_timer%start('conductivity-integrand-gpu')
       allocate (integ(18, nen, loop_over))
       ctx = rsrec_gpu_context()
-      rc = rsrec_kubo_integrand(ctx, int(loop_over, c_int), int(this%control%cond_ll, c_int), c_loc(this%recursion%mu_nm_stochastic), &
-                                int(nen, c_int), c_loc(ene), real(this%en%energy_min, c_double), real(this%en%energy_max, c_double), &
-                                c_loc(integ))
+      rc = 1
+      if (rsrec_gpu_kubo_diag_resident(this%control%cond_ll) == loop_over) then
+         ! the recursion (RSREC_KUBO_DIAG) left the orbital-diagonal moments of these vectors on the device: nothing is uploaded.  If the
+         ! library did not keep them (they did not fit beside the call's buffers) it says so, and the host array is used as always.
+         call g_timer%start('conductivity-integrand-gpu-resident')
+         rc = rsrec_kubo_integrand_diag(ctx, int(loop_over, c_int), int(this%control%cond_ll, c_int), c_null_ptr, int(nen, c_int), &
+                                        c_loc(ene), real(this%en%energy_min, c_double), real(this%en%energy_max, c_double), c_loc(integ))
+         call g_timer%stop('conductivity-integrand-gpu-resident')
+      end if
+      call g_timer%start('conductivity-integrand-gpu')
+      if (rc /= 0) then
+         rc = rsrec_kubo_integrand(ctx, int(loop_over, c_int), int(this%control%cond_ll, c_int), c_loc(this%recursion%mu_nm_stochastic), &
+                                   int(nen, c_int), c_loc(ene), real(this%en%energy_min, c_double), real(this%en%energy_max, c_double), &
+                                   c_loc(integ))
+      end if
       if (rc /= 0) call g_logger%fatal('conductivity_gpu%calculate_conductivity_tensor: '//rsrec_error_string(ctx), __FILE__, __LINE__)
       call g_timer%stop('conductivity-integrand-gpu')
 

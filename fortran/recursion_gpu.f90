@@ -41,6 +41,10 @@ module recursion_gpu_mod
       !> local-axis runs: announce the chains recur_b leaves on the device (in each site's local frame) to the device LDOS / moment
       !> stages of bands_gpu.  Off unless RSREC_LOCAL_AXIS_DEVICE is set: such a run then keeps the inherited host stages.
       logical :: local_axis_device = .false.
+      !> compute_moments_stochastic forms only the orbital-diagonal moments mu_nm_stochastic(l, l, n, m, i) (rsrec_kubo_moments_diag) and
+      !> leaves the other elements of the array zero: conductivity.f90:289 and :292 are the only reads of the array, both on the diagonal.
+      !> The moments also stay on the device for conductivity_gpu.  Off unless RSREC_KUBO_DIAG is set.
+      logical :: kubo_diag = .false.
    contains
       procedure :: recur => gpu_recur
       procedure :: recur_b => gpu_recur_b
@@ -61,7 +65,7 @@ module recursion_gpu_mod
       procedure :: gpu_constructor
    end interface recursion_gpu
 
-   public :: rsrec_gpu_shutdown, rsrec_gpu_context, rsrec_gpu_block_resident, rsrec_gpu_cheb_resident
+   public :: rsrec_gpu_shutdown, rsrec_gpu_context, rsrec_gpu_block_resident, rsrec_gpu_cheb_resident, rsrec_gpu_kubo_diag_resident
 
    !> (the per-process device context g_handle lives in rsrec_context_mod; re-exported above for the hosts that used it from here)
    !> number of sites whose block coefficients the last driver call left on the device (0: none -- another driver ran since, or the
@@ -69,6 +73,8 @@ module recursion_gpu_mod
    integer, save :: g_block_resident = 0
    !> the same for the Chebyshev moments mu_n of chebyshev_recur (every other driver resets it)
    integer, save :: g_cheb_resident = 0
+   !> vectors and cond_ll of the orbital-diagonal Kubo moments compute_moments_stochastic left on the device (kubo_diag; 0: none)
+   integer, save :: g_kubo_diag_nvec = 0, g_kubo_diag_ll = 0
 
 contains
 
@@ -84,6 +90,7 @@ contains
       obj%control => hamiltonian_obj%charge%lattice%control
       call obj%restore_to_default()
       if (rsrec_env_flag('RSREC_LOCAL_AXIS_DEVICE')) obj%local_axis_device = .true.   ! (hosts that cannot reach the member: fortran/shadow/)
+      if (rsrec_env_flag('RSREC_KUBO_DIAG')) obj%kubo_diag = .true.
    end function gpu_constructor
 
    !> Sites of this rank whose a_b / b2_b (as recur_b produced them) are also resident on the device; 0 if they are not.
@@ -91,6 +98,14 @@ contains
       integer :: n
       n = g_block_resident
    end function rsrec_gpu_block_resident
+
+   !> Vectors whose orbital-diagonal Kubo moments of order cond_ll the last compute_moments_stochastic announced as resident on the device
+   !> (for rsrec_kubo_integrand_diag with a null pointer); 0 if there are none of that cond_ll, or another driver ran since.
+   function rsrec_gpu_kubo_diag_resident(cond_ll) result(n)
+      integer, intent(in) :: cond_ll
+      integer :: n
+      n = merge(g_kubo_diag_nvec, 0, cond_ll == g_kubo_diag_ll)
+   end function rsrec_gpu_kubo_diag_resident
 
    !> Sites of this rank whose mu_n (as chebyshev_recur produced them) are also resident on the device; 0 if they are not.
    function rsrec_gpu_cheb_resident() result(n)
@@ -179,6 +194,7 @@ contains
       nloc = end_atom - start_atom + 1
       g_block_resident = 0
       g_cheb_resident = 0
+      g_kubo_diag_nvec = 0
       if (nloc <= 0) return
       allocate (seeds(nloc), ab(18, 18, llmax, nloc), bb(18, 18, llmax, nloc))
 
@@ -284,6 +300,7 @@ contains
       call sync_device(this, .true.)
       g_block_resident = 0
       g_cheb_resident = 0
+      g_kubo_diag_nvec = 0
       rc = rsrec_block_lanczos_seeded(g_handle, int(nch, c_int), 2_c_int, c_loc(seeds), c_loc(coef), int(llmax, c_int), c_loc(ab), c_loc(bb))
       call check(rc, 'rsrec_block_lanczos_seeded')
       do c = 1, nch
@@ -342,6 +359,7 @@ contains
       call g_timer%start('<PSI_0|PSI_n>')
       g_block_resident = 0
       g_cheb_resident = 0
+      g_kubo_diag_nvec = 0
       rc = rsrec_chebyshev(g_handle, int(nloc, c_int), c_loc(seeds), int(this%control%lld, c_int), real(a, c_double), real(b, c_double), c_loc(mu))
       call g_timer%stop('<PSI_0|PSI_n>')
       call check(rc, 'rsrec_chebyshev')
@@ -390,6 +408,7 @@ contains
       call g_timer%start('<PSI_0|PSI_n>')
       g_block_resident = 0
       g_cheb_resident = 0
+      g_kubo_diag_nvec = 0
       rc = rsrec_chebyshev_seeded(g_handle, int(nch, c_int), 2_c_int, c_loc(seeds), c_loc(coef), int(this%control%lld, c_int), &
                                   real(a, c_double), real(b, c_double), c_loc(mu))
       call g_timer%stop('<PSI_0|PSI_n>')
@@ -419,6 +438,7 @@ contains
       call sync_device(this, .true.)
       g_block_resident = 0
       g_cheb_resident = 0
+      g_kubo_diag_nvec = 0
       rc = rsrec_scalar_lanczos(g_handle, int(nloc, c_int), c_loc(seeds), int(this%lattice%control%lld, c_int), int(llmax_a, c_int), c_loc(a), c_loc(b2))
       call check(rc, 'rsrec_scalar_lanczos')
       ! the reference fills rows 1..lld of a(:,:,i_loc,1) / b2 and leaves the rest untouched (:3516-3519)
@@ -463,10 +483,11 @@ contains
    subroutine gpu_compute_moments_stochastic(this)
       use math_mod, only: pi, i_unit
       class(recursion_gpu), intent(inout) :: this
-      integer :: i, k, loop_over, nseed, cll
+      integer :: i, k, l, loop_over, nseed, cll
       integer(c_int) :: rc
       real(rp) :: a, b, rng
       integer(c_int), allocatable, target :: seeds(:, :)
+      complex(rp), allocatable, target :: mu_diag(:, :, :, :)
       complex(rp), allocatable, target :: coef(:, :), mu(:, :, :, :, :), va(:, :, :, :), vb(:, :, :, :), voa(:, :, :, :), vob(:, :, :, :)
       type(c_ptr) :: p_voa, p_vob
 
@@ -511,6 +532,22 @@ contains
          p_voa = c_loc(voa)
          p_vob = c_loc(vob)
       end if
+      g_kubo_diag_nvec = 0
+      if (this%kubo_diag) then
+         ! only the diagonals are formed, downloaded and stored; every other element of mu_nm_stochastic stays zero (nothing reads them:
+         ! conductivity.f90:289, :292).  The library keeps the diagonals for conductivity_gpu%calculate_conductivity_tensor.
+         allocate (mu_diag(18, cll, cll, loop_over))
+         rc = rsrec_kubo_moments_diag(g_handle, int(loop_over, c_int), int(nseed, c_int), c_loc(seeds), c_loc(coef), int(cll, c_int), &
+                                      real(a, c_double), real(b, c_double), c_loc(va), p_voa, c_loc(vb), p_vob, c_loc(mu_diag))
+         call check(rc, 'rsrec_kubo_moments_diag')
+         this%mu_nm_stochastic = (0.0_rp, 0.0_rp)
+         do l = 1, 18
+            this%mu_nm_stochastic(l, l, :, :, :) = mu_diag(l, :, :, :)
+         end do
+         g_kubo_diag_nvec = loop_over
+         g_kubo_diag_ll = cll
+         return
+      end if
       allocate (mu(18, 18, cll, cll, loop_over))
       rc = rsrec_kubo_moments(g_handle, int(loop_over, c_int), int(nseed, c_int), c_loc(seeds), c_loc(coef), int(cll, c_int), &
                               real(a, c_double), real(b, c_double), c_loc(va), p_voa, c_loc(vb), p_vob, c_loc(mu))
@@ -549,6 +586,7 @@ contains
       call sync_device(this, .true.)
       g_block_resident = 0
       g_cheb_resident = 0
+      g_kubo_diag_nvec = 0
       allocate (seeds(this%lattice%kk), cr(3, this%lattice%kk), mu_n_orb(18, 18, ll))
       do k = 1, this%lattice%kk
          seeds(k) = int(k, c_int)

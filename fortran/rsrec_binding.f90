@@ -194,6 +194,18 @@ module rsrec_binding
          integer(c_int) :: rc
       end function
 
+      ! the same from the orbital-diagonal moments (18,cond_ll,cond_ll,nvec); mu_diag = c_null_ptr: the moments rsrec_kubo_moments_diag left
+      ! resident on the handle (an error if there are none, or nvec / cond_ll differ)
+      function rsrec_kubo_integrand_diag(handle, nvec, cond_ll, mu_diag, nen, ene, energy_min, energy_max, integrand) &
+         bind(C, name='rsrec_kubo_integrand_diag') result(rc)
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: handle
+         integer(c_int), value :: nvec, cond_ll, nen
+         type(c_ptr), value :: mu_diag, ene, integrand
+         real(c_double), value :: energy_min, energy_max
+         integer(c_int) :: rc
+      end function
+
       ! exchange couplings of the rank's pairs: intersite g + Jij / Dij / Iij integrands + Simpson integrals (exchange.f90:1032-1615)
       function rsrec_exchange(handle, kind, npairs, same, lld, nen, ene, nv1, fermi, sym_term, energy_min, energy_max, a_inf, b_inf, &
                               coef_a, coef_b, dpar, pair_offset, npairs_total, xc, so, fo, parts, jcum, integrand) &
@@ -273,6 +285,18 @@ module rsrec_binding
          integer(c_int), value :: nvec, nseed, cond_ll
          real(c_double), value :: a, b
          type(c_ptr), value :: seed_atoms, seed_coef, v_a, vo_a, v_b, vo_b, mu_nm
+         integer(c_int) :: rc
+      end function
+
+      ! only the orbital-diagonal moments mu_nm(l,l,n,m,v) -- conductivity.f90:289, :292 read nothing else: mu_diag (18,cond_ll,cond_ll,nvec),
+      ! or c_null_ptr; they also stay resident on the handle for rsrec_kubo_integrand_diag
+      function rsrec_kubo_moments_diag(handle, nvec, nseed, seed_atoms, seed_coef, cond_ll, a, b, v_a, vo_a, v_b, vo_b, mu_diag) &
+         bind(C, name='rsrec_kubo_moments_diag') result(rc)
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: handle
+         integer(c_int), value :: nvec, nseed, cond_ll
+         real(c_double), value :: a, b
+         type(c_ptr), value :: seed_atoms, seed_coef, v_a, vo_a, v_b, vo_b, mu_diag
          integer(c_int) :: rc
       end function
 

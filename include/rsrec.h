@@ -246,6 +246,21 @@ int rsrec_chebyshev_seeded(rsrec_t *h, int nchains, int nseed, const int32_t *se
 int rsrec_kubo_moments(rsrec_t *h, int nvec, int nseed, const int32_t *seed_atoms, const double *seed_coef, int cond_ll, double a, double b,
                        const double *v_a, const double *vo_a, const double *v_b, const double *vo_b, double *mu_nm);
 
+/* The orbital-diagonal part of the same moments, mu_nm_stochastic(l, l, n, m, v): the reference reads the array in two places only,
+ * conductivity.f90:289 and :292, and both take (l2, l2, n, m, ntype) -- only conductivity.f90:289, :292 read the moments, and neither
+ * reads an off-diagonal element.  Same recurrences and arguments as rsrec_kubo_moments; the contraction forms the 18 diagonals alone
+ * (k_kubo_gram_diag: 1/18 of the flops, 1/18 of the download).
+ *   mu_diag : complex (18,cond_ll,cond_ll,nvec) out, host or device memory (detected), mu_diag(l,n,m,v) = mu_nm(l,l,n,m,v); NULL: nothing
+ *             is copied out.  1 <= cond_ll <= RSREC_COND_LL_MAX.
+ * The diagonal moments of all nvec vectors stay on the handle after the call (72 MB per vector at cond_ll = 500) for
+ * rsrec_kubo_integrand_diag(mu_diag = NULL) -- unless they do not fit the device beside the call's buffers: the call still succeeds
+ * and nothing stays.  They are dropped by the next rsrec_kubo_moments / rsrec_kubo_moments_diag call, by rsrec_set_hamiltonian, by a
+ * rsrec_set_lattice that changes the lattice, and whenever another entry point takes the Kubo buffers' memory back.
+ * Results are run-to-run bit-identical and do not depend on how many vectors advance together (options kubo_lchunk, kubo_vbatch apply
+ * as in rsrec_kubo_moments).  rsrec_get_timing as rsrec_kubo_moments: out[0] device ms, out[5] ms in the contractions. */
+int rsrec_kubo_moments_diag(rsrec_t *h, int nvec, int nseed, const int32_t *seed_atoms, const double *seed_coef, int cond_ll, double a, double b,
+                            const double *v_a, const double *vo_a, const double *v_b, const double *vo_b, double *mu_diag);
+
 /* The Kubo-Bastin conductivity integrand of calculate_gamma_nm + calculate_conductivity_tensor (conductivity.f90:158-268), without the
  * (nen, cond_ll, cond_ll) array gamma_nm (the sum factorises into two tables of nen x cond_ll, kernels_cond.hpp):
  *   integrand(l, i, v) = factor sum_{n,m} gamma_nm(i, n, m) mu_nm(l, l, n, m, v),   factor = 16 / (pi (energy_max - energy_min)^2)
@@ -259,6 +274,13 @@ int rsrec_kubo_moments(rsrec_t *h, int nvec, int nseed, const int32_t *seed_atom
 #define RSREC_COND_LL_MAX 4096
 int rsrec_kubo_integrand(rsrec_t *h, int nvec, int cond_ll, const double *mu_nm, int nen, const double *ene, double energy_min,
                          double energy_max, double *integrand);
+/* The same integrand from the orbital-diagonal moments (only conductivity.f90:289, :292 read the moments, both on the diagonal):
+ *   mu_diag : complex (18,cond_ll,cond_ll,nvec), host or device, as rsrec_kubo_moments_diag returns it; NULL = the moments that call
+ *             left resident on the handle.  RSREC_ERR_ARG (with a message; the handle stays usable) if nothing is resident or nvec /
+ *             cond_ll differ from the resident call.
+ * Everything else as rsrec_kubo_integrand, and the same bits as that call gives on a full array with these diagonals. */
+int rsrec_kubo_integrand_diag(rsrec_t *h, int nvec, int cond_ll, const double *mu_diag, int nen, const double *ene, double energy_min,
+                              double energy_max, double *integrand);
 
 /* Exchange couplings of the pairs of one rank: green%calculate_intersite_gf / _twoindex (green.f90:386-469) and the integrands and
  * Fermi-weighted Simpson integrals of exchange%calculate_exchange / _twoindex (exchange.f90:1032-1615), without the intersite arrays
@@ -460,7 +482,7 @@ int rsrec_comm_destroy(rsrec_t *h);
  *   "s5_host_emit" 1 = swizzle k_spmm5's operator streams on the host instead of assembling them on the device (cross-check) [0]
  *   "orth_oop"   1 = the orthogonalisation pass writes u_{n+1} into a third u vector instead of over u_{n-1} (faster on the HBM, one more work vector) [1]
  *   "sat_pct"    a chain whose region holds at least this share (per cent) of the lattice runs on the list of ALL atoms instead of its own [100]
- *   "kubo_lchunk" rsrec_kubo_moments: left vectors held on the device at a time [0 = as many as fit];  "kubo_vbatch" vectors of a call advanced
+ *   "kubo_lchunk" rsrec_kubo_moments / _diag: left vectors held on the device at a time [0 = as many as fit];  "kubo_vbatch" vectors of a call advanced
  *                together as the chains of every launch [0 = up to 8, as many as fit beside a whole left matrix each] */
 int rsrec_set_option(rsrec_t *h, const char *key, long value);
 /* Timing of the last recursion call, measured with HIP events on the engine's own stream:

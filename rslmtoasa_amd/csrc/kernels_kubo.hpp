@@ -124,6 +124,112 @@ __global__ __launch_bounds__(256) void k_kubo_gram_reduce(const double2* __restr
     }
 }
 
+// ---- the orbital-diagonal moments alone -------------------------------------------------------------------------------------------
+// conductivity.f90:289 and :292 read mu_nm_stochastic(l, l, n, m, v) and nothing else does: of every 18 x 18 block only the diagonal
+//   mu_diag(c, n, m) = sum_rho conj(L_m[rho][c]) R_n[rho][c]
+// is used.  Per column c that is a cond_ll x cond_ll Gram matrix over rho: 18 independent GEMMs with 1/18 of the flops of k_kubo_gram
+// on the same vectors, at 4 flop per byte read (16 x 16 tile) instead of 48 -- so the way the vectors are read decides.  A row of a
+// vector is 288 contiguous bytes holding all 18 columns, and the four rows of a k-step are 1 152 contiguous bytes: a workgroup
+// (4 waves) stages the k-step slab of 16 left and 16 right vectors into LDS with whole-line reads (8 lanes x 16 B = 128 contiguous
+// bytes of one vector per load, nine loads per lane), and wave w takes columns w, w + 4, ... (5, 5, 4, 4) from there, one
+// v_mfma_f64_16x16x4 tile of C_c each: every slab is read once for all 18 columns of its (m-block, n-block).
+// LDS image  [row r of the k-step][vector v][column c]  of 16-byte complex numbers, vector stride 19 (18 + 1 pad), row stride
+// 16 x 19 = 304: lane (l15, l4) reads slot 304 l4 + 19 l15 + c, and 19 l15 mod 16 runs over all 16 residues while 304 = 0 mod 16, so
+// each 16-lane group of a ds_read_b128 covers the 64 banks once.  The next slab is requested into registers before the MFMAs of the
+// current one and written after them (one LDS buffer, two barriers per k-step of 64-80 MFMA issue slots per wave).
+// Work split and slice ownership as k_kubo_gram; partials  part[ks][m][n][c]  (c fastest, padded to whole tiles), summed in slice order
+// by k_kubo_gram_diag_reduce.  Padding vectors of the last tile repeat a valid vector and land in padding partials that the reduce
+// never reads; the rows of the last k-step past 18 kk lie in the vector's zero block.
+constexpr int KD_T = 16;                      // vectors per tile, both ways
+constexpr int KD_VS = NB + 1;                 // LDS slots (16 B) per vector row
+constexpr int KD_RS = KD_T * KD_VS;           // per row of the k-step
+constexpr int KD_LOADS = 2 * KD_T * 4 * NB / 256;   // 16-byte loads per lane and k-step: 9
+
+__global__ __launch_bounds__(256, 3) void k_kubo_gram_diag(const double* __restrict__ L, size_t ls, int mvec, const double* __restrict__ R, size_t rs, int nvec,
+                                                        int ksteps_total, int ksplit, double2* __restrict__ part, int nbm, int nbn) {
+    typedef double kg_d2 __attribute__((ext_vector_type(2)));
+    __shared__ kg_d2 slab[2 * 4 * KD_RS];                     // left image, then right image: 2 x 19 456 B
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int l15 = lane & 15, l4 = lane >> 4;
+    const int ntask_mn = nbm * nbn;
+    const int xcd = blockIdx.x & 7, t = (int)(blockIdx.x >> 3);
+    if (t >= ntask_mn * (ksplit >> 3)) return;                 // (whole workgroup: no barrier is left waiting)
+    const int ks = xcd + 8 * (t / ntask_mn), mn = t % ntask_mn;
+    const int bm = mn / nbn, bn = mn - bm * nbn;
+    const int per = (ksteps_total + ksplit - 1) / ksplit;
+    const int s0 = ks * per, s1 = min(ksteps_total, s0 + per);
+    // staging: lanes 8 v' .. 8 v' + 7 own vector v' of the 32 (left 0-15, right 16-31) and read its 72 slots j, j + 8, ..., j + 64
+    const int sv = threadIdx.x >> 3, sj = threadIdx.x & 7;
+    const double* src;
+    if (sv < KD_T) src = L + (size_t)min(bm * KD_T + sv, mvec - 1) * ls;
+    else src = R + (size_t)min(bn * KD_T + sv - KD_T, nvec - 1) * rs;
+    src += (size_t)144 * s0 + 2 * sj;
+    int dst[KD_LOADS];
+#pragma unroll
+    for (int i = 0; i < KD_LOADS; ++i) {
+        const int q = sj + 8 * i, r = q / NB, c = q - NB * r;
+        dst[i] = (sv < KD_T ? 0 : 4 * KD_RS) + r * KD_RS + (sv & (KD_T - 1)) * KD_VS + c;
+    }
+    kg_d2 nxt[KD_LOADS];
+    auto fetch = [&]() {
+#pragma unroll
+        for (int i = 0; i < KD_LOADS; ++i) nxt[i] = *reinterpret_cast<const kg_d2*>(src + 16 * i);
+        src += 144;
+    };
+    auto stage = [&]() {
+#pragma unroll
+        for (int i = 0; i < KD_LOADS; ++i) slab[dst[i]] = nxt[i];
+    };
+    constexpr int KD_C = (NB + 3) / 4;                         // columns per wave: 5 (waves 2, 3: the last one is skipped)
+    double4_t cre[KD_C], cim[KD_C];
+#pragma unroll
+    for (int q = 0; q < KD_C; ++q) { cre[q] = (double4_t){0, 0, 0, 0}; cim[q] = (double4_t){0, 0, 0, 0}; }
+    const int ncol = wave < NB - 4 * (KD_C - 1) ? KD_C : KD_C - 1;
+    const int rd = l4 * KD_RS + l15 * KD_VS + wave;
+    if (s0 < s1) fetch();
+#pragma unroll 1
+    for (int s = s0; s < s1; ++s) {
+        stage();
+        __syncthreads();
+        if (s + 1 < s1) fetch();
+#pragma unroll
+        for (int q = 0; q < KD_C; ++q) {
+            if (q == KD_C - 1 && ncol < KD_C) break;           // (wave-uniform)
+            const kg_d2 a = slab[rd + 4 * q], b = slab[4 * KD_RS + rd + 4 * q];
+            const double ar = a[0], ai = a[1], nai = -ai;
+            cre[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, b[0], cre[q], 0, 0, 0);
+            cim[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, b[1], cim[q], 0, 0, 0);
+            cre[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, b[1], cre[q], 0, 0, 0);
+            cim[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(nai, b[0], cim[q], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+    // D register rr of lane (l15, l4): left vector l4 + 4 rr, right vector l15 of the tile
+    const size_t ldp = (size_t)nbn * KD_T;
+    double2* P = part + (size_t)ks * ((size_t)nbm * KD_T) * ldp * NB;
+#pragma unroll
+    for (int q = 0; q < KD_C; ++q) {
+        if (q == KD_C - 1 && ncol < KD_C) break;
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            const int i = bm * KD_T + l4 + 4 * rr, j = bn * KD_T + l15;
+            P[((size_t)i * ldp + j) * NB + wave + 4 * q] = make_double2(cre[q][rr], cim[q][rr]);
+        }
+    }
+}
+
+// sum of the slices' partials in slice order -> mu_diag(c, n0 + n, m0 + m): c fastest on both sides, one thread per element
+__global__ __launch_bounds__(256) void k_kubo_gram_diag_reduce(const double2* __restrict__ part, int ksplit, int prow /*padded left vectors of a slice*/, int pcol, int mvec, int nvec,
+                                                              double2* __restrict__ mu /*this vector's (18,cond_ll,cond_ll)*/, int cond_ll, int m0, int n0) {
+    const size_t slice = (size_t)prow * pcol * NB, rowlen = (size_t)nvec * NB;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < (size_t)mvec * rowlen; e += (size_t)gridDim.x * blockDim.x) {
+        const size_t m = e / rowlen, nc = e - m * rowlen;      // nc = 18 n + c
+        double sr = 0.0, si = 0.0;
+        for (int ks = 0; ks < ksplit; ++ks) { const double2 v = part[(size_t)ks * slice + m * (size_t)pcol * NB + nc]; sr += v.x; si += v.y; }
+        mu[nc + (size_t)NB * ((size_t)n0 + (size_t)cond_ll * (m0 + m))] = make_double2(sr, si);
+    }
+}
+
 // reference layout (column-major interleaved 18x18 blocks, as the Fortran arrays psi(18,18,kk)) <-> CI (row-major): a block transpose
 template <bool TO_CI>
 __global__ __launch_bounds__(384) void k_block_transpose(int kk, const double2* __restrict__ src, double2* __restrict__ dst) {

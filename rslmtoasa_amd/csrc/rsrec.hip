@@ -144,6 +144,7 @@ struct rsrec_handle {
     long opt_kubo_lchunk = 0;    // rsrec_kubo_moments: left vectors held at a time (0: as many as fit)
     long opt_kubo_vbatch = 0;    // rsrec_kubo_moments: random vectors advanced together as the chains of one launch (0: up to 8, as many as fit beside a whole left matrix)
     int n_kubo_left_chunks = 0;
+    int kubo_diag_nvec = 0, kubo_diag_ll = 0;   // rsrec_kubo_moments_diag: the call whose diagonal moments lie in d_kubo[4] (0: nothing resident)
     long opt_orth3 = 1;          // k_mfma_orth3: 1 one 512-register wave per SIMD (tables in registers), 2 two waves per SIMD (tables in LDS)
     long opt_graph = 1;          // level loop of small batches as one HIP graph: 0 never, 1 calls of up to 8 chains, 2 every single-batch call
     // The captured level loop of the last small-batch block-Lanczos call (every SCF iteration repeats it with the same lattice, seeds,
@@ -526,6 +527,7 @@ extern "C" int rsrec_set_lattice(rsrec_t* h, int kk, int nncols, const int32_t* 
     // unchanged-lattice shortcut above pointing at half-replaced tables), and the cached regions of the old lattice are released
     h->have_lattice = false;
     h->have_ham = false;
+    h->kubo_diag_nvec = h->kubo_diag_ll = 0;                     // (resident Kubo moments belong to the lattice they were computed on)
     h->lat_nn.clear(); h->lat_iz.clear();
     release_regions(h);
     h->kk = kk; h->nslots = nslots; h->nmax = nmax; h->ntype = ntype;
@@ -599,6 +601,7 @@ extern "C" int rsrec_set_hamiltonian(rsrec_t* h, int nslots, int hoh, int nsp, c
     const size_t B = 2 * (size_t)BLK;   // doubles per block
     const int ntype = h->ntype, nmax = h->nmax;
     h->hslots = nslots; h->hoh = hoh ? 1 : 0; h->nsp = nsp;
+    h->kubo_diag_nvec = h->kubo_diag_ll = 0;                     // (resident Kubo moments belong to the Hamiltonian they were computed with)
     h->host_ee.assign(ee, ee + 2 * (size_t)BLK * nslots * h->ntype);
     h->host_lsham.assign(lsham, lsham + 2 * (size_t)BLK * h->ntype);
     h->host_eeo.clear(); h->host_enim.clear(); h->host_hall.clear(); h->host_hallo.clear();
@@ -716,7 +719,7 @@ DevProblem make_problem(const rsrec_t* h) {
 // (rsrec_kubo_integrand: tables, S / D planes, partials; up to ~10 GB at RSREC_COND_LL_MAX).  Every entry point that reserves large
 // buffers of its own gives them back before it does, so that it plans on memory that is really free.
 void release_kubo_buffers(rsrec_t* h, bool moments, bool integrand) {
-    if (moments) for (auto& kb : h->d_kubo) kb.release();
+    if (moments) { for (auto& kb : h->d_kubo) kb.release(); h->kubo_diag_nvec = h->kubo_diag_ll = 0; }
     if (integrand) for (auto& cb : h->d_cond) cb.release();
 }
 
@@ -3322,12 +3325,19 @@ int whole_lattice_end(rsrec_t* h, WholeLatticeCall& W, bool rest_is_own_spans = 
 // left / right matrices and is contracted by itself.  A whole left matrix per vector goes first: vectors are added only while it fits.
 struct KuboPlan {
     int cond_ll = 0, n_cu = 0;
+    bool diag = false, resident = false;     // rsrec_kubo_moments_diag: 18 instead of 324 elements per (n, m); the moments of ALL vectors of the call fit d_kubo[4]
     int nchunk = 0, lchunk = 0, nbv = 0;     // right vectors per contraction; left vectors held at a time; vectors in flight
     int ksteps_total = 0, nbn_max = 0;       // k-steps of 4 rows (the last one may end inside the zero block); column blocks of a full contraction
     size_t velems = 0, sstride = 0;          // doubles of one vector; between two slots of a buffer (nbv chains each)
     size_t bytes[5] = {0, 0, 0, 0, 0};       // of the five buffers
     // slices of the row index per contraction: enough wave tasks for a few rounds of the device, at least 64 k-steps per task
     int ksplit_for(int lc) const {
+        if (diag) {                                                               // one workgroup per task, three of them per CU (158 registers)
+            const long blocks = (long)((lc + KD_T - 1) / KD_T) * nbn_max;
+            long ksp = (12L * 3 * n_cu + blocks - 1) / std::max(1L, blocks);
+            ksp = std::min<long>({ksp, 64, std::max(1, ksteps_total / 64)});
+            return (int)std::max<long>(8, (ksp + 7) / 8 * 8);
+        }
         const long blocks = (long)((lc * NB + KG_BLK - 1) / KG_BLK) * nbn_max;
         long ksp = (12L * 8 * n_cu + blocks - 1) / std::max(1L, blocks);          // up to a dozen rounds of the device's wave slots
         ksp = std::min<long>({ksp, 64, std::max(1, ksteps_total / 64)});
@@ -3343,8 +3353,9 @@ struct KuboPlan {
     double* Rslot(int q) const { return Rm + (size_t)q * sstride; }
 };
 
-int kubo_plan(rsrec_t* h, int nvec, int cond_ll, KuboPlan& P) {
+int kubo_plan(rsrec_t* h, int nvec, int cond_ll, bool diag, KuboPlan& P) {
     const int kk = h->kk;
+    P.diag = diag;
     P.cond_ll = cond_ll; P.n_cu = h->n_cu; P.velems = (size_t)(kk + 1) * BLD;
     P.nchunk = std::min(cond_ll, 64);
     size_t free_b = 0, total_b = 0;
@@ -3354,9 +3365,12 @@ int kubo_plan(rsrec_t* h, int nvec, int cond_ll, KuboPlan& P) {
     for (auto& kb : h->d_kubo) reusable += kb.bytes;             // the buffers of the previous call (reused where they are large enough)
     const double budget = 0.9 * (double)(free_b + reusable);
     P.ksteps_total = (int)((NB * (size_t)kk + 3) / 4);
-    P.nbn_max = (P.nchunk * NB + KG_BLK - 1) / KG_BLK;
-    auto part_bytes = [&](int lc) { return (double)P.ksplit_for(lc) * ((lc * NB + KG_BLK - 1) / KG_BLK) * KG_BLK * (double)P.nbn_max * KG_BLK * 16.0; };
-    auto need_for = [&](int lc, int nv) { return (11.0 + lc + P.nchunk) * nv * P.velems * 8 + part_bytes(lc) + (double)nv * cond_ll * cond_ll * BLK * 16.0; };
+    P.nbn_max = diag ? (P.nchunk + KD_T - 1) / KD_T : (P.nchunk * NB + KG_BLK - 1) / KG_BLK;
+    const double mu_bytes = (double)cond_ll * cond_ll * (diag ? NB : BLK) * 16.0;  // one vector's moments
+    auto part_bytes = [&](int lc) {
+        if (diag) return (double)P.ksplit_for(lc) * ((lc + KD_T - 1) / KD_T) * KD_T * (double)P.nbn_max * KD_T * NB * 16.0;
+        return (double)P.ksplit_for(lc) * ((lc * NB + KG_BLK - 1) / KG_BLK) * KG_BLK * (double)P.nbn_max * KG_BLK * 16.0; };
+    auto need_for = [&](int lc, int nv) { return (11.0 + lc + P.nchunk) * nv * P.velems * 8 + part_bytes(lc) + (double)nv * mu_bytes; };
     int lchunk = cond_ll;
     if (h->opt_kubo_lchunk > 0) lchunk = (int)std::min<long>(cond_ll, h->opt_kubo_lchunk);
     int nbv = (int)std::min<long>(nvec, h->opt_kubo_vbatch > 0 ? h->opt_kubo_vbatch : 8);
@@ -3366,7 +3380,9 @@ int kubo_plan(rsrec_t* h, int nvec, int cond_ll, KuboPlan& P) {
         return fail(h, RSREC_ERR_DEVICE, "rsrec_kubo_moments: %.1f GB needed for one left vector at a time on %d atoms, %.1f GB free", need_for(1, 1) * 1e-9, kk, free_b * 1e-9);
     P.lchunk = lchunk; P.nbv = nbv; P.sstride = (size_t)nbv * P.velems;
     P.bytes[0] = 11 * P.sstride * 8; P.bytes[1] = (size_t)lchunk * P.sstride * 8; P.bytes[2] = (size_t)P.nchunk * P.sstride * 8;
-    P.bytes[3] = (size_t)part_bytes(lchunk); P.bytes[4] = (size_t)nbv * cond_ll * cond_ll * BLK * 16;
+    // the diagonal moments of the whole call stay on the handle if they fit beside everything else; lchunk and nbv do not depend on it
+    P.resident = diag && need_for(lchunk, nbv) + (double)(nvec - nbv) * mu_bytes <= budget;
+    P.bytes[3] = (size_t)part_bytes(lchunk); P.bytes[4] = (size_t)(P.resident ? nvec : nbv) * (size_t)mu_bytes;
     return RSREC_OK;
 }
 
@@ -3434,12 +3450,41 @@ int kubo_left_chunk(WholeLatticeCall& W, const KuboPlan& P, int m0, double a, do
     return RSREC_OK;
 }
 
+// The same for the orbital-diagonal moments alone: per column c the Gram matrix of the chunk's left and the block's right vectors, tiles of
+// 16 x 16 vectors x all 18 columns x `ksplit` slices of (k,r), one workgroup each (k_kubo_gram_diag), then k_kubo_gram_diag_reduce.
+// mu_off: where the batch's first vector lies in P.mu (resident moments of the whole call), in vectors.
+int kubo_contract_diag(WholeLatticeCall& W, const KuboPlan& P, int m0, int n, size_t mu_off) {
+    rsrec_t* h = W.h;
+    const int nl = n % P.nchunk, n0 = n - nl, nv = nl + 1, mv = std::min(P.lchunk, P.cond_ll - m0);
+    const int nbm = (mv + KD_T - 1) / KD_T, nbn = (nv + KD_T - 1) / KD_T;
+    // slices: as kubo_contract, for 3 workgroups per CU
+    int ksplit = 8;
+    const long slots = 3L * h->n_cu, cap = std::min<long>(P.ksplit_for(P.lchunk), std::max(8, P.ksteps_total / 64 / 8 * 8));
+    double best = 0.0;
+    for (long c = 8; c <= cap; c += 8) {
+        const long tasks = (long)nbm * nbn * c, rounds = (tasks + slots - 1) / slots;
+        const double eff = (double)tasks / (double)(rounds * slots) * (rounds >= 3 ? 1.0 : 0.9);
+        if (eff > best + 1e-9) { best = eff; ksplit = (int)c; }
+    }
+    HIPCK(h, hipGetLastError());
+    hipEvent_t g0 = next_event(h);
+    const unsigned wgs = 8u * (unsigned)((long)nbm * nbn * (ksplit / 8));
+    const size_t mu_vec = (size_t)P.cond_ll * P.cond_ll * NB;
+    for (int c = 0; c < W.SD.nchains; ++c) {
+        k_kubo_gram_diag<<<wgs, 256, 0, h->stream>>>(P.Lm + (size_t)c * P.velems, P.sstride, mv, P.Rm + (size_t)c * P.velems, P.sstride, nv, P.ksteps_total, ksplit, P.part, nbm, nbn);
+        k_kubo_gram_diag_reduce<<<(int)std::min<long>(4096, ((long)mv * nv * NB + 255) / 256), 256, 0, h->stream>>>(P.part, ksplit, nbm * KD_T, nbn * KD_T, mv, nv, P.mu + (mu_off + c) * mu_vec, P.cond_ll, m0, n0);
+    }
+    W.rest_ev.emplace_back(g0, next_event(h));
+    return RSREC_OK;
+}
+
 // The block of right vectors that ends with order n (slots 0 .. n % nchunk of Rm) against the left chunk from m0 on, between its events:
 // C[(m,c)][(n,c')] = sum_{k,r} conj(L_m[(k,r)][c]) R_n[(k,r)][c'], blocks of C x `ksplit` slices of (k,r), one wave each (k_kubo_gram), then
 // the slices summed in fixed order into mu (k_kubo_gram_reduce).  One contraction per vector of the batch: its matrices are the chain-c
 // columns of the slots (leading dimension = a whole slot).
-int kubo_contract(WholeLatticeCall& W, const KuboPlan& P, int m0, int n) {
+int kubo_contract(WholeLatticeCall& W, const KuboPlan& P, int m0, int n, size_t mu_off = 0) {
     rsrec_t* h = W.h;
+    if (P.diag) return kubo_contract_diag(W, P, m0, n, mu_off);
     const int nl = n % P.nchunk, n0 = n - nl, ncols = (nl + 1) * NB, m_rows = std::min(P.lchunk, P.cond_ll - m0) * NB;
     const int nbm = (m_rows + KG_BLK - 1) / KG_BLK, nbn = (ncols + KG_BLK - 1) / KG_BLK;
     // slices: the multiple of 8 (<= what the partial buffer was sized for, >= 64 k-steps per task) that fills whole rounds of
@@ -3464,28 +3509,27 @@ int kubo_contract(WholeLatticeCall& W, const KuboPlan& P, int m0, int n) {
     return RSREC_OK;
 }
 
-}  // namespace
-
-// compute_moments_stochastic (recursion.f90:979-1234):  mu(:,:,n,m,i) = sum_k [T_{m-1}(H~) r_i]_k^H [v_a T_{n-1}(H~) v_b r_i]_k,
-// H~ = (H - b)/a.  The SpMMs are k_spmm5 over all atoms (blocks outside the reference's growing region are exact zeros); the
-// cond_ll x cond_ll moment contraction of a vector is one complex GEMM  L^H R  over the (atom, row) index (k_kubo_gram on the vectors in place).
-extern "C" int rsrec_kubo_moments(rsrec_t* h, int nvec, int nseed, const int32_t* seed_atoms, const double* seed_coef, int cond_ll, double a, double b,
-                                  const double* v_a, const double* vo_a, const double* v_b, const double* vo_b, double* mu_nm) {
-    XFER(check_ready(h, "rsrec_kubo_moments"));
-    if (nvec < 0 || nseed < 1 || cond_ll < 1 || a == 0.0 || !v_a || !v_b || !mu_nm || (nvec > 0 && (!seed_atoms || !seed_coef)))
-        return fail(h, RSREC_ERR_ARG, "rsrec_kubo_moments: bad argument");
-    if (h->hoh && (!vo_a || !vo_b)) return fail(h, RSREC_ERR_ARG, "rsrec_kubo_moments: hoh requires vo_a and vo_b");
-    if (!h->s5_built) return fail(h, RSREC_ERR_ARG, "rsrec_kubo_moments: lattice has too many neighbour slots for the SpMM kernel");
-    XFER(check_seeds(h, "rsrec_kubo_moments", seed_atoms, (size_t)nvec * nseed, 0));
+// What rsrec_kubo_moments and rsrec_kubo_moments_diag share: everything but the contraction kernels (kubo_contract) and the shape of the
+// result -- `out`: complex (18,18,cond_ll,cond_ll,nvec) on the host, or with `diag` complex (18,cond_ll,cond_ll,nvec), host or device or
+// NULL, and then the moments of the whole call stay in d_kubo[4] if they fit there.
+int kubo_moments_run(rsrec_t* h, const char* fn, bool diag, int nvec, int nseed, const int32_t* seed_atoms, const double* seed_coef, int cond_ll, double a, double b,
+                     const double* v_a, const double* vo_a, const double* v_b, const double* vo_b, double* out) {
+    XFER(check_ready(h, fn));
+    if (nvec < 0 || nseed < 1 || cond_ll < 1 || (diag && cond_ll > RSREC_COND_LL_MAX) || a == 0.0 || !v_a || !v_b || (!diag && !out) || (nvec > 0 && (!seed_atoms || !seed_coef)))
+        return fail(h, RSREC_ERR_ARG, "%s: bad argument", fn);
+    if (h->hoh && (!vo_a || !vo_b)) return fail(h, RSREC_ERR_ARG, "%s: hoh requires vo_a and vo_b", fn);
+    if (!h->s5_built) return fail(h, RSREC_ERR_ARG, "%s: lattice has too many neighbour slots for the SpMM kernel", fn);
+    XFER(check_seeds(h, fn, seed_atoms, (size_t)nvec * nseed, 0));
     HIPCK(h, hipSetDevice(h->device));
     reset_timing(h);
     if (nvec == 0) return RSREC_OK;
+    h->kubo_diag_nvec = h->kubo_diag_ll = 0;                       // (d_kubo[4] is about to be overwritten)
     release_kubo_buffers(h, false, true);                          // (the integrand's buffers; this call's own stay for the next one)
     XFER(build_kubo_operator(h, 0, v_a, vo_a));
     XFER(build_kubo_operator(h, 1, v_b, vo_b));
     if (h->hoh && h->nmax > 0) XFER(build_kubo_hbulk(h));
     KuboPlan P;
-    XFER(kubo_plan(h, nvec, cond_ll, P));
+    XFER(kubo_plan(h, nvec, cond_ll, diag, P));
     XFER(kubo_reserve(h, P));
     HIPCK(h, h->d_seed.reserve((size_t)nseed * 4));
     HIPCK(h, h->d_seedcoef.reserve((size_t)nseed * sizeof(double2)));
@@ -3494,10 +3538,12 @@ extern "C" int rsrec_kubo_moments(rsrec_t* h, int nvec, int nseed, const int32_t
     W.hps = P.vec(KuboPlan::HPS); W.p1 = P.vec(KuboPlan::P1); W.p2 = P.vec(KuboPlan::P2);
     W.ev_begin = next_event(h);
     const KuboSeeds S{nseed, seed_atoms, seed_coef};
-    const size_t mu_vec = 2 * (size_t)BLK * cond_ll * cond_ll;                    // doubles of one vector's moments
+    const size_t mu_vec = 2 * (size_t)(diag ? NB : BLK) * cond_ll * cond_ll;      // doubles of one vector's moments
+    const bool out_dev = diag && out && is_device_ptr(out);       // (the full call's mu_nm is host memory, as ever)
     int n_left_chunks = 0;
     for (int iv0 = 0; iv0 < nvec; iv0 += P.nbv) {
         const int nb = std::min(P.nbv, nvec - iv0);                               // vectors of this batch = chains of its launches
+        const size_t mu_off = P.resident ? (size_t)iv0 : 0;                       // where the batch's moments lie in P.mu, in vectors
         whole_lattice_batch(W, nb, false);
         XFER(kubo_seed_batch(h, P, S, iv0, nb));
         for (int m0 = 0; m0 < cond_ll; m0 += P.lchunk, ++n_left_chunks) {
@@ -3509,27 +3555,59 @@ extern "C" int rsrec_kubo_moments(rsrec_t* h, int nvec, int nseed, const int32_t
             for (int n = 0; n < cond_ll; ++n) {
                 Y.step(W, n, a, b);
                 whole_lattice_apply_v(W, h->kubo_op[0], Y.cur, P.Rslot(n % P.nchunk));
-                if (n % P.nchunk == P.nchunk - 1 || n == cond_ll - 1) XFER(kubo_contract(W, P, m0, n));
+                if (n % P.nchunk == P.nchunk - 1 || n == cond_ll - 1) XFER(kubo_contract(W, P, m0, n, mu_off));
             }
         }
         HIPCK(h, hipGetLastError());
-        XFER(xfer_d2h(h, mu_nm + mu_vec * iv0, P.mu, (size_t)nb * mu_vec * 8));
+        const double* src = reinterpret_cast<const double*>(P.mu) + mu_vec * mu_off;
+        if (out_dev) HIPCK(h, hipMemcpyAsync(out + mu_vec * iv0, src, (size_t)nb * mu_vec * 8, hipMemcpyDeviceToDevice, h->stream));
+        else if (out) XFER(xfer_d2h(h, out + mu_vec * iv0, src, (size_t)nb * mu_vec * 8));
     }
     XFER(whole_lattice_end(h, W, true));
     h->n_kubo_left_chunks = n_left_chunks;
+    if (P.resident) { h->kubo_diag_nvec = nvec; h->kubo_diag_ll = cond_ll; }
     return RSREC_OK;
 }
+
+}  // namespace
+
+// compute_moments_stochastic (recursion.f90:979-1234):  mu(:,:,n,m,i) = sum_k [T_{m-1}(H~) r_i]_k^H [v_a T_{n-1}(H~) v_b r_i]_k,
+// H~ = (H - b)/a.  The SpMMs are k_spmm5 over all atoms (blocks outside the reference's growing region are exact zeros); the
+// cond_ll x cond_ll moment contraction of a vector is one complex GEMM  L^H R  over the (atom, row) index (k_kubo_gram on the vectors in place).
+extern "C" int rsrec_kubo_moments(rsrec_t* h, int nvec, int nseed, const int32_t* seed_atoms, const double* seed_coef, int cond_ll, double a, double b,
+                                  const double* v_a, const double* vo_a, const double* v_b, const double* vo_b, double* mu_nm) {
+    if (!h) return RSREC_ERR_ARG;
+    return kubo_moments_run(h, "rsrec_kubo_moments", false, nvec, nseed, seed_atoms, seed_coef, cond_ll, a, b, v_a, vo_a, v_b, vo_b, mu_nm);
+}
+
+// The same recurrences, but only the orbital-diagonal moments mu(l,l,n,m,i) are contracted (k_kubo_gram_diag): conductivity.f90:289 and
+// :292 are the only reads of mu_nm_stochastic in the reference, and both take (l2, l2, n, m, ntype).
+extern "C" int rsrec_kubo_moments_diag(rsrec_t* h, int nvec, int nseed, const int32_t* seed_atoms, const double* seed_coef, int cond_ll, double a, double b,
+                                       const double* v_a, const double* vo_a, const double* v_b, const double* vo_b, double* mu_diag) {
+    if (!h) return RSREC_ERR_ARG;
+    return kubo_moments_run(h, "rsrec_kubo_moments_diag", true, nvec, nseed, seed_atoms, seed_coef, cond_ll, a, b, v_a, vo_a, v_b, vo_b, mu_diag);
+}
+
+namespace {
 
 // The conductivity integrand of calculate_gamma_nm + calculate_conductivity_tensor (conductivity.f90:158-268) in factorised form
 // (kernels_cond.hpp): integrand(l, i, v) = factor sum_{n,m} Gamma(i,n,m) mu(l,l,n,m,v), no Gamma array.  Vectors one after another:
 // the S / D planes of one vector (18 x L x L x 32 B: 144 MB at L = 500) are the largest buffer.
-extern "C" int rsrec_kubo_integrand(rsrec_t* h, int nvec, int cond_ll, const double* mu_nm, int nen, const double* ene, double energy_min,
-                                    double energy_max, double* integrand) {
-    if (!h) return RSREC_ERR_ARG;
-    if (nvec < 1 || cond_ll < 1 || cond_ll > RSREC_COND_LL_MAX || nen < 1 || !mu_nm || !ene || !integrand)
-        return fail(h, RSREC_ERR_ARG, "rsrec_kubo_integrand: bad argument (nvec=%d cond_ll=%d nen=%d)", nvec, cond_ll, nen);
+// Shared by rsrec_kubo_integrand (`mu_nm`: the full moments (18,18,L,L,nvec)) and rsrec_kubo_integrand_diag (`diag`; `mu_nm`: the diagonals
+// (18,L,L,nvec), or NULL: the resident ones of the last rsrec_kubo_moments_diag call) -- they differ in where k_cond_gather reads.
+int kubo_integrand_run(rsrec_t* h, const char* fn, bool diag, int nvec, int cond_ll, const double* mu_nm, int nen, const double* ene, double energy_min,
+                       double energy_max, double* integrand) {
+    if (nvec < 1 || cond_ll < 1 || cond_ll > RSREC_COND_LL_MAX || nen < 1 || (!diag && !mu_nm) || !ene || !integrand)
+        return fail(h, RSREC_ERR_ARG, "%s: bad argument (nvec=%d cond_ll=%d nen=%d)", fn, nvec, cond_ll, nen);
     if (!std::isfinite(energy_min) || !std::isfinite(energy_max) || !(energy_max > energy_min))
-        return fail(h, RSREC_ERR_ARG, "rsrec_kubo_integrand: energy window [%g, %g] is empty", energy_min, energy_max);
+        return fail(h, RSREC_ERR_ARG, "%s: energy window [%g, %g] is empty", fn, energy_min, energy_max);
+    const bool resident = diag && !mu_nm;
+    if (resident) {
+        if (!h->kubo_diag_nvec) return fail(h, RSREC_ERR_ARG, "%s: no diagonal moments are resident on the handle (rsrec_kubo_moments_diag first, or pass mu_diag)", fn);
+        if (nvec != h->kubo_diag_nvec || cond_ll != h->kubo_diag_ll)
+            return fail(h, RSREC_ERR_ARG, "%s: nvec=%d cond_ll=%d asked, the resident moments have nvec=%d cond_ll=%d", fn, nvec, cond_ll, h->kubo_diag_nvec, h->kubo_diag_ll);
+        mu_nm = h->d_kubo[4].as<double>();
+    }
     HIPCK(h, hipSetDevice(h->device));
     reset_timing(h);
     const int L = cond_ll, lk = (L + 3) / 4 * 4, ln = (L + 15) / 16 * 16, ep = (nen + KC_ROWS - 1) / KC_ROWS * KC_ROWS, ntiles = ln / 16;
@@ -3546,6 +3624,7 @@ extern "C" int rsrec_kubo_integrand(rsrec_t* h, int nvec, int cond_ll, const dou
     const size_t per_vec_out = (size_t)NB * nen;
     // buffer 0: tb (lk x ep), ta (ln x ep complex), pre (ep), w (L), ene (nen);  1: S / D planes;  2: partials;  3: staging
     const size_t o_ta = (size_t)lk * ep, o_pre = o_ta + 2 * (size_t)ln * ep, o_w = o_pre + ep, o_ene = o_w + L, n0 = o_ene + nen;
+    const size_t mu_elems = (size_t)(diag ? NB : BLK) * L * L;        // complex numbers of one vector's moments as the caller holds them
     const size_t mu_compact = mu_dev ? 0 : (size_t)NB * L * L * 2, n3 = mu_compact + (out_dev ? 0 : 2 * per_vec_out * nvec);
     // the moments' buffers (d_kubo) stay for the next rsrec_kubo_moments call unless this call needs their memory
     const size_t want[4] = {n0 * sizeof(double), (size_t)NB * lk * ln * sizeof(double4_t), (size_t)NB * ntiles * ep * sizeof(double2), n3 * sizeof(double)};
@@ -3553,7 +3632,8 @@ extern "C" int rsrec_kubo_integrand(rsrec_t* h, int nvec, int cond_ll, const dou
         if (!want[k]) continue;
         if (h->d_cond[k].reserve(want[k]) != hipSuccess) {
             (void)hipGetLastError();
-            release_kubo_buffers(h, true, false);
+            if (resident) for (int q = 0; q < 4; ++q) h->d_kubo[q].release();      // (all but the moments being read)
+            else release_kubo_buffers(h, true, false);
             HIPCK(h, h->d_cond[k].reserve(want[k]));
         }
     }
@@ -3565,7 +3645,7 @@ extern "C" int rsrec_kubo_integrand(rsrec_t* h, int nvec, int cond_ll, const dou
     HIPCK(h, hipGetLastError());
     double* stage = h->d_cond[3].as<double>();
     double2* out = out_dev ? reinterpret_cast<double2*>(integrand) : reinterpret_cast<double2*>(stage + mu_compact);
-    std::vector<double> diag(mu_dev ? 0 : mu_compact);
+    std::vector<double> dg(mu_dev || diag ? 0 : mu_compact);
     const size_t gelems = (size_t)NB * lk * ln;
     const dim3 cgrid((unsigned)((ep + 4 * KC_ROWS - 1) / (4 * KC_ROWS)), (unsigned)ntiles, NB);
     std::vector<std::pair<hipEvent_t, hipEvent_t>> cev;
@@ -3573,16 +3653,19 @@ extern "C" int rsrec_kubo_integrand(rsrec_t* h, int nvec, int cond_ll, const dou
         const double2* src;
         int sl, sn;
         if (mu_dev) {
-            src = reinterpret_cast<const double2*>(mu_nm) + (size_t)BLK * L * L * v;
-            sl = NB + 1; sn = BLK;                                   // the diagonals where they lie: nothing of size 18 x 18 x L x L is copied
+            src = reinterpret_cast<const double2*>(mu_nm) + mu_elems * v;
+            sl = diag ? 1 : NB + 1; sn = diag ? NB : BLK;            // the diagonals where they lie: nothing of size 18 x 18 x L x L is copied
         } else {                                                     // host moments: only the 18 diagonals cross the bus
-            const double* mv = mu_nm + 2 * (size_t)BLK * L * L * v;
-            for (size_t nm = 0; nm < (size_t)L * L; ++nm)
-                for (int l = 0; l < NB; ++l) {
-                    diag[2 * (nm * NB + l)] = mv[2 * (nm * BLK + (size_t)l * (NB + 1))];
-                    diag[2 * (nm * NB + l) + 1] = mv[2 * (nm * BLK + (size_t)l * (NB + 1)) + 1];
-                }
-            XFER(xfer_h2d(h, stage, diag.data(), mu_compact * sizeof(double)));
+            const double* mv = mu_nm + 2 * mu_elems * v;
+            if (!diag) {
+                for (size_t nm = 0; nm < (size_t)L * L; ++nm)
+                    for (int l = 0; l < NB; ++l) {
+                        dg[2 * (nm * NB + l)] = mv[2 * (nm * BLK + (size_t)l * (NB + 1))];
+                        dg[2 * (nm * NB + l) + 1] = mv[2 * (nm * BLK + (size_t)l * (NB + 1)) + 1];
+                    }
+                mv = dg.data();
+            }
+            XFER(xfer_h2d(h, stage, mv, mu_compact * sizeof(double)));
             src = reinterpret_cast<const double2*>(stage);
             sl = 1; sn = NB;
         }
@@ -3601,6 +3684,21 @@ extern "C" int rsrec_kubo_integrand(rsrec_t* h, int nvec, int cond_ll, const dou
     h->t_total_ms = ev_ms(e_begin, e_end);
     for (auto& pr : cev) h->t_rest_ms += ev_ms(pr.first, pr.second);      // the contractions (k_cond_contract + k_cond_reduce)
     return RSREC_OK;
+}
+
+}  // namespace
+
+extern "C" int rsrec_kubo_integrand(rsrec_t* h, int nvec, int cond_ll, const double* mu_nm, int nen, const double* ene, double energy_min,
+                                    double energy_max, double* integrand) {
+    if (!h) return RSREC_ERR_ARG;
+    return kubo_integrand_run(h, "rsrec_kubo_integrand", false, nvec, cond_ll, mu_nm, nen, ene, energy_min, energy_max, integrand);
+}
+
+// The same from the orbital-diagonal moments of rsrec_kubo_moments_diag, handed in or resident on the handle (mu_diag = NULL)
+extern "C" int rsrec_kubo_integrand_diag(rsrec_t* h, int nvec, int cond_ll, const double* mu_diag, int nen, const double* ene, double energy_min,
+                                         double energy_max, double* integrand) {
+    if (!h) return RSREC_ERR_ARG;
+    return kubo_integrand_run(h, "rsrec_kubo_integrand_diag", true, nvec, cond_ll, mu_diag, nen, ene, energy_min, energy_max, integrand);
 }
 
 // chebyshev_orbital_mod (recursion.f90:2834-3049), the moment part (:2893-3013), device-resident: the seeds are chains advanced together.

@@ -342,10 +342,15 @@ class Recursion:
         self._check(self._L.rsrec_chebyshev(self._h, n, _ptr(seeds), lld, a, b, _ptr(mu)))
         self.mu_n[:, :, :, :n] = mu
 
-    def compute_moments_stochastic(self, v_a, v_b, cond_ll, vo_a=None, vo_b=None, seeds=None, coefs=None, atlist=None):
+    def compute_moments_stochastic(self, v_a, v_b, cond_ll, vo_a=None, vo_b=None, seeds=None, coefs=None, atlist=None, diag=False,
+                                   resident_only=False):
         """Kubo-Bastin double moments mu_nm_stochastic(18,18,cond_ll,cond_ll,nvec) (recursion.f90:979-1234).
         ``cond_calctype='per_type'``: pass ``atlist`` (lattice%atlist, one seed atom per type).  Random vectors: pass ``seeds``
-        (nvec, nseed) atoms and ``coefs`` (nvec, nseed) complex (the caller owns the random numbers)."""
+        (nvec, nseed) atoms and ``coefs`` (nvec, nseed) complex (the caller owns the random numbers).
+
+        ``diag=True``: only the orbital-diagonal moments mu_nm(l,l,n,m,v), the ones conductivity.f90:289, :292 read
+        (``rsrec_kubo_moments_diag``): complex128 (18, cond_ll, cond_ll, nvec) in Fortran order.  They also stay on the device for
+        ``Conductivity.integrand(None, ene)``; with ``resident_only=True`` nothing is downloaded and None is returned."""
         a, b = chebyshev_scaling(self.en.energy_min, self.en.energy_max)
         if seeds is None:
             seeds = np.asarray(atlist, dtype=np.int32).reshape(-1, 1)
@@ -353,8 +358,14 @@ class Recursion:
         seeds = np.ascontiguousarray(seeds, dtype=np.int32)
         coefs = np.ascontiguousarray(coefs, dtype=np.complex128)
         nvec, nseed = seeds.shape
-        mu = np.zeros((18, 18, cond_ll, cond_ll, nvec), np.complex128, order="F")
         keep = [None if v is None else _fc(v, np.complex128) for v in (v_a, vo_a, v_b, vo_b)]
+        if diag:
+            mu = None if resident_only else np.zeros((18, cond_ll, cond_ll, nvec), np.complex128, order="F")
+            self._check(self._L.rsrec_kubo_moments_diag(self._h, nvec, nseed, _ptr(seeds), _ptr(coefs), int(cond_ll), a, b,
+                                                        _ptr(keep[0]), _ptr(keep[1]), _ptr(keep[2]), _ptr(keep[3]), _ptr(mu)))
+            self.mu_diag_resident = (int(cond_ll), nvec)             # what Conductivity.integrand(None, ...) asks the library for
+            return mu
+        mu = np.zeros((18, 18, cond_ll, cond_ll, nvec), np.complex128, order="F")
         self._check(self._L.rsrec_kubo_moments(self._h, nvec, nseed, _ptr(seeds), _ptr(coefs), int(cond_ll), a, b,
                                                _ptr(keep[0]), _ptr(keep[1]), _ptr(keep[2]), _ptr(keep[3]), _ptr(mu)))
         self.mu_nm_stochastic = mu
