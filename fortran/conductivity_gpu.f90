@@ -6,9 +6,13 @@
 ! one call of librsrec, rsrec_kubo_integrand, on the per-process device context (rsrec_context_mod); the sum factorises and no
 ! array of that size exists anywhere (rslmtoasa_amd/csrc/kernels_cond.hpp).  So:
 !   calculate_gamma_nm            : allocates nothing (the tables it would fill are built on the device per call)
-!   calculate_conductivity_tensor : the device integrand, then the reference's tail (:283-372) restated line for line: the sums over
-!                                   the orbitals, simpson_f of math_mod (kept as it is, read past the array end included), and the
-!                                   same files and formats (fort.123, cond_total*.out, <symbol>_cond*.out with 'per_type').
+!   calculate_conductivity_tensor : the device integrand, then the reference's tail (:283-372): the sums over the vectors and the
+!                                   orbitals and the 38 (1 + ntype) nE Fermi-weighted Simpson integrals are one more call,
+!                                   rsrec_kubo_conductivity (region conductivity-tensor-gpu); the host writes the same files in the same
+!                                   formats (fort.123, cond_total*.out, <symbol>_cond*.out with 'per_type').  The device rule takes the
+!                                   element simpson_f reads past its arrays as zero (include/rsrec.h).
+!                                   RSREC_HOST_COND_TAIL set in the environment: the tail restated line for line on the host instead, with
+!                                   simpson_f of math_mod as it is, the stray read included (region conductivity-tensor-host).
 ! Errors of the library become g_logger%fatal, the reference's error behaviour on this path.
 !------------------------------------------------------------------------------
 module conductivity_gpu_mod
@@ -21,7 +25,7 @@ module conductivity_gpu_mod
    use logger_mod, only: g_logger
    use timer_mod, only: g_timer
    use rsrec_binding
-   use rsrec_context_mod, only: rsrec_gpu_context
+   use rsrec_context_mod, only: rsrec_gpu_context, rsrec_env_flag
    use recursion_gpu_mod, only: rsrec_gpu_kubo_diag_resident
    implicit none
 
@@ -62,26 +66,20 @@ contains
 
    subroutine gpu_calculate_conductivity_tensor(this)
       class(conductivity_gpu), intent(inout) :: this
-      integer :: i, l2, ntype, loop_over, nen
+      integer :: loop_over, nen
       integer(c_int) :: rc
       type(c_ptr) :: ctx
       complex(rp), dimension(:, :, :), allocatable, target :: integ           ! (18, nen, loop_over): integrand_at(l2, l2, :, v), factor applied
-      real(rp), dimension(:, :), allocatable :: integrand_l_im, integrand_l_real
-      real(rp), dimension(:), allocatable :: integrand_tot_real, integrand_tot_im, wscale, real_part_l, im_part_l
+      real(rp), dimension(:), allocatable :: wscale
       real(rp), dimension(:), allocatable, target :: ene
-      real(rp) :: a, b, real_part, im_part, factor, volume, de
-      character(len=*), parameter :: fname_cond_total = "cond_total.out"
-      character(len=*), parameter :: fname_cond_orb_real = "cond_total_orb_real.out"
-      character(len=*), parameter :: fname_cond_orb_im = "cond_total_orb_im.out"
-      character(len=sl) :: fname_r, fname_orb_r, fname_orb_i
+      real(rp) :: a, b, factor, volume, de
 
       nen = this%en%channels_ldos + 10
       ! :238-241, :249-252
       a = (this%en%energy_max - this%en%energy_min)/(2 - 0.3)
       b = (this%en%energy_max + this%en%energy_min)/2
       de = this%en%energy_max - this%en%energy_min
-      allocate (wscale(nen), ene(nen), real_part_l(18), im_part_l(18), integrand_tot_real(nen), integrand_tot_im(nen))
-      allocate (integrand_l_real(18, nen), integrand_l_im(18, nen))
+      allocate (wscale(nen), ene(nen))
       ene(:) = this%en%ene(1:nen)
       wscale(:) = (this%en%ene(:) - b)/a
 
@@ -124,6 +122,102 @@ contains
       end if
       if (rc /= 0) call g_logger%fatal('conductivity_gpu%calculate_conductivity_tensor: '//rsrec_error_string(ctx), __FILE__, __LINE__)
       call g_timer%stop('conductivity-integrand-gpu')
+
+      ! :283-372
+      if (rsrec_env_flag('RSREC_HOST_COND_TAIL')) then
+         call g_timer%start('conductivity-tensor-host')
+         call host_tail(this, integ, wscale, a, b, loop_over, nen)
+         call g_timer%stop('conductivity-tensor-host')
+      else
+         call g_timer%start('conductivity-tensor-gpu')
+         call device_tail(this, ctx, integ, ene, wscale, a, b, loop_over, nen)
+         call g_timer%stop('conductivity-tensor-gpu')
+      end if
+
+      deallocate (integ, wscale, ene)
+   end subroutine gpu_calculate_conductivity_tensor
+
+   !> The tail on the device: series and sigma (38, nen, nsets) from one rsrec_kubo_conductivity call -- rows 1-2 Re / Im of the total,
+   !> 3-20 / 21-38 Re / Im of the orbitals; set 1 the sum over the vectors, set 1 + ntype that type alone ('per_type') -- then the
+   !> reference's files, formats, divisions and unit numbers (:293-367).
+   subroutine device_tail(this, ctx, integ, ene, wscale, a, b, loop_over, nen)
+      class(conductivity_gpu), intent(inout) :: this
+      type(c_ptr), intent(in) :: ctx
+      complex(rp), dimension(:, :, :), intent(in), target :: integ
+      real(rp), dimension(:), intent(in), target :: ene
+      real(rp), dimension(:), intent(in) :: wscale
+      real(rp), intent(in) :: a, b
+      integer, intent(in) :: loop_over, nen
+      integer :: i, ntype, nsets, per_vector
+      integer(c_int) :: rc
+      real(rp), dimension(:, :, :), allocatable, target :: sigma, series
+      character(len=*), parameter :: fname_cond_total = "cond_total.out"
+      character(len=*), parameter :: fname_cond_orb_real = "cond_total_orb_real.out"
+      character(len=*), parameter :: fname_cond_orb_im = "cond_total_orb_im.out"
+      character(len=sl) :: fname_r, fname_orb_r, fname_orb_i
+
+      per_vector = 0
+      if (this%control%cond_calctype == 'per_type') per_vector = 1
+      nsets = 1 + per_vector*loop_over
+      allocate (sigma(38, nen, nsets), series(38, nen, nsets))
+      rc = rsrec_kubo_conductivity(ctx, int(loop_over, c_int), int(per_vector, c_int), int(nen, c_int), int(this%en%nv1, c_int), c_loc(ene), &
+                                   real(this%en%energy_min, c_double), real(this%en%energy_max, c_double), 0.0_c_double, c_loc(integ), &
+                                   c_loc(sigma), c_loc(series))
+      if (rc /= 0) call g_logger%fatal('conductivity_gpu%calculate_conductivity_tensor: '//rsrec_error_string(ctx), __FILE__, __LINE__)
+
+      ! :293-313
+      open (unit=3, file=fname_cond_total, status='replace', action='write')
+      open (unit=32, file=fname_cond_orb_real, status='replace', action='write')
+      open (unit=33, file=fname_cond_orb_im, status='replace', action='write')
+      do i = 1, nen
+         write (123, '(3es16.6)') (a*wscale(i) + b) - this%en%fermi, series(1, i, 1), series(2, i, 1)
+         write (3, '(3es16.6)') (a*wscale(i) + b) - this%en%fermi, sigma(1, i, 1)/real(loop_over), sigma(2, i, 1)/real(loop_over)
+         write (32, '(19es16.6)') (a*wscale(i) + b) - this%en%fermi, sigma(3:20, i, 1)/real(loop_over)
+         write (33, '(19es16.6)') (a*wscale(i) + b) - this%en%fermi, sigma(21:38, i, 1)/real(loop_over)
+      end do
+
+      ! :316-367
+      if (per_vector == 1) then
+         do ntype = 1, loop_over
+            fname_r = trim(this%lattice%symbolic_atoms(ntype)%element%symbol)//"_cond.out"
+            fname_orb_r = trim(this%lattice%symbolic_atoms(ntype)%element%symbol)//"_cond_orb_real.out"
+            fname_orb_i = trim(this%lattice%symbolic_atoms(ntype)%element%symbol)//"_cond_orb_im.out"
+
+            open (unit=100 + ntype, file=fname_r, status='replace', action='write')
+            open (unit=300 + ntype, file=fname_orb_r, status='replace', action='write')
+            open (unit=400 + ntype, file=fname_orb_i, status='replace', action='write')
+            do i = 1, nen
+               write (100 + ntype, '(3es16.6)') (a*wscale(i) + b) - this%en%fermi, sigma(1, i, 1 + ntype), sigma(2, i, 1 + ntype)
+               write (300 + ntype, '(19es16.6)') (a*wscale(i) + b) - this%en%fermi, sigma(3:20, i, 1 + ntype)
+               write (400 + ntype, '(19es16.6)') (a*wscale(i) + b) - this%en%fermi, sigma(21:38, i, 1 + ntype)
+            end do
+            close (100 + ntype)
+            close (300 + ntype)
+            close (400 + ntype)
+         end do
+      end if
+      deallocate (sigma, series)
+   end subroutine device_tail
+
+   !> The tail on the host (RSREC_HOST_COND_TAIL): the reference's lines (:283-372) restated, simpson_f of math_mod kept as it is -- its
+   !> loop reads Y(nv1 + 10) and Ene(nv1 + 10), one element past both arrays.
+   subroutine host_tail(this, integ, wscale, a, b, loop_over, nen)
+      class(conductivity_gpu), intent(inout) :: this
+      complex(rp), dimension(:, :, :), intent(in) :: integ
+      real(rp), dimension(:), intent(in) :: wscale
+      real(rp), intent(in) :: a, b
+      integer, intent(in) :: loop_over, nen
+      integer :: i, l2, ntype
+      real(rp), dimension(:, :), allocatable :: integrand_l_im, integrand_l_real
+      real(rp), dimension(:), allocatable :: integrand_tot_real, integrand_tot_im, real_part_l, im_part_l
+      real(rp) :: real_part, im_part
+      character(len=*), parameter :: fname_cond_total = "cond_total.out"
+      character(len=*), parameter :: fname_cond_orb_real = "cond_total_orb_real.out"
+      character(len=*), parameter :: fname_cond_orb_im = "cond_total_orb_im.out"
+      character(len=sl) :: fname_r, fname_orb_r, fname_orb_i
+
+      allocate (real_part_l(18), im_part_l(18), integrand_tot_real(nen), integrand_tot_im(nen))
+      allocate (integrand_l_real(18, nen), integrand_l_im(18, nen))
 
       ! :283-291: integrand(l2, l2, :) is the sum of integrand_at over the vectors
       integrand_tot_real(:) = 0.0d0
@@ -195,7 +289,7 @@ contains
          end do
       end if
 
-      deallocate (integ, integrand_tot_real, integrand_tot_im, wscale, ene, real_part_l, im_part_l, integrand_l_real, integrand_l_im)
-   end subroutine gpu_calculate_conductivity_tensor
+      deallocate (integrand_tot_real, integrand_tot_im, real_part_l, im_part_l, integrand_l_real, integrand_l_im)
+   end subroutine host_tail
 
 end module conductivity_gpu_mod

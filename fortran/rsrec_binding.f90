@@ -206,6 +206,18 @@ module rsrec_binding
          integer(c_int) :: rc
       end function
 
+      ! the conductivity from the integrand: the 38 series of every set (the sum over the vectors; with per_vector /= 0 every vector too)
+      ! and their Fermi-weighted Simpson integrals up to every energy (conductivity.f90:283-372); sigma, series: real (38, nen, nsets)
+      function rsrec_kubo_conductivity(handle, nvec, per_vector, nen, nv1, ene, energy_min, energy_max, temperature, integrand, sigma, series) &
+         bind(C, name='rsrec_kubo_conductivity') result(rc)
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: handle
+         integer(c_int), value :: nvec, per_vector, nen, nv1
+         type(c_ptr), value :: ene, integrand, sigma, series
+         real(c_double), value :: energy_min, energy_max, temperature
+         integer(c_int) :: rc
+      end function
+
       ! exchange couplings of the rank's pairs: intersite g + Jij / Dij / Iij integrands + Simpson integrals (exchange.f90:1032-1615)
       function rsrec_exchange(handle, kind, npairs, same, lld, nen, ene, nv1, fermi, sym_term, energy_min, energy_max, a_inf, b_inf, &
                               coef_a, coef_b, dpar, pair_offset, npairs_total, xc, so, fo, parts, jcum, integrand) &

@@ -46,7 +46,7 @@ contains
 
    !> .true. if the environment variable `name` is set to a non-empty value: run-time switches of the drop-in types for hosts that
    !> cannot set their members (the reference's unmodified calculation.f90 behind the shadow modules): RSREC_HOST_LDOS, RSREC_HOST_MOMENTS, RSREC_HOST_HAM,
-   !> RSREC_DEFER_G0
+   !> RSREC_DEFER_G0, RSREC_HOST_COND_TAIL
    function rsrec_env_flag(name) result(set)
       character(len=*), intent(in) :: name
       logical :: set

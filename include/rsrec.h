@@ -282,6 +282,28 @@ int rsrec_kubo_integrand(rsrec_t *h, int nvec, int cond_ll, const double *mu_nm,
 int rsrec_kubo_integrand_diag(rsrec_t *h, int nvec, int cond_ll, const double *mu_diag, int nen, const double *ene, double energy_min,
                               double energy_max, double *integrand);
 
+/* The conductivity itself: the tail of calculate_conductivity_tensor (conductivity.f90:283-372) -- the sums of the integrand over the
+ * vectors and the orbitals, and their Fermi-weighted Simpson integrals up to every energy of the mesh (kernels_cond.hpp):
+ *   sigma(r, i, s) = simpson_f(x, EF = x(i), nv1, S(r, :, s), fermi = .true., dfermi = .false., temperature)      (math.f90:1600-1632)
+ * on the scaled axis x = (ene - b) / a of rsrec_kubo_integrand.  Rows r of a set: 1 Re total, 2 Im total, 3-20 Re orbital 1..18, 21-38 Im
+ * orbital 1..18.  Rows, sets and vectors are numbered from 1 here (Fortran).  Set 1 is the sum over the vectors (v ascending; the total is the sum over the orbitals, l ascending: the reference's
+ * order); with per_vector != 0 set 1 + v is vector v alone ('per_type'): nsets = 1 + (per_vector ? nvec : 0).
+ *   integrand : complex (18,nen,nvec) in, as rsrec_kubo_integrand delivers it
+ *   sigma     : real (38,nen,nsets) out.  NOT divided by nvec: the caller applies / real(loop_over) where the reference does (:321)
+ *   series    : real (38,nen,nsets) out or NULL: the integrated series S themselves (rows 1-2 of set 1 are fort.123's columns)
+ *   integrand, sigma, series: host or device memory, each detected by itself.  ene: real (nen) host.
+ *   nv1       : energy%nv1; the rule's loop runs I = 2, nv1 + 9, 2, so nen >= nv1 + 9 (energy%e_mesh makes nen = nv1 + 9)
+ *   temperature: simpson_f's argument T, applied on the scaled axis as the reference's call would apply it (kBT = 0.633362019e-5 T + 1e-15
+ *               in units of x); 0 is what the reference passes
+ * Deviation from the reference: simpson_f reads Y(nv1 + 10) and Ene(nv1 + 10), one element past its arrays when nen = nv1 + 9.  Here every
+ * term with an index above nen is zero, as in the exchange entry points.
+ * Needs no lattice and no Hamiltonian.  Resident diagonal moments (rsrec_kubo_moments_diag) survive the call.  Two calls with the same
+ * inputs give the same bits, and a set's values do not depend on the other vectors of the call.  Errors: RSREC_ERR_ARG with a message
+ * (nvec < 1, nen < 3, nv1 < 1, nen < nv1 + 9, an empty or non-finite window, a negative or non-finite temperature, a NULL ene, integrand
+ * or sigma); the handle stays usable.  rsrec_get_timing: out[0] device ms of the call, out[5] ms in its two kernels. */
+int rsrec_kubo_conductivity(rsrec_t *h, int nvec, int per_vector, int nen, int nv1, const double *ene, double energy_min, double energy_max,
+                            double temperature, const double *integrand, double *sigma, double *series);
+
 /* Exchange couplings of the pairs of one rank: green%calculate_intersite_gf / _twoindex (green.f90:386-469) and the integrands and
  * Fermi-weighted Simpson integrals of exchange%calculate_exchange / _twoindex (exchange.f90:1032-1615), without the intersite arrays
  * (kernels_exchange.hpp: g0 of a pair's chains stays in LDS; every quantity is a trace Tr(D_i A D_j B) of the diagonal d_matrix).

@@ -1,7 +1,9 @@
-"""Drop-in counterpart of ``type(conductivity)`` (conductivity.f90:47-72): the energy-resolved Kubo-Bastin integrand on the GPU.
+"""Drop-in counterpart of ``type(conductivity)`` (conductivity.f90:47-72): the Kubo-Bastin conductivity on the GPU.
 
-calculate_gamma_nm + calculate_conductivity_tensor (:158-268) become one call, ``rsrec_kubo_integrand``, that never forms the
-(nE, cond_ll, cond_ll) array gamma_nm.  The Simpson integrations and the output files stay with the caller (host work of O(nE^2)).
+calculate_gamma_nm + the loops of calculate_conductivity_tensor (:158-281) become one call, ``rsrec_kubo_integrand``, that never forms
+the (nE, cond_ll, cond_ll) array gamma_nm.  The tail of calculate_conductivity_tensor (:283-372) -- the sums over the vectors and the
+orbitals and the Fermi-weighted Simpson integral of each of the 38 series up to every energy of the mesh -- is a second call,
+``rsrec_kubo_conductivity`` (``tensor``).  Only the formatting of the output files stays with the caller.
 """
 import ctypes as C
 
@@ -68,7 +70,52 @@ class Conductivity:
                       float(self.en.energy_min), float(self.en.energy_max), out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def tensor(self, integrand, ene, nv1=None, per_vector=False, temperature=0.0, series=False):
+        """The conductivity of calculate_conductivity_tensor's tail (:283-372): real (38, nen, nsets), Fortran order, with
+        sigma[r, i, s] = simpson_f(x, EF = x[i], nv1, S[r, :, s], fermi = .true., T) on the scaled axis x = (ene - b)/a.
+
+        Rows: 0 Re total, 1 Im total, 2-19 Re orbital 1..18, 20-37 Im orbital 1..18.  Sets from 0, as numpy indexes them (the C header and the Fortran side count from 1): set 0 is the sum over the vectors; with
+        ``per_vector`` set 1 + v is vector v alone ('per_type').  NOT divided by the number of vectors: the reference divides when it
+        prints (:321).  Terms simpson_f would read past the mesh are zero (include/rsrec.h).
+        ``integrand``: complex (18, nen[, nvec]) as ``integrand()`` returns it -- a numpy array or a contiguous complex128 torch tensor
+        on the GPU (Fortran order: shape reversed), read in place.
+        ``nv1``: energy%nv1; left at None the Energy object's, or len(ene) - 9 (the mesh energy%e_mesh makes).
+        ``temperature``: in K, the T simpson_f would be given on the unscaled axis; the rule runs on the scaled one, so the library gets T / a.
+        ``series``: also return the integrated series S (38, nen, nsets); rows 0-1 of set 0 are fort.123's columns."""
+        ene = np.ascontiguousarray(ene, dtype=np.float64).ravel()
+        rec = self.recursion
+        if hasattr(integrand, "data_ptr"):                 # torch tensor: read where it lies (GPU memory is not copied)
+            if integrand.element_size() != 16 or not integrand.is_complex() or not integrand.is_contiguous():
+                raise ValueError("an integrand tensor must be contiguous complex128 (the Fortran array seen from C: shape reversed)")
+            if integrand.is_cuda:
+                import torch
+                torch.cuda.synchronize(integrand.device)   # the library reads it on its own stream
+            shape, ptr, keep = tuple(integrand.shape)[::-1], C.c_void_p(integrand.data_ptr()), integrand
+        else:
+            keep = np.asfortranarray(integrand, dtype=np.complex128)
+            shape, ptr = keep.shape, keep.ctypes.data_as(C.c_void_p)
+        if len(shape) == 2:
+            shape = shape + (1,)
+        if len(shape) != 3 or shape[0] != 18 or shape[1] != ene.size:
+            raise ValueError("integrand must be (18, nen[, nvec]) with nen = len(ene) = %d, got %s" % (ene.size, shape))
+        if nv1 is None:
+            nv1 = getattr(self.en, "nv1", None)
+        if nv1 is None:
+            nv1 = ene.size - 9
+        nvec = shape[2]
+        nsets = 1 + (nvec if per_vector else 0)
+        a = (float(self.en.energy_max) - float(self.en.energy_min)) / float(np.float32(2.0) - np.float32(0.3))
+        t_scaled = float(temperature) / a if np.isfinite(a) and a > 0 else float(temperature)      # (an empty window: the library refuses it)
+        sigma = np.zeros((38, ene.size, nsets), np.float64, order="F")
+        ser = np.zeros((38, ene.size, nsets), np.float64, order="F") if series else None
+        rec._check(rec._L.rsrec_kubo_conductivity(rec._h, int(nvec), int(bool(per_vector)), ene.size, int(nv1), ene.ctypes.data_as(C.c_void_p),
+                                                  float(self.en.energy_min), float(self.en.energy_max), t_scaled,
+                                                  ptr, sigma.ctypes.data_as(C.c_void_p), ser.ctypes.data_as(C.c_void_p) if series else None))
+        del keep
+        return (sigma, ser) if series else sigma
+
     def timing(self):
-        """(device ms of the last call, ms in its contraction kernels)."""
+        """(device ms of the last call, ms in its kernels): after ``integrand`` the contraction kernels; after ``tensor`` the series and
+        integral kernels, which are all of that call's device work, so the two values are equal."""
         t = self.recursion.timing()
         return t["total_ms"], t["rest_ms"]

@@ -11,6 +11,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "kernels_mfma.hpp"
+#include "kernels_simpson.hpp"
 
 namespace rsrec {
 
@@ -141,6 +142,72 @@ __global__ __launch_bounds__(256) void k_cond_reduce(int nen, int ep, int ntiles
     double sr = 0.0, si = 0.0;
     for (int t = 0; t < ntiles; ++t) { const double2 v = part[((size_t)l * ntiles + t) * ep + i]; sr += v.x; si += v.y; }
     out[e] = make_double2(pre[i] * sr, pre[i] * si);
+}
+
+// ---- the conductivity itself: the tail of calculate_conductivity_tensor (conductivity.f90:283-372) ----
+// sigma(r, i, s) = simpson_f(x, EF = x(i), nv1, S(r, :, s), fermi = .true., T) for the 38 series r of every set s: Re and Im of the total
+// and of the 18 orbitals; sets and vectors 0-based in this file: set 0 the sum over the vectors, set 1 + v vector v alone ('per_type').
+constexpr int CT_ROWS = 2 + 2 * NB;           // 38: Re total, Im total, Re orbital 1..18, Im orbital 1..18
+constexpr int CT_TILE = 512;                  // Fermi weights staged in LDS at a time (CT_TILE + 1: neighbouring tiles share their end point)
+
+// The series, in the order the reference forms them (:283-291, :316-326).  One thread per (energy k, set s).
+//   set 0    : orbital row l = 0.0 + sum_v integ(l, k, v), v ascending;  total row = 0.0 + sum_l of the orbital rows, l ascending
+//   set 1 + v: orbital row l = integ(l, k, v);  total row = the same sum over l
+// sk: [k][row + 38 set], the layout k_cond_tensor reads (neighbouring threads, neighbouring addresses); series (optional): (38, nen, nsets).
+__global__ __launch_bounds__(256) void k_cond_series(int nen, int nvec, int nsets, const double2* __restrict__ integ, double* __restrict__ sk,
+                                                     double* __restrict__ series) {
+#pragma clang fp contract(off)
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= nen * nsets) return;
+    const int k = e % nen, s = e / nen;
+    double* o = sk + ((size_t)k * nsets + s) * CT_ROWS;
+    double* p = series ? series + ((size_t)s * nen + k) * CT_ROWS : nullptr;
+    double tr = 0.0, ti = 0.0;
+    for (int l = 0; l < NB; ++l) {
+        double re, im;
+        if (s == 0) {
+            re = 0.0; im = 0.0;
+            for (int v = 0; v < nvec; ++v) { const double2 z = integ[((size_t)v * nen + k) * NB + l]; re += z.x; im += z.y; }
+        } else {
+            const double2 z = integ[((size_t)(s - 1) * nen + k) * NB + l];
+            re = z.x; im = z.y;
+        }
+        tr += re; ti += im;
+        o[2 + l] = re; o[2 + NB + l] = im;
+        if (p) { p[2 + l] = re; p[2 + NB + l] = im; }
+    }
+    o[0] = tr; o[1] = ti;
+    if (p) { p[0] = tr; p[1] = ti; }
+}
+
+// The integrals.  Workgroup (i, y): limit EF = x(i), columns c = y blockDim.x + thread of the ncol = 38 nsets (row, set) columns.
+// The weight row f(k) = fermifun(x(k), x(i), kBT) of the limit is computed once per workgroup, CT_TILE + 1 values at a time, in LDS (its
+// size does not depend on nen); every thread then runs its column's serial loop over that tile (simpson_fermi_terms: the bits of one pass
+// over I = 2 .. nv1 + 9).  x(k) = (ene(k) - b) / a as k_cond_basis forms it; weights and integrand from index nen on are zero.
+// No T = 0 special case: kBT = 1e-15 gives the weights 1, 0.5, 0 by itself.  sigma: (38, nen, nsets).
+__global__ __launch_bounds__(1024) void k_cond_tensor(int nen, int nv1, int ncol, const double* __restrict__ ene, double a, double b, double T,
+                                                      const double* __restrict__ sk, double* __restrict__ sigma) {
+#pragma clang fp contract(off)
+    __shared__ double fw[CT_TILE + 1];
+    const int i = blockIdx.x, c = blockIdx.y * blockDim.x + threadIdx.x;
+    const bool live = c < ncol;
+    const double xi = (ene[i] - b) / a, kbt = simpson_kbt(T);
+    const int itop = nv1 + 9;                                        // last I (1-based) of the loop
+    auto y = [&](int k) -> double { return k < nen ? sk[(size_t)k * ncol + c] : 0.0; };
+    double A = 0.0;
+    for (int t0 = 0; t0 + 2 <= itop; t0 += CT_TILE) {                // this tile: I = t0 + 2 .. t0 + CT_TILE, 0-based indices t0 .. t0 + CT_TILE
+        __syncthreads();
+        for (int j = threadIdx.x; j <= CT_TILE; j += blockDim.x) {
+            const int k = t0 + j;
+            fw[j] = k < nen ? fermifun((ene[k] - b) / a, xi, kbt) : 0.0;
+        }
+        __syncthreads();
+        if (live) A = simpson_fermi_terms(A, t0 + 2, min(t0 + CT_TILE, itop), nen, [&](int k) -> double { return fw[k - t0]; }, y);
+    }
+    if (live) {
+        const double H = (ene[1] - b) / a - (ene[0] - b) / a;
+        sigma[((size_t)(c / CT_ROWS) * nen + i) * CT_ROWS + c % CT_ROWS] = H * A / 3.0;
+    }
 }
 
 }  // namespace rsrec

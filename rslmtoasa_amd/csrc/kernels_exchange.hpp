@@ -12,6 +12,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "kernels_green.hpp"
+#include "kernels_simpson.hpp"
 
 namespace rsrec {
 
@@ -216,8 +217,7 @@ __global__ void k_exchange_fermi(int nen, const double* __restrict__ ene, double
 #pragma clang fp contract(off)
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= nen) return;
-    const double kbt = 0.633362019e-5 * 0.0 + 1.0e-15;
-    fw[k] = 1.0 / (exp((ene[k] - ef) / kbt) + 1.0);
+    fw[k] = fermifun(ene[k], ef, simpson_kbt(0.0));
 }
 
 // integrand y(k) of output q (0..66: xc, so, fo, parts) from the 41 rows at energy k, in the reference's expression order
@@ -239,20 +239,12 @@ __device__ __forceinline__ double xc_quantity(const double* __restrict__ r, int 
     return r[13 + q - 39];
 }
 
-// simpson_f(fermi = .true., T = 0) (math.f90:1600-1632) of one integrand y(k) (0-based k; zero from nen on) with the Fermi weights fw,
-// in the reference's summation order.  Its loop runs I = 2, nv1 + 9, 2 and reads Y(I + 1) one element past its arrays at the last I;
-// that term is zero here.  The one Simpson rule of the exchange module's integrals (k_exchange_integrate, k_rows_integrate).
+// simpson_f(fermi = .true., T = 0) (math.f90:1600-1632) of one integrand y(k) (0-based k; zero from nen on) with the Fermi weights fw:
+// the library's one Simpson rule (kernels_simpson.hpp: the reference's summation order, the term it reads past its arrays taken as zero)
+// on a weight array.  The rule of the exchange module's integrals (k_exchange_integrate, k_rows_integrate).
 template <class Y>
 __device__ __forceinline__ double xc_simpson_fermi(int nen, int nv1, double H, const double* __restrict__ fw, Y y) {
-#pragma clang fp contract(off)
-    const int itop = nv1 + 9;                                       // last I (1-based) of the loop
-    double A = 0.0;
-    for (int I = 2; I <= itop; I += 2) {
-        const int k = I - 1;                                        // 0-based index of Y(I)
-        const double f0 = fw[k - 1], f1 = k < nen ? fw[k] : 0.0, f2 = k + 1 < nen ? fw[k + 1] : 0.0;
-        A = ((A + y(k - 1) * f0) + 4.0 * y(k) * f1) + y(k + 1) * f2;
-    }
-    return H * A / 3.0;
+    return simpson_fermi(nen, nv1, H, [&](int k) -> double { return fw[k]; }, y);
 }
 
 // xc_simpson_fermi of every output of every pair, and the cumulative second-order J of fort.150.

@@ -126,6 +126,8 @@ struct rsrec_handle {
                                       // their hipMalloc / hipFree cost 0.1-1.3 s per call on some boxes of the pool); given back when the recursion plans a batch
     DevBuf d_cond[4];                 // rsrec_kubo_integrand: basis tables, S / D planes, column-tile partials, staging (mu diagonals, integrand);
                                       // given back with d_kubo when the recursion plans a batch
+    DevBuf d_ctens[2];                // rsrec_kubo_conductivity: mesh + series as k_cond_tensor reads them; staging (integrand in, sigma / series out);
+                                      // given back with d_cond
     DevBuf d_bsqrt, d_term, d_gim, d_ldos;   // stages on resident coefficients: sqrt(B^2), terminators; LDOS stage: Im g0_jj, output images
     DevBuf d_ops, d_spec;                    // spectra stage: operators (+ their traces with the Chebyshev moments), Im Tr(O g0) of the rank's sites
     void* pin = nullptr;              // pinned host staging buffer: every per-call transfer goes through it (see xfer_*)
@@ -385,7 +387,7 @@ void spatial_key_from_graph(rsrec_t* h) {
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------------------------
-extern "C" int rsrec_version(void) { return 100; }
+extern "C" int rsrec_version(void) { return 101; }
 
 extern "C" int rsrec_device_count(void) {
     int n = 0;
@@ -720,7 +722,7 @@ DevProblem make_problem(const rsrec_t* h) {
 // buffers of its own gives them back before it does, so that it plans on memory that is really free.
 void release_kubo_buffers(rsrec_t* h, bool moments, bool integrand) {
     if (moments) { for (auto& kb : h->d_kubo) kb.release(); h->kubo_diag_nvec = h->kubo_diag_ll = 0; }
-    if (integrand) for (auto& cb : h->d_cond) cb.release();
+    if (integrand) { for (auto& cb : h->d_cond) cb.release(); for (auto& cb : h->d_ctens) cb.release(); }
 }
 
 struct BatchPlan {
@@ -3590,6 +3592,23 @@ extern "C" int rsrec_kubo_moments_diag(rsrec_t* h, int nvec, int nseed, const in
 
 namespace {
 
+// The energy scale of the conductivity, x = (ene - b) / a, as the reference forms it (conductivity.f90:179-180, :238-241): 2 - 0.3 is default REAL(4)
+struct KuboScale {
+    double a, b;
+    KuboScale(double energy_min, double energy_max) : a((energy_max - energy_min) / (double)(2.0f - 0.3f)), b((energy_max + energy_min) / 2) {}
+};
+
+// Reserve a buffer of the conductivity calls.  The moments' buffers (d_kubo) stay for the next rsrec_kubo_moments call unless this one needs
+// their memory; `keep_diag`: the resident diagonal moments (d_kubo[4]) stay even then.
+int reserve_beside_kubo(rsrec_t* h, DevBuf& buf, size_t bytes, bool keep_diag) {
+    if (!bytes || buf.reserve(bytes) == hipSuccess) return RSREC_OK;
+    (void)hipGetLastError();
+    if (keep_diag) for (int q = 0; q < 4; ++q) h->d_kubo[q].release();      // (all but the moments)
+    else release_kubo_buffers(h, true, false);
+    HIPCK(h, buf.reserve(bytes));
+    return RSREC_OK;
+}
+
 // The conductivity integrand of calculate_gamma_nm + calculate_conductivity_tensor (conductivity.f90:158-268) in factorised form
 // (kernels_cond.hpp): integrand(l, i, v) = factor sum_{n,m} Gamma(i,n,m) mu(l,l,n,m,v), no Gamma array.  Vectors one after another:
 // the S / D planes of one vector (18 x L x L x 32 B: 144 MB at L = 500) are the largest buffer.
@@ -3611,8 +3630,9 @@ int kubo_integrand_run(rsrec_t* h, const char* fn, bool diag, int nvec, int cond
     HIPCK(h, hipSetDevice(h->device));
     reset_timing(h);
     const int L = cond_ll, lk = (L + 3) / 4 * 4, ln = (L + 15) / 16 * 16, ep = (nen + KC_ROWS - 1) / KC_ROWS * KC_ROWS, ntiles = ln / 16;
-    // a, b and factor as the reference forms them (:179-180, :254-256): 2 - 0.3 is default REAL(4)
-    const double a = (energy_max - energy_min) / (double)(2.0f - 0.3f), b = (energy_max + energy_min) / 2, de = energy_max - energy_min;
+    // a, b and factor as the reference forms them (:179-180, :254-256)
+    const KuboScale sc(energy_min, energy_max);
+    const double a = sc.a, b = sc.b, de = energy_max - energy_min;
     const double factor = 16 / (3.14159265358979323846 * (de * de));
     // Lorentz kernel x weights (:186-194): lorentz_kernel forms (real(ll) - 1)/real(bign) and 1 - that in single precision (math.f90:1674)
     std::vector<double> w(L);
@@ -3626,17 +3646,8 @@ int kubo_integrand_run(rsrec_t* h, const char* fn, bool diag, int nvec, int cond
     const size_t o_ta = (size_t)lk * ep, o_pre = o_ta + 2 * (size_t)ln * ep, o_w = o_pre + ep, o_ene = o_w + L, n0 = o_ene + nen;
     const size_t mu_elems = (size_t)(diag ? NB : BLK) * L * L;        // complex numbers of one vector's moments as the caller holds them
     const size_t mu_compact = mu_dev ? 0 : (size_t)NB * L * L * 2, n3 = mu_compact + (out_dev ? 0 : 2 * per_vec_out * nvec);
-    // the moments' buffers (d_kubo) stay for the next rsrec_kubo_moments call unless this call needs their memory
     const size_t want[4] = {n0 * sizeof(double), (size_t)NB * lk * ln * sizeof(double4_t), (size_t)NB * ntiles * ep * sizeof(double2), n3 * sizeof(double)};
-    for (int k = 0; k < 4; ++k) {
-        if (!want[k]) continue;
-        if (h->d_cond[k].reserve(want[k]) != hipSuccess) {
-            (void)hipGetLastError();
-            if (resident) for (int q = 0; q < 4; ++q) h->d_kubo[q].release();      // (all but the moments being read)
-            else release_kubo_buffers(h, true, false);
-            HIPCK(h, h->d_cond[k].reserve(want[k]));
-        }
-    }
+    for (int k = 0; k < 4; ++k) XFER(reserve_beside_kubo(h, h->d_cond[k], want[k], resident));      // (resident: the moments being read stay)
     double* T = h->d_cond[0].as<double>();
     XFER(xfer_h2d(h, T + o_w, w.data(), (size_t)L * sizeof(double)));
     XFER(xfer_h2d(h, T + o_ene, ene, (size_t)nen * sizeof(double)));
@@ -3699,6 +3710,60 @@ extern "C" int rsrec_kubo_integrand_diag(rsrec_t* h, int nvec, int cond_ll, cons
                                          double energy_max, double* integrand) {
     if (!h) return RSREC_ERR_ARG;
     return kubo_integrand_run(h, "rsrec_kubo_integrand_diag", true, nvec, cond_ll, mu_diag, nen, ene, energy_min, energy_max, integrand);
+}
+
+namespace {
+
+// The tail of calculate_conductivity_tensor (conductivity.f90:283-372) on the device: the 38 series of every set (k_cond_series) and their
+// Fermi-weighted Simpson integrals up to every mesh energy (k_cond_tensor).  Needs no lattice and no Hamiltonian.
+int kubo_conductivity_run(rsrec_t* h, int nvec, bool per_vector, int nen, int nv1, const double* ene, double energy_min, double energy_max,
+                          double temperature, const double* integrand, double* sigma, double* series) {
+    const char* fn = "rsrec_kubo_conductivity";
+    if (nvec < 1 || nen < 3 || nv1 < 1 || !ene || !integrand || !sigma)
+        return fail(h, RSREC_ERR_ARG, "%s: bad argument (nvec=%d nen=%d nv1=%d)", fn, nvec, nen, nv1);
+    if (nen < nv1 + 9) return fail(h, RSREC_ERR_ARG, "%s: nen=%d is below nv1 + 9 = %d, the last point simpson_f weights", fn, nen, nv1 + 9);
+    if (!std::isfinite(energy_min) || !std::isfinite(energy_max) || !(energy_max > energy_min))
+        return fail(h, RSREC_ERR_ARG, "%s: energy window [%g, %g] is empty", fn, energy_min, energy_max);
+    if (!std::isfinite(temperature) || temperature < 0) return fail(h, RSREC_ERR_ARG, "%s: temperature %g is negative or not finite", fn, temperature);
+    const size_t nsets = 1 + (per_vector ? (size_t)nvec : 0), ncol = (size_t)CT_ROWS * nsets, n_in = (size_t)2 * NB * nen * nvec, n_out = ncol * nen;
+    if (ncol * nen > (size_t)INT32_MAX) return fail(h, RSREC_ERR_ARG, "%s: nvec=%d nen=%d: too many (series, energy) pairs", fn, nvec, nen);
+    HIPCK(h, hipSetDevice(h->device));
+    reset_timing(h);
+    const KuboScale sc(energy_min, energy_max);
+    const bool in_dev = is_device_ptr(integrand), sig_dev = is_device_ptr(sigma), ser_dev = series && is_device_ptr(series);
+    // buffer 0: ene (nen), the series [k][column];  1: staging -- integrand | sigma | series, each only for a caller array on the host
+    const size_t o_sig = in_dev ? 0 : n_in, o_ser = o_sig + (sig_dev ? 0 : n_out), n1 = o_ser + (series && !ser_dev ? n_out : 0);
+    const bool keep_diag = h->kubo_diag_nvec != 0;                   // resident diagonal moments survive the call
+    XFER(reserve_beside_kubo(h, h->d_ctens[0], ((size_t)nen + n_out) * sizeof(double), keep_diag));
+    XFER(reserve_beside_kubo(h, h->d_ctens[1], n1 * sizeof(double), keep_diag));
+    double* d_ene = h->d_ctens[0].as<double>();
+    double* d_sk = d_ene + nen;
+    double* stage = h->d_ctens[1].as<double>();
+    XFER(xfer_h2d(h, d_ene, ene, (size_t)nen * sizeof(double)));
+    if (!in_dev) XFER(xfer_h2d(h, stage, integrand, n_in * sizeof(double)));
+    const double2* d_in = reinterpret_cast<const double2*>(in_dev ? integrand : stage);
+    double* d_sig = sig_dev ? sigma : stage + o_sig;
+    double* d_ser = !series ? nullptr : ser_dev ? series : stage + o_ser;
+    const int threads = (int)std::min<size_t>(1024, (ncol + 63) / 64 * 64);
+    const dim3 grid((unsigned)nen, (unsigned)((ncol + threads - 1) / threads));
+    hipEvent_t e_begin = next_event(h);
+    k_cond_series<<<(int)(((size_t)nen * nsets + 255) / 256), 256, 0, h->stream>>>(nen, nvec, (int)nsets, d_in, d_sk, d_ser);
+    k_cond_tensor<<<grid, threads, 0, h->stream>>>(nen, nv1, (int)ncol, d_ene, sc.a, sc.b, temperature, d_sk, d_sig);
+    hipEvent_t e_end = next_event(h);
+    HIPCK(h, hipGetLastError());
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    if (!sig_dev) XFER(xfer_d2h(h, sigma, d_sig, n_out * sizeof(double)));
+    if (series && !ser_dev) XFER(xfer_d2h(h, series, d_ser, n_out * sizeof(double)));
+    h->t_total_ms = h->t_rest_ms = ev_ms(e_begin, e_end);            // (the call's device work is its two kernels)
+    return RSREC_OK;
+}
+
+}  // namespace
+
+extern "C" int rsrec_kubo_conductivity(rsrec_t* h, int nvec, int per_vector, int nen, int nv1, const double* ene, double energy_min, double energy_max,
+                                       double temperature, const double* integrand, double* sigma, double* series) {
+    if (!h) return RSREC_ERR_ARG;
+    return kubo_conductivity_run(h, nvec, per_vector != 0, nen, nv1, ene, energy_min, energy_max, temperature, integrand, sigma, series);
 }
 
 // chebyshev_orbital_mod (recursion.f90:2834-3049), the moment part (:2893-3013), device-resident: the seeds are chains advanced together.
