@@ -124,7 +124,12 @@ int rsrec_block_lanczos_local_axis(rsrec_t *h, int nsites, const int32_t *seed_a
 int rsrec_pack_diag(rsrec_t *h, int site_offset, int nsites_total, double *a_img, double *b2_img);
 
 /* In-place principal square root of `nmat` Hermitian 18x18 matrices: b2_b <- sqrt(b2_b).
- * Replaces zsqr (recursion.f90:1980-2023). */
+ * Replaces zsqr (recursion.f90:1980-2023).
+ *   Both triangles of every matrix are read and must agree to rounding (zheev('U') of the reference reads the upper one only): the
+ *   root returned is the one of the Hermitian matrix both stand for.  Any finite scale is fine -- the solver works on the matrix
+ *   times a power of two that brings max|entry| into [1, 2), and sqrt(S 2^k) = sqrt(S) 2^(k/2) holds bit for bit for even k.  A
+ *   matrix with a NaN or Inf entry comes back all NaN and the call still returns RSREC_OK (the reference prints zheev's info and
+ *   goes on, :2013); RSREC_ERR_EIG only if the Jacobi sweeps of a finite matrix do not converge. */
 int rsrec_zsqr(rsrec_t *h, int nmat, double *b2_b);
 
 /* Green function from the block coefficients -- the stage right after the recursion.

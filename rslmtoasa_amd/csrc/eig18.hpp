@@ -29,6 +29,42 @@ __device__ inline int jacobi18(Eig18Shared& sh) {
     const int tid = threadIdx.x, nt = blockDim.x;
     for (int e = tid; e < 324; e += nt) sh.V[e] = make_double2((e % 18) == (e / 18) ? 1.0 : 0.0, 0.0);
     __syncthreads();
+    // Largest |component| (a NaN or Inf anywhere makes it Inf).  The matrix is brought to max|A| in [1, 2) with sc = 2^-ilogb(max|A|) and the
+    // eigenvalues are scaled back at the end.  The two convergence sums below are sums of SQUARES: on the entries as they come they
+    // underflow for max|A| below about 2^-500 (the loop then stopped early, below 2^-540 before the first sweep: sqrt of the diagonal came
+    // back, no error raised) and overflow above 2^+500 (a finite matrix took the NaN exit); and far enough down the rotations themselves
+    // lose their phases x / |x| to subnormal x (degenerate spectra: 1e-8 off at 2^-600).  sc is a power of two and every step of the
+    // method is homogeneous, so wherever nothing under- or overflowed before, sweep count and result keep their bits.
+    if (tid < 18) {
+        double m = 0.0;
+        for (int r = 0; r < 18; ++r) {
+            const double2 v = sh.A[r + 18 * tid];
+            // (fmax drops a NaN operand, so a NaN counts as Inf here)
+            m = fmax(m, (v.x == v.x && v.y == v.y) ? fmax(fabs(v.x), fabs(v.y)) : __builtin_inf());
+        }
+        sh.red[tid] = m;
+    }
+    __syncthreads();
+    double amax = 0.0;
+    for (int c = 0; c < 18; ++c) amax = fmax(amax, sh.red[c]);
+    __syncthreads();
+    if (!(amax < __builtin_inf())) {
+        // NaN / Inf in -> NaN out, reported as -2.  This is what a Krylov breakdown looks like one level later: sqrt of a
+        // rounding-negative (or 1 / an exactly zero) eigenvalue of B^2 puts NaN into B, B^-1 and every vector (recursion.f90:1950-1951),
+        // and the NEXT level's zheev gets a NaN matrix.  The compiled reference (MKL zheev) returns info /= 0 for it and crecal_b calls
+        // g_logger%fatal('Diagonalization error') (:1942) -- measured: oracle/make_fixtures.py fuzz_seed_case, the 8-atom cell at
+        // LL = 14; round 1-3 assumed a silent NaN here.  zsqr only prints the info (:2013) and goes on: its caller ignores -2.
+        if (tid < 18) sh.ev[tid] = __builtin_nan("");
+        __syncthreads();
+        return -2;
+    }
+    int ex = amax > 0.0 ? ilogb(amax) : 0;
+    ex = ex < -1000 ? -1000 : (ex > 1000 ? 1000 : ex);        // (2^-ex and 2^ex stay normal numbers; a subnormal matrix still lands above 2^-75)
+    if (ex != 0) {
+        const double sc = ldexp(1.0, -ex);
+        for (int e = tid; e < 324; e += nt) { sh.A[e].x *= sc; sh.A[e].y *= sc; }
+        __syncthreads();
+    }
     // Frobenius norm (fixed-order sum by thread 0 over 18 column sums -> deterministic)
     if (tid < 18) {
         double s = 0.0;
@@ -39,16 +75,6 @@ __device__ inline int jacobi18(Eig18Shared& sh) {
     double nrm = 0.0;
     for (int c = 0; c < 18; ++c) nrm += sh.red[c];
     __syncthreads();
-    if (!(nrm == nrm) || nrm > 1.0e300) {
-        // NaN / Inf in -> NaN out, reported as -2.  This is what a Krylov breakdown looks like one level later: sqrt of a
-        // rounding-negative (or 1 / an exactly zero) eigenvalue of B^2 puts NaN into B, B^-1 and every vector (recursion.f90:1950-1951),
-        // and the NEXT level's zheev gets a NaN matrix.  The compiled reference (MKL zheev) returns info /= 0 for it and crecal_b calls
-        // g_logger%fatal('Diagonalization error') (:1942) -- measured: oracle/make_fixtures.py fuzz_seed_case, the 8-atom cell at
-        // LL = 14; round 1-3 assumed a silent NaN here.  zsqr only prints the info (:2013) and goes on: its caller ignores -2.
-        if (tid < 18) sh.ev[tid] = __builtin_nan("");
-        __syncthreads();
-        return -2;
-    }
     int sweep = 0;
     for (; sweep < 40; ++sweep) {
         if (tid < 18) {
@@ -120,7 +146,7 @@ __device__ inline int jacobi18(Eig18Shared& sh) {
             __syncthreads();
         }
     }
-    if (tid < 18) sh.ev[tid] = sh.A[tid + 18 * tid].x;
+    if (tid < 18) sh.ev[tid] = ldexp(sh.A[tid + 18 * tid].x, ex);      // (exact: back to the scale of the input)
     __syncthreads();
     return sweep < 40 ? sweep : -1;
 }
