@@ -506,6 +506,10 @@ int rsrec_comm_destroy(rsrec_t *h);
  *                spin half of the neighbour blocks; the round-2 default), 0 = both spins on every XCD (2-4 % faster, round 3) [0]
  *   "s5_octet"   atoms with their own operator blocks (nmax) from which their groups are formed over 8 CHAINS of the batch (they then share
  *                the atom's operator fragments the way 8 atoms of a type do) once every chain's region covers the lattice; 0 = never [8]
+ *   "s5_gram_min" the A_n Gram sum u^H (H u) formed in k_spmm5's epilogue instead of by a pass of its own over u and H u: a chain folds at a level
+ *                when its region there has at least this many groups of 8 atoms; 0 = always.  Only block Lanczos on the matrix-core set with k_spmm5,
+ *                on an operator with one class of atoms, without hoh, that rsrec_set_hamiltonian found Hermitian (opposite slots from nn, blocks
+ *                compared to 1e-12 of the largest element); everything else keeps the separate pass [256: from there on the folded level measured faster, DESIGN.md]
  *   "s5_host_emit" 1 = swizzle k_spmm5's operator streams on the host instead of assembling them on the device (cross-check) [0]
  *   "orth_oop"   1 = the orthogonalisation pass writes u_{n+1} into a third u vector instead of over u_{n-1} (faster on the HBM, one more work vector) [1]
  *   "sat_pct"    a chain whose region holds at least this share (per cent) of the lattice runs on the list of ALL atoms instead of its own [100]
@@ -516,7 +520,7 @@ int rsrec_set_option(rsrec_t *h, const char *key, long value);
  *   out[0] total device ms, out[1] ms in the H|psi> kernels, out[2] number of H|psi> launches,
  *   out[3] atom-steps processed (sum over chains and steps of active atoms), out[4] block multiplies in H|psi>,
  *   out[5] ms in the remaining recursion kernels, out[6] host ms (region bookkeeping + transfers),
- *   out[7] 1 if the timed H|psi> kernel also forms the A_n partial (VALU / fused variants), else 0,
+ *   out[7] 1 if the timed H|psi> kernel also forms the A_n partial (VALU set; k_spmm5 when every launch of the call folded the Gram), else 0,
  *   out[8] matrix flops EXECUTED by the timed k_spmm5 launches (padding of the MFMA tiles included, structural zeros of spin-diagonal
  *          blocks not: they are skipped), per operator class of the groups; 0 for the other kernels.
  *   out[9] flops of the H|psi> applications that the operator's BLOCK STRUCTURE requires: out[4] counts the reference's zgemm on full
@@ -525,6 +529,7 @@ int rsrec_set_option(rsrec_t *h, const char *key, long value);
  *   out[10] block arrays (0..4: ee, eeo, hall, hallo) the last rsrec_set_hamiltonian took from rsrec_assemble_blocks' device copies.
  *   out[11] H|psi> launches of the last call in which the atoms with their own operator blocks were grouped over 8 chains (option "s5_octet").
  *   out[12] rsrec_block_lanczos_local_axis: ms in the conjugation of the resident coefficients with the sites' rotations (part of out[5]).
+ *   out[13] H|psi> launches of the last call whose epilogue formed the A_n Gram of at least one chain (option "s5_gram_min").
  * After rsrec_block_green: out[0] = kernel + transfers, out[1] = the Green kernel alone. */
 int rsrec_get_timing(rsrec_t *h, double *out, int n);
 

@@ -157,14 +157,73 @@ template <class T> __device__ __forceinline__ void st_stream(T* p, T v) {
 #endif
 }
 
+// ---- A_n Gram folded into k_spmm5's epilogue (kernels_spmm5.hpp, S5Gram) --------------------------------------------------
+// One partial of S5_GRAM_DOUBLES per (chain, group of the chain's H|psi> list, output spin).  Which (chain, level) passes fold is this one
+// rule on the chain's group count at that level: k_spmm5, k_mfma_adot, k_gram_groupsum and the host all ask it.
+constexpr int S5_GRAM_DOUBLES = 584;
+constexpr long S5_GRAM_MIN_NEVER = 1L << 40;   // a group count no region reaches
+constexpr int S5_GRAM_MAXW = 8;        // workgroups of k_gram_groupsum per chain, at most (= the 36x36 images it fills)
+__host__ __device__ inline bool s5_gram_folds(long ngroups, long min_groups) { return ngroups > 0 && ngroups >= min_groups; }
+// workgroups that sum the partials of a folded chain: a function of its group count alone (batch-size reproducibility)
+__host__ __device__ inline int s5_gram_workgroups(int ngroups) { return ngroups / 4 < 1 ? 1 : (ngroups / 4 < S5_GRAM_MAXW ? ngroups / 4 : S5_GRAM_MAXW); }
+struct GramFold { const int* cum = nullptr; int nlev = 0; long min_groups = 0; };     // cum: the counts of the H|psi> lists, [chain][nlev]; nullptr: nothing folds
+
+// Fixed-order sum of a folded chain's partials: workgroup w of nw = s5_gram_workgroups(ngroups) adds the groups [w ngroups / nw,
+// (w + 1) ngroups / nw), both spins of a group one after the other, one thread per entry; completes the matrix -- G[a < 16][16 + e] =
+// conj(G[16 + e][a]), exact for the summed matrix of a Hermitian operator and linear, so applied to every workgroup's share -- and writes
+// the canonical 36x36 real image (CI columns) into slot w of the chain's k_mfma_adot partials: Re G -> [re a][re b], Im G -> [re a][im b],
+// the two other quadrants zero, so that reduce_gram finds C = G.  The remaining slots of the launch (gridDim.x of them per chain) are
+// zeroed: the reducers add them as +0.  At most S5_GRAM_MAXW <= 16 images, so k_presum16's first chunk is the same sequential sum.
+__global__ __launch_bounds__(640) void k_gram_groupsum(GramFold F, int level, const double* __restrict__ gpart, size_t cstride, double* __restrict__ partial /*[chain][gridDim.x][1296]*/) {
+    __shared__ double sm[S5_GRAM_DOUBLES];
+    const int chain = blockIdx.y, w = blockIdx.x;
+    const int ngroups = F.cum[(size_t)chain * F.nlev + level] / GROUP;
+    if (!s5_gram_folds(ngroups, F.min_groups)) return;                       // k_mfma_adot filled this chain's slots
+    double* img = partial + ((size_t)chain * gridDim.x + w) * 1296;
+    const int nw = s5_gram_workgroups(ngroups);
+    if (w >= nw) {
+        for (int e = threadIdx.x; e < 1296; e += blockDim.x) img[e] = 0.0;
+        return;
+    }
+    const size_t g0 = (size_t)w * ngroups / nw, g1 = (size_t)(w + 1) * ngroups / nw;
+    if (threadIdx.x < S5_GRAM_DOUBLES) {
+        const double* src = gpart + (size_t)chain * cstride + threadIdx.x;
+        double s = 0.0;
+        size_t q = 2 * g0;
+        for (; q + 16 <= 2 * g1; q += 16) {
+            double v[16];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) v[i] = ld_stream(src + (q + i) * S5_GRAM_DOUBLES);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) s += v[i];
+        }
+        for (; q < 2 * g1; ++q) s += ld_stream(src + q * S5_GRAM_DOUBLES);
+        sm[threadIdx.x] = s;
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < 1296; e += blockDim.x) {
+        const int r = e / 36, c = e - 36 * r, a = r >> 1, b = c >> 1, part = c & 1;
+        double v = 0.0;
+        if ((r & 1) == 0) {
+            if (a < 16 && b < 16) v = sm[256 * part + 4 * (16 * (a & 3) + b) + (a >> 2)];
+            else if (a >= 16 && b < 16) v = sm[512 + 2 * (16 * (a - 16) + b) + part];
+            else if (a >= 16) v = sm[576 + 2 * (2 * (a - 16) + (b - 16)) + part];
+            else { const double t = sm[512 + 2 * (16 * (b - 16) + a) + part]; v = part ? -t : t; }
+        }
+        img[e] = v;
+    }
+}
+
 #ifndef ADOT_UNROLL
 #define ADOT_UNROLL 4
 #endif
 // ---- A_n partial: Gm = sum_rows psihat^T * that   (hop_b :1642) -------------------------------------------------------
 __global__ __launch_bounds__(MF_WAVES * 64, 2) void k_mfma_adot(ChainView CV, int level, int zero_block, const double* __restrict__ psi,
-                                                               const double* __restrict__ tvec, double* partial /*[chain][nblk][1296]*/) {
+                                                               const double* __restrict__ tvec, double* partial /*[chain][nblk][1296]*/,
+                                                               GramFold F = GramFold() /*chains whose Gram k_spmm5 formed: nothing to do*/) {
     __shared__ double lds[MF_WAVES * 1296];
     const int chain = blockIdx.y;
+    if (F.cum && s5_gram_folds(F.cum[(size_t)chain * F.nlev + level] / GROUP, F.min_groups)) return;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int ngroups = CV.count_of(chain, level) / GROUP;

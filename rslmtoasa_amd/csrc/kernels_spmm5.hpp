@@ -728,12 +728,28 @@ __device__ __forceinline__ void s5_run_stream_n(S5AccN<NMAIN + (HASREM ? 1 : 0)>
 // level); its Gram matrices are formed by k_mfma_cheb<., true> in one pass over cur and out.
 struct S5Epilogue { int kind = 0; const double* cur = nullptr; const double* old = nullptr; double a = 1.0, b = 0.0; };
 
+// A_n Gram in the epilogue (GRAM; kind 0, one input, whole groups): G = sum_atoms u^H t' with t' = H u still in the accumulators and the
+// own-atom block of u read back from the input vector.  A wave forms the partial of its (group, output spin) over the eight atoms in tile
+// order and writes it to out[chain][group index in the chain's list][spin][S5_GRAM_DOUBLES]:
+//   [0, 256)   Re G[a][b], a, b < 16, as the 16x16x4 result registers lie: double 4 lane + j = row a = (lane >> 4) + 4 j, column b = lane & 15
+//   [256, 512) Im G[a][b], likewise
+//   [512, 576) G[16 + e][b], b < 16: complex at 2 (16 e + b)
+//   [576, 584) G[16 + e'][16 + e]:   complex at 2 (2 e' + e)
+// G[a < 16][16 + e] is never formed: G is Hermitian when H is, and k_gram_groupsum completes the summed matrix from the strip (the
+// partial of one group is NOT Hermitian -- H couples the groups and the spins).  The ninth tile (columns 16, 17 of eight different atoms)
+// would need per-atom operands for those entries; as it is it only feeds the 2x2 corner.
+// Which (chain, level) passes fold is ONE rule on the chain's group count at that level (the count of the H|psi> list), the same for
+// k_spmm5, k_mfma_adot (which leaves a folded chain alone), k_gram_groupsum and the host.
+// (S5_GRAM_DOUBLES, s5_gram_folds and k_gram_groupsum: kernels_mfma.hpp, beside k_mfma_adot.)
+struct S5Gram { double* out = nullptr; size_t cstride = 0; long min_groups = 0; };
+
 // OCT (global-load form only): a group is ONE atom with its own operator blocks (class tau < nmax) and its 8 tiles are 8 chains of the
 // batch -- blockIdx.y counts octets of chains, the groups are the run [run_lo, run_hi) of the class-sorted list of all atoms, which
 // every chain of the launch must be on (the host launches this form only then).  Chains share an atom's fragments the way 8 atoms of a
 // type do; as groups of their own such atoms fill one tile of nine.
 // NSP = 3 (LDS / persistent form only): split tasks -- a wave takes a third of a group's tiles (s5_run_stream_n); up to 16 waves per workgroup.
-template <bool TWO, bool LDSA, bool OCT = false, int NSP = 1>
+// GRAM: the launch may fold the A_n Gram (S5Gram above) -- a variant of its own, so that the plain kernel keeps its registers.
+template <bool TWO, bool LDSA, bool OCT = false, int NSP = 1, bool GRAM = false>
 __global__ __launch_bounds__(NSP == 3 ? 768 : S5_WG_GROUPS * 128) void k_spmm5(SpmmDims D, const int* __restrict__ order_all, const int* __restrict__ cum,
                                                const int* __restrict__ nbr /*nbr5: (kk+1) x (nslots+2)*/,
                                                const int* __restrict__ izp, const double* __restrict__ frag, const int* __restrict__ meta, int ntr,
@@ -743,7 +759,8 @@ __global__ __launch_bounds__(NSP == 3 ? 768 : S5_WG_GROUPS * 128) void k_spmm5(S
                                                int ntau = 0, int lds_tau = 0 /*LDSA: the operator class whose stream is staged (all groups must be of it)*/,
                                                int* __restrict__ queue = nullptr /*LDSA: [chain][16] group counters, zero at launch: persistent workgroups, one group per pull*/,
                                                int spin_by_xcd = 1 /*LDSA: 1: even XCDs spin 0, odd spin 1 (collinear operators); 0: both spins on every XCD*/,
-                                               S5Epilogue epi = S5Epilogue()) {
+                                               S5Epilogue epi = S5Epilogue(), S5Gram gram = S5Gram()) {
+    static_assert(!GRAM || (!TWO && !OCT && NSP == 1), "the Gram epilogue: one input, whole groups of atoms");
     extern __shared__ double s5_lds[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -793,6 +810,7 @@ __global__ __launch_bounds__(NSP == 3 ? 768 : S5_WG_GROUPS * 128) void k_spmm5(S
     for (int chain = OCT ? GROUP * (int)blockIdx.y : (int)blockIdx.y; chain < D.nchains; chain += OCT ? GROUP * (int)gridDim.y : (int)gridDim.y) {
     const int count = cum[(chain / D.cpo) * D.nlev + D.level];
     int ngroups = count / GROUP;
+    const bool fold = GRAM && gram.out != nullptr && epi.kind == 0 && s5_gram_folds(ngroups, gram.min_groups);
     const int ob = D.obase[(chain / D.cpo) * D.nlev + D.level];
     const int* __restrict__ order = order_all + (size_t)(chain / D.cpo) * D.ostride + ob;
     const bool on_full_list = D.sat_base > 0 && ob == D.sat_base;          // the class-sorted list of all atoms
@@ -1005,11 +1023,118 @@ __global__ __launch_bounds__(NSP == 3 ? 768 : S5_WG_GROUPS * 128) void k_spmm5(S
         if (kpart) continue;                                // (probe: one part stores)
 #endif
 
+        // The Gram epilogue (see S5Gram): result register j of tile t < 8 is the B operand of k-step j of a 16x16x4 whose A operand is the
+        // own-atom element of u at the same (m, c = l15) -- its part matching the row for Re G, (-Ui, Ur) for Im G; the remainder register
+        // (re, im of m = 8, two padding rows) is a fifth k-step.  Rows 16, 17 of G and the corner on the vector pipe from the same registers.
+        // Tiles in order, a few at a time: their operands live in the registers of the dead operand sets.
+        if constexpr (GRAM) if (fold) {
+            // the lane's coordinates again, from an instruction the compiler cannot move: derived from the kernel's own l15 / l4 every lane
+            // constant of this block was hoisted over the stream loop, which has no register to spare (the allocator then spilled)
+            unsigned gl;
+            asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(gl));
+            const int lane = (int)gl, l15 = lane & 15, l4 = lane >> 4;
+            const double* __restrict__ ub = in_all + vo;
+            double4_t gre = {0, 0, 0, 0}, gim = {0, 0, 0, 0};
+            double sre[2] = {0.0, 0.0}, sim[2] = {0.0, 0.0}, kre[2] = {0.0, 0.0}, kim[2] = {0.0, 0.0};
+            // this lane's coefficients of the remainder row: l4 = 0 holds Re t'(m = 8), l4 = 1 Im t'(m = 8), l4 >= 2 padding
+            auto rem_coef = [&](s5_d2 u, double& cr, double& ci) {
+                cr = l4 == 0 ? u[0] : (l4 == 1 ? u[1] : 0.0);
+                ci = l4 == 0 ? -u[1] : (l4 == 1 ? u[0] : 0.0);
+            };
+            auto gram_tiles = [&](auto t0c, auto t1c) {
+                constexpr int T0 = decltype(t0c)::value, T1 = decltype(t1c)::value, NT = T1 - T0;
+                s5_d2 gu[NT][3], gs[NT][3][2];
+#pragma unroll
+                for (int i = 0; i < NT; ++i) {
+                    const int t = T0 + i;
+                    const double* ab = ub + (size_t)BLD * ((t < 8) ? vatom[t] : my_rem_atom) + 324 * sig;
+#pragma unroll
+                    for (int p = 0; p < 3; ++p) {
+                        const int row = 36 * (p < 2 ? 4 * p + l4 : 8);
+                        if (t < 8) gu[i][p] = *reinterpret_cast<const s5_d2*>(ab + row + 2 * l15);
+#pragma unroll
+                        for (int e = 0; e < 2; ++e) gs[i][p][e] = *reinterpret_cast<const s5_d2*>(ab + row + 32 + 2 * e);
+                    }
+                }
+#pragma unroll
+                for (int i = 0; i < NT; ++i) {
+                    const int t = T0 + i;
+                    const double x8 = acc.r[t];
+                    if (t < 8) {
+#pragma unroll
+                        for (int p = 0; p < 2; ++p) {
+                            gre = __builtin_amdgcn_mfma_f64_16x16x4f64(gu[i][p][0], acc.m[t][2 * p], gre, 0, 0, 0);
+                            gre = __builtin_amdgcn_mfma_f64_16x16x4f64(gu[i][p][1], acc.m[t][2 * p + 1], gre, 0, 0, 0);
+                            gim = __builtin_amdgcn_mfma_f64_16x16x4f64(-gu[i][p][1], acc.m[t][2 * p], gim, 0, 0, 0);
+                            gim = __builtin_amdgcn_mfma_f64_16x16x4f64(gu[i][p][0], acc.m[t][2 * p + 1], gim, 0, 0, 0);
+                        }
+                        double cr, ci;
+                        rem_coef(gu[i][2], cr, ci);
+                        gre = __builtin_amdgcn_mfma_f64_16x16x4f64(cr, x8, gre, 0, 0, 0);
+                        gim = __builtin_amdgcn_mfma_f64_16x16x4f64(ci, x8, gim, 0, 0, 0);
+                    }
+                    double (&are)[2] = (t < 8) ? sre : kre;
+                    double (&aim)[2] = (t < 8) ? sim : kim;
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+#pragma unroll
+                        for (int p = 0; p < 2; ++p) {
+                            const double ur = gs[i][p][e][0], ui = gs[i][p][e][1], tr = acc.m[t][2 * p], ti = acc.m[t][2 * p + 1];
+                            are[e] = fma(ur, tr, are[e]); are[e] = fma(ui, ti, are[e]);
+                            aim[e] = fma(ur, ti, aim[e]); aim[e] = fma(-ui, tr, aim[e]);
+                        }
+                        double cr, ci;
+                        rem_coef(gs[i][2][e], cr, ci);
+                        are[e] = fma(cr, x8, are[e]);
+                        aim[e] = fma(ci, x8, aim[e]);
+                    }
+                }
+            };
+            gram_tiles(S5C<0>{}, S5C<2>{});
+            __builtin_amdgcn_sched_barrier(0);
+            gram_tiles(S5C<2>{}, S5C<4>{});
+            __builtin_amdgcn_sched_barrier(0);
+            gram_tiles(S5C<4>{}, S5C<6>{});
+            __builtin_amdgcn_sched_barrier(0);
+            gram_tiles(S5C<6>{}, S5C<8>{});
+            __builtin_amdgcn_sched_barrier(0);
+            gram_tiles(S5C<8>{}, S5C<9>{});
+            __builtin_amdgcn_sched_barrier(0);
+            // the four lanes of a column (l4 = 0..3) in that order; the corner then over its eight atoms (l15 >> 1) in that order
+            auto sum_l4 = [&](double v) {
+                double s = __shfl(v, l15);
+                s += __shfl(v, l15 + 16); s += __shfl(v, l15 + 32); s += __shfl(v, l15 + 48);
+                return s;
+            };
+            auto sum_atoms = [&](double v) {
+                double s = __shfl(v, l15 & 1);
+#pragma unroll
+                for (int a = 1; a < GROUP; ++a) s += __shfl(v, 2 * a + (l15 & 1));
+                return s;
+            };
+            double* gp = gram.out + (size_t)chain * gram.cstride + ((size_t)g * 2 + sig) * S5_GRAM_DOUBLES;
+            s5_d2 v;
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                v[0] = gre[2 * p]; v[1] = gre[2 * p + 1];
+                *reinterpret_cast<s5_d2*>(gp + 4 * lane + 2 * p) = v;
+                v[0] = gim[2 * p]; v[1] = gim[2 * p + 1];
+                *reinterpret_cast<s5_d2*>(gp + 256 + 4 * lane + 2 * p) = v;
+            }
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                v[0] = sum_l4(sre[e]); v[1] = sum_l4(sim[e]);
+                if (l4 == e) *reinterpret_cast<s5_d2*>(gp + 512 + 2 * (16 * e + l15)) = v;
+                v[0] = sum_atoms(sum_l4(kre[e])); v[1] = sum_atoms(sum_l4(kim[e]));
+                if (lane < 2) *reinterpret_cast<s5_d2*>(gp + 576 + 2 * (2 * e + lane)) = v;
+            }
+        }
         // 16x16x4 result register j, lane (l15, l4): real-form row l4 + 4 j of spin sig = (part j & 1, m = l4 + 4 (j >> 1)), column l15:
         // registers (2 p, 2 p + 1) are the real and imaginary part of element (m = 4 p + l4, c) -> one 16-byte store in the CI
         // layout; the 4x4x4 result: row 16 + l4 -> l4 = 0: re, 1: im of m = 8
         // Epilogue operands first, for several tiles at once (the three operand sets of the stream are dead: ~110 registers are free):
         // two memory round trips per group instead of one per tile.  Padding atoms read the zero block; only their stores are skipped.
+        const int ekind = GRAM ? 0 : epi.kind;              // (the Gram variant is launched without an element-wise epilogue)
         auto finish = [&](auto t0c, auto t1c) {
             constexpr int T0 = decltype(t0c)::value, T1 = decltype(t1c)::value, NT = T1 - T0;
             size_t eo[NT];
@@ -1017,7 +1142,7 @@ __global__ __launch_bounds__(NSP == 3 ? 768 : S5_WG_GROUPS * 128) void k_spmm5(S
             for (int i = 0; i < NT; ++i) { const int t = T0 + i; eo[i] = (size_t)BLD * ((t < 8) ? vatom[t] : my_rem_atom) + 324 * sig + ((t < 8) ? 2 * l15 : 32 + 2 * (l15 & 1)); }
             s5_d2 ec[NT][2], ez[NT][2];
             double ecr[NT], ezr[NT];
-            if (epi.kind) {
+            if (ekind) {
                 const double* cb = epi.cur + vo;
 #pragma unroll
                 for (int i = 0; i < NT; ++i) {
@@ -1025,7 +1150,7 @@ __global__ __launch_bounds__(NSP == 3 ? 768 : S5_WG_GROUPS * 128) void k_spmm5(S
                     for (int p = 0; p < 2; ++p) ec[i][p] = *reinterpret_cast<const s5_d2*>(cb + eo[i] + 36 * (4 * p + l4));
                     ecr[i] = cb[eo[i] + 288 + (l4 & 1)];
                 }
-                if (epi.kind == 2) {
+                if (ekind == 2) {
                     const double* zb = epi.old + vo;
 #pragma unroll
                     for (int i = 0; i < NT; ++i) {
@@ -1043,16 +1168,16 @@ __global__ __launch_bounds__(NSP == 3 ? 768 : S5_WG_GROUPS * 128) void k_spmm5(S
 #pragma unroll
                 for (int p = 0; p < 2; ++p) {
                     s5_d2 v; v[0] = acc.m[t][2 * p]; v[1] = acc.m[t][2 * p + 1];
-                    if (epi.kind) {
+                    if (ekind) {
                         v[0] = (v[0] - epi.b * ec[i][p][0]) / epi.a; v[1] = (v[1] - epi.b * ec[i][p][1]) / epi.a;
-                        if (epi.kind == 2) { v[0] = v[0] * 2.0 - ez[i][p][0]; v[1] = v[1] * 2.0 - ez[i][p][1]; }
+                        if (ekind == 2) { v[0] = v[0] * 2.0 - ez[i][p][0]; v[1] = v[1] * 2.0 - ez[i][p][1]; }
                     }
                     if (a != zero_block) *reinterpret_cast<s5_d2*>(ob + 36 * (4 * p + l4)) = v;
                 }
                 double r = acc.r[t];
-                if (epi.kind) {
+                if (ekind) {
                     r = (r - epi.b * ecr[i]) / epi.a;
-                    if (epi.kind == 2) r = r * 2.0 - ezr[i];
+                    if (ekind == 2) r = r * 2.0 - ezr[i];
                 }
                 if (a != zero_block && l4 < 2) ob[288 + l4] = r;
             }

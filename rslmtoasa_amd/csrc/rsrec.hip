@@ -149,6 +149,16 @@ struct rsrec_handle {
     int kubo_diag_nvec = 0, kubo_diag_ll = 0;   // rsrec_kubo_moments_diag: the call whose diagonal moments lie in d_kubo[4] (0: nothing resident)
     long opt_orth3 = 1;          // k_mfma_orth3: 1 one 512-register wave per SIMD (tables in registers), 2 two waves per SIMD (tables in LDS)
     long opt_graph = 1;          // level loop of small batches as one HIP graph: 0 never, 1 calls of up to 8 chains, 2 every single-batch call
+    // A_n Gram folded into k_spmm5's epilogue (kernels_spmm5.hpp, S5Gram): a chain folds at a level when its region there has at least this
+    // many groups of 8 atoms (0: always).  Measured per level on 16^3, 22^3 and 46^3: up to 84 groups the folded level is
+    // 0.01-0.04 ms slower, at 139 and 212 groups the two are within the trace's 0.01 ms, from 308 groups on the folded level is faster in every
+    // measurement -- 256 lies between.  Only operators that passed the Hermiticity check of rsrec_set_hamiltonian fold at all.
+    long opt_s5_gram_min = 256;
+    int ham_hermitian = 0;       // the operator as last set: one class, no hoh, and H_ji = H_ij^H block by block (see check_hermitian)
+    std::vector<int> opp_slot;   // per slot: the slot that leads back (nbr(nbr(i, s), opp_slot[s]) == i for every atom i), empty: no unique map
+    int opp_epoch = -1;          // lattice_epoch opp_slot was derived for
+    DevBuf d_gram;               // the folded Gram's partials: [chain][group][spin][S5_GRAM_DOUBLES]
+    double n_gram_folded = 0, n_gram_all = 0, n_gram_levels = 0;   // H|psi> launches of the last call in which some / every chain folded; all its launches
     // The captured level loop of the last small-batch block-Lanczos call (every SCF iteration repeats it with the same lattice, seeds,
     // depth and buffers; the operator's VALUES are read through device pointers and may change).  key = everything the nodes hold by value.
     hipGraphExec_t graph_exec = nullptr;
@@ -170,6 +180,7 @@ struct rsrec_handle {
         double atom_steps, block_mults;
         DevBuf order, cum;
         std::vector<int> level_max;     // per level: largest active-atom count over the chains of this entry
+        std::vector<int> hop_min, hop_max;  // per level: smallest / largest count of the H|psi> lists (padding included) over the chains
         std::vector<double> level_groups;   // [level][tau]: groups of 8 atoms (padding included) of operator class tau, summed over the chains
         std::vector<double> mult_hist;      // [pass 0/1][tau][nslots + 1]: block multiplications of the call by (pass, operator class, slot), summed over the chains
         // the list of ALL atoms (used once a region covers the lattice) is sorted by operator class: one run of groups per class
@@ -226,6 +237,7 @@ const OptionEntry OPTIONS[] = {
     {"s5_octet", &rsrec_handle::opt_s5_octet},
     {"s5_spin_xcd", &rsrec_handle::opt_s5_spin_xcd},
     {"s5_run_min", &rsrec_handle::opt_s5_run_min},
+    {"s5_gram_min", &rsrec_handle::opt_s5_gram_min},
 };
 
 int fail(rsrec_t* h, int code, const char* fmt, ...) {
@@ -463,9 +475,9 @@ extern "C" int rsrec_set_option(rsrec_t* h, const char* key, long value) {
 
 extern "C" int rsrec_get_timing(rsrec_t* h, double* out, int n) {
     if (!h || !out) return RSREC_ERR_ARG;
-    const double v[13] = {h->t_total_ms, h->t_hop_ms, h->n_hop_launch, h->n_atom_steps, h->n_block_mult, h->t_rest_ms, h->t_host_ms, (double)h->hop_fuses_a, h->n_hop_mfma_flop,
-                          h->n_req_flop, (double)h->n_asm_reused, (double)h->n_octet_launch, h->t_rot_ms};
-    for (int i = 0; i < n && i < 13; ++i) out[i] = v[i];
+    const double v[14] = {h->t_total_ms, h->t_hop_ms, h->n_hop_launch, h->n_atom_steps, h->n_block_mult, h->t_rest_ms, h->t_host_ms, (double)h->hop_fuses_a, h->n_hop_mfma_flop,
+                          h->n_req_flop, (double)h->n_asm_reused, (double)h->n_octet_launch, h->t_rot_ms, h->n_gram_folded};
+    for (int i = 0; i < n && i < 14; ++i) out[i] = v[i];
     return RSREC_OK;
 }
 
@@ -592,6 +604,51 @@ extern "C" int rsrec_set_positions(rsrec_t* h, const double* cr) {
     return RSREC_OK;
 }
 
+namespace {
+
+// Is the operator as set Hermitian, H_ji = H_ij^H?  Asked of operators with one class and no hoh only (what the Gram fold serves).  The
+// slot that leads back comes from the neighbour table: slot s of atom i leads to j, and s' is the slot of j that holds i -- the same s'
+// for every atom, and the only one, or there is no map and the answer is no.  Then ee[s'] = ee[s]^H and ee[0] + lsham Hermitian (st: the
+// stencil with l.s folded into slot 0), to 1e-12 of the largest element.
+bool check_hermitian(rsrec_t* h, const double* st) {
+    if (h->ntype != 1 || h->nmax != 0 || h->hoh) return false;
+    const int ns = h->nslots, kk = h->kk;
+    if (h->opp_epoch != h->lattice_epoch) {
+        h->opp_epoch = h->lattice_epoch;
+        std::vector<int> opp(ns, -1);
+        bool ok = true;
+        opp[0] = 0;
+        for (int i = 0; i < kk && ok; ++i)
+            for (int s = 1; s < ns && ok; ++s) {
+                const int j = h->nbr[(size_t)i * ns + s];
+                if (j < 0) continue;
+                int back = -1, nback = 0;
+                for (int q = 0; q < ns; ++q) if (h->nbr[(size_t)j * ns + q] == i) { back = q; ++nback; }
+                if (nback != 1 || back == 0 || (opp[s] >= 0 && opp[s] != back)) ok = false;
+                else opp[s] = back;
+            }
+        for (int s = 0; s < ns && ok; ++s) if (opp[s] < 0 || opp[opp[s]] != s) ok = false;
+        if (!ok) opp.clear();
+        h->opp_slot.swap(opp);
+    }
+    if (h->opp_slot.empty()) return false;
+    const size_t B = 2 * (size_t)BLK;
+    double big = 0.0;
+    for (size_t e = 0; e < B * ns; ++e) big = std::max(big, std::fabs(st[e]));
+    const double tol = 1e-12 * big;
+    for (int s = 0; s < ns; ++s) {
+        const double *a = st + B * s, *b = st + B * h->opp_slot[s];
+        for (int r = 0; r < NB; ++r)
+            for (int c = 0; c < NB; ++c) {
+                const double dr = b[2 * (c + NB * r)] - a[2 * (r + NB * c)], di = b[2 * (c + NB * r) + 1] + a[2 * (r + NB * c) + 1];
+                if (!(std::fabs(dr) <= tol && std::fabs(di) <= tol)) return false;
+            }
+    }
+    return true;
+}
+
+}  // namespace
+
 extern "C" int rsrec_set_hamiltonian(rsrec_t* h, int nslots, int hoh, int nsp, const double* ee, const double* lsham, const double* eeo,
                                      const double* enim, const double* hall, const double* hallo) {
     if (!h) return RSREC_ERR_ARG;
@@ -615,6 +672,7 @@ extern "C" int rsrec_set_hamiltonian(rsrec_t* h, int nslots, int hoh, int nsp, c
     if (!hoh)
         for (int t = 0; t < ntype; ++t)
             for (size_t e = 0; e < B; ++e) st[B * nslots * t + e] += lsham[B * t + e];
+    h->ham_hermitian = check_hermitian(h, st.data()) ? 1 : 0;
     // Arrays that rsrec_assemble_blocks produced (the caller hands back, bit for bit, what it was given) are already on the device:
     // a device-to-device copy (+ the l.s fold) replaces the upload.  Anything else -- arrays built on the host, or edited since -- is uploaded.
     h->n_asm_reused = 0;
@@ -730,13 +788,14 @@ struct BatchPlan {
 };
 
 // how many chains are advanced together, and how many workgroups each gets
-int plan_batch(rsrec_t* h, int nchains, int nvec, size_t vec_elems_per_chain, BatchPlan& bp) {
+int plan_batch(rsrec_t* h, int nchains, int nvec, size_t vec_elems_per_chain, BatchPlan& bp, size_t extra_bytes_per_chain = 0) {
     release_kubo_buffers(h, true, true);                         // (a Kubo call keeps its buffers for the next one; the recursion takes the memory back)
     size_t free_b = 0, total_b = 0;
     HIPCK(h, hipMemGetInfo(&free_b, &total_b));
     size_t reusable = 0;
     for (int v = 0; v < 5; ++v) reusable += h->d_vec[v].bytes;
-    const double per_chain = (double)nvec * vec_elems_per_chain * sizeof(double2) + (double)h->kk * 4 + 4096;
+    if (extra_bytes_per_chain) reusable += h->d_gram.bytes;        // (a call that does not fold leaves the buffer alone: it is not free memory)
+    const double per_chain = (double)nvec * vec_elems_per_chain * sizeof(double2) + (double)h->kk * 4 + 4096 + (double)extra_bytes_per_chain;
     long cap = (long)((0.85 * (double)(free_b + reusable)) / per_chain);
     if (cap < 1) return fail(h, RSREC_ERR_DEVICE, "not enough device memory for one chain (%.1f MB needed, %.1f MB free)", per_chain / 1e6, free_b / 1e6);
     long b = h->opt_batch > 0 ? h->opt_batch : 64;
@@ -936,6 +995,7 @@ int upload_regions(rsrec_t* h, const int* seeds0, int nb, int nseed, int nlev, i
     XFER(xfer_h2d(h, e->cum.p, cum.data(), cum.size() * 4));
     HIPCK(h, hipStreamSynchronize(h->stream));   // order/cum are stack-local vectors
     e->level_max.assign(nlev, 0);
+    e->hop_min.assign(nlev, INT32_MAX); e->hop_max.assign(nlev, 0);
     e->level_groups.assign((size_t)nlev * ntau_h, 0.0);
     {
         // groups by operator class: the saturated list is the same for every chain; a level-major list is walked once per chain
@@ -954,6 +1014,7 @@ int upload_regions(rsrec_t* h, const int* seeds0, int nb, int nseed, int nlev, i
             for (int l = 0; l < nlev; ++l) {
                 const int cnt = cum[(size_t)c * nlev + l];
                 e->level_max[l] = std::max(e->level_max[l], cnt);
+                e->hop_min[l] = std::min(e->hop_min[l], cnt); e->hop_max[l] = std::max(e->hop_max[l], cnt);
                 const bool sat = cum[(size_t)(nb + c) * nlev + l] == sat_off;   // (level_max: the larger of the two lists' counts sizes the launches)
                 e->level_max[l] = std::max(e->level_max[l], cum[(size_t)(2 * nb + c) * nlev + l]);
                 if (sat) e->level_sat[l] += 1;
@@ -994,6 +1055,7 @@ void reset_timing(rsrec_t* h) {
     h->t_total_ms = h->t_hop_ms = h->t_rest_ms = h->t_host_ms = h->t_rot_ms = 0;
     h->n_hop_launch = h->n_atom_steps = h->n_block_mult = h->n_hop_mfma_flop = h->n_req_flop = 0;
     h->n_octet_launch = 0;
+    h->n_gram_folded = h->n_gram_all = h->n_gram_levels = 0;
     h->ev_used = 0;
     h->n_recursion_calls++;          // (every timed entry point: recursions, Green / LDOS stages, Kubo moments)
 }
@@ -1138,6 +1200,7 @@ void s5_prepare(rsrec_t* h) {
         const int ask = (int)std::min<size_t>((size_t)optin, S5_LDS_LIMIT);
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_spmm5<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ask) == hipSuccess &&
             hipFuncSetAttribute(reinterpret_cast<const void*>(k_spmm5<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ask) == hipSuccess &&
+            hipFuncSetAttribute(reinterpret_cast<const void*>(k_spmm5<false, true, false, 1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ask) == hipSuccess &&
             hipFuncSetAttribute(reinterpret_cast<const void*>(k_spmm5<false, true, false, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, ask) == hipSuccess &&
             hipFuncSetAttribute(reinterpret_cast<const void*>(k_spmm5<true, true, false, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, ask) == hipSuccess)
             h->s5_lds_limit = (size_t)ask;
@@ -1147,7 +1210,7 @@ void s5_prepare(rsrec_t* h) {
 // one launch: the LDS / persistent form for operator class `one` (>= 0) if it is wanted and fits, else the global-load form
 template <bool TWO>
 void launch_s5_one(rsrec_t* h, dim3 grid, const SpmmDims& SD, const int* order, const int* cum, const int* iz, const Spmm5Operator& op, int set,
-                   const double* in, double* out, const double* in2, const double* extra, int ntau, S5Epilogue epi, int one) {
+                   const double* in, double* out, const double* in2, const double* extra, int ntau, S5Epilogue epi, int one, S5Gram gram = S5Gram()) {
     const size_t lds_bytes = (size_t)op.ntr * S5_TRIPLE * sizeof(double);
     // s5_lds: 0 never, 1 (default) whenever the groups of the launch are of one class and its stream fits
     const bool want = h->opt_s5_lds >= 1;
@@ -1179,8 +1242,14 @@ void launch_s5_one(rsrec_t* h, dim3 grid, const SpmmDims& SD, const int* order, 
             // the split stream requests its operands five steps ahead: up to two triples past the stream's end (never used) -- one more triple of LDS where it fits
             const size_t lds3 = std::min(lds_limit, lds_bytes + (size_t)S5_TRIPLE_BYTES);
             k_spmm5<TWO, true, false, 3><<<g2, thr3, lds3, h->stream>>>(SD, order, cum, h->d_nbr5.as<int>(), iz, op.frag_set(set), op.meta_set(set), op.ntr, in, out, in2, nullptr, ntau, one, queue, spin_by_xcd, epi);
+        } else if constexpr (!TWO) {
+            if (gram.out) k_spmm5<false, true, false, 1, true><<<g2, thr, lds_bytes, h->stream>>>(SD, order, cum, h->d_nbr5.as<int>(), iz, op.frag_set(set), op.meta_set(set), op.ntr, in, out, in2, nullptr, ntau, one, queue, spin_by_xcd, epi, gram);
+            else k_spmm5<false, true><<<g2, thr, lds_bytes, h->stream>>>(SD, order, cum, h->d_nbr5.as<int>(), iz, op.frag_set(set), op.meta_set(set), op.ntr, in, out, in2, nullptr, ntau, one, queue, spin_by_xcd, epi);
         } else
         k_spmm5<TWO, true><<<g2, thr, lds_bytes, h->stream>>>(SD, order, cum, h->d_nbr5.as<int>(), iz, op.frag_set(set), op.meta_set(set), op.ntr, in, out, in2, nullptr, ntau, one, queue, spin_by_xcd, epi);
+    } else if constexpr (!TWO) {
+        if (gram.out) k_spmm5<false, false, false, 1, true><<<grid, S5_WG_GROUPS * 128, 0, h->stream>>>(SD, order, cum, h->d_nbr5.as<int>(), iz, op.frag_set(set), op.meta_set(set), op.ntr, in, out, in2, extra, ntau, 0, nullptr, 1, epi, gram);
+        else k_spmm5<false, false><<<grid, S5_WG_GROUPS * 128, 0, h->stream>>>(SD, order, cum, h->d_nbr5.as<int>(), iz, op.frag_set(set), op.meta_set(set), op.ntr, in, out, in2, extra, ntau, 0, nullptr, 1, epi);
     } else
         k_spmm5<TWO, false><<<grid, S5_WG_GROUPS * 128, 0, h->stream>>>(SD, order, cum, h->d_nbr5.as<int>(), iz, op.frag_set(set), op.meta_set(set), op.ntr, in, out, in2, extra, ntau, 0, nullptr, 1, epi);
 }
@@ -1193,7 +1262,8 @@ void launch_s5_one(rsrec_t* h, dim3 grid, const SpmmDims& SD, const int* order, 
 // s5_lds = 2; by default they keep the global-load form, which is faster for them.  Per-chain stream heads (local-axis runs): global loads.
 template <bool TWO>
 void launch_s5(rsrec_t* h, dim3 grid, const SpmmDims& SD0, const int* order, const int* cum, const int* iz, const Spmm5Operator& op, int set,
-               const double* in, double* out, const double* in2 = nullptr, const double* extra = nullptr, int ntau = 0, S5Epilogue epi = S5Epilogue()) {
+               const double* in, double* out, const double* in2 = nullptr, const double* extra = nullptr, int ntau = 0, S5Epilogue epi = S5Epilogue(),
+               S5Gram gram = S5Gram() /*the caller established that the operator is one the Gram fold serves (gram_eligible)*/) {
     SpmmDims SD = SD0;
     const int one = op.single_class(set);
     const rsrec_handle::RegionEntry* E = h->cur_entry;
@@ -1236,7 +1306,7 @@ void launch_s5(rsrec_t* h, dim3 grid, const SpmmDims& SD0, const int* order, con
         h->n_octet_launch++;
     }
     if (!multi) {
-        launch_s5_one<TWO>(h, grid, SD, order, cum, iz, op, set, in, out, in2, extra, ntau, epi, one);
+        launch_s5_one<TWO>(h, grid, SD, order, cum, iz, op, set, in, out, in2, extra, ntau, epi, one, gram);
         if (oct_aside) (void)hipStreamWaitEvent(h->stream, h->ev_oct_out, 0);            // the level goes on when both launches are done
     } else {
         // class runs worth workgroups of their own: at least two groups per workgroup of a full persistent launch over the chains on the list
@@ -1380,13 +1450,15 @@ RecursionCall recursion_call(const rsrec_t* h, bool mfma, int nchains, int nseed
 
 // Plans the batches and reserves what every recursion needs: `nvec` work vectors (all but `skip_vec`), the partials, the seeds with `coef_slots`
 // coefficients per chain, the status word (cleared here), the side stream; opens the timed span.  The caller reserves its resident outputs BEFORE it.
-int recursion_begin(rsrec_t* h, RecursionCall& RC, int nvec, int skip_vec, int coef_slots) {
+int recursion_begin(rsrec_t* h, RecursionCall& RC, int nvec, int skip_vec, int coef_slots, size_t gram_doubles_per_chain = 0) {
     if (RC.mfma && !RC.ci) XFER(ensure_s4(h));
     RC.nvec = nvec; RC.skip_vec = skip_vec;
     BatchPlan bp;
-    XFER(plan_batch(h, RC.nchains, nvec - (skip_vec >= 0 ? 1 : 0), RC.velems / 2, bp));
+    XFER(plan_batch(h, RC.nchains, nvec - (skip_vec >= 0 ? 1 : 0), RC.velems / 2, bp, gram_doubles_per_chain * sizeof(double)));
     const int B = RC.B = bp.batch; RC.nblk = bp.nblk;
     for (int v = 0; v < nvec; ++v) if (v != skip_vec) HIPCK(h, h->d_vec[v].reserve((size_t)B * RC.velems * sizeof(double)));
+    // the folded Gram's partials go with the work vectors: reserved here, before any stream capture
+    if (gram_doubles_per_chain) HIPCK(h, h->d_gram.reserve((size_t)B * gram_doubles_per_chain * sizeof(double)));
     // first stage: two Gram partials (1296 doubles) of up to 256 workgroups per chain; the VALU set's 2 nblk <= 512 partials are as large
     XFER(reserve_partials(h, B, (size_t)B * 256 * 2 * 1296 * sizeof(double)));
     XFER(ensure_side_stream(h));
@@ -1482,7 +1554,7 @@ int clear_vectors(rsrec_t* h, const RecursionCall& RC, int nb, int zero_block_on
 // H = h - (h o) h + e_nu + l.s with src as second input (extra on-site slot) on those of level 2 step.  `extra` / `ntau`: the per-chain on-site
 // fragments of a local-axis run (the single launch is then a two-input one as well).  Else the cooperative k_spmm4 on LayoutRM (plain operator).
 int apply_h(rsrec_t* h, RecursionCall& RC, const RecursionBatch& b, int step, const double* src, double* dst, double* hps, const double* extra, int ntau,
-            S5Epilogue epi = S5Epilogue()) {
+            S5Epilogue epi = S5Epilogue(), S5Gram gram = S5Gram()) {
     const bool hoh = h->hoh != 0;
     const int lv_final = hoh ? 2 * step : step;
     const Spmm5Operator& OP = *RC.op; const DevProblem& P = RC.P; const ChainView& CV = b.CV;
@@ -1494,7 +1566,7 @@ int apply_h(rsrec_t* h, RecursionCall& RC, const RecursionBatch& b, int step, co
         SD.level = lv_final;
         launch_s5<true>(h, s5_grid(h, b.grid_mf, lv_final), SD, CV.order, CV.cum, P.iz, OP, 1, hps, dst, src, extra, ntau, epi);
     } else if (extra) launch_s5<true>(h, s5_grid(h, b.grid_mf, lv_final), SD, CV.order, CV.cum, P.iz, OP, 0, src, dst, src, extra, ntau, epi);
-    else launch_s5<false>(h, s5_grid(h, b.grid_mf, lv_final), SD, CV.order, CV.cum, P.iz, OP, 0, src, dst, nullptr, nullptr, 0, epi);
+    else launch_s5<false>(h, s5_grid(h, b.grid_mf, lv_final), SD, CV.order, CV.cum, P.iz, OP, 0, src, dst, nullptr, nullptr, 0, epi, gram);
     RC.hop_ev.emplace_back(e0, next_event(h)); h->n_hop_launch += hoh ? 2 : 1;
     return RSREC_OK;
 }
@@ -1598,7 +1670,15 @@ int run_block_lanczos(rsrec_t* h, int nchains, int nseed, const int32_t* seed_at
     const bool oop = MFMA && h->opt_orth_oop != 0 && h->opt_orth3 != 2;
     const int nvec = MFMA ? (oop && hoh ? 5 : 4) : (hoh ? 3 : 2);
     const bool use_v1 = !MFMA || hoh || oop;
-    XFER(recursion_begin(h, RC, nvec, use_v1 ? -1 : 1, nseed));
+    // The A_n Gram in k_spmm5's epilogue: block Lanczos on the matrix-core set with k_spmm5, a Hermitian operator of one class, no hoh, no
+    // per-chain stream heads, whole-group waves, and images enough for k_gram_groupsum in every launch of the post-hop passes.  A property of
+    // the operator and the options, never of the launch; which (chain, level) passes then fold is s5_gram_folds on the chain's group count.
+    const size_t gram_groups = ((size_t)kk + 7 * (size_t)(h->nmax + h->ntype) + 8 + GROUP - 1) / GROUP;      // no list is longer
+    const bool gram_eligible = MFMA && ci && !hoh && !rot && h->ntype == 1 && h->nmax == 0 && h->ham_hermitian && h->opt_s5_split != 3 &&
+                               RC.op->single_class(0) >= 0 && (h->opt_nblk <= 0 || 2 * h->opt_nblk >= S5_GRAM_MAXW) &&
+                               s5_gram_folds((long)gram_groups, h->opt_s5_gram_min);
+    const size_t gram_cstride = gram_eligible ? gram_groups * 2 * S5_GRAM_DOUBLES : 0;
+    XFER(recursion_begin(h, RC, nvec, use_v1 ? -1 : 1, nseed, gram_cstride));
     const int B = RC.B, nblk = RC.nblk;
     HIPCK(h, h->d_frags.reserve((size_t)B * 3 * 27 * 64 * sizeof(double)));
     HIPCK(h, h->d_bmats.reserve((size_t)B * 2 * BLK * sizeof(double2)));
@@ -1616,6 +1696,14 @@ int run_block_lanczos(rsrec_t* h, int nchains, int nseed, const int32_t* seed_at
         RecursionBatch bt;
         XFER(recursion_batch(h, RC, seed_atoms, seed_coef, c0, nb, bt));
         const ChainView &CV = bt.CV, &CVp = bt.CVp;
+        // what folds at a level: 0 no chain, 1 some chains (k_mfma_adot serves the others), 2 every chain (no k_mfma_adot launch)
+        const rsrec_handle::RegionEntry* RE = h->cur_entry;
+        auto fold_at = [&](int lv) -> int {
+            if (!gram_eligible || !RE || lv < 0 || lv >= (int)RE->hop_max.size()) return 0;
+            if (!s5_gram_folds(RE->hop_max[lv] / GROUP, h->opt_s5_gram_min)) return 0;
+            return s5_gram_folds(RE->hop_min[lv] / GROUP, h->opt_s5_gram_min) ? 2 : 1;
+        };
+        for (int ll = 0; ll < nsteps; ++ll) { const int f = fold_at(ll + 1); h->n_gram_folded += f > 0; h->n_gram_all += f == 2; h->n_gram_levels += 1; }
         // everything from here to the coefficients' download is stream work only: small batches replay it as a HIP graph
         auto enqueue_levels = [&]() -> int {
             XFER(clear_vectors(h, RC, nb, MFMA && !hoh ? 2 : -1));
@@ -1639,9 +1727,13 @@ int run_block_lanczos(rsrec_t* h, int nchains, int nseed, const int32_t* seed_at
                 if (MFMA) {
                     // matrix-core kernel set, un-normalised vectors (kernels_uscheme.hpp): psi = u_n, t2 = u_{n-1}; u_{n+1} overwrites u_{n-1}
                     // (with hoh, h psi of the first pass goes into the pmn buffer, free in the u-scheme)
-                    XFER(apply_h(h, RC, bt, ll + 1, psi, hpsi, pmn, bt.la_extra, ntau));
+                    const int folds = fold_at(lv_final);
+                    const GramFold GF{folds ? CV.cum : nullptr, RC.nlev, h->opt_s5_gram_min};
+                    XFER(apply_h(h, RC, bt, ll + 1, psi, hpsi, pmn, bt.la_extra, ntau, S5Epilogue(),
+                                 folds ? S5Gram{h->d_gram.as<double>(), gram_cstride, h->opt_s5_gram_min} : S5Gram()));
                     const dim3 gl = level_grid(h, bt.grid_mf, lv_final);
-                    k_mfma_adot<<<gl, MF_WAVES * 64, 0, h->stream>>>(CVp, lv_final, kk, psi, hpsi, gpartial);
+                    if (folds < 2) k_mfma_adot<<<gl, MF_WAVES * 64, 0, h->stream>>>(CVp, lv_final, kk, psi, hpsi, gpartial, GF);
+                    if (folds) k_gram_groupsum<<<gl, 640, 0, h->stream>>>(GF, lv_final, h->d_gram.as<double>(), gram_cstride, gpartial);
                     int n2 = gl.x; const double* p2 = presum(h, gpartial, nb, n2, 1296);
                     XFER(side_reduce_wait(h, SR));
                     k_reduce_a_u<<<nb, 1024, 0, h->stream>>>(p2, n2, dA + (size_t)ll * BLK, cstride, h->d_bmats.as<double2>(), bfrags, ci);
@@ -1689,7 +1781,7 @@ int run_block_lanczos(rsrec_t* h, int nchains, int nseed, const int32_t* seed_at
                                           (uintptr_t)h->d_status.p, (uintptr_t)h->d_seed.p, (uintptr_t)h->d_seedcoef.p, (uintptr_t)h->d_la_extra.p, (uintptr_t)h->d_s5queue.p,
                                           (uintptr_t)h->cur_entry, (uintptr_t)h->p2_slot, (uintptr_t)OP.single_class(0), (uintptr_t)OP.spin_mixing,
                                           (uintptr_t)h->lattice_epoch, (uintptr_t)OP.sched_epoch, (uintptr_t)h->nslots, (uintptr_t)h->nmax, (uintptr_t)h->ntype, (uintptr_t)h->hslots,
-                                          (uintptr_t)B, (uintptr_t)h->n_cu};
+                                          (uintptr_t)B, (uintptr_t)h->n_cu, (uintptr_t)h->d_gram.p, (uintptr_t)gram_eligible};
             for (int v = 0; v < nvec; ++v) key.push_back((uintptr_t)h->d_vec[v].p);
             // ... and every option: launch shapes and kernel choices follow them (all but `graph`, which only decides whether this path is taken)
             for (const OptionEntry& o : OPTIONS)
@@ -1702,6 +1794,7 @@ int run_block_lanczos(rsrec_t* h, int nchains, int nseed, const int32_t* seed_at
         XFER(xfer_d2h(h, b2_b + (size_t)c0 * cstride * 2, dB, (size_t)nb * cstride * sizeof(double2)));
         HIPCK(h, hipStreamSynchronize(h->stream));
     }
+    if (MFMA && h->n_gram_levels > 0 && h->n_gram_all == h->n_gram_levels) h->hop_fuses_a = 1;   // every H|psi> launch also formed the A_n Gram
     return recursion_end(h, RC, 1, lld, seed_coef != nullptr);
 }
 

@@ -16,7 +16,7 @@ by = {}
 for r in rows:
     k = r["Kernel_Name"].split("(")[0].replace("void ", "").replace("rsrec::", "").split("<")[0]
     by.setdefault(k, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) * 1e-6)
-for k in ("k_spmm5", "k_mfma_adot", "k_mfma_orth3"):
+for k in ("k_spmm5", "k_mfma_adot", "k_gram_groupsum", "k_mfma_orth3"):
     if k in by:
         print(k, " ".join("%.2f" % v for v in by[k]))
 PY
