@@ -13,6 +13,10 @@
 !                                   element simpson_f reads past its arrays as zero (include/rsrec.h).
 !                                   RSREC_HOST_COND_TAIL set in the environment: the tail restated line for line on the host instead, with
 !                                   simpson_f of math_mod as it is, the stray read included (region conductivity-tensor-host).
+!                                   RSREC_KUBO_RESPONSES (recursion_gpu): the recursion formed the moments of further responses to the
+!                                   same field; the integrand of all of them is one call, and the tail runs once per response -- the
+!                                   namelist's response writes the files above, further response <op> the same files as <op>_fort.123,
+!                                   <op>_cond_total*.out, <op>_<symbol>_cond*.out.
 ! Errors of the library become g_logger%fatal, the reference's error behaviour on this path.
 !------------------------------------------------------------------------------
 module conductivity_gpu_mod
@@ -26,7 +30,7 @@ module conductivity_gpu_mod
    use timer_mod, only: g_timer
    use rsrec_binding
    use rsrec_context_mod, only: rsrec_gpu_context, rsrec_env_flag
-   use recursion_gpu_mod, only: rsrec_gpu_kubo_diag_resident
+   use recursion_gpu_mod, only: rsrec_gpu_kubo_diag_resident, rsrec_gpu_kubo_responses, rsrec_gpu_kubo_response_name, rsrec_gpu_kubo_response_diag
    implicit none
 
    private
@@ -66,10 +70,12 @@ contains
 
    subroutine gpu_calculate_conductivity_tensor(this)
       class(conductivity_gpu), intent(inout) :: this
-      integer :: loop_over, nen
+      integer :: loop_over, nen, nresp, j
       integer(c_int) :: rc
       type(c_ptr) :: ctx
-      complex(rp), dimension(:, :, :), allocatable, target :: integ           ! (18, nen, loop_over): integrand_at(l2, l2, :, v), factor applied
+      complex(rp), dimension(:, :, :), allocatable, target :: integ           ! (18, nen, loop_over): integrand_at(l2, l2, :, v), factor applied;
+                                                                              ! further responses: loop_over more vectors each
+      character(len=sl) :: prefix
       real(rp), dimension(:), allocatable :: wscale
       real(rp), dimension(:), allocatable, target :: ene
       real(rp) :: a, b, factor, volume, de
@@ -103,14 +109,15 @@ contains
       write (*, *) factor, volume, de
 
       ! :268-281 (and calculate_gamma_nm :158-225): integrand_at(l2, l2, i, ntype) for every vector, on the device
-      allocate (integ(18, nen, loop_over))
+      nresp = rsrec_gpu_kubo_responses()
+      allocate (integ(18, nen, loop_over*(1 + nresp)))
       ctx = rsrec_gpu_context()
       rc = 1
-      if (rsrec_gpu_kubo_diag_resident(this%control%cond_ll) == loop_over) then
+      if (rsrec_gpu_kubo_diag_resident(this%control%cond_ll) == loop_over*(1 + nresp)) then
          ! the recursion (RSREC_KUBO_DIAG) left the orbital-diagonal moments of these vectors on the device: nothing is uploaded.  If the
          ! library did not keep them (they did not fit beside the call's buffers) it says so, and the host array is used as always.
          call g_timer%start('conductivity-integrand-gpu-resident')
-         rc = rsrec_kubo_integrand_diag(ctx, int(loop_over, c_int), int(this%control%cond_ll, c_int), c_null_ptr, int(nen, c_int), &
+         rc = rsrec_kubo_integrand_diag(ctx, int(loop_over*(1 + nresp), c_int), int(this%control%cond_ll, c_int), c_null_ptr, int(nen, c_int), &
                                         c_loc(ene), real(this%en%energy_min, c_double), real(this%en%energy_max, c_double), c_loc(integ))
          call g_timer%stop('conductivity-integrand-gpu-resident')
       end if
@@ -119,36 +126,48 @@ contains
          rc = rsrec_kubo_integrand(ctx, int(loop_over, c_int), int(this%control%cond_ll, c_int), c_loc(this%recursion%mu_nm_stochastic), &
                                    int(nen, c_int), c_loc(ene), real(this%en%energy_min, c_double), real(this%en%energy_max, c_double), &
                                    c_loc(integ))
+         do j = 1, nresp                                         ! (the further responses: their diagonals as the recursion kept them)
+            if (rc /= 0) exit
+            rc = rsrec_kubo_integrand_diag(ctx, int(loop_over, c_int), int(this%control%cond_ll, c_int), rsrec_gpu_kubo_response_diag(j), &
+                                           int(nen, c_int), c_loc(ene), real(this%en%energy_min, c_double), real(this%en%energy_max, c_double), &
+                                           c_loc(integ(1, 1, j*loop_over + 1)))
+         end do
       end if
       if (rc /= 0) call g_logger%fatal('conductivity_gpu%calculate_conductivity_tensor: '//rsrec_error_string(ctx), __FILE__, __LINE__)
       call g_timer%stop('conductivity-integrand-gpu')
 
-      ! :283-372
-      if (rsrec_env_flag('RSREC_HOST_COND_TAIL')) then
-         call g_timer%start('conductivity-tensor-host')
-         call host_tail(this, integ, wscale, a, b, loop_over, nen)
-         call g_timer%stop('conductivity-tensor-host')
-      else
-         call g_timer%start('conductivity-tensor-gpu')
-         call device_tail(this, ctx, integ, ene, wscale, a, b, loop_over, nen)
-         call g_timer%stop('conductivity-tensor-gpu')
-      end if
+      ! :283-372, once per response: the namelist's first, under the reference's file names
+      do j = 0, nresp
+         prefix = ''
+         if (j > 0) prefix = trim(rsrec_gpu_kubo_response_name(j))//'_'
+         if (rsrec_env_flag('RSREC_HOST_COND_TAIL')) then
+            call g_timer%start('conductivity-tensor-host')
+            call host_tail(this, integ(:, :, j*loop_over + 1:(j + 1)*loop_over), wscale, a, b, loop_over, nen, trim(prefix))
+            call g_timer%stop('conductivity-tensor-host')
+         else
+            call g_timer%start('conductivity-tensor-gpu')
+            call device_tail(this, ctx, integ(:, :, j*loop_over + 1:(j + 1)*loop_over), ene, wscale, a, b, loop_over, nen, trim(prefix))
+            call g_timer%stop('conductivity-tensor-gpu')
+         end if
+      end do
 
       deallocate (integ, wscale, ene)
    end subroutine gpu_calculate_conductivity_tensor
 
    !> The tail on the device: series and sigma (38, nen, nsets) from one rsrec_kubo_conductivity call -- rows 1-2 Re / Im of the total,
    !> 3-20 / 21-38 Re / Im of the orbitals; set 1 the sum over the vectors, set 1 + ntype that type alone ('per_type') -- then the
-   !> reference's files, formats, divisions and unit numbers (:293-367).
-   subroutine device_tail(this, ctx, integ, ene, wscale, a, b, loop_over, nen)
+   !> reference's files, formats, divisions and unit numbers (:293-367).  `prefix` goes before every file name (a further response's
+   !> '<op>_'; empty: the reference's names, fort.123 the unit's own file).
+   subroutine device_tail(this, ctx, integ, ene, wscale, a, b, loop_over, nen, prefix)
       class(conductivity_gpu), intent(inout) :: this
       type(c_ptr), intent(in) :: ctx
-      complex(rp), dimension(:, :, :), intent(in), target :: integ
+      complex(rp), dimension(:, :, :), intent(in), target, contiguous :: integ
+      character(len=*), intent(in) :: prefix
       real(rp), dimension(:), intent(in), target :: ene
       real(rp), dimension(:), intent(in) :: wscale
       real(rp), intent(in) :: a, b
       integer, intent(in) :: loop_over, nen
-      integer :: i, ntype, nsets, per_vector
+      integer :: i, ntype, nsets, per_vector, u123
       integer(c_int) :: rc
       real(rp), dimension(:, :, :), allocatable, target :: sigma, series
       character(len=*), parameter :: fname_cond_total = "cond_total.out"
@@ -166,22 +185,28 @@ contains
       if (rc /= 0) call g_logger%fatal('conductivity_gpu%calculate_conductivity_tensor: '//rsrec_error_string(ctx), __FILE__, __LINE__)
 
       ! :293-313
-      open (unit=3, file=fname_cond_total, status='replace', action='write')
-      open (unit=32, file=fname_cond_orb_real, status='replace', action='write')
-      open (unit=33, file=fname_cond_orb_im, status='replace', action='write')
+      open (unit=3, file=prefix//fname_cond_total, status='replace', action='write')
+      open (unit=32, file=prefix//fname_cond_orb_real, status='replace', action='write')
+      open (unit=33, file=prefix//fname_cond_orb_im, status='replace', action='write')
+      u123 = 123                                               ! (the reference writes the unit unopened: fort.123)
+      if (len(prefix) > 0) then
+         u123 = 1123
+         open (unit=u123, file=prefix//'fort.123', status='replace', action='write')
+      end if
       do i = 1, nen
-         write (123, '(3es16.6)') (a*wscale(i) + b) - this%en%fermi, series(1, i, 1), series(2, i, 1)
+         write (u123, '(3es16.6)') (a*wscale(i) + b) - this%en%fermi, series(1, i, 1), series(2, i, 1)
          write (3, '(3es16.6)') (a*wscale(i) + b) - this%en%fermi, sigma(1, i, 1)/real(loop_over), sigma(2, i, 1)/real(loop_over)
          write (32, '(19es16.6)') (a*wscale(i) + b) - this%en%fermi, sigma(3:20, i, 1)/real(loop_over)
          write (33, '(19es16.6)') (a*wscale(i) + b) - this%en%fermi, sigma(21:38, i, 1)/real(loop_over)
       end do
+      if (u123 /= 123) close (u123)
 
       ! :316-367
       if (per_vector == 1) then
          do ntype = 1, loop_over
-            fname_r = trim(this%lattice%symbolic_atoms(ntype)%element%symbol)//"_cond.out"
-            fname_orb_r = trim(this%lattice%symbolic_atoms(ntype)%element%symbol)//"_cond_orb_real.out"
-            fname_orb_i = trim(this%lattice%symbolic_atoms(ntype)%element%symbol)//"_cond_orb_im.out"
+            fname_r = prefix//trim(this%lattice%symbolic_atoms(ntype)%element%symbol)//"_cond.out"
+            fname_orb_r = prefix//trim(this%lattice%symbolic_atoms(ntype)%element%symbol)//"_cond_orb_real.out"
+            fname_orb_i = prefix//trim(this%lattice%symbolic_atoms(ntype)%element%symbol)//"_cond_orb_im.out"
 
             open (unit=100 + ntype, file=fname_r, status='replace', action='write')
             open (unit=300 + ntype, file=fname_orb_r, status='replace', action='write')
@@ -201,13 +226,14 @@ contains
 
    !> The tail on the host (RSREC_HOST_COND_TAIL): the reference's lines (:283-372) restated, simpson_f of math_mod kept as it is -- its
    !> loop reads Y(nv1 + 10) and Ene(nv1 + 10), one element past both arrays.
-   subroutine host_tail(this, integ, wscale, a, b, loop_over, nen)
+   subroutine host_tail(this, integ, wscale, a, b, loop_over, nen, prefix)
       class(conductivity_gpu), intent(inout) :: this
       complex(rp), dimension(:, :, :), intent(in) :: integ
+      character(len=*), intent(in) :: prefix
       real(rp), dimension(:), intent(in) :: wscale
       real(rp), intent(in) :: a, b
       integer, intent(in) :: loop_over, nen
-      integer :: i, l2, ntype
+      integer :: i, l2, ntype, u123
       real(rp), dimension(:, :), allocatable :: integrand_l_im, integrand_l_real
       real(rp), dimension(:), allocatable :: integrand_tot_real, integrand_tot_im, real_part_l, im_part_l
       real(rp) :: real_part, im_part
@@ -234,12 +260,17 @@ contains
       end do
 
       ! :293-313
-      open (unit=3, file=fname_cond_total, status='replace', action='write')
-      open (unit=32, file=fname_cond_orb_real, status='replace', action='write')
-      open (unit=33, file=fname_cond_orb_im, status='replace', action='write')
+      open (unit=3, file=prefix//fname_cond_total, status='replace', action='write')
+      open (unit=32, file=prefix//fname_cond_orb_real, status='replace', action='write')
+      open (unit=33, file=prefix//fname_cond_orb_im, status='replace', action='write')
+      u123 = 123                                               ! (the reference writes the unit unopened: fort.123)
+      if (len(prefix) > 0) then
+         u123 = 1123
+         open (unit=u123, file=prefix//'fort.123', status='replace', action='write')
+      end if
       do i = 1, nen
          real_part = 0.0d0; im_part = 0.0d0; real_part_l(:) = 0.0d0; im_part_l(:) = 0.0d0
-         write (123, '(3es16.6)') (a*wscale(i) + b) - this%en%fermi, integrand_tot_real(i), integrand_tot_im(i)
+         write (u123, '(3es16.6)') (a*wscale(i) + b) - this%en%fermi, integrand_tot_real(i), integrand_tot_im(i)
          call simpson_f(real_part, wscale, wscale(i), this%en%nv1, integrand_tot_real(:), .true., .false., 0.0d0)
          call simpson_f(im_part, wscale, wscale(i), this%en%nv1, integrand_tot_im(:), .true., .false., 0.0d0)
          write (3, '(3es16.6)') (a*wscale(i) + b) - this%en%fermi, real_part/real(loop_over), im_part/real(loop_over)
@@ -250,6 +281,7 @@ contains
          write (32, '(19es16.6)') (a*wscale(i) + b) - this%en%fermi, real_part_l(1:18)/real(loop_over)
          write (33, '(19es16.6)') (a*wscale(i) + b) - this%en%fermi, im_part_l(1:18)/real(loop_over)
       end do
+      if (u123 /= 123) close (u123)
 
       ! :316-367
       if (this%control%cond_calctype == 'per_type') then
@@ -263,9 +295,9 @@ contains
                integrand_tot_im(:) = integrand_tot_im(:) + integrand_l_im(l2, :)
             end do
 
-            fname_r = trim(this%lattice%symbolic_atoms(ntype)%element%symbol)//"_cond.out"
-            fname_orb_r = trim(this%lattice%symbolic_atoms(ntype)%element%symbol)//"_cond_orb_real.out"
-            fname_orb_i = trim(this%lattice%symbolic_atoms(ntype)%element%symbol)//"_cond_orb_im.out"
+            fname_r = prefix//trim(this%lattice%symbolic_atoms(ntype)%element%symbol)//"_cond.out"
+            fname_orb_r = prefix//trim(this%lattice%symbolic_atoms(ntype)%element%symbol)//"_cond_orb_real.out"
+            fname_orb_i = prefix//trim(this%lattice%symbolic_atoms(ntype)%element%symbol)//"_cond_orb_im.out"
 
             open (unit=100 + ntype, file=fname_r, status='replace', action='write')
             open (unit=300 + ntype, file=fname_orb_r, status='replace', action='write')

@@ -45,6 +45,12 @@ module recursion_gpu_mod
       !> leaves the other elements of the array zero: conductivity.f90:289 and :292 are the only reads of the array, both on the diagonal.
       !> The moments also stay on the device for conductivity_gpu.  Off unless RSREC_KUBO_DIAG is set.
       logical :: kubo_diag = .false.
+      !> RSREC_KUBO_RESPONSES: further responses to the same applied field, 'op' or 'op:pol' separated by commas (op: a name
+      !> set_kubo_operator_slot accepts; pol: the polarisation, the namelist's pol_alpha if left out), e.g. 'charge,orbital:z'.
+      !> compute_moments_stochastic then forms the diagonal moments of linear_out AND of these in one rsrec_kubo_moments_diag_multi call
+      !> (the left vectors and the right recurrence are shared), and conductivity_gpu writes each further response's files with the
+      !> prefix '<op>_'.  Implies kubo_diag.  Empty (the default): a run is what it was.
+      character(len=256) :: kubo_responses = ''
    contains
       procedure :: recur => gpu_recur
       procedure :: recur_b => gpu_recur_b
@@ -66,6 +72,7 @@ module recursion_gpu_mod
    end interface recursion_gpu
 
    public :: rsrec_gpu_shutdown, rsrec_gpu_context, rsrec_gpu_block_resident, rsrec_gpu_cheb_resident, rsrec_gpu_kubo_diag_resident
+   public :: rsrec_gpu_kubo_responses, rsrec_gpu_kubo_response_name, rsrec_gpu_kubo_response_diag
 
    !> (the per-process device context g_handle lives in rsrec_context_mod; re-exported above for the hosts that used it from here)
    !> number of sites whose block coefficients the last driver call left on the device (0: none -- another driver ran since, or the
@@ -75,6 +82,12 @@ module recursion_gpu_mod
    integer, save :: g_cheb_resident = 0
    !> vectors and cond_ll of the orbital-diagonal Kubo moments compute_moments_stochastic left on the device (kubo_diag; 0: none)
    integer, save :: g_kubo_diag_nvec = 0, g_kubo_diag_ll = 0
+   !> the further responses (kubo_responses) of the last compute_moments_stochastic: how many, their operator names, and their diagonal
+   !> moments (18, cond_ll, cond_ll, vectors, response) on the host, for the case that the library kept nothing resident
+   integer, parameter :: kubo_nout_max = 8                     ! RSREC_KUBO_NOUT_MAX (include/rsrec.h)
+   integer, save :: g_kubo_nresp = 0
+   character(len=32), save :: g_kubo_resp_op(kubo_nout_max - 1) = ''
+   complex(rp), allocatable, save, target :: g_kubo_resp_diag(:, :, :, :, :)
 
 contains
 
@@ -83,6 +96,7 @@ contains
       type(recursion_gpu) :: obj
       class(hamiltonian), target, intent(in) :: hamiltonian_obj     ! (class: a type(hamiltonian_gpu) is accepted as well)
       type(energy), target, intent(in) :: energy_obj
+      integer :: n, stat
 
       obj%hamiltonian => hamiltonian_obj
       obj%lattice => hamiltonian_obj%charge%lattice
@@ -91,6 +105,9 @@ contains
       call obj%restore_to_default()
       if (rsrec_env_flag('RSREC_LOCAL_AXIS_DEVICE')) obj%local_axis_device = .true.   ! (hosts that cannot reach the member: fortran/shadow/)
       if (rsrec_env_flag('RSREC_KUBO_DIAG')) obj%kubo_diag = .true.
+      call get_environment_variable('RSREC_KUBO_RESPONSES', obj%kubo_responses, n, stat)
+      if (stat > 0 .or. n == 0) obj%kubo_responses = ''
+      if (stat == -1) call g_logger%fatal('recursion_gpu: RSREC_KUBO_RESPONSES is longer than 256 characters', __FILE__, __LINE__)
    end function gpu_constructor
 
    !> Sites of this rank whose a_b / b2_b (as recur_b produced them) are also resident on the device; 0 if they are not.
@@ -106,6 +123,26 @@ contains
       integer :: n
       n = merge(g_kubo_diag_nvec, 0, cond_ll == g_kubo_diag_ll)
    end function rsrec_gpu_kubo_diag_resident
+
+   !> Further responses (RSREC_KUBO_RESPONSES) whose moments the last compute_moments_stochastic formed beside linear_out's; 0: none
+   function rsrec_gpu_kubo_responses() result(n)
+      integer :: n
+      n = g_kubo_nresp
+   end function rsrec_gpu_kubo_responses
+
+   !> operator name of further response j = 1 .. rsrec_gpu_kubo_responses(): the prefix of its output files
+   function rsrec_gpu_kubo_response_name(j) result(name)
+      integer, intent(in) :: j
+      character(len=32) :: name
+      name = g_kubo_resp_op(j)
+   end function rsrec_gpu_kubo_response_name
+
+   !> its diagonal moments (18, cond_ll, cond_ll, vectors) on the host, as rsrec_kubo_integrand_diag takes them
+   function rsrec_gpu_kubo_response_diag(j) result(p)
+      integer, intent(in) :: j
+      type(c_ptr) :: p
+      p = c_loc(g_kubo_resp_diag(1, 1, 1, 1, j))
+   end function rsrec_gpu_kubo_response_diag
 
    !> Sites of this rank whose mu_n (as chebyshev_recur produced them) are also resident on the device; 0 if they are not.
    function rsrec_gpu_cheb_resident() result(n)
@@ -483,11 +520,14 @@ contains
    subroutine gpu_compute_moments_stochastic(this)
       use math_mod, only: pi, i_unit
       class(recursion_gpu), intent(inout) :: this
-      integer :: i, k, l, loop_over, nseed, cll
+      integer :: i, j, k, l, loop_over, nseed, cll, nresp
       integer(c_int) :: rc
       real(rp) :: a, b, rng
       integer(c_int), allocatable, target :: seeds(:, :)
       complex(rp), allocatable, target :: mu_diag(:, :, :, :)
+      complex(rp), allocatable, target :: vout(:, :, :, :, :), voout(:, :, :, :, :), mu_multi(:, :, :, :, :)
+      character(len=32) :: resp_op(kubo_nout_max - 1)
+      character(len=10) :: resp_pol(kubo_nout_max - 1), pol_alpha
       complex(rp), allocatable, target :: coef(:, :), mu(:, :, :, :, :), va(:, :, :, :), vb(:, :, :, :), voa(:, :, :, :), vob(:, :, :, :)
       type(c_ptr) :: p_voa, p_vob
 
@@ -507,6 +547,23 @@ contains
       allocate (this%mu_nm_stochastic(18, 18, cll, cll, loop_over))
       a = (this%en%energy_max - this%en%energy_min)/(2 - 0.3)      ! :1023-1024
       b = (this%en%energy_max + this%en%energy_min)/2
+      ! the further responses first: each is the reference's own set-up with its operator and polarisation in the output slot; the
+      ! namelist's response comes last, so that the Hamiltonian object ends as in a plain run
+      g_kubo_nresp = 0
+      call parse_kubo_responses(this%kubo_responses, this%hamiltonian%pol_alpha, nresp, resp_op, resp_pol)
+      pol_alpha = this%hamiltonian%pol_alpha
+      do j = 1, nresp
+         this%hamiltonian%pol_alpha = resp_pol(j)
+         call this%setup_kubo_operators(trim(resp_op(j)), this%control%linear_in)
+         if (j == 1) then
+            allocate (vout(size(this%hamiltonian%v_a, 1), size(this%hamiltonian%v_a, 2), size(this%hamiltonian%v_a, 3), &
+                           size(this%hamiltonian%v_a, 4), nresp + 1))
+            if (this%hamiltonian%hoh) allocate (voout, mold=vout)
+         end if
+         vout(:, :, :, :, 1 + j) = this%hamiltonian%v_a
+         if (this%hamiltonian%hoh) voout(:, :, :, :, 1 + j) = this%hamiltonian%vo_a
+      end do
+      this%hamiltonian%pol_alpha = pol_alpha
       call this%setup_kubo_operators(this%control%linear_out, this%control%linear_in)
       allocate (seeds(nseed, loop_over), coef(nseed, loop_over))
       do i = 1, loop_over
@@ -533,6 +590,34 @@ contains
          p_vob = c_loc(vob)
       end if
       g_kubo_diag_nvec = 0
+      if (nresp > 0) then
+         ! the diagonal moments of 1 + nresp responses in one call: set 1 (linear_out) is stored as under kubo_diag, the others are kept for
+         ! conductivity_gpu in case the library keeps nothing resident
+         vout(:, :, :, :, 1) = va
+         p_voa = c_null_ptr
+         if (this%hamiltonian%hoh) then
+            voout(:, :, :, :, 1) = voa
+            p_voa = c_loc(voout)
+         end if
+         allocate (mu_multi(18, cll, cll, loop_over, 1 + nresp))
+         call g_timer%start('kubo-multi-gpu')
+         rc = rsrec_kubo_moments_diag_multi(g_handle, int(1 + nresp, c_int), int(loop_over, c_int), int(nseed, c_int), c_loc(seeds), c_loc(coef), &
+                                            int(cll, c_int), real(a, c_double), real(b, c_double), c_loc(vout), p_voa, c_loc(vb), p_vob, &
+                                            c_loc(mu_multi))
+         call g_timer%stop('kubo-multi-gpu')
+         call check(rc, 'rsrec_kubo_moments_diag_multi')
+         this%mu_nm_stochastic = (0.0_rp, 0.0_rp)
+         do l = 1, 18
+            this%mu_nm_stochastic(l, l, :, :, :) = mu_multi(l, :, :, :, 1)
+         end do
+         if (allocated(g_kubo_resp_diag)) deallocate (g_kubo_resp_diag)
+         allocate (g_kubo_resp_diag, source=mu_multi(:, :, :, :, 2:))
+         g_kubo_nresp = nresp
+         g_kubo_resp_op(1:nresp) = resp_op(1:nresp)
+         g_kubo_diag_nvec = loop_over*(1 + nresp)
+         g_kubo_diag_ll = cll
+         return
+      end if
       if (this%kubo_diag) then
          ! only the diagonals are formed, downloaded and stored; every other element of mu_nm_stochastic stays zero (nothing reads them:
          ! conductivity.f90:289, :292).  The library keeps the diagonals for conductivity_gpu%calculate_conductivity_tensor.
@@ -554,6 +639,43 @@ contains
       call check(rc, 'rsrec_kubo_moments')
       this%mu_nm_stochastic = mu
    end subroutine gpu_compute_moments_stochastic
+
+   !> RSREC_KUBO_RESPONSES taken apart: 'op' or 'op:pol' separated by commas -> operator names and polarisations (default_pol where none
+   !> is given).  An operator may be named once: its name is the prefix of the response's files.
+   subroutine parse_kubo_responses(list, default_pol, n, op, pol)
+      character(len=*), intent(in) :: list, default_pol
+      integer, intent(out) :: n
+      character(len=32), intent(out) :: op(:)
+      character(len=10), intent(out) :: pol(:)
+      integer :: p0, p1, c
+      character(len=len(list)) :: item
+
+      n = 0
+      p0 = 1
+      do while (p0 <= len_trim(list))
+         p1 = index(list(p0:), ',')
+         if (p1 == 0) then
+            p1 = len_trim(list) + 1
+         else
+            p1 = p0 + p1 - 1
+         end if
+         item = adjustl(list(p0:p1 - 1))
+         p0 = p1 + 1
+         if (len_trim(item) == 0) cycle
+         if (n == size(op)) call g_logger%fatal('RSREC_KUBO_RESPONSES: more than '//int2str(size(op))//' further responses', __FILE__, __LINE__)
+         n = n + 1
+         c = index(item, ':')
+         if (c == 0) then
+            op(n) = trim(item)
+            pol(n) = default_pol
+         else
+            op(n) = trim(item(:c - 1))
+            pol(n) = trim(adjustl(item(c + 1:)))
+         end if
+         if (len_trim(op(n)) == 0 .or. len_trim(pol(n)) == 0) call g_logger%fatal('RSREC_KUBO_RESPONSES: empty operator or polarisation in "'//trim(item)//'"', __FILE__, __LINE__)
+         if (any(op(1:n - 1) == op(n))) call g_logger%fatal('RSREC_KUBO_RESPONSES: operator "'//trim(op(n))//'" is named twice', __FILE__, __LINE__)
+      end do
+   end subroutine parse_kubo_responses
 
    !---------------------------------------------------------------------------
    !> Orbital moment from position-operator Chebyshev moments (replaces recursion.f90:2834-3049).  The reference loops over all kk

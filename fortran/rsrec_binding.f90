@@ -312,6 +312,18 @@ module rsrec_binding
          integer(c_int) :: rc
       end function
 
+      ! the same for nout output operators v_out / vo_out (18,18,nslots,ntype,nout) on one input operator: mu_diag
+      ! (18,cond_ll,cond_ll,nvec,nout), set j = rsrec_kubo_moments_diag with v_a = v_out(:,:,:,:,j); resident as nvec*nout vectors
+      function rsrec_kubo_moments_diag_multi(handle, nout, nvec, nseed, seed_atoms, seed_coef, cond_ll, a, b, v_out, vo_out, v_b, vo_b, mu_diag) &
+         bind(C, name='rsrec_kubo_moments_diag_multi') result(rc)
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: handle
+         integer(c_int), value :: nout, nvec, nseed, cond_ll
+         real(c_double), value :: a, b
+         type(c_ptr), value :: seed_atoms, seed_coef, v_out, vo_out, v_b, vo_b, mu_diag
+         integer(c_int) :: rc
+      end function
+
       function rsrec_apply_operator(handle, vel, v_op, vo_op, psi_in, psi_out, a, b) bind(C, name='rsrec_apply_operator') result(rc)
          import :: c_int, c_ptr, c_double
          type(c_ptr), value :: handle

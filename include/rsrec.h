@@ -266,6 +266,26 @@ int rsrec_kubo_moments(rsrec_t *h, int nvec, int nseed, const int32_t *seed_atom
 int rsrec_kubo_moments_diag(rsrec_t *h, int nvec, int nseed, const int32_t *seed_atoms, const double *seed_coef, int cond_ll, double a, double b,
                             const double *v_a, const double *vo_a, const double *v_b, const double *vo_b, double *mu_diag);
 
+/* The diagonal moments of several responses to one applied field (the reference's sigma_xy, sigma_xy_z-spin and sigma_xy_z-orb examples
+ * are three runs that differ in linear_out alone): set j is what rsrec_kubo_moments_diag returns for v_a = v_out(:,:,:,:,j),
+ * vo_a = vo_out(:,:,:,:,j) with the same other arguments, bit for bit.  The left vectors T_{m-1}(H~) r and the right recurrence
+ * T_{n-1}(H~) v_b r do not depend on the output operator and are formed once: (2 + nout) cond_ll whole-lattice products instead of
+ * 3 nout cond_ll, and with hoh the h_bulk pass of every V product is shared too ((5 + 2 nout) cond_ll - 1 launches instead of
+ * nout (7 cond_ll - 1)).  With random vectors all responses are evaluated on the same vectors.
+ *   nout    : 1 .. RSREC_KUBO_NOUT_MAX
+ *   v_out, vo_out : complex (18,18,nslots,ntype,nout); vo_out: hoh only, else NULL
+ *   mu_diag : complex (18,cond_ll,cond_ll,nvec,nout) out, host or device (detected) or NULL.  The set index is outermost: a set's slice is
+ *             what rsrec_kubo_integrand_diag and rsrec_kubo_conductivity take.
+ * The moments of all nvec * nout (vector, set) pairs stay on the handle in that layout when they fit (the rules of
+ * rsrec_kubo_moments_diag): rsrec_kubo_integrand_diag(h, nvec * nout, cond_ll, NULL, ...) then returns the integrand (18,nen,nvec,nout).
+ * Errors: RSREC_ERR_ARG with a message for nout out of range, a NULL v_out or v_b, hoh without vo_out or vo_b, and the argument errors of
+ * rsrec_kubo_moments_diag; the handle stays usable.  Run-to-run bit-identical; a set's bits depend neither on kubo_vbatch nor on the other
+ * sets of the call or their order.  rsrec_get_timing as rsrec_kubo_moments_diag. */
+#define RSREC_KUBO_NOUT_MAX 8
+int rsrec_kubo_moments_diag_multi(rsrec_t *h, int nout, int nvec, int nseed, const int32_t *seed_atoms, const double *seed_coef,
+                                  int cond_ll, double a, double b, const double *v_out, const double *vo_out, const double *v_b,
+                                  const double *vo_b, double *mu_diag);
+
 /* The Kubo-Bastin conductivity integrand of calculate_gamma_nm + calculate_conductivity_tensor (conductivity.f90:158-268), without the
  * (nen, cond_ll, cond_ll) array gamma_nm (the sum factorises into two tables of nen x cond_ll, kernels_cond.hpp):
  *   integrand(l, i, v) = factor sum_{n,m} gamma_nm(i, n, m) mu_nm(l, l, n, m, v),   factor = 16 / (pi (energy_max - energy_min)^2)

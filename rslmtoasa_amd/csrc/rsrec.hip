@@ -117,7 +117,7 @@ struct rsrec_handle {
     long n_asm_calls = 0, n_ldos_calls = 0, n_recursion_calls = 0;   // life-time counters of the handle (RSREC_REPORT)
     Spmm5Operator s5_la; int s5_la_ok = 0;   // operator tables of local-axis runs: H without the on-site l.s term, which comes per chain
     DevBuf d_la_extra, d_rot;               // per-chain on-site fragments; the rotations of all chains of the call (k_rotate_coef)
-    Spmm5Operator kubo_op[2], kubo_hbulk;   // v_a / v_b tables of the last rsrec_kubo_moments call
+    Spmm5Operator kubo_op[RSREC_KUBO_NOUT_MAX], kubo_op_b, kubo_hbulk;   // output operators (v_a: [0]) / v_b tables of the last rsrec_kubo_moments call
     Spmm5Operator orb_plain;                // h as ham_vec_matmul applies it when hoh is set (rsrec_orbital_moments, rsrec_apply_operator vel = 2)
     // work
     DevBuf d_green_in, d_green_out;   // inputs and outputs of the calls on caller arrays: the Green stages (green_pipeline), rsrec_terminator,
@@ -146,7 +146,7 @@ struct rsrec_handle {
     long opt_kubo_lchunk = 0;    // rsrec_kubo_moments: left vectors held at a time (0: as many as fit)
     long opt_kubo_vbatch = 0;    // rsrec_kubo_moments: random vectors advanced together as the chains of one launch (0: up to 8, as many as fit beside a whole left matrix)
     int n_kubo_left_chunks = 0;
-    int kubo_diag_nvec = 0, kubo_diag_ll = 0;   // rsrec_kubo_moments_diag: the call whose diagonal moments lie in d_kubo[4] (0: nothing resident)
+    int kubo_diag_nvec = 0, kubo_diag_ll = 0;   // rsrec_kubo_moments_diag / _multi: the call whose diagonal moments lie in d_kubo[4] (0: nothing resident; _multi: nvec * nout)
     long opt_orth3 = 1;          // k_mfma_orth3: 1 one 512-register wave per SIMD (tables in registers), 2 two waves per SIMD (tables in LDS)
     long opt_graph = 1;          // level loop of small batches as one HIP graph: 0 never, 1 calls of up to 8 chains, 2 every single-batch call
     // A_n Gram folded into k_spmm5's epilogue (kernels_spmm5.hpp, S5Gram): a chain folds at a level when its region there has at least this
@@ -3238,18 +3238,18 @@ int build_operator_table(rsrec_t* h, Spmm5Operator& op, int nset, const char* wh
     return RSREC_OK;
 }
 
-// Operator tables of a velocity-type operator (recursion.f90:587-784): which = 0 -> kubo_op[0] (v_a), 1 -> kubo_op[1] (v_b).
+// Operator tables of a velocity-type operator (recursion.f90:587-784) into `op`: kubo_op[j] (output operator j; v_a is j = 0) or kubo_op_b (v_b).
 //   set 0: V itself -- per-type blocks v_op(:,:,slot,type) for the bulk atoms; the reference has no velocity operator for the
 //          per-atom (impurity) region yet (":591 NOT YET IMPLEMENTED"): those rows of V psi are zero, as there.
 //   set 1 (hoh): -vo_op(:,:,slot,type) for slots >= 2 and the identity in the extra slot, so that one pass over h psi with V psi as
 //          second input gives  V psi - sum_{slot >= 2} vo_slot (h psi)_nbr  (velo_hoh_vec_matmul :750-776; its on-site vo term is
 //          commented out in the reference, its e_nu / l.s terms are zero).
-int build_kubo_operator(rsrec_t* h, int which, const double* v, const double* vo) {
+int build_kubo_operator(rsrec_t* h, Spmm5Operator& op, const double* v, const double* vo) {
     const int nset = h->hoh ? 2 : 1;
     const size_t B = 2 * (size_t)BLK;
     std::vector<double> neg((size_t)h->ntype * h->nslots * B, 0.0), ident(B, 0.0);
     for (int d = 0; d < NB; ++d) ident[2 * (d + NB * d)] = 1.0;
-    return build_operator_table(h, h->kubo_op[which], nset, "rsrec_kubo_moments", [&](auto&& blk) {
+    return build_operator_table(h, op, nset, "rsrec_kubo_moments", [&](auto&& blk) {
         for (int t = 0; t < h->ntype; ++t)
             for (int s = 0; s < h->nslots; ++s) {
                 blk(0, h->nmax + t, s) = v + B * (s + (size_t)h->hslots * t);
@@ -3370,11 +3370,18 @@ void whole_lattice_apply_h(WholeLatticeCall& W, const double* in, double* out, S
     whole_lattice_spmm(W, W.h->s5_op, 1, W.hps, out, in, epi);
 }
 // out = V in   (velo_vec_matmul :587 / velo_hoh_vec_matmul :656)
-void whole_lattice_apply_v(WholeLatticeCall& W, const Spmm5Operator& vop, const double* in, double* out) {
+// in two halves, for several V on one `in`: h_bulk in -> p1 (hoh only; it does not depend on V), then out = V in from it
+void whole_lattice_apply_v_prepare(WholeLatticeCall& W, const double* in) {
+    if (W.h->hoh) whole_lattice_spmm(W, W.h->nmax > 0 ? W.h->kubo_hbulk : W.h->s5_op, 0, in, W.p1, nullptr);
+}
+void whole_lattice_apply_v_prepared(WholeLatticeCall& W, const Spmm5Operator& vop, const double* in, double* out) {
     if (!W.h->hoh) { whole_lattice_spmm(W, vop, 0, in, out, nullptr); return; }
     whole_lattice_spmm(W, vop, 0, in, W.p2, nullptr);
-    whole_lattice_spmm(W, W.h->nmax > 0 ? W.h->kubo_hbulk : W.h->s5_op, 0, in, W.p1, nullptr);
     whole_lattice_spmm(W, vop, 1, W.p1, out, W.p2);
+}
+void whole_lattice_apply_v(WholeLatticeCall& W, const Spmm5Operator& vop, const double* in, double* out) {
+    whole_lattice_apply_v_prepare(W, in);
+    whole_lattice_apply_v_prepared(W, vop, in, out);
 }
 
 // The three-term recurrence on whole vectors, H~ = (H - b)/a: with T_0(H~) x in `cur`, step(n) for n = 0, 1, 2, ... leaves T_n(H~) x in `cur`
@@ -3410,7 +3417,8 @@ int whole_lattice_end(rsrec_t* h, WholeLatticeCall& W, bool rest_is_own_spans = 
 }
 
 // The device memory of a rsrec_kubo_moments call, decided before anything is reserved: 11 work vectors, `lchunk` left vectors, one block of
-// right vectors, the slices' partial blocks, the moments of the vectors in flight -- the five buffers of d_kubo, in that order.
+// right vectors per output operator (`nout`; 1 but for rsrec_kubo_moments_diag_multi), the slices' partial blocks, `nout` moment images of
+// the vectors in flight -- the five buffers of d_kubo, in that order.
 // The left matrix is held in chunks of `lchunk` vectors (all of them if they fit: cond_ll x kk x 5184 B is 21 GB for cond_ll = 500
 // on 8 000 atoms, 252 GB on 10^5): each chunk continues the left recurrence where the previous one stopped and is contracted
 // with ALL right vectors, so the right recurrence (2 of the 3 SpMMs per moment order) is repeated once per chunk.
@@ -3419,7 +3427,7 @@ int whole_lattice_end(rsrec_t* h, WholeLatticeCall& W, bool rest_is_own_spans = 
 // every launch (chain c of a buffer slot lies c vectors behind chain 0, exactly like the sites of a recursion batch); each keeps its own
 // left / right matrices and is contracted by itself.  A whole left matrix per vector goes first: vectors are added only while it fits.
 struct KuboPlan {
-    int cond_ll = 0, n_cu = 0;
+    int cond_ll = 0, n_cu = 0, nout = 1;     // nout: output operators (sets) of the call, each with right slots and moments of its own
     bool diag = false, resident = false;     // rsrec_kubo_moments_diag: 18 instead of 324 elements per (n, m); the moments of ALL vectors of the call fit d_kubo[4]
     int nchunk = 0, lchunk = 0, nbv = 0;     // right vectors per contraction; left vectors held at a time; vectors in flight
     int ksteps_total = 0, nbn_max = 0;       // k-steps of 4 rows (the last one may end inside the zero block); column blocks of a full contraction
@@ -3445,12 +3453,12 @@ struct KuboPlan {
     enum { PSIREF = 0, Y = 1 /* .. 3: the right recurrence */, L0 = 4, HPS = 6, P1 = 7, P2 = 8, L1 = 9 };   // work vectors (L0, L1: T_{m0-2} r, T_{m0-1} r, the left recurrence across a chunk border)
     double* vec(int v) const { return work + (size_t)v * sstride; }
     double* Lslot(int q) const { return Lm + (size_t)q * sstride; }
-    double* Rslot(int q) const { return Rm + (size_t)q * sstride; }
+    double* Rslot(int j, int q) const { return Rm + ((size_t)j * nchunk + q) * sstride; }      // slot q of set j
 };
 
-int kubo_plan(rsrec_t* h, int nvec, int cond_ll, bool diag, KuboPlan& P) {
+int kubo_plan(rsrec_t* h, int nout, int nvec, int cond_ll, bool diag, KuboPlan& P) {
     const int kk = h->kk;
-    P.diag = diag;
+    P.diag = diag; P.nout = nout;
     P.cond_ll = cond_ll; P.n_cu = h->n_cu; P.velems = (size_t)(kk + 1) * BLD;
     P.nchunk = std::min(cond_ll, 64);
     size_t free_b = 0, total_b = 0;
@@ -3465,7 +3473,7 @@ int kubo_plan(rsrec_t* h, int nvec, int cond_ll, bool diag, KuboPlan& P) {
     auto part_bytes = [&](int lc) {
         if (diag) return (double)P.ksplit_for(lc) * ((lc + KD_T - 1) / KD_T) * KD_T * (double)P.nbn_max * KD_T * NB * 16.0;
         return (double)P.ksplit_for(lc) * ((lc * NB + KG_BLK - 1) / KG_BLK) * KG_BLK * (double)P.nbn_max * KG_BLK * 16.0; };
-    auto need_for = [&](int lc, int nv) { return (11.0 + lc + P.nchunk) * nv * P.velems * 8 + part_bytes(lc) + (double)nv * mu_bytes; };
+    auto need_for = [&](int lc, int nv) { return (11.0 + lc + (double)nout * P.nchunk) * nv * P.velems * 8 + part_bytes(lc) + (double)nv * nout * mu_bytes; };
     int lchunk = cond_ll;
     if (h->opt_kubo_lchunk > 0) lchunk = (int)std::min<long>(cond_ll, h->opt_kubo_lchunk);
     int nbv = (int)std::min<long>(nvec, h->opt_kubo_vbatch > 0 ? h->opt_kubo_vbatch : 8);
@@ -3474,10 +3482,10 @@ int kubo_plan(rsrec_t* h, int nvec, int cond_ll, bool diag, KuboPlan& P) {
     if (need_for(lchunk, nbv) > budget)
         return fail(h, RSREC_ERR_DEVICE, "rsrec_kubo_moments: %.1f GB needed for one left vector at a time on %d atoms, %.1f GB free", need_for(1, 1) * 1e-9, kk, free_b * 1e-9);
     P.lchunk = lchunk; P.nbv = nbv; P.sstride = (size_t)nbv * P.velems;
-    P.bytes[0] = 11 * P.sstride * 8; P.bytes[1] = (size_t)lchunk * P.sstride * 8; P.bytes[2] = (size_t)P.nchunk * P.sstride * 8;
+    P.bytes[0] = 11 * P.sstride * 8; P.bytes[1] = (size_t)lchunk * P.sstride * 8; P.bytes[2] = (size_t)nout * P.nchunk * P.sstride * 8;
     // the diagonal moments of the whole call stay on the handle if they fit beside everything else; lchunk and nbv do not depend on it
-    P.resident = diag && need_for(lchunk, nbv) + (double)(nvec - nbv) * mu_bytes <= budget;
-    P.bytes[3] = (size_t)part_bytes(lchunk); P.bytes[4] = (size_t)(P.resident ? nvec : nbv) * (size_t)mu_bytes;
+    P.resident = diag && need_for(lchunk, nbv) + (double)(nvec - nbv) * nout * mu_bytes <= budget;
+    P.bytes[3] = (size_t)part_bytes(lchunk); P.bytes[4] = (size_t)(P.resident ? nvec : nbv) * nout * (size_t)mu_bytes;
     return RSREC_OK;
 }
 
@@ -3547,8 +3555,8 @@ int kubo_left_chunk(WholeLatticeCall& W, const KuboPlan& P, int m0, double a, do
 
 // The same for the orbital-diagonal moments alone: per column c the Gram matrix of the chunk's left and the block's right vectors, tiles of
 // 16 x 16 vectors x all 18 columns x `ksplit` slices of (k,r), one workgroup each (k_kubo_gram_diag), then k_kubo_gram_diag_reduce.
-// mu_off: where the batch's first vector lies in P.mu (resident moments of the whole call), in vectors.
-int kubo_contract_diag(WholeLatticeCall& W, const KuboPlan& P, int m0, int n, size_t mu_off) {
+// mu_off: where the batch's first vector lies in P.mu (resident moments of the whole call; the images of set j), in vectors.
+int kubo_contract_diag(WholeLatticeCall& W, const KuboPlan& P, int j, int m0, int n, size_t mu_off) {
     rsrec_t* h = W.h;
     const int nl = n % P.nchunk, n0 = n - nl, nv = nl + 1, mv = std::min(P.lchunk, P.cond_ll - m0);
     const int nbm = (mv + KD_T - 1) / KD_T, nbn = (nv + KD_T - 1) / KD_T;
@@ -3566,20 +3574,20 @@ int kubo_contract_diag(WholeLatticeCall& W, const KuboPlan& P, int m0, int n, si
     const unsigned wgs = 8u * (unsigned)((long)nbm * nbn * (ksplit / 8));
     const size_t mu_vec = (size_t)P.cond_ll * P.cond_ll * NB;
     for (int c = 0; c < W.SD.nchains; ++c) {
-        k_kubo_gram_diag<<<wgs, 256, 0, h->stream>>>(P.Lm + (size_t)c * P.velems, P.sstride, mv, P.Rm + (size_t)c * P.velems, P.sstride, nv, P.ksteps_total, ksplit, P.part, nbm, nbn);
+        k_kubo_gram_diag<<<wgs, 256, 0, h->stream>>>(P.Lm + (size_t)c * P.velems, P.sstride, mv, P.Rslot(j, 0) + (size_t)c * P.velems, P.sstride, nv, P.ksteps_total, ksplit, P.part, nbm, nbn);
         k_kubo_gram_diag_reduce<<<(int)std::min<long>(4096, ((long)mv * nv * NB + 255) / 256), 256, 0, h->stream>>>(P.part, ksplit, nbm * KD_T, nbn * KD_T, mv, nv, P.mu + (mu_off + c) * mu_vec, P.cond_ll, m0, n0);
     }
     W.rest_ev.emplace_back(g0, next_event(h));
     return RSREC_OK;
 }
 
-// The block of right vectors that ends with order n (slots 0 .. n % nchunk of Rm) against the left chunk from m0 on, between its events:
+// The block of right vectors of set j that ends with order n (its slots 0 .. n % nchunk of Rm) against the left chunk from m0 on, between its events:
 // C[(m,c)][(n,c')] = sum_{k,r} conj(L_m[(k,r)][c]) R_n[(k,r)][c'], blocks of C x `ksplit` slices of (k,r), one wave each (k_kubo_gram), then
 // the slices summed in fixed order into mu (k_kubo_gram_reduce).  One contraction per vector of the batch: its matrices are the chain-c
 // columns of the slots (leading dimension = a whole slot).
-int kubo_contract(WholeLatticeCall& W, const KuboPlan& P, int m0, int n, size_t mu_off = 0) {
+int kubo_contract(WholeLatticeCall& W, const KuboPlan& P, int j, int m0, int n, size_t mu_off = 0) {
     rsrec_t* h = W.h;
-    if (P.diag) return kubo_contract_diag(W, P, m0, n, mu_off);
+    if (P.diag) return kubo_contract_diag(W, P, j, m0, n, mu_off);
     const int nl = n % P.nchunk, n0 = n - nl, ncols = (nl + 1) * NB, m_rows = std::min(P.lchunk, P.cond_ll - m0) * NB;
     const int nbm = (m_rows + KG_BLK - 1) / KG_BLK, nbn = (ncols + KG_BLK - 1) / KG_BLK;
     // slices: the multiple of 8 (<= what the partial buffer was sized for, >= 64 k-steps per task) that fills whole rounds of
@@ -3597,22 +3605,26 @@ int kubo_contract(WholeLatticeCall& W, const KuboPlan& P, int m0, int n, size_t 
     const unsigned wgs = 8u * (unsigned)(((long)nbm * nbn * (ksplit / 8) + 3) / 4);
     const size_t mu_vec = (size_t)P.cond_ll * P.cond_ll * BLK;
     for (int c = 0; c < W.SD.nchains; ++c) {
-        k_kubo_gram<<<wgs, 256, 0, h->stream>>>(P.Lm + (size_t)c * P.velems, P.sstride, m_rows, P.Rm + (size_t)c * P.velems, P.sstride, ncols, P.ksteps_total, ksplit, P.part, nbm, nbn);
+        k_kubo_gram<<<wgs, 256, 0, h->stream>>>(P.Lm + (size_t)c * P.velems, P.sstride, m_rows, P.Rslot(j, 0) + (size_t)c * P.velems, P.sstride, ncols, P.ksteps_total, ksplit, P.part, nbm, nbn);
         k_kubo_gram_reduce<<<std::min(4096, (m_rows * ncols + 255) / 256), 256, 0, h->stream>>>(P.part, ksplit, nbm * KG_BLK, nbn * KG_BLK, m_rows, ncols, P.mu + (size_t)c * mu_vec, P.cond_ll, m0, n0);
     }
     W.rest_ev.emplace_back(g0, next_event(h));
     return RSREC_OK;
 }
 
-// What rsrec_kubo_moments and rsrec_kubo_moments_diag share: everything but the contraction kernels (kubo_contract) and the shape of the
-// result -- `out`: complex (18,18,cond_ll,cond_ll,nvec) on the host, or with `diag` complex (18,cond_ll,cond_ll,nvec), host or device or
-// NULL, and then the moments of the whole call stay in d_kubo[4] if they fit there.
-int kubo_moments_run(rsrec_t* h, const char* fn, bool diag, int nvec, int nseed, const int32_t* seed_atoms, const double* seed_coef, int cond_ll, double a, double b,
-                     const double* v_a, const double* vo_a, const double* v_b, const double* vo_b, double* out) {
+// What rsrec_kubo_moments, rsrec_kubo_moments_diag and rsrec_kubo_moments_diag_multi share: everything but the contraction kernels
+// (kubo_contract) and the shape of the result -- `out`: complex (18,18,cond_ll,cond_ll,nvec) on the host, or with `diag` complex
+// (18,cond_ll,cond_ll,nvec,nout), host or device or NULL, and then the moments of the whole call stay in d_kubo[4] if they fit there.
+// `nout` output operators v_out(:,:,:,:,j) (the single-response calls: 1, v_a): the left vectors and the right recurrence T_{n-1}(H~) v_b r
+// do not depend on the output operator, so they are formed once, and per order n every set j gets  v_out_j T_{n-1}(H~) v_b r  into a right
+// slot of its own and is contracted by itself -- the launches of set j are those of the single-response call with v_a = v_out_j.
+int kubo_moments_run(rsrec_t* h, const char* fn, bool diag, int nout, int nvec, int nseed, const int32_t* seed_atoms, const double* seed_coef, int cond_ll,
+                     double a, double b, const double* v_out, const double* vo_out, const double* v_b, const double* vo_b, double* out) {
     XFER(check_ready(h, fn));
-    if (nvec < 0 || nseed < 1 || cond_ll < 1 || (diag && cond_ll > RSREC_COND_LL_MAX) || a == 0.0 || !v_a || !v_b || (!diag && !out) || (nvec > 0 && (!seed_atoms || !seed_coef)))
+    if (nout < 1 || nout > RSREC_KUBO_NOUT_MAX) return fail(h, RSREC_ERR_ARG, "%s: nout=%d is not in 1..%d", fn, nout, RSREC_KUBO_NOUT_MAX);
+    if (nvec < 0 || nseed < 1 || cond_ll < 1 || (diag && cond_ll > RSREC_COND_LL_MAX) || a == 0.0 || !v_out || !v_b || (!diag && !out) || (nvec > 0 && (!seed_atoms || !seed_coef)))
         return fail(h, RSREC_ERR_ARG, "%s: bad argument", fn);
-    if (h->hoh && (!vo_a || !vo_b)) return fail(h, RSREC_ERR_ARG, "%s: hoh requires vo_a and vo_b", fn);
+    if (h->hoh && (!vo_out || !vo_b)) return fail(h, RSREC_ERR_ARG, "%s: hoh requires %s and vo_b", fn, nout > 1 ? "vo_out" : "vo_a");
     if (!h->s5_built) return fail(h, RSREC_ERR_ARG, "%s: lattice has too many neighbour slots for the SpMM kernel", fn);
     XFER(check_seeds(h, fn, seed_atoms, (size_t)nvec * nseed, 0));
     HIPCK(h, hipSetDevice(h->device));
@@ -3620,11 +3632,12 @@ int kubo_moments_run(rsrec_t* h, const char* fn, bool diag, int nvec, int nseed,
     if (nvec == 0) return RSREC_OK;
     h->kubo_diag_nvec = h->kubo_diag_ll = 0;                       // (d_kubo[4] is about to be overwritten)
     release_kubo_buffers(h, false, true);                          // (the integrand's buffers; this call's own stay for the next one)
-    XFER(build_kubo_operator(h, 0, v_a, vo_a));
-    XFER(build_kubo_operator(h, 1, v_b, vo_b));
+    const size_t op_doubles = 2 * (size_t)BLK * h->hslots * h->ntype;             // one operator of v_out / vo_out
+    for (int j = 0; j < nout; ++j) XFER(build_kubo_operator(h, h->kubo_op[j], v_out + op_doubles * j, vo_out ? vo_out + op_doubles * j : nullptr));
+    XFER(build_kubo_operator(h, h->kubo_op_b, v_b, vo_b));
     if (h->hoh && h->nmax > 0) XFER(build_kubo_hbulk(h));
     KuboPlan P;
-    XFER(kubo_plan(h, nvec, cond_ll, diag, P));
+    XFER(kubo_plan(h, nout, nvec, cond_ll, diag, P));
     XFER(kubo_reserve(h, P));
     HIPCK(h, h->d_seed.reserve((size_t)nseed * 4));
     HIPCK(h, h->d_seedcoef.reserve((size_t)nseed * sizeof(double2)));
@@ -3638,7 +3651,8 @@ int kubo_moments_run(rsrec_t* h, const char* fn, bool diag, int nvec, int nseed,
     int n_left_chunks = 0;
     for (int iv0 = 0; iv0 < nvec; iv0 += P.nbv) {
         const int nb = std::min(P.nbv, nvec - iv0);                               // vectors of this batch = chains of its launches
-        const size_t mu_off = P.resident ? (size_t)iv0 : 0;                       // where the batch's moments lie in P.mu, in vectors
+        // where the batch's moments of set j lie in P.mu, in vectors: the layout of the result (set outermost) if the whole call is resident
+        auto mu_off = [&](int j) { return P.resident ? (size_t)j * nvec + iv0 : (size_t)j * P.nbv; };
         whole_lattice_batch(W, nb, false);
         XFER(kubo_seed_batch(h, P, S, iv0, nb));
         for (int m0 = 0; m0 < cond_ll; m0 += P.lchunk, ++n_left_chunks) {
@@ -3646,21 +3660,26 @@ int kubo_moments_run(rsrec_t* h, const char* fn, bool diag, int nvec, int nseed,
             // right vectors  v_a T_{n-1}(H~) v_b r  (:1154-1187), written into the slots of Rm and contracted with the left vectors of
             // this chunk, 64 at a time
             ChebyshevStepper Y{P.vec(KuboPlan::Y), P.vec(KuboPlan::Y + 1), P.vec(KuboPlan::Y + 2)};
-            whole_lattice_apply_v(W, h->kubo_op[1], P.vec(KuboPlan::PSIREF), Y.cur);      // v1 = v0 = v_b r
+            whole_lattice_apply_v(W, h->kubo_op_b, P.vec(KuboPlan::PSIREF), Y.cur);       // v1 = v0 = v_b r
             for (int n = 0; n < cond_ll; ++n) {
                 Y.step(W, n, a, b);
-                whole_lattice_apply_v(W, h->kubo_op[0], Y.cur, P.Rslot(n % P.nchunk));
-                if (n % P.nchunk == P.nchunk - 1 || n == cond_ll - 1) XFER(kubo_contract(W, P, m0, n, mu_off));
+                whole_lattice_apply_v_prepare(W, Y.cur);
+                for (int j = 0; j < nout; ++j) whole_lattice_apply_v_prepared(W, h->kubo_op[j], Y.cur, P.Rslot(j, n % P.nchunk));
+                if (n % P.nchunk == P.nchunk - 1 || n == cond_ll - 1)
+                    for (int j = 0; j < nout; ++j) XFER(kubo_contract(W, P, j, m0, n, mu_off(j)));
             }
         }
         HIPCK(h, hipGetLastError());
-        const double* src = reinterpret_cast<const double*>(P.mu) + mu_vec * mu_off;
-        if (out_dev) HIPCK(h, hipMemcpyAsync(out + mu_vec * iv0, src, (size_t)nb * mu_vec * 8, hipMemcpyDeviceToDevice, h->stream));
-        else if (out) XFER(xfer_d2h(h, out + mu_vec * iv0, src, (size_t)nb * mu_vec * 8));
+        for (int j = 0; j < nout && out; ++j) {
+            const double* src = reinterpret_cast<const double*>(P.mu) + mu_vec * mu_off(j);
+            double* dst = out + mu_vec * ((size_t)j * nvec + iv0);
+            if (out_dev) HIPCK(h, hipMemcpyAsync(dst, src, (size_t)nb * mu_vec * 8, hipMemcpyDeviceToDevice, h->stream));
+            else XFER(xfer_d2h(h, dst, src, (size_t)nb * mu_vec * 8));
+        }
     }
     XFER(whole_lattice_end(h, W, true));
     h->n_kubo_left_chunks = n_left_chunks;
-    if (P.resident) { h->kubo_diag_nvec = nvec; h->kubo_diag_ll = cond_ll; }
+    if (P.resident) { h->kubo_diag_nvec = nvec * nout; h->kubo_diag_ll = cond_ll; }
     return RSREC_OK;
 }
 
@@ -3672,7 +3691,7 @@ int kubo_moments_run(rsrec_t* h, const char* fn, bool diag, int nvec, int nseed,
 extern "C" int rsrec_kubo_moments(rsrec_t* h, int nvec, int nseed, const int32_t* seed_atoms, const double* seed_coef, int cond_ll, double a, double b,
                                   const double* v_a, const double* vo_a, const double* v_b, const double* vo_b, double* mu_nm) {
     if (!h) return RSREC_ERR_ARG;
-    return kubo_moments_run(h, "rsrec_kubo_moments", false, nvec, nseed, seed_atoms, seed_coef, cond_ll, a, b, v_a, vo_a, v_b, vo_b, mu_nm);
+    return kubo_moments_run(h, "rsrec_kubo_moments", false, 1, nvec, nseed, seed_atoms, seed_coef, cond_ll, a, b, v_a, vo_a, v_b, vo_b, mu_nm);
 }
 
 // The same recurrences, but only the orbital-diagonal moments mu(l,l,n,m,i) are contracted (k_kubo_gram_diag): conductivity.f90:289 and
@@ -3680,7 +3699,17 @@ extern "C" int rsrec_kubo_moments(rsrec_t* h, int nvec, int nseed, const int32_t
 extern "C" int rsrec_kubo_moments_diag(rsrec_t* h, int nvec, int nseed, const int32_t* seed_atoms, const double* seed_coef, int cond_ll, double a, double b,
                                        const double* v_a, const double* vo_a, const double* v_b, const double* vo_b, double* mu_diag) {
     if (!h) return RSREC_ERR_ARG;
-    return kubo_moments_run(h, "rsrec_kubo_moments_diag", true, nvec, nseed, seed_atoms, seed_coef, cond_ll, a, b, v_a, vo_a, v_b, vo_b, mu_diag);
+    return kubo_moments_run(h, "rsrec_kubo_moments_diag", true, 1, nvec, nseed, seed_atoms, seed_coef, cond_ll, a, b, v_a, vo_a, v_b, vo_b, mu_diag);
+}
+
+// The diagonal moments of `nout` responses to one applied field: set j is rsrec_kubo_moments_diag with v_a = v_out(:,:,:,:,j).  The left
+// vectors, the right recurrence and (hoh) the h_bulk pass of every V product are shared: (2 + nout) cond_ll whole-lattice products
+// instead of 3 nout cond_ll.
+extern "C" int rsrec_kubo_moments_diag_multi(rsrec_t* h, int nout, int nvec, int nseed, const int32_t* seed_atoms, const double* seed_coef, int cond_ll,
+                                             double a, double b, const double* v_out, const double* vo_out, const double* v_b, const double* vo_b,
+                                             double* mu_diag) {
+    if (!h) return RSREC_ERR_ARG;
+    return kubo_moments_run(h, "rsrec_kubo_moments_diag_multi", true, nout, nvec, nseed, seed_atoms, seed_coef, cond_ll, a, b, v_out, vo_out, v_b, vo_b, mu_diag);
 }
 
 namespace {
@@ -3947,7 +3976,7 @@ extern "C" int rsrec_apply_operator(rsrec_t* h, int vel, const double* v_op, con
     reset_timing(h);
     const int kk = h->kk;
     const size_t velems = (size_t)(kk + 1) * BLD, nd = (size_t)kk * BLD;
-    if (vel == 1) { XFER(build_kubo_operator(h, 0, v_op, vo_op)); if (h->hoh && h->nmax > 0) XFER(build_kubo_hbulk(h)); }
+    if (vel == 1) { XFER(build_kubo_operator(h, h->kubo_op[0], v_op, vo_op)); if (h->hoh && h->nmax > 0) XFER(build_kubo_hbulk(h)); }
     if (vel == 2 && h->hoh) XFER(build_plain_operator(h));                              // ham_vec_matmul under hoh: the plain operator (recursion.f90:913)
     for (int v = 0; v < 6; ++v) HIPCK(h, h->d_vec[v].reserve(velems * 8));
     for (int v = 0; v < 6; ++v) HIPCK(h, hipMemsetAsync(h->d_vec[v].p, 0, velems * 8, h->stream));

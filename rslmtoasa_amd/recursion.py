@@ -371,6 +371,32 @@ class Recursion:
         self.mu_nm_stochastic = mu
         return mu
 
+    def compute_moments_stochastic_multi(self, v_out, v_b, cond_ll, vo_out=None, vo_b=None, seeds=None, coefs=None, atlist=None,
+                                         resident_only=False):
+        """The orbital-diagonal Kubo moments of several responses to one applied field (``rsrec_kubo_moments_diag_multi``):
+        ``v_out`` (18, 18, nslots, ntype, nout) holds one output operator per response (``vo_out`` likewise, hoh only), ``v_b`` the
+        input operator; vectors as in ``compute_moments_stochastic``.  Set j of the result, complex128 (18, cond_ll, cond_ll, nvec,
+        nout) in Fortran order, is ``compute_moments_stochastic(v_out[..., j], v_b, diag=True)`` bit for bit, at (2 + nout) instead of
+        3 nout whole-lattice products per moment order.  The moments stay on the device as nvec * nout vectors, set outermost:
+        ``Conductivity.integrand(None, ene)`` returns (18, nen, nvec * nout), and ``Conductivity.tensor`` takes a set's slice
+        ``[:, :, j * nvec:(j + 1) * nvec]``.  ``resident_only=True``: nothing is downloaded and None is returned."""
+        a, b = chebyshev_scaling(self.en.energy_min, self.en.energy_max)
+        if seeds is None:
+            seeds = np.asarray(atlist, dtype=np.int32).reshape(-1, 1)
+            coefs = np.ones(seeds.shape, np.complex128)
+        seeds = np.ascontiguousarray(seeds, dtype=np.int32)
+        coefs = np.ascontiguousarray(coefs, dtype=np.complex128)
+        nvec, nseed = seeds.shape
+        keep = [None if v is None else _fc(v, np.complex128) for v in (v_out, vo_out, v_b, vo_b)]
+        if keep[0].ndim != 5 or (keep[1] is not None and keep[1].shape != keep[0].shape):
+            raise ValueError("v_out (and vo_out) must be (18, 18, nslots, ntype, nout), got %s" % (keep[0].shape,))
+        nout = keep[0].shape[4]
+        mu = None if resident_only else np.zeros((18, cond_ll, cond_ll, nvec, nout), np.complex128, order="F")
+        self._check(self._L.rsrec_kubo_moments_diag_multi(self._h, nout, nvec, nseed, _ptr(seeds), _ptr(coefs), int(cond_ll), a, b,
+                                                          _ptr(keep[0]), _ptr(keep[1]), _ptr(keep[2]), _ptr(keep[3]), _ptr(mu)))
+        self.mu_diag_resident = (int(cond_ll), nvec * nout)      # what Conductivity.integrand(None, ...) asks the library for
+        return mu
+
     def ham_vec_matmul(self, psi_in, a, b):
         """psi_out = (H psi_in - b psi_in)/a on a whole vector psi(18,18,kk) with the PLAIN operator ee + l.s, whatever hoh says
         (recursion.f90:913-977)."""

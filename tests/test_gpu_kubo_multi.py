@@ -1,0 +1,318 @@
+"""The orbital-diagonal Kubo moments of several responses to one applied field (rsrec_kubo_moments_diag_multi): the left vectors
+T_{m-1}(H~) r and the right recurrence T_{n-1}(H~) v_b r do not depend on the output operator, so one call forms them once and
+contracts every output operator's right vectors by itself.  Set j of the result must be what rsrec_kubo_moments_diag returns for
+v_a = v_out(:,:,:,:,j) -- bit for bit on the ragged lattice of tests/test_gpu_kubo_diag.py (338 k-steps: the contraction takes 8
+slices on any device), and at helpers.RTOL against the compiled reference's moments.  Also: independence of the other sets and of
+the vectors in flight, host / device / resident output, the resident integrand, the launch counts, the refusals, the Python mirror."""
+
+import numpy as np
+import pytest
+
+import cond_reference as R
+from helpers import RTOL, load_golden
+from rslmtoasa_amd import _lib
+from rslmtoasa_amd.conductivity import Conductivity
+from rslmtoasa_amd.recursion import Control, Energy, Hamiltonian, Lattice, Recursion
+from test_gpu_kubo_diag import DIAG, golden_case, integrand_call, ptr, ragged_case, same_bits, vec_err
+
+pytestmark = pytest.mark.gpu
+FN = "rsrec_kubo_moments_diag_multi"
+NOUT_MAX = 8
+
+
+@pytest.fixture(scope="module", autouse=True)
+def torch_first():
+    import torch
+    torch.cuda.init()                                  # torch's HIP runtime before librsrec's (as bench.py does)
+    torch.cuda.set_device(0)
+
+
+def stack(ops):
+    """output operators (18, 18, nslots, ntype) -> (18, 18, nslots, ntype, nout), Fortran order; None if there are none (no hoh)"""
+    return None if ops[0] is None else np.asfortranarray(np.stack(ops, axis=-1), dtype=np.complex128)
+
+
+def multi_call(c, outs, cond_ll, out, vecs=None, nout=None, v_b="case", vo_b="case"):
+    """rsrec_kubo_moments_diag_multi on the case's vectors with output operators outs = [(v, vo), ...]; returns the return code"""
+    rec = c.rec
+    sel = slice(None) if vecs is None else vecs
+    seeds, coefs = np.ascontiguousarray(c.seeds[sel]), np.ascontiguousarray(c.coefs[sel])
+    nvec, nseed = seeds.shape
+    v_out = stack([o[0] for o in outs]) if outs else None
+    vo_out = stack([o[1] for o in outs]) if outs else None
+    vb = c.ops[2] if isinstance(v_b, str) else v_b
+    vob = c.ops[3] if isinstance(vo_b, str) else vo_b
+    return getattr(rec._L, FN)(rec._h, len(outs) if nout is None else nout, nvec, nseed, ptr(seeds), ptr(coefs), int(cond_ll), c.a, c.b,
+                               ptr(v_out), ptr(vo_out), ptr(vb), ptr(vob), ptr(out))
+
+
+def multi(c, outs, cond_ll, vecs=None):
+    nvec = len(c.seeds[slice(None) if vecs is None else vecs])
+    mu = np.zeros((18, cond_ll, cond_ll, nvec, len(outs)), np.complex128, order="F")
+    c.rec._check(multi_call(c, outs, cond_ll, mu, vecs))
+    return mu
+
+
+def single(c, op, cond_ll, vecs=None):
+    """rsrec_kubo_moments_diag with (v_a, vo_a) = op and the case's v_b"""
+    keep = c.ops
+    c.ops = [op[0], op[1], keep[2], keep[3]]
+    try:
+        return c.diag(cond_ll, vecs)
+    finally:
+        c.ops = keep
+
+
+class Ragged:
+    """The ragged lattice with three output operators: the case's v_a, its v_b used as an output operator, one more random operator."""
+
+    def __init__(self, hoh):
+        self.c = c = ragged_case(hoh)
+        rng = np.random.default_rng(777 + int(hoh))
+
+        def vel():
+            return np.asfortranarray((rng.standard_normal((18, 18, 5, 2)) + 1j * rng.standard_normal((18, 18, 5, 2))) * 0.2)
+        extra = (vel(), vel() if hoh else None)
+        self.outs = [(c.ops[0], c.ops[1]), (c.ops[2], c.ops[3]), extra]
+        self.cache = {}
+
+    def single(self, j, cond_ll, lchunk=0):
+        """the single-response moments of output operator j, computed once per (j, cond_ll, kubo_lchunk) and left unchanged"""
+        key = (j, cond_ll, lchunk)
+        if key not in self.cache:
+            self.c.rec.set_option("kubo_lchunk", lchunk)
+            try:
+                mu = single(self.c, self.outs[j], cond_ll)
+            finally:
+                self.c.rec.set_option("kubo_lchunk", 0)
+            mu.setflags(write=False)
+            self.cache[key] = mu
+        return self.cache[key]
+
+
+@pytest.fixture(scope="module")
+def ragged():
+    cases = {hoh: Ragged(hoh) for hoh in (False, True)}
+    yield cases
+    for r in cases.values():
+        r.c.rec.close()
+
+
+# ---- 1. bitwise against the single-response call --------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("lchunk", [0, 3])
+@pytest.mark.parametrize("cond_ll", [1, 2, 17, 65])
+@pytest.mark.parametrize("hoh", [False, True])
+def test_every_set_has_the_single_response_bits(hoh, cond_ll, lchunk, ragged):
+    """cond_ll 65 crosses the border of a block of 64 right vectors, where the right slots of every set are reused; kubo_lchunk 3:
+    left-chunk borders, the right recurrence repeated per chunk."""
+    r = ragged[hoh]
+    r.c.rec.set_option("kubo_lchunk", lchunk)
+    try:
+        mu = multi(r.c, r.outs, cond_ll)
+    finally:
+        r.c.rec.set_option("kubo_lchunk", 0)
+    assert mu.shape == (18, cond_ll, cond_ll, 3, 3) and np.isfinite(mu).all()
+    for j in range(3):
+        ref = r.single(j, cond_ll, lchunk)
+        assert np.abs(ref).max() > 0
+        assert same_bits(mu[..., j], ref), (j, vec_err(mu[..., j], ref))
+    assert not same_bits(mu[..., 0], mu[..., 1]) and not same_bits(mu[..., 1], mu[..., 2])
+
+
+# ---- 2. against the compiled reference -------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", ["fccPt_kubo", "fccPt_kubo_hoh", "fccPt_kubo_random"])
+def test_sets_match_reference_and_single_response(name):
+    z, c = golden_case(name)
+    try:
+        L = int(z["cond_ll"])
+        outs = [(c.ops[0], c.ops[1]), (c.ops[2], c.ops[3])]
+        mu = multi(c, outs, L)
+        second = single(c, outs[1], L)
+    finally:
+        c.rec.close()
+    ref = z["mu_nm"][DIAG, DIAG]
+    assert mu.shape == ref.shape + (2,)
+    e1, e2 = vec_err(mu[..., 0], ref), vec_err(mu[..., 1], second)
+    print("multi vs reference", name, e1, "second set vs single call", e2)
+    assert e1 < RTOL
+    assert e2 < RTOL
+
+
+# ---- 3. - 6. one set, other sets, vectors in flight, where the output goes: bitwise ------------------------------------------------------
+
+@pytest.mark.parametrize("hoh", [False, True])
+def test_one_set_has_the_single_response_bits(hoh, ragged):
+    r = ragged[hoh]
+    assert same_bits(multi(r.c, r.outs[:1], 17)[..., 0], r.single(0, 17))
+
+
+@pytest.mark.parametrize("hoh", [False, True])
+def test_a_set_does_not_depend_on_the_other_sets(hoh, ragged):
+    r = ragged[hoh]
+    a, b, cc = r.outs
+    abc, ca, only_b = multi(r.c, [a, b, cc], 19), multi(r.c, [cc, a], 19), multi(r.c, [b], 19)
+    assert same_bits(abc[..., 0], ca[..., 1])
+    assert same_bits(abc[..., 2], ca[..., 0])
+    assert same_bits(abc[..., 1], only_b[..., 0])
+
+
+def test_vectors_in_flight_do_not_change_a_vector(ragged):
+    r = ragged[False]
+    try:
+        r.c.rec.set_option("kubo_vbatch", 3)
+        three = multi(r.c, r.outs, 19)
+        r.c.rec.set_option("kubo_vbatch", 1)
+        one_by_one = multi(r.c, r.outs, 19)
+        assert same_bits(one_by_one, three)
+        for v in range(3):
+            assert same_bits(multi(r.c, r.outs, 19, vecs=slice(v, v + 1))[:, :, :, 0, :], three[:, :, :, v, :])
+    finally:
+        r.c.rec.set_option("kubo_vbatch", 0)
+
+
+def test_host_device_and_resident_output_same_bits(ragged):
+    import torch
+    r = ragged[True]
+    L, nvec, nout = 17, len(r.c.seeds), 3
+    host = multi(r.c, r.outs, L)
+    dev = torch.zeros((nout, nvec, L, L, 18), dtype=torch.complex128, device="cuda")      # (18, L, L, nvec, nout) seen from C
+    r.c.rec._check(multi_call(r.c, r.outs, L, dev))
+    torch.cuda.synchronize()
+    assert same_bits(host, np.asfortranarray(dev.cpu().numpy().transpose(4, 3, 2, 1, 0)))
+    r.c.rec._check(multi_call(r.c, r.outs, L, None))                                       # nothing copied out ...
+    assert same_bits(multi(r.c, r.outs, L), host)                                          # ... and the next download has the same bits
+
+
+# ---- 7. resident moments ----------------------------------------------------------------------------------------------------------------
+
+def test_resident_moments(ragged):
+    r = ragged[False]
+    c = r.c
+    L, nvec, nout = 17, len(c.seeds), 3
+    z = dict(ene=np.linspace(-0.7, 0.5, 37), energy_min=-0.8, energy_max=0.6)
+    mu = multi(c, r.outs, L)
+    rc, res = integrand_call(c, "rsrec_kubo_integrand_diag", nvec * nout, L, None, z)
+    assert rc == 0, c.last_error()
+    rc, down = integrand_call(c, "rsrec_kubo_integrand_diag", nvec * nout, L, mu.reshape((18, L, L, nvec * nout), order="F"), z)
+    assert rc == 0 and np.isfinite(res).all() and np.abs(res).max() > 0
+    assert same_bits(res, down)
+    for j in range(nout):                                  # the set index is outermost: a set's slice is the single call's integrand
+        rc, one = integrand_call(c, "rsrec_kubo_integrand_diag", nvec, L, np.asfortranarray(mu[..., j]), z)
+        assert rc == 0 and same_bits(res[:, :, j * nvec:(j + 1) * nvec], one)
+    rc, _ = integrand_call(c, "rsrec_kubo_integrand_diag", nvec, L, None, z)               # nvec * nout are resident, not nvec
+    assert rc == _lib.ERR_ARG and len(c.last_error()) > 0
+    assert integrand_call(c, "rsrec_kubo_integrand_diag", nvec * nout, L, None, z)[0] == 0   # the refusal dropped nothing
+    single(c, r.outs[0], L)                                                                  # a single-response call: nvec again
+    assert integrand_call(c, "rsrec_kubo_integrand_diag", nvec * nout, L, None, z)[0] == _lib.ERR_ARG
+    rc, res1 = integrand_call(c, "rsrec_kubo_integrand_diag", nvec, L, None, z)
+    assert rc == 0 and same_bits(res1, res[:, :, :nvec])
+
+
+# ---- 8. launch counts ----------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("hoh", [False, True])
+def test_launch_counts(hoh, ragged):
+    """kubo_lchunk = 0 and all vectors in one batch: L - 1 left SpMMs, one v_b r, L - 1 right steps, J L output products; under hoh an H
+    product is 2 launches and a V product 3, of which the h_bulk pass is shared by the sets."""
+    r = ragged[hoh]
+    L = 17
+
+    def want(J):
+        return 4 * L - 1 + L * (1 + 2 * J) if hoh else 2 * L - 1 + J * L
+
+    r.c.rec.set_option("kubo_vbatch", 3)
+    try:
+        single(r.c, r.outs[0], L)
+        t1 = r.c.rec.timing()
+        assert t1["hop_launches"] == want(1) == ((7 * L - 1) if hoh else (3 * L - 1))      # the formula, on the single-response call
+        for J in (1, 2, 3):
+            multi(r.c, r.outs[:J], L)
+            t = r.c.rec.timing()
+            assert t["hop_launches"] == want(J), (J, t["hop_launches"], want(J))
+            assert t["total_ms"] > 0 and t["hop_ms"] > 0 and t["rest_ms"] > 0 and t["hop_ms"] + t["rest_ms"] <= t["total_ms"] * 1.001
+    finally:
+        r.c.rec.set_option("kubo_vbatch", 0)
+
+
+# ---- 9. refusals ----------------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("hoh", [False, True])
+def test_refusals_leave_the_handle_usable(hoh, ragged):
+    r = ragged[hoh]
+    c, L = r.c, 5
+    out = np.zeros((18, L, L, 3, NOUT_MAX + 1), np.complex128, order="F")
+
+    def refused(rc):
+        assert rc == _lib.ERR_ARG, rc
+        assert FN.encode() in c.last_error(), c.last_error()
+
+    refused(multi_call(c, r.outs, L, out, nout=0))
+    refused(multi_call(c, r.outs, L, out, nout=-1))
+    refused(multi_call(c, r.outs * 3, L, out, nout=NOUT_MAX + 1))
+    refused(multi_call(c, [], L, out, nout=2))                                  # v_out NULL
+    refused(multi_call(c, r.outs, L, out, v_b=None))
+    if hoh:
+        refused(multi_call(c, [(o[0], None) for o in r.outs], L, out))          # hoh without vo_out
+        refused(multi_call(c, r.outs, L, out, vo_b=None))
+    refused(multi_call(c, r.outs, 0, out))                                      # the single-response call's argument errors
+    refused(multi_call(c, r.outs, 100000, None))
+    keep = c.a
+    c.a = 0.0
+    try:
+        refused(multi_call(c, r.outs, L, out))
+    finally:
+        c.a = keep
+    bad = c.seeds.copy()
+    bad[1, 3] = c.rec.lattice.kk + 1
+    keep, c.seeds = c.seeds, bad
+    try:
+        refused(multi_call(c, r.outs, L, out))                                  # (an atom outside the lattice)
+    finally:
+        c.seeds = keep
+    mu = multi(c, r.outs, L)                                                    # a valid call succeeds afterwards
+    for j in range(3):
+        assert same_bits(mu[..., j], r.single(j, L))
+    full = multi(c, (r.outs * 3)[:NOUT_MAX], 2)                                 # ... and so does one with the largest nout
+    assert same_bits(full[..., NOUT_MAX - 1], full[..., (NOUT_MAX - 1) % 3])
+
+
+# ---- 10. the Python mirror --------------------------------------------------------------------------------------------------------------------
+
+def test_python_mirror_multi_and_conductivity():
+    import rslmtoasa_amd.recursion as Rm
+    z = load_golden("fccPt_kubo")
+    a, b = float(z["acheb"]), float(z["bcheb"])
+    half = a * float(np.float32(2) - np.float32(0.3)) / 2
+    ham = Hamiltonian(ee=z["ee"], lsham=z["lsham"], hoh=False)
+    lat = Lattice(nn=z["nn"], iz=z["iz"], irec=np.asarray(z["atlist"], np.int32), nmax=0, ntype=z["ee"].shape[3])
+    rec = Recursion(ham, lat, Control(lld=int(z["cond_ll"]), nsp=int(z["nsp"])), Energy(b - half, b + half), device=0)
+    orig = Rm.chebyshev_scaling
+    Rm.chebyshev_scaling = lambda e0, e1: (a, b)
+    try:
+        L = int(z["cond_ll"])
+        ops = [z["v_a"], z["v_b"]]
+        cond = Conductivity(rec)
+        ene = R.energy_mesh(b - half, b + half, 300)
+        per_response = []
+        for v in ops:
+            mu1 = rec.compute_moments_stochastic(v, z["v_b"], L, atlist=z["atlist"], diag=True)
+            integ = cond.integrand(None, ene)
+            per_response.append((mu1, integ, cond.tensor(integ, ene, per_vector=True)))
+        mu = rec.compute_moments_stochastic_multi(np.stack(ops, axis=-1), z["v_b"], L, atlist=z["atlist"])
+        nvec = mu.shape[3]
+        assert mu.shape == (18, L, L, 1, 2) and mu.dtype == np.complex128 and mu.flags.f_contiguous
+        assert rec.mu_diag_resident == (L, nvec * 2)
+        integ = cond.integrand(None, ene)
+        assert integ.shape == (18, ene.size, nvec * 2)
+        for j, (mu1, integ1, sigma1) in enumerate(per_response):
+            assert same_bits(mu[..., j], mu1)
+            mine = integ[:, :, j * nvec:(j + 1) * nvec]
+            assert same_bits(mine, integ1)
+            assert same_bits(cond.tensor(mine, ene, per_vector=True), sigma1)
+        assert rec.compute_moments_stochastic_multi(np.stack(ops, axis=-1), z["v_b"], L, atlist=z["atlist"], resident_only=True) is None
+        assert same_bits(cond.integrand(None, ene), integ)
+    finally:
+        Rm.chebyshev_scaling = orig
+        rec.close()
