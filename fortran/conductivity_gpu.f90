@@ -17,6 +17,10 @@
 !                                   same field; the integrand of all of them is one call, and the tail runs once per response -- the
 !                                   namelist's response writes the files above, further response <op> the same files as <op>_fort.123,
 !                                   <op>_cond_total*.out, <op>_<symbol>_cond*.out.
+!                                   RSREC_KUBO_FIELDS (recursion_gpu): likewise for further applied-field directions -- every (response,
+!                                   field) pair is one more set of the same integrand call and one more pass of the tail; the files of
+!                                   further field f carry 'E<f>_' before whatever the set is called otherwise (Ey_fort.123,
+!                                   Ey_cond_total.out, Ey_spin_cond_total.out, Ey_<symbol>_cond.out).
 ! Errors of the library become g_logger%fatal, the reference's error behaviour on this path.
 !------------------------------------------------------------------------------
 module conductivity_gpu_mod

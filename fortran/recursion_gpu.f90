@@ -51,6 +51,13 @@ module recursion_gpu_mod
       !> (the left vectors and the right recurrence are shared), and conductivity_gpu writes each further response's files with the
       !> prefix '<op>_'.  Implies kubo_diag.  Empty (the default): a run is what it was.
       character(len=256) :: kubo_responses = ''
+      !> RSREC_KUBO_FIELDS: further applied-field directions beside the namelist's v_beta, letters x, y, z separated by commas, e.g. 'y' or
+      !> 'y,z' (at most RSREC_KUBO_NIN_MAX - 1; no letter twice, none that is the namelist's own axis-aligned v_beta).
+      !> compute_moments_stochastic then forms the diagonal moments of every (response, field) pair -- linear_out and kubo_responses times
+      !> v_beta and these -- in one rsrec_kubo_moments_diag_tensor call (one left chunk, the fields' right recurrences as chains of one
+      !> launch), and conductivity_gpu writes the files of further field f with the prefix 'E<f>_' before whatever the set is called
+      !> otherwise (Ey_fort.123, Ey_spin_cond_total.out).  Implies kubo_diag.  Empty (the default): a run is what it was.
+      character(len=64) :: kubo_fields = ''
    contains
       procedure :: recur => gpu_recur
       procedure :: recur_b => gpu_recur_b
@@ -82,11 +89,13 @@ module recursion_gpu_mod
    integer, save :: g_cheb_resident = 0
    !> vectors and cond_ll of the orbital-diagonal Kubo moments compute_moments_stochastic left on the device (kubo_diag; 0: none)
    integer, save :: g_kubo_diag_nvec = 0, g_kubo_diag_ll = 0
-   !> the further responses (kubo_responses) of the last compute_moments_stochastic: how many, their operator names, and their diagonal
-   !> moments (18, cond_ll, cond_ll, vectors, response) on the host, for the case that the library kept nothing resident
+   !> the further sets (kubo_responses, kubo_fields) of the last compute_moments_stochastic: how many, their names (operator name; under a
+   !> further field f 'E<f>' or 'E<f>_<op>'), and their diagonal moments (18, cond_ll, cond_ll, vectors, set) on the host, for the case that
+   !> the library kept nothing resident.  Order: the library's, response fastest, the namelist's pair (not held here) first.
    integer, parameter :: kubo_nout_max = 8                     ! RSREC_KUBO_NOUT_MAX (include/rsrec.h)
+   integer, parameter :: kubo_nin_max = 4, kubo_nset_max = 16  ! RSREC_KUBO_NIN_MAX, RSREC_KUBO_NSET_MAX
    integer, save :: g_kubo_nresp = 0
-   character(len=32), save :: g_kubo_resp_op(kubo_nout_max - 1) = ''
+   character(len=40), save :: g_kubo_resp_op(kubo_nset_max - 1) = ''
    complex(rp), allocatable, save, target :: g_kubo_resp_diag(:, :, :, :, :)
 
 contains
@@ -108,6 +117,9 @@ contains
       call get_environment_variable('RSREC_KUBO_RESPONSES', obj%kubo_responses, n, stat)
       if (stat > 0 .or. n == 0) obj%kubo_responses = ''
       if (stat == -1) call g_logger%fatal('recursion_gpu: RSREC_KUBO_RESPONSES is longer than 256 characters', __FILE__, __LINE__)
+      call get_environment_variable('RSREC_KUBO_FIELDS', obj%kubo_fields, n, stat)
+      if (stat > 0 .or. n == 0) obj%kubo_fields = ''
+      if (stat == -1) call g_logger%fatal('recursion_gpu: RSREC_KUBO_FIELDS is longer than 64 characters', __FILE__, __LINE__)
    end function gpu_constructor
 
    !> Sites of this rank whose a_b / b2_b (as recur_b produced them) are also resident on the device; 0 if they are not.
@@ -124,16 +136,17 @@ contains
       n = merge(g_kubo_diag_nvec, 0, cond_ll == g_kubo_diag_ll)
    end function rsrec_gpu_kubo_diag_resident
 
-   !> Further responses (RSREC_KUBO_RESPONSES) whose moments the last compute_moments_stochastic formed beside linear_out's; 0: none
+   !> Further sets (RSREC_KUBO_RESPONSES, RSREC_KUBO_FIELDS) whose moments the last compute_moments_stochastic formed beside the namelist
+   !> pair's; 0: none
    function rsrec_gpu_kubo_responses() result(n)
       integer :: n
       n = g_kubo_nresp
    end function rsrec_gpu_kubo_responses
 
-   !> operator name of further response j = 1 .. rsrec_gpu_kubo_responses(): the prefix of its output files
+   !> name of further set j = 1 .. rsrec_gpu_kubo_responses(): the prefix of its output files
    function rsrec_gpu_kubo_response_name(j) result(name)
       integer, intent(in) :: j
-      character(len=32) :: name
+      character(len=40) :: name
       name = g_kubo_resp_op(j)
    end function rsrec_gpu_kubo_response_name
 
@@ -520,7 +533,7 @@ contains
    subroutine gpu_compute_moments_stochastic(this)
       use math_mod, only: pi, i_unit
       class(recursion_gpu), intent(inout) :: this
-      integer :: i, j, k, l, loop_over, nseed, cll, nresp
+      integer :: i, j, k, l, loop_over, nseed, cll, nresp, nfield, s
       integer(c_int) :: rc
       real(rp) :: a, b, rng
       integer(c_int), allocatable, target :: seeds(:, :)
@@ -528,6 +541,10 @@ contains
       complex(rp), allocatable, target :: vout(:, :, :, :, :), voout(:, :, :, :, :), mu_multi(:, :, :, :, :)
       character(len=32) :: resp_op(kubo_nout_max - 1)
       character(len=10) :: resp_pol(kubo_nout_max - 1), pol_alpha
+      complex(rp), allocatable, target :: vin(:, :, :, :, :), voin(:, :, :, :, :), mu_tensor(:, :, :, :, :, :)
+      character(len=1) :: field(kubo_nin_max - 1)
+      real(rp) :: v_beta(3)
+      type(c_ptr) :: p_voin
       complex(rp), allocatable, target :: coef(:, :), mu(:, :, :, :, :), va(:, :, :, :), vb(:, :, :, :), voa(:, :, :, :), vob(:, :, :, :)
       type(c_ptr) :: p_voa, p_vob
 
@@ -564,6 +581,24 @@ contains
          if (this%hamiltonian%hoh) voout(:, :, :, :, 1 + j) = this%hamiltonian%vo_a
       end do
       this%hamiltonian%pol_alpha = pol_alpha
+      ! the further fields likewise: the reference's own set-up with the unit vector as v_beta; v_b / vo_b are kept
+      call parse_kubo_fields(this%kubo_fields, this%hamiltonian%v_beta, nfield, field)
+      if ((1 + nfield)*(1 + nresp) > kubo_nset_max) &
+         call g_logger%fatal('RSREC_KUBO_FIELDS x RSREC_KUBO_RESPONSES: more than '//int2str(kubo_nset_max)//' (response, field) pairs', __FILE__, __LINE__)
+      v_beta = this%hamiltonian%v_beta
+      do i = 1, nfield
+         this%hamiltonian%v_beta = 0.0_rp
+         this%hamiltonian%v_beta(index('xyz', field(i))) = 1.0_rp
+         call this%setup_kubo_operators(this%control%linear_out, this%control%linear_in)
+         if (i == 1) then
+            allocate (vin(size(this%hamiltonian%v_b, 1), size(this%hamiltonian%v_b, 2), size(this%hamiltonian%v_b, 3), &
+                          size(this%hamiltonian%v_b, 4), nfield + 1))
+            if (this%hamiltonian%hoh) allocate (voin, mold=vin)
+         end if
+         vin(:, :, :, :, 1 + i) = this%hamiltonian%v_b
+         if (this%hamiltonian%hoh) voin(:, :, :, :, 1 + i) = this%hamiltonian%vo_b
+      end do
+      this%hamiltonian%v_beta = v_beta
       call this%setup_kubo_operators(this%control%linear_out, this%control%linear_in)
       allocate (seeds(nseed, loop_over), coef(nseed, loop_over))
       do i = 1, loop_over
@@ -590,6 +625,53 @@ contains
          p_vob = c_loc(vob)
       end if
       g_kubo_diag_nvec = 0
+      if (nfield > 0) then
+         ! the diagonal moments of (1 + nresp) x (1 + nfield) (response, field) pairs in one call: set (1, 1) -- the namelist's pair -- is
+         ! stored as under kubo_diag, the others are kept for conductivity_gpu in case the library keeps nothing resident
+         if (.not. allocated(vout)) allocate (vout(size(va, 1), size(va, 2), size(va, 3), size(va, 4), 1))
+         vout(:, :, :, :, 1) = va
+         vin(:, :, :, :, 1) = vb
+         p_voa = c_null_ptr; p_voin = c_null_ptr
+         if (this%hamiltonian%hoh) then
+            if (.not. allocated(voout)) allocate (voout, mold=vout)
+            voout(:, :, :, :, 1) = voa
+            voin(:, :, :, :, 1) = vob
+            p_voa = c_loc(voout)
+            p_voin = c_loc(voin)
+         end if
+         allocate (mu_tensor(18, cll, cll, loop_over, 1 + nresp, 1 + nfield))
+         call g_timer%start('kubo-tensor-gpu')
+         rc = rsrec_kubo_moments_diag_tensor(g_handle, int(1 + nfield, c_int), int(1 + nresp, c_int), int(loop_over, c_int), int(nseed, c_int), &
+                                             c_loc(seeds), c_loc(coef), int(cll, c_int), real(a, c_double), real(b, c_double), c_loc(vout), p_voa, &
+                                             c_loc(vin), p_voin, c_loc(mu_tensor))
+         call g_timer%stop('kubo-tensor-gpu')
+         call check(rc, 'rsrec_kubo_moments_diag_tensor')
+         this%mu_nm_stochastic = (0.0_rp, 0.0_rp)
+         do l = 1, 18
+            this%mu_nm_stochastic(l, l, :, :, :) = mu_tensor(l, :, :, :, 1, 1)
+         end do
+         if (allocated(g_kubo_resp_diag)) deallocate (g_kubo_resp_diag)
+         allocate (g_kubo_resp_diag(18, cll, cll, loop_over, (1 + nresp)*(1 + nfield) - 1))
+         s = 0
+         do i = 0, nfield                                        ! (the library's set order: the field outermost)
+            do j = 0, nresp
+               if (i == 0 .and. j == 0) cycle
+               s = s + 1
+               g_kubo_resp_diag(:, :, :, :, s) = mu_tensor(:, :, :, :, 1 + j, 1 + i)
+               if (i == 0) then
+                  g_kubo_resp_op(s) = resp_op(j)
+               else if (j == 0) then
+                  g_kubo_resp_op(s) = 'E'//field(i)
+               else
+                  g_kubo_resp_op(s) = 'E'//field(i)//'_'//trim(resp_op(j))
+               end if
+            end do
+         end do
+         g_kubo_nresp = s
+         g_kubo_diag_nvec = loop_over*(1 + s)
+         g_kubo_diag_ll = cll
+         return
+      end if
       if (nresp > 0) then
          ! the diagonal moments of 1 + nresp responses in one call: set 1 (linear_out) is stored as under kubo_diag, the others are kept for
          ! conductivity_gpu in case the library keeps nothing resident
@@ -676,6 +758,46 @@ contains
          if (any(op(1:n - 1) == op(n))) call g_logger%fatal('RSREC_KUBO_RESPONSES: operator "'//trim(op(n))//'" is named twice', __FILE__, __LINE__)
       end do
    end subroutine parse_kubo_responses
+
+   !> RSREC_KUBO_FIELDS taken apart: letters x, y, z separated by commas -> the further field directions.  Refused: an unknown letter, a
+   !> letter twice, a letter that is the namelist's own axis-aligned v_beta (the pair would be formed twice and its files written twice),
+   !> more than RSREC_KUBO_NIN_MAX - 1 letters.
+   subroutine parse_kubo_fields(list, v_beta, n, field)
+      character(len=*), intent(in) :: list
+      real(rp), intent(in) :: v_beta(3)
+      integer, intent(out) :: n
+      character(len=1), intent(out) :: field(:)
+      integer :: p0, p1, ax
+      real(rp) :: axis(3)
+      character(len=len(list)) :: item
+
+      n = 0
+      p0 = 1
+      do while (p0 <= len_trim(list))
+         p1 = index(list(p0:), ',')
+         if (p1 == 0) then
+            p1 = len_trim(list) + 1
+         else
+            p1 = p0 + p1 - 1
+         end if
+         item = adjustl(list(p0:p1 - 1))
+         p0 = p1 + 1
+         if (len_trim(item) == 0) cycle
+         ax = 0
+         if (len_trim(item) == 1) ax = index('xyz', item(1:1))
+         if (ax == 0) call g_logger%fatal('RSREC_KUBO_FIELDS: "'//trim(item)//'" is not one of x, y, z', __FILE__, __LINE__)
+         if (any(field(1:n) == item(1:1))) call g_logger%fatal('RSREC_KUBO_FIELDS: direction "'//item(1:1)//'" is named twice', __FILE__, __LINE__)
+         axis = 0.0_rp
+         axis(ax) = 1.0_rp
+         if (norm2(v_beta) > 0.0_rp) then
+            if (all(abs(v_beta/norm2(v_beta) - axis) < 1.0e-12_rp)) &
+               call g_logger%fatal('RSREC_KUBO_FIELDS: direction "'//item(1:1)//'" is the namelist''s own v_beta', __FILE__, __LINE__)
+         end if
+         if (n == size(field)) call g_logger%fatal('RSREC_KUBO_FIELDS: more than '//int2str(size(field))//' further directions', __FILE__, __LINE__)
+         n = n + 1
+         field(n) = item(1:1)
+      end do
+   end subroutine parse_kubo_fields
 
    !---------------------------------------------------------------------------
    !> Orbital moment from position-operator Chebyshev moments (replaces recursion.f90:2834-3049).  The reference loops over all kk

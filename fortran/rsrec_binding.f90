@@ -324,6 +324,19 @@ module rsrec_binding
          integer(c_int) :: rc
       end function
 
+      ! the same for nout output operators and nin input operators v_in / vo_in (18,18,nslots,ntype,nin): mu_diag
+      ! (18,cond_ll,cond_ll,nvec,nout,nin), set (j, i) = rsrec_kubo_moments_diag with (v_a, v_b) = (v_out(:,:,:,:,j), v_in(:,:,:,:,i));
+      ! resident as nvec*nout*nin vectors, the input outermost
+      function rsrec_kubo_moments_diag_tensor(handle, nin, nout, nvec, nseed, seed_atoms, seed_coef, cond_ll, a, b, v_out, vo_out, v_in, vo_in, &
+                                              mu_diag) bind(C, name='rsrec_kubo_moments_diag_tensor') result(rc)
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: handle
+         integer(c_int), value :: nin, nout, nvec, nseed, cond_ll
+         real(c_double), value :: a, b
+         type(c_ptr), value :: seed_atoms, seed_coef, v_out, vo_out, v_in, vo_in, mu_diag
+         integer(c_int) :: rc
+      end function
+
       function rsrec_apply_operator(handle, vel, v_op, vo_op, psi_in, psi_out, a, b) bind(C, name='rsrec_apply_operator') result(rc)
          import :: c_int, c_ptr, c_double
          type(c_ptr), value :: handle

@@ -286,6 +286,33 @@ int rsrec_kubo_moments_diag_multi(rsrec_t *h, int nout, int nvec, int nseed, con
                                   int cond_ll, double a, double b, const double *v_out, const double *vo_out, const double *v_b,
                                   const double *vo_b, double *mu_diag);
 
+/* The diagonal moments of several responses to several applied fields (sigma_xx beside sigma_xy, a Hall angle, the 3 x 3 tensor of a
+ * response: the reference's example families in which v_alpha and v_beta take x, y and z in turn).  Set (j, i) is what
+ * rsrec_kubo_moments_diag returns for (v_a, v_b) = (v_out(:,:,:,:,j), v_in(:,:,:,:,i)) and the matching vo operators, bit for bit:
+ *   mu(l,n,m,v,j,i) = sum_k [T_{m-1}(H~) r_v]_k^H [v_out_j T_{n-1}(H~) v_in_i r_v]_k  on the diagonal.
+ * The left vectors are formed once for all sets; the right recurrences of the nin inputs advance together as chains of one launch (chain
+ * i nb + c: vector c of input i; at most 8 / nin vectors advance together); every output operator is applied once per order to all inputs'
+ * chains.  Per order 1 + nin + nin nout whole-lattice products in 2 + nout launches (hoh: 5 + 2 nout), against nin (2 + nout) for nin multi
+ * calls.  With kubo_lchunk = 0 and one batch the call makes 2 L - 2 + nin + nout L SpMM launches (hoh: 4 L - 3 + 2 nin + L (1 + 2 nout)).
+ *   nin     : 1 .. RSREC_KUBO_NIN_MAX;  nout : 1 .. RSREC_KUBO_NOUT_MAX;  nin * nout <= RSREC_KUBO_NSET_MAX
+ *   v_out, vo_out : complex (18,18,nslots,ntype,nout);  v_in, vo_in : complex (18,18,nslots,ntype,nin);  vo_*: hoh only, else NULL
+ *   mu_diag : complex (18,cond_ll,cond_ll,nvec,nout,nin) out, host or device (detected) or NULL.  The input index is outermost: slice
+ *             [..., i] is what rsrec_kubo_moments_diag_multi returns for v_b = v_in(:,:,:,:,i), and a single set's slice is what
+ *             rsrec_kubo_integrand_diag and rsrec_kubo_conductivity take.
+ * The moments of all nvec * nout * nin (vector, set) pairs stay on the handle in that layout when they fit (the rules of
+ * rsrec_kubo_moments_diag): rsrec_kubo_integrand_diag(h, nvec * nout * nin, cond_ll, NULL, ...) then returns (18,nen,nvec,nout,nin).
+ * Option kubo_setgroup (this call only): the contraction stages one tile of left vectors for up to that many sets of a vector
+ * (k_kubo_gram_diag_sets) -- 1: every set by itself with k_kubo_gram_diag, 2 / 3: groups of at most that width (larger values: 3), 0: the
+ * default (2: measured 0.75 of the per-set contraction at cond_ll = 500; groups of 3 measured no faster than 1).  A set's bits depend neither on it, nor on kubo_vbatch, nor on the other sets of the call or their order.
+ * Errors: RSREC_ERR_ARG with a message for nin, nout or nin * nout out of range, a NULL v_out or v_in, hoh without vo_out or vo_in, and the
+ * argument errors of rsrec_kubo_moments_diag; the handle stays usable.  Run-to-run bit-identical.  rsrec_get_timing as
+ * rsrec_kubo_moments_diag_multi. */
+#define RSREC_KUBO_NIN_MAX 4
+#define RSREC_KUBO_NSET_MAX 16
+int rsrec_kubo_moments_diag_tensor(rsrec_t *h, int nin, int nout, int nvec, int nseed, const int32_t *seed_atoms, const double *seed_coef,
+                                   int cond_ll, double a, double b, const double *v_out, const double *vo_out, const double *v_in,
+                                   const double *vo_in, double *mu_diag);
+
 /* The Kubo-Bastin conductivity integrand of calculate_gamma_nm + calculate_conductivity_tensor (conductivity.f90:158-268), without the
  * (nen, cond_ll, cond_ll) array gamma_nm (the sum factorises into two tables of nen x cond_ll, kernels_cond.hpp):
  *   integrand(l, i, v) = factor sum_{n,m} gamma_nm(i, n, m) mu_nm(l, l, n, m, v),   factor = 16 / (pi (energy_max - energy_min)^2)
@@ -534,7 +561,9 @@ int rsrec_comm_destroy(rsrec_t *h);
  *   "orth_oop"   1 = the orthogonalisation pass writes u_{n+1} into a third u vector instead of over u_{n-1} (faster on the HBM, one more work vector) [1]
  *   "sat_pct"    a chain whose region holds at least this share (per cent) of the lattice runs on the list of ALL atoms instead of its own [100]
  *   "kubo_lchunk" rsrec_kubo_moments / _diag: left vectors held on the device at a time [0 = as many as fit];  "kubo_vbatch" vectors of a call advanced
- *                together as the chains of every launch [0 = up to 8, as many as fit beside a whole left matrix each] */
+ *                together as the chains of every launch [0 = up to 8, as many as fit beside a whole left matrix each]
+ *   "kubo_setgroup" rsrec_kubo_moments_diag_tensor: sets of a vector contracted against one staged tile of left vectors; 1 = every set by itself,
+ *                2 / 3 = groups of at most that width [0 = 2] */
 int rsrec_set_option(rsrec_t *h, const char *key, long value);
 /* Timing of the last recursion call, measured with HIP events on the engine's own stream:
  *   out[0] total device ms, out[1] ms in the H|psi> kernels, out[2] number of H|psi> launches,

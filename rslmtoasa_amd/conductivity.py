@@ -23,7 +23,8 @@ class Conductivity:
         ``mu_nm``: complex (18, 18, cond_ll, cond_ll, nvec) in the reference's layout (recursion%mu_nm_stochastic) -- a numpy array
         or a contiguous complex128 torch tensor on the GPU (Fortran order: the tensor's memory must be the reference's array).
         Also the orbital-diagonal moments alone, complex (18, cond_ll, cond_ll[, nvec]) as ``compute_moments_stochastic(diag=True)``
-        returns them, or ``None``: the moments that call left resident on the device (``rsrec_kubo_integrand_diag``).
+        returns them, or ``None``: the moments that call left resident on the device (``rsrec_kubo_integrand_diag``) -- after
+        ``compute_moments_stochastic_multi`` / ``_tensor`` those of all sets, (18, nen, nvec * nout[ * nin]), set outermost.
         ``diag``: True / False says which of the two ``mu_nm`` is.  Left at None the shape decides; the one shape that is both --
         (18, 18, 18, 18): one vector's full moments at cond_ll = 18, or the diagonals of 18 vectors at cond_ll = 18 -- then means the
         full moments, as it always has: pass diag=True for the diagonals.

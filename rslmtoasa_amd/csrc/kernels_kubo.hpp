@@ -218,6 +218,123 @@ __global__ __launch_bounds__(256, 3) void k_kubo_gram_diag(const double* __restr
     }
 }
 
+// ---- one left tile, several sets (rsrec_kubo_moments_diag_tensor) -----------------------------------------------------------------------
+// All sets (output operator j, input operator i) of a vector are contracted against the SAME left vectors, and k_kubo_gram_diag is bound
+// by reading its slabs.  k_kubo_gram_diag_sets<S> is that kernel with S right operands: a workgroup stages the k-step slab of its 16 left
+// vectors once and the slabs of the 16 right vectors of S sets -- (1 + S) slabs per task instead of 2 S -- keeps S sets of accumulators
+// and writes S partial images (image s at part + s * image), which k_kubo_gram_diag_reduce sums per set as ever.
+// Bits: the task split (ksplit, per, slice ownership, tiles), the LDS image of a slab, the operand a lane reads and the four MFMAs per
+// (column, k-step) are k_kubo_gram_diag's, per set; the sets only share the `a` operand.  So element (m, n, c) of a set is accumulated over
+// the same k-steps in the same order by the same instructions as there, whatever the other sets of the group are.
+// Staging: (1 + S) x 16 vectors of 72 slots; as there 8 lanes own a vector and read 9 slots each, now in two passes (vectors sv and
+// sv + 32; S = 2 has 48 vectors: the second pass is for the lanes of the first 16 only).  LDS: (1 + S) x 19 456 B.
+// Registers (the compiler's resource-usage remarks for gfx950): a set's accumulators are 80 registers (5 columns x re, im x double4), the staged
+// slots 36 per pass.  S = 2: 256 VGPRs, no scratch, two workgroups per CU.  S = 3 (240 accumulator registers) does not fit the 256 of two
+// waves per SIMD -- 444 B of scratch per lane under __launch_bounds__(256, 2) -- so it is built for ONE workgroup per CU: 148 VGPRs + 240
+// AGPRs, no scratch.
+template <int S>
+struct KuboRights { const double* r[S]; };               // the right operands of a group: same vector stride, same number of vectors
+
+template <int S>
+__global__ __launch_bounds__(256, S == 3 ? 1 : 2) void k_kubo_gram_diag_sets(const double* __restrict__ L, size_t ls, int mvec, KuboRights<S> R, size_t rs, int nvec,
+                                                                int ksteps_total, int ksplit, double2* __restrict__ part, size_t image /*double2 between two sets' partials*/,
+                                                                int nbm, int nbn) {
+    typedef double kg_d2 __attribute__((ext_vector_type(2)));
+    static_assert(S == 2 || S == 3, "two passes of 32 staged vectors");
+    constexpr int NV = (1 + S) * KD_T;                         // staged vectors: left, then the sets' right ones
+    __shared__ kg_d2 slab[(1 + S) * 4 * KD_RS];                // left image, then one right image per set
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int l15 = lane & 15, l4 = lane >> 4;
+    const int ntask_mn = nbm * nbn;
+    const int xcd = blockIdx.x & 7, t = (int)(blockIdx.x >> 3);
+    if (t >= ntask_mn * (ksplit >> 3)) return;                 // (whole workgroup: no barrier is left waiting)
+    const int ks = xcd + 8 * (t / ntask_mn), mn = t % ntask_mn;
+    const int bm = mn / nbn, bn = mn - bm * nbn;
+    const int per = (ksteps_total + ksplit - 1) / ksplit;
+    const int s0 = ks * per, s1 = min(ksteps_total, s0 + per);
+    // staging: lanes 8 v' .. 8 v' + 7 own vectors v' and v' + 32 of the NV and read their 72 slots j, j + 8, ..., j + 64
+    const int sv = threadIdx.x >> 3, sj = threadIdx.x & 7;
+    const bool two = sv + 32 < NV;                             // (S = 3: every lane; S = 2: the lanes of vectors 0-15)
+    auto vector_of = [&](int v) -> const double* {
+        if (v < KD_T) return L + (size_t)min(bm * KD_T + v, mvec - 1) * ls;
+        const double* base = R.r[0];
+#pragma unroll
+        for (int q = 1; q < S; ++q) if ((v - KD_T) / KD_T == q) base = R.r[q];
+        return base + (size_t)min(bn * KD_T + ((v - KD_T) & (KD_T - 1)), nvec - 1) * rs;
+    };
+    const double* src0 = vector_of(sv) + (size_t)144 * s0 + 2 * sj;
+    const double* src1 = vector_of(two ? sv + 32 : sv) + (size_t)144 * s0 + 2 * sj;
+    int dst[KD_LOADS];                                         // of the first pass; the second lies two images further on
+#pragma unroll
+    for (int i = 0; i < KD_LOADS; ++i) {
+        const int q = sj + 8 * i, r = q / NB, c = q - NB * r;
+        dst[i] = (sv / KD_T) * 4 * KD_RS + r * KD_RS + (sv & (KD_T - 1)) * KD_VS + c;
+    }
+    kg_d2 nxt0[KD_LOADS], nxt1[KD_LOADS];
+    auto fetch = [&]() {
+#pragma unroll
+        for (int i = 0; i < KD_LOADS; ++i) nxt0[i] = *reinterpret_cast<const kg_d2*>(src0 + 16 * i);
+        if (two) {
+#pragma unroll
+            for (int i = 0; i < KD_LOADS; ++i) nxt1[i] = *reinterpret_cast<const kg_d2*>(src1 + 16 * i);
+        }
+        src0 += 144; src1 += 144;
+    };
+    auto stage = [&]() {
+#pragma unroll
+        for (int i = 0; i < KD_LOADS; ++i) slab[dst[i]] = nxt0[i];
+        if (two) {
+#pragma unroll
+            for (int i = 0; i < KD_LOADS; ++i) slab[dst[i] + 2 * 4 * KD_RS] = nxt1[i];
+        }
+    };
+    constexpr int KD_C = (NB + 3) / 4;                         // columns per wave: 5 (waves 2, 3: the last one is skipped)
+    double4_t cre[S][KD_C], cim[S][KD_C];
+#pragma unroll
+    for (int g = 0; g < S; ++g)
+#pragma unroll
+        for (int q = 0; q < KD_C; ++q) { cre[g][q] = (double4_t){0, 0, 0, 0}; cim[g][q] = (double4_t){0, 0, 0, 0}; }
+    const int ncol = wave < NB - 4 * (KD_C - 1) ? KD_C : KD_C - 1;
+    const int rd = l4 * KD_RS + l15 * KD_VS + wave;
+    if (s0 < s1) fetch();
+#pragma unroll 1
+    for (int s = s0; s < s1; ++s) {
+        stage();
+        __syncthreads();
+        if (s + 1 < s1) fetch();
+#pragma unroll
+        for (int q = 0; q < KD_C; ++q) {
+            if (q == KD_C - 1 && ncol < KD_C) break;           // (wave-uniform)
+            const kg_d2 a = slab[rd + 4 * q];
+            const double ar = a[0], ai = a[1], nai = -ai;
+#pragma unroll
+            for (int g = 0; g < S; ++g) {
+                const kg_d2 b = slab[(1 + g) * 4 * KD_RS + rd + 4 * q];
+                cre[g][q] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, b[0], cre[g][q], 0, 0, 0);
+                cim[g][q] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, b[1], cim[g][q], 0, 0, 0);
+                cre[g][q] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, b[1], cre[g][q], 0, 0, 0);
+                cim[g][q] = __builtin_amdgcn_mfma_f64_16x16x4f64(nai, b[0], cim[g][q], 0, 0, 0);
+            }
+        }
+        __syncthreads();
+    }
+    // D register rr of lane (l15, l4): left vector l4 + 4 rr, right vector l15 of the tile; one partial image per set
+    const size_t ldp = (size_t)nbn * KD_T;
+#pragma unroll
+    for (int g = 0; g < S; ++g) {
+        double2* P = part + (size_t)g * image + (size_t)ks * ((size_t)nbm * KD_T) * ldp * NB;
+#pragma unroll
+        for (int q = 0; q < KD_C; ++q) {
+            if (q == KD_C - 1 && ncol < KD_C) break;
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+                const int i = bm * KD_T + l4 + 4 * rr, j = bn * KD_T + l15;
+                P[((size_t)i * ldp + j) * NB + wave + 4 * q] = make_double2(cre[g][q][rr], cim[g][q][rr]);
+            }
+        }
+    }
+}
+
 // sum of the slices' partials in slice order -> mu_diag(c, n0 + n, m0 + m): c fastest on both sides, one thread per element
 __global__ __launch_bounds__(256) void k_kubo_gram_diag_reduce(const double2* __restrict__ part, int ksplit, int prow /*padded left vectors of a slice*/, int pcol, int mvec, int nvec,
                                                               double2* __restrict__ mu /*this vector's (18,cond_ll,cond_ll)*/, int cond_ll, int m0, int n0) {

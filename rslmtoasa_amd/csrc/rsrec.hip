@@ -117,7 +117,7 @@ struct rsrec_handle {
     long n_asm_calls = 0, n_ldos_calls = 0, n_recursion_calls = 0;   // life-time counters of the handle (RSREC_REPORT)
     Spmm5Operator s5_la; int s5_la_ok = 0;   // operator tables of local-axis runs: H without the on-site l.s term, which comes per chain
     DevBuf d_la_extra, d_rot;               // per-chain on-site fragments; the rotations of all chains of the call (k_rotate_coef)
-    Spmm5Operator kubo_op[RSREC_KUBO_NOUT_MAX], kubo_op_b, kubo_hbulk;   // output operators (v_a: [0]) / v_b tables of the last rsrec_kubo_moments call
+    Spmm5Operator kubo_op[RSREC_KUBO_NOUT_MAX], kubo_op_b[RSREC_KUBO_NIN_MAX], kubo_hbulk;   // output operators (v_a: [0]) / input operators (v_b: [0]) of the last rsrec_kubo_moments call
     Spmm5Operator orb_plain;                // h as ham_vec_matmul applies it when hoh is set (rsrec_orbital_moments, rsrec_apply_operator vel = 2)
     // work
     DevBuf d_green_in, d_green_out;   // inputs and outputs of the calls on caller arrays: the Green stages (green_pipeline), rsrec_terminator,
@@ -145,8 +145,9 @@ struct rsrec_handle {
     long opt_s5_host_emit = 0;   // 1: swizzle k_spmm5's operator streams on the host (round-2 path) instead of assembling them on the device
     long opt_kubo_lchunk = 0;    // rsrec_kubo_moments: left vectors held at a time (0: as many as fit)
     long opt_kubo_vbatch = 0;    // rsrec_kubo_moments: random vectors advanced together as the chains of one launch (0: up to 8, as many as fit beside a whole left matrix)
+    long opt_kubo_setgroup = 0;  // rsrec_kubo_moments_diag_tensor: sets of a vector contracted against one staged left tile (k_kubo_gram_diag_sets): 0 default (2), 1 every set by itself (k_kubo_gram_diag), 2 / 3 groups of at most that width
     int n_kubo_left_chunks = 0;
-    int kubo_diag_nvec = 0, kubo_diag_ll = 0;   // rsrec_kubo_moments_diag / _multi: the call whose diagonal moments lie in d_kubo[4] (0: nothing resident; _multi: nvec * nout)
+    int kubo_diag_nvec = 0, kubo_diag_ll = 0;   // rsrec_kubo_moments_diag / _multi / _tensor: the call whose diagonal moments lie in d_kubo[4] (0: nothing resident; _multi: nvec * nout; _tensor: nvec * nout * nin)
     long opt_orth3 = 1;          // k_mfma_orth3: 1 one 512-register wave per SIMD (tables in registers), 2 two waves per SIMD (tables in LDS)
     long opt_graph = 1;          // level loop of small batches as one HIP graph: 0 never, 1 calls of up to 8 chains, 2 every single-batch call
     // A_n Gram folded into k_spmm5's epilogue (kernels_spmm5.hpp, S5Gram): a chain folds at a level when its region there has at least this
@@ -233,6 +234,7 @@ const OptionEntry OPTIONS[] = {
     {"sat_pct", &rsrec_handle::opt_sat_pct},
     {"kubo_lchunk", &rsrec_handle::opt_kubo_lchunk},
     {"kubo_vbatch", &rsrec_handle::opt_kubo_vbatch},
+    {"kubo_setgroup", &rsrec_handle::opt_kubo_setgroup},
     {"s5_host_emit", &rsrec_handle::opt_s5_host_emit},
     {"s5_octet", &rsrec_handle::opt_s5_octet},
     {"s5_spin_xcd", &rsrec_handle::opt_s5_spin_xcd},
@@ -3418,7 +3420,9 @@ int whole_lattice_end(rsrec_t* h, WholeLatticeCall& W, bool rest_is_own_spans = 
 
 // The device memory of a rsrec_kubo_moments call, decided before anything is reserved: 11 work vectors, `lchunk` left vectors, one block of
 // right vectors per output operator (`nout`; 1 but for rsrec_kubo_moments_diag_multi), the slices' partial blocks, `nout` moment images of
-// the vectors in flight -- the five buffers of d_kubo, in that order.
+// the vectors in flight -- the five buffers of d_kubo, in that order.  rsrec_kubo_moments_diag_tensor (`nin` input operators): the right
+// recurrences of all inputs advance as nin x nbv chains of one launch, so the work vectors and the right slots are nin times as wide
+// (the left slots are not), there are nin x nout sets of moments, and the partial buffer holds one image per set of a contraction group.
 // The left matrix is held in chunks of `lchunk` vectors (all of them if they fit: cond_ll x kk x 5184 B is 21 GB for cond_ll = 500
 // on 8 000 atoms, 252 GB on 10^5): each chunk continues the left recurrence where the previous one stopped and is contracted
 // with ALL right vectors, so the right recurrence (2 of the 3 SpMMs per moment order) is repeated once per chunk.
@@ -3427,11 +3431,13 @@ int whole_lattice_end(rsrec_t* h, WholeLatticeCall& W, bool rest_is_own_spans = 
 // every launch (chain c of a buffer slot lies c vectors behind chain 0, exactly like the sites of a recursion batch); each keeps its own
 // left / right matrices and is contracted by itself.  A whole left matrix per vector goes first: vectors are added only while it fits.
 struct KuboPlan {
-    int cond_ll = 0, n_cu = 0, nout = 1;     // nout: output operators (sets) of the call, each with right slots and moments of its own
+    int cond_ll = 0, n_cu = 0, nout = 1;     // nout: output operators of the call, each with right slots of its own
+    int nin = 1, setgroup = 1;               // input operators (sets: nin x nout, input outermost); sets of a vector contracted per k_kubo_gram_diag_sets launch (1: k_kubo_gram_diag)
     bool diag = false, resident = false;     // rsrec_kubo_moments_diag: 18 instead of 324 elements per (n, m); the moments of ALL vectors of the call fit d_kubo[4]
     int nchunk = 0, lchunk = 0, nbv = 0;     // right vectors per contraction; left vectors held at a time; vectors in flight
     int ksteps_total = 0, nbn_max = 0;       // k-steps of 4 rows (the last one may end inside the zero block); column blocks of a full contraction
-    size_t velems = 0, sstride = 0;          // doubles of one vector; between two slots of a buffer (nbv chains each)
+    size_t velems = 0, sstride = 0, lstride = 0;   // doubles of one vector; between two work vectors / right slots (nin x nbv chains each); between two left slots (nbv chains)
+    size_t part_image = 0;                   // double2 of one set's slice partials (diag)
     size_t bytes[5] = {0, 0, 0, 0, 0};       // of the five buffers
     // slices of the row index per contraction: enough wave tasks for a few rounds of the device, at least 64 k-steps per task
     int ksplit_for(int lc) const {
@@ -3452,13 +3458,19 @@ struct KuboPlan {
     double2 *part = nullptr, *mu = nullptr;
     enum { PSIREF = 0, Y = 1 /* .. 3: the right recurrence */, L0 = 4, HPS = 6, P1 = 7, P2 = 8, L1 = 9 };   // work vectors (L0, L1: T_{m0-2} r, T_{m0-1} r, the left recurrence across a chunk border)
     double* vec(int v) const { return work + (size_t)v * sstride; }
-    double* Lslot(int q) const { return Lm + (size_t)q * sstride; }
-    double* Rslot(int j, int q) const { return Rm + ((size_t)j * nchunk + q) * sstride; }      // slot q of set j
+    double* Lslot(int q) const { return Lm + (size_t)q * lstride; }
+    double* Rslot(int j, int q) const { return Rm + ((size_t)j * nchunk + q) * sstride; }      // slot q of output operator j (all inputs' chains)
 };
 
-int kubo_plan(rsrec_t* h, int nout, int nvec, int cond_ll, bool diag, KuboPlan& P) {
+constexpr int KUBO_CHAINS_MAX = 8;           // chains of a whole-lattice launch of the Kubo calls
+constexpr int KUBO_SETGROUP_MAX = 3;         // widest k_kubo_gram_diag_sets built
+constexpr int KUBO_SETGROUP_DEFAULT = 2;     // what kubo_setgroup = 0 means: pairs measured 0.75 of the per-set contraction at cond_ll = 500, triples (one workgroup per CU) 1.01
+
+int kubo_plan(rsrec_t* h, int nin, int nout, int setgroup, int nvec, int cond_ll, bool diag, KuboPlan& P) {
     const int kk = h->kk;
-    P.diag = diag; P.nout = nout;
+    P.diag = diag; P.nout = nout; P.nin = nin;
+    const int nset = nin * nout;
+    P.setgroup = std::max(1, std::min({setgroup, KUBO_SETGROUP_MAX, nset}));
     P.cond_ll = cond_ll; P.n_cu = h->n_cu; P.velems = (size_t)(kk + 1) * BLD;
     P.nchunk = std::min(cond_ll, 64);
     size_t free_b = 0, total_b = 0;
@@ -3473,19 +3485,20 @@ int kubo_plan(rsrec_t* h, int nout, int nvec, int cond_ll, bool diag, KuboPlan& 
     auto part_bytes = [&](int lc) {
         if (diag) return (double)P.ksplit_for(lc) * ((lc + KD_T - 1) / KD_T) * KD_T * (double)P.nbn_max * KD_T * NB * 16.0;
         return (double)P.ksplit_for(lc) * ((lc * NB + KG_BLK - 1) / KG_BLK) * KG_BLK * (double)P.nbn_max * KG_BLK * 16.0; };
-    auto need_for = [&](int lc, int nv) { return (11.0 + lc + (double)nout * P.nchunk) * nv * P.velems * 8 + part_bytes(lc) + (double)nv * nout * mu_bytes; };
+    auto need_for = [&](int lc, int nv) { return (11.0 * nin + lc + (double)nset * P.nchunk) * nv * P.velems * 8 + P.setgroup * part_bytes(lc) + (double)nv * nset * mu_bytes; };
     int lchunk = cond_ll;
     if (h->opt_kubo_lchunk > 0) lchunk = (int)std::min<long>(cond_ll, h->opt_kubo_lchunk);
-    int nbv = (int)std::min<long>(nvec, h->opt_kubo_vbatch > 0 ? h->opt_kubo_vbatch : 8);
+    int nbv = (int)std::min<long>({(long)nvec, h->opt_kubo_vbatch > 0 ? h->opt_kubo_vbatch : KUBO_CHAINS_MAX, (long)(KUBO_CHAINS_MAX / nin)});   // nin x nbv chains per launch
     while (nbv > 1 && need_for(lchunk, nbv) > budget) --nbv;
     while (lchunk > 1 && need_for(lchunk, nbv) > budget) lchunk = (lchunk + 1) / 2;
     if (need_for(lchunk, nbv) > budget)
         return fail(h, RSREC_ERR_DEVICE, "rsrec_kubo_moments: %.1f GB needed for one left vector at a time on %d atoms, %.1f GB free", need_for(1, 1) * 1e-9, kk, free_b * 1e-9);
-    P.lchunk = lchunk; P.nbv = nbv; P.sstride = (size_t)nbv * P.velems;
-    P.bytes[0] = 11 * P.sstride * 8; P.bytes[1] = (size_t)lchunk * P.sstride * 8; P.bytes[2] = (size_t)nout * P.nchunk * P.sstride * 8;
+    P.lchunk = lchunk; P.nbv = nbv; P.lstride = (size_t)nbv * P.velems; P.sstride = (size_t)nin * P.lstride;
+    P.bytes[0] = 11 * P.sstride * 8; P.bytes[1] = (size_t)lchunk * P.lstride * 8; P.bytes[2] = (size_t)nout * P.nchunk * P.sstride * 8;
     // the diagonal moments of the whole call stay on the handle if they fit beside everything else; lchunk and nbv do not depend on it
-    P.resident = diag && need_for(lchunk, nbv) + (double)(nvec - nbv) * nout * mu_bytes <= budget;
-    P.bytes[3] = (size_t)part_bytes(lchunk); P.bytes[4] = (size_t)(P.resident ? nvec : nbv) * nout * (size_t)mu_bytes;
+    P.resident = diag && need_for(lchunk, nbv) + (double)(nvec - nbv) * nset * mu_bytes <= budget;
+    P.part_image = (size_t)part_bytes(lchunk) / 16;
+    P.bytes[3] = P.setgroup * P.part_image * 16; P.bytes[4] = (size_t)(P.resident ? nvec : nbv) * nset * (size_t)mu_bytes;
     return RSREC_OK;
 }
 
@@ -3553,14 +3566,10 @@ int kubo_left_chunk(WholeLatticeCall& W, const KuboPlan& P, int m0, double a, do
     return RSREC_OK;
 }
 
-// The same for the orbital-diagonal moments alone: per column c the Gram matrix of the chunk's left and the block's right vectors, tiles of
-// 16 x 16 vectors x all 18 columns x `ksplit` slices of (k,r), one workgroup each (k_kubo_gram_diag), then k_kubo_gram_diag_reduce.
-// mu_off: where the batch's first vector lies in P.mu (resident moments of the whole call; the images of set j), in vectors.
-int kubo_contract_diag(WholeLatticeCall& W, const KuboPlan& P, int j, int m0, int n, size_t mu_off) {
-    rsrec_t* h = W.h;
-    const int nl = n % P.nchunk, n0 = n - nl, nv = nl + 1, mv = std::min(P.lchunk, P.cond_ll - m0);
-    const int nbm = (mv + KD_T - 1) / KD_T, nbn = (nv + KD_T - 1) / KD_T;
-    // slices: as kubo_contract, for 3 workgroups per CU
+// Slices of a diagonal contraction of nbm x nbn tiles: the multiple of 8 (<= what the partial buffer was sized for, >= 64 k-steps per task)
+// that fills whole rounds of 3 workgroups per CU best.  k_kubo_gram_diag and k_kubo_gram_diag_sets both take it from here: the slice
+// partition decides the order of every element's sum, so a set's bits are the same whichever kernel contracts it.
+int kubo_diag_ksplit(const rsrec_t* h, const KuboPlan& P, int nbm, int nbn) {
     int ksplit = 8;
     const long slots = 3L * h->n_cu, cap = std::min<long>(P.ksplit_for(P.lchunk), std::max(8, P.ksteps_total / 64 / 8 * 8));
     double best = 0.0;
@@ -3569,13 +3578,34 @@ int kubo_contract_diag(WholeLatticeCall& W, const KuboPlan& P, int j, int m0, in
         const double eff = (double)tasks / (double)(rounds * slots) * (rounds >= 3 ? 1.0 : 0.9);
         if (eff > best + 1e-9) { best = eff; ksplit = (int)c; }
     }
+    return ksplit;
+}
+
+// The same for the orbital-diagonal moments alone: per column c the Gram matrix of the chunk's left and the block's right vectors, tiles of
+// 16 x 16 vectors x all 18 columns x `ksplit` slices of (k,r), one workgroup each (k_kubo_gram_diag), then k_kubo_gram_diag_reduce.
+// Sets s_lo .. s_lo + ns - 1 of the call (set s = input s / nout, output s % nout: the right vectors are the chains of input i in the slots
+// of output j) for the `nb` vectors of the batch; ns = 1: k_kubo_gram_diag, 2 or 3: k_kubo_gram_diag_sets, one partial image per set.
+// mu_off(s): where the batch's first vector of set s lies in P.mu (resident moments of the whole call; the images of the sets), in vectors.
+template <class MuOff>
+int kubo_contract_diag(WholeLatticeCall& W, const KuboPlan& P, int nb, int s_lo, int ns, int m0, int n, MuOff&& mu_off) {
+    rsrec_t* h = W.h;
+    const int nl = n % P.nchunk, n0 = n - nl, nv = nl + 1, mv = std::min(P.lchunk, P.cond_ll - m0);
+    const int nbm = (mv + KD_T - 1) / KD_T, nbn = (nv + KD_T - 1) / KD_T;
+    const int ksplit = kubo_diag_ksplit(h, P, nbm, nbn);
+    if (ns < 1 || ns > P.setgroup || (size_t)ksplit * nbm * KD_T * nbn * KD_T * NB > P.part_image)
+        return fail(h, RSREC_ERR_DEVICE, "rsrec_kubo_moments: contraction group outside the planned partial buffer");
     HIPCK(h, hipGetLastError());
     hipEvent_t g0 = next_event(h);
     const unsigned wgs = 8u * (unsigned)((long)nbm * nbn * (ksplit / 8));
     const size_t mu_vec = (size_t)P.cond_ll * P.cond_ll * NB;
-    for (int c = 0; c < W.SD.nchains; ++c) {
-        k_kubo_gram_diag<<<wgs, 256, 0, h->stream>>>(P.Lm + (size_t)c * P.velems, P.sstride, mv, P.Rslot(j, 0) + (size_t)c * P.velems, P.sstride, nv, P.ksteps_total, ksplit, P.part, nbm, nbn);
-        k_kubo_gram_diag_reduce<<<(int)std::min<long>(4096, ((long)mv * nv * NB + 255) / 256), 256, 0, h->stream>>>(P.part, ksplit, nbm * KD_T, nbn * KD_T, mv, nv, P.mu + (mu_off + c) * mu_vec, P.cond_ll, m0, n0);
+    for (int c = 0; c < nb; ++c) {
+        const double* L = P.Lm + (size_t)c * P.velems;
+        auto right = [&](int s) { return P.Rslot(s % P.nout, 0) + ((size_t)(s / P.nout) * nb + c) * P.velems; };
+        if (ns == 1) k_kubo_gram_diag<<<wgs, 256, 0, h->stream>>>(L, P.lstride, mv, right(s_lo), P.sstride, nv, P.ksteps_total, ksplit, P.part, nbm, nbn);
+        else if (ns == 2) k_kubo_gram_diag_sets<2><<<wgs, 256, 0, h->stream>>>(L, P.lstride, mv, KuboRights<2>{{right(s_lo), right(s_lo + 1)}}, P.sstride, nv, P.ksteps_total, ksplit, P.part, P.part_image, nbm, nbn);
+        else k_kubo_gram_diag_sets<3><<<wgs, 256, 0, h->stream>>>(L, P.lstride, mv, KuboRights<3>{{right(s_lo), right(s_lo + 1), right(s_lo + 2)}}, P.sstride, nv, P.ksteps_total, ksplit, P.part, P.part_image, nbm, nbn);
+        for (int g = 0; g < ns; ++g)
+            k_kubo_gram_diag_reduce<<<(int)std::min<long>(4096, ((long)mv * nv * NB + 255) / 256), 256, 0, h->stream>>>(P.part + (size_t)g * P.part_image, ksplit, nbm * KD_T, nbn * KD_T, mv, nv, P.mu + (mu_off(s_lo + g) + c) * mu_vec, P.cond_ll, m0, n0);
     }
     W.rest_ev.emplace_back(g0, next_event(h));
     return RSREC_OK;
@@ -3585,9 +3615,8 @@ int kubo_contract_diag(WholeLatticeCall& W, const KuboPlan& P, int j, int m0, in
 // C[(m,c)][(n,c')] = sum_{k,r} conj(L_m[(k,r)][c]) R_n[(k,r)][c'], blocks of C x `ksplit` slices of (k,r), one wave each (k_kubo_gram), then
 // the slices summed in fixed order into mu (k_kubo_gram_reduce).  One contraction per vector of the batch: its matrices are the chain-c
 // columns of the slots (leading dimension = a whole slot).
-int kubo_contract(WholeLatticeCall& W, const KuboPlan& P, int j, int m0, int n, size_t mu_off = 0) {
+int kubo_contract(WholeLatticeCall& W, const KuboPlan& P, int j, int m0, int n) {
     rsrec_t* h = W.h;
-    if (P.diag) return kubo_contract_diag(W, P, j, m0, n, mu_off);
     const int nl = n % P.nchunk, n0 = n - nl, ncols = (nl + 1) * NB, m_rows = std::min(P.lchunk, P.cond_ll - m0) * NB;
     const int nbm = (m_rows + KG_BLK - 1) / KG_BLK, nbn = (ncols + KG_BLK - 1) / KG_BLK;
     // slices: the multiple of 8 (<= what the partial buffer was sized for, >= 64 k-steps per task) that fills whole rounds of
@@ -3605,26 +3634,32 @@ int kubo_contract(WholeLatticeCall& W, const KuboPlan& P, int j, int m0, int n, 
     const unsigned wgs = 8u * (unsigned)(((long)nbm * nbn * (ksplit / 8) + 3) / 4);
     const size_t mu_vec = (size_t)P.cond_ll * P.cond_ll * BLK;
     for (int c = 0; c < W.SD.nchains; ++c) {
-        k_kubo_gram<<<wgs, 256, 0, h->stream>>>(P.Lm + (size_t)c * P.velems, P.sstride, m_rows, P.Rslot(j, 0) + (size_t)c * P.velems, P.sstride, ncols, P.ksteps_total, ksplit, P.part, nbm, nbn);
+        k_kubo_gram<<<wgs, 256, 0, h->stream>>>(P.Lm + (size_t)c * P.velems, P.lstride, m_rows, P.Rslot(j, 0) + (size_t)c * P.velems, P.sstride, ncols, P.ksteps_total, ksplit, P.part, nbm, nbn);
         k_kubo_gram_reduce<<<std::min(4096, (m_rows * ncols + 255) / 256), 256, 0, h->stream>>>(P.part, ksplit, nbm * KG_BLK, nbn * KG_BLK, m_rows, ncols, P.mu + (size_t)c * mu_vec, P.cond_ll, m0, n0);
     }
     W.rest_ev.emplace_back(g0, next_event(h));
     return RSREC_OK;
 }
 
-// What rsrec_kubo_moments, rsrec_kubo_moments_diag and rsrec_kubo_moments_diag_multi share: everything but the contraction kernels
-// (kubo_contract) and the shape of the result -- `out`: complex (18,18,cond_ll,cond_ll,nvec) on the host, or with `diag` complex
-// (18,cond_ll,cond_ll,nvec,nout), host or device or NULL, and then the moments of the whole call stay in d_kubo[4] if they fit there.
-// `nout` output operators v_out(:,:,:,:,j) (the single-response calls: 1, v_a): the left vectors and the right recurrence T_{n-1}(H~) v_b r
-// do not depend on the output operator, so they are formed once, and per order n every set j gets  v_out_j T_{n-1}(H~) v_b r  into a right
-// slot of its own and is contracted by itself -- the launches of set j are those of the single-response call with v_a = v_out_j.
-int kubo_moments_run(rsrec_t* h, const char* fn, bool diag, int nout, int nvec, int nseed, const int32_t* seed_atoms, const double* seed_coef, int cond_ll,
-                     double a, double b, const double* v_out, const double* vo_out, const double* v_b, const double* vo_b, double* out) {
+// What rsrec_kubo_moments, rsrec_kubo_moments_diag, rsrec_kubo_moments_diag_multi and rsrec_kubo_moments_diag_tensor share: everything but
+// the contraction kernels and the shape of the result -- `out`: complex (18,18,cond_ll,cond_ll,nvec) on the host, or with `diag` complex
+// (18,cond_ll,cond_ll,nvec,nout,nin), host or device or NULL, and then the moments of the whole call stay in d_kubo[4] if they fit there.
+// `nout` output operators v_out(:,:,:,:,j) (the single-response calls: 1, v_a) and `nin` input operators v_in(:,:,:,:,i) (all but the tensor
+// call: 1, v_b); set (j, i), input outermost, has the launches and the bits of the single-response call with (v_a, v_b) = (v_out_j, v_in_i):
+//   - the left vectors depend on neither operator: one chunk for all sets, nb chains;
+//   - the right recurrences T_{n-1}(H~) v_in_i r of all inputs advance as the nin x nb chains of ONE launch (chain i nb + c: vector c of input i);
+//   - per order n every output operator is applied once to all those chains, into a right slot of its own (hoh: after one shared h_bulk pass);
+//   - every set is contracted against the left chunk, `setgroup` sets of a vector per launch (kubo_contract_diag).
+// `tensor`: the entry point with several inputs; only there option kubo_setgroup applies, and the error texts name v_in / vo_in.
+int kubo_moments_run(rsrec_t* h, const char* fn, bool diag, bool tensor, int nin, int nout, int nvec, int nseed, const int32_t* seed_atoms, const double* seed_coef,
+                     int cond_ll, double a, double b, const double* v_out, const double* vo_out, const double* v_in, const double* vo_in, double* out) {
     XFER(check_ready(h, fn));
     if (nout < 1 || nout > RSREC_KUBO_NOUT_MAX) return fail(h, RSREC_ERR_ARG, "%s: nout=%d is not in 1..%d", fn, nout, RSREC_KUBO_NOUT_MAX);
-    if (nvec < 0 || nseed < 1 || cond_ll < 1 || (diag && cond_ll > RSREC_COND_LL_MAX) || a == 0.0 || !v_out || !v_b || (!diag && !out) || (nvec > 0 && (!seed_atoms || !seed_coef)))
+    if (nin < 1 || nin > RSREC_KUBO_NIN_MAX) return fail(h, RSREC_ERR_ARG, "%s: nin=%d is not in 1..%d", fn, nin, RSREC_KUBO_NIN_MAX);
+    if (nin * nout > RSREC_KUBO_NSET_MAX) return fail(h, RSREC_ERR_ARG, "%s: nin*nout=%d sets, at most %d", fn, nin * nout, RSREC_KUBO_NSET_MAX);
+    if (nvec < 0 || nseed < 1 || cond_ll < 1 || (diag && cond_ll > RSREC_COND_LL_MAX) || a == 0.0 || !v_out || !v_in || (!diag && !out) || (nvec > 0 && (!seed_atoms || !seed_coef)))
         return fail(h, RSREC_ERR_ARG, "%s: bad argument", fn);
-    if (h->hoh && (!vo_out || !vo_b)) return fail(h, RSREC_ERR_ARG, "%s: hoh requires %s and vo_b", fn, nout > 1 ? "vo_out" : "vo_a");
+    if (h->hoh && (!vo_out || !vo_in)) return fail(h, RSREC_ERR_ARG, "%s: hoh requires %s and %s", fn, tensor || nout > 1 ? "vo_out" : "vo_a", tensor ? "vo_in" : "vo_b");
     if (!h->s5_built) return fail(h, RSREC_ERR_ARG, "%s: lattice has too many neighbour slots for the SpMM kernel", fn);
     XFER(check_seeds(h, fn, seed_atoms, (size_t)nvec * nseed, 0));
     HIPCK(h, hipSetDevice(h->device));
@@ -3632,17 +3667,19 @@ int kubo_moments_run(rsrec_t* h, const char* fn, bool diag, int nout, int nvec, 
     if (nvec == 0) return RSREC_OK;
     h->kubo_diag_nvec = h->kubo_diag_ll = 0;                       // (d_kubo[4] is about to be overwritten)
     release_kubo_buffers(h, false, true);                          // (the integrand's buffers; this call's own stay for the next one)
-    const size_t op_doubles = 2 * (size_t)BLK * h->hslots * h->ntype;             // one operator of v_out / vo_out
+    const size_t op_doubles = 2 * (size_t)BLK * h->hslots * h->ntype;             // one operator of v_out / vo_out / v_in / vo_in
     for (int j = 0; j < nout; ++j) XFER(build_kubo_operator(h, h->kubo_op[j], v_out + op_doubles * j, vo_out ? vo_out + op_doubles * j : nullptr));
-    XFER(build_kubo_operator(h, h->kubo_op_b, v_b, vo_b));
+    for (int i = 0; i < nin; ++i) XFER(build_kubo_operator(h, h->kubo_op_b[i], v_in + op_doubles * i, vo_in ? vo_in + op_doubles * i : nullptr));
     if (h->hoh && h->nmax > 0) XFER(build_kubo_hbulk(h));
+    const int nset = nin * nout;
+    const int setgroup = !tensor ? 1 : (h->opt_kubo_setgroup <= 0 ? KUBO_SETGROUP_DEFAULT : (int)std::min<long>(h->opt_kubo_setgroup, KUBO_SETGROUP_MAX));
     KuboPlan P;
-    XFER(kubo_plan(h, nout, nvec, cond_ll, diag, P));
+    XFER(kubo_plan(h, nin, nout, setgroup, nvec, cond_ll, diag, P));
     XFER(kubo_reserve(h, P));
     HIPCK(h, h->d_seed.reserve((size_t)nseed * 4));
     HIPCK(h, h->d_seedcoef.reserve((size_t)nseed * sizeof(double2)));
     WholeLatticeCall W;
-    XFER(whole_lattice_begin(h, W, P.nbv, true));
+    XFER(whole_lattice_begin(h, W, P.nbv * nin, true));
     W.hps = P.vec(KuboPlan::HPS); W.p1 = P.vec(KuboPlan::P1); W.p2 = P.vec(KuboPlan::P2);
     W.ev_begin = next_event(h);
     const KuboSeeds S{nseed, seed_atoms, seed_coef};
@@ -3650,9 +3687,9 @@ int kubo_moments_run(rsrec_t* h, const char* fn, bool diag, int nout, int nvec, 
     const bool out_dev = diag && out && is_device_ptr(out);       // (the full call's mu_nm is host memory, as ever)
     int n_left_chunks = 0;
     for (int iv0 = 0; iv0 < nvec; iv0 += P.nbv) {
-        const int nb = std::min(P.nbv, nvec - iv0);                               // vectors of this batch = chains of its launches
-        // where the batch's moments of set j lie in P.mu, in vectors: the layout of the result (set outermost) if the whole call is resident
-        auto mu_off = [&](int j) { return P.resident ? (size_t)j * nvec + iv0 : (size_t)j * P.nbv; };
+        const int nb = std::min(P.nbv, nvec - iv0);                               // vectors of this batch; chains of its launches: nb (left, v_in r) or nin nb (right)
+        // where the batch's moments of set s lie in P.mu, in vectors: the layout of the result (set outermost) if the whole call is resident
+        auto mu_off = [&](int s) { return P.resident ? (size_t)s * nvec + iv0 : (size_t)s * P.nbv; };
         whole_lattice_batch(W, nb, false);
         XFER(kubo_seed_batch(h, P, S, iv0, nb));
         for (int m0 = 0; m0 < cond_ll; m0 += P.lchunk, ++n_left_chunks) {
@@ -3660,26 +3697,31 @@ int kubo_moments_run(rsrec_t* h, const char* fn, bool diag, int nout, int nvec, 
             // right vectors  v_a T_{n-1}(H~) v_b r  (:1154-1187), written into the slots of Rm and contracted with the left vectors of
             // this chunk, 64 at a time
             ChebyshevStepper Y{P.vec(KuboPlan::Y), P.vec(KuboPlan::Y + 1), P.vec(KuboPlan::Y + 2)};
-            whole_lattice_apply_v(W, h->kubo_op_b, P.vec(KuboPlan::PSIREF), Y.cur);       // v1 = v0 = v_b r
+            whole_lattice_apply_v_prepare(W, P.vec(KuboPlan::PSIREF));                     // v1 = v0 = v_in_i r into the chains of input i
+            for (int i = 0; i < nin; ++i) whole_lattice_apply_v_prepared(W, h->kubo_op_b[i], P.vec(KuboPlan::PSIREF), Y.cur + (size_t)i * nb * P.velems);
+            if (nin > 1) whole_lattice_batch(W, nin * nb, false);
             for (int n = 0; n < cond_ll; ++n) {
                 Y.step(W, n, a, b);
                 whole_lattice_apply_v_prepare(W, Y.cur);
                 for (int j = 0; j < nout; ++j) whole_lattice_apply_v_prepared(W, h->kubo_op[j], Y.cur, P.Rslot(j, n % P.nchunk));
-                if (n % P.nchunk == P.nchunk - 1 || n == cond_ll - 1)
-                    for (int j = 0; j < nout; ++j) XFER(kubo_contract(W, P, j, m0, n, mu_off(j)));
+                if (n % P.nchunk == P.nchunk - 1 || n == cond_ll - 1) {
+                    if (!diag) XFER(kubo_contract(W, P, 0, m0, n));
+                    else for (int s = 0; s < nset; s += P.setgroup) XFER(kubo_contract_diag(W, P, nb, s, std::min(P.setgroup, nset - s), m0, n, mu_off));
+                }
             }
+            if (nin > 1) whole_lattice_batch(W, nb, false);
         }
         HIPCK(h, hipGetLastError());
-        for (int j = 0; j < nout && out; ++j) {
-            const double* src = reinterpret_cast<const double*>(P.mu) + mu_vec * mu_off(j);
-            double* dst = out + mu_vec * ((size_t)j * nvec + iv0);
+        for (int s = 0; s < nset && out; ++s) {
+            const double* src = reinterpret_cast<const double*>(P.mu) + mu_vec * mu_off(s);
+            double* dst = out + mu_vec * ((size_t)s * nvec + iv0);
             if (out_dev) HIPCK(h, hipMemcpyAsync(dst, src, (size_t)nb * mu_vec * 8, hipMemcpyDeviceToDevice, h->stream));
             else XFER(xfer_d2h(h, dst, src, (size_t)nb * mu_vec * 8));
         }
     }
     XFER(whole_lattice_end(h, W, true));
     h->n_kubo_left_chunks = n_left_chunks;
-    if (P.resident) { h->kubo_diag_nvec = nvec * nout; h->kubo_diag_ll = cond_ll; }
+    if (P.resident) { h->kubo_diag_nvec = nvec * nset; h->kubo_diag_ll = cond_ll; }
     return RSREC_OK;
 }
 
@@ -3691,7 +3733,7 @@ int kubo_moments_run(rsrec_t* h, const char* fn, bool diag, int nout, int nvec, 
 extern "C" int rsrec_kubo_moments(rsrec_t* h, int nvec, int nseed, const int32_t* seed_atoms, const double* seed_coef, int cond_ll, double a, double b,
                                   const double* v_a, const double* vo_a, const double* v_b, const double* vo_b, double* mu_nm) {
     if (!h) return RSREC_ERR_ARG;
-    return kubo_moments_run(h, "rsrec_kubo_moments", false, 1, nvec, nseed, seed_atoms, seed_coef, cond_ll, a, b, v_a, vo_a, v_b, vo_b, mu_nm);
+    return kubo_moments_run(h, "rsrec_kubo_moments", false, false, 1, 1, nvec, nseed, seed_atoms, seed_coef, cond_ll, a, b, v_a, vo_a, v_b, vo_b, mu_nm);
 }
 
 // The same recurrences, but only the orbital-diagonal moments mu(l,l,n,m,i) are contracted (k_kubo_gram_diag): conductivity.f90:289 and
@@ -3699,7 +3741,7 @@ extern "C" int rsrec_kubo_moments(rsrec_t* h, int nvec, int nseed, const int32_t
 extern "C" int rsrec_kubo_moments_diag(rsrec_t* h, int nvec, int nseed, const int32_t* seed_atoms, const double* seed_coef, int cond_ll, double a, double b,
                                        const double* v_a, const double* vo_a, const double* v_b, const double* vo_b, double* mu_diag) {
     if (!h) return RSREC_ERR_ARG;
-    return kubo_moments_run(h, "rsrec_kubo_moments_diag", true, 1, nvec, nseed, seed_atoms, seed_coef, cond_ll, a, b, v_a, vo_a, v_b, vo_b, mu_diag);
+    return kubo_moments_run(h, "rsrec_kubo_moments_diag", true, false, 1, 1, nvec, nseed, seed_atoms, seed_coef, cond_ll, a, b, v_a, vo_a, v_b, vo_b, mu_diag);
 }
 
 // The diagonal moments of `nout` responses to one applied field: set j is rsrec_kubo_moments_diag with v_a = v_out(:,:,:,:,j).  The left
@@ -3709,7 +3751,18 @@ extern "C" int rsrec_kubo_moments_diag_multi(rsrec_t* h, int nout, int nvec, int
                                              double a, double b, const double* v_out, const double* vo_out, const double* v_b, const double* vo_b,
                                              double* mu_diag) {
     if (!h) return RSREC_ERR_ARG;
-    return kubo_moments_run(h, "rsrec_kubo_moments_diag_multi", true, nout, nvec, nseed, seed_atoms, seed_coef, cond_ll, a, b, v_out, vo_out, v_b, vo_b, mu_diag);
+    return kubo_moments_run(h, "rsrec_kubo_moments_diag_multi", true, false, 1, nout, nvec, nseed, seed_atoms, seed_coef, cond_ll, a, b, v_out, vo_out, v_b, vo_b, mu_diag);
+}
+
+// The diagonal moments of `nout` responses to `nin` applied fields: set (j, i), input outermost, is rsrec_kubo_moments_diag with
+// (v_a, v_b) = (v_out(:,:,:,:,j), v_in(:,:,:,:,i)).  Per moment order 1 + nin + nin nout whole-lattice products in 2 + nout launches
+// (the inputs' right recurrences are chains of one launch) instead of 3 nin nout, and one staged left tile serves `kubo_setgroup` sets in
+// the contraction (k_kubo_gram_diag_sets).
+extern "C" int rsrec_kubo_moments_diag_tensor(rsrec_t* h, int nin, int nout, int nvec, int nseed, const int32_t* seed_atoms, const double* seed_coef, int cond_ll,
+                                              double a, double b, const double* v_out, const double* vo_out, const double* v_in, const double* vo_in,
+                                              double* mu_diag) {
+    if (!h) return RSREC_ERR_ARG;
+    return kubo_moments_run(h, "rsrec_kubo_moments_diag_tensor", true, true, nin, nout, nvec, nseed, seed_atoms, seed_coef, cond_ll, a, b, v_out, vo_out, v_in, vo_in, mu_diag);
 }
 
 namespace {

@@ -397,6 +397,41 @@ class Recursion:
         self.mu_diag_resident = (int(cond_ll), nvec * nout)      # what Conductivity.integrand(None, ...) asks the library for
         return mu
 
+    def compute_moments_stochastic_tensor(self, v_out, v_in, cond_ll, vo_out=None, vo_in=None, seeds=None, coefs=None, atlist=None,
+                                          resident_only=False):
+        """The orbital-diagonal Kubo moments of several responses to several applied fields (``rsrec_kubo_moments_diag_tensor``):
+        ``v_out`` (18, 18, nslots, ntype, nout) holds one output operator per response and ``v_in`` (18, 18, nslots, ntype, nin) one
+        input operator per field (``vo_out``, ``vo_in`` likewise, hoh only); a single (18, 18, nslots, ntype) operator counts as one
+        output or one input.  Vectors as in ``compute_moments_stochastic``.  Set (j, i) of the result, complex128 (18, cond_ll, cond_ll,
+        nvec, nout, nin) in Fortran order, is ``compute_moments_stochastic(v_out[..., j], v_in[..., i], diag=True)`` bit for bit, and
+        slice ``[..., i]`` is ``compute_moments_stochastic_multi(v_out, v_in[..., i])``.  The moments stay on the device as
+        nvec * nout * nin vectors, input outermost: ``Conductivity.integrand(None, ene)`` returns (18, nen, nvec * nout * nin), and
+        ``Conductivity.tensor`` takes a set's slice ``[:, :, s * nvec:(s + 1) * nvec]`` with s = i * nout + j.
+        ``resident_only=True``: nothing is downloaded and None is returned."""
+        a, b = chebyshev_scaling(self.en.energy_min, self.en.energy_max)
+        if seeds is None:
+            seeds = np.asarray(atlist, dtype=np.int32).reshape(-1, 1)
+            coefs = np.ones(seeds.shape, np.complex128)
+        seeds = np.ascontiguousarray(seeds, dtype=np.int32)
+        coefs = np.ascontiguousarray(coefs, dtype=np.complex128)
+        nvec, nseed = seeds.shape
+
+        def five(v):                        # one operator (18, 18, nslots, ntype) -> a stack of one
+            if v is None:
+                return None
+            v = np.asarray(v)
+            return _fc(v[..., None] if v.ndim == 4 else v, np.complex128)
+        keep = [five(v) for v in (v_out, vo_out, v_in, vo_in)]
+        for name, k, ko in (("v_out", keep[0], keep[1]), ("v_in", keep[2], keep[3])):
+            if k is None or k.ndim != 5 or (ko is not None and ko.shape != k.shape):
+                raise ValueError("%s (and its vo) must be (18, 18, nslots, ntype[, n]), got %s" % (name, None if k is None else k.shape))
+        nout, nin = keep[0].shape[4], keep[2].shape[4]
+        mu = None if resident_only else np.zeros((18, cond_ll, cond_ll, nvec, nout, nin), np.complex128, order="F")
+        self._check(self._L.rsrec_kubo_moments_diag_tensor(self._h, nin, nout, nvec, nseed, _ptr(seeds), _ptr(coefs), int(cond_ll), a, b,
+                                                           _ptr(keep[0]), _ptr(keep[1]), _ptr(keep[2]), _ptr(keep[3]), _ptr(mu)))
+        self.mu_diag_resident = (int(cond_ll), nvec * nout * nin)      # what Conductivity.integrand(None, ...) asks the library for
+        return mu
+
     def ham_vec_matmul(self, psi_in, a, b):
         """psi_out = (H psi_in - b psi_in)/a on a whole vector psi(18,18,kk) with the PLAIN operator ee + l.s, whatever hoh says
         (recursion.f90:913-977)."""

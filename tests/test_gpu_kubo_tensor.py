@@ -1,0 +1,414 @@
+"""The orbital-diagonal Kubo moments of several responses to several applied fields (rsrec_kubo_moments_diag_tensor): one left chunk
+for all sets, the right recurrences of all inputs as chains of one launch, every output operator applied once per order to all of them,
+and the sets of a vector contracted against one staged left tile (k_kubo_gram_diag_sets, option kubo_setgroup).  Set (j, i) of the
+result must be what rsrec_kubo_moments_diag returns for (v_a, v_b) = (v_out_j, v_in_i) -- bit for bit on the ragged lattice of
+tests/test_gpu_kubo_diag.py (75 atoms: 18 x 75 = 2 mod 4, the last k-step ends in the zero block; 338 k-steps: 8 slices on any
+device) -- and at helpers.RTOL against the CPU oracle and the compiled reference's moments.  Also: slice [..., i] against the multi
+call, independence of the option, of the other sets and of the vectors in flight, the output paths, the launch counts, the refusals
+and the Python mirror."""
+
+import numpy as np
+import pytest
+
+import cond_reference as R
+from helpers import RTOL, load_golden
+from rslmtoasa_amd import _lib
+from rslmtoasa_amd.conductivity import Conductivity
+from rslmtoasa_amd.recursion import Control, Energy, Hamiltonian, Lattice, Recursion
+from test_gpu_kubo_diag import DIAG, KK_ODD, golden_case, integrand_call, ptr, ragged_case, same_bits, vec_err
+from test_gpu_kubo_multi import multi_call, stack
+from test_gpu_spmm_random import random_problem
+
+pytestmark = pytest.mark.gpu
+FN = "rsrec_kubo_moments_diag_tensor"
+NIN_MAX, NOUT_MAX, NSET_MAX = 4, 8, 16
+SIZES = [(1, 1), (2, 1), (1, 2), (2, 2), (3, 3)]        # (nin, nout): set groups of 1, 2, 3, 3 + 1, 3 + 3 + 3 at kubo_setgroup = 3
+
+
+@pytest.fixture(scope="module", autouse=True)
+def torch_first():
+    import torch
+    torch.cuda.init()                                  # torch's HIP runtime before librsrec's (as bench.py does)
+    torch.cuda.set_device(0)
+
+
+def tensor_call(c, outs, ins, cond_ll, out, vecs=None, nin=None, nout=None):
+    """rsrec_kubo_moments_diag_tensor on the case's vectors with operators outs, ins = [(v, vo), ...]; returns the return code"""
+    rec = c.rec
+    sel = slice(None) if vecs is None else vecs
+    seeds, coefs = np.ascontiguousarray(c.seeds[sel]), np.ascontiguousarray(c.coefs[sel])
+    nvec, nseed = seeds.shape
+    v_out, vo_out = (stack([o[0] for o in outs]), stack([o[1] for o in outs])) if outs else (None, None)
+    v_in, vo_in = (stack([o[0] for o in ins]), stack([o[1] for o in ins])) if ins else (None, None)
+    return getattr(rec._L, FN)(rec._h, len(ins) if nin is None else nin, len(outs) if nout is None else nout, nvec, nseed, ptr(seeds), ptr(coefs),
+                               int(cond_ll), c.a, c.b, ptr(v_out), ptr(vo_out), ptr(v_in), ptr(vo_in), ptr(out))
+
+
+def tensor(c, outs, ins, cond_ll, vecs=None):
+    nvec = len(c.seeds[slice(None) if vecs is None else vecs])
+    mu = np.zeros((18, cond_ll, cond_ll, nvec, len(outs), len(ins)), np.complex128, order="F")
+    c.rec._check(tensor_call(c, outs, ins, cond_ll, mu, vecs))
+    return mu
+
+
+def single(c, out_op, in_op, cond_ll, vecs=None):
+    """rsrec_kubo_moments_diag with (v_a, vo_a) = out_op and (v_b, vo_b) = in_op"""
+    keep = c.ops
+    c.ops = [out_op[0], out_op[1], in_op[0], in_op[1]]
+    try:
+        return c.diag(cond_ll, vecs)
+    finally:
+        c.ops = keep
+
+
+class Ragged:
+    """The ragged lattice with three output and three input operators: the case's own v_a / v_b on both sides plus a seeded random one
+    each, so that no two of the nine sets are the same pair."""
+
+    def __init__(self, hoh):
+        self.hoh = hoh
+        self.c = c = ragged_case(hoh)
+        rng = np.random.default_rng(888 + int(hoh))
+
+        def vel():
+            return np.asfortranarray((rng.standard_normal((18, 18, 5, 2)) + 1j * rng.standard_normal((18, 18, 5, 2))) * 0.2)
+
+        def op():
+            return (vel(), vel() if hoh else None)
+        self.outs = [(c.ops[0], c.ops[1]), (c.ops[2], c.ops[3]), op()]
+        self.ins = [(c.ops[2], c.ops[3]), (c.ops[0], c.ops[1]), op()]
+        self.cache = {}
+
+    def single(self, j, i, cond_ll, lchunk=0):
+        """the single call's moments of the pair (out j, in i), computed once per (j, i, cond_ll, kubo_lchunk) and left unchanged"""
+        key = (j, i, cond_ll, lchunk)
+        if key not in self.cache:
+            self.c.rec.set_option("kubo_lchunk", lchunk)
+            try:
+                mu = single(self.c, self.outs[j], self.ins[i], cond_ll)
+            finally:
+                self.c.rec.set_option("kubo_lchunk", 0)
+            mu.setflags(write=False)
+            self.cache[key] = mu
+        return self.cache[key]
+
+
+@pytest.fixture(scope="module")
+def ragged():
+    cases = {hoh: Ragged(hoh) for hoh in (False, True)}
+    yield cases
+    for r in cases.values():
+        r.c.rec.close()
+
+
+def want_launches(L, nin, nout, hoh):
+    """SpMM launches of one batch at kubo_lchunk = 0: L - 1 left steps, nin products v_in r, L - 1 right steps, nout L output products; under
+    hoh an H product is 2 launches and a V product 3, of which the h_bulk pass is shared by all operators applied to the same vectors."""
+    return 4 * L - 3 + 2 * nin + L * (1 + 2 * nout) if hoh else 2 * L - 2 + nin + nout * L
+
+
+# ---- 1. bitwise against the single call --------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("lchunk", [0, 3])
+@pytest.mark.parametrize("cond_ll", [1, 2, 17, 65])
+@pytest.mark.parametrize("size", SIZES)
+@pytest.mark.parametrize("hoh", [False, True])
+def test_every_set_has_the_single_call_bits(hoh, size, cond_ll, lchunk, ragged):
+    """kubo_setgroup = 3: the widest groups, and the remainders of two and one.  cond_ll 65 crosses the border of a block of 64 right
+    vectors; kubo_lchunk 3: left-chunk borders.  nin = 3 on 3 vectors: at most 8 / 3 = 2 vectors advance together, so the call runs a
+    batch of two and a remainder of one -- twice the launches of one batch."""
+    r = ragged[hoh]
+    nin, nout = size
+    rec = r.c.rec
+    rec.set_option("kubo_lchunk", lchunk)
+    rec.set_option("kubo_setgroup", 3)
+    try:
+        mu = tensor(r.c, r.outs[:nout], r.ins[:nin], cond_ll)
+        launches = rec.timing()["hop_launches"]
+    finally:
+        rec.set_option("kubo_lchunk", 0)
+        rec.set_option("kubo_setgroup", 0)
+    assert mu.shape == (18, cond_ll, cond_ll, 3, nout, nin) and np.isfinite(mu).all()
+    for i in range(nin):
+        for j in range(nout):
+            ref = r.single(j, i, cond_ll, lchunk)
+            assert np.abs(ref).max() > 0
+            assert same_bits(mu[..., j, i], ref), (j, i, vec_err(mu[..., j, i], ref))
+    flat = mu.reshape(mu.shape[:4] + (nout * nin,), order="F")
+    for s in range(1, nout * nin):
+        assert not same_bits(flat[..., s - 1], flat[..., s])
+    if lchunk == 0:
+        batches = 2 if nin == 3 else 1
+        assert launches == batches * want_launches(cond_ll, nin, nout, hoh), (launches, batches)
+
+
+# ---- 2. slice [..., i] is the multi call for v_b = v_in_i ------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("hoh", [False, True])
+def test_input_slice_has_the_multi_call_bits(hoh, ragged):
+    r = ragged[hoh]
+    L = 19
+    mu = tensor(r.c, r.outs, r.ins, L)
+    for i, (vb, vob) in enumerate(r.ins):
+        ref = np.zeros((18, L, L, 3, 3), np.complex128, order="F")
+        r.c.rec._check(multi_call(r.c, r.outs, L, ref, v_b=vb, vo_b=vob))
+        assert np.abs(ref).max() > 0 and same_bits(mu[..., i], ref), i
+
+
+# ---- 3. option kubo_setgroup --------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("cond_ll", [17, 65])
+@pytest.mark.parametrize("hoh", [False, True])
+def test_setgroup_does_not_change_a_bit(hoh, cond_ll, ragged):
+    """1: k_kubo_gram_diag per set; 2: pairs (+ one); 3: triples; 0: the default; 7: clamped to the widest kernel built (3)."""
+    r = ragged[hoh]
+    got = {}
+    try:
+        for g in (1, 2, 3, 0, 7):
+            r.c.rec.set_option("kubo_setgroup", g)
+            got[g] = tensor(r.c, r.outs, r.ins[:2], cond_ll)
+    finally:
+        r.c.rec.set_option("kubo_setgroup", 0)
+    assert np.abs(got[1]).max() > 0
+    for g in (2, 3, 0, 7):
+        assert same_bits(got[g], got[1]), g
+    for i in range(2):
+        for j in range(3):
+            assert same_bits(got[1][..., j, i], r.single(j, i, cond_ll))
+
+
+# ---- 4. independence ------------------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("setgroup", [1, 3])
+@pytest.mark.parametrize("hoh", [False, True])
+def test_a_set_does_not_depend_on_the_other_sets(hoh, setgroup, ragged):
+    r = ragged[hoh]
+    (oa, ob, oc), (ia, ib, ic) = r.outs, r.ins
+    r.c.rec.set_option("kubo_setgroup", setgroup)
+    try:
+        full = tensor(r.c, [oa, ob, oc], [ia, ib, ic], 19)
+        perm = tensor(r.c, [oc, oa], [ic, ia, ib], 19)             # permuted on both sides, one output dropped
+        one = tensor(r.c, [ob], [ib], 19)                          # everything else dropped
+    finally:
+        r.c.rec.set_option("kubo_setgroup", 0)
+    out_of, in_of = {0: 2, 1: 0}, {0: 2, 1: 0, 2: 1}               # position in perm -> position in full
+    for pi, i in in_of.items():
+        for pj, j in out_of.items():
+            assert same_bits(perm[..., pj, pi], full[..., j, i]), (pj, pi)
+    assert same_bits(one[..., 0, 0], full[..., 1, 1])
+
+
+def test_vectors_in_flight_do_not_change_a_vector(ragged):
+    r = ragged[False]
+    rec = r.c.rec
+    outs, ins = r.outs[:2], r.ins[:2]
+    try:
+        rec.set_option("kubo_setgroup", 3)
+        rec.set_option("kubo_vbatch", 3)
+        three = tensor(r.c, outs, ins, 19)
+        rec.set_option("kubo_vbatch", 1)
+        one_by_one = tensor(r.c, outs, ins, 19)
+        assert same_bits(one_by_one, three)
+        for v in range(3):
+            assert same_bits(tensor(r.c, outs, ins, 19, vecs=slice(v, v + 1))[:, :, :, 0], three[:, :, :, v])
+    finally:
+        rec.set_option("kubo_vbatch", 0)
+        rec.set_option("kubo_setgroup", 0)
+
+
+# ---- 5. against arithmetic that is not the code under test ---------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("hoh", [False, True])
+def test_sets_match_the_cpu_oracle(hoh, ragged, oracle_lib):
+    """The C restatement of compute_moments_stochastic on the same lattice (rebuilt from ragged_case's seed), one pair at a time."""
+    r = ragged[hoh]
+    rng = np.random.default_rng(4242 + int(hoh))
+    p = random_problem(rng, KK_ODD, 5, 2, 0, hoh, False)
+    if hoh:
+        p["eeo"] = np.asfortranarray(p["eeo"] * 0.1)
+    o = oracle_lib.Oracle(p)
+    L = 6
+    mu = tensor(r.c, r.outs[:2], r.ins[:2], L)
+    for i in range(2):
+        for j in range(2):
+            ref = o.kubo_moments(r.c.seeds, r.c.coefs, L, r.c.a, r.c.b, r.outs[j][0], r.ins[i][0], r.outs[j][1], r.ins[i][1])[DIAG, DIAG]
+            err = vec_err(mu[..., j, i], ref)
+            print("tensor set", (j, i), "vs oracle", err)
+            assert err < RTOL
+
+
+@pytest.mark.parametrize("name", ["fccPt_kubo", "fccPt_kubo_hoh", "fccPt_kubo_random"])
+def test_first_set_matches_reference(name):
+    z, c = golden_case(name)
+    try:
+        L = int(z["cond_ll"])
+        a, b = (c.ops[0], c.ops[1]), (c.ops[2], c.ops[3])
+        mu = tensor(c, [a, b], [b, a], L)
+    finally:
+        c.rec.close()
+    ref = z["mu_nm"][DIAG, DIAG]
+    assert mu.shape == ref.shape + (2, 2)
+    err = vec_err(mu[..., 0, 0], ref)
+    print("tensor set (0, 0) vs reference", name, err)
+    assert err < RTOL
+
+
+# ---- 6. output paths --------------------------------------------------------------------------------------------------------------------------------
+
+def test_host_device_and_resident_output_same_bits(ragged):
+    import torch
+    r = ragged[True]
+    L, nvec, nout, nin = 17, len(r.c.seeds), 3, 2
+    outs, ins = r.outs, r.ins[:2]
+    host = tensor(r.c, outs, ins, L)
+    dev = torch.zeros((nin, nout, nvec, L, L, 18), dtype=torch.complex128, device="cuda")     # (18, L, L, nvec, nout, nin) seen from C
+    r.c.rec._check(tensor_call(r.c, outs, ins, L, dev))
+    torch.cuda.synchronize()
+    assert same_bits(host, np.asfortranarray(dev.cpu().numpy().transpose(5, 4, 3, 2, 1, 0)))
+    r.c.rec._check(tensor_call(r.c, outs, ins, L, None))                                     # nothing copied out ...
+    assert same_bits(tensor(r.c, outs, ins, L), host)                                        # ... and the next download has the same bits
+    assert same_bits(tensor(r.c, outs, ins, L), host)                                        # run to run
+
+
+def test_resident_moments(ragged):
+    r = ragged[False]
+    c = r.c
+    L, nvec, nout, nin = 17, len(c.seeds), 2, 2
+    nset = nout * nin
+    z = dict(ene=np.linspace(-0.7, 0.5, 37), energy_min=-0.8, energy_max=0.6)
+    mu = tensor(c, r.outs[:nout], r.ins[:nin], L)
+    rc, res = integrand_call(c, "rsrec_kubo_integrand_diag", nvec * nset, L, None, z)
+    assert rc == 0, c.last_error()
+    rc, down = integrand_call(c, "rsrec_kubo_integrand_diag", nvec * nset, L, mu.reshape((18, L, L, nvec * nset), order="F"), z)
+    assert rc == 0 and np.isfinite(res).all() and np.abs(res).max() > 0
+    assert same_bits(res, down)
+    for i in range(nin):                                   # input outermost, then output: a set's slice is the single call's integrand
+        for j in range(nout):
+            s = i * nout + j
+            rc, one = integrand_call(c, "rsrec_kubo_integrand_diag", nvec, L, np.asfortranarray(r.single(j, i, L)), z)
+            assert rc == 0 and same_bits(res[:, :, s * nvec:(s + 1) * nvec], one)
+    rc, _ = integrand_call(c, "rsrec_kubo_integrand_diag", nvec, L, None, z)                 # nvec * nset are resident, not nvec
+    assert rc == _lib.ERR_ARG and len(c.last_error()) > 0
+    assert integrand_call(c, "rsrec_kubo_integrand_diag", nvec * nset, L, None, z)[0] == 0   # the refusal dropped nothing
+    single(c, r.outs[0], r.ins[0], L)                                                        # a single-response call: nvec again
+    assert integrand_call(c, "rsrec_kubo_integrand_diag", nvec * nset, L, None, z)[0] == _lib.ERR_ARG
+    rc, res1 = integrand_call(c, "rsrec_kubo_integrand_diag", nvec, L, None, z)
+    assert rc == 0 and same_bits(res1, res[:, :, :nvec])
+
+
+# ---- 7. launch counts --------------------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("size", [(1, 1), (2, 1), (3, 2), (3, 3)])
+@pytest.mark.parametrize("hoh", [False, True])
+def test_launch_counts(hoh, size, ragged):
+    """kubo_lchunk = 0 and one batch (3 vectors, or the 2 that fit the 8 chains of a launch beside nin = 3)."""
+    r = ragged[hoh]
+    L = 17
+    nin, nout = size
+    vecs = slice(0, 2) if nin == 3 else None
+    rec = r.c.rec
+    rec.set_option("kubo_vbatch", 3)
+    try:
+        if size == (1, 1):
+            single(r.c, r.outs[0], r.ins[0], L)
+            assert rec.timing()["hop_launches"] == want_launches(L, 1, 1, hoh) == ((7 * L - 1) if hoh else (3 * L - 1))   # the formula, on the single call
+        tensor(r.c, r.outs[:nout], r.ins[:nin], L, vecs)
+        t = rec.timing()
+        assert t["hop_launches"] == want_launches(L, nin, nout, hoh), (size, t["hop_launches"])
+        assert t["total_ms"] > 0 and t["hop_ms"] > 0 and t["rest_ms"] > 0 and t["hop_ms"] + t["rest_ms"] <= t["total_ms"] * 1.001
+    finally:
+        rec.set_option("kubo_vbatch", 0)
+
+
+# ---- 8. refusals ---------------------------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("hoh", [False, True])
+def test_refusals_leave_the_handle_usable(hoh, ragged):
+    r = ragged[hoh]
+    c, L = r.c, 5
+    out = np.zeros((18, L, L, 3, NSET_MAX + 4), np.complex128, order="F")
+    outs, ins = r.outs, r.ins
+
+    def refused(rc):
+        assert rc == _lib.ERR_ARG, rc
+        assert FN.encode() in c.last_error(), c.last_error()
+
+    refused(tensor_call(c, outs, ins, L, out, nin=0))
+    refused(tensor_call(c, outs, ins, L, out, nin=-1))
+    refused(tensor_call(c, outs, ins * 2, L, out, nin=NIN_MAX + 1))
+    refused(tensor_call(c, outs, ins, L, out, nout=0))
+    refused(tensor_call(c, outs * 3, ins[:1], L, out, nout=NOUT_MAX + 1))
+    refused(tensor_call(c, (outs * 2)[:5], (ins * 2)[:4], L, out))              # 4 x 5 = 20 sets
+    refused(tensor_call(c, [], ins, L, out, nout=2))                            # v_out NULL
+    refused(tensor_call(c, outs, [], L, out, nin=2))                            # v_in NULL
+    if hoh:
+        refused(tensor_call(c, [(o[0], None) for o in outs], ins, L, out))      # hoh without vo_out
+        refused(tensor_call(c, outs, [(o[0], None) for o in ins], L, out))      # hoh without vo_in
+    refused(tensor_call(c, outs, ins, 0, out))                                  # the single call's argument errors
+    refused(tensor_call(c, outs, ins, 100000, None))
+    keep = c.a
+    c.a = 0.0
+    try:
+        refused(tensor_call(c, outs, ins, L, out))
+    finally:
+        c.a = keep
+    bad = c.seeds.copy()
+    bad[1, 3] = c.rec.lattice.kk + 1
+    keep, c.seeds = c.seeds, bad
+    try:
+        refused(tensor_call(c, outs, ins, L, out))                              # (an atom outside the lattice)
+    finally:
+        c.seeds = keep
+    mu = tensor(c, outs, ins[:2], L)                                            # a valid call succeeds afterwards
+    for i in range(2):
+        for j in range(3):
+            assert same_bits(mu[..., j, i], r.single(j, i, L))
+    full = tensor(c, (outs * 2)[:4], (ins * 2)[:4], 2)                          # ... and so does one with 16 sets
+    assert same_bits(full[..., 3, 3], full[..., 0, 0]) and not same_bits(full[..., 3, 3], full[..., 2, 3])
+    assert same_bits(full[..., 0, 0], r.single(0, 0, 2))
+
+
+# ---- 9. the Python mirror --------------------------------------------------------------------------------------------------------------------------------
+
+def test_python_mirror_tensor_and_conductivity():
+    import rslmtoasa_amd.recursion as Rm
+    z = load_golden("fccPt_kubo")
+    a, b = float(z["acheb"]), float(z["bcheb"])
+    half = a * float(np.float32(2) - np.float32(0.3)) / 2
+    ham = Hamiltonian(ee=z["ee"], lsham=z["lsham"], hoh=False)
+    lat = Lattice(nn=z["nn"], iz=z["iz"], irec=np.asarray(z["atlist"], np.int32), nmax=0, ntype=z["ee"].shape[3])
+    rec = Recursion(ham, lat, Control(lld=int(z["cond_ll"]), nsp=int(z["nsp"])), Energy(b - half, b + half), device=0)
+    orig = Rm.chebyshev_scaling
+    Rm.chebyshev_scaling = lambda e0, e1: (a, b)
+    try:
+        L = int(z["cond_ll"])
+        ops = [z["v_a"], z["v_b"]]
+        cond = Conductivity(rec)
+        ene = R.energy_mesh(b - half, b + half, 300)
+        per_set = {}
+        for i, vi in enumerate(ops):
+            for j, vj in enumerate(ops):
+                mu1 = rec.compute_moments_stochastic(vj, vi, L, atlist=z["atlist"], diag=True)
+                integ = cond.integrand(None, ene)
+                per_set[(j, i)] = (mu1, integ, cond.tensor(integ, ene, per_vector=True))
+        mu = rec.compute_moments_stochastic_tensor(np.stack(ops, axis=-1), np.stack(ops, axis=-1), L, atlist=z["atlist"])
+        nvec = mu.shape[3]
+        assert mu.shape == (18, L, L, 1, 2, 2) and mu.dtype == np.complex128 and mu.flags.f_contiguous
+        assert rec.mu_diag_resident == (L, nvec * 4)
+        integ = cond.integrand(None, ene)
+        assert integ.shape == (18, ene.size, nvec * 4)
+        for (j, i), (mu1, integ1, sigma1) in per_set.items():
+            s = i * 2 + j
+            assert same_bits(mu[..., j, i], mu1)
+            mine = integ[:, :, s * nvec:(s + 1) * nvec]
+            assert same_bits(mine, integ1)
+            assert same_bits(cond.tensor(mine, ene, per_vector=True), sigma1)
+        one = rec.compute_moments_stochastic_tensor(z["v_a"], z["v_b"], L, atlist=z["atlist"])      # single operators: one output, one input
+        assert one.shape == (18, L, L, 1, 1, 1) and one.flags.f_contiguous and rec.mu_diag_resident == (L, nvec)
+        assert same_bits(one[..., 0, 0], per_set[(0, 1)][0])
+        assert rec.compute_moments_stochastic_tensor(np.stack(ops, axis=-1), np.stack(ops, axis=-1), L, atlist=z["atlist"], resident_only=True) is None
+        assert rec.mu_diag_resident == (L, nvec * 4)
+        assert same_bits(cond.integrand(None, ene), integ)
+    finally:
+        Rm.chebyshev_scaling = orig
+        rec.close()
