@@ -535,18 +535,15 @@ contains
       class(recursion_gpu), intent(inout) :: this
       integer :: i, j, k, l, loop_over, nseed, cll, nresp, nfield, s
       integer(c_int) :: rc
-      real(rp) :: a, b, rng
+      real(rp) :: a, b, rng, v_beta(3)
       integer(c_int), allocatable, target :: seeds(:, :)
-      complex(rp), allocatable, target :: mu_diag(:, :, :, :)
-      complex(rp), allocatable, target :: vout(:, :, :, :, :), voout(:, :, :, :, :), mu_multi(:, :, :, :, :)
+      ! the operator stacks: slot 1 the namelist's pair, slots 2.. the further responses (vout, voout) / fields (vin, voin)
+      complex(rp), allocatable, target :: vout(:, :, :, :, :), voout(:, :, :, :, :), vin(:, :, :, :, :), voin(:, :, :, :, :)
+      complex(rp), allocatable, target :: coef(:, :), mu(:, :, :, :, :), mu_sets(:, :, :, :, :, :)
       character(len=32) :: resp_op(kubo_nout_max - 1)
       character(len=10) :: resp_pol(kubo_nout_max - 1), pol_alpha
-      complex(rp), allocatable, target :: vin(:, :, :, :, :), voin(:, :, :, :, :), mu_tensor(:, :, :, :, :, :)
       character(len=1) :: field(kubo_nin_max - 1)
-      real(rp) :: v_beta(3)
-      type(c_ptr) :: p_voin
-      complex(rp), allocatable, target :: coef(:, :), mu(:, :, :, :, :), va(:, :, :, :), vb(:, :, :, :), voa(:, :, :, :), vob(:, :, :, :)
-      type(c_ptr) :: p_voa, p_vob
+      type(c_ptr) :: p_voout, p_voin
 
       cll = this%control%cond_ll
       select case (this%control%cond_calctype)
@@ -572,13 +569,7 @@ contains
       do j = 1, nresp
          this%hamiltonian%pol_alpha = resp_pol(j)
          call this%setup_kubo_operators(trim(resp_op(j)), this%control%linear_in)
-         if (j == 1) then
-            allocate (vout(size(this%hamiltonian%v_a, 1), size(this%hamiltonian%v_a, 2), size(this%hamiltonian%v_a, 3), &
-                           size(this%hamiltonian%v_a, 4), nresp + 1))
-            if (this%hamiltonian%hoh) allocate (voout, mold=vout)
-         end if
-         vout(:, :, :, :, 1 + j) = this%hamiltonian%v_a
-         if (this%hamiltonian%hoh) voout(:, :, :, :, 1 + j) = this%hamiltonian%vo_a
+         call stack(vout, voout, this%hamiltonian%v_a, this%hamiltonian%vo_a, 1 + j, 1 + nresp)
       end do
       this%hamiltonian%pol_alpha = pol_alpha
       ! the further fields likewise: the reference's own set-up with the unit vector as v_beta; v_b / vo_b are kept
@@ -590,16 +581,12 @@ contains
          this%hamiltonian%v_beta = 0.0_rp
          this%hamiltonian%v_beta(index('xyz', field(i))) = 1.0_rp
          call this%setup_kubo_operators(this%control%linear_out, this%control%linear_in)
-         if (i == 1) then
-            allocate (vin(size(this%hamiltonian%v_b, 1), size(this%hamiltonian%v_b, 2), size(this%hamiltonian%v_b, 3), &
-                          size(this%hamiltonian%v_b, 4), nfield + 1))
-            if (this%hamiltonian%hoh) allocate (voin, mold=vin)
-         end if
-         vin(:, :, :, :, 1 + i) = this%hamiltonian%v_b
-         if (this%hamiltonian%hoh) voin(:, :, :, :, 1 + i) = this%hamiltonian%vo_b
+         call stack(vin, voin, this%hamiltonian%v_b, this%hamiltonian%vo_b, 1 + i, 1 + nfield)
       end do
       this%hamiltonian%v_beta = v_beta
       call this%setup_kubo_operators(this%control%linear_out, this%control%linear_in)
+      call stack(vout, voout, this%hamiltonian%v_a, this%hamiltonian%vo_a, 1, 1 + nresp)
+      call stack(vin, voin, this%hamiltonian%v_b, this%hamiltonian%vo_b, 1, 1 + nfield)
       allocate (seeds(nseed, loop_over), coef(nseed, loop_over))
       do i = 1, loop_over
          call random_seed()                                       ! :1076
@@ -615,40 +602,48 @@ contains
          end if
       end do
       call sync_device(this, .true.)
-      p_voa = c_null_ptr; p_vob = c_null_ptr
-      allocate (va, source=this%hamiltonian%v_a)
-      allocate (vb, source=this%hamiltonian%v_b)
+      p_voout = c_null_ptr; p_voin = c_null_ptr
       if (this%hamiltonian%hoh) then
-         allocate (voa, source=this%hamiltonian%vo_a)
-         allocate (vob, source=this%hamiltonian%vo_b)
-         p_voa = c_loc(voa)
-         p_vob = c_loc(vob)
+         p_voout = c_loc(voout)
+         p_voin = c_loc(voin)
       end if
       g_kubo_diag_nvec = 0
-      if (nfield > 0) then
-         ! the diagonal moments of (1 + nresp) x (1 + nfield) (response, field) pairs in one call: set (1, 1) -- the namelist's pair -- is
-         ! stored as under kubo_diag, the others are kept for conductivity_gpu in case the library keeps nothing resident
-         if (.not. allocated(vout)) allocate (vout(size(va, 1), size(va, 2), size(va, 3), size(va, 4), 1))
-         vout(:, :, :, :, 1) = va
-         vin(:, :, :, :, 1) = vb
-         p_voa = c_null_ptr; p_voin = c_null_ptr
-         if (this%hamiltonian%hoh) then
-            if (.not. allocated(voout)) allocate (voout, mold=vout)
-            voout(:, :, :, :, 1) = voa
-            voin(:, :, :, :, 1) = vob
-            p_voa = c_loc(voout)
-            p_voin = c_loc(voin)
+      if (nfield == 0 .and. nresp == 0 .and. .not. this%kubo_diag) then
+         allocate (mu(18, 18, cll, cll, loop_over))
+         rc = rsrec_kubo_moments(g_handle, int(loop_over, c_int), int(nseed, c_int), c_loc(seeds), c_loc(coef), int(cll, c_int), &
+                                 real(a, c_double), real(b, c_double), c_loc(vout), p_voout, c_loc(vin), p_voin, c_loc(mu))
+         call check(rc, 'rsrec_kubo_moments')
+         this%mu_nm_stochastic = mu
+      else
+         ! only the diagonals are formed, downloaded and stored, of (1 + nresp) x (1 + nfield) (response, field) pairs; the entry point is
+         ! the narrowest that takes the stacks (with trailing extents of 1 the three result layouts are this one).  The library keeps the
+         ! diagonals for conductivity_gpu%calculate_conductivity_tensor.
+         allocate (mu_sets(18, cll, cll, loop_over, 1 + nresp, 1 + nfield))
+         if (nfield > 0) then
+            call g_timer%start('kubo-tensor-gpu')
+            rc = rsrec_kubo_moments_diag_tensor(g_handle, int(1 + nfield, c_int), int(1 + nresp, c_int), int(loop_over, c_int), int(nseed, c_int), &
+                                                c_loc(seeds), c_loc(coef), int(cll, c_int), real(a, c_double), real(b, c_double), c_loc(vout), p_voout, &
+                                                c_loc(vin), p_voin, c_loc(mu_sets))
+            call g_timer%stop('kubo-tensor-gpu')
+            call check(rc, 'rsrec_kubo_moments_diag_tensor')
+         else if (nresp > 0) then
+            call g_timer%start('kubo-multi-gpu')
+            rc = rsrec_kubo_moments_diag_multi(g_handle, int(1 + nresp, c_int), int(loop_over, c_int), int(nseed, c_int), c_loc(seeds), c_loc(coef), &
+                                               int(cll, c_int), real(a, c_double), real(b, c_double), c_loc(vout), p_voout, c_loc(vin), p_voin, &
+                                               c_loc(mu_sets))
+            call g_timer%stop('kubo-multi-gpu')
+            call check(rc, 'rsrec_kubo_moments_diag_multi')
+         else
+            rc = rsrec_kubo_moments_diag(g_handle, int(loop_over, c_int), int(nseed, c_int), c_loc(seeds), c_loc(coef), int(cll, c_int), &
+                                         real(a, c_double), real(b, c_double), c_loc(vout), p_voout, c_loc(vin), p_voin, c_loc(mu_sets))
+            call check(rc, 'rsrec_kubo_moments_diag')
          end if
-         allocate (mu_tensor(18, cll, cll, loop_over, 1 + nresp, 1 + nfield))
-         call g_timer%start('kubo-tensor-gpu')
-         rc = rsrec_kubo_moments_diag_tensor(g_handle, int(1 + nfield, c_int), int(1 + nresp, c_int), int(loop_over, c_int), int(nseed, c_int), &
-                                             c_loc(seeds), c_loc(coef), int(cll, c_int), real(a, c_double), real(b, c_double), c_loc(vout), p_voa, &
-                                             c_loc(vin), p_voin, c_loc(mu_tensor))
-         call g_timer%stop('kubo-tensor-gpu')
-         call check(rc, 'rsrec_kubo_moments_diag_tensor')
+         ! set (1, 1) -- the namelist's pair -- onto the diagonal of mu_nm_stochastic, every other element of which stays zero (nothing
+         ! reads them: conductivity.f90:289, :292); the others are kept under their names for conductivity_gpu in case the library keeps
+         ! nothing resident
          this%mu_nm_stochastic = (0.0_rp, 0.0_rp)
          do l = 1, 18
-            this%mu_nm_stochastic(l, l, :, :, :) = mu_tensor(l, :, :, :, 1, 1)
+            this%mu_nm_stochastic(l, l, :, :, :) = mu_sets(l, :, :, :, 1, 1)
          end do
          if (allocated(g_kubo_resp_diag)) deallocate (g_kubo_resp_diag)
          allocate (g_kubo_resp_diag(18, cll, cll, loop_over, (1 + nresp)*(1 + nfield) - 1))
@@ -657,7 +652,7 @@ contains
             do j = 0, nresp
                if (i == 0 .and. j == 0) cycle
                s = s + 1
-               g_kubo_resp_diag(:, :, :, :, s) = mu_tensor(:, :, :, :, 1 + j, 1 + i)
+               g_kubo_resp_diag(:, :, :, :, s) = mu_sets(:, :, :, :, 1 + j, 1 + i)
                if (i == 0) then
                   g_kubo_resp_op(s) = resp_op(j)
                else if (j == 0) then
@@ -670,71 +665,33 @@ contains
          g_kubo_nresp = s
          g_kubo_diag_nvec = loop_over*(1 + s)
          g_kubo_diag_ll = cll
-         return
       end if
-      if (nresp > 0) then
-         ! the diagonal moments of 1 + nresp responses in one call: set 1 (linear_out) is stored as under kubo_diag, the others are kept for
-         ! conductivity_gpu in case the library keeps nothing resident
-         vout(:, :, :, :, 1) = va
-         p_voa = c_null_ptr
-         if (this%hamiltonian%hoh) then
-            voout(:, :, :, :, 1) = voa
-            p_voa = c_loc(voout)
+   contains
+      !> operator v (and vo under hoh) into slot `slot` of the stack of n; the stack takes its shape from the first operator it is given
+      subroutine stack(vs, vos, v, vo, slot, n)
+         complex(rp), allocatable, intent(inout) :: vs(:, :, :, :, :), vos(:, :, :, :, :)
+         complex(rp), allocatable, intent(in) :: v(:, :, :, :), vo(:, :, :, :)
+         integer, intent(in) :: slot, n
+
+         if (.not. allocated(vs)) then
+            allocate (vs(size(v, 1), size(v, 2), size(v, 3), size(v, 4), n))
+            if (this%hamiltonian%hoh) allocate (vos, mold=vs)
          end if
-         allocate (mu_multi(18, cll, cll, loop_over, 1 + nresp))
-         call g_timer%start('kubo-multi-gpu')
-         rc = rsrec_kubo_moments_diag_multi(g_handle, int(1 + nresp, c_int), int(loop_over, c_int), int(nseed, c_int), c_loc(seeds), c_loc(coef), &
-                                            int(cll, c_int), real(a, c_double), real(b, c_double), c_loc(vout), p_voa, c_loc(vb), p_vob, &
-                                            c_loc(mu_multi))
-         call g_timer%stop('kubo-multi-gpu')
-         call check(rc, 'rsrec_kubo_moments_diag_multi')
-         this%mu_nm_stochastic = (0.0_rp, 0.0_rp)
-         do l = 1, 18
-            this%mu_nm_stochastic(l, l, :, :, :) = mu_multi(l, :, :, :, 1)
-         end do
-         if (allocated(g_kubo_resp_diag)) deallocate (g_kubo_resp_diag)
-         allocate (g_kubo_resp_diag, source=mu_multi(:, :, :, :, 2:))
-         g_kubo_nresp = nresp
-         g_kubo_resp_op(1:nresp) = resp_op(1:nresp)
-         g_kubo_diag_nvec = loop_over*(1 + nresp)
-         g_kubo_diag_ll = cll
-         return
-      end if
-      if (this%kubo_diag) then
-         ! only the diagonals are formed, downloaded and stored; every other element of mu_nm_stochastic stays zero (nothing reads them:
-         ! conductivity.f90:289, :292).  The library keeps the diagonals for conductivity_gpu%calculate_conductivity_tensor.
-         allocate (mu_diag(18, cll, cll, loop_over))
-         rc = rsrec_kubo_moments_diag(g_handle, int(loop_over, c_int), int(nseed, c_int), c_loc(seeds), c_loc(coef), int(cll, c_int), &
-                                      real(a, c_double), real(b, c_double), c_loc(va), p_voa, c_loc(vb), p_vob, c_loc(mu_diag))
-         call check(rc, 'rsrec_kubo_moments_diag')
-         this%mu_nm_stochastic = (0.0_rp, 0.0_rp)
-         do l = 1, 18
-            this%mu_nm_stochastic(l, l, :, :, :) = mu_diag(l, :, :, :)
-         end do
-         g_kubo_diag_nvec = loop_over
-         g_kubo_diag_ll = cll
-         return
-      end if
-      allocate (mu(18, 18, cll, cll, loop_over))
-      rc = rsrec_kubo_moments(g_handle, int(loop_over, c_int), int(nseed, c_int), c_loc(seeds), c_loc(coef), int(cll, c_int), &
-                              real(a, c_double), real(b, c_double), c_loc(va), p_voa, c_loc(vb), p_vob, c_loc(mu))
-      call check(rc, 'rsrec_kubo_moments')
-      this%mu_nm_stochastic = mu
+         vs(:, :, :, :, slot) = v
+         if (this%hamiltonian%hoh) vos(:, :, :, :, slot) = vo
+      end subroutine stack
    end subroutine gpu_compute_moments_stochastic
 
-   !> RSREC_KUBO_RESPONSES taken apart: 'op' or 'op:pol' separated by commas -> operator names and polarisations (default_pol where none
-   !> is given).  An operator may be named once: its name is the prefix of the response's files.
-   subroutine parse_kubo_responses(list, default_pol, n, op, pol)
-      character(len=*), intent(in) :: list, default_pol
-      integer, intent(out) :: n
-      character(len=32), intent(out) :: op(:)
-      character(len=10), intent(out) :: pol(:)
-      integer :: p0, p1, c
-      character(len=len(list)) :: item
+   !> The next non-empty item of the comma-separated `list` from position p0 on, left-adjusted; p0 moves behind it.  .false.: none is left.
+   function next_item(list, p0, item) result(found)
+      character(len=*), intent(in) :: list
+      integer, intent(inout) :: p0
+      character(len=*), intent(out) :: item
+      logical :: found
+      integer :: p1
 
-      n = 0
-      p0 = 1
-      do while (p0 <= len_trim(list))
+      found = .false.
+      do while (p0 <= len_trim(list) .and. .not. found)
          p1 = index(list(p0:), ',')
          if (p1 == 0) then
             p1 = len_trim(list) + 1
@@ -743,7 +700,23 @@ contains
          end if
          item = adjustl(list(p0:p1 - 1))
          p0 = p1 + 1
-         if (len_trim(item) == 0) cycle
+         found = len_trim(item) > 0
+      end do
+   end function next_item
+
+   !> RSREC_KUBO_RESPONSES taken apart: 'op' or 'op:pol' separated by commas -> operator names and polarisations (default_pol where none
+   !> is given).  An operator may be named once: its name is the prefix of the response's files.
+   subroutine parse_kubo_responses(list, default_pol, n, op, pol)
+      character(len=*), intent(in) :: list, default_pol
+      integer, intent(out) :: n
+      character(len=32), intent(out) :: op(:)
+      character(len=10), intent(out) :: pol(:)
+      integer :: p0, c
+      character(len=len(list)) :: item
+
+      n = 0
+      p0 = 1
+      do while (next_item(list, p0, item))
          if (n == size(op)) call g_logger%fatal('RSREC_KUBO_RESPONSES: more than '//int2str(size(op))//' further responses', __FILE__, __LINE__)
          n = n + 1
          c = index(item, ':')
@@ -767,22 +740,13 @@ contains
       real(rp), intent(in) :: v_beta(3)
       integer, intent(out) :: n
       character(len=1), intent(out) :: field(:)
-      integer :: p0, p1, ax
+      integer :: p0, ax
       real(rp) :: axis(3)
       character(len=len(list)) :: item
 
       n = 0
       p0 = 1
-      do while (p0 <= len_trim(list))
-         p1 = index(list(p0:), ',')
-         if (p1 == 0) then
-            p1 = len_trim(list) + 1
-         else
-            p1 = p0 + p1 - 1
-         end if
-         item = adjustl(list(p0:p1 - 1))
-         p0 = p1 + 1
-         if (len_trim(item) == 0) cycle
+      do while (next_item(list, p0, item))
          ax = 0
          if (len_trim(item) == 1) ax = index('xyz', item(1:1))
          if (ax == 0) call g_logger%fatal('RSREC_KUBO_FIELDS: "'//trim(item)//'" is not one of x, y, z', __FILE__, __LINE__)

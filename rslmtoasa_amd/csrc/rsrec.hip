@@ -3439,16 +3439,11 @@ struct KuboPlan {
     size_t velems = 0, sstride = 0, lstride = 0;   // doubles of one vector; between two work vectors / right slots (nin x nbv chains each); between two left slots (nbv chains)
     size_t part_image = 0;                   // double2 of one set's slice partials (diag)
     size_t bytes[5] = {0, 0, 0, 0, 0};       // of the five buffers
-    // slices of the row index per contraction: enough wave tasks for a few rounds of the device, at least 64 k-steps per task
+    // slices of the row index per contraction: enough wave tasks for a dozen rounds of the device, at least 64 k-steps per task.  diag: one
+    // workgroup per task, three of them per CU (158 registers); otherwise one wave per task, eight per CU
     int ksplit_for(int lc) const {
-        if (diag) {                                                               // one workgroup per task, three of them per CU (158 registers)
-            const long blocks = (long)((lc + KD_T - 1) / KD_T) * nbn_max;
-            long ksp = (12L * 3 * n_cu + blocks - 1) / std::max(1L, blocks);
-            ksp = std::min<long>({ksp, 64, std::max(1, ksteps_total / 64)});
-            return (int)std::max<long>(8, (ksp + 7) / 8 * 8);
-        }
-        const long blocks = (long)((lc * NB + KG_BLK - 1) / KG_BLK) * nbn_max;
-        long ksp = (12L * 8 * n_cu + blocks - 1) / std::max(1L, blocks);          // up to a dozen rounds of the device's wave slots
+        const long blocks = (long)(diag ? (lc + KD_T - 1) / KD_T : (lc * NB + KG_BLK - 1) / KG_BLK) * nbn_max;
+        long ksp = (12L * (diag ? 3 : 8) * n_cu + blocks - 1) / std::max(1L, blocks);
         ksp = std::min<long>({ksp, 64, std::max(1, ksteps_total / 64)});
         return (int)std::max<long>(8, (ksp + 7) / 8 * 8);
     }
@@ -3566,16 +3561,17 @@ int kubo_left_chunk(WholeLatticeCall& W, const KuboPlan& P, int m0, double a, do
     return RSREC_OK;
 }
 
-// Slices of a diagonal contraction of nbm x nbn tiles: the multiple of 8 (<= what the partial buffer was sized for, >= 64 k-steps per task)
-// that fills whole rounds of 3 workgroups per CU best.  k_kubo_gram_diag and k_kubo_gram_diag_sets both take it from here: the slice
-// partition decides the order of every element's sum, so a set's bits are the same whichever kernel contracts it.
-int kubo_diag_ksplit(const rsrec_t* h, const KuboPlan& P, int nbm, int nbn) {
+// Slices of a contraction of nbm x nbn tiles: the multiple of 8 (<= what the partial buffer was sized for, >= 64 k-steps per task) that fills
+// whole rounds of the device's `per_cu` task slots per CU best (8 waves: k_kubo_gram; 3 workgroups: k_kubo_gram_diag and
+// k_kubo_gram_diag_sets) -- 361 blocks x 24 slices are 4.2 rounds of 2 048 slots (85 % of the last round idle), x 32 are 5.6.  The slice
+// partition decides the order of every element's sum, so a set's bits are the same whichever diagonal kernel contracts it.
+int kubo_ksplit(const rsrec_t* h, const KuboPlan& P, int per_cu, int nbm, int nbn) {
     int ksplit = 8;
-    const long slots = 3L * h->n_cu, cap = std::min<long>(P.ksplit_for(P.lchunk), std::max(8, P.ksteps_total / 64 / 8 * 8));
+    const long slots = (long)per_cu * h->n_cu, cap = std::min<long>(P.ksplit_for(P.lchunk), std::max(8, P.ksteps_total / 64 / 8 * 8));
     double best = 0.0;
     for (long c = 8; c <= cap; c += 8) {
         const long tasks = (long)nbm * nbn * c, rounds = (tasks + slots - 1) / slots;
-        const double eff = (double)tasks / (double)(rounds * slots) * (rounds >= 3 ? 1.0 : 0.9);
+        const double eff = (double)tasks / (double)(rounds * slots) * (rounds >= 3 ? 1.0 : 0.9);   // (few rounds: the tail of the slowest wave shows)
         if (eff > best + 1e-9) { best = eff; ksplit = (int)c; }
     }
     return ksplit;
@@ -3591,7 +3587,7 @@ int kubo_contract_diag(WholeLatticeCall& W, const KuboPlan& P, int nb, int s_lo,
     rsrec_t* h = W.h;
     const int nl = n % P.nchunk, n0 = n - nl, nv = nl + 1, mv = std::min(P.lchunk, P.cond_ll - m0);
     const int nbm = (mv + KD_T - 1) / KD_T, nbn = (nv + KD_T - 1) / KD_T;
-    const int ksplit = kubo_diag_ksplit(h, P, nbm, nbn);
+    const int ksplit = kubo_ksplit(h, P, 3, nbm, nbn);
     if (ns < 1 || ns > P.setgroup || (size_t)ksplit * nbm * KD_T * nbn * KD_T * NB > P.part_image)
         return fail(h, RSREC_ERR_DEVICE, "rsrec_kubo_moments: contraction group outside the planned partial buffer");
     HIPCK(h, hipGetLastError());
@@ -3619,16 +3615,7 @@ int kubo_contract(WholeLatticeCall& W, const KuboPlan& P, int j, int m0, int n) 
     rsrec_t* h = W.h;
     const int nl = n % P.nchunk, n0 = n - nl, ncols = (nl + 1) * NB, m_rows = std::min(P.lchunk, P.cond_ll - m0) * NB;
     const int nbm = (m_rows + KG_BLK - 1) / KG_BLK, nbn = (ncols + KG_BLK - 1) / KG_BLK;
-    // slices: the multiple of 8 (<= what the partial buffer was sized for, >= 64 k-steps per task) that fills whole rounds of
-    // the device's wave slots best -- 361 blocks x 24 slices are 4.2 rounds of 2 048 slots (85 % of the last round idle), x 32 are 5.6
-    int ksplit = 8;
-    const long slots = 8L * h->n_cu, cap = std::min<long>(P.ksplit_for(P.lchunk), std::max(8, P.ksteps_total / 64 / 8 * 8));
-    double best = 0.0;
-    for (long c = 8; c <= cap; c += 8) {
-        const long tasks = (long)nbm * nbn * c, rounds = (tasks + slots - 1) / slots;
-        const double eff = (double)tasks / (double)(rounds * slots) * (rounds >= 3 ? 1.0 : 0.9);   // (few rounds: the tail of the slowest wave shows)
-        if (eff > best + 1e-9) { best = eff; ksplit = (int)c; }
-    }
+    const int ksplit = kubo_ksplit(h, P, 8, nbm, nbn);
     HIPCK(h, hipGetLastError());
     hipEvent_t g0 = next_event(h);
     const unsigned wgs = 8u * (unsigned)(((long)nbm * nbn * (ksplit / 8) + 3) / 4);

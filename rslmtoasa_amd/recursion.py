@@ -351,6 +351,15 @@ class Recursion:
         ``diag=True``: only the orbital-diagonal moments mu_nm(l,l,n,m,v), the ones conductivity.f90:289, :292 read
         (``rsrec_kubo_moments_diag``): complex128 (18, cond_ll, cond_ll, nvec) in Fortran order.  They also stay on the device for
         ``Conductivity.integrand(None, ene)``; with ``resident_only=True`` nothing is downloaded and None is returned."""
+        keep = [None if v is None else _fc(v, np.complex128) for v in (v_a, vo_a, v_b, vo_b)]
+        if diag:
+            return self._kubo_moments(self._L.rsrec_kubo_moments_diag, (), keep, cond_ll, seeds, coefs, atlist, (), resident_only)
+        return self._kubo_moments(self._L.rsrec_kubo_moments, (), keep, cond_ll, seeds, coefs, atlist, None, False)
+
+    def _kubo_moments(self, entry, counts, ops, cond_ll, seeds, coefs, atlist, sets, resident_only):
+        """What the compute_moments_stochastic* methods share: the vectors normalised, the result allocated, the call of ``entry`` and
+        the bookkeeping.  ``counts``: the set counts the entry point takes before nvec; ``ops``: its four operators (v_out, vo_out,
+        v_in, vo_in), Fortran-contiguous or None; ``sets``: the trailing extents of the diagonal result, None for the full moments."""
         a, b = chebyshev_scaling(self.en.energy_min, self.en.energy_max)
         if seeds is None:
             seeds = np.asarray(atlist, dtype=np.int32).reshape(-1, 1)
@@ -358,17 +367,13 @@ class Recursion:
         seeds = np.ascontiguousarray(seeds, dtype=np.int32)
         coefs = np.ascontiguousarray(coefs, dtype=np.complex128)
         nvec, nseed = seeds.shape
-        keep = [None if v is None else _fc(v, np.complex128) for v in (v_a, vo_a, v_b, vo_b)]
-        if diag:
-            mu = None if resident_only else np.zeros((18, cond_ll, cond_ll, nvec), np.complex128, order="F")
-            self._check(self._L.rsrec_kubo_moments_diag(self._h, nvec, nseed, _ptr(seeds), _ptr(coefs), int(cond_ll), a, b,
-                                                        _ptr(keep[0]), _ptr(keep[1]), _ptr(keep[2]), _ptr(keep[3]), _ptr(mu)))
-            self.mu_diag_resident = (int(cond_ll), nvec)             # what Conductivity.integrand(None, ...) asks the library for
-            return mu
-        mu = np.zeros((18, 18, cond_ll, cond_ll, nvec), np.complex128, order="F")
-        self._check(self._L.rsrec_kubo_moments(self._h, nvec, nseed, _ptr(seeds), _ptr(coefs), int(cond_ll), a, b,
-                                               _ptr(keep[0]), _ptr(keep[1]), _ptr(keep[2]), _ptr(keep[3]), _ptr(mu)))
-        self.mu_nm_stochastic = mu
+        shape = (18, 18, cond_ll, cond_ll, nvec) if sets is None else (18, cond_ll, cond_ll, nvec) + sets
+        mu = None if resident_only else np.zeros(shape, np.complex128, order="F")
+        self._check(entry(self._h, *counts, nvec, nseed, _ptr(seeds), _ptr(coefs), int(cond_ll), a, b, *[_ptr(k) for k in ops], _ptr(mu)))
+        if sets is None:
+            self.mu_nm_stochastic = mu
+        else:
+            self.mu_diag_resident = (int(cond_ll), nvec * int(np.prod(sets)))   # what Conductivity.integrand(None, ...) asks the library for
         return mu
 
     def compute_moments_stochastic_multi(self, v_out, v_b, cond_ll, vo_out=None, vo_b=None, seeds=None, coefs=None, atlist=None,
@@ -380,22 +385,12 @@ class Recursion:
         3 nout whole-lattice products per moment order.  The moments stay on the device as nvec * nout vectors, set outermost:
         ``Conductivity.integrand(None, ene)`` returns (18, nen, nvec * nout), and ``Conductivity.tensor`` takes a set's slice
         ``[:, :, j * nvec:(j + 1) * nvec]``.  ``resident_only=True``: nothing is downloaded and None is returned."""
-        a, b = chebyshev_scaling(self.en.energy_min, self.en.energy_max)
-        if seeds is None:
-            seeds = np.asarray(atlist, dtype=np.int32).reshape(-1, 1)
-            coefs = np.ones(seeds.shape, np.complex128)
-        seeds = np.ascontiguousarray(seeds, dtype=np.int32)
-        coefs = np.ascontiguousarray(coefs, dtype=np.complex128)
-        nvec, nseed = seeds.shape
         keep = [None if v is None else _fc(v, np.complex128) for v in (v_out, vo_out, v_b, vo_b)]
         if keep[0].ndim != 5 or (keep[1] is not None and keep[1].shape != keep[0].shape):
             raise ValueError("v_out (and vo_out) must be (18, 18, nslots, ntype, nout), got %s" % (keep[0].shape,))
         nout = keep[0].shape[4]
-        mu = None if resident_only else np.zeros((18, cond_ll, cond_ll, nvec, nout), np.complex128, order="F")
-        self._check(self._L.rsrec_kubo_moments_diag_multi(self._h, nout, nvec, nseed, _ptr(seeds), _ptr(coefs), int(cond_ll), a, b,
-                                                          _ptr(keep[0]), _ptr(keep[1]), _ptr(keep[2]), _ptr(keep[3]), _ptr(mu)))
-        self.mu_diag_resident = (int(cond_ll), nvec * nout)      # what Conductivity.integrand(None, ...) asks the library for
-        return mu
+        return self._kubo_moments(self._L.rsrec_kubo_moments_diag_multi, (nout,), keep, cond_ll, seeds, coefs, atlist, (nout,),
+                                  resident_only)
 
     def compute_moments_stochastic_tensor(self, v_out, v_in, cond_ll, vo_out=None, vo_in=None, seeds=None, coefs=None, atlist=None,
                                           resident_only=False):
@@ -408,14 +403,6 @@ class Recursion:
         nvec * nout * nin vectors, input outermost: ``Conductivity.integrand(None, ene)`` returns (18, nen, nvec * nout * nin), and
         ``Conductivity.tensor`` takes a set's slice ``[:, :, s * nvec:(s + 1) * nvec]`` with s = i * nout + j.
         ``resident_only=True``: nothing is downloaded and None is returned."""
-        a, b = chebyshev_scaling(self.en.energy_min, self.en.energy_max)
-        if seeds is None:
-            seeds = np.asarray(atlist, dtype=np.int32).reshape(-1, 1)
-            coefs = np.ones(seeds.shape, np.complex128)
-        seeds = np.ascontiguousarray(seeds, dtype=np.int32)
-        coefs = np.ascontiguousarray(coefs, dtype=np.complex128)
-        nvec, nseed = seeds.shape
-
         def five(v):                        # one operator (18, 18, nslots, ntype) -> a stack of one
             if v is None:
                 return None
@@ -426,11 +413,8 @@ class Recursion:
             if k is None or k.ndim != 5 or (ko is not None and ko.shape != k.shape):
                 raise ValueError("%s (and its vo) must be (18, 18, nslots, ntype[, n]), got %s" % (name, None if k is None else k.shape))
         nout, nin = keep[0].shape[4], keep[2].shape[4]
-        mu = None if resident_only else np.zeros((18, cond_ll, cond_ll, nvec, nout, nin), np.complex128, order="F")
-        self._check(self._L.rsrec_kubo_moments_diag_tensor(self._h, nin, nout, nvec, nseed, _ptr(seeds), _ptr(coefs), int(cond_ll), a, b,
-                                                           _ptr(keep[0]), _ptr(keep[1]), _ptr(keep[2]), _ptr(keep[3]), _ptr(mu)))
-        self.mu_diag_resident = (int(cond_ll), nvec * nout * nin)      # what Conductivity.integrand(None, ...) asks the library for
-        return mu
+        return self._kubo_moments(self._L.rsrec_kubo_moments_diag_tensor, (nin, nout), keep, cond_ll, seeds, coefs, atlist, (nout, nin),
+                                  resident_only)
 
     def ham_vec_matmul(self, psi_in, a, b):
         """psi_out = (H psi_in - b psi_in)/a on a whole vector psi(18,18,kk) with the PLAIN operator ee + l.s, whatever hoh says

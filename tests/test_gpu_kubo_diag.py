@@ -4,117 +4,18 @@ the diagonal route forms mu_diag(l, n, m, v) = mu_nm(l, l, n, m, v) alone.  Chec
 (tests/golden/fccPt_kubo*.npz), against the full route on the same handle, for bitwise repeatability and independence of the vectors
 in flight, and -- the integrand -- bitwise against rsrec_kubo_integrand on the full array built from the same diagonals.
 Error measure and tolerance of the moments: those of tests/test_gpu_kubo.py (max |mu - ref| of a vector over its largest |ref|, RTOL)."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import cond_reference as R
-from helpers import RTOL, load_golden, objects_from, random_vec_coefficients
+from helpers import RTOL, load_golden
+from kubo_cases import DIAG, KK_ODD, golden_case, integrand_call, ragged_case, same_bits, vec_err
+from kubo_cases import torch_first  # noqa: F401 (autouse)
 from rslmtoasa_amd import _lib
 from rslmtoasa_amd.conductivity import Conductivity
 from rslmtoasa_amd.recursion import Control, Energy, Hamiltonian, Lattice, Recursion
-from test_gpu_spmm_random import random_problem
 
 pytestmark = pytest.mark.gpu
-DIAG = np.arange(18)
-
-
-def ptr(a):
-    if a is None:
-        return None
-    if hasattr(a, "data_ptr"):
-        return C.c_void_p(a.data_ptr())
-    return a.ctypes.data_as(C.c_void_p)
-
-
-def fcc(a):
-    return None if a is None else np.asfortranarray(a, dtype=np.complex128)
-
-
-def vec_err(mu, ref):
-    return max(np.abs(mu[..., i] - ref[..., i]).max() / np.abs(ref[..., i]).max() for i in range(ref.shape[-1]))
-
-
-def same_bits(a, b):
-    return np.array_equal(np.ravel(a, order="K").view(np.float64), np.ravel(b, order="K").view(np.float64))
-
-
-class Case:
-    """A handle with the operators, scaling and random vectors of one problem; the moment calls go straight to the library."""
-
-    def __init__(self, p, a, b, v_a, v_b, vo_a, vo_b, seeds, coefs, irec=(1,)):
-        self.rec = Recursion(*objects_from(p, np.asarray(irec, np.int32), 4, nsp=int(p.get("nsp", 2))), device=0)
-        self.a, self.b = float(a), float(b)
-        self.ops = [fcc(v_a), fcc(vo_a), fcc(v_b), fcc(vo_b)]
-        self.seeds = np.ascontiguousarray(seeds, dtype=np.int32)
-        self.coefs = np.ascontiguousarray(coefs, dtype=np.complex128)
-
-    def call(self, name, cond_ll, out, vecs=None):
-        """rsrec_kubo_moments / rsrec_kubo_moments_diag on vectors `vecs` (default: all) into `out` (numpy, torch, or None)."""
-        rec = self.rec
-        sel = slice(None) if vecs is None else vecs
-        seeds, coefs = np.ascontiguousarray(self.seeds[sel]), np.ascontiguousarray(self.coefs[sel])
-        nvec, nseed = seeds.shape
-        fn = getattr(rec._L, name)
-        return fn(rec._h, nvec, nseed, ptr(seeds), ptr(coefs), int(cond_ll), self.a, self.b, *[ptr(o) for o in self.ops], ptr(out))
-
-    def full(self, cond_ll, vecs=None):
-        nvec = len(self.seeds[slice(None) if vecs is None else vecs])
-        mu = np.zeros((18, 18, cond_ll, cond_ll, nvec), np.complex128, order="F")
-        self.rec._check(self.call("rsrec_kubo_moments", cond_ll, mu, vecs))
-        return mu
-
-    def diag(self, cond_ll, vecs=None):
-        nvec = len(self.seeds[slice(None) if vecs is None else vecs])
-        mu = np.zeros((18, cond_ll, cond_ll, nvec), np.complex128, order="F")
-        self.rec._check(self.call("rsrec_kubo_moments_diag", cond_ll, mu, vecs))
-        return mu
-
-    def last_error(self):
-        buf = C.create_string_buffer(512)
-        self.rec._L.rsrec_last_error(self.rec._h, buf, 512)
-        return buf.value
-
-
-def golden_case(name):
-    z = load_golden(name)
-    p = {k: z[k] for k in ("nn", "iz", "ee", "lsham", "eeo", "enim") if k in z}
-    p.update(nmax=0, hoh=int(z["hoh"]), nsp=int(z["nsp"]))
-    if "rng" in z:
-        seeds, coefs = random_vec_coefficients(z["rng"])
-    else:
-        seeds = np.asarray(z["atlist"], np.int32).reshape(-1, 1)
-        coefs = np.ones(seeds.shape, np.complex128)
-    return z, Case(p, z["acheb"], z["bcheb"], z["v_a"], z["v_b"], z.get("vo_a"), z.get("vo_b"), seeds, coefs, irec=z["atlist"])
-
-
-@pytest.fixture(scope="module", autouse=True)
-def torch_first():
-    import torch
-    torch.cuda.init()                                  # torch's HIP runtime before librsrec's (as bench.py does)
-    torch.cuda.set_device(0)
-
-
-KK_ODD = 75            # 18 kk = 1350 = 2 mod 4: the last k-step of the contraction ends in the zero block
-
-
-def ragged_case(hoh):
-    """Random ragged lattice with an ODD number of atoms, random velocity blocks, three random-phase vectors.  a bounds the operator
-    norm (5 slots of 18 x 18 complex Gaussian blocks of deviation 0.28 each: < 15) with room, so the recurrences stay tame."""
-    rng = np.random.default_rng(4242 + int(hoh))
-    p = random_problem(rng, KK_ODD, 5, 2, 0, hoh, False)
-    if hoh:                                                # (h - h o h: keep the second-order part small against a)
-        p["eeo"] = np.asfortranarray(p["eeo"] * 0.1)
-
-    def vel():
-        return np.asfortranarray((rng.standard_normal((18, 18, 5, 2)) + 1j * rng.standard_normal((18, 18, 5, 2))) * 0.2)
-    v_a, v_b = vel(), vel()
-    vo_a, vo_b = (vel(), vel()) if hoh else (None, None)
-    nvec = 3
-    seeds = np.tile(np.arange(1, KK_ODD + 1, dtype=np.int32), (nvec, 1))
-    coefs = np.exp(2j * np.pi * rng.random((nvec, KK_ODD))) / np.sqrt(KK_ODD)
-    return Case(p, 60.0, 0.1, v_a, v_b, vo_a, vo_b, seeds, coefs)
 
 
 @pytest.fixture(scope="module")
@@ -229,13 +130,6 @@ def cond_rec():
     z, c = golden_case("fccPt_kubo")
     yield z, c
     c.rec.close()
-
-
-def integrand_call(c, name, nvec, L, mu, z):
-    ene = np.ascontiguousarray(z["ene"], np.float64)
-    out = np.zeros((18, ene.size, nvec), np.complex128, order="F")
-    rc = getattr(c.rec._L, name)(c.rec._h, nvec, L, ptr(mu), ene.size, ptr(ene), float(z["energy_min"]), float(z["energy_max"]), ptr(out))
-    return rc, out
 
 
 @pytest.mark.parametrize("name", ["cond_integrand_L7", "cond_integrand_L24"])

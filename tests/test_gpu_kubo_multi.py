@@ -10,92 +10,20 @@ import pytest
 
 import cond_reference as R
 from helpers import RTOL, load_golden
+from kubo_cases import DIAG, golden_case, integrand_call, multi, multi_call, ragged_pair, same_bits, single, vec_err
+from kubo_cases import torch_first  # noqa: F401 (autouse)
 from rslmtoasa_amd import _lib
 from rslmtoasa_amd.conductivity import Conductivity
 from rslmtoasa_amd.recursion import Control, Energy, Hamiltonian, Lattice, Recursion
-from test_gpu_kubo_diag import DIAG, golden_case, integrand_call, ptr, ragged_case, same_bits, vec_err
 
 pytestmark = pytest.mark.gpu
 FN = "rsrec_kubo_moments_diag_multi"
 NOUT_MAX = 8
 
 
-@pytest.fixture(scope="module", autouse=True)
-def torch_first():
-    import torch
-    torch.cuda.init()                                  # torch's HIP runtime before librsrec's (as bench.py does)
-    torch.cuda.set_device(0)
-
-
-def stack(ops):
-    """output operators (18, 18, nslots, ntype) -> (18, 18, nslots, ntype, nout), Fortran order; None if there are none (no hoh)"""
-    return None if ops[0] is None else np.asfortranarray(np.stack(ops, axis=-1), dtype=np.complex128)
-
-
-def multi_call(c, outs, cond_ll, out, vecs=None, nout=None, v_b="case", vo_b="case"):
-    """rsrec_kubo_moments_diag_multi on the case's vectors with output operators outs = [(v, vo), ...]; returns the return code"""
-    rec = c.rec
-    sel = slice(None) if vecs is None else vecs
-    seeds, coefs = np.ascontiguousarray(c.seeds[sel]), np.ascontiguousarray(c.coefs[sel])
-    nvec, nseed = seeds.shape
-    v_out = stack([o[0] for o in outs]) if outs else None
-    vo_out = stack([o[1] for o in outs]) if outs else None
-    vb = c.ops[2] if isinstance(v_b, str) else v_b
-    vob = c.ops[3] if isinstance(vo_b, str) else vo_b
-    return getattr(rec._L, FN)(rec._h, len(outs) if nout is None else nout, nvec, nseed, ptr(seeds), ptr(coefs), int(cond_ll), c.a, c.b,
-                               ptr(v_out), ptr(vo_out), ptr(vb), ptr(vob), ptr(out))
-
-
-def multi(c, outs, cond_ll, vecs=None):
-    nvec = len(c.seeds[slice(None) if vecs is None else vecs])
-    mu = np.zeros((18, cond_ll, cond_ll, nvec, len(outs)), np.complex128, order="F")
-    c.rec._check(multi_call(c, outs, cond_ll, mu, vecs))
-    return mu
-
-
-def single(c, op, cond_ll, vecs=None):
-    """rsrec_kubo_moments_diag with (v_a, vo_a) = op and the case's v_b"""
-    keep = c.ops
-    c.ops = [op[0], op[1], keep[2], keep[3]]
-    try:
-        return c.diag(cond_ll, vecs)
-    finally:
-        c.ops = keep
-
-
-class Ragged:
-    """The ragged lattice with three output operators: the case's v_a, its v_b used as an output operator, one more random operator."""
-
-    def __init__(self, hoh):
-        self.c = c = ragged_case(hoh)
-        rng = np.random.default_rng(777 + int(hoh))
-
-        def vel():
-            return np.asfortranarray((rng.standard_normal((18, 18, 5, 2)) + 1j * rng.standard_normal((18, 18, 5, 2))) * 0.2)
-        extra = (vel(), vel() if hoh else None)
-        self.outs = [(c.ops[0], c.ops[1]), (c.ops[2], c.ops[3]), extra]
-        self.cache = {}
-
-    def single(self, j, cond_ll, lchunk=0):
-        """the single-response moments of output operator j, computed once per (j, cond_ll, kubo_lchunk) and left unchanged"""
-        key = (j, cond_ll, lchunk)
-        if key not in self.cache:
-            self.c.rec.set_option("kubo_lchunk", lchunk)
-            try:
-                mu = single(self.c, self.outs[j], cond_ll)
-            finally:
-                self.c.rec.set_option("kubo_lchunk", 0)
-            mu.setflags(write=False)
-            self.cache[key] = mu
-        return self.cache[key]
-
-
 @pytest.fixture(scope="module")
 def ragged():
-    cases = {hoh: Ragged(hoh) for hoh in (False, True)}
-    yield cases
-    for r in cases.values():
-        r.c.rec.close()
+    yield from ragged_pair(777, False)
 
 
 # ---- 1. bitwise against the single-response call --------------------------------------------------------------------------------------
@@ -114,7 +42,7 @@ def test_every_set_has_the_single_response_bits(hoh, cond_ll, lchunk, ragged):
         r.c.rec.set_option("kubo_lchunk", 0)
     assert mu.shape == (18, cond_ll, cond_ll, 3, 3) and np.isfinite(mu).all()
     for j in range(3):
-        ref = r.single(j, cond_ll, lchunk)
+        ref = r.single(j, 0, cond_ll, lchunk)
         assert np.abs(ref).max() > 0
         assert same_bits(mu[..., j], ref), (j, vec_err(mu[..., j], ref))
     assert not same_bits(mu[..., 0], mu[..., 1]) and not same_bits(mu[..., 1], mu[..., 2])
@@ -129,7 +57,7 @@ def test_sets_match_reference_and_single_response(name):
         L = int(z["cond_ll"])
         outs = [(c.ops[0], c.ops[1]), (c.ops[2], c.ops[3])]
         mu = multi(c, outs, L)
-        second = single(c, outs[1], L)
+        second = single(c, outs[1], cond_ll=L)
     finally:
         c.rec.close()
     ref = z["mu_nm"][DIAG, DIAG]
@@ -145,7 +73,7 @@ def test_sets_match_reference_and_single_response(name):
 @pytest.mark.parametrize("hoh", [False, True])
 def test_one_set_has_the_single_response_bits(hoh, ragged):
     r = ragged[hoh]
-    assert same_bits(multi(r.c, r.outs[:1], 17)[..., 0], r.single(0, 17))
+    assert same_bits(multi(r.c, r.outs[:1], 17)[..., 0], r.single(0, 0, 17))
 
 
 @pytest.mark.parametrize("hoh", [False, True])
@@ -204,7 +132,7 @@ def test_resident_moments(ragged):
     rc, _ = integrand_call(c, "rsrec_kubo_integrand_diag", nvec, L, None, z)               # nvec * nout are resident, not nvec
     assert rc == _lib.ERR_ARG and len(c.last_error()) > 0
     assert integrand_call(c, "rsrec_kubo_integrand_diag", nvec * nout, L, None, z)[0] == 0   # the refusal dropped nothing
-    single(c, r.outs[0], L)                                                                  # a single-response call: nvec again
+    single(c, r.outs[0], cond_ll=L)                                                          # a single-response call: nvec again
     assert integrand_call(c, "rsrec_kubo_integrand_diag", nvec * nout, L, None, z)[0] == _lib.ERR_ARG
     rc, res1 = integrand_call(c, "rsrec_kubo_integrand_diag", nvec, L, None, z)
     assert rc == 0 and same_bits(res1, res[:, :, :nvec])
@@ -224,7 +152,7 @@ def test_launch_counts(hoh, ragged):
 
     r.c.rec.set_option("kubo_vbatch", 3)
     try:
-        single(r.c, r.outs[0], L)
+        single(r.c, r.outs[0], cond_ll=L)
         t1 = r.c.rec.timing()
         assert t1["hop_launches"] == want(1) == ((7 * L - 1) if hoh else (3 * L - 1))      # the formula, on the single-response call
         for J in (1, 2, 3):
@@ -273,7 +201,7 @@ def test_refusals_leave_the_handle_usable(hoh, ragged):
         c.seeds = keep
     mu = multi(c, r.outs, L)                                                    # a valid call succeeds afterwards
     for j in range(3):
-        assert same_bits(mu[..., j], r.single(j, L))
+        assert same_bits(mu[..., j], r.single(j, 0, L))
     full = multi(c, (r.outs * 3)[:NOUT_MAX], 2)                                 # ... and so does one with the largest nout
     assert same_bits(full[..., NOUT_MAX - 1], full[..., (NOUT_MAX - 1) % 3])
 

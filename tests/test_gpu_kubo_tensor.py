@@ -12,11 +12,11 @@ import pytest
 
 import cond_reference as R
 from helpers import RTOL, load_golden
+from kubo_cases import DIAG, KK_ODD, golden_case, integrand_call, multi_call, ragged_pair, same_bits, single, tensor, tensor_call, vec_err
+from kubo_cases import torch_first  # noqa: F401 (autouse)
 from rslmtoasa_amd import _lib
 from rslmtoasa_amd.conductivity import Conductivity
 from rslmtoasa_amd.recursion import Control, Energy, Hamiltonian, Lattice, Recursion
-from test_gpu_kubo_diag import DIAG, KK_ODD, golden_case, integrand_call, ptr, ragged_case, same_bits, vec_err
-from test_gpu_kubo_multi import multi_call, stack
 from test_gpu_spmm_random import random_problem
 
 pytestmark = pytest.mark.gpu
@@ -25,80 +25,9 @@ NIN_MAX, NOUT_MAX, NSET_MAX = 4, 8, 16
 SIZES = [(1, 1), (2, 1), (1, 2), (2, 2), (3, 3)]        # (nin, nout): set groups of 1, 2, 3, 3 + 1, 3 + 3 + 3 at kubo_setgroup = 3
 
 
-@pytest.fixture(scope="module", autouse=True)
-def torch_first():
-    import torch
-    torch.cuda.init()                                  # torch's HIP runtime before librsrec's (as bench.py does)
-    torch.cuda.set_device(0)
-
-
-def tensor_call(c, outs, ins, cond_ll, out, vecs=None, nin=None, nout=None):
-    """rsrec_kubo_moments_diag_tensor on the case's vectors with operators outs, ins = [(v, vo), ...]; returns the return code"""
-    rec = c.rec
-    sel = slice(None) if vecs is None else vecs
-    seeds, coefs = np.ascontiguousarray(c.seeds[sel]), np.ascontiguousarray(c.coefs[sel])
-    nvec, nseed = seeds.shape
-    v_out, vo_out = (stack([o[0] for o in outs]), stack([o[1] for o in outs])) if outs else (None, None)
-    v_in, vo_in = (stack([o[0] for o in ins]), stack([o[1] for o in ins])) if ins else (None, None)
-    return getattr(rec._L, FN)(rec._h, len(ins) if nin is None else nin, len(outs) if nout is None else nout, nvec, nseed, ptr(seeds), ptr(coefs),
-                               int(cond_ll), c.a, c.b, ptr(v_out), ptr(vo_out), ptr(v_in), ptr(vo_in), ptr(out))
-
-
-def tensor(c, outs, ins, cond_ll, vecs=None):
-    nvec = len(c.seeds[slice(None) if vecs is None else vecs])
-    mu = np.zeros((18, cond_ll, cond_ll, nvec, len(outs), len(ins)), np.complex128, order="F")
-    c.rec._check(tensor_call(c, outs, ins, cond_ll, mu, vecs))
-    return mu
-
-
-def single(c, out_op, in_op, cond_ll, vecs=None):
-    """rsrec_kubo_moments_diag with (v_a, vo_a) = out_op and (v_b, vo_b) = in_op"""
-    keep = c.ops
-    c.ops = [out_op[0], out_op[1], in_op[0], in_op[1]]
-    try:
-        return c.diag(cond_ll, vecs)
-    finally:
-        c.ops = keep
-
-
-class Ragged:
-    """The ragged lattice with three output and three input operators: the case's own v_a / v_b on both sides plus a seeded random one
-    each, so that no two of the nine sets are the same pair."""
-
-    def __init__(self, hoh):
-        self.hoh = hoh
-        self.c = c = ragged_case(hoh)
-        rng = np.random.default_rng(888 + int(hoh))
-
-        def vel():
-            return np.asfortranarray((rng.standard_normal((18, 18, 5, 2)) + 1j * rng.standard_normal((18, 18, 5, 2))) * 0.2)
-
-        def op():
-            return (vel(), vel() if hoh else None)
-        self.outs = [(c.ops[0], c.ops[1]), (c.ops[2], c.ops[3]), op()]
-        self.ins = [(c.ops[2], c.ops[3]), (c.ops[0], c.ops[1]), op()]
-        self.cache = {}
-
-    def single(self, j, i, cond_ll, lchunk=0):
-        """the single call's moments of the pair (out j, in i), computed once per (j, i, cond_ll, kubo_lchunk) and left unchanged"""
-        key = (j, i, cond_ll, lchunk)
-        if key not in self.cache:
-            self.c.rec.set_option("kubo_lchunk", lchunk)
-            try:
-                mu = single(self.c, self.outs[j], self.ins[i], cond_ll)
-            finally:
-                self.c.rec.set_option("kubo_lchunk", 0)
-            mu.setflags(write=False)
-            self.cache[key] = mu
-        return self.cache[key]
-
-
 @pytest.fixture(scope="module")
 def ragged():
-    cases = {hoh: Ragged(hoh) for hoh in (False, True)}
-    yield cases
-    for r in cases.values():
-        r.c.rec.close()
+    yield from ragged_pair(888, True)
 
 
 def want_launches(L, nin, nout, hoh):
