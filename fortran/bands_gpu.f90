@@ -27,6 +27,16 @@
 !> an iteration.  Deviation: `g0_x, g0_y, g0_z, d_orb` stay zero on this route (no routine of the reference reads them);
 !> RSREC_HOST_MOMENTS restores them with the host route.
 !>
+!> The integrals of those tails run on the device as well (`device_tail`, the default of the spectra route): right after the spectra call,
+!> while its image is still on the handle, ONE `rsrec_spectra_integrals` call (timer region `moment-integrals-gpu`) integrates the 15 rows
+!> as they are -- `simpson_m` of orders 0, 1, 2 up to the Fermi level and the cumulative `simpson_f` up to every mesh energy, the latter in
+!> O(nE) instead of the O(nE^2) loops behind `<sym>_spinene.out` / `<sym>_orbene.out`.  The integrals are linear, so the three routines
+!> form dx / dy / dz (sums of three rows) and the dspd rows (which need the moment direction calculate_magnetic_moments has just updated:
+!> no table built before that call could hold it) from the rows' integrals; the file formats, the `-1/pi` and `0.5/pi` factors, `ql`,
+!> `gravity_center`, `mtot`, `mom` and the log lines stay here.  RSREC_HOST_MOMENT_TAIL keeps the reference's host loops (region
+!> `moment-integrals-host`).  `calculate_orbital_quadrupoles` takes the same route while the chains are resident and g0 is pending: one
+!> six-operator spectra call, one integrals call, no g0.
+!>
 !> `g0` on demand: the remaining consumers of `g0` (orbital quadrupoles, projected Green function, orbital DOS) and every case the
 !> device route does not take are inherited; the overrides below only make sure `g0` exists first (`green_gpu%fetch_g0`, a no-op unless
 !> `green_gpu%defer_g0` postponed it).
@@ -71,6 +81,16 @@ module bands_gpu_mod
       integer :: spec_resident = -1       ! residency count the image was made for
       !> the operators, built once: 1-12 = P(c, l), c = 0, x, y, z outer, l = s, p, d inner; 13-15 = Lx, Ly, Lz
       complex(rp), dimension(:, :, :), allocatable :: spec_ops
+      !> .false.: the Simpson tails of the spectra route stay the reference's host loops (RSREC_HOST_MOMENT_TAIL)
+      logical :: device_tail = .true.
+      !> number of rsrec_spectra_integrals calls made (diagnostics / tests)
+      integer :: n_device_tail = 0
+      !> the integrals of the 15 rows of `spec`: tail_mom(p + 1, k, site) = simpson_m(nexp = p), tail_cum(k, ie, site) = simpson_f up to ene(ie);
+      !> valid for the Fermi-level arguments they were made with
+      real(rp), dimension(:, :, :), allocatable :: tail_mom, tail_cum
+      logical :: tail_valid = .false.
+      integer :: tail_nv1 = -1
+      real(rp) :: tail_e1 = 0.0_rp, tail_fermi = 0.0_rp
    contains
       procedure :: calculate_fermi => gpu_calculate_fermi
       procedure :: calculate_magnetic_moments => gpu_calculate_magnetic_moments
@@ -107,6 +127,7 @@ contains
       call obj%restore_to_default()
       if (rsrec_env_flag('RSREC_HOST_LDOS')) obj%device_ldos = .false.   ! (hosts that cannot reach the member: fortran/shadow/)
       if (rsrec_env_flag('RSREC_HOST_MOMENTS')) obj%device_moments = .false.
+      if (rsrec_env_flag('RSREC_HOST_MOMENT_TAIL')) obj%device_tail = .false.
    end function gpu_constructor
 
    !> bands.f90:178-217.  In a pair run (lattice%njij /= 0: the exchange post-processing, calculation.f90:816-950) atoms_per_process
@@ -173,6 +194,7 @@ contains
       real(rp), allocatable, target :: ene(:), dtot(:), dosia(:, :), dosial(:, :, :)
 
       this%spec_valid = .false.           ! a new Green function: the moment stage after it forms its own image
+      this%tail_valid = .false.
       if (.not. device_stage_usable(this)) then
          call ensure_g0(this)
          call this%bands%calculate_fermi()
@@ -360,7 +382,59 @@ contains
       this%n_device_spectra = this%n_device_spectra + 1
       this%spec_valid = .true.
       this%spec_resident = nres
+      this%tail_valid = .false.
+      if (this%device_tail) call spectra_tail(this, .true.)       ! the image is on the handle now: nothing is uploaded
    end subroutine ensure_spectra
+
+   !> mom and cum of the 15 rows of the image, one library call.  resident: the image is the one the spectra call has just left on the
+   !> handle; else the type's copy is passed.
+   subroutine spectra_tail(this, resident)
+      class(bands_gpu), intent(inout), target :: this
+      logical, intent(in) :: resident
+      integer :: nv, nrec
+      integer(c_int) :: rc
+      type(c_ptr) :: handle, sptr
+      real(rp), allocatable, target :: ene(:)
+      real(rp), dimension(:, :, :), pointer :: sp, pm, pc
+
+      nv = this%en%channels_ldos + 10
+      nrec = this%lattice%nrec
+      if (allocated(this%tail_cum)) then
+         if (size(this%tail_cum, 2) /= nv .or. size(this%tail_cum, 3) /= nrec) deallocate (this%tail_cum, this%tail_mom)
+      end if
+      if (.not. allocated(this%tail_cum)) allocate (this%tail_mom(3, 15, nrec), this%tail_cum(15, nv, nrec))
+      allocate (ene(nv))
+      ene = this%en%ene(1:nv)
+      handle = rsrec_gpu_context()
+      sp => this%spec
+      pm => this%tail_mom
+      pc => this%tail_cum
+      sptr = c_null_ptr
+      if (.not. resident) sptr = c_loc(sp)
+      call g_timer%start('moment-integrals-gpu')
+      rc = rsrec_spectra_integrals(handle, 15_c_int, sptr, 15_c_int, c_null_ptr, int(nv, c_int), c_loc(ene), int(this%en%nv1, c_int), &
+                                   int(this%nv1, c_int), real(this%en%edel, c_double), real(this%e1, c_double), real(this%en%fermi, c_double), &
+                                   int(end_atom - start_atom + 1, c_int), int(start_atom - 1, c_int), int(nrec, c_int), c_loc(pm), c_loc(pc))
+      call g_timer%stop('moment-integrals-gpu')
+      if (rc /= 0) call g_logger%fatal('rsrec_spectra_integrals: '//rsrec_error_string(handle), __FILE__, __LINE__)
+      this%n_device_tail = this%n_device_tail + 1
+      this%tail_valid = .true.
+      this%tail_nv1 = this%nv1
+      this%tail_e1 = this%e1
+      this%tail_fermi = this%en%fermi
+   end subroutine spectra_tail
+
+   !> The image and, on the device tail, its integrals for the Fermi-level arguments as they are NOW (a routine that moved them since the
+   !> spectra call gets a second call on the type's copy of the image)
+   subroutine ensure_tail(this)
+      class(bands_gpu), intent(inout) :: this
+      call ensure_spectra(this)
+      if (.not. this%device_tail) return
+      if (this%tail_valid) then
+         if (this%tail_nv1 == this%nv1 .and. this%tail_e1 == this%e1 .and. this%tail_fermi == this%en%fermi) return
+      end if
+      call spectra_tail(this, .false.)
+   end subroutine ensure_tail
 
    !> calculate_magnetic_moments (bands.f90:791-855) reads nothing of g0 itself: it integrates the dx, dy, dz of calculate_projected_dos.
    !> A call through the parent component would bind that inner call to the reference's routine (the parent component's dynamic type is
@@ -378,24 +452,42 @@ contains
       end if
 
       call this%calculate_projected_dos()
+      call ensure_tail(this)
 
       do na = start_atom, end_atom
          na_loc = g2l_map(na)
          pb = this%lattice%nbulk + na
-         call simpson_m(this%symbolic_atom(pb)%potential%mx, this%en%edel, this%en%fermi, this%nv1, this%dx(:, na_loc), this%e1, 0, this%en%ene)
-         call simpson_m(this%symbolic_atom(pb)%potential%my, this%en%edel, this%en%fermi, this%nv1, this%dy(:, na_loc), this%e1, 0, this%en%ene)
-         call simpson_m(this%symbolic_atom(pb)%potential%mz, this%en%edel, this%en%fermi, this%nv1, this%dz(:, na_loc), this%e1, 0, this%en%ene)
+         if (this%device_tail) then
+            ! dx, dy, dz are -(row + row + row)/pi of the x, y, z brackets (rows 4-6, 7-9, 10-12), and so are their integrals
+            this%symbolic_atom(pb)%potential%mx = bracket_sum(this%tail_mom(1, 4:6, na))
+            this%symbolic_atom(pb)%potential%my = bracket_sum(this%tail_mom(1, 7:9, na))
+            this%symbolic_atom(pb)%potential%mz = bracket_sum(this%tail_mom(1, 10:12, na))
+         else
+            call g_timer%start('moment-integrals-host')
+            call simpson_m(this%symbolic_atom(pb)%potential%mx, this%en%edel, this%en%fermi, this%nv1, this%dx(:, na_loc), this%e1, 0, this%en%ene)
+            call simpson_m(this%symbolic_atom(pb)%potential%my, this%en%edel, this%en%fermi, this%nv1, this%dy(:, na_loc), this%e1, 0, this%en%ene)
+            call simpson_m(this%symbolic_atom(pb)%potential%mz, this%en%edel, this%en%fermi, this%nv1, this%dz(:, na_loc), this%e1, 0, this%en%ene)
+            call g_timer%stop('moment-integrals-host')
+         end if
 
          fnamemag = trim(this%symbolic_atom(pb)%element%symbol)//"_spinene.out"
          unitmag = 1000
          open (unit=unitmag, file=fnamemag, status='replace', action='write')
+         if (.not. this%device_tail) call g_timer%start('moment-integrals-host')
          do ie = 1, this%en%channels_ldos + 10
-            mxe = 0.0d0; mye = 0.d00; mze = 0.0d0
-            call simpson_f(mxe, this%en%ene, this%en%ene(ie), this%en%nv1, this%dx(:, na_loc), .true., .false., 0.0d0)
-            call simpson_f(mye, this%en%ene, this%en%ene(ie), this%en%nv1, this%dy(:, na_loc), .true., .false., 0.0d0)
-            call simpson_f(mze, this%en%ene, this%en%ene(ie), this%en%nv1, this%dz(:, na_loc), .true., .false., 0.0d0)
+            if (this%device_tail) then
+               mxe = bracket_sum(this%tail_cum(4:6, ie, na))
+               mye = bracket_sum(this%tail_cum(7:9, ie, na))
+               mze = bracket_sum(this%tail_cum(10:12, ie, na))
+            else
+               mxe = 0.0d0; mye = 0.d00; mze = 0.0d0
+               call simpson_f(mxe, this%en%ene, this%en%ene(ie), this%en%nv1, this%dx(:, na_loc), .true., .false., 0.0d0)
+               call simpson_f(mye, this%en%ene, this%en%ene(ie), this%en%nv1, this%dy(:, na_loc), .true., .false., 0.0d0)
+               call simpson_f(mze, this%en%ene, this%en%ene(ie), this%en%nv1, this%dz(:, na_loc), .true., .false., 0.0d0)
+            end if
             write (unitmag, '(4es16.6)') this%en%ene(ie) - this%en%fermi, mxe, mye, mze
          end do
+         if (.not. this%device_tail) call g_timer%stop('moment-integrals-host')
          rewind (unitmag)
          close (unitmag)
 
@@ -403,9 +495,17 @@ contains
          this%symbolic_atom(pb)%potential%mom0(2) = this%symbolic_atom(pb)%potential%my
          this%symbolic_atom(pb)%potential%mom0(3) = this%symbolic_atom(pb)%potential%mz
 
-         call simpson_m(this%symbolic_atom(pb)%potential%mom1(1), this%en%edel, this%en%fermi, this%nv1, this%dx(:, na_loc), this%e1, 1, this%en%ene)
-         call simpson_m(this%symbolic_atom(pb)%potential%mom1(2), this%en%edel, this%en%fermi, this%nv1, this%dy(:, na_loc), this%e1, 1, this%en%ene)
-         call simpson_m(this%symbolic_atom(pb)%potential%mom1(3), this%en%edel, this%en%fermi, this%nv1, this%dz(:, na_loc), this%e1, 1, this%en%ene)
+         if (this%device_tail) then
+            this%symbolic_atom(pb)%potential%mom1(1) = bracket_sum(this%tail_mom(2, 4:6, na))
+            this%symbolic_atom(pb)%potential%mom1(2) = bracket_sum(this%tail_mom(2, 7:9, na))
+            this%symbolic_atom(pb)%potential%mom1(3) = bracket_sum(this%tail_mom(2, 10:12, na))
+         else
+            call g_timer%start('moment-integrals-host')
+            call simpson_m(this%symbolic_atom(pb)%potential%mom1(1), this%en%edel, this%en%fermi, this%nv1, this%dx(:, na_loc), this%e1, 1, this%en%ene)
+            call simpson_m(this%symbolic_atom(pb)%potential%mom1(2), this%en%edel, this%en%fermi, this%nv1, this%dy(:, na_loc), this%e1, 1, this%en%ene)
+            call simpson_m(this%symbolic_atom(pb)%potential%mom1(3), this%en%edel, this%en%fermi, this%nv1, this%dz(:, na_loc), this%e1, 1, this%en%ene)
+            call g_timer%stop('moment-integrals-host')
+         end if
 
          this%symbolic_atom(pb)%potential%mtot = sqrt((this%symbolic_atom(pb)%potential%mx**2) + (this%symbolic_atom(pb)%potential%my**2) + &
                                                       (this%symbolic_atom(pb)%potential%mz**2)) + 1.0d-15
@@ -429,6 +529,13 @@ contains
       end do
    end subroutine gpu_calculate_magnetic_moments
 
+   !> -(a + b + c)/pi of three rows' integrals, the expression calculate_projected_dos applies to the rows themselves
+   pure function bracket_sum(v) result(r)
+      real(rp), intent(in) :: v(3)
+      real(rp) :: r
+      r = -(v(1) + v(2) + v(3))/pi
+   end function bracket_sum
+
    !> calculate_orbital_moments (bands.f90:1075-1156): lxi, lyi, lzi from the image, the tail restated
    subroutine gpu_calculate_orbital_moments(this)
       class(bands_gpu) :: this
@@ -443,28 +550,44 @@ contains
          call this%bands%calculate_orbital_moments()
          return
       end if
-      call ensure_spectra(this)
+      call ensure_tail(this)
       nv = this%en%channels_ldos + 10
       do na = start_atom, end_atom
          lx = 0.0d0; ly = 0.0d0; lz = 0.d0
-         lxi = 0.0d0; lyi = 0.0d0; lzi = 0.0d0
-         lxi(1:nv) = this%spec(13, :, na)
-         lyi(1:nv) = this%spec(14, :, na)
-         lzi(1:nv) = this%spec(15, :, na)
+         if (this%device_tail) then
+            lx = this%tail_mom(1, 13, na)
+            ly = this%tail_mom(1, 14, na)
+            lz = this%tail_mom(1, 15, na)
+         else
+            lxi = 0.0d0; lyi = 0.0d0; lzi = 0.0d0
+            lxi(1:nv) = this%spec(13, :, na)
+            lyi(1:nv) = this%spec(14, :, na)
+            lzi(1:nv) = this%spec(15, :, na)
 
-         call simpson_m(lx, this%en%edel, this%en%fermi, this%nv1, lxi, this%e1, 0, this%en%ene)
-         call simpson_m(ly, this%en%edel, this%en%fermi, this%nv1, lyi, this%e1, 0, this%en%ene)
-         call simpson_m(lz, this%en%edel, this%en%fermi, this%nv1, lzi, this%e1, 0, this%en%ene)
+            call g_timer%start('moment-integrals-host')
+            call simpson_m(lx, this%en%edel, this%en%fermi, this%nv1, lxi, this%e1, 0, this%en%ene)
+            call simpson_m(ly, this%en%edel, this%en%fermi, this%nv1, lyi, this%e1, 0, this%en%ene)
+            call simpson_m(lz, this%en%edel, this%en%fermi, this%nv1, lzi, this%e1, 0, this%en%ene)
+            call g_timer%stop('moment-integrals-host')
+         end if
 
          fnameorb = trim(this%symbolic_atom(this%lattice%nbulk + na)%element%symbol)//"_orbene.out"
          unitorb = (rank + 1)*132 + na
          open (unit=unitorb, file=fnameorb, status='replace', action='write')
+         if (.not. this%device_tail) call g_timer%start('moment-integrals-host')
          do ie = 1, this%en%channels_ldos + 10
-            call simpson_f(lxe, this%en%ene, this%en%ene(ie), this%en%nv1, lxi, .true., .false., 0.0d0)
-            call simpson_f(lye, this%en%ene, this%en%ene(ie), this%en%nv1, lyi, .true., .false., 0.0d0)
-            call simpson_f(lze, this%en%ene, this%en%ene(ie), this%en%nv1, lzi, .true., .false., 0.0d0)
+            if (this%device_tail) then
+               lxe = this%tail_cum(13, ie, na)
+               lye = this%tail_cum(14, ie, na)
+               lze = this%tail_cum(15, ie, na)
+            else
+               call simpson_f(lxe, this%en%ene, this%en%ene(ie), this%en%nv1, lxi, .true., .false., 0.0d0)
+               call simpson_f(lye, this%en%ene, this%en%ene(ie), this%en%nv1, lyi, .true., .false., 0.0d0)
+               call simpson_f(lze, this%en%ene, this%en%ene(ie), this%en%nv1, lzi, .true., .false., 0.0d0)
+            end if
             write (unitorb, '(4es16.6)') this%en%ene(ie) - this%en%fermi, -(lxe/pi), -(lye/pi), -(lze/pi)
          end do
+         if (.not. this%device_tail) call g_timer%stop('moment-integrals-host')
          rewind (unitorb)
          close (unitorb)
 
@@ -479,10 +602,106 @@ contains
       end do
    end subroutine gpu_calculate_orbital_moments
 
+   !> calculate_orbital_quadrupoles (bands.f90:878-1067).  On the spectra route with the device tail -- the chains still resident, g0 still
+   !> pending -- the six Q operators (:906-955) go through one spectra call and one integrals call: Im Tr(Q g0) of :985-993, simpson_m of
+   !> :998-1004 and the cumulative simpson_f of :1019-1025 without a g0; the file and the two log lines are the reference's.  (The
+   !> reference first calls calculate_orbital_dos, which reads g0; the quadrupoles read nothing of what it leaves.)  In every other case: g0
+   !> and the reference's routine.
    subroutine gpu_calculate_orbital_quadrupoles(this)
       class(bands_gpu) :: this
-      call ensure_g0(this)
-      call this%bands%calculate_orbital_quadrupoles()
+      real(rp) :: q(6), qe(6), qx2y2, q3z2r2
+      integer :: na, ie, k, nv, nrec, unitquad
+      integer(c_int) :: rc, sym_i
+      type(c_ptr) :: handle
+      character(len=256) :: fnamequad
+      complex(rp), dimension(9, 9) :: mL
+      complex(rp), dimension(18, 18, 3) :: mL_ext
+      complex(rp), dimension(:, :, :), allocatable, target :: ops
+      real(rp), dimension(:, :, :), allocatable, target :: qspec, qmom, qcum
+      real(rp), allocatable, target :: ene(:)
+
+      if (.not. (spectra_route(this) .and. this%device_tail)) then
+         call ensure_g0(this)
+         call this%bands%calculate_orbital_quadrupoles()
+         return
+      end if
+
+      mL_ext = (0.0_rp, 0.0_rp)
+      do k = 1, 3
+         select case (k)
+         case (1); mL = L_x
+         case (2); mL = L_y
+         case (3); mL = L_z
+         end select
+         call hcpx(mL, 'cart2sph')
+         mL_ext(1:9, 1:9, k) = mL
+         mL_ext(10:18, 10:18, k) = mL
+      end do
+      allocate (ops(18, 18, 6))
+      ops(:, :, 1) = matmul(mL_ext(:, :, 1), mL_ext(:, :, 1))                                                             ! Qxx, Qyy, Qzz
+      ops(:, :, 2) = matmul(mL_ext(:, :, 2), mL_ext(:, :, 2))
+      ops(:, :, 3) = matmul(mL_ext(:, :, 3), mL_ext(:, :, 3))
+      ops(:, :, 4) = 0.5_rp*(matmul(mL_ext(:, :, 1), mL_ext(:, :, 2)) + matmul(mL_ext(:, :, 2), mL_ext(:, :, 1)))         ! Qxy, Qyz, Qzx
+      ops(:, :, 5) = 0.5_rp*(matmul(mL_ext(:, :, 2), mL_ext(:, :, 3)) + matmul(mL_ext(:, :, 3), mL_ext(:, :, 2)))
+      ops(:, :, 6) = 0.5_rp*(matmul(mL_ext(:, :, 3), mL_ext(:, :, 1)) + matmul(mL_ext(:, :, 1), mL_ext(:, :, 3)))
+
+      nv = this%en%channels_ldos + 10
+      nrec = this%lattice%nrec
+      allocate (ene(nv), qspec(6, nv, nrec), qmom(3, 6, nrec), qcum(6, nv, nrec))
+      ene = this%en%ene(1:nv)
+      sym_i = 0
+      if (this%control%sym_term) sym_i = 1
+      handle = rsrec_gpu_context()
+      call g_timer%start('spectra-gpu')
+      if (trim(this%control%recur) == 'chebyshev') then
+         rc = rsrec_chebyshev_spectra(handle, 6_c_int, c_loc(ops), int(nv, c_int), c_loc(ene), real(this%en%energy_min, c_double), &
+                                      real(this%en%energy_max, c_double), int(start_atom - 1, c_int), int(nrec, c_int), c_loc(qspec))
+      else
+         rc = rsrec_block_spectra(handle, 6_c_int, c_loc(ops), int(nv, c_int), c_loc(ene), 0.0_c_double, 0.0_c_double, sym_i, &
+                                  int(start_atom - 1, c_int), int(nrec, c_int), c_loc(qspec))
+      end if
+      call g_timer%stop('spectra-gpu')
+      if (rc /= 0) call g_logger%fatal('rsrec_'//trim(this%control%recur)//'_spectra: '//rsrec_error_string(handle), __FILE__, __LINE__)
+      this%n_device_spectra = this%n_device_spectra + 1
+      ! (the handle's resident image is now the six-row one, not the 15 rows of ensure_spectra: spectra_tail(resident = .true.) is only ever
+      ! called from ensure_spectra, right behind its own spectra call; every later repeat (ensure_tail) passes the type's copy this%spec)
+      call g_timer%start('moment-integrals-gpu')
+      rc = rsrec_spectra_integrals(handle, 6_c_int, c_null_ptr, 6_c_int, c_null_ptr, int(nv, c_int), c_loc(ene), int(this%en%nv1, c_int), &
+                                   int(this%nv1, c_int), real(this%en%edel, c_double), real(this%e1, c_double), real(this%en%fermi, c_double), &
+                                   int(end_atom - start_atom + 1, c_int), int(start_atom - 1, c_int), int(nrec, c_int), c_loc(qmom), c_loc(qcum))
+      call g_timer%stop('moment-integrals-gpu')
+      if (rc /= 0) call g_logger%fatal('rsrec_spectra_integrals: '//rsrec_error_string(handle), __FILE__, __LINE__)
+      this%n_device_tail = this%n_device_tail + 1
+
+      do na = start_atom, end_atom
+         fnamequad = trim(this%symbolic_atom(this%lattice%nbulk + na)%element%symbol)//"_orbquadene.out"
+         unitquad = (rank + 1)*132 + na
+         open (unit=unitquad, file=fnamequad, status='replace', action='write')
+         do ie = 1, nv
+            qe = qcum(:, ie, na)
+            write (unitquad, '(9es16.6)') this%en%ene(ie) - this%en%fermi, &
+               -(qe(1)/pi), -(qe(2)/pi), -(qe(3)/pi), &
+               -(qe(4)/pi), -(qe(5)/pi), -(qe(6)/pi), &
+               -((qe(1) - qe(2))/pi), &
+               -((2.0_rp*qe(3) - qe(1) - qe(2))/pi)
+         end do
+         rewind (unitquad)
+         close (unitquad)
+
+         q = -(qmom(1, :, na)/pi)
+         qx2y2 = q(1) - q(2)
+         q3z2r2 = 2.0_rp*q(3) - q(1) - q(2)
+
+         call g_logger%info('Orbital quadrupoles of atom'//fmt('i4', na)// &
+                            ' Qxx Qyy Qzz Qxy Qyz Qzx = '// &
+                            fmt('f10.6', q(1))//' '//fmt('f10.6', q(2))//' '//fmt('f10.6', q(3))//' '// &
+                            fmt('f10.6', q(4))//' '//fmt('f10.6', q(5))//' '//fmt('f10.6', q(6)), &
+                            __FILE__, __LINE__)
+         call g_logger%info('Traceless orbital quadrupoles of atom'//fmt('i4', na)// &
+                            ' Qx2y2 Q3z2r2 = '// &
+                            fmt('f10.6', qx2y2)//' '//fmt('f10.6', q3z2r2), &
+                            __FILE__, __LINE__)
+      end do
    end subroutine gpu_calculate_orbital_quadrupoles
 
    !> calculate_moments (bands.f90:409-524): dspd from the image and the (mixed) moment directions, the tail restated.  Local-axis runs
@@ -494,7 +713,8 @@ contains
       real(rp) :: sgef, pmef, smef, isgn, mnorm
       real(rp), dimension(3) :: mom
       real(rp), dimension(this%en%channels_ldos + 10) :: y
-      real(rp), dimension(3, atoms_per_process) :: mom_prev
+      real(rp), dimension(3, atoms_per_process) :: mom_prev, mom_used
+      real(rp), dimension(3) :: band_int
 #ifdef USE_MPI
       integer :: pot_size
       real(rp), dimension(:, :), allocatable :: T_comm
@@ -513,13 +733,14 @@ contains
       end do
 
       call this%calculate_orbital_moments()
-      call ensure_spectra(this)
+      call ensure_tail(this)
 
       this%dspd(:, :, :) = 0.0d0
       do na_glob = start_atom, end_atom
          na = g2l_map(na_glob)
          plusbulk = this%lattice%nbulk + na_glob
          mom = this%symbolic_atom(plusbulk)%potential%mom
+         mom_used(:, na) = mom
          do isp = 1, 2
             isgn = (-1.0d0)**(isp - 1)
             soff = 3*(isp - 1)
@@ -553,11 +774,23 @@ contains
                nsp = 1
             end if
             soff = 3*(nsp - 1)
-            y(:) = this%dspd(i, :, na)
             sgef = 0.0d0; pmef = 0.0d0; smef = 0.0d0
-            call simpson_m(sgef, this%en%edel, this%en%fermi, this%nv1, y, this%e1, 0, this%en%ene)
-            call simpson_m(pmef, this%en%edel, this%en%fermi, this%nv1, y, this%e1, 1, this%en%ene)
-            call simpson_m(smef, this%en%edel, this%en%fermi, this%nv1, y, this%e1, 2, this%en%ene)
+            if (this%device_tail) then
+               ! the dspd row is a combination of four rows of the image (see above), and so are its integrals
+               l = i - soff
+               isgn = (-1.0d0)**(nsp - 1)
+               mom = mom_used(:, na)
+               band_int(:) = (-this%tail_mom(:, l, na_glob) - isgn*mom(3)*this%tail_mom(:, 9 + l, na_glob) &
+                              - isgn*mom(2)*this%tail_mom(:, 6 + l, na_glob) - isgn*mom(1)*this%tail_mom(:, 3 + l, na_glob))*0.5d0/pi
+               sgef = band_int(1); pmef = band_int(2); smef = band_int(3)
+            else
+               y(:) = this%dspd(i, :, na)
+               call g_timer%start('moment-integrals-host')
+               call simpson_m(sgef, this%en%edel, this%en%fermi, this%nv1, y, this%e1, 0, this%en%ene)
+               call simpson_m(pmef, this%en%edel, this%en%fermi, this%nv1, y, this%e1, 1, this%en%ene)
+               call simpson_m(smef, this%en%edel, this%en%fermi, this%nv1, y, this%e1, 2, this%en%ene)
+               call g_timer%stop('moment-integrals-host')
+            end if
             this%symbolic_atom(plusbulk)%potential%gravity_center(i - soff, nsp) = (pmef/sgef) - this%symbolic_atom(plusbulk)%potential%vmad
             this%symbolic_atom(plusbulk)%potential%ql(1, i - soff - 1, nsp) = sgef
             this%symbolic_atom(plusbulk)%potential%ql(2, i - soff - 1, nsp) = 0.0d0

@@ -183,6 +183,18 @@ module rsrec_binding
          integer(c_int) :: rc
       end function
 
+      ! the integrals behind the spectra: mom(p+1, s, site) = simpson_m(.., nexp = p) and cum(s, ie, site) = simpson_f(.., EF = ene(ie), T = 0) of
+      ! the series y = comb . spec (comb = NULL: the rows themselves); spec = NULL: the image the last spectra call left on the device
+      function rsrec_spectra_integrals(handle, nop, spec, nser, comb, nen, ene, nv1, nv1_fermi, edel, e1, fermi, nsites, site_offset, &
+                                       nsites_total, mom, cum) bind(C, name='rsrec_spectra_integrals') result(rc)
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: handle
+         integer(c_int), value :: nop, nser, nen, nv1, nv1_fermi, nsites, site_offset, nsites_total
+         real(c_double), value :: edel, e1, fermi
+         type(c_ptr), value :: spec, comb, ene, mom, cum
+         integer(c_int) :: rc
+      end function
+
       ! the Kubo-Bastin conductivity integrand integrand_at(l,l,:,v), factor applied, without gamma_nm (conductivity.f90:158-281)
       function rsrec_kubo_integrand(handle, nvec, cond_ll, mu_nm, nen, ene, energy_min, energy_max, integrand) &
          bind(C, name='rsrec_kubo_integrand') result(rc)

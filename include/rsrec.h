@@ -219,6 +219,34 @@ int rsrec_block_spectra(rsrec_t *h, int nop, const double *ops, int nen, const d
 int rsrec_chebyshev_spectra(rsrec_t *h, int nop, const double *ops, int nen, const double *ene, double energy_min, double energy_max,
                         int site_offset, int nsites_total, double *spec);
 
+/* The integrals that follow the spectra in an SCF iteration (bands.f90:476-496, :807-832, :1129-1143, :1040-1060), on the device.
+ * A series is a fixed-order real combination of the spectra rows of one site,
+ *   y(s, i, site) = 0.0 + sum_k comb(k, s, site) spec(k, i, site),  k ascending, no FMA contraction
+ * (dx / dy / dz, the six dspd rows with the site's moment direction, the L and Q rows), and every series gets
+ *   cum(s, i, site) = simpson_f(ene, EF = ene(i), nv1, y(s, :, site), fermi = .true., .false., T = 0)   for every i of the mesh
+ *   mom(p+1, s, site) = simpson_m(.., H = edel, EF = fermi, NPTS = nv1_fermi, y(s, :, site), EA = e1, nexp = p, ene),  p = 0, 1, 2
+ * (math.f90:1600-1632, :1579-1598, the end term (EF - EA)/6 included when e1 /= fermi).  cum costs O(nen) per series: at T = 0 the Fermi
+ * weights are exactly 1, 0.5, 0, the triples below a limit are a running sum shared by all limits, and only the one or two triples that
+ * hold the limit differ (kernels_moments.hpp).  For finite input cum carries the bits of the rule evaluated limit by limit; every index
+ * above nen contributes zero (the convention of kernels_simpson.hpp).  No atomics, fixed order: results are identical run to run.
+ *   spec : real (nop, nen, nsites_total), HOST or DEVICE memory (detected), the zero-padded image of the spectra calls; the sites
+ *          site_offset+1 .. site_offset+nsites are read.  NULL: the image the last rsrec_block_spectra / rsrec_chebyshev_spectra call on
+ *          this handle produced -- those calls keep it on the handle (nop nen nsites doubles) until the resident chains are dropped; nop,
+ *          nen, nsites, site_offset and nsites_total must then be that call's.  With spec given neither lattice nor Hamiltonian is needed.
+ *   comb : real (nop, nser, nsites), HOST or DEVICE memory, or NULL: the series are the rows themselves (nser = nop).
+ *          1 <= nop <= 32, 1 <= nser <= RSREC_MOMENT_NSER_MAX.
+ *   ene  : real (nen), host; ascending by more than 1e-12 per point (what makes the weights exact).  nv1: the mesh's nv1 of the cumulative
+ *          rule, nen >= nv1 + 9.  nv1_fermi, edel, e1, fermi: bands%nv1, energy%edel, bands%e1, energy%fermi; 1 <= nv1_fermi <= nen - 2.
+ *   mom  : real (3, nser, nsites_total) out;  cum : real (nser, nen, nsites_total) out -- zero-padded images like spec, each HOST or DEVICE
+ *          memory (detected); either may be NULL, not both.
+ * RSREC_ERR_ARG with a message (the handle stays usable) for: no resident image or one of another shape; nen < nv1 + 9; nv1_fermi out of
+ * range; non-finite edel, e1 or fermi; nop or nser out of range; a mesh that does not ascend.
+ * rsrec_get_timing: out[0] device ms of the call. */
+#define RSREC_MOMENT_NSER_MAX 64
+int rsrec_spectra_integrals(rsrec_t *h, int nop, const double *spec, int nser, const double *comb, int nen, const double *ene, int nv1,
+                            int nv1_fermi, double edel, double e1, double fermi, int nsites, int site_offset, int nsites_total,
+                            double *mom, double *cum);
+
 /* Chebyshev (KPM, moment doubling) recursion.  Replaces chebyshev_recur (recursion.f90:3057-3130) with
  * cheb_0th_mom (:2145), cheb_1st_mom[_hoh] (:2169/:2245), chebyshev_recur_ll[_hoh] (:2495/:2605).
  *   a, b : scale and shift, a = (energy_max-energy_min)/(2-0.3), b = (energy_max+energy_min)/2 (:3078-3079)

@@ -178,3 +178,42 @@ def band_moments(dspd, h, ef, npts, ea, ene, vmad=0.0):
             cg[i, s] = (pm / sg) - vm[s]
             q3[i, s] = sm - 2.0 * (pm / sg) * pm + ((pm / sg) ** 2) * sg
     return occ, cg, q3
+
+
+#: the series groups of ``series_table`` and the rows each adds
+SERIES_GROUPS = OrderedDict([("spin", ("dx", "dy", "dz")), ("dspd", tuple("dspd%d" % i for i in range(1, 7))), ("orbital", L_NAMES),
+                             ("quadrupole", Q_NAMES)])
+
+
+def series_table(mom, names=SCF_OPERATORS, groups=("spin", "dspd", "orbital"), scaled=False):
+    """The ``comb`` argument of ``Green.spectra_integrals``: (nop, nser, nsites), ``y(s, i, site) = sum_k comb[k, s, site] spec[k, i, site]``,
+    and the names of its series.  ``mom`` (3, nsites): the unit vectors potential%mom of the sites.  Groups, in the order asked for:
+
+    ``spin``: dx, dy, dz, the s + p + d sums of the x, y, z brackets (``projected_dos``);
+    ``dspd``: the six rows l + 3 (isp - 1) of ``spin_resolved_dos`` with the site's moment direction;
+    ``orbital``: the Lx, Ly, Lz rows (``orbital_integrands``);  ``quadrupole``: the six Q rows.
+
+    The integrals are linear, so the reference's constant factors can be applied to a series or to its integrals.  ``scaled=False`` (what
+    the Fortran drop-in passes) leaves them to the caller: -1/pi on ``spin``, 0.5/pi on ``dspd``.  ``scaled=True`` puts them into the table:
+    ``comb . spec`` then equals ``projected_dos`` / ``spin_resolved_dos`` / ``orbital_integrands`` up to the rounding of the products."""
+    mom = np.asarray(mom, dtype=np.float64).reshape(3, -1)
+    ns = mom.shape[1]
+    names = list(names)
+    ser = [n for g in groups for n in SERIES_GROUPS[g]]
+    comb = np.zeros((len(names), len(ser), ns), order="F")
+    for g in groups:
+        for n in SERIES_GROUPS[g]:
+            s = ser.index(n)
+            if g == "spin":
+                for l in ORBITALS:
+                    comb[names.index("P%s%s" % (n[1], l)), s, :] = -1.0 / np.pi if scaled else 1.0
+            elif g == "dspd":
+                i = int(n[4:]) - 1
+                isgn, l = (-1.0) ** (i // 3), list(ORBITALS)[i % 3]
+                f = 0.5 / np.pi if scaled else 1.0
+                comb[names.index("P0" + l), s, :] = -f
+                for c, m in zip("xyz", mom):
+                    comb[names.index("P%s%s" % (c, l)), s, :] = -isgn * m * f
+            else:
+                comb[names.index(n), s, :] = 1.0
+    return comb, ser

@@ -38,6 +38,7 @@
 #include "kernels_green.hpp"
 #include "kernels_ldos.hpp"
 #include "kernels_spectra.hpp"
+#include "kernels_moments.hpp"
 #include "kernels_kubo.hpp"
 #include "kernels_cond.hpp"
 #include "kernels_exchange.hpp"
@@ -130,6 +131,10 @@ struct rsrec_handle {
                                       // given back with d_cond
     DevBuf d_bsqrt, d_term, d_gim, d_ldos;   // stages on resident coefficients: sqrt(B^2), terminators; LDOS stage: Im g0_jj, output images
     DevBuf d_ops, d_spec;                    // spectra stage: operators (+ their traces with the Chebyshev moments), Im Tr(O g0) of the rank's sites
+    // the image the last spectra call left in d_spec ([site][nen][nop] of the rank's sites), for rsrec_spectra_integrals(spec = NULL):
+    // nop = 0: none.  Dropped where the resident chains are dropped.
+    struct SpecImage { int nop = 0, nen = 0, n = 0, site_offset = 0, nsites_total = 0; } spec_res;
+    DevBuf d_mint;                           // rsrec_spectra_integrals: uploaded inputs | series | running sums | mesh | output images
     void* pin = nullptr;              // pinned host staging buffer: every per-call transfer goes through it (see xfer_*)
     size_t pin_bytes = 0;
     DevBuf d_frags, d_vec[6], d_partial, d_partial2, d_coefA, d_coefB, d_bmats, d_status, d_seed, d_seedcoef, d_mu, d_scal, d_zsqr;
@@ -1662,7 +1667,7 @@ int run_block_lanczos(rsrec_t* h, int nchains, int nseed, const int32_t* seed_at
     const size_t velems = RC.velems, cstride = (size_t)lld * BLK, orth_lds = TILE_ATOMS * BLK * sizeof(double2);
     // the coefficients of ALL chains of the call stay on the device (resident input of rsrec_pack_diag / rsrec_block_ldos): reserved before
     // the batch is planned from the free memory
-    h->res_kind = 0;
+    h->res_kind = 0; h->spec_res.nop = 0;
     HIPCK(h, h->d_coefA.reserve((size_t)nchains * lld * BLK * sizeof(double2)));
     HIPCK(h, h->d_coefB.reserve((size_t)nchains * lld * BLK * sizeof(double2)));
     if (rot) {                                          // the rotations of all chains, once per call (k_rotate_coef)
@@ -2536,6 +2541,7 @@ extern "C" int rsrec_block_spectra(rsrec_t* h, int nop, const double* ops, int n
                                    int site_offset, int nsites_total, double* spec) {
     if (!h) return RSREC_ERR_ARG;
     XFER(spectra_check(h, "rsrec_block_spectra", nop, ops, spec));
+    h->spec_res.nop = 0;
     const size_t obytes = (size_t)nop * BLK * sizeof(double2), per_site = (size_t)nop * nen;
     SiteStage S;
     XFER(site_stage_begin(h, S, "rsrec_block_spectra", 1, nen, ene, 0.0, 0.0, site_offset, nsites_total, h->d_spec, per_site));
@@ -2553,7 +2559,9 @@ extern "C" int rsrec_block_spectra(rsrec_t* h, int nop, const double* ops, int n
     HIPCK(h, hipGetLastError());
     hipEvent_t k1 = next_event(h);
     XFER(spectra_deliver(h, S.d_out, per_site, S.n, site_offset, nsites_total, spec));
-    return site_stage_end(h, S, S.k0, k1, next_event(h));   // hop: the Green kernel with its epilogue; rest: zsqr + terminator + delivery
+    XFER(site_stage_end(h, S, S.k0, k1, next_event(h)));    // hop: the Green kernel with its epilogue; rest: zsqr + terminator + delivery
+    h->spec_res.nop = nop; h->spec_res.nen = nen; h->spec_res.n = S.n; h->spec_res.site_offset = site_offset; h->spec_res.nsites_total = nsites_total;
+    return RSREC_OK;
 }
 
 // Im Tr(O_k g0) of green%chebyshev_green for the sites of the last rsrec_chebyshev call, from the moments it left on the device:
@@ -2562,6 +2570,7 @@ extern "C" int rsrec_chebyshev_spectra(rsrec_t* h, int nop, const double* ops, i
                                        int site_offset, int nsites_total, double* spec) {
     if (!h) return RSREC_ERR_ARG;
     XFER(spectra_check(h, "rsrec_chebyshev_spectra", nop, ops, spec));
+    h->spec_res.nop = 0;
     const size_t obytes = (size_t)nop * BLK * sizeof(double2), per_site = (size_t)nop * nen;
     SiteStage S;
     XFER(site_stage_begin(h, S, "rsrec_chebyshev_spectra", 2, nen, ene, energy_min, energy_max, site_offset, nsites_total, h->d_spec, per_site));
@@ -2585,7 +2594,82 @@ extern "C" int rsrec_chebyshev_spectra(rsrec_t* h, int nop, const double* ops, i
     HIPCK(h, hipGetLastError());
     hipEvent_t k1 = next_event(h);
     XFER(spectra_deliver(h, S.d_out, per_site, S.n, site_offset, nsites_total, spec));
-    return site_stage_end(h, S, k0, k1, next_event(h));     // hop: the energy sum alone; rest: the operator traces + delivery
+    XFER(site_stage_end(h, S, k0, k1, next_event(h)));      // hop: the energy sum alone; rest: the operator traces + delivery
+    h->spec_res.nop = nop; h->spec_res.nen = nen; h->spec_res.n = S.n; h->spec_res.site_offset = site_offset; h->spec_res.nsites_total = nsites_total;
+    return RSREC_OK;
+}
+// The integrals behind the spectra (kernels_moments.hpp): the series y = comb . spec of every site, their cumulative Simpson integrals up to
+// every mesh energy (T = 0, a prefix of the rule) and their simpson_m integrals of orders 0, 1, 2 up to the Fermi level.  Reads no chains:
+// spec is the caller's image or the one the last spectra call left in d_spec, so no SiteStage -- only its image rules (site_offset,
+// nsites_total, host or device memory) and its timing apply.
+extern "C" int rsrec_spectra_integrals(rsrec_t* h, int nop, const double* spec, int nser, const double* comb, int nen, const double* ene, int nv1,
+                                       int nv1_fermi, double edel, double e1, double fermi, int nsites, int site_offset, int nsites_total,
+                                       double* mom, double* cum) {
+    const char* who = "rsrec_spectra_integrals";
+    if (!h) return RSREC_ERR_ARG;
+    if (!ene) return fail(h, RSREC_ERR_ARG, "%s: bad argument: ene is NULL", who);
+    if (!mom && !cum) return fail(h, RSREC_ERR_ARG, "%s: bad argument: mom and cum are both NULL", who);
+    if (nsites < 1 || site_offset < 0) return fail(h, RSREC_ERR_ARG, "%s: bad argument: nsites = %d, site_offset = %d", who, nsites, site_offset);
+    if (nv1 < 1) return fail(h, RSREC_ERR_ARG, "%s: bad argument: nv1 = %d", who, nv1);
+    if (nop < 1 || nop > SPECTRA_MAX_OPS) return fail(h, RSREC_ERR_ARG, "%s: nop = %d outside 1..%d", who, nop, SPECTRA_MAX_OPS);
+    if (nser < 1 || nser > MOMENT_MAX_SERIES) return fail(h, RSREC_ERR_ARG, "%s: nser = %d outside 1..%d", who, nser, MOMENT_MAX_SERIES);
+    if (!comb && nser != nop) return fail(h, RSREC_ERR_ARG, "%s: without comb the series are the %d rows, not nser = %d", who, nop, nser);
+    if (site_offset + nsites > nsites_total) return fail(h, RSREC_ERR_ARG, "%s: sites %d..%d outside 1..%d", who, site_offset + 1, site_offset + nsites, nsites_total);
+    if (nen < nv1 + 9) return fail(h, RSREC_ERR_ARG, "%s: nen = %d below nv1 + 9 = %d, the points the rule reads", who, nen, nv1 + 9);
+    if (nv1_fermi < 1 || nv1_fermi + 2 > nen) return fail(h, RSREC_ERR_ARG, "%s: nv1_fermi = %d outside 1..nen - 2 = %d", who, nv1_fermi, nen - 2);
+    if (!std::isfinite(edel) || !std::isfinite(e1) || !std::isfinite(fermi)) return fail(h, RSREC_ERR_ARG, "%s: edel, e1 and fermi must be finite", who);
+    // the prefix form rests on Fermi weights that are exactly 1, 0.5, 0: kBT = 1e-15 against an ascending mesh of step > 1e-12
+    for (int k = 0; k + 1 < nen; ++k)
+        if (!(ene[k + 1] - ene[k] > 1.0e-12)) return fail(h, RSREC_ERR_ARG, "%s: the mesh must ascend by more than 1e-12 per point (ene(%d), ene(%d))", who, k + 1, k + 2);
+    if (!spec) {
+        const auto& R = h->spec_res;
+        if (R.nop == 0) return fail(h, RSREC_ERR_ARG, "%s: no spectra image resident (call rsrec_block_spectra / rsrec_chebyshev_spectra first, or pass spec)", who);
+        if (R.nop != nop || R.nen != nen || R.n != nsites || R.site_offset != site_offset || R.nsites_total != nsites_total)
+            return fail(h, RSREC_ERR_ARG, "%s: the resident image is (%d, %d) for sites %d..%d of %d, the call asks for (%d, %d) for sites %d..%d of %d", who, R.nop, R.nen,
+                        R.site_offset + 1, R.site_offset + R.n, R.nsites_total, nop, nen, site_offset + 1, site_offset + nsites, nsites_total);
+    }
+    HIPCK(h, hipSetDevice(h->device));
+    const size_t n = (size_t)nsites, slab = (size_t)nop * nen * n, ncomb = comb ? (size_t)nop * nser * n : 0;
+    const int ntrip = (nv1 + 9) / 2;
+    const bool spec_up = spec && !is_device_ptr(spec), comb_up = comb && !is_device_ptr(comb);
+    const bool cum_dev = cum && is_device_ptr(cum), mom_dev = mom && is_device_ptr(mom);
+    const size_t ncum = (size_t)nser * nen * nsites_total, nmom = (size_t)3 * nser * nsites_total;
+    // the scratch: uploaded spec | uploaded comb | series | running sums | mesh | cum image | mom image (each only where it is needed)
+    const size_t o_comb = spec_up ? slab : 0, o_y = o_comb + (comb_up ? ncomb : 0), o_p = o_y + (comb ? (size_t)nser * nen * n : 0);
+    const size_t o_ene = o_p + (cum ? (size_t)nser * (ntrip + 1) * n : 0), o_cum = o_ene + nen, o_mom = o_cum + (cum && !cum_dev ? ncum : 0);
+    HIPCK(h, h->d_mint.reserve((o_mom + (mom && !mom_dev ? nmom : 0)) * sizeof(double)));
+    double* W = h->d_mint.as<double>();
+    const double* d_spec = !spec ? h->d_spec.as<double>() : spec + (size_t)site_offset * nop * nen;
+    if (spec_up) { XFER(xfer_h2d(h, W, d_spec, slab * sizeof(double))); d_spec = W; }
+    const double* d_comb = comb;
+    if (comb_up) { XFER(xfer_h2d(h, W + o_comb, comb, ncomb * sizeof(double))); d_comb = W + o_comb; }
+    double* d_ene = W + o_ene;
+    XFER(xfer_h2d(h, d_ene, ene, (size_t)nen * sizeof(double)));
+    reset_timing(h);
+    hipEvent_t e0 = next_event(h);
+    const unsigned gx = (unsigned)(((size_t)nen * nser + MI_WIDTH - 1) / MI_WIDTH);
+    const double* d_y = d_spec;                      // without comb the series are the rows where they lie
+    int ld = nop;
+    if (comb) {
+        k_moment_series<<<dim3(gx, nsites), MI_WIDTH, 0, h->stream>>>(nop, nser, nen, d_spec, d_comb, W + o_y);
+        d_y = W + o_y; ld = nser;
+    }
+    double* o_cum_p = cum_dev ? cum : W + o_cum;
+    double* o_mom_p = mom_dev ? mom : W + o_mom;
+    if (cum) {
+        k_moment_prefix<<<(unsigned)((nser * n + MI_WIDTH - 1) / MI_WIDTH), MI_WIDTH, 0, h->stream>>>(nser, ld, nen, ntrip, nsites, d_y, W + o_p);
+        k_moment_cum<<<dim3(gx, nsites_total), MI_WIDTH, 0, h->stream>>>(nser, ld, nen, nv1, site_offset, nsites, d_ene, d_y, W + o_p, o_cum_p);
+    }
+    if (mom)
+        k_moment_fermi<<<(unsigned)((nmom + MI_WIDTH - 1) / MI_WIDTH), MI_WIDTH, 0, h->stream>>>(nser, ld, nen, nv1_fermi, edel, e1, fermi, site_offset, nsites,
+                                                                                              nsites_total, d_ene, d_y, o_mom_p);
+    HIPCK(h, hipGetLastError());
+    hipEvent_t e1v = next_event(h);
+    if (cum && !cum_dev) XFER(xfer_d2h(h, cum, o_cum_p, ncum * sizeof(double)));
+    if (mom && !mom_dev) XFER(xfer_d2h(h, mom, o_mom_p, nmom * sizeof(double)));
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    finish_timing(h, e0, e1v, {});
+    return RSREC_OK;
 }
 
 namespace {
@@ -3135,7 +3219,7 @@ int run_chebyshev(rsrec_t* h, int nsites, int nseed, const int32_t* seed_atoms, 
     const size_t velems = RC.velems, mstride = (size_t)nmom * BLK;
     // the moments of ALL chains of the call stay on the device (rsrec_pack_moments): reserved BEFORE the batch is planned from the free
     // memory, so a call over many sites (nrec ~ kk) sizes its vectors around them instead of failing behind them
-    h->res_kind = 0;
+    h->res_kind = 0; h->spec_res.nop = 0;
     HIPCK(h, h->d_mu.reserve((size_t)nsites * nmom * BLK * sizeof(double2)));
     // k_spmm5 forms the new vector in its epilogue (dst = (H src - b src)/a [* 2 - p0]; the default of the matrix-core set); k_mfma_cheb then
     // only sums the Grams and H psi is never held: vector 3 is neither allocated nor cleared
@@ -4001,7 +4085,7 @@ extern "C" int rsrec_orbital_moments(rsrec_t* h, int nseeds, const int32_t* seed
         }
     }
     XFER(whole_lattice_end(h, W));
-    h->res_kind = 0;
+    h->res_kind = 0; h->spec_res.nop = 0;
     return RSREC_OK;
 }
 

@@ -217,6 +217,59 @@ class Green:
                                                   int(site_offset), int(ntot), sptr))
         return spec
 
+    def spectra_integrals(self, nv1, nv1_fermi, edel, e1, fermi, spec=None, comb=None, nop=None, nsites=None, site_offset=0, nsites_total=None,
+                          want=("mom", "cum"), out=None):
+        """The integrals that follow the spectra (``rsrec_spectra_integrals``): for every series ``y = comb . spec`` of every site,
+        ``cum(s, i, site)`` = the reference's ``simpson_f`` (Fermi weights, T = 0) up to every mesh energy ``ene[i]`` and
+        ``mom(p, s, site)`` = its ``simpson_m`` of order p = 0, 1, 2 up to the Fermi level.  Returns ``(mom, cum)``, the zero-padded images
+        (3, nser, nsites_total) and (nser, nen, nsites_total); an entry not in ``want`` is None.
+
+        ``spec``: the image (nop, nen, nsites_total) of ``block_spectra`` / ``chebyshev_spectra``, a numpy array or a device tensor in that
+        memory order; None: the image the last of those calls left on the device (``nop`` must then be given).  ``comb``: (nop, nser,
+        nsites) as ``bands.series_table`` builds it, numpy or device; None: the rows themselves.  ``nv1``: the mesh's nv1 (the cumulative
+        rule reads nv1 + 9 points); ``nv1_fermi, edel, e1, fermi``: bands%nv1, energy%edel, bands%e1, energy%fermi.
+        ``out`` = (mom, cum) raw DEVICE addresses (or None each): written in place, None returned in their stead."""
+        import ctypes as C
+        from .exchange import _any_ptr as P
+        rec = self.recursion
+        nen = len(self.ene)
+        if spec is None:
+            if nop is None:
+                raise ValueError("nop must be given with the resident image")
+            n, ntot = self._sites(site_offset, nsites_total)
+            n = n if nsites is None else int(nsites)
+        else:
+            if not hasattr(spec, "data_ptr"):
+                spec = np.asfortranarray(spec, dtype=np.float64)
+                if spec.ndim != 3 or spec.shape[1] != nen:
+                    raise ValueError("spec must be (nop, %d, nsites_total), got %r" % (nen, spec.shape))
+                nop, ntot = spec.shape[0], spec.shape[2]
+            else:
+                if nop is None or nsites_total is None:
+                    raise ValueError("nop and nsites_total must be given with a device image")
+                ntot = int(nsites_total)
+            n = ntot - site_offset if nsites is None else int(nsites)
+        nop = int(nop)
+        if comb is None:
+            nser = nop
+        elif hasattr(comb, "data_ptr"):
+            nser = int(comb.numel()) // (nop * n)
+        else:
+            comb = np.asfortranarray(comb, dtype=np.float64)
+            if comb.ndim == 2:
+                comb = np.asfortranarray(comb[:, :, None])
+            if comb.shape[0] != nop or comb.shape[2] != n:
+                raise ValueError("comb must be (%d, nser, %d), got %r" % (nop, n, comb.shape))
+            nser = comb.shape[1]
+        out = (None, None) if out is None else out
+        mom = np.zeros((3, nser, ntot), order="F") if "mom" in want and out[0] is None else None
+        cum = np.zeros((nser, nen, ntot), order="F") if "cum" in want and out[1] is None else None
+        pm = C.c_void_p(int(out[0])) if out[0] is not None else P(mom)
+        pc = C.c_void_p(int(out[1])) if out[1] is not None else P(cum)
+        rec._check(rec._L.rsrec_spectra_integrals(rec._h, nop, P(spec), int(nser), P(comb), nen, _ptr(self.ene), int(nv1), int(nv1_fermi), float(edel),
+                                                  float(e1), float(fermi), int(n), int(site_offset), int(ntot), pm, pc))
+        return mom, cum
+
     def ldos(self):
         """Orbital-resolved local density of states, -Im g0_jj / pi (density_of_states.f90:248-260)."""
         d = np.arange(18)
