@@ -59,25 +59,23 @@ shadowed exchange exchange_gpu
 shadowed conductivity conductivity_gpu
 ref include_codes/abspinlib/stdtypes.f90 include_codes/abspinlib/mtprng.f90 include_codes/abspinlib/parameters.f90 include_codes/abspinlib/constants.f90 include_codes/abspinlib/randomnumbers.f90 include_codes/abspinlib/depondt.f90 spin_dynamics.f90 calculation.f90 include_codes/abspinlib/abSpinlib.f90 include_codes/abspinlib/constrain.f90
 LIBOBJS="$OBJS"
+# link <main object name> <program>: the program of oracle/_ref from that main program on the objects above
+link() {
+  "$FC" "$OUT/obj/$1.o" $LIBOBJS -fopenmp -L"$MKLDIR" -lmkl_rt -Wl,-rpath,"$MKLDIR" \
+    -L"$ROOT/rslmtoasa_amd" -lrsrec -Wl,-rpath,'$ORIGIN/../../rslmtoasa_amd' -Wl,-rpath,/opt/rocm/lib \
+    -o "$ROOT/oracle/_ref/$2"
+}
 ref main.f90
-"$FC" "$OUT/obj/main.o" $LIBOBJS -fopenmp -L"$MKLDIR" -lmkl_rt -Wl,-rpath,"$MKLDIR" \
-  -L"$ROOT/rslmtoasa_amd" -lrsrec -Wl,-rpath,'$ORIGIN/../../rslmtoasa_amd' -Wl,-rpath,/opt/rocm/lib \
-  -o "$ROOT/oracle/_ref/rslmto_dropin.x"
+link main rslmto_dropin.x
 # tests/fortran/damping_gpu_driver.f90: the exchange flow up to the pair recursion, then calculate_gilbert_damping / calculate_jij_auxgreen
 # (which the reference's main program leaves commented out), on the same object set
 fc "$ROOT/tests/fortran/damping_gpu_driver.f90" damping_gpu_driver
-"$FC" "$OUT/obj/damping_gpu_driver.o" $LIBOBJS -fopenmp -L"$MKLDIR" -lmkl_rt -Wl,-rpath,"$MKLDIR" \
-  -L"$ROOT/rslmtoasa_amd" -lrsrec -Wl,-rpath,'$ORIGIN/../../rslmtoasa_amd' -Wl,-rpath,/opt/rocm/lib \
-  -o "$ROOT/oracle/_ref/damping_gpu.x"
+link damping_gpu_driver damping_gpu.x
 # tests/fortran/contour_gpu_driver.f90: the same flow, then the Gauss-Legendre contour routines of exchange and bands (GPU types, and in
 # its _plain mode the reference's own types over the same objects)
 fc "$ROOT/tests/fortran/contour_gpu_driver.f90" contour_gpu_driver
-"$FC" "$OUT/obj/contour_gpu_driver.o" $LIBOBJS -fopenmp -L"$MKLDIR" -lmkl_rt -Wl,-rpath,"$MKLDIR" \
-  -L"$ROOT/rslmtoasa_amd" -lrsrec -Wl,-rpath,'$ORIGIN/../../rslmtoasa_amd' -Wl,-rpath,/opt/rocm/lib \
-  -o "$ROOT/oracle/_ref/contour_gpu.x"
+link contour_gpu_driver contour_gpu.x
 # tests/fortran/jijk_gpu_driver.f90: the same flow on an input with trios, then calculate_jijk (GPU type, or the reference's own in plain mode)
 fc "$ROOT/tests/fortran/jijk_gpu_driver.f90" jijk_gpu_driver
-"$FC" "$OUT/obj/jijk_gpu_driver.o" $LIBOBJS -fopenmp -L"$MKLDIR" -lmkl_rt -Wl,-rpath,"$MKLDIR" \
-  -L"$ROOT/rslmtoasa_amd" -lrsrec -Wl,-rpath,'$ORIGIN/../../rslmtoasa_amd' -Wl,-rpath,/opt/rocm/lib \
-  -o "$ROOT/oracle/_ref/jijk_gpu.x"
+link jijk_gpu_driver jijk_gpu.x
 echo "built $ROOT/oracle/_ref/rslmto_dropin.x (zero-edit drop-in: the reference's own main program)"

@@ -106,12 +106,36 @@ contains
       end select
    end function gpu_constructor
 
+   !> What the device routines take alike for the pairs first .. last of lattice%ijpair: the kind of the pair recursion (a control%recur
+   !> without one is fatal), control%sym_term as the library takes it, and same(p) = 1 where pair first + p - 1 is an i == j pair
+   subroutine pair_front(this, first, last, ikind, sym_i, same)
+      class(exchange_gpu), intent(in) :: this
+      integer, intent(in) :: first, last
+      integer(c_int), intent(out) :: ikind, sym_i
+      integer(c_int), dimension(:), allocatable, target, intent(out) :: same
+      integer :: ij
+
+      select case (this%control%recur)
+      case ('block')
+         ikind = 0
+      case ('chebyshev')
+         ikind = 1
+      case default
+         call g_logger%fatal('exchange_gpu: control%recur '//trim(this%control%recur)//' has no pair recursion', __FILE__, __LINE__)
+      end select
+      sym_i = merge(1_c_int, 0_c_int, this%control%sym_term)
+      allocate (same(max(last - first + 1, 0)))
+      do ij = first, last
+         same(ij - first + 1) = merge(1_c_int, 0_c_int, this%lattice%ijpair(ij, 1) == this%lattice%ijpair(ij, 2))
+      end do
+   end subroutine pair_front
+
    !> rsrec_exchange for the pairs start_atom .. end_atom of this rank (get_mpi_variables over njij), on the resident chains of the
    !> pair recursion; the images are reduced over the ranks as :1543-1546 / :1375-1382 reduce theirs.
    subroutine exchange_on_device(this)
       class(exchange_gpu), intent(inout) :: this
-      integer :: nloc, nen, njij, p, ij, side, l, at, ikind
-      integer(c_int) :: rc, sym_i
+      integer :: nloc, nen, njij, p, ij, side, l, at
+      integer(c_int) :: rc, ikind, sym_i
       type(c_ptr) :: ctx
       integer(c_int), dimension(:), allocatable, target :: same
       real(rp), dimension(:), allocatable, target :: ene
@@ -121,24 +145,15 @@ contains
       nen = this%en%channels_ldos + 10
       njij = this%lattice%njij
       nloc = end_atom - start_atom + 1
-      select case (this%control%recur)
-      case ('block')
-         ikind = 0
-      case ('chebyshev')
-         ikind = 1
-      case default
-         call g_logger%fatal('exchange_gpu: control%recur '//trim(this%control%recur)//' has no pair recursion', __FILE__, __LINE__)
-      end select
+      call pair_front(this, start_atom, end_atom, ikind, sym_i, same)
       allocate (xc(13, njij), so(13, njij), fo(13, njij), parts(28, njij), jcum(nen, max(nloc, 0)))
       xc = 0.0_rp; so = 0.0_rp; fo = 0.0_rp; parts = 0.0_rp; jcum = 0.0_rp
       if (nloc > 0) then
-         allocate (same(nloc), ene(nen), dpar(4, 3, 2, nloc))
+         allocate (ene(nen), dpar(4, 3, 2, nloc))
          ene(:) = this%en%ene(1:nen)
          ! d_matrix's parameters of atoms i and j (symbolic_atom.f90:250-255): (c_up + vmad, c_dn + vmad, dele_up, dele_dn) per l
          do ij = start_atom, end_atom
             p = ij - start_atom + 1
-            same(p) = 0
-            if (this%lattice%ijpair(ij, 1) == this%lattice%ijpair(ij, 2)) same(p) = 1
             do side = 1, 2
                at = this%lattice%iz(this%lattice%ijpair(ij, side))
                associate (pot => this%symbolic_atom(at)%potential)
@@ -151,12 +166,10 @@ contains
                end associate
             end do
          end do
-         sym_i = 0
-         if (this%control%sym_term) sym_i = 1
          ctx = rsrec_gpu_context()
          call g_timer%start('exchange-gpu')
          ! coefficients and terminators NULL: the chains recur_b_ij / chebyshev_recur_ij left on the device (i == j pairs: one chain)
-         rc = rsrec_exchange(ctx, int(ikind, c_int), int(nloc, c_int), c_loc(same), int(this%control%lld, c_int), int(nen, c_int), &
+         rc = rsrec_exchange(ctx, ikind, int(nloc, c_int), c_loc(same), int(this%control%lld, c_int), int(nen, c_int), &
                              c_loc(ene), int(this%en%nv1, c_int), real(this%en%fermi, c_double), sym_i, &
                              real(this%en%energy_min, c_double), real(this%en%energy_max, c_double), c_null_ptr, c_null_ptr, &
                              c_null_ptr, c_null_ptr, c_loc(dpar), int(start_atom - 1, c_int), int(njij, c_int), c_loc(xc), c_loc(so), &
@@ -190,6 +203,21 @@ contains
       end if
    end subroutine open_unit
 
+   !> the records of the pair (i, j) in jij.out, dij.out and aij.out (units 20, 30, 40) and its line on unit 99 (:1589-1596, :1905-1912),
+   !> from its column of T_comm_xc: Jij | Dij | Iij
+   subroutine write_pair_records(this, i, j, col)
+      class(exchange_gpu), intent(in) :: this
+      integer, intent(in) :: i, j
+      real(rp), dimension(13), intent(in) :: col
+
+      associate (iz => this%lattice%iz, cr => this%lattice%cr)
+         write (20, '(2i8,2x,3f12.6,2x,1f12.6,1x,f12.6)') iz(i), iz(j), cr(:, j) - cr(:, i), col(1), norm2(cr(:, i) - cr(:, j))
+         write (30, '(2i8,2x,3f12.6,2x,3f12.6,1x,f12.6)') iz(i), iz(j), cr(:, j) - cr(:, i), col(2:4), norm2(cr(:, i) - cr(:, j))
+         write (40, '(2i8,2x,3f12.6,2x,9f12.6,1x,f12.6)') iz(i), iz(j), cr(:, j) - cr(:, i), col(5:13), norm2(cr(:, i) - cr(:, j))
+         write (99, *) 'null', (cr(:, j) + cr(:, i))/2, col(2:4)/norm2(col(2:4))
+      end associate
+   end subroutine write_pair_records
+
    !> calculate_exchange (:1437-1615)
    subroutine gpu_calculate_exchange(this)
       class(exchange_gpu) :: this
@@ -222,13 +250,7 @@ contains
             print '(3f12.6)', this%aij(2, :)
             print '(3f12.6)', this%aij(3, :)
 
-            write (20, '(2i8,2x,3f12.6,2x,1f12.6,1x,f12.6)') &
-               this%lattice%iz(i), this%lattice%iz(j), this%lattice%cr(:, j) - this%lattice%cr(:, i), this%jij, norm2(this%lattice%cr(:, i) - this%lattice%cr(:, j))
-            write (30, '(2i8,2x,3f12.6,2x,3f12.6,1x,f12.6)') &
-               this%lattice%iz(i), this%lattice%iz(j), this%lattice%cr(:, j) - this%lattice%cr(:, i), this%dmi, norm2(this%lattice%cr(:, i) - this%lattice%cr(:, j))
-            write (40, '(2i8,2x,3f12.6,2x,9f12.6,1x,f12.6)') &
-               this%lattice%iz(i), this%lattice%iz(j), this%lattice%cr(:, j) - this%lattice%cr(:, i), this%aij, norm2(this%lattice%cr(:, i) - this%lattice%cr(:, j))
-            write (99, *) 'null', (this%lattice%cr(:, j) + this%lattice%cr(:, i))/2, this%dmi/norm2(this%dmi)
+            call write_pair_records(this, i, j, this%xc(:, njij_glob))
             jtens = 0.0d0
             jtens(1, 1) = this%jij
             jtens(2, 2) = jtens(1, 1)
@@ -342,8 +364,8 @@ contains
    !> calculate_gilbert_damping (:613-743)
    subroutine gpu_calculate_gilbert_damping(this)
       class(exchange_gpu) :: this
-      integer :: nloc, nen, njij, p, ij, side, i, j, k, nv, ief, ikind, lmaxi
-      integer(c_int) :: rc, sym_i
+      integer :: nloc, nen, njij, p, ij, side, i, j, k, nv, ief, lmaxi
+      integer(c_int) :: rc, ikind, sym_i
       type(c_ptr) :: ctx
       real(rp) :: spin_i, diff, factor, distance_alat
       integer(c_int), dimension(:), allocatable, target :: same
@@ -357,14 +379,7 @@ contains
       nen = size(this%en%ene)
       njij = this%lattice%njij
       nloc = end_atom - start_atom + 1
-      select case (this%control%recur)
-      case ('block')
-         ikind = 0
-      case ('chebyshev')
-         ikind = 1
-      case default
-         call g_logger%fatal('exchange_gpu: control%recur '//trim(this%control%recur)//' has no pair recursion', __FILE__, __LINE__)
-      end select
+      call pair_front(this, start_atom, end_atom, ikind, sym_i, same)
       ! :695-702, the closest energy point of the Fermi level (the same for every pair)
       ief = 0; diff = 1000.0_rp
       do nv = 1, nen
@@ -376,22 +391,18 @@ contains
       allocate (at_ef(18, njij), total(9, nen))
       at_ef = 0.0_rp; total = 0.0_rp
       if (nloc > 0) then
-         allocate (same(nloc), ene(nen), tmat(18, 18, 3, 2, nloc))
+         allocate (ene(nen), tmat(18, 18, 3, 2, nloc))
          ene(:) = this%en%ene(1:nen)
          do ij = start_atom, end_atom
             p = ij - start_atom + 1
-            same(p) = 0
-            if (this%lattice%ijpair(ij, 1) == this%lattice%ijpair(ij, 2)) same(p) = 1
             do side = 1, 2
                tmat(:, :, :, side, p) = this%hamiltonian%tmat(:, :, :, this%lattice%iz(this%lattice%ijpair(ij, side)))
             end do
          end do
-         sym_i = 0
-         if (this%control%sym_term) sym_i = 1
          ctx = rsrec_gpu_context()
          call g_timer%start('damping-gpu')
          ! coefficients and terminators NULL: the chains recur_b_ij / chebyshev_recur_ij left on the device (i == j pairs: one chain)
-         rc = rsrec_damping(ctx, int(ikind, c_int), int(nloc, c_int), c_loc(same), int(this%control%lld, c_int), int(nen, c_int), &
+         rc = rsrec_damping(ctx, ikind, int(nloc, c_int), c_loc(same), int(this%control%lld, c_int), int(nen, c_int), &
                             c_loc(ene), int(ief, c_int), sym_i, real(this%en%energy_min, c_double), real(this%en%energy_max, c_double), &
                             c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_loc(tmat), int(start_atom - 1, c_int), int(njij, c_int), &
                             c_loc(at_ef), c_loc(total), c_null_ptr)
@@ -447,8 +458,8 @@ contains
    !> calculate_exchange_gauss_legendre (:1756-1919)
    subroutine gpu_calculate_exchange_gauss_legendre(this)
       class(exchange_gpu) :: this
-      integer :: nloc, njij, p, ij, side, i, j, ikind, fermi_point, njij_glob, at
-      integer(c_int) :: rc, sym_i
+      integer :: nloc, njij, p, ij, side, i, j, fermi_point, njij_glob, at
+      integer(c_int) :: rc, ikind, sym_i
       type(c_ptr) :: ctx
       integer(c_int), dimension(:), allocatable, target :: same
       real(rp), dimension(64), target :: x, w
@@ -457,14 +468,7 @@ contains
 
       njij = this%lattice%njij
       nloc = end_atom - start_atom + 1
-      select case (this%control%recur)
-      case ('block')
-         ikind = 0
-      case ('chebyshev')
-         ikind = 1
-      case default
-         call g_logger%fatal('exchange_gpu: control%recur '//trim(this%control%recur)//' has no pair recursion', __FILE__, __LINE__)
-      end select
+      call pair_front(this, start_atom, end_atom, ikind, sym_i, same)
       allocate (T_comm_xc(13, njij))
       T_comm_xc = 0.0_rp
 
@@ -482,22 +486,18 @@ contains
       end do
 
       if (nloc > 0) then
-         allocate (same(nloc), dmat(9, 9, 2, nloc))
+         allocate (dmat(9, 9, 2, nloc))
          do ij = start_atom, end_atom
             p = ij - start_atom + 1
-            same(p) = 0
-            if (this%lattice%ijpair(ij, 1) == this%lattice%ijpair(ij, 2)) same(p) = 1
             do side = 1, 2
                at = this%lattice%iz(this%lattice%ijpair(ij, side))
                dmat(:, :, side, p) = real(this%hamiltonian%ee(1:9, 1:9, 1, at) - this%hamiltonian%ee(10:18, 10:18, 1, at))
             end do
          end do
-         sym_i = 0
-         if (this%control%sym_term) sym_i = 1
          ctx = rsrec_gpu_context()
          call g_timer%start('exchange-contour-gpu')
          ! coefficients and terminators NULL: the chains recur_b_ij / chebyshev_recur_ij left on the device (i == j pairs: one chain)
-         rc = rsrec_exchange_contour(ctx, int(ikind, c_int), int(nloc, c_int), c_loc(same), int(this%control%lld, c_int), 64_c_int, &
+         rc = rsrec_exchange_contour(ctx, ikind, int(nloc, c_int), c_loc(same), int(this%control%lld, c_int), 64_c_int, &
                                      c_loc(x), c_loc(w), real(this%en%ene(fermi_point), c_double), sym_i, &
                                      real(this%en%energy_min, c_double), real(this%en%energy_max, c_double), c_null_ptr, c_null_ptr, &
                                      c_null_ptr, c_null_ptr, c_loc(dmat), int(start_atom - 1, c_int), int(njij, c_int), &
@@ -535,13 +535,7 @@ contains
             print '(3f12.6)', this%aij(2, :)
             print '(3f12.6)', this%aij(3, :)
             !
-            write (20, '(2i8,2x,3f12.6,2x,1f12.6,1x,f12.6)') &
-               this%lattice%iz(i), this%lattice%iz(j), this%lattice%cr(:, j) - this%lattice%cr(:, i), (this%jij), norm2(this%lattice%cr(:, i) - this%lattice%cr(:, j))
-            write (30, '(2i8,2x,3f12.6,2x,3f12.6,1x,f12.6)') &
-               this%lattice%iz(i), this%lattice%iz(j), this%lattice%cr(:, j) - this%lattice%cr(:, i), (this%dmi), norm2(this%lattice%cr(:, i) - this%lattice%cr(:, j))
-            write (40, '(2i8,2x,3f12.6,2x,9f12.6,1x,f12.6)') &
-               this%lattice%iz(i), this%lattice%iz(j), this%lattice%cr(:, j) - this%lattice%cr(:, i), this%aij, norm2(this%lattice%cr(:, i) - this%lattice%cr(:, j))
-            write (99, *) 'null', (this%lattice%cr(:, j) + this%lattice%cr(:, i))/2, this%dmi/norm2(this%dmi)
+            call write_pair_records(this, i, j, T_comm_xc(:, njij_glob))
          end do
       end if
       close (20)
@@ -581,10 +575,10 @@ contains
    !> lmax /= 2, when the pairs are not exactly the trios' pairs, or when this rank does not hold every pair (more than one rank).
    subroutine gpu_calculate_jijk(this)
       class(exchange_gpu) :: this
-      integer :: ntrio, njij, nen, t, a, l, s, at, ikind, q
+      integer :: ntrio, njij, nen, t, a, l, s, at
       integer :: atoms(3)
       logical :: device
-      integer(c_int) :: rc, sym_i
+      integer(c_int) :: rc, ikind, sym_i
       type(c_ptr) :: ctx
       integer(c_int), dimension(:), allocatable, target :: same
       real(rp), dimension(:), allocatable, target :: ene
@@ -597,10 +591,8 @@ contains
 
       ntrio = this%lattice%njijk
       njij = this%lattice%njij
-      ikind = -1
-      if (this%control%recur == 'block') ikind = 0
-      if (this%control%recur == 'chebyshev') ikind = 1
-      device = ntrio > 0 .and. njij == 3*ntrio .and. start_atom == 1 .and. end_atom == njij .and. ikind >= 0
+      device = ntrio > 0 .and. njij == 3*ntrio .and. start_atom == 1 .and. end_atom == njij .and. &
+               (this%control%recur == 'block' .or. this%control%recur == 'chebyshev')
       if (device) then
          do t = 1, ntrio
             do a = 1, 3
@@ -616,13 +608,9 @@ contains
       end if
 
       nen = this%en%channels_ldos + 10
-      allocate (same(njij), ene(nen), apar(3, 3, 2, 3, ntrio), dmat(9, 9, ntrio), jijk(9, ntrio), uni(3, ntrio), d18(18, 18))
+      allocate (ene(nen), apar(3, 3, 2, 3, ntrio), dmat(9, 9, ntrio), jijk(9, ntrio), uni(3, ntrio), d18(18, 18))
       ene(:) = this%en%ene(1:nen)
       jijk = 0.0_rp
-      do q = 1, njij
-         same(q) = 0
-         if (this%lattice%ijpair(q, 1) == this%lattice%ijpair(q, 2)) same(q) = 1
-      end do
       do t = 1, ntrio
          atoms(:) = int(this%lattice%ijktrio(t, 1:3))
          do a = 1, 3
@@ -645,12 +633,11 @@ contains
          call this%symbolic_atom(this%lattice%iz(atoms(3)))%disp_matrix(d18, uni(:, t), 2, this%lattice%wav)
          dmat(:, :, t) = d18(1:9, 1:9)
       end do
-      sym_i = 0
-      if (this%control%sym_term) sym_i = 1
+      call pair_front(this, 1, njij, ikind, sym_i, same)
       ctx = rsrec_gpu_context()
       call g_timer%start('jijk-gpu')
       ! coefficients and terminators NULL: the chains recur_b_ij / chebyshev_recur_ij left on the device (i == j pairs: one chain)
-      rc = rsrec_spin_lattice(ctx, int(ikind, c_int), int(njij, c_int), c_loc(same), int(this%control%lld, c_int), int(nen, c_int), &
+      rc = rsrec_spin_lattice(ctx, ikind, int(njij, c_int), c_loc(same), int(this%control%lld, c_int), int(nen, c_int), &
                               c_loc(ene), int(this%en%nv1, c_int), real(this%en%fermi, c_double), sym_i, &
                               real(this%en%energy_min, c_double), real(this%en%energy_max, c_double), c_null_ptr, c_null_ptr, &
                               c_null_ptr, c_null_ptr, c_loc(apar), c_loc(dmat), 0_c_int, int(ntrio, c_int), c_loc(jijk), c_null_ptr)

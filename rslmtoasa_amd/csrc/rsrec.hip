@@ -2717,6 +2717,7 @@ struct PairCall {
     double *din, *d_ene, *d_fixed_in, *d_chunk_in, *d_rows, *d_fixed_out, *d_chunk_out;
     int *d_same, *d_cb;
     size_t off_ab, off_bs, off_ai, off_bi;
+    size_t row_doubles, fixed_out, chunk_out;      // doubles of the rows of one pair, of the call's own outputs, of the chunk outputs of one pair
 };
 
 // the chains of one chunk, as the kernels read them
@@ -2737,6 +2738,7 @@ int pair_call_begin(rsrec_t* h, PairCall& c, const char* who, int kind, int npai
     if (kind == 0 && !a_inf && lld < 2) return fail(h, RSREC_ERR_ARG, "%s: the device terminator needs lld >= 2", who);
     c.who = who; c.kind = kind; c.npairs = npairs; c.lld = lld; c.nen = nen; c.per = per;
     c.a_inf = a_inf; c.b_inf = b_inf; c.coef_a = coef_a; c.coef_b = coef_b;
+    c.row_doubles = row_doubles; c.fixed_out = fixed_out; c.chunk_out = chunk_out;
     const int nchains = per * npairs;
     c.resident = coef_a == nullptr;
     int nsame = 0;
@@ -2835,8 +2837,39 @@ int pair_call_chunk(rsrec_t* h, const PairCall& c, int p0, PairChunk& k) {
     return RSREC_OK;
 }
 
-// end of such a call: the status word, the stream, the timing (total; hop = rest = the kernel stages of the chunks)
-int pair_call_end(rsrec_t* h, hipEvent_t e0, const std::vector<std::pair<hipEvent_t, hipEvent_t>>& kev) {
+// an image of such a call for the caller: n doubles at `off` of the call's own outputs
+struct PairImage { double* dst; size_t off, n; };
+
+// The call that pair_call_begin set up: its own outputs zeroed and, where `fermi` is given, the Fermi weights in the first nen doubles
+// of its own inputs; then chunk by chunk the coefficients, stage(p0, k) (the fetch of the chunk's own inputs), kernel(p0, k) and
+// reduce(p0, k) (one launch each, timed together as the kernel stage) and the chunk's outputs and rows to `chunk_out` and `rows`
+// where given; then the images, the status word, the stream and the timing (total; hop = rest = the kernel stages of the chunks).
+template <class Stage, class Kernel, class Reduce>
+int pair_call_run(rsrec_t* h, const PairCall& c, const double* fermi, double* chunk_out, double* rows, std::initializer_list<PairImage> images,
+                  Stage stage, Kernel kernel, Reduce reduce) {
+    reset_timing(h);
+    hipEvent_t e0 = next_event(h);
+    // (a value that runs across the chunks, rsrec_damping's total, lives in these outputs: this one memset is what starts it at zero)
+    HIPCK(h, hipMemsetAsync(c.d_fixed_out, 0, c.fixed_out * sizeof(double), h->stream));
+    if (fermi) k_exchange_fermi<<<(c.nen + 255) / 256, 256, 0, h->stream>>>(c.nen, c.d_ene, *fermi, c.d_fixed_in);
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> kev;
+    for (int p0 = 0; p0 < c.npairs; p0 += c.P) {
+        PairChunk k;
+        XFER(pair_call_chunk(h, c, p0, k));
+        XFER(stage(p0, k));
+        std::pair<hipEvent_t, hipEvent_t> ev;
+        ev.first = next_event(h);
+        kernel(p0, k);
+        HIPCK(h, hipGetLastError());
+        reduce(p0, k);
+        HIPCK(h, hipGetLastError());
+        ev.second = next_event(h);
+        kev.push_back(ev);
+        if (chunk_out) XFER(xc_deliver(h, chunk_out + (size_t)p0 * c.chunk_out, c.d_chunk_out, (size_t)k.np * c.chunk_out));
+        if (rows) XFER(xc_deliver(h, rows + (size_t)p0 * c.row_doubles, c.d_rows, (size_t)k.np * c.row_doubles));
+        if (p0 + c.P < c.npairs) HIPCK(h, hipStreamSynchronize(h->stream));       // the chunk's staging buffers are reused
+    }
+    for (const PairImage& im : images) XFER(xc_deliver(h, im.dst, c.d_fixed_out + im.off, im.n));
     hipEvent_t e1 = next_event(h);
     const int rc = finish_status(h);
     h->t_total_ms = ev_ms(e0, e1);
@@ -2844,6 +2877,22 @@ int pair_call_end(rsrec_t* h, hipEvent_t e0, const std::vector<std::pair<hipEven
     for (auto& pr : kev) h->t_rest_ms += ev_ms(pr.first, pr.second);
     h->t_hop_ms = h->t_rest_ms;
     return rc;
+}
+
+// (a call whose chunks have no inputs of their own)
+int no_stage(int, const PairChunk&) { return RSREC_OK; }
+
+// simpson_f's mesh, for the calls that integrate over the energies
+int check_simpson_mesh(rsrec_t* h, const char* who, int nen, int nv1) {
+    if (nen < nv1 + 9) return fail(h, RSREC_ERR_ARG, "%s: nen = %d < nv1 + 9 = %d (simpson_f integrates to nv1 + 10)", who, nen, nv1 + 9);
+    return RSREC_OK;
+}
+
+// the Chebyshev kernels that keep `shared` bytes of dressed blocks in LDS beside the phase table (those of a pair, or of a trio)
+int check_cheb_lds(rsrec_t* h, const char* who, int kind, int lld, size_t shared, const char* whose) {
+    if (kind == 1 && (size_t)(2 * lld + 2) * sizeof(double2) + sizeof(XcChebLds) + shared > (size_t)64 * 1024)
+        return fail(h, RSREC_ERR_ARG, "%s: lld = %d too deep for the Chebyshev phase table beside the %s's blocks", who, lld, whose);
+    return RSREC_OK;
 }
 
 }  // namespace
@@ -2856,53 +2905,29 @@ extern "C" int rsrec_exchange(rsrec_t* h, int kind, int npairs, const int32_t* s
     if (!h) return RSREC_ERR_ARG;
     if (npairs < 1 || lld < 1 || nv1 < 1 || !same || !ene || !dpar || !xc || !so || !fo || !parts || pair_offset < 0 || npairs_total < pair_offset + npairs)
         return fail(h, RSREC_ERR_ARG, "rsrec_exchange: bad argument");
-    if (nen < nv1 + 9) return fail(h, RSREC_ERR_ARG, "rsrec_exchange: nen = %d < nv1 + 9 = %d (simpson_f integrates to nv1 + 10)", nen, nv1 + 9);
-    const size_t nimg = (size_t)XC_NOUT * npairs_total;
+    XFER(check_simpson_mesh(h, "rsrec_exchange", nen, nv1));
+    const size_t nt = (size_t)npairs_total, nimg = (size_t)XC_NOUT * nt;
     PairCall c;
     // own inputs: fermi weights | dpar;  own outputs: the images (xc, so, fo, parts) and jcum of the chunk
-    int rc = pair_call_begin(h, c, "rsrec_exchange", kind, npairs, same, lld, nen, ene, energy_min, energy_max, a_inf, b_inf, coef_a, coef_b,
-                             (size_t)nen * XC_NINT, (size_t)nen + (size_t)24 * npairs, 0, nimg, (size_t)nen);
-    if (rc) return rc;
-    double* d_ene = c.d_ene;
+    XFER(pair_call_begin(h, c, "rsrec_exchange", kind, npairs, same, lld, nen, ene, energy_min, energy_max, a_inf, b_inf, coef_a, coef_b,
+                         (size_t)nen * XC_NINT, (size_t)nen + (size_t)24 * npairs, 0, nimg, (size_t)nen));
     double* d_fw = c.d_fixed_in;
     double* d_dpar = d_fw + nen;
-    double* d_int = c.d_rows;
     double* d_img = c.d_fixed_out;
-    double* d_jc = c.d_chunk_out;
     XFER(xfer_h2d(h, d_dpar, dpar, (size_t)24 * npairs * sizeof(double)));
-    reset_timing(h);
-    hipEvent_t e0 = next_event(h);
-    HIPCK(h, hipMemsetAsync(d_img, 0, nimg * sizeof(double), h->stream));
-    k_exchange_fermi<<<(nen + 255) / 256, 256, 0, h->stream>>>(nen, d_ene, fermi, d_fw);
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> kev;
-    for (int p0 = 0; p0 < npairs; p0 += c.P) {
-        PairChunk k;
-        rc = pair_call_chunk(h, c, p0, k);
-        if (rc) return rc;
-        const int np = k.np;
-        std::pair<hipEvent_t, hipEvent_t> ev;
-        ev.first = next_event(h);
-        if (kind == 0)
-            k_exchange_block<<<dim3(nen, np), 256, 0, h->stream>>>(lld, nen, d_ene, sym_term, k.ta, k.tb, k.sa, k.sb, c.d_same + p0, c.d_cb + p0, k.c0,
-                                                                d_dpar + (size_t)24 * p0, d_int);
-        else
-            k_exchange_cheb<<<dim3(nen, np), 256, (size_t)c.nm * sizeof(double2), h->stream>>>(c.nm, nen, d_ene, c.ca, c.cb, k.ta, k.sa, c.d_same + p0, c.d_cb + p0,
-                                                                                             k.c0, d_dpar + (size_t)24 * p0, d_int);
-        HIPCK(h, hipGetLastError());
-        k_exchange_integrate<<<np, 128, 0, h->stream>>>(nen, nv1, d_ene, d_fw, d_int, pair_offset + p0, d_img, d_img + (size_t)13 * npairs_total,
-                                                        d_img + (size_t)26 * npairs_total, d_img + (size_t)39 * npairs_total, jcum ? d_jc : nullptr, 0);
-        HIPCK(h, hipGetLastError());
-        ev.second = next_event(h);
-        kev.push_back(ev);
-        if (jcum) XFER(xc_deliver(h, jcum + (size_t)p0 * nen, d_jc, (size_t)np * nen));
-        if (integrand) XFER(xc_deliver(h, integrand + (size_t)p0 * nen * XC_NINT, d_int, (size_t)np * nen * XC_NINT));
-        if (p0 + c.P < npairs) HIPCK(h, hipStreamSynchronize(h->stream));         // the chunk's staging buffers are reused
-    }
-    XFER(xc_deliver(h, xc, d_img, (size_t)13 * npairs_total));
-    XFER(xc_deliver(h, so, d_img + (size_t)13 * npairs_total, (size_t)13 * npairs_total));
-    XFER(xc_deliver(h, fo, d_img + (size_t)26 * npairs_total, (size_t)13 * npairs_total));
-    XFER(xc_deliver(h, parts, d_img + (size_t)39 * npairs_total, (size_t)28 * npairs_total));
-    return pair_call_end(h, e0, kev);
+    return pair_call_run(h, c, &fermi, jcum, integrand, {{xc, 0, 13 * nt}, {so, 13 * nt, 13 * nt}, {fo, 26 * nt, 13 * nt}, {parts, 39 * nt, 28 * nt}}, no_stage,
+        [&](int p0, const PairChunk& k) {
+            if (kind == 0)
+                k_exchange_block<<<dim3(nen, k.np), 256, 0, h->stream>>>(lld, nen, c.d_ene, sym_term, k.ta, k.tb, k.sa, k.sb, c.d_same + p0, c.d_cb + p0, k.c0,
+                                                                      d_dpar + (size_t)24 * p0, c.d_rows);
+            else
+                k_exchange_cheb<<<dim3(nen, k.np), 256, (size_t)c.nm * sizeof(double2), h->stream>>>(c.nm, nen, c.d_ene, c.ca, c.cb, k.ta, k.sa, c.d_same + p0,
+                                                                                                   c.d_cb + p0, k.c0, d_dpar + (size_t)24 * p0, c.d_rows);
+        },
+        [&](int p0, const PairChunk& k) {
+            k_exchange_integrate<<<k.np, 128, 0, h->stream>>>(nen, nv1, c.d_ene, d_fw, c.d_rows, pair_offset + p0, d_img, d_img + 13 * nt, d_img + 26 * nt,
+                                                              d_img + 39 * nt, jcum ? c.d_chunk_out : nullptr, 0);
+        });
 }
 
 // exchange%calculate_gilbert_damping (exchange.f90:674-694) for the pairs of one rank: the nine traces Tr(T_i^k Aij (T_j^l)^H Aji) per
@@ -2915,45 +2940,27 @@ extern "C" int rsrec_damping(rsrec_t* h, int kind, int npairs, const int32_t* sa
         return fail(h, RSREC_ERR_ARG, "rsrec_damping: bad argument");
     if (!tmat) return fail(h, RSREC_ERR_ARG, "rsrec_damping: no torque matrices (tmat is NULL)");
     if (ief < 1 || ief > nen) return fail(h, RSREC_ERR_ARG, "rsrec_damping: ief = %d outside 1..%d", ief, nen);
-    const size_t nimg = (size_t)DP_NROW * npairs_total, ntot = (size_t)9 * nen, rdoubles = (size_t)nen * DP_NROW;
+    const size_t nimg = (size_t)DP_NROW * npairs_total, ntot = (size_t)9 * nen;
     PairCall c;
-    // own chunk inputs: tmat of the chunk's pairs;  own outputs: the at_ef image | total
-    int rc = pair_call_begin(h, c, "rsrec_damping", kind, npairs, same, lld, nen, ene, energy_min, energy_max, a_inf, b_inf, coef_a, coef_b, rdoubles, 0,
-                             (size_t)2 * DP_TMAT, nimg + ntot, 0);
-    if (rc) return rc;
+    // own chunk inputs: tmat of the chunk's pairs;  own outputs: the at_ef image | total, k_damping_reduce adding to it chunk after chunk
+    XFER(pair_call_begin(h, c, "rsrec_damping", kind, npairs, same, lld, nen, ene, energy_min, energy_max, a_inf, b_inf, coef_a, coef_b,
+                         (size_t)nen * DP_NROW, 0, (size_t)2 * DP_TMAT, nimg + ntot, 0));
     double* d_img = c.d_fixed_out;
-    double* d_tot = d_img + nimg;
-    reset_timing(h);
-    hipEvent_t e0 = next_event(h);
-    // (total's running value lives in d_tot across the chunks, k_damping_reduce adding to it: this one memset is what starts it at zero)
-    HIPCK(h, hipMemsetAsync(d_img, 0, (nimg + ntot) * sizeof(double), h->stream));
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> kev;
-    for (int p0 = 0; p0 < npairs; p0 += c.P) {
-        PairChunk k;
-        rc = pair_call_chunk(h, c, p0, k);
-        if (rc) return rc;
-        const int np = k.np;
-        const double* tm = nullptr;
-        XFER(xc_fetch(h, tmat + (size_t)p0 * 2 * DP_TMAT, c.d_chunk_in, (size_t)np * 2 * DP_TMAT, &tm));
-        std::pair<hipEvent_t, hipEvent_t> ev;
-        ev.first = next_event(h);
-        if (kind == 0)
-            k_damping_block<<<dim3(nen, np), 256, 0, h->stream>>>(lld, nen, c.d_ene, sym_term, k.ta, k.tb, k.sa, k.sb, c.d_same + p0, c.d_cb + p0, k.c0,
-                                                               reinterpret_cast<const double2*>(tm), c.d_rows);
-        else
-            k_damping_cheb<<<dim3(nen, np), 256, (size_t)c.nm * sizeof(double2), h->stream>>>(c.nm, nen, c.d_ene, c.ca, c.cb, k.ta, k.sa, c.d_same + p0, c.d_cb + p0,
-                                                                                            k.c0, reinterpret_cast<const double2*>(tm), c.d_rows);
-        HIPCK(h, hipGetLastError());
-        k_damping_reduce<<<(unsigned)((ntot + (size_t)DP_NROW * np + 255) / 256), 256, 0, h->stream>>>(nen, np, ief - 1, c.d_rows, pair_offset + p0, d_img, d_tot);
-        HIPCK(h, hipGetLastError());
-        ev.second = next_event(h);
-        kev.push_back(ev);
-        if (rows) XFER(xc_deliver(h, rows + (size_t)p0 * rdoubles, c.d_rows, (size_t)np * rdoubles));
-        if (p0 + c.P < npairs) HIPCK(h, hipStreamSynchronize(h->stream));         // the chunk's staging buffers are reused
-    }
-    XFER(xc_deliver(h, at_ef, d_img, nimg));
-    XFER(xc_deliver(h, total, d_tot, ntot));
-    return pair_call_end(h, e0, kev);
+    const double* tm = nullptr;
+    return pair_call_run(h, c, nullptr, nullptr, rows, {{at_ef, 0, nimg}, {total, nimg, ntot}},
+        [&](int p0, const PairChunk& k) { return xc_fetch(h, tmat + (size_t)p0 * 2 * DP_TMAT, c.d_chunk_in, (size_t)k.np * 2 * DP_TMAT, &tm); },
+        [&](int p0, const PairChunk& k) {
+            if (kind == 0)
+                k_damping_block<<<dim3(nen, k.np), 256, 0, h->stream>>>(lld, nen, c.d_ene, sym_term, k.ta, k.tb, k.sa, k.sb, c.d_same + p0, c.d_cb + p0, k.c0,
+                                                                     reinterpret_cast<const double2*>(tm), c.d_rows);
+            else
+                k_damping_cheb<<<dim3(nen, k.np), 256, (size_t)c.nm * sizeof(double2), h->stream>>>(c.nm, nen, c.d_ene, c.ca, c.cb, k.ta, k.sa, c.d_same + p0,
+                                                                                                  c.d_cb + p0, k.c0, reinterpret_cast<const double2*>(tm), c.d_rows);
+        },
+        [&](int p0, const PairChunk& k) {
+            k_damping_reduce<<<(unsigned)((ntot + (size_t)DP_NROW * k.np + 255) / 256), 256, 0, h->stream>>>(nen, k.np, ief - 1, c.d_rows, pair_offset + p0, d_img,
+                                                                                                             d_img + nimg);
+        });
 }
 
 // exchange%calculate_jij_auxgreen (exchange.f90:171-335) for the pairs of one rank: the 9 tensor components (or J00) per energy from the
@@ -2966,46 +2973,27 @@ extern "C" int rsrec_exchange_aux(rsrec_t* h, int kind, int npairs, const int32_
         return fail(h, RSREC_ERR_ARG, "rsrec_exchange_aux: bad argument");
     if (!apar) return fail(h, RSREC_ERR_ARG, "rsrec_exchange_aux: no potential parameters (apar is NULL)");
     if (!jaux) return fail(h, RSREC_ERR_ARG, "rsrec_exchange_aux: no output (jaux is NULL)");
-    if (kind == 1 && (size_t)(2 * lld + 2) * sizeof(double2) + sizeof(XcChebLds) + sizeof(AuxShared) > (size_t)64 * 1024)
-        return fail(h, RSREC_ERR_ARG, "rsrec_exchange_aux: lld = %d too deep for the Chebyshev phase table beside the pair's blocks", lld);
-    if (nen < nv1 + 9) return fail(h, RSREC_ERR_ARG, "rsrec_exchange_aux: nen = %d < nv1 + 9 = %d (simpson_f integrates to nv1 + 10)", nen, nv1 + 9);
-    const size_t nimg = (size_t)AX_NROW * npairs_total, rdoubles = (size_t)nen * AX_NROW;
+    XFER(check_cheb_lds(h, "rsrec_exchange_aux", kind, lld, sizeof(AuxShared), "pair"));
+    XFER(check_simpson_mesh(h, "rsrec_exchange_aux", nen, nv1));
+    const size_t nimg = (size_t)AX_NROW * npairs_total;
     PairCall c;
     // own inputs: fermi weights;  own chunk inputs: apar of the chunk's pairs;  own output: the jaux image
-    int rc = pair_call_begin(h, c, "rsrec_exchange_aux", kind, npairs, same, lld, nen, ene, energy_min, energy_max, a_inf, b_inf, coef_a, coef_b, rdoubles,
-                             (size_t)nen, (size_t)2 * AX_APAR, nimg, 0);
-    if (rc) return rc;
-    double* d_fw = c.d_fixed_in;
-    double* d_img = c.d_fixed_out;
-    reset_timing(h);
-    hipEvent_t e0 = next_event(h);
-    HIPCK(h, hipMemsetAsync(d_img, 0, nimg * sizeof(double), h->stream));
-    k_exchange_fermi<<<(nen + 255) / 256, 256, 0, h->stream>>>(nen, c.d_ene, fermi, d_fw);
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> kev;
-    for (int p0 = 0; p0 < npairs; p0 += c.P) {
-        PairChunk k;
-        rc = pair_call_chunk(h, c, p0, k);
-        if (rc) return rc;
-        const int np = k.np;
-        const double* ap = nullptr;
-        XFER(xc_fetch(h, apar + (size_t)p0 * 2 * AX_APAR, c.d_chunk_in, (size_t)np * 2 * AX_APAR, &ap));
-        std::pair<hipEvent_t, hipEvent_t> ev;
-        ev.first = next_event(h);
-        if (kind == 0)
-            k_aux_block<<<dim3(nen, np), 256, 0, h->stream>>>(lld, nen, c.d_ene, sym_term, k.ta, k.tb, k.sa, k.sb, c.d_same + p0, c.d_cb + p0, k.c0, ap, c.d_rows);
-        else
-            k_aux_cheb<<<dim3(nen, np), 256, (size_t)c.nm * sizeof(double2), h->stream>>>(c.nm, nen, c.d_ene, c.ca, c.cb, k.ta, k.sa, c.d_same + p0, c.d_cb + p0,
-                                                                                        k.c0, ap, c.d_rows);
-        HIPCK(h, hipGetLastError());
-        k_rows_integrate<<<np, 64, 0, h->stream>>>(nen, nv1, AX_NROW, c.d_ene, d_fw, c.d_rows, pair_offset + p0, d_img);
-        HIPCK(h, hipGetLastError());
-        ev.second = next_event(h);
-        kev.push_back(ev);
-        if (rows) XFER(xc_deliver(h, rows + (size_t)p0 * rdoubles, c.d_rows, (size_t)np * rdoubles));
-        if (p0 + c.P < npairs) HIPCK(h, hipStreamSynchronize(h->stream));         // the chunk's staging buffers are reused
-    }
-    XFER(xc_deliver(h, jaux, d_img, nimg));
-    return pair_call_end(h, e0, kev);
+    XFER(pair_call_begin(h, c, "rsrec_exchange_aux", kind, npairs, same, lld, nen, ene, energy_min, energy_max, a_inf, b_inf, coef_a, coef_b,
+                         (size_t)nen * AX_NROW, (size_t)nen, (size_t)2 * AX_APAR, nimg, 0));
+    const double* ap = nullptr;
+    return pair_call_run(h, c, &fermi, nullptr, rows, {{jaux, 0, nimg}},
+        [&](int p0, const PairChunk& k) { return xc_fetch(h, apar + (size_t)p0 * 2 * AX_APAR, c.d_chunk_in, (size_t)k.np * 2 * AX_APAR, &ap); },
+        [&](int p0, const PairChunk& k) {
+            if (kind == 0)
+                k_aux_block<<<dim3(nen, k.np), 256, 0, h->stream>>>(lld, nen, c.d_ene, sym_term, k.ta, k.tb, k.sa, k.sb, c.d_same + p0, c.d_cb + p0, k.c0, ap,
+                                                                 c.d_rows);
+            else
+                k_aux_cheb<<<dim3(nen, k.np), 256, (size_t)c.nm * sizeof(double2), h->stream>>>(c.nm, nen, c.d_ene, c.ca, c.cb, k.ta, k.sa, c.d_same + p0,
+                                                                                              c.d_cb + p0, k.c0, ap, c.d_rows);
+        },
+        [&](int p0, const PairChunk& k) {
+            k_rows_integrate<<<k.np, 64, 0, h->stream>>>(nen, nv1, AX_NROW, c.d_ene, c.d_fixed_in, c.d_rows, pair_offset + p0, c.d_fixed_out);
+        });
 }
 
 // exchange%calculate_jijk (exchange.f90:338-601) for the trios of one rank.  The pairs of trio t are 3 t .. 3 t + 2 = (i,j), (i,k), (j,k)
@@ -3017,57 +3005,39 @@ extern "C" int rsrec_spin_lattice(rsrec_t* h, int kind, int npairs, const int32_
     if (!h) return RSREC_ERR_ARG;
     if (npairs < 1 || lld < 1 || nv1 < 1 || !same || !ene || trio_offset < 0) return fail(h, RSREC_ERR_ARG, "rsrec_spin_lattice: bad argument");
     if (npairs % 3) return fail(h, RSREC_ERR_ARG, "rsrec_spin_lattice: npairs = %d is not a multiple of 3 (a trio is the pairs (i,j), (i,k), (j,k))", npairs);
-    const int ntrios = npairs / 3;
-    if (ntrios_total < trio_offset + ntrios) return fail(h, RSREC_ERR_ARG, "rsrec_spin_lattice: bad argument");
+    if (ntrios_total < trio_offset + npairs / 3) return fail(h, RSREC_ERR_ARG, "rsrec_spin_lattice: bad argument");
     if (!apar) return fail(h, RSREC_ERR_ARG, "rsrec_spin_lattice: no potential parameters (apar is NULL)");
     if (!dmat) return fail(h, RSREC_ERR_ARG, "rsrec_spin_lattice: no displacement matrices (dmat is NULL)");
     if (!jijk) return fail(h, RSREC_ERR_ARG, "rsrec_spin_lattice: no output (jijk is NULL)");
-    if (nen < nv1 + 9) return fail(h, RSREC_ERR_ARG, "rsrec_spin_lattice: nen = %d < nv1 + 9 = %d (simpson_f integrates to nv1 + 10)", nen, nv1 + 9);
-    if (kind == 1 && (size_t)(2 * lld + 2) * sizeof(double2) + sizeof(XcChebLds) + sizeof(JkShared) > (size_t)64 * 1024)
-        return fail(h, RSREC_ERR_ARG, "rsrec_spin_lattice: lld = %d too deep for the Chebyshev phase table beside the trio's blocks", lld);
-    const size_t nimg = (size_t)AX_NROW * ntrios_total, rdoubles = (size_t)nen * AX_NROW;      // rows of one trio
+    XFER(check_simpson_mesh(h, "rsrec_spin_lattice", nen, nv1));
+    XFER(check_cheb_lds(h, "rsrec_spin_lattice", kind, lld, sizeof(JkShared), "trio"));
+    const size_t nimg = (size_t)AX_NROW * ntrios_total;
     constexpr size_t TRIO_IN = (size_t)3 * JK_APAR + 2 * 81;                                   // apar | dmat of one trio
-    static_assert(TRIO_IN % 3 == 0 && (3 * JK_APAR) % 2 == 0, "trio inputs split over its pairs; dmat is read as double2");
+    static_assert(TRIO_IN % 3 == 0 && (3 * JK_APAR) % 2 == 0 && AX_NROW % 3 == 0, "a trio's inputs and rows split over its pairs; dmat is read as double2");
     PairCall c;
     // chunks of whole trios.  Per pair: a third of a trio's rows and inputs.  Own inputs: fermi weights;  own output: the jijk image
-    int rc = pair_call_begin(h, c, "rsrec_spin_lattice", kind, npairs, same, lld, nen, ene, energy_min, energy_max, a_inf, b_inf, coef_a, coef_b,
-                             rdoubles / 3, (size_t)nen, TRIO_IN / 3, nimg, 0, 4, 3);
-    if (rc) return rc;
-    double* d_fw = c.d_fixed_in;
-    double* d_img = c.d_fixed_out;
+    XFER(pair_call_begin(h, c, "rsrec_spin_lattice", kind, npairs, same, lld, nen, ene, energy_min, energy_max, a_inf, b_inf, coef_a, coef_b,
+                         (size_t)nen * AX_NROW / 3, (size_t)nen, TRIO_IN / 3, nimg, 0, 4, 3));
     double* d_ap = c.d_chunk_in;
     double* d_dm = d_ap + (size_t)(c.P / 3) * 3 * JK_APAR;
-    reset_timing(h);
-    hipEvent_t e0 = next_event(h);
-    HIPCK(h, hipMemsetAsync(d_img, 0, nimg * sizeof(double), h->stream));
-    k_exchange_fermi<<<(nen + 255) / 256, 256, 0, h->stream>>>(nen, c.d_ene, fermi, d_fw);
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> kev;
-    for (int p0 = 0; p0 < npairs; p0 += c.P) {
-        PairChunk k;
-        rc = pair_call_chunk(h, c, p0, k);
-        if (rc) return rc;
-        const int nt = k.np / 3, t0 = p0 / 3;
-        const double *ap = nullptr, *dm = nullptr;
-        XFER(xc_fetch(h, apar + (size_t)t0 * 3 * JK_APAR, d_ap, (size_t)nt * 3 * JK_APAR, &ap));
-        XFER(xc_fetch(h, dmat + (size_t)t0 * 2 * 81, d_dm, (size_t)nt * 2 * 81, &dm));
-        std::pair<hipEvent_t, hipEvent_t> ev;
-        ev.first = next_event(h);
-        if (kind == 0)
-            k_jijk_block<<<dim3(nen, nt), 256, 0, h->stream>>>(lld, nen, c.d_ene, sym_term, k.ta, k.tb, k.sa, k.sb, c.d_same + p0, c.d_cb + p0, k.c0, ap,
-                                                            reinterpret_cast<const double2*>(dm), c.d_rows);
-        else
-            k_jijk_cheb<<<dim3(nen, nt), 256, (size_t)c.nm * sizeof(double2), h->stream>>>(c.nm, nen, c.d_ene, c.ca, c.cb, k.ta, k.sa, c.d_same + p0, c.d_cb + p0,
-                                                                                         k.c0, ap, reinterpret_cast<const double2*>(dm), c.d_rows);
-        HIPCK(h, hipGetLastError());
-        k_rows_integrate<<<nt, 64, 0, h->stream>>>(nen, nv1, AX_NROW, c.d_ene, d_fw, c.d_rows, trio_offset + t0, d_img);
-        HIPCK(h, hipGetLastError());
-        ev.second = next_event(h);
-        kev.push_back(ev);
-        if (rows) XFER(xc_deliver(h, rows + (size_t)t0 * rdoubles, c.d_rows, (size_t)nt * rdoubles));
-        if (p0 + c.P < npairs) HIPCK(h, hipStreamSynchronize(h->stream));         // the chunk's staging buffers are reused
-    }
-    XFER(xc_deliver(h, jijk, d_img, nimg));
-    return pair_call_end(h, e0, kev);
+    const double *ap = nullptr, *dm = nullptr;
+    return pair_call_run(h, c, &fermi, nullptr, rows, {{jijk, 0, nimg}},
+        [&](int p0, const PairChunk& k) {
+            const size_t t0 = p0 / 3, nt = k.np / 3;
+            XFER(xc_fetch(h, apar + t0 * 3 * JK_APAR, d_ap, nt * 3 * JK_APAR, &ap));
+            return xc_fetch(h, dmat + t0 * 2 * 81, d_dm, nt * 2 * 81, &dm);
+        },
+        [&](int p0, const PairChunk& k) {
+            if (kind == 0)
+                k_jijk_block<<<dim3(nen, k.np / 3), 256, 0, h->stream>>>(lld, nen, c.d_ene, sym_term, k.ta, k.tb, k.sa, k.sb, c.d_same + p0, c.d_cb + p0, k.c0, ap,
+                                                                      reinterpret_cast<const double2*>(dm), c.d_rows);
+            else
+                k_jijk_cheb<<<dim3(nen, k.np / 3), 256, (size_t)c.nm * sizeof(double2), h->stream>>>(c.nm, nen, c.d_ene, c.ca, c.cb, k.ta, k.sa, c.d_same + p0,
+                                                                                                   c.d_cb + p0, k.c0, ap, reinterpret_cast<const double2*>(dm), c.d_rows);
+        },
+        [&](int p0, const PairChunk& k) {
+            k_rows_integrate<<<k.np / 3, 64, 0, h->stream>>>(nen, nv1, AX_NROW, c.d_ene, c.d_fixed_in, c.d_rows, trio_offset + p0 / 3, c.d_fixed_out);
+        });
 }
 
 namespace {
@@ -3095,48 +3065,30 @@ extern "C" int rsrec_exchange_contour(rsrec_t* h, int kind, int npairs, const in
     if (!dmat) return fail(h, RSREC_ERR_ARG, "rsrec_exchange_contour: no dmat (NULL)");
     if (is_device_ptr(x) || is_device_ptr(w)) return fail(h, RSREC_ERR_ARG, "rsrec_exchange_contour: x and w are host arrays");
     std::vector<double> eta;
-    int rc = contour_eta(h, "rsrec_exchange_contour", npts, x, eta);
-    if (rc) return rc;
-    const size_t nimg = (size_t)CT_NROW * npairs_total, rdoubles = (size_t)npts * CT_NROW;
+    XFER(contour_eta(h, "rsrec_exchange_contour", npts, x, eta));
+    const size_t nimg = (size_t)CT_NROW * npairs_total;
     PairCall c;
     // the "energies" of the call are the points' eta;  own inputs: x | w;  own chunk inputs: dmat of the chunk's pairs;  own output: the xc image
-    rc = pair_call_begin(h, c, "rsrec_exchange_contour", kind, npairs, same, lld, npts, eta.data(), energy_min, energy_max, a_inf, b_inf, coef_a, coef_b,
-                         rdoubles, (size_t)2 * npts, (size_t)CT_DMAT, nimg, 0);
-    if (rc) return rc;
+    XFER(pair_call_begin(h, c, "rsrec_exchange_contour", kind, npairs, same, lld, npts, eta.data(), energy_min, energy_max, a_inf, b_inf, coef_a, coef_b,
+                         (size_t)npts * CT_NROW, (size_t)2 * npts, (size_t)CT_DMAT, nimg, 0));
     double* d_x = c.d_fixed_in;
     double* d_w = d_x + npts;
-    double* d_img = c.d_fixed_out;
     XFER(xfer_h2d(h, d_x, x, (size_t)npts * sizeof(double)));
     XFER(xfer_h2d(h, d_w, w, (size_t)npts * sizeof(double)));
-    reset_timing(h);
-    hipEvent_t ev0 = next_event(h);
-    HIPCK(h, hipMemsetAsync(d_img, 0, nimg * sizeof(double), h->stream));
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> kev;
-    for (int p0 = 0; p0 < npairs; p0 += c.P) {
-        PairChunk k;
-        rc = pair_call_chunk(h, c, p0, k);                                      // (the terminators: once per chain, not once per point)
-        if (rc) return rc;
-        const int np = k.np;
-        const double* dm = nullptr;
-        XFER(xc_fetch(h, dmat + (size_t)p0 * CT_DMAT, c.d_chunk_in, (size_t)np * CT_DMAT, &dm));
-        std::pair<hipEvent_t, hipEvent_t> ev;
-        ev.first = next_event(h);
-        if (kind == 0)
-            k_contour_xc_block<<<dim3(npts, np), 256, 0, h->stream>>>(lld, npts, e0, c.d_ene, d_x, d_w, sym_term, k.ta, k.tb, k.sa, k.sb, c.d_same + p0, c.d_cb + p0,
-                                                                   k.c0, dm, c.d_rows);
-        else
-            k_contour_xc_cheb<<<dim3(npts, np), 256, (size_t)c.nm * sizeof(double2), h->stream>>>(c.nm, npts, e0, c.d_ene, d_x, d_w, c.ca, c.cb, k.ta, k.sa,
-                                                                                                c.d_same + p0, c.d_cb + p0, k.c0, dm, c.d_rows);
-        HIPCK(h, hipGetLastError());
-        k_contour_xc_sum<<<(np * CT_NROW + 255) / 256, 256, 0, h->stream>>>(npts, np, c.d_rows, pair_offset + p0, d_img);
-        HIPCK(h, hipGetLastError());
-        ev.second = next_event(h);
-        kev.push_back(ev);
-        if (rows) XFER(xc_deliver(h, rows + (size_t)p0 * rdoubles, c.d_rows, (size_t)np * rdoubles));
-        if (p0 + c.P < npairs) HIPCK(h, hipStreamSynchronize(h->stream));         // the chunk's staging buffers are reused
-    }
-    XFER(xc_deliver(h, xc, d_img, nimg));
-    return pair_call_end(h, ev0, kev);
+    const double* dm = nullptr;
+    return pair_call_run(h, c, nullptr, nullptr, rows, {{xc, 0, nimg}},           // (the terminators: once per chain, not once per point)
+        [&](int p0, const PairChunk& k) { return xc_fetch(h, dmat + (size_t)p0 * CT_DMAT, c.d_chunk_in, (size_t)k.np * CT_DMAT, &dm); },
+        [&](int p0, const PairChunk& k) {
+            if (kind == 0)
+                k_contour_xc_block<<<dim3(npts, k.np), 256, 0, h->stream>>>(lld, npts, e0, c.d_ene, d_x, d_w, sym_term, k.ta, k.tb, k.sa, k.sb, c.d_same + p0,
+                                                                         c.d_cb + p0, k.c0, dm, c.d_rows);
+            else
+                k_contour_xc_cheb<<<dim3(npts, k.np), 256, (size_t)c.nm * sizeof(double2), h->stream>>>(c.nm, npts, e0, c.d_ene, d_x, d_w, c.ca, c.cb, k.ta, k.sa,
+                                                                                                      c.d_same + p0, c.d_cb + p0, k.c0, dm, c.d_rows);
+        },
+        [&](int p0, const PairChunk& k) {
+            k_contour_xc_sum<<<(k.np * CT_NROW + 255) / 256, 256, 0, h->stream>>>(npts, k.np, c.d_rows, pair_offset + p0, c.d_fixed_out);
+        });
 }
 
 // The occupations of bands%calculate_moments_gauss_legendre / calculate_occupation_gauss_legendre for the on-site chains of one rank.
@@ -3148,47 +3100,29 @@ extern "C" int rsrec_contour_occupation(rsrec_t* h, int kind, int nsites, int ll
         return fail(h, RSREC_ERR_ARG, "rsrec_contour_occupation: bad argument");
     if (is_device_ptr(x) || is_device_ptr(w)) return fail(h, RSREC_ERR_ARG, "rsrec_contour_occupation: x and w are host arrays");
     std::vector<double> eta;
-    int rc = contour_eta(h, "rsrec_contour_occupation", npts, x, eta);
-    if (rc) return rc;
-    const size_t nimg = (size_t)NB * nsites_total, rdoubles = (size_t)npts * NB * 2;
+    XFER(contour_eta(h, "rsrec_contour_occupation", npts, x, eta));
+    const size_t nimg = (size_t)NB * nsites_total;
     const std::vector<int32_t> same(nsites, 0);
     PairCall c;
     // one chain per site;  own inputs: x | w;  own output: the occ image;  the rows of a chunk: the diagonal of g at every point
-    rc = pair_call_begin(h, c, "rsrec_contour_occupation", kind, nsites, same.data(), lld, npts, eta.data(), energy_min, energy_max, a_inf, b_inf, coef_a,
-                         coef_b, rdoubles, (size_t)2 * npts, 0, nimg, 0, 1);
-    if (rc) return rc;
+    XFER(pair_call_begin(h, c, "rsrec_contour_occupation", kind, nsites, same.data(), lld, npts, eta.data(), energy_min, energy_max, a_inf, b_inf, coef_a,
+                         coef_b, (size_t)npts * NB * 2, (size_t)2 * npts, 0, nimg, 0, 1));
     double* d_x = c.d_fixed_in;
     double* d_w = d_x + npts;
-    double* d_img = c.d_fixed_out;
     double2* d_gd = reinterpret_cast<double2*>(c.d_rows);
     XFER(xfer_h2d(h, d_x, x, (size_t)npts * sizeof(double)));
     XFER(xfer_h2d(h, d_w, w, (size_t)npts * sizeof(double)));
-    reset_timing(h);
-    hipEvent_t ev0 = next_event(h);
-    HIPCK(h, hipMemsetAsync(d_img, 0, nimg * sizeof(double), h->stream));
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> kev;
-    for (int s0 = 0; s0 < nsites; s0 += c.P) {
-        PairChunk k;
-        rc = pair_call_chunk(h, c, s0, k);
-        if (rc) return rc;
-        const int ns = k.np;
-        std::pair<hipEvent_t, hipEvent_t> ev;
-        ev.first = next_event(h);
-        if (kind == 0)
-            k_contour_occ_block<<<dim3((npts + GREEN_WAVES - 1) / GREEN_WAVES, ns), GREEN_WAVES * 64, 0, h->stream>>>(lld, npts, e0, c.d_ene, sym_term, k.ta, k.tb,
-                                                                                                                   k.sa, k.sb, d_gd);
-        else
-            k_contour_occ_cheb<<<dim3(npts, ns), 64, (size_t)c.nm * sizeof(double2), h->stream>>>(c.nm, npts, e0, c.d_ene, c.ca, c.cb, k.ta, k.sa, d_gd);
-        HIPCK(h, hipGetLastError());
-        k_contour_occ_sum<<<(ns * NB + 255) / 256, 256, 0, h->stream>>>(npts, ns, d_x, d_w, d_gd, site_offset + s0, d_img);
-        HIPCK(h, hipGetLastError());
-        ev.second = next_event(h);
-        kev.push_back(ev);
-        if (gdiag) XFER(xc_deliver(h, gdiag + (size_t)s0 * rdoubles, c.d_rows, (size_t)ns * rdoubles));
-        if (s0 + c.P < nsites) HIPCK(h, hipStreamSynchronize(h->stream));         // the chunk's staging buffers are reused
-    }
-    XFER(xc_deliver(h, occ, d_img, nimg));
-    return pair_call_end(h, ev0, kev);
+    return pair_call_run(h, c, nullptr, nullptr, gdiag, {{occ, 0, nimg}}, no_stage,
+        [&](int, const PairChunk& k) {
+            if (kind == 0)
+                k_contour_occ_block<<<dim3((npts + GREEN_WAVES - 1) / GREEN_WAVES, k.np), GREEN_WAVES * 64, 0, h->stream>>>(lld, npts, e0, c.d_ene, sym_term, k.ta,
+                                                                                                                         k.tb, k.sa, k.sb, d_gd);
+            else
+                k_contour_occ_cheb<<<dim3(npts, k.np), 64, (size_t)c.nm * sizeof(double2), h->stream>>>(c.nm, npts, e0, c.d_ene, c.ca, c.cb, k.ta, k.sa, d_gd);
+        },
+        [&](int s0, const PairChunk& k) {
+            k_contour_occ_sum<<<(k.np * NB + 255) / 256, 256, 0, h->stream>>>(npts, k.np, d_x, d_w, d_gd, site_offset + s0, c.d_fixed_out);
+        });
 }
 
 namespace {

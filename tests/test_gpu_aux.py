@@ -5,71 +5,14 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import aux_reference as R
+from pair_cases import (FERMI, TRIOS, aux_reference, chain_g0 as all_g0, check_aux as check, jijk_reference, random_apar,
+                        random_trio_dmat as random_dmat, run_device_script, setup)
 from rslmtoasa_amd import _lib
-from rslmtoasa_amd.exchange import Exchange, disp_matrix, trio_pairs
-from test_gpu_exchange import TOL, close, setup
+from rslmtoasa_amd.exchange import Exchange, trio_pairs
 
 pytestmark = pytest.mark.gpu
 
 PAIRS = np.array([(1, 1), (1, 2), (1, 9), (5, 60), (3, 3)], np.int32)
-TRIOS = np.array([(1, 2, 9), (5, 60, 17), (1, 2, 1)], np.int32)          # the last repeats an atom: its pair (i,k) is an i == k pair
-FERMI = -0.05
-
-
-def random_apar(n, nq, seed):
-    """(c + vmad, dele[, qpar]) per l, spin and side / atom, random and different everywhere: a swap of sides, spins or atoms shows."""
-    rng = np.random.default_rng(seed)
-    out = np.zeros((nq, 3, 2, nq, n), order="F")
-    out[0] = rng.uniform(-0.15, 0.4, out[0].shape)
-    out[1] = rng.uniform(0.04, 0.22, out[1].shape)
-    if nq == 3:
-        out[2] = rng.uniform(0.01, 0.45, out[2].shape)
-    return out
-
-
-def random_dmat(ntrios, seed=5):
-    """disp_matrix of a random displacement per trio (a dense complex 9 x 9 with the reference's zero pattern), plus an imaginary part
-    the reference's matrix does not have, so that the complex arithmetic is exercised."""
-    rng = np.random.default_rng(seed)
-    out = np.zeros((9, 9, ntrios), np.complex128, order="F")
-    for t in range(ntrios):
-        out[:, :, t] = disp_matrix(rng.normal(size=3), 2.6) * (1.0 + 0.3j)
-    return out
-
-
-def all_g0(rec, g, kind, n, zsqr=True):
-    """g0 (18, 18, nE, n) of the first n chain slots from the library's Green kernels."""
-    if kind == "block":
-        if zsqr:
-            rec.zsqr()
-        a_inf, b_inf, _, _ = g.terminator(nsites=n)
-        return g.block_green(a_inf, b_inf, nsites=n).copy()
-    return g.chebyshev_green(nsites=n).copy()
-
-
-def aux_reference(g0, pairs, apar, ene, nv1):
-    return [R.jij_aux_pair(g0[..., 4 * q:4 * q + 4], pairs[q, 0] == pairs[q, 1], apar[..., q], ene, FERMI, nv1) for q in range(len(pairs))]
-
-
-def jijk_reference(g0, trios, apar, dmat, ene, nv1):
-    pairs = trio_pairs(trios)
-    out = []
-    for t in range(len(trios)):
-        gs = [g0[..., 4 * q:4 * q + 4] for q in range(3 * t, 3 * t + 3)]
-        sames = [bool(pairs[q, 0] == pairs[q, 1]) for q in range(3 * t, 3 * t + 3)]
-        out.append(R.jijk_trio(gs, sames, apar[..., t], dmat[..., t], ene, FERMI, nv1))
-    return out
-
-
-def check(res, ref):
-    """Integrals and rows of every pair / trio, relative to its largest row (integrals: to its largest integral)."""
-    val, rows = res
-    for q, (rv, rr) in enumerate(ref):
-        print(q, np.abs(val[:, q] - rv).max() / np.abs(rv).max(), np.abs(rows[:, :, q] - rr).max() / np.abs(rr).max())
-        assert close(val[:, q], rv, 0.0), q
-        assert close(rows[:, :, q], rr, 0.0), q
-        assert np.abs(rr).max() > 1e-6
 
 
 CASES = [("block", False), ("block", True), ("chebyshev", False)]
@@ -102,16 +45,11 @@ def test_jijk_matches_restatement(kind, hoh):
 
 
 DEVICE_SCRIPT = r"""
-import sys
-sys.path[:0] = [sys.argv[1], sys.argv[1] + "/tests"]
-import numpy as np, torch
-torch.cuda.init(); torch.cuda.set_device(0)          # torch's HIP runtime before librsrec's (as bench.py does)
-import test_gpu_aux as T
 from rslmtoasa_amd.exchange import Exchange, trio_pairs
 pairs = trio_pairs(T.TRIOS)                          # (1,1) among them: the resident chains are compacted
 rec, g, ene, nv1, _ = T.setup(pairs, lld=8, channels=100)
 x = Exchange(rec, g)
-aa, at, dm = T.random_apar(len(pairs), 2, 31), T.random_apar(len(T.TRIOS), 3, 32), T.random_dmat(len(T.TRIOS))
+aa, at, dm = T.random_apar(len(pairs), 2, 31), T.random_apar(len(T.TRIOS), 3, 32), T.random_trio_dmat(len(T.TRIOS))
 calls = {"aux": lambda **kw: x.aux(T.FERMI, nv1, aa, rows=True, **kw), "jijk": lambda **kw: x.spin_lattice(T.FERMI, nv1, at, dm, rows=True, **kw)}
 first = {k: f(resident=True) for k, f in calls.items()}
 again = {k: f(resident=True) for k, f in calls.items()}
@@ -123,9 +61,9 @@ for k, f in calls.items():
     for other in (again[k], f(), f(a_inf=a_inf, b_inf=b_inf), f(coef=(ta, tb))):
         for a, b in zip(first[k], other):
             assert np.array_equal(a, b), k
-g0 = T.all_g0(rec, g, "block", 4 * len(pairs), zsqr=False)
-T.check(first["aux"], T.aux_reference(g0, pairs, aa, ene, nv1))
-T.check(first["jijk"], T.jijk_reference(g0, T.TRIOS, at, dm, ene, nv1))
+g0 = T.chain_g0(rec, g, "block", 4 * len(pairs), zsqr=False)
+T.check_aux(first["aux"], T.aux_reference(g0, pairs, aa, ene, nv1))
+T.check_aux(first["jijk"], T.jijk_reference(g0, T.TRIOS, at, dm, ene, nv1))
 rec.close()
 print("AUX_DEVICE_OK")
 """
@@ -134,10 +72,7 @@ print("AUX_DEVICE_OK")
 def test_coefficient_sources_agree_bitwise():
     """Resident chains (compacted: the trio (1,2,1) holds the pair (1,1)), host arrays with device and with caller terminators, and
     device-pointer coefficients give the same bits; so do two calls.  Own process: torch's HIP runtime has to start before librsrec's."""
-    import os, subprocess, sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "-c", DEVICE_SCRIPT, root], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "AUX_DEVICE_OK" in r.stdout, (r.stdout + r.stderr)[-3000:]
+    run_device_script(DEVICE_SCRIPT, "sources", "AUX_DEVICE_OK")
 
 
 def test_a_trio_does_not_depend_on_the_others_or_on_the_split():

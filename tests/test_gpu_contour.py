@@ -11,52 +11,20 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from contour_reference import chebyshev_green_eta, contour_eta, contour_pair, occupation, ordered_sum
+from contour_reference import chebyshev_green_eta, contour_eta, occupation
 from exchange_reference import PI
 from helpers import objects_from, supercell_problem
+from pair_cases import (EMAX, EMIN, TOL, block_g_at_points, check_contour_pairs as check_pairs, onsite, random_contour_dmat as random_dmat,
+                        run_device_script, setup)
 from rslmtoasa_amd import _lib
 from rslmtoasa_amd.exchange import Exchange, contour_dmat, gauss_legendre
 from rslmtoasa_amd.green import Green
 from rslmtoasa_amd.recursion import Recursion
-from test_gpu_exchange import TOL, close, setup
 
 pytestmark = pytest.mark.gpu
 
 PAIRS = np.array([(1, 1), (1, 2), (1, 9), (5, 60), (3, 3)], np.int32)
 NPTS = (1, 5, 64, 67)          # 67: past one wave's worth of points
-EMIN, EMAX = -3.0, 1.8         # the recursion's energy window in ``setup`` (the Chebyshev scaling)
-
-
-def random_dmat(npairs, seed=33):
-    """Random dense real matrices per pair and side: nothing of the kernel may lean on the structure of a physical dmat, and the two sides
-    differ, so a swap of the sides changes the values."""
-    rng = np.random.default_rng(seed)
-    return np.asfortranarray(rng.standard_normal((9, 9, 2, npairs)))
-
-
-def block_g_at_points(rec, e0, eta, nchains, a_inf, b_inf):
-    """g (18, 18, npts, nchains) from one single-energy Green.block_green call per point: the loop the contour calls replace."""
-    g1 = Green(rec, np.array([e0]))
-    out = np.zeros((18, 18, len(eta), nchains), np.complex128)
-    for k, et in enumerate(eta):
-        out[:, :, k, :] = g1.block_green(a_inf, b_inf, eta=1j * et, nsites=nchains)[:, :, 0, :]
-    return out
-
-
-def check_pairs(xc, rows, g, pairs, dmat, x, w, col0=0):
-    for q in range(len(pairs)):
-        rxc, rrows = contour_pair(g[..., 4 * q:4 * q + 4], pairs[q, 0] == pairs[q, 1], dmat[..., q], x, w)
-        floor = np.abs(rrows).max()
-        worst = np.abs(rows[:, :, q] - rrows).max() / max(floor, 1e-300)
-        print("pair %d, %d points: largest row %.3e, worst row deviation / floor %.2e, xc deviation / scale %.2e"
-              % (q, len(x), floor, worst, np.abs(xc[:, col0 + q] - rxc).max() / (floor * 1.0e3 / 4.0 / PI)))
-        for r in range(13):
-            assert close(rows[r, :, q], rrows[r], floor), (q, r)
-        assert close(xc[:, col0 + q], rxc, floor * 1.0e3 / 4.0 / PI), q
-        # the device's sum over the points is the ordered sum of its own rows, bit for bit
-        sign = np.array([-1.0] + [1.0] * 3 + [-1.0] * 9)
-        assert np.array_equal(xc[:, col0 + q], sign * ordered_sum(rows[:, :, q]) * 1.0e3 / 4.0 / PI), q
-    assert np.abs(rows).max() > 0
 
 
 @pytest.mark.parametrize("hoh", [False, True])
@@ -110,17 +78,6 @@ def test_chebyshev_matches_restatement():
         xc, rows = Exchange(rec, g).contour(x, w, e0, dmat, kind="chebyshev", rows=True)
         check_pairs(xc, rows, gp, PAIRS, dmat, x, w)
     rec.close()
-
-
-def onsite(kind, lld, sites=(1, 30, 64), hoh=False):
-    p = supercell_problem((4, 4, 4), hoh=hoh)
-    ham, lat, ctl, en = objects_from(p, list(sites), lld, emin=EMIN, emax=EMAX)
-    rec = Recursion(ham, lat, ctl, en)
-    if kind == "block":
-        rec.recur_b()
-    else:
-        rec.chebyshev_recur()
-    return rec
 
 
 def occ_close(occ, ref, y):
@@ -197,21 +154,15 @@ def test_occupation_images_of_a_partition_sum_to_the_single_call():
 
 
 DEVICE_SCRIPT = r"""
-import sys
-sys.path[:0] = [sys.argv[1], sys.argv[1] + "/tests"]
-import numpy as np, torch
-torch.cuda.init(); torch.cuda.set_device(0)          # torch's HIP runtime before librsrec's (as bench.py does)
-import test_gpu_exchange as X
-import test_gpu_contour as T
+from contour_reference import contour_eta
 from rslmtoasa_amd.exchange import Exchange, gauss_legendre
-mode = sys.argv[2]
 if mode == "sources":
     pairs = np.array([(1, 1), (1, 2), (7, 30), (2, 2), (9, 40)], np.int32)
     for kind, lld in (("block", 8), ("chebyshev", 6)):
-        rec, g, ene, nv1, dpar = X.setup(pairs, lld=lld, channels=100, kind=kind)
+        rec, g, ene, nv1, dpar = T.setup(pairs, lld=lld, channels=100, kind=kind)
         ex = Exchange(rec, g)
         x, w = gauss_legendre(64)
-        e0, dmat = float(ene[50]), T.random_dmat(len(pairs))
+        e0, dmat = float(ene[50]), T.random_contour_dmat(len(pairs))
         res_dev = ex.contour(x, w, e0, dmat, kind=kind, rows=True, resident=True)          # block: the i == j pairs compacted
         res_dev2 = ex.contour(x, w, e0, dmat, kind=kind, rows=True, resident=True)
         td = torch.from_numpy(np.ascontiguousarray(dmat.transpose(3, 2, 1, 0))).cuda()
@@ -222,8 +173,8 @@ if mode == "sources":
             ta = torch.from_numpy(np.ascontiguousarray(rec.a_b.transpose(3, 2, 1, 0))).cuda()
             tb = torch.from_numpy(np.ascontiguousarray(rec.b2_b.transpose(3, 2, 1, 0))).cuda()
             others.append(ex.contour(x, w, e0, td, rows=True, coef=(ta, tb)))
-            gp = T.block_g_at_points(rec, e0, T.contour_eta(x), 4 * len(pairs), a_inf, b_inf)
-            T.check_pairs(res_dev[0], res_dev[1], gp, pairs, dmat, x, w)
+            gp = T.block_g_at_points(rec, e0, contour_eta(x), 4 * len(pairs), a_inf, b_inf)
+            T.check_contour_pairs(res_dev[0], res_dev[1], gp, pairs, dmat, x, w)
         else:
             tm = torch.from_numpy(np.ascontiguousarray(rec.mu_n.transpose(3, 2, 1, 0))).cuda()
             others = [ex.contour(x, w, e0, dmat, kind=kind, rows=True), ex.contour(x, w, e0, td, kind=kind, rows=True, coef=(tm,))]
@@ -234,11 +185,11 @@ if mode == "sources":
 else:
     # just above one chunk of pairs at lld 4 (512 MiB of staged coefficients: 3236 pairs), every pair the same chains
     pairs = np.array([(1, 2)], np.int32)
-    rec, g, ene, nv1, dpar = X.setup(pairs, lld=4, channels=40)
+    rec, g, ene, nv1, dpar = T.setup(pairs, lld=4, channels=40)
     rec.zsqr()
     ex = Exchange(rec, g)
     x, w = gauss_legendre(5)
-    e0, dmat = float(ene[20]), T.random_dmat(1)
+    e0, dmat = float(ene[20]), T.random_contour_dmat(1)
     one = ex.contour(x, w, e0, dmat, rows=True)
     n = 3300
     ta = torch.from_numpy(np.ascontiguousarray(rec.a_b[..., :4].transpose(3, 2, 1, 0))).cuda().repeat(n, 1, 1, 1)
@@ -253,23 +204,14 @@ print("CONTOUR_DEVICE_OK")
 """
 
 
-def run_device_script(mode):
-    """Own process: torch's HIP runtime has to be initialised before librsrec's (the other tests of this session have started it)."""
-    import os, subprocess, sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "-c", DEVICE_SCRIPT, root, mode], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "CONTOUR_DEVICE_OK" in r.stdout, (r.stdout + r.stderr)[-3000:]
-    print(r.stdout)
-
-
 def test_coefficient_sources_agree_bitwise():
     """Resident chains (block: i == j pairs compacted), caller coefficients with and without caller terminators, and device-pointer
     coefficients and dmat give the same bits; so does a repeated call.  And they match the restatement."""
-    run_device_script("sources")
+    run_device_script(DEVICE_SCRIPT, "sources", "CONTOUR_DEVICE_OK")
 
 
 def test_pairs_past_one_chunk_carry_the_single_pair_result():
-    run_device_script("chunks")
+    run_device_script(DEVICE_SCRIPT, "chunks", "CONTOUR_DEVICE_OK")
 
 
 SPLIT_PAIRS = np.array([(1, 1), (1, 2), (3, 19), (2, 2), (4, 50), (6, 7), (8, 8)], np.int32)

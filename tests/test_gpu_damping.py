@@ -5,21 +5,14 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from damping_reference import damping_rows, total_damping
-from helpers import objects_from, supercell_problem
+from pair_cases import (chain_g0, check_damping as check_against, close, damping_restated as restated, ordered_total, random_tmat,
+                        run_device_script, setup)
 from rslmtoasa_amd import _lib
 from rslmtoasa_amd.exchange import Exchange, damping_tmat
-from test_gpu_exchange import TOL, close, setup
 
 pytestmark = pytest.mark.gpu
 
 PAIRS = np.array([(1, 1), (1, 2), (1, 9), (1, 17), (5, 60), (3, 3)], np.int32)
-
-
-def random_tmat(npairs, seed=21):
-    """Random complex torque matrices per pair and side: nothing of the kernel may lean on the structure of a physical tmat."""
-    rng = np.random.default_rng(seed)
-    return np.asfortranarray(rng.standard_normal((18, 18, 3, 2, npairs)) + 1j * rng.standard_normal((18, 18, 3, 2, npairs)))
 
 
 def angular_momentum():
@@ -62,50 +55,10 @@ def physical_tmat(xi_p, xi_d):
     return t
 
 
-def green_g0(rec, g, kind, npairs, zsqr=True):
-    """g0 of the 4 * npairs chains from the library's Green kernels (block: zsqr on the recursion's b2_b unless done already)."""
-    n = 4 * npairs
-    if kind == "block":
-        if zsqr:
-            rec.zsqr()
-        a_inf, b_inf, _, _ = g.terminator(nsites=n)
-        return g.block_green(a_inf, b_inf, nsites=n).copy()
-    return g.chebyshev_green(nsites=n).copy()
-
-
-def restated(g0, pairs, tmat):
-    return [damping_rows(g0[..., 4 * q:4 * q + 4], pairs[q, 0] == pairs[q, 1], tmat[..., q]) for q in range(len(pairs))]
-
-
-def ordered_total(rows):
-    """total_damping from the device's own rows, the pairs added in ascending order."""
-    t = np.zeros((9, rows.shape[1]))
-    for q in range(rows.shape[2]):
-        t = t + rows[:9, :, q]
-    return t
-
-
-def check_against(res, ref, ief, col0=0):
-    at_ef, total, rows = res
-    assert rows.shape[2] == len(ref)
-    for q, rr in enumerate(ref):
-        floor = np.abs(rr).max()                      # a row that vanishes by symmetry is judged on the pair's largest row
-        worst = max(np.abs(rows[r, :, q] - rr[r]).max() for r in range(18)) / max(floor, 1e-300)
-        print("pair %d: largest row %.3e, worst deviation / floor %.2e" % (q, floor, worst))
-        for r in range(18):
-            assert close(rows[r, :, q], rr[r], floor), (q, r)
-        assert close(at_ef[:, col0 + q], rr[:, ief - 1], floor), q
-        assert np.array_equal(at_ef[:, col0 + q], rows[:, ief - 1, q]), q
-    rt = total_damping(ref)
-    assert close(total, rt, max(np.abs(rr[:9]).max() for rr in ref))
-    assert np.array_equal(total, ordered_total(rows))
-    assert np.abs(rows).max() > 0
-
-
 def run_values(kind, hoh, tmat_of, lld=10):
     rec, g, ene, nv1, dpar = setup(PAIRS, hoh=hoh, kind=kind, lld=lld)
     tmat = tmat_of(len(PAIRS))
-    g0 = green_g0(rec, g, kind, len(PAIRS))
+    g0 = chain_g0(rec, g, kind, 4 * len(PAIRS))
     ref = restated(g0, PAIRS, tmat)
     ief = 166
     coef = (rec.a_b, rec.b2_b) if kind == "block" else None
@@ -140,17 +93,10 @@ def test_physical_tmat_matches_restatement(kind, hoh):
 
 
 DEVICE_SCRIPT = r"""
-import sys
-sys.path[:0] = [sys.argv[1], sys.argv[1] + "/tests"]
-import numpy as np, torch
-torch.cuda.init(); torch.cuda.set_device(0)          # torch's HIP runtime before librsrec's (as bench.py does)
-import test_gpu_exchange as X
-import test_gpu_damping as T
 from rslmtoasa_amd.exchange import Exchange
-mode = sys.argv[2]
 if mode == "sources":
     pairs = np.array([(1, 1), (1, 2), (7, 30), (2, 2), (9, 40)], np.int32)
-    rec, g, ene, nv1, dpar = X.setup(pairs, lld=8)
+    rec, g, ene, nv1, dpar = T.setup(pairs, lld=8)
     x = Exchange(rec, g)
     tmat, ief = T.random_tmat(len(pairs)), 120
     res_dev = x.damping(tmat, ief, rows=True, resident=True)
@@ -166,12 +112,12 @@ if mode == "sources":
     for other in (res_dev2, res_host, res_host_t, res_t):
         for a, b in zip(res_dev, other):
             assert np.array_equal(a, b)
-    g0 = T.green_g0(rec, g, "block", len(pairs), zsqr=False)
-    T.check_against(res_dev, T.restated(g0, pairs, tmat), ief)
+    g0 = T.chain_g0(rec, g, "block", 4 * len(pairs), zsqr=False)
+    T.check_damping(res_dev, T.damping_restated(g0, pairs, tmat), ief)
 else:
     # 8192 pairs at nE = 2510: g0 of their chains would take 427 GB, more than the device holds
     pairs = np.array([(1, 2)], np.int32)
-    rec, g, ene, nv1, dpar = X.setup(pairs, lld=4, channels=2501)
+    rec, g, ene, nv1, dpar = T.setup(pairs, lld=4, channels=2501)
     assert len(ene) == 2510
     rec.zsqr()
     x = Exchange(rec, g)
@@ -197,25 +143,16 @@ print("DAMPING_DEVICE_OK")
 """
 
 
-def run_device_script(mode):
-    """Own process: torch's HIP runtime has to be initialised before librsrec's (the other tests of this session have started it)."""
-    import os, subprocess, sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "-c", DEVICE_SCRIPT, root, mode], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0 and "DAMPING_DEVICE_OK" in r.stdout, (r.stdout + r.stderr)[-3000:]
-    print(r.stdout)
-
-
 def test_coefficient_sources_agree_bitwise():
     """Resident chains (i == j pairs compacted), caller coefficients with and without caller terminators, and device-pointer
     coefficients and tmat give the same bits; so does a repeated call.  And they match the restatement."""
-    run_device_script("sources")
+    run_device_script(DEVICE_SCRIPT, "sources", "DAMPING_DEVICE_OK")
 
 
 def test_memory_is_bounded_for_8192_pairs():
     """8192 pairs at nE = 2510 and lld 4 with rows = NULL finish; every pair (all the same chains) carries
     the single-pair result and total is the ordered sum."""
-    run_device_script("memory")
+    run_device_script(DEVICE_SCRIPT, "memory", "DAMPING_DEVICE_OK")
 
 
 SPLIT_PAIRS = np.array([(1, 1), (1, 2), (3, 19), (2, 2), (4, 50), (6, 7), (8, 8)], np.int32)

@@ -3,95 +3,16 @@ intersite Green functions, the 41 energy-resolved integrands, the Simpson integr
 import numpy as np
 import pytest
 
-from exchange_reference import PI, combos, exchange_pair, simpson_f
+from exchange_reference import PI, combos, simpson_f
 from helpers import load_golden, objects_from, supercell_problem
+from pair_cases import (check_exchange as check_against, close, exchange_restated as reference, onsite, pair_list, random_contour_dmat,
+                        random_tmat, run_device_script, setup)
 from rslmtoasa_amd import _lib
-from rslmtoasa_amd.exchange import Exchange, exchange_dpar
+from rslmtoasa_amd.exchange import Exchange, gauss_legendre
 from rslmtoasa_amd.green import Green
 from rslmtoasa_amd.recursion import Recursion
 
 pytestmark = pytest.mark.gpu
-
-TOL = 1e-12
-
-
-def mesh(channels_ldos, emin=-0.6, emax=0.4, fermi=-0.05):
-    """energy%ene and nv1 as e_mesh builds them (energy.f90:184-207)."""
-    if channels_ldos % 2 == 0:
-        nv1 = channels_ldos + 1
-    else:
-        nv1, channels_ldos = channels_ldos, channels_ldos - 1
-    edel = (emax - emin) / channels_ldos
-    edel = (fermi - emin) / round((fermi - emin) / edel)
-    ene = emin + edel * np.arange(channels_ldos + 10)
-    return ene, nv1
-
-
-def pair_list(kk, n, rng):
-    """n pairs of a kk-atom cell, the first an i == j pair, the rest a mix of near and distant atoms."""
-    pairs = [(1, 1)]
-    for _ in range(n - 1):
-        i = int(rng.integers(1, kk + 1))
-        j = int(rng.integers(1, kk + 1))
-        pairs.append((i, j))
-    return np.array(pairs, np.int32)
-
-
-def setup(pairs, lld=10, hoh=False, dims=(4, 4, 4), channels=300, kind="block", fermi=-0.05):
-    p = supercell_problem(dims, hoh=hoh)
-    ham, lat, ctl, en = objects_from(p, [1], lld, emin=-3.0, emax=1.8)
-    lat.ijpair = pairs
-    rec = Recursion(ham, lat, ctl, en)
-    if kind == "block":
-        rec.recur_b_ij()
-    else:
-        rec.chebyshev_recur_ij()
-    ene, nv1 = mesh(channels, fermi=fermi)
-    g = Green(rec, ene)
-    ntype = 1
-    c = np.array([[[-0.02, 0.05], [0.31, 0.36], [-0.12, 0.01]]])[:ntype]
-    dele = np.array([[[0.21, 0.20], [0.12, 0.11], [0.045, 0.052]]])[:ntype]
-    dpar = exchange_dpar(c, dele, np.array([0.013]), p["iz"], pairs)
-    return rec, g, ene, nv1, dpar
-
-
-def reference(rec, g, ene, nv1, dpar, fermi, kind, pairs, cumulative=True, zsqr=True):
-    """Restated outputs of every pair, from g0 of the library's Green kernels (pinned to the reference by test_gpu_green).
-    Block: runs zsqr on the recursion's b2_b unless that was done already (``zsqr=False``)."""
-    n = 4 * len(pairs)
-    if kind == "block":
-        if zsqr:
-            rec.zsqr()
-        a_inf, b_inf, _, _ = g.terminator(nsites=n)
-        g0 = g.block_green(a_inf, b_inf, nsites=n).copy()
-    else:
-        g0 = g.chebyshev_green(nsites=n).copy()
-    out = [exchange_pair(g0[..., 4 * q:4 * q + 4], pairs[q, 0] == pairs[q, 1], dpar[..., q], ene, fermi, nv1, cumulative) for q in range(len(pairs))]
-    return out, g0
-
-
-def close(mine, ref, floor, tol=TOL):
-    """max deviation relative to the largest magnitude of the compared set, or to `floor` (the largest quantity of the same kind of
-    the pair) where that is larger: quantities that vanish by symmetry are judged on the pair's scale."""
-    mine, ref = np.asarray(mine), np.asarray(ref)
-    scale = max(np.abs(ref).max(), floor, 1e-300)
-    return np.abs(mine - ref).max() / scale <= tol
-
-
-def check_against(res, out, with_jcum=True):
-    xc, so, fo, parts = res[:4]
-    for q, (rxc, rso, rfo, rparts, rj, rrows) in enumerate(out):
-        fv = max(np.abs(np.concatenate([rxc, rso, rfo, rparts])).max() * 1e-2, 1e-14)
-        for grp in (slice(0, 1), slice(1, 4), slice(4, 13)):
-            assert close(xc[grp, q], rxc[grp], fv) and close(so[grp, q], rso[grp], fv) and close(fo[grp, q], rfo[grp], fv), q
-        for grp in (slice(0, 4), slice(4, 10), slice(10, 28)):
-            assert close(parts[grp, q], rparts[grp], fv), q
-        if with_jcum:
-            assert close(res[4][:, q], rj, 0.0), q
-        integ = res[-1]
-        fr = np.abs(rrows).max() * 1e-2
-        for r in range(41):
-            assert close(integ[r, :, q], rrows[r], fr), (q, r)
 
 
 @pytest.mark.parametrize("hoh", [False, True])
@@ -123,13 +44,7 @@ def test_chebyshev_matches_restatement():
 
 
 DEVICE_SCRIPT = r"""
-import sys
-sys.path[:0] = [sys.argv[1], sys.argv[1] + "/tests"]
-import numpy as np, torch
-torch.cuda.init(); torch.cuda.set_device(0)          # torch's HIP runtime before librsrec's (as bench.py does)
-import test_gpu_exchange as T
 from rslmtoasa_amd.exchange import Exchange
-mode = sys.argv[2]
 if mode == "sources":
     pairs = np.array([(1, 1), (1, 2), (7, 30), (2, 2), (9, 40)], np.int32)
     rec, g, ene, nv1, dpar = T.setup(pairs, lld=8)
@@ -147,8 +62,8 @@ if mode == "sources":
     for other in (res_dev2, res_host, res_host_t, res_t):
         for a, b in zip(res_dev, other):
             assert np.array_equal(a, b)
-    out, _ = T.reference(rec, g, ene, nv1, dpar, fermi, "block", pairs, zsqr=False)
-    T.check_against(res_dev, out)
+    out, _ = T.exchange_restated(rec, g, ene, nv1, dpar, fermi, "block", pairs, zsqr=False)
+    T.check_exchange(res_dev, out)
 else:
     # 8192 pairs at nE = 2510: g0 of their chains would take 427 GB, more than the device holds
     pairs = np.array([(1, 2)], np.int32)
@@ -171,24 +86,15 @@ print("EXCHANGE_DEVICE_OK")
 """
 
 
-def run_device_script(mode):
-    """Own process: torch's HIP runtime has to be initialised before librsrec's (the other tests of this session have started it)."""
-    import os, subprocess, sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "-c", DEVICE_SCRIPT, root, mode], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0 and "EXCHANGE_DEVICE_OK" in r.stdout, (r.stdout + r.stderr)[-3000:]
-    print(r.stdout)
-
-
 def test_coefficient_sources_agree_bitwise():
     """Host arrays, device arrays and the chains the last seeded call left on the device (i == j pairs: compacted, as recur_b_ij runs
     them) give the same bits; so do repeated calls.  And they match the restatement."""
-    run_device_script("sources")
+    run_device_script(DEVICE_SCRIPT, "sources", "EXCHANGE_DEVICE_OK")
 
 
 def test_memory_is_bounded_for_8192_pairs():
     """8192 pairs at nE = 2510 and lld 4 finish, and every pair (all the same chains) carries the single-pair result."""
-    run_device_script("memory")
+    run_device_script(DEVICE_SCRIPT, "memory", "EXCHANGE_DEVICE_OK")
 
 
 def test_many_pairs_on_a_supercell():
@@ -218,6 +124,40 @@ def test_partitioned_images_sum_to_the_single_call():
     rec.rank, rec.nprocs = 0, 1
     for k in range(4):
         assert np.array_equal(parts[0][k] + parts[1][k], whole[k])
+    rec.close()
+
+
+@pytest.mark.parametrize("kind", ["block", "chebyshev"])
+@pytest.mark.parametrize("case", ["compute", "damping", "contour", "contour_occupation"])
+def test_chunk_caps_give_the_uncapped_bits(case, kind, monkeypatch):
+    """RSREC_PAIR_CHUNK = 1, 2 and 4 make these five-pair (three-site) calls run two to five chunks, the last one short: every array they
+    return, per-item rows included, carries the bits of the one-chunk call, on the resident chains and on the host coefficient arrays."""
+    if case == "contour_occupation":
+        rec = onsite(kind, 8)
+        x, w = gauss_legendre(8)
+        g = Green(rec, np.array([-0.07]))
+        call = lambda **kw: g.contour_occupation(x, w, -0.07, kind=kind, diag=True, **kw)
+    else:
+        pairs = np.array([(1, 1), (1, 2), (7, 30), (2, 2), (9, 40)], np.int32)
+        rec, g, ene, nv1, dpar = setup(pairs, lld=8, channels=100, kind=kind)
+        ex = Exchange(rec, g)
+        x, w = gauss_legendre(8)
+        tmat, dmat = random_tmat(len(pairs)), random_contour_dmat(len(pairs))
+        call = {"compute": lambda **kw: ex.compute(-0.05, nv1, dpar, kind=kind, integrand=True, cumulative=True, **kw),
+                "damping": lambda **kw: ex.damping(tmat, 61, kind=kind, rows=True, **kw),
+                "contour": lambda **kw: ex.contour(x, w, float(ene[50]), dmat, kind=kind, rows=True, **kw)}[case]
+    one = call(resident=True)
+    if kind == "block":
+        rec.zsqr()
+    one_host = call()
+    assert np.abs(one[0]).max() > 0 and np.abs(one_host[0]).max() > 0
+    for cap in ("1", "2", "4"):
+        monkeypatch.setenv("RSREC_PAIR_CHUNK", cap)
+        many, many_host = call(resident=True), call()
+        monkeypatch.delenv("RSREC_PAIR_CHUNK")
+        assert len(many) == len(one) and len(many_host) == len(one_host)
+        for a, b in list(zip(one, many)) + list(zip(one_host, many_host)):
+            assert np.array_equal(a, b), cap
     rec.close()
 
 

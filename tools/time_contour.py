@@ -60,8 +60,8 @@ def timed(fn, reps):
 
 
 def main():
-    import test_gpu_contour as T
-    import test_gpu_exchange as X
+    import pair_cases as X
+    from contour_reference import contour_eta
     from rslmtoasa_amd.exchange import Exchange, gauss_legendre
     ap = argparse.ArgumentParser()
     ap.add_argument("--lld", type=int, default=20)
@@ -73,7 +73,7 @@ def main():
     ap.add_argument("--loop-pairs", type=int, default=4)
     args = ap.parse_args()
     x, w = gauss_legendre(args.npts)
-    eta = T.contour_eta(x)
+    eta = contour_eta(x)
     base = np.array([(1, 2), (1, 9), (3, 17), (5, 60)], np.int32)
     rec, g, ene, nv1, dpar = X.setup(base, lld=args.lld, dims=tuple(args.dims), channels=100)
     rec.zsqr()
@@ -87,7 +87,7 @@ def main():
         a_h = np.asfortranarray(np.tile(a16, (1, 1, 1, reps))[..., :4 * n])
         b_h = np.asfortranarray(np.tile(b16, (1, 1, 1, reps))[..., :4 * n])
         rec.lattice.ijpair = np.tile(base, (reps, 1))[:n]
-        dmat = T.random_dmat(n)
+        dmat = X.random_contour_dmat(n)
         dev = []
 
         def new():

@@ -21,7 +21,7 @@ def main():
     import torch
     torch.cuda.init()                                  # torch's HIP runtime before librsrec's
     torch.cuda.set_device(0)
-    import test_gpu_exchange as T
+    import pair_cases as T
     from rslmtoasa_amd.exchange import Exchange
     ap = argparse.ArgumentParser()
     ap.add_argument("--lld", type=int, nargs="+", default=[20, 50])
