@@ -58,6 +58,11 @@ module recursion_gpu_mod
       !> launch), and conductivity_gpu writes the files of further field f with the prefix 'E<f>_' before whatever the set is called
       !> otherwise (Ey_fort.123, Ey_spin_cond_total.out).  Implies kubo_diag.  Empty (the default): a run is what it was.
       character(len=64) :: kubo_fields = ''
+      !> RSREC_PAIR_DIRECT: chebyshev_recur_ij takes the pair moments from ONE Chebyshev chain per atom (rsrec_chebyshev_pairs_direct)
+      !> instead of four chains per pair.  1 ('1'): one chain per distinct first atom of the rank's pairs, M_ij := M_ji^H (H Hermitian, as the
+      !> reference's moment doubling already requires); the slots stored in mu_n then LACK the (M_ii + M_jj)/2 every consumer cancels
+      !> (INTEGRATION.md).  2 ('both'): chains from both atoms of every pair, the reference's own slot values.  0 (unset): the four-chain call.
+      integer :: pair_direct = 0
    contains
       procedure :: recur => gpu_recur
       procedure :: recur_b => gpu_recur_b
@@ -106,6 +111,7 @@ contains
       class(hamiltonian), target, intent(in) :: hamiltonian_obj     ! (class: a type(hamiltonian_gpu) is accepted as well)
       type(energy), target, intent(in) :: energy_obj
       integer :: n, stat
+      character(len=8) :: direct
 
       obj%hamiltonian => hamiltonian_obj
       obj%lattice => hamiltonian_obj%charge%lattice
@@ -120,6 +126,16 @@ contains
       call get_environment_variable('RSREC_KUBO_FIELDS', obj%kubo_fields, n, stat)
       if (stat > 0 .or. n == 0) obj%kubo_fields = ''
       if (stat == -1) call g_logger%fatal('recursion_gpu: RSREC_KUBO_FIELDS is longer than 64 characters', __FILE__, __LINE__)
+      call get_environment_variable('RSREC_PAIR_DIRECT', direct, n, stat)
+      if (stat == 0 .and. n > 0) then
+         select case (trim(direct))
+         case ('1'); obj%pair_direct = 1
+         case ('both'); obj%pair_direct = 2
+         case default; call g_logger%fatal('recursion_gpu: RSREC_PAIR_DIRECT is "'//trim(direct)//'", not 1 or both', __FILE__, __LINE__)
+         end select
+      else if (stat == -1) then
+         call g_logger%fatal('recursion_gpu: RSREC_PAIR_DIRECT is not 1 or both', __FILE__, __LINE__)
+      end if
    end function gpu_constructor
 
    !> Sites of this rank whose a_b / b2_b (as recur_b produced them) are also resident on the device; 0 if they are not.
@@ -428,12 +444,31 @@ contains
       integer(c_int), allocatable, target :: seeds(:, :)
       integer, allocatable :: slot(:)
       complex(rp), allocatable, target :: coef(:, :), mu(:, :, :, :)
+      integer(c_int), allocatable, target :: pairs(:, :)
 
       nch = 4*max(end_atom - start_atom + 1, 0)
       if (nch <= 0) return
       nmom = 2*this%control%lld + 2
       a = (this%en%energy_max - this%en%energy_min)/(2 - 0.3)
       b = (this%en%energy_max + this%en%energy_min)/2
+      if (this%pair_direct /= 0) then
+         ! one chain per atom: pair p of the call is the rank's pair with ij_loc = p, its four slots are columns 4 p - 3 .. 4 p
+         allocate (pairs(2, nch/4), mu(18, 18, nmom, nch))
+         do ij = start_atom, end_atom
+            pairs(:, g2l_map(ij)) = [int(this%lattice%ijpair(ij, 1), c_int), int(this%lattice%ijpair(ij, 2), c_int)]
+         end do
+         call sync_device(this, .true.)
+         call g_timer%start('pair-direct-gpu')
+         g_block_resident = 0
+         g_cheb_resident = 0
+         g_kubo_diag_nvec = 0
+         rc = rsrec_chebyshev_pairs_direct(g_handle, int(nch/4, c_int), c_loc(pairs), int(this%control%lld, c_int), real(a, c_double), &
+                                           real(b, c_double), int(merge(1, 0, this%pair_direct == 2), c_int), c_loc(mu), c_null_ptr)
+         call g_timer%stop('pair-direct-gpu')
+         call check(rc, 'rsrec_chebyshev_pairs_direct')
+         this%mu_n(:, :, 1:nmom, 1:nch) = mu
+         return
+      end if
       allocate (seeds(2, nch), coef(2, nch), slot(nch), mu(18, 18, nmom, nch))
       c = 0
       do ij = start_atom, end_atom

@@ -385,6 +385,17 @@ module rsrec_binding
          integer(c_int) :: rc
       end function
 
+      !> ijpair: int32 (2, npairs); mu_n: complex (18,18,2*lld+2,4*npairs); m_pair: complex (18,18,2*lld+2,2,npairs) or c_null_ptr
+      function rsrec_chebyshev_pairs_direct(handle, npairs, ijpair, lld, a, b, both_ends, mu_n, m_pair) &
+         bind(C, name='rsrec_chebyshev_pairs_direct') result(rc)
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: handle
+         integer(c_int), value :: npairs, lld, both_ends
+         real(c_double), value :: a, b
+         type(c_ptr), value :: ijpair, mu_n, m_pair
+         integer(c_int) :: rc
+      end function
+
       function rsrec_scalar_lanczos(handle, nsites, seed_atoms, lld, llmax, a, b2) bind(C, name='rsrec_scalar_lanczos') result(rc)
          import :: c_int, c_ptr
          type(c_ptr), value :: handle

@@ -260,6 +260,36 @@ int rsrec_chebyshev(rsrec_t *h, int nsites, const int32_t *seed_atoms, int lld, 
 int rsrec_chebyshev_seeded(rsrec_t *h, int nchains, int nseed, const int32_t *seed_atoms, const double *seed_coef,
                            int lld, double a, double b, double *mu_n);
 
+/* The pair moments of chebyshev_recur_ij from ONE chain per atom instead of four per pair.  Everything that reads the four moment sets of
+ * a pair only recombines them (green.f90:446-453; chebyshev_green_ij is linear in the moments) into
+ *   M_ij(n) = <i| T_{n-1}(H~) |j>,  M_ji(n) = <j| T_{n-1}(H~) |i>,   n = 1 .. 2*lld+2,
+ * and M_ji(n) is the 18x18 block at atom j of the Chebyshev vector psi_{n-1} started from the identity at atom i: one chain from i, run
+ * for 2*lld+1 applications of H~ (three-term recurrence, no moment doubling, no Gram pass), gives M_ji for every j at once.
+ *   ijpair    : int32 (2,npairs), 1-based: pair p is (ijpair(1,p), ijpair(2,p)) = (i, j)
+ *   both_ends : 0: the sources are the distinct FIRST atoms of the pairs and M_ij := M_ji^H.  THE CALLER ASSERTS THAT H IS HERMITIAN (the
+ *               reference's own doubling identities, mu_{2n+1} = 2 psi_n^H psi_n - mu_1, already require it); nothing checks it.
+ *               1: the sources are the distinct atoms of both columns and nothing is conjugated: M_ij comes from source j, M_ji from
+ *               source i, M_ii and M_jj from their own sources.
+ *   mu_n      : complex (18,18,2*lld+2,4*npairs) out, slot order ij_loc*4 - 4 + reci as rsrec_chebyshev_seeded fills it for the reference's
+ *               seeds.  With o = (M_ij + M_ji)/2, q = i (M_ij - M_ji)/2, d = (M_ii + M_jj)/2:
+ *                 i /= j, both_ends = 1: d + o, d - o, d + q, d - q -- the reference's own slot values;
+ *                 i /= j, both_ends = 0: o, -o, q, -q -- THE REFERENCE'S SLOTS WITHOUT d, which every consumer cancels (gij and gji are
+ *                 differences of slots 1, 2 and of slots 3, 4); slots 2 and 4 are the exact negatives of slots 1 and 3;
+ *                 i == j: M_ii / 2 in all four slots (the reference's second seed coefficient overwrites the first).
+ *   m_pair    : complex (18,18,2*lld+2,2,npairs) out or NULL: M_ij and M_ji themselves.
+ * A moment of an order at which the chain's growing region has not reached the target atom is an exact zero.
+ * The packed image stays resident exactly as a rsrec_chebyshev_seeded call of 4*npairs chains of depth lld leaves its moments: rsrec_exchange,
+ * rsrec_damping, rsrec_exchange_aux, rsrec_spin_lattice and rsrec_exchange_contour with NULL coefficient arrays, and rsrec_pack_moments,
+ * follow it unchanged.  Cost of P pairs around one atom: 2*lld+1 chain applications instead of 4*P*(lld+1).
+ * Every sum runs in a fixed order without atomics: the same inputs give the same bits, and a pair's moments depend neither on the other
+ * pairs of the call nor on option batch.  Both kernel sets (option kernels), hoh and per-atom operator blocks are served.
+ * RSREC_ERR_DIVERGED if sum(real(M_ii(n))) > 1000 for any source and order -- the reference's test (recursion.f90:2479) on the one moment
+ * that is a chain moment.  RSREC_ERR_ARG for an atom outside 1..kk, lld < 1, a == 0 or a NULL ijpair / mu_n with npairs > 0; the handle
+ * stays usable.  npairs = 0 returns RSREC_OK.  rsrec_get_timing as rsrec_chebyshev_seeded: out[0] device ms, out[1] ms in the H|psi>
+ * launches, out[2] their number. */
+int rsrec_chebyshev_pairs_direct(rsrec_t *h, int npairs, const int32_t *ijpair, int lld, double a, double b, int both_ends,
+                                 double *mu_n, double *m_pair);
+
 /* Stochastic Kubo-Bastin double moments.  Replaces compute_moments_stochastic (recursion.f90:979-1234) together with the
  * whole-vector products it is built from: ham_vec_matmul (:913), ham_hoh_vec_matmul (:785), velo_vec_matmul (:587),
  * velo_hoh_vec_matmul (:656):

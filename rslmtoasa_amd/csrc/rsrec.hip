@@ -16,6 +16,7 @@
 #include <hsa/hsa_ext_amd.h>
 #include <dlfcn.h>
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -45,6 +46,7 @@
 #include "kernels_auxgreen.hpp"
 #include "kernels_contour.hpp"
 #include "kernels_assemble.hpp"
+#include "kernels_fan.hpp"
 
 using namespace rsrec;
 
@@ -138,6 +140,7 @@ struct rsrec_handle {
     void* pin = nullptr;              // pinned host staging buffer: every per-call transfer goes through it (see xfer_*)
     size_t pin_bytes = 0;
     DevBuf d_frags, d_vec[6], d_partial, d_partial2, d_coefA, d_coefB, d_bmats, d_status, d_seed, d_seedcoef, d_mu, d_scal, d_zsqr;
+    DevBuf d_fan, d_fan_tab, d_mpair;   // rsrec_chebyshev_pairs_direct: gathered blocks M(18,18,nmom,entry); entry and pair tables; M_ij / M_ji of every pair
     // options
     long opt_batch = 0, opt_kernels = 0, opt_nblk = 0, opt_spmm5 = 2, opt_chain_fold = 1, opt_s5_cap = 0, opt_side = 1, opt_s5_lds = 1, opt_s5_queue = 1, opt_cheb_fused = 1;
     long opt_s5_waves = 8;
@@ -3239,6 +3242,181 @@ extern "C" int rsrec_chebyshev_seeded(rsrec_t* h, int nchains, int nseed, const 
 
 extern "C" int rsrec_chebyshev(rsrec_t* h, int nsites, const int32_t* seed_atoms, int lld, double a, double b, double* mu_n) {
     return rsrec_chebyshev_seeded(h, nsites, 1, seed_atoms, nullptr, lld, a, b, mu_n);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Pair moments from one chain per atom (kernels_fan.hpp): a sibling of run_chebyshev on the same RecursionCall / recursion_batch set-up
+namespace {
+
+// the level at which every atom joins the growing region of a chain seeded at `seed` (grow_region's rule: an atom joins when one of ITS
+// neighbour slots holds an atom already inside), -1: not within levels 0 .. nlev - 1
+void region_levels(const rsrec_t* h, int seed, int nlev, std::vector<int>& dist) {
+    dist.assign(h->kk, -1);
+    std::vector<int> frontier{seed}, next;
+    dist[seed] = 0;
+    for (int level = 0; !frontier.empty() && level + 1 < nlev; ++level) {
+        next.clear();
+        for (int n : frontier)
+            for (int q = h->radj_ptr[n]; q < h->radj_ptr[n + 1]; ++q) {
+                const int i = h->radj[q];
+                if (dist[i] < 0) { dist[i] = level + 1; next.push_back(i); }
+            }
+        frontier.swap(next);
+    }
+}
+
+// Sources, gathered blocks and pair records of a call.  Sources ascend by atom; a source's entries follow each other, its own block first.
+struct FanPlan {
+    std::vector<int32_t> sources;          // 1-based atoms, as recursion_batch takes seeds
+    std::vector<FanEntry> entries;
+    std::vector<int> ent_begin;            // first entry of every source, and the total behind the last
+    std::vector<FanPair> pairs;
+};
+void fan_plan(const rsrec_t* h, int npairs, const int32_t* ijpair, int both_ends, int nlev, FanPlan& F) {
+    for (int p = 0; p < npairs; ++p) {
+        F.sources.push_back(ijpair[2 * p]);
+        if (both_ends) F.sources.push_back(ijpair[2 * p + 1]);
+    }
+    std::sort(F.sources.begin(), F.sources.end());
+    F.sources.erase(std::unique(F.sources.begin(), F.sources.end()), F.sources.end());
+    const int nsrc = (int)F.sources.size();
+    auto source_of = [&](int atom1) { return (int)(std::lower_bound(F.sources.begin(), F.sources.end(), atom1) - F.sources.begin()); };
+    std::vector<std::vector<int>> targets(nsrc);                 // 0-based atoms, the source itself first
+    for (int s = 0; s < nsrc; ++s) targets[s].push_back(F.sources[s] - 1);
+    auto slot_of = [&](int s, int atom0) {                       // position of a target in its source's list, appended when new
+        auto& T = targets[s];
+        const auto it = std::find(T.begin(), T.end(), atom0);
+        if (it != T.end()) return (int)(it - T.begin());
+        T.push_back(atom0);
+        return (int)T.size() - 1;
+    };
+    std::vector<std::array<int, 4>> local(npairs);               // (source, slot) of ji and ij
+    for (int p = 0; p < npairs; ++p) {
+        const int i = ijpair[2 * p], j = ijpair[2 * p + 1];
+        const int si = source_of(i);
+        local[p] = {si, slot_of(si, j - 1), -1, -1};
+        if (both_ends && i != j) { const int sj = source_of(j); local[p][2] = sj; local[p][3] = slot_of(sj, i - 1); }
+    }
+    F.ent_begin.assign(nsrc + 1, 0);
+    std::vector<int> dist;
+    for (int s = 0; s < nsrc; ++s) {
+        F.ent_begin[s] = (int)F.entries.size();
+        region_levels(h, F.sources[s] - 1, nlev, dist);
+        for (int atom0 : targets[s]) F.entries.push_back(FanEntry{s, atom0, dist[atom0], atom0 == F.sources[s] - 1 ? 1 : 0});
+    }
+    F.ent_begin[nsrc] = (int)F.entries.size();
+    F.pairs.resize(npairs);
+    for (int p = 0; p < npairs; ++p) {
+        const int i = ijpair[2 * p], j = ijpair[2 * p + 1];
+        FanPair& P = F.pairs[p];
+        P.ii = F.ent_begin[local[p][0]];
+        P.ji = F.ent_begin[local[p][0]] + local[p][1];
+        P.ij = P.jj = -1;
+        if (i == j) P.mode = 0;
+        else if (!both_ends) P.mode = 1;
+        else { P.mode = 2; P.ij = F.ent_begin[local[p][2]] + local[p][3]; P.jj = F.ent_begin[local[p][2]]; }
+    }
+}
+
+// L = LayoutCM with the VALU kernels; the matrix-core set always takes k_spmm5 on CI vectors here (the new vector is formed in its epilogue)
+template <class L, bool MFMA>
+int run_pairs_direct(rsrec_t* h, int npairs, const int32_t* ijpair, int lld, double a, double b, int both_ends, double* mu_n, double* m_pair) {
+    const bool hoh = h->hoh != 0;
+    const int napply = 2 * lld + 1;                              // psi_1 .. psi_{2 lld + 1}: moment n + 1 is a block of psi_n
+    const int nmom = 2 * lld + 2;
+    FanPlan F;
+    RecursionCall RC = recursion_call(h, MFMA, 0, 1, napply);
+    fan_plan(h, npairs, ijpair, both_ends, RC.nlev, F);
+    const int nsrc = RC.nchains = (int)F.sources.size(), nent = (int)F.entries.size();
+    if (MFMA) RC.ci = 1;
+    const size_t velems = RC.velems, mstride = (size_t)nmom * BLK;
+    // resident outputs first, the batch is planned from what is left (see run_chebyshev)
+    h->res_kind = 0; h->spec_res.nop = 0;
+    HIPCK(h, h->d_mu.reserve((size_t)4 * npairs * mstride * sizeof(double2)));
+    HIPCK(h, h->d_fan.reserve((size_t)nent * mstride * sizeof(double2)));
+    const size_t ent_bytes = (size_t)nent * sizeof(FanEntry), pair_off = (ent_bytes + 255) / 256 * 256;
+    HIPCK(h, h->d_fan_tab.reserve(pair_off + (size_t)npairs * sizeof(FanPair)));
+    if (m_pair) HIPCK(h, h->d_mpair.reserve((size_t)2 * npairs * mstride * sizeof(double2)));
+    XFER(recursion_begin(h, RC, MFMA ? (hoh ? 5 : 4) : (hoh ? 4 : 3), MFMA ? 3 : -1, 1));
+    XFER(xfer_h2d(h, h->d_fan_tab.p, F.entries.data(), ent_bytes));
+    XFER(xfer_h2d(h, static_cast<char*>(h->d_fan_tab.p) + pair_off, F.pairs.data(), (size_t)npairs * sizeof(FanPair)));
+    const FanEntry* d_ent = h->d_fan_tab.as<FanEntry>();
+    const FanPair* d_pairs = reinterpret_cast<const FanPair*>(static_cast<const char*>(h->d_fan_tab.p) + pair_off);
+    double2* img = h->d_fan.as<double2>();
+    const int nblk = RC.nblk;
+    for (int c0 = 0; c0 < nsrc; c0 += RC.B) {
+        const int nb = std::min(RC.B, nsrc - c0);
+        const int e0 = F.ent_begin[c0], ne = F.ent_begin[c0 + nb] - e0;
+        RecursionBatch bt;
+        XFER(recursion_batch(h, RC, F.sources.data(), nullptr, c0, nb, bt));
+        const ChainView& CV = bt.CV;
+        XFER(clear_vectors(h, RC, nb));
+        double *p0 = h->d_vec[0].as<double>(), *p1 = h->d_vec[1].as<double>(), *p2 = h->d_vec[2].as<double>();
+        double* tmp = MFMA ? nullptr : h->d_vec[3].as<double>();
+        double* hps = (MFMA && hoh) ? h->d_vec[4].as<double>() : nullptr;   // hoh: h psi of the first pass
+        auto gather = [&](const double* vec, int level, int n) {
+            if (MFMA) k_fan_gather<LayoutCI><<<ne, FAN_THREADS, 0, h->stream>>>(vec, velems, d_ent, e0, c0, level, n, nmom, img, h->d_status.as<int>());
+            else k_fan_gather<L><<<ne, FAN_THREADS, 0, h->stream>>>(vec, velems, d_ent, e0, c0, level, n, nmom, img, h->d_status.as<int>());
+        };
+        if (MFMA) k_seed<LayoutCI><<<nb, 64, 0, h->stream>>>(p0, velems, h->d_seed.as<int>(), h->d_seedcoef.as<double2>(), 1);
+        else k_seed<L><<<nb, 64, 0, h->stream>>>(p0, velems, h->d_seed.as<int>(), h->d_seedcoef.as<double2>(), 1);
+        gather(p0, 0, 0);
+        const dim3 grid(nblk, nb);
+        for (int t = 1; t <= napply; ++t) {
+            const bool first = (t == 1);
+            const int lv_final = hoh ? 2 * t : t;
+            double *src = first ? p0 : p1, *dst = first ? p1 : p2;
+            if (MFMA) XFER(apply_h(h, RC, bt, t, src, dst, hps, nullptr, 0, cheb_epilogue(first, src, p0, a, b)));
+            else {
+                hipEvent_t ev0 = next_event(h);
+                ApplyArgs G{};
+                G.partial = h->d_partial.as<double2>(); G.a = a; G.b = b;     // (the kernels' Gram partials are written and never read)
+                if (!hoh) {
+                    G.in = src; G.cur = src; G.v0 = p0; G.out = dst; G.level = lv_final;
+                    if (first) k_apply<AM_CHEB1, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
+                    else k_apply<AM_CHEBN, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
+                } else {
+                    G.in = src; G.out = tmp; G.level = 2 * t - 1;
+                    k_apply<AM_STORE, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
+                    G.in = tmp; G.v1 = tmp; G.cur = src; G.v0 = p0; G.out = dst; G.level = lv_final;
+                    if (first) k_apply<AM_HOH_CHEB1, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
+                    else k_apply<AM_HOH_CHEBN, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
+                }
+                RC.hop_ev.emplace_back(ev0, next_event(h)); h->n_hop_launch += hoh ? 2 : 1;
+            }
+            gather(dst, lv_final, t);
+            if (!first) { double* o = p0; p0 = p1; p1 = p2; p2 = o; }
+        }
+        HIPCK(h, hipGetLastError());
+        HIPCK(h, hipStreamSynchronize(h->stream));               // the next batch's uploads reuse the seeds
+    }
+    double2* mu = h->d_mu.as<double2>();
+    double2* mp = m_pair ? h->d_mpair.as<double2>() : nullptr;
+    for (int q0 = 0; q0 < npairs; q0 += 32768) {                 // (grid.y holds 65535 at most)
+        const int nq = std::min(32768, npairs - q0);
+        k_fan_pack<<<dim3(nmom, nq), FAN_THREADS, 0, h->stream>>>(img, d_pairs + q0, nmom, mu + (size_t)4 * q0 * mstride, mp ? mp + (size_t)2 * q0 * mstride : nullptr);
+    }
+    HIPCK(h, hipGetLastError());
+    XFER(xfer_d2h(h, mu_n, mu, (size_t)4 * npairs * mstride * sizeof(double2)));
+    if (m_pair) XFER(xfer_d2h(h, m_pair, mp, (size_t)2 * npairs * mstride * sizeof(double2)));
+    XFER(recursion_end(h, RC, 2, lld, true));
+    h->res_n = 4 * npairs;                                       // what a seeded call of 4 npairs chains leaves
+    return RSREC_OK;
+}
+
+}  // namespace
+
+extern "C" int rsrec_chebyshev_pairs_direct(rsrec_t* h, int npairs, const int32_t* ijpair, int lld, double a, double b, int both_ends, double* mu_n,
+                                            double* m_pair) {
+    int rc = check_ready(h, "rsrec_chebyshev_pairs_direct");
+    if (rc) return rc;
+    if (npairs < 0 || lld < 1 || a == 0.0 || (npairs > 0 && (!ijpair || !mu_n))) return fail(h, RSREC_ERR_ARG, "rsrec_chebyshev_pairs_direct: bad argument");
+    XFER(check_seeds(h, "rsrec_chebyshev_pairs_direct", ijpair, (size_t)2 * npairs, 1));
+    HIPCK(h, hipSetDevice(h->device));
+    reset_timing(h);
+    if (npairs == 0) return RSREC_OK;
+    if (h->opt_kernels != 1 && h->s5_built) return run_pairs_direct<LayoutRM, true>(h, npairs, ijpair, lld, a, b, both_ends ? 1 : 0, mu_n, m_pair);
+    return run_pairs_direct<LayoutCM, false>(h, npairs, ijpair, lld, a, b, both_ends ? 1 : 0, mu_n, m_pair);
 }
 
 // ------------------------------------------------------------------------------------------------------------------

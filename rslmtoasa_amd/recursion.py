@@ -328,6 +328,26 @@ class Recursion:
         self._check(self._L.rsrec_chebyshev_seeded(self._h, nch, 2, _ptr(sa), _ptr(sc), lld, a, b, _ptr(mu)))
         self.mu_n[:, :, :, slots] = mu
 
+    def chebyshev_recur_ij_direct(self, both_ends=False):
+        """The moments ``chebyshev_recur_ij`` delivers, from one chain per atom instead of four per pair
+        (``rsrec_chebyshev_pairs_direct``): the block at atom j of the Chebyshev vector started at atom i is M_ji(n) = <j|T_n|i>.
+        ``both_ends=False``: one chain per distinct first atom, M_ij := M_ji^H (the caller asserts a Hermitian H), and the slots written to
+        ``self.mu_n`` lack the (M_ii + M_jj)/2 that every consumer cancels.  ``both_ends=True``: chains from both atoms of every pair,
+        the reference's own slot values.  Same rank partition of ``ijpair`` and the same slots ij_loc*4 - 4 + reci as
+        ``chebyshev_recur_ij``; the image stays resident for ``Exchange.compute(resident=True)`` and its siblings.  Returns ``m_pair``
+        (18, 18, 2 lld + 2, 2, npairs): M_ij and M_ji of this rank's pairs."""
+        lld = self.control.lld
+        a, b = chebyshev_scaling(self.en.energy_min, self.en.energy_max)
+        pairs = np.asarray(self.lattice.ijpair, dtype=np.int32).reshape(-1, 2)
+        start, end = site_partition(self.rank, self.nprocs, len(pairs))
+        mine = np.ascontiguousarray(pairs[start - 1:end])            # (npairs, 2) in C order = (2, npairs) column-major
+        n = len(mine)
+        mu = np.zeros((18, 18, 2 * lld + 2, 4 * n), np.complex128, order="F")
+        m_pair = np.zeros((18, 18, 2 * lld + 2, 2, n), np.complex128, order="F")
+        self._check(self._L.rsrec_chebyshev_pairs_direct(self._h, n, _ptr(mine), lld, a, b, int(bool(both_ends)), _ptr(mu), _ptr(m_pair)))
+        self.mu_n[:, :, :, :4 * n] = mu
+        return m_pair
+
     def zsqr(self):
         """b2_b <- sqrt(b2_b) in place (recursion.f90:1980-2023)."""
         self._check(self._L.rsrec_zsqr(self._h, self.b2_b.shape[2] * self.b2_b.shape[3], _ptr(self.b2_b)))
