@@ -396,6 +396,18 @@ module rsrec_binding
          integer(c_int) :: rc
       end function
 
+      !> sources: int32 (nsrc); cr: real (3,kk); cell: real (3,3) or c_null_ptr; kpt: real (3,nk); group: int32 (kk) or c_null_ptr;
+      !> s_k: complex (18,18,2*lld+2,nk,ngroup,nsrc) or c_null_ptr
+      function rsrec_chebyshev_bloch(handle, nsrc, sources, lld, a, b, cr, cell, nk, kpt, ngroup, group, s_k) &
+         bind(C, name='rsrec_chebyshev_bloch') result(rc)
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: handle
+         integer(c_int), value :: nsrc, lld, nk, ngroup
+         real(c_double), value :: a, b
+         type(c_ptr), value :: sources, cr, cell, kpt, group, s_k
+         integer(c_int) :: rc
+      end function
+
       function rsrec_scalar_lanczos(handle, nsites, seed_atoms, lld, llmax, a, b2) bind(C, name='rsrec_scalar_lanczos') result(rc)
          import :: c_int, c_ptr
          type(c_ptr), value :: handle

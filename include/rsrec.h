@@ -290,6 +290,43 @@ int rsrec_chebyshev_seeded(rsrec_t *h, int nchains, int nseed, const int32_t *se
 int rsrec_chebyshev_pairs_direct(rsrec_t *h, int npairs, const int32_t *ijpair, int lld, double a, double b, int both_ends,
                                  double *mu_n, double *m_pair);
 
+/* k-resolved Chebyshev moments from ONE chain per atom (no counterpart in the reference, which has no k-space routine).  The Chebyshev
+ * vector psi_n started from the identity at atom i holds <j| T_n(H~) |i> at every atom j of its region; its lattice Fourier sum
+ *   S_i(k, n) = sum_j exp(-i k.(r_j - r_i)) <j| T_n(H~) |i>
+ * is the k-resolved moment: T_n(H~(k)) itself on a periodic one-atom cell, and with the kernel-weighted sum of rsrec_chebyshev_ldos /
+ * rsrec_chebyshev_spectra / rsrec_chebyshev_green the Bloch spectral function A(k,E) = -Im Tr G(k,E) / pi (bands of bulk cells, unfolded
+ * bands of supercells; with atoms grouped by layer and k in the surface plane the k-parallel resolved spectral function of a slab).
+ *   sources : int32 (nsrc), 1-based atoms: chain s starts from the identity at sources(s).  Duplicates are allowed and give equal bits.
+ *   cr      : real (3,kk), the positions for THIS call (the rsrec_set_positions hint is neither read nor changed)
+ *   cell    : real (3,3), columns = the supercell vectors, or NULL.  Given: every displacement d = cr(:,j) - cr(:,i) is reduced to its
+ *             minimum image d - cell nint(cell^-1 d).  For k commensurate with the supercell the reduction does not matter (the phase
+ *             of a supercell vector is 1); for any other k the sum only means something while the chain's region has not wrapped
+ *             around the cell, and the minimum image is then the displacement the hopping path actually covered.
+ *   kpt     : real (3,nk), Cartesian, 2 pi included: the phase is exp(-i k.d).  1 <= nk <= RSREC_BLOCH_NK_MAX.
+ *   group   : int32 (kk), values 0..ngroup, 0 = the atom is left out; NULL with ngroup = 1: every atom in group 1.
+ *             1 <= ngroup <= RSREC_BLOCH_NGROUP_MAX.
+ *   s_k     : complex (18,18,2*lld+2,nk,ngroup,nsrc) out, or NULL (nothing is downloaded):
+ *               s_k(:,:,n,q,g,s) = sum over the atoms j with group(j) == g inside the chain's region at order n-1
+ *                                  of exp(-i k_q.d(j,i_s)) [psi_{n-1}]_j,    n = 1 .. 2*lld+2
+ *             psi follows the three-term recurrence of rsrec_chebyshev_pairs_direct: 2*lld+1 applications of H~, no moment doubling.
+ * An atom contributes from the order at which it joins the region; nothing outside the region is ever read.
+ * The image stays resident exactly as a rsrec_chebyshev call of nsrc*ngroup*nk sites of depth lld leaves its moments, image index
+ * q + nk*((g-1) + ngroup*(s-1)) (0-based q): rsrec_chebyshev_ldos, rsrec_chebyshev_spectra and rsrec_pack_moments follow unchanged, called
+ * with nsites_total >= that count.
+ * The phases are tabulated once per (source, k-point, atom) with FP64 sincos; the sums are FP64 matrix-core GEMMs (kernels_bloch.hpp).
+ * Every sum runs in a fixed order without atomics: the bits of an image depend only on its own k-point, the atom set of its own group
+ * and its own source -- not on the other k-points, groups or sources of the call, nor on option batch, nor on what earlier calls left in
+ * the work buffers.  Both kernel sets (option kernels), hoh and per-atom operator blocks are served.
+ * RSREC_ERR_DIVERGED if sum(real(M_ii(n))) > 1000 for the own block of any source at any order (as rsrec_chebyshev_pairs_direct).
+ * RSREC_ERR_ARG with a message, the handle staying usable, for: nk or ngroup out of range; a group value outside 0..ngroup; NULL group
+ * with ngroup > 1; a source outside 1..kk; NULL sources, cr or kpt; a singular cell; lld < 1; a == 0.  nsrc = 0 returns RSREC_OK.
+ * rsrec_get_timing: out[0] device ms, out[1] ms in the H|psi> launches, out[2] their number, out[5] ms in the phase-table and Bloch-sum
+ * kernels alone. */
+#define RSREC_BLOCH_NK_MAX 4096
+#define RSREC_BLOCH_NGROUP_MAX 16
+int rsrec_chebyshev_bloch(rsrec_t *h, int nsrc, const int32_t *sources, int lld, double a, double b, const double *cr, const double *cell,
+                          int nk, const double *kpt, int ngroup, const int32_t *group, double *s_k);
+
 /* Stochastic Kubo-Bastin double moments.  Replaces compute_moments_stochastic (recursion.f90:979-1234) together with the
  * whole-vector products it is built from: ham_vec_matmul (:913), ham_hoh_vec_matmul (:785), velo_vec_matmul (:587),
  * velo_hoh_vec_matmul (:656):

@@ -47,6 +47,7 @@
 #include "kernels_contour.hpp"
 #include "kernels_assemble.hpp"
 #include "kernels_fan.hpp"
+#include "kernels_bloch.hpp"
 
 using namespace rsrec;
 
@@ -141,6 +142,7 @@ struct rsrec_handle {
     size_t pin_bytes = 0;
     DevBuf d_frags, d_vec[6], d_partial, d_partial2, d_coefA, d_coefB, d_bmats, d_status, d_seed, d_seedcoef, d_mu, d_scal, d_zsqr;
     DevBuf d_fan, d_fan_tab, d_mpair;   // rsrec_chebyshev_pairs_direct: gathered blocks M(18,18,nmom,entry); entry and pair tables; M_ij / M_ji of every pair
+    DevBuf d_bloch_geo, d_bloch_tab;    // rsrec_chebyshev_bloch: positions and k-points of the call; lists, segment offsets and level counts of a batch
     // options
     long opt_batch = 0, opt_kernels = 0, opt_nblk = 0, opt_spmm5 = 2, opt_chain_fold = 1, opt_s5_cap = 0, opt_side = 1, opt_s5_lds = 1, opt_s5_queue = 1, opt_cheb_fused = 1;
     long opt_s5_waves = 8;
@@ -3417,6 +3419,206 @@ extern "C" int rsrec_chebyshev_pairs_direct(rsrec_t* h, int npairs, const int32_
     if (npairs == 0) return RSREC_OK;
     if (h->opt_kernels != 1 && h->s5_built) return run_pairs_direct<LayoutRM, true>(h, npairs, ijpair, lld, a, b, both_ends ? 1 : 0, mu_n, m_pair);
     return run_pairs_direct<LayoutCM, false>(h, npairs, ijpair, lld, a, b, both_ends ? 1 : 0, mu_n, m_pair);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// k-resolved moments from one chain per atom (kernels_bloch.hpp): a sibling of run_pairs_direct -- the same chain, and behind the seed and every
+// H|psi> launch the Bloch sum of the vector just written instead of the gather of a few blocks
+namespace {
+
+struct BlochCall {
+    int nsrc, lld, nk, ngroup;
+    const int32_t *sources, *group;
+    double a, b;
+    const double *cr, *kpt;
+    BlochGeom G;
+    double* s_k;
+};
+
+// The lists of a batch's chains as BlochLists takes them: per chain one segment per group, the group's atoms sorted by (level at which the
+// atom joins the chain's region, atom); atoms the region never reaches are left out.  maxcnt[group][level]: the longest list of the batch.
+struct BlochBatchLists { std::vector<int> list, seg_off, count, tot, maxcnt; };
+void bloch_lists(const rsrec_t* h, const BlochCall& A, int c0, int nb, int nlev, BlochBatchLists& T) {
+    const int kk = h->kk, ng = A.ngroup;
+    T.list.assign((size_t)nb * kk, 0); T.seg_off.assign((size_t)nb * ng, 0); T.count.assign((size_t)nb * ng * nlev, 0);
+    T.tot.assign(nb, 0); T.maxcnt.assign((size_t)ng * nlev, 0);
+    std::vector<int> dist, fill((size_t)ng * nlev);
+    for (int c = 0; c < nb; ++c) {
+        region_levels(h, A.sources[c0 + c] - 1, nlev, dist);
+        int* cnt = T.count.data() + (size_t)c * ng * nlev;
+        for (int j = 0; j < kk; ++j) {
+            const int g = A.group ? A.group[j] : 1;
+            if (g > 0 && dist[j] >= 0) cnt[(size_t)(g - 1) * nlev + dist[j]] += 1;
+        }
+        int off = 0;                                             // (group, level) buckets in order: atoms ascend inside a bucket
+        for (int g = 0; g < ng; ++g) {
+            T.seg_off[(size_t)c * ng + g] = off;
+            for (int l = 0; l < nlev; ++l) { fill[(size_t)g * nlev + l] = off; off += cnt[(size_t)g * nlev + l]; }
+        }
+        T.tot[c] = off;
+        for (int j = 0; j < kk; ++j) {
+            const int g = A.group ? A.group[j] : 1;
+            if (g > 0 && dist[j] >= 0) T.list[(size_t)c * kk + fill[(size_t)(g - 1) * nlev + dist[j]]++] = j;
+        }
+        for (int g = 0; g < ng; ++g) {
+            int run = 0;
+            for (int l = 0; l < nlev; ++l) {
+                run += cnt[(size_t)g * nlev + l];
+                cnt[(size_t)g * nlev + l] = run;
+                T.maxcnt[(size_t)g * nlev + l] = std::max(T.maxcnt[(size_t)g * nlev + l], run);
+            }
+        }
+    }
+}
+
+// L = LayoutCM with the VALU kernels; the matrix-core set takes k_spmm5 on CI vectors, as run_pairs_direct does
+template <class L, bool MFMA>
+int run_bloch(rsrec_t* h, const BlochCall& A) {
+    const bool hoh = h->hoh != 0;
+    const int kk = h->kk, nsrc = A.nsrc, nk = A.nk, ng = A.ngroup;
+    const int napply = 2 * A.lld + 1, nmom = 2 * A.lld + 2;
+    const int mpad = (2 * nk + BLOCH_MROWS - 1) / BLOCH_MROWS * BLOCH_MROWS, mchunk = std::min(mpad, BLOCH_MCHUNK);
+    const size_t nimg = (size_t)nk * ng * nsrc, mstride = (size_t)nmom * BLK;
+    RecursionCall RC = recursion_call(h, MFMA, nsrc, 1, napply);
+    if (MFMA) RC.ci = 1;
+    const size_t velems = RC.velems;
+    // the resident image first, the batch is planned from what is left (see run_chebyshev)
+    h->res_kind = 0; h->spec_res.nop = 0;
+    HIPCK(h, h->d_mu.reserve(nimg * mstride * sizeof(double2)));
+    HIPCK(h, h->d_bloch_geo.reserve((size_t)3 * (kk + nk) * sizeof(double)));
+    // per chain, sized with the work vectors (the buffer recursion_begin reserves for per-chain extras): the phase table and the partials
+    const size_t tab_doubles = (size_t)kk * mpad, part_doubles = (size_t)BLOCH_MAXSPLIT * mchunk * BLD;
+    XFER(recursion_begin(h, RC, MFMA ? (hoh ? 5 : 4) : (hoh ? 4 : 3), MFMA ? 3 : -1, 1, tab_doubles + part_doubles));
+    double* table = h->d_gram.as<double>();
+    double* partial = table + (size_t)RC.B * tab_doubles;
+    double *d_cr = h->d_bloch_geo.as<double>(), *d_kpt = d_cr + (size_t)3 * kk;
+    XFER(xfer_h2d(h, d_cr, A.cr, (size_t)3 * kk * sizeof(double)));
+    XFER(xfer_h2d(h, d_kpt, A.kpt, (size_t)3 * nk * sizeof(double)));
+    const size_t n_list = (size_t)RC.B * kk, n_off = (size_t)RC.B * ng, n_cnt = n_off * RC.nlev;
+    HIPCK(h, h->d_bloch_tab.reserve((n_list + n_off + n_cnt + RC.B) * sizeof(int)));
+    int *d_list = h->d_bloch_tab.as<int>(), *d_off = d_list + n_list, *d_cnt = d_off + n_off, *d_tot = d_cnt + n_cnt;
+    double2* mu = h->d_mu.as<double2>();
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> bloch_ev;
+    BlochBatchLists T;
+    const int nblk = RC.nblk;
+    for (int c0 = 0; c0 < nsrc; c0 += RC.B) {
+        const int nb = std::min(RC.B, nsrc - c0);
+        RecursionBatch bt;
+        XFER(recursion_batch(h, RC, A.sources, nullptr, c0, nb, bt));
+        const ChainView& CV = bt.CV;
+        bloch_lists(h, A, c0, nb, RC.nlev, T);
+        XFER(xfer_h2d(h, d_list, T.list.data(), (size_t)nb * kk * sizeof(int)));
+        XFER(xfer_h2d(h, d_off, T.seg_off.data(), (size_t)nb * ng * sizeof(int)));
+        XFER(xfer_h2d(h, d_cnt, T.count.data(), (size_t)nb * ng * RC.nlev * sizeof(int)));
+        XFER(xfer_h2d(h, d_tot, T.tot.data(), (size_t)nb * sizeof(int)));
+        const BlochLists BL{d_list, d_off, d_cnt, kk, ng, RC.nlev};
+        const int* d_src = h->d_seed.as<int>();                  // (one seed per chain: the batch's 0-based source atoms)
+        XFER(clear_vectors(h, RC, nb));
+        double *p0 = h->d_vec[0].as<double>(), *p1 = h->d_vec[1].as<double>(), *p2 = h->d_vec[2].as<double>();
+        double* tmp = MFMA ? nullptr : h->d_vec[3].as<double>();
+        double* hps = (MFMA && hoh) ? h->d_vec[4].as<double>() : nullptr;   // hoh: h psi of the first pass
+        {
+            hipEvent_t e0 = next_event(h);
+            const int maxtot = *std::max_element(T.tot.begin(), T.tot.end());
+            const unsigned gx = (unsigned)std::min<size_t>(4096, ((size_t)maxtot * (mpad / 2) + 255) / 256);
+            k_bloch_phase<<<dim3(std::max(1u, gx), nb), 256, 0, h->stream>>>(BL, d_tot, d_src, d_cr, d_kpt, nk, mpad, A.G, table);
+            bloch_ev.emplace_back(e0, next_event(h));
+        }
+        // the Bloch sums of the vector of order n (region level `level`) into moment n of the batch's images
+        auto bloch_pass = [&](const double* vec, int level, int n) {
+            hipEvent_t e0 = next_event(h);
+            if (MFMA) k_bloch_diverge<LayoutCI><<<nb, BLOCH_THREADS, 0, h->stream>>>(vec, velems, d_src, h->d_status.as<int>());
+            else k_bloch_diverge<L><<<nb, BLOCH_THREADS, 0, h->stream>>>(vec, velems, d_src, h->d_status.as<int>());
+            for (int g = 0; g < ng; ++g) {
+                if (!MFMA) { k_bloch_valu<L><<<dim3(nk, nb), BLOCH_THREADS, 0, h->stream>>>(BL, g, level, vec, velems, table, mpad, nk, c0, n, nmom, mu); continue; }
+                const int splits = bloch_splits(T.maxcnt[(size_t)g * RC.nlev + level]);
+                for (int m0 = 0; m0 < mpad; m0 += BLOCH_MCHUNK) {
+                    const int mrows = std::min(BLOCH_MCHUNK, mpad - m0), q0 = m0 / 2, nq = std::min(nk - q0, mrows / 2);
+                    k_bloch_mfma<<<dim3(BLOCH_NPB * (mrows / BLOCH_MROWS), splits, nb), BLOCH_WAVES * 64, 0, h->stream>>>(BL, g, level, vec, velems, table, mpad, m0, mrows, partial);
+                    k_bloch_reduce<<<dim3(nq, nb), BLOCH_THREADS, 0, h->stream>>>(BL, g, level, partial, mrows, q0, nk, c0, n, nmom, mu);
+                }
+            }
+            bloch_ev.emplace_back(e0, next_event(h));
+        };
+        if (MFMA) k_seed<LayoutCI><<<nb, 64, 0, h->stream>>>(p0, velems, h->d_seed.as<int>(), h->d_seedcoef.as<double2>(), 1);
+        else k_seed<L><<<nb, 64, 0, h->stream>>>(p0, velems, h->d_seed.as<int>(), h->d_seedcoef.as<double2>(), 1);
+        bloch_pass(p0, 0, 0);
+        const dim3 grid(nblk, nb);
+        for (int t = 1; t <= napply; ++t) {
+            const bool first = (t == 1);
+            const int lv_final = hoh ? 2 * t : t;
+            double *src = first ? p0 : p1, *dst = first ? p1 : p2;
+            if (MFMA) XFER(apply_h(h, RC, bt, t, src, dst, hps, nullptr, 0, cheb_epilogue(first, src, p0, A.a, A.b)));
+            else {
+                hipEvent_t ev0 = next_event(h);
+                ApplyArgs G{};
+                G.partial = h->d_partial.as<double2>(); G.a = A.a; G.b = A.b;     // (the kernels' Gram partials are written and never read)
+                if (!hoh) {
+                    G.in = src; G.cur = src; G.v0 = p0; G.out = dst; G.level = lv_final;
+                    if (first) k_apply<AM_CHEB1, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
+                    else k_apply<AM_CHEBN, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
+                } else {
+                    G.in = src; G.out = tmp; G.level = 2 * t - 1;
+                    k_apply<AM_STORE, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
+                    G.in = tmp; G.v1 = tmp; G.cur = src; G.v0 = p0; G.out = dst; G.level = lv_final;
+                    if (first) k_apply<AM_HOH_CHEB1, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
+                    else k_apply<AM_HOH_CHEBN, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
+                }
+                RC.hop_ev.emplace_back(ev0, next_event(h)); h->n_hop_launch += hoh ? 2 : 1;
+            }
+            bloch_pass(dst, lv_final, t);
+            if (!first) { double* o = p0; p0 = p1; p1 = p2; p2 = o; }
+        }
+        HIPCK(h, hipGetLastError());
+        HIPCK(h, hipStreamSynchronize(h->stream));               // the next batch's uploads reuse the seeds and the lists
+    }
+    if (A.s_k) XFER(xfer_d2h(h, A.s_k, mu, nimg * mstride * sizeof(double2)));
+    const int rc = recursion_end(h, RC, 2, A.lld, false);
+    h->t_rest_ms = 0;                                            // out[5]: the phase table and the Bloch passes alone
+    for (auto& pr : bloch_ev) h->t_rest_ms += ev_ms(pr.first, pr.second);
+    h->d_gram.release();                                         // (tables and partials: not left behind as another call's Gram buffer)
+    if (rc) return rc;
+    h->res_n = (int)nimg;                                        // what an rsrec_chebyshev call of nsrc * ngroup * nk sites leaves
+    return RSREC_OK;
+}
+
+}  // namespace
+
+extern "C" int rsrec_chebyshev_bloch(rsrec_t* h, int nsrc, const int32_t* sources, int lld, double a, double b, const double* cr, const double* cell,
+                                     int nk, const double* kpt, int ngroup, const int32_t* group, double* s_k) {
+    const char* who = "rsrec_chebyshev_bloch";
+    int rc = check_ready(h, who);
+    if (rc) return rc;
+    if (nsrc < 0 || lld < 1 || a == 0.0) return fail(h, RSREC_ERR_ARG, "%s: nsrc < 0, lld < 1 or a == 0", who);
+    if (nk < 1 || nk > RSREC_BLOCH_NK_MAX) return fail(h, RSREC_ERR_ARG, "%s: nk = %d outside 1..%d", who, nk, RSREC_BLOCH_NK_MAX);
+    if (ngroup < 1 || ngroup > RSREC_BLOCH_NGROUP_MAX) return fail(h, RSREC_ERR_ARG, "%s: ngroup = %d outside 1..%d", who, ngroup, RSREC_BLOCH_NGROUP_MAX);
+    if (!cr || !kpt || (nsrc > 0 && !sources)) return fail(h, RSREC_ERR_ARG, "%s: NULL sources, cr or kpt", who);
+    if (!group && ngroup != 1) return fail(h, RSREC_ERR_ARG, "%s: ngroup = %d needs a group array", who, ngroup);
+    if (group)
+        for (int j = 0; j < h->kk; ++j)
+            if (group[j] < 0 || group[j] > ngroup) return fail(h, RSREC_ERR_ARG, "%s: group(%d) = %d outside 0..%d", who, j + 1, group[j], ngroup);
+    XFER(check_seeds(h, who, sources, (size_t)nsrc, 1));
+    if ((size_t)nk * ngroup * (size_t)nsrc > (size_t)INT32_MAX) return fail(h, RSREC_ERR_ARG, "%s: nk * ngroup * nsrc exceeds the index range", who);
+    BlochCall A{nsrc, lld, nk, ngroup, sources, group, a, b, cr, kpt, BlochGeom{}, s_k};
+    A.G.wrap = cell ? 1 : 0;
+    if (cell) {
+        const double* c = cell;                                  // column-major: c[3 col + row]
+        const double cof[9] = {c[4] * c[8] - c[5] * c[7], c[5] * c[6] - c[3] * c[8], c[3] * c[7] - c[4] * c[6],
+                               c[7] * c[2] - c[8] * c[1], c[8] * c[0] - c[6] * c[2], c[6] * c[1] - c[7] * c[0],
+                               c[1] * c[5] - c[2] * c[4], c[2] * c[3] - c[0] * c[5], c[0] * c[4] - c[1] * c[3]};
+        const double det = c[0] * cof[0] + c[1] * cof[1] + c[2] * cof[2];
+        double len = 1.0;
+        for (int v = 0; v < 3; ++v) len *= std::sqrt(c[3 * v] * c[3 * v] + c[3 * v + 1] * c[3 * v + 1] + c[3 * v + 2] * c[3 * v + 2]);
+        if (!std::isfinite(det) || !(std::fabs(det) > 1e-12 * len)) return fail(h, RSREC_ERR_ARG, "%s: singular cell", who);
+        // inv(row i, col j) = cof(j, i) / det with cof[3 j + i] the cofactor of c(i, j) as laid out above
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) { A.G.cell[3 * j + i] = c[3 * j + i]; A.G.inv[3 * j + i] = cof[3 * i + j] / det; }
+    }
+    HIPCK(h, hipSetDevice(h->device));
+    reset_timing(h);
+    if (nsrc == 0) return RSREC_OK;
+    if (h->opt_kernels != 1 && h->s5_built) return run_bloch<LayoutRM, true>(h, A);
+    return run_bloch<LayoutCM, false>(h, A);
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -348,6 +348,44 @@ class Recursion:
         self.mu_n[:, :, :, :4 * n] = mu
         return m_pair
 
+    def chebyshev_bloch(self, sources, kpts, cr, cell=None, group=None, download=True):
+        """k-resolved Chebyshev moments from one chain per source atom (``rsrec_chebyshev_bloch``): the lattice Fourier sum
+        S_i(k, n) = sum_j exp(-i k.(r_j - r_i)) <j|T_n(H~)|i> of the Chebyshev vector started at atom i -- T_n(H~(k)) itself on a periodic
+        one-atom cell.  ``sources``: 1-based atoms; ``kpts`` (3, nk) Cartesian with 2 pi; ``cr`` (3, kk) positions; ``cell`` (3, 3) with the
+        supercell vectors as columns (displacements are then reduced to their minimum image) or None; ``group`` (kk) with values 0..ngroup
+        (0: left out) or None (every atom in group 1).  Returns (18, 18, 2 lld + 2, nk, ngroup, nsrc), or None with ``download=False``;
+        either way the image stays resident as ``chebyshev_recur`` of nk * ngroup * nsrc sites leaves it (image q + nk (g + ngroup s))."""
+        lld = self.control.lld
+        a, b = chebyshev_scaling(self.en.energy_min, self.en.energy_max)
+        src = np.ascontiguousarray(sources, dtype=np.int32).ravel()
+        k = _fc(kpts, np.float64).reshape(3, -1, order="F")
+        cr = _fc(cr, np.float64)
+        if cr.shape != (3, self.lattice.kk):
+            raise ValueError("cr must be (3, kk), got %r" % (cr.shape,))
+        cell = None if cell is None else _fc(cell, np.float64).reshape(3, 3, order="F")
+        ngroup = 1
+        if group is not None:
+            group = np.ascontiguousarray(group, dtype=np.int32).ravel()
+            if group.shape != (self.lattice.kk,):
+                raise ValueError("group must be (kk,), got %r" % (group.shape,))
+            ngroup = max(int(group.max()), 1)
+        nk = k.shape[1]
+        s_k = np.zeros((18, 18, 2 * lld + 2, nk, ngroup, len(src)), np.complex128, order="F") if download else None
+        self._check(self._L.rsrec_chebyshev_bloch(self._h, len(src), _ptr(src), lld, a, b, _ptr(cr), _ptr(cell), nk, _ptr(k), ngroup, _ptr(group), _ptr(s_k)))
+        return s_k
+
+    def bloch_spectral(self, green, sources, kpts, cr, cell=None, group=None):
+        """Orbital-resolved Bloch spectral weights on ``green``'s energy mesh: ``chebyshev_bloch`` without a download, then the LDOS stage
+        on the resident image (``green.chebyshev_ldos``).  Returns ``dosial`` as (nk, ngroup, nsrc, 18, nen); summed over the orbitals it
+        is A(k,E) = -Im Tr G(k,E) / pi of the source's group sum."""
+        self.chebyshev_bloch(sources, kpts, cr, cell=cell, group=group, download=False)
+        nk = np.asarray(kpts).reshape(3, -1, order="F").shape[1]
+        ngroup = 1 if group is None else max(int(np.max(group)), 1)
+        nsrc = np.asarray(sources).size
+        nimg = nk * ngroup * nsrc
+        img = green.chebyshev_ldos(nsites_total=nimg)
+        return img["dosial"].reshape((nk, ngroup, nsrc, 18, -1), order="F")
+
     def zsqr(self):
         """b2_b <- sqrt(b2_b) in place (recursion.f90:1980-2023)."""
         self._check(self._L.rsrec_zsqr(self._h, self.b2_b.shape[2] * self.b2_b.shape[3], _ptr(self.b2_b)))
