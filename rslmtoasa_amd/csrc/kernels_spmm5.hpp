@@ -47,6 +47,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <type_traits>
+#include <utility>
 #include <vector>
 #include "kernels_valu.hpp"
 #include "kernels_mfma.hpp"
@@ -59,6 +60,9 @@ namespace rsrec {
 #endif
 #ifndef RSREC_S5_PRIO
 #define RSREC_S5_PRIO 0
+#endif
+#ifndef RSREC_S5_GRAM_STRIP_LOADS
+#define RSREC_S5_GRAM_STRIP_LOADS 0   // TIMING PROBE: 1 = the Gram epilogue loads the strip operands of every tile (five rounds of two tiles, result stores behind it)
 #endif
 #ifndef S5_WG_GROUPS
 #define S5_WG_GROUPS 4   // groups of 8 atoms per workgroup (x 2 spin waves each): 4 -> 512 threads
@@ -425,6 +429,22 @@ __device__ __forceinline__ void s5_mfma(S5Acc& acc, const S5Single& o) {
 }
 
 template <int N> using S5C = std::integral_constant<int, N>;
+// f(S5C<T0>, S5C<0>), f(S5C<T0 + 1>, S5C<1>), ...: a tile loop whose index is a constant expression in the body
+template <int T0, int... I, class F>
+__device__ __forceinline__ void s5_each_tile(std::integer_sequence<int, I...>, F&& f) { (f(S5C<T0 + I>{}, S5C<I>{}), ...); }
+// v of lane SRC (0..15) of the caller's row of 16 lanes, i.e. of lane SRC + 16 (lane >> 4): a DPP row broadcast -- no LDS round trip, no
+// address register; every lane of the wave must be active
+template <int SRC>
+__device__ __forceinline__ s5_d2 s5_row_bcast(s5_d2 v) {
+    s5_d2 r;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {       // (bound_ctrl: no previous value of the destination to keep, so none is set up)
+        const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v[c]), 0x150 + SRC /*row_newbcast:SRC*/, 0xf, 0xf, true);
+        const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v[c]), 0x150 + SRC, 0xf, 0xf, true);
+        r[c] = __hiloint2double(hi, lo);
+    }
+    return r;
+}
 #define S5_GLOBAL __attribute__((address_space(1)))
 #define S5_CONST __attribute__((address_space(4)))
 #define S5_LDS __attribute__((address_space(3)))
@@ -1023,10 +1043,72 @@ __global__ __launch_bounds__(NSP == 3 ? 768 : S5_WG_GROUPS * 128) void k_spmm5(S
         if (kpart) continue;                                // (probe: one part stores)
 #endif
 
+        // 16x16x4 result register j, lane (l15, l4): real-form row l4 + 4 j of spin sig = (part j & 1, m = l4 + 4 (j >> 1)), column l15:
+        // registers (2 p, 2 p + 1) are the real and imaginary part of element (m = 4 p + l4, c) -> one 16-byte store in the CI
+        // layout; the 4x4x4 result: row 16 + l4 -> l4 = 0: re, 1: im of m = 8
+        // Epilogue operands first, for several tiles at once (the three operand sets of the stream are dead: ~110 registers are free):
+        // two memory round trips per group instead of one per tile.  Padding atoms read the zero block; only their stores are skipped.
+        // (the Gram variant: the lane's coordinates once more from an instruction the compiler cannot move, so that no lane constant of
+        // `finish` is held over the stream loop either)
+        int fl15 = l15, fl4 = l4;
+        if constexpr (GRAM) {
+            unsigned fl;
+            asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(fl));
+            fl15 = (int)fl & 15; fl4 = (int)fl >> 4;
+        }
+        const int ekind = GRAM ? 0 : epi.kind;              // (the Gram variant is launched without an element-wise epilogue)
+        auto finish = [&](auto t0c, auto t1c) {
+            constexpr int T0 = decltype(t0c)::value, T1 = decltype(t1c)::value, NT = T1 - T0;
+            size_t eo[NT];
+#pragma unroll
+            for (int i = 0; i < NT; ++i) { const int t = T0 + i; eo[i] = (size_t)BLD * ((t < 8) ? vatom[t] : my_rem_atom) + 324 * sig + ((t < 8) ? 2 * fl15 : 32 + 2 * (fl15 & 1)); }
+            s5_d2 ec[NT][2], ez[NT][2];
+            double ecr[NT], ezr[NT];
+            if (ekind) {
+                const double* cb = epi.cur + vo;
+#pragma unroll
+                for (int i = 0; i < NT; ++i) {
+#pragma unroll
+                    for (int p = 0; p < 2; ++p) ec[i][p] = *reinterpret_cast<const s5_d2*>(cb + eo[i] + 36 * (4 * p + fl4));
+                    ecr[i] = cb[eo[i] + 288 + (fl4 & 1)];
+                }
+                if (ekind == 2) {
+                    const double* zb = epi.old + vo;
+#pragma unroll
+                    for (int i = 0; i < NT; ++i) {
+#pragma unroll
+                        for (int p = 0; p < 2; ++p) ez[i][p] = *reinterpret_cast<const s5_d2*>(zb + eo[i] + 36 * (4 * p + fl4));
+                        ezr[i] = zb[eo[i] + 288 + (fl4 & 1)];
+                    }
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < NT; ++i) {
+                const int t = T0 + i;
+                const int a = (t < 8) ? vatom[t] : my_rem_atom;
+                double* ob = out + eo[i];
+#pragma unroll
+                for (int p = 0; p < 2; ++p) {
+                    s5_d2 v; v[0] = acc.m[t][2 * p]; v[1] = acc.m[t][2 * p + 1];
+                    if (ekind) {
+                        v[0] = (v[0] - epi.b * ec[i][p][0]) / epi.a; v[1] = (v[1] - epi.b * ec[i][p][1]) / epi.a;
+                        if (ekind == 2) { v[0] = v[0] * 2.0 - ez[i][p][0]; v[1] = v[1] * 2.0 - ez[i][p][1]; }
+                    }
+                    if (a != zero_block) *reinterpret_cast<s5_d2*>(ob + 36 * (4 * p + fl4)) = v;
+                }
+                double r = acc.r[t];
+                if (ekind) {
+                    r = (r - epi.b * ecr[i]) / epi.a;
+                    if (ekind == 2) r = r * 2.0 - ezr[i];
+                }
+                if (a != zero_block && fl4 < 2) ob[288 + fl4] = r;
+            }
+        };
         // The Gram epilogue (see S5Gram): result register j of tile t < 8 is the B operand of k-step j of a 16x16x4 whose A operand is the
         // own-atom element of u at the same (m, c = l15) -- its part matching the row for Re G, (-Ui, Ur) for Im G; the remainder register
         // (re, im of m = 8, two padding rows) is a fifth k-step.  Rows 16, 17 of G and the corner on the vector pipe from the same registers.
         // Tiles in order, a few at a time: their operands live in the registers of the dead operand sets.
+        bool stored = false;                                // the Gram epilogue issued the group's result stores (`finish`) itself
         if constexpr (GRAM) if (fold) {
             // the lane's coordinates again, from an instruction the compiler cannot move: derived from the kernel's own l15 / l4 every lane
             // constant of this block was hoisted over the stream loop, which has no register to spare (the allocator then spilled)
@@ -1041,26 +1123,45 @@ __global__ __launch_bounds__(NSP == 3 ? 768 : S5_WG_GROUPS * 128) void k_spmm5(S
                 cr = l4 == 0 ? u[0] : (l4 == 1 ? u[1] : 0.0);
                 ci = l4 == 0 ? -u[1] : (l4 == 1 ? u[0] : 0.0);
             };
+            // The strip operands of a tile -- columns 16, 17 of its own-atom block at the lane's rows (4 p + l4 for p = 0, 1, and row 8),
+            // the same in the 16 lanes of a row -- are what the remainder tile holds for all eight atoms: its lane (l15, l4) has them of
+            // atom l15 >> 1 (the zero block for a padding atom, as vatom[t] is).  They are loaded once, for t = 8, kept, and tile t < 8
+            // takes its own from lane 2 t of the row, one (p, e) pair at a time: 33 loads per epilogue instead of 81, 12 operand
+            // registers per tile instead of 36, and with that four tiles per round of loads -- two round trips instead of five.
+            constexpr bool STRIP_LOADS = RSREC_S5_GRAM_STRIP_LOADS != 0;
+            auto strip_loads = [&](s5_d2 (&gs)[3][2], const double* ab) {
+#pragma unroll
+                for (int p = 0; p < 3; ++p)
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) gs[p][e] = *reinterpret_cast<const s5_d2*>(ab + 36 * (p < 2 ? 4 * p + l4 : 8) + 32 + 2 * e);
+            };
+            s5_d2 gs8[3][2];
+            if constexpr (!STRIP_LOADS) strip_loads(gs8, ub + (size_t)BLD * my_rem_atom + 324 * sig);
             auto gram_tiles = [&](auto t0c, auto t1c) {
                 constexpr int T0 = decltype(t0c)::value, T1 = decltype(t1c)::value, NT = T1 - T0;
-                s5_d2 gu[NT][3], gs[NT][3][2];
+                s5_d2 gu[NT][3], gs[STRIP_LOADS ? NT : 1][3][2];
 #pragma unroll
                 for (int i = 0; i < NT; ++i) {
                     const int t = T0 + i;
                     const double* ab = ub + (size_t)BLD * ((t < 8) ? vatom[t] : my_rem_atom) + 324 * sig;
 #pragma unroll
-                    for (int p = 0; p < 3; ++p) {
-                        const int row = 36 * (p < 2 ? 4 * p + l4 : 8);
-                        if (t < 8) gu[i][p] = *reinterpret_cast<const s5_d2*>(ab + row + 2 * l15);
-#pragma unroll
-                        for (int e = 0; e < 2; ++e) gs[i][p][e] = *reinterpret_cast<const s5_d2*>(ab + row + 32 + 2 * e);
-                    }
+                    for (int p = 0; p < 3; ++p)
+                        if (t < 8) gu[i][p] = *reinterpret_cast<const s5_d2*>(ab + 36 * (p < 2 ? 4 * p + l4 : 8) + 2 * l15);
+                    if constexpr (STRIP_LOADS) strip_loads(gs[i], ab);
                 }
-#pragma unroll
-                for (int i = 0; i < NT; ++i) {
-                    const int t = T0 + i;
+                // the result stores of the group between the first round's loads and their use: they wait for nothing, and the next group's
+                // first operands then do not queue behind them (measured: DESIGN section 3)
+                if constexpr (!STRIP_LOADS && T0 == 0) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    finish(S5C<0>{}, S5C<5>{});
+                    finish(S5C<5>{}, S5C<9>{});
+                    stored = true;
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                s5_each_tile<T0>(std::make_integer_sequence<int, NT>{}, [&](auto tc, auto ic) {
+                    constexpr int t = decltype(tc)::value, i = decltype(ic)::value;
                     const double x8 = acc.r[t];
-                    if (t < 8) {
+                    if constexpr (t < 8) {
 #pragma unroll
                         for (int p = 0; p < 2; ++p) {
                             gre = __builtin_amdgcn_mfma_f64_16x16x4f64(gu[i][p][0], acc.m[t][2 * p], gre, 0, 0, 0);
@@ -1073,32 +1174,50 @@ __global__ __launch_bounds__(NSP == 3 ? 768 : S5_WG_GROUPS * 128) void k_spmm5(S
                         gre = __builtin_amdgcn_mfma_f64_16x16x4f64(cr, x8, gre, 0, 0, 0);
                         gim = __builtin_amdgcn_mfma_f64_16x16x4f64(ci, x8, gim, 0, 0, 0);
                     }
+                    auto strip = [&](int p, int e) -> s5_d2 {
+                        if constexpr (STRIP_LOADS) return gs[i][p][e];
+                        else if constexpr (t < 8) return s5_row_bcast<2 * t>(gs8[p][e]);
+                        else return gs8[p][e];
+                    };
                     double (&are)[2] = (t < 8) ? sre : kre;
                     double (&aim)[2] = (t < 8) ? sim : kim;
 #pragma unroll
                     for (int e = 0; e < 2; ++e) {
 #pragma unroll
                         for (int p = 0; p < 2; ++p) {
-                            const double ur = gs[i][p][e][0], ui = gs[i][p][e][1], tr = acc.m[t][2 * p], ti = acc.m[t][2 * p + 1];
+                            const s5_d2 u = strip(p, e);
+                            const double ur = u[0], ui = u[1], tr = acc.m[t][2 * p], ti = acc.m[t][2 * p + 1];
                             are[e] = fma(ur, tr, are[e]); are[e] = fma(ui, ti, are[e]);
                             aim[e] = fma(ur, ti, aim[e]); aim[e] = fma(-ui, tr, aim[e]);
                         }
                         double cr, ci;
-                        rem_coef(gs[i][2][e], cr, ci);
+                        rem_coef(strip(2, e), cr, ci);
                         are[e] = fma(cr, x8, are[e]);
                         aim[e] = fma(ci, x8, aim[e]);
                     }
+                });
+                // (the strip rows and the corner are formed HERE: left alone, their fma chains sink to their use in the sums below and take
+                // their operands with them -- the kept strips alone are 24 registers over the shuffles of the sums: the allocator spilled)
+                if constexpr (!STRIP_LOADS) {
+                    if constexpr (T0 < 8) asm volatile("" : "+v"(sre[0]), "+v"(sre[1]), "+v"(sim[0]), "+v"(sim[1]));
+                    if constexpr (T1 == 9) asm volatile("" : "+v"(kre[0]), "+v"(kre[1]), "+v"(kim[0]), "+v"(kim[1]));
                 }
             };
-            gram_tiles(S5C<0>{}, S5C<2>{});
-            __builtin_amdgcn_sched_barrier(0);
-            gram_tiles(S5C<2>{}, S5C<4>{});
-            __builtin_amdgcn_sched_barrier(0);
-            gram_tiles(S5C<4>{}, S5C<6>{});
-            __builtin_amdgcn_sched_barrier(0);
-            gram_tiles(S5C<6>{}, S5C<8>{});
-            __builtin_amdgcn_sched_barrier(0);
-            gram_tiles(S5C<8>{}, S5C<9>{});
+            if constexpr (STRIP_LOADS) {
+                gram_tiles(S5C<0>{}, S5C<2>{});
+                __builtin_amdgcn_sched_barrier(0);
+                gram_tiles(S5C<2>{}, S5C<4>{});
+                __builtin_amdgcn_sched_barrier(0);
+                gram_tiles(S5C<4>{}, S5C<6>{});
+                __builtin_amdgcn_sched_barrier(0);
+                gram_tiles(S5C<6>{}, S5C<8>{});
+                __builtin_amdgcn_sched_barrier(0);
+                gram_tiles(S5C<8>{}, S5C<9>{});
+            } else {
+                gram_tiles(S5C<0>{}, S5C<4>{});
+                __builtin_amdgcn_sched_barrier(0);
+                gram_tiles(S5C<4>{}, S5C<9>{});         // (the corner has no loads of its own)
+            }
             __builtin_amdgcn_sched_barrier(0);
             // the four lanes of a column (l4 = 0..3) in that order; the corner then over its eight atoms (l15 >> 1) in that order
             auto sum_l4 = [&](double v) {
@@ -1129,61 +1248,10 @@ __global__ __launch_bounds__(NSP == 3 ? 768 : S5_WG_GROUPS * 128) void k_spmm5(S
                 if (lane < 2) *reinterpret_cast<s5_d2*>(gp + 576 + 2 * (2 * e + lane)) = v;
             }
         }
-        // 16x16x4 result register j, lane (l15, l4): real-form row l4 + 4 j of spin sig = (part j & 1, m = l4 + 4 (j >> 1)), column l15:
-        // registers (2 p, 2 p + 1) are the real and imaginary part of element (m = 4 p + l4, c) -> one 16-byte store in the CI
-        // layout; the 4x4x4 result: row 16 + l4 -> l4 = 0: re, 1: im of m = 8
-        // Epilogue operands first, for several tiles at once (the three operand sets of the stream are dead: ~110 registers are free):
-        // two memory round trips per group instead of one per tile.  Padding atoms read the zero block; only their stores are skipped.
-        const int ekind = GRAM ? 0 : epi.kind;              // (the Gram variant is launched without an element-wise epilogue)
-        auto finish = [&](auto t0c, auto t1c) {
-            constexpr int T0 = decltype(t0c)::value, T1 = decltype(t1c)::value, NT = T1 - T0;
-            size_t eo[NT];
-#pragma unroll
-            for (int i = 0; i < NT; ++i) { const int t = T0 + i; eo[i] = (size_t)BLD * ((t < 8) ? vatom[t] : my_rem_atom) + 324 * sig + ((t < 8) ? 2 * l15 : 32 + 2 * (l15 & 1)); }
-            s5_d2 ec[NT][2], ez[NT][2];
-            double ecr[NT], ezr[NT];
-            if (ekind) {
-                const double* cb = epi.cur + vo;
-#pragma unroll
-                for (int i = 0; i < NT; ++i) {
-#pragma unroll
-                    for (int p = 0; p < 2; ++p) ec[i][p] = *reinterpret_cast<const s5_d2*>(cb + eo[i] + 36 * (4 * p + l4));
-                    ecr[i] = cb[eo[i] + 288 + (l4 & 1)];
-                }
-                if (ekind == 2) {
-                    const double* zb = epi.old + vo;
-#pragma unroll
-                    for (int i = 0; i < NT; ++i) {
-#pragma unroll
-                        for (int p = 0; p < 2; ++p) ez[i][p] = *reinterpret_cast<const s5_d2*>(zb + eo[i] + 36 * (4 * p + l4));
-                        ezr[i] = zb[eo[i] + 288 + (l4 & 1)];
-                    }
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < NT; ++i) {
-                const int t = T0 + i;
-                const int a = (t < 8) ? vatom[t] : my_rem_atom;
-                double* ob = out + eo[i];
-#pragma unroll
-                for (int p = 0; p < 2; ++p) {
-                    s5_d2 v; v[0] = acc.m[t][2 * p]; v[1] = acc.m[t][2 * p + 1];
-                    if (ekind) {
-                        v[0] = (v[0] - epi.b * ec[i][p][0]) / epi.a; v[1] = (v[1] - epi.b * ec[i][p][1]) / epi.a;
-                        if (ekind == 2) { v[0] = v[0] * 2.0 - ez[i][p][0]; v[1] = v[1] * 2.0 - ez[i][p][1]; }
-                    }
-                    if (a != zero_block) *reinterpret_cast<s5_d2*>(ob + 36 * (4 * p + l4)) = v;
-                }
-                double r = acc.r[t];
-                if (ekind) {
-                    r = (r - epi.b * ecr[i]) / epi.a;
-                    if (ekind == 2) r = r * 2.0 - ezr[i];
-                }
-                if (a != zero_block && l4 < 2) ob[288 + l4] = r;
-            }
-        };
-        finish(S5C<0>{}, S5C<5>{});
-        finish(S5C<5>{}, S5C<9>{});
+        if (!stored) {
+            finish(S5C<0>{}, S5C<5>{});
+            finish(S5C<5>{}, S5C<9>{});
+        }
     }
     }   // chains of this workgroup
 }
