@@ -21,6 +21,12 @@
 !                                   field) pair is one more set of the same integrand call and one more pass of the tail; the files of
 !                                   further field f carry 'E<f>_' before whatever the set is called otherwise (Ey_fort.123,
 !                                   Ey_cond_total.out, Ey_spin_cond_total.out, Ey_<symbol>_cond.out).
+!                                   RSREC_KUBO_OPTICAL=<nw>: after the DC tensor, the optical conductivity sigma(omega_k), omega_k = k edel,
+!                                   k = 1 .. nw, at energy%fermi and T = 0 from the orbital diagonals of mu_nm_stochastic
+!                                   (rsrec_kubo_optical, region conductivity-optical-gpu) -> optical_cond.out: omega_k, then Re and Im of
+!                                   the sum over orbitals and vectors divided by loop_over, in cond_total.out's format.  Unset: nothing
+!                                   of this runs.  RSREC_KUBO_OPTICAL_MOMENTS=<file> beside it: the diagonals that call was given,
+!                                   complex (18, cond_ll, cond_ll, loop_over), as a stream of raw bytes (for checking the file).
 ! Errors of the library become g_logger%fatal, the reference's error behaviour on this path.
 !------------------------------------------------------------------------------
 module conductivity_gpu_mod
@@ -74,7 +80,7 @@ contains
 
    subroutine gpu_calculate_conductivity_tensor(this)
       class(conductivity_gpu), intent(inout) :: this
-      integer :: loop_over, nen, nresp, j
+      integer :: loop_over, nen, nresp, j, nw_opt
       integer(c_int) :: rc
       type(c_ptr) :: ctx
       complex(rp), dimension(:, :, :), allocatable, target :: integ           ! (18, nen, loop_over): integrand_at(l2, l2, :, v), factor applied;
@@ -155,8 +161,72 @@ contains
          end if
       end do
 
+      ! RSREC_KUBO_OPTICAL=<nw>: sigma(omega) of the namelist's pair
+      nw_opt = optical_frequencies()
+      if (nw_opt > 0) call optical_tail(this, ctx, ene, loop_over, nen, nw_opt)
+
       deallocate (integ, wscale, ene)
    end subroutine gpu_calculate_conductivity_tensor
+
+   !> RSREC_KUBO_OPTICAL as a number of frequencies; 0: unset or empty
+   function optical_frequencies() result(nw)
+      integer :: nw
+      character(len=16) :: val
+      integer :: n, stat, ios
+      nw = 0
+      call get_environment_variable('RSREC_KUBO_OPTICAL', val, n, stat)
+      if (stat > 0 .or. n == 0) return
+      ios = 1
+      if (stat == 0) read (val, *, iostat=ios) nw
+      if (ios /= 0 .or. nw < 1) call g_logger%fatal('conductivity_gpu: RSREC_KUBO_OPTICAL must be a number of frequencies >= 1', __FILE__, __LINE__)
+   end function optical_frequencies
+
+   !> sigma(omega_k), k = 1 .. nw, at energy%fermi from the orbital diagonals of mu_nm_stochastic -> optical_cond.out
+   subroutine optical_tail(this, ctx, ene, loop_over, nen, nw)
+      class(conductivity_gpu), intent(inout) :: this
+      type(c_ptr), intent(in) :: ctx
+      real(rp), dimension(:), intent(in), target :: ene
+      integer, intent(in) :: loop_over, nen, nw
+      complex(rp), dimension(:, :, :, :), allocatable, target :: dg, opt       ! (18, cond_ll, cond_ll, loop_over), (18, nw, 1, loop_over)
+      real(rp), target :: fermi(1)
+      complex(rp) :: tot
+      integer :: l, n, m, v, k, ll, nchar, stat, u
+      integer(c_int) :: rc
+      character(len=sl) :: fname
+
+      ll = this%control%cond_ll
+      allocate (dg(18, ll, ll, loop_over), opt(18, nw, 1, loop_over))
+      do v = 1, loop_over
+         do m = 1, ll
+            do n = 1, ll
+               do l = 1, 18
+                  dg(l, n, m, v) = this%recursion%mu_nm_stochastic(l, l, n, m, v)
+               end do
+            end do
+         end do
+      end do
+      call get_environment_variable('RSREC_KUBO_OPTICAL_MOMENTS', fname, nchar, stat)
+      if (stat == 0 .and. nchar > 0) then
+         open (newunit=u, file=trim(fname), access='stream', form='unformatted', status='replace', action='write')
+         write (u) dg
+         close (u)
+      end if
+      fermi(1) = this%en%fermi
+      call g_timer%start('conductivity-optical-gpu')
+      rc = rsrec_kubo_optical(ctx, int(loop_over, c_int), int(ll, c_int), c_loc(dg), int(nen, c_int), c_loc(ene), &
+                              real(this%en%energy_min, c_double), real(this%en%energy_max, c_double), int(nw, c_int), 1_c_int, c_loc(fermi), &
+                              0.0_c_double, c_loc(opt))
+      if (rc /= 0) call g_logger%fatal('conductivity_gpu%optical_tail: '//rsrec_error_string(ctx), __FILE__, __LINE__)
+      call g_timer%stop('conductivity-optical-gpu')
+
+      open (unit=34, file='optical_cond.out', status='replace', action='write')
+      do k = 1, nw
+         tot = sum(opt(:, k, 1, :))
+         write (34, '(3es16.6)') k*(ene(2) - ene(1)), real(tot)/real(loop_over), aimag(tot)/real(loop_over)
+      end do
+      close (34)
+      deallocate (dg, opt)
+   end subroutine optical_tail
 
    !> The tail on the device: series and sigma (38, nen, nsets) from one rsrec_kubo_conductivity call -- rows 1-2 Re / Im of the total,
    !> 3-20 / 21-38 Re / Im of the orbitals; set 1 the sum over the vectors, set 1 + ntype that type alone ('per_type') -- then the

@@ -230,6 +230,18 @@ module rsrec_binding
          integer(c_int) :: rc
       end function
 
+      ! the optical conductivity from the orbital-diagonal moments (NULL: the resident ones) on a uniform mesh: opt complex (18, nw, nfermi, nset),
+      ! opt(l, k, f, s) at omega_k = k (ene(2) - ene(1)) and Fermi level fermi(f); J(E, E') is never formed (kernels_optical.hpp)
+      function rsrec_kubo_optical(handle, nset, cond_ll, mu_diag, nen, ene, energy_min, energy_max, nw, nfermi, fermi, temperature, opt) &
+         bind(C, name='rsrec_kubo_optical') result(rc)
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: handle
+         integer(c_int), value :: nset, cond_ll, nen, nw, nfermi
+         type(c_ptr), value :: mu_diag, ene, fermi, opt
+         real(c_double), value :: energy_min, energy_max, temperature
+         integer(c_int) :: rc
+      end function
+
       ! exchange couplings of the rank's pairs: intersite g + Jij / Dij / Iij integrands + Simpson integrals (exchange.f90:1032-1615)
       function rsrec_exchange(handle, kind, npairs, same, lld, nen, ene, nv1, fermi, sym_term, energy_min, energy_max, a_inf, b_inf, &
                               coef_a, coef_b, dpar, pair_offset, npairs_total, xc, so, fo, parts, jcum, integrand) &

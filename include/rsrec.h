@@ -451,6 +451,32 @@ int rsrec_kubo_integrand_diag(rsrec_t *h, int nvec, int cond_ll, const double *m
 int rsrec_kubo_conductivity(rsrec_t *h, int nvec, int per_vector, int nen, int nv1, const double *ene, double energy_min, double energy_max,
                             double temperature, const double *integrand, double *sigma, double *series);
 
+/* The frequency-dependent (optical) conductivity from the same orbital-diagonal moments (kernels_optical.hpp).  The moments are the
+ * Chebyshev double expansion of the current-matrix-element density j(x, y) = <r| delta(y - H~) v_a delta(x - H~) v_b |r>; on the scaled
+ * axis x_i = (ene_i - b) / a of rsrec_kubo_integrand (i = 0 .. nen - 1), which must be uniform with step Delta = ene(2) - ene(1) > 0
+ * (|ene_i - ene_0 - i Delta| <= 1e-9 Delta),
+ *   D(i,n)       = 2 w_n T_{n-1}(x_i) / (pi sqrt(1 - x_i^2)),  n = 1 .. cond_ll;  w_n = g_n weights_n, the table of rsrec_kubo_integrand
+ *                  (Lorentz kernel, lambda = 6, weights_1 = 0.5); T from the three-term recurrence; a row with |x_i| >= 1 is zero
+ *   J_{l,s}(i,j) = sum_{n,m} D(i,n) mu_diag(l,n,m,s) D(j,m)
+ *   opt(l,k,f,s) = (pi / a^2) (1/k) sum_{i=0}^{nen-1-k} [F_f(x_i) - F_f(x_{i+k})] J_{l,s}(i, i+k),      omega_k = k Delta, k = 1 .. nw
+ *   F_f(x)       = 1 / (exp((x - x_F,f) / kT) + 1),  x_F,f = (fermi_f - b) / a,  kT = 0.633362019e-5 temperature + 1e-15 on the scaled axis
+ *                  (the convention of rsrec_kubo_conductivity; no T = 0 special case)
+ * Complex throughout: no real part is taken, and e^2 hbar / Omega and the sign convention of the velocity operators stay with the caller.
+ * The rectangle rule on the mesh: h / (k h) = 1 / k.  J is never formed in memory: two real x complex GEMMs per (orbital, set) on the
+ * FP64 matrix cores, the second fused with the frequency sum over the tiles i < j <= i + nw.
+ *   mu_diag : complex (18,cond_ll,cond_ll,nset), host or device (detected); NULL = the moments rsrec_kubo_moments_diag / _multi / _tensor left
+ *             resident (nset = all their sets), with the rules and the error of rsrec_kubo_integrand_diag.  1 <= cond_ll <= RSREC_COND_LL_MAX.
+ *   ene     : real (nen) host, nen >= 2;   fermi : real (nfermi) host, 1 <= nfermi <= RSREC_OPT_NFERMI_MAX;   1 <= nw <= nen - 1
+ *   opt     : complex (18,nw,nfermi,nset) out, host or device
+ * Needs no lattice and no Hamiltonian.  Resident diagonal moments survive the call.  The bits of opt(:,:,f,s) depend only on that set,
+ * that Fermi level and the mesh: not on the other sets or levels of the call, their order, or earlier calls (fixed summation order, no
+ * atomics).  Errors: RSREC_ERR_ARG with a message, the handle staying usable, for a mesh that is not uniform or does not increase,
+ * nen < 2, nw or nfermi out of range, an empty or non-finite window, a negative or non-finite temperature, a non-finite Fermi level, a NULL
+ * ene, fermi or opt.  rsrec_get_timing: out[0] device ms of the call, out[5] ms in its kernels. */
+#define RSREC_OPT_NFERMI_MAX 16
+int rsrec_kubo_optical(rsrec_t *h, int nset, int cond_ll, const double *mu_diag, int nen, const double *ene, double energy_min, double energy_max,
+                       int nw, int nfermi, const double *fermi, double temperature, double *opt);
+
 /* Exchange couplings of the pairs of one rank: green%calculate_intersite_gf / _twoindex (green.f90:386-469) and the integrands and
  * Fermi-weighted Simpson integrals of exchange%calculate_exchange / _twoindex (exchange.f90:1032-1615), without the intersite arrays
  * (kernels_exchange.hpp: g0 of a pair's chains stays in LDS; every quantity is a trace Tr(D_i A D_j B) of the diagonal d_matrix).

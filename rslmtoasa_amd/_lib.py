@@ -57,6 +57,8 @@ _SIGNATURES = {
     "rsrec_kubo_integrand": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_void_p]),
     "rsrec_kubo_integrand_diag": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_void_p]),
     "rsrec_kubo_conductivity": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_double] + [C.c_void_p] * 3),
+    "rsrec_kubo_optical": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p,
+                                     C.c_double, C.c_void_p]),
     "rsrec_apply_operator": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double]),
     "rsrec_zsqr": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "rsrec_chebyshev_green": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),

@@ -4,6 +4,8 @@ calculate_gamma_nm + the loops of calculate_conductivity_tensor (:158-281) becom
 the (nE, cond_ll, cond_ll) array gamma_nm.  The tail of calculate_conductivity_tensor (:283-372) -- the sums over the vectors and the
 orbitals and the Fermi-weighted Simpson integral of each of the 38 series up to every energy of the mesh -- is a second call,
 ``rsrec_kubo_conductivity`` (``tensor``).  Only the formatting of the output files stays with the caller.
+``optical`` goes beyond the reference, which stops at DC: the frequency-dependent conductivity sigma(omega) from the same
+orbital-diagonal moments (``rsrec_kubo_optical``).
 """
 import ctypes as C
 
@@ -115,8 +117,62 @@ class Conductivity:
         del keep
         return (sigma, ser) if series else sigma
 
+    def optical(self, mu, ene, fermi, nw=None, temperature=0.0):
+        """The optical conductivity sigma(omega) from the orbital-diagonal moments (``rsrec_kubo_optical``, include/rsrec.h has the
+        formula): complex (18, nw, nfermi, nset), Fortran order; opt[l, k - 1, f, s] belongs to omega_k = k (ene[1] - ene[0]).
+
+        ``mu``: the orbital diagonals, complex (18, cond_ll, cond_ll[, nset]) -- a numpy array or a contiguous complex128 torch tensor
+        on the GPU (Fortran order: shape reversed), read in place -- or ``None``: the moments ``compute_moments_stochastic(diag=True)``
+        / ``_multi`` / ``_tensor`` left resident on the device, all their sets.  A full (18, 18, cond_ll, cond_ll[, nvec]) array has
+        its diagonals taken on the host.  The one shape that is both, (18, 18, 18, 18), means the full moments, as in ``integrand``.
+        ``ene``: a uniform increasing mesh.  ``fermi``: one Fermi level or a sequence of up to 16, in the units of ``ene``.
+        ``nw``: frequencies omega_1 .. omega_nw; left at None all nen - 1 the mesh holds.
+        ``temperature``: in K on the unscaled axis; the weights are formed on the scaled one, so the library gets T / a as in ``tensor``."""
+        ene = np.ascontiguousarray(ene, dtype=np.float64).ravel()
+        fermi = np.ascontiguousarray(np.atleast_1d(fermi), dtype=np.float64).ravel()
+        rec = self.recursion
+        if nw is None:
+            nw = ene.size - 1
+        keep = None
+        if mu is None:
+            cond_ll, nset = getattr(rec, "mu_diag_resident", None) or (1, 1)      # (nothing asked for yet: the library refuses with its message)
+            ptr = None
+        else:
+            if hasattr(mu, "data_ptr"):                    # torch tensor: read where it lies (GPU memory is not copied)
+                if mu.element_size() != 16 or not mu.is_complex() or not mu.is_contiguous():
+                    raise ValueError("a mu tensor must be contiguous complex128 (the Fortran array seen from C: shape reversed)")
+                shape = tuple(mu.shape)[::-1]
+                if len(shape) in (4, 5) and shape[:2] == (18, 18) and shape[2] == shape[3]:
+                    mu = mu.cpu().numpy().transpose(tuple(range(len(shape)))[::-1])          # (the full moments: diagonals on the host below)
+                elif mu.is_cuda:
+                    import torch
+                    torch.cuda.synchronize(mu.device)      # the library reads it on its own stream
+            if not hasattr(mu, "data_ptr"):
+                mu = np.asarray(mu)
+                if mu.ndim in (4, 5) and mu.shape[:2] == (18, 18) and mu.shape[2] == mu.shape[3]:
+                    idx = np.arange(18)
+                    mu = mu[idx, idx]
+                keep = np.asfortranarray(mu, dtype=np.complex128)
+                shape, ptr = keep.shape, keep.ctypes.data_as(C.c_void_p)
+            else:
+                keep, ptr = mu, C.c_void_p(mu.data_ptr())
+            if len(shape) == 3:
+                shape = shape + (1,)
+            if len(shape) != 4 or shape[0] != 18 or shape[1] != shape[2]:
+                raise ValueError("mu must be (18, cond_ll, cond_ll[, nset]) or (18, 18, cond_ll, cond_ll[, nvec]), got %s" % (shape,))
+            cond_ll, nset = shape[1], shape[3]
+        a = (float(self.en.energy_max) - float(self.en.energy_min)) / float(np.float32(2.0) - np.float32(0.3))
+        t_scaled = float(temperature) / a if np.isfinite(a) and a > 0 else float(temperature)      # (an empty window: the library refuses it)
+        out = np.zeros((18, max(int(nw), 0), fermi.size, nset), np.complex128, order="F")
+        rec._check(rec._L.rsrec_kubo_optical(rec._h, int(nset), int(cond_ll), ptr, ene.size, ene.ctypes.data_as(C.c_void_p),
+                                             float(self.en.energy_min), float(self.en.energy_max), int(nw), fermi.size,
+                                             fermi.ctypes.data_as(C.c_void_p), t_scaled, out.ctypes.data_as(C.c_void_p)))
+        del keep
+        return out
+
     def timing(self):
         """(device ms of the last call, ms in its kernels): after ``integrand`` the contraction kernels; after ``tensor`` the series and
-        integral kernels, which are all of that call's device work, so the two values are equal."""
+        integral kernels, which are all of that call's device work, so the two values are equal; after ``optical`` the table kernels and
+        the two stages of every chunk."""
         t = self.recursion.timing()
         return t["total_ms"], t["rest_ms"]

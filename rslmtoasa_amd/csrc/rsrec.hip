@@ -42,6 +42,7 @@
 #include "kernels_moments.hpp"
 #include "kernels_kubo.hpp"
 #include "kernels_cond.hpp"
+#include "kernels_optical.hpp"
 #include "kernels_exchange.hpp"
 #include "kernels_auxgreen.hpp"
 #include "kernels_contour.hpp"
@@ -132,6 +133,8 @@ struct rsrec_handle {
                                       // given back with d_kubo when the recursion plans a batch
     DevBuf d_ctens[2];                // rsrec_kubo_conductivity: mesh + series as k_cond_tensor reads them; staging (integrand in, sigma / series out);
                                       // given back with d_cond
+    DevBuf d_opt[5];                  // rsrec_kubo_optical: tables (basis, Fermi weights and ranges, live tiles); moment planes, projections and tile
+                                      // partials of a chunk of orbitals; staging (a set's diagonals in, opt out); given back with d_cond
     DevBuf d_bsqrt, d_term, d_gim, d_ldos;   // stages on resident coefficients: sqrt(B^2), terminators; LDOS stage: Im g0_jj, output images
     DevBuf d_ops, d_spec;                    // spectra stage: operators (+ their traces with the Chebyshev moments), Im Tr(O g0) of the rank's sites
     // the image the last spectra call left in d_spec ([site][nen][nop] of the rank's sites), for rsrec_spectra_integrals(spec = NULL):
@@ -792,7 +795,7 @@ DevProblem make_problem(const rsrec_t* h) {
 // buffers of its own gives them back before it does, so that it plans on memory that is really free.
 void release_kubo_buffers(rsrec_t* h, bool moments, bool integrand) {
     if (moments) { for (auto& kb : h->d_kubo) kb.release(); h->kubo_diag_nvec = h->kubo_diag_ll = 0; }
-    if (integrand) { for (auto& cb : h->d_cond) cb.release(); for (auto& cb : h->d_ctens) cb.release(); }
+    if (integrand) { for (auto& cb : h->d_cond) cb.release(); for (auto& cb : h->d_ctens) cb.release(); for (auto& cb : h->d_opt) cb.release(); }
 }
 
 struct BatchPlan {
@@ -4158,6 +4161,17 @@ struct KuboScale {
     KuboScale(double energy_min, double energy_max) : a((energy_max - energy_min) / (double)(2.0f - 0.3f)), b((energy_max + energy_min) / 2) {}
 };
 
+// w_n = g_n weights_n, n = 1 .. L: Lorentz kernel (lambda = 6) x the half weight of n = 1 (conductivity.f90:186-194).  lorentz_kernel forms
+// (real(ll) - 1)/real(bign) and 1 - that in single precision (math.f90:1674)
+std::vector<double> kubo_kernel_weights(int L) {
+    std::vector<double> w(L);
+    for (int ll = 1; ll <= L; ++ll) {
+        const float r = ((float)ll - 1.0f) / (float)L, t = 1.0f - r;
+        w[ll - 1] = std::sinh(6.0 * (double)t) / std::sinh(6.0) * (ll == 1 ? 0.5 : 1.0);
+    }
+    return w;
+}
+
 // Reserve a buffer of the conductivity calls.  The moments' buffers (d_kubo) stay for the next rsrec_kubo_moments call unless this one needs
 // their memory; `keep_diag`: the resident diagonal moments (d_kubo[4]) stay even then.
 int reserve_beside_kubo(rsrec_t* h, DevBuf& buf, size_t bytes, bool keep_diag) {
@@ -4194,12 +4208,7 @@ int kubo_integrand_run(rsrec_t* h, const char* fn, bool diag, int nvec, int cond
     const KuboScale sc(energy_min, energy_max);
     const double a = sc.a, b = sc.b, de = energy_max - energy_min;
     const double factor = 16 / (3.14159265358979323846 * (de * de));
-    // Lorentz kernel x weights (:186-194): lorentz_kernel forms (real(ll) - 1)/real(bign) and 1 - that in single precision (math.f90:1674)
-    std::vector<double> w(L);
-    for (int ll = 1; ll <= L; ++ll) {
-        const float r = ((float)ll - 1.0f) / (float)L, t = 1.0f - r;
-        w[ll - 1] = std::sinh(6.0 * (double)t) / std::sinh(6.0) * (ll == 1 ? 0.5 : 1.0);
-    }
+    const std::vector<double> w = kubo_kernel_weights(L);
     const bool mu_dev = is_device_ptr(mu_nm), out_dev = is_device_ptr(integrand);
     const size_t per_vec_out = (size_t)NB * nen;
     // buffer 0: tb (lk x ep), ta (ln x ep complex), pre (ep), w (L), ene (nen);  1: S / D planes;  2: partials;  3: staging
@@ -4324,6 +4333,111 @@ extern "C" int rsrec_kubo_conductivity(rsrec_t* h, int nvec, int per_vector, int
                                        double temperature, const double* integrand, double* sigma, double* series) {
     if (!h) return RSREC_ERR_ARG;
     return kubo_conductivity_run(h, nvec, per_vector != 0, nen, nv1, ene, energy_min, energy_max, temperature, integrand, sigma, series);
+}
+
+namespace {
+
+// sigma(omega) from the orbital-diagonal moments (kernels_optical.hpp): per set the tables once, then per chunk of orbitals the moment planes
+// (k_opt_gather), stage 1 (k_opt_project), the fused stage 2 (k_opt_fused) and the sum of the tile partials (k_opt_reduce).  The
+// projections and partials of a chunk stay below OPT_WORK_BYTES (one orbital at least).  Needs no lattice and no Hamiltonian.
+constexpr size_t OPT_WORK_BYTES = (size_t)1 << 30;
+int kubo_optical_run(rsrec_t* h, int nset, int cond_ll, const double* mu_diag, int nen, const double* ene, double energy_min, double energy_max, int nw,
+                     int nfermi, const double* fermi, double temperature, double* opt) {
+    const char* fn = "rsrec_kubo_optical";
+    if (nset < 1 || cond_ll < 1 || cond_ll > RSREC_COND_LL_MAX || !ene || !fermi || !opt)
+        return fail(h, RSREC_ERR_ARG, "%s: bad argument (nset=%d cond_ll=%d, or a NULL ene, fermi or opt)", fn, nset, cond_ll);
+    if (nen < 2 || nen > (1 << 20)) return fail(h, RSREC_ERR_ARG, "%s: nen=%d is outside 2 .. %d", fn, nen, 1 << 20);
+    if (nw < 1 || nw > nen - 1) return fail(h, RSREC_ERR_ARG, "%s: nw=%d is outside 1 .. nen - 1 = %d", fn, nw, nen - 1);
+    if (nfermi < 1 || nfermi > RSREC_OPT_NFERMI_MAX) return fail(h, RSREC_ERR_ARG, "%s: nfermi=%d is outside 1 .. %d", fn, nfermi, RSREC_OPT_NFERMI_MAX);
+    if (!std::isfinite(energy_min) || !std::isfinite(energy_max) || !(energy_max > energy_min))
+        return fail(h, RSREC_ERR_ARG, "%s: energy window [%g, %g] is empty", fn, energy_min, energy_max);
+    if (!std::isfinite(temperature) || temperature < 0) return fail(h, RSREC_ERR_ARG, "%s: temperature %g is negative or not finite", fn, temperature);
+    for (int f = 0; f < nfermi; ++f)
+        if (!std::isfinite(fermi[f])) return fail(h, RSREC_ERR_ARG, "%s: Fermi level %d is not finite", fn, f + 1);
+    const double step = ene[1] - ene[0];
+    if (!std::isfinite(ene[0]) || !std::isfinite(step) || !(step > 0)) return fail(h, RSREC_ERR_ARG, "%s: the mesh does not increase (ene(2) - ene(1) = %g)", fn, step);
+    for (int i = 2; i < nen; ++i)
+        if (!(std::fabs(ene[i] - ene[0] - i * step) <= 1e-9 * step))
+            return fail(h, RSREC_ERR_ARG, "%s: the mesh is not uniform: ene(%d) is %g off ene(1) + %d steps of %g", fn, i + 1, ene[i] - ene[0] - i * step, i, step);
+    const bool resident = !mu_diag;
+    if (resident) {
+        if (!h->kubo_diag_nvec) return fail(h, RSREC_ERR_ARG, "%s: no diagonal moments are resident on the handle (rsrec_kubo_moments_diag first, or pass mu_diag)", fn);
+        if (nset != h->kubo_diag_nvec || cond_ll != h->kubo_diag_ll)
+            return fail(h, RSREC_ERR_ARG, "%s: nset=%d cond_ll=%d asked, the resident moments have nvec=%d cond_ll=%d", fn, nset, cond_ll, h->kubo_diag_nvec, h->kubo_diag_ll);
+        mu_diag = h->d_kubo[4].as<double>();
+    }
+    HIPCK(h, hipSetDevice(h->device));
+    reset_timing(h);
+    const int L = cond_ll, nf = nfermi, lp = (L + KO_TM - 1) / KO_TM * KO_TM, lk = (L + 3) / 4 * 4, ep = (nen + KO_TI - 1) / KO_TI * KO_TI;
+    const int nti = ep / KO_TI, ntj = (nen + KO_TJ - 1) / KO_TJ, nb = ep / KO_FB;
+    const KuboScale sc(energy_min, energy_max);
+    const double pref = 3.14159265358979323846 / (sc.a * sc.a);
+    const std::vector<double> w = kubo_kernel_weights(L);
+    const bool mu_dev = is_device_ptr(mu_diag), out_dev = is_device_ptr(opt);
+    const size_t mu_set = (size_t)NB * L * L, out_set = (size_t)NB * nw * nf;      // complex numbers of one set
+    // the chunk of orbitals: projections + partials of a chunk within OPT_WORK_BYTES
+    const size_t pt_l = (size_t)lp * ep * sizeof(double2), part_l = (size_t)nti * ntj * nf * KO_NDIAG * sizeof(double2);
+    const int nl_max = (int)std::max<size_t>(1, std::min<size_t>(NB, OPT_WORK_BYTES / (pt_l + part_l)));
+    // buffer 0: td (lp x ep), ft (nf x ep), fr (nf x nb complex), w (L), ene (nen), fermi (nf), live (nti x ntj int);  1: moment planes;
+    // 2: projections;  3: partials;  4: staging -- a set's diagonals | opt, each only for a caller array on the host
+    const size_t o_ft = (size_t)lp * ep, o_fr = o_ft + (size_t)nf * ep, o_w = o_fr + 2 * (size_t)nf * nb, o_ene = o_w + L, o_fermi = o_ene + nen,
+                 o_live = o_fermi + nf, n0 = o_live + ((size_t)nti * ntj + 1) / 2;
+    const size_t o_out = mu_dev ? 0 : 2 * mu_set, n4 = o_out + (out_dev ? 0 : 2 * out_set * nset);
+    const size_t want[5] = {n0 * sizeof(double), (size_t)nl_max * lp * lp * sizeof(double2), nl_max * pt_l, nl_max * part_l, n4 * sizeof(double)};
+    const bool keep_diag = h->kubo_diag_nvec != 0;                  // resident diagonal moments survive the call
+    for (int k = 0; k < 5; ++k) XFER(reserve_beside_kubo(h, h->d_opt[k], want[k], keep_diag));
+    double* T = h->d_opt[0].as<double>();
+    XFER(xfer_h2d(h, T + o_w, w.data(), (size_t)L * sizeof(double)));
+    XFER(xfer_h2d(h, T + o_ene, ene, (size_t)nen * sizeof(double)));
+    XFER(xfer_h2d(h, T + o_fermi, fermi, (size_t)nf * sizeof(double)));
+    double2* d_fr = reinterpret_cast<double2*>(T + o_fr);
+    int* d_live = reinterpret_cast<int*>(T + o_live);
+    double* stage = h->d_opt[4].as<double>();
+    double2* out = out_dev ? reinterpret_cast<double2*>(opt) : reinterpret_cast<double2*>(stage + o_out);
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> kev;
+    hipEvent_t e_begin = next_event(h);
+    k_opt_basis<<<(ep + 255) / 256, 256, 0, h->stream>>>(nen, ep, L, lp, nf, T + o_ene, T + o_w, T + o_fermi, sc.a, sc.b, temperature, T, T + o_ft);
+    k_opt_fermi_range<<<(nb * nf + 255) / 256, 256, 0, h->stream>>>(nen, ep, nf, T + o_ft, d_fr);
+    k_opt_tiles<<<(nti * ntj + 255) / 256, 256, 0, h->stream>>>(nen, ep, nw, nf, nti, ntj, d_fr, d_live);
+    HIPCK(h, hipGetLastError());
+    kev.emplace_back(e_begin, next_event(h));
+    for (int s = 0; s < nset; ++s) {
+        const double2* src;
+        if (mu_dev) src = reinterpret_cast<const double2*>(mu_diag) + mu_set * s;
+        else {
+            if (s > 0) HIPCK(h, hipStreamSynchronize(h->stream));    // (the staging of the last set's diagonals is overwritten)
+            XFER(xfer_h2d(h, stage, mu_diag + 2 * mu_set * s, 2 * mu_set * sizeof(double)));
+            src = reinterpret_cast<const double2*>(stage);
+        }
+        for (int l0 = 0; l0 < NB; l0 += nl_max) {
+            const int nl = std::min(nl_max, NB - l0);
+            const size_t gelems = (size_t)nl * lp * lp;
+            hipEvent_t c0 = next_event(h);
+            k_opt_gather<<<(int)std::min<size_t>(4096, (gelems + 255) / 256), 256, 0, h->stream>>>(src, l0, nl, L, lp, h->d_opt[1].as<double2>());
+            k_opt_project<<<dim3((unsigned)((ep + 255) / 256), (unsigned)(lp / KO_TM), (unsigned)nl), 256, 0, h->stream>>>(
+                ep, lp, lk, T, h->d_opt[1].as<double2>(), h->d_opt[2].as<double2>());
+            k_opt_fused<<<dim3((unsigned)((ntj + 3) / 4), (unsigned)nti, (unsigned)nl), 256, 0, h->stream>>>(
+                nen, ep, lp, lk, nw, nf, nti, ntj, T, h->d_opt[2].as<double2>(), T + o_ft, d_live, h->d_opt[3].as<double2>());
+            k_opt_reduce<<<(int)(((size_t)nl * nw * nf + 255) / 256), 256, 0, h->stream>>>(nw, nf, nti, ntj, l0, nl, pref, d_live, h->d_opt[3].as<double2>(),
+                                                                                            out + out_set * s);
+            HIPCK(h, hipGetLastError());
+            kev.emplace_back(c0, next_event(h));
+        }
+    }
+    hipEvent_t e_end = next_event(h);
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    if (!out_dev) XFER(xfer_d2h(h, opt, out, out_set * nset * sizeof(double2)));
+    h->t_total_ms = ev_ms(e_begin, e_end);
+    for (auto& pr : kev) h->t_rest_ms += ev_ms(pr.first, pr.second);        // the kernels: tables, then gather + the two stages + reduce per chunk
+    return RSREC_OK;
+}
+
+}  // namespace
+
+extern "C" int rsrec_kubo_optical(rsrec_t* h, int nset, int cond_ll, const double* mu_diag, int nen, const double* ene, double energy_min, double energy_max,
+                                  int nw, int nfermi, const double* fermi, double temperature, double* opt) {
+    if (!h) return RSREC_ERR_ARG;
+    return kubo_optical_run(h, nset, cond_ll, mu_diag, nen, ene, energy_min, energy_max, nw, nfermi, fermi, temperature, opt);
 }
 
 // chebyshev_orbital_mod (recursion.f90:2834-3049), the moment part (:2893-3013), device-resident: the seeds are chains advanced together.
