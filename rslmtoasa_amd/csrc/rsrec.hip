@@ -1434,8 +1434,10 @@ __global__ __launch_bounds__(256) void k_rotate_coef(double2* __restrict__ A, do
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// What run_block_lanczos and run_chebyshev share, as the pair calls share PairCall and the on-site stages SiteStage: the call's decisions and
-// reservations (RecursionCall), a batch's uploads (RecursionBatch), the matrix-core H|psi> step (apply_h), SideReduce and replay_level_loop.
+// What the chain drivers (run_block_lanczos, run_chebyshev, run_pairs_direct, run_bloch) share, as the pair calls share PairCall and the on-site
+// stages SiteStage: the call's decisions and reservations (RecursionCall), a batch's uploads (RecursionBatch), seed_chains, the H|psi> step of
+// either kernel set (apply_h, valu_apply_h), SideReduce and replay_level_loop; the Chebyshev drivers also the three-term recurrence
+// (ChainChebyshev), and the two "one chain per atom" drivers their whole level loop (chain_level_loop).
 struct RecursionCall {
     bool mfma = false, side = false;     // kernel set; the side stream takes the levels' reductions
     int nchains = 0, nseed = 1, napply = 0, nlev = 0;   // napply: applications of H per chain; nlev: levels of its region lists
@@ -1462,6 +1464,12 @@ RecursionCall recursion_call(const rsrec_t* h, bool mfma, int nchains, int nseed
     RC.ci = (mfma && (h->hoh || rot || h->opt_spmm5 == 2 || (h->opt_spmm5 == 1 && large) || !spmm4_usable(h))) ? 1 : 0;
     return RC;
 }
+
+// kernels: 0 = auto, 1 = FP64 VALU kernel set, 2 = matrix-core set.  The matrix-core SpMM tables exist for lattices with up to
+// S4_MAXSLOTS - 1 neighbour slots; beyond that the VALU set (any stencil) runs.
+bool matrix_core_set(const rsrec_t* h) { return h->opt_kernels != 1 && h->s5_built; }
+// what the last call left resident is gone once a call reserves (or overwrites) the buffers it lay in
+void drop_resident(rsrec_t* h) { h->res_kind = 0; h->spec_res.nop = 0; }
 
 // Plans the batches and reserves what every recursion needs: `nvec` work vectors (all but `skip_vec`), the partials, the seeds with `coef_slots`
 // coefficients per chain, the status word (cleared here), the side stream; opens the timed span.  The caller reserves its resident outputs BEFORE it.
@@ -1591,6 +1599,73 @@ S5Epilogue cheb_epilogue(bool first, const double* cur, const double* old, doubl
     S5Epilogue E; E.kind = first ? 1 : 2; E.cur = cur; E.old = first ? nullptr : old; E.a = a; E.b = b;
     return E;
 }
+// One H|psi> of the VALU set (LayoutCM), the counterpart of apply_h: `out` = MODE of H src as application `step` of the batch's chains, between
+// the events the call's hop time is read from.  With hoh two launches -- h src into `hps` on the lists of level 2 step - 1, then MODE_HOH on
+// those of level 2 step.  v0: psi (Lanczos) | T_{n-2} (Chebyshev); ca, cb: the Chebyshev scaling.  The Gram partials go to d_partial.
+template <int MODE, int MODE_HOH>
+int valu_apply_h(rsrec_t* h, RecursionCall& RC, const RecursionBatch& b, int step, const double* src, const double* v0, double* out, double* hps,
+                 double ca = 0.0, double cb = 0.0) {
+    const bool hoh = h->hoh != 0;
+    const dim3 grid(RC.nblk, b.nb);
+    hipEvent_t e0 = next_event(h);                   // [e0, e1] brackets exactly the H|psi> kernel(s) of this step
+    ApplyArgs G{};
+    G.partial = h->d_partial.as<double2>(); G.a = ca; G.b = cb; G.in = src; G.cur = src; G.v0 = v0; G.out = out; G.level = step;
+    if (!hoh) k_apply<MODE, LayoutCM><<<grid, NTHREADS, 0, h->stream>>>(RC.P, b.CV, G);
+    else {
+        G.out = hps; G.level = 2 * step - 1;
+        k_apply<AM_STORE, LayoutCM><<<grid, NTHREADS, 0, h->stream>>>(RC.P, b.CV, G);
+        G.in = hps; G.v1 = hps; G.out = out; G.level = 2 * step;
+        k_apply<MODE_HOH, LayoutCM><<<grid, NTHREADS, 0, h->stream>>>(RC.P, b.CV, G);
+    }
+    RC.hop_ev.emplace_back(e0, next_event(h)); h->n_hop_launch += hoh ? 2 : 1;
+    return RSREC_OK;
+}
+
+// k_seed on vector `vec` of a batch's chains, in the layout the call's kernels read: CI (k_spmm5), LayoutRM (k_spmm4) or LayoutCM (VALU set)
+void seed_chains(rsrec_t* h, const RecursionCall& RC, int nb, double* vec) {
+    const auto seed = RC.ci ? k_seed<LayoutCI> : RC.mfma ? k_seed<LayoutRM> : k_seed<LayoutCM>;
+    seed<<<nb, 64, 0, h->stream>>>(vec, RC.velems, h->d_seed.as<int>(), h->d_seedcoef.as<double2>(), RC.nseed);
+}
+
+// The three-term recurrence on a batch's chains, H~ = (H - b)/a, shaped like ChebyshevStepper: with T_0(H~) x in `cur` (work vector 0),
+// step(t) for t = 1, 2, ... leaves T_t(H~) x in `cur`, T_{t-1}(H~) x in `old` and the region level it ran on in `level`; from t = 2 on work
+// vectors 0 .. 2 rotate, and `spare` is T_{t-2}(H~) x.  VALU set: k_apply forms `cur` (tmp: h psi of the hoh first pass).  Matrix-core set:
+// k_spmm5's epilogue forms it (hps: h psi of the hoh first pass) -- or, with `plain_h`, apply_h leaves H old in `tmp` and the caller forms `cur`
+// (run_chebyshev with cheb_fused = 0, and k_spmm4, which has no epilogue).
+struct ChainChebyshev {
+    double *old, *cur, *spare, *tmp, *hps;
+    double a, b;
+    int level = 0;
+    ChainChebyshev(const rsrec_t* h, const RecursionCall& RC, double a_, double b_)
+        : old(h->d_vec[1].as<double>()), cur(h->d_vec[0].as<double>()), spare(h->d_vec[2].as<double>()), tmp(h->d_vec[3].as<double>()),
+          hps(RC.ci && h->hoh ? h->d_vec[4].as<double>() : nullptr), a(a_), b(b_) {}
+    int step(rsrec_t* h, RecursionCall& RC, const RecursionBatch& bt, int t, bool plain_h = false) {
+        const bool first = t == 1;
+        if (first) std::swap(old, cur);
+        else { double* o = spare; spare = old; old = cur; cur = o; }
+        level = h->hoh ? 2 * t : t;
+        if (RC.mfma) return apply_h(h, RC, bt, t, old, plain_h ? tmp : cur, hps, nullptr, 0, plain_h ? S5Epilogue() : cheb_epilogue(first, old, spare, a, b));
+        if (first) return valu_apply_h<AM_CHEB1, AM_HOH_CHEB1>(h, RC, bt, t, old, old, cur, tmp, a, b);
+        return valu_apply_h<AM_CHEBN, AM_HOH_CHEBN>(h, RC, bt, t, old, spare, cur, tmp, a, b);
+    }
+};
+
+// The level loop of the "one chain per atom" drivers on one batch: clear, seed, then the vector of every order n = 0 .. napply goes to
+// pass(vec, region level, n) as soon as it is formed; returns when the stream is idle (the next batch's uploads reuse the seeds).
+template <class Pass>
+int chain_level_loop(rsrec_t* h, RecursionCall& RC, const RecursionBatch& bt, double a, double b, Pass&& pass) {
+    XFER(clear_vectors(h, RC, bt.nb));
+    ChainChebyshev S(h, RC, a, b);
+    seed_chains(h, RC, bt.nb, S.cur);
+    pass(S.cur, 0, 0);
+    for (int t = 1; t <= RC.napply; ++t) {
+        XFER(S.step(h, RC, bt, t));
+        pass(S.cur, S.level, t);
+    }
+    HIPCK(h, hipGetLastError());
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    return RSREC_OK;
+}
 // The side-stream hand-off of a level's reduction (partial sums -> coefficients), which the main stream's next H|psi> does not need: begin
 // gives the stream to reduce on -- with `side` the side stream, behind everything queued on the main stream so far --, end marks the
 // reduction's end there, and wait holds the main stream until then: before the first launch that reads its result or reuses its input.
@@ -1672,10 +1747,10 @@ int run_block_lanczos(rsrec_t* h, int nchains, int nseed, const int32_t* seed_at
     if (rot && !MFMA) return fail(h, RSREC_ERR_ARG, "local-axis recursion needs the matrix-core kernel set (option kernels = 0 or 2)");
     RecursionCall RC = recursion_call(h, MFMA, nchains, nseed, nsteps, rot);
     const int ci = RC.ci, ntau = h->nmax + h->ntype;
-    const size_t velems = RC.velems, cstride = (size_t)lld * BLK, orth_lds = TILE_ATOMS * BLK * sizeof(double2);
+    const size_t cstride = (size_t)lld * BLK, orth_lds = TILE_ATOMS * BLK * sizeof(double2);
     // the coefficients of ALL chains of the call stay on the device (resident input of rsrec_pack_diag / rsrec_block_ldos): reserved before
     // the batch is planned from the free memory
-    h->res_kind = 0; h->spec_res.nop = 0;
+    drop_resident(h);
     HIPCK(h, h->d_coefA.reserve((size_t)nchains * lld * BLK * sizeof(double2)));
     HIPCK(h, h->d_coefB.reserve((size_t)nchains * lld * BLK * sizeof(double2)));
     if (rot) {                                          // the rotations of all chains, once per call (k_rotate_coef)
@@ -1727,8 +1802,7 @@ int run_block_lanczos(rsrec_t* h, int nchains, int nseed, const int32_t* seed_at
             if (MFMA) HIPCK(h, hipMemsetAsync(bfrags, 0, (size_t)nb * 3 * 27 * 64 * sizeof(double), h->stream));
             double *psi = h->d_vec[0].as<double>(), *t2 = h->d_vec[3].as<double>();   // (swapped every level)
             double* t3 = oop ? h->d_vec[hoh ? 4 : 1].as<double>() : nullptr;
-            if (ci) k_seed<LayoutCI><<<nb, 64, 0, h->stream>>>(psi, velems, h->d_seed.as<int>(), h->d_seedcoef.as<double2>(), nseed);
-            else k_seed<L><<<nb, 64, 0, h->stream>>>(psi, velems, h->d_seed.as<int>(), h->d_seedcoef.as<double2>(), nseed);
+            seed_chains(h, RC, nb, psi);
             k_set_identity<<<nb, 256, 0, h->stream>>>(dB, cstride);                                  // b2temp_b(:,:,1) = I  (:1837)
             if (MFMA) k_uscheme_init<<<nb, 256, 0, h->stream>>>(h->d_bmats.as<double2>(), bfrags, ci);
             const dim3 grid(nblk, nb);
@@ -1763,18 +1837,7 @@ int run_block_lanczos(rsrec_t* h, int nchains, int nseed, const int32_t* seed_at
                     continue;
                 }
                 // FP64 VALU kernel set: the reference's literal order on the reference's layout
-                hipEvent_t e0 = next_event(h);
-                ApplyArgs G{}; G.partial = partial;
-                if (!hoh) {
-                    G.in = psi; G.v0 = psi; G.out = pmn; G.level = lv_final;
-                    k_apply<AM_LANCZOS, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
-                } else {
-                    G.in = psi; G.out = hpsi; G.level = 2 * ll + 1;
-                    k_apply<AM_STORE, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
-                    G.in = hpsi; G.v1 = hpsi; G.cur = psi; G.v0 = psi; G.out = pmn; G.level = lv_final;
-                    k_apply<AM_HOH_LANCZOS, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
-                }
-                RC.hop_ev.emplace_back(e0, next_event(h)); h->n_hop_launch += hoh ? 2 : 1;   // [e0, e1] brackets exactly the H|psi> kernel(s) of this step
+                XFER((valu_apply_h<AM_LANCZOS, AM_HOH_LANCZOS>(h, RC, bt, ll + 1, psi, psi, pmn, hpsi)));
                 k_reduce_a<<<nb, 1024, 0, h->stream>>>(partial, nblk, dA + (size_t)ll * BLK, cstride);
                 k_orth<L><<<grid, NTHREADS, orth_lds, h->stream>>>(CV, lv_final, psi, pmn, (const double*)nullptr, dA + (size_t)ll * BLK, cstride, partial);
                 k_reduce_b_eig<<<nb, 1024, 0, h->stream>>>(partial, nblk, dB + (size_t)(ll + 1) * BLK, cstride, h->d_bmats.as<double2>(), h->d_status.as<int>());
@@ -1824,10 +1887,7 @@ extern "C" int rsrec_block_lanczos_seeded(rsrec_t* h, int nchains, int nseed, co
     HIPCK(h, hipSetDevice(h->device));
     reset_timing(h);
     if (nchains == 0) return RSREC_OK;
-    // kernels: 0 = auto, 1 = FP64 VALU kernel set, 2 = matrix-core set.  The matrix-core SpMM tables exist for lattices with up to
-    // S4_MAXSLOTS - 1 neighbour slots; beyond that the VALU set (any stencil) runs.
-    const bool use_mfma = (h->opt_kernels != 1) && h->s5_built;
-    if (use_mfma) return run_block_lanczos<LayoutRM, true>(h, nchains, nseed, seed_atoms, seed_coef, lld, a_b, b2_b);
+    if (matrix_core_set(h)) return run_block_lanczos<LayoutRM, true>(h, nchains, nseed, seed_atoms, seed_coef, lld, a_b, b2_b);
     return run_block_lanczos<LayoutCM, false>(h, nchains, nseed, seed_atoms, seed_coef, lld, a_b, b2_b);
 }
 
@@ -3150,7 +3210,7 @@ void cheb_mu1_scales(int nb, int nseed, const std::vector<int>& seeds0, std::vec
     }
 }
 
-template <class L, bool MFMA>
+template <bool MFMA>
 int run_chebyshev(rsrec_t* h, int nsites, int nseed, const int32_t* seed_atoms, const double* seed_coef, int lld, double a, double b, double* mu_n) {
     const int kk = h->kk;
     const bool hoh = h->hoh != 0;
@@ -3158,12 +3218,12 @@ int run_chebyshev(rsrec_t* h, int nsites, int nseed, const int32_t* seed_atoms, 
     const int nmom = 2 * lld + 2;
     RecursionCall RC = recursion_call(h, MFMA, nsites, nseed, napply);
     const int ci = RC.ci;
-    const size_t velems = RC.velems, mstride = (size_t)nmom * BLK;
+    const size_t mstride = (size_t)nmom * BLK;
     // the moments of ALL chains of the call stay on the device (rsrec_pack_moments): reserved BEFORE the batch is planned from the free
     // memory, so a call over many sites (nrec ~ kk) sizes its vectors around them instead of failing behind them
-    h->res_kind = 0; h->spec_res.nop = 0;
+    drop_resident(h);
     HIPCK(h, h->d_mu.reserve((size_t)nsites * nmom * BLK * sizeof(double2)));
-    // k_spmm5 forms the new vector in its epilogue (dst = (H src - b src)/a [* 2 - p0]; the default of the matrix-core set); k_mfma_cheb then
+    // k_spmm5 forms the new vector in its epilogue (cur = (H old - b old)/a [* 2 - spare]; the default of the matrix-core set); k_mfma_cheb then
     // only sums the Grams and H psi is never held: vector 3 is neither allocated nor cleared
     const bool fused = ci && h->opt_cheb_fused;
     XFER(recursion_begin(h, RC, MFMA ? (hoh ? 5 : 4) : (hoh ? 4 : 3), fused ? 3 : -1, nseed + 1));
@@ -3174,53 +3234,31 @@ int run_chebyshev(rsrec_t* h, int nsites, int nseed, const int32_t* seed_atoms, 
         double2* mu = h->d_mu.as<double2>() + (size_t)c0 * mstride;       // this batch's slice of the resident moments
         RecursionBatch bt;
         XFER(recursion_batch(h, RC, seed_atoms, seed_coef, c0, nb, bt, cheb_mu1_scales));
-        const ChainView &CV = bt.CV, &CVp = bt.CVp;
+        const ChainView& CVp = bt.CVp;
         XFER(clear_vectors(h, RC, nb));
         HIPCK(h, hipMemsetAsync(mu, 0, (size_t)nb * mstride * sizeof(double2), h->stream));
-        double *p0 = h->d_vec[0].as<double>(), *p1 = h->d_vec[1].as<double>(), *p2 = h->d_vec[2].as<double>(), *tmp = h->d_vec[3].as<double>();
-        double* hps = (ci && hoh) ? h->d_vec[4].as<double>() : nullptr;     // hoh: h psi of the first pass
-        if (ci) k_seed<LayoutCI><<<nb, 64, 0, h->stream>>>(p0, velems, h->d_seed.as<int>(), h->d_seedcoef.as<double2>(), nseed);
-        else k_seed<L><<<nb, 64, 0, h->stream>>>(p0, velems, h->d_seed.as<int>(), h->d_seedcoef.as<double2>(), nseed);
+        ChainChebyshev S(h, RC, a, b);
+        seed_chains(h, RC, nb, S.cur);
         k_set_identity<<<nb, 256, 0, h->stream>>>(mu, mstride, h->d_seedcoef.as<double>() + (size_t)nb * nseed * 2);   // mu_1 (cheb_0th_mom :2157)
-        const dim3 grid(nblk, nb);
         for (int t = 1; t <= napply; ++t) {      // t = 1: first moment; t >= 2: recursion step ll = t-1
             const bool first = (t == 1);
-            const int lv_final = hoh ? 2 * t : t;
-            double *src = first ? p0 : p1, *dst = first ? p1 : p2;
+            XFER(S.step(h, RC, bt, t, MFMA && !fused));        // unfused: H old is in S.tmp and k_mfma_cheb forms S.cur
             if (MFMA) {
-                const dim3 gl = level_grid(h, bt.grid_mf, lv_final);
-                XFER(apply_h(h, RC, bt, t, src, fused ? dst : tmp, hps, nullptr, 0, fused ? cheb_epilogue(first, src, p0, a, b) : S5Epilogue()));
+                const dim3 gl = level_grid(h, bt.grid_mf, S.level);
                 double* gp = h->d_partial.as<double>();
                 XFER(side_reduce_wait(h, SR));                    // gp is free again
                 if (fused) {
-                    if (first) k_mfma_cheb<true, true><<<gl, MF_WAVES * 64, 0, h->stream>>>(CVp, lv_final, kk, nullptr, src, nullptr, dst, a, b, gp);
-                    else k_mfma_cheb<false, true><<<gl, MF_WAVES * 64, 0, h->stream>>>(CVp, lv_final, kk, nullptr, src, nullptr, dst, a, b, gp);
-                } else if (first) k_mfma_cheb<true><<<gl, MF_WAVES * 64, 0, h->stream>>>(CVp, lv_final, kk, tmp, src, nullptr, dst, a, b, gp);
-                else k_mfma_cheb<false><<<gl, MF_WAVES * 64, 0, h->stream>>>(CVp, lv_final, kk, tmp, src, p0, dst, a, b, gp);
+                    if (first) k_mfma_cheb<true, true><<<gl, MF_WAVES * 64, 0, h->stream>>>(CVp, S.level, kk, nullptr, S.old, nullptr, S.cur, a, b, gp);
+                    else k_mfma_cheb<false, true><<<gl, MF_WAVES * 64, 0, h->stream>>>(CVp, S.level, kk, nullptr, S.old, nullptr, S.cur, a, b, gp);
+                } else if (first) k_mfma_cheb<true><<<gl, MF_WAVES * 64, 0, h->stream>>>(CVp, S.level, kk, S.tmp, S.old, nullptr, S.cur, a, b, gp);
+                else k_mfma_cheb<false><<<gl, MF_WAVES * 64, 0, h->stream>>>(CVp, S.level, kk, S.tmp, S.old, S.spare, S.cur, a, b, gp);
                 hipStream_t rs; XFER(side_reduce_begin(h, SR, rs));
                 int n2 = gl.x; const double* gp2 = presum(h, gp, nb, n2, 2 * 1296, rs, SR.side ? 1 : 0);
                 k_reduce_cheb_mf<<<nb, 1024, 0, rs>>>(gp2, n2, first ? 1 : 0, t - 1, mu, mstride, h->d_status.as<int>(), nseed > 1 ? 1 : 0, ci);
                 XFER(side_reduce_end(h, SR));
-                if (!first) { double* o = p0; p0 = p1; p1 = p2; p2 = o; }
                 continue;
             }
-            hipEvent_t e0 = next_event(h);
-            ApplyArgs G{};
-            G.partial = h->d_partial.as<double2>(); G.a = a; G.b = b;
-            if (!hoh) {
-                G.in = src; G.cur = src; G.v0 = p0; G.out = dst; G.level = lv_final;
-                if (first) k_apply<AM_CHEB1, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
-                else k_apply<AM_CHEBN, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
-            } else {
-                G.in = src; G.out = tmp; G.level = 2 * t - 1;
-                k_apply<AM_STORE, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
-                G.in = tmp; G.v1 = tmp; G.cur = src; G.v0 = p0; G.out = dst; G.level = lv_final;
-                if (first) k_apply<AM_HOH_CHEB1, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
-                else k_apply<AM_HOH_CHEBN, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
-            }
-            RC.hop_ev.emplace_back(e0, next_event(h)); h->n_hop_launch += hoh ? 2 : 1;
             k_reduce_cheb<<<nb, 1024, 0, h->stream>>>(h->d_partial.as<double2>(), nblk, first ? 1 : 0, t - 1, mu, mstride, h->d_status.as<int>(), nseed > 1 ? 1 : 0);
-            if (!first) { double* o = p0; p0 = p1; p1 = p2; p2 = o; }   // psi0 <- psi1 <- psi2 (:2585-2587) by rotating buffers
         }
         HIPCK(h, hipGetLastError());
         XFER(side_reduce_wait(h, SR));
@@ -3241,8 +3279,8 @@ extern "C" int rsrec_chebyshev_seeded(rsrec_t* h, int nchains, int nseed, const 
     HIPCK(h, hipSetDevice(h->device));
     reset_timing(h);
     if (nchains == 0) return RSREC_OK;
-    if (h->opt_kernels != 1 && h->s5_built) return run_chebyshev<LayoutRM, true>(h, nchains, nseed, seed_atoms, seed_coef, lld, a, b, mu_n);
-    return run_chebyshev<LayoutCM, false>(h, nchains, nseed, seed_atoms, seed_coef, lld, a, b, mu_n);
+    if (matrix_core_set(h)) return run_chebyshev<true>(h, nchains, nseed, seed_atoms, seed_coef, lld, a, b, mu_n);
+    return run_chebyshev<false>(h, nchains, nseed, seed_atoms, seed_coef, lld, a, b, mu_n);
 }
 
 extern "C" int rsrec_chebyshev(rsrec_t* h, int nsites, const int32_t* seed_atoms, int lld, double a, double b, double* mu_n) {
@@ -3323,8 +3361,8 @@ void fan_plan(const rsrec_t* h, int npairs, const int32_t* ijpair, int both_ends
     }
 }
 
-// L = LayoutCM with the VALU kernels; the matrix-core set always takes k_spmm5 on CI vectors here (the new vector is formed in its epilogue)
-template <class L, bool MFMA>
+// VALU set: LayoutCM vectors; the matrix-core set always takes k_spmm5 on CI vectors here (the new vector is formed in its epilogue)
+template <bool MFMA>
 int run_pairs_direct(rsrec_t* h, int npairs, const int32_t* ijpair, int lld, double a, double b, int both_ends, double* mu_n, double* m_pair) {
     const bool hoh = h->hoh != 0;
     const int napply = 2 * lld + 1;                              // psi_1 .. psi_{2 lld + 1}: moment n + 1 is a block of psi_n
@@ -3336,7 +3374,7 @@ int run_pairs_direct(rsrec_t* h, int npairs, const int32_t* ijpair, int lld, dou
     if (MFMA) RC.ci = 1;
     const size_t velems = RC.velems, mstride = (size_t)nmom * BLK;
     // resident outputs first, the batch is planned from what is left (see run_chebyshev)
-    h->res_kind = 0; h->spec_res.nop = 0;
+    drop_resident(h);
     HIPCK(h, h->d_mu.reserve((size_t)4 * npairs * mstride * sizeof(double2)));
     HIPCK(h, h->d_fan.reserve((size_t)nent * mstride * sizeof(double2)));
     const size_t ent_bytes = (size_t)nent * sizeof(FanEntry), pair_off = (ent_bytes + 255) / 256 * 256;
@@ -3348,52 +3386,15 @@ int run_pairs_direct(rsrec_t* h, int npairs, const int32_t* ijpair, int lld, dou
     const FanEntry* d_ent = h->d_fan_tab.as<FanEntry>();
     const FanPair* d_pairs = reinterpret_cast<const FanPair*>(static_cast<const char*>(h->d_fan_tab.p) + pair_off);
     double2* img = h->d_fan.as<double2>();
-    const int nblk = RC.nblk;
     for (int c0 = 0; c0 < nsrc; c0 += RC.B) {
         const int nb = std::min(RC.B, nsrc - c0);
         const int e0 = F.ent_begin[c0], ne = F.ent_begin[c0 + nb] - e0;
         RecursionBatch bt;
         XFER(recursion_batch(h, RC, F.sources.data(), nullptr, c0, nb, bt));
-        const ChainView& CV = bt.CV;
-        XFER(clear_vectors(h, RC, nb));
-        double *p0 = h->d_vec[0].as<double>(), *p1 = h->d_vec[1].as<double>(), *p2 = h->d_vec[2].as<double>();
-        double* tmp = MFMA ? nullptr : h->d_vec[3].as<double>();
-        double* hps = (MFMA && hoh) ? h->d_vec[4].as<double>() : nullptr;   // hoh: h psi of the first pass
-        auto gather = [&](const double* vec, int level, int n) {
+        XFER(chain_level_loop(h, RC, bt, a, b, [&](const double* vec, int level, int n) {
             if (MFMA) k_fan_gather<LayoutCI><<<ne, FAN_THREADS, 0, h->stream>>>(vec, velems, d_ent, e0, c0, level, n, nmom, img, h->d_status.as<int>());
-            else k_fan_gather<L><<<ne, FAN_THREADS, 0, h->stream>>>(vec, velems, d_ent, e0, c0, level, n, nmom, img, h->d_status.as<int>());
-        };
-        if (MFMA) k_seed<LayoutCI><<<nb, 64, 0, h->stream>>>(p0, velems, h->d_seed.as<int>(), h->d_seedcoef.as<double2>(), 1);
-        else k_seed<L><<<nb, 64, 0, h->stream>>>(p0, velems, h->d_seed.as<int>(), h->d_seedcoef.as<double2>(), 1);
-        gather(p0, 0, 0);
-        const dim3 grid(nblk, nb);
-        for (int t = 1; t <= napply; ++t) {
-            const bool first = (t == 1);
-            const int lv_final = hoh ? 2 * t : t;
-            double *src = first ? p0 : p1, *dst = first ? p1 : p2;
-            if (MFMA) XFER(apply_h(h, RC, bt, t, src, dst, hps, nullptr, 0, cheb_epilogue(first, src, p0, a, b)));
-            else {
-                hipEvent_t ev0 = next_event(h);
-                ApplyArgs G{};
-                G.partial = h->d_partial.as<double2>(); G.a = a; G.b = b;     // (the kernels' Gram partials are written and never read)
-                if (!hoh) {
-                    G.in = src; G.cur = src; G.v0 = p0; G.out = dst; G.level = lv_final;
-                    if (first) k_apply<AM_CHEB1, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
-                    else k_apply<AM_CHEBN, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
-                } else {
-                    G.in = src; G.out = tmp; G.level = 2 * t - 1;
-                    k_apply<AM_STORE, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
-                    G.in = tmp; G.v1 = tmp; G.cur = src; G.v0 = p0; G.out = dst; G.level = lv_final;
-                    if (first) k_apply<AM_HOH_CHEB1, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
-                    else k_apply<AM_HOH_CHEBN, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
-                }
-                RC.hop_ev.emplace_back(ev0, next_event(h)); h->n_hop_launch += hoh ? 2 : 1;
-            }
-            gather(dst, lv_final, t);
-            if (!first) { double* o = p0; p0 = p1; p1 = p2; p2 = o; }
-        }
-        HIPCK(h, hipGetLastError());
-        HIPCK(h, hipStreamSynchronize(h->stream));               // the next batch's uploads reuse the seeds
+            else k_fan_gather<LayoutCM><<<ne, FAN_THREADS, 0, h->stream>>>(vec, velems, d_ent, e0, c0, level, n, nmom, img, h->d_status.as<int>());
+        }));
     }
     double2* mu = h->d_mu.as<double2>();
     double2* mp = m_pair ? h->d_mpair.as<double2>() : nullptr;
@@ -3420,8 +3421,8 @@ extern "C" int rsrec_chebyshev_pairs_direct(rsrec_t* h, int npairs, const int32_
     HIPCK(h, hipSetDevice(h->device));
     reset_timing(h);
     if (npairs == 0) return RSREC_OK;
-    if (h->opt_kernels != 1 && h->s5_built) return run_pairs_direct<LayoutRM, true>(h, npairs, ijpair, lld, a, b, both_ends ? 1 : 0, mu_n, m_pair);
-    return run_pairs_direct<LayoutCM, false>(h, npairs, ijpair, lld, a, b, both_ends ? 1 : 0, mu_n, m_pair);
+    if (matrix_core_set(h)) return run_pairs_direct<true>(h, npairs, ijpair, lld, a, b, both_ends ? 1 : 0, mu_n, m_pair);
+    return run_pairs_direct<false>(h, npairs, ijpair, lld, a, b, both_ends ? 1 : 0, mu_n, m_pair);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -3474,8 +3475,8 @@ void bloch_lists(const rsrec_t* h, const BlochCall& A, int c0, int nb, int nlev,
     }
 }
 
-// L = LayoutCM with the VALU kernels; the matrix-core set takes k_spmm5 on CI vectors, as run_pairs_direct does
-template <class L, bool MFMA>
+// VALU set: LayoutCM vectors; the matrix-core set takes k_spmm5 on CI vectors, as run_pairs_direct does
+template <bool MFMA>
 int run_bloch(rsrec_t* h, const BlochCall& A) {
     const bool hoh = h->hoh != 0;
     const int kk = h->kk, nsrc = A.nsrc, nk = A.nk, ng = A.ngroup;
@@ -3486,7 +3487,7 @@ int run_bloch(rsrec_t* h, const BlochCall& A) {
     if (MFMA) RC.ci = 1;
     const size_t velems = RC.velems;
     // the resident image first, the batch is planned from what is left (see run_chebyshev)
-    h->res_kind = 0; h->spec_res.nop = 0;
+    drop_resident(h);
     HIPCK(h, h->d_mu.reserve(nimg * mstride * sizeof(double2)));
     HIPCK(h, h->d_bloch_geo.reserve((size_t)3 * (kk + nk) * sizeof(double)));
     // per chain, sized with the work vectors (the buffer recursion_begin reserves for per-chain extras): the phase table and the partials
@@ -3503,12 +3504,10 @@ int run_bloch(rsrec_t* h, const BlochCall& A) {
     double2* mu = h->d_mu.as<double2>();
     std::vector<std::pair<hipEvent_t, hipEvent_t>> bloch_ev;
     BlochBatchLists T;
-    const int nblk = RC.nblk;
     for (int c0 = 0; c0 < nsrc; c0 += RC.B) {
         const int nb = std::min(RC.B, nsrc - c0);
         RecursionBatch bt;
         XFER(recursion_batch(h, RC, A.sources, nullptr, c0, nb, bt));
-        const ChainView& CV = bt.CV;
         bloch_lists(h, A, c0, nb, RC.nlev, T);
         XFER(xfer_h2d(h, d_list, T.list.data(), (size_t)nb * kk * sizeof(int)));
         XFER(xfer_h2d(h, d_off, T.seg_off.data(), (size_t)nb * ng * sizeof(int)));
@@ -3516,10 +3515,6 @@ int run_bloch(rsrec_t* h, const BlochCall& A) {
         XFER(xfer_h2d(h, d_tot, T.tot.data(), (size_t)nb * sizeof(int)));
         const BlochLists BL{d_list, d_off, d_cnt, kk, ng, RC.nlev};
         const int* d_src = h->d_seed.as<int>();                  // (one seed per chain: the batch's 0-based source atoms)
-        XFER(clear_vectors(h, RC, nb));
-        double *p0 = h->d_vec[0].as<double>(), *p1 = h->d_vec[1].as<double>(), *p2 = h->d_vec[2].as<double>();
-        double* tmp = MFMA ? nullptr : h->d_vec[3].as<double>();
-        double* hps = (MFMA && hoh) ? h->d_vec[4].as<double>() : nullptr;   // hoh: h psi of the first pass
         {
             hipEvent_t e0 = next_event(h);
             const int maxtot = *std::max_element(T.tot.begin(), T.tot.end());
@@ -3531,9 +3526,9 @@ int run_bloch(rsrec_t* h, const BlochCall& A) {
         auto bloch_pass = [&](const double* vec, int level, int n) {
             hipEvent_t e0 = next_event(h);
             if (MFMA) k_bloch_diverge<LayoutCI><<<nb, BLOCH_THREADS, 0, h->stream>>>(vec, velems, d_src, h->d_status.as<int>());
-            else k_bloch_diverge<L><<<nb, BLOCH_THREADS, 0, h->stream>>>(vec, velems, d_src, h->d_status.as<int>());
+            else k_bloch_diverge<LayoutCM><<<nb, BLOCH_THREADS, 0, h->stream>>>(vec, velems, d_src, h->d_status.as<int>());
             for (int g = 0; g < ng; ++g) {
-                if (!MFMA) { k_bloch_valu<L><<<dim3(nk, nb), BLOCH_THREADS, 0, h->stream>>>(BL, g, level, vec, velems, table, mpad, nk, c0, n, nmom, mu); continue; }
+                if (!MFMA) { k_bloch_valu<LayoutCM><<<dim3(nk, nb), BLOCH_THREADS, 0, h->stream>>>(BL, g, level, vec, velems, table, mpad, nk, c0, n, nmom, mu); continue; }
                 const int splits = bloch_splits(T.maxcnt[(size_t)g * RC.nlev + level]);
                 for (int m0 = 0; m0 < mpad; m0 += BLOCH_MCHUNK) {
                     const int mrows = std::min(BLOCH_MCHUNK, mpad - m0), q0 = m0 / 2, nq = std::min(nk - q0, mrows / 2);
@@ -3543,37 +3538,7 @@ int run_bloch(rsrec_t* h, const BlochCall& A) {
             }
             bloch_ev.emplace_back(e0, next_event(h));
         };
-        if (MFMA) k_seed<LayoutCI><<<nb, 64, 0, h->stream>>>(p0, velems, h->d_seed.as<int>(), h->d_seedcoef.as<double2>(), 1);
-        else k_seed<L><<<nb, 64, 0, h->stream>>>(p0, velems, h->d_seed.as<int>(), h->d_seedcoef.as<double2>(), 1);
-        bloch_pass(p0, 0, 0);
-        const dim3 grid(nblk, nb);
-        for (int t = 1; t <= napply; ++t) {
-            const bool first = (t == 1);
-            const int lv_final = hoh ? 2 * t : t;
-            double *src = first ? p0 : p1, *dst = first ? p1 : p2;
-            if (MFMA) XFER(apply_h(h, RC, bt, t, src, dst, hps, nullptr, 0, cheb_epilogue(first, src, p0, A.a, A.b)));
-            else {
-                hipEvent_t ev0 = next_event(h);
-                ApplyArgs G{};
-                G.partial = h->d_partial.as<double2>(); G.a = A.a; G.b = A.b;     // (the kernels' Gram partials are written and never read)
-                if (!hoh) {
-                    G.in = src; G.cur = src; G.v0 = p0; G.out = dst; G.level = lv_final;
-                    if (first) k_apply<AM_CHEB1, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
-                    else k_apply<AM_CHEBN, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
-                } else {
-                    G.in = src; G.out = tmp; G.level = 2 * t - 1;
-                    k_apply<AM_STORE, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
-                    G.in = tmp; G.v1 = tmp; G.cur = src; G.v0 = p0; G.out = dst; G.level = lv_final;
-                    if (first) k_apply<AM_HOH_CHEB1, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
-                    else k_apply<AM_HOH_CHEBN, L><<<grid, NTHREADS, 0, h->stream>>>(RC.P, CV, G);
-                }
-                RC.hop_ev.emplace_back(ev0, next_event(h)); h->n_hop_launch += hoh ? 2 : 1;
-            }
-            bloch_pass(dst, lv_final, t);
-            if (!first) { double* o = p0; p0 = p1; p1 = p2; p2 = o; }
-        }
-        HIPCK(h, hipGetLastError());
-        HIPCK(h, hipStreamSynchronize(h->stream));               // the next batch's uploads reuse the seeds and the lists
+        XFER(chain_level_loop(h, RC, bt, A.a, A.b, bloch_pass));   // (it ends idle: the next batch's uploads reuse the lists too)
     }
     if (A.s_k) XFER(xfer_d2h(h, A.s_k, mu, nimg * mstride * sizeof(double2)));
     const int rc = recursion_end(h, RC, 2, A.lld, false);
@@ -3620,8 +3585,7 @@ extern "C" int rsrec_chebyshev_bloch(rsrec_t* h, int nsrc, const int32_t* source
     HIPCK(h, hipSetDevice(h->device));
     reset_timing(h);
     if (nsrc == 0) return RSREC_OK;
-    if (h->opt_kernels != 1 && h->s5_built) return run_bloch<LayoutRM, true>(h, A);
-    return run_bloch<LayoutCM, false>(h, A);
+    return matrix_core_set(h) ? run_bloch<true>(h, A) : run_bloch<false>(h, A);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -4513,7 +4477,7 @@ extern "C" int rsrec_orbital_moments(rsrec_t* h, int nseeds, const int32_t* seed
         }
     }
     XFER(whole_lattice_end(h, W));
-    h->res_kind = 0; h->spec_res.nop = 0;
+    drop_resident(h);
     return RSREC_OK;
 }
 

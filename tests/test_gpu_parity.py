@@ -67,6 +67,19 @@ def test_chebyshev_golden(name, kernels):
     rec.close()
 
 
+@pytest.mark.parametrize("name", CHEB_CASES)
+def test_chebyshev_golden_unfused(name):
+    """k_spmm5 on CI vectors with cheb_fused = 0: the SpMM leaves plain H psi and k_mfma_cheb forms the new vector."""
+    g = load_golden(name)
+    rec = make(problem_dict(g), g["irec"], g["lld"], nsp=g["nsp"], emin=g["emin"], emax=g["emax"])
+    rec.set_option("kernels", 2)
+    rec.set_option("spmm5", 2)
+    rec.set_option("cheb_fused", 0)
+    rec.chebyshev_recur()
+    assert rel_err(rec.mu_n[:, :, :, : g["nrec"]], g["mu_n"]) < RTOL
+    rec.close()
+
+
 @pytest.mark.parametrize("name", SCALAR_CASES)
 def test_scalar_lanczos_golden(name):
     g = load_golden(name)
