@@ -160,7 +160,7 @@ template <class T> __device__ __forceinline__ void st_stream(T* p, T v) {
 // ---- A_n Gram folded into k_spmm5's epilogue (kernels_spmm5.hpp, S5Gram) --------------------------------------------------
 // One partial of S5_GRAM_DOUBLES per (chain, group of the chain's H|psi> list, output spin).  Which (chain, level) passes fold is this one
 // rule on the chain's group count at that level: k_spmm5, k_mfma_adot, k_gram_groupsum and the host all ask it.
-constexpr int S5_GRAM_DOUBLES = 584;
+constexpr int S5_GRAM_DOUBLES = 328;   // S 256, strips 64, corner 8 (kernels_spmm5.hpp, S5Gram)
 constexpr long S5_GRAM_MIN_NEVER = 1L << 40;   // a group count no region reaches
 constexpr int S5_GRAM_MAXW = 8;        // workgroups of k_gram_groupsum per chain, at most (= the 36x36 images it fills)
 __host__ __device__ inline bool s5_gram_folds(long ngroups, long min_groups) { return ngroups > 0 && ngroups >= min_groups; }
@@ -169,12 +169,13 @@ __host__ __device__ inline int s5_gram_workgroups(int ngroups) { return ngroups 
 struct GramFold { const int* cum = nullptr; int nlev = 0; long min_groups = 0; };     // cum: the counts of the H|psi> lists, [chain][nlev]; nullptr: nothing folds
 
 // Fixed-order sum of a folded chain's partials: workgroup w of nw = s5_gram_workgroups(ngroups) adds the groups [w ngroups / nw,
-// (w + 1) ngroups / nw), both spins of a group one after the other, one thread per entry; completes the matrix -- G[a < 16][16 + e] =
-// conj(G[16 + e][a]), exact for the summed matrix of a Hermitian operator and linear, so applied to every workgroup's share -- and writes
+// (w + 1) ngroups / nw), both spins of a group one after the other, one thread per entry; completes the matrix -- Re G[a][b] = (S[a][b] +
+// S[b][a]) / 2 and Im G[a][b] = (S[a][b] - S[b][a]) / 2 for a, b < 16, G[a < 16][16 + e] = conj(G[16 + e][a]): exact for the summed matrix
+// of a Hermitian operator and linear, so applied to every workgroup's share -- and writes
 // the canonical 36x36 real image (CI columns) into slot w of the chain's k_mfma_adot partials: Re G -> [re a][re b], Im G -> [re a][im b],
 // the two other quadrants zero, so that reduce_gram finds C = G.  The remaining slots of the launch (gridDim.x of them per chain) are
 // zeroed: the reducers add them as +0.  At most S5_GRAM_MAXW <= 16 images, so k_presum16's first chunk is the same sequential sum.
-__global__ __launch_bounds__(640) void k_gram_groupsum(GramFold F, int level, const double* __restrict__ gpart, size_t cstride, double* __restrict__ partial /*[chain][gridDim.x][1296]*/) {
+__global__ __launch_bounds__(384) void k_gram_groupsum(GramFold F, int level, const double* __restrict__ gpart, size_t cstride, double* __restrict__ partial /*[chain][gridDim.x][1296]*/) {
     __shared__ double sm[S5_GRAM_DOUBLES];
     const int chain = blockIdx.y, w = blockIdx.x;
     const int ngroups = F.cum[(size_t)chain * F.nlev + level] / GROUP;
@@ -205,10 +206,13 @@ __global__ __launch_bounds__(640) void k_gram_groupsum(GramFold F, int level, co
         const int r = e / 36, c = e - 36 * r, a = r >> 1, b = c >> 1, part = c & 1;
         double v = 0.0;
         if ((r & 1) == 0) {
-            if (a < 16 && b < 16) v = sm[256 * part + 4 * (16 * (a & 3) + b) + (a >> 2)];
-            else if (a >= 16 && b < 16) v = sm[512 + 2 * (16 * (a - 16) + b) + part];
-            else if (a >= 16) v = sm[576 + 2 * (2 * (a - 16) + (b - 16)) + part];
-            else { const double t = sm[512 + 2 * (16 * (b - 16) + a) + part]; v = part ? -t : t; }
+            if (a < 16 && b < 16) {
+                const double sab = sm[4 * (16 * (a & 3) + b) + (a >> 2)], sba = sm[4 * (16 * (b & 3) + a) + (b >> 2)];
+                v = 0.5 * (part ? sab - sba : sab + sba);
+            }
+            else if (a >= 16 && b < 16) v = sm[256 + 2 * (16 * (a - 16) + b) + part];
+            else if (a >= 16) v = sm[320 + 2 * (2 * (a - 16) + (b - 16)) + part];
+            else { const double t = sm[256 + 2 * (16 * (b - 16) + a) + part]; v = part ? -t : t; }
         }
         img[e] = v;
     }

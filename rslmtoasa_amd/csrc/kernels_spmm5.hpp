@@ -751,13 +751,16 @@ struct S5Epilogue { int kind = 0; const double* cur = nullptr; const double* old
 // A_n Gram in the epilogue (GRAM; kind 0, one input, whole groups): G = sum_atoms u^H t' with t' = H u still in the accumulators and the
 // own-atom block of u read back from the input vector.  A wave forms the partial of its (group, output spin) over the eight atoms in tile
 // order and writes it to out[chain][group index in the chain's list][spin][S5_GRAM_DOUBLES]:
-//   [0, 256)   Re G[a][b], a, b < 16, as the 16x16x4 result registers lie: double 4 lane + j = row a = (lane >> 4) + 4 j, column b = lane & 15
-//   [256, 512) Im G[a][b], likewise
-//   [512, 576) G[16 + e][b], b < 16: complex at 2 (16 e + b)
-//   [576, 584) G[16 + e'][16 + e]:   complex at 2 (2 e' + e)
-// G[a < 16][16 + e] is never formed: G is Hermitian when H is, and k_gram_groupsum completes the summed matrix from the strip (the
-// partial of one group is NOT Hermitian -- H couples the groups and the spins).  The ninth tile (columns 16, 17 of eight different atoms)
-// would need per-atom operands for those entries; as it is it only feeds the 2x2 corner.
+//   [0, 256)   S[a][b] = Re G[a][b] + Im G[a][b], a, b < 16, as the 16x16x4 result registers lie: double 4 lane + j = row a =
+//              (lane >> 4) + 4 j, column b = lane & 15.  S = (Ur - Ui)^T Tr + (Ur + Ui)^T Ti: one accumulator and half the MFMAs of
+//              Re G = Ur^T Tr + Ui^T Ti and Im G = Ur^T Ti - Ui^T Tr apart; the operand sums are formed on the u side, t' is untouched
+//   [256, 320) G[16 + e][b], b < 16: complex at 2 (16 e + b)
+//   [320, 328) G[16 + e'][16 + e]:   complex at 2 (2 e' + e)
+// G is Hermitian when H is (the fold serves only operators that passed the host's Hermiticity check), so of the summed matrix Re G is
+// symmetric and Im G antisymmetric: Re G = (S + S^T) / 2, Im G = (S - S^T) / 2 hold one tile of information, not two, and
+// G[a < 16][16 + e] = conj(G[16 + e][a]) is never formed.  k_gram_groupsum applies both to the summed matrix (the partial of one group is
+// NOT Hermitian -- H couples the groups and the spins -- but the identities are linear).  The ninth tile (columns 16, 17 of eight
+// different atoms) would need per-atom operands for the strip entries; as it is it only feeds the 2x2 corner.
 // Which (chain, level) passes fold is ONE rule on the chain's group count at that level (the count of the H|psi> list), the same for
 // k_spmm5, k_mfma_adot (which leaves a folded chain alone), k_gram_groupsum and the host.
 // (S5_GRAM_DOUBLES, s5_gram_folds and k_gram_groupsum: kernels_mfma.hpp, beside k_mfma_adot.)
@@ -1105,8 +1108,9 @@ __global__ __launch_bounds__(NSP == 3 ? 768 : S5_WG_GROUPS * 128) void k_spmm5(S
             }
         };
         // The Gram epilogue (see S5Gram): result register j of tile t < 8 is the B operand of k-step j of a 16x16x4 whose A operand is the
-        // own-atom element of u at the same (m, c = l15) -- its part matching the row for Re G, (-Ui, Ur) for Im G; the remainder register
-        // (re, im of m = 8, two padding rows) is a fifth k-step.  Rows 16, 17 of G and the corner on the vector pipe from the same registers.
+        // own-atom element of u at the same (m, c = l15) -- Ur - Ui against a real row and Ur + Ui against an imaginary one, for S = Re G +
+        // Im G; the remainder register (re, im of m = 8, two padding rows) is a fifth k-step.  Rows 16, 17 of G and the corner on the vector
+        // pipe from the same registers.
         // Tiles in order, a few at a time: their operands live in the registers of the dead operand sets.
         bool stored = false;                                // the Gram epilogue issued the group's result stores (`finish`) itself
         if constexpr (GRAM) if (fold) {
@@ -1116,7 +1120,7 @@ __global__ __launch_bounds__(NSP == 3 ? 768 : S5_WG_GROUPS * 128) void k_spmm5(S
             asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(gl));
             const int lane = (int)gl, l15 = lane & 15, l4 = lane >> 4;
             const double* __restrict__ ub = in_all + vo;
-            double4_t gre = {0, 0, 0, 0}, gim = {0, 0, 0, 0};
+            double4_t gs = {0, 0, 0, 0};                        // S = Re G + Im G of the 16x16 block (see S5Gram)
             double sre[2] = {0.0, 0.0}, sim[2] = {0.0, 0.0}, kre[2] = {0.0, 0.0}, kim[2] = {0.0, 0.0};
             // this lane's coefficients of the remainder row: l4 = 0 holds Re t'(m = 8), l4 = 1 Im t'(m = 8), l4 >= 2 padding
             auto rem_coef = [&](s5_d2 u, double& cr, double& ci) {
@@ -1129,17 +1133,17 @@ __global__ __launch_bounds__(NSP == 3 ? 768 : S5_WG_GROUPS * 128) void k_spmm5(S
             // takes its own from lane 2 t of the row, one (p, e) pair at a time: 33 loads per epilogue instead of 81, 12 operand
             // registers per tile instead of 36, and with that four tiles per round of loads -- two round trips instead of five.
             constexpr bool STRIP_LOADS = RSREC_S5_GRAM_STRIP_LOADS != 0;
-            auto strip_loads = [&](s5_d2 (&gs)[3][2], const double* ab) {
+            auto strip_loads = [&](s5_d2 (&gst)[3][2], const double* ab) {
 #pragma unroll
                 for (int p = 0; p < 3; ++p)
 #pragma unroll
-                    for (int e = 0; e < 2; ++e) gs[p][e] = *reinterpret_cast<const s5_d2*>(ab + 36 * (p < 2 ? 4 * p + l4 : 8) + 32 + 2 * e);
+                    for (int e = 0; e < 2; ++e) gst[p][e] = *reinterpret_cast<const s5_d2*>(ab + 36 * (p < 2 ? 4 * p + l4 : 8) + 32 + 2 * e);
             };
             s5_d2 gs8[3][2];
             if constexpr (!STRIP_LOADS) strip_loads(gs8, ub + (size_t)BLD * my_rem_atom + 324 * sig);
             auto gram_tiles = [&](auto t0c, auto t1c) {
                 constexpr int T0 = decltype(t0c)::value, T1 = decltype(t1c)::value, NT = T1 - T0;
-                s5_d2 gu[NT][3], gs[STRIP_LOADS ? NT : 1][3][2];
+                s5_d2 gu[NT][3], gst[STRIP_LOADS ? NT : 1][3][2];
 #pragma unroll
                 for (int i = 0; i < NT; ++i) {
                     const int t = T0 + i;
@@ -1147,7 +1151,7 @@ __global__ __launch_bounds__(NSP == 3 ? 768 : S5_WG_GROUPS * 128) void k_spmm5(S
 #pragma unroll
                     for (int p = 0; p < 3; ++p)
                         if (t < 8) gu[i][p] = *reinterpret_cast<const s5_d2*>(ab + 36 * (p < 2 ? 4 * p + l4 : 8) + 2 * l15);
-                    if constexpr (STRIP_LOADS) strip_loads(gs[i], ab);
+                    if constexpr (STRIP_LOADS) strip_loads(gst[i], ab);
                 }
                 // the result stores of the group between the first round's loads and their use: they wait for nothing, and the next group's
                 // first operands then do not queue behind them (measured: DESIGN section 3)
@@ -1164,18 +1168,16 @@ __global__ __launch_bounds__(NSP == 3 ? 768 : S5_WG_GROUPS * 128) void k_spmm5(S
                     if constexpr (t < 8) {
 #pragma unroll
                         for (int p = 0; p < 2; ++p) {
-                            gre = __builtin_amdgcn_mfma_f64_16x16x4f64(gu[i][p][0], acc.m[t][2 * p], gre, 0, 0, 0);
-                            gre = __builtin_amdgcn_mfma_f64_16x16x4f64(gu[i][p][1], acc.m[t][2 * p + 1], gre, 0, 0, 0);
-                            gim = __builtin_amdgcn_mfma_f64_16x16x4f64(-gu[i][p][1], acc.m[t][2 * p], gim, 0, 0, 0);
-                            gim = __builtin_amdgcn_mfma_f64_16x16x4f64(gu[i][p][0], acc.m[t][2 * p + 1], gim, 0, 0, 0);
+                            const double um = gu[i][p][0] - gu[i][p][1], up = gu[i][p][0] + gu[i][p][1];
+                            gs = __builtin_amdgcn_mfma_f64_16x16x4f64(um, acc.m[t][2 * p], gs, 0, 0, 0);
+                            gs = __builtin_amdgcn_mfma_f64_16x16x4f64(up, acc.m[t][2 * p + 1], gs, 0, 0, 0);
                         }
                         double cr, ci;
                         rem_coef(gu[i][2], cr, ci);
-                        gre = __builtin_amdgcn_mfma_f64_16x16x4f64(cr, x8, gre, 0, 0, 0);
-                        gim = __builtin_amdgcn_mfma_f64_16x16x4f64(ci, x8, gim, 0, 0, 0);
+                        gs = __builtin_amdgcn_mfma_f64_16x16x4f64(cr + ci, x8, gs, 0, 0, 0);
                     }
                     auto strip = [&](int p, int e) -> s5_d2 {
-                        if constexpr (STRIP_LOADS) return gs[i][p][e];
+                        if constexpr (STRIP_LOADS) return gst[i][p][e];
                         else if constexpr (t < 8) return s5_row_bcast<2 * t>(gs8[p][e]);
                         else return gs8[p][e];
                     };
@@ -1235,17 +1237,15 @@ __global__ __launch_bounds__(NSP == 3 ? 768 : S5_WG_GROUPS * 128) void k_spmm5(S
             s5_d2 v;
 #pragma unroll
             for (int p = 0; p < 2; ++p) {
-                v[0] = gre[2 * p]; v[1] = gre[2 * p + 1];
+                v[0] = gs[2 * p]; v[1] = gs[2 * p + 1];
                 *reinterpret_cast<s5_d2*>(gp + 4 * lane + 2 * p) = v;
-                v[0] = gim[2 * p]; v[1] = gim[2 * p + 1];
-                *reinterpret_cast<s5_d2*>(gp + 256 + 4 * lane + 2 * p) = v;
             }
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
                 v[0] = sum_l4(sre[e]); v[1] = sum_l4(sim[e]);
-                if (l4 == e) *reinterpret_cast<s5_d2*>(gp + 512 + 2 * (16 * e + l15)) = v;
+                if (l4 == e) *reinterpret_cast<s5_d2*>(gp + 256 + 2 * (16 * e + l15)) = v;
                 v[0] = sum_atoms(sum_l4(kre[e])); v[1] = sum_atoms(sum_l4(kim[e]));
-                if (lane < 2) *reinterpret_cast<s5_d2*>(gp + 576 + 2 * (2 * e + lane)) = v;
+                if (lane < 2) *reinterpret_cast<s5_d2*>(gp + 320 + 2 * (2 * e + lane)) = v;
             }
         }
         if (!stored) {

@@ -1822,7 +1822,7 @@ int run_block_lanczos(rsrec_t* h, int nchains, int nseed, const int32_t* seed_at
                                  folds ? S5Gram{h->d_gram.as<double>(), gram_cstride, h->opt_s5_gram_min} : S5Gram()));
                     const dim3 gl = level_grid(h, bt.grid_mf, lv_final);
                     if (folds < 2) k_mfma_adot<<<gl, MF_WAVES * 64, 0, h->stream>>>(CVp, lv_final, kk, psi, hpsi, gpartial, GF);
-                    if (folds) k_gram_groupsum<<<gl, 640, 0, h->stream>>>(GF, lv_final, h->d_gram.as<double>(), gram_cstride, gpartial);
+                    if (folds) k_gram_groupsum<<<gl, 384, 0, h->stream>>>(GF, lv_final, h->d_gram.as<double>(), gram_cstride, gpartial);
                     int n2 = gl.x; const double* p2 = presum(h, gpartial, nb, n2, 1296);
                     XFER(side_reduce_wait(h, SR));
                     k_reduce_a_u<<<nb, 1024, 0, h->stream>>>(p2, n2, dA + (size_t)ll * BLK, cstride, h->d_bmats.as<double2>(), bfrags, ci);
