@@ -41,9 +41,11 @@ __host__ __device__ constexpr int gram_col(int part, int c, int ci) { return ci 
 // XCD has its own 4 MiB L2.  Every psi block is read by ~15 neighbouring atoms, so groups that are close in the region order
 // must run on the SAME XCD for those re-reads to hit L2: XCD x owns the contiguous chunk x of the group list and its resident
 // workgroups sweep that chunk as a sliding window.  Placement only affects speed, never results.
-// Workgroups that take part in a (chain, level) pass: a function of that chain's group count only, so that the work
-// assignment and the order of the partial sums do not depend on which chains share a launch (batch-size reproducibility);
-// the launch itself is sized by the largest chain of the batch and surplus workgroups leave at once.
+// Workgroups that take part in a (chain, level) pass: a function of that chain's group count only (inside one band of
+// mfma_workgroups_per_chain, which caps gridDim.x), so that the work assignment does not depend on which chains share a launch;
+// the launch itself is sized by the largest chain of the batch and surplus workgroups leave at once, their partials all zero.
+// The ORDER in which a chain's partials are then summed is sum_partials16's (below), whichever route they take to the reducer:
+// together the two make a chain's results independent of the batch it runs in (tests/test_gpu_batch_composition.py).
 __device__ __forceinline__ int active_workgroups(int ngroups) { return max(1, min((int)gridDim.x, (ngroups + MF_WAVES - 1) / MF_WAVES)); }
 
 struct GroupWalk {
@@ -277,13 +279,25 @@ struct SpmmDims {
 };
 
 // ---- reductions of the 36x36 real partials ----------------------------------------------------------------------------
+// The ONE order in which a chain's partials are summed, whoever reads them: blocks of 16 in index order, then the block sums in index order.
+// This is k_presum16 followed by a sequential sum of its (at most 16) outputs, so a reducer that reads the partials themselves and one that
+// reads their presums do the same arithmetic, and all-zero partials behind a chain's own (the launch is sized by the largest chain of the
+// batch) add +0: the order depends on that chain's partial count alone, not on the launch width, on whether k_presum16 ran, or on which
+// chains share the call (tests/test_gpu_batch_composition.py).  Up to 16 partials it is the plain sequential sum.
+__device__ __forceinline__ double sum_partials16(const double* __restrict__ p /*element of partial 0*/, int nblk, size_t stride) {
+    double s = 0.0;
+    for (int p0 = 0; p0 < nblk; p0 += 16) {
+        const int p1 = min(nblk, p0 + 16);
+        double b = 0.0;
+        for (int q = p0; q < p1; ++q) b += p[(size_t)q * stride];
+        s += b;
+    }
+    return s;
+}
+
 // returns C[cp + 18 c] (complex) for tid < 324:  C_re = G[re cp][re c] + G[im cp][im c],  C_im = G[re cp][im c] - G[im cp][re c]
 __device__ __forceinline__ double2 reduce_gram(const double* __restrict__ partial /*[nblk][1296]*/, int nblk, double* lds /*1296*/, int ci = 0) {
-    for (int e = threadIdx.x; e < 1296; e += blockDim.x) {
-        double s = 0.0;
-        for (int p = 0; p < nblk; ++p) s += partial[(size_t)p * 1296 + e];
-        lds[e] = s;
-    }
+    for (int e = threadIdx.x; e < 1296; e += blockDim.x) lds[e] = sum_partials16(partial + e, nblk, 1296);
     __syncthreads();
     double2 c = make_double2(0, 0);
     if (threadIdx.x < BLK) {

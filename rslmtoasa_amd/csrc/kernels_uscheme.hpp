@@ -494,9 +494,7 @@ __global__ __launch_bounds__(1024) void k_reduce_cheb_mf(const double* __restric
     const double* P = partial + (size_t)chain * nblk * 2 * 1296;
     for (int e = tid; e < 2 * 1296; e += blockDim.x) {
         const int which = e / 1296, k = e % 1296;
-        double s = 0.0;
-        for (int p = 0; p < nblk; ++p) s += P[((size_t)p * 2 + which) * 1296 + k];
-        img[which][k] = s;
+        img[which][k] = sum_partials16(P + (size_t)which * 1296 + k, nblk, 2 * 1296);
     }
     __syncthreads();
     double2* m = mu + chain * mustride;
@@ -527,8 +525,10 @@ __global__ __launch_bounds__(1024) void k_reduce_cheb_mf(const double* __restric
 
 // First stage of the partial-sum reductions: out[chain][b][:] = sum of in[chain][16 b .. 16 b + 15][:] in index order.  The
 // 36x36 Gram partials of up to 256 workgroups per chain (2.6 MB) were summed by ONE workgroup per chain in the reduce kernels:
-// at a single chain that is one CU's L2 bandwidth, 40-100 us per level and half of the single-site recursion.  Fixed grouping
-// (16) and fixed order keep the result independent of launch width and batch composition (trailing all-zero partials add +0).
+// at a single chain that is one CU's L2 bandwidth, 40-100 us per level and half of the single-site recursion.  The grouping (16)
+// and the order are those of sum_partials16 (kernels_mfma.hpp), with which the reduce kernels sum whatever they are handed -- these
+// block sums or, where this stage does not run (launches of up to 32 workgroups, or no room for its output), the partials themselves:
+// the result is the same arithmetic either way, independent of launch width and batch composition (trailing all-zero partials add +0).
 // grid = (nblk2 * ceil(width / 256), chains): one output element per thread, its 16 addends in flight together
 __global__ __launch_bounds__(256) void k_presum16(const double* __restrict__ in, int nblk, int nblk2, int width, double* __restrict__ out) {
     const int nchunk = (width + 255) >> 8;

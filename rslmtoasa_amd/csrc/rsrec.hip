@@ -1116,7 +1116,8 @@ int ensure_side_stream(rsrec_t* h) {
 }
 
 // Partial sums of a batch of B chains: the first stage as the caller sizes it, the second stage (presum) in two slots -- slot 1 is the side
-// stream's -- sized once, never grown mid-stream.  p2_slot decides which reductions take the two-stage path, and with it their rounding.
+// stream's -- sized once, never grown mid-stream.  p2_slot decides which reductions take the two-stage path -- their speed, not their rounding:
+// the reduce kernels sum partials and presums in the same order (sum_partials16).
 int reserve_partials(rsrec_t* h, int B, size_t first_stage_bytes) {
     HIPCK(h, h->d_partial.reserve(first_stage_bytes));
     h->p2_slot = (size_t)B * 16 * 2 * 1296;
@@ -1156,7 +1157,9 @@ int finish_status(rsrec_t* h) {
 // Workgroups per chain of the matrix-core post-hop kernels (Gram, orthogonalisation, Chebyshev step): they hold their 36x36
 // coefficient tables in registers and run one wave per SIMD, so long-lived waves win -- about two workgroups per CU over
 // the whole batch (measured at 64 chains: 8 per chain 4.3 ms per level, 64 per chain 5.0 ms).  Three fixed bands, so that the
-// work assignment (and with it the rounding of the reductions) only changes when the batch size crosses a band.
+// work assignment (and with it the rounding of the reductions) only changes when the batch size crosses a band: inside a band a
+// chain's bits do not depend on the other chains of the call (a chain of more than 8 x 4 groups in calls of fewer than 32 chains
+// and of 32 or more does differ: the cap is another one).
 int mfma_workgroups_per_chain(const rsrec_t* h, int batch) {
     if (h->opt_nblk > 0) return (int)std::min<long>(2 * h->opt_nblk, 256);
     return batch >= 32 ? 8 : (batch >= 16 ? 32 : 256);
@@ -1186,7 +1189,9 @@ dim3 s5_grid(const rsrec_t* h, dim3 full, int level) {
     return dim3(gx, (full.y + fold - 1) / fold);
 }
 
-// Two-stage reduction of per-workgroup partials (k_presum16): returns the buffer and count the final reduce kernel reads.
+// Two-stage reduction of per-workgroup partials (k_presum16): returns the buffer and count the final reduce kernel reads.  `nblk` is the
+// launch width, i.e. the LARGEST chain's: whether this stage runs, and either fall-back to the single stage, must not show in any chain's
+// result -- the reduce kernels' sum_partials16 is k_presum16's order applied to whatever they read.
 const double* presum(rsrec_t* h, const double* partial, int nb, int& nblk, int width, hipStream_t stream = nullptr, int slot = 0) {
     if (nblk <= 32) return partial;
     const int nblk2 = (nblk + 15) / 16;
