@@ -420,6 +420,18 @@ module rsrec_binding
          integer(c_int) :: rc
       end function
 
+      !> seed_atoms: int32 (nseed,nchains), 0 = unused entry; seed_coef: complex (nseed,nchains); group: int32 (kk) or c_null_ptr;
+      !> m_g: complex (18,18,2*lld+2,ngroup,nchains), host or device memory, or c_null_ptr
+      function rsrec_chebyshev_lattice(handle, nchains, nseed, seed_atoms, seed_coef, lld, a, b, ngroup, group, m_g) &
+         bind(C, name='rsrec_chebyshev_lattice') result(rc)
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: handle
+         integer(c_int), value :: nchains, nseed, lld, ngroup
+         real(c_double), value :: a, b
+         type(c_ptr), value :: seed_atoms, seed_coef, group, m_g
+         integer(c_int) :: rc
+      end function
+
       function rsrec_scalar_lanczos(handle, nsites, seed_atoms, lld, llmax, a, b2) bind(C, name='rsrec_scalar_lanczos') result(rc)
          import :: c_int, c_ptr
          type(c_ptr), value :: handle

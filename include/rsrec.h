@@ -327,6 +327,46 @@ int rsrec_chebyshev_pairs_direct(rsrec_t *h, int npairs, const int32_t *ijpair, 
 int rsrec_chebyshev_bloch(rsrec_t *h, int nsrc, const int32_t *sources, int lld, double a, double b, const double *cr, const double *cell,
                           int nk, const double *kpt, int ngroup, const int32_t *group, double *s_k);
 
+/* Chebyshev moments from whole-lattice seeds (no counterpart in the reference).  rsrec_chebyshev_pairs_direct and rsrec_chebyshev_bloch start
+ * every chain from ONE atom -- right for a perfect crystal, where every source gives the same answer.  Here the seed covers the lattice,
+ * |x> = sum_j c_j |j> (x) 1_18, and the moment is the seed-weighted sum of the vector's own blocks, group by group:
+ *   M_g(n) = sum_{j in group g} conj(c_j) [T_n(H~) x]_j = <x| P_g T_n(H~) |x>,   H~ = (H - b)/a.
+ *   - plane-wave seeds c_j = exp(+i k.r_j)/sqrt(kk): sum_g M_g(n) is the average over ALL sources i of rsrec_chebyshev_bloch's S_i(k, n) -- the
+ *     effective (unfolded) band structure of a disordered supercell, resolved by atom type or layer through `group`, from one chain per
+ *     k-point instead of kk;
+ *   - random-phase seeds (the vectors cond_calctype = 'random_vec' draws): M_g(n) is the stochastic trace over the atoms of g -- the DOS and
+ *     the operator spectra of the whole cell by type, on the vectors a conductivity run uses;
+ *   - a seed on one atom i with coefficient 1: M is the chain's own block M_ii(n) of rsrec_chebyshev_pairs_direct.
+ *   seed_atoms : int32 (nseed,nchains), 1-based, 0 = unused entry;  seed_coef : complex (nseed,nchains).  1 <= nseed <= kk.  The seed is
+ *                placed exactly as rsrec_kubo_moments places its vectors (entries in order: of several on one atom the last one stays), and
+ *                the projection weight of an atom is the conjugate of the coefficient actually placed there.
+ *   a, b, lld  : as rsrec_chebyshev_pairs_direct: the three-term recurrence, 2*lld+1 applications of H~, orders n = 1 .. 2*lld+2 (order 1 is
+ *                the seed itself).  A projected moment has no doubling identity (P_g does not commute with H): one layout serves every use.
+ *   group      : int32 (kk), values 0..ngroup, 0 = the atom is left out; NULL with ngroup = 1: every atom in group 1.
+ *                1 <= ngroup <= RSREC_LATTICE_NGROUP_MAX.
+ *   m_g        : complex (18,18,2*lld+2,ngroup,nchains) out, host or device memory (detected), or NULL (nothing is downloaded).
+ * The image stays resident exactly as a rsrec_chebyshev call of nchains*ngroup sites of depth lld leaves its moments, image index
+ * (g-1) + ngroup*(c-1): rsrec_chebyshev_ldos, rsrec_chebyshev_spectra, rsrec_pack_moments and rsrec_spectra_integrals follow unchanged, called
+ * with nsites_total >= that count.  The LDOS stage reads the REAL PART OF THE DIAGONAL of an image: for a single group that is the
+ * symmetrised group weight (P_g delta + delta P_g)/2 -- M_g itself is not Hermitian, only the sum over the groups is.
+ * Normalisation: with |c_j|^2 = 1/kk the first moment has tr M_g(1) = 18 N_g/kk (N_g atoms in group g); the caller divides.
+ * Every product runs over the WHOLE lattice from order 0 (one k_spmm5 launch per order, two with hoh; there is no growing region), so a
+ * sparse seed pays for the whole lattice and gains nothing over the one-atom calls above.  Behind the seed and every product one projection
+ * pass reads the blocks of the grouped seeded atoms once (kernels_lattice.hpp).  Up to 8 chains advance together as the chains of one
+ * launch (option lattice_vbatch), fewer if the work vectors do not fit.  Both kernel sets (option kernels), hoh and per-atom operator
+ * blocks are served.
+ * Every sum runs in a fixed order without atomics: the bits of an image depend on its own chain and on the atom set of its own group alone
+ * -- not on the other chains of the call or their order, on the other groups' membership, on lattice_vbatch, or on what earlier calls left
+ * in the work buffers.
+ * RSREC_ERR_DIVERGED if for any chain and order sum_g sum(real(M_g(n))) > 1000 max(1, sum_j |c_j|^2): the sums the call forms anyway (a
+ * diverging recurrence grows wherever the vector is non-zero).  RSREC_ERR_ARG with a message, the handle staying usable, for: ngroup out
+ * of range; a group value outside 0..ngroup; NULL group with ngroup > 1; a seed atom outside 0..kk; nseed out of range; a chain without
+ * any seed; NULL seeds with nchains > 0; nchains < 0; lld < 1; a == 0.  nchains = 0 returns RSREC_OK.
+ * rsrec_get_timing: out[0] device ms, out[1] ms in the H|psi> launches, out[2] their number, out[5] ms in the projection kernels alone. */
+#define RSREC_LATTICE_NGROUP_MAX 16
+int rsrec_chebyshev_lattice(rsrec_t *h, int nchains, int nseed, const int32_t *seed_atoms, const double *seed_coef, int lld, double a, double b,
+                            int ngroup, const int32_t *group, double *m_g);
+
 /* Stochastic Kubo-Bastin double moments.  Replaces compute_moments_stochastic (recursion.f90:979-1234) together with the
  * whole-vector products it is built from: ham_vec_matmul (:913), ham_hoh_vec_matmul (:785), velo_vec_matmul (:587),
  * velo_hoh_vec_matmul (:656):
@@ -683,6 +723,7 @@ int rsrec_comm_destroy(rsrec_t *h);
  *   "sat_pct"    a chain whose region holds at least this share (per cent) of the lattice runs on the list of ALL atoms instead of its own [100]
  *   "kubo_lchunk" rsrec_kubo_moments / _diag: left vectors held on the device at a time [0 = as many as fit];  "kubo_vbatch" vectors of a call advanced
  *                together as the chains of every launch [0 = up to 8, as many as fit beside a whole left matrix each]
+ *   "lattice_vbatch" rsrec_chebyshev_lattice: chains of a call advanced together as the chains of every launch [0 = up to 8, as many as fit]
  *   "kubo_setgroup" rsrec_kubo_moments_diag_tensor: sets of a vector contracted against one staged tile of left vectors; 1 = every set by itself,
  *                2 / 3 = groups of at most that width [0 = 2] */
 int rsrec_set_option(rsrec_t *h, const char *key, long value);

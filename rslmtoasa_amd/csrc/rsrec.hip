@@ -49,6 +49,7 @@
 #include "kernels_assemble.hpp"
 #include "kernels_fan.hpp"
 #include "kernels_bloch.hpp"
+#include "kernels_lattice.hpp"
 
 using namespace rsrec;
 
@@ -146,6 +147,7 @@ struct rsrec_handle {
     DevBuf d_frags, d_vec[6], d_partial, d_partial2, d_coefA, d_coefB, d_bmats, d_status, d_seed, d_seedcoef, d_mu, d_scal, d_zsqr;
     DevBuf d_fan, d_fan_tab, d_mpair;   // rsrec_chebyshev_pairs_direct: gathered blocks M(18,18,nmom,entry); entry and pair tables; M_ij / M_ji of every pair
     DevBuf d_bloch_geo, d_bloch_tab;    // rsrec_chebyshev_bloch: positions and k-points of the call; lists, segment offsets and level counts of a batch
+    DevBuf d_lat_tab, d_lat_w, d_lat_part;   // rsrec_chebyshev_lattice: lists and offsets of a batch; weights and divergence bounds; split partials
     // options
     long opt_batch = 0, opt_kernels = 0, opt_nblk = 0, opt_spmm5 = 2, opt_chain_fold = 1, opt_s5_cap = 0, opt_side = 1, opt_s5_lds = 1, opt_s5_queue = 1, opt_cheb_fused = 1;
     long opt_s5_waves = 8;
@@ -158,6 +160,7 @@ struct rsrec_handle {
     long opt_s5_host_emit = 0;   // 1: swizzle k_spmm5's operator streams on the host (round-2 path) instead of assembling them on the device
     long opt_kubo_lchunk = 0;    // rsrec_kubo_moments: left vectors held at a time (0: as many as fit)
     long opt_kubo_vbatch = 0;    // rsrec_kubo_moments: random vectors advanced together as the chains of one launch (0: up to 8, as many as fit beside a whole left matrix)
+    long opt_lattice_vbatch = 0; // rsrec_chebyshev_lattice: chains advanced together as the chains of one launch (0: up to 8, as many as fit)
     long opt_kubo_setgroup = 0;  // rsrec_kubo_moments_diag_tensor: sets of a vector contracted against one staged left tile (k_kubo_gram_diag_sets): 0 default (2), 1 every set by itself (k_kubo_gram_diag), 2 / 3 groups of at most that width
     int n_kubo_left_chunks = 0;
     int kubo_diag_nvec = 0, kubo_diag_ll = 0;   // rsrec_kubo_moments_diag / _multi / _tensor: the call whose diagonal moments lie in d_kubo[4] (0: nothing resident; _multi: nvec * nout; _tensor: nvec * nout * nin)
@@ -248,6 +251,7 @@ const OptionEntry OPTIONS[] = {
     {"kubo_lchunk", &rsrec_handle::opt_kubo_lchunk},
     {"kubo_vbatch", &rsrec_handle::opt_kubo_vbatch},
     {"kubo_setgroup", &rsrec_handle::opt_kubo_setgroup},
+    {"lattice_vbatch", &rsrec_handle::opt_lattice_vbatch},
     {"s5_host_emit", &rsrec_handle::opt_s5_host_emit},
     {"s5_octet", &rsrec_handle::opt_s5_octet},
     {"s5_spin_xcd", &rsrec_handle::opt_s5_spin_xcd},
@@ -3679,14 +3683,15 @@ struct WholeLatticeCall {
 };
 
 // The list of all atoms as the one region (cached like every region) and the launch shape for a full batch of `chains_per_slot` chains.
-int whole_lattice_begin(rsrec_t* h, WholeLatticeCall& W, int chains_per_slot, bool timed) {
+// `grouped`: the list padded into operator-class groups of 8, as k_spmm5 walks it (false: the VALU set's k_apply, rsrec_chebyshev_lattice).
+int whole_lattice_begin(rsrec_t* h, WholeLatticeCall& W, int chains_per_slot, bool timed, bool grouped = true) {
     const int kk = h->kk;
     const size_t velems = (size_t)(kk + 1) * BLD;
     std::vector<int> all(kk);
     for (int i = 0; i < kk; ++i) all[i] = i;
     int ostride = kk;
     double dummy1 = 0, dummy2 = 0;
-    XFER(upload_regions(h, all.data(), 1, kk, 1, 1, false, true, ostride, dummy1, dummy2));
+    XFER(upload_regions(h, all.data(), 1, kk, 1, 1, false, grouped, ostride, dummy1, dummy2));
     W.h = h; W.timed = timed;
     chain_views(h, 1, velems, chains_per_slot, ostride, W.CV);
     W.SD = SpmmDims{kk, h->nslots, h->nmax, 1, chains_per_slot, ostride, 0, velems, W.CV.obase, chains_per_slot};
@@ -3760,10 +3765,13 @@ void whole_lattice_apply_v(WholeLatticeCall& W, const Spmm5Operator& vop, const 
 // (n = 0: nothing to do) and T_{n-1}(H~) x in `old`; from n = 2 on the three buffers rotate, and `spare` is T_{n-2}(H~) x during the launch.
 struct ChebyshevStepper {
     double *old, *cur, *spare;
-    void step(WholeLatticeCall& W, int n, double a, double b) {
-        if (n == 0) return;
+    void rotate(int n) {                 // the buffers of step n >= 1, before its launch
         if (n == 1) std::swap(old, cur);
         else { double* o = spare; spare = old; old = cur; cur = o; }
+    }
+    void step(WholeLatticeCall& W, int n, double a, double b) {
+        if (n == 0) return;
+        rotate(n);
         whole_lattice_apply_h(W, old, cur, cheb_epilogue(n == 1, old, spare, a, b));
     }
 };
@@ -3887,25 +3895,38 @@ int kubo_reserve(rsrec_t* h, KuboPlan& P) {
 
 struct KuboSeeds { int nseed; const int32_t* atoms; const double* coef; };   // the caller's (nvec, nseed) tables; atom 0 = unused entry
 
+// The used entries of vector iv in the caller's order: 0-based atoms and their coefficients (re, im).  k_seed places them in this order, so
+// of several entries on one atom the last one is the coefficient that is placed.
+void whole_vector_seeds(const KuboSeeds& S, int iv, std::vector<int>& s0, std::vector<double>& c0) {
+    s0.clear(); c0.clear();
+    for (int k = 0; k < S.nseed; ++k) {
+        const size_t e = (size_t)iv * S.nseed + k;
+        if (S.atoms[e] == 0) continue;
+        s0.push_back(S.atoms[e] - 1); c0.push_back(S.coef[2 * e]); c0.push_back(S.coef[2 * e + 1]);
+    }
+}
+
+// r_i of vectors iv0 .. iv0 + nb - 1 as the chains of `vec` (cleared by the caller), in layout L: vec(l,l,seed(k)) = coef(k).  What
+// rsrec_kubo_moments and rsrec_chebyshev_lattice (`who`) share; d_seed and d_seedcoef hold nseed entries.
+template <class L>
+int seed_whole_vectors(rsrec_t* h, const char* who, const KuboSeeds& S, int iv0, int nb, double* vec, size_t velems) {
+    std::vector<int> s0; std::vector<double> c0;
+    for (int c = 0; c < nb; ++c) {
+        whole_vector_seeds(S, iv0 + c, s0, c0);
+        if (s0.empty()) return fail(h, RSREC_ERR_ARG, "%s: vector %d has no seed", who, iv0 + c + 1);
+        XFER(xfer_h2d(h, h->d_seed.p, s0.data(), s0.size() * 4));
+        XFER(xfer_h2d(h, h->d_seedcoef.p, c0.data(), c0.size() * 8));
+        k_seed<L><<<1, 64, 0, h->stream>>>(vec + (size_t)c * velems, velems, h->d_seed.as<int>(), h->d_seedcoef.as<double2>(), (int)s0.size());
+        HIPCK(h, hipStreamSynchronize(h->stream));                            // the seed tables are reused by the next vector
+    }
+    return RSREC_OK;
+}
+
 // r_i of vectors iv0 .. iv0 + nb - 1 as the chains of PSIREF: psiref(l,l,seed(k)) = coef(k)
 int kubo_seed_batch(rsrec_t* h, const KuboPlan& P, const KuboSeeds& S, int iv0, int nb) {
     double* psiref = P.vec(KuboPlan::PSIREF);
     HIPCK(h, hipMemsetAsync(psiref, 0, P.sstride * 8, h->stream));
-    for (int c = 0; c < nb; ++c) {
-        const int iv = iv0 + c;
-        std::vector<int> s0; std::vector<double> c0;
-        for (int k = 0; k < S.nseed; ++k) {
-            const size_t e = (size_t)iv * S.nseed + k;
-            if (S.atoms[e] == 0) continue;
-            s0.push_back(S.atoms[e] - 1); c0.push_back(S.coef[2 * e]); c0.push_back(S.coef[2 * e + 1]);
-        }
-        if (s0.empty()) return fail(h, RSREC_ERR_ARG, "rsrec_kubo_moments: vector %d has no seed", iv + 1);
-        XFER(xfer_h2d(h, h->d_seed.p, s0.data(), s0.size() * 4));
-        XFER(xfer_h2d(h, h->d_seedcoef.p, c0.data(), c0.size() * 8));
-        k_seed<LayoutCI><<<1, 64, 0, h->stream>>>(psiref + (size_t)c * P.velems, P.velems, h->d_seed.as<int>(), h->d_seedcoef.as<double2>(), (int)s0.size());
-        HIPCK(h, hipStreamSynchronize(h->stream));                            // the seed tables are reused by the next vector
-    }
-    return RSREC_OK;
+    return seed_whole_vectors<LayoutCI>(h, "rsrec_kubo_moments", S, iv0, nb, psiref, P.velems);
 }
 
 // Left vectors  T_{m-1}(H~) r,  m = m0 .. m0 + lchunk - 1 (recursion.f90:1120-1142), each written by its SpMM into its slot of Lm; the
@@ -4518,6 +4539,190 @@ extern "C" int rsrec_apply_operator(rsrec_t* h, int vel, const double* v_op, con
     XFER(whole_lattice_end(h, W));                        // (the span ends before the download)
     XFER(xfer_d2h(h, psi_out, tmp, nd * 8));
     return RSREC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Chebyshev moments from whole-lattice seeds (kernels_lattice.hpp): the Kubo calls' left recurrence -- WholeLatticeCall + ChebyshevStepper on
+// vectors seeded like theirs -- and behind the seed and every step the projection of the vector on the seed, group by group
+namespace {
+
+struct LatticeCall {
+    int nchains, lld, ngroup;
+    KuboSeeds S;
+    const int32_t* group;
+    double a, b;
+    double* m_g;
+};
+
+// The lists of chains c0 .. c0 + nb - 1 as LatticeLists takes them: per chain the seeded atoms of groups 1 .. ngroup sorted by (group, atom)
+// with the conjugate of the coefficient k_seed leaves there (the last entry on an atom), the groups' segments and partial slots, and the
+// divergence bound 1000 max(1, sum |c|^2) over the placed coefficients, added in atom order.
+struct LatticeBatchLists { std::vector<int> list, seg_off, split_off; std::vector<double> weight, bound; int pstride = 1; };
+void lattice_lists(const rsrec_t* h, const LatticeCall& A, int c0, int nb, LatticeBatchLists& T) {
+    const int kk = h->kk, ng = A.ngroup;
+    T.list.assign((size_t)nb * kk, 0); T.weight.assign((size_t)2 * nb * kk, 0.0);
+    T.seg_off.assign((size_t)nb * (ng + 1), 0); T.split_off.assign((size_t)nb * (ng + 1), 0); T.bound.assign(nb, 0.0);
+    T.pstride = 1;
+    std::vector<int> s0, placed(kk), fill(ng);
+    std::vector<double> cf;
+    for (int c = 0; c < nb; ++c) {
+        whole_vector_seeds(A.S, c0 + c, s0, cf);
+        std::fill(placed.begin(), placed.end(), -1);
+        for (size_t k = 0; k < s0.size(); ++k) placed[s0[k]] = (int)k;
+        int *goff = T.seg_off.data() + (size_t)c * (ng + 1), *soff = T.split_off.data() + (size_t)c * (ng + 1);
+        double norm2 = 0.0;
+        for (int j = 0; j < kk; ++j) {
+            if (placed[j] < 0) continue;
+            norm2 += cf[2 * placed[j]] * cf[2 * placed[j]] + cf[2 * placed[j] + 1] * cf[2 * placed[j] + 1];
+            const int g = A.group ? A.group[j] : 1;
+            if (g > 0) goff[g] += 1;
+        }
+        for (int g = 0; g < ng; ++g) {
+            soff[g + 1] = soff[g] + lattice_splits(goff[g + 1]);
+            fill[g] = goff[g];
+            goff[g + 1] += goff[g];
+        }
+        for (int j = 0; j < kk; ++j) {
+            const int g = A.group ? A.group[j] : 1;
+            if (placed[j] < 0 || g <= 0) continue;
+            const size_t pos = (size_t)c * kk + fill[g - 1]++;
+            T.list[pos] = j; T.weight[2 * pos] = cf[2 * placed[j]]; T.weight[2 * pos + 1] = -cf[2 * placed[j] + 1];
+        }
+        T.pstride = std::max(T.pstride, soff[ng]);
+        T.bound[c] = 1000.0 * std::max(1.0, norm2);
+    }
+}
+
+// The step of ChebyshevStepper with the VALU set's k_apply on LayoutCM vectors, over the list of all atoms (level 0 of the one region):
+// Y.cur = (H old - b old)/a [* 2 - spare]; with hoh h old goes into `tmp` first.  k_apply also writes its Gram partials (d_partial), which
+// nothing reads here.  Every launch between its own events, as whole_lattice_spmm's.
+void lattice_step_valu(WholeLatticeCall& W, ChebyshevStepper& Y, const DevProblem& P, int nblk, int n, double a, double b, double* tmp) {
+    if (n == 0) return;
+    rsrec_t* h = W.h;
+    Y.rotate(n);
+    const bool first = n == 1;
+    const dim3 grid(nblk, W.SD.nchains);
+    ApplyArgs G{};
+    G.partial = h->d_partial.as<double2>(); G.a = a; G.b = b; G.in = Y.old; G.cur = Y.old; G.v0 = first ? Y.old : Y.spare; G.out = Y.cur; G.level = 0;
+    auto timed = [&](auto&& launch) {
+        hipEvent_t e0 = next_event(h);
+        launch();
+        W.hop_ev.emplace_back(e0, next_event(h));
+        W.chain_launches += W.SD.nchains;
+    };
+    if (!h->hoh) {
+        timed([&] { if (first) k_apply<AM_CHEB1, LayoutCM><<<grid, NTHREADS, 0, h->stream>>>(P, W.CV, G); else k_apply<AM_CHEBN, LayoutCM><<<grid, NTHREADS, 0, h->stream>>>(P, W.CV, G); });
+        return;
+    }
+    G.out = tmp;
+    timed([&] { k_apply<AM_STORE, LayoutCM><<<grid, NTHREADS, 0, h->stream>>>(P, W.CV, G); });
+    G.in = tmp; G.v1 = tmp; G.out = Y.cur;
+    timed([&] { if (first) k_apply<AM_HOH_CHEB1, LayoutCM><<<grid, NTHREADS, 0, h->stream>>>(P, W.CV, G); else k_apply<AM_HOH_CHEBN, LayoutCM><<<grid, NTHREADS, 0, h->stream>>>(P, W.CV, G); });
+}
+
+// Matrix-core set: k_spmm5 on CI vectors; VALU set: k_apply on LayoutCM vectors.  Work vectors 0 .. 2: the recurrence; 3 (hoh): h psi.
+template <bool MFMA>
+int run_lattice(rsrec_t* h, const char* who, const LatticeCall& A) {
+    using L = typename std::conditional<MFMA, LayoutCI, LayoutCM>::type;
+    const bool hoh = h->hoh != 0;
+    const int kk = h->kk, ng = A.ngroup, napply = 2 * A.lld + 1, nmom = 2 * A.lld + 2, nvec = hoh ? 4 : 3;
+    const size_t velems = (size_t)(kk + 1) * BLD, mstride = (size_t)nmom * BLK, nimg = (size_t)A.nchains * ng;
+    const size_t pmax = (size_t)kk / LATTICE_SPLIT_ATOMS + ng + 1;                // partial slots a chain can need
+    // the resident image first, the batch is planned from what is left (see run_chebyshev)
+    drop_resident(h);
+    release_kubo_buffers(h, true, true);
+    HIPCK(h, h->d_mu.reserve(nimg * mstride * sizeof(double2)));
+    size_t free_b = 0, total_b = 0, reusable = h->d_lat_tab.bytes + h->d_lat_w.bytes + h->d_lat_part.bytes + (MFMA ? 0 : h->d_partial.bytes + h->d_partial2.bytes);
+    HIPCK(h, hipMemGetInfo(&free_b, &total_b));
+    for (int v = 0; v < nvec; ++v) reusable += h->d_vec[v].bytes;
+    const double per_chain = (double)nvec * velems * 8 + (double)kk * 20 + (double)pmax * BLK * 16 + (MFMA ? 0.0 : 3.0 * 256 * 2 * 1296 * 8) + 4096;
+    const double budget = 0.85 * (double)(free_b + reusable);
+    int nbv = (int)std::min<long>(A.nchains, h->opt_lattice_vbatch > 0 ? std::min<long>(h->opt_lattice_vbatch, 64) : KUBO_CHAINS_MAX);
+    while (nbv > 1 && per_chain * nbv > budget) --nbv;
+    if (per_chain * nbv > budget) return fail(h, RSREC_ERR_DEVICE, "%s: %.1f GB needed for one chain on %d atoms, %.1f GB free", who, per_chain * 1e-9, kk, free_b * 1e-9);
+    for (int v = 0; v < nvec; ++v) HIPCK(h, h->d_vec[v].reserve((size_t)nbv * velems * sizeof(double)));
+    if (!MFMA) XFER(reserve_partials(h, nbv, (size_t)nbv * 256 * 2 * 1296 * sizeof(double)));
+    const int nblk = (int)std::max<long>(1, std::min<long>({h->opt_nblk > 0 ? h->opt_nblk : std::max<long>(2048 / nbv, 16), 256, (kk + TILE_ATOMS - 1) / TILE_ATOMS}));
+    HIPCK(h, h->d_status.reserve(64));
+    HIPCK(h, hipMemsetAsync(h->d_status.p, 0, 64, h->stream));
+    HIPCK(h, h->d_seed.reserve((size_t)A.S.nseed * 4));
+    HIPCK(h, h->d_seedcoef.reserve((size_t)A.S.nseed * sizeof(double2)));
+    const size_t n_list = (size_t)nbv * kk, n_off = (size_t)nbv * (ng + 1);
+    HIPCK(h, h->d_lat_tab.reserve((n_list + 2 * n_off) * sizeof(int)));
+    HIPCK(h, h->d_lat_w.reserve(n_list * sizeof(double2) + (size_t)nbv * sizeof(double)));
+    HIPCK(h, h->d_lat_part.reserve((size_t)nbv * pmax * BLK * sizeof(double2)));
+    int *d_list = h->d_lat_tab.as<int>(), *d_seg = d_list + n_list, *d_split = d_seg + n_off;
+    double2* d_w = h->d_lat_w.as<double2>();
+    double* d_bound = reinterpret_cast<double*>(d_w + n_list);
+    double2* partial = h->d_lat_part.as<double2>();
+    double2* mu = h->d_mu.as<double2>();
+    WholeLatticeCall W;
+    XFER(whole_lattice_begin(h, W, nbv, true, MFMA));
+    W.hps = hoh ? h->d_vec[3].as<double>() : nullptr;
+    const DevProblem P = make_problem(h);
+    W.ev_begin = next_event(h);
+    LatticeBatchLists T;
+    for (int c0 = 0; c0 < A.nchains; c0 += nbv) {
+        const int nb = std::min(nbv, A.nchains - c0);
+        whole_lattice_batch(W, nb, false);
+        lattice_lists(h, A, c0, nb, T);
+        if ((size_t)T.pstride > pmax) return fail(h, RSREC_ERR_DEVICE, "%s: split partials outside the planned buffer", who);
+        XFER(xfer_h2d(h, d_list, T.list.data(), (size_t)nb * kk * sizeof(int)));
+        XFER(xfer_h2d(h, d_seg, T.seg_off.data(), (size_t)nb * (ng + 1) * sizeof(int)));
+        XFER(xfer_h2d(h, d_split, T.split_off.data(), (size_t)nb * (ng + 1) * sizeof(int)));
+        XFER(xfer_h2d(h, d_w, T.weight.data(), (size_t)nb * kk * sizeof(double2)));
+        XFER(xfer_h2d(h, d_bound, T.bound.data(), (size_t)nb * sizeof(double)));
+        const LatticeLists LL{d_list, d_w, d_seg, d_split, kk, ng, T.pstride};
+        for (int v = 0; v < nvec; ++v) HIPCK(h, hipMemsetAsync(h->d_vec[v].p, 0, (size_t)nb * velems * sizeof(double), h->stream));
+        ChebyshevStepper Y{h->d_vec[0].as<double>(), h->d_vec[1].as<double>(), h->d_vec[2].as<double>()};
+        XFER(seed_whole_vectors<L>(h, who, A.S, c0, nb, Y.cur, velems));
+        for (int n = 0; n <= napply; ++n) {
+            if (MFMA) Y.step(W, n, A.a, A.b);
+            else lattice_step_valu(W, Y, P, nblk, n, A.a, A.b, h->d_vec[3].as<double>());
+            // moment n + 1 of the batch's images: the projection of the vector of order n
+            hipEvent_t e0 = next_event(h);
+            k_lattice_project<<<dim3(T.pstride, nb), LATTICE_THREADS, 0, h->stream>>>(LL, Y.cur, velems, partial);
+            k_lattice_reduce<L><<<dim3(ng, nb, LATTICE_RWG), 64, 0, h->stream>>>(LL, partial, c0, n, nmom, mu);
+            k_lattice_diverge<<<nb, LATTICE_THREADS, 0, h->stream>>>(mu, c0, n, nmom, ng, d_bound, h->d_status.as<int>());
+            W.rest_ev.emplace_back(e0, next_event(h));
+        }
+        HIPCK(h, hipGetLastError());
+    }
+    if (A.m_g) {
+        if (is_device_ptr(A.m_g)) HIPCK(h, hipMemcpyAsync(A.m_g, mu, nimg * mstride * sizeof(double2), hipMemcpyDeviceToDevice, h->stream));
+        else XFER(xfer_d2h(h, A.m_g, mu, nimg * mstride * sizeof(double2)));
+    }
+    XFER(whole_lattice_end(h, W, true));
+    XFER(finish_status(h));
+    h->res_kind = 2; h->res_n = (int)nimg; h->res_lld = A.lld; h->res_seeded = false;   // what an rsrec_chebyshev call of nchains * ngroup sites leaves
+    return RSREC_OK;
+}
+
+}  // namespace
+
+extern "C" int rsrec_chebyshev_lattice(rsrec_t* h, int nchains, int nseed, const int32_t* seed_atoms, const double* seed_coef, int lld, double a, double b,
+                                       int ngroup, const int32_t* group, double* m_g) {
+    const char* who = "rsrec_chebyshev_lattice";
+    int rc = check_ready(h, who);
+    if (rc) return rc;
+    if (nchains < 0 || lld < 1 || a == 0.0) return fail(h, RSREC_ERR_ARG, "%s: nchains < 0, lld < 1 or a == 0", who);
+    if (nseed < 1 || nseed > h->kk) return fail(h, RSREC_ERR_ARG, "%s: nseed = %d outside 1..%d", who, nseed, h->kk);
+    if (ngroup < 1 || ngroup > RSREC_LATTICE_NGROUP_MAX) return fail(h, RSREC_ERR_ARG, "%s: ngroup = %d outside 1..%d", who, ngroup, RSREC_LATTICE_NGROUP_MAX);
+    if (nchains > 0 && (!seed_atoms || !seed_coef)) return fail(h, RSREC_ERR_ARG, "%s: NULL seed_atoms or seed_coef", who);
+    if (!group && ngroup != 1) return fail(h, RSREC_ERR_ARG, "%s: ngroup = %d needs a group array", who, ngroup);
+    if (group)
+        for (int j = 0; j < h->kk; ++j)
+            if (group[j] < 0 || group[j] > ngroup) return fail(h, RSREC_ERR_ARG, "%s: group(%d) = %d outside 0..%d", who, j + 1, group[j], ngroup);
+    XFER(check_seeds(h, who, seed_atoms, (size_t)nchains * nseed, 0));
+    for (int c = 0; c < nchains; ++c)
+        if (std::all_of(seed_atoms + (size_t)c * nseed, seed_atoms + (size_t)(c + 1) * nseed, [](int32_t s) { return s == 0; }))
+            return fail(h, RSREC_ERR_ARG, "%s: vector %d has no seed", who, c + 1);
+    if ((size_t)nchains * ngroup > (size_t)INT32_MAX) return fail(h, RSREC_ERR_ARG, "%s: nchains * ngroup exceeds the index range", who);
+    HIPCK(h, hipSetDevice(h->device));
+    reset_timing(h);
+    if (nchains == 0) return RSREC_OK;
+    const LatticeCall A{nchains, lld, ngroup, KuboSeeds{nseed, seed_atoms, seed_coef}, group, a, b, m_g};
+    return matrix_core_set(h) ? run_lattice<true>(h, who, A) : run_lattice<false>(h, who, A);
 }
 
 extern "C" int rsrec_scalar_lanczos(rsrec_t* h, int nsites, const int32_t* seed_atoms, int lld, int llmax, double* a, double* b2) {

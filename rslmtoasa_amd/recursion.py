@@ -386,6 +386,72 @@ class Recursion:
         img = green.chebyshev_ldos(nsites_total=nimg)
         return img["dosial"].reshape((nk, ngroup, nsrc, 18, -1), order="F")
 
+    def _group(self, group):
+        """(group as int32 (kk) or None, ngroup) of the calls that take atom groups 0..ngroup."""
+        if group is None:
+            return None, 1
+        group = np.ascontiguousarray(group, dtype=np.int32).ravel()
+        if group.shape != (self.lattice.kk,):
+            raise ValueError("group must be (kk,), got %r" % (group.shape,))
+        return group, max(int(group.max()), 1)
+
+    def chebyshev_lattice(self, seeds, coefs, group=None, download=True):
+        """Chebyshev moments from whole-lattice seeds (``rsrec_chebyshev_lattice``): chain c starts from |x> = sum_j c_j |j> (x) 1_18 with
+        ``seeds`` (nchains, nseed) 1-based atoms (0: unused entry) and ``coefs`` (nchains, nseed) complex, placed as
+        ``compute_moments_stochastic`` places its vectors, and M_g(n) = sum_{j in g} conj(c_j) [T_{n-1}(H~) x]_j = <x|P_g T_{n-1}(H~)|x>.
+        ``group`` (kk) with values 0..ngroup (0: left out) or None (every atom in group 1).  Returns (18, 18, 2 lld + 2, ngroup, nchains),
+        or None with ``download=False``; either way the image stays resident as ``chebyshev_recur`` of ngroup * nchains sites leaves it
+        (image g + ngroup c).  Nothing is normalised here: with |c_j|^2 = 1/kk, tr M_g(1) = 18 N_g / kk, and the caller divides.  Only the
+        sum over the groups is Hermitian; the LDOS stage reads the real part of an image's diagonal, the symmetrised group weight."""
+        lld = self.control.lld
+        a, b = chebyshev_scaling(self.en.energy_min, self.en.energy_max)
+        seeds = np.ascontiguousarray(seeds, dtype=np.int32)
+        coefs = np.ascontiguousarray(coefs, dtype=np.complex128)
+        if seeds.ndim != 2 or coefs.shape != seeds.shape:
+            raise ValueError("seeds and coefs must both be (nchains, nseed), got %r and %r" % (seeds.shape, coefs.shape))
+        group, ngroup = self._group(group)
+        nchains, nseed = seeds.shape
+        m_g = np.zeros((18, 18, 2 * lld + 2, ngroup, nchains), np.complex128, order="F") if download else None
+        self._check(self._L.rsrec_chebyshev_lattice(self._h, nchains, nseed, _ptr(seeds), _ptr(coefs), lld, a, b, ngroup, _ptr(group), _ptr(m_g)))
+        return m_g
+
+    def bloch_average(self, kpts, cr, group=None, download=True):
+        """The source average of ``chebyshev_bloch``, one chain per k-point instead of kk: plane-wave seeds c_j = exp(+i k.r_j) / sqrt(kk) on
+        every atom, built here in float64 from ``kpts`` (3, nk) Cartesian with 2 pi and ``cr`` (3, kk).  The sum over the groups of the
+        result is (1/kk) sum_i S_i(k, n), the moments of the effective (unfolded) band structure of a disordered supercell; ``group``
+        resolves it by atom type or layer, tr M_g(1) = 18 N_g / kk.  Returns (18, 18, 2 lld + 2, ngroup, nk), see ``chebyshev_lattice``."""
+        kk = self.lattice.kk
+        k = np.asarray(kpts, np.float64).reshape(3, -1, order="F")
+        cr = np.asarray(cr, np.float64)
+        if cr.shape != (3, kk):
+            raise ValueError("cr must be (3, kk), got %r" % (cr.shape,))
+        coefs = np.exp(1j * (k.T @ cr)) / np.sqrt(float(kk))                      # (nk, kk)
+        seeds = np.tile(np.arange(1, kk + 1, dtype=np.int32), (k.shape[1], 1))
+        return self.chebyshev_lattice(seeds, coefs, group=group, download=download)
+
+    def bloch_average_spectral(self, green, kpts, cr, group=None):
+        """Orbital-resolved weights of the source-averaged Bloch spectral function on ``green``'s energy mesh: ``bloch_average`` without a
+        download, then the LDOS stage on the resident image.  Returns ``dosial`` as (ngroup, nk, 18, nen); summed over the orbitals and the
+        groups it is the effective A(k,E) of the cell, each group carrying its weight N_g / kk."""
+        self.bloch_average(kpts, cr, group=group, download=False)
+        nk = np.asarray(kpts).reshape(3, -1, order="F").shape[1]
+        ngroup = self._group(group)[1]
+        img = green.chebyshev_ldos(nsites_total=ngroup * nk)
+        return img["dosial"].reshape((ngroup, nk, 18, -1), order="F")
+
+    def cell_moments(self, rng, group=None, download=True):
+        """Stochastic-trace moments of the whole cell by atom group, on the vectors ``cond_calctype = 'random_vec'`` builds from its random
+        numbers ``rng`` (kk, nvec) (recursion.f90:1130-1138): c_j = exp(2 pi i rng_j) / sqrt(real(kk)), the single-precision square root
+        widened, as there.  M_g(n) estimates (1/kk) sum_{j in g} <j|T_{n-1}(H~)|j>: tr M_g(1) = 18 N_g / kk up to that rounding of the norm,
+        and the caller divides.  Returns (18, 18, 2 lld + 2, ngroup, nvec), see ``chebyshev_lattice``."""
+        rng = np.asarray(rng, np.float64)
+        if rng.ndim != 2 or rng.shape[0] != self.lattice.kk:
+            raise ValueError("rng must be (kk, nvec), got %r" % (rng.shape,))
+        kk, nvec = rng.shape
+        coefs = np.ascontiguousarray((np.exp(2.0 * np.pi * 1j * rng) / float(np.sqrt(np.float32(kk)))).T)
+        seeds = np.tile(np.arange(1, kk + 1, dtype=np.int32), (nvec, 1))
+        return self.chebyshev_lattice(seeds, coefs, group=group, download=download)
+
     def zsqr(self):
         """b2_b <- sqrt(b2_b) in place (recursion.f90:1980-2023)."""
         self._check(self._L.rsrec_zsqr(self._h, self.b2_b.shape[2] * self.b2_b.shape[3], _ptr(self.b2_b)))
