@@ -16,12 +16,12 @@
 #include <string>
 #include <vector>
 #include "kernels_valu.hpp"
+#include "region_plan.hpp"    // GROUP: atoms per wave (one type) -- the host planner pads the lists into groups of it
 
 namespace rsrec {
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
-constexpr int GROUP = 8;            // atoms per wave (one type)
 constexpr int MF_WAVES = 4;         // waves per workgroup
 
 // CI layout ("complex interleaved", the large-launch path's ONE vector layout): element (r, c) of an 18x18 block = one complex

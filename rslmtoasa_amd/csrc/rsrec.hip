@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "../../include/rsrec.h"
+#include "region_plan.hpp"
 #include "kernels_valu.hpp"
 #include "kernels_mfma.hpp"
 #include "kernels_spmm4.hpp"
@@ -191,30 +192,17 @@ struct rsrec_handle {
     size_t ev_used = 0;
     // regions are purely topological: they are reused while the lattice and the seeds stay the same (every SCF iteration
     // of the reference calls recur_b with the same lattice%nn and lattice%irec)
-    struct RegionEntry {
+    struct RegionEntry : RegionStats {      // a plan (region_plan.hpp) whose lists are on the device
+        RegionKey key;
         std::vector<int> seeds;
-        int nlev, napply, flags, epoch, ostride;
-        double atom_steps, block_mults;
+        int epoch = 0;
+        uint64_t serial = 0;                // from next_region_serial: names the entry in the captured graph's key (an address can come back)
         DevBuf order, cum;
-        std::vector<int> level_max;     // per level: largest active-atom count over the chains of this entry
-        std::vector<int> hop_min, hop_max;  // per level: smallest / largest count of the H|psi> lists (padding included) over the chains
-        std::vector<double> level_groups;   // [level][tau]: groups of 8 atoms (padding included) of operator class tau, summed over the chains
-        std::vector<double> mult_hist;      // [pass 0/1][tau][nslots + 1]: block multiplications of the call by (pass, operator class, slot), summed over the chains
-        // the list of ALL atoms (used once a region covers the lattice) is sorted by operator class: one run of groups per class
-        struct ClassRun { int tau, lo, hi; };
-        std::vector<ClassRun> sat_runs;
-        std::vector<int> level_sat;         // per level: chains of this entry that use that list
-        int sat_base = 0;                   // its offset inside an order row
     };
     std::vector<std::unique_ptr<RegionEntry>> region_cache;
+    uint64_t next_region_serial = 1;        // never repeats
     int lattice_epoch = 0;
-    const int* cur_order = nullptr;
-    const int* cur_cum = nullptr;     // [nrows][nlev] counts, [nrows][nlev] list offsets (the lists of H|psi>), then the same two tables for the streaming passes
-    const std::vector<int>* cur_level_max = nullptr;
-    const std::vector<double>* cur_level_groups = nullptr;
-    const std::vector<double>* cur_mult_hist = nullptr;
-    const RegionEntry* cur_entry = nullptr;
-    int cur_nrows = 0;
+    const RegionEntry* cur_entry = nullptr;   // what upload_regions made current: the lists, tables and statistics every launch of the call reads
     std::vector<unsigned> spatial_key;   // per atom: position along a space-filling curve (locality hint for the saturated order)
     // coefficients left on the device by the last recursion call: 0 = none, 1 = block Lanczos (d_coefA = a_b, d_coefB = b2_b, never its
     // root), 2 = Chebyshev (d_mu = mu_n of all chains)
@@ -336,83 +324,8 @@ int xfer_h2d(rsrec_t* h, void* dst_dev, const void* src, size_t bytes) {
 }
 #define XFER(call) do { int rc__ = (call); if (rc__) return rc__; } while (0)
 
-struct Region {
-    std::vector<int> order;   // atoms sorted by (distance, index)
-    std::vector<int> cum;     // cum[L] = #atoms with distance <= L, L = 0..nlev-1
-};
-
-// Breadth-first growth of the active region, restating izero/idum of hop_b (recursion.f90:1604-1636):
-// atom i joins the region when one of ITS neighbour slots holds an atom already in it.
-void grow_region(const rsrec_t* h, const int* seeds, int nseed, int nlev, Region& R) {
-    const int kk = h->kk;
-    std::vector<int> dist(kk, -1);
-    R.order.clear();
-    R.order.reserve(kk);
-    R.cum.assign(nlev, 0);
-    std::vector<int> frontier, next;
-    for (int s = 0; s < nseed; ++s)
-        if (dist[seeds[s]] < 0) { dist[seeds[s]] = 0; frontier.push_back(seeds[s]); }
-    std::sort(frontier.begin(), frontier.end());
-    int level = 0;
-    while (!frontier.empty() && level < nlev) {
-        R.order.insert(R.order.end(), frontier.begin(), frontier.end());
-        R.cum[level] = (int)R.order.size();
-        next.clear();
-        for (int n : frontier)
-            for (int q = h->radj_ptr[n]; q < h->radj_ptr[n + 1]; ++q) {
-                const int i = h->radj[q];
-                if (dist[i] < 0) { dist[i] = level + 1; next.push_back(i); }
-            }
-        std::sort(next.begin(), next.end());
-        frontier.swap(next);
-        ++level;
-    }
-    for (int L = std::max(level, 1); L < nlev; ++L) R.cum[L] = R.cum[L - 1];
-    R.order.resize(kk, 0);   // tail is never read (cum bounds every loop)
-}
-
-inline unsigned spread3(unsigned v) {           // 10 bits -> every third bit
-    v &= 1023u;
-    v = (v | (v << 16)) & 0x030000FFu;
-    v = (v | (v << 8)) & 0x0300F00Fu;
-    v = (v | (v << 4)) & 0x030C30C3u;
-    v = (v | (v << 2)) & 0x09249249u;
-    return v;
-}
-inline unsigned morton3(unsigned x, unsigned y, unsigned z) { return spread3(x) | (spread3(y) << 1) | (spread3(z) << 2); }
-
-// breadth-first distances over the (symmetrised) neighbour graph from one atom
-void bfs_dist(const rsrec_t* h, int start, std::vector<int>& dist) {
-    const int kk = h->kk, ns = h->nslots;
-    dist.assign(kk, -1);
-    std::vector<int> cur{start}, nxt;
-    dist[start] = 0;
-    int d = 0;
-    while (!cur.empty()) {
-        nxt.clear();
-        for (int n : cur) {
-            for (int j = 1; j < ns; ++j) { const int i = h->nbr[(size_t)n * ns + j]; if (i >= 0 && dist[i] < 0) { dist[i] = d + 1; nxt.push_back(i); } }
-            for (int q = h->radj_ptr[n]; q < h->radj_ptr[n + 1]; ++q) { const int i = h->radj[q]; if (dist[i] < 0) { dist[i] = d + 1; nxt.push_back(i); } }
-        }
-        cur.swap(nxt);
-        ++d;
-    }
-}
-
-// Locality hint when the caller gives no coordinates: graph distances to three far-apart landmark atoms act as
-// pseudo-coordinates (adequate for ordering: atoms with similar distance triples are close in the lattice).
-void spatial_key_from_graph(rsrec_t* h) {
-    const int kk = h->kk;
-    std::vector<int> d0, d1, d2;
-    bfs_dist(h, 0, d0);
-    int l1 = 0;
-    for (int i = 0; i < kk; ++i) if (d0[i] >= d0[l1]) l1 = i;
-    bfs_dist(h, l1, d1);
-    int l2 = 0, best = -1;
-    for (int i = 0; i < kk; ++i) { const int m = std::min(d0[i], d1[i]); if (m >= best) { best = m; l2 = i; } }
-    bfs_dist(h, l2, d2);
-    h->spatial_key.resize(kk);
-    for (int i = 0; i < kk; ++i) h->spatial_key[i] = morton3((unsigned)std::max(d0[i], 0), (unsigned)std::max(d1[i], 0), (unsigned)std::max(d2[i], 0));
+LatticeView lattice_view(const rsrec_t* h) {
+    return LatticeView{h->kk, h->nslots, h->nmax, h->ntype, h->nbr.data(), h->iz0.data(), h->radj_ptr.data(), h->radj.data(), h->spatial_key.data()};
 }
 
 }  // namespace
@@ -523,7 +436,7 @@ static void release_regions(rsrec_t* h) {
     release_graph(h);
     if (!h->region_cache.empty()) (void)hipDeviceSynchronize();
     h->region_cache.clear();
-    h->cur_order = nullptr; h->cur_cum = nullptr; h->cur_entry = nullptr; h->cur_level_max = nullptr; h->cur_level_groups = nullptr; h->cur_mult_hist = nullptr;
+    h->cur_entry = nullptr;
 }
 
 extern "C" int rsrec_set_lattice(rsrec_t* h, int kk, int nncols, const int32_t* nn, const int32_t* iz, int nmax, int ntype) {
@@ -543,7 +456,7 @@ extern "C" int rsrec_set_lattice(rsrec_t* h, int kk, int nncols, const int32_t* 
         nslots = std::max(nslots, nr);
         if (iz[i] < 1 || iz[i] > ntype) return fail(h, RSREC_ERR_ARG, "rsrec_set_lattice: iz(%d)=%d outside 1..%d", i + 1, iz[i], ntype);
     }
-    std::vector<int> nbr_new((size_t)kk * nslots, -1), iz_new(kk), deg(kk + 1, 0);
+    std::vector<int> nbr_new((size_t)kk * nslots, -1), iz_new(kk);
     for (int i = 0; i < kk; ++i) {
         iz_new[i] = iz[i] - 1;
         nbr_new[(size_t)i * nslots] = i;
@@ -553,7 +466,6 @@ extern "C" int rsrec_set_lattice(rsrec_t* h, int kk, int nncols, const int32_t* 
             if (n == 0) continue;
             if (n < 0 || n > kk) return fail(h, RSREC_ERR_ARG, "rsrec_set_lattice: nn(%d,%d)=%d outside 0..%d", i + 1, j + 1, n, kk);
             nbr_new[(size_t)i * nslots + j] = n - 1;
-            deg[n - 1]++;
         }
     }
     // from here on the handle changes: until the last table is uploaded it holds no lattice (a failed upload must not leave the
@@ -566,15 +478,7 @@ extern "C" int rsrec_set_lattice(rsrec_t* h, int kk, int nncols, const int32_t* 
     h->kk = kk; h->nslots = nslots; h->nmax = nmax; h->ntype = ntype;
     h->nbr.swap(nbr_new);
     h->iz0.swap(iz_new);
-    h->radj_ptr.assign(kk + 1, 0);
-    for (int n = 0; n < kk; ++n) h->radj_ptr[n + 1] = h->radj_ptr[n] + deg[n];
-    h->radj.resize(h->radj_ptr[kk]);
-    std::vector<int> fill(h->radj_ptr.begin(), h->radj_ptr.end() - 1);
-    for (int i = 0; i < kk; ++i)
-        for (int j = 1; j < nslots; ++j) {
-            const int n = h->nbr[(size_t)i * nslots + j];
-            if (n >= 0) h->radj[fill[n]++] = i;
-        }
+    reverse_adjacency(kk, nslots, h->nbr.data(), h->radj_ptr, h->radj);
     HIPCK(h, h->d_nbr.reserve(h->nbr.size() * sizeof(int)));
     HIPCK(h, h->d_iz.reserve((size_t)kk * sizeof(int)));
     HIPCK(h, hipMemcpy(h->d_nbr.p, h->nbr.data(), h->nbr.size() * sizeof(int), hipMemcpyHostToDevice));
@@ -590,7 +494,7 @@ extern "C" int rsrec_set_lattice(rsrec_t* h, int kk, int nncols, const int32_t* 
         HIPCK(h, h->d_nbr5.reserve(n5.size() * sizeof(int)));
         HIPCK(h, hipMemcpy(h->d_nbr5.p, n5.data(), n5.size() * sizeof(int), hipMemcpyHostToDevice));
     }
-    spatial_key_from_graph(h);
+    spatial_key_from_graph(lattice_view(h), h->spatial_key);
     h->lat_nn.assign(nn, nn + (size_t)kk * nncols);
     h->lat_iz.assign(iz, iz + kk);
     h->lat_nncols = nncols;
@@ -607,17 +511,7 @@ extern "C" int rsrec_set_positions(rsrec_t* h, const double* cr) {
     const int kk = h->kk;
     if (h->lat_cr.size() == 3 * (size_t)kk && std::memcmp(h->lat_cr.data(), cr, h->lat_cr.size() * sizeof(double)) == 0) return RSREC_OK;
     h->lat_cr.assign(cr, cr + 3 * (size_t)kk);
-    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-    for (int i = 0; i < kk; ++i)
-        for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], cr[3 * (size_t)i + a]); hi[a] = std::max(hi[a], cr[3 * (size_t)i + a]); }
-    double span = 1e-300;
-    for (int a = 0; a < 3; ++a) span = std::max(span, hi[a] - lo[a]);
-    h->spatial_key.resize(kk);
-    for (int i = 0; i < kk; ++i) {
-        unsigned q[3];
-        for (int a = 0; a < 3; ++a) q[a] = (unsigned)std::min(1023.0, std::max(0.0, (cr[3 * (size_t)i + a] - lo[a]) / span * 1023.0));
-        h->spatial_key[i] = morton3(q[0], q[1], q[2]);
-    }
+    spatial_key_from_positions(kk, cr, h->spatial_key);
     h->lattice_epoch++;        // cached region orders were built with the old keys: they can never match again
     release_regions(h);
     return RSREC_OK;
@@ -828,225 +722,28 @@ int plan_batch(rsrec_t* h, int nchains, int nvec, size_t vec_elems_per_chain, Ba
     return RSREC_OK;
 }
 
-// Upload the regions of one batch. seeds: [nb][nseed] 0-based.
-// grouped = true: every BFS level is sorted by operator class tau (per-atom blocks first, then types) and each class run is
-// padded with -1 to a multiple of GROUP, so that 8 consecutive entries always share their operator blocks (MFMA kernels).
-int upload_regions(rsrec_t* h, const int* seeds0, int nb, int nseed, int nlev, int napply, bool two_pass, bool grouped, int& ostride,
-                   double& atom_steps, double& block_mults) {
-    const int kk = h->kk;
-    // order row = [one list per level of the growing region, each sorted by (operator class, position) | the same for ALL atoms]; every
-    // list is padded into operator-class groups of 8 when grouped.  (Rounds 1-3 kept ONE level-major list -- shell after shell, a level's
-    // atoms a prefix of it -- which costs 4 bytes per atom and chain but walks a level shell by shell: the waves of an XCD then work on a band
-    // of one shell while the blocks they gather lie in the bands of the two neighbouring shells, handled elsewhere and at other times.
-    // Measured per launch on 64 x 22^3 / 46^3 (tools/per_level_pmc.sh, per_level_trace.sh): L2 hit rate 0.38-0.41 on the growing levels
-    // against 0.55 on the list of all atoms, 1.7x the fabric bytes and 1.5x the time per atom -- and on the 46^3 cell the regions grow for 26
-    // of the 49 levels.  A list per level, position-sorted as a whole, gives the growing region the locality of the saturated one.)
-    // The streaming passes behind H|psi> (Gram sums, orthogonalisation, moment sums) read every active block once and gather nothing: they keep
-    // the level-major list (shell after shell, each shell sorted by class and position; a level = a prefix), whose walk is closer to address
-    // order -- on the per-level lists k_mfma_orth3 was 2.8 % slower (46^3, same box).  row = [level-major | per level | all atoms].
-    const int cap = grouped ? kk + 7 * h->nmax + 7 * h->ntype + 8 : kk;          // capacity of one list of all atoms
-    const int cap_pre = ((grouped ? kk + 7 * h->nmax + 7 * h->ntype * nlev + 8 : kk) + GROUP - 1) / GROUP * GROUP;   // capacity of the level-major list (a multiple of 8: every list starts on a group border)
-    const int flags = (two_pass ? 1 : 0) | (grouped ? 2 : 0) | ((int)std::min<long>(100, std::max<long>(1, h->opt_sat_pct)) << 2) | (nseed << 9);
+// The regions of one batch on the device, current for the launches that follow (h->cur_entry).  seeds0: [nb][nseed] 0-based.  Regions are purely
+// topological: an entry is reused while the lattice and the seeds stay the same (every SCF iteration of the reference calls recur_b with the same
+// lattice%nn and lattice%irec).  A new entry joins the cache once its lists are on the device: a failure leaves cache and current entry as they were.
+constexpr size_t REGION_CACHE_MAX = 256;
+int upload_regions(rsrec_t* h, const int* seeds0, int nb, int nseed, int nlev, int napply, bool two_pass, bool grouped) {
+    const RegionKey key{nb, nseed, nlev, napply, two_pass, grouped, (int)std::min<long>(100, std::max<long>(1, h->opt_sat_pct))};
     for (const auto& e : h->region_cache)
-        if (e->epoch == h->lattice_epoch && e->nlev == nlev && e->napply == napply && e->flags == flags && (int)e->seeds.size() == nb * nseed &&
-            std::equal(e->seeds.begin(), e->seeds.end(), seeds0)) {
-            h->cur_order = e->order.as<int>(); h->cur_cum = e->cum.as<int>(); h->cur_nrows = nb; h->cur_level_max = &e->level_max; h->cur_level_groups = &e->level_groups;
-            h->cur_mult_hist = &e->mult_hist;
-            h->cur_entry = e.get();
-            ostride = e->ostride;
-            atom_steps += e->atom_steps; block_mults += e->block_mults;
-            return RSREC_OK;
-        }
-    const int ntau_h = h->nmax + h->ntype, nfs_h = h->nslots + 1;
-    const int sat_pct = (int)std::min<long>(100, std::max<long>(1, h->opt_sat_pct));
-    const int sat_from = (int)(((long)sat_pct * kk + 99) / 100);   // regions of at least this many atoms run on the list of all atoms (100: only the whole lattice)
-    // the regions first (a few short-lived host threads; see below), then the row size they need
-    std::vector<Region> regs(nb);
-    auto run_threads = [&](auto&& fn) {
-        const int nthr = std::max(1, std::min({nb, 8, (int)std::thread::hardware_concurrency()}));
-        if (nthr == 1) { for (int c = 0; c < nb; ++c) fn(c); return; }
-        std::atomic<int> next_chain{0};
-        std::vector<std::thread> pool;
-        for (int t = 0; t < nthr; ++t)
-            pool.emplace_back([&]() { for (int c = next_chain++; c < nb; c = next_chain++) fn(c); });
-        for (auto& th : pool) th.join();
-    };
-    run_threads([&](int c) { grow_region(h, seeds0 + (size_t)c * nseed, nseed, nlev, regs[c]); });
-    size_t lvneed = 8;
-    for (int c = 0; c < nb; ++c) {
-        size_t need = 0;
-        for (int L = 0; L < nlev; ++L) {
-            const int n = regs[c].cum[L];
-            if (n >= sat_from || (L > 0 && n == regs[c].cum[L - 1])) continue;       // list of all atoms / the previous level's list again
-            need += (size_t)n + (grouped ? (size_t)7 * std::min(ntau_h, n) + 8 : 0);
-        }
-        lvneed = std::max(lvneed, need);
-    }
-    lvneed = (lvneed + 7) / 8 * 8;
-    if (lvneed + (size_t)cap > (size_t)INT32_MAX) return fail(h, RSREC_ERR_ARG, "region lists of %zu entries per chain exceed the index range", lvneed + (size_t)cap);
-    if ((size_t)cap_pre + lvneed + (size_t)cap > (size_t)INT32_MAX) return fail(h, RSREC_ERR_ARG, "region lists of %zu entries per chain exceed the index range", (size_t)cap_pre + lvneed + (size_t)cap);
-    const int sat_off = cap_pre + (int)lvneed;
-    ostride = sat_off + cap;
-    std::vector<int> order((size_t)nb * ostride, -1), cum((size_t)4 * nb * nlev, 0);      // counts, offsets (H|psi>); counts, offsets (streaming passes)
-    std::vector<double> as(nb, 0.0), bm(nb, 0.0);
-    const size_t hist_n = (size_t)2 * ntau_h * nfs_h;
-    std::vector<double> hist((size_t)nb * hist_n, 0.0);
-    auto tau = [&](int i) { return i < h->nmax ? i : h->nmax + h->iz0[i]; };
-    const std::vector<unsigned>& key = h->spatial_key;
-    auto before = [&](int x, int y) {                       // operator class first (groups must be homogeneous), then position
-        const int tx = grouped ? tau(x) : 0, ty = grouped ? tau(y) : 0;
-        if (tx != ty) return tx < ty;
-        if (key[x] != key[y]) return key[x] < key[y];
-        return x < y;
-    };
-    // the list of all atoms is the same for every chain of the lattice
-    std::vector<int> all(kk), sat_list;
-    for (int i = 0; i < kk; ++i) all[i] = i;
-    std::sort(all.begin(), all.end(), before);
-    sat_list.reserve(cap);
-    for (int q = 0; q < kk; ++q) {
-        if (grouped && q > 0 && tau(all[q]) != tau(all[q - 1])) while (sat_list.size() % GROUP) sat_list.push_back(-1);
-        sat_list.push_back(all[q]);
-    }
-    if (grouped) while (sat_list.size() % GROUP) sat_list.push_back(-1);
-    const int sat_count = (int)sat_list.size();
-    // One region per chain, built by a few short-lived host threads.  (Not OpenMP: its idle workers spin for 200 ms after a
-    // parallel region -- one per visible CPU, 256 on the GPU boxes -- and burn the process's CPU quota: the host thread was then
-    // descheduled for 60-90 ms at a time during the next two or three calls, inside whatever HIP call it happened to be in.)
-    std::vector<double> lgroups((size_t)nb * nlev * ntau_h, 0.0);     // [chain][level][class]: groups of the level's own list
-    auto build_chain = [&](int c) {
-        const Region& R = regs[c];
-        int* orow = order.data() + (size_t)c * ostride;
-        int* crow = cum.data() + (size_t)c * nlev;
-        int* brow = cum.data() + (size_t)(nb + c) * nlev;
-        int* crow2 = cum.data() + (size_t)(2 * nb + c) * nlev;
-        int* brow2 = cum.data() + (size_t)(3 * nb + c) * nlev;
-        std::copy(sat_list.begin(), sat_list.end(), orow + sat_off);
-        int w = cap_pre, wp = 0;
-        std::vector<int> lev, region, merged;
-        for (int L = 0; L < nlev; ++L) {
-            const int lo = L ? R.cum[L - 1] : 0, hi = R.cum[L];
-            // once the region covers most of the lattice the sorted list of all atoms is used instead: blocks outside
-            // the region are exactly zero, so a superset changes nothing
-            if (hi >= sat_from) { crow[L] = crow2[L] = sat_count; brow[L] = brow2[L] = sat_off; continue; }
-            lev.assign(R.order.begin() + lo, R.order.begin() + hi);
-            std::sort(lev.begin(), lev.end(), before);
-            for (size_t q = 0; q < lev.size(); ++q) {            // level-major list: this shell behind the earlier ones
-                if (grouped && q > 0 && tau(lev[q]) != tau(lev[q - 1])) while (wp % GROUP) orow[wp++] = -1;
-                orow[wp++] = lev[q];
-            }
-            if (grouped) while (wp % GROUP) orow[wp++] = -1;
-            crow2[L] = wp; brow2[L] = 0;
-            if (L > 0 && hi == lo) { crow[L] = crow[L - 1]; brow[L] = brow[L - 1]; continue; }     // the region has stopped growing: the previous level's list again
-            merged.resize(region.size() + lev.size());
-            std::merge(region.begin(), region.end(), lev.begin(), lev.end(), merged.begin(), before);
-            region.swap(merged);
-            brow[L] = w;
-            double* G = lgroups.data() + ((size_t)c * nlev + L) * ntau_h;
-            for (size_t q = 0; q < region.size(); ++q) {
-                if (grouped && q > 0 && tau(region[q]) != tau(region[q - 1])) while (w % GROUP) orow[w++] = -1;
-                if (w % GROUP == 0) G[grouped ? tau(region[q]) : 0] += 1.0;
-                orow[w++] = region[q];
-            }
-            if (grouped) while (w % GROUP) orow[w++] = -1;
-            crow[L] = w - brow[L];
-        }
-        // bookkeeping in the reference's terms: application t (1..napply) multiplies one block per (atom, slot) whose
-        // source atom lies in the region before it; post-hop work runs on the region after it.
-        double a_s = 0.0, b_m = 0.0;
-        for (int t = 1; t <= napply; ++t) {
-            const int lv_after = two_pass ? 2 * t : t;
-            a_s += R.cum[std::min(lv_after, nlev - 1)];
-        }
-        std::vector<int> lev_of(kk, -1);
-        {
-            int lv = 0;
-            for (int q = 0; q < R.cum[nlev - 1]; ++q) {
-                while (q >= R.cum[lv]) ++lv;
-                lev_of[R.order[q]] = lv;
-            }
-        }
-        // uses1[d] / uses2[d]: applications whose first / second (hoh) pass sees a source at distance d inside the region
-        std::vector<double> uses1(nlev + 1, 0.0), uses2(nlev + 1, 0.0);
-        for (int d = 0; d < nlev; ++d)
-            for (int t = 1; t <= napply; ++t) {
-                if (!two_pass) { if (d <= t - 1) uses1[d] += 1.0; }
-                else { if (d <= 2 * (t - 1)) uses1[d] += 1.0; if (d <= 2 * t - 1) uses2[d] += 1.0; }
-            }
-        // one multiplication per (target atom i, slot s) whose source nbr(i, s) is active (hop_b :1576-1625), kept by (pass, operator class
-        // of the target, slot): the reference's count is their sum, the flops the block structure requires weigh them by block class
-        double* H = hist.data() + (size_t)c * hist_n;
-        const int ns = h->nslots;
-        for (int i = 0; i < kk; ++i) {
-            const int ti = tau(i);
-            for (int s = 0; s < ns; ++s) {
-                const int n = h->nbr[(size_t)i * ns + s];
-                if (n < 0 || lev_of[n] < 0) continue;
-                H[(size_t)ti * nfs_h + s] += uses1[lev_of[n]];
-                if (two_pass) H[((size_t)ntau_h + ti) * nfs_h + s] += uses2[lev_of[n]];
-            }
-            if (two_pass && lev_of[i] >= 0) H[((size_t)ntau_h + ti) * nfs_h + ns] += uses1[lev_of[i]];   // e_nu psi + l.s psi on-site (:1437-1438), one merged block here
-        }
-        for (size_t q = 0; q < hist_n; ++q) b_m += H[q];
-        if (two_pass) for (int t2 = 0; t2 < ntau_h; ++t2) b_m += H[((size_t)ntau_h + t2) * nfs_h + ns];       // the reference multiplies enim and lsham separately
-        as[c] = a_s; bm[c] = b_m;
-    };
-    run_threads(build_chain);
-    double as_sum = 0.0, bm_sum = 0.0;
-    for (int c = 0; c < nb; ++c) { as_sum += as[c]; bm_sum += bm[c]; }
-    atom_steps += as_sum; block_mults += bm_sum;
-    if (h->region_cache.size() >= 256) {          // bounded: drop everything (the engine is idle between calls)
-        HIPCK(h, hipStreamSynchronize(h->stream));
-        h->region_cache.clear();
-        h->cur_entry = nullptr;
-    }
-    h->region_cache.push_back(std::make_unique<rsrec_handle::RegionEntry>());
-    rsrec_handle::RegionEntry* e = h->region_cache.back().get();
-    e->seeds.assign(seeds0, seeds0 + (size_t)nb * nseed);
-    e->nlev = nlev; e->napply = napply; e->flags = flags; e->epoch = h->lattice_epoch; e->ostride = ostride;
-    e->atom_steps = as_sum; e->block_mults = bm_sum;
-    e->mult_hist.assign(hist_n, 0.0);
-    for (int c = 0; c < nb; ++c)
-        for (size_t q = 0; q < hist_n; ++q) e->mult_hist[q] += hist[(size_t)c * hist_n + q];
-    HIPCK(h, e->order.reserve(order.size() * 4));
-    HIPCK(h, e->cum.reserve(cum.size() * 4));
-    XFER(xfer_h2d(h, e->order.p, order.data(), order.size() * 4));
-    XFER(xfer_h2d(h, e->cum.p, cum.data(), cum.size() * 4));
-    HIPCK(h, hipStreamSynchronize(h->stream));   // order/cum are stack-local vectors
-    e->level_max.assign(nlev, 0);
-    e->hop_min.assign(nlev, INT32_MAX); e->hop_max.assign(nlev, 0);
-    e->level_groups.assign((size_t)nlev * ntau_h, 0.0);
-    {
-        // groups by operator class: the saturated list is the same for every chain; a level-major list is walked once per chain
-        std::vector<double> sat_hist(ntau_h, 0.0);
-        for (int g = 0; g < sat_count / GROUP; ++g) sat_hist[tau(sat_list[(size_t)g * GROUP])] += 1.0;
-        e->sat_base = sat_off;
-        e->level_sat.assign(nlev, 0);
-        if (grouped)
-            for (int g = 0; g < sat_count / GROUP; ++g) {
-                const int t = tau(sat_list[(size_t)g * GROUP]);
-                if (e->sat_runs.empty() || e->sat_runs.back().tau != t) e->sat_runs.push_back({t, g, g + 1});
-                else e->sat_runs.back().hi = g + 1;
-            }
-        for (int c = 0; c < nb; ++c) {
-            const double* prev = nullptr;
-            for (int l = 0; l < nlev; ++l) {
-                const int cnt = cum[(size_t)c * nlev + l];
-                e->level_max[l] = std::max(e->level_max[l], cnt);
-                e->hop_min[l] = std::min(e->hop_min[l], cnt); e->hop_max[l] = std::max(e->hop_max[l], cnt);
-                const bool sat = cum[(size_t)(nb + c) * nlev + l] == sat_off;   // (level_max: the larger of the two lists' counts sizes the launches)
-                e->level_max[l] = std::max(e->level_max[l], cum[(size_t)(2 * nb + c) * nlev + l]);
-                if (sat) e->level_sat[l] += 1;
-                const double* G = lgroups.data() + ((size_t)c * nlev + l) * ntau_h;
-                if (!sat && l > 0 && cum[(size_t)(nb + c) * nlev + l] == cum[(size_t)(nb + c) * nlev + l - 1] && prev) G = prev;     // the previous level's list again
-                for (int t2 = 0; t2 < ntau_h; ++t2) e->level_groups[(size_t)l * ntau_h + t2] += sat ? sat_hist[t2] : G[t2];
-                prev = sat ? nullptr : G;
-            }
-        }
-    }
-    h->cur_order = e->order.as<int>(); h->cur_cum = e->cum.as<int>(); h->cur_nrows = nb; h->cur_level_max = &e->level_max; h->cur_level_groups = &e->level_groups;
-    h->cur_mult_hist = &e->mult_hist;
-    h->cur_entry = e;
+        if (e->epoch == h->lattice_epoch && e->key == key && std::equal(e->seeds.begin(), e->seeds.end(), seeds0)) { h->cur_entry = e.get(); return RSREC_OK; }
+    RegionPlan plan;
+    const std::string refused = plan_regions(lattice_view(h), key, seeds0, plan);
+    if (!refused.empty()) return fail(h, RSREC_ERR_ARG, "%s", refused.c_str());
+    auto e = std::make_unique<rsrec_handle::RegionEntry>();
+    static_cast<RegionStats&>(*e) = std::move(static_cast<RegionStats&>(plan));
+    e->key = key; e->epoch = h->lattice_epoch; e->serial = h->next_region_serial++; e->seeds.assign(seeds0, seeds0 + (size_t)nb * nseed);
+    HIPCK(h, e->order.reserve(plan.order.size() * 4));
+    HIPCK(h, e->cum.reserve(plan.cum.size() * 4));
+    XFER(xfer_h2d(h, e->order.p, plan.order.data(), plan.order.size() * 4));
+    XFER(xfer_h2d(h, e->cum.p, plan.cum.data(), plan.cum.size() * 4));
+    HIPCK(h, hipStreamSynchronize(h->stream));   // the plan's order / cum are local
+    if (h->region_cache.size() >= REGION_CACHE_MAX) release_regions(h);   // bounded: drop everything, the captured level loop with the lists it points into
+    h->region_cache.push_back(std::move(e));
+    h->cur_entry = h->region_cache.back().get();
     return RSREC_OK;
 }
 
@@ -1054,9 +751,9 @@ int upload_regions(rsrec_t* h, const int* seeds0, int nb, int nseed, int nlev, i
 // full 18x18 blocks (zgemm, recursion.f90:1618: 46 656 flop each), but the hopping blocks of a collinear magnet are spin-diagonal
 // (hamiltonian.f90:1553-1617) and need half of that.  This -- not the reference's count -- is what a roofline fraction is measured in.
 double required_hop_flops(const rsrec_t* h, const Spmm5Operator& op) {
-    if (!h->cur_mult_hist) return 0.0;
+    if (!h->cur_entry) return 0.0;
     const int ntau = h->nmax + h->ntype, nfs = h->nslots + 1;
-    const std::vector<double>& H = *h->cur_mult_hist;
+    const std::vector<double>& H = h->cur_entry->mult_hist;
     if (H.size() != (size_t)2 * ntau * nfs) return 0.0;
     double f = 0.0;
     for (int pass = 0; pass < 2; ++pass)
@@ -1131,12 +828,14 @@ int reserve_partials(rsrec_t* h, int B, size_t first_stage_bytes) {
 
 // the lists of the region entry upload_regions made current, as the kernels walk them: CV the per-level lists of H|psi>, CVp (where asked
 // for) the level-major lists of the streaming passes behind it
-void chain_views(const rsrec_t* h, int nlev, size_t velems, int cpo, int ostride, ChainView& CV, ChainView* CVp = nullptr) {
-    const size_t tab = (size_t)h->cur_nrows * nlev;
-    CV.order = h->cur_order; CV.cum = h->cur_cum; CV.obase = h->cur_cum + tab; CV.nlev = nlev; CV.vstride = velems; CV.cpo = cpo; CV.ostride = ostride;
+void chain_views(const rsrec_t* h, size_t velems, int cpo, ChainView& CV, ChainView* CVp = nullptr) {
+    const rsrec_handle::RegionEntry& E = *h->cur_entry;
+    const size_t tab = (size_t)E.key.nb * E.key.nlev;
+    const int* cum = E.cum.as<int>();
+    CV.order = E.order.as<int>(); CV.cum = cum; CV.obase = cum + tab; CV.nlev = E.key.nlev; CV.vstride = velems; CV.cpo = cpo; CV.ostride = E.ostride;
     if (!CVp) return;
     *CVp = CV;
-    CVp->cum = h->cur_cum + 2 * tab; CVp->obase = h->cur_cum + 3 * tab;
+    CVp->cum = cum + 2 * tab; CVp->obase = cum + 3 * tab;
 }
 
 // timing of a call from its events: the whole call, the H|psi> kernels (or whatever hop_ev brackets), and the rest
@@ -1172,8 +871,8 @@ int mfma_workgroups_per_chain(const rsrec_t* h, int batch) {
 // launch size of a (level) pass: enough workgroups for the largest chain of the batch at that level, at most `full.x`
 // (the kernels' own active_workgroups() keeps each chain's work assignment independent of it)
 dim3 level_grid(const rsrec_t* h, dim3 full, int level) {
-    if (!h->cur_level_max || level < 0 || level >= (int)h->cur_level_max->size()) return full;
-    const int groups = (*h->cur_level_max)[level] / GROUP;
+    if (!h->cur_entry || level < 0 || level >= (int)h->cur_entry->level_max.size()) return full;
+    const int groups = h->cur_entry->level_max[level] / GROUP;
     return dim3(std::max(1, std::min((int)full.x, (groups + MF_WAVES - 1) / MF_WAVES)), full.y);
 }
 
@@ -1183,8 +882,8 @@ dim3 level_grid(const rsrec_t* h, dim3 full, int level) {
 // (measured: folding chains into longer-lived workgroups, i.e. LESS dynamic balancing, costs 10-25 %).
 dim3 s5_grid(const rsrec_t* h, dim3 full, int level) {
     int gx = full.x;
-    if (h->cur_level_max && level >= 0 && level < (int)h->cur_level_max->size()) {
-        const int groups = (*h->cur_level_max)[level] / GROUP;
+    if (h->cur_entry && level >= 0 && level < (int)h->cur_entry->level_max.size()) {
+        const int groups = h->cur_entry->level_max[level] / GROUP;
         gx = std::max(1, (groups + S5_WG_GROUPS - 1) / S5_WG_GROUPS);
         if (gx > 8) gx = (gx + 7) / 8 * 8;                 // same number of workgroups on every XCD
         if (h->opt_s5_cap > 0) gx = std::min(gx, (int)h->opt_s5_cap);
@@ -1302,8 +1001,8 @@ void launch_s5(rsrec_t* h, dim3 grid, const SpmmDims& SD0, const int* order, con
     // region has no active neighbour there and comes out as the zeros it already is -- and the main launch passes over them.
     bool octets = false, oct_aside = false;
     double pa_pairs = 0.0;
-    if (h->cur_level_groups && SD.level >= 0 && (size_t)(SD.level + 1) * op.ntau <= h->cur_level_groups->size() && op.ntau == h->nmax + h->ntype)
-        for (int t = 0; t < h->nmax; ++t) pa_pairs += (*h->cur_level_groups)[(size_t)SD.level * op.ntau + t];
+    if (E && SD.level >= 0 && (size_t)(SD.level + 1) * op.ntau <= E->level_groups.size() && op.ntau == h->nmax + h->ntype)
+        for (int t = 0; t < h->nmax; ++t) pa_pairs += E->level_groups[(size_t)SD.level * op.ntau + t];
     if (!multi && one < 0 && h->opt_s5_octet > 0 && h->nmax >= h->opt_s5_octet && !extra && E && SD.cpo == 1 && SD.nchains >= 2 && op.ntau == h->nmax + h->ntype &&
         2.0 * pa_pairs >= (double)h->nmax * SD.nchains && (double)GROUP * (double)(h->kk + 1) * BLD * 8.0 < 4294967296.0) {
         SpmmDims SO = SD;
@@ -1369,9 +1068,9 @@ void launch_s5(rsrec_t* h, dim3 grid, const SpmmDims& SD0, const int* order, con
         }
         launch_s5_one<TWO>(h, grid, SD, order, cum, iz, op, set, in, out, in2, nullptr, ntau, epi, -1);
     }
-    if (h->cur_level_groups && SD.level >= 0 && (size_t)(SD.level + 1) * op.ntau <= h->cur_level_groups->size() && SD.cpo == 1 && op.ntau == h->nmax + h->ntype)
+    if (E && SD.level >= 0 && (size_t)(SD.level + 1) * op.ntau <= E->level_groups.size() && SD.cpo == 1 && op.ntau == h->nmax + h->ntype)
         for (int t = 0; t < op.ntau; ++t) {
-            double groups = (*h->cur_level_groups)[(size_t)SD.level * op.ntau + t];
+            double groups = E->level_groups[(size_t)SD.level * op.ntau + t];
             if (octets && t < h->nmax) groups = (double)((SD.nchains + GROUP - 1) / GROUP);          // one group per octet of chains instead of one per chain
             h->n_hop_mfma_flop += groups * op.flops_per_group(set, t);
         }
@@ -1554,8 +1253,9 @@ int recursion_batch(rsrec_t* h, const RecursionCall& RC, const int32_t* seed_ato
     std::vector<double> coef, fr;
     stage_seeds(seed_atoms, seed_coef, c0, nb, RC.nseed, seeds0, coef);
     if (extra_coef) extra_coef(nb, RC.nseed, seeds0, coef);
-    b.nb = nb; b.ostride = h->kk;
-    XFER(upload_regions(h, seeds0.data(), nb, RC.nseed, RC.nlev, RC.napply, h->hoh != 0, RC.mfma, b.ostride, h->n_atom_steps, h->n_block_mult));
+    XFER(upload_regions(h, seeds0.data(), nb, RC.nseed, RC.nlev, RC.napply, h->hoh != 0, RC.mfma));
+    b.nb = nb; b.ostride = h->cur_entry->ostride;
+    h->n_atom_steps += h->cur_entry->atom_steps; h->n_block_mult += h->cur_entry->block_mults;
     h->n_req_flop += required_hop_flops(h, *RC.op);
     XFER(xfer_h2d(h, h->d_seed.p, seeds0.data(), seeds0.size() * 4));
     XFER(xfer_h2d(h, h->d_seedcoef.p, coef.data(), coef.size() * 8));
@@ -1566,7 +1266,7 @@ int recursion_batch(rsrec_t* h, const RecursionCall& RC, const int32_t* seed_ato
     }
     HIPCK(h, hipStreamSynchronize(h->stream));
     h->t_host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - th0).count();
-    chain_views(h, RC.nlev, RC.velems, 1, b.ostride, b.CV, &b.CVp);
+    chain_views(h, RC.velems, 1, b.CV, &b.CVp);
     b.grid_mf = dim3(std::max(1, std::min(mfma_workgroups_per_chain(h, RC.B), (b.ostride / GROUP + MF_WAVES - 1) / MF_WAVES)), nb);
     return RSREC_OK;
 }
@@ -1862,11 +1562,11 @@ int run_block_lanczos(rsrec_t* h, int nchains, int nseed, const int32_t* seed_at
             const Spmm5Operator& OP = *RC.op;
             // what the nodes hold BY VALUE: every pointer and dimension a kernel argument is made of
             std::vector<uintptr_t> key = {(uintptr_t)1 /*block Lanczos*/, (uintptr_t)nb, (uintptr_t)lld, (uintptr_t)nseed, (uintptr_t)hoh, (uintptr_t)ci, (uintptr_t)(rot != nullptr), (uintptr_t)kk,
-                                          (uintptr_t)h->cur_order, (uintptr_t)h->cur_cum, (uintptr_t)bt.ostride, (uintptr_t)OP.d_frag, (uintptr_t)OP.d_meta, (uintptr_t)OP.ntr,
+                                          (uintptr_t)bt.CV.order, (uintptr_t)bt.CV.cum, (uintptr_t)bt.ostride, (uintptr_t)OP.d_frag, (uintptr_t)OP.d_meta, (uintptr_t)OP.ntr,
                                           (uintptr_t)h->s4_op.frag_set(0), (uintptr_t)h->s4_op.meta_set(0), (uintptr_t)h->d_nbr.p, (uintptr_t)h->d_nbr5.p, (uintptr_t)h->d_iz.p,
                                           (uintptr_t)h->d_partial.p, (uintptr_t)h->d_partial2.p, (uintptr_t)h->d_frags.p, (uintptr_t)dA, (uintptr_t)dB, (uintptr_t)h->d_bmats.p,
                                           (uintptr_t)h->d_status.p, (uintptr_t)h->d_seed.p, (uintptr_t)h->d_seedcoef.p, (uintptr_t)h->d_la_extra.p, (uintptr_t)h->d_s5queue.p,
-                                          (uintptr_t)h->cur_entry, (uintptr_t)h->p2_slot, (uintptr_t)OP.single_class(0), (uintptr_t)OP.spin_mixing,
+                                          (uintptr_t)h->cur_entry->serial, (uintptr_t)h->p2_slot, (uintptr_t)OP.single_class(0), (uintptr_t)OP.spin_mixing,
                                           (uintptr_t)h->lattice_epoch, (uintptr_t)OP.sched_epoch, (uintptr_t)h->nslots, (uintptr_t)h->nmax, (uintptr_t)h->ntype, (uintptr_t)h->hslots,
                                           (uintptr_t)B, (uintptr_t)h->n_cu, (uintptr_t)h->d_gram.p, (uintptr_t)gram_eligible};
             for (int v = 0; v < nvec; ++v) key.push_back((uintptr_t)h->d_vec[v].p);
@@ -3300,23 +3000,6 @@ extern "C" int rsrec_chebyshev(rsrec_t* h, int nsites, const int32_t* seed_atoms
 // Pair moments from one chain per atom (kernels_fan.hpp): a sibling of run_chebyshev on the same RecursionCall / recursion_batch set-up
 namespace {
 
-// the level at which every atom joins the growing region of a chain seeded at `seed` (grow_region's rule: an atom joins when one of ITS
-// neighbour slots holds an atom already inside), -1: not within levels 0 .. nlev - 1
-void region_levels(const rsrec_t* h, int seed, int nlev, std::vector<int>& dist) {
-    dist.assign(h->kk, -1);
-    std::vector<int> frontier{seed}, next;
-    dist[seed] = 0;
-    for (int level = 0; !frontier.empty() && level + 1 < nlev; ++level) {
-        next.clear();
-        for (int n : frontier)
-            for (int q = h->radj_ptr[n]; q < h->radj_ptr[n + 1]; ++q) {
-                const int i = h->radj[q];
-                if (dist[i] < 0) { dist[i] = level + 1; next.push_back(i); }
-            }
-        frontier.swap(next);
-    }
-}
-
 // Sources, gathered blocks and pair records of a call.  Sources ascend by atom; a source's entries follow each other, its own block first.
 struct FanPlan {
     std::vector<int32_t> sources;          // 1-based atoms, as recursion_batch takes seeds
@@ -3353,7 +3036,8 @@ void fan_plan(const rsrec_t* h, int npairs, const int32_t* ijpair, int both_ends
     std::vector<int> dist;
     for (int s = 0; s < nsrc; ++s) {
         F.ent_begin[s] = (int)F.entries.size();
-        region_levels(h, F.sources[s] - 1, nlev, dist);
+        const int seed = F.sources[s] - 1;
+        region_levels(lattice_view(h), &seed, 1, nlev, dist);
         for (int atom0 : targets[s]) F.entries.push_back(FanEntry{s, atom0, dist[atom0], atom0 == F.sources[s] - 1 ? 1 : 0});
     }
     F.ent_begin[nsrc] = (int)F.entries.size();
@@ -3457,7 +3141,8 @@ void bloch_lists(const rsrec_t* h, const BlochCall& A, int c0, int nb, int nlev,
     T.tot.assign(nb, 0); T.maxcnt.assign((size_t)ng * nlev, 0);
     std::vector<int> dist, fill((size_t)ng * nlev);
     for (int c = 0; c < nb; ++c) {
-        region_levels(h, A.sources[c0 + c] - 1, nlev, dist);
+        const int seed = A.sources[c0 + c] - 1;
+        region_levels(lattice_view(h), &seed, 1, nlev, dist);
         int* cnt = T.count.data() + (size_t)c * ng * nlev;
         for (int j = 0; j < kk; ++j) {
             const int g = A.group ? A.group[j] : 1;
@@ -3688,13 +3373,11 @@ int whole_lattice_begin(rsrec_t* h, WholeLatticeCall& W, int chains_per_slot, bo
     const int kk = h->kk;
     const size_t velems = (size_t)(kk + 1) * BLD;
     std::vector<int> all(kk);
-    for (int i = 0; i < kk; ++i) all[i] = i;
-    int ostride = kk;
-    double dummy1 = 0, dummy2 = 0;
-    XFER(upload_regions(h, all.data(), 1, kk, 1, 1, false, grouped, ostride, dummy1, dummy2));
+    std::iota(all.begin(), all.end(), 0);
+    XFER(upload_regions(h, all.data(), 1, kk, 1, 1, false, grouped));
     W.h = h; W.timed = timed;
-    chain_views(h, 1, velems, chains_per_slot, ostride, W.CV);
-    W.SD = SpmmDims{kk, h->nslots, h->nmax, 1, chains_per_slot, ostride, 0, velems, W.CV.obase, chains_per_slot};
+    chain_views(h, velems, chains_per_slot, W.CV);
+    W.SD = SpmmDims{kk, h->nslots, h->nmax, 1, chains_per_slot, W.CV.ostride, 0, velems, W.CV.obase, chains_per_slot};
     W.grid = s5_grid(h, dim3(256, (unsigned)chains_per_slot), 0);
     W.iz = h->d_iz.as<int>();
     return RSREC_OK;
@@ -4771,15 +4454,13 @@ extern "C" int rsrec_scalar_lanczos(rsrec_t* h, int nsites, const int32_t* seed_
             seeds0[q] = seed_atoms[c0 + q] - 1;
             for (int l = 0; l < NB; ++l) { so[2 * (q * NB + l)] = seeds0[q]; so[2 * (q * NB + l) + 1] = l; }
         }
-        double dummy1 = 0, dummy2 = 0;
-        int ostride = kk;
-        rc = upload_regions(h, seeds0.data(), nb, 1, nlev, nsteps, false, false, ostride, dummy1, dummy2);
+        rc = upload_regions(h, seeds0.data(), nb, 1, nlev, nsteps, false, false);
         if (rc) return rc;
-        h->n_atom_steps += dummy1 * NB;
+        h->n_atom_steps += h->cur_entry->atom_steps * NB;
         XFER(xfer_h2d(h, h->d_seed.p, so.data(), so.size() * 4));
         HIPCK(h, hipStreamSynchronize(h->stream));
         ChainView CV;
-        chain_views(h, nlev, velems, NB, ostride, CV);
+        chain_views(h, velems, NB, CV);
         for (int v = 0; v < 2; ++v) HIPCK(h, hipMemsetAsync(h->d_vec[v].p, 0, (size_t)nc * velems * sizeof(double2), h->stream));
         HIPCK(h, hipMemsetAsync(ca, 0, (size_t)nch * 2 * lld * sizeof(double), h->stream));
         k_scalar_seed<<<nc, 64, 0, h->stream>>>(psi, velems, h->d_seed.as<int>(), cb, lld);

@@ -161,3 +161,34 @@ def random_vec_coefficients(rng):
     coefs = np.ascontiguousarray((np.exp(2.0 * np.pi * 1j * rng) / norm).T)
     seeds = np.tile(np.arange(1, kk + 1, dtype=np.int32), (nvec, 1))
     return seeds, coefs
+
+
+def random_problem(rng, kk, nslots, ntype, nmax, hoh, collinear):
+    """Random ragged lattice with random operator blocks: up to `nslots` slots, atoms with fewer slots and absent neighbours, `ntype` types,
+    per-atom blocks for the first `nmax` atoms (plain numpy: the GPU tests and the CPU test of the region planner share it)."""
+    nn = np.zeros((kk, nslots + 1), np.int32, order="F")
+    for k in range(kk):
+        nr = nslots if k % 7 else int(rng.integers(1, nslots + 1))     # most atoms full, some with fewer slots
+        nn[k, 0] = nr
+        for nb in range(2, nr + 1):
+            nn[k, nb - 1] = 0 if rng.random() < 0.1 else int(rng.integers(1, kk + 1))   # 0 = absent neighbour
+    nn[kk - 1, 0] = nslots                                               # at least one atom uses every slot
+    iz = rng.integers(1, ntype + 1, kk).astype(np.int32)
+
+    def blocks(n, last):
+        a = (rng.standard_normal((18, 18, n, last)) + 1j * rng.standard_normal((18, 18, n, last))) * 0.2
+        if collinear:                                                    # hopping blocks of a collinear magnet: no spin-flip part
+            a[:9, 9:] = 0
+            a[9:, :9] = 0
+        return np.asfortranarray(a)
+
+    p = dict(nn=nn, iz=iz, nmax=nmax, hoh=int(hoh), nsp=2, ee=blocks(nslots, ntype),
+             lsham=np.asfortranarray((rng.standard_normal((18, 18, ntype)) + 1j * rng.standard_normal((18, 18, ntype))) * 0.1))
+    if nmax:
+        p["hall"] = blocks(nslots, nmax)
+    if hoh:
+        p["eeo"] = blocks(nslots, ntype)
+        p["enim"] = np.asfortranarray((rng.standard_normal((18, 18, ntype)) + 1j * rng.standard_normal((18, 18, ntype))) * 0.1)
+        if nmax:
+            p["hallo"] = blocks(nslots, nmax)
+    return p

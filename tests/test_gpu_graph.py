@@ -96,6 +96,37 @@ def test_graph_recaptures_when_the_lattice_changes_on_the_same_handle():
     rec.close()
 
 
+def test_graph_survives_the_eviction_of_the_region_cache():
+    """The region cache drops everything at 256 entries, and the captured level loop -- which holds the lists' addresses, grids and fold
+    decisions by value -- must go with it: 256 calls with other site pairs between two calls with (1, 77) cross the eviction with a live graph
+    (a freed entry or list commonly comes back at the same address).  Every call must give the bits of the launch-per-kernel path."""
+    p = supercell_problem((4, 4, 8))
+    rec = Recursion(*objects_from(p, np.array([1, 77], dtype=np.int32), 4), device=0)
+
+    def run(sites, graph):
+        rec.lattice.irec = np.array(sites, dtype=np.int32)
+        rec.set_option("graph", graph)
+        rec.a_b[:] = 0
+        rec.b2_b[:] = 0
+        rec.recur_b()
+        return rec.a_b.copy(), rec.b2_b.copy()
+
+    def same(x, y):
+        return np.array_equal(x[0], y[0]) and np.array_equal(x[1], y[1])
+
+    first = run((1, 77), 1)                              # capture
+    assert same(run((1, 77), 1), first)                  # replay
+    others = [(a, (a + d) % 128 + 1) for a in range(1, 129) for d in (0, 1)]
+    assert len(set(others)) == 256 and (1, 77) not in others
+    for k, sites in enumerate(others):
+        out = run(sites, 1)
+        if k % 32 == 0:
+            assert same(run(sites, 0), out), sites
+    assert same(run((1, 77), 1), first)
+    assert same(run((1, 77), 0), first)
+    rec.close()
+
+
 def test_allreduce_sum_counts_complex_images_in_doubles():
     """One-rank communicator = identity; what is checked is the marshalling: a complex128 F-ordered image is 2 doubles per element, and
     anything that is not float64 / complex128 is refused (round-3 advisor finding: operator precedence let every F-ordered array through)."""

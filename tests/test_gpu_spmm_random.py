@@ -7,39 +7,10 @@ blocks, with and without hoh.  The schedule of the kernel (a stream of 9-orbital
 import numpy as np
 import pytest
 
-from helpers import objects_from
+from helpers import objects_from, random_problem  # noqa: F401  (random_problem: other test modules import it from here)
 from rslmtoasa_amd.recursion import Recursion
 
 pytestmark = pytest.mark.gpu
-
-
-def random_problem(rng, kk, nslots, ntype, nmax, hoh, collinear):
-    nn = np.zeros((kk, nslots + 1), np.int32, order="F")
-    for k in range(kk):
-        nr = nslots if k % 7 else int(rng.integers(1, nslots + 1))     # most atoms full, some with fewer slots
-        nn[k, 0] = nr
-        for nb in range(2, nr + 1):
-            nn[k, nb - 1] = 0 if rng.random() < 0.1 else int(rng.integers(1, kk + 1))   # 0 = absent neighbour
-    nn[kk - 1, 0] = nslots                                               # at least one atom uses every slot
-    iz = rng.integers(1, ntype + 1, kk).astype(np.int32)
-
-    def blocks(n, last):
-        a = (rng.standard_normal((18, 18, n, last)) + 1j * rng.standard_normal((18, 18, n, last))) * 0.2
-        if collinear:                                                    # hopping blocks of a collinear magnet: no spin-flip part
-            a[:9, 9:] = 0
-            a[9:, :9] = 0
-        return np.asfortranarray(a)
-
-    p = dict(nn=nn, iz=iz, nmax=nmax, hoh=int(hoh), nsp=2, ee=blocks(nslots, ntype),
-             lsham=np.asfortranarray((rng.standard_normal((18, 18, ntype)) + 1j * rng.standard_normal((18, 18, ntype))) * 0.1))
-    if nmax:
-        p["hall"] = blocks(nslots, nmax)
-    if hoh:
-        p["eeo"] = blocks(nslots, ntype)
-        p["enim"] = np.asfortranarray((rng.standard_normal((18, 18, ntype)) + 1j * rng.standard_normal((18, 18, ntype))) * 0.1)
-        if nmax:
-            p["hallo"] = blocks(nslots, nmax)
-    return p
 
 
 def apply_blocks(p, x, use_o):
