@@ -420,6 +420,18 @@ module rsrec_binding
          integer(c_int) :: rc
       end function
 
+      !> as rsrec_chebyshev_bloch; w: complex (2*lld+2,ne); g_k: complex (18,18,ne,nk,ngroup,nsrc), a_k: real (18,ne,nk,ngroup,nsrc),
+      !> host or device memory, either one c_null_ptr
+      function rsrec_chebyshev_bloch_map(handle, nsrc, sources, lld, a, b, cr, cell, nk, kpt, ngroup, group, ne, w, g_k, a_k) &
+         bind(C, name='rsrec_chebyshev_bloch_map') result(rc)
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: handle
+         integer(c_int), value :: nsrc, lld, nk, ngroup, ne
+         real(c_double), value :: a, b
+         type(c_ptr), value :: sources, cr, cell, kpt, group, w, g_k, a_k
+         integer(c_int) :: rc
+      end function
+
       !> seed_atoms: int32 (nseed,nchains), 0 = unused entry; seed_coef: complex (nseed,nchains); group: int32 (kk) or c_null_ptr;
       !> m_g: complex (18,18,2*lld+2,ngroup,nchains), host or device memory, or c_null_ptr
       function rsrec_chebyshev_lattice(handle, nchains, nseed, seed_atoms, seed_coef, lld, a, b, ngroup, group, m_g) &

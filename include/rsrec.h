@@ -327,6 +327,44 @@ int rsrec_chebyshev_pairs_direct(rsrec_t *h, int npairs, const int32_t *ijpair, 
 int rsrec_chebyshev_bloch(rsrec_t *h, int nsrc, const int32_t *sources, int lld, double a, double b, const double *cr, const double *cell,
                           int nk, const double *kpt, int ngroup, const int32_t *group, double *s_k);
 
+/* Functions of H at MANY k-points and a FEW energies from one chain per atom: constant-energy maps A(k, E_F) on dense 2-D grids, layer-resolved
+ * cuts of slabs (no counterpart in the reference).  rsrec_chebyshev_bloch Bloch-sums the vector of every order and keeps every moment of every
+ * k-point; here the sums are taken in the other order.  With psi_n = T_n(H~)|i> the vector the chain forms anyway,
+ *   Y_e = sum_n w(n,e) psi_{n-1},      g_k(:,:,e,q,g,s) = sum_{j in group g, in the final region of source s} exp(-i k_q.d(j,i_s)) [Y_e]_j
+ *                                                       = sum_n w(n,e) s_k(:,:,n,q,g,s)   of rsrec_chebyshev_bloch,
+ * at the cost of ne complex axpys per order and ONE Bloch sum per energy behind the last order: nothing grows as orders x k-points.
+ *   sources, lld, a, b, cr, cell, kpt, ngroup, group : exactly as rsrec_chebyshev_bloch -- the same chain (three-term recurrence, 2*lld+1
+ *             applications, twice the launches with hoh), minimum-image rule and groups --, with 1 <= nk <= RSREC_BLOCH_MAP_NK_MAX.
+ *   w       : complex (2*lld+2, ne), column-major, host memory: row n weights order n-1.  1 <= ne <= RSREC_BLOCH_MAP_NE_MAX.  The library does
+ *             not interpret the weights: the kernel-weighted coefficients of rsrec_chebyshev_green,
+ *               w(n,e) = jackson(n) (2 for n > 1) (-i exp(-i (n-1) acos x_e)) / sqrt(a^2 - (E_e - b)^2),   x_e = (E_e - b)/a,
+ *             give G(k,E); others give other functions of H (a Fermi function: occupations n(k)).
+ *   g_k     : complex (18,18,ne,nk,ngroup,nsrc) out, host or device memory (detected), or NULL: the layout of s_k with the energy in the
+ *             moment's place.
+ *   a_k     : real (18,ne,nk,ngroup,nsrc) out, host or device memory (detected), or NULL: -Im g_k(l,l,...)/pi, formed on the device from the
+ *             same blocks -- bit for bit the diagonal of g_k; a dense map that only wants orbital weights downloads 144 B per point and
+ *             energy instead of 5 184 B.  At least one of g_k and a_k is given.
+ * Nothing is normalised, and only the sum over the groups has a non-negative spectral weight (a single group's image is not Hermitian).
+ * An atom contributes to Y_e from the order at which it joins the source's region; nothing outside the region of the current level is read
+ * or written, and the Y_e of a batch are cleared before the seed.  The accumulation is one streaming pass per two orders (option
+ * "blochmap_orders" = 1: per order; the same bits), 1 + 2 ne block streams per atom (kernels_blochmap.hpp).  Behind the last order the
+ * k-points are taken in chunks: phase table, per energy and group the GEMM and reduce kernels of rsrec_chebyshev_bloch on Y_e, the diagonal,
+ * and the chunk's slice of the outputs.  The accumulators, ONE chunk's table and partials are charged per chain when the batch is planned:
+ * a call with large ne runs a smaller batch.  The call leaves no resident image, and drops what an earlier call left.
+ * Every sum runs in a fixed order without atomics: the bits of g_k(:,:,e,q,g,s) depend only on its own k-point, column e of w, the atom set
+ * of its own group and its own source -- not on the other k-points, energies, groups or sources of the call, on ne or nk, on how the
+ * k-points are cut into chunks, on options batch and blochmap_orders, or on what earlier calls left in the work buffers.  Both kernel sets
+ * (option kernels), hoh and per-atom operator blocks are served.
+ * RSREC_ERR_DIVERGED as rsrec_chebyshev_bloch (the source's own block at every order).  RSREC_ERR_ARG with a message, the handle staying
+ * usable, for everything rsrec_chebyshev_bloch refuses (nk against RSREC_BLOCH_MAP_NK_MAX), ne out of range, NULL w, a non-finite weight,
+ * g_k and a_k both NULL.  nsrc = 0 returns RSREC_OK.
+ * rsrec_get_timing: out[0] device ms, out[1] ms in the H|psi> launches, out[2] their number, out[5] ms in the accumulation passes, the
+ * phase tables and the final sums together, out[14], out[15], out[16] the three apart. */
+#define RSREC_BLOCH_MAP_NE_MAX 16
+#define RSREC_BLOCH_MAP_NK_MAX 1048576
+int rsrec_chebyshev_bloch_map(rsrec_t *h, int nsrc, const int32_t *sources, int lld, double a, double b, const double *cr, const double *cell,
+                              int nk, const double *kpt, int ngroup, const int32_t *group, int ne, const double *w, double *g_k, double *a_k);
+
 /* Chebyshev moments from whole-lattice seeds (no counterpart in the reference).  rsrec_chebyshev_pairs_direct and rsrec_chebyshev_bloch start
  * every chain from ONE atom -- right for a perfect crystal, where every source gives the same answer.  Here the seed covers the lattice,
  * |x> = sum_j c_j |j> (x) 1_18, and the moment is the seed-weighted sum of the vector's own blocks, group by group:
@@ -741,6 +779,7 @@ int rsrec_set_option(rsrec_t *h, const char *key, long value);
  *   out[11] H|psi> launches of the last call in which the atoms with their own operator blocks were grouped over 8 chains (option "s5_octet").
  *   out[12] rsrec_block_lanczos_local_axis: ms in the conjugation of the resident coefficients with the sites' rotations (part of out[5]).
  *   out[13] H|psi> launches of the last call whose epilogue formed the A_n Gram of at least one chain (option "s5_gram_min").
+ *   out[14..16] rsrec_chebyshev_bloch_map: ms in the accumulation passes, the phase tables and the final sums (together: out[5]).
  * After rsrec_block_green: out[0] = kernel + transfers, out[1] = the Green kernel alone. */
 int rsrec_get_timing(rsrec_t *h, double *out, int n);
 

@@ -50,6 +50,7 @@
 #include "kernels_assemble.hpp"
 #include "kernels_fan.hpp"
 #include "kernels_bloch.hpp"
+#include "kernels_blochmap.hpp"
 #include "kernels_lattice.hpp"
 
 using namespace rsrec;
@@ -148,6 +149,7 @@ struct rsrec_handle {
     DevBuf d_frags, d_vec[6], d_partial, d_partial2, d_coefA, d_coefB, d_bmats, d_status, d_seed, d_seedcoef, d_mu, d_scal, d_zsqr;
     DevBuf d_fan, d_fan_tab, d_mpair;   // rsrec_chebyshev_pairs_direct: gathered blocks M(18,18,nmom,entry); entry and pair tables; M_ij / M_ji of every pair
     DevBuf d_bloch_geo, d_bloch_tab;    // rsrec_chebyshev_bloch: positions and k-points of the call; lists, segment offsets and level counts of a batch
+    DevBuf d_map_w;                     // rsrec_chebyshev_bloch_map: the weights w(n, e) of the call
     DevBuf d_lat_tab, d_lat_w, d_lat_part;   // rsrec_chebyshev_lattice: lists and offsets of a batch; weights and divergence bounds; split partials
     // options
     long opt_batch = 0, opt_kernels = 0, opt_nblk = 0, opt_spmm5 = 2, opt_chain_fold = 1, opt_s5_cap = 0, opt_side = 1, opt_s5_lds = 1, opt_s5_queue = 1, opt_cheb_fused = 1;
@@ -162,6 +164,8 @@ struct rsrec_handle {
     long opt_kubo_lchunk = 0;    // rsrec_kubo_moments: left vectors held at a time (0: as many as fit)
     long opt_kubo_vbatch = 0;    // rsrec_kubo_moments: random vectors advanced together as the chains of one launch (0: up to 8, as many as fit beside a whole left matrix)
     long opt_lattice_vbatch = 0; // rsrec_chebyshev_lattice: chains advanced together as the chains of one launch (0: up to 8, as many as fit)
+    long opt_blochmap_orders = 2;  // rsrec_chebyshev_bloch_map: orders added to the accumulators per pass (1 | 2: same bits, see kernels_blochmap.hpp)
+    long opt_blochmap_kchunk = 0;  // rsrec_chebyshev_bloch_map: k-points per chunk of the final sums (0: 256, one launch's rows of the phase matrix); tests force it small
     long opt_kubo_setgroup = 0;  // rsrec_kubo_moments_diag_tensor: sets of a vector contracted against one staged left tile (k_kubo_gram_diag_sets): 0 default (2), 1 every set by itself (k_kubo_gram_diag), 2 / 3 groups of at most that width
     int n_kubo_left_chunks = 0;
     int kubo_diag_nvec = 0, kubo_diag_ll = 0;   // rsrec_kubo_moments_diag / _multi / _tensor: the call whose diagonal moments lie in d_kubo[4] (0: nothing resident; _multi: nvec * nout; _tensor: nvec * nout * nin)
@@ -185,6 +189,7 @@ struct rsrec_handle {
     // timing of last call
     double t_total_ms = 0, t_hop_ms = 0, t_rest_ms = 0, t_host_ms = 0;
     double t_rot_ms = 0;      // local-axis recursion: ms in k_rotate_coef (part of t_rest_ms)
+    double t_map_ms[3] = {0, 0, 0};   // rsrec_chebyshev_bloch_map: ms in the accumulation passes, the phase tables, the final sums (their sum: t_rest_ms)
     double n_hop_launch = 0, n_atom_steps = 0, n_block_mult = 0, n_hop_mfma_flop = 0;   // mfma_flop: matrix flops EXECUTED by the timed k_spmm5 launches
     double n_req_flop = 0;    // flops of H|psi> the operator's block structure requires (spin-diagonal blocks: half a zgemm), see required_hop_flops
     int hop_fuses_a = 1;      // 1: the timed H|psi> kernel also forms pmn and the A_n partial (VALU path); 0: pure SpMM (MFMA path)
@@ -240,6 +245,8 @@ const OptionEntry OPTIONS[] = {
     {"kubo_vbatch", &rsrec_handle::opt_kubo_vbatch},
     {"kubo_setgroup", &rsrec_handle::opt_kubo_setgroup},
     {"lattice_vbatch", &rsrec_handle::opt_lattice_vbatch},
+    {"blochmap_orders", &rsrec_handle::opt_blochmap_orders},
+    {"blochmap_kchunk", &rsrec_handle::opt_blochmap_kchunk},
     {"s5_host_emit", &rsrec_handle::opt_s5_host_emit},
     {"s5_octet", &rsrec_handle::opt_s5_octet},
     {"s5_spin_xcd", &rsrec_handle::opt_s5_spin_xcd},
@@ -407,9 +414,9 @@ extern "C" int rsrec_set_option(rsrec_t* h, const char* key, long value) {
 
 extern "C" int rsrec_get_timing(rsrec_t* h, double* out, int n) {
     if (!h || !out) return RSREC_ERR_ARG;
-    const double v[14] = {h->t_total_ms, h->t_hop_ms, h->n_hop_launch, h->n_atom_steps, h->n_block_mult, h->t_rest_ms, h->t_host_ms, (double)h->hop_fuses_a, h->n_hop_mfma_flop,
-                          h->n_req_flop, (double)h->n_asm_reused, (double)h->n_octet_launch, h->t_rot_ms, h->n_gram_folded};
-    for (int i = 0; i < n && i < 14; ++i) out[i] = v[i];
+    const double v[17] = {h->t_total_ms, h->t_hop_ms, h->n_hop_launch, h->n_atom_steps, h->n_block_mult, h->t_rest_ms, h->t_host_ms, (double)h->hop_fuses_a, h->n_hop_mfma_flop,
+                          h->n_req_flop, (double)h->n_asm_reused, (double)h->n_octet_launch, h->t_rot_ms, h->n_gram_folded, h->t_map_ms[0], h->t_map_ms[1], h->t_map_ms[2]};
+    for (int i = 0; i < n && i < 17; ++i) out[i] = v[i];
     return RSREC_OK;
 }
 
@@ -769,6 +776,7 @@ double required_hop_flops(const rsrec_t* h, const Spmm5Operator& op) {
 
 void reset_timing(rsrec_t* h) {
     h->t_total_ms = h->t_hop_ms = h->t_rest_ms = h->t_host_ms = h->t_rot_ms = 0;
+    h->t_map_ms[0] = h->t_map_ms[1] = h->t_map_ms[2] = 0;
     h->n_hop_launch = h->n_atom_steps = h->n_block_mult = h->n_hop_mfma_flop = h->n_req_flop = 0;
     h->n_octet_launch = 0;
     h->n_gram_folded = h->n_gram_all = h->n_gram_levels = 0;
@@ -3134,11 +3142,12 @@ struct BlochCall {
 
 // The lists of a batch's chains as BlochLists takes them: per chain one segment per group, the group's atoms sorted by (level at which the
 // atom joins the chain's region, atom); atoms the region never reaches are left out.  maxcnt[group][level]: the longest list of the batch.
-struct BlochBatchLists { std::vector<int> list, seg_off, count, tot, maxcnt; };
+// join[chain][kk]: that level for every atom on a list, INT_MAX for the others (the accumulation pass of run_bloch_map walks the atoms in order).
+struct BlochBatchLists { std::vector<int> list, seg_off, count, tot, maxcnt, join; };
 void bloch_lists(const rsrec_t* h, const BlochCall& A, int c0, int nb, int nlev, BlochBatchLists& T) {
     const int kk = h->kk, ng = A.ngroup;
     T.list.assign((size_t)nb * kk, 0); T.seg_off.assign((size_t)nb * ng, 0); T.count.assign((size_t)nb * ng * nlev, 0);
-    T.tot.assign(nb, 0); T.maxcnt.assign((size_t)ng * nlev, 0);
+    T.tot.assign(nb, 0); T.maxcnt.assign((size_t)ng * nlev, 0); T.join.assign((size_t)nb * kk, INT_MAX);
     std::vector<int> dist, fill((size_t)ng * nlev);
     for (int c = 0; c < nb; ++c) {
         const int seed = A.sources[c0 + c] - 1;
@@ -3156,7 +3165,7 @@ void bloch_lists(const rsrec_t* h, const BlochCall& A, int c0, int nb, int nlev,
         T.tot[c] = off;
         for (int j = 0; j < kk; ++j) {
             const int g = A.group ? A.group[j] : 1;
-            if (g > 0 && dist[j] >= 0) T.list[(size_t)c * kk + fill[(size_t)(g - 1) * nlev + dist[j]]++] = j;
+            if (g > 0 && dist[j] >= 0) { T.list[(size_t)c * kk + fill[(size_t)(g - 1) * nlev + dist[j]]++] = j; T.join[(size_t)c * kk + j] = dist[j]; }
         }
         for (int g = 0; g < ng; ++g) {
             int run = 0;
@@ -3246,13 +3255,13 @@ int run_bloch(rsrec_t* h, const BlochCall& A) {
 
 }  // namespace
 
-extern "C" int rsrec_chebyshev_bloch(rsrec_t* h, int nsrc, const int32_t* sources, int lld, double a, double b, const double* cr, const double* cell,
-                                     int nk, const double* kpt, int ngroup, const int32_t* group, double* s_k) {
-    const char* who = "rsrec_chebyshev_bloch";
-    int rc = check_ready(h, who);
-    if (rc) return rc;
+namespace {
+
+// The argument checks rsrec_chebyshev_bloch and rsrec_chebyshev_bloch_map share (nk_max: the call's own limit); fills the cell's geometry
+int bloch_check_args(rsrec_t* h, const char* who, int nsrc, const int32_t* sources, int lld, double a, const double* cr, const double* cell, int nk, int nk_max,
+                     const double* kpt, int ngroup, const int32_t* group, BlochGeom& G) {
     if (nsrc < 0 || lld < 1 || a == 0.0) return fail(h, RSREC_ERR_ARG, "%s: nsrc < 0, lld < 1 or a == 0", who);
-    if (nk < 1 || nk > RSREC_BLOCH_NK_MAX) return fail(h, RSREC_ERR_ARG, "%s: nk = %d outside 1..%d", who, nk, RSREC_BLOCH_NK_MAX);
+    if (nk < 1 || nk > nk_max) return fail(h, RSREC_ERR_ARG, "%s: nk = %d outside 1..%d", who, nk, nk_max);
     if (ngroup < 1 || ngroup > RSREC_BLOCH_NGROUP_MAX) return fail(h, RSREC_ERR_ARG, "%s: ngroup = %d outside 1..%d", who, ngroup, RSREC_BLOCH_NGROUP_MAX);
     if (!cr || !kpt || (nsrc > 0 && !sources)) return fail(h, RSREC_ERR_ARG, "%s: NULL sources, cr or kpt", who);
     if (!group && ngroup != 1) return fail(h, RSREC_ERR_ARG, "%s: ngroup = %d needs a group array", who, ngroup);
@@ -3261,8 +3270,8 @@ extern "C" int rsrec_chebyshev_bloch(rsrec_t* h, int nsrc, const int32_t* source
             if (group[j] < 0 || group[j] > ngroup) return fail(h, RSREC_ERR_ARG, "%s: group(%d) = %d outside 0..%d", who, j + 1, group[j], ngroup);
     XFER(check_seeds(h, who, sources, (size_t)nsrc, 1));
     if ((size_t)nk * ngroup * (size_t)nsrc > (size_t)INT32_MAX) return fail(h, RSREC_ERR_ARG, "%s: nk * ngroup * nsrc exceeds the index range", who);
-    BlochCall A{nsrc, lld, nk, ngroup, sources, group, a, b, cr, kpt, BlochGeom{}, s_k};
-    A.G.wrap = cell ? 1 : 0;
+    G = BlochGeom{};
+    G.wrap = cell ? 1 : 0;
     if (cell) {
         const double* c = cell;                                  // column-major: c[3 col + row]
         const double cof[9] = {c[4] * c[8] - c[5] * c[7], c[5] * c[6] - c[3] * c[8], c[3] * c[7] - c[4] * c[6],
@@ -3274,12 +3283,173 @@ extern "C" int rsrec_chebyshev_bloch(rsrec_t* h, int nsrc, const int32_t* source
         if (!std::isfinite(det) || !(std::fabs(det) > 1e-12 * len)) return fail(h, RSREC_ERR_ARG, "%s: singular cell", who);
         // inv(row i, col j) = cof(j, i) / det with cof[3 j + i] the cofactor of c(i, j) as laid out above
         for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) { A.G.cell[3 * j + i] = c[3 * j + i]; A.G.inv[3 * j + i] = cof[3 * i + j] / det; }
+            for (int j = 0; j < 3; ++j) { G.cell[3 * j + i] = c[3 * j + i]; G.inv[3 * j + i] = cof[3 * i + j] / det; }
     }
+    return RSREC_OK;
+}
+
+}  // namespace
+
+extern "C" int rsrec_chebyshev_bloch(rsrec_t* h, int nsrc, const int32_t* sources, int lld, double a, double b, const double* cr, const double* cell,
+                                     int nk, const double* kpt, int ngroup, const int32_t* group, double* s_k) {
+    const char* who = "rsrec_chebyshev_bloch";
+    int rc = check_ready(h, who);
+    if (rc) return rc;
+    BlochCall A{nsrc, lld, nk, ngroup, sources, group, a, b, cr, kpt, BlochGeom{}, s_k};
+    XFER(bloch_check_args(h, who, nsrc, sources, lld, a, cr, cell, nk, RSREC_BLOCH_NK_MAX, kpt, ngroup, group, A.G));
     HIPCK(h, hipSetDevice(h->device));
     reset_timing(h);
     if (nsrc == 0) return RSREC_OK;
     return matrix_core_set(h) ? run_bloch<true>(h, A) : run_bloch<false>(h, A);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Functions of H at many k-points from one chain per atom (kernels_blochmap.hpp): a sibling of run_bloch on the same chain and the same lists --
+// behind the seed and every H|psi> launch the vector is added into ne weighted sums Y_e instead of being Bloch-summed, and ONE Bloch sum per
+// energy follows the last order, a chunk of k-points at a time
+namespace {
+
+struct BlochMapCall {
+    BlochCall B;                 // sources, window, geometry, k-points and groups as rsrec_chebyshev_bloch takes them (s_k unused)
+    int ne;
+    const double* w;             // complex (2 lld + 2, ne)
+    double *g_k, *a_k;
+};
+
+template <bool MFMA>
+int run_bloch_map(rsrec_t* h, const BlochMapCall& M) {
+    const BlochCall& A = M.B;
+    const bool hoh = h->hoh != 0, two = h->opt_blochmap_orders != 1;
+    const int kk = h->kk, nsrc = A.nsrc, nk = A.nk, ng = A.ngroup, ne = M.ne;
+    const int napply = 2 * A.lld + 1, nmom = 2 * A.lld + 2;
+    // k-points per chunk of the final sums: one launch's rows of the phase matrix unless the option says otherwise.  A point's bits do not
+    // depend on it: the rows of the phase matrix are independent in the product.
+    const int kchunk = (int)std::min<long>(nk, h->opt_blochmap_kchunk > 0 ? h->opt_blochmap_kchunk : BLOCH_MCHUNK / 2);
+    auto pad_rows = [](int nq) { return (2 * nq + BLOCH_MROWS - 1) / BLOCH_MROWS * BLOCH_MROWS; };
+    const int mpad_max = pad_rows(kchunk);
+    RecursionCall RC = recursion_call(h, MFMA, nsrc, 1, napply);
+    if (MFMA) RC.ci = 1;
+    const size_t velems = RC.velems;
+    // an output in device memory is written in place by the kernels; a host array gets the chunk's images from a staging buffer
+    const bool g_dev = M.g_k && is_device_ptr(M.g_k), a_dev = M.a_k && is_device_ptr(M.a_k);
+    drop_resident(h);                                            // the call leaves no image, and what an earlier call left goes with the buffers
+    HIPCK(h, h->d_bloch_geo.reserve((size_t)3 * (kk + nk) * sizeof(double)));
+    HIPCK(h, h->d_map_w.reserve((size_t)nmom * ne * sizeof(double2)));
+    // per chain, charged in the batch plan with the work vectors: the accumulators, the phase table and the partials of ONE chunk, its staged images
+    const size_t acc_doubles = (size_t)ne * velems, tab_doubles = (size_t)kk * mpad_max, part_doubles = (size_t)BLOCH_MAXSPLIT * std::min(mpad_max, BLOCH_MCHUNK) * BLD;
+    const size_t sg_doubles = g_dev ? 0 : (size_t)kchunk * ng * ne * 2 * BLK, sa_doubles = M.a_k && !a_dev ? (size_t)kchunk * ng * ne * NB : 0;
+    XFER(recursion_begin(h, RC, MFMA ? (hoh ? 5 : 4) : (hoh ? 4 : 3), MFMA ? 3 : -1, 1, acc_doubles + tab_doubles + part_doubles + sg_doubles + sa_doubles));
+    double* Y = h->d_gram.as<double>();
+    double* table = Y + (size_t)RC.B * acc_doubles;
+    double* partial = table + (size_t)RC.B * tab_doubles;
+    double* stage_g = partial + (size_t)RC.B * part_doubles;
+    double* stage_a = stage_g + (size_t)RC.B * sg_doubles;
+    double2* g_out = g_dev ? reinterpret_cast<double2*>(M.g_k) : reinterpret_cast<double2*>(stage_g);
+    double* a_out = a_dev ? M.a_k : stage_a;
+    double *d_cr = h->d_bloch_geo.as<double>(), *d_kpt = d_cr + (size_t)3 * kk;
+    XFER(xfer_h2d(h, d_cr, A.cr, (size_t)3 * kk * sizeof(double)));
+    XFER(xfer_h2d(h, d_kpt, A.kpt, (size_t)3 * nk * sizeof(double)));
+    XFER(xfer_h2d(h, h->d_map_w.p, M.w, (size_t)nmom * ne * sizeof(double2)));
+    const double2* d_w = h->d_map_w.as<double2>();
+    const size_t n_list = (size_t)RC.B * kk, n_off = (size_t)RC.B * ng, n_cnt = n_off * RC.nlev;
+    HIPCK(h, h->d_bloch_tab.reserve((2 * n_list + n_off + n_cnt + RC.B) * sizeof(int)));
+    int *d_list = h->d_bloch_tab.as<int>(), *d_off = d_list + n_list, *d_cnt = d_off + n_off, *d_tot = d_cnt + n_cnt, *d_join = d_tot + RC.B;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> map_ev[3];    // accumulation passes | phase tables | final sums
+    BlochBatchLists T;
+    const int last = RC.nlev - 1;                                // the region level of the last order
+    const dim3 acc_grid((unsigned)(((size_t)kk * BLK + MAP_WG_ELEMS - 1) / MAP_WG_ELEMS), 1);
+    for (int c0 = 0; c0 < nsrc; c0 += RC.B) {
+        const int nb = std::min(RC.B, nsrc - c0);
+        RecursionBatch bt;
+        XFER(recursion_batch(h, RC, A.sources, nullptr, c0, nb, bt));
+        bloch_lists(h, A, c0, nb, RC.nlev, T);
+        XFER(xfer_h2d(h, d_list, T.list.data(), (size_t)nb * kk * sizeof(int)));
+        XFER(xfer_h2d(h, d_off, T.seg_off.data(), (size_t)nb * ng * sizeof(int)));
+        XFER(xfer_h2d(h, d_cnt, T.count.data(), (size_t)nb * ng * RC.nlev * sizeof(int)));
+        XFER(xfer_h2d(h, d_tot, T.tot.data(), (size_t)nb * sizeof(int)));
+        XFER(xfer_h2d(h, d_join, T.join.data(), (size_t)nb * kk * sizeof(int)));
+        const BlochLists BL{d_list, d_off, d_cnt, kk, ng, RC.nlev};
+        const int* d_src = h->d_seed.as<int>();                  // (one seed per chain: the batch's 0-based source atoms)
+        HIPCK(h, hipMemsetAsync(Y, 0, (size_t)nb * acc_doubles * sizeof(double), h->stream));
+        // Y_e += w(n, e) psi_n on the atoms inside at the order's level; with two orders per pass the odd orders add the vector before them too
+        const double* prev = nullptr;
+        int prev_level = 0;
+        auto accum_pass = [&](const double* vec, int level, int n) {
+            hipEvent_t e0 = next_event(h);
+            if (MFMA) k_bloch_diverge<LayoutCI><<<nb, BLOCH_THREADS, 0, h->stream>>>(vec, velems, d_src, h->d_status.as<int>());
+            else k_bloch_diverge<LayoutCM><<<nb, BLOCH_THREADS, 0, h->stream>>>(vec, velems, d_src, h->d_status.as<int>());
+            const dim3 grid(acc_grid.x, nb);
+            const double2 *x = reinterpret_cast<const double2*>(vec), *xo = reinterpret_cast<const double2*>(prev);
+            if (!two) k_map_accum<false><<<grid, MAP_THREADS, 0, h->stream>>>(d_join, kk, level, level, x, x, velems / 2, d_w, n, nmom, ne, reinterpret_cast<double2*>(Y));
+            else if (n & 1) k_map_accum<true><<<grid, MAP_THREADS, 0, h->stream>>>(d_join, kk, level, prev_level, x, xo, velems / 2, d_w, n, nmom, ne, reinterpret_cast<double2*>(Y));
+            prev = vec; prev_level = level;
+            map_ev[0].emplace_back(e0, next_event(h));
+        };
+        XFER(chain_level_loop(h, RC, bt, A.a, A.b, accum_pass));  // (the last order, 2 lld + 1, is odd: every order has been added when it ends)
+        for (int q0 = 0; q0 < nk; q0 += kchunk) {
+            const int nq = std::min(kchunk, nk - q0), mpad = pad_rows(nq);
+            hipEvent_t e0 = next_event(h);
+            const int maxtot = *std::max_element(T.tot.begin(), T.tot.end());
+            const unsigned gx = (unsigned)std::min<size_t>(4096, ((size_t)maxtot * (mpad / 2) + 255) / 256);
+            k_bloch_phase<<<dim3(std::max(1u, gx), nb), 256, 0, h->stream>>>(BL, d_tot, d_src, d_cr, d_kpt + (size_t)3 * q0, nq, mpad, A.G, table);
+            hipEvent_t e1 = next_event(h);
+            map_ev[1].emplace_back(e0, e1);
+            const MapSlot gs = g_dev ? MapSlot{q0, nk, c0} : MapSlot{0, nq, 0}, as = a_dev ? MapSlot{q0, nk, c0} : MapSlot{0, nq, 0};
+            for (int e = 0; e < ne; ++e) {
+                const double* vec = Y + (size_t)e * velems;      // energy e of chain c: Y + (c ne + e) velems
+                for (int g = 0; g < ng; ++g) {
+                    if (!MFMA) {
+                        k_bloch_valu<LayoutCM><<<dim3(nq, nb), BLOCH_THREADS, 0, h->stream>>>(BL, g, last, vec, acc_doubles, table, mpad, gs.nk, gs.c0, e, ne, g_out + (size_t)gs.q0 * ne * BLK);
+                        continue;
+                    }
+                    const int splits = bloch_splits(T.maxcnt[(size_t)g * RC.nlev + last]);
+                    for (int m0 = 0; m0 < mpad; m0 += BLOCH_MCHUNK) {
+                        const int mrows = std::min(BLOCH_MCHUNK, mpad - m0), nqq = std::min(nq - m0 / 2, mrows / 2);
+                        k_bloch_mfma<<<dim3(BLOCH_NPB * (mrows / BLOCH_MROWS), splits, nb), BLOCH_WAVES * 64, 0, h->stream>>>(BL, g, last, vec, acc_doubles, table, mpad, m0, mrows, partial);
+                        k_bloch_reduce<<<dim3(nqq, nb), BLOCH_THREADS, 0, h->stream>>>(BL, g, last, partial, mrows, gs.q0 + m0 / 2, gs.nk, gs.c0, e, ne, g_out);
+                    }
+                }
+            }
+            if (M.a_k) k_map_diag<<<dim3(nq, ng, nb), MAP_DIAG_THREADS, 0, h->stream>>>(g_out, gs, a_out, as, ng, ne);
+            HIPCK(h, hipGetLastError());
+            map_ev[2].emplace_back(e1, next_event(h));
+            // the chunk's slice of a host array: per (chain, group) the chunk's points are contiguous on both sides
+            for (int c = 0; c < nb; ++c)
+                for (int g = 0; g < ng; ++g) {
+                    const size_t from = (size_t)nq * (g + (size_t)ng * c) * ne, to = ((size_t)q0 + (size_t)nk * (g + (size_t)ng * (c0 + c))) * ne;
+                    if (M.g_k && !g_dev) XFER(xfer_d2h(h, M.g_k + to * 2 * BLK, stage_g + from * 2 * BLK, (size_t)nq * ne * BLK * sizeof(double2)));
+                    if (M.a_k && !a_dev) XFER(xfer_d2h(h, M.a_k + to * NB, stage_a + from * NB, (size_t)nq * ne * NB * sizeof(double)));
+                }
+        }
+    }
+    const int rc = recursion_end(h, RC, 0, A.lld, false);        // (res_kind 0: nothing stays resident)
+    h->t_rest_ms = 0;                                            // out[5]: the three parts together
+    for (int k = 0; k < 3; ++k) {
+        for (auto& pr : map_ev[k]) h->t_map_ms[k] += ev_ms(pr.first, pr.second);
+        h->t_rest_ms += h->t_map_ms[k];
+    }
+    h->d_gram.release();                                         // (accumulators, tables and partials: not left behind as another call's Gram buffer)
+    return rc;
+}
+
+}  // namespace
+
+extern "C" int rsrec_chebyshev_bloch_map(rsrec_t* h, int nsrc, const int32_t* sources, int lld, double a, double b, const double* cr, const double* cell,
+                                         int nk, const double* kpt, int ngroup, const int32_t* group, int ne, const double* w, double* g_k, double* a_k) {
+    const char* who = "rsrec_chebyshev_bloch_map";
+    int rc = check_ready(h, who);
+    if (rc) return rc;
+    BlochMapCall M{BlochCall{nsrc, lld, nk, ngroup, sources, group, a, b, cr, kpt, BlochGeom{}, nullptr}, ne, w, g_k, a_k};
+    XFER(bloch_check_args(h, who, nsrc, sources, lld, a, cr, cell, nk, RSREC_BLOCH_MAP_NK_MAX, kpt, ngroup, group, M.B.G));
+    if (ne < 1 || ne > RSREC_BLOCH_MAP_NE_MAX) return fail(h, RSREC_ERR_ARG, "%s: ne = %d outside 1..%d", who, ne, RSREC_BLOCH_MAP_NE_MAX);
+    if (!w) return fail(h, RSREC_ERR_ARG, "%s: NULL w", who);
+    for (size_t q = 0; q < (size_t)2 * (2 * lld + 2) * ne; ++q)
+        if (!std::isfinite(w[q])) return fail(h, RSREC_ERR_ARG, "%s: weight (%zu, %zu) is not finite", who, q / 2 % (2 * lld + 2) + 1, q / 2 / (2 * lld + 2) + 1);
+    if (!g_k && !a_k) return fail(h, RSREC_ERR_ARG, "%s: g_k and a_k are both NULL", who);
+    HIPCK(h, hipSetDevice(h->device));
+    reset_timing(h);
+    if (nsrc == 0) return RSREC_OK;
+    return matrix_core_set(h) ? run_bloch_map<true>(h, M) : run_bloch_map<false>(h, M);
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -82,6 +82,23 @@ def chebyshev_scaling(energy_min, energy_max):
     return a, b
 
 
+def chebyshev_green_weights(energies, lld, energy_min, energy_max):
+    """The coefficients ``green%chebyshev_green`` applies to the moments, as the weights ``Recursion.bloch_map`` takes: complex (2 lld + 2, ne),
+    w(n, e) = jackson(n) (2 for n > 1) (-i exp(-i (n-1) acos x_e)) / sqrt(a^2 - (E_e - b)^2), x_e = (E_e - b) / a, with the Jackson kernel of
+    math.f90:1641-1655 and a, b of ``chebyshev_scaling``.  Raises ValueError for an energy outside the open window (energy_min, energy_max)."""
+    ene = np.atleast_1d(np.asarray(energies, np.float64)).ravel()
+    if not np.all((ene > energy_min) & (ene < energy_max)):
+        raise ValueError("energies must lie inside the open window (%g, %g)" % (energy_min, energy_max))
+    a, b = chebyshev_scaling(energy_min, energy_max)
+    nm = 2 * lld + 2
+    n = np.arange(nm, dtype=np.float64)
+    th = np.pi * n / (nm + 1.0)
+    kern = ((nm - n + 1.0) * np.cos(th) + np.sin(th) / np.tan(np.pi / (nm + 1.0))) / (nm + 1.0)
+    kern[1:] *= 2.0
+    phase = -1j * np.exp(-1j * n[:, None] * np.arccos((ene - b) / a)[None, :])
+    return np.asfortranarray(kern[:, None] * phase / np.sqrt(a * a - (ene - b) ** 2)[None, :])
+
+
 def _fc(a, dtype):
     return np.asfortranarray(np.asarray(a, dtype=dtype))
 
@@ -129,10 +146,10 @@ class Recursion:
 
 
     def timing(self):
-        out = (C.c_double * 14)()
-        self._L.rsrec_get_timing(self._h, out, 14)
+        out = (C.c_double * 17)()
+        self._L.rsrec_get_timing(self._h, out, 17)
         keys = ("total_ms", "hop_ms", "hop_launches", "atom_steps", "block_multiplies", "rest_ms", "host_ms", "hop_fuses_a", "hop_mfma_flop", "hop_required_flop",
-                "operator_arrays_from_device", "octet_launches", "rotate_ms", "gram_folded_launches")
+                "operator_arrays_from_device", "octet_launches", "rotate_ms", "gram_folded_launches", "map_accum_ms", "map_phase_ms", "map_final_ms")
         return dict(zip(keys, list(out)))
 
     # -- state (restore_to_default, recursion.f90:3713-3825) --------------------------------------------
@@ -385,6 +402,53 @@ class Recursion:
         nimg = nk * ngroup * nsrc
         img = green.chebyshev_ldos(nsites_total=nimg)
         return img["dosial"].reshape((nk, ngroup, nsrc, 18, -1), order="F")
+
+    def chebyshev_green_weights(self, energies):
+        """``chebyshev_green_weights`` of this module at the object's depth and window: complex (2 lld + 2, ne)."""
+        return chebyshev_green_weights(energies, self.control.lld, self.en.energy_min, self.en.energy_max)
+
+    def bloch_map(self, sources, kpts, cr, energies=None, weights=None, cell=None, group=None, blocks=True, diag=True):
+        """A function of H at many k-points and a few energies from one chain per source atom (``rsrec_chebyshev_bloch_map``): the sums of
+        ``chebyshev_bloch`` in the other order, g_k(:, :, e, q, g, s) = sum_n w(n, e) S_s(k_q, n) restricted to group g, without ever forming
+        the moments -- ne accumulated vectors per chain and one Bloch sum per energy.  ``sources``, ``kpts`` (3, nk), ``cr``, ``cell`` and
+        ``group`` as ``chebyshev_bloch`` takes them (kk atoms); give either ``energies`` -- the Green weights of ``chebyshev_green_weights``,
+        so that g_k = G(k, E) -- or ``weights`` complex (2 lld + 2, ne), row n for order n - 1, any function of H.  Returns ``(g_k, a_k)``:
+        g_k complex (18, 18, ne, nk, ngroup, nsrc) or None with ``blocks=False``; a_k real (18, ne, nk, ngroup, nsrc) = -Im diag g_k / pi,
+        bit for bit, or None with ``diag=False``.  Nothing is normalised, nothing stays resident, and only the sum over the groups has a
+        non-negative spectral weight."""
+        if (energies is None) == (weights is None):
+            raise ValueError("give either energies or weights")
+        lld = self.control.lld
+        a, b = chebyshev_scaling(self.en.energy_min, self.en.energy_max)
+        w = self.chebyshev_green_weights(energies) if weights is None else _fc(weights, np.complex128)
+        if w.ndim != 2 or w.shape[0] != 2 * lld + 2:
+            raise ValueError("weights must be (2 lld + 2, ne) = (%d, ne), got %r" % (2 * lld + 2, w.shape))
+        if not (blocks or diag):
+            raise ValueError("nothing asked for: blocks and diag are both False")
+        src = np.ascontiguousarray(sources, dtype=np.int32).ravel()
+        k = _fc(kpts, np.float64).reshape(3, -1, order="F")
+        cr = _fc(cr, np.float64)
+        if cr.shape != (3, self.lattice.kk):
+            raise ValueError("cr must be (3, kk), got %r" % (cr.shape,))
+        cell = None if cell is None else _fc(cell, np.float64).reshape(3, 3, order="F")
+        group, ngroup = self._group(group)
+        ne, nk = w.shape[1], k.shape[1]
+        g_k = np.zeros((18, 18, ne, nk, ngroup, len(src)), np.complex128, order="F") if blocks else None
+        a_k = np.zeros((18, ne, nk, ngroup, len(src)), np.float64, order="F") if diag else None
+        self._check(self._L.rsrec_chebyshev_bloch_map(self._h, len(src), _ptr(src), lld, a, b, _ptr(cr), _ptr(cell), nk, _ptr(k), ngroup, _ptr(group),
+                                                      ne, _ptr(w), _ptr(g_k), _ptr(a_k)))
+        return g_k, a_k
+
+    def constant_energy_map(self, sources, origin, u, v, n1, n2, cr, energy, cell=None, group=None):
+        """A(k, E) at one energy on the grid k = origin + (i / n1) u + (j / n2) v, i < n1, j < n2 (Cartesian, 2 pi included) -- a Fermi-surface
+        or constant-energy cut: ``bloch_map`` with the Green weights of ``energy``, diagonal only, summed over the 18 orbitals.  Returns
+        (n1, n2, ngroup, nsrc).  Nothing is normalised (kk atoms, one source: the trace of the source's own spectral function), and only
+        the sum over the groups has a non-negative spectral weight."""
+        origin, u, v = (np.asarray(x, np.float64).reshape(3) for x in (origin, u, v))
+        i, j = np.meshgrid(np.arange(n1) / float(n1), np.arange(n2) / float(n2), indexing="ij")
+        k = origin[:, None] + u[:, None] * i.ravel(order="F")[None, :] + v[:, None] * j.ravel(order="F")[None, :]
+        a_k = self.bloch_map(sources, k, cr, energies=[energy], cell=cell, group=group, blocks=False)[1]
+        return a_k.sum(axis=0)[0].reshape((n1, n2) + a_k.shape[3:], order="F")
 
     def _group(self, group):
         """(group as int32 (kk) or None, ngroup) of the calls that take atom groups 0..ngroup."""
