@@ -348,6 +348,19 @@ module rsrec_binding
          integer(c_int) :: rc
       end function
 
+      ! the double sum over those moments at ne weight columns without the moments: wl, wr complex (cond_ll,ne), row n for order n - 1;
+      ! s_full (18,18,ne,nvec,nout) and s_diag (18,ne,nvec,nout) = sum_{n,m} wl(m,e) wr(n,e) mu_j(:,:,n,m,v), either may be c_null_ptr.
+      ! Nothing is normalised, nothing stays resident.  The reference writes no file this could fill: there is no drop-in switch.
+      function rsrec_kubo_single_shot(handle, nout, nvec, nseed, seed_atoms, seed_coef, cond_ll, a, b, v_out, vo_out, v_b, vo_b, ne, wl, wr, &
+                                      s_full, s_diag) bind(C, name='rsrec_kubo_single_shot') result(rc)
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: handle
+         integer(c_int), value :: nout, nvec, nseed, cond_ll, ne
+         real(c_double), value :: a, b
+         type(c_ptr), value :: seed_atoms, seed_coef, v_out, vo_out, v_b, vo_b, wl, wr, s_full, s_diag
+         integer(c_int) :: rc
+      end function
+
       ! the same for nout output operators and nin input operators v_in / vo_in (18,18,nslots,ntype,nin): mu_diag
       ! (18,cond_ll,cond_ll,nvec,nout,nin), set (j, i) = rsrec_kubo_moments_diag with (v_a, v_b) = (v_out(:,:,:,:,j), v_in(:,:,:,:,i));
       ! resident as nvec*nout*nin vectors, the input outermost

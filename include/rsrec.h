@@ -486,6 +486,44 @@ int rsrec_kubo_moments_diag_tensor(rsrec_t *h, int nin, int nout, int nvec, int 
                                    int cond_ll, double a, double b, const double *v_out, const double *vo_out, const double *v_in,
                                    const double *vo_in, double *mu_diag);
 
+/* Single-shot Kubo sums: the double sum over the moments at a few weight columns, without the moments (kernels_shot.hpp).
+ *   L_e = sum_m conj(wl(m,e)) T_{m-1}(H~) r,   R_e = sum_n wr(n,e) T_{n-1}(H~) v_b r,
+ *   s(:,:,e,v,j) = sum_k [L_e]_k^H [v_out_j R_e]_k = sum_{n,m} wl(m,e) wr(n,e) mu_j(:,:,n,m,v)
+ * with mu_j what rsrec_kubo_moments returns for (v_a, v_b) = (v_out(:,:,:,:,j), v_b).  No left matrix, no cond_ll x cond_ll contraction and
+ * no moment array: 2 (cond_ll - 1) chain steps per vector whatever the cell size and about 2 ne + 2 P + 6 work vectors per vector in flight
+ * (P: option "shot_orders"), so cond_ll in the thousands fits on a 10^5-atom cell.  The weights are not interpreted.  wl = wr = the damped
+ * expansion of delta(E_e - H) gives the Kubo-Greenwood sigma(E_e); two columns per energy give the reference's Kubo-Bastin integrand at
+ * chosen energies (Recursion.kubo_greenwood_weights / kubo_bastin_weights of the Python front end).  A Fermi-sea integral over a whole
+ * energy mesh (sigma_xy) still needs the moments: rsrec_kubo_moments_diag and rsrec_kubo_conductivity.
+ *   seeds, a, b, v_out / vo_out (18,18,nslots,ntype,nout), v_b / vo_b : exactly as rsrec_kubo_moments_diag_multi takes them.
+ *             1 <= nout <= RSREC_KUBO_NOUT_MAX.  One applied field per call; several fields are several calls.
+ *   wl, wr  : complex (cond_ll, ne) column-major, host; row n weights order n - 1.  1 <= ne <= RSREC_KUBO_SHOT_NE_MAX,
+ *             1 <= cond_ll <= RSREC_KUBO_SHOT_LL_MAX.  wl enters bilinearly as written above: the library conjugates it when it
+ *             accumulates the bra side.
+ *   s_full  : complex (18,18,ne,nvec,nout) out;  s_diag : complex (18,ne,nvec,nout) out, bit for bit the diagonal of s_full.  Each host
+ *             or device memory (detected) or NULL; at least one is given.
+ * Nothing is normalised and nothing stays resident; resident diagonal moments of an earlier Kubo call are dropped, as any Kubo call drops
+ * them.  The buffers are the handle's Kubo buffers, planned before anything is reserved; the vector batch (at most 4: the left and the
+ * right recurrence of a vector advance as two chains of the same launches, option kubo_vbatch) shrinks with ne, and if not even one vector
+ * fits the call returns RSREC_ERR_DEVICE with the bytes needed.  A diverging recurrence is not detected, as in rsrec_kubo_moments_diag.
+ * SpMM launches per batch of nb vectors (rsrec_get_timing out[2] is their sum over the batches):
+ *     cond_ll + nb nout ceil(ne / 8)           = 1 (v_b r) + cond_ll - 1 (both recurrences) + the final V products, 8 columns per launch
+ *     2 cond_ll + 1 + nb (1 + 2 nout) ceil(ne / 8)   with hoh (every H product two launches, every V product two and a shared h_bulk pass).
+ * Determinism: no atomics, every sum in a fixed order.  The bits of s(:,:,e,v,j) depend on their own column of wl / wr, their own vector
+ * and their own output operator only -- not on ne or the other columns, the other vectors or kubo_vbatch, the other output operators or
+ * their order, shot_orders, whether the outputs are host or device memory, or what earlier calls left in the buffers.  Both kernel sets
+ * (option kernels: the Grams on the matrix cores or on plain FMAs) give the same values to rounding, not the same bits.
+ * Errors: RSREC_ERR_ARG with a message that names the function for ne, cond_ll or nout out of range, a NULL wl, wr, v_out or v_b, a
+ * non-finite weight, both outputs NULL, hoh without vo_out / vo_b, and every seed error of rsrec_kubo_moments_diag; the handle stays usable.
+ * nvec = 0 returns RSREC_OK.  rsrec_get_timing: out[0], out[1], out[2], out[5] as rsrec_kubo_moments_diag; out[17] ms in the accumulation
+ * passes, out[18] ms in the final stage (its V products, which out[1] counts as well, and the Grams); out[17] + out[18] = out[5]. */
+#define RSREC_KUBO_SHOT_NE_MAX 16
+#define RSREC_KUBO_SHOT_LL_MAX 65536
+int rsrec_kubo_single_shot(rsrec_t *h, int nout, int nvec, int nseed, const int32_t *seed_atoms, const double *seed_coef,
+                           int cond_ll, double a, double b, const double *v_out, const double *vo_out,
+                           const double *v_b, const double *vo_b, int ne, const double *wl, const double *wr,
+                           double *s_full, double *s_diag);
+
 /* The Kubo-Bastin conductivity integrand of calculate_gamma_nm + calculate_conductivity_tensor (conductivity.f90:158-268), without the
  * (nen, cond_ll, cond_ll) array gamma_nm (the sum factorises into two tables of nen x cond_ll, kernels_cond.hpp):
  *   integrand(l, i, v) = factor sum_{n,m} gamma_nm(i, n, m) mu_nm(l, l, n, m, v),   factor = 16 / (pi (energy_max - energy_min)^2)
@@ -763,7 +801,10 @@ int rsrec_comm_destroy(rsrec_t *h);
  *                together as the chains of every launch [0 = up to 8, as many as fit beside a whole left matrix each]
  *   "lattice_vbatch" rsrec_chebyshev_lattice: chains of a call advanced together as the chains of every launch [0 = up to 8, as many as fit]
  *   "kubo_setgroup" rsrec_kubo_moments_diag_tensor: sets of a vector contracted against one staged tile of left vectors; 1 = every set by itself,
- *                2 / 3 = groups of at most that width [0 = 2] */
+ *                2 / 3 = groups of at most that width [0 = 2]
+ *   "shot_orders" rsrec_kubo_single_shot: orders P added to the accumulators per pass, 1..16 (larger values: 16); the ring holds P + 2 orders per
+ *                chain and a pass moves (P + 2 ne) / P block streams per order and chain; the same bits for every value [0 = 16: the fastest of
+ *                1, 2, 4, 8, 16 at ne = 2 and 16 on 8 000 and 97 336 atoms, 0.87-0.99 of the call's time at 8 and 0.33-0.83 of it at 1, DESIGN.md section 5] */
 int rsrec_set_option(rsrec_t *h, const char *key, long value);
 /* Timing of the last recursion call, measured with HIP events on the engine's own stream:
  *   out[0] total device ms, out[1] ms in the H|psi> kernels, out[2] number of H|psi> launches,
@@ -780,6 +821,9 @@ int rsrec_set_option(rsrec_t *h, const char *key, long value);
  *   out[12] rsrec_block_lanczos_local_axis: ms in the conjugation of the resident coefficients with the sites' rotations (part of out[5]).
  *   out[13] H|psi> launches of the last call whose epilogue formed the A_n Gram of at least one chain (option "s5_gram_min").
  *   out[14..16] rsrec_chebyshev_bloch_map: ms in the accumulation passes, the phase tables and the final sums (together: out[5]).
+ *   out[17..18] rsrec_kubo_single_shot: ms in the accumulation passes and in the final stage (together: out[5]).
+ *   out[19..20] rsrec_kubo_moments and its _diag / _multi / _tensor forms: left chunks formed, summed over the vector batches of the call (one
+ *           per batch when every left matrix fits), and the left vectors per chunk as planned (cond_ll then; option kubo_lchunk caps it).
  * After rsrec_block_green: out[0] = kernel + transfers, out[1] = the Green kernel alone. */
 int rsrec_get_timing(rsrec_t *h, double *out, int n);
 

@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RSREC_LIB") or os.path.join(_HERE, "librsrec.so")
 
 ERR_ARG, ERR_DEVICE, ERR_DIVERGED, ERR_EIG = 1, 2, 3, 4
+KUBO_SHOT_NE_MAX, KUBO_SHOT_LL_MAX = 16, 65536      # RSREC_KUBO_SHOT_NE_MAX, RSREC_KUBO_SHOT_LL_MAX of include/rsrec.h
 
 _lib = None
 
@@ -42,6 +43,8 @@ _SIGNATURES = {
     "rsrec_kubo_moments_diag": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double] + [C.c_void_p] * 5),
     "rsrec_kubo_moments_diag_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double] + [C.c_void_p] * 5),
     "rsrec_kubo_moments_diag_tensor": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double] + [C.c_void_p] * 5),
+    "rsrec_kubo_single_shot": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double] + [C.c_void_p] * 4
+                               + [C.c_int] + [C.c_void_p] * 4),
     "rsrec_exchange": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double]
                        + [C.c_void_p] * 5 + [C.c_int, C.c_int] + [C.c_void_p] * 6),
     "rsrec_damping": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double]

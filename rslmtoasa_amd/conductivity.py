@@ -170,6 +170,37 @@ class Conductivity:
         del keep
         return out
 
+    def _single_shot(self, weights, per_call, pairs, v_a, v_b, energies, cond_ll, vo_a, vo_b, seeds, coefs, atlist):
+        """``Recursion.kubo_single_shot`` on the weights ``weights(energies, ...)`` of ``per_call`` energies at a time; ``pairs``: an
+        energy is the sum of two adjacent columns."""
+        ene = np.atleast_1d(np.asarray(energies, np.float64)).ravel()
+        rec = self.recursion
+        parts = []
+        for i0 in range(0, ene.size, per_call):
+            wl, wr = weights(ene[i0:i0 + per_call], cond_ll, float(self.en.energy_min), float(self.en.energy_max))
+            s = rec.kubo_single_shot(v_a, v_b, wl, wr, vo_out=vo_a, vo_b=vo_b, seeds=seeds, coefs=coefs, atlist=atlist)[:, :, :, 0]
+            parts.append(s[:, 0::2] + s[:, 1::2] if pairs else s)
+        if not parts:
+            raise ValueError("no energies given")
+        return np.asfortranarray(np.concatenate(parts, axis=1))
+
+    def integrand_at(self, v_a, v_b, energies, cond_ll, vo_a=None, vo_b=None, seeds=None, coefs=None, atlist=None):
+        """The Kubo-Bastin integrand at a few energies without the moments (``rsrec_kubo_single_shot`` on ``kubo_bastin_weights``): complex
+        (18, nE, nvec), what ``integrand(compute_moments_stochastic(v_a, v_b, cond_ll, ..., diag=True), ene)`` gives at those energies,
+        to rounding.  Neither a left matrix nor a cond_ll x cond_ll contraction is formed, so cond_ll may be in the thousands on a
+        10^5-atom cell.  Runs 8 energies per call (two weight columns each): more energies rerun the chains, once per 8.  A Fermi-sea
+        integral over the whole mesh (``tensor``) still needs the moments."""
+        from .recursion import kubo_bastin_weights
+        return self._single_shot(kubo_bastin_weights, 8, True, v_a, v_b, energies, cond_ll, vo_a, vo_b, seeds, coefs, atlist)
+
+    def greenwood(self, v_a, v_b, energies, cond_ll, vo_a=None, vo_b=None, seeds=None, coefs=None, atlist=None):
+        """The Kubo-Greenwood sums s(l, E, v) = sum_{n,m} d(m, E) d(n, E) mu(l, l, n, m, v), the stochastic estimate of the orbital-diagonal
+        part of Tr[v_a delta(E - H) v_b delta(E - H)] with the Jackson-damped delta of ``kubo_greenwood_weights``: complex (18, nE, nvec).
+        Up to 16 energies per call; more rerun the chains, once per 16.  Prefactors (pi hbar e^2 / volume) and the average over the vectors
+        are the caller's."""
+        from .recursion import kubo_greenwood_weights
+        return self._single_shot(kubo_greenwood_weights, 16, False, v_a, v_b, energies, cond_ll, vo_a, vo_b, seeds, coefs, atlist)
+
     def timing(self):
         """(device ms of the last call, ms in its kernels): after ``integrand`` the contraction kernels; after ``tensor`` the series and
         integral kernels, which are all of that call's device work, so the two values are equal; after ``optical`` the table kernels and

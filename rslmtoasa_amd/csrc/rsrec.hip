@@ -52,6 +52,7 @@
 #include "kernels_bloch.hpp"
 #include "kernels_blochmap.hpp"
 #include "kernels_lattice.hpp"
+#include "kernels_shot.hpp"
 
 using namespace rsrec;
 
@@ -150,6 +151,7 @@ struct rsrec_handle {
     DevBuf d_fan, d_fan_tab, d_mpair;   // rsrec_chebyshev_pairs_direct: gathered blocks M(18,18,nmom,entry); entry and pair tables; M_ij / M_ji of every pair
     DevBuf d_bloch_geo, d_bloch_tab;    // rsrec_chebyshev_bloch: positions and k-points of the call; lists, segment offsets and level counts of a batch
     DevBuf d_map_w;                     // rsrec_chebyshev_bloch_map: the weights w(n, e) of the call
+    DevBuf d_shot_w;                    // rsrec_kubo_single_shot: the weights of the call, [conj(wl) | wr][e][order]
     DevBuf d_lat_tab, d_lat_w, d_lat_part;   // rsrec_chebyshev_lattice: lists and offsets of a batch; weights and divergence bounds; split partials
     // options
     long opt_batch = 0, opt_kernels = 0, opt_nblk = 0, opt_spmm5 = 2, opt_chain_fold = 1, opt_s5_cap = 0, opt_side = 1, opt_s5_lds = 1, opt_s5_queue = 1, opt_cheb_fused = 1;
@@ -166,8 +168,9 @@ struct rsrec_handle {
     long opt_lattice_vbatch = 0; // rsrec_chebyshev_lattice: chains advanced together as the chains of one launch (0: up to 8, as many as fit)
     long opt_blochmap_orders = 2;  // rsrec_chebyshev_bloch_map: orders added to the accumulators per pass (1 | 2: same bits, see kernels_blochmap.hpp)
     long opt_blochmap_kchunk = 0;  // rsrec_chebyshev_bloch_map: k-points per chunk of the final sums (0: 256, one launch's rows of the phase matrix); tests force it small
+    long opt_shot_orders = 0;    // rsrec_kubo_single_shot: orders added to the accumulators per pass (1..16; 0: SHOT_ORDERS_DEFAULT = 16; the same bits for every value)
     long opt_kubo_setgroup = 0;  // rsrec_kubo_moments_diag_tensor: sets of a vector contracted against one staged left tile (k_kubo_gram_diag_sets): 0 default (2), 1 every set by itself (k_kubo_gram_diag), 2 / 3 groups of at most that width
-    int n_kubo_left_chunks = 0;
+    int n_kubo_left_chunks = 0, kubo_lchunk_planned = 0;   // of the last Kubo moment call: left chunks formed over all its batches; left vectors per chunk as kubo_plan decided
     int kubo_diag_nvec = 0, kubo_diag_ll = 0;   // rsrec_kubo_moments_diag / _multi / _tensor: the call whose diagonal moments lie in d_kubo[4] (0: nothing resident; _multi: nvec * nout; _tensor: nvec * nout * nin)
     long opt_orth3 = 1;          // k_mfma_orth3: 1 one 512-register wave per SIMD (tables in registers), 2 two waves per SIMD (tables in LDS)
     long opt_graph = 1;          // level loop of small batches as one HIP graph: 0 never, 1 calls of up to 8 chains, 2 every single-batch call
@@ -189,6 +192,7 @@ struct rsrec_handle {
     // timing of last call
     double t_total_ms = 0, t_hop_ms = 0, t_rest_ms = 0, t_host_ms = 0;
     double t_rot_ms = 0;      // local-axis recursion: ms in k_rotate_coef (part of t_rest_ms)
+    double t_shot_ms[2] = {0, 0};     // rsrec_kubo_single_shot: ms in the accumulation passes, in the final stage (their sum: t_rest_ms)
     double t_map_ms[3] = {0, 0, 0};   // rsrec_chebyshev_bloch_map: ms in the accumulation passes, the phase tables, the final sums (their sum: t_rest_ms)
     double n_hop_launch = 0, n_atom_steps = 0, n_block_mult = 0, n_hop_mfma_flop = 0;   // mfma_flop: matrix flops EXECUTED by the timed k_spmm5 launches
     double n_req_flop = 0;    // flops of H|psi> the operator's block structure requires (spin-diagonal blocks: half a zgemm), see required_hop_flops
@@ -244,6 +248,7 @@ const OptionEntry OPTIONS[] = {
     {"kubo_lchunk", &rsrec_handle::opt_kubo_lchunk},
     {"kubo_vbatch", &rsrec_handle::opt_kubo_vbatch},
     {"kubo_setgroup", &rsrec_handle::opt_kubo_setgroup},
+    {"shot_orders", &rsrec_handle::opt_shot_orders},
     {"lattice_vbatch", &rsrec_handle::opt_lattice_vbatch},
     {"blochmap_orders", &rsrec_handle::opt_blochmap_orders},
     {"blochmap_kchunk", &rsrec_handle::opt_blochmap_kchunk},
@@ -414,9 +419,9 @@ extern "C" int rsrec_set_option(rsrec_t* h, const char* key, long value) {
 
 extern "C" int rsrec_get_timing(rsrec_t* h, double* out, int n) {
     if (!h || !out) return RSREC_ERR_ARG;
-    const double v[17] = {h->t_total_ms, h->t_hop_ms, h->n_hop_launch, h->n_atom_steps, h->n_block_mult, h->t_rest_ms, h->t_host_ms, (double)h->hop_fuses_a, h->n_hop_mfma_flop,
-                          h->n_req_flop, (double)h->n_asm_reused, (double)h->n_octet_launch, h->t_rot_ms, h->n_gram_folded, h->t_map_ms[0], h->t_map_ms[1], h->t_map_ms[2]};
-    for (int i = 0; i < n && i < 17; ++i) out[i] = v[i];
+    const double v[21] = {h->t_total_ms, h->t_hop_ms, h->n_hop_launch, h->n_atom_steps, h->n_block_mult, h->t_rest_ms, h->t_host_ms, (double)h->hop_fuses_a, h->n_hop_mfma_flop,
+                          h->n_req_flop, (double)h->n_asm_reused, (double)h->n_octet_launch, h->t_rot_ms, h->n_gram_folded, h->t_map_ms[0], h->t_map_ms[1], h->t_map_ms[2], h->t_shot_ms[0], h->t_shot_ms[1], (double)h->n_kubo_left_chunks, (double)h->kubo_lchunk_planned};
+    for (int i = 0; i < n && i < 21; ++i) out[i] = v[i];
     return RSREC_OK;
 }
 
@@ -777,6 +782,8 @@ double required_hop_flops(const rsrec_t* h, const Spmm5Operator& op) {
 void reset_timing(rsrec_t* h) {
     h->t_total_ms = h->t_hop_ms = h->t_rest_ms = h->t_host_ms = h->t_rot_ms = 0;
     h->t_map_ms[0] = h->t_map_ms[1] = h->t_map_ms[2] = 0;
+    h->t_shot_ms[0] = h->t_shot_ms[1] = 0;
+    h->n_kubo_left_chunks = h->kubo_lchunk_planned = 0;
     h->n_hop_launch = h->n_atom_steps = h->n_block_mult = h->n_hop_mfma_flop = h->n_req_flop = 0;
     h->n_octet_launch = 0;
     h->n_gram_folded = h->n_gram_all = h->n_gram_levels = 0;
@@ -3728,16 +3735,26 @@ int kubo_plan(rsrec_t* h, int nin, int nout, int setgroup, int nvec, int cond_ll
     return RSREC_OK;
 }
 
-// The plan's buffers: the recursion's work vectors go, and buffers that have to grow are given back first, so that the new sizes are asked of
-// the memory the budget counted on.  Block kk of every vector and slot stays the zero block.
+// The five Kubo buffers at the sizes a plan wants.  Buffers that have to grow are given back first; one that is larger than wanted stays.  The
+// plans count ALL bytes of the old buffers as free, so a buffer kept oversize (the work vectors of a single-shot call before a moment call)
+// can make a hipMalloc fail that the plan allowed: then everything is given back and asked for once more.
+int reserve_kubo_buffers(rsrec_t* h, const size_t (&want)[5], const char* who) {
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        for (int q = 0; q < 5; ++q) if (attempt || h->d_kubo[q].bytes < want[q]) h->d_kubo[q].release();
+        bool ok = true;
+        for (int q = 0; q < 5 && ok; ++q) ok = h->d_kubo[q].reserve(want[q]) == hipSuccess;
+        if (ok) return RSREC_OK;
+        (void)hipGetLastError();
+    }
+    for (auto& kb : h->d_kubo) kb.release();
+    return fail(h, RSREC_ERR_DEVICE, "%s: out of device memory (%.0f bytes needed)", who, (double)(want[0] + want[1] + want[2] + want[3] + want[4]));
+}
+
+// The plan's buffers: the recursion's work vectors go, and buffers that have to grow are given back first (reserve_kubo_buffers), so that the
+// new sizes are asked of the memory the budget counted on.  Block kk of every vector and slot stays the zero block.
 int kubo_reserve(rsrec_t* h, KuboPlan& P) {
     for (int v = 0; v < 6; ++v) h->d_vec[v].release();
-    for (int q = 0; q < 5; ++q) if (h->d_kubo[q].bytes < P.bytes[q]) h->d_kubo[q].release();
-    for (int q = 0; q < 5; ++q)
-        if (h->d_kubo[q].reserve(P.bytes[q]) != hipSuccess) {
-            for (auto& kb : h->d_kubo) kb.release();
-            return fail(h, RSREC_ERR_DEVICE, "rsrec_kubo_moments: out of device memory");
-        }
+    XFER(reserve_kubo_buffers(h, P.bytes, "rsrec_kubo_moments"));
     P.work = h->d_kubo[0].as<double>(); P.Lm = h->d_kubo[1].as<double>(); P.Rm = h->d_kubo[2].as<double>();
     P.part = h->d_kubo[3].as<double2>(); P.mu = h->d_kubo[4].as<double2>();
     HIPCK(h, hipMemsetAsync(P.Lm, 0, P.bytes[1], h->stream));
@@ -3951,8 +3968,193 @@ int kubo_moments_run(rsrec_t* h, const char* fn, bool diag, bool tensor, int nin
         }
     }
     XFER(whole_lattice_end(h, W, true));
-    h->n_kubo_left_chunks = n_left_chunks;
+    h->n_kubo_left_chunks = n_left_chunks; h->kubo_lchunk_planned = P.lchunk;
     if (P.resident) { h->kubo_diag_nvec = nvec * nset; h->kubo_diag_ll = cond_ll; }
+    return RSREC_OK;
+}
+
+// The device memory of a rsrec_kubo_single_shot call, decided before anything is reserved (as kubo_plan does).  Per vector in flight: the ring
+// of P + 2 order slots and the ne accumulators of its left and its right chain, and with hoh the two chains' h psi; once per call the ne
+// products W_e = v_out_j R_e of the vector whose Grams are formed, and with hoh h_bulk R_e of all columns (shared by the output operators)
+// and the V R_e of a launch's chains.  The vector batch shrinks with ne: 2 nbv <= KUBO_CHAINS_MAX chains, fewer if they do not fit.
+constexpr int SHOT_ORDERS_DEFAULT = 16;      // what shot_orders = 0 means: the fastest of 1, 2, 4, 8, 16 in every measured configuration
+struct ShotPlan {
+    int P = 0, R = 0, nbv = 0, ne = 0, G = 0;    // orders per pass, ring slots, vectors in flight, columns, chains of a final V launch (<= 8)
+    int ksteps_total = 0, ksplit = 0;
+    size_t velems = 0, slot = 0;                 // doubles of a vector; of a ring slot (2 nbv chains)
+    size_t nvectors = 0, bytes_work = 0, bytes_part = 0, bytes_out = 0;
+    double *ring = nullptr, *acc = nullptr, *w = nullptr, *hps = nullptr, *p1 = nullptr, *p2 = nullptr;
+    double2 *part = nullptr, *full = nullptr, *diag = nullptr;
+    double* ring_slot(int n) const { return ring + (size_t)(n % R) * slot; }
+    double* acc_of(int chain, int e) const { return acc + ((size_t)chain * ne + e) * velems; }
+};
+
+int shot_plan(rsrec_t* h, int nvec, int nout, int ne, ShotPlan& P) {
+    const int kk = h->kk;
+    const bool hoh = h->hoh != 0;
+    P.ne = ne; P.G = std::min(ne, KUBO_CHAINS_MAX);
+    P.P = h->opt_shot_orders <= 0 ? SHOT_ORDERS_DEFAULT : (int)std::min<long>(h->opt_shot_orders, SHOT_ORDERS_MAX);
+    P.R = P.P + 2;
+    P.velems = (size_t)(kk + 1) * BLD;
+    P.ksteps_total = (int)((NB * (size_t)kk + 3) / 4);
+    P.ksplit = shot_ksplit(P.ksteps_total);
+    P.bytes_part = (size_t)ne * P.ksplit * BLK * 16;
+    P.bytes_out = (size_t)(BLK + NB) * ne * nvec * nout * 16;
+    size_t free_b = 0, total_b = 0;
+    HIPCK(h, hipMemGetInfo(&free_b, &total_b));
+    size_t reusable = 0;
+    for (int v = 0; v < 6; ++v) reusable += h->d_vec[v].bytes;
+    for (auto& kb : h->d_kubo) reusable += kb.bytes;
+    const double budget = 0.9 * (double)(free_b + reusable);
+    auto vectors_for = [&](int nv) { return (size_t)nv * (2 * P.R + 2 * ne + (hoh ? 2 : 0)) + ne + (hoh ? std::max(nv, ne) + std::max(nv, P.G) : 0); };
+    auto need_for = [&](int nv) { return (double)vectors_for(nv) * P.velems * 8 + (double)P.bytes_part + (double)P.bytes_out; };
+    int nbv = (int)std::min<long>({(long)nvec, h->opt_kubo_vbatch > 0 ? h->opt_kubo_vbatch : KUBO_CHAINS_MAX, (long)(KUBO_CHAINS_MAX / 2)});
+    while (nbv > 1 && need_for(nbv) > budget) --nbv;
+    if (need_for(nbv) > budget)
+        return fail(h, RSREC_ERR_DEVICE, "rsrec_kubo_single_shot: %.0f bytes needed for one vector at a time on %d atoms (ne=%d, shot_orders=%d), %.0f bytes free",
+                    need_for(1), kk, ne, P.P, (double)free_b);
+    P.nbv = nbv; P.slot = (size_t)2 * nbv * P.velems; P.nvectors = vectors_for(nbv); P.bytes_work = P.nvectors * P.velems * 8;
+    return RSREC_OK;
+}
+
+// The plan's buffers out of the handle's Kubo buffers: d_kubo[0] the work vectors, [3] the slice partials, [4] the results of the whole call;
+// the left and right matrices of an earlier moment call go (the budget counted them as free).  Everything is cleared: block kk of every vector
+// stays the zero block, and nothing an earlier call left is ever read.
+int shot_reserve(rsrec_t* h, ShotPlan& P) {
+    const bool hoh = h->hoh != 0;
+    const size_t want[5] = {P.bytes_work, 0, 0, P.bytes_part, P.bytes_out};
+    for (int v = 0; v < 6; ++v) h->d_vec[v].release();
+    h->d_kubo[1].release(); h->d_kubo[2].release();
+    XFER(reserve_kubo_buffers(h, want, "rsrec_kubo_single_shot"));
+    double* at = h->d_kubo[0].as<double>();
+    auto take = [&](size_t nv) { double* p = at; at += nv * P.velems; return p; };
+    P.ring = take((size_t)P.R * 2 * P.nbv);
+    P.acc = take((size_t)2 * P.nbv * P.ne);
+    P.w = take(P.ne);
+    if (hoh) { P.hps = take(2 * P.nbv); P.p1 = take(std::max(P.nbv, P.ne)); P.p2 = take(std::max(P.nbv, P.G)); }
+    P.part = h->d_kubo[3].as<double2>();
+    P.full = h->d_kubo[4].as<double2>();
+    P.diag = P.full + P.bytes_out / 16 / (BLK + NB) * BLK;
+    HIPCK(h, hipMemsetAsync(h->d_kubo[0].p, 0, P.bytes_work, h->stream));
+    return RSREC_OK;
+}
+
+// one accumulation pass: orders n0 .. n0 + cnt - 1 of the ring into the accumulators of the launch's chains (the first nb: left)
+void shot_accumulate(rsrec_t* h, const ShotPlan& P, int nb, int n0, int cnt, int cond_ll) {
+    const size_t total = (size_t)h->kk * BLK, vs = P.velems / 2;
+    const double2* ring = reinterpret_cast<const double2*>(P.ring);
+    double2* acc = reinterpret_cast<double2*>(P.acc);
+    const double2* w = h->d_shot_w.as<double2>();
+    auto go = [&](auto kern, int per_wg) {
+        const dim3 grid((unsigned)((total + per_wg - 1) / per_wg), (unsigned)(2 * nb));
+        kern<<<grid, SHOT_THREADS, 0, h->stream>>>(ring, P.slot / 2, P.R, n0 % P.R, cnt, vs, total, w, nb, n0, cond_ll, P.ne, acc);
+    };
+    if (cnt <= 1) go(k_shot_accum<1, 4>, SHOT_THREADS * 4);
+    else if (cnt <= 2) go(k_shot_accum<2, 4>, SHOT_THREADS * 4);
+    else if (cnt <= 4) go(k_shot_accum<4, 4>, SHOT_THREADS * 4);
+    else if (cnt <= 8) go(k_shot_accum<8, 2>, SHOT_THREADS * 2);
+    else go(k_shot_accum<16, 1>, SHOT_THREADS);
+}
+
+// rsrec_kubo_single_shot behind its argument checks.  Per batch of nb vectors: chains 0 .. nb - 1 carry T_n(H~) r, chains nb .. 2 nb - 1
+// T_n(H~) v_b r, and both advance in the same cond_ll - 1 launches (twice that with hoh); one launch (hoh: three) forms v_b r.  After every
+// P orders and after the last one a pass adds the ring's new orders into the 2 nb ne accumulators.  Final stage, vector by vector: with hoh
+// h_bulk R_e of all columns once, then per output operator W_e = v_out_j R_e, up to 8 columns per launch, and the Grams L_e^H W_e of all
+// columns in one launch.  SpMM launches of a batch:  cond_ll + nb nout ceil(ne / 8)  (hoh:  2 cond_ll + 1 + nb (1 + 2 nout) ceil(ne / 8)).
+int kubo_single_shot_run(rsrec_t* h, const char* fn, int nout, int nvec, int nseed, const int32_t* seed_atoms, const double* seed_coef, int cond_ll, double a,
+                         double b, const double* v_out, const double* vo_out, const double* v_b, const double* vo_b, int ne, const double* wl, const double* wr,
+                         double* s_full, double* s_diag) {
+    HIPCK(h, hipSetDevice(h->device));
+    reset_timing(h);
+    if (nvec == 0) return RSREC_OK;
+    h->kubo_diag_nvec = h->kubo_diag_ll = 0;                       // (d_kubo[4] is about to be overwritten)
+    release_kubo_buffers(h, false, true);
+    const size_t op_doubles = 2 * (size_t)BLK * h->hslots * h->ntype;
+    for (int j = 0; j < nout; ++j) XFER(build_kubo_operator(h, h->kubo_op[j], v_out + op_doubles * j, vo_out ? vo_out + op_doubles * j : nullptr));
+    XFER(build_kubo_operator(h, h->kubo_op_b[0], v_b, vo_b));
+    if (h->hoh && h->nmax > 0) XFER(build_kubo_hbulk(h));
+    ShotPlan P;
+    XFER(shot_plan(h, nvec, nout, ne, P));
+    XFER(shot_reserve(h, P));
+    HIPCK(h, h->d_seed.reserve((size_t)nseed * 4));
+    HIPCK(h, h->d_seedcoef.reserve((size_t)nseed * sizeof(double2)));
+    // the weights as the pass reads them: [side][e][order], side 0 = conj(wl) (the bra side), side 1 = wr
+    {
+        std::vector<double> wt((size_t)4 * ne * cond_ll);
+        for (size_t q = 0; q < (size_t)ne * cond_ll; ++q) {
+            wt[2 * q] = wl[2 * q]; wt[2 * q + 1] = -wl[2 * q + 1];
+            wt[2 * ((size_t)ne * cond_ll + q)] = wr[2 * q]; wt[2 * ((size_t)ne * cond_ll + q) + 1] = wr[2 * q + 1];
+        }
+        HIPCK(h, h->d_shot_w.reserve(wt.size() * 8));
+        XFER(xfer_h2d(h, h->d_shot_w.p, wt.data(), wt.size() * 8));
+    }
+    WholeLatticeCall W;
+    XFER(whole_lattice_begin(h, W, std::max(2 * P.nbv, P.G), true));
+    W.hps = P.hps; W.p2 = P.p2;
+    W.ev_begin = next_event(h);
+    const KuboSeeds S{nseed, seed_atoms, seed_coef};
+    const bool mfma = h->opt_kernels != 1;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> acc_ev, fin_ev;
+    const size_t acc_bytes = (size_t)2 * P.nbv * ne * P.velems * 8;
+    for (int iv0 = 0; iv0 < nvec; iv0 += P.nbv) {
+        const int nb = std::min(P.nbv, nvec - iv0);
+        double* r0 = P.ring_slot(0);
+        HIPCK(h, hipMemsetAsync(r0, 0, P.slot * 8, h->stream));
+        HIPCK(h, hipMemsetAsync(P.acc, 0, acc_bytes, h->stream));
+        XFER(seed_whole_vectors<LayoutCI>(h, fn, S, iv0, nb, r0, P.velems));
+        whole_lattice_batch(W, nb, false);
+        W.p1 = P.p1;
+        whole_lattice_apply_v(W, h->kubo_op_b[0], r0, r0 + (size_t)nb * P.velems);          // v_b r into the right chains
+        whole_lattice_batch(W, 2 * nb, false);
+        for (int n = 0, n0 = 0; n < cond_ll; ++n) {
+            if (n >= 1) {
+                const double* cur = P.ring_slot(n - 1);
+                whole_lattice_apply_h(W, cur, P.ring_slot(n), cheb_epilogue(n == 1, cur, n >= 2 ? P.ring_slot(n - 2) : nullptr, a, b));
+            }
+            if (n - n0 + 1 == P.P || n == cond_ll - 1) {
+                hipEvent_t e0 = next_event(h);
+                shot_accumulate(h, P, nb, n0, n - n0 + 1, cond_ll);
+                acc_ev.emplace_back(e0, next_event(h));
+                n0 = n + 1;
+            }
+        }
+        HIPCK(h, hipGetLastError());
+        hipEvent_t f0 = next_event(h);
+        for (int c = 0; c < nb; ++c) {
+            const double* Rc = P.acc_of(nb + c, 0);
+            if (h->hoh)
+                for (int e0 = 0; e0 < ne; e0 += P.G) {
+                    whole_lattice_batch(W, std::min(P.G, ne - e0), false);
+                    W.p1 = P.p1 + (size_t)e0 * P.velems;
+                    whole_lattice_apply_v_prepare(W, Rc + (size_t)e0 * P.velems);
+                }
+            for (int j = 0; j < nout; ++j) {
+                for (int e0 = 0; e0 < ne; e0 += P.G) {
+                    whole_lattice_batch(W, std::min(P.G, ne - e0), false);
+                    W.p1 = h->hoh ? P.p1 + (size_t)e0 * P.velems : nullptr;
+                    whole_lattice_apply_v_prepared(W, h->kubo_op[j], Rc + (size_t)e0 * P.velems, P.w + (size_t)e0 * P.velems);
+                }
+                const dim3 grid((unsigned)P.ksplit, (unsigned)ne);
+                if (mfma) k_shot_gram<<<grid, 64, 0, h->stream>>>(P.acc_of(c, 0), P.velems, P.w, P.velems, P.ksteps_total, P.ksplit, P.part);
+                else k_shot_gram_valu<<<grid, SHOT_GRAM_VALU_THREADS, 0, h->stream>>>(P.acc_of(c, 0), P.velems, P.w, P.velems, P.ksteps_total, P.ksplit, P.part);
+                k_shot_gram_reduce<<<ne, SHOT_GRAM_VALU_THREADS, 0, h->stream>>>(P.part, P.ksplit, ne, iv0 + c, nvec, j, P.full, P.diag);
+            }
+        }
+        fin_ev.emplace_back(f0, next_event(h));
+        HIPCK(h, hipGetLastError());
+    }
+    const size_t nimg = (size_t)ne * nvec * nout;
+    auto deliver = [&](double* dst, const double2* src, size_t n) {
+        if (!dst) return (int)RSREC_OK;
+        if (is_device_ptr(dst)) { HIPCK(h, hipMemcpyAsync(dst, src, n * 16, hipMemcpyDeviceToDevice, h->stream)); return (int)RSREC_OK; }
+        return xfer_d2h(h, dst, src, n * 16);
+    };
+    XFER(deliver(s_full, P.full, nimg * BLK));
+    XFER(deliver(s_diag, P.diag, nimg * NB));
+    XFER(whole_lattice_end(h, W, true));
+    for (auto& pr : acc_ev) h->t_shot_ms[0] += ev_ms(pr.first, pr.second);
+    for (auto& pr : fin_ev) h->t_shot_ms[1] += ev_ms(pr.first, pr.second);
+    h->t_rest_ms = h->t_shot_ms[0] + h->t_shot_ms[1];
     return RSREC_OK;
 }
 
@@ -3994,6 +4196,29 @@ extern "C" int rsrec_kubo_moments_diag_tensor(rsrec_t* h, int nin, int nout, int
                                               double* mu_diag) {
     if (!h) return RSREC_ERR_ARG;
     return kubo_moments_run(h, "rsrec_kubo_moments_diag_tensor", true, true, nin, nout, nvec, nseed, seed_atoms, seed_coef, cond_ll, a, b, v_out, vo_out, v_in, vo_in, mu_diag);
+}
+
+// The double sum over the moments of rsrec_kubo_moments at ne weight columns without the moments (kernels_shot.hpp):
+//   s(:,:,e,v,j) = sum_{n,m} wl(m,e) wr(n,e) mu_j(:,:,n,m,v),   mu_j = rsrec_kubo_moments with (v_a, v_b) = (v_out_j, v_b)
+// 2 (cond_ll - 1) chain steps per vector whatever the cell size, about 2 ne + 2 P + 6 work vectors per vector in flight.
+extern "C" int rsrec_kubo_single_shot(rsrec_t* h, int nout, int nvec, int nseed, const int32_t* seed_atoms, const double* seed_coef, int cond_ll, double a, double b,
+                                      const double* v_out, const double* vo_out, const double* v_b, const double* vo_b, int ne, const double* wl, const double* wr,
+                                      double* s_full, double* s_diag) {
+    if (!h) return RSREC_ERR_ARG;
+    const char* fn = "rsrec_kubo_single_shot";
+    XFER(check_ready(h, fn));
+    if (nout < 1 || nout > RSREC_KUBO_NOUT_MAX) return fail(h, RSREC_ERR_ARG, "%s: nout=%d is not in 1..%d", fn, nout, RSREC_KUBO_NOUT_MAX);
+    if (ne < 1 || ne > RSREC_KUBO_SHOT_NE_MAX) return fail(h, RSREC_ERR_ARG, "%s: ne=%d is not in 1..%d", fn, ne, RSREC_KUBO_SHOT_NE_MAX);
+    if (cond_ll < 1 || cond_ll > RSREC_KUBO_SHOT_LL_MAX) return fail(h, RSREC_ERR_ARG, "%s: cond_ll=%d is not in 1..%d", fn, cond_ll, RSREC_KUBO_SHOT_LL_MAX);
+    if (!wl || !wr || !v_out || !v_b) return fail(h, RSREC_ERR_ARG, "%s: wl, wr, v_out and v_b must be given", fn);
+    if (!s_full && !s_diag) return fail(h, RSREC_ERR_ARG, "%s: s_full and s_diag are both NULL", fn);
+    if (nvec < 0 || nseed < 1 || a == 0.0 || (nvec > 0 && (!seed_atoms || !seed_coef))) return fail(h, RSREC_ERR_ARG, "%s: bad argument", fn);
+    if (h->hoh && (!vo_out || !vo_b)) return fail(h, RSREC_ERR_ARG, "%s: hoh requires vo_out and vo_b", fn);
+    if (!h->s5_built) return fail(h, RSREC_ERR_ARG, "%s: lattice has too many neighbour slots for the SpMM kernel", fn);
+    for (size_t q = 0; q < 2 * (size_t)cond_ll * ne; ++q)
+        if (!std::isfinite(wl[q]) || !std::isfinite(wr[q])) return fail(h, RSREC_ERR_ARG, "%s: weight %zu of column %zu is not finite", fn, q / 2 % cond_ll + 1, q / 2 / cond_ll + 1);
+    XFER(check_seeds(h, fn, seed_atoms, (size_t)nvec * nseed, 0));
+    return kubo_single_shot_run(h, fn, nout, nvec, nseed, seed_atoms, seed_coef, cond_ll, a, b, v_out, vo_out, v_b, vo_b, ne, wl, wr, s_full, s_diag);
 }
 
 namespace {

@@ -99,6 +99,80 @@ def chebyshev_green_weights(energies, lld, energy_min, energy_max):
     return np.asfortranarray(kern[:, None] * phase / np.sqrt(a * a - (ene - b) ** 2)[None, :])
 
 
+def _scaled_energies(energies, energy_min, energy_max, nmax, who, window=True):
+    """(x_e, a) of a weight table: the energies on the Chebyshev axis.  ValueError for more than nmax energies and for one outside the
+    open window (energy_min, energy_max), or with window=False outside the open axis |x_e| < 1 (which holds the window)."""
+    ene = np.atleast_1d(np.asarray(energies, np.float64)).ravel()
+    if ene.size > nmax:
+        raise ValueError("%s: at most %d energies per call, got %d" % (who, nmax, ene.size))
+    a, b = chebyshev_scaling(energy_min, energy_max)
+    x = (ene - b) / a
+    if window and not np.all((ene > energy_min) & (ene < energy_max)):
+        raise ValueError("%s: energies must lie inside the open window (%g, %g)" % (who, energy_min, energy_max))
+    if not np.all(np.abs(x) < 1.0):
+        raise ValueError("%s: energies must lie inside (b - a, b + a) = (%g, %g)" % (who, b - abs(a), b + abs(a)))
+    return x, a
+
+
+def _chebyshev_t(x, cond_ll):
+    """T_n(x_e), n = 0 .. cond_ll - 1, by the three-term recurrence (conductivity.f90:203-207): real (cond_ll, ne)."""
+    t = np.empty((cond_ll, x.size))
+    t[0] = 1.0
+    if cond_ll > 1:
+        t[1] = x
+    for k in range(2, cond_ll):
+        t[k] = 2.0 * x * t[k - 1] - t[k - 2]
+    return t
+
+
+def kubo_bastin_weights(energies, cond_ll, energy_min, energy_max):
+    """The weights with which ``Recursion.kubo_single_shot`` gives the reference's Kubo-Bastin integrand at chosen energies: ``(wl, wr)``,
+    complex (cond_ll, 2 nE) in Fortran order.  gamma_nm of calculate_gamma_nm (conductivity.f90:216-218) is a sum of two products,
+    gw_n gw_m [c_n T_m + conj(c)_m T_n] / (1 - x^2)^2, so two columns per energy reproduce it -- column 2 i: wr = F gw c_n / (1 - x^2)^2,
+    wl = gw T_m; column 2 i + 1: wr = F gw T_n / (1 - x^2)^2, wl = gw conj(c)_m -- and the sum of the two columns of ``s_diag`` is
+    integrand_at(l, l, i, v) with the reference's factor F = 16 / (pi (energy_max - energy_min)^2) inside wr.  The reference's quirks are
+    kept: the Lorentz kernel gw (lambda = 6) forms (n - 1) / cond_ll and 1 - that in REAL(4) (math.f90:1664-1676), weights(1) = 0.5
+    (:194), `2 - 0.3` of the scaling is default real (:179), T_n comes from the recurrence and c_n = (x - i n sqrt(1 - x^2)) exp(i n acos x)
+    (:197-200).  Raises ValueError for an energy outside the open window (energy_min, energy_max) and for more than 8 energies (16 columns
+    per call)."""
+    cond_ll = int(cond_ll)
+    x, _ = _scaled_energies(energies, energy_min, energy_max, _lib.KUBO_SHOT_NE_MAX // 2, "kubo_bastin_weights")
+    n = np.arange(cond_ll, dtype=np.float64)[:, None]
+    acos_x, s = np.arccos(x)[None, :], np.sqrt(1.0 - x ** 2)[None, :]
+    cn = (x[None, :] - 1j * n * s) * np.exp(1j * n * acos_x)
+    cm = (x[None, :] + 1j * n * s) * np.exp(-1j * n * acos_x)
+    t = _chebyshev_t(x, cond_ll)
+    step = np.arange(1, cond_ll + 1, dtype=np.float32)
+    lor = np.float32(1) - (step - np.float32(1)) / np.float32(cond_ll)                # REAL(4) throughout
+    gw = np.sinh(6.0 * lor.astype(np.float64)) / np.sinh(6.0)
+    gw[0] *= 0.5
+    gw = gw[:, None]
+    f = 16.0 / (np.pi * (energy_max - energy_min) ** 2) / ((1.0 - x ** 2) ** 2)[None, :]
+    wl = np.empty((cond_ll, 2 * x.size), np.complex128, order="F")
+    wr = np.empty((cond_ll, 2 * x.size), np.complex128, order="F")
+    wl[:, 0::2], wr[:, 0::2] = gw * t, f * gw * cn
+    wl[:, 1::2], wr[:, 1::2] = gw * cm, f * gw * t
+    return wl, wr
+
+
+def kubo_greenwood_weights(energies, cond_ll, energy_min, energy_max):
+    """The weights with which ``Recursion.kubo_single_shot`` gives the Kubo-Greenwood trace Tr[v_out delta(E - H) v_b delta(E - H)]:
+    ``(wl, wr)`` with wl = wr = d, real values as complex (cond_ll, nE) in Fortran order,
+    d(n, e) = jackson_n (2 - delta_{n,1}) T_{n-1}(x_e) / (pi a sqrt(1 - x_e^2)), x_e = (E_e - b) / a, so that
+    sum_n d(n, e) T_{n-1}(H~) = delta(E_e - H) broadened by the Jackson kernel of cond_ll terms (math.f90:1641-1655), a and b of
+    ``chebyshev_scaling``.  The delta function is finite on the whole Chebyshev axis, so energies beyond the window are taken as long
+    as |x_e| < 1.  Raises ValueError for an energy outside (b - a, b + a) and for more than 16 energies."""
+    cond_ll = int(cond_ll)
+    x, a = _scaled_energies(energies, energy_min, energy_max, _lib.KUBO_SHOT_NE_MAX, "kubo_greenwood_weights", window=False)
+    n = np.arange(cond_ll, dtype=np.float64)
+    th = np.pi * n / (cond_ll + 1.0)
+    kern = ((cond_ll - n + 1.0) * np.cos(th) + np.sin(th) / np.tan(np.pi / (cond_ll + 1.0))) / (cond_ll + 1.0)
+    kern[1:] *= 2.0
+    d = kern[:, None] * _chebyshev_t(x, cond_ll) / (np.pi * a * np.sqrt(1.0 - x ** 2))[None, :]
+    d = np.asfortranarray(d, dtype=np.complex128)
+    return d, d.copy(order="F")
+
+
 def _fc(a, dtype):
     return np.asfortranarray(np.asarray(a, dtype=dtype))
 
@@ -146,10 +220,11 @@ class Recursion:
 
 
     def timing(self):
-        out = (C.c_double * 17)()
-        self._L.rsrec_get_timing(self._h, out, 17)
+        out = (C.c_double * 21)()
+        self._L.rsrec_get_timing(self._h, out, 21)
         keys = ("total_ms", "hop_ms", "hop_launches", "atom_steps", "block_multiplies", "rest_ms", "host_ms", "hop_fuses_a", "hop_mfma_flop", "hop_required_flop",
-                "operator_arrays_from_device", "octet_launches", "rotate_ms", "gram_folded_launches", "map_accum_ms", "map_phase_ms", "map_final_ms")
+                "operator_arrays_from_device", "octet_launches", "rotate_ms", "gram_folded_launches", "map_accum_ms", "map_phase_ms", "map_final_ms",
+                "shot_accum_ms", "shot_final_ms", "kubo_left_chunks", "kubo_lchunk_planned")
         return dict(zip(keys, list(out)))
 
     # -- state (restore_to_default, recursion.f90:3713-3825) --------------------------------------------
@@ -603,6 +678,47 @@ class Recursion:
         nout, nin = keep[0].shape[4], keep[2].shape[4]
         return self._kubo_moments(self._L.rsrec_kubo_moments_diag_tensor, (nin, nout), keep, cond_ll, seeds, coefs, atlist, (nout, nin),
                                   resident_only)
+
+    def kubo_single_shot(self, v_out, v_b, wl, wr, vo_out=None, vo_b=None, seeds=None, coefs=None, atlist=None, blocks=False):
+        """The double sum over the Kubo moments at a few weight columns without the moments (``rsrec_kubo_single_shot``):
+        s(:, :, e, v, j) = sum_{n,m} wl(m, e) wr(n, e) mu_j(:, :, n, m, v), mu_j what ``compute_moments_stochastic`` returns for
+        (v_a, v_b) = (v_out[..., j], v_b), from L_e = sum_m conj(wl(m, e)) T_{m-1}(H~) r and R_e = sum_n wr(n, e) T_{n-1}(H~) v_b r --
+        no left matrix, no cond_ll x cond_ll contraction, 2 (cond_ll - 1) chain steps per vector whatever the cell size.
+        ``v_out`` (18, 18, nslots, ntype[, nout]) (``vo_out`` likewise, hoh only), ``v_b`` one input operator; ``wl``, ``wr`` complex
+        (cond_ll, ne), ne <= 16, row n for order n - 1 (``kubo_greenwood_weights``, ``kubo_bastin_weights``, or any table: the library does
+        not interpret them, and conjugates ``wl`` itself on the bra side).  Vectors as ``compute_moments_stochastic_multi`` takes them:
+        ``atlist``, or ``seeds`` and ``coefs`` (nvec, nseed).  Returns ``s_diag`` complex (18, ne, nvec, nout) in Fortran order, or
+        ``(s_diag, s_full)`` with ``blocks=True``, s_full complex (18, 18, ne, nvec, nout) whose diagonal s_diag is bit for bit.
+        Nothing is normalised and nothing stays resident (resident diagonal moments of an earlier call are dropped).  A Fermi-sea
+        integral over a whole mesh (sigma_xy) still needs the moments: ``compute_moments_stochastic(diag=True)`` and
+        ``Conductivity.tensor``."""
+        def five(v):
+            if v is None:
+                return None
+            v = np.asarray(v)
+            return _fc(v[..., None] if v.ndim == 4 else v, np.complex128)
+        keep = [five(v_out), five(vo_out), None if v_b is None else _fc(v_b, np.complex128), None if vo_b is None else _fc(vo_b, np.complex128)]
+        if keep[0] is None or keep[0].ndim != 5 or (keep[1] is not None and keep[1].shape != keep[0].shape):
+            raise ValueError("v_out (and vo_out) must be (18, 18, nslots, ntype[, nout]), got %s" % (None if keep[0] is None else keep[0].shape,))
+        wl, wr = _fc(wl, np.complex128), _fc(wr, np.complex128)
+        if wl.ndim != 2 or wr.shape != wl.shape:
+            raise ValueError("wl and wr must both be (cond_ll, ne), got %r and %r" % (wl.shape, wr.shape))
+        cond_ll, ne = wl.shape
+        nout = keep[0].shape[4]
+        a, b = chebyshev_scaling(self.en.energy_min, self.en.energy_max)
+        if seeds is None:
+            seeds = np.asarray(atlist, dtype=np.int32).reshape(-1, 1)
+            coefs = np.ones(seeds.shape, np.complex128)
+        seeds = np.ascontiguousarray(seeds, dtype=np.int32)
+        coefs = np.ascontiguousarray(coefs, dtype=np.complex128)
+        nvec, nseed = seeds.shape
+        s_diag = np.zeros((18, ne, nvec, nout), np.complex128, order="F")
+        s_full = np.zeros((18, 18, ne, nvec, nout), np.complex128, order="F") if blocks else None
+        self._check(self._L.rsrec_kubo_single_shot(self._h, nout, nvec, nseed, _ptr(seeds), _ptr(coefs), int(cond_ll), a, b, *[_ptr(k) for k in keep],
+                                                   int(ne), _ptr(wl), _ptr(wr), _ptr(s_full), _ptr(s_diag)))
+        if nvec > 0:                                   # (a call without vectors returns before the handle drops anything)
+            self.mu_diag_resident = None
+        return (s_diag, s_full) if blocks else s_diag
 
     def ham_vec_matmul(self, psi_in, a, b):
         """psi_out = (H psi_in - b psi_in)/a on a whole vector psi(18,18,kk) with the PLAIN operator ee + l.s, whatever hoh says
