@@ -457,6 +457,19 @@ module rsrec_binding
          integer(c_int) :: rc
       end function
 
+      !> the 18 x 18 block of ne functions of H on every atom from the same seeds: w complex (2*lld+2,ne), host; d_full complex
+      !> (18,18,ne,kk), d_diag complex (18,ne,kk), host or device memory, either may be c_null_ptr; cnorm real (kk) or c_null_ptr.
+      !> Nothing is normalised, nothing stays resident.  The reference has no counterpart: there is no drop-in switch.
+      function rsrec_chebyshev_site_map(handle, nvec, nseed, seed_atoms, seed_coef, lld, a, b, ne, w, d_full, d_diag, cnorm) &
+         bind(C, name='rsrec_chebyshev_site_map') result(rc)
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: handle
+         integer(c_int), value :: nvec, nseed, lld, ne
+         real(c_double), value :: a, b
+         type(c_ptr), value :: seed_atoms, seed_coef, w, d_full, d_diag, cnorm
+         integer(c_int) :: rc
+      end function
+
       function rsrec_scalar_lanczos(handle, nsites, seed_atoms, lld, llmax, a, b2) bind(C, name='rsrec_scalar_lanczos') result(rc)
          import :: c_int, c_ptr
          type(c_ptr), value :: handle

@@ -405,6 +405,45 @@ int rsrec_chebyshev_bloch_map(rsrec_t *h, int nsrc, const int32_t *sources, int 
 int rsrec_chebyshev_lattice(rsrec_t *h, int nchains, int nseed, const int32_t *seed_atoms, const double *seed_coef, int lld, double a, double b,
                             int ngroup, const int32_t *group, double *m_g);
 
+/* Per-atom blocks of ne functions of H for a whole cell, from whole-lattice seeds (kernels_sitemap.hpp).  With the seeds
+ * |x^v> = sum_j c^v_j |j> (x) 1_18 of rsrec_chebyshev_lattice the vector the chain forms anyway holds, at atom j,
+ *   conj(c^v_j) [f(H~) x^v]_j = |c^v_j|^2 f(H~)_jj + sum_{k != j} conj(c^v_j) c^v_k f(H~)_jk,
+ * and the call sums it over the vectors while the orders stream by:
+ *   z_n[j]     = sum_v conj(c^v_j) [T_{n-1}(H~) x^v]_j       (v ascending within a tile of vectors, fused multiply-adds)
+ *   D(:,:,e,j) = sum_n w(n,e) z_n[j]                          (n ascending)
+ *   - random-phase seeds: the second term averages out over the vectors -- the stochastic on-site density matrix of EVERY atom;
+ *   - probing seeds (non-zero only on atoms far apart): the second term is small, and exactly zero when the degree 2*lld+1 is below the
+ *     graph distance between seeded atoms;
+ *   - one-atom seeds with coefficient 1: D(:,:,e,j) = sum_n w(n,e) M_jj(n) of rsrec_chebyshev_pairs_direct.
+ * With the columns of the Green weights this is the LDOS of every atom at ne energies; with the Chebyshev coefficients of f, E f, E^2 f for a
+ * Fermi function f the occupation matrices and band moments of every atom: 2*lld+1 whole-lattice products per vector, ne accumulators for
+ * the whole call, nothing that grows as atoms x orders -- O(N) where one chain per atom is O(N^2).
+ *   seed_atoms, seed_coef, nseed, lld, a, b : exactly as rsrec_chebyshev_lattice (placement: of several entries on one atom the last stays;
+ *             three-term recurrence, 2*lld+1 applications of H~, orders n = 1 .. 2*lld+2; no growing region).
+ *   w       : complex (2*lld+2, ne) column-major, host memory, not interpreted, as in rsrec_chebyshev_bloch_map.  1 <= ne <= RSREC_SITE_MAP_NE_MAX.
+ *   d_full  : complex (18,18,ne,kk) out;  d_diag : complex (18,ne,kk) out, bit for bit the diagonal of d_full.  Each host or device memory
+ *             (detected) or NULL; at least one is given.  The blocks are in the reference's column-major order.
+ *   cnorm   : real (kk) out or NULL: sum_v |c^v_j|^2 of the coefficients actually placed.  The caller divides; nothing is normalised.
+ * An atom on which no vector of the call has a coefficient gives an exact zero block.  Both kernel sets (option kernels: the products are
+ * k_spmm5 launches on CI vectors either way), hoh and per-atom operator blocks are served.  The call leaves no resident image and drops what
+ * an earlier call left.  Up to 8 vectors advance as the chains of one launch (option kubo_vbatch), fewer if the ring does not fit; per
+ * vector in flight the call holds PT + 2 ring slots (one more with hoh), once per call ne accumulators of kk blocks and, for a host output,
+ * a staging slice whose size does not depend on kk.  RSREC_ERR_DEVICE with the bytes needed if one vector at a time does not fit.
+ * Reproducibility: fixed order, no float atomics; the same inputs and options give the same bits whatever earlier calls left in the buffers.
+ * The bits of column e depend on neither ne nor the other columns; the bits of an atom's block do not depend on which outputs are asked for,
+ * nor on host or device destination.  They DO depend on the order of the vectors, on sitemap_vtile, sitemap_orders and on the vector batch:
+ * the accumulator is shared by all vectors, and the sequence of adds into it is (batch, pass, tile, order).
+ * RSREC_ERR_DIVERGED if the real or imaginary part of any element of any z_n exceeds 1000 max(1, sum_v sum_j |c^v_j|^2) in magnitude, tested
+ * by the accumulation pass on the values it holds; the outputs are then left alone.  RSREC_ERR_ARG with a message, the handle staying
+ * usable, for everything rsrec_chebyshev_lattice refuses about seeds, lld and a, for ne out of range, NULL w, a non-finite weight, and
+ * d_full and d_diag both NULL.  nvec = 0 returns RSREC_OK and writes nothing.
+ * rsrec_get_timing: out[0] device ms, out[1] ms in the H|psi> launches, out[2] their number ((2 with hoh, else 1) (2*lld+1) per batch),
+ * out[5] ms in the accumulation passes plus the output stage; out[21], out[22] the two apart. */
+#define RSREC_SITE_MAP_NE_MAX 16
+int rsrec_chebyshev_site_map(rsrec_t *h, int nvec, int nseed, const int32_t *seed_atoms, const double *seed_coef,
+                             int lld, double a, double b, int ne, const double *w,
+                             double *d_full, double *d_diag, double *cnorm);
+
 /* Stochastic Kubo-Bastin double moments.  Replaces compute_moments_stochastic (recursion.f90:979-1234) together with the
  * whole-vector products it is built from: ham_vec_matmul (:913), ham_hoh_vec_matmul (:785), velo_vec_matmul (:587),
  * velo_hoh_vec_matmul (:656):
@@ -804,7 +843,13 @@ int rsrec_comm_destroy(rsrec_t *h);
  *                2 / 3 = groups of at most that width [0 = 2]
  *   "shot_orders" rsrec_kubo_single_shot: orders P added to the accumulators per pass, 1..16 (larger values: 16); the ring holds P + 2 orders per
  *                chain and a pass moves (P + 2 ne) / P block streams per order and chain; the same bits for every value [0 = 16: the fastest of
- *                1, 2, 4, 8, 16 at ne = 2 and 16 on 8 000 and 97 336 atoms, 0.87-0.99 of the call's time at 8 and 0.33-0.83 of it at 1, DESIGN.md section 5] */
+ *                1, 2, 4, 8, 16 at ne = 2 and 16 on 8 000 and 97 336 atoms, 0.87-0.99 of the call's time at 8 and 0.33-0.83 of it at 1, DESIGN.md section 5]
+ *   "sitemap_orders" rsrec_chebyshev_site_map: orders PT added to the accumulators per pass, 1, 2, 4, 8 or 16 (other values: the power of two below);
+ *                the ring holds PT + 2 orders per vector [0 = 2]
+ *   "sitemap_vtile" rsrec_chebyshev_site_map: vectors VT folded into z per pass, 1, 2, 4 or 8; a tile-pass moves (VT PT + 2 ne) 16 B per element.  VT PT <= 16:
+ *                the value the caller did not set follows the other to VT PT = 16 (VT <= 8), of two set values VT gives way.  The bits depend on VT [0 = 8.  <8,2> is the fastest call of
+ *                <1,16>, <2,8>, <4,4>, <8,2>, or within 0.02 % of it, in 7 of 9 measured configurations on 10 648 and 97 336 atoms, all four within 1.2 % of each other, and
+ *                keeps the shallowest ring, DESIGN.md section 5] */
 int rsrec_set_option(rsrec_t *h, const char *key, long value);
 /* Timing of the last recursion call, measured with HIP events on the engine's own stream:
  *   out[0] total device ms, out[1] ms in the H|psi> kernels, out[2] number of H|psi> launches,
@@ -824,6 +869,7 @@ int rsrec_set_option(rsrec_t *h, const char *key, long value);
  *   out[17..18] rsrec_kubo_single_shot: ms in the accumulation passes and in the final stage (together: out[5]).
  *   out[19..20] rsrec_kubo_moments and its _diag / _multi / _tensor forms: left chunks formed, summed over the vector batches of the call (one
  *           per batch when every left matrix fits), and the left vectors per chunk as planned (cond_ll then; option kubo_lchunk caps it).
+ *   out[21..22] rsrec_chebyshev_site_map: ms in the accumulation passes and in the output stage (together: out[5]).
  * After rsrec_block_green: out[0] = kernel + transfers, out[1] = the Green kernel alone. */
 int rsrec_get_timing(rsrec_t *h, double *out, int n);
 

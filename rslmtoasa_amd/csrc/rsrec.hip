@@ -53,6 +53,7 @@
 #include "kernels_blochmap.hpp"
 #include "kernels_lattice.hpp"
 #include "kernels_shot.hpp"
+#include "kernels_sitemap.hpp"
 
 using namespace rsrec;
 
@@ -152,6 +153,7 @@ struct rsrec_handle {
     DevBuf d_bloch_geo, d_bloch_tab;    // rsrec_chebyshev_bloch: positions and k-points of the call; lists, segment offsets and level counts of a batch
     DevBuf d_map_w;                     // rsrec_chebyshev_bloch_map: the weights w(n, e) of the call
     DevBuf d_shot_w;                    // rsrec_kubo_single_shot: the weights of the call, [conj(wl) | wr][e][order]
+    DevBuf d_site_w, d_site_coef;       // rsrec_chebyshev_site_map: the weights w(n, e) of the call; the conjugated coefficient tables of a batch, (kk) per vector
     DevBuf d_lat_tab, d_lat_w, d_lat_part;   // rsrec_chebyshev_lattice: lists and offsets of a batch; weights and divergence bounds; split partials
     // options
     long opt_batch = 0, opt_kernels = 0, opt_nblk = 0, opt_spmm5 = 2, opt_chain_fold = 1, opt_s5_cap = 0, opt_side = 1, opt_s5_lds = 1, opt_s5_queue = 1, opt_cheb_fused = 1;
@@ -169,6 +171,7 @@ struct rsrec_handle {
     long opt_blochmap_orders = 2;  // rsrec_chebyshev_bloch_map: orders added to the accumulators per pass (1 | 2: same bits, see kernels_blochmap.hpp)
     long opt_blochmap_kchunk = 0;  // rsrec_chebyshev_bloch_map: k-points per chunk of the final sums (0: 256, one launch's rows of the phase matrix); tests force it small
     long opt_shot_orders = 0;    // rsrec_kubo_single_shot: orders added to the accumulators per pass (1..16; 0: SHOT_ORDERS_DEFAULT = 16; the same bits for every value)
+    long opt_sitemap_orders = 0, opt_sitemap_vtile = 0;   // rsrec_chebyshev_site_map: orders PT added per pass (1..16) and vectors VT folded per pass (1..8), VT PT <= 16; 0: SITE_*_DEFAULT
     long opt_kubo_setgroup = 0;  // rsrec_kubo_moments_diag_tensor: sets of a vector contracted against one staged left tile (k_kubo_gram_diag_sets): 0 default (2), 1 every set by itself (k_kubo_gram_diag), 2 / 3 groups of at most that width
     int n_kubo_left_chunks = 0, kubo_lchunk_planned = 0;   // of the last Kubo moment call: left chunks formed over all its batches; left vectors per chunk as kubo_plan decided
     int kubo_diag_nvec = 0, kubo_diag_ll = 0;   // rsrec_kubo_moments_diag / _multi / _tensor: the call whose diagonal moments lie in d_kubo[4] (0: nothing resident; _multi: nvec * nout; _tensor: nvec * nout * nin)
@@ -192,6 +195,7 @@ struct rsrec_handle {
     // timing of last call
     double t_total_ms = 0, t_hop_ms = 0, t_rest_ms = 0, t_host_ms = 0;
     double t_rot_ms = 0;      // local-axis recursion: ms in k_rotate_coef (part of t_rest_ms)
+    double t_site_ms[2] = {0, 0};     // rsrec_chebyshev_site_map: ms in the accumulation passes, in the output stage (their sum: t_rest_ms)
     double t_shot_ms[2] = {0, 0};     // rsrec_kubo_single_shot: ms in the accumulation passes, in the final stage (their sum: t_rest_ms)
     double t_map_ms[3] = {0, 0, 0};   // rsrec_chebyshev_bloch_map: ms in the accumulation passes, the phase tables, the final sums (their sum: t_rest_ms)
     double n_hop_launch = 0, n_atom_steps = 0, n_block_mult = 0, n_hop_mfma_flop = 0;   // mfma_flop: matrix flops EXECUTED by the timed k_spmm5 launches
@@ -249,6 +253,8 @@ const OptionEntry OPTIONS[] = {
     {"kubo_vbatch", &rsrec_handle::opt_kubo_vbatch},
     {"kubo_setgroup", &rsrec_handle::opt_kubo_setgroup},
     {"shot_orders", &rsrec_handle::opt_shot_orders},
+    {"sitemap_orders", &rsrec_handle::opt_sitemap_orders},
+    {"sitemap_vtile", &rsrec_handle::opt_sitemap_vtile},
     {"lattice_vbatch", &rsrec_handle::opt_lattice_vbatch},
     {"blochmap_orders", &rsrec_handle::opt_blochmap_orders},
     {"blochmap_kchunk", &rsrec_handle::opt_blochmap_kchunk},
@@ -419,9 +425,9 @@ extern "C" int rsrec_set_option(rsrec_t* h, const char* key, long value) {
 
 extern "C" int rsrec_get_timing(rsrec_t* h, double* out, int n) {
     if (!h || !out) return RSREC_ERR_ARG;
-    const double v[21] = {h->t_total_ms, h->t_hop_ms, h->n_hop_launch, h->n_atom_steps, h->n_block_mult, h->t_rest_ms, h->t_host_ms, (double)h->hop_fuses_a, h->n_hop_mfma_flop,
-                          h->n_req_flop, (double)h->n_asm_reused, (double)h->n_octet_launch, h->t_rot_ms, h->n_gram_folded, h->t_map_ms[0], h->t_map_ms[1], h->t_map_ms[2], h->t_shot_ms[0], h->t_shot_ms[1], (double)h->n_kubo_left_chunks, (double)h->kubo_lchunk_planned};
-    for (int i = 0; i < n && i < 21; ++i) out[i] = v[i];
+    const double v[23] = {h->t_total_ms, h->t_hop_ms, h->n_hop_launch, h->n_atom_steps, h->n_block_mult, h->t_rest_ms, h->t_host_ms, (double)h->hop_fuses_a, h->n_hop_mfma_flop,
+                          h->n_req_flop, (double)h->n_asm_reused, (double)h->n_octet_launch, h->t_rot_ms, h->n_gram_folded, h->t_map_ms[0], h->t_map_ms[1], h->t_map_ms[2], h->t_shot_ms[0], h->t_shot_ms[1], (double)h->n_kubo_left_chunks, (double)h->kubo_lchunk_planned, h->t_site_ms[0], h->t_site_ms[1]};
+    for (int i = 0; i < n && i < 23; ++i) out[i] = v[i];
     return RSREC_OK;
 }
 
@@ -783,6 +789,7 @@ void reset_timing(rsrec_t* h) {
     h->t_total_ms = h->t_hop_ms = h->t_rest_ms = h->t_host_ms = h->t_rot_ms = 0;
     h->t_map_ms[0] = h->t_map_ms[1] = h->t_map_ms[2] = 0;
     h->t_shot_ms[0] = h->t_shot_ms[1] = 0;
+    h->t_site_ms[0] = h->t_site_ms[1] = 0;
     h->n_kubo_left_chunks = h->kubo_lchunk_planned = 0;
     h->n_hop_launch = h->n_atom_steps = h->n_block_mult = h->n_hop_mfma_flop = h->n_req_flop = 0;
     h->n_octet_launch = 0;
@@ -4801,6 +4808,235 @@ extern "C" int rsrec_chebyshev_lattice(rsrec_t* h, int nchains, int nseed, const
     if (nchains == 0) return RSREC_OK;
     const LatticeCall A{nchains, lld, ngroup, KuboSeeds{nseed, seed_atoms, seed_coef}, group, a, b, m_g};
     return matrix_core_set(h) ? run_lattice<true>(h, who, A) : run_lattice<false>(h, who, A);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Per-atom blocks of ne functions of H from whole-lattice seeds (kernels_sitemap.hpp): the vectors of rsrec_chebyshev_lattice on the ring of
+// rsrec_kubo_single_shot, folded over the vectors before the weights are applied, into ne accumulators shared by all vectors of the call
+namespace {
+
+constexpr int SITE_ORDERS_DEFAULT = 2, SITE_VTILE_DEFAULT = 8;   // what sitemap_orders = 0 / sitemap_vtile = 0 mean: <8,2>, the fastest call or within 0.02 % of it in 7 of the 9 measured configurations, the four shapes within 1.2 %
+constexpr int SITE_STAGE_ATOMS = 512;                            // atoms per slice of a host output: the staging buffer does not grow with kk
+
+struct SiteCall {
+    int nvec, lld, ne;
+    KuboSeeds S;
+    double a, b;
+    const double* w;
+    double *d_full, *d_diag, *cnorm;
+};
+
+// The device memory of a call, decided before anything is reserved.  Per vector in flight: the ring of PT + 2 order slots, with hoh h psi,
+// and its coefficient table; once per call the ne accumulators and the staging slice of a host output.
+struct SitePlan {
+    int VT = 0, PT = 0, R = 0, nbv = 0, ne = 0;
+    size_t velems = 0, slot = 0, dstride = 0;      // doubles of a vector; of a ring slot (nbv vectors); complex elements of an accumulator
+    size_t bytes_work = 0, bytes_acc = 0, bytes_stage = 0;
+    double *ring = nullptr, *hps = nullptr;
+    double2 *acc = nullptr, *stage_full = nullptr, *stage_diag = nullptr;
+    double* ring_slot(int n) const { return ring + (size_t)(n % R) * slot; }
+};
+
+// VT and PT from the options: a value the caller set stays and the other follows it to VT PT = 16 (VT <= 8); of two set values VT gives way
+void site_tile_shape(const rsrec_t* h, int& VT, int& PT) {
+    auto pow2_floor = [](long v, int hi) { int q = 1; while (2 * q <= v && 2 * q <= hi) q *= 2; return q; };
+    VT = h->opt_sitemap_vtile > 0 ? pow2_floor(h->opt_sitemap_vtile, SITE_VTILE_MAX) : SITE_VTILE_DEFAULT;
+    PT = h->opt_sitemap_orders > 0 ? pow2_floor(h->opt_sitemap_orders, SITE_ORDERS_MAX) : SITE_ORDERS_DEFAULT;
+    if (h->opt_sitemap_vtile > 0 && h->opt_sitemap_orders <= 0) PT = SITE_LOADS_MAX / VT;                    // (the 16 loads stay in flight)
+    else if (h->opt_sitemap_orders > 0 && h->opt_sitemap_vtile <= 0) VT = std::min(SITE_VTILE_MAX, SITE_LOADS_MAX / PT);
+    else VT = std::min(VT, SITE_LOADS_MAX / PT);
+}
+
+int site_plan(rsrec_t* h, const char* who, const SiteCall& A, bool stage, SitePlan& P) {
+    const int kk = h->kk;
+    const bool hoh = h->hoh != 0;
+    site_tile_shape(h, P.VT, P.PT);
+    P.R = P.PT + 2; P.ne = A.ne;
+    P.velems = (size_t)(kk + 1) * BLD;
+    P.dstride = (size_t)kk * BLK;
+    P.bytes_acc = (size_t)A.ne * P.dstride * sizeof(double2);
+    P.bytes_stage = stage ? (size_t)std::min(kk, SITE_STAGE_ATOMS) * A.ne * (BLK + NB) * sizeof(double2) : 0;
+    size_t free_b = 0, total_b = 0;
+    HIPCK(h, hipMemGetInfo(&free_b, &total_b));
+    size_t reusable = h->d_site_coef.bytes;
+    for (int v = 0; v < 6; ++v) reusable += h->d_vec[v].bytes;
+    for (auto& kb : h->d_kubo) reusable += kb.bytes;
+    const double budget = 0.9 * (double)(free_b + reusable);
+    auto need_for = [&](int nv) { return (double)nv * ((P.R + (hoh ? 1 : 0)) * (double)P.velems * 8 + (double)kk * 16) + (double)P.bytes_acc + (double)P.bytes_stage; };
+    int nbv = (int)std::min<long>({(long)A.nvec, h->opt_kubo_vbatch > 0 ? h->opt_kubo_vbatch : KUBO_CHAINS_MAX, (long)KUBO_CHAINS_MAX});
+    while (nbv > 1 && need_for(nbv) > budget) --nbv;
+    if (need_for(nbv) > budget)
+        return fail(h, RSREC_ERR_DEVICE, "%s: %.0f bytes needed for one vector at a time on %d atoms (ne=%d, sitemap_orders=%d), %.0f bytes free", who, need_for(1), kk,
+                    A.ne, P.PT, (double)free_b);
+    P.nbv = nbv; P.slot = (size_t)nbv * P.velems;
+    P.bytes_work = (size_t)(P.R + (hoh ? 1 : 0)) * P.slot * 8;
+    return RSREC_OK;
+}
+
+// The plan's buffers out of the handle's Kubo buffers: d_kubo[0] the ring (and h psi), [3] the accumulators, [4] the staging slice.  The ring is
+// cleared (block kk of every vector stays the zero block) and so are the accumulators: once per call, they persist across the batches.
+int site_reserve(rsrec_t* h, const char* who, SitePlan& P) {
+    const size_t want[5] = {P.bytes_work, 0, 0, P.bytes_acc, P.bytes_stage};
+    for (int v = 0; v < 6; ++v) h->d_vec[v].release();
+    h->d_kubo[1].release(); h->d_kubo[2].release();
+    XFER(reserve_kubo_buffers(h, want, who));
+    P.ring = h->d_kubo[0].as<double>();
+    P.hps = h->hoh ? P.ring + (size_t)P.R * P.slot : nullptr;
+    P.acc = h->d_kubo[3].as<double2>();
+    P.stage_full = h->d_kubo[4].as<double2>();
+    P.stage_diag = P.stage_full ? P.stage_full + P.bytes_stage / sizeof(double2) / (BLK + NB) * BLK : nullptr;
+    HIPCK(h, hipMemsetAsync(h->d_kubo[0].p, 0, P.bytes_work, h->stream));
+    HIPCK(h, hipMemsetAsync(h->d_kubo[3].p, 0, P.bytes_acc, h->stream));
+    return RSREC_OK;
+}
+
+// one accumulation pass of one tile: orders n0 .. n0 + cnt - 1 of vectors v0 .. v0 + nv - 1 of the batch into the ne accumulators
+template <int VT>
+void site_accumulate_vt(rsrec_t* h, const SitePlan& P, const SitePass& S, int PT) {
+    const double2* ring = reinterpret_cast<const double2*>(P.ring);
+    const double2 *coef = h->d_site_coef.as<double2>(), *w = h->d_site_w.as<double2>();
+    const unsigned grid = (unsigned)((S.total + SITE_THREADS - 1) / SITE_THREADS);
+    int* status = h->d_status.as<int>();
+    auto go = [&](auto kern) { kern<<<grid, SITE_THREADS, 0, h->stream>>>(ring, coef, w, S, P.acc, status); };
+    if (PT == 1) go(k_site_accum<VT, 1>);
+    else if (PT == 2) go(k_site_accum<VT, 2>);
+    else if constexpr (VT <= 4) {
+        if (PT == 4) go(k_site_accum<VT, 4>);
+        else if constexpr (VT <= 2) {
+            if (PT == 8) go(k_site_accum<VT, 8>);
+            else if constexpr (VT == 1) go(k_site_accum<1, 16>);
+        }
+    }
+}
+void site_accumulate(rsrec_t* h, const SitePlan& P, const SitePass& S) {
+    if (P.VT == 1) site_accumulate_vt<1>(h, P, S, P.PT);
+    else if (P.VT == 2) site_accumulate_vt<2>(h, P, S, P.PT);
+    else if (P.VT == 4) site_accumulate_vt<4>(h, P, S, P.PT);
+    else site_accumulate_vt<8>(h, P, S, P.PT);
+}
+
+// rsrec_chebyshev_site_map behind its argument checks.  Per batch of nb vectors: 2 lld + 1 launches (twice that with hoh) advance all of
+// them through the ring; after every PT orders and after the last one, one pass per tile of VT vectors adds the ring's new orders into the
+// accumulators.  Behind the last batch k_site_out writes the blocks, in place into device memory or slice by slice through the staging buffer.
+int run_site_map(rsrec_t* h, const char* who, const SiteCall& A) {
+    const int kk = h->kk, ne = A.ne, nmom = 2 * A.lld + 2;
+    drop_resident(h);                                            // the call leaves no image, and what an earlier call left goes with the buffers
+    h->kubo_diag_nvec = h->kubo_diag_ll = 0;
+    release_kubo_buffers(h, false, true);
+    // one host pass over the seeds: the conjugated coefficient every vector leaves on every atom (the last entry on an atom stays), cnorm,
+    // and the divergence bound
+    std::vector<double> table((size_t)2 * A.nvec * kk, 0.0), cn(kk, 0.0);
+    {
+        std::vector<int> s0; std::vector<double> cf;
+        for (int v = 0; v < A.nvec; ++v) {
+            whole_vector_seeds(A.S, v, s0, cf);
+            double* tv = table.data() + (size_t)2 * v * kk;
+            for (size_t k = 0; k < s0.size(); ++k) { tv[2 * s0[k]] = cf[2 * k]; tv[2 * s0[k] + 1] = -cf[2 * k + 1]; }
+            for (int j = 0; j < kk; ++j) cn[j] += tv[2 * j] * tv[2 * j] + tv[2 * j + 1] * tv[2 * j + 1];
+        }
+    }
+    double norm2 = 0.0;
+    for (int j = 0; j < kk; ++j) norm2 += cn[j];
+    const bool full_dev = A.d_full && is_device_ptr(A.d_full), diag_dev = A.d_diag && is_device_ptr(A.d_diag);
+    const bool stage = (A.d_full && !full_dev) || (A.d_diag && !diag_dev);
+    SitePlan P;
+    XFER(site_plan(h, who, A, stage, P));
+    XFER(site_reserve(h, who, P));
+    HIPCK(h, h->d_status.reserve(64));
+    HIPCK(h, hipMemsetAsync(h->d_status.p, 0, 64, h->stream));
+    HIPCK(h, h->d_seed.reserve((size_t)A.S.nseed * 4));
+    HIPCK(h, h->d_seedcoef.reserve((size_t)A.S.nseed * sizeof(double2)));
+    HIPCK(h, h->d_site_coef.reserve((size_t)P.nbv * kk * sizeof(double2)));
+    HIPCK(h, h->d_site_w.reserve((size_t)nmom * ne * sizeof(double2)));
+    XFER(xfer_h2d(h, h->d_site_w.p, A.w, (size_t)nmom * ne * sizeof(double2)));
+    WholeLatticeCall W;
+    XFER(whole_lattice_begin(h, W, P.nbv, true));
+    W.hps = P.hps;
+    W.ev_begin = next_event(h);
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> acc_ev, out_ev;
+    SitePass S{};
+    S.slot_stride = P.slot / 2; S.vstride = P.velems / 2; S.total = (size_t)kk * BLK; S.dstride = P.dstride;
+    S.nring = P.R; S.kk = kk; S.nmom = nmom; S.ne = ne; S.bound = 1000.0 * std::max(1.0, norm2);
+    for (int iv0 = 0; iv0 < A.nvec; iv0 += P.nbv) {
+        const int nb = std::min(P.nbv, A.nvec - iv0);
+        double* r0 = P.ring_slot(0);
+        HIPCK(h, hipMemsetAsync(r0, 0, P.slot * 8, h->stream));
+        XFER(xfer_h2d(h, h->d_site_coef.p, table.data() + (size_t)2 * iv0 * kk, (size_t)nb * kk * sizeof(double2)));
+        XFER(seed_whole_vectors<LayoutCI>(h, who, A.S, iv0, nb, r0, P.velems));
+        whole_lattice_batch(W, nb, false);
+        for (int n = 0, n0 = 0; n < nmom; ++n) {
+            if (n >= 1) {
+                const double* cur = P.ring_slot(n - 1);
+                whole_lattice_apply_h(W, cur, P.ring_slot(n), cheb_epilogue(n == 1, cur, n >= 2 ? P.ring_slot(n - 2) : nullptr, A.a, A.b));
+            }
+            if (n - n0 + 1 == P.PT || n == nmom - 1) {
+                hipEvent_t e0 = next_event(h);
+                S.n0 = n0; S.slot0 = n0 % P.R; S.cnt = n - n0 + 1;
+                for (int v0 = 0; v0 < nb; v0 += P.VT) {
+                    S.v0 = v0; S.nv = std::min(P.VT, nb - v0);
+                    site_accumulate(h, P, S);
+                }
+                acc_ev.emplace_back(e0, next_event(h));
+                n0 = n + 1;
+            }
+        }
+        HIPCK(h, hipGetLastError());
+    }
+    // the divergence word before anything is written: a diverged call returns the error and leaves the outputs alone
+    const int rc_status = finish_status(h);
+    if (rc_status) { (void)whole_lattice_end(h, W, true); return rc_status; }
+    hipEvent_t o0 = next_event(h);
+    const unsigned out_rows = (unsigned)std::min(kk, 4096);
+    if (full_dev || diag_dev)
+        k_site_out<LayoutCI><<<dim3(ne, out_rows), SITE_OUT_THREADS, 0, h->stream>>>(P.acc, P.dstride, 0, kk, ne, full_dev ? reinterpret_cast<double2*>(A.d_full) : nullptr,
+                                                                                     diag_dev ? reinterpret_cast<double2*>(A.d_diag) : nullptr);
+    if (stage)
+        for (int j0 = 0; j0 < kk; j0 += SITE_STAGE_ATOMS) {
+            const int nj = std::min(SITE_STAGE_ATOMS, kk - j0);
+            double2* sf = A.d_full && !full_dev ? P.stage_full : nullptr;
+            double2* sd = A.d_diag && !diag_dev ? P.stage_diag : nullptr;
+            k_site_out<LayoutCI><<<dim3(ne, nj), SITE_OUT_THREADS, 0, h->stream>>>(P.acc, P.dstride, j0, nj, ne, sf, sd);
+            if (sf) XFER(xfer_d2h(h, A.d_full + (size_t)j0 * ne * 2 * BLK, sf, (size_t)nj * ne * BLK * sizeof(double2)));
+            if (sd) XFER(xfer_d2h(h, A.d_diag + (size_t)j0 * ne * 2 * NB, sd, (size_t)nj * ne * NB * sizeof(double2)));
+        }
+    HIPCK(h, hipGetLastError());
+    out_ev.emplace_back(o0, next_event(h));
+    if (A.cnorm) {
+        if (is_device_ptr(A.cnorm)) HIPCK(h, hipMemcpyAsync(A.cnorm, cn.data(), (size_t)kk * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        else std::copy(cn.begin(), cn.end(), A.cnorm);
+    }
+    XFER(whole_lattice_end(h, W, true));
+    for (auto& pr : acc_ev) h->t_site_ms[0] += ev_ms(pr.first, pr.second);
+    for (auto& pr : out_ev) h->t_site_ms[1] += ev_ms(pr.first, pr.second);
+    h->t_rest_ms = h->t_site_ms[0] + h->t_site_ms[1];
+    return RSREC_OK;
+}
+
+}  // namespace
+
+extern "C" int rsrec_chebyshev_site_map(rsrec_t* h, int nvec, int nseed, const int32_t* seed_atoms, const double* seed_coef, int lld, double a, double b, int ne,
+                                        const double* w, double* d_full, double* d_diag, double* cnorm) {
+    const char* who = "rsrec_chebyshev_site_map";
+    int rc = check_ready(h, who);
+    if (rc) return rc;
+    if (nvec < 0 || lld < 1 || a == 0.0) return fail(h, RSREC_ERR_ARG, "%s: nvec < 0, lld < 1 or a == 0", who);
+    if (nseed < 1 || nseed > h->kk) return fail(h, RSREC_ERR_ARG, "%s: nseed = %d outside 1..%d", who, nseed, h->kk);
+    if (nvec > 0 && (!seed_atoms || !seed_coef)) return fail(h, RSREC_ERR_ARG, "%s: NULL seed_atoms or seed_coef", who);
+    if (ne < 1 || ne > RSREC_SITE_MAP_NE_MAX) return fail(h, RSREC_ERR_ARG, "%s: ne = %d outside 1..%d", who, ne, RSREC_SITE_MAP_NE_MAX);
+    if (!w) return fail(h, RSREC_ERR_ARG, "%s: NULL w", who);
+    for (size_t q = 0; q < (size_t)2 * (2 * lld + 2) * ne; ++q)
+        if (!std::isfinite(w[q])) return fail(h, RSREC_ERR_ARG, "%s: weight (%zu, %zu) is not finite", who, q / 2 % (2 * lld + 2) + 1, q / 2 / (2 * lld + 2) + 1);
+    if (!d_full && !d_diag) return fail(h, RSREC_ERR_ARG, "%s: d_full and d_diag are both NULL", who);
+    if (!h->s5_built) return fail(h, RSREC_ERR_ARG, "%s: lattice has too many neighbour slots for the SpMM kernel", who);
+    XFER(check_seeds(h, who, seed_atoms, (size_t)nvec * nseed, 0));
+    for (int c = 0; c < nvec; ++c)
+        if (std::all_of(seed_atoms + (size_t)c * nseed, seed_atoms + (size_t)(c + 1) * nseed, [](int32_t s) { return s == 0; }))
+            return fail(h, RSREC_ERR_ARG, "%s: vector %d has no seed", who, c + 1);
+    HIPCK(h, hipSetDevice(h->device));
+    reset_timing(h);
+    if (nvec == 0) return RSREC_OK;
+    const SiteCall A{nvec, lld, ne, KuboSeeds{nseed, seed_atoms, seed_coef}, a, b, w, d_full, d_diag, cnorm};
+    return run_site_map(h, who, A);
 }
 
 extern "C" int rsrec_scalar_lanczos(rsrec_t* h, int nsites, const int32_t* seed_atoms, int lld, int llmax, double* a, double* b2) {

@@ -48,6 +48,21 @@ def supercell_positions(dims, primitive=BCC_PRIMITIVE):
     return np.asfortranarray((cells @ primitive).T)
 
 
+def supercell_colouring(dims, stride):
+    """A colouring of the supercell's atoms for probing vectors (``recursion.probing_seeds``): int32 (kk) in ``bcc_supercell``'s
+    numbering, colour = (c1 mod s) + s ((c2 mod s) + s (c3 mod s)) with s = ``stride``, s^3 colours.  Two atoms of one colour differ by
+    a multiple of s in every cell index, and a neighbour slot whose displacement changes each cell index by at most 1 (the bcc stencil's
+    two shells) moves one index by at most 1 per hop: same-coloured atoms are at least s hops apart, so a polynomial of degree < s in
+    H has no matrix element between them.  Raises ValueError unless s divides every dimension (the periodic images would come closer)."""
+    n1, n2, n3 = (int(x) for x in dims)
+    s = int(stride)
+    if s < 1 or n1 % s or n2 % s or n3 % s:
+        raise ValueError("stride %d does not divide every dimension of %r" % (s, (n1, n2, n3)))
+    c1, c2, c3 = np.meshgrid(np.arange(n1), np.arange(n2), np.arange(n3), indexing="ij")
+    c1, c2, c3 = (c.ravel(order="F") for c in (c1, c2, c3))
+    return ((c1 % s) + s * ((c2 % s) + s * (c3 % s))).astype(np.int32)
+
+
 def spread_sites(kk, nsites):
     """Seed sites 1 + k*floor(kk/S), k = 0..S-1, 1-based like ``irec``."""
     stride = max(kk // max(nsites, 1), 1)

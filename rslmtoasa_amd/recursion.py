@@ -99,6 +99,56 @@ def chebyshev_green_weights(energies, lld, energy_min, energy_max):
     return np.asfortranarray(kern[:, None] * phase / np.sqrt(a * a - (ene - b) ** 2)[None, :])
 
 
+def chebyshev_fermi_weights(fermi, kT, lld, energy_min, energy_max, powers=(0, 1, 2), jackson=False):
+    """The weights with which ``Recursion.site_map`` gives the occupation matrix and the band moments of every atom: real values as
+    complex (2 lld + 2, len(powers)) in Fortran order, column q the Chebyshev coefficients of E^q / (1 + exp((E - fermi) / kT)) in
+    x = (E - b) / a, a and b of ``chebyshev_scaling``, so that sum_n w(n, q) T_{n-1}(H~) = H^q f(H) to the accuracy of a degree-(2 lld + 1)
+    expansion.  Chebyshev-Gauss quadrature on the N = 2 lld + 2 points x_k = cos(pi (k + 1/2) / N):
+    c_n = (2 - delta_n0) / N sum_k F(a x_k + b) cos(n pi (k + 1/2) / N) -- the interpolant through those points.  ``jackson=True`` multiplies
+    row n by the Jackson damping g_n of N terms (math.f90:1641-1655), which trades the Gibbs ripples of a cold Fermi function for a
+    broadening of about pi a / N."""
+    nm = 2 * int(lld) + 2
+    a, b = chebyshev_scaling(energy_min, energy_max)
+    powers = [int(q) for q in powers]
+    k = np.arange(nm, dtype=np.float64)
+    theta = np.pi * (k + 0.5) / nm
+    ene = a * np.cos(theta) + b
+    with np.errstate(over="ignore"):
+        fermi_fn = 1.0 / (1.0 + np.exp((ene - fermi) / kT))
+    n = np.arange(nm, dtype=np.float64)
+    cosines = np.cos(n[:, None] * theta[None, :])                                       # (n, k)
+    w = np.empty((nm, len(powers)), np.complex128, order="F")
+    for col, q in enumerate(powers):
+        c = 2.0 / nm * (cosines @ (ene ** q * fermi_fn))
+        c[0] *= 0.5
+        w[:, col] = c
+    if jackson:
+        th = np.pi * n / (nm + 1.0)
+        g = ((nm - n + 1.0) * np.cos(th) + np.sin(th) / np.tan(np.pi / (nm + 1.0))) / (nm + 1.0)
+        w *= g[:, None]
+    return w
+
+
+def probing_seeds(colour, rng=None):
+    """Probing vectors for ``Recursion.site_map`` from a colouring of the atoms: ``colour`` int (kk) with values 0 .. nc - 1.  Returns
+    ``(seeds (nc, kk) int32, coefs (nc, kk) complex)``: vector c has coefficient 1 on the atoms of colour c -- or +-1 drawn from ``rng``
+    (a numpy Generator) -- and entry 0 (unused) elsewhere.  When same-coloured atoms are further apart than the degree of the polynomial,
+    D / cnorm of ``site_map`` is exact (``lattice.supercell_colouring``)."""
+    colour = np.asarray(colour)
+    if colour.ndim != 1 or colour.size == 0 or colour.min() < 0:
+        raise ValueError("colour must be (kk) with values 0 .. nc - 1")
+    kk, nc = colour.size, int(colour.max()) + 1
+    atoms = np.arange(1, kk + 1, dtype=np.int32)
+    sign = np.ones(kk) if rng is None else rng.choice([-1.0, 1.0], kk)
+    seeds = np.zeros((nc, kk), np.int32)
+    coefs = np.zeros((nc, kk), np.complex128)
+    for c in range(nc):
+        on = colour == c
+        seeds[c, on] = atoms[on]
+        coefs[c, on] = sign[on]
+    return seeds, coefs
+
+
 def _scaled_energies(energies, energy_min, energy_max, nmax, who, window=True):
     """(x_e, a) of a weight table: the energies on the Chebyshev axis.  ValueError for more than nmax energies and for one outside the
     open window (energy_min, energy_max), or with window=False outside the open axis |x_e| < 1 (which holds the window)."""
@@ -220,11 +270,11 @@ class Recursion:
 
 
     def timing(self):
-        out = (C.c_double * 21)()
-        self._L.rsrec_get_timing(self._h, out, 21)
+        out = (C.c_double * 23)()
+        self._L.rsrec_get_timing(self._h, out, 23)
         keys = ("total_ms", "hop_ms", "hop_launches", "atom_steps", "block_multiplies", "rest_ms", "host_ms", "hop_fuses_a", "hop_mfma_flop", "hop_required_flop",
                 "operator_arrays_from_device", "octet_launches", "rotate_ms", "gram_folded_launches", "map_accum_ms", "map_phase_ms", "map_final_ms",
-                "shot_accum_ms", "shot_final_ms", "kubo_left_chunks", "kubo_lchunk_planned")
+                "shot_accum_ms", "shot_final_ms", "kubo_left_chunks", "kubo_lchunk_planned", "site_accum_ms", "site_out_ms")
         return dict(zip(keys, list(out)))
 
     # -- state (restore_to_default, recursion.f90:3713-3825) --------------------------------------------
@@ -553,6 +603,60 @@ class Recursion:
         m_g = np.zeros((18, 18, 2 * lld + 2, ngroup, nchains), np.complex128, order="F") if download else None
         self._check(self._L.rsrec_chebyshev_lattice(self._h, nchains, nseed, _ptr(seeds), _ptr(coefs), lld, a, b, ngroup, _ptr(group), _ptr(m_g)))
         return m_g
+
+    def site_map(self, seeds, coefs, weights=None, energies=None, blocks=True, diag=True, norm=True):
+        """The 18 x 18 block of ne functions of H on EVERY atom from a few whole-lattice vectors (``rsrec_chebyshev_site_map``):
+        D(:, :, e, j) = sum_v conj(c^v_j) [sum_n w(n, e) T_{n-1}(H~) x^v]_j = cnorm_j f_e(H~)_jj + cross terms, with ``seeds`` and ``coefs``
+        (nvec, nseed) as ``chebyshev_lattice`` takes them.  The cross terms average out over random-phase vectors and vanish for probing
+        vectors whose atoms are further apart than the degree 2 lld + 1 (``probing_seeds``).  Give either ``weights`` complex
+        (2 lld + 2, ne), row n for order n - 1, ne <= 16 -- any function of H, e.g. ``chebyshev_fermi_weights`` -- or ``energies``, shorthand
+        for ``chebyshev_green_weights``.  Returns ``(d_full, d_diag, cnorm)``: complex (18, 18, ne, kk), complex (18, ne, kk) -- bit for bit
+        the diagonal of d_full -- and real (kk) = sum_v |c^v_j|^2 of the coefficients placed; each None when ``blocks``, ``diag`` or
+        ``norm`` is False.  Nothing is normalised (divide by cnorm) and nothing stays resident.  The bits depend on the order of the
+        vectors and on the options sitemap_vtile, sitemap_orders and kubo_vbatch: the accumulators are shared by all vectors."""
+        if (energies is None) == (weights is None):
+            raise ValueError("give either energies or weights")
+        lld = self.control.lld
+        a, b = chebyshev_scaling(self.en.energy_min, self.en.energy_max)
+        w = self.chebyshev_green_weights(energies) if weights is None else _fc(weights, np.complex128)
+        if w.ndim != 2 or w.shape[0] != 2 * lld + 2:
+            raise ValueError("weights must be (2 lld + 2, ne) = (%d, ne), got %r" % (2 * lld + 2, w.shape))
+        if not (blocks or diag):
+            raise ValueError("nothing asked for: blocks and diag are both False")
+        seeds = np.ascontiguousarray(seeds, dtype=np.int32)
+        coefs = np.ascontiguousarray(coefs, dtype=np.complex128)
+        if seeds.ndim != 2 or coefs.shape != seeds.shape:
+            raise ValueError("seeds and coefs must both be (nvec, nseed), got %r and %r" % (seeds.shape, coefs.shape))
+        nvec, nseed = seeds.shape
+        ne, kk = w.shape[1], self.lattice.kk
+        d_full = np.zeros((18, 18, ne, kk), np.complex128, order="F") if blocks else None
+        d_diag = np.zeros((18, ne, kk), np.complex128, order="F") if diag else None
+        cnorm = np.zeros(kk, np.float64) if norm else None
+        self._check(self._L.rsrec_chebyshev_site_map(self._h, nvec, nseed, _ptr(seeds), _ptr(coefs), lld, a, b, ne, _ptr(w), _ptr(d_full), _ptr(d_diag),
+                                                     _ptr(cnorm)))
+        return d_full, d_diag, cnorm
+
+    @staticmethod
+    def _site_norm(cnorm):
+        """What the front ends divide by: cnorm, and 1 on an atom no vector seeds (its block is an exact zero and stays one)."""
+        return np.where(cnorm > 0, cnorm, 1.0)
+
+    def site_ldos(self, seeds, coefs, energies):
+        """The orbital-resolved LDOS of every atom at a few energies from the vectors of ``site_map``: -Im d_diag / pi / cnorm with the
+        Green weights of ``energies``, real (18, ne, kk) -- the map an STM-like image of an impurity cell or a slab surface is cut from.
+        Exact for one-atom and for far-apart probing seeds, a stochastic estimate for random-phase ones.  An atom seeded by no vector
+        gives zeros."""
+        _, d_diag, cnorm = self.site_map(seeds, coefs, energies=energies, blocks=False)
+        return -d_diag.imag / np.pi / self._site_norm(cnorm)[None, None, :]
+
+    def site_occupations(self, seeds, coefs, fermi, kT, powers=(0,)):
+        """The occupation matrix of every atom, and with further ``powers`` its energy moments: d_full / cnorm of ``site_map`` on the columns
+        of ``chebyshev_fermi_weights(fermi, kT, lld, energy_min, energy_max, powers)``, complex (18, 18, len(powers), kk); column q
+        estimates [H^q f(H)]_jj.  The trace of column 0 is the atom's charge, the spin blocks give its moment.  An atom seeded by no
+        vector gives zeros."""
+        w = chebyshev_fermi_weights(fermi, kT, self.control.lld, self.en.energy_min, self.en.energy_max, powers)
+        d_full, _, cnorm = self.site_map(seeds, coefs, weights=w, diag=False)
+        return d_full / self._site_norm(cnorm)[None, None, None, :]
 
     def bloch_average(self, kpts, cr, group=None, download=True):
         """The source average of ``chebyshev_bloch``, one chain per k-point instead of kk: plane-wave seeds c_j = exp(+i k.r_j) / sqrt(kk) on
