@@ -470,6 +470,21 @@ module rsrec_binding
          integer(c_int) :: rc
       end function
 
+      !> wave-packet propagation: nt * stride steps of the Chebyshev table w complex (korder), host, from psi(0) = r, chi(0) = 0 with
+      !> D = d_op / do_op (18,18,nslots,ntype), applied as v_b / vo_b are; a record after every stride steps: ret complex (18,18,nt,nvec),
+      !> m0_full (18,18,mom,nvec), m0_diag (18,mom,nvec), m_full (18,18,mom,nt,nvec), m_diag (18,mom,nt,nvec), host or device memory, each
+      !> may be c_null_ptr (mom = 0: ret only).  Nothing is normalised, nothing stays resident.  The reference has no counterpart: there
+      !> is no drop-in switch.
+      function rsrec_chebyshev_evolve(handle, nvec, nseed, seed_atoms, seed_coef, a, b, d_op, do_op, korder, w, nt, stride, mom, &
+                                      ret, m0_full, m0_diag, m_full, m_diag) bind(C, name='rsrec_chebyshev_evolve') result(rc)
+         import :: c_int, c_ptr, c_double
+         type(c_ptr), value :: handle
+         integer(c_int), value :: nvec, nseed, korder, nt, stride, mom
+         real(c_double), value :: a, b
+         type(c_ptr), value :: seed_atoms, seed_coef, d_op, do_op, w, ret, m0_full, m0_diag, m_full, m_diag
+         integer(c_int) :: rc
+      end function
+
       function rsrec_scalar_lanczos(handle, nsites, seed_atoms, lld, llmax, a, b2) bind(C, name='rsrec_scalar_lanczos') result(rc)
          import :: c_int, c_ptr
          type(c_ptr), value :: handle

@@ -563,6 +563,54 @@ int rsrec_kubo_single_shot(rsrec_t *h, int nout, int nvec, int nseed, const int3
                            const double *v_b, const double *vo_b, int ne, const double *wl, const double *wr,
                            double *s_full, double *s_diag);
 
+/* Wave-packet propagation: the energy-resolved spreading of a random state in time (kernels_evolve.hpp), the time-dependent route to
+ * sigma(E) of large disordered cells (Roche-Mayou; LSQT).  With w the Chebyshev coefficients of exp(-i H tau) in H~ = (H - b)/a, one step is
+ *   psi' = sum_n w(n) p_n,   p_n = T_n(H~) psi,
+ *   chi' = sum_n w(n) g_n,   g_0 = chi,  g_1 = H~ g_0 + (1/a) D p_0,  g_{n+1} = 2 H~ g_n - g_{n-1} + (2/a) D p_n,      n = 0 .. korder - 1,
+ * which gives psi' = U(tau) psi and chi' = [X, U(tau)] psi + U(tau) chi exactly when D = [X, H]; for any other D, chi' is the Frechet
+ * derivative of exp(-i H tau) in direction D on psi, plus U(tau) chi.  Steps compose: from psi(0) = r (the placed seed) and chi(0) = 0,
+ * chi(t) = [X, U(t)] r, and no position operator ever touches the periodic cell.  nt * stride steps are taken and a record is taken
+ * after every `stride` of them, at t_s = s stride tau, s = 1 .. nt:
+ *   ret(:,:,s,v)  = r^H psi(t_s) = sum_j conj(c_j) [psi(t_s)]_j                        (the seed projection of rsrec_chebyshev_lattice)
+ *   m(:,:,n,s,v)  = chi(t_s)^H T_{n-1}(H~) chi(t_s),  n = 1 .. mom                     (a plain three-term chain from chi(t_s): mom - 1 products)
+ *   m0(:,:,n,v)   = r^H T_{n-1}(H~) r                                                  (the same stage on r: the DOS moments DX^2 is divided by)
+ *   seeds, a, b : exactly as rsrec_kubo_moments takes them.
+ *   d_op, do_op : complex (18,18,nslots,ntype), applied exactly as the Kubo calls apply v_b / vo_b (bulk atoms only, unscaled); do_op is
+ *             given with hoh only.  Not interpreted (Recursion.position_commutator of the Python front end builds [X, H]).
+ *   w       : complex (korder), host memory: the step's coefficients of orders 0 .. korder - 1 with the phase exp(-i b tau) in them
+ *             (evolution_weights of the Python front end).  Not interpreted.  2 <= korder <= RSREC_EVOLVE_KORDER_MAX.
+ *   nt, stride, mom : 1 <= nt <= RSREC_EVOLVE_NT_MAX, 1 <= stride <= RSREC_EVOLVE_STRIDE_MAX, 0 <= mom <= RSREC_EVOLVE_MOM_MAX.
+ *   ret     : complex (18,18,nt,nvec);  m0_full (18,18,mom,nvec), m0_diag (18,mom,nvec);  m_full (18,18,mom,nt,nvec), m_diag (18,mom,nt,nvec),
+ *             the diag forms bit for bit the diagonals of the full ones.  Each host or device memory (detected) or NULL; at least one is
+ *             given; with mom = 0 the four moment outputs must be NULL and only ret is formed.  A stage nobody asks for is not run.
+ * Nothing is normalised and nothing stays resident; resident diagonal moments of an earlier Kubo call are dropped, as any Kubo call drops
+ * them.  Per vector the p and the g recurrence advance as two chains of the same launches, one operator product D p_n is made per order,
+ * and one pass per order adds the source term into g_{n+1}; the two sums ride in that pass (option "evolve_orders" = 1) or are added
+ * from a ring every P orders (2 .. 16) -- the same bits either way.  Up to 4 vectors are in flight (option kubo_vbatch); the buffers are the
+ * handle's Kubo buffers, planned before anything is reserved: per vector in flight 5 + 2 R work vectors (R = 3 fused, P + 2 batched: 41 by default; 4
+ * more with hoh), whose ring also serves the moment stage.  RSREC_ERR_DEVICE with the bytes needed if one vector at a time does not fit.
+ * Both kernel sets (option kernels: the Grams on the matrix cores or on plain FMAs), hoh and per-atom operator blocks are served.
+ * Determinism: no atomics, every sum in a fixed order.  The bits of a vector's outputs depend on that vector, the operators, w, stride and
+ * the records before them only -- not on nt, the other vectors, their order or kubo_vbatch, evolve_orders, which outputs are asked for,
+ * host or device destination, or what earlier calls left in the buffers.
+ * Errors: RSREC_ERR_ARG with a message that names the function, the handle staying usable, for korder, nt, stride or mom out of range, a
+ * NULL w or d_op, a non-finite weight, hoh without do_op, every output NULL, a moment output with mom = 0, and every seed error of
+ * rsrec_kubo_moments_diag.  nvec = 0 returns RSREC_OK.  RSREC_ERR_DIVERGED if any element of ret is not finite or exceeds
+ * 1000 max(1, sum_j |c_j|^2) in magnitude (tested on the host behind the last record); the outputs are then left alone.
+ * rsrec_get_timing: out[0] device ms, out[1] / out[2] ms in and number of the H|psi> and D launches, the moment stage's included; out[5]
+ * everything else = out[23] ms in the step passes (source add and accumulation) + out[24] ms in the record stage (the seed projection and
+ * the moment stage with its Grams; its H products are counted by out[1] as well).  The events behind these figures are folded into the
+ * sums and reused whenever more than 8192 are pending behind a step or a record (one stream synchronisation each time), so a run of
+ * thousands of steps holds a bounded number of them. */
+#define RSREC_EVOLVE_KORDER_MAX 4096
+#define RSREC_EVOLVE_NT_MAX 1024
+#define RSREC_EVOLVE_STRIDE_MAX 65536
+#define RSREC_EVOLVE_MOM_MAX 65536
+int rsrec_chebyshev_evolve(rsrec_t *h, int nvec, int nseed, const int32_t *seed_atoms, const double *seed_coef,
+                           double a, double b, const double *d_op, const double *do_op,
+                           int korder, const double *w, int nt, int stride, int mom,
+                           double *ret, double *m0_full, double *m0_diag, double *m_full, double *m_diag);
+
 /* The Kubo-Bastin conductivity integrand of calculate_gamma_nm + calculate_conductivity_tensor (conductivity.f90:158-268), without the
  * (nen, cond_ll, cond_ll) array gamma_nm (the sum factorises into two tables of nen x cond_ll, kernels_cond.hpp):
  *   integrand(l, i, v) = factor sum_{n,m} gamma_nm(i, n, m) mu_nm(l, l, n, m, v),   factor = 16 / (pi (energy_max - energy_min)^2)
@@ -849,7 +897,10 @@ int rsrec_comm_destroy(rsrec_t *h);
  *   "sitemap_vtile" rsrec_chebyshev_site_map: vectors VT folded into z per pass, 1, 2, 4 or 8; a tile-pass moves (VT PT + 2 ne) 16 B per element.  VT PT <= 16:
  *                the value the caller did not set follows the other to VT PT = 16 (VT <= 8), of two set values VT gives way.  The bits depend on VT [0 = 8.  <8,2> is the fastest call of
  *                <1,16>, <2,8>, <4,4>, <8,2>, or within 0.02 % of it, in 7 of 9 measured configurations on 10 648 and 97 336 atoms, all four within 1.2 % of each other, and
- *                keeps the shallowest ring, DESIGN.md section 5] */
+ *                keeps the shallowest ring, DESIGN.md section 5]
+ *   "evolve_orders" rsrec_chebyshev_evolve: 1 = the two sums ride in the per-order pass that adds the source term (fused); 2..16 = that pass adds the
+ *                source alone and a ring collects that many orders per accumulation pass (batched; larger values: 16); the same bits for every value
+ *                [0 = 16: the fastest step of 1, 4, 16 with 1 and 4 vectors on 10 648 and 97 336 atoms, 4.4-9.6 % below the fused one, DESIGN.md section 5] */
 int rsrec_set_option(rsrec_t *h, const char *key, long value);
 /* Timing of the last recursion call, measured with HIP events on the engine's own stream:
  *   out[0] total device ms, out[1] ms in the H|psi> kernels, out[2] number of H|psi> launches,
@@ -870,6 +921,8 @@ int rsrec_set_option(rsrec_t *h, const char *key, long value);
  *   out[19..20] rsrec_kubo_moments and its _diag / _multi / _tensor forms: left chunks formed, summed over the vector batches of the call (one
  *           per batch when every left matrix fits), and the left vectors per chunk as planned (cond_ll then; option kubo_lchunk caps it).
  *   out[21..22] rsrec_chebyshev_site_map: ms in the accumulation passes and in the output stage (together: out[5]).
+ *   out[23..24] rsrec_chebyshev_evolve: ms in the step passes (source add and accumulation) and in the record stage (seed projection, moment
+ *           chains and their Grams); together: out[5].
  * After rsrec_block_green: out[0] = kernel + transfers, out[1] = the Green kernel alone. */
 int rsrec_get_timing(rsrec_t *h, double *out, int n);
 

@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("RSREC_LIB") or os.path.join(_HERE, "librsrec.so")
 ERR_ARG, ERR_DEVICE, ERR_DIVERGED, ERR_EIG = 1, 2, 3, 4
 KUBO_SHOT_NE_MAX, KUBO_SHOT_LL_MAX = 16, 65536      # RSREC_KUBO_SHOT_NE_MAX, RSREC_KUBO_SHOT_LL_MAX of include/rsrec.h
 SITE_MAP_NE_MAX = 16                                # RSREC_SITE_MAP_NE_MAX
+EVOLVE_KORDER_MAX, EVOLVE_NT_MAX, EVOLVE_STRIDE_MAX, EVOLVE_MOM_MAX = 4096, 1024, 65536, 65536      # RSREC_EVOLVE_*_MAX
 
 _lib = None
 
@@ -80,6 +81,8 @@ _SIGNATURES = {
                                             C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rsrec_chebyshev_lattice": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p]),
     "rsrec_chebyshev_site_map": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int] + [C.c_void_p] * 4),
+    "rsrec_chebyshev_evolve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                         C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5),
     "rsrec_scalar_lanczos":(C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "rsrec_site_partition": (None, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rsrec_last_error": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t]),

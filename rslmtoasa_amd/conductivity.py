@@ -201,6 +201,38 @@ class Conductivity:
         from .recursion import kubo_greenwood_weights
         return self._single_shot(kubo_greenwood_weights, 16, False, v_a, v_b, energies, cond_ll, vo_a, vo_b, seeds, coefs, atlist)
 
+    def spreading(self, evo, energies, energy_min, energy_max, tau, stride, jackson=True):
+        """The energy-resolved mean-square spreading of the wave packets of ``Recursion.evolve`` (the Roche-Mayou route to sigma(E)):
+        DX^2(E, t_s) = Tr[delta(E - H) (X(t_s) - X)^2] / Tr delta(E - H), estimated on the call's vectors as
+        sum_n d_n(E) M_n(s) / sum_n d_n(E) M0_n with M_n(s) = Re sum_{l,v} m_diag(l, n, s, v), M0_n = Re sum_{l,v} m0_diag(l, n, v)
+        and d_n(E) = g_n (2 - delta_n1) T_{n-1}(x) / (pi a sqrt(1 - x^2)), x = (E - b) / a: the expansion of delta(E - H) in the mom
+        moments of the call, with the Jackson kernel g_n of mom terms (math.f90:1641-1655) unless ``jackson=False``.
+        ``evo``: the dict ``Recursion.evolve`` returned with mom > 0; ``energy_min``, ``energy_max``: the window its a, b came from
+        (``chebyshev_scaling``); ``tau``, ``stride``: the step and the steps per record of that call, t_s = s stride tau.  Host numpy.
+        Returns a dict: ``t`` (nt), ``dos`` (nE) = sum_n d_n M0_n (the sum over the vectors, not their mean), ``dx2`` (nE, nt) and
+        ``diffusion`` (nE, nt) = DX^2 / t_s.  sigma(E) = e^2 rho(E) max_t D(E, t) with the caller's rho per volume; where the DOS
+        estimate is not positive the ratio is NaN."""
+        from .recursion import _chebyshev_t, _scaled_energies
+        if "m_diag" not in evo or "m0_diag" not in evo:
+            raise ValueError("spreading needs the m_diag and m0_diag of an evolve call with mom > 0")
+        md, m0 = np.asarray(evo["m_diag"]), np.asarray(evo["m0_diag"])
+        mom, nt = md.shape[1], md.shape[2]
+        x, a = _scaled_energies(energies, energy_min, energy_max, 1 << 30, "spreading", window=False)
+        n = np.arange(mom, dtype=np.float64)
+        if jackson:
+            th = np.pi * n / (mom + 1.0)
+            kern = ((mom - n + 1.0) * np.cos(th) + np.sin(th) / np.tan(np.pi / (mom + 1.0))) / (mom + 1.0)
+        else:
+            kern = np.ones(mom)
+        kern[1:] *= 2.0
+        d = kern[:, None] * _chebyshev_t(x, mom) / (np.pi * abs(a) * np.sqrt(1.0 - x ** 2))[None, :]         # (mom, nE)
+        num = d.T @ md.real.sum(axis=(0, 3))                                                                 # (nE, nt)
+        dos = d.T @ m0.real.sum(axis=(0, 2))                                                                 # (nE)
+        t = np.arange(1, nt + 1, dtype=np.float64) * float(stride) * float(tau)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            dx2 = np.where(dos[:, None] > 0, num / dos[:, None], np.nan)
+        return {"t": t, "dos": dos, "dx2": dx2, "diffusion": dx2 / t[None, :]}
+
     def timing(self):
         """(device ms of the last call, ms in its kernels): after ``integrand`` the contraction kernels; after ``tensor`` the series and
         integral kernels, which are all of that call's device work, so the two values are equal; after ``optical`` the table kernels and

@@ -54,6 +54,7 @@
 #include "kernels_lattice.hpp"
 #include "kernels_shot.hpp"
 #include "kernels_sitemap.hpp"
+#include "kernels_evolve.hpp"
 
 using namespace rsrec;
 
@@ -153,6 +154,7 @@ struct rsrec_handle {
     DevBuf d_bloch_geo, d_bloch_tab;    // rsrec_chebyshev_bloch: positions and k-points of the call; lists, segment offsets and level counts of a batch
     DevBuf d_map_w;                     // rsrec_chebyshev_bloch_map: the weights w(n, e) of the call
     DevBuf d_shot_w;                    // rsrec_kubo_single_shot: the weights of the call, [conj(wl) | wr][e][order]
+    DevBuf d_evo_w;                     // rsrec_chebyshev_evolve: the step's weights w(order) of the call
     DevBuf d_site_w, d_site_coef;       // rsrec_chebyshev_site_map: the weights w(n, e) of the call; the conjugated coefficient tables of a batch, (kk) per vector
     DevBuf d_lat_tab, d_lat_w, d_lat_part;   // rsrec_chebyshev_lattice: lists and offsets of a batch; weights and divergence bounds; split partials
     // options
@@ -171,6 +173,7 @@ struct rsrec_handle {
     long opt_blochmap_orders = 2;  // rsrec_chebyshev_bloch_map: orders added to the accumulators per pass (1 | 2: same bits, see kernels_blochmap.hpp)
     long opt_blochmap_kchunk = 0;  // rsrec_chebyshev_bloch_map: k-points per chunk of the final sums (0: 256, one launch's rows of the phase matrix); tests force it small
     long opt_shot_orders = 0;    // rsrec_kubo_single_shot: orders added to the accumulators per pass (1..16; 0: SHOT_ORDERS_DEFAULT = 16; the same bits for every value)
+    long opt_evolve_orders = 0;  // rsrec_chebyshev_evolve: 1 the accumulations ride in the per-order pass (fused), 2..16 a ring collects that many orders per accumulation pass (batched); 0: EVO_ORDERS_DEFAULT; the same bits for every value
     long opt_sitemap_orders = 0, opt_sitemap_vtile = 0;   // rsrec_chebyshev_site_map: orders PT added per pass (1..16) and vectors VT folded per pass (1..8), VT PT <= 16; 0: SITE_*_DEFAULT
     long opt_kubo_setgroup = 0;  // rsrec_kubo_moments_diag_tensor: sets of a vector contracted against one staged left tile (k_kubo_gram_diag_sets): 0 default (2), 1 every set by itself (k_kubo_gram_diag), 2 / 3 groups of at most that width
     int n_kubo_left_chunks = 0, kubo_lchunk_planned = 0;   // of the last Kubo moment call: left chunks formed over all its batches; left vectors per chunk as kubo_plan decided
@@ -195,6 +198,7 @@ struct rsrec_handle {
     // timing of last call
     double t_total_ms = 0, t_hop_ms = 0, t_rest_ms = 0, t_host_ms = 0;
     double t_rot_ms = 0;      // local-axis recursion: ms in k_rotate_coef (part of t_rest_ms)
+    double t_evo_ms[2] = {0, 0};      // rsrec_chebyshev_evolve: ms in the step passes, in the record stage (their sum: t_rest_ms)
     double t_site_ms[2] = {0, 0};     // rsrec_chebyshev_site_map: ms in the accumulation passes, in the output stage (their sum: t_rest_ms)
     double t_shot_ms[2] = {0, 0};     // rsrec_kubo_single_shot: ms in the accumulation passes, in the final stage (their sum: t_rest_ms)
     double t_map_ms[3] = {0, 0, 0};   // rsrec_chebyshev_bloch_map: ms in the accumulation passes, the phase tables, the final sums (their sum: t_rest_ms)
@@ -254,6 +258,7 @@ const OptionEntry OPTIONS[] = {
     {"kubo_setgroup", &rsrec_handle::opt_kubo_setgroup},
     {"shot_orders", &rsrec_handle::opt_shot_orders},
     {"sitemap_orders", &rsrec_handle::opt_sitemap_orders},
+    {"evolve_orders", &rsrec_handle::opt_evolve_orders},
     {"sitemap_vtile", &rsrec_handle::opt_sitemap_vtile},
     {"lattice_vbatch", &rsrec_handle::opt_lattice_vbatch},
     {"blochmap_orders", &rsrec_handle::opt_blochmap_orders},
@@ -425,9 +430,9 @@ extern "C" int rsrec_set_option(rsrec_t* h, const char* key, long value) {
 
 extern "C" int rsrec_get_timing(rsrec_t* h, double* out, int n) {
     if (!h || !out) return RSREC_ERR_ARG;
-    const double v[23] = {h->t_total_ms, h->t_hop_ms, h->n_hop_launch, h->n_atom_steps, h->n_block_mult, h->t_rest_ms, h->t_host_ms, (double)h->hop_fuses_a, h->n_hop_mfma_flop,
-                          h->n_req_flop, (double)h->n_asm_reused, (double)h->n_octet_launch, h->t_rot_ms, h->n_gram_folded, h->t_map_ms[0], h->t_map_ms[1], h->t_map_ms[2], h->t_shot_ms[0], h->t_shot_ms[1], (double)h->n_kubo_left_chunks, (double)h->kubo_lchunk_planned, h->t_site_ms[0], h->t_site_ms[1]};
-    for (int i = 0; i < n && i < 23; ++i) out[i] = v[i];
+    const double v[25] = {h->t_total_ms, h->t_hop_ms, h->n_hop_launch, h->n_atom_steps, h->n_block_mult, h->t_rest_ms, h->t_host_ms, (double)h->hop_fuses_a, h->n_hop_mfma_flop,
+                          h->n_req_flop, (double)h->n_asm_reused, (double)h->n_octet_launch, h->t_rot_ms, h->n_gram_folded, h->t_map_ms[0], h->t_map_ms[1], h->t_map_ms[2], h->t_shot_ms[0], h->t_shot_ms[1], (double)h->n_kubo_left_chunks, (double)h->kubo_lchunk_planned, h->t_site_ms[0], h->t_site_ms[1], h->t_evo_ms[0], h->t_evo_ms[1]};
+    for (int i = 0; i < n && i < 25; ++i) out[i] = v[i];
     return RSREC_OK;
 }
 
@@ -790,6 +795,7 @@ void reset_timing(rsrec_t* h) {
     h->t_map_ms[0] = h->t_map_ms[1] = h->t_map_ms[2] = 0;
     h->t_shot_ms[0] = h->t_shot_ms[1] = 0;
     h->t_site_ms[0] = h->t_site_ms[1] = 0;
+    h->t_evo_ms[0] = h->t_evo_ms[1] = 0;
     h->n_kubo_left_chunks = h->kubo_lchunk_planned = 0;
     h->n_hop_launch = h->n_atom_steps = h->n_block_mult = h->n_hop_mfma_flop = h->n_req_flop = 0;
     h->n_octet_launch = 0;
@@ -5037,6 +5043,327 @@ extern "C" int rsrec_chebyshev_site_map(rsrec_t* h, int nvec, int nseed, const i
     if (nvec == 0) return RSREC_OK;
     const SiteCall A{nvec, lld, ne, KuboSeeds{nseed, seed_atoms, seed_coef}, a, b, w, d_full, d_diag, cnorm};
     return run_site_map(h, who, A);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Wave-packet propagation (kernels_evolve.hpp): psi(t) = U(t) r and chi(t) = [X, U(t)] r step by step, on the whole-lattice products of
+// the Kubo calls; per record the projection of psi on the seed (kernels_lattice.hpp) and the Chebyshev moments of chi (kernels_shot.hpp's Grams)
+namespace {
+
+constexpr size_t EVO_EVENTS_MAX = 8192;      // pending timing events of a call before they are folded into the sums (run_evolve)
+constexpr int EVO_ORDERS_DEFAULT = 16;       // what evolve_orders = 0 means: batched, the fastest of 1, 4, 16 in every measured configuration
+
+struct EvoCall {
+    int nvec;
+    KuboSeeds S;
+    double a, b;
+    int korder;
+    const double* w;
+    int nt, stride, mom;
+    double *ret, *m0_full, *m0_diag, *m_full, *m_diag;
+};
+
+// The device memory of a call, decided before anything is reserved (as shot_plan does).  Per vector in flight, with its p and its g chain:
+// two state slots (psi | chi now, and the sums that become the next ones), the ring of R order slots, D p_n, and with hoh the chains' h psi
+// and the two temporaries of the operator product.  The moment stage needs nothing of its own: the step ring is idle then and holds
+// 2 R orders of the moment chains (they are nb chains wide, the step's slots 2 nb).
+struct EvoPlan {
+    bool fused = false;
+    int P = 0, R = 0, Rm = 0, Pm = 0, nbv = 0;   // orders per accumulation pass, step-ring slots; moment-ring slots and orders per Gram flush; vectors in flight
+    int ksteps_total = 0, ksplit = 0;
+    size_t velems = 0, slot = 0, mslot = 0, pmax = 0;   // doubles of a vector, of a step slot (2 nbv chains), of a moment slot (nbv chains); projection partials per chain
+    size_t bytes_work = 0, bytes_part = 0, bytes_out = 0;
+    size_t off[6] = {0, 0, 0, 0, 0, 0};                  // complex elements: ret, m0_full, m0_diag, m_full, m_diag, end
+    double *state[2] = {nullptr, nullptr}, *ring = nullptr, *dp = nullptr, *hps = nullptr, *p1 = nullptr, *p2 = nullptr;
+    double2 *part = nullptr, *out = nullptr;
+    double* step_slot(const double* x0, int n) const { return n == 0 ? const_cast<double*>(x0) : ring + (size_t)((n - 1) % R) * slot; }
+    double* mom_slot(const double* l0, int n) const { return n == 0 ? const_cast<double*>(l0) : ring + (size_t)((n - 1) % Rm) * mslot; }
+};
+
+int evo_plan(rsrec_t* h, const char* who, const EvoCall& A, EvoPlan& P) {
+    const int kk = h->kk;
+    const bool hoh = h->hoh != 0;
+    const long po = h->opt_evolve_orders <= 0 ? EVO_ORDERS_DEFAULT : std::min<long>(h->opt_evolve_orders, EVO_ORDERS_MAX);
+    P.fused = po == 1; P.P = (int)po; P.R = P.fused ? 3 : P.P + 2;
+    P.Rm = 2 * P.R; P.Pm = P.Rm - 2;
+    P.velems = (size_t)(kk + 1) * BLD;
+    P.ksteps_total = (int)((NB * (size_t)kk + 3) / 4);
+    P.ksplit = shot_ksplit(P.ksteps_total);
+    P.pmax = (size_t)kk / LATTICE_SPLIT_ATOMS + 2;
+    P.bytes_part = (size_t)P.Pm * P.ksplit * BLK * 16;
+    const size_t nv = (size_t)A.nvec, mo = (size_t)A.mom;
+    const size_t n_out[5] = {(size_t)BLK * A.nt * nv, A.m0_full ? BLK * mo * nv : 0, A.m0_diag ? NB * mo * nv : 0, A.m_full ? BLK * mo * A.nt * nv : 0,
+                             A.m_diag ? NB * mo * A.nt * nv : 0};
+    for (int q = 0; q < 5; ++q) P.off[q + 1] = P.off[q] + n_out[q];
+    P.bytes_out = P.off[5] * 16;
+    size_t free_b = 0, total_b = 0;
+    HIPCK(h, hipMemGetInfo(&free_b, &total_b));
+    size_t reusable = h->d_lat_tab.bytes + h->d_lat_w.bytes + h->d_lat_part.bytes;
+    for (int v = 0; v < 6; ++v) reusable += h->d_vec[v].bytes;
+    for (auto& kb : h->d_kubo) reusable += kb.bytes;
+    const double budget = 0.9 * (double)(free_b + reusable);
+    auto vectors_for = [&](int nbv) { return (size_t)nbv * (4 + 2 * P.R + 1 + (hoh ? 4 : 0)); };
+    auto need_for = [&](int nbv) {
+        return (double)vectors_for(nbv) * P.velems * 8 + (double)nbv * ((double)P.pmax * BLK * 16 + (double)kk * 20 + 64) + (double)P.bytes_part + (double)P.bytes_out;
+    };
+    int nbv = (int)std::min<long>({(long)A.nvec, h->opt_kubo_vbatch > 0 ? h->opt_kubo_vbatch : KUBO_CHAINS_MAX, (long)(KUBO_CHAINS_MAX / 2)});
+    while (nbv > 1 && need_for(nbv) > budget) --nbv;
+    if (need_for(nbv) > budget)
+        return fail(h, RSREC_ERR_DEVICE, "%s: %.0f bytes needed for one vector at a time on %d atoms (evolve_orders=%d, mom=%d, nt=%d), %.0f bytes free", who, need_for(1), kk,
+                    P.P, A.mom, A.nt, (double)free_b);
+    P.nbv = nbv; P.slot = (size_t)2 * nbv * P.velems; P.mslot = (size_t)nbv * P.velems; P.bytes_work = vectors_for(nbv) * P.velems * 8;
+    return RSREC_OK;
+}
+
+// The plan's buffers out of the handle's Kubo buffers: d_kubo[0] the work vectors, [3] the Grams' slice partials, [4] the outputs of the whole
+// call.  Everything is cleared: block kk of every vector stays the zero block, and nothing an earlier call left is ever read.
+int evo_reserve(rsrec_t* h, const char* who, EvoPlan& P) {
+    const size_t want[5] = {P.bytes_work, 0, 0, P.bytes_part, P.bytes_out};
+    for (int v = 0; v < 6; ++v) h->d_vec[v].release();
+    h->d_kubo[1].release(); h->d_kubo[2].release();
+    XFER(reserve_kubo_buffers(h, want, who));
+    double* at = h->d_kubo[0].as<double>();
+    auto take = [&](size_t nv) { double* p = at; at += nv * P.velems; return p; };
+    P.state[0] = take(2 * P.nbv); P.state[1] = take(2 * P.nbv);
+    P.ring = take((size_t)2 * P.R * P.nbv);
+    P.dp = take(P.nbv);
+    if (h->hoh) { P.hps = take(2 * P.nbv); P.p1 = take(P.nbv); P.p2 = take(P.nbv); }
+    P.part = h->d_kubo[3].as<double2>();
+    P.out = h->d_kubo[4].as<double2>();
+    HIPCK(h, hipMemsetAsync(h->d_kubo[0].p, 0, P.bytes_work, h->stream));
+    HIPCK(h, hipMemsetAsync(h->d_kubo[4].p, 0, P.bytes_out, h->stream));
+    return RSREC_OK;
+}
+
+// accumulation pass of the batched form (and of order 0 in the fused one): orders n0 .. n0 + cnt - 1 of the step into the sums y
+void evo_accumulate(rsrec_t* h, const EvoPlan& P, int nb, const double* x0, int n0, int cnt, double* y) {
+    const size_t total = (size_t)h->kk * BLK, vs = P.velems / 2;
+    EvoOrders X;
+    for (int p = 0; p < EVO_ORDERS_MAX; ++p) X.x[p] = reinterpret_cast<const double2*>(P.step_slot(x0, n0 + (p < cnt ? p : 0)));
+    const double2* w = h->d_evo_w.as<double2>() + n0;
+    auto go = [&](auto kern, int per_wg) {
+        const dim3 grid((unsigned)((total + per_wg - 1) / per_wg), (unsigned)(2 * nb));
+        kern<<<grid, EVO_THREADS, 0, h->stream>>>(X, cnt, vs, total, w, reinterpret_cast<double2*>(y));
+    };
+    if (cnt <= 1) go(k_evo_accum<1, 4>, EVO_THREADS * 4);
+    else if (cnt <= 2) go(k_evo_accum<2, 4>, EVO_THREADS * 4);
+    else if (cnt <= 4) go(k_evo_accum<4, 4>, EVO_THREADS * 4);
+    else if (cnt <= 8) go(k_evo_accum<8, 2>, EVO_THREADS * 2);
+    else go(k_evo_accum<16, 1>, EVO_THREADS);
+}
+
+// One step: the sums of the korder orders started from the state x0 = [psi | chi] into y (cleared here).  korder - 1 launches advance
+// both chains of every vector, one operator product per order forms D p_n, and the per-order pass adds it into g(n + 1).
+int evo_step(WholeLatticeCall& W, const EvoPlan& P, const EvoCall& A, int nb, const double* x0, double* y, std::vector<std::pair<hipEvent_t, hipEvent_t>>& pass_ev) {
+    rsrec_t* h = W.h;
+    const size_t total = (size_t)h->kk * BLK, vs = P.velems / 2;
+    const double2* w = h->d_evo_w.as<double2>();
+    const unsigned wgs = (unsigned)((total + EVO_THREADS * EVO_SOURCE_U - 1) / (EVO_THREADS * EVO_SOURCE_U));
+    HIPCK(h, hipMemsetAsync(y, 0, P.slot * 8, h->stream));
+    for (int n = 0, n0 = 0; n < A.korder; ++n) {
+        hipEvent_t e0 = nullptr;
+        if (n >= 1) {
+            const double* cur = P.step_slot(x0, n - 1);
+            double* nxt = P.step_slot(x0, n);
+            whole_lattice_batch(W, 2 * nb, false);
+            whole_lattice_apply_h(W, cur, nxt, cheb_epilogue(n == 1, cur, n >= 2 ? P.step_slot(x0, n - 2) : nullptr, A.a, A.b));
+            whole_lattice_batch(W, nb, false);
+            whole_lattice_apply_v(W, h->kubo_op_b[0], cur, P.dp);                        // D p_{n-1}: the p chains are the slot's first nb
+            e0 = next_event(h);
+            const double f = (n == 1 ? 1.0 : 2.0) / A.a;
+            if (P.fused)
+                k_evo_source<true><<<dim3(wgs, 2 * nb), EVO_THREADS, 0, h->stream>>>(reinterpret_cast<double2*>(nxt), reinterpret_cast<const double2*>(P.dp), f, vs, total, nb, 0,
+                                                                                      w + n, reinterpret_cast<double2*>(y));
+            else
+                k_evo_source<false><<<dim3(wgs, nb), EVO_THREADS, 0, h->stream>>>(reinterpret_cast<double2*>(nxt), reinterpret_cast<const double2*>(P.dp), f, vs, total, nb, nb,
+                                                                                   w + n, reinterpret_cast<double2*>(y));
+        } else e0 = next_event(h);
+        if (P.fused) { if (n == 0) evo_accumulate(h, P, nb, x0, 0, 1, y); }
+        else if (n - n0 + 1 == P.P || n == A.korder - 1) { evo_accumulate(h, P, nb, x0, n0, n - n0 + 1, y); n0 = n + 1; }
+        pass_ev.emplace_back(e0, next_event(h));
+    }
+    return RSREC_OK;
+}
+
+// The moment stage of nb chains that start at l0 (chi of the batch's vectors, or r for m0): m(:, :, n, iv, j0 + c) = L^H T_{n-1}(H~) L for
+// n = 1 .. mom by a plain three-term chain, mom - 1 launches for all nb chains together; the orders collect in the idle step ring and every
+// Pm of them one Gram launch per vector (two where the ring wraps) forms their blocks.  full / diag: (.., mom, nrec, nvec) images, either may be null.
+void evo_moments(WholeLatticeCall& W, const EvoPlan& P, const EvoCall& A, int nb, const double* l0, int iv, int nrec, int j0, double2* full, double2* diag) {
+    rsrec_t* h = W.h;
+    const bool mfma = h->opt_kernels != 1;
+    auto grams = [&](const double* w0, size_t ws, int q, int cnt) {          // orders q .. q + cnt - 1 lie at w0 + e ws
+        for (int c = 0; c < nb; ++c) {
+            const double* L = l0 + (size_t)c * P.velems;
+            const double* Wc = w0 + (size_t)c * P.velems;
+            const dim3 grid((unsigned)P.ksplit, (unsigned)cnt);
+            if (mfma) k_shot_gram<<<grid, 64, 0, h->stream>>>(L, 0, Wc, ws, P.ksteps_total, P.ksplit, P.part);
+            else k_shot_gram_valu<<<grid, SHOT_GRAM_VALU_THREADS, 0, h->stream>>>(L, 0, Wc, ws, P.ksteps_total, P.ksplit, P.part);
+            k_shot_gram_reduce<<<cnt, SHOT_GRAM_VALU_THREADS, 0, h->stream>>>(P.part, P.ksplit, A.mom, iv, nrec, j0 + c, full ? full + (size_t)q * BLK : nullptr,
+                                                                             diag ? diag + (size_t)q * NB : nullptr);
+        }
+    };
+    whole_lattice_batch(W, nb, false);
+    grams(l0, 0, 0, 1);
+    for (int n = 1, n0 = 1; n < A.mom; ++n) {
+        const double* cur = P.mom_slot(l0, n - 1);
+        whole_lattice_apply_h(W, cur, P.mom_slot(l0, n), cheb_epilogue(n == 1, cur, n >= 2 ? P.mom_slot(l0, n - 2) : nullptr, A.a, A.b));
+        if (n - n0 + 1 < P.Pm && n != A.mom - 1) continue;
+        for (int q = n0; q <= n;) {
+            const int s = (q - 1) % P.Rm, cnt = std::min(n - q + 1, P.Rm - s);
+            grams(P.ring + (size_t)s * P.mslot, P.mslot, q, cnt);
+            q += cnt;
+        }
+        n0 = n + 1;
+    }
+}
+
+// rsrec_chebyshev_evolve behind its argument checks.  Per batch of nb vectors: chains 0 .. nb - 1 carry psi, chains nb .. 2 nb - 1 chi; the
+// two state slots swap roles after every step.  SpMM launches of a batch: nt stride (korder - 1) (1 + 1) for the steps, (1 + nrec) (mom - 1)
+// for the moment stages (nrec = nt if m_* is asked for, the 1 if m0_* is); with hoh every H product is two launches and every D product three.
+int run_evolve(rsrec_t* h, const char* who, const EvoCall& A) {
+    const int kk = h->kk, nvec = A.nvec;
+    h->kubo_diag_nvec = h->kubo_diag_ll = 0;                       // (d_kubo[4] is about to be overwritten)
+    release_kubo_buffers(h, false, true);
+    EvoPlan P;
+    XFER(evo_plan(h, who, A, P));
+    XFER(evo_reserve(h, who, P));
+    HIPCK(h, h->d_seed.reserve((size_t)A.S.nseed * 4));
+    HIPCK(h, h->d_seedcoef.reserve((size_t)A.S.nseed * sizeof(double2)));
+    HIPCK(h, h->d_evo_w.reserve((size_t)A.korder * sizeof(double2)));
+    XFER(xfer_h2d(h, h->d_evo_w.p, A.w, (size_t)A.korder * sizeof(double2)));
+    const size_t n_list = (size_t)P.nbv * kk, n_off = (size_t)P.nbv * 2;
+    HIPCK(h, h->d_lat_tab.reserve((n_list + 2 * n_off) * sizeof(int)));
+    HIPCK(h, h->d_lat_w.reserve(n_list * sizeof(double2)));
+    HIPCK(h, h->d_lat_part.reserve((size_t)P.nbv * P.pmax * BLK * sizeof(double2)));
+    int *d_list = h->d_lat_tab.as<int>(), *d_seg = d_list + n_list, *d_split = d_seg + n_off;
+    double2* d_w = h->d_lat_w.as<double2>();
+    double2* partial = h->d_lat_part.as<double2>();
+    double2 *ret = P.out + P.off[0], *m0f = A.m0_full ? P.out + P.off[1] : nullptr, *m0d = A.m0_diag ? P.out + P.off[2] : nullptr;
+    double2 *mf = A.m_full ? P.out + P.off[3] : nullptr, *md = A.m_diag ? P.out + P.off[4] : nullptr;
+    WholeLatticeCall W;
+    XFER(whole_lattice_begin(h, W, 2 * P.nbv, true));
+    W.hps = P.hps; W.p1 = P.p1; W.p2 = P.p2;
+    W.ev_begin = next_event(h);
+    const LatticeCall LC{nvec, 0, 1, A.S, nullptr, A.a, A.b, nullptr};
+    LatticeBatchLists T;
+    std::vector<double> bound(nvec, 0.0);
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> pass_ev, rec_ev;
+    // The events of a long run are folded into the sums and given back to the pool whenever more than EVO_EVENTS_MAX are pending (checked
+    // behind every step and every record, never inside a timed span): a call of thousands of steps holds a bounded number of events --
+    // about EVO_EVENTS_MAX plus those of one step or one moment stage -- at the price of one stream synchronisation per fold.
+    const size_t ev_base = h->ev_used;
+    double hop_ms = 0.0, hop_launches = 0.0;
+    auto fold_events = [&](bool force) {
+        if (!force && h->ev_used - ev_base <= EVO_EVENTS_MAX) return (int)RSREC_OK;
+        HIPCK(h, hipStreamSynchronize(h->stream));
+        for (auto& pr : W.hop_ev) hop_ms += ev_ms(pr.first, pr.second);
+        for (auto& pr : pass_ev) h->t_evo_ms[0] += ev_ms(pr.first, pr.second);
+        for (auto& pr : rec_ev) h->t_evo_ms[1] += ev_ms(pr.first, pr.second);
+        hop_launches += (double)W.hop_ev.size();
+        W.hop_ev.clear(); pass_ev.clear(); rec_ev.clear();
+        h->ev_used = ev_base;
+        return (int)RSREC_OK;
+    };
+    auto run_batches = [&]() {
+    for (int iv0 = 0; iv0 < nvec; iv0 += P.nbv) {
+        const int nb = std::min(P.nbv, nvec - iv0);
+        lattice_lists(h, LC, iv0, nb, T);
+        if ((size_t)T.pstride > P.pmax) return fail(h, RSREC_ERR_DEVICE, "%s: split partials outside the planned buffer", who);
+        std::copy(T.bound.begin(), T.bound.end(), bound.begin() + iv0);
+        XFER(xfer_h2d(h, d_list, T.list.data(), (size_t)nb * kk * sizeof(int)));
+        XFER(xfer_h2d(h, d_seg, T.seg_off.data(), (size_t)nb * 2 * sizeof(int)));
+        XFER(xfer_h2d(h, d_split, T.split_off.data(), (size_t)nb * 2 * sizeof(int)));
+        XFER(xfer_h2d(h, d_w, T.weight.data(), (size_t)nb * kk * sizeof(double2)));
+        const LatticeLists LL{d_list, d_w, d_seg, d_split, kk, 1, T.pstride};
+        int cur = 0;
+        HIPCK(h, hipMemsetAsync(P.state[0], 0, P.slot * 8, h->stream));                  // psi(0) = r into the p chains, chi(0) = 0
+        XFER(seed_whole_vectors<LayoutCI>(h, who, A.S, iv0, nb, P.state[0], P.velems));
+        if (m0f || m0d) {
+            hipEvent_t e0 = next_event(h);
+            evo_moments(W, P, A, nb, P.state[0], 0, 1, iv0, m0f, m0d);
+            rec_ev.emplace_back(e0, next_event(h));
+        }
+        for (int s = 0; s < A.nt; ++s) {
+            for (int k = 0; k < A.stride; ++k) {
+                XFER(evo_step(W, P, A, nb, P.state[cur], P.state[1 - cur], pass_ev));
+                cur = 1 - cur;
+                XFER(fold_events(false));
+            }
+            HIPCK(h, hipGetLastError());
+            hipEvent_t e0 = next_event(h);
+            k_lattice_project<<<dim3(T.pstride, nb), LATTICE_THREADS, 0, h->stream>>>(LL, P.state[cur], P.velems, partial);
+            k_lattice_reduce<LayoutCI><<<dim3(1, nb, LATTICE_RWG), 64, 0, h->stream>>>(LL, partial, iv0, s, A.nt, ret);
+            if (mf || md) evo_moments(W, P, A, nb, P.state[cur] + (size_t)nb * P.velems, s, A.nt, iv0, mf, md);
+            rec_ev.emplace_back(e0, next_event(h));
+            XFER(fold_events(false));
+        }
+        HIPCK(h, hipGetLastError());
+    }
+    return (int)RSREC_OK;
+    };
+    // a failure in the middle of the batches leaves with nothing queued on the stream
+    if (const int rc_run = run_batches()) { (void)hipStreamSynchronize(h->stream); (void)hipGetLastError(); return rc_run; }
+    // the divergence test on ret before anything is written: a diverged call returns the error and leaves the outputs alone
+    std::vector<double> hret(2 * (P.off[1] - P.off[0]));
+    XFER(xfer_d2h(h, hret.data(), ret, hret.size() * 8));
+    XFER(fold_events(true));
+    XFER(whole_lattice_end(h, W, true));                           // (every launch span is folded: total_ms from the call's first event)
+    h->t_hop_ms = hop_ms; h->n_hop_launch = hop_launches;
+    h->t_rest_ms = h->t_evo_ms[0] + h->t_evo_ms[1];
+    const size_t per_vec = (size_t)BLK * A.nt;
+    for (int v = 0; v < nvec; ++v)
+        for (size_t q = 0; q < per_vec; ++q) {
+            const double re = hret[2 * (v * per_vec + q)], im = hret[2 * (v * per_vec + q) + 1];
+            if (!(std::hypot(re, im) <= bound[v]))
+                return fail(h, RSREC_ERR_DIVERGED, "%s: the projection of vector %d on its seed left 1000 max(1, sum |c|^2) at record %zu. Check the weights and a, b", who, v + 1,
+                            q / BLK + 1);
+        }
+    auto deliver = [&](double* dst, const double2* src, size_t n) {
+        if (!dst) return (int)RSREC_OK;
+        if (is_device_ptr(dst)) { HIPCK(h, hipMemcpyAsync(dst, src, n * 16, hipMemcpyDeviceToDevice, h->stream)); return (int)RSREC_OK; }
+        return xfer_d2h(h, dst, src, n * 16);
+    };
+    if (A.ret && !is_device_ptr(A.ret)) std::copy(hret.begin(), hret.end(), A.ret);
+    else XFER(deliver(A.ret, ret, P.off[1] - P.off[0]));
+    XFER(deliver(A.m0_full, m0f, P.off[2] - P.off[1]));
+    XFER(deliver(A.m0_diag, m0d, P.off[3] - P.off[2]));
+    XFER(deliver(A.m_full, mf, P.off[4] - P.off[3]));
+    XFER(deliver(A.m_diag, md, P.off[5] - P.off[4]));
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    return RSREC_OK;
+}
+
+}  // namespace
+
+extern "C" int rsrec_chebyshev_evolve(rsrec_t* h, int nvec, int nseed, const int32_t* seed_atoms, const double* seed_coef, double a, double b, const double* d_op,
+                                      const double* do_op, int korder, const double* w, int nt, int stride, int mom, double* ret, double* m0_full, double* m0_diag,
+                                      double* m_full, double* m_diag) {
+    if (!h) return RSREC_ERR_ARG;
+    const char* fn = "rsrec_chebyshev_evolve";
+    XFER(check_ready(h, fn));
+    if (korder < 2 || korder > RSREC_EVOLVE_KORDER_MAX) return fail(h, RSREC_ERR_ARG, "%s: korder=%d is not in 2..%d", fn, korder, RSREC_EVOLVE_KORDER_MAX);
+    if (nt < 1 || nt > RSREC_EVOLVE_NT_MAX) return fail(h, RSREC_ERR_ARG, "%s: nt=%d is not in 1..%d", fn, nt, RSREC_EVOLVE_NT_MAX);
+    if (stride < 1 || stride > RSREC_EVOLVE_STRIDE_MAX) return fail(h, RSREC_ERR_ARG, "%s: stride=%d is not in 1..%d", fn, stride, RSREC_EVOLVE_STRIDE_MAX);
+    if (mom < 0 || mom > RSREC_EVOLVE_MOM_MAX) return fail(h, RSREC_ERR_ARG, "%s: mom=%d is not in 0..%d", fn, mom, RSREC_EVOLVE_MOM_MAX);
+    if (!w || !d_op) return fail(h, RSREC_ERR_ARG, "%s: w and d_op must be given", fn);
+    if (!ret && !m0_full && !m0_diag && !m_full && !m_diag) return fail(h, RSREC_ERR_ARG, "%s: every output is NULL", fn);
+    if (mom == 0 && (m0_full || m0_diag || m_full || m_diag)) return fail(h, RSREC_ERR_ARG, "%s: mom=0 forms ret only: the moment outputs must be NULL", fn);
+    if (nvec < 0 || nseed < 1 || a == 0.0 || (nvec > 0 && (!seed_atoms || !seed_coef))) return fail(h, RSREC_ERR_ARG, "%s: bad argument", fn);
+    if (h->hoh && !do_op) return fail(h, RSREC_ERR_ARG, "%s: hoh requires do_op", fn);
+    if (!h->s5_built) return fail(h, RSREC_ERR_ARG, "%s: lattice has too many neighbour slots for the SpMM kernel", fn);
+    for (size_t q = 0; q < 2 * (size_t)korder; ++q)
+        if (!std::isfinite(w[q])) return fail(h, RSREC_ERR_ARG, "%s: weight %zu is not finite", fn, q / 2 + 1);
+    XFER(check_seeds(h, fn, seed_atoms, (size_t)nvec * nseed, 0));
+    for (int c = 0; c < nvec; ++c)
+        if (std::all_of(seed_atoms + (size_t)c * nseed, seed_atoms + (size_t)(c + 1) * nseed, [](int32_t s) { return s == 0; }))
+            return fail(h, RSREC_ERR_ARG, "%s: vector %d has no seed", fn, c + 1);
+    HIPCK(h, hipSetDevice(h->device));
+    reset_timing(h);
+    if (nvec == 0) return RSREC_OK;
+    XFER(build_kubo_operator(h, h->kubo_op_b[0], d_op, do_op));
+    if (h->hoh && h->nmax > 0) XFER(build_kubo_hbulk(h));
+    const EvoCall A{nvec, KuboSeeds{nseed, seed_atoms, seed_coef}, a, b, korder, w, nt, stride, mom, ret, m0_full, m0_diag, m_full, m_diag};
+    return run_evolve(h, fn, A);
 }
 
 extern "C" int rsrec_scalar_lanczos(rsrec_t* h, int nsites, const int32_t* seed_atoms, int lld, int llmax, double* a, double* b2) {

@@ -223,6 +223,92 @@ def kubo_greenwood_weights(energies, cond_ll, energy_min, energy_max):
     return d, d.copy(order="F")
 
 
+def evolution_weights(tau, korder, a, b):
+    """The weights of one time step of ``Recursion.evolve``: complex (korder), w_n = the Chebyshev coefficient of order n of
+    exp(-i a tau x) times exp(-i b tau), so that sum_n w_n T_n(H~) = exp(-i H tau) with H~ = (H - b) / a, up to the neglected orders
+    (``evolution_order``).  A cosine transform at N >= 4 korder Chebyshev nodes x_k = cos(pi (k + 1/2) / N):
+    c_n = (2 - delta_n0) / N sum_k exp(-i a tau x_k) cos(n pi (k + 1/2) / N), which equals (2 - delta_n0) (-i)^n J_n(a tau) up to
+    the aliased orders 2 N - n and beyond (N also exceeds 2 |a tau| + 64, so those are far below rounding).  The angle
+    n (2 k + 1) pi / (2 N) is reduced in integers before the cosine is taken.  numpy only."""
+    korder = int(korder)
+    if korder < 1:
+        raise ValueError("evolution_weights: korder must be at least 1")
+    z = float(a) * float(tau)
+    if not np.isfinite(z) or not np.isfinite(float(b) * float(tau)):
+        raise ValueError("evolution_weights: a tau and b tau must be finite")
+    nn = max(4 * korder, 2 * int(np.ceil(abs(z))) + 64)
+    k = np.arange(nn, dtype=np.int64)
+    # the samples: the phase a tau x_k is tens of radians, so it is formed in numpy's widest real type before it is rounded
+    wide = np.longdouble
+    phase = wide(a) * wide(tau) * np.cos((2 * k.astype(wide) + 1) * _pi_wide() / (2 * wide(nn)))
+    f = np.cos(phase).astype(np.float64) - 1j * np.sin(phase).astype(np.float64)
+    c = np.empty(korder, np.complex128)
+    for n0 in range(0, korder, 256):                                      # (rows in chunks: the cosine table of 4096 orders is half a GB)
+        n = np.arange(n0, min(korder, n0 + 256), dtype=np.int64)
+        cosines = np.cos(np.pi * ((n[:, None] * (2 * k + 1)[None, :]) % (4 * nn)) / (2.0 * nn))
+        c[n0:n0 + n.size] = (2.0 / nn) * (cosines @ f)
+    c[0] *= 0.5
+    return c * np.exp(-1j * float(b) * float(tau))
+
+
+def _pi_wide():
+    """pi in numpy's widest real type (4 atan 1 there; the double where there is none wider)"""
+    return 4 * np.arctan(np.longdouble(1))
+
+
+def evolution_order(tau, a, tol=1e-14):
+    """The smallest korder for ``evolution_weights(tau, korder, a, b)`` whose first neglected coefficient, and every one behind it,
+    is below ``tol`` in magnitude: the coefficients 2 |J_n(a tau)| fall faster than geometrically once n exceeds |a tau|, about
+    |a tau| + 40 at 1e-14 for |a tau| of a few tens."""
+    z = abs(float(a) * float(tau))
+    length = int(np.ceil(z)) + 32
+    while True:
+        mag = np.abs(evolution_weights(tau, length, a, 0.0))
+        over = np.nonzero(mag >= tol)[0]
+        if over.size == 0:
+            return 2
+        if over[-1] + 1 < length:
+            return max(2, int(over[-1]) + 1)
+        length *= 2
+
+
+def position_commutator(ee, slot_vec, direction, alat=1.0, eeo_factor=None):
+    """The operator D = [X, H] of ``Recursion.evolve`` for the position along ``direction`` (3; normalised here), in the (type, slot)
+    form of the velocity operators: d_op(:, :, m, t) = ((r_i - r_j) . dir) alat ee(:, :, m, t) for neighbour slot m of an atom i of
+    type t, zero in the on-site slot -- i times the reference's v_a (build_realspace_velocity_operators, hamiltonian.f90:1343-1348).
+    ``ee`` (18, 18, nslots, ntype); ``slot_vec`` (nslots, 3) or (nslots, 3, ntype), fewer rows for a stencil with unused slots: r_j - r_i of slot m in units of
+    alat (row 0, the atom itself, is ignored), as ``lattice.bcc_supercell`` takes it.  Only differences of positions enter, so a
+    periodic cell needs no position operator.  Returns ``d_op``, or with ``eeo_factor`` ``(d_op, do_op)`` for hoh: do_op(:, :, m, t) =
+    d_op(:, :, m, t) @ eeo_factor(:, :, m, t), the reference's product with obarm of the neighbour's type (:1356-1358);
+    ``eeo_factor`` is (18, 18, nslots, ntype), or one (18, 18) matrix for every slot and type."""
+    ee = np.asarray(ee, np.complex128)
+    if ee.ndim != 4 or ee.shape[:2] != (18, 18):
+        raise ValueError("ee must be (18, 18, nslots, ntype), got %s" % (ee.shape,))
+    nslots, ntype = ee.shape[2:]
+    sv = np.asarray(slot_vec, np.float64)
+    if sv.ndim == 2:
+        sv = np.repeat(sv[:, :, None], ntype, axis=2)
+    if sv.ndim == 3 and sv.shape[0] < nslots:                             # (slots the stencil does not use: zero blocks)
+        sv = np.concatenate([sv, np.zeros((nslots - sv.shape[0],) + sv.shape[1:])], axis=0)
+    if sv.shape != (nslots, 3, ntype):
+        raise ValueError("slot_vec must be (%d, 3) or (%d, 3, %d), got %s" % (nslots, nslots, ntype, np.shape(slot_vec)))
+    d = np.asarray(direction, np.float64).ravel()
+    if d.size != 3 or not np.linalg.norm(d) > 0:
+        raise ValueError("direction must be a non-zero 3-vector")
+    d = d / np.linalg.norm(d)
+    dot = -np.einsum("x,mxt->mt", d, sv) * float(alat)                    # (r_i - r_j) . dir
+    dot[0] = 0.0
+    d_op = np.asfortranarray(ee * dot[None, None])
+    if eeo_factor is None:
+        return d_op
+    ob = np.asarray(eeo_factor, np.complex128)
+    if ob.shape == (18, 18):
+        ob = np.broadcast_to(ob[:, :, None, None], ee.shape)
+    if ob.shape != ee.shape:
+        raise ValueError("eeo_factor must be (18, 18) or %s, got %s" % (ee.shape, np.shape(eeo_factor)))
+    return d_op, np.asfortranarray(np.einsum("abmt,bcmt->acmt", d_op, ob))
+
+
 def _fc(a, dtype):
     return np.asfortranarray(np.asarray(a, dtype=dtype))
 
@@ -270,11 +356,12 @@ class Recursion:
 
 
     def timing(self):
-        out = (C.c_double * 23)()
-        self._L.rsrec_get_timing(self._h, out, 23)
+        out = (C.c_double * 25)()
+        self._L.rsrec_get_timing(self._h, out, 25)
         keys = ("total_ms", "hop_ms", "hop_launches", "atom_steps", "block_multiplies", "rest_ms", "host_ms", "hop_fuses_a", "hop_mfma_flop", "hop_required_flop",
                 "operator_arrays_from_device", "octet_launches", "rotate_ms", "gram_folded_launches", "map_accum_ms", "map_phase_ms", "map_final_ms",
-                "shot_accum_ms", "shot_final_ms", "kubo_left_chunks", "kubo_lchunk_planned", "site_accum_ms", "site_out_ms")
+                "shot_accum_ms", "shot_final_ms", "kubo_left_chunks", "kubo_lchunk_planned", "site_accum_ms", "site_out_ms",
+                "evolve_pass_ms", "evolve_record_ms")
         return dict(zip(keys, list(out)))
 
     # -- state (restore_to_default, recursion.f90:3713-3825) --------------------------------------------
@@ -823,6 +910,41 @@ class Recursion:
         if nvec > 0:                                   # (a call without vectors returns before the handle drops anything)
             self.mu_diag_resident = None
         return (s_diag, s_full) if blocks else s_diag
+
+    def evolve(self, d_op, w, nt, stride=1, mom=0, do_op=None, seeds=None, coefs=None, atlist=None, blocks=False):
+        """Wave-packet propagation (``rsrec_chebyshev_evolve``): psi(t) = U(t) r and chi(t) = [X, U(t)] r from psi(0) = r, chi(0) = 0 in
+        nt * stride steps of the Chebyshev table ``w`` (``evolution_weights(tau, korder, a, b)`` with a, b of ``chebyshev_scaling``; complex
+        (korder), not interpreted), with D = ``d_op`` (``do_op`` too with hoh; ``position_commutator``).  A record after every ``stride``
+        steps, s = 1 .. nt.  Vectors as ``compute_moments_stochastic`` takes them: ``atlist``, or ``seeds`` and ``coefs`` (nvec, nseed).
+        Returns a dict, Fortran order: ``ret`` complex (18, 18, nt, nvec) = r^H psi(t_s); with ``mom`` > 0 also ``m_diag`` (18, mom, nt,
+        nvec), the orbital diagonals of chi(t_s)^H T_{n-1}(H~) chi(t_s), and ``m0_diag`` (18, mom, nvec), the same of r (the DOS moments);
+        with ``blocks=True`` also ``m_full`` (18, 18, mom, nt, nvec) and ``m0_full``, whose diagonals the diag forms are bit for bit.
+        Nothing is normalised and nothing stays resident (resident diagonal moments of an earlier call are dropped).
+        ``Conductivity.spreading`` turns the dict into DX^2(E, t), D(E, t) and the DOS."""
+        d_op = _fc(d_op, np.complex128)
+        do_op = None if do_op is None else _fc(do_op, np.complex128)
+        w = np.ascontiguousarray(w, dtype=np.complex128).ravel()
+        a, b = chebyshev_scaling(self.en.energy_min, self.en.energy_max)
+        if seeds is None:
+            seeds = np.asarray(atlist, dtype=np.int32).reshape(-1, 1)
+            coefs = np.ones(seeds.shape, np.complex128)
+        seeds = np.ascontiguousarray(seeds, dtype=np.int32)
+        coefs = np.ascontiguousarray(coefs, dtype=np.complex128)
+        nvec, nseed = seeds.shape
+        nt, stride, mom = int(nt), int(stride), int(mom)
+
+        def out(*shape):
+            return np.zeros(shape, np.complex128, order="F")
+        res = {"ret": out(18, 18, max(nt, 0), nvec)}
+        if mom > 0:
+            res["m0_diag"], res["m_diag"] = out(18, mom, nvec), out(18, mom, max(nt, 0), nvec)
+            if blocks:
+                res["m0_full"], res["m_full"] = out(18, 18, mom, nvec), out(18, 18, mom, max(nt, 0), nvec)
+        self._check(self._L.rsrec_chebyshev_evolve(self._h, nvec, nseed, _ptr(seeds), _ptr(coefs), a, b, _ptr(d_op), _ptr(do_op), int(w.size), _ptr(w), nt, stride, mom,
+                                                   _ptr(res["ret"]), _ptr(res.get("m0_full")), _ptr(res.get("m0_diag")), _ptr(res.get("m_full")), _ptr(res.get("m_diag"))))
+        if nvec > 0:                                   # (a call without vectors returns before the handle drops anything)
+            self.mu_diag_resident = None
+        return res
 
     def ham_vec_matmul(self, psi_in, a, b):
         """psi_out = (H psi_in - b psi_in)/a on a whole vector psi(18,18,kk) with the PLAIN operator ee + l.s, whatever hoh says
